@@ -219,6 +219,27 @@ def roofline(eng, ex, dtype, iters=3):
             "all_kernels_ms_per_step_eager_events": total_ms}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as float32 `<out_dir>/<name>.npy`.  An array that would take the total past 64 MB is
+    cut to a fixed sample of whole images along the batch axis (seeded, so two builds dump the same images) and its
+    image indices go to `<name>_index.npy`."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES
+    for name, a in arrays.items():
+        a = a.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > budget:
+            per = a[0].nbytes
+            keep = max(1, min(a.shape[0], budget // per))
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[idx]
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+        budget -= a.nbytes
+
+
 def dry_run(args, rank, world):
     """The distributed skeleton of main() on CPU with gloo: barrier, stubbed step time, MAX over ranks, the final
     all-gather of the images, rank 0 prints the JSON line (marked "dry": true, not a measurement)."""
@@ -238,6 +259,8 @@ def dry_run(args, rank, world):
         dist.all_gather_into_tensor(out, x)
         x = out
     assert x.shape[0] == world * B and float(x[-1, 0, 0, 0]) == world - 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": x})
     ms = elapsed * 1e3 / K
     if rank == 0:
         print(json.dumps({"metric": "sampled images/sec (2000-step 128x128 SR3)", "dry": True,
@@ -265,7 +288,13 @@ def main():
     ap.add_argument("--dry", action="store_true",
                     help="launcher / collective rehearsal on CPU (gloo): no kernels run, the timing is a stub and "
                          "the JSON line says so; used by the CPU tests of the N > 1 path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the final images of every rank, float32) "
+                         "as DIR/<name>.npy; the inputs depend on the arguments only, so two builds compare output "
+                         "for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` without a launcher: start N fresh ranks ourselves, BEFORE anything touches the GPU
     from diffsplitting_amd import parallel
@@ -366,6 +395,8 @@ def main():
         x = out.to(dev)
     assert torch.isfinite(x).all(), "sampler produced non-finite pixels"
     assert eng.handoff_timeouts() == 0, "a bounded hand-off spin of k_conv_ws gave up: the timed pixels are wrong"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"images": x})    # the K-th step's state: what p_sample_loop returns
 
     ms_per_step = elapsed * 1e3 / K
     images_per_s = world * B / (ms_per_step * 1e-3 * SAMPLE_STEPS)

@@ -141,6 +141,23 @@ def test_bench_self_launches_n_ranks_dry():
     assert abs(line["value"] - 2 * 16 / (1.1e-3 * 2000)) < 1e-6       # whole-job aggregate
 
 
+def test_bench_dump_outputs_dry(tmp_path):
+    """--dump-outputs writes the gathered images of every rank as float32 .npy (here the --dry stub: rank r's images
+    are filled with r)."""
+    import subprocess
+    import sys
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0",
+                        "--batch", "4", "--dry", "--dump-outputs", str(out)], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    x = np.load(out / "images.npy")
+    assert x.dtype == np.float32 and x.shape == (8, 3, 8, 8)
+    assert (x[:4] == 0).all() and (x[4:] == 1).all()
+
+
 def test_bench_refuses_mismatched_world():
     import subprocess
     import sys
