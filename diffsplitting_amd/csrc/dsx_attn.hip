@@ -375,17 +375,16 @@ template <int ST, int NDB, int CS = 1> hipError_t launch_attn_one(const AttnArgs
   hipLaunchKernelGGL((k_attn<ST, NDB, CS>), dim3((unsigned)(a.B * QT * CS)), dim3(256), attn_lds_bytes<ST>(), st, a);
   return hipGetLastError();
 }
-template <int ST> hipError_t launch_attn_st(const AttnArgs& a, hipStream_t st) {
+template <int ST> hipError_t launch_attn_st(const AttnArgs& a, bool col_split, hipStream_t st) {
   const int ndb = (a.C + 127) / 128;
   switch (ndb) {
     case 1: return launch_attn_one<ST, 1>(a, st);
     case 2: return launch_attn_one<ST, 2>(a, st);
     case 3: case 4: {
       // few query tiles (the 16 x 16 maps at batch 16: 128 workgroups): two workgroups per tile, half of the output
-      // channels each (measured: 17.9 -> see DESIGN.md); DSX_ATTN_CS=1 keeps one
-      static const int cs_on = getenv("DSX_ATTN_CS") ? atoi(getenv("DSX_ATTN_CS")) : 2;
+      // channels each (measured: 17.9 -> see DESIGN.md); the planner may keep one
       const int QT = (a.L + BQ - 1) / BQ;
-      if (cs_on == 2 && a.B * QT <= 160) return launch_attn_one<ST, 4, 2>(a, st);
+      if (col_split && a.B * QT <= 160) return launch_attn_one<ST, 4, 2>(a, st);
       return launch_attn_one<ST, 4>(a, st);
     }
     case 5: case 6: case 7: case 8: return launch_attn_one<ST, 8>(a, st);
@@ -396,16 +395,16 @@ template <int ST> hipError_t launch_attn_st(const AttnArgs& a, hipStream_t st) {
 
 bool attn_supported(int C, int L) { return C >= 8 && C <= 1024 && (C & 7) == 0 && L >= 1 && (long long)L * 3 * C * 4 < (1LL << 31); }
 
-hipError_t launch_attn(const AttnArgs& a, hipStream_t st) {
+hipError_t launch_attn(const AttnArgs& a, bool col_split, hipStream_t st) {
   if (!attn_supported(a.C, a.L) || a.B < 1) return hipErrorInvalidValue;
   const int epu = a.storage == 0 ? 4 : 8;             // elements per 16-byte unit
   if ((a.ld % epu) || (a.ldo % 4) || ((uintptr_t)a.q & 15) || ((uintptr_t)a.k & 15) || ((uintptr_t)a.v & 15) ||
       ((uintptr_t)a.out & 15))
     return hipErrorInvalidValue;                      // 16-byte loads / 8- or 16-byte stores
   switch (a.storage) {
-    case 0: return launch_attn_st<0>(a, st);
-    case 1: return launch_attn_st<1>(a, st);
-    case 2: return launch_attn_st<2>(a, st);
+    case 0: return launch_attn_st<0>(a, col_split, st);
+    case 1: return launch_attn_st<1>(a, col_split, st);
+    case 2: return launch_attn_st<2>(a, col_split, st);
     default: return hipErrorInvalidValue;
   }
 }

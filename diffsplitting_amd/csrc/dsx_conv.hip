@@ -1768,8 +1768,7 @@ static size_t conv_img_lds(int dtype, int ks) {
   return (size_t)8 * 2 * pw * rb + (size_t)8 * 8 * 2 * KC * sizeof(float);
 }
 bool conv_img_applicable(int dtype, int ks, int stride, const ConvArgs& a, bool gn, int gn_groups) {
-  static const int on = getenv("DSX_IMG") ? atoi(getenv("DSX_IMG")) : 1;
-  if (!on || stride != 1 || a.up || !(ks == 1 || ks == 3)) return false;
+  if (stride != 1 || a.up || !(ks == 1 || ks == 3)) return false;
   if (a.Hs != 8 || a.Ws != 8 || a.Ho != 8 || a.Wo != 8) return false;
   const int KC = dtype != 0 ? 32 : 16, C = a.C0 + a.C1;
   if (a.C0 % (8 * KC) || a.C1 % (8 * KC) || C / (8 * KC) > 8 || C < 8 * KC) return false;
@@ -1963,9 +1962,8 @@ __global__ __launch_bounds__(256) void k_conv_first(const ConvArgs a) {
 }
 
 bool conv_first_applicable(int ks, int stride, const ConvArgs& a, bool gn) {
-  static const int on = getenv("DSX_FIRST") ? atoi(getenv("DSX_FIRST")) : 1;
   const int C = a.C0 + a.C1;
-  return on && ks == 3 && stride == 1 && !a.up && !gn && !a.swish && C >= 1 && C <= 7 && a.Cout >= 16 && a.Cout <= 64 &&
+  return ks == 3 && stride == 1 && !a.up && !gn && !a.swish && C >= 1 && C <= 7 && a.Cout >= 16 && a.Cout <= 64 &&
          (a.Cout & 15) == 0 && (a.Ho & 15) == 0 && (a.Wo & 15) == 0 && a.Ho == a.Hs && a.Wo == a.Ws && a.out_ld == a.Cout;
 }
 hipError_t launch_conv_first(int dtype, const ConvArgs& a, hipStream_t st) {

@@ -332,7 +332,9 @@ struct AttnArgs {
   float div, inv_div;     // sqrt(C) and its reciprocal
 };
 bool attn_supported(int C, int L);
-hipError_t launch_attn(const AttnArgs& a, hipStream_t st);
+// `col_split`: launches with few query tiles and 257..512 channels run two workgroups per tile, half of the output
+// channels each (the planner's choice, PlanKnobs::attn_cs)
+hipError_t launch_attn(const AttnArgs& a, bool col_split, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // layout, sampler update, RNG, tiling

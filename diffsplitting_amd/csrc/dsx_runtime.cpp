@@ -47,6 +47,116 @@ extern "C" int dsx_device_count(void) {
   return n;
 }
 
+// ------------------------------------------------------------------ planner knobs
+// Every tuning switch of the launch planner, read from the environment by read_plan_knobs()
+// once per plan: dsx_exec_create and dsx_plan_dry_run.  The defaults are the shipped plan.
+namespace {
+struct PlanKnobs {
+  bool conv_naive = false;   // DSX_CONV_IMPL=naive: the plain direct-conv kernel for every conv (cross-checks)
+  int first = 1;             // DSX_FIRST: the UNet's first conv (few input channels) on the im2col-in-K kernel
+  int img = 1;               // DSX_IMG: 8 x 8 maps on the image-resident kernel
+  // warp-specialised persistent kernel (k_conv_ws): only needs ~one workgroup per CU
+  int ws = 1;                // DSX_WS
+  int ws_1x1 = 1;            // DSX_WS_1X1: 1 x 1 convs on it too
+  int ws_min_grid = 224;     // DSX_WS_MIN_GRID: work items it needs (the parity tests lower it to force it onto small grids)
+  // Two 64-byte chunks per (tile, group) item where the geometry allows it: under the 16 x 16 MFMA shape the loaders,
+  // not the MFMAs, bound an item (their VALU stream gets 8 of every 16 issue cycles), and their per-item costs (DMA
+  // issue, wait, fetch, barrier: ~1.3 k of 3.2 k cycles per 32 channels on the 64-pixel tile) are paid once per 64
+  // channels this way.  Measured (same-box A/B): the 512-channel 16 x 16 layers -8 .. -11 %, a 256 -> 512 layer
+  // with only 4 two-chunk groups +7 % (hence the 12-chunk minimum there); the 128 x 128 tile -2.6 % over its 22 launches.
+  int ws_g2 = 1;             // DSX_WS_G2: several chunks per item for the 3 x 3 convs
+  int ws_g2_min64 = 12;      // DSX_WS_G2_MIN64: chunks (64-pixel tile); fewer -> one-chunk groups
+  int ws_g2_min128 = 4;      // DSX_WS_G2_MIN128: chunks (128-pixel tiles)
+  int ws_g4_min64 = 16;      // DSX_WS_G4_MIN64: four chunks per item (64-pixel tile) from this many chunks
+  int ws_c4 = 1;             // DSX_WS_C4: 1 x 1 convs, four chunks (128 input channels) per item
+  int ws_c4_min = 8;         // DSX_WS_C4_MIN: chunks: at least two groups
+  // 1 x 1 convs with several N tiles: an XCD takes every N tile of its M tiles (ws_map 3).  With the N tiles dealt over
+  // the XCDs (the 3 x 3 choice: there the weights are the larger operand) every L2 fetched most of the input: 65.7 MB
+  // per launch of the 512 -> 1536 qkv conv against 18.4 MB algorithmic (PMC, profiles/r03_pmc_summary.txt).
+  int ws_map3 = 1;           // DSX_WS_MAP3
+  int xcd_bands = 1;         // DSX_XCD_BANDS: contiguous tile bands per XCD instead of round-robin tiles
+  int host_fin = 1;          // DSX_HOST_FIN: residual 1 x 1 convs host the finalize of their block's second GroupNorm
+  int prefetch = 1;          // DSX_PREFETCH: L2 weight prefetch (l2_prefetch in dsx_kernels.h)
+  int prefetch_ws = 1;       // DSX_PREFETCH_WS: ... also carried by the previous k_conv_ws launch
+  int fuse_stats = 1;        // DSX_FUSE_STATS: GroupNorm statistics in the conv (or split-K reduce) epilogue
+  // Narrow outputs (<= 32 channels: the UNet's final conv, 64 -> 3 at full resolution): HBM-bound layers that the
+  // generic 128 x 32 tile walked as two 32-channel groups with a barrier pair each and a 16 x 8 pixel halo.  The
+  // two-chunk variant stages ALL input channels of a 16 x 16 (or 16 x 8) pixel patch once -- one load phase, one
+  // conversion, one barrier, 36 MFMA steps per row block -- with three workgroups per CU overlapping their phases.
+  int narrow_g2 = 1;         // DSX_NARROW_G2
+  int min_grid = 512;        // DSX_MIN_GRID: workgroups a k_conv_mfma launch needs before split-K is considered
+  int splitk = 1;            // DSX_SPLITK
+  int attn_cs = 2;           // DSX_ATTN_CS: 2 = two attention workgroups per query tile on few-tile launches, 1 = one
+  int stamp_op = -1;         // DSX_STAMP_OP=<conv ordinal>[,<block>]: in-kernel phase stamps of that launch (-DDSX_STAMPS)
+  int stamp_block = 0;
+  int ablate = 0;            // DSX_ABLATE (-DDSX_DIAG builds only): timing experiments, results are wrong when non-zero
+  // tile preference lists (TILE_* indices, "0,2,3,4"): the first that fills the chip wins
+  std::vector<int> tiles_wide{TILE_128x128, TILE_64x128, TILE_64x64};              // DSX_TILES_WIDE
+  std::vector<int> tiles_narrow{TILE_64x64, TILE_128x64};                          // DSX_TILES_NARROW
+  std::vector<int> tiles_slim{TILE_128x32, TILE_64x64, TILE_128x64};               // DSX_TILES_SLIM: Cout <= 32
+  std::vector<int> tiles_wide_split{TILE_64x128, TILE_128x128, TILE_64x64};        // DSX_TILES_WIDE_SPLIT
+  std::vector<int> tiles_narrow_split{TILE_64x64, TILE_128x64};                    // DSX_TILES_NARROW_SPLIT
+  std::vector<int> tiles_narrow_g2{TILE_256x32, TILE_128x32};                      // DSX_TILES_NARROW_G2
+  // the 128 x 128 tile (2 x 2 waves of 64 pixels x 64 channels: each LDS pixel fragment feeds two MFMAs and each
+  // converted group twice the MFMA work of the 64 x 128 tile) wherever it still fills the chip
+  std::vector<int> tiles_ws_wide{TILE_128x128, TILE_64x128};                       // DSX_TILES_WS_WIDE
+  std::vector<int> tiles_ws_wide_1x1{TILE_128x128, TILE_64x128};                   // DSX_TILES_WS_WIDE_1X1
+  // 1 x 1 without GroupNorm / Swish in front (residual and attention-output convs): the loaders only copy, the kernel is
+  // bound by the weight stream, and only the one-N-block tiles have the deep weight ring (measured: 32^2 layers -2 us each)
+  std::vector<int> tiles_ws_wide_1x1_raw{TILE_64x128, TILE_128x128};               // DSX_TILES_WS_WIDE_1X1_RAW
+  std::vector<int> tiles_ws_narrow{TILE_256x64, TILE_128x64, TILE_64x64};          // DSX_TILES_WS_NARROW
+};
+}  // namespace
+
+// a tile preference list "0,2,3,4"; an empty string keeps `dflt`
+static std::vector<int> tile_order(const char* e, const std::vector<int>& dflt) {
+  if (!*e) return dflt;
+  std::vector<int> v;
+  for (const char* p = e; *p;) {
+    v.push_back(atoi(p));
+    while (*p && *p != ',') ++p;
+    if (*p == ',') ++p;
+  }
+  return v;
+}
+
+static PlanKnobs read_plan_knobs() {
+  PlanKnobs k;
+  static const struct { const char* name; int PlanKnobs::*field; } ints[] = {
+      {"DSX_FIRST", &PlanKnobs::first}, {"DSX_IMG", &PlanKnobs::img}, {"DSX_WS", &PlanKnobs::ws},
+      {"DSX_WS_1X1", &PlanKnobs::ws_1x1}, {"DSX_WS_MIN_GRID", &PlanKnobs::ws_min_grid}, {"DSX_WS_G2", &PlanKnobs::ws_g2},
+      {"DSX_WS_G2_MIN64", &PlanKnobs::ws_g2_min64}, {"DSX_WS_G2_MIN128", &PlanKnobs::ws_g2_min128},
+      {"DSX_WS_G4_MIN64", &PlanKnobs::ws_g4_min64}, {"DSX_WS_C4", &PlanKnobs::ws_c4},
+      {"DSX_WS_C4_MIN", &PlanKnobs::ws_c4_min}, {"DSX_WS_MAP3", &PlanKnobs::ws_map3},
+      {"DSX_XCD_BANDS", &PlanKnobs::xcd_bands}, {"DSX_HOST_FIN", &PlanKnobs::host_fin},
+      {"DSX_PREFETCH", &PlanKnobs::prefetch}, {"DSX_PREFETCH_WS", &PlanKnobs::prefetch_ws},
+      {"DSX_FUSE_STATS", &PlanKnobs::fuse_stats}, {"DSX_NARROW_G2", &PlanKnobs::narrow_g2},
+      {"DSX_MIN_GRID", &PlanKnobs::min_grid}, {"DSX_SPLITK", &PlanKnobs::splitk}, {"DSX_ATTN_CS", &PlanKnobs::attn_cs},
+#ifdef DSX_DIAG
+      {"DSX_ABLATE", &PlanKnobs::ablate},
+#endif
+  };
+  static const struct { const char* name; std::vector<int> PlanKnobs::*field; } lists[] = {
+      {"DSX_TILES_WIDE", &PlanKnobs::tiles_wide}, {"DSX_TILES_NARROW", &PlanKnobs::tiles_narrow},
+      {"DSX_TILES_SLIM", &PlanKnobs::tiles_slim}, {"DSX_TILES_WIDE_SPLIT", &PlanKnobs::tiles_wide_split},
+      {"DSX_TILES_NARROW_SPLIT", &PlanKnobs::tiles_narrow_split}, {"DSX_TILES_NARROW_G2", &PlanKnobs::tiles_narrow_g2},
+      {"DSX_TILES_WS_WIDE", &PlanKnobs::tiles_ws_wide}, {"DSX_TILES_WS_WIDE_1X1", &PlanKnobs::tiles_ws_wide_1x1},
+      {"DSX_TILES_WS_WIDE_1X1_RAW", &PlanKnobs::tiles_ws_wide_1x1_raw}, {"DSX_TILES_WS_NARROW", &PlanKnobs::tiles_ws_narrow},
+  };
+  for (const auto& e : ints)
+    if (const char* v = getenv(e.name)) k.*e.field = atoi(v);
+  for (const auto& e : lists)
+    if (const char* v = getenv(e.name)) k.*e.field = tile_order(v, k.*e.field);
+  const char* impl = getenv("DSX_CONV_IMPL");
+  k.conv_naive = impl && !strcmp(impl, "naive");
+  if (const char* se = getenv("DSX_STAMP_OP")) {
+    const char* comma = strchr(se, ',');
+    k.stamp_op = atoi(se);
+    k.stamp_block = comma ? atoi(comma + 1) : 0;
+  }
+  return k;
+}
+
 // ------------------------------------------------------------------ model
 namespace {
 
@@ -114,7 +224,7 @@ struct dsx_model {
   size_t arena_bytes = 0;
   float *d_freq = nullptr, *d_w1 = nullptr, *d_b1 = nullptr, *d_w2 = nullptr, *d_b2 = nullptr;
   float *d_wf = nullptr, *d_bf = nullptr;
-  bool want_naive = false;
+  bool want_naive = false;  // DSX_CONV_IMPL=naive at creation: the device image also holds the naive kernel's weights
 };
 
 static int add_param(dsx_model* m, const std::string& name, std::initializer_list<int64_t> shape) {
@@ -267,8 +377,7 @@ extern "C" int dsx_model_create(const dsx_unet_cfg* cfg, dsx_model** out) {
     md.conv = add_conv(m, "final_conv.block.3", pre, md.cout, 3, true);
     m->mods.push_back(md);
   }
-  const char* env = getenv("DSX_CONV_IMPL");
-  m->want_naive = env && !strcmp(env, "naive");
+  m->want_naive = read_plan_knobs().conv_naive;
   *out = m;
   return DSX_OK;
 }
@@ -613,6 +722,7 @@ struct OpInfo {            // what one launch of the plan computes (for profilin
 
 struct dsx_exec {
   dsx_model* m = nullptr;
+  PlanKnobs knobs;             // read when the plan is built
   int B = 0, H = 0, W = 0, cond_c = 0, x_c = 0;
   char* ws = nullptr;
   size_t ws_bytes = 0, ws_used = 0;
@@ -701,23 +811,8 @@ static int pow2_divisor(int v, int cap) {  // largest power of two dividing v, <
   return p;
 }
 
-// tile preference lists, overridable for tuning: DSX_TILES_WIDE / DSX_TILES_NARROW = "0,2,3,4"
-static std::vector<int> tile_order(const char* env, std::initializer_list<int> dflt) {
-  std::vector<int> v(dflt);
-  const char* e = getenv(env);
-  if (e && *e) {
-    v.clear();
-    for (const char* p = e; *p;) {
-      v.push_back(atoi(p));
-      while (*p && *p != ',') ++p;
-      if (*p == ',') ++p;
-    }
-  }
-  return v;
-}
-
 // geometry of `tile` for this conv (unsplit); false if the tile cannot be used
-static bool tile_geometry(int dtype, int tile, int ks, int stride, const ConvArgs& a, ConvArgs& c) {
+static bool tile_geometry(int dtype, int tile, int ks, int stride, int ablate, const ConvArgs& a, ConvArgs& c) {
   if (tile < 0 || tile >= TILE_COUNT) return false;
   if (stride == 2 && tile != TILE_64x64) return false;
   const ConvTileInfo ti = conv_tile_info(tile);
@@ -732,115 +827,67 @@ static bool tile_geometry(int dtype, int tile, int ks, int stride, const ConvArg
   c.n_tiles = (c.nblocks * 32 + ti.BN - 1) / ti.BN;
   c.ksplit = 1; c.groups_per_split = a.kchunks / conv_chunk_multiple(ks); c.slab_stride = 0;
   c.lds_row = conv_lds_row(ks, stride, c.tw_log2);
-#ifdef DSX_DIAG
-  c.ablate = getenv("DSX_ABLATE") ? atoi(getenv("DSX_ABLATE")) : 0;   // diagnostic build only
-#else
-  c.ablate = 0;
-#endif
+  c.ablate = ablate;
   return conv_lds_bytes(dtype, tile, ks, stride, c) != 0;
 }
 
+// geometry of `tile` on the two-chunk (cpg = 2) variant of k_conv_mfma: one image per M tile, one N tile, every two
+// 64-byte chunks one staged group; false if the tile cannot be used
+static bool g2_geometry(int tile, const ConvArgs& a, ConvArgs& g) {
+  const ConvTileInfo ti = conv_tile_info(tile);
+  const int TW = pow2_divisor(a.Wo, 16), TH = pow2_divisor(a.Ho, std::max(1, ti.BM / TW));
+  if (TW * TH != ti.BM) return false;
+  g = a;
+  g.cpg = 2;
+  g.tw_log2 = ilog2(TW); g.th_log2 = ilog2(TH); g.tb_log2 = 0;
+  g.tiles_x = a.Wo / TW; g.tiles_y = a.Ho / TH;
+  g.m_tiles = g.tiles_x * g.tiles_y * a.B;
+  g.n_tiles = 1;
+  g.ksplit = 1; g.groups_per_split = a.kchunks / 2; g.slab_stride = 0;
+  g.lds_row = conv_lds_row_g2(g.tw_log2);
+  g.ablate = 0;
+  return conv_g2_lds_bytes(tile, g) != 0;
+}
+
 // choose tile + geometry (+ split-K) for one conv; returns false if no MFMA config fits.
+// Pass 0: the warp-specialised persistent kernel: the widest tile (least re-staging of the activations per output
+//         channel) that still gives >= ws_min_grid work items.
 // Pass 1: the first tile of the preference list whose plain grid fills the chip.
 // Pass 2: small-M layers — the first tile of the split list, K split across workgroups
 //         (slabs + a reduce launch) until the grid fills the chip.
-static bool pick_conv(int dtype, int ks, int stride, ConvArgs& a, int& tile_out) {
-  static const std::vector<int> wide = tile_order("DSX_TILES_WIDE", {TILE_128x128, TILE_64x128, TILE_64x64});
-  static const std::vector<int> narrow = tile_order("DSX_TILES_NARROW", {TILE_64x64, TILE_128x64});
-  static const std::vector<int> slim = tile_order("DSX_TILES_SLIM", {TILE_128x32, TILE_64x64, TILE_128x64});   // Cout <= 32
-  static const std::vector<int> wide2 = tile_order("DSX_TILES_WIDE_SPLIT", {TILE_64x128, TILE_128x128, TILE_64x64});
-  static const std::vector<int> narrow2 = tile_order("DSX_TILES_NARROW_SPLIT", {TILE_64x64, TILE_128x64});
-  static const int min_grid = getenv("DSX_MIN_GRID") ? atoi(getenv("DSX_MIN_GRID")) : 512;
-  static const int splitk_on = getenv("DSX_SPLITK") ? atoi(getenv("DSX_SPLITK")) : 1;
+// Narrow outputs (<= 32 channels) go to the two-chunk variant of k_conv_mfma first (PlanKnobs::narrow_g2).
+static bool pick_conv(const PlanKnobs& k, int dtype, int ks, int stride, ConvArgs& a, int& tile_out) {
   const bool is_wide = a.Cout > 64;
   const int kgroups = a.kchunks / conv_chunk_multiple(ks);
   ConvArgs c;
-  // Pass 0: the warp-specialised persistent kernel only needs ~one workgroup per CU: take the widest
-  // tile (least re-staging of the activations per output channel) that still gives >= ws_min work items.
-  static const int ws_on = getenv("DSX_WS") ? atoi(getenv("DSX_WS")) : 1;
-  // (read at every plan, not cached: the parity tests lower it to force the persistent kernel onto small grids)
-  const int ws_min = getenv("DSX_WS_MIN_GRID") ? atoi(getenv("DSX_WS_MIN_GRID")) : 224;
-  // the 128 x 128 tile (2 x 2 waves of 64 pixels x 64 channels: each LDS pixel fragment feeds two MFMAs and each
-  // converted group twice the MFMA work of the 64 x 128 tile) wherever it still fills the chip
-  static const std::vector<int> ws_wide3 = tile_order("DSX_TILES_WS_WIDE", {TILE_128x128, TILE_64x128});
-  static const std::vector<int> ws_wide1 = tile_order("DSX_TILES_WS_WIDE_1X1", {TILE_128x128, TILE_64x128});
-  // 1 x 1 without GroupNorm / Swish in front (residual and attention-output convs): the loaders only copy, the kernel is
-  // bound by the weight stream, and only the one-N-block tiles have the deep weight ring (measured: 32^2 layers -2 us each)
-  static const std::vector<int> ws_wide1raw = tile_order("DSX_TILES_WS_WIDE_1X1_RAW", {TILE_64x128, TILE_128x128});
-  const std::vector<int>& ws_wide = ks == 1 ? ((a.has_gn || a.swish) ? ws_wide1 : ws_wide1raw) : ws_wide3;
-  static const std::vector<int> ws_narrow = tile_order("DSX_TILES_WS_NARROW", {TILE_256x64, TILE_128x64, TILE_64x64});
-  // Pass -1 (experiment, off: DSX_CPG2=1 enables it): few input channels at a large map (the 64-channel layers of the
-  // 128^2 level) on the two-chunk variant of k_conv_mfma: every 64 input channels are one staged group, three
-  // workgroups per CU overlap their load / MFMA / epilogue phases.  Measured slower than the persistent kernel
-  // (64->64 @128^2: 60 us vs 42 us), see DESIGN.md.
-  static const int g2_on = getenv("DSX_CPG2") ? atoi(getenv("DSX_CPG2")) : 0;
-  static const int g2_max_c = getenv("DSX_CPG2_MAXC") ? atoi(getenv("DSX_CPG2_MAXC")) : 64;
-  if (g2_on && ks == 3 && stride == 1 && a.Cout == 64 && a.stage_mode == 0 && a.kchunks % 2 == 0 &&
-      a.C0 % 64 == 0 && a.C1 % 64 == 0 && a.C0 + a.C1 <= g2_max_c) {
-    ConvArgs g = a;
-    const int tile = TILE_128x64;
-    const ConvTileInfo ti = conv_tile_info(tile);
-    const int TW = pow2_divisor(a.Wo, 16), TH = pow2_divisor(a.Ho, std::max(1, ti.BM / TW));
-    if (TW * TH == ti.BM) {
-      g.cpg = 2;
-      g.tw_log2 = ilog2(TW); g.th_log2 = ilog2(TH); g.tb_log2 = 0;
-      g.tiles_x = a.Wo / TW; g.tiles_y = a.Ho / TH;
-      g.m_tiles = g.tiles_x * g.tiles_y * a.B;
-      g.n_tiles = 1;
-      g.ksplit = 1; g.groups_per_split = a.kchunks / 2; g.slab_stride = 0;
-      g.lds_row = conv_lds_row_g2(g.tw_log2);
-      g.ablate = 0;
-      if (conv_g2_lds_bytes(tile, g) != 0 && g.m_tiles >= 512) { a = g; tile_out = tile; return true; }
-    }
+  const int gw2 = 2 * (dtype != DSX_DTYPE_F32 ? 32 : 16);          // channels per two-chunk group
+  if (k.narrow_g2 && ks == 3 && stride == 1 && a.Cout <= 32 && a.stage_mode == 0 && a.kchunks % 2 == 0 &&
+      a.C0 % gw2 == 0 && a.C1 % gw2 == 0 && !a.up) {
+    for (int tile : k.tiles_narrow_g2)
+      if (g2_geometry(tile, a, c)) { a = c; tile_out = tile; return true; }
   }
-  // Narrow outputs (<= 32 channels: the UNet's final conv, 64 -> 3 at full resolution): HBM-bound layers that the
-  // generic 128 x 32 tile walked as two 32-channel groups with a barrier pair each and a 16 x 8 pixel halo.  The
-  // two-chunk variant stages ALL input channels of a 16 x 16 (or 16 x 8) pixel patch once -- one load phase, one
-  // conversion, one barrier, 36 MFMA steps per row block -- with three workgroups per CU overlapping their phases.
-  static const int narrow_on = getenv("DSX_NARROW_G2") ? atoi(getenv("DSX_NARROW_G2")) : 1;
-  {
-    const int gw2 = 2 * (dtype != DSX_DTYPE_F32 ? 32 : 16);          // channels per two-chunk group
-    if (narrow_on && ks == 3 && stride == 1 && a.Cout <= 32 && a.stage_mode == 0 && a.kchunks % 2 == 0 &&
-        a.C0 % gw2 == 0 && a.C1 % gw2 == 0 && !a.up) {
-      static const std::vector<int> narrow_tiles = tile_order("DSX_TILES_NARROW_G2", {TILE_256x32, TILE_128x32});
-      for (int tile : narrow_tiles) {
-        ConvArgs g = a;
-        const ConvTileInfo ti = conv_tile_info(tile);
-        const int TW = pow2_divisor(a.Wo, 16), TH = pow2_divisor(a.Ho, std::max(1, ti.BM / TW));
-        if (TW * TH != ti.BM) continue;
-        g.cpg = 2;
-        g.tw_log2 = ilog2(TW); g.th_log2 = ilog2(TH); g.tb_log2 = 0;
-        g.tiles_x = a.Wo / TW; g.tiles_y = a.Ho / TH;
-        g.m_tiles = g.tiles_x * g.tiles_y * a.B;
-        g.n_tiles = 1;
-        g.ksplit = 1; g.groups_per_split = a.kchunks / 2; g.slab_stride = 0;
-        g.lds_row = conv_lds_row_g2(g.tw_log2);
-        g.ablate = 0;
-        if (conv_g2_lds_bytes(tile, g) != 0) { a = g; tile_out = tile; return true; }
-      }
-    }
-  }
-  static const int ws_1x1 = getenv("DSX_WS_1X1") ? atoi(getenv("DSX_WS_1X1")) : 1;
-  if (ws_on && (ks != 1 || ws_1x1) && stride == 1 && a.stage_mode == 0) {
-    for (int tile : (is_wide ? ws_wide : ws_narrow)) {
-      if (!tile_geometry(dtype, tile, ks, stride, a, c)) continue;
+  if (k.ws && (ks != 1 || k.ws_1x1) && stride == 1 && a.stage_mode == 0) {
+    const std::vector<int>& ws_wide =
+        ks == 1 ? ((a.has_gn || a.swish) ? k.tiles_ws_wide_1x1 : k.tiles_ws_wide_1x1_raw) : k.tiles_ws_wide;
+    for (int tile : (is_wide ? ws_wide : k.tiles_ws_narrow)) {
+      if (!tile_geometry(dtype, tile, ks, stride, k.ablate, a, c)) continue;
       if (conv_ws_lds_bytes(dtype, tile, ks, c) == 0) continue;
-      if ((long long)c.m_tiles * c.n_tiles >= ws_min) { a = c; tile_out = tile; return true; }
+      if ((long long)c.m_tiles * c.n_tiles >= k.ws_min_grid) { a = c; tile_out = tile; return true; }
     }
   }
-  for (int tile : (is_wide ? wide : (a.Cout <= 32 ? slim : narrow))) {
-    if (!tile_geometry(dtype, tile, ks, stride, a, c)) continue;
-    if ((long long)c.m_tiles * c.n_tiles >= min_grid) { a = c; tile_out = tile; return true; }
+  for (int tile : (is_wide ? k.tiles_wide : (a.Cout <= 32 ? k.tiles_slim : k.tiles_narrow))) {
+    if (!tile_geometry(dtype, tile, ks, stride, k.ablate, a, c)) continue;
+    if ((long long)c.m_tiles * c.n_tiles >= k.min_grid) { a = c; tile_out = tile; return true; }
   }
   int best = -1;
   long long best_eff = -1;
   ConvArgs best_a = a;
-  for (int tile : (is_wide ? wide2 : (a.Cout <= 32 ? slim : narrow2))) {
-    if (!tile_geometry(dtype, tile, ks, stride, a, c)) continue;
+  for (int tile : (is_wide ? k.tiles_wide_split : (a.Cout <= 32 ? k.tiles_slim : k.tiles_narrow_split))) {
+    if (!tile_geometry(dtype, tile, ks, stride, k.ablate, a, c)) continue;
     const long long grid = (long long)c.m_tiles * c.n_tiles;
     long long eff = grid;
-    if (splitk_on && grid < min_grid && kgroups >= 4 && (a.Cout % 16) == 0 && a.out_ld == a.Cout) {
-      const int want = (int)((min_grid + grid - 1) / grid);
+    if (k.splitk && grid < k.min_grid && kgroups >= 4 && (a.Cout % 16) == 0 && a.out_ld == a.Cout) {
+      const int want = (int)((k.min_grid + grid - 1) / grid);
       int S = std::min(want, kgroups / 2);  // at least two channel groups per slice
       const int gps = (kgroups + S - 1) / S;
       S = (kgroups + gps - 1) / gps;
@@ -851,7 +898,7 @@ static bool pick_conv(int dtype, int ks, int stride, ConvArgs& a, int& tile_out)
       }
     }
     if (eff > best_eff) { best = tile; best_a = c; best_eff = eff; }
-    if (eff >= min_grid) break;
+    if (eff >= k.min_grid) break;
   }
   if (best < 0) return false;
   a = best_a;
@@ -890,7 +937,18 @@ static int ws_wg_per_n(const ConvArgs& a) {
   return wpn;
 }
 
+// the GroupNorm partial sums of `t` come from the epilogue of the launch being planned (fp32 rows [B][nchunk][C][2])
+static float* plan_fused_stats(dsx_exec* ex, const Tensor& t, int nchunk, int C) {
+  StatInfo& si = ex->stats[t.id];
+  si.nchunk = nchunk;
+  si.part = ws_alloc(ex, (size_t)ex->B * nchunk * C * 2 * sizeof(float));
+  si.planned = true;
+  si.f32 = true;
+  return (float*)si.part;
+}
+
 static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
+  const PlanKnobs& k = ex->knobs;
   ex->pending_gn_pf.reset();
   ConvArgs a{};
   a.src0 = s.x0.p; a.C0 = s.x0.C;
@@ -930,38 +988,24 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
   const double esz = dtype != 0 ? 2.0 : 4.0;   // activation element size in HBM
   const double bytes = esz * ((double)a.B * a.Hs * a.Ws * cin + npix * a.Cout * (s.has_resid || s.resid ? 1 : 0)) +
                        (a.out_bf16 ? 2.0 : 4.0) * npix * a.Cout + wbytes;
-  {  // diagnostics: DSX_STAMP_OP=<conv ordinal>[,<block>] -> in-kernel phase stamps of that launch
-    static const char* se = getenv("DSX_STAMP_OP");
-    if (se) {
-      const int want = atoi(se);
-      const char* comma = strchr(se, ',');
-      if (ex->conv_ordinal == want) {
-        a.stamp = (unsigned long long*)ws_alloc(ex, 128 * 8);
-        a.stamp_block = comma ? atoi(comma + 1) : 0;
-        ex->stamp_buf = a.stamp;
-      }
-    }
-    ex->conv_ordinal++;
+  if (ex->conv_ordinal++ == k.stamp_op) {   // diagnostics: in-kernel phase stamps of this launch
+    a.stamp = (unsigned long long*)ws_alloc(ex, 128 * 8);
+    a.stamp_block = k.stamp_block;
+    ex->stamp_buf = a.stamp;
   }
   // ---- the UNet's first conv (few input channels): im2col-in-K kernel
-  if (!ex->m->want_naive && !s.film && !s.resid && !s.has_resid && conv_first_applicable(ks, stride, a, s.gn != nullptr)) {
+  if (!k.conv_naive && k.first && !s.film && !s.resid && !s.has_resid &&
+      conv_first_applicable(ks, stride, a, s.gn != nullptr)) {
     ex->launches++;
     a.wpack = s.w->pack_first;
-    if (s.want_stats) {
-      StatInfo& si = ex->stats[s.out.id];
-      si.nchunk = (a.Ho >> 4) * (a.Wo >> 4) * 4;
-      si.part = ws_alloc(ex, (size_t)a.B * si.nchunk * a.Cout * 2 * sizeof(float));
-      si.planned = true;
-      si.f32 = true;
-      a.stat_part = (float*)si.part;
-    }
+    if (s.want_stats) a.stat_part = plan_fused_stats(ex, s.out, (a.Ho >> 4) * (a.Wo >> 4) * 4, a.Cout);
     if (ex->sizing) return DSX_OK;
     add_op(ex, DSX_OP_CONV_MFMA, fmt("conv3x3 %d->%d @%dx%d first", (int)cin, a.Cout, a.Ho, a.Wo), flops, bytes,
            [=](hipStream_t st) { return launch_conv_first(dtype, a, st); });
     return DSX_OK;
   }
   // ---- 8 x 8 maps: the image-resident kernel (GroupNorm finalised in its prologue, statistics in its epilogue)
-  if (!ex->m->want_naive && conv_img_applicable(dtype, ks, stride, a, s.gn != nullptr, ex->m->cfg.norm_groups)) {
+  if (!k.conv_naive && k.img && conv_img_applicable(dtype, ks, stride, a, s.gn != nullptr, ex->m->cfg.norm_groups)) {
     ex->launches++;
     if (s.gn) {
       plan_stats(ex, s.x0);
@@ -974,56 +1018,33 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
       }
       a.gn_gamma = s.gn->gamma; a.gn_beta = s.gn->beta; a.gn_groups = ex->m->cfg.norm_groups; a.gn_eps = 1e-5f;
     }
-    if (s.want_stats) {
-      StatInfo& si = ex->stats[s.out.id];
-      si.nchunk = 1;
-      si.part = ws_alloc(ex, (size_t)a.B * a.Cout * 2 * sizeof(float));
-      si.planned = true;
-      si.f32 = true;
-      a.stat_part = (float*)si.part;
-    }
+    if (s.want_stats) a.stat_part = plan_fused_stats(ex, s.out, 1, a.Cout);
     if (ex->sizing) return DSX_OK;
-    static const int pf_on = getenv("DSX_PREFETCH") ? atoi(getenv("DSX_PREFETCH")) : 1;
     const PrefetchArgs mine{a.wpack, (unsigned)((size_t)a.kchunks * ks * ks * 2 * 1024), a.nblocks, nullptr};   // one slice per N block
-    if (pf_on && ex->prev_img_pf) *ex->prev_img_pf = mine;      // the previous image-resident conv warms the L2s for this one
+    if (k.prefetch && ex->prev_img_pf) *ex->prev_img_pf = mine;      // the previous image-resident conv warms the L2s for this one
     auto pf = std::make_shared<PrefetchArgs>(PrefetchArgs{nullptr, 0u, 0, nullptr});
     ex->prev_img_pf = pf;
     add_op(ex, DSX_OP_CONV_MFMA, fmt("conv%dx%d %d->%d @%dx%d img", ks, ks, (int)cin, a.Cout, a.Ho, a.Wo), flops, bytes,
            [=](hipStream_t st) { ConvArgs b = a; b.pf = *pf; return launch_conv_img(dtype, ks, b, st); });
     return DSX_OK;
   }
-  static const int fuse_stats = getenv("DSX_FUSE_STATS") ? atoi(getenv("DSX_FUSE_STATS")) : 1;
-  static const int ws_enabled = getenv("DSX_WS") ? atoi(getenv("DSX_WS")) : 1;
-  static const int ws_1x1_enabled = getenv("DSX_WS_1X1") ? atoi(getenv("DSX_WS_1X1")) : 1;
   int tile = -1;
-  const bool mfma_ok = !ex->m->want_naive && pick_conv(dtype, ks, stride, a, tile);   // (keyed on a.has_gn, never on pointers)
-  const bool use_ws = mfma_ok && a.cpg != 2 && ws_enabled && (ks != 1 || ws_1x1_enabled) && stride == 1 && a.stage_mode == 0 &&
+  const bool mfma_ok = !k.conv_naive && pick_conv(k, dtype, ks, stride, a, tile);   // (keyed on a.has_gn, never on pointers)
+  const bool use_ws = mfma_ok && a.cpg != 2 && k.ws && (ks != 1 || k.ws_1x1) && stride == 1 && a.stage_mode == 0 &&
                       a.ksplit == 1 && conv_ws_lds_bytes(dtype, tile, ks, a) != 0;
-  if (use_ws && ks == 3) {
-    // (these knobs are read at every plan: the tests flip them)
-    // Two 64-byte chunks per (tile, group) item where the geometry allows it: under the 16 x 16 MFMA shape the loaders,
-    // not the MFMAs, bound an item (their VALU stream gets 8 of every 16 issue cycles), and their per-item costs (DMA
-    // issue, wait, fetch, barrier: ~1.3 k of 3.2 k cycles per 32 channels on the 64-pixel tile) are paid once per 64
-    // channels this way.  Measured (A/B in one gpurun call): the 512-channel 16 x 16 layers -8 .. -11 %, a 256 -> 512 layer
-    // with only 4 two-chunk groups +7 % (hence the 12-chunk minimum there); the 128 x 128 tile -2.6 % over its 22 launches.
-    const int ws_g2 = getenv("DSX_WS_G2") ? atoi(getenv("DSX_WS_G2")) : 1;
-    const int g2_min64 = getenv("DSX_WS_G2_MIN64") ? atoi(getenv("DSX_WS_G2_MIN64")) : 12;     // chunks: fewer -> one-chunk groups
-    const int g2_min128 = getenv("DSX_WS_G2_MIN128") ? atoi(getenv("DSX_WS_G2_MIN128")) : 4;
+  if (use_ws && ks == 3) {   // several 64-byte chunks per (tile, group) item (PlanKnobs::ws_g2)
     ConvArgs t2 = a;
     t2.ws_cpg = 2; t2.lds_row = conv_lds_row_g2(a.tw_log2);
-    const int min_chunks = conv_tile_info(tile).BM == 64 ? g2_min64 : g2_min128;
-    if (ws_g2 && a.kchunks >= min_chunks && conv_ws_lds_bytes(dtype, tile, ks, t2) != 0) { a.ws_cpg = 2; a.lds_row = t2.lds_row; }
-    const int g4_min64 = getenv("DSX_WS_G4_MIN64") ? atoi(getenv("DSX_WS_G4_MIN64")) : 16;   // four chunks (64-pixel tile)
+    const int min_chunks = conv_tile_info(tile).BM == 64 ? k.ws_g2_min64 : k.ws_g2_min128;
+    if (k.ws_g2 && a.kchunks >= min_chunks && conv_ws_lds_bytes(dtype, tile, ks, t2) != 0) { a.ws_cpg = 2; a.lds_row = t2.lds_row; }
     ConvArgs t4 = a;
     t4.ws_cpg = 4; t4.lds_row = conv_lds_row_3x3_c(a.tw_log2, 4);
-    if (ws_g2 && a.kchunks >= g4_min64 && conv_ws_lds_bytes(dtype, tile, ks, t4) != 0) { a.ws_cpg = 4; a.lds_row = t4.lds_row; }
+    if (k.ws_g2 && a.kchunks >= k.ws_g4_min64 && conv_ws_lds_bytes(dtype, tile, ks, t4) != 0) { a.ws_cpg = 4; a.lds_row = t4.lds_row; }
   }
   if (use_ws && ks == 1) {   // the same for 1 x 1 convs: four chunks (128 input channels) per item
-    const int ws_c4 = getenv("DSX_WS_C4") ? atoi(getenv("DSX_WS_C4")) : 1;
-    const int c4_min = getenv("DSX_WS_C4_MIN") ? atoi(getenv("DSX_WS_C4_MIN")) : 8;   // chunks: at least two groups
     ConvArgs t4 = a;
     t4.ws_cpg = 4; t4.lds_row = conv_lds_row_1x1_c4(a.tw_log2);
-    if (ws_c4 && a.kchunks >= c4_min && conv_ws_lds_bytes(dtype, tile, ks, t4) != 0) { a.ws_cpg = 4; a.lds_row = t4.lds_row; }
+    if (k.ws_c4 && a.kchunks >= k.ws_c4_min && conv_ws_lds_bytes(dtype, tile, ks, t4) != 0) { a.ws_cpg = 4; a.lds_row = t4.lds_row; }
   }
   // (Tried and rejected in round 3, measured: the GroupNorm finalised by the consuming conv's own compute waves during
   // their start-up wait -- 14 to 22 k_gn_finalize launches fewer, but every such conv started 3-7 us later, the same
@@ -1034,33 +1055,18 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
     a.gn_scale = sc; a.gn_shift = sh;
   }
   ex->launches++;
-  if (fuse_stats && s.want_stats && mfma_ok && (use_ws ? conv_ws_fuses_stats(tile) : conv_tile_fuses_stats(tile)) &&
-      a.ksplit == 1 && a.tb_log2 == 0 &&
-      (a.Cout & 15) == 0 &&
-      a.out_ld == a.Cout && (a.resid_ld & 7) == 0) {
-    StatInfo& si = ex->stats[s.out.id];
-    si.nchunk = a.tiles_x * a.tiles_y * (use_ws ? conv_ws_tile_wm(tile) : conv_tile_wm(tile));
-    si.part = ws_alloc(ex, (size_t)a.B * si.nchunk * a.Cout * 2 * sizeof(float));
-    si.planned = true;
-    si.f32 = true;
-    a.stat_part = (float*)si.part;
-  }
+  if (k.fuse_stats && s.want_stats && mfma_ok && (use_ws ? conv_ws_fuses_stats(tile) : conv_tile_fuses_stats(tile)) &&
+      a.ksplit == 1 && a.tb_log2 == 0 && (a.Cout & 15) == 0 && a.out_ld == a.Cout && (a.resid_ld & 7) == 0)
+    a.stat_part = plan_fused_stats(ex, s.out, a.tiles_x * a.tiles_y * (use_ws ? conv_ws_tile_wm(tile) : conv_tile_wm(tile)), a.Cout);
   float* slab = nullptr;
   float* reduce_stats = nullptr;
   if (mfma_ok && a.ksplit > 1) {
     slab = (float*)ws_alloc(ex, (size_t)a.ksplit * a.slab_stride * sizeof(float));
     ex->launches++;
-    if (fuse_stats && s.want_stats && a.Cout % 64 == 0 && a.out_ld == a.Cout && (a.Ho * a.Wo) % 16 == 0) {
-      StatInfo& si = ex->stats[s.out.id];   // statistics in the reduce launch
-      si.nchunk = a.Ho * a.Wo / 16;
-      si.part = ws_alloc(ex, (size_t)a.B * si.nchunk * a.Cout * 2 * sizeof(float));
-      si.planned = true;
-      si.f32 = true;
-      reduce_stats = (float*)si.part;
-    }
+    if (k.fuse_stats && s.want_stats && a.Cout % 64 == 0 && a.out_ld == a.Cout && (a.Ho * a.Wo) % 16 == 0)
+      reduce_stats = plan_fused_stats(ex, s.out, a.Ho * a.Wo / 16, a.Cout);   // statistics in the reduce launch
   }
-  const int host_on = getenv("DSX_HOST_FIN") ? atoi(getenv("DSX_HOST_FIN")) : 1;   // (read at every plan: the tests flip it)
-  const bool host_fin = s.host_fin && host_on && use_ws;   // (shapes only: the sizing pass arms it too, plan_gn counts launches)
+  const bool host_fin = s.host_fin && k.host_fin && use_ws;   // (shapes only: the sizing pass arms it too, plan_gn counts launches)
   if (host_fin) ex->fin_host_armed = true;
   if (ex->sizing) return DSX_OK;
   if (mfma_ok) {
@@ -1084,18 +1090,14 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
     } else {
       ConvArgs w = a;
       w.handoff_timeouts = ex->handoff_timeouts;
-      w.xcd_bands = getenv("DSX_XCD_BANDS") ? atoi(getenv("DSX_XCD_BANDS")) : 1;
+      w.xcd_bands = k.xcd_bands;
       w.ws_wg_per_n = ws_wg_per_n(a);
-      // 1 x 1 convs with several N tiles: an XCD takes every N tile of its M tiles (ws_map 3).  With the N tiles dealt over
-      // the XCDs (the 3 x 3 choice: there the weights are the larger operand) every L2 fetched most of the input: 65.7 MB
-      // per launch of the 512 -> 1536 qkv conv against 18.4 MB algorithmic (PMC, profiles/r03_pmc_summary.txt).
-      const int map3_on = getenv("DSX_WS_MAP3") ? atoi(getenv("DSX_WS_MAP3")) : 1;
-      bool map3 = false;
-      if (map3_on && use_ws && ks == 1 && a.n_tiles >= 2 && a.n_tiles <= 32) {
+      // 1 x 1 convs with several N tiles: an XCD takes every N tile of its M tiles (PlanKnobs::ws_map3)
+      const bool map3 = k.ws_map3 && use_ws && ks == 1 && a.n_tiles >= 2 && a.n_tiles <= 32;
+      if (map3) {
         int wpn3 = std::max(8, (256 / a.n_tiles) / 8 * 8);
         if (wpn3 > a.m_tiles) wpn3 = (a.m_tiles + 7) / 8 * 8;
         w.ws_wg_per_n = wpn3;
-        map3 = true;
       }
       {   // division-free start-up of k_conv_ws: quotients and fastdiv magics (see ConvArgs::ws_map)
         const int NT = a.n_tiles, wpn = w.ws_wg_per_n, per_img = a.tiles_x * a.tiles_y;
@@ -1129,16 +1131,13 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
       }
       if (use_ws) {
         // this conv's k_gn_finalize launch pulls the weight slices into the L2 of the XCD group that will read them
-        // (k_conv_ws keys its N tile on blockIdx % 8 in exactly these two cases)
-        static const int pf_on = getenv("DSX_PREFETCH") ? atoi(getenv("DSX_PREFETCH")) : 1;
-        const int NT = a.n_tiles;
-        const bool keyed = !map3 && ((NT <= 8 && 8 % NT == 0 && w.ws_wg_per_n % (8 / NT) == 0) || (NT % 8) == 0);
+        // (k_conv_ws keys its N tile on blockIdx % 8 in exactly ws_map 0 and 1)
+        const bool keyed = w.ws_map == 0 || w.ws_map == 1;
         const size_t wblock = (size_t)a.kchunks * ks * ks * 2 * 1024;     // bytes of one 32-channel N block's fragments
-        const PrefetchArgs mine{a.wpack, (unsigned)(wblock * (ti.BN / 32)), NT, nullptr};
-        static const int pf_ws = getenv("DSX_PREFETCH_WS") ? atoi(getenv("DSX_PREFETCH_WS")) : 1;
-        if (pf_on && ex->pending_gn_pf && keyed) *ex->pending_gn_pf = mine;
+        const PrefetchArgs mine{a.wpack, (unsigned)(wblock * (ti.BN / 32)), a.n_tiles, nullptr};
+        if (k.prefetch && ex->pending_gn_pf && keyed) *ex->pending_gn_pf = mine;
         // no finalize launch in front (1 x 1 without GroupNorm, upsampling conv): the previous k_conv_ws launch carries it
-        else if (pf_on && pf_ws && ex->prev_ws_pf && keyed) *ex->prev_ws_pf = mine;
+        else if (k.prefetch && k.prefetch_ws && ex->prev_ws_pf && keyed) *ex->prev_ws_pf = mine;
         auto npf = std::make_shared<PrefetchArgs>(PrefetchArgs{nullptr, 0u, 0, nullptr});
         ex->prev_ws_pf = npf;
         w.pf = PrefetchArgs{nullptr, 0u, 0, nullptr};
@@ -1269,8 +1268,9 @@ static int plan_res(dsx_exec* ex, const Module& md, const Tensor& x0, const Tens
     g.out = av.p; g.ldo = C; g.storage = qkv.st;
     g.B = B; g.L = L; g.C = C; g.div = sqrtf((float)C); g.inv_div = 1.0f / g.div;
     const double esz = qkv.st ? 2.0 : 4.0;
+    const bool col_split = ex->knobs.attn_cs == 2;
     add_op(ex, DSX_OP_ATTN_GEMM, fmt("attn fused L=%d d=%d", L, C), 4.0 * B * L * (double)L * C,
-           B * esz * 4.0 * L * C, [=](hipStream_t st) { return launch_attn(g, st); });
+           B * esz * 4.0 * L * C, [=](hipStream_t st) { return launch_attn(g, col_split, st); });
   }
   Tensor o2 = new_tensor(ex, C, H, W);
   ConvSpec co{};
@@ -1362,6 +1362,8 @@ extern "C" int dsx_exec_create(dsx_model* m, int B, int H, int W, int cond_chann
   HIP_TRY(ops_init());
   dsx_exec* ex = new dsx_exec();
   ex->m = m; ex->B = B; ex->H = H; ex->W = W;
+  ex->knobs = read_plan_knobs();
+  ex->knobs.conv_naive = m->want_naive;   // the model's device image decides (naive weights exist only then)
   ex->cond_c = cond_channels; ex->x_c = m->cfg.in_channel - cond_channels;
   ex->sizing = true;
   int rc = build_plan(ex);
@@ -1402,6 +1404,8 @@ extern "C" int dsx_plan_dry_run(const dsx_unet_cfg* cfg, int dtype, int B, int H
       if (c->pw >= 0) conv_geometry(c->cout, c->cin, c->ks, dtype, c->kchunks, c->nblocks);
   dsx_exec* ex = new dsx_exec();
   ex->m = m; ex->B = B; ex->H = H; ex->W = W;
+  ex->knobs = read_plan_knobs();
+  ex->knobs.conv_naive = m->want_naive;   // the model's device image decides (naive weights exist only then)
   ex->cond_c = cond_channels; ex->x_c = m->cfg.in_channel - cond_channels;
   ex->sizing = true;
   rc = build_plan(ex);

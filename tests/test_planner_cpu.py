@@ -4,7 +4,8 @@ Round 1 shipped a workspace overflow: the planner's sizing pass and its planning
 preferences (a tiling decision keyed on a pointer that is null while sizing) and a conv wrote past the workspace
 (`Memory access fault`, DSX_MIN_GRID=448).  dsx_exec_create now fails unless both passes walk exactly the same
 number of bytes; these tests pin that for every tile-preference environment setting used while tuning, for all
-BASELINE configs and operand types.  Most knobs are read once per process, so every setting runs in a child."""
+BASELINE configs and operand types.  The knobs are read from the environment at plan time; every setting runs in a
+child process with its own environment."""
 import json
 import os
 import subprocess
