@@ -80,6 +80,9 @@ SIGNATURES = {
     "dsx_stitch": (_i, [_vp, _i64, _i, _i, _i, _pi32, _vp, _pi64, _vp]),
     "dsx_stitch_psnr_blocks": (_i, [_i, _i]),
     "dsx_stitch_psnr": (_i, [_vp, _i64, _i, _i, _i, _pi32, _vp, _pi64, _vp, _vp, _vp]),
+    "dsx_image_metrics_blocks": (_i, [_i, _i]),
+    "dsx_image_metrics": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp,
+                               C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "dsx_tileplan_create": (_i, [_pi64, _pi64, _pi64, _i, C.POINTER(_vp)]),
     "dsx_tileplan_destroy": (None, [_vp]),
     "dsx_tileplan_total": (_i64, [_vp]),

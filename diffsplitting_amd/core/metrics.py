@@ -1,0 +1,163 @@
+"""The reference's image-quality module (core/metrics.py), same names and signatures: tensor2img, save_img,
+calculate_psnr and calculate_ssim, plus ``image_metrics``, the batched device form of PSNR and SSIM.
+
+SSIM runs on the MI355X (``dsx_image_metrics``, include/dsx.h): there is no CPU fallback, so calculate_ssim raises
+DsxError without a device.  The reference writes its grid with torchvision's make_grid and its files with cv2; neither
+is a dependency here, so the grid is written out below and files are written with PIL, to the same pixels.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .._lib import DsxError, check, lib
+
+
+def _make_grid(t, nrow, padding=2, pad_value=0.0):
+    """torchvision.utils.make_grid(t, nrow, padding=2, normalize=False) of a (B, C, H, W) tensor."""
+    if t.size(1) == 1:
+        t = torch.cat((t, t, t), 1)
+    if t.size(0) == 1:
+        return t.squeeze(0)
+    nmaps = t.size(0)
+    xmaps = min(nrow, nmaps)
+    ymaps = int(math.ceil(float(nmaps) / xmaps))
+    height, width = int(t.size(2) + padding), int(t.size(3) + padding)
+    grid = t.new_full((t.size(1), height * ymaps + padding, width * xmaps + padding), pad_value)
+    k = 0
+    for y in range(ymaps):
+        for x in range(xmaps):
+            if k >= nmaps:
+                break
+            grid.narrow(1, y * height + padding, height - padding).narrow(
+                2, x * width + padding, width - padding).copy_(t[k])
+            k += 1
+    return grid
+
+
+def tensor2img(tensor, out_type=np.uint8, min_max=(-1, 1)):
+    """Tensor (4-D (B, 3/1, H, W) as a grid, 3-D (C, H, W) or 2-D (H, W), any range) -> HWC or HW numpy image in
+    [0, 255] (core/metrics.py:8-34): clamp to min_max, to [0, 1], * 255, round half to even, uint8."""
+    tensor = tensor.squeeze().float().cpu().clamp_(*min_max)
+    tensor = (tensor - min_max[0]) / (min_max[1] - min_max[0])
+    n_dim = tensor.dim()
+    if n_dim == 4:
+        img_np = _make_grid(tensor, nrow=int(math.sqrt(len(tensor)))).numpy()
+        img_np = np.transpose(img_np, (1, 2, 0))
+    elif n_dim == 3:
+        img_np = np.transpose(tensor.numpy(), (1, 2, 0))
+    elif n_dim == 2:
+        img_np = tensor.numpy()
+    else:
+        raise TypeError(f"Only support 4D, 3D and 2D tensor. But received with dimension: {n_dim:d}")
+    if out_type == np.uint8:
+        img_np = (img_np * 255.0).round()
+    return img_np.astype(out_type)
+
+
+def save_img(img, img_path, mode='RGB'):
+    """Write a channel-first image as core/metrics.py:37-59 lays it out (6-channel CIFAR pairs and 2-channel Hagen
+    pairs side by side), to the pixels cv2.imwrite would write: 3-channel arrays are BGR to cv2, so they are reversed
+    before PIL writes RGB; other modes write a single-channel 8- or 16-bit image."""
+    from PIL import Image
+    if len(img.shape) == 3 and img.shape[0] not in [1, 3]:
+        if mode == 'RGB':
+            img = np.transpose(img, (1, 2, 0))
+            img = img.reshape((img.shape[0], img.shape[1], 2, 3))
+            img = img.transpose((0, 2, 1, 3))
+            img = img.reshape((img.shape[0], img.shape[1] * img.shape[2], img.shape[3]))
+        else:
+            img = img.transpose((1, 0, 2))
+            img = img.reshape((img.shape[0], -1, 1))
+    else:
+        assert len(img.shape) == 3, f'img shape is {img.shape}'
+        img = img.transpose((1, 2, 0))
+    if mode == 'RGB':
+        img = img.astype(np.uint8)
+    if img.ndim == 3 and img.shape[2] == 1:
+        img = img[:, :, 0]
+    if img.ndim == 3:
+        if img.shape[2] != 3 or img.dtype != np.uint8:
+            raise ValueError(f"save_img writes 3-channel uint8 or 1-channel uint8/uint16 images, got {img.shape} "
+                             f"{img.dtype}")
+        Image.fromarray(np.ascontiguousarray(img[:, :, ::-1])).save(img_path)
+    elif img.dtype in (np.uint8, np.uint16):
+        Image.fromarray(np.ascontiguousarray(img)).save(img_path)          # mode L / I;16
+    else:
+        raise ValueError(f"save_img writes uint8 or uint16 single-channel images, got {img.dtype}")
+
+
+def calculate_psnr(img1, img2):
+    """PSNR of two [0, 255] images in float64 (core/metrics.py:62-69); inf when they are equal."""
+    img1 = img1.astype(np.float64)
+    img2 = img2.astype(np.float64)
+    mse = np.mean((img1 - img2) ** 2)
+    if mse == 0:
+        return float('inf')
+    return 20 * math.log10(255.0 / math.sqrt(mse))
+
+
+def _psnr_from_ssd(ssd, n, data_range):
+    mse = ssd / n
+    if mse == 0:
+        return float('inf')
+    return 20 * math.log10(data_range / math.sqrt(mse))
+
+
+def _run(a, b, quantize, lo, hi, data_range, stream=None):
+    """dsx_image_metrics on (B, C, H, W) fp32 CUDA tensors -> (ssim [B], ssd [B]) float64 numpy arrays."""
+    _lib.require_gpu()
+    B, Cn, H, W = a.shape
+    blocks = check(lib.dsx_image_metrics_blocks(H, W))
+    part = torch.empty((B * Cn * blocks * 2,), dtype=torch.float64, device=a.device)
+    ssim = np.empty(B, np.float64)
+    ssd = np.empty(B, np.float64)
+    if stream is None:
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+    pd = C.POINTER(C.c_double)
+    check(lib.dsx_image_metrics(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), B, Cn, H, W, int(quantize),
+                                float(lo), float(hi), float(data_range), C.c_void_p(part.data_ptr()),
+                                ssim.ctypes.data_as(pd), ssd.ctypes.data_as(pd), C.c_void_p(stream)))
+    return ssim, ssd
+
+
+def calculate_ssim(img1, img2):
+    """SSIM of two [0, 255] images (core/metrics.py:95-113): 2-D, H x W x 1 or H x W x 3 (the mean over the valid
+    region of all three channels, as the reference's three calls of ssim() on the whole array give).  Computed on
+    the device from the images' fp32 values, with the reference's constants (L = 255)."""
+    if not img1.shape == img2.shape:
+        raise ValueError('Input images must have the same dimensions.')
+    if img1.ndim == 2:
+        a, b = img1[None], img2[None]
+    elif img1.ndim == 3 and img1.shape[2] in (1, 3):
+        a, b = np.transpose(img1, (2, 0, 1)), np.transpose(img2, (2, 0, 1))
+    else:
+        raise ValueError('Wrong input image dimensions.')
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ta = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))[None].to(dev)
+    tb = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float32))[None].to(dev)
+    ssim, _ = _run(ta, tb, False, 0.0, 1.0, 255.0)
+    return float(ssim[0])
+
+
+def image_metrics(pred, target, min_max=(-1, 1), quantize=True, data_range=255.0, stream=None):
+    """Per-image (psnr, ssim) of two (B, C, H, W) CUDA tensors in one launch, float64 CPU tensors of length B.
+
+    quantize=True: for every i, equal to calculate_psnr(tensor2img(pred[i], min_max=min_max), tensor2img(target[i],
+    min_max=min_max)) (bit-equal) and the matching calculate_ssim (the mean over all C channels) at the default
+    data_range = 255, the reference's peak and L.  quantize=False: PSNR and SSIM of the raw fp32 values with
+    peak = L = data_range (stitched prediction frames)."""
+    if pred.shape != target.shape or pred.dim() != 4:
+        raise ValueError(f"pred and target must be (B, C, H, W) of one shape, got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    if not (pred.is_cuda and target.is_cuda):
+        raise DsxError("image_metrics runs on the device: pass CUDA tensors")
+    a = pred.to(torch.float32).contiguous()
+    b = target.to(torch.float32).contiguous()
+    ssim, ssd = _run(a, b, quantize, min_max[0], min_max[1], data_range, stream)
+    n = a.shape[1] * a.shape[2] * a.shape[3]
+    psnr = [_psnr_from_ssd(s, n, float(data_range)) for s in ssd.tolist()]
+    return torch.tensor(psnr, dtype=torch.float64), torch.from_numpy(ssim)

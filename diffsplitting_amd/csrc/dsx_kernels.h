@@ -392,6 +392,15 @@ hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions /*dev*/, 
 hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const int* regions, const long long* off,
                              TileSeq seq, float* flat, hipStream_t st);
 
+// SSIM (core/metrics.py:72-92) + sum of squared differences of `planes` image pairs (H, W >= 11), optionally quantised
+// on the load as tensor2img does (:14-34); part[planes][image_metrics_tiles(H, W)][2] = {sum of the SSIM map over
+// the tile, SSD (uint64 bits when quantised, else fp64)}.  win = the 11 taps of cv2.getGaussianKernel(11, 1.5).
+struct SsimWindow { double w[11]; };
+int image_metrics_tiles(int H, int W);
+hipError_t launch_image_metrics(const float* a, const float* b, int planes, int H, int W, int quantize, float lo,
+                                float hi, float rng, double c1, double c2, const SsimWindow& win, double* part,
+                                hipStream_t st);
+
 // relu(u) * sigmoid-mask reduction of the TimePredictor head
 hipError_t launch_masked_mean(const float* u, const float* mask, int B, long long n, float* out,
                               hipStream_t st);

@@ -659,6 +659,123 @@ hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions, TileSeq 
   return hipGetLastError();
 }
 
+// SSIM (core/metrics.py:72-92) + sum of squared differences (calculate_psnr, :62-69) of image pairs in one pass.
+// One workgroup per (32 x 32 tile of the valid region [5:-5, 5:-5], image plane): the 42 x 42 input tile (10-pixel
+// halo, re-read by the neighbours through L2) is staged in LDS, quantised on the load when asked (tensor2img,
+// :14-34: clamp, (x - lo) / (hi - lo) with IEEE division, * 255, round half to even); then the 11-tap Gaussian is
+// applied horizontally to the five moments x, y, x^2, y^2, x y of all 42 rows (fp64, to LDS) and vertically to the
+// 32 output rows.  Each plane's pixels are partitioned among its tiles (edge tiles also own the 5-pixel border) for
+// the SSD: exact uint64 of integers when quantised, fp64 otherwise.  Fixed reduction order (thread -> wave shuffles
+// -> 4 waves), no atomics: part[plane][tile] = {sum of the SSIM map over the tile, SSD}, bitwise reproducible.
+constexpr int kSsimT = 32, kSsimIn = kSsimT + 10;
+__device__ __forceinline__ float metrics_load(const float* p, bool quantize, float lo, float hi, float rng) {
+  float x = *p;
+  if (quantize) x = rintf((fminf(fmaxf(x, lo), hi) - lo) / rng * 255.0f);
+  return x;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__global__ __launch_bounds__(256) void k_image_metrics(const float* __restrict__ a, const float* __restrict__ b, int H,
+                                                       int W, int quantize, float lo, float hi, float rng, double c1,
+                                                       double c2, SsimWindow win, int tiles_x, double* __restrict__ part) {
+  __shared__ float sa[kSsimIn][kSsimIn], sb[kSsimIn][kSsimIn];
+  __shared__ double hm[5][kSsimIn][kSsimT];
+  __shared__ double red[4];
+  __shared__ unsigned long long redq[4];
+  const int tile = blockIdx.x, plane = blockIdx.y;
+  const int y0 = (tile / tiles_x) * kSsimT, x0 = (tile % tiles_x) * kSsimT;    // output tile = input rows/cols + 5
+  const int ty_last = (H - 10 + kSsimT - 1) / kSsimT - 1, tx_last = tiles_x - 1;
+  // pixels of this tile's SSD share: its output rows/cols, widened to the image edge on the edge tiles
+  const int oy0 = y0 == 0 ? 0 : y0 + 5, oy1 = y0 / kSsimT == ty_last ? H : y0 + 5 + kSsimT;
+  const int ox0 = x0 == 0 ? 0 : x0 + 5, ox1 = x0 / kSsimT == tx_last ? W : x0 + 5 + kSsimT;
+  const size_t pl = (size_t)plane * H * W;
+  const bool q = quantize != 0;
+  double ssd = 0;
+  unsigned long long ssdq = 0;
+  for (int i = threadIdx.x; i < kSsimIn * kSsimIn; i += 256) {
+    const int r = i / kSsimIn, c = i % kSsimIn, y = y0 + r, x = x0 + c;
+    float va = 0.f, vb = 0.f;
+    if (y < H && x < W) {
+      va = metrics_load(a + pl + (size_t)y * W + x, q, lo, hi, rng);
+      vb = metrics_load(b + pl + (size_t)y * W + x, q, lo, hi, rng);
+      if (y >= oy0 && y < oy1 && x >= ox0 && x < ox1) {
+        if (q) { const int d = (int)va - (int)vb; ssdq += (unsigned long long)(d * d); }
+        else { const double d = (double)va - (double)vb; ssd += d * d; }
+      }
+    }
+    sa[r][c] = va; sb[r][c] = vb;
+  }
+  __syncthreads();
+  const int col = threadIdx.x & (kSsimT - 1), r8 = threadIdx.x / kSsimT;
+  for (int r = r8; r < kSsimIn; r += 256 / kSsimT) {
+    double m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0;
+#pragma unroll
+    for (int k = 0; k < 11; ++k) {
+      const double u = sa[r][col + k], v = sb[r][col + k], w = win.w[k];
+      m0 += w * u; m1 += w * v; m2 += w * (u * u); m3 += w * (v * v); m4 += w * (u * v);
+    }
+    hm[0][r][col] = m0; hm[1][r][col] = m1; hm[2][r][col] = m2; hm[3][r][col] = m3; hm[4][r][col] = m4;
+  }
+  __syncthreads();
+  // vertical: 4 consecutive output rows per thread share their 14 rows of horizontal sums (taps in ascending order)
+  constexpr int kRows = kSsimT / (256 / kSsimT);
+  const int rv = r8 * kRows;
+  double acc = 0;
+  if (x0 + col < W - 10) {
+    double mu1[kRows] = {}, mu2[kRows] = {}, e11[kRows] = {}, e22[kRows] = {}, e12[kRows] = {};
+#pragma unroll
+    for (int k = 0; k < kRows + 10; ++k) {
+      const double h0 = hm[0][rv + k][col], h1 = hm[1][rv + k][col], h2 = hm[2][rv + k][col],
+                   h3 = hm[3][rv + k][col], h4 = hm[4][rv + k][col];
+#pragma unroll
+      for (int j = 0; j < kRows; ++j) {
+        if (k - j >= 0 && k - j < 11) {
+          const double w = win.w[k - j];
+          mu1[j] += w * h0; mu2[j] += w * h1; e11[j] += w * h2; e22[j] += w * h3; e12[j] += w * h4;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+      if (y0 + rv + j < H - 10) {
+        const double mu11 = mu1[j] * mu1[j], mu22 = mu2[j] * mu2[j], mu12 = mu1[j] * mu2[j];
+        const double s11 = e11[j] - mu11, s22 = e22[j] - mu22, s12 = e12[j] - mu12;
+        acc += ((2 * mu12 + c1) * (2 * s12 + c2)) / ((mu11 + mu22 + c1) * (s11 + s22 + c2));
+      }
+    }
+  }
+  acc = wave_sum(acc); ssd = wave_sum(ssd); ssdq = wave_sum_u64(ssdq);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { red[wave] = acc; redq[wave] = q ? ssdq : (unsigned long long)__double_as_longlong(ssd); }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double* o = part + ((size_t)plane * gridDim.x + tile) * 2;
+    o[0] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (q) {
+      o[1] = __longlong_as_double((long long)((redq[0] + redq[1]) + (redq[2] + redq[3])));
+    } else {
+      double s[4];
+      for (int w = 0; w < 4; ++w) s[w] = __longlong_as_double((long long)redq[w]);
+      o[1] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+  }
+}
+int image_metrics_tiles(int H, int W) {
+  return ((H - 10 + kSsimT - 1) / kSsimT) * ((W - 10 + kSsimT - 1) / kSsimT);
+}
+hipError_t launch_image_metrics(const float* a, const float* b, int planes, int H, int W, int quantize, float lo,
+                                float hi, float rng, double c1, double c2, const SsimWindow& win, double* part,
+                                hipStream_t st) {
+  if (H < 11 || W < 11 || planes < 1 || planes > 65535) return hipErrorInvalidValue;
+  const int tiles_x = (W - 10 + kSsimT - 1) / kSsimT;
+  hipLaunchKernelGGL(k_image_metrics, dim3((unsigned)image_metrics_tiles(H, W), (unsigned)planes), dim3(256), 0, st,
+                     a, b, H, W, quantize, lo, hi, rng, c1, c2, win, tiles_x, part);
+  return hipGetLastError();
+}
+
 // TimePredictor head (time_predictor.py:38-44): sum(relu(u)*mask) / sum(mask) per image
 __global__ __launch_bounds__(256) void k_masked_mean(const float* __restrict__ u,
                                                      const float* __restrict__ mask, long long n,

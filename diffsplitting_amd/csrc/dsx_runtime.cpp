@@ -1973,6 +1973,51 @@ extern "C" int dsx_stitch_psnr(const float* tiles, int64_t count, int C, int ph,
   return DSX_OK;
 }
 
+// SSIM + SSD of image pairs (core/metrics.py:62-92), optionally on the tensor2img quantisation (:14-34)
+extern "C" int dsx_image_metrics_blocks(int H, int W) {
+  if (H < 11 || W < 11) return fail(DSX_ERR_INVALID, "SSIM needs H, W >= 11 (got %d x %d)", H, W);
+  return image_metrics_tiles(H, W);
+}
+extern "C" int dsx_image_metrics(const float* a, const float* b, int B, int C, int H, int W, int quantize, double lo,
+                                 double hi, double data_range, double* partials_dev, double* out_ssim,
+                                 double* out_ssd, void* stream) {
+  if (!a || !b || !partials_dev || !out_ssim || !out_ssd || B < 1 || C < 1)
+    return fail(DSX_ERR_INVALID, "bad argument");
+  if (H < 11 || W < 11) return fail(DSX_ERR_INVALID, "SSIM needs H, W >= 11 (got %d x %d)", H, W);
+  if ((int64_t)B * C > 65535) return fail(DSX_ERR_INVALID, "B * C = %lld image planes, at most 65535", (long long)B * C);
+  if (!(data_range > 0) || !std::isfinite(data_range)) return fail(DSX_ERR_INVALID, "data_range must be positive");
+  if (quantize && !(std::isfinite(lo) && std::isfinite(hi) && hi > lo))
+    return fail(DSX_ERR_INVALID, "quantisation needs finite min_max with lo < hi");
+  // cv2.getGaussianKernel(11, 1.5): exp(-x^2 / (2 sigma^2)) scaled by 1 / sum, in double
+  SsimWindow win;
+  double sum = 0;
+  for (int i = 0; i < 11; ++i) { const double x = i - 5.0; win.w[i] = std::exp((-0.5 / (1.5 * 1.5)) * x * x); sum += win.w[i]; }
+  sum = 1.0 / sum;
+  for (int i = 0; i < 11; ++i) win.w[i] *= sum;
+  const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
+  // tensor2img's arithmetic: clamp bounds as fp32, hi - lo in double then fp32 (torch divides by a Python float)
+  const int planes = B * C, tiles = image_metrics_tiles(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(launch_image_metrics(a, b, planes, H, W, quantize ? 1 : 0, (float)lo, (float)hi, (float)(hi - lo), c1, c2,
+                               win, partials_dev, st));
+  std::vector<double> part((size_t)planes * tiles * 2);
+  HIP_TRY(hipMemcpyAsync(part.data(), partials_dev, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const double valid = (double)C * (H - 10) * (W - 10);
+  for (int i = 0; i < B; ++i) {
+    double s = 0, d = 0;
+    uint64_t dq = 0;
+    for (size_t j = (size_t)i * C * tiles; j < (size_t)(i + 1) * C * tiles; ++j) {
+      s += part[j * 2];
+      if (quantize) { uint64_t u; std::memcpy(&u, &part[j * 2 + 1], 8); dq += u; }
+      else d += part[j * 2 + 1];
+    }
+    out_ssim[i] = s / valid;
+    out_ssd[i] = quantize ? (double)dq : d;
+  }
+  return DSX_OK;
+}
+
 // tiles of both channels cut out of device-resident frames AND normalised in the same pass: the batch source of tiled
 // prediction without the per-tile host crop + host->device copy of the reference's DataLoader(batch_size = 1)
 extern "C" int dsx_tiles_gather_norm(const float* frames0, const float* frames1, const int64_t data_shape[3],

@@ -278,6 +278,20 @@ int dsx_stitch_psnr(const float* tiles_dev, int64_t count, int C, int ph, int pw
                     float* canvas_dev, const int64_t data_shape[3], const float* gt_canvas_dev, double* partials_dev,
                     void* stream);
 
+/* Image-quality metrics of the reference's core/metrics.py on B image pairs a, b (B,C,H,W fp32 on the device), in one
+ * pass: per image, the mean over its C channels of the SSIM map of ssim() (core/metrics.py:72-92: cv2.getGaussianKernel
+ * (11, 1.5) window, valid region [5:-5, 5:-5], C1 = (0.01 L)^2, C2 = (0.03 L)^2 with L = data_range, moments in fp64)
+ * and the sum of squared differences over the whole image (calculate_psnr, :62-69).  quantize != 0 first maps both
+ * images as tensor2img (:14-34) does: clamp to [lo, hi], (x - lo) / (hi - lo) in fp32, * 255, round half to even;
+ * the SSD is then an exact integer.  H and W >= 11 (the reference returns NaN below).
+ * dsx_image_metrics_blocks(H, W): workgroups per image plane; partials_dev holds B * C * blocks * 2 doubles.
+ * out_ssim_host[B], out_ssd_host[B] (exact when quantised, below 2^53) are written after the stream is synchronised;
+ * the per-block partials are added in a fixed order, so equal inputs give bitwise-equal outputs. */
+int dsx_image_metrics_blocks(int H, int W);
+int dsx_image_metrics(const float* a_dev, const float* b_dev, int B, int C, int H, int W, int quantize, double lo,
+                      double hi, double data_range, double* partials_dev, double* out_ssim_host, double* out_ssd_host,
+                      void* stream);
+
 /* ------------------------------------------------- tile plan with device-resident tables (the stall-free forms)
  * The entry points above take host tables and upload them per call (a small allocation and a synchronous copy each).
  * A dsx_tileplan keeps the patch starts and valid regions of every tile on the device (uploaded once, at first
