@@ -12,9 +12,13 @@ noise; the default K=2000 is one complete sampling loop.  Every step costs the
 same, so images/s = N*B / (2000 * ms_per_step).  Inputs (conditioning images,
 initial noise, weights) are resident in HBM before the timed region.
 
-Adds `roofline` (conv-MFMA kernel family, measured live with HIP events around
-each launch of an eager replay) and `cpu_baseline` (the CPU oracle on the host
-cores, a bounded sample) to the JSON line.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and
+prints the JSON line.  `--full` adds the figures that take runs of their own:
+`roofline` (conv-MFMA kernel family, measured live with HIP events around each
+launch of an eager replay), `fp32_parity` (the fp32 build on the same workload)
+and `cpu_baseline` (the CPU oracle on the host cores, a bounded sample).
+
+    python bench.py --gpus 1 --steps 2000 --warmup 10 --full
 """
 import argparse
 import ctypes as C
@@ -279,9 +283,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=16, help="images per GPU (BASELINE config: 16)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-fp32-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the result line's own figures, also measure the roofline of the conv family, the fp32 "
+                         "parity build and the CPU oracle baseline (each in runs of its own) and add them to the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out roofline")
+    ap.add_argument("--no-fp32-parity", action="store_true", help="with --full: leave out fp32_parity")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--split", type=int, default=int(os.environ.get("DSX_BENCH_SPLIT", "1")),
                     help="run the per-GPU batch as this many independent sub-batches on separate HIP streams")
@@ -417,11 +424,11 @@ def main():
         gf = eng.flops(128, 128)
         line["unet_gflop_per_image_step"] = gf / 1e9
         line["sustained_tflops_per_gpu"] = gf * B / (ms_per_step * 1e-3) / 1e12
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             line["roofline"] = roofline(eng, eng.executor(B // nsplit, 128, 128, 3), args.dtype)
-        if world == 1 and not args.no_fp32_parity and args.dtype == "bf16":
+        if args.full and world == 1 and not args.no_fp32_parity and args.dtype == "bf16":
             line["fp32_parity"] = fp32_parity_line(sd, B)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd)                       # batch 4: the reference's CPU-runnable case
             b16 = cpu_baseline(sd, batch=16, warm=1, timed=8)             # the headline batch as well
             line["cpu_baseline"]["batch16"] = {"value": b16["value"], "unit": b16["unit"], "sample": b16["sample"]}

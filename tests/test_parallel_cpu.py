@@ -158,6 +158,15 @@ def test_bench_dump_outputs_dry(tmp_path):
     assert (x[:4] == 0).all() and (x[4:] == 1).all()
 
 
+def test_bench_full_is_an_option():
+    """Roofline, fp32 parity and CPU baseline are asked for with --full; a plain run prints the headline line only."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stderr[-2000:]
+
+
 def test_bench_refuses_mismatched_world():
     import subprocess
     import sys
