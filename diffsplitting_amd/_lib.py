@@ -31,7 +31,16 @@ class StepTable(C.Structure):
                 ("per_sample", C.c_int32)]
 
 
+class LayerInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "kind", "op_begin", "op_end", "op_main", "ks", "stride", "up", "swish", "B", "Hs", "Ws", "Ho", "Wo",
+        "C0", "C1", "src_dtype", "gn_gamma_param", "gn_beta_param", "gn_in_kernel", "w_param", "b_param",
+        "bias_in_film", "film_off", "film_bs", "resid_ld", "out_ld", "Cout", "out_dtype", "ld", "reserved")] + \
+        [(n, C.c_uint64) for n in ("src0", "src1", "gn_scale", "gn_shift", "film", "resid", "out")]
+
+
 FLAVOUR_SR3, FLAVOUR_DDPM = 0, 1
+LAYER_CONV, LAYER_ATTN, LAYER_FILM, LAYER_INPUT = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 TILING_TRIM, TILING_PAD, TILING_SHIFT = 0, 1, 2
 
@@ -66,6 +75,9 @@ SIGNATURES = {
     "dsx_exec_profile": (_i, [_vp, _i, _vp, _vp]),
     "dsx_exec_time_kind": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "dsx_exec_read_stamps": (_i, [_vp, _vp]),
+    "dsx_exec_num_layers": (_i, [_vp]),
+    "dsx_exec_layer_info": (_i, [_vp, _i, C.POINTER(LayerInfo)]),
+    "dsx_exec_copy_workspace": (_i, [_vp, _u64, C.c_size_t, _vp, _vp]),
     "dsx_unet_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "dsx_time_predictor_set_mask": (_i, [_vp, _vp, _vp]),
     "dsx_time_predictor_forward": (_i, [_vp, _vp, _vp, _vp]),

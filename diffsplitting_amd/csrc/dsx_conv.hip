@@ -1614,6 +1614,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
           else { const double2 v = *(const double2*)((const double*)part + idx); gs[p] += v.x; gq[p] += v.y; }
         }
       }
+      const StatPivot& piv = first ? a.gn_piv0 : a.gn_piv1;
+      if (piv.bias || piv.film)                 // shifted partials (k_conv_first / split-K reduce producers): rare here
+        stat_unshift(gs[p], gq[p], (double)stat_pivot(piv, b, first ? c : c - a.C0), (double)(a.Hs * a.Ws));
     }
     // Group sums over <= 64 lanes in fp32 (a channel's sums over the 64 pixels already are fp32 values of the producer's
     // epilogue; the xor butterfly gives every lane of a group the same bits), the cancellation-prone E[x^2] - mean^2 in
@@ -1934,17 +1937,20 @@ __global__ __launch_bounds__(256) void k_conv_first(const ConvArgs a) {
     for (int mb = 0; mb < 2; ++mb) {
       const int m = (wave * 2 + mb) * 32 + li;
       const size_t opix = ((size_t)b * a.Ho + (oy0 + (m >> 4))) * a.Wo + (ox0 + (m & 15));
-      float x[16];
+      float x[16], pv[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) x[r] = acc[mb][nb][r];
+      for (int r = 0; r < 16; ++r) { x[r] = acc[mb][nb][r]; pv[r] = 0.f; }
       if (live) {
         if (a.bias) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { const float4 tt = *(const float4*)(a.bias + nbase + 4 * j); x[4 * j] += tt.x; x[4 * j + 1] += tt.y; x[4 * j + 2] += tt.z; x[4 * j + 3] += tt.w; }
+          for (int j = 0; j < 4; ++j) { const float4 tt = *(const float4*)(a.bias + nbase + 4 * j); pv[4 * j] = tt.x; pv[4 * j + 1] = tt.y; pv[4 * j + 2] = tt.z; pv[4 * j + 3] = tt.w; }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) x[r] += pv[r];
         }
         store16<true>(a.out, opix * a.out_ld + nbase, x, okind, 16);
+        // statistics shifted by the bias (StatPivot): a uniform input region gives x ~ bias, whose raw sums would cancel
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { s1[r] += x[r]; s2[r] += x[r] * x[r]; }
+        for (int r = 0; r < 16; ++r) { const float d = x[r] - pv[r]; s1[r] += d; s2[r] += d * d; }
       }
     }
     if (a.stat_part != nullptr) {

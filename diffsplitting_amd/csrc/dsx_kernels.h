@@ -73,10 +73,31 @@ __device__ __forceinline__ void l2_prefetch_retire(const PrefetchArgs& pf, const
 }
 #endif
 
+// Shifted fp32 GroupNorm partials: a producer that has a per-(image, channel) pivot p = bias[c] + film[b][c] (either
+// pointer may be null) sums x - p and (x - p)^2, so that a flat map whose level comes from the bias (a uniform background
+// through the first conv) does not cancel in E[x^2] - E[x]^2; the consumer adds the pivot back in double.  Every tile of
+// the map uses the same pivot; producer and consumer compute it with this one expression (bitwise the same value).
+struct StatPivot {
+  const float* bias;     // [C] or nullptr
+  const float* film;     // [B][film_bs] or nullptr
+  int film_bs;
+};
+#if defined(__HIPCC__)
+__device__ __forceinline__ float stat_pivot(const StatPivot& p, int b, int c) {
+  return (p.bias ? p.bias[c] : 0.f) + (p.film ? p.film[(size_t)b * p.film_bs + c] : 0.f);
+}
+// channel sums (s, q) of x - p over `count` pixels -> sums of x
+__device__ __forceinline__ void stat_unshift(double& s, double& q, double p, double count) {
+  q += 2.0 * p * s + count * p * p;
+  s += count * p;
+}
+#endif
+
 // GroupNorm of the concatenation of (t0, t1) -> scale/shift[b][C0+C1]
 struct GnFinArgs {
   const void* part0; int C0, nchunk0, f32_0;   // partials: double (k_chan_stats) or float (conv epilogue)
   const void* part1; int C1, nchunk1, f32_1;
+  StatPivot piv0, piv1;  // pivots of shifted fp32 partials (all-null: unshifted)
   int B, groups;
   double count;          // elements per channel (H*W)
   const float* gamma;    // [C0+C1]
@@ -103,7 +124,8 @@ __device__ __forceinline__ void gn_finalize_item(const GnFinArgs& a, const int b
   // they are issued 8 at a time (the kernel is pure load latency otherwise)
   const int n0 = max(0, min(a.C0, c_lo + cpg) - c_lo);      // first n0 channels from source 0
   const int n1 = cpg - n0;
-  auto accumulate = [&](const void* part, int is_f32, int nsrc, int nchunk, int Csrc, int cbase) __attribute__((always_inline)) {
+  auto accumulate = [&](const void* part, int is_f32, int nsrc, int nchunk, int Csrc, int cbase, const StatPivot& piv) __attribute__((always_inline)) {
+    const bool shifted = piv.bias || piv.film;
     const int items = nsrc * nchunk;
     for (int i0 = tid; i0 < items; i0 += NT * 8) {
       double ps[8], pq[8];
@@ -116,6 +138,11 @@ __device__ __forceinline__ void gn_finalize_item(const GnFinArgs& a, const int b
           const size_t idx = (((size_t)b * nchunk + ch) * Csrc + c) * 2;
           if (is_f32) { const float2 v = *(const float2*)((const float*)part + idx); ps[u] = v.x; pq[u] = v.y; }
           else { const double2 v = *(const double2*)((const double*)part + idx); ps[u] = v.x; pq[u] = v.y; }
+          if (shifted) {   // sum over the chunks of (s + 2 p s_k) + count p^2: the count term once, with chunk 0
+            const double p = (double)stat_pivot(piv, b, c);
+            pq[u] += 2.0 * p * ps[u] + (ch == 0 ? a.count * p * p : 0.0);
+            ps[u] += ch == 0 ? a.count * p : 0.0;
+          }
         }
       }
 #pragma unroll
@@ -126,8 +153,8 @@ __device__ __forceinline__ void gn_finalize_item(const GnFinArgs& a, const int b
   const int c_own = c_lo + tid;
   const bool own = tid < cpg;
   const float g_own = own ? a.gamma[c_own] : 0.f, b_own = own ? a.beta[c_own] : 0.f;
-  if (n0 > 0) accumulate(a.part0, a.f32_0, n0, a.nchunk0, a.C0, c_lo);
-  if (n1 > 0) accumulate(a.part1, a.f32_1, n1, a.nchunk1, a.C1, c_lo + n0 - a.C0);
+  if (n0 > 0) accumulate(a.part0, a.f32_0, n0, a.nchunk0, a.C0, c_lo, a.piv0);
+  if (n1 > 0) accumulate(a.part1, a.f32_1, n1, a.nchunk1, a.C1, c_lo + n0 - a.C0, a.piv1);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
   if constexpr (NW > 1) {
@@ -220,6 +247,7 @@ struct ConvArgs {
   // left them ([B][nchunk][C][2], double from k_chan_stats or float from a fused epilogue) and the affine parameters
   const void* gn_part0; int gn_nchunk0, gn_pf32_0;
   const void* gn_part1; int gn_nchunk1, gn_pf32_1;
+  StatPivot gn_piv0, gn_piv1;   // pivots of shifted fp32 partials (GnFinArgs::piv0 / piv1)
   const float* gn_gamma; const float* gn_beta;
   int gn_groups; float gn_eps;
   PrefetchArgs pf;        // weight slices of the next conv launch (see l2_prefetch)
@@ -318,7 +346,8 @@ struct SplitKReduceArgs {
   const void* resid; int resid_ld;
   void* out;
   int act_bf16;                          // storage kind of resid and out (0 fp32, 1 bf16, 2 fp16)
-  float* stat_part;                      // nullptr, or GroupNorm partials [B][HW/16][N][2] of `out` (N % 64 == 0, HW % 16 == 0)
+  float* stat_part;                      // nullptr, or GroupNorm partials [B][HW/16][N][2] of `out` (N % 64 == 0, HW % 16 == 0),
+                                         // shifted by the pivot bias[n] + film[b][n] (StatPivot)
 };
 hipError_t launch_splitk_reduce(const SplitKReduceArgs& a, hipStream_t st);
 

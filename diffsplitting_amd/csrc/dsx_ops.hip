@@ -268,6 +268,7 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_stats(const SplitKReduceA
     for (int k = 0; k < 4; ++k) v[k] += slab[(size_t)s * a.slab_stride + idx[k]];
   }
   float s1 = 0.f, s2 = 0.f;
+  const float pv = stat_pivot(StatPivot{a.bias, a.film, a.film_bs}, b, n);   // the statistics are shifted by it
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     float x = v[k];
@@ -275,7 +276,8 @@ __global__ __launch_bounds__(256) void k_splitk_reduce_stats(const SplitKReduceA
     if (a.film) x += fl;
     if (a.resid) x += rs[k];
     store1_act(a.out, idx[k], x, a.act_bf16);
-    s1 += x; s2 += x * x;
+    const float d = x - pv;
+    s1 += d; s2 += d * d;
   }
   red[0][pl][threadIdx.x & 63] = s1;
   red[1][pl][threadIdx.x & 63] = s2;

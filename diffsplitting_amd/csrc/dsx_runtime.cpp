@@ -709,6 +709,7 @@ struct StatInfo {          // GroupNorm partial sums of one tensor, produced at 
   int nchunk = 0;
   bool planned = false;
   bool f32 = false;
+  StatPivot piv{nullptr, nullptr, 0};   // fp32 partials shifted by this pivot (k_conv_first, split-K reduce)
 };
 
 struct OpInfo {            // what one launch of the plan computes (for profiling / roofline)
@@ -770,6 +771,12 @@ struct dsx_exec {
   // time predictor head
   float* tp_w = nullptr; float* tp_b = nullptr; float* tp_mask = nullptr;
   int launches = 0;
+  // layer table (dsx_exec_layer_info): recorded by the planning pass only; what plan_conv's kernel branch chose for
+  // the GroupNorm of the layer being planned
+  std::vector<dsx_layer_info> layers;
+  float* rec_gn_scale = nullptr;
+  float* rec_gn_shift = nullptr;
+  int rec_gn_in_kernel = 0;
 };
 
 static void add_op(dsx_exec* ex, int kind, const std::string& desc, double flops, double bytes,
@@ -947,7 +954,44 @@ static float* plan_fused_stats(dsx_exec* ex, const Tensor& t, int nchunk, int C)
   return (float*)si.part;
 }
 
+static dsx_layer_info new_layer(dsx_exec* ex, int kind, int op_begin) {
+  dsx_layer_info L;
+  memset(&L, 0, sizeof L);
+  L.kind = kind;
+  L.op_begin = op_begin; L.op_end = (int)ex->op_info.size(); L.op_main = L.op_end - 1;
+  L.B = ex->B;
+  L.gn_gamma_param = L.gn_beta_param = L.w_param = L.b_param = -1;
+  return L;
+}
+
+static int plan_conv_ops(dsx_exec* ex, const ConvSpec& s);
+
+// plan_conv_ops, plus the layer-table entry of the conv in the planning pass
 static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
+  const int op0 = (int)ex->op_info.size();
+  ex->rec_gn_scale = ex->rec_gn_shift = nullptr;
+  ex->rec_gn_in_kernel = 0;
+  const int rc = plan_conv_ops(ex, s);
+  if (rc || ex->sizing) return rc;
+  dsx_layer_info L = new_layer(ex, DSX_LAYER_CONV, op0);
+  for (int i = L.op_end - 1; i >= op0; --i)
+    if (ex->op_info[i].kind == DSX_OP_CONV_MFMA || ex->op_info[i].kind == DSX_OP_CONV_NAIVE) { L.op_main = i; break; }
+  L.ks = s.w->ks; L.stride = s.stride; L.up = s.up ? 1 : 0; L.swish = s.swish ? 1 : 0;
+  L.Hs = s.x0.H; L.Ws = s.x0.W; L.Ho = s.out.H; L.Wo = s.out.W;
+  L.C0 = s.x0.C; L.C1 = s.x1.C; L.src_dtype = s.x0.st;
+  L.src0 = (uint64_t)(uintptr_t)s.x0.p; L.src1 = s.x1.C ? (uint64_t)(uintptr_t)s.x1.p : 0;
+  if (s.gn) { L.gn_gamma_param = s.gn->pg; L.gn_beta_param = s.gn->pb; }
+  L.gn_in_kernel = ex->rec_gn_in_kernel;
+  L.gn_scale = (uint64_t)(uintptr_t)ex->rec_gn_scale; L.gn_shift = (uint64_t)(uintptr_t)ex->rec_gn_shift;
+  L.w_param = s.w->pw; L.b_param = s.w->pb; L.bias_in_film = s.bias_in_film ? 1 : 0;
+  if (s.film) { L.film = (uint64_t)(uintptr_t)ex->film; L.film_off = (int)(s.film - ex->film); L.film_bs = s.film_bs; }
+  L.resid = (uint64_t)(uintptr_t)s.resid; L.resid_ld = s.resid_ld;
+  L.out = (uint64_t)(uintptr_t)s.out.p; L.out_ld = s.out.C; L.Cout = s.w->cout; L.out_dtype = s.out.st;
+  ex->layers.push_back(L);
+  return DSX_OK;
+}
+
+static int plan_conv_ops(dsx_exec* ex, const ConvSpec& s) {
   const PlanKnobs& k = ex->knobs;
   ex->pending_gn_pf.reset();
   ConvArgs a{};
@@ -998,7 +1042,10 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
       conv_first_applicable(ks, stride, a, s.gn != nullptr)) {
     ex->launches++;
     a.wpack = s.w->pack_first;
-    if (s.want_stats) a.stat_part = plan_fused_stats(ex, s.out, (a.Ho >> 4) * (a.Wo >> 4) * 4, a.Cout);
+    if (s.want_stats) {
+      a.stat_part = plan_fused_stats(ex, s.out, (a.Ho >> 4) * (a.Wo >> 4) * 4, a.Cout);
+      ex->stats[s.out.id].piv = StatPivot{a.bias, nullptr, 0};   // the kernel sums x - bias
+    }
     if (ex->sizing) return DSX_OK;
     add_op(ex, DSX_OP_CONV_MFMA, fmt("conv3x3 %d->%d @%dx%d first", (int)cin, a.Cout, a.Ho, a.Wo), flops, bytes,
            [=](hipStream_t st) { return launch_conv_first(dtype, a, st); });
@@ -1011,12 +1058,13 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
       plan_stats(ex, s.x0);
       if (s.x1.C) plan_stats(ex, s.x1);
       const StatInfo& s0 = ex->stats[s.x0.id];
-      a.gn_part0 = s0.part; a.gn_nchunk0 = s0.nchunk; a.gn_pf32_0 = s0.f32 ? 1 : 0;
+      a.gn_part0 = s0.part; a.gn_nchunk0 = s0.nchunk; a.gn_pf32_0 = s0.f32 ? 1 : 0; a.gn_piv0 = s0.piv;
       if (s.x1.C) {
         const StatInfo& s1 = ex->stats[s.x1.id];
-        a.gn_part1 = s1.part; a.gn_nchunk1 = s1.nchunk; a.gn_pf32_1 = s1.f32 ? 1 : 0;
+        a.gn_part1 = s1.part; a.gn_nchunk1 = s1.nchunk; a.gn_pf32_1 = s1.f32 ? 1 : 0; a.gn_piv1 = s1.piv;
       }
       a.gn_gamma = s.gn->gamma; a.gn_beta = s.gn->beta; a.gn_groups = ex->m->cfg.norm_groups; a.gn_eps = 1e-5f;
+      ex->rec_gn_in_kernel = 1;
     }
     if (s.want_stats) a.stat_part = plan_fused_stats(ex, s.out, 1, a.Cout);
     if (ex->sizing) return DSX_OK;
@@ -1053,6 +1101,7 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
     float *sc = nullptr, *sh = nullptr;
     plan_gn(ex, *s.gn, s.x0, s.x1.C ? &s.x1 : nullptr, &sc, &sh);
     a.gn_scale = sc; a.gn_shift = sh;
+    ex->rec_gn_scale = sc; ex->rec_gn_shift = sh;
   }
   ex->launches++;
   if (k.fuse_stats && s.want_stats && mfma_ok && (use_ws ? conv_ws_fuses_stats(tile) : conv_tile_fuses_stats(tile)) &&
@@ -1063,8 +1112,10 @@ static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
   if (mfma_ok && a.ksplit > 1) {
     slab = (float*)ws_alloc(ex, (size_t)a.ksplit * a.slab_stride * sizeof(float));
     ex->launches++;
-    if (k.fuse_stats && s.want_stats && a.Cout % 64 == 0 && a.out_ld == a.Cout && (a.Ho * a.Wo) % 16 == 0)
+    if (k.fuse_stats && s.want_stats && a.Cout % 64 == 0 && a.out_ld == a.Cout && (a.Ho * a.Wo) % 16 == 0) {
       reduce_stats = plan_fused_stats(ex, s.out, a.Ho * a.Wo / 16, a.Cout);   // statistics in the reduce launch
+      ex->stats[s.out.id].piv = StatPivot{a.bias, a.film, a.film_bs};         // shifted by bias + film
+    }
   }
   const bool host_fin = s.host_fin && k.host_fin && use_ws;   // (shapes only: the sizing pass arms it too, plan_gn counts launches)
   if (host_fin) ex->fin_host_armed = true;
@@ -1208,6 +1259,8 @@ static void plan_gn(dsx_exec* ex, const GnW& g, const Tensor& t0, const Tensor* 
   a.part1 = t1 ? ex->stats[t1->id].part : nullptr; a.C1 = t1 ? t1->C : 0;
   a.nchunk1 = t1 ? ex->stats[t1->id].nchunk : 0;
   a.f32_1 = (t1 && ex->stats[t1->id].f32) ? 1 : 0;
+  a.piv0 = ex->stats[t0.id].piv;
+  if (t1) a.piv1 = ex->stats[t1->id].piv;
   a.B = ex->B; a.groups = ex->m->cfg.norm_groups; a.count = (double)t0.H * t0.W;
   a.gamma = g.gamma; a.beta = g.beta; a.eps = 1e-5f;
   a.scale = *scale; a.shift = *shift;
@@ -1269,8 +1322,15 @@ static int plan_res(dsx_exec* ex, const Module& md, const Tensor& x0, const Tens
     g.B = B; g.L = L; g.C = C; g.div = sqrtf((float)C); g.inv_div = 1.0f / g.div;
     const double esz = qkv.st ? 2.0 : 4.0;
     const bool col_split = ex->knobs.attn_cs == 2;
+    const int op0 = (int)ex->op_info.size();
     add_op(ex, DSX_OP_ATTN_GEMM, fmt("attn fused L=%d d=%d", L, C), 4.0 * B * L * (double)L * C,
            B * esz * 4.0 * L * C, [=](hipStream_t st) { return launch_attn(g, col_split, st); });
+    dsx_layer_info li = new_layer(ex, DSX_LAYER_ATTN, op0);
+    li.Hs = li.Ho = H; li.Ws = li.Wo = W; li.C0 = li.C1 = C; li.src_dtype = qkv.st;
+    li.src0 = (uint64_t)(uintptr_t)g.q; li.src1 = (uint64_t)(uintptr_t)g.k; li.resid = (uint64_t)(uintptr_t)g.v;
+    li.ld = g.ld;
+    li.out = (uint64_t)(uintptr_t)av.p; li.out_ld = C; li.Cout = C; li.out_dtype = av.st;
+    ex->layers.push_back(li);
   }
   Tensor o2 = new_tensor(ex, C, H, W);
   ConvSpec co{};
@@ -1290,6 +1350,7 @@ static int build_plan(dsx_exec* ex) {
   ex->pending_gn_pf.reset();
   ex->op_info.clear();
   ex->stats.clear();
+  ex->layers.clear();
   ex->launches = 0;
   const int B = ex->B;
   ex->step_ctr = (int*)ws_alloc(ex, 256);
@@ -1302,6 +1363,23 @@ static int build_plan(dsx_exec* ex) {
   ex->in_x = new_tensor(ex, ex->x_c, ex->H, ex->W);
   ex->x_state = ex->in_x.st ? (float*)ws_alloc(ex, (size_t)B * ex->H * ex->W * ex->x_c * sizeof(float))
                               : (float*)ex->in_x.p;
+  if (!ex->sizing) {
+    if (ex->film) {
+      dsx_layer_info L = new_layer(ex, DSX_LAYER_FILM, 0);
+      L.op_main = -1;
+      L.film = L.out = (uint64_t)(uintptr_t)ex->film; L.film_bs = L.Cout = L.out_ld = m->F;
+      ex->layers.push_back(L);
+    }
+    for (const Tensor* t : {&ex->in_cond, &ex->in_x}) {
+      if (!t->C) continue;
+      dsx_layer_info L = new_layer(ex, DSX_LAYER_INPUT, 0);
+      L.op_main = -1;
+      L.Ho = L.Hs = ex->H; L.Wo = L.Ws = ex->W;
+      L.C0 = t == &ex->in_x ? ex->cond_c : 0;
+      L.out = (uint64_t)(uintptr_t)t->p; L.Cout = L.out_ld = t->C; L.out_dtype = t->st;
+      ex->layers.push_back(L);
+    }
+  }
   std::vector<Tensor> feats;
   Tensor x;
   int rc;
@@ -1452,6 +1530,19 @@ extern "C" int dsx_exec_handoff_timeouts(dsx_exec* ex, unsigned* count) {
 extern "C" int dsx_exec_num_launches(const dsx_exec* ex) { return ex ? ex->launches : 0; }
 
 extern "C" int dsx_exec_num_ops(const dsx_exec* ex) { return ex ? (int)ex->ops.size() : 0; }
+extern "C" int dsx_exec_num_layers(const dsx_exec* ex) { return ex ? (int)ex->layers.size() : 0; }
+extern "C" int dsx_exec_layer_info(const dsx_exec* ex, int i, dsx_layer_info* info) {
+  if (!ex || !info || i < 0 || i >= (int)ex->layers.size()) return fail(DSX_ERR_INVALID, "bad layer index");
+  *info = ex->layers[i];
+  return DSX_OK;
+}
+extern "C" int dsx_exec_copy_workspace(const dsx_exec* ex, uint64_t src, size_t bytes, void* dst, void* stream) {
+  if (!ex || !dst) return fail(DSX_ERR_INVALID, "null argument");
+  const uint64_t lo = (uint64_t)(uintptr_t)ex->ws, hi = lo + ex->ws_bytes;
+  if (!ex->ws || src < lo || src > hi || bytes > hi - src) return fail(DSX_ERR_INVALID, "range is not inside the workspace");
+  HIP_TRY(hipMemcpyAsync(dst, (const void*)(uintptr_t)src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return DSX_OK;
+}
 extern "C" int dsx_exec_op_info(const dsx_exec* ex, int i, char* desc, int cap, int* kind, double* flops,
                                 double* bytes) {
   if (!ex || i < 0 || i >= (int)ex->op_info.size()) return fail(DSX_ERR_INVALID, "bad op index");

@@ -240,6 +240,64 @@ class UNetEngine:
             out.append(desc.value.decode())
         return out
 
+    def layer_table(self, B, H, W, cond_channels=0):
+        """The plan's layer table (dsx_exec_layer_info) with the recorded tensors copied out of the workspace: call it
+        after a forward of this geometry.  One dict per layer: the dsx_layer_info fields, `desc` (the description of
+        its conv / attention launch), the param names, and torch tensors in their storage dtype -- `x0`, `x1`
+        (B, Hs, Ws, C), `gn_scale` / `gn_shift` (B, C0 + C1), `film` (B, Cout), `resid` (B, Ho, Wo, Cout), `out`
+        (B, Ho, Wo, Cout); attention: `q`, `k`, `v`, `out` (B, L, C).  Absent entries are None."""
+        ex = self.executor(B, H, W, cond_channels)
+        descs = self.op_descriptions(B, H, W, cond_channels)
+        st = _stream_ptr()
+        dts = {_lib.DTYPE_F32: torch.float32, _lib.DTYPE_BF16: torch.bfloat16, _lib.DTYPE_F16: torch.float16}
+        info = _lib.LayerInfo()
+
+        def fetch(addr, shape, dtype, ld=None):
+            """rows of `shape[-1]` elements at pitch `ld` (whole rows are copied, then sliced)"""
+            if not addr:
+                return None
+            ld = ld or shape[-1]
+            n = 1
+            for s in shape[:-1]:
+                n *= s
+            t = torch.empty(n * ld, dtype=dtype, device="cuda")
+            check(lib.dsx_exec_copy_workspace(ex, addr, (n * ld - ld + shape[-1]) * t.element_size(),
+                                              C.c_void_p(t.data_ptr()), st))
+            return t.view(n, ld)[:, :shape[-1]].reshape(shape)
+
+        out = []
+        for i in range(int(lib.dsx_exec_num_layers(ex))):
+            check(lib.dsx_exec_layer_info(ex, i, C.byref(info)))
+            d = {name: getattr(info, name) for name, _ in _lib.LayerInfo._fields_}
+            d["desc"] = descs[d["op_main"]] if d["op_main"] >= 0 else ""
+            for key in ("w_param", "b_param", "gn_gamma_param", "gn_beta_param"):
+                d[key.replace("param", "name")] = self.param_names[d[key]] if d[key] >= 0 else None
+            sdt, odt, b = dts[d["src_dtype"]], dts[d["out_dtype"]], d["B"]
+            kind = d["kind"]
+            if kind == _lib.LAYER_CONV:
+                d["x0"] = fetch(d["src0"], (b, d["Hs"], d["Ws"], d["C0"]), sdt)
+                d["x1"] = fetch(d["src1"], (b, d["Hs"], d["Ws"], d["C1"]), sdt) if d["C1"] else None
+                cin = d["C0"] + d["C1"]
+                d["gn_scale"] = fetch(d["gn_scale"], (b, cin), torch.float32)
+                d["gn_shift"] = fetch(d["gn_shift"], (b, cin), torch.float32)
+                d["film"] = (fetch(d["film"], (b, d["film_bs"]), torch.float32)[:, d["film_off"]:d["film_off"] + d["Cout"]]
+                             if d["film"] else None)
+                d["resid"] = fetch(d["resid"], (b, d["Ho"], d["Wo"], d["Cout"]), sdt, d["resid_ld"])
+                d["out"] = fetch(d["out"], (b, d["Ho"], d["Wo"], d["Cout"]), odt, d["out_ld"])
+            elif kind == _lib.LAYER_ATTN:
+                L, c = d["Ho"] * d["Wo"], d["C0"]
+                d["q"] = fetch(d["src0"], (b, L, c), sdt, d["ld"])
+                d["k"] = fetch(d["src1"], (b, L, c), sdt, d["ld"])
+                d["v"] = fetch(d["resid"], (b, L, c), sdt, d["ld"])
+                d["out"] = fetch(d["out"], (b, L, c), odt, d["out_ld"])
+            elif kind == _lib.LAYER_FILM:
+                d["out"] = fetch(d["out"], (b, d["Cout"]), torch.float32)
+            else:
+                d["out"] = fetch(d["out"], (b, d["Ho"], d["Wo"], d["Cout"]), odt)
+            out.append(d)
+        torch.cuda.current_stream().synchronize()
+        return out
+
     def forward(self, x, time=None, cond_channels=0):
         """denoise_fn(x, t): x (B,Cin,H,W) fp32 cuda NCHW -> (B,Cout,H,W)."""
         if not x.is_cuda or x.dtype != torch.float32:

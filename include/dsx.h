@@ -142,6 +142,38 @@ int dsx_exec_time_kind(dsx_exec* ex, int kind, int iters, float* ms_per_replay, 
 /* diagnostics: in-kernel phase stamps (s_memtime) of the conv launch selected by DSX_STAMP_OP */
 int dsx_exec_read_stamps(dsx_exec* ex, unsigned long long* out128);
 
+/* Layer table (verification): what each layer of the plan reads and writes, recorded by the planning pass; the plan
+ * itself is unaffected.  The workspace is never reused, so after one dsx_unet_forward every address below still holds
+ * that forward's value and a test can recompute each layer from the kernels' own inputs.  Addresses are device
+ * addresses inside the workspace (0 = absent); tensors are NHWC in their storage type (DSX_DTYPE_*) with row pitch
+ * `*_ld` elements per pixel; per-channel vectors (gn_scale / gn_shift [B][C0 + C1], film [B][film_bs]) are fp32.
+ *   CONV  : out = conv(act(cat(src0, src1))) + bias + film + resid; act = GroupNorm (gn_scale / gn_shift, or inside
+ *           the kernel when gn_in_kernel) then Swish if `swish`; `up`: nearest x2 in front of the conv.
+ *   ATTN  : out[B][L][C] (ld C) = softmax(q k^T / sqrt(C)) v, q / k / v rows of pitch `ld` (q = src0, k = src1,
+ *           v = resid).
+ *   FILM  : out = the [B][film_bs] FiLM vector of every ResnetBlock (conv1's bias folded in where bias_in_film).
+ *   INPUT : out = channels [C0, C0 + Cout) of the network input, staged (B, Ho, Wo, Cout) in the storage type. */
+enum { DSX_LAYER_CONV = 0, DSX_LAYER_ATTN = 1, DSX_LAYER_FILM = 2, DSX_LAYER_INPUT = 3 };
+typedef struct dsx_layer_info {
+  int32_t kind;                       /* DSX_LAYER_* */
+  int32_t op_begin, op_end, op_main;  /* ops [op_begin, op_end) of dsx_exec_op_info compute it; op_main: its conv /
+                                         attention launch */
+  int32_t ks, stride, up, swish;
+  int32_t B, Hs, Ws, Ho, Wo;
+  int32_t C0, C1, src_dtype;          /* sources (attention: C0 = C1 = head dimension, L = Ho * Wo) */
+  int32_t gn_gamma_param, gn_beta_param, gn_in_kernel;     /* -1: no GroupNorm */
+  int32_t w_param, b_param, bias_in_film;                  /* dsx_model_param_info indices, -1: none */
+  int32_t film_off, film_bs;                               /* film + film_off: this layer's [B] x Cout slice */
+  int32_t resid_ld, out_ld, Cout, out_dtype, ld;           /* ld: attention q / k / v pitch */
+  int32_t reserved;
+  uint64_t src0, src1, gn_scale, gn_shift, film, resid, out;
+} dsx_layer_info;
+int dsx_exec_num_layers(const dsx_exec* ex);
+int dsx_exec_layer_info(const dsx_exec* ex, int index, dsx_layer_info* info);
+/* Copies `bytes` from device address `src` (which must lie inside the workspace) to the caller's device buffer `dst`
+ * on `stream`. */
+int dsx_exec_copy_workspace(const dsx_exec* ex, uint64_t src, size_t bytes, void* dst_dev, void* stream);
+
 /* One UNet forward: replaces denoise_fn(x, t)
  * (sr3 unet.py:235-259 / ddpm unet.py:220-243).
  *   x_nchw_dev : (B, in_channel, H, W) fp32, NCHW as the reference passes it

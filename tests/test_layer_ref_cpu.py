@@ -1,0 +1,199 @@
+"""The per-layer checker of tests/test_gpu_layers.py, checked on the CPU: it must accept a kernel-like result (fp32
+accumulation, fp32 activation rounded to the operand type) and reject each of the small, localised mistakes a conv or
+attention kernel makes.  The simulated kernel below rounds with its own bit-level code (pack_conv's f2bf), not with
+layer_ref's, so a wrong rounding in the reference makes the acceptance tests fail."""
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import layer_ref
+
+DT = {"bf16": torch.bfloat16, "f32": torch.float32}
+
+
+def f2bf_np(x):
+    """fp32 -> bf16 round to nearest even, bit-level (pack_conv's f2bf), returned as fp32"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32)
+
+
+def trunc_bf_np(x):
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)
+    return u.view(np.float32)
+
+
+def op_round(t32, dt, trunc=False):
+    """fp32 torch tensor -> operand type (simulated kernel), as fp32"""
+    if dt == "f32":
+        return t32
+    f = trunc_bf_np if trunc else f2bf_np
+    return torch.from_numpy(f(t32.numpy()).reshape(t32.shape))
+
+
+def make_layer(dt, cin, seed, B=2, H=8, W=8, cout=32):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((B, H, W, cin), generator=g) * 1.5 + 0.3
+    x = torch.from_numpy(f2bf_np(x.numpy()).reshape(x.shape)) if dt == "bf16" else x
+    w = torch.randn((cout, cin, 3, 3), generator=g) / math.sqrt(9 * cin)
+    bias = 0.1 * torch.randn((cout,), generator=g)
+    film = 0.2 * torch.randn((B, cout), generator=g)
+    sc = (0.5 + torch.rand((B, cin), generator=g)).float()
+    sh = (0.3 * torch.randn((B, cin), generator=g)).float()
+    layer = dict(ks=3, stride=1, up=False, swish=True, x0=x.to(DT[dt]), x1=None, gn_scale=sc, gn_shift=sh,
+                 film=film, resid=None)
+    return layer, w, bias
+
+
+def simulate(layer, w, bias, dt, trunc_w=False, a_hook=None, y_hook=None, pad_mode="zeros"):
+    """what the kernel computes: fp32 activation, operands rounded to T, fp32 accumulation, fp32 epilogue, one store"""
+    x = layer["x0"].float().permute(0, 3, 1, 2)
+    t = x * layer["gn_scale"][:, :, None, None] + layer["gn_shift"][:, :, None, None]
+    a = op_round(t * torch.sigmoid(t), dt)
+    if a_hook:
+        a = a_hook(a)
+    wr = op_round(w.float(), dt, trunc_w)
+    if pad_mode == "zeros":
+        y = F.conv2d(a, wr, padding=1)
+    else:
+        y = F.conv2d(F.pad(a, (1, 1, 1, 1), mode=pad_mode), wr)
+    y = y + bias[None, :, None, None] + layer["film"][:, :, None, None]
+    if y_hook:
+        y = y_hook(y, a, wr)
+    out = dict(layer)
+    out["out"] = y.permute(0, 2, 3, 1).contiguous().to(DT[dt])
+    return out
+
+
+def verdict(layer, w, bias, dt):
+    return layer_ref.check_conv(layer, w, bias, torch.ones(1), None, 1, DT[dt], where="synthetic")
+
+
+CASES = [(dt, cin) for dt in ("bf16", "f32") for cin in (64, 1024)]
+
+
+@pytest.mark.parametrize("dt,cin", CASES)
+def test_accepts_kernel_like_result(dt, cin):
+    layer, w, bias = make_layer(dt, cin, seed=cin)
+    v = verdict(simulate(layer, w, bias, dt), w, bias, dt)
+    assert v.ok, v.message()
+    # the bound is tight: the real error uses a visible part of it
+    assert v.ratio > (0.1 if dt == "bf16" else 0.002), v.ratio
+
+
+@pytest.mark.parametrize("dt,cin", CASES)
+def test_rejects_one_dropped_tap(dt, cin):
+    layer, w, bias = make_layer(dt, cin, seed=1 + cin)
+
+    def drop(y, a, wr):                    # output pixel (1, 4, 5) misses tap (0, 0), i.e. input pixel (3, 4)
+        y = y.clone()
+        y[1, :, 4, 5] -= wr[:, :, 0, 0] @ a[1, :, 3, 4]
+        return y
+    v = verdict(simulate(layer, w, bias, dt, y_hook=drop), w, bias, dt)
+    assert not v.ok and v.index[0] == 1 and v.index[2:] == (4, 5), v.message()
+
+
+@pytest.mark.parametrize("dt,cin", CASES)
+def test_rejects_channels_swapped_inside_a_16_byte_unit(dt, cin):
+    layer, w, bias = make_layer(dt, cin, seed=2 + cin)
+    unit = 8 if dt == "bf16" else 4
+    c = unit * 3 + 1                        # channels c, c + 1 of one unit
+
+    def swap(a):
+        a = a.clone()
+        a[:, [c, c + 1]] = a[:, [c + 1, c]]
+        return a
+    v = verdict(simulate(layer, w, bias, dt, a_hook=swap), w, bias, dt)
+    assert not v.ok, v.message()
+
+
+@pytest.mark.parametrize("dt,cin", CASES)
+def test_rejects_halo_tap_from_the_neighbouring_pixel(dt, cin):
+    layer, w, bias = make_layer(dt, cin, seed=3 + cin)
+    good = simulate(layer, w, bias, dt)
+    bad = simulate(layer, w, bias, dt, pad_mode="replicate")    # the zero padding read as the edge pixel
+    out = good["out"].clone()
+    out[0, 0, 3] = bad["out"][0, 0, 3]                          # at one border pixel only
+    good["out"] = out
+    v = verdict(good, w, bias, dt)
+    assert not v.ok and v.index[0] == 0 and v.index[2:] == (0, 3), v.message()
+
+
+@pytest.mark.parametrize("dt,cin", CASES)
+def test_rejects_film_from_the_wrong_channel(dt, cin):
+    layer, w, bias = make_layer(dt, cin, seed=4 + cin)
+    wrong = dict(layer)
+    f = layer["film"].clone()
+    f[:, 5] = layer["film"][:, 6]
+    wrong["film"] = f
+    sim = simulate(wrong, w, bias, dt)
+    sim["film"] = layer["film"]                  # the checker knows the right vector
+    v = verdict(sim, w, bias, dt)
+    assert not v.ok and v.index[1] == 5, v.message()
+
+
+@pytest.mark.parametrize("cin", [64, 1024])
+def test_rejects_weights_truncated_to_bf16(cin):
+    layer, w, bias = make_layer("bf16", cin, seed=5 + cin)
+    v = verdict(simulate(layer, w, bias, "bf16", trunc_w=True), w, bias, "bf16")
+    assert not v.ok and v.aggregate, v.message()
+
+
+# ------------------------------------------------------------------------------------------------ attention
+def make_attention(dt, seed, B=2, L=96, C=64):
+    g = torch.Generator().manual_seed(seed)
+    q, k, v = (torch.randn((B, L, C), generator=g) for _ in range(3))
+    q = q * 2.0                                   # a peaked softmax, as after GroupNorm with learnt scales
+    if dt == "bf16":
+        q, k, v = (torch.from_numpy(f2bf_np(t.numpy()).reshape(t.shape)) for t in (q, k, v))
+    return q, k, v
+
+
+def simulate_attention(q, k, v, dt, drop=None):
+    s = (q @ k.transpose(-1, -2)) / math.sqrt(q.shape[-1])
+    if drop is not None:
+        b, row, key = drop
+        s[b, row, key] = -float("inf")
+    m = s.max(-1, keepdim=True).values
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    o = (op_round(p, dt) @ v) / l
+    return o.to(DT[dt])
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f32"])
+def test_attention_accepts_and_rejects_a_dropped_key(dt):
+    q, k, v = make_attention(dt, seed=11)
+    layer = dict(q=q.to(DT[dt]), k=k.to(DT[dt]), v=v.to(DT[dt]), out=simulate_attention(q, k, v, dt))
+    ok = layer_ref.check_attention(layer, DT[dt], where="attn")
+    assert ok.ok, ok.message()
+    s = q[1, 17] @ k[1].T
+    key = int(torch.argmax(s))                    # the row's heaviest key is lost
+    layer["out"] = simulate_attention(q, k, v, dt, drop=(1, 17, key))
+    bad = layer_ref.check_attention(layer, DT[dt], where="attn")
+    assert not bad.ok and bad.index[:2] == (1, 17), bad.message()
+
+
+def test_gn_stats_checker_accepts_exact_and_rejects_a_missing_tile():
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn((2, 16, 16, 32), generator=g) * 0.7 + 2.0
+    gamma, beta = 1 + 0.1 * torch.randn(32, generator=g), 0.1 * torch.randn(32, generator=g)
+    groups = 8
+
+    def stats(xs):
+        xx = xs.permute(0, 3, 1, 2).double().reshape(2, groups, -1)
+        mu, var = xx.mean(-1), xx.var(-1, unbiased=False)
+        r = 1 / torch.sqrt(var + 1e-5)
+        sc = gamma.double() * r.repeat_interleave(4, 1)
+        return sc.float(), (beta.double() - mu.repeat_interleave(4, 1) * sc).float()
+    sc, sh = stats(x)
+    layer = dict(x0=x, x1=None, gn_scale=sc, gn_shift=sh)
+    v1, v2, _ = layer_ref.check_gn_stats(layer, gamma, beta, groups, torch.float32)
+    assert v1.ok and v2.ok, (v1.message(), v2.message())
+    sc2, sh2 = stats(x[:, :, 4:])                 # one 16 x 4 strip of pixels left out of the sums
+    layer.update(gn_scale=sc2, gn_shift=sh2)
+    v1, v2, _ = layer_ref.check_gn_stats(layer, gamma, beta, groups, torch.float32)
+    assert not (v1.ok and v2.ok)
