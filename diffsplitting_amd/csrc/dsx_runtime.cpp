@@ -10,7 +10,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -89,6 +88,7 @@ struct PlanKnobs {
   int attn_cs = 2;           // DSX_ATTN_CS: 2 = two attention workgroups per query tile on few-tile launches, 1 = one
   int stamp_op = -1;         // DSX_STAMP_OP=<conv ordinal>[,<block>]: in-kernel phase stamps of that launch (-DDSX_STAMPS)
   int stamp_block = 0;
+  std::string plan_dump;     // DSX_PLAN_DUMP=<path>: every planning pass writes its launches there (dump_plan); empty = off
   int ablate = 0;            // DSX_ABLATE (-DDSX_DIAG builds only): timing experiments, results are wrong when non-zero
   // tile preference lists (TILE_* indices, "0,2,3,4"): the first that fills the chip wins
   std::vector<int> tiles_wide{TILE_128x128, TILE_64x128, TILE_64x64};              // DSX_TILES_WIDE
@@ -149,6 +149,7 @@ static PlanKnobs read_plan_knobs() {
     if (const char* v = getenv(e.name)) k.*e.field = tile_order(v, k.*e.field);
   const char* impl = getenv("DSX_CONV_IMPL");
   k.conv_naive = impl && !strcmp(impl, "naive");
+  if (const char* path = getenv("DSX_PLAN_DUMP")) k.plan_dump = path;
   if (const char* se = getenv("DSX_STAMP_OP")) {
     const char* comma = strchr(se, ',');
     k.stamp_op = atoi(se);
@@ -712,11 +713,22 @@ struct StatInfo {          // GroupNorm partial sums of one tensor, produced at 
   StatPivot piv{nullptr, nullptr, 0};   // fp32 partials shifted by this pivot (k_conv_first, split-K reduce)
 };
 
-struct OpInfo {            // what one launch of the plan computes (for profiling / roofline)
-  int kind;                // DSX_OP_*
+// One launch of the plan as plain data: what it computes (for profiling / roofline), which launch_* function takes
+// it and every argument of that call.  launch_op() is the only place that turns one into a launch.
+enum Launcher { L_CONV_FIRST, L_CONV_IMG, L_CONV_WS, L_CONV_MFMA, L_SPLITK_REDUCE, L_CONV_NAIVE, L_CHAN_STATS,
+                L_GN_FINALIZE, L_ATTN };
+struct ChanStatsArgs { const void* x; int xbf, B, HW, C, nchunk; double* part; };   // the parameters of launch_chan_stats
+struct PlanOp {
+  int kind = 0;            // DSX_OP_*
   std::string desc;
-  double flops;            // algorithmic 2*MAC
-  double bytes;            // algorithmic HBM bytes: inputs + outputs + weights, each once
+  double flops = 0;        // algorithmic 2*MAC
+  double bytes = 0;        // algorithmic HBM bytes: inputs + outputs + weights, each once
+  Launcher launcher = L_CONV_MFMA;
+  int dtype = 0, tile = 0, ks = 0, stride = 0, col_split = 0;   // scalar launch parameters (a launcher reads the ones it takes)
+  union Args {             // the member `launcher` names
+    ConvArgs conv; SplitKReduceArgs reduce; NaiveConvArgs naive; ChanStatsArgs stats; GnFinArgs fin; AttnArgs attn;
+    Args() { memset((void*)this, 0, sizeof *this); }
+  } args;
 };
 
 }  // namespace
@@ -728,21 +740,14 @@ struct dsx_exec {
   char* ws = nullptr;
   size_t ws_bytes = 0, ws_used = 0;
   bool sizing = true;
-  std::vector<std::function<hipError_t(hipStream_t)>> ops;  // the UNet forward
-  std::vector<OpInfo> op_info;                               // parallel to ops
+  std::vector<PlanOp> ops;     // the UNet forward (recorded by the planning pass only)
   int conv_ordinal = 0;
-  bool overflow = false;
-  // L2 weight prefetch (l2_prefetch in dsx_kernels.h): the k_gn_finalize launch planned for the conv being planned,
-  // and the previous image-resident conv, receive the weight slices of that conv (filled in once its kernel and
-  // tiling are known)
-  std::shared_ptr<PrefetchArgs> pending_gn_pf;
-  std::shared_ptr<PrefetchArgs> prev_img_pf;
-  std::shared_ptr<PrefetchArgs> prev_ws_pf;    // slot of the previous k_conv_ws launch: the next conv's weight slices
-  // GroupNorm finalize hosted by the residual 1 x 1 conv in front of it (k_conv_ws loader waves): armed by plan_conv for
-  // the conv plan_res marks, consumed by the plan_gn that follows it immediately.  Shapes only: both planner passes agree.
-  struct HostedFin { bool on = false; GnFinArgs a{}; std::shared_ptr<PrefetchArgs> pf; };
-  std::shared_ptr<HostedFin> fin_host;
-  bool fin_host_armed = false;
+  // Late binding is a write into an earlier element of `ops` (-1: none).  L2 weight prefetch (l2_prefetch in
+  // dsx_kernels.h): the previous image-resident conv and the previous k_conv_ws launch receive the weight slices of a
+  // later conv once its kernel and tiling are known.  GroupNorm finalize hosted by the residual 1 x 1 conv in front of it
+  // (k_conv_ws loader waves): `fin_host_op` is that conv, the next finalize planned writes its arguments there.
+  int prev_img_op = -1, prev_ws_op = -1, fin_host_op = -1;
+  bool fin_host_armed = false;   // both passes (launch count): the next finalize is hosted, it is no launch of its own
   unsigned long long* stamp_buf = nullptr;
   std::vector<StatInfo> stats;
   // fixed buffers
@@ -771,18 +776,54 @@ struct dsx_exec {
   // time predictor head
   float* tp_w = nullptr; float* tp_b = nullptr; float* tp_mask = nullptr;
   int launches = 0;
-  // layer table (dsx_exec_layer_info): recorded by the planning pass only; what plan_conv's kernel branch chose for
-  // the GroupNorm of the layer being planned
-  std::vector<dsx_layer_info> layers;
-  float* rec_gn_scale = nullptr;
-  float* rec_gn_shift = nullptr;
-  int rec_gn_in_kernel = 0;
+  std::vector<dsx_layer_info> layers;   // layer table (dsx_exec_layer_info): recorded by the planning pass only
 };
 
-static void add_op(dsx_exec* ex, int kind, const std::string& desc, double flops, double bytes,
-                   std::function<hipError_t(hipStream_t)> fn) {
-  ex->ops.push_back(std::move(fn));
-  ex->op_info.push_back(OpInfo{kind, desc, flops, bytes});
+static hipError_t launch_op(const PlanOp& o, hipStream_t st) {
+  switch (o.launcher) {
+    case L_CONV_FIRST: return launch_conv_first(o.dtype, o.args.conv, st);
+    case L_CONV_IMG: return launch_conv_img(o.dtype, o.ks, o.args.conv, st);
+    case L_CONV_WS: return launch_conv_ws(o.dtype, o.tile, o.ks, o.args.conv, st);
+    case L_CONV_MFMA: return launch_conv(o.dtype, o.tile, o.ks, o.stride, o.args.conv, st);
+    case L_SPLITK_REDUCE: return launch_splitk_reduce(o.args.reduce, st);
+    case L_CONV_NAIVE: return launch_conv_naive(o.args.naive, st);
+    case L_CHAN_STATS: {
+      const ChanStatsArgs& c = o.args.stats;
+      return launch_chan_stats(c.x, c.xbf, c.B, c.HW, c.C, c.nchunk, c.part, st);
+    }
+    case L_GN_FINALIZE: return launch_gn_finalize(o.args.fin, st);
+    case L_ATTN: return launch_attn(o.args.attn, o.col_split != 0, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+// PlanKnobs::plan_dump: one line per PlanOp, the argument struct of its launcher as hex bytes.  The bytes include the
+// structs' padding (zero with this compiler, not by the language): compare dumps of builds with one compiler and layout.
+static int dump_plan(const dsx_exec* ex) {
+  static const struct { const char* name; size_t bytes; } L[] = {
+      {"conv_first", sizeof(ConvArgs)}, {"conv_img", sizeof(ConvArgs)}, {"conv_ws", sizeof(ConvArgs)},
+      {"conv_mfma", sizeof(ConvArgs)}, {"splitk_reduce", sizeof(SplitKReduceArgs)}, {"conv_naive", sizeof(NaiveConvArgs)},
+      {"chan_stats", sizeof(ChanStatsArgs)}, {"gn_finalize", sizeof(GnFinArgs)}, {"attn", sizeof(AttnArgs)}};
+  FILE* f = fopen(ex->knobs.plan_dump.c_str(), "w");
+  if (!f) return fail(DSX_ERR_INVALID, "DSX_PLAN_DUMP: cannot write %s", ex->knobs.plan_dump.c_str());
+  for (size_t i = 0; i < ex->ops.size(); ++i) {
+    const PlanOp& o = ex->ops[i];
+    fprintf(f, "%zu kind=%d desc=\"%s\" flops=%.17g bytes=%.17g launcher=%s dtype=%d tile=%d ks=%d stride=%d col_split=%d args=",
+            i, o.kind, o.desc.c_str(), o.flops, o.bytes, L[o.launcher].name, o.dtype, o.tile, o.ks, o.stride, o.col_split);
+    const unsigned char* p = (const unsigned char*)&o.args;
+    for (size_t b = 0; b < L[o.launcher].bytes; ++b) fprintf(f, "%02x", p[b]);
+    fputc('\n', f);
+  }
+  fclose(f);
+  return DSX_OK;
+}
+
+// appends a launch to the plan and returns its index (the caller fills in the scalar parameters and `args`)
+static int add_op(dsx_exec* ex, int kind, const std::string& desc, double flops, double bytes, Launcher launcher) {
+  PlanOp op;
+  op.kind = kind; op.desc = desc; op.flops = flops; op.bytes = bytes; op.launcher = launcher;
+  ex->ops.push_back(op);
+  return (int)ex->ops.size() - 1;
 }
 static std::string fmt(const char* f, ...) {
   char buf[256];
@@ -797,7 +838,6 @@ static char* ws_alloc(dsx_exec* ex, size_t bytes) {
   size_t off = (ex->ws_used + 255) & ~(size_t)255;
   ex->ws_used = off + bytes;
   if (ex->sizing) return nullptr;
-  if (ex->ws_used > ex->ws_bytes) ex->overflow = true;   // sizing and planning passes diverged: reported by build_plan
   return ex->ws + off;
 }
 // activations are stored in the MFMA operand type (bf16 build: bf16); `f32` forces fp32 (network output)
@@ -856,14 +896,45 @@ static bool g2_geometry(int tile, const ConvArgs& a, ConvArgs& g) {
   return conv_g2_lds_bytes(tile, g) != 0;
 }
 
-// choose tile + geometry (+ split-K) for one conv; returns false if no MFMA config fits.
+namespace {
+// Everything a planning decision about one conv may depend on: integers and booleans, no pointer.  Both planner passes
+// build the same ConvShape, so they decide alike by construction.
+struct ConvShape {
+  int B, Hs, Ws, Ho, Wo, C0, C1, Cout, ks, stride;
+  bool up, swish, has_gn, has_resid, has_film;
+  int resid_ld, out_ld;
+  int out_st;              // storage kind of the output
+  int kchunks, nblocks;
+  bool want_stats;         // a GroupNorm will read the output
+  bool may_host_fin;       // plan_res: a residual 1 x 1 conv whose block's second GroupNorm has fused statistics
+  bool has_naive;          // the model carries the plain direct-conv weights (read off a pointer of the model, which
+                           // is the same in both passes: not a workspace address)
+};
+enum ConvKernel { CONV_FIRST, CONV_IMG, CONV_WS, CONV_MFMA, CONV_MFMA_G2, CONV_SPLITK, CONV_NAIVE };
+enum StatSource { STATS_NONE, STATS_EPILOGUE, STATS_REDUCE };   // who produces the output's GroupNorm partial sums
+enum PivotKind { PIVOT_NONE, PIVOT_BIAS, PIVOT_BIAS_FILM };     // what they are shifted by (StatPivot)
+// What decide_conv chose.  plan_conv reserves and emits from this alone.
+struct ConvChoice {
+  ConvKernel kernel;
+  int tile;                // TILE_* of the MFMA kernels, -1 otherwise
+  ConvArgs geo;            // every pointer member null: the shape, the tile geometry, ws_cpg / lds_row, the split-K
+                           // slicing and (CONV_WS) the ws_map / workgroups-per-N / fastdiv block
+  StatSource stats;
+  int stat_nchunk;         // rows per image of the partial sums
+  PivotKind pivot;
+  bool gn_in_kernel;       // the kernel finalizes the GroupNorm in front of it (no scale / shift, no finalize launch)
+  bool hosts_fin;          // its loader waves run the next GroupNorm finalize
+};
+}  // namespace
+
+// tile + geometry (+ split-K) of one MFMA conv; returns false if no MFMA config fits.
 // Pass 0: the warp-specialised persistent kernel: the widest tile (least re-staging of the activations per output
 //         channel) that still gives >= ws_min_grid work items.
 // Pass 1: the first tile of the preference list whose plain grid fills the chip.
 // Pass 2: small-M layers — the first tile of the split list, K split across workgroups
 //         (slabs + a reduce launch) until the grid fills the chip.
 // Narrow outputs (<= 32 channels) go to the two-chunk variant of k_conv_mfma first (PlanKnobs::narrow_g2).
-static bool pick_conv(const PlanKnobs& k, int dtype, int ks, int stride, ConvArgs& a, int& tile_out) {
+static bool decide_tile(const PlanKnobs& k, int dtype, int ks, int stride, bool ws_allowed, ConvArgs& a, int& tile_out) {
   const bool is_wide = a.Cout > 64;
   const int kgroups = a.kchunks / conv_chunk_multiple(ks);
   ConvArgs c;
@@ -873,7 +944,7 @@ static bool pick_conv(const PlanKnobs& k, int dtype, int ks, int stride, ConvArg
     for (int tile : k.tiles_narrow_g2)
       if (g2_geometry(tile, a, c)) { a = c; tile_out = tile; return true; }
   }
-  if (k.ws && (ks != 1 || k.ws_1x1) && stride == 1 && a.stage_mode == 0) {
+  if (ws_allowed) {
     const std::vector<int>& ws_wide =
         ks == 1 ? ((a.has_gn || a.swish) ? k.tiles_ws_wide_1x1 : k.tiles_ws_wide_1x1_raw) : k.tiles_ws_wide;
     for (int tile : (is_wide ? ws_wide : k.tiles_ws_narrow)) {
@@ -913,6 +984,145 @@ static bool pick_conv(const PlanKnobs& k, int dtype, int ks, int stride, ConvArg
   return true;
 }
 
+// workgroups per N tile of a k_conv_ws launch (whole XCD groups per N tile, see the kernel)
+static int ws_wg_per_n(const ConvArgs& a) {
+  int wpn = std::min(a.m_tiles, std::max(1, 256 / std::max(1, a.n_tiles)));
+  if (a.n_tiles <= 8 && 8 % a.n_tiles == 0) {
+    const int unit = 8 / a.n_tiles;
+    wpn = std::max(unit, wpn / unit * unit);
+    if (wpn > a.m_tiles) wpn = (a.m_tiles + unit - 1) / unit * unit;
+  }
+  return wpn;
+}
+
+// k_conv_ws, chunks per (tile, group) item: several 64-byte chunks where the geometry allows it (PlanKnobs::ws_g2, ws_c4)
+static void decide_ws_chunks(const PlanKnobs& k, int dtype, int ks, int tile, ConvArgs& a) {
+  auto take = [&](bool wanted, int cpg, int lds_row) {
+    ConvArgs t = a;
+    t.ws_cpg = cpg; t.lds_row = lds_row;
+    if (wanted && conv_ws_lds_bytes(dtype, tile, ks, t) != 0) { a.ws_cpg = cpg; a.lds_row = lds_row; }
+  };
+  if (ks == 3) {
+    const int min_chunks = conv_tile_info(tile).BM == 64 ? k.ws_g2_min64 : k.ws_g2_min128;
+    take(k.ws_g2 && a.kchunks >= min_chunks, 2, conv_lds_row_g2(a.tw_log2));
+    take(k.ws_g2 && a.kchunks >= k.ws_g4_min64, 4, conv_lds_row_3x3_c(a.tw_log2, 4));
+  }
+  if (ks == 1) take(k.ws_c4 && a.kchunks >= k.ws_c4_min, 4, conv_lds_row_1x1_c4(a.tw_log2));   // 128 input channels per item
+}
+
+// k_conv_ws, blockIdx -> work mapping and its division-free start-up: quotients and fastdiv magics (ConvArgs::ws_map)
+static int decide_ws_startup(const PlanKnobs& k, int ks, ConvArgs& w) {
+  w.xcd_bands = k.xcd_bands;
+  w.ws_wg_per_n = ws_wg_per_n(w);
+  // 1 x 1 convs with several N tiles: an XCD takes every N tile of its M tiles (PlanKnobs::ws_map3)
+  const bool map3 = k.ws_map3 && ks == 1 && w.n_tiles >= 2 && w.n_tiles <= 32;
+  if (map3) {
+    int wpn3 = std::max(8, (256 / w.n_tiles) / 8 * 8);
+    if (wpn3 > w.m_tiles) wpn3 = (w.m_tiles + 7) / 8 * 8;
+    w.ws_wg_per_n = wpn3;
+  }
+  const int NT = w.n_tiles, wpn = w.ws_wg_per_n, per_img = w.tiles_x * w.tiles_y;
+  w.ws_map = map3 ? 3 : ((NT <= 8 && 8 % NT == 0 && wpn % (8 / NT) == 0) ? 0 : ((NT % 8) == 0 ? 1 : 2));
+  w.ws_nt_log2 = NT <= 8 ? ilog2(NT) : 0;
+  w.ws_per = map3 ? NT : (NT >> 3);
+  w.ws_adv_x = wpn % w.tiles_x; w.ws_adv_y = (wpn / w.tiles_x) % w.tiles_y; w.ws_adv_b = wpn / per_img;
+  const int PW = ((1 << w.tw_log2) - 1) + ks;                       // stride 1
+  const int upg = 4 * (w.ws_cpg ? w.ws_cpg : conv_chunk_multiple(ks));   // 16-byte units per pixel and group
+  const int pstep = 256 / upg;                                      // loader threads / units per pixel
+  w.ws_dpy = pstep / PW; w.ws_dpx = pstep - w.ws_dpy * PW;
+  w.mg_tiles_x = fastdiv_magic((unsigned)w.tiles_x); w.mg_per_img = fastdiv_magic((unsigned)per_img);
+  w.mg_pw = fastdiv_magic((unsigned)PW); w.mg_wpn = fastdiv_magic((unsigned)wpn);
+  w.mg_per = fastdiv_magic((unsigned)std::max(1, w.ws_per));
+  w.ws_bigdiv = ((long long)w.m_tiles + wpn >= 65536 || w.tiles_x >= 65536 || per_img >= 65536) ? 1 : 0;
+  // the magics are exact for dividends below 65536; check the ones this launch can produce (a few thousand
+  // multiplications per conv at plan time) rather than trust the bound
+  auto exact = [](unsigned d, unsigned magic, unsigned nmax) {
+    for (unsigned n = 0; n <= nmax; ++n) {
+      const unsigned q = magic ? (unsigned)(((unsigned long long)n * magic) >> 32) : n;
+      if (q != n / d) return false;
+    }
+    return true;
+  };
+  const unsigned grid = (unsigned)(NT * wpn);
+  const unsigned nt_max = w.ws_bigdiv ? 0u : (unsigned)(w.m_tiles + wpn);
+  if (!exact((unsigned)w.tiles_x, w.mg_tiles_x, grid) || !exact((unsigned)per_img, w.mg_per_img, grid) ||
+      !exact((unsigned)PW, w.mg_pw, 255u) || !exact((unsigned)wpn, w.mg_wpn, std::max(grid, nt_max)) ||
+      !exact((unsigned)std::max(1, w.ws_per), w.mg_per, grid >> 3))
+    return fail(DSX_ERR_INVALID, "planner: fastdiv magic not exact for conv %dx%d @%dx%d", ks, ks, w.Ho, w.Wo);
+  return DSX_OK;
+}
+
+// Every decision about one conv, from its shape alone: kernel family, tile and geometry, where the GroupNorm statistics
+// of its output come from, who finalizes the GroupNorm in front of it, whether it hosts the next finalize.  It sees no
+// executor, tensor or device address (the geometry helpers get a ConvArgs whose pointers are all null), so the sizing
+// pass and the planning pass cannot decide differently.
+static int decide_conv(const PlanKnobs& k, int dtype, int norm_groups, const ConvShape& s, ConvChoice& ch) {
+  ch = ConvChoice{};
+  ch.tile = -1;
+  ConvArgs& a = ch.geo;
+  a.C0 = s.C0; a.C1 = s.C1;
+  a.B = s.B; a.Hs = s.Hs; a.Ws = s.Ws; a.up = s.up ? 1 : 0;
+  a.Ho = s.Ho; a.Wo = s.Wo;
+  a.swish = s.swish ? 1 : 0;
+  a.has_gn = s.has_gn ? 1 : 0;
+  a.act_bf16 = dtype;   // storage kind of the sources / residual
+  a.out_bf16 = s.out_st;
+  {
+    const int gw = conv_chunk_multiple(s.ks) * (dtype != 0 ? 32 : 16);  // channels per staged group
+    const int um = dtype != 0 ? 7 : 3;                                   // channels per 16-byte unit - 1
+    a.stage_mode = ((a.C0 & um) || (a.C1 & um)) ? 2 : ((a.C1 == 0 || a.C0 % gw == 0) ? 0 : 1);
+  }
+  a.resid_ld = s.resid_ld; a.out_ld = s.out_ld; a.Cout = s.Cout;
+  a.nblocks = s.nblocks; a.kchunks = s.kchunks;
+  const int ks = s.ks, stride = s.stride;
+  // ---- the UNet's first conv (few input channels): im2col-in-K kernel.  (Preserved: this used to test the FiLM
+  // pointer, which is null while sizing; has_film is what the planning pass saw.)
+  if (!k.conv_naive && k.first && !s.has_film && !s.has_resid && conv_first_applicable(ks, stride, a, s.has_gn)) {
+    ch.kernel = CONV_FIRST;
+    if (s.want_stats) { ch.stats = STATS_EPILOGUE; ch.stat_nchunk = (a.Ho >> 4) * (a.Wo >> 4) * 4; ch.pivot = PIVOT_BIAS; }   // the kernel sums x - bias
+    return DSX_OK;
+  }
+  // ---- 8 x 8 maps: the image-resident kernel (GroupNorm finalised in its prologue, statistics in its epilogue).
+  // (Preserved: conv_img_applicable tests `a.resid && (a.resid_ld & 3)` on a pointer that is null here; has_resid
+  // stands for it, as the planning pass saw it.)
+  if (!k.conv_naive && k.img && !(s.has_resid && (s.resid_ld & 3)) &&
+      conv_img_applicable(dtype, ks, stride, a, s.has_gn, norm_groups)) {
+    ch.kernel = CONV_IMG;
+    ch.gn_in_kernel = s.has_gn;
+    if (s.want_stats) { ch.stats = STATS_EPILOGUE; ch.stat_nchunk = 1; }
+    return DSX_OK;
+  }
+  const bool ws_allowed = k.ws && (ks != 1 || k.ws_1x1) && stride == 1 && a.stage_mode == 0;
+  if (k.conv_naive || !decide_tile(k, dtype, ks, stride, ws_allowed, a, ch.tile)) {
+    if (!s.has_naive)
+      return fail(DSX_ERR_INVALID, "no MFMA tile fits conv %dx%d (%dx%d out, B=%d); set DSX_CONV_IMPL=naive", ks, ks,
+                  a.Ho, a.Wo, a.B);
+    ch.kernel = CONV_NAIVE;
+    return DSX_OK;
+  }
+  // (Preserved: k_conv_ws whenever its conditions hold for the tile that was picked, whichever pass of decide_tile
+  // picked it -- so also with fewer than ws_min_grid items when a fallback pass chose the tile and split-K did not apply.)
+  const int tile = ch.tile;
+  const bool use_ws = ws_allowed && a.cpg != 2 && a.ksplit == 1 && conv_ws_lds_bytes(dtype, tile, ks, a) != 0;
+  ch.kernel = a.ksplit > 1 ? CONV_SPLITK : (use_ws ? CONV_WS : (a.cpg == 2 ? CONV_MFMA_G2 : CONV_MFMA));
+  if (use_ws) decide_ws_chunks(k, dtype, ks, tile, a);
+  // (Tried and rejected in round 3, measured: the GroupNorm finalised by the consuming conv's own compute waves during
+  // their start-up wait -- 14 to 22 k_gn_finalize launches fewer, but every such conv started 3-7 us later, the same
+  // or more than the launch it replaced cost inside the captured graph: step +0.4 .. +1.1 %.  DESIGN.md section 4.)
+  if (k.fuse_stats && s.want_stats && (use_ws ? conv_ws_fuses_stats(tile) : conv_tile_fuses_stats(tile)) &&
+      a.ksplit == 1 && a.tb_log2 == 0 && (a.Cout & 15) == 0 && a.out_ld == a.Cout && (a.resid_ld & 7) == 0) {
+    ch.stats = STATS_EPILOGUE;
+    ch.stat_nchunk = a.tiles_x * a.tiles_y * (use_ws ? conv_ws_tile_wm(tile) : conv_tile_wm(tile));
+  }
+  if (a.ksplit > 1 && k.fuse_stats && s.want_stats && a.Cout % 64 == 0 && a.out_ld == a.Cout && (a.Ho * a.Wo) % 16 == 0) {
+    ch.stats = STATS_REDUCE;   // statistics in the reduce launch, shifted by bias + film
+    ch.stat_nchunk = a.Ho * a.Wo / 16;
+    ch.pivot = PIVOT_BIAS_FILM;
+  }
+  ch.hosts_fin = s.may_host_fin && k.host_fin && use_ws;
+  return use_ws ? decide_ws_startup(k, ks, a) : DSX_OK;
+}
+
 struct ConvSpec {
   const ConvW* w;
   Tensor x0, x1;       // x1.p == nullptr / C == 0: single source
@@ -923,25 +1133,33 @@ struct ConvSpec {
   bool has_resid = false;
   bool host_fin = false;     // plan_res: this residual 1 x 1 conv may host the finalize of the block's second GroupNorm
   bool swish = false;
-  const float* film = nullptr; int film_bs = 0;
-  const void* resid = nullptr; int resid_ld = 0;
+  int film_off = -1;         // FiLM vector of the conv: offset into dsx_exec::film (row stride dsx_model::F), -1: none
+  const void* resid = nullptr; int resid_ld = 0;   // (the pointer is null while sizing: decisions read has_resid)
   Tensor out;
   bool want_stats = false;   // a GroupNorm will read `out`: produce its statistics in the epilogue
   bool bias_in_film = false; // the conv bias is already part of the FiLM vector (dsx_model_finalize)
 };
 
-static void plan_stats(dsx_exec* ex, const Tensor& t);
-static void plan_gn(dsx_exec* ex, const GnW& g, const Tensor& t0, const Tensor* t1, float** scale, float** shift);
-
-// workgroups per N tile of a k_conv_ws launch (whole XCD groups per N tile, see the kernel)
-static int ws_wg_per_n(const ConvArgs& a) {
-  int wpn = std::min(a.m_tiles, std::max(1, 256 / std::max(1, a.n_tiles)));
-  if (a.n_tiles <= 8 && 8 % a.n_tiles == 0) {
-    const int unit = 8 / a.n_tiles;
-    wpn = std::max(unit, wpn / unit * unit);
-    if (wpn > a.m_tiles) wpn = (a.m_tiles + unit - 1) / unit * unit;
-  }
-  return wpn;
+// reserves the k_chan_stats partial sums of `t` unless a producer already planned its statistics; true if it did
+static bool reserve_stats(dsx_exec* ex, const Tensor& t) {
+  StatInfo& si = ex->stats[t.id];
+  if (si.planned) return false;
+  int nchunk = std::max(1, 512 / ex->B);
+  nchunk = std::min(nchunk, std::max(1, t.H * t.W / 16));
+  nchunk = std::min(nchunk, 64);
+  si.nchunk = nchunk;
+  si.part = ws_alloc(ex, (size_t)ex->B * nchunk * t.C * 2 * sizeof(double));
+  si.planned = true;
+  si.f32 = false;
+  return true;
+}
+static void emit_stats(dsx_exec* ex, const Tensor& t) {
+  const StatInfo& si = ex->stats[t.id];
+  const int HW = t.H * t.W;
+  const int i = add_op(ex, DSX_OP_GN_STATS, fmt("gn_stats C=%d @%dx%d", t.C, t.H, t.W), 0.0,
+                       (t.st ? 2.0 : 4.0) * ex->B * HW * t.C, L_CHAN_STATS);
+  ChanStatsArgs& c = ex->ops[i].args.stats;
+  c.x = t.p; c.xbf = t.st; c.B = ex->B; c.HW = HW; c.C = t.C; c.nchunk = si.nchunk; c.part = (double*)si.part;
 }
 
 // the GroupNorm partial sums of `t` come from the epilogue of the launch being planned (fp32 rows [B][nchunk][C][2])
@@ -954,305 +1172,10 @@ static float* plan_fused_stats(dsx_exec* ex, const Tensor& t, int nchunk, int C)
   return (float*)si.part;
 }
 
-static dsx_layer_info new_layer(dsx_exec* ex, int kind, int op_begin) {
-  dsx_layer_info L;
-  memset(&L, 0, sizeof L);
-  L.kind = kind;
-  L.op_begin = op_begin; L.op_end = (int)ex->op_info.size(); L.op_main = L.op_end - 1;
-  L.B = ex->B;
-  L.gn_gamma_param = L.gn_beta_param = L.w_param = L.b_param = -1;
-  return L;
-}
-
-static int plan_conv_ops(dsx_exec* ex, const ConvSpec& s);
-
-// plan_conv_ops, plus the layer-table entry of the conv in the planning pass
-static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
-  const int op0 = (int)ex->op_info.size();
-  ex->rec_gn_scale = ex->rec_gn_shift = nullptr;
-  ex->rec_gn_in_kernel = 0;
-  const int rc = plan_conv_ops(ex, s);
-  if (rc || ex->sizing) return rc;
-  dsx_layer_info L = new_layer(ex, DSX_LAYER_CONV, op0);
-  for (int i = L.op_end - 1; i >= op0; --i)
-    if (ex->op_info[i].kind == DSX_OP_CONV_MFMA || ex->op_info[i].kind == DSX_OP_CONV_NAIVE) { L.op_main = i; break; }
-  L.ks = s.w->ks; L.stride = s.stride; L.up = s.up ? 1 : 0; L.swish = s.swish ? 1 : 0;
-  L.Hs = s.x0.H; L.Ws = s.x0.W; L.Ho = s.out.H; L.Wo = s.out.W;
-  L.C0 = s.x0.C; L.C1 = s.x1.C; L.src_dtype = s.x0.st;
-  L.src0 = (uint64_t)(uintptr_t)s.x0.p; L.src1 = s.x1.C ? (uint64_t)(uintptr_t)s.x1.p : 0;
-  if (s.gn) { L.gn_gamma_param = s.gn->pg; L.gn_beta_param = s.gn->pb; }
-  L.gn_in_kernel = ex->rec_gn_in_kernel;
-  L.gn_scale = (uint64_t)(uintptr_t)ex->rec_gn_scale; L.gn_shift = (uint64_t)(uintptr_t)ex->rec_gn_shift;
-  L.w_param = s.w->pw; L.b_param = s.w->pb; L.bias_in_film = s.bias_in_film ? 1 : 0;
-  if (s.film) { L.film = (uint64_t)(uintptr_t)ex->film; L.film_off = (int)(s.film - ex->film); L.film_bs = s.film_bs; }
-  L.resid = (uint64_t)(uintptr_t)s.resid; L.resid_ld = s.resid_ld;
-  L.out = (uint64_t)(uintptr_t)s.out.p; L.out_ld = s.out.C; L.Cout = s.w->cout; L.out_dtype = s.out.st;
-  ex->layers.push_back(L);
-  return DSX_OK;
-}
-
-static int plan_conv_ops(dsx_exec* ex, const ConvSpec& s) {
-  const PlanKnobs& k = ex->knobs;
-  ex->pending_gn_pf.reset();
-  ConvArgs a{};
-  a.src0 = s.x0.p; a.C0 = s.x0.C;
-  a.src1 = s.x1.C ? s.x1.p : nullptr; a.C1 = s.x1.C;
-  a.B = ex->B; a.Hs = s.x0.H; a.Ws = s.x0.W; a.up = s.up ? 1 : 0;
-  a.Ho = s.out.H; a.Wo = s.out.W;
-  a.swish = s.swish ? 1 : 0;
-  a.has_gn = s.gn ? 1 : 0;
-  a.act_bf16 = ex->m->dtype;   // storage kind of the sources / residual
-  a.out_bf16 = s.out.st;
-  {
-    const int gw = conv_chunk_multiple(s.w->ks) * (ex->m->dtype != 0 ? 32 : 16);  // channels per staged group
-    const int um = ex->m->dtype != 0 ? 7 : 3;                                       // channels per 16-byte unit - 1
-    a.stage_mode = ((a.C0 & um) || (a.C1 & um)) ? 2 : ((a.C1 == 0 || a.C0 % gw == 0) ? 0 : 1);
-  }
-  a.wpack = s.w->pack; a.bias = s.bias_in_film ? nullptr : s.w->bias;
-  a.film = s.film; a.film_bs = s.film_bs;
-  a.resid = s.resid; a.resid_ld = s.resid_ld;
-  a.out = s.out.p; a.out_ld = s.out.C; a.Cout = s.w->cout;
-  a.nblocks = s.w->nblocks; a.kchunks = s.w->kchunks;
-  if (a.C0 + a.C1 != s.w->cin) return fail(DSX_ERR_INVALID, "conv channel mismatch");
-  {
-    // the conv kernels address their sources with 32-bit byte offsets (0x80000000 = forced out of bounds, the
-    // zero padding): a source tensor of 2 GiB or more would silently read as zeros
-    const long long esz_src = ex->m->dtype != DSX_DTYPE_F32 ? 2 : 4;
-    const long long src_bytes = (long long)a.B * a.Hs * a.Ws * std::max(a.C0, a.C1) * esz_src;
-    if (src_bytes >= (1LL << 31))
-      return fail(DSX_ERR_INVALID,
-                  "conv source of %lld bytes (B=%d, %dx%d, %d channels) exceeds the 2 GiB the kernels address; "
-                  "use a smaller batch per executor", src_bytes, a.B, a.Hs, a.Ws, std::max(a.C0, a.C1));
-  }
-  const int dtype = ex->m->dtype, ks = s.w->ks, stride = s.stride;
-  const double npix = (double)a.B * a.Ho * a.Wo;
-  const double cin = a.C0 + a.C1;
-  const double flops = 2.0 * npix * a.Cout * cin * ks * ks;
-  const double wbytes = (double)a.Cout * cin * ks * ks * (dtype != 0 ? 2 : 4);
-  const double esz = dtype != 0 ? 2.0 : 4.0;   // activation element size in HBM
-  const double bytes = esz * ((double)a.B * a.Hs * a.Ws * cin + npix * a.Cout * (s.has_resid || s.resid ? 1 : 0)) +
-                       (a.out_bf16 ? 2.0 : 4.0) * npix * a.Cout + wbytes;
-  if (ex->conv_ordinal++ == k.stamp_op) {   // diagnostics: in-kernel phase stamps of this launch
-    a.stamp = (unsigned long long*)ws_alloc(ex, 128 * 8);
-    a.stamp_block = k.stamp_block;
-    ex->stamp_buf = a.stamp;
-  }
-  // ---- the UNet's first conv (few input channels): im2col-in-K kernel
-  if (!k.conv_naive && k.first && !s.film && !s.resid && !s.has_resid &&
-      conv_first_applicable(ks, stride, a, s.gn != nullptr)) {
-    ex->launches++;
-    a.wpack = s.w->pack_first;
-    if (s.want_stats) {
-      a.stat_part = plan_fused_stats(ex, s.out, (a.Ho >> 4) * (a.Wo >> 4) * 4, a.Cout);
-      ex->stats[s.out.id].piv = StatPivot{a.bias, nullptr, 0};   // the kernel sums x - bias
-    }
-    if (ex->sizing) return DSX_OK;
-    add_op(ex, DSX_OP_CONV_MFMA, fmt("conv3x3 %d->%d @%dx%d first", (int)cin, a.Cout, a.Ho, a.Wo), flops, bytes,
-           [=](hipStream_t st) { return launch_conv_first(dtype, a, st); });
-    return DSX_OK;
-  }
-  // ---- 8 x 8 maps: the image-resident kernel (GroupNorm finalised in its prologue, statistics in its epilogue)
-  if (!k.conv_naive && k.img && conv_img_applicable(dtype, ks, stride, a, s.gn != nullptr, ex->m->cfg.norm_groups)) {
-    ex->launches++;
-    if (s.gn) {
-      plan_stats(ex, s.x0);
-      if (s.x1.C) plan_stats(ex, s.x1);
-      const StatInfo& s0 = ex->stats[s.x0.id];
-      a.gn_part0 = s0.part; a.gn_nchunk0 = s0.nchunk; a.gn_pf32_0 = s0.f32 ? 1 : 0; a.gn_piv0 = s0.piv;
-      if (s.x1.C) {
-        const StatInfo& s1 = ex->stats[s.x1.id];
-        a.gn_part1 = s1.part; a.gn_nchunk1 = s1.nchunk; a.gn_pf32_1 = s1.f32 ? 1 : 0; a.gn_piv1 = s1.piv;
-      }
-      a.gn_gamma = s.gn->gamma; a.gn_beta = s.gn->beta; a.gn_groups = ex->m->cfg.norm_groups; a.gn_eps = 1e-5f;
-      ex->rec_gn_in_kernel = 1;
-    }
-    if (s.want_stats) a.stat_part = plan_fused_stats(ex, s.out, 1, a.Cout);
-    if (ex->sizing) return DSX_OK;
-    const PrefetchArgs mine{a.wpack, (unsigned)((size_t)a.kchunks * ks * ks * 2 * 1024), a.nblocks, nullptr};   // one slice per N block
-    if (k.prefetch && ex->prev_img_pf) *ex->prev_img_pf = mine;      // the previous image-resident conv warms the L2s for this one
-    auto pf = std::make_shared<PrefetchArgs>(PrefetchArgs{nullptr, 0u, 0, nullptr});
-    ex->prev_img_pf = pf;
-    add_op(ex, DSX_OP_CONV_MFMA, fmt("conv%dx%d %d->%d @%dx%d img", ks, ks, (int)cin, a.Cout, a.Ho, a.Wo), flops, bytes,
-           [=](hipStream_t st) { ConvArgs b = a; b.pf = *pf; return launch_conv_img(dtype, ks, b, st); });
-    return DSX_OK;
-  }
-  int tile = -1;
-  const bool mfma_ok = !k.conv_naive && pick_conv(k, dtype, ks, stride, a, tile);   // (keyed on a.has_gn, never on pointers)
-  const bool use_ws = mfma_ok && a.cpg != 2 && k.ws && (ks != 1 || k.ws_1x1) && stride == 1 && a.stage_mode == 0 &&
-                      a.ksplit == 1 && conv_ws_lds_bytes(dtype, tile, ks, a) != 0;
-  if (use_ws && ks == 3) {   // several 64-byte chunks per (tile, group) item (PlanKnobs::ws_g2)
-    ConvArgs t2 = a;
-    t2.ws_cpg = 2; t2.lds_row = conv_lds_row_g2(a.tw_log2);
-    const int min_chunks = conv_tile_info(tile).BM == 64 ? k.ws_g2_min64 : k.ws_g2_min128;
-    if (k.ws_g2 && a.kchunks >= min_chunks && conv_ws_lds_bytes(dtype, tile, ks, t2) != 0) { a.ws_cpg = 2; a.lds_row = t2.lds_row; }
-    ConvArgs t4 = a;
-    t4.ws_cpg = 4; t4.lds_row = conv_lds_row_3x3_c(a.tw_log2, 4);
-    if (k.ws_g2 && a.kchunks >= k.ws_g4_min64 && conv_ws_lds_bytes(dtype, tile, ks, t4) != 0) { a.ws_cpg = 4; a.lds_row = t4.lds_row; }
-  }
-  if (use_ws && ks == 1) {   // the same for 1 x 1 convs: four chunks (128 input channels) per item
-    ConvArgs t4 = a;
-    t4.ws_cpg = 4; t4.lds_row = conv_lds_row_1x1_c4(a.tw_log2);
-    if (k.ws_c4 && a.kchunks >= k.ws_c4_min && conv_ws_lds_bytes(dtype, tile, ks, t4) != 0) { a.ws_cpg = 4; a.lds_row = t4.lds_row; }
-  }
-  // (Tried and rejected in round 3, measured: the GroupNorm finalised by the consuming conv's own compute waves during
-  // their start-up wait -- 14 to 22 k_gn_finalize launches fewer, but every such conv started 3-7 us later, the same
-  // or more than the launch it replaced cost inside the captured graph: step +0.4 .. +1.1 %.  DESIGN.md section 4.)
-  if (s.gn) {   // every other kernel takes the per-channel scale / shift a k_gn_finalize launch prepares
-    float *sc = nullptr, *sh = nullptr;
-    plan_gn(ex, *s.gn, s.x0, s.x1.C ? &s.x1 : nullptr, &sc, &sh);
-    a.gn_scale = sc; a.gn_shift = sh;
-    ex->rec_gn_scale = sc; ex->rec_gn_shift = sh;
-  }
-  ex->launches++;
-  if (k.fuse_stats && s.want_stats && mfma_ok && (use_ws ? conv_ws_fuses_stats(tile) : conv_tile_fuses_stats(tile)) &&
-      a.ksplit == 1 && a.tb_log2 == 0 && (a.Cout & 15) == 0 && a.out_ld == a.Cout && (a.resid_ld & 7) == 0)
-    a.stat_part = plan_fused_stats(ex, s.out, a.tiles_x * a.tiles_y * (use_ws ? conv_ws_tile_wm(tile) : conv_tile_wm(tile)), a.Cout);
-  float* slab = nullptr;
-  float* reduce_stats = nullptr;
-  if (mfma_ok && a.ksplit > 1) {
-    slab = (float*)ws_alloc(ex, (size_t)a.ksplit * a.slab_stride * sizeof(float));
-    ex->launches++;
-    if (k.fuse_stats && s.want_stats && a.Cout % 64 == 0 && a.out_ld == a.Cout && (a.Ho * a.Wo) % 16 == 0) {
-      reduce_stats = plan_fused_stats(ex, s.out, a.Ho * a.Wo / 16, a.Cout);   // statistics in the reduce launch
-      ex->stats[s.out.id].piv = StatPivot{a.bias, a.film, a.film_bs};         // shifted by bias + film
-    }
-  }
-  const bool host_fin = s.host_fin && k.host_fin && use_ws;   // (shapes only: the sizing pass arms it too, plan_gn counts launches)
-  if (host_fin) ex->fin_host_armed = true;
-  if (ex->sizing) return DSX_OK;
-  if (mfma_ok) {
-    const ConvTileInfo ti = conv_tile_info(tile);
-    const std::string d = fmt("conv%dx%d%s%s %d->%d @%dx%d tile%dx%d", ks, ks, stride == 2 ? "s2" : "",
-                              a.up ? "up" : "", (int)cin, a.Cout, a.Ho, a.Wo, ti.BM, ti.BN);
-    if (a.ksplit > 1) {
-      ConvArgs p = a;  // slices write raw sums into fp32 slabs; a reduce launch applies the epilogue
-      p.out = slab; p.out_bf16 = 0;
-      SplitKReduceArgs ra{};
-      ra.slab = slab; ra.nsplit = a.ksplit; ra.slab_stride = a.slab_stride;
-      ra.M = (long long)a.B * a.Ho * a.Wo; ra.N = a.Cout; ra.HW = a.Ho * a.Wo;
-      ra.bias = a.bias; ra.film = a.film; ra.film_bs = a.film_bs;
-      ra.resid = a.resid; ra.resid_ld = a.resid_ld; ra.out = a.out; ra.act_bf16 = a.act_bf16;
-      ra.stat_part = reduce_stats;
-      add_op(ex, DSX_OP_CONV_MFMA, d + fmt(" splitK%d", a.ksplit), flops, bytes,
-             [=](hipStream_t st) { return launch_conv(dtype, tile, ks, stride, p, st); });
-      add_op(ex, DSX_OP_SPLITK_REDUCE, fmt("splitk_reduce x%d %d ch @%dx%d", a.ksplit, a.Cout, a.Ho, a.Wo), 0.0,
-             (4.0 * a.ksplit + esz) * (double)ra.M * ra.N,
-             [=](hipStream_t st) { return launch_splitk_reduce(ra, st); });
-    } else {
-      ConvArgs w = a;
-      w.handoff_timeouts = ex->handoff_timeouts;
-      w.xcd_bands = k.xcd_bands;
-      w.ws_wg_per_n = ws_wg_per_n(a);
-      // 1 x 1 convs with several N tiles: an XCD takes every N tile of its M tiles (PlanKnobs::ws_map3)
-      const bool map3 = k.ws_map3 && use_ws && ks == 1 && a.n_tiles >= 2 && a.n_tiles <= 32;
-      if (map3) {
-        int wpn3 = std::max(8, (256 / a.n_tiles) / 8 * 8);
-        if (wpn3 > a.m_tiles) wpn3 = (a.m_tiles + 7) / 8 * 8;
-        w.ws_wg_per_n = wpn3;
-      }
-      {   // division-free start-up of k_conv_ws: quotients and fastdiv magics (see ConvArgs::ws_map)
-        const int NT = a.n_tiles, wpn = w.ws_wg_per_n, per_img = a.tiles_x * a.tiles_y;
-        w.ws_map = map3 ? 3 : ((NT <= 8 && 8 % NT == 0 && wpn % (8 / NT) == 0) ? 0 : ((NT % 8) == 0 ? 1 : 2));
-        w.ws_nt_log2 = NT <= 8 ? ilog2(NT) : 0;
-        w.ws_per = map3 ? NT : (NT >> 3);
-        w.ws_adv_x = wpn % a.tiles_x; w.ws_adv_y = (wpn / a.tiles_x) % a.tiles_y; w.ws_adv_b = wpn / per_img;
-        const int PW = ((1 << a.tw_log2) - 1) + ks;                       // stride 1
-        const int upg = 4 * (a.ws_cpg ? a.ws_cpg : conv_chunk_multiple(ks));   // 16-byte units per pixel and group
-        const int pstep = 256 / upg;                                      // loader threads / units per pixel
-        w.ws_dpy = pstep / PW; w.ws_dpx = pstep - w.ws_dpy * PW;
-        w.mg_tiles_x = fastdiv_magic((unsigned)a.tiles_x); w.mg_per_img = fastdiv_magic((unsigned)per_img);
-        w.mg_pw = fastdiv_magic((unsigned)PW); w.mg_wpn = fastdiv_magic((unsigned)wpn);
-        w.mg_per = fastdiv_magic((unsigned)std::max(1, w.ws_per));
-        w.ws_bigdiv = ((long long)a.m_tiles + wpn >= 65536 || a.tiles_x >= 65536 || per_img >= 65536) ? 1 : 0;
-        // the magics are exact for dividends below 65536; check the ones this launch can produce (a few thousand
-        // multiplications per conv at plan time) rather than trust the bound
-        auto exact = [](unsigned d, unsigned magic, unsigned nmax) {
-          for (unsigned n = 0; n <= nmax; ++n) {
-            const unsigned q = magic ? (unsigned)(((unsigned long long)n * magic) >> 32) : n;
-            if (q != n / d) return false;
-          }
-          return true;
-        };
-        const unsigned grid = (unsigned)(NT * wpn);
-        const unsigned nt_max = w.ws_bigdiv ? 0u : (unsigned)(a.m_tiles + wpn);
-        if (!exact((unsigned)a.tiles_x, w.mg_tiles_x, grid) || !exact((unsigned)per_img, w.mg_per_img, grid) ||
-            !exact((unsigned)PW, w.mg_pw, 255u) || !exact((unsigned)wpn, w.mg_wpn, std::max(grid, nt_max)) ||
-            !exact((unsigned)std::max(1, w.ws_per), w.mg_per, grid >> 3))
-          return fail(DSX_ERR_INVALID, "planner: fastdiv magic not exact for conv %dx%d @%dx%d", ks, ks, a.Ho, a.Wo);
-      }
-      if (use_ws) {
-        // this conv's k_gn_finalize launch pulls the weight slices into the L2 of the XCD group that will read them
-        // (k_conv_ws keys its N tile on blockIdx % 8 in exactly ws_map 0 and 1)
-        const bool keyed = w.ws_map == 0 || w.ws_map == 1;
-        const size_t wblock = (size_t)a.kchunks * ks * ks * 2 * 1024;     // bytes of one 32-channel N block's fragments
-        const PrefetchArgs mine{a.wpack, (unsigned)(wblock * (ti.BN / 32)), a.n_tiles, nullptr};
-        if (k.prefetch && ex->pending_gn_pf && keyed) *ex->pending_gn_pf = mine;
-        // no finalize launch in front (1 x 1 without GroupNorm, upsampling conv): the previous k_conv_ws launch carries it
-        else if (k.prefetch && k.prefetch_ws && ex->prev_ws_pf && keyed) *ex->prev_ws_pf = mine;
-        auto npf = std::make_shared<PrefetchArgs>(PrefetchArgs{nullptr, 0u, 0, nullptr});
-        ex->prev_ws_pf = npf;
-        w.pf = PrefetchArgs{nullptr, 0u, 0, nullptr};
-        if (host_fin) {
-          auto hf = std::make_shared<dsx_exec::HostedFin>();
-          ex->fin_host = hf;
-          add_op(ex, DSX_OP_CONV_MFMA, d + (a.ws_cpg == 4 ? " ws c4 +gn" : " ws +gn"), flops, bytes, [=](hipStream_t st) {
-            ConvArgs b = w;
-            b.pf = *npf;
-            if (hf->on) { b.fin_on = 1; b.fin = hf->a; if (hf->pf) b.fin.pf = *hf->pf; }
-            return launch_conv_ws(dtype, tile, ks, b, st);
-          });
-        } else {
-          add_op(ex, DSX_OP_CONV_MFMA, d + (a.ws_cpg == 2 ? " ws c2" : (a.ws_cpg == 4 ? " ws c4" : " ws")), flops, bytes,
-                 [=](hipStream_t st) { ConvArgs b = w; b.pf = *npf; return launch_conv_ws(dtype, tile, ks, b, st); });
-        }
-      } else {
-        add_op(ex, DSX_OP_CONV_MFMA, a.cpg == 2 ? d + " g2" : d, flops, bytes,
-               [=](hipStream_t st) { return launch_conv(dtype, tile, ks, stride, a, st); });
-      }
-    }
-  } else {
-    if (!s.w->naive)
-      return fail(DSX_ERR_INVALID,
-                  "no MFMA tile fits conv %dx%d (%dx%d out, B=%d); set DSX_CONV_IMPL=naive", ks, ks,
-                  a.Ho, a.Wo, a.B);
-    NaiveConvArgs na{};
-    na.c = a; na.w = s.w->naive; na.ks = ks; na.stride = stride; na.sigmoid_out = 0;
-    add_op(ex, DSX_OP_CONV_NAIVE, fmt("conv%dx%d-naive %d->%d @%dx%d", ks, ks, (int)cin, a.Cout, a.Ho, a.Wo),
-           flops, bytes, [=](hipStream_t st) { return launch_conv_naive(na, st); });
-  }
-  return DSX_OK;
-}
-
-static void plan_stats(dsx_exec* ex, const Tensor& t) {
-  StatInfo& si = ex->stats[t.id];
-  if (si.planned) return;
-  const int HW = t.H * t.W;
-  int nchunk = std::max(1, 512 / ex->B);
-  nchunk = std::min(nchunk, std::max(1, HW / 16));
-  nchunk = std::min(nchunk, 64);
-  si.nchunk = nchunk;
-  si.part = ws_alloc(ex, (size_t)ex->B * nchunk * t.C * 2 * sizeof(double));
-  si.planned = true;
-  si.f32 = false;
-  ex->launches++;
-  if (ex->sizing) return;
-  const void* x = t.p; double* part = (double*)si.part;
-  const int B = ex->B, C = t.C, xbf = t.st;
-  add_op(ex, DSX_OP_GN_STATS, fmt("gn_stats C=%d @%dx%d", C, t.H, t.W), 0.0, (xbf ? 2.0 : 4.0) * B * HW * C,
-         [=](hipStream_t st) { return launch_chan_stats(x, xbf, B, HW, C, nchunk, part, st); });
-}
-
-// GroupNorm over cat(t0, t1) -> device scale/shift [B][C]
-static void plan_gn(dsx_exec* ex, const GnW& g, const Tensor& t0, const Tensor* t1, float** scale, float** shift) {
-  plan_stats(ex, t0);
-  if (t1) plan_stats(ex, *t1);
-  const int C = t0.C + (t1 ? t1->C : 0);
-  *scale = (float*)ws_alloc(ex, (size_t)ex->B * C * sizeof(float));
-  *shift = (float*)ws_alloc(ex, (size_t)ex->B * C * sizeof(float));
-  const bool hosted = ex->fin_host_armed;      // the launch in front is a residual 1 x 1 conv whose loader waves do it
-  ex->fin_host_armed = false;
-  if (!hosted) ex->launches++;
-  if (ex->sizing) return;
+// GroupNorm over cat(t0, t1) -> device scale/shift [B][C]: a k_gn_finalize launch, or (hosted) the arguments of the
+// residual 1 x 1 conv in front that runs it.  Returns the op whose prefetch slot the consuming conv may fill.
+static int emit_gn_finalize(dsx_exec* ex, const GnW& g, const Tensor& t0, const Tensor* t1, float* scale, float* shift,
+                            bool hosted) {
   GnFinArgs a{};
   a.part0 = ex->stats[t0.id].part; a.C0 = t0.C; a.nchunk0 = ex->stats[t0.id].nchunk;
   a.f32_0 = ex->stats[t0.id].f32 ? 1 : 0;
@@ -1263,16 +1186,200 @@ static void plan_gn(dsx_exec* ex, const GnW& g, const Tensor& t0, const Tensor* 
   if (t1) a.piv1 = ex->stats[t1->id].piv;
   a.B = ex->B; a.groups = ex->m->cfg.norm_groups; a.count = (double)t0.H * t0.W;
   a.gamma = g.gamma; a.beta = g.beta; a.eps = 1e-5f;
-  a.scale = *scale; a.shift = *shift;
-  auto pf = std::make_shared<PrefetchArgs>(PrefetchArgs{nullptr, 0u, 0, nullptr});
-  ex->pending_gn_pf = pf;    // plan_conv fills it in once it has chosen the consumer's kernel and tiling
-  if (hosted && ex->fin_host) {
-    ex->fin_host->a = a; ex->fin_host->pf = pf; ex->fin_host->on = true;
-    ex->fin_host.reset();
-    return;
+  a.scale = scale; a.shift = shift;
+  if (hosted && ex->fin_host_op >= 0) {
+    const int host = ex->fin_host_op;
+    ex->fin_host_op = -1;
+    ex->ops[host].args.conv.fin_on = 1;
+    ex->ops[host].args.conv.fin = a;
+    return host;
   }
-  add_op(ex, DSX_OP_GN_FINALIZE, fmt("gn_finalize C=%d", C), 0.0, 0.0,
-         [=](hipStream_t st) { GnFinArgs b = a; b.pf = *pf; return launch_gn_finalize(b, st); });
+  const int i = add_op(ex, DSX_OP_GN_FINALIZE, fmt("gn_finalize C=%d", a.C0 + a.C1), 0.0, 0.0, L_GN_FINALIZE);
+  ex->ops[i].args.fin = a;
+  return i;
+}
+
+static dsx_layer_info new_layer(dsx_exec* ex, int kind, int op_begin) {
+  dsx_layer_info L;
+  memset(&L, 0, sizeof L);
+  L.kind = kind;
+  L.op_begin = op_begin; L.op_end = (int)ex->ops.size(); L.op_main = L.op_end - 1;
+  L.B = ex->B;
+  L.gn_gamma_param = L.gn_beta_param = L.w_param = L.b_param = -1;
+  return L;
+}
+
+// the launches of one conv, from its choice and its bound arguments; `fin_op`: the finalize planned for it (-1: none).
+// Returns the index of the conv launch itself.
+static int emit_conv_ops(dsx_exec* ex, const ConvChoice& ch, const ConvArgs& a, int ks, int stride, int fin_op,
+                         float* slab, float* reduce_stats, const float* naive_w) {
+  const PlanKnobs& k = ex->knobs;
+  const int dtype = ex->m->dtype, tile = ch.tile, cin = a.C0 + a.C1;
+  const double npix = (double)a.B * a.Ho * a.Wo;
+  const double flops = 2.0 * npix * a.Cout * cin * ks * ks;
+  const double esz = dtype != 0 ? 2.0 : 4.0;   // activation element size in HBM
+  const double bytes = esz * ((double)a.B * a.Hs * a.Ws * cin + npix * a.Cout * (a.resid ? 1 : 0)) +
+                       (a.out_bf16 ? 2.0 : 4.0) * npix * a.Cout + (double)a.Cout * cin * ks * ks * esz;
+  auto conv_op = [&](const std::string& desc, Launcher l, const ConvArgs& args) {
+    const int i = add_op(ex, DSX_OP_CONV_MFMA, desc, flops, bytes, l);
+    PlanOp& o = ex->ops[i];
+    o.dtype = dtype; o.tile = tile; o.ks = ks; o.stride = stride; o.args.conv = args;
+    return i;
+  };
+  if (ch.kernel == CONV_FIRST)
+    return conv_op(fmt("conv3x3 %d->%d @%dx%d first", cin, a.Cout, a.Ho, a.Wo), L_CONV_FIRST, a);
+  if (ch.kernel == CONV_IMG) {
+    // the previous image-resident conv warms the L2s for this one: one slice per N block
+    if (k.prefetch && ex->prev_img_op >= 0)
+      ex->ops[ex->prev_img_op].args.conv.pf = PrefetchArgs{a.wpack, (unsigned)((size_t)a.kchunks * ks * ks * 2 * 1024), a.nblocks, nullptr};
+    return ex->prev_img_op = conv_op(fmt("conv%dx%d %d->%d @%dx%d img", ks, ks, cin, a.Cout, a.Ho, a.Wo), L_CONV_IMG, a);
+  }
+  if (ch.kernel == CONV_NAIVE) {
+    const int i = add_op(ex, DSX_OP_CONV_NAIVE, fmt("conv%dx%d-naive %d->%d @%dx%d", ks, ks, cin, a.Cout, a.Ho, a.Wo),
+                         flops, bytes, L_CONV_NAIVE);
+    NaiveConvArgs& na = ex->ops[i].args.naive;
+    na.c = a; na.w = naive_w; na.ks = ks; na.stride = stride; na.sigmoid_out = 0;
+    return i;
+  }
+  const ConvTileInfo ti = conv_tile_info(tile);
+  const std::string d = fmt("conv%dx%d%s%s %d->%d @%dx%d tile%dx%d", ks, ks, stride == 2 ? "s2" : "",
+                            a.up ? "up" : "", cin, a.Cout, a.Ho, a.Wo, ti.BM, ti.BN);
+  if (ch.kernel == CONV_SPLITK) {
+    ConvArgs p = a;  // slices write raw sums into fp32 slabs; a reduce launch applies the epilogue
+    p.out = slab; p.out_bf16 = 0;
+    const int main_op = conv_op(d + fmt(" splitK%d", a.ksplit), L_CONV_MFMA, p);
+    const long long M = (long long)a.B * a.Ho * a.Wo;
+    const int i = add_op(ex, DSX_OP_SPLITK_REDUCE, fmt("splitk_reduce x%d %d ch @%dx%d", a.ksplit, a.Cout, a.Ho, a.Wo), 0.0,
+                         (4.0 * a.ksplit + esz) * (double)M * a.Cout, L_SPLITK_REDUCE);
+    SplitKReduceArgs& ra = ex->ops[i].args.reduce;
+    ra.slab = slab; ra.nsplit = a.ksplit; ra.slab_stride = a.slab_stride;
+    ra.M = M; ra.N = a.Cout; ra.HW = a.Ho * a.Wo;
+    ra.bias = a.bias; ra.film = a.film; ra.film_bs = a.film_bs;
+    ra.resid = a.resid; ra.resid_ld = a.resid_ld; ra.out = a.out; ra.act_bf16 = a.act_bf16;
+    ra.stat_part = reduce_stats;
+    return main_op;
+  }
+  if (ch.kernel != CONV_WS) return conv_op(a.cpg == 2 ? d + " g2" : d, L_CONV_MFMA, a);
+  // this conv's finalize pulls the weight slices into the L2 of the XCD group that will read them (k_conv_ws keys its
+  // N tile on blockIdx % 8 in exactly ws_map 0 and 1); no finalize in front (1 x 1 without GroupNorm, upsampling
+  // conv): the previous k_conv_ws launch carries it
+  const bool keyed = a.ws_map == 0 || a.ws_map == 1;
+  const size_t wblock = (size_t)a.kchunks * ks * ks * 2 * 1024;     // bytes of one 32-channel N block's fragments
+  const PrefetchArgs mine{a.wpack, (unsigned)(wblock * (ti.BN / 32)), a.n_tiles, nullptr};
+  if (k.prefetch && fin_op >= 0 && keyed) {
+    PlanOp& f = ex->ops[fin_op];
+    (f.launcher == L_GN_FINALIZE ? f.args.fin.pf : f.args.conv.fin.pf) = mine;
+  } else if (k.prefetch && k.prefetch_ws && ex->prev_ws_op >= 0 && keyed) {
+    ex->ops[ex->prev_ws_op].args.conv.pf = mine;
+  }
+  const char* cpg = a.ws_cpg == 4 ? " ws c4" : ((a.ws_cpg == 2 && !ch.hosts_fin) ? " ws c2" : " ws");
+  ex->prev_ws_op = conv_op(d + cpg + (ch.hosts_fin ? " +gn" : ""), L_CONV_WS, a);
+  if (ch.hosts_fin) ex->fin_host_op = ex->prev_ws_op;
+  return ex->prev_ws_op;
+}
+
+static ConvShape conv_shape(const dsx_exec* ex, const ConvSpec& s) {
+  ConvShape h{};
+  h.B = ex->B; h.Hs = s.x0.H; h.Ws = s.x0.W; h.Ho = s.out.H; h.Wo = s.out.W;
+  h.C0 = s.x0.C; h.C1 = s.x1.C; h.Cout = s.w->cout; h.ks = s.w->ks; h.stride = s.stride;
+  h.up = s.up; h.swish = s.swish; h.has_gn = s.gn != nullptr; h.has_resid = s.has_resid; h.has_film = s.film_off >= 0;
+  h.resid_ld = s.resid_ld; h.out_ld = s.out.C; h.out_st = s.out.st;
+  h.kchunks = s.w->kchunks; h.nblocks = s.w->nblocks;
+  h.want_stats = s.want_stats; h.may_host_fin = s.host_fin; h.has_naive = s.w->naive != nullptr;
+  return h;
+}
+
+// One conv of the plan: decide (from the shape alone), reserve (every workspace byte of this conv, both passes), emit
+// (planning pass only: the launches and the layer-table entry, from the choice and the addresses just reserved).
+static int plan_conv(dsx_exec* ex, const ConvSpec& s) {
+  const PlanKnobs& k = ex->knobs;
+  const ConvShape shape = conv_shape(ex, s);
+  if (shape.C0 + shape.C1 != s.w->cin) return fail(DSX_ERR_INVALID, "conv channel mismatch");
+  {
+    // the conv kernels address their sources with 32-bit byte offsets (0x80000000 = forced out of bounds, the
+    // zero padding): a source tensor of 2 GiB or more would silently read as zeros
+    const long long esz_src = ex->m->dtype != DSX_DTYPE_F32 ? 2 : 4;
+    const long long src_bytes = (long long)shape.B * shape.Hs * shape.Ws * std::max(shape.C0, shape.C1) * esz_src;
+    if (src_bytes >= (1LL << 31))
+      return fail(DSX_ERR_INVALID,
+                  "conv source of %lld bytes (B=%d, %dx%d, %d channels) exceeds the 2 GiB the kernels address; "
+                  "use a smaller batch per executor", src_bytes, shape.B, shape.Hs, shape.Ws, std::max(shape.C0, shape.C1));
+  }
+  ConvChoice ch;
+  if (int rc = decide_conv(k, ex->m->dtype, ex->m->cfg.norm_groups, shape, ch)) return rc;
+
+  // ---- reserve: all workspace of this conv, in this order in both passes
+  ConvArgs a = ch.geo;
+  if (ex->conv_ordinal++ == k.stamp_op) {   // diagnostics: in-kernel phase stamps of this launch
+    a.stamp = (unsigned long long*)ws_alloc(ex, 128 * 8);
+    a.stamp_block = k.stamp_block;
+    ex->stamp_buf = a.stamp;
+  }
+  const Tensor* x1 = s.x1.C ? &s.x1 : nullptr;
+  bool new_stats0 = false, new_stats1 = false;
+  float *gn_scale = nullptr, *gn_shift = nullptr;
+  bool fin_hosted = false;
+  if (s.gn) {   // statistics of the sources no producer fused; every kernel but k_conv_img takes a finalized scale / shift
+    new_stats0 = reserve_stats(ex, s.x0);
+    if (x1) new_stats1 = reserve_stats(ex, *x1);
+    if (!ch.gn_in_kernel) {
+      gn_scale = (float*)ws_alloc(ex, (size_t)ex->B * (shape.C0 + shape.C1) * sizeof(float));
+      gn_shift = (float*)ws_alloc(ex, (size_t)ex->B * (shape.C0 + shape.C1) * sizeof(float));
+      fin_hosted = ex->fin_host_armed;     // the launch in front is a residual 1 x 1 conv whose loader waves do it
+      ex->fin_host_armed = false;
+    }
+  }
+  if (ch.stats == STATS_EPILOGUE) a.stat_part = plan_fused_stats(ex, s.out, ch.stat_nchunk, a.Cout);
+  float* slab = ch.kernel == CONV_SPLITK ? (float*)ws_alloc(ex, (size_t)a.ksplit * a.slab_stride * sizeof(float)) : nullptr;
+  float* reduce_stats = ch.stats == STATS_REDUCE ? plan_fused_stats(ex, s.out, ch.stat_nchunk, a.Cout) : nullptr;
+  ex->launches += (new_stats0 ? 1 : 0) + (new_stats1 ? 1 : 0) + ((s.gn && !ch.gn_in_kernel && !fin_hosted) ? 1 : 0) + 1 +
+                  (ch.kernel == CONV_SPLITK ? 1 : 0);
+  if (ch.hosts_fin) ex->fin_host_armed = true;
+  // the addresses the choice leaves open (null while sizing)
+  a.src0 = s.x0.p; a.src1 = x1 ? x1->p : nullptr;
+  a.wpack = ch.kernel == CONV_FIRST ? s.w->pack_first : s.w->pack;
+  a.bias = s.bias_in_film ? nullptr : s.w->bias;
+  if (s.film_off >= 0 && !ex->sizing) { a.film = ex->film + s.film_off; a.film_bs = ex->m->F; }
+  a.resid = s.resid; a.out = s.out.p;
+  a.gn_scale = gn_scale; a.gn_shift = gn_shift;
+  if (ch.kernel == CONV_WS) a.handoff_timeouts = ex->handoff_timeouts;
+  if (ch.pivot == PIVOT_BIAS) ex->stats[s.out.id].piv = StatPivot{a.bias, nullptr, 0};
+  if (ch.pivot == PIVOT_BIAS_FILM) ex->stats[s.out.id].piv = StatPivot{a.bias, a.film, a.film_bs};
+  if (ex->sizing) return DSX_OK;
+
+  // ---- emit
+  const int op0 = (int)ex->ops.size();
+  if (new_stats0) emit_stats(ex, s.x0);
+  if (new_stats1) emit_stats(ex, *x1);
+  int fin_op = -1;
+  if (s.gn && ch.gn_in_kernel) {
+    const StatInfo& s0 = ex->stats[s.x0.id];
+    a.gn_part0 = s0.part; a.gn_nchunk0 = s0.nchunk; a.gn_pf32_0 = s0.f32 ? 1 : 0; a.gn_piv0 = s0.piv;
+    if (x1) {
+      const StatInfo& s1 = ex->stats[x1->id];
+      a.gn_part1 = s1.part; a.gn_nchunk1 = s1.nchunk; a.gn_pf32_1 = s1.f32 ? 1 : 0; a.gn_piv1 = s1.piv;
+    }
+    a.gn_gamma = s.gn->gamma; a.gn_beta = s.gn->beta; a.gn_groups = ex->m->cfg.norm_groups; a.gn_eps = 1e-5f;
+  } else if (s.gn) {
+    fin_op = emit_gn_finalize(ex, *s.gn, s.x0, x1, gn_scale, gn_shift, fin_hosted);
+  }
+  const int main_op = emit_conv_ops(ex, ch, a, shape.ks, shape.stride, fin_op, slab, reduce_stats, s.w->naive);
+
+  dsx_layer_info L = new_layer(ex, DSX_LAYER_CONV, op0);
+  L.op_main = main_op;
+  L.ks = shape.ks; L.stride = s.stride; L.up = s.up ? 1 : 0; L.swish = s.swish ? 1 : 0;
+  L.Hs = s.x0.H; L.Ws = s.x0.W; L.Ho = s.out.H; L.Wo = s.out.W;
+  L.C0 = s.x0.C; L.C1 = s.x1.C; L.src_dtype = s.x0.st;
+  L.src0 = (uint64_t)(uintptr_t)s.x0.p; L.src1 = x1 ? (uint64_t)(uintptr_t)x1->p : 0;
+  if (s.gn) { L.gn_gamma_param = s.gn->pg; L.gn_beta_param = s.gn->pb; }
+  L.gn_in_kernel = ch.gn_in_kernel ? 1 : 0;
+  L.gn_scale = (uint64_t)(uintptr_t)gn_scale; L.gn_shift = (uint64_t)(uintptr_t)gn_shift;
+  L.w_param = s.w->pw; L.b_param = s.w->pb; L.bias_in_film = s.bias_in_film ? 1 : 0;
+  if (s.film_off >= 0) { L.film = (uint64_t)(uintptr_t)ex->film; L.film_off = s.film_off; L.film_bs = ex->m->F; }
+  L.resid = (uint64_t)(uintptr_t)s.resid; L.resid_ld = s.resid_ld;
+  L.out = (uint64_t)(uintptr_t)s.out.p; L.out_ld = s.out.C; L.Cout = s.w->cout; L.out_dtype = s.out.st;
+  ex->layers.push_back(L);
+  return DSX_OK;
 }
 
 static int plan_res(dsx_exec* ex, const Module& md, const Tensor& x0, const Tensor* x1, Tensor& y) {
@@ -1282,7 +1389,7 @@ static int plan_res(dsx_exec* ex, const Module& md, const Tensor& x0, const Tens
   ConvSpec c1{};
   c1.w = &md.conv1; c1.x0 = x0; if (x1) c1.x1 = *x1;
   c1.gn = &md.gn1; c1.swish = true;
-  if (md.film_off >= 0 && !ex->sizing) { c1.film = ex->film + md.film_off; c1.film_bs = ex->m->F; }
+  c1.film_off = md.film_off;
   c1.bias_in_film = md.film_off >= 0 && md.conv1.pb >= 0;
   c1.out = h; c1.want_stats = true;
   if ((rc = plan_conv(ex, c1))) return rc;
@@ -1292,7 +1399,7 @@ static int plan_res(dsx_exec* ex, const Module& md, const Tensor& x0, const Tens
     ConvSpec cr{};
     cr.w = &md.res; cr.x0 = x0; if (x1) cr.x1 = *x1; cr.out = r;
     // the hosted finalize reads h's GroupNorm partial sums: only when conv1's epilogue produced them (fused statistics;
-    // both planner passes agree, `planned` is set from shapes).  Otherwise c2's plan_gn adds a k_chan_stats launch
+    // `planned` follows from conv1's ConvChoice).  Otherwise c2 adds a k_chan_stats launch
     // AFTER this conv and the finalize must stay behind it as a launch of its own.
     cr.host_fin = ex->stats[h.id].planned;
     if ((rc = plan_conv(ex, cr))) return rc;
@@ -1304,7 +1411,7 @@ static int plan_res(dsx_exec* ex, const Module& md, const Tensor& x0, const Tens
   c2.w = &md.conv2; c2.x0 = h; c2.gn = &md.gn2; c2.swish = true;
   c2.resid = r.p; c2.resid_ld = md.cout; c2.has_resid = true; c2.out = o; c2.want_stats = true;
   if ((rc = plan_conv(ex, c2))) return rc;
-  ex->fin_host_armed = false; ex->fin_host.reset();
+  ex->fin_host_armed = false; ex->fin_host_op = -1;
   if (!md.attn) { y = o; return DSX_OK; }
   // SelfAttention (unet.py:113-142)
   const int C = md.cout, L = H * W, B = ex->B;
@@ -1321,10 +1428,10 @@ static int plan_res(dsx_exec* ex, const Module& md, const Tensor& x0, const Tens
     g.out = av.p; g.ldo = C; g.storage = qkv.st;
     g.B = B; g.L = L; g.C = C; g.div = sqrtf((float)C); g.inv_div = 1.0f / g.div;
     const double esz = qkv.st ? 2.0 : 4.0;
-    const bool col_split = ex->knobs.attn_cs == 2;
-    const int op0 = (int)ex->op_info.size();
-    add_op(ex, DSX_OP_ATTN_GEMM, fmt("attn fused L=%d d=%d", L, C), 4.0 * B * L * (double)L * C,
-           B * esz * 4.0 * L * C, [=](hipStream_t st) { return launch_attn(g, col_split, st); });
+    const int op0 = add_op(ex, DSX_OP_ATTN_GEMM, fmt("attn fused L=%d d=%d", L, C), 4.0 * B * L * (double)L * C,
+                           B * esz * 4.0 * L * C, L_ATTN);
+    ex->ops[op0].col_split = ex->knobs.attn_cs == 2 ? 1 : 0;
+    ex->ops[op0].args.attn = g;
     dsx_layer_info li = new_layer(ex, DSX_LAYER_ATTN, op0);
     li.Hs = li.Ho = H; li.Ws = li.Wo = W; li.C0 = li.C1 = C; li.src_dtype = qkv.st;
     li.src0 = (uint64_t)(uintptr_t)g.q; li.src1 = (uint64_t)(uintptr_t)g.k; li.resid = (uint64_t)(uintptr_t)g.v;
@@ -1345,10 +1452,8 @@ static int build_plan(dsx_exec* ex) {
   ex->ws_used = 0;
   ex->ops.clear();
   ex->conv_ordinal = 0;
-  ex->prev_img_pf.reset();
-  ex->prev_ws_pf.reset();
-  ex->pending_gn_pf.reset();
-  ex->op_info.clear();
+  ex->prev_img_op = ex->prev_ws_op = ex->fin_host_op = -1;
+  ex->fin_host_armed = false;
   ex->stats.clear();
   ex->layers.clear();
   ex->launches = 0;
@@ -1427,8 +1532,33 @@ static int build_plan(dsx_exec* ex) {
   }
   ex->out = x;
   if (ex->out.st) return fail(DSX_ERR_STATE, "internal error: the network output must be an fp32 tensor");
-  if (ex->overflow)
-    return fail(DSX_ERR_STATE, "internal error: the planning pass needs more workspace than the sizing pass reserved");
+  return ex->knobs.plan_dump.empty() ? DSX_OK : dump_plan(ex);
+}
+
+// Both planner passes.  The sizing pass walks the plan without a workspace and records no launch; the planning pass
+// walks it again over the workspace: `fake_base` (dsx_plan_dry_run: an address that is never dereferenced), or device
+// memory allocated here.  They must reserve exactly the same bytes.
+static int run_planner(dsx_exec* ex, char* fake_base, size_t* sizing_bytes) {
+  ex->sizing = true;
+  int rc = build_plan(ex);
+  const size_t sized = ex->ws_used;
+  if (sizing_bytes) *sizing_bytes = sized;
+  if (rc) return rc;
+  ex->ws_bytes = sized + 4096;
+  ex->ws = fake_base;
+  if (!fake_base) {
+    const hipError_t e = hipMalloc((void**)&ex->ws, ex->ws_bytes);
+    if (e != hipSuccess) {
+      ex->ws = nullptr;
+      return fail(DSX_ERR_HIP, "hipMalloc(%zu) for the activation workspace failed: %s", ex->ws_bytes, hipGetErrorString(e));
+    }
+  }
+  ex->sizing = false;
+  if ((rc = build_plan(ex))) return rc;
+  // ws_used only grows, so a pass that ran past the workspace fails here too.  The dry run (fake base: nothing is ever
+  // written) reports both counts to its caller instead, as include/dsx.h documents.
+  if (!fake_base && ex->ws_used != sized)
+    return fail(DSX_ERR_STATE, "planner: sizing pass reserved %zu bytes, planning pass used %zu", sized, ex->ws_used);
   return DSX_OK;
 }
 
@@ -1443,23 +1573,9 @@ extern "C" int dsx_exec_create(dsx_model* m, int B, int H, int W, int cond_chann
   ex->knobs = read_plan_knobs();
   ex->knobs.conv_naive = m->want_naive;   // the model's device image decides (naive weights exist only then)
   ex->cond_c = cond_channels; ex->x_c = m->cfg.in_channel - cond_channels;
-  ex->sizing = true;
-  int rc = build_plan(ex);
-  if (rc) { delete ex; return rc; }
-  ex->ws_bytes = ex->ws_used + 4096;
-  hipError_t e = hipMalloc((void**)&ex->ws, ex->ws_bytes);
-  if (e != hipSuccess) {
-    delete ex;
-    return fail(DSX_ERR_HIP, "hipMalloc(%zu) for the activation workspace failed: %s", ex->ws_bytes,
-                hipGetErrorString(e));
-  }
-  ex->sizing = false;
-  const size_t sized = ex->ws_used;
-  rc = build_plan(ex);
-  if (rc == DSX_OK && ex->ws_used != sized)
-    rc = fail(DSX_ERR_STATE, "internal error: sizing pass reserved %zu bytes, planning pass used %zu", sized, ex->ws_used);
-  if (rc) { (void)hipFree(ex->ws); delete ex; return rc; }
-  e = hipMemset(ex->step_ctr, 0, 256);
+  const int rc = run_planner(ex, nullptr, nullptr);
+  if (rc) { if (ex->ws) (void)hipFree(ex->ws); delete ex; return rc; }
+  const hipError_t e = hipMemset(ex->step_ctr, 0, 256);
   if (e != hipSuccess) { (void)hipFree(ex->ws); delete ex; return fail(DSX_ERR_HIP, "hipMemset failed"); }
   *out = ex;
   return DSX_OK;
@@ -1485,19 +1601,8 @@ extern "C" int dsx_plan_dry_run(const dsx_unet_cfg* cfg, int dtype, int B, int H
   ex->knobs = read_plan_knobs();
   ex->knobs.conv_naive = m->want_naive;   // the model's device image decides (naive weights exist only then)
   ex->cond_c = cond_channels; ex->x_c = m->cfg.in_channel - cond_channels;
-  ex->sizing = true;
-  rc = build_plan(ex);
-  const size_t sized = ex->ws_used;
-  size_t planned = 0;
-  if (rc == DSX_OK) {
-    ex->sizing = false;
-    ex->ws = (char*)(uintptr_t)0x100000000ull;   // never dereferenced: no launch happens
-    ex->ws_bytes = ~(size_t)0 >> 1;
-    rc = build_plan(ex);
-    planned = ex->ws_used;
-  }
-  if (sizing_bytes) *sizing_bytes = sized;
-  if (planning_bytes) *planning_bytes = planned;
+  rc = run_planner(ex, (char*)(uintptr_t)0x100000000ull, sizing_bytes);   // never dereferenced: no launch happens
+  if (planning_bytes) *planning_bytes = ex->sizing ? 0 : ex->ws_used;
   if (launches) *launches = ex->launches;
   ex->ws = nullptr;
   delete ex;
@@ -1545,8 +1650,8 @@ extern "C" int dsx_exec_copy_workspace(const dsx_exec* ex, uint64_t src, size_t 
 }
 extern "C" int dsx_exec_op_info(const dsx_exec* ex, int i, char* desc, int cap, int* kind, double* flops,
                                 double* bytes) {
-  if (!ex || i < 0 || i >= (int)ex->op_info.size()) return fail(DSX_ERR_INVALID, "bad op index");
-  const OpInfo& o = ex->op_info[i];
+  if (!ex || i < 0 || i >= (int)ex->ops.size()) return fail(DSX_ERR_INVALID, "bad op index");
+  const PlanOp& o = ex->ops[i];
   if (desc && cap > 0) snprintf(desc, cap, "%s", o.desc.c_str());
   if (kind) *kind = o.kind;
   if (flops) *flops = o.flops;
@@ -1562,7 +1667,7 @@ extern "C" int dsx_exec_time_kind(dsx_exec* ex, int kind, int iters, float* ms_p
   // kind >= 0: the launches of that kind; -1: every launch of the forward; <= -2: every launch except kind (-kind - 2)
   auto selected = [&](int k) { return kind >= 0 ? k == kind : (kind == -1 ? true : k != -kind - 2); };
   int n = 0;
-  for (auto& oi : ex->op_info) n += selected(oi.kind) ? 1 : 0;
+  for (auto& op : ex->ops) n += selected(op.kind) ? 1 : 0;
   if (launches) *launches = n;
   if (n == 0) { *ms_per_replay = 0.f; return DSX_OK; }
   hipGraph_t graph = nullptr;
@@ -1571,7 +1676,7 @@ extern "C" int dsx_exec_time_kind(dsx_exec* ex, int kind, int iters, float* ms_p
   HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
   hipError_t err = hipSuccess;
   for (size_t i = 0; i < ex->ops.size() && err == hipSuccess; ++i)
-    if (selected(ex->op_info[i].kind)) err = ex->ops[i](st);
+    if (selected(ex->ops[i].kind)) err = launch_op(ex->ops[i], st);
   hipError_t e2 = hipStreamEndCapture(st, &graph);
   if (err != hipSuccess || e2 != hipSuccess || !graph) {
     if (graph) (void)hipGraphDestroy(graph);
@@ -1615,9 +1720,9 @@ extern "C" int dsx_exec_profile(dsx_exec* ex, int iters, float* ms_per_op, void*
   for (int it = 0; it < iters; ++it) {
     static const bool trace = getenv("DSX_TRACE") != nullptr;   // debugging: name each launch, sync after it
     for (size_t i = 0; i < n; ++i) {
-      if (trace) { fprintf(stderr, "[dsx] op %zu: %s\n", i, ex->op_info[i].desc.c_str()); fflush(stderr); }
+      if (trace) { fprintf(stderr, "[dsx] op %zu: %s\n", i, ex->ops[i].desc.c_str()); fflush(stderr); }
       HIP_TRY(hipEventRecord(ev[2 * i], st));
-      HIP_TRY(ex->ops[i](st));
+      HIP_TRY(launch_op(ex->ops[i], st));
       HIP_TRY(hipEventRecord(ev[2 * i + 1], st));
       if (trace) HIP_TRY(hipStreamSynchronize(st));
     }
@@ -1646,7 +1751,7 @@ static int run_unet(dsx_exec* ex, bool from_table, int n_time, hipStream_t st, i
     t.wf = m->d_wf; t.bf = m->d_bf; t.F = m->F; t.film = ex->film;
     HIP_TRY(launch_temb(t, st));
   }
-  for (auto& op : ex->ops) HIP_TRY(op(st));
+  for (auto& op : ex->ops) HIP_TRY(launch_op(op, st));
   return DSX_OK;
 }
 

@@ -171,3 +171,31 @@ def test_random_shapes_size_and_plan_alike(seed):
         res = json.loads(r.stdout.strip().splitlines()[-1])
         assert not res["bad"], res["bad"][:5]
         assert res["ok"] >= 90, res
+
+
+@pytest.mark.parametrize("name,dt", [("c2_sr3_128_b16", "f32"), ("c2_sr3_128_b16", "bf16"), ("c3_hagen_512_b8", "bf16"),
+                                     ("ragged_48x80_b3", "bf16")])
+def test_plan_ops_match_recorded_plan(name, dt, tmp_path, monkeypatch):
+    """The launches of the plan at default knobs, as DSX_PLAN_DUMP writes them: their (kind, description) sequence --
+    kernel family, tile and chunk variant of every layer, and the launch order -- equals tests/golden/plan_ops.json,
+    recorded from the planner before it was rewritten as decide / reserve / emit.  A planner change that means to
+    alter a plan regenerates the fixture from the dump."""
+    import re
+    from diffsplitting_amd import engine
+    flavour, kw, B, H, W, cc = CONFIGS[name]
+    cfg = engine.make_cfg(flavour, kw["in_channel"], kw["out_channel"], kw["inner_channel"], kw["norm_groups"],
+                          kw["channel_mults"], kw["attn_res"], kw["res_blocks"], kw["image_size"])
+    path = tmp_path / "plan.txt"
+    monkeypatch.setenv("DSX_PLAN_DUMP", str(path))
+    a, b, n = engine.plan_dry_run(cfg, dt, B, H, W, cc)
+    assert a == b
+    ops = []
+    for i, line in enumerate(path.read_text().splitlines()):
+        m = re.match(r'(\d+) kind=(\d+) desc="([^"]*)" flops=\S+ bytes=\S+ launcher=\w+ dtype=\d+ tile=-?\d+ ks=\d+ '
+                     r'stride=\d+ col_split=\d+ args=([0-9a-f]+)$', line)
+        assert m and int(m.group(1)) == i, line[:200]
+        ops.append([int(m.group(2)), m.group(3)])
+    with open(os.path.join(ROOT, "tests", "golden", "plan_ops.json")) as f:
+        want = json.load(f)[f"{name}/{dt}"]
+    assert len(ops) == n == len(want)          # every launch of the plan is one line of the dump
+    assert ops == want
