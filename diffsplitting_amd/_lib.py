@@ -89,6 +89,10 @@ SIGNATURES = {
     "dsx_tile_regions": (_i, [_pi64, _pi64, _pi64, _i, _pi32, _i64]),
     "dsx_tiles_gather": (_i, [_vp, _pi64, _pi64, _pi64, _pi64, _i64, _vp, _vp]),
     "dsx_tiles_gather_norm": (_i, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, _f, _f, C.POINTER(C.c_double), _i, _vp, _vp, _vp]),
+    "dsx_tiles_gather_mix": (_i, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, C.POINTER(C.c_double), C.c_double,
+                                  C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    "dsx_mix_range_blocks": (_i, [_i64, _i]),
+    "dsx_mix_range": (_i, [_vp, _vp, _i64, C.POINTER(C.c_double), _i, _vp, C.POINTER(C.c_double), _vp]),
     "dsx_stitch": (_i, [_vp, _i64, _i, _i, _i, _pi32, _vp, _pi64, _vp]),
     "dsx_stitch_psnr_blocks": (_i, [_i, _i]),
     "dsx_stitch_psnr": (_i, [_vp, _i64, _i, _i, _i, _pi32, _vp, _pi64, _vp, _vp, _vp]),
@@ -101,6 +105,8 @@ SIGNATURES = {
     "dsx_tileplan_regions": (_i, [_vp, _pi32, _i64]),
     "dsx_tileplan_gather": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "dsx_tileplan_gather_norm": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _f, _f, C.POINTER(C.c_double), _i, _vp, _vp, _vp]),
+    "dsx_tileplan_gather_mix": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, C.POINTER(C.c_double), C.c_double,
+                                     C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
     "dsx_tileplan_stitch": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "dsx_tileplan_pack_layout": (_i, [_vp, _i, _pi64, _pi64]),
     "dsx_tileplan_pack": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),

@@ -406,6 +406,20 @@ hipError_t launch_tiles_gather(const float* frames, int H, int W, int ph, int pw
 hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
                                     TileSeq seq, float w0, float w1, const double norm[6], int from_norm_target,
                                     float* tin, float* ttar, hipStream_t st);
+// crop + target normalisation + the two mixed inputs of the TimePredictor evaluation and their min-max-normalised
+// classifier views, fused (op list: include/dsx.h, dsx_tiles_gather_mix).  norm = {mean_t0, std_t0, mean_t1, std_t1};
+// w0 = (float)(1 - t), w1 = (float)t; lo / rng = (float)lo, (float)(hi - lo) of the table rows of the two channels.
+// Any of ttar / tmix / tcls may be nullptr (not all three); each is (count, 2, ph, pw).
+struct MixWeights { float w0, w1, lo0, rng0, lo1, rng1; };
+hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
+                                   TileSeq seq, const double norm[4], const MixWeights& mw, float* ttar, float* tmix,
+                                   float* tcls, hipStream_t st);
+// min / max over all pixels of t * a + (1 - t) * b, t = t_int / n for t_int = 0..n, on the normalised channels
+// (compute_input_normalization_dict, data/time_predictor_dataset.py:6-21), fp64 with every operation rounded on its
+// own.  part[mix_range_blocks(pixels)][n + 1][2] = {min, max} per pixel workgroup; the caller reduces over the rows.
+int mix_range_blocks(long long pixels);
+hipError_t launch_mix_range(const float* f0, const float* f1, long long pixels, const double norm[4], int n, double* part,
+                            hipStream_t st);
 // source of a paste: whole predicted tiles (count, C, ph, pw) of the sequence, or the gathered packed exchange buffer
 // [world][rank_stride] (valid regions [C][h][w] of rank q's tiles q, q + world, ... back to back; `off` = pixel offset
 // of each tile id inside its rank's run)

@@ -528,6 +528,132 @@ hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, int H, int
   return hipGetLastError();
 }
 
+// One IEEE operation each, never contracted into an fma: the pragma takes the `contract` flag off the instruction, and
+// the backend fuses a product into a sum only when both carry it.
+__device__ __forceinline__ float mul_f(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_f(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double mul_d(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double add_d(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// The mixed inputs of the TimePredictor evaluation (notebooks/EvaluateJointIndiIterative.ipynb cells 40/43,
+// time_prediction_evaluation.ipynb cell 4) cut, normalised, mixed and min-max-normalised in one pass; the op list is
+// in include/dsx.h (dsx_tiles_gather_mix).  Channel 0 is indi1's input, channel 1 indi2's.
+struct GatherMixArgs {
+  const float* f0; const float* f1;
+  int H, W, ph, pw;
+  const int* starts;       // dev [..][3], indexed by tile id
+  TileSeq seq;
+  double mt0, st0, mt1, st1;
+  MixWeights mw;
+  float* ttar; float* tmix; float* tcls;   // (count, 2, ph, pw) each, or nullptr
+};
+__global__ void k_tiles_gather_mix(const GatherMixArgs a) {
+  const long long k = blockIdx.y, t = a.seq.first + k * a.seq.stride;
+  const int n = a.starts[t * 3], y0 = a.starts[t * 3 + 1], x0 = a.starts[t * 3 + 2];
+  const int total = a.ph * a.pw;
+  const MixWeights w = a.mw;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int y = i / a.pw, x = i % a.pw;
+    const size_t src = ((size_t)n * a.H + (y0 + y)) * a.W + (x0 + x);
+    const float t0 = (float)(((double)a.f0[src] - a.mt0) / a.st0), t1 = (float)(((double)a.f1[src] - a.mt1) / a.st1);
+    const size_t d0 = (size_t)(k * 2) * total + i, d1 = d0 + total;
+    if (a.ttar) { a.ttar[d0] = t0; a.ttar[d1] = t1; }
+    if (a.tmix || a.tcls) {
+      const float m0 = add_f(mul_f(t0, w.w0), mul_f(t1, w.w1));
+      const float m1 = add_f(mul_f(t1, w.w0), mul_f(t0, w.w1));
+      if (a.tmix) { a.tmix[d0] = m0; a.tmix[d1] = m1; }
+      if (a.tcls) {
+        a.tcls[d0] = add_f(mul_f(2.0f, add_f(m0, -w.lo0)) / w.rng0, -1.0f);
+        a.tcls[d1] = add_f(mul_f(2.0f, add_f(m1, -w.lo1)) / w.rng1, -1.0f);
+      }
+    }
+  }
+}
+hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
+                                   TileSeq seq, const double norm[4], const MixWeights& mw, float* ttar, float* tmix,
+                                   float* tcls, hipStream_t st) {
+  GatherMixArgs a{f0, f1, H, W, ph, pw, starts, seq, norm[0], norm[1], norm[2], norm[3], mw, ttar, tmix, tcls};
+  int gx = (ph * pw + 255) / 256;
+  if (gx > 64) gx = 64;
+  hipLaunchKernelGGL(k_tiles_gather_mix, dim3((unsigned)gx, (unsigned)seq.count), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// The TimePredictor's input range table (compute_input_normalization_dict, data/time_predictor_dataset.py:6-21): for
+// every t_int in 0..n the min and max over all pixels of  t * a + (1 - t) * b,  t = t_int / n,  a, b = the normalised
+// channels -- n + 1 numpy passes over the frame set in the reference, one launch here.  All of it in fp64 with every
+// operation rounded on its own (numpy has no fma), so the table is bitwise numpy's; min / max are exact, the result
+// does not depend on the reduction tree.  fp64-VALU-bound, not HBM-bound: a thread keeps the running min / max of
+// kMixTB values of t in registers (and their weights) while it strides over its workgroup's pixel chunk; the t blocks
+// are blockIdx.x, so the workgroups that re-read a chunk are dispatched together and find it in L2 / MALL.  Wave
+// reduction by shuffles, the four waves through LDS, one partial row per workgroup: part[chunk][t_int][{min, max}].
+constexpr int kMixTB = 8;
+constexpr int kMixMaxChunks = 512;
+__global__ __launch_bounds__(256) void k_mix_range(const float* __restrict__ f0, const float* __restrict__ f1,
+                                                   long long pixels, long long chunk, double m0, double s0, double m1,
+                                                   double s1, int n, double* __restrict__ part) {
+  __shared__ double red[4][kMixTB][2];
+  const int tb = blockIdx.x * kMixTB;
+  double tw[kMixTB], uw[kMixTB], mn[kMixTB], mx[kMixTB];
+#pragma unroll
+  for (int j = 0; j < kMixTB; ++j) {
+    const int ti = min(tb + j, n);             // the rows past n of the last block repeat row n and are not written
+    tw[j] = (double)ti / (double)n;            // IEEE division, as numpy's t_int / n_timesteps
+    uw[j] = 1.0 - tw[j];
+    mn[j] = INFINITY; mx[j] = -INFINITY;
+  }
+  const long long p0 = blockIdx.y * chunk, p1 = min(pixels, p0 + chunk);
+  for (long long p = p0 + threadIdx.x; p < p1; p += 256) {
+    const double a = ((double)f0[p] - m0) / s0, b = ((double)f1[p] - m1) / s1;
+#pragma unroll
+    for (int j = 0; j < kMixTB; ++j) {
+      const double v = add_d(mul_d(tw[j], a), mul_d(uw[j], b));
+      mn[j] = fmin(mn[j], v); mx[j] = fmax(mx[j], v);
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < kMixTB; ++j) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mn[j] = fmin(mn[j], __shfl_xor(mn[j], o, 64)); mx[j] = fmax(mx[j], __shfl_xor(mx[j], o, 64)); }
+    if (lane == 0) { red[wave][j][0] = mn[j]; red[wave][j][1] = mx[j]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < kMixTB * 2) {
+    const int j = threadIdx.x >> 1, kk = threadIdx.x & 1;
+    if (tb + j <= n) {
+      const double r0 = red[0][j][kk], r1 = red[1][j][kk], r2 = red[2][j][kk], r3 = red[3][j][kk];
+      part[((size_t)blockIdx.y * (n + 1) + (tb + j)) * 2 + kk] =
+          kk ? fmax(fmax(r0, r1), fmax(r2, r3)) : fmin(fmin(r0, r1), fmin(r2, r3));
+    }
+  }
+}
+// pixel workgroups (= rows of partials) of a call: about a thousand pixels per workgroup at least, 512 chunks at most
+int mix_range_blocks(long long pixels) {
+  const long long g = (pixels + 1023) / 1024;
+  return (int)(g > kMixMaxChunks ? kMixMaxChunks : (g < 1 ? 1 : g));
+}
+hipError_t launch_mix_range(const float* f0, const float* f1, long long pixels, const double norm[4], int n, double* part,
+                            hipStream_t st) {
+  const int gy = mix_range_blocks(pixels);
+  const long long chunk = (pixels + gy - 1) / gy;
+  hipLaunchKernelGGL(k_mix_range, dim3((unsigned)((n + kMixTB) / kMixTB), (unsigned)gy), dim3(256), 0, st, f0, f1, pixels,
+                     chunk, norm[0], norm[1], norm[2], norm[3], n, part);
+  return hipGetLastError();
+}
+
 // Where the pixels of tile `t` (the k-th of the launch) come from: whole predicted tiles (count, C, ph, pw), or the
 // packed exchange buffer of tiled multi-GPU prediction -- per rank one flat run of valid regions [C][h][w], tile after
 // tile in id order (rank q owns the ids q, q + world, ...); `off` = pixel offset of every tile inside its rank's run.

@@ -2235,6 +2235,84 @@ extern "C" int dsx_tiles_gather_norm(const float* frames0, const float* frames1,
   return DSX_OK;
 }
 
+// ---- mixed-input evaluation (the TimePredictor's inputs): host-side argument checks shared by both gather_mix forms
+namespace {
+static int norm4_ok(const double norm[4]) {
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(norm[i])) return fail(DSX_ERR_INVALID, "normalisation statistics must be finite");
+  if (norm[1] == 0.0 || norm[3] == 0.0) return fail(DSX_ERR_INVALID, "zero standard deviation");
+  return DSX_OK;
+}
+static int mix_weights(double t, const double* lohi, const float* target, const float* mix, const float* cls,
+                       MixWeights& mw) {
+  if (!target && !mix && !cls) return fail(DSX_ERR_INVALID, "gather_mix: every output pointer is NULL");
+  if (!std::isfinite(t)) return fail(DSX_ERR_INVALID, "mixing weight t must be finite");
+  mw = MixWeights{(float)(1.0 - t), (float)t, 0.f, 1.f, 0.f, 1.f};
+  if (cls) {
+    if (!lohi) return fail(DSX_ERR_INVALID, "the classifier view needs the (lo, hi) pairs of its two table rows");
+    for (int c = 0; c < 2; ++c) {
+      const double lo = lohi[2 * c], hi = lohi[2 * c + 1];
+      if (!std::isfinite(lo) || !std::isfinite(hi) || hi - lo == 0.0)
+        return fail(DSX_ERR_INVALID, "table row of channel %d: lo and hi must be finite and differ", c);
+    }
+    mw.lo0 = (float)lohi[0]; mw.rng0 = (float)(lohi[1] - lohi[0]);
+    mw.lo1 = (float)lohi[2]; mw.rng1 = (float)(lohi[3] - lohi[2]);
+  }
+  return DSX_OK;
+}
+}  // namespace
+
+extern "C" int dsx_tiles_gather_mix(const float* frames0, const float* frames1, const int64_t data_shape[3],
+                                    const int64_t patch_shape[3], const int64_t* patch_start, const int64_t* tile_ids,
+                                    int64_t count, const double norm[4], double t, const double* lohi, float* target,
+                                    float* mix, float* cls, void* stream) {
+  MixWeights mw;
+  int rc = mix_weights(t, lohi, target, mix, cls, mw);
+  if (rc) return rc;
+  if (!norm) return fail(DSX_ERR_INVALID, "null argument");
+  if ((rc = norm4_ok(norm))) return rc;
+  if (!frames0 || !frames1 || !data_shape || !patch_shape || !patch_start || count < 0)
+    return fail(DSX_ERR_INVALID, "bad argument");
+  if (count > 65535) return fail(DSX_ERR_INVALID, "at most 65535 tiles per call");
+  if (count == 0) return DSX_OK;
+  std::vector<int> starts;
+  if ((rc = check_starts(patch_start, tile_ids, count, data_shape, patch_shape, starts))) return rc;
+  DevTemp d;
+  HIP_TRY(d.upload(starts.data(), starts.size() * 4));
+  HIP_TRY(launch_tiles_gather_mix(frames0, frames1, (int)data_shape[1], (int)data_shape[2], (int)patch_shape[1],
+                                  (int)patch_shape[2], (const int*)d.p, TileSeq{0, 1, count}, norm, mw, target, mix, cls,
+                                  (hipStream_t)stream));
+  return DSX_OK;
+}
+
+// the range table of the mixed inputs in one launch; the min / max over the partial rows on the host (exact)
+extern "C" int dsx_mix_range_blocks(int64_t pixels, int n_timesteps) {
+  if (pixels < 1) return fail(DSX_ERR_INVALID, "mix_range: no pixels");
+  if (n_timesteps < 1 || n_timesteps > 1024) return fail(DSX_ERR_INVALID, "n_timesteps = %d, must be in 1..1024", n_timesteps);
+  return mix_range_blocks(pixels);
+}
+extern "C" int dsx_mix_range(const float* frames0, const float* frames1, int64_t pixels, const double norm[4],
+                             int n_timesteps, double* partials_dev, double* out_minmax, void* stream) {
+  const int rows = dsx_mix_range_blocks(pixels, n_timesteps);
+  if (rows < 0) return rows;
+  if (!norm) return fail(DSX_ERR_INVALID, "null argument");
+  int rc = norm4_ok(norm);
+  if (rc) return rc;
+  if (!frames0 || !frames1 || !partials_dev || !out_minmax) return fail(DSX_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(launch_mix_range(frames0, frames1, pixels, norm, n_timesteps, partials_dev, st));
+  const size_t row = (size_t)(n_timesteps + 1) * 2;
+  std::vector<double> part((size_t)rows * row);
+  HIP_TRY(hipMemcpyAsync(part.data(), partials_dev, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (size_t i = 0; i < row; i += 2) {
+    double lo = part[i], hi = part[i + 1];
+    for (int r = 1; r < rows; ++r) { lo = std::fmin(lo, part[r * row + i]); hi = std::fmax(hi, part[r * row + i + 1]); }
+    out_minmax[i] = lo; out_minmax[i + 1] = hi;
+  }
+  return DSX_OK;
+}
+
 // ------------------------------------------------------------------ tile plan with device-resident tables
 // One handle per (data, grid, patch, mode): patch starts and valid regions of every tile are uploaded ONCE; every call
 // names its tiles as the arithmetic sequence first, first + stride, ... (a rank's shard r, r + W, ... or a batch of
@@ -2388,6 +2466,22 @@ extern "C" int dsx_tileplan_gather_norm(dsx_tileplan* p, const float* frames0, c
   HIP_TRY(launch_tiles_gather_norm(frames0, frames1, (int)p->t.D[1], (int)p->t.D[2], (int)p->t.p[1], (int)p->t.p[2],
                                    p->d_starts, TileSeq{first, stride, count}, w0, w1, norm, from_norm_target, tiles_in,
                                    tiles_target, (hipStream_t)stream));
+  return DSX_OK;
+}
+extern "C" int dsx_tileplan_gather_mix(dsx_tileplan* p, const float* frames0, const float* frames1, int64_t first,
+                                       int64_t stride, int64_t count, const double norm[4], double t, const double* lohi,
+                                       float* target, float* mix, float* cls, void* stream) {
+  MixWeights mw;
+  int rc = mix_weights(t, lohi, target, mix, cls, mw);
+  if (rc) return rc;
+  if (!p || !frames0 || !frames1 || !norm) return fail(DSX_ERR_INVALID, "null argument");
+  if ((rc = norm4_ok(norm))) return rc;
+  rc = seq_ok(p, first, stride, count);
+  if (rc || count == 0) return rc;
+  if ((rc = plan_device(p))) return rc;
+  HIP_TRY(launch_tiles_gather_mix(frames0, frames1, (int)p->t.D[1], (int)p->t.D[2], (int)p->t.p[1], (int)p->t.p[2],
+                                  p->d_starts, TileSeq{first, stride, count}, norm, mw, target, mix, cls,
+                                  (hipStream_t)stream));
   return DSX_OK;
 }
 // paste whole predicted tiles (count, C, ph, pw) of the sequence; gt_canvas != NULL: also the PSNR partial sums

@@ -72,3 +72,97 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
         netG.inference(tiles, continuous=False, **kw)
         ex.add(netG.last_full_batch, chunk)
     return ex.finish(), plan
+
+
+# ---- mixed-input evaluation (BASELINE C5: JointIndi + TimePredictor) -----------------------------------------------
+def _batches(ids, batch):
+    """Batches of ``batch`` consecutive entries of the arithmetic id list ``ids``; the last short batch is moved back
+    to end at the last id (still arithmetic, same batch size: no second executor) -> (chunk, entries to keep)."""
+    batch = max(1, min(int(batch), len(ids)))
+    for i in range(0, len(ids), batch):
+        if i + batch <= len(ids):
+            yield ids[i:i + batch], batch
+        else:
+            yield ids[len(ids) - batch:], len(ids) - i
+
+
+@torch.no_grad()
+def evaluate_time_predictor(val_set, time_predictor, num_timesteps=20, batch_tiles=16):
+    """The classifier sweep of notebooks/time_prediction_evaluation.ipynb cells 3-7: for every mixing ratio of
+    ``np.arange(0, 1.01, 1 / num_timesteps)`` the TimePredictor's estimate on every tile of ``val_set`` (a
+    ``SplitDatasetTiledPred``), fed ``target0 * t + target1 * (1 - t)`` min-max-normalised with row
+    ``int(t * num_timesteps)`` of the range table (the 'cls' channel 1 of ``mixed_tiles``).  One fused gather launch
+    and one batched TimePredictor forward per (ratio, batch); the last short batch overlaps the one before it, so the
+    whole sweep runs on one executor.  Returns ``(all_pred (n + 1, n_tiles) float32 numpy, rmse)`` with the RMSE of
+    cell 7.  One rank (the sweep is not sharded)."""
+    import numpy as np
+    from .time_predictor_dataset import compute_input_normalization_dict
+    n = int(num_timesteps)
+    table = compute_input_normalization_dict(val_set._data_dict, n, val_set._mean_target, val_set._std_target)
+    gt = np.arange(0, 1.01, 1 / n)[:n + 1]
+    assert len(gt) == n + 1
+    ids = range(len(val_set))
+    all_pred = torch.empty((n + 1, len(ids)), dtype=torch.float32, device=val_set._dev[0].device)
+    for k, t in enumerate(gt):
+        for chunk, keep in _batches(ids, batch_tiles):
+            cls = val_set.mixed_tiles(chunk, float(t), table, want=("cls",))["cls"]
+            pred = time_predictor(cls[:, 1:2])
+            all_pred[k, chunk[-1] + 1 - keep:chunk[-1] + 1] = pred[len(chunk) - keep:]
+    all_pred = all_pred.cpu().numpy()
+    mse = ((all_pred - gt.reshape(-1, 1)) ** 2).mean(axis=1)          # cell 7
+    return all_pred, float(np.sqrt(mse.mean()))
+
+
+@torch.no_grad()
+def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1, mmse_count=1, batch_tiles=8,
+                        t_from="classifier", table=None, table_timesteps=100, group=None):
+    """The out-of-distribution split of notebooks/EvaluateJointIndiIterative.ipynb cells 59-64, batched: the two
+    channels of every tile of ``val_set`` (a ``SplitDatasetTiledPred``) mixed at ``mixing_t`` -> the TimePredictor's
+    estimate of the mixing time per tile (``pred_t_0 = 1 - TP(cls[:, 0])``, ``pred_t_1 = TP(cls[:, 1])``, cell 40) ->
+    ``netG.indi1`` on ``mix[:, 0]`` started at pred_t_0 and ``netG.indi2`` on ``mix[:, 1]`` at pred_t_1 (per-sample
+    step tables, one batched loop per sampler) -> mean over ``mmse_count`` repeats -> stitched, with RangeInvariantPsnr
+    accumulated while pasting.
+
+    ``t_from="given"`` skips the classifier and starts both samplers at ``mixing_t`` (the reference's scalar
+    ``t_float_start``).  ``table``: the range table (computed with ``table_timesteps`` rows when not given; cell 40
+    uses 100).  Returns ``((canvas (N,H,W,2), psnr (N,2)), pred_t (n_tiles, 2))``.
+
+    The score is taken in normalised space against ``val_set.normalized_target_frames()``: the notebook de-normalises
+    prediction and target first, a positive affine map per channel, under which RangeInvariantPsnr does not change --
+    no extra pass.  A sampler's own ``noise_source`` is used (set ``netG.noise_source`` to give both the same).
+    Several ranks: tiles are sharded through ``TileExchange`` as in ``predict_tiled``; ``pred_t`` then holds this
+    rank's tiles only (NaN elsewhere) -- the sharded form is not covered by a test."""
+    if t_from not in ("classifier", "given"):
+        raise ValueError("t_from must be 'classifier' or 'given'")
+    i1, i2 = netG.indi1, netG.indi2
+    if getattr(netG, "noise_source", None) is not None:
+        i1.noise_source = i2.noise_source = netG.noise_source
+    dev = val_set._dev[0].device
+    plan = val_set.plan
+    if t_from == "classifier" and table is None:
+        from .time_predictor_dataset import compute_input_normalization_dict
+        table = compute_input_normalization_dict(val_set._data_dict, table_timesteps, val_set._mean_target,
+                                                 val_set._std_target)
+    ex = TileExchange(plan, 2, dev, group, gt=val_set.normalized_target_frames())
+    ids = parallel.shard_ids(plan.total, ex.rank, ex.world)
+    pred_t = torch.full((plan.total, 2), float("nan"), dtype=torch.float32, device=dev)
+    want = ("mix", "cls") if t_from == "classifier" else ("mix",)
+    for i in range(0, len(ids), batch_tiles):
+        chunk = ids[i:i + batch_tiles]
+        out = val_set.mixed_tiles(chunk, mixing_t, table if t_from == "classifier" else None, want=want)
+        in1, in2 = out["mix"][:, 0:1].contiguous(), out["mix"][:, 1:2].contiguous()
+        if t_from == "classifier":
+            t1 = 1 - time_predictor(out["cls"][:, 0:1])
+            t2 = time_predictor(out["cls"][:, 1:2])
+            pred_t[chunk[0]:chunk[-1] + 1:ex.world] = torch.stack([t1, t2], dim=1)
+        else:
+            t1 = t2 = mixing_t
+            pred_t[chunk[0]:chunk[-1] + 1:ex.world] = float(mixing_t)
+        acc1 = acc2 = None
+        for _ in range(int(mmse_count)):                              # as core/psnr_based_t_refinement.py:26-39
+            i1.inference(in1, continuous=False, num_timesteps=num_timesteps, t_float_start=t1)
+            acc1 = i1.last_full_batch.clone() if acc1 is None else acc1 + i1.last_full_batch
+            i2.inference(in2, continuous=False, num_timesteps=num_timesteps, t_float_start=t2)
+            acc2 = i2.last_full_batch.clone() if acc2 is None else acc2 + i2.last_full_batch
+        ex.add(torch.cat([acc1, acc2], dim=1) / mmse_count, chunk)
+    return ex.finish(), pred_t

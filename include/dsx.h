@@ -291,6 +291,41 @@ int dsx_tiles_gather_norm(const float* frames0_dev, const float* frames1_dev, co
                           int64_t count, float w0, float w1, const double norm[6], int from_norm_target,
                           float* tiles_in_dev, float* tiles_target_dev, void* stream);
 
+/* The mixed inputs of the TimePredictor evaluation for a whole batch of tiles, from the two raw frame stacks, in one
+ * pass: replaces get_inputs + normalize_indi1/2 (notebooks/EvaluateJointIndiIterative.ipynb cells 40, 43), the
+ * classifier sweep's mixing (notebooks/time_prediction_evaluation.ipynb cell 4) and the arithmetic of
+ * TimePredictorDataset.__getitem__ (data/time_predictor_dataset.py:50-89).  norm = {mean_target0, std_target0,
+ * mean_target1, std_target1} (float64), t = the mixing weight of the call.  Outputs, each (count, 2, ph, pw) fp32,
+ * any of them may be NULL (not all three):
+ *   target : t0, t1 = the normalised channels, exactly as dsx_tiles_gather_norm writes them
+ *   mix    : channel 0 = t0*(1-t) + t1*t (input of indi1), channel 1 = t1*(1-t) + t0*t (input of indi2)
+ *   cls    : 2*(m - lo)/(hi - lo) - 1 of the two mix channels, lohi = {lo0, hi0, lo1, hi1}: the rows int((1-t)*n) and
+ *            int(t*n) of the dsx_mix_range table (the caller picks the rows; lohi may be NULL iff cls is)
+ * fp32, every operation rounded on its own (no fma), in this order:
+ *   w1 = (float)t,  w0 = (float)(1.0 - t)                      (the subtraction in double)
+ *   m0 = fadd(fmul(t0, w0), fmul(t1, w1)),  m1 = fadd(fmul(t1, w0), fmul(t0, w1))
+ *   cls_c = fsub(fdiv(fmul(2, fsub(m_c, (float)lo_c)), (float)(hi_c - lo_c)), 1)   (hi - lo in double, IEEE division)
+ * which is what torch computes for a float32 tensor and Python / float64 scalars.  TimePredictorDataset mixes
+ * t*patch1 + (1-t)*patch2 and normalises with row t_int: channel 1.  Host-side refusals (before any device work):
+ * all outputs NULL, non-finite t or statistics, zero std, cls with a non-finite or empty (hi == lo) row. */
+int dsx_tiles_gather_mix(const float* frames0_dev, const float* frames1_dev, const int64_t data_shape[3],
+                         const int64_t patch_shape[3], const int64_t* patch_start_host, const int64_t* tile_ids_host,
+                         int64_t count, const double norm[4], double t, const double lohi[4], float* target_dev,
+                         float* mix_dev, float* cls_dev, void* stream);
+
+/* The range table the classifier's inputs are normalised with (compute_input_normalization_dict,
+ * data/time_predictor_dataset.py:6-21), in one launch instead of n + 1 host passes over the frame set: for every
+ * t_int in 0..n_timesteps the min and max over all `pixels` of both stacks (all frames, flat) of
+ *   v = t*a + (1.0 - t)*b,   a = ((double)x0 - mean0)/std0,  b = ((double)x1 - mean1)/std1,  t = (double)t_int/n
+ * in fp64 with every product, sum and quotient rounded on its own (never an fma): bitwise numpy's float64 result for
+ * frames that fp32 holds exactly, bitwise repeatable (min / max do not depend on the reduction order).  Frames are
+ * assumed finite.  norm = {mean0, std0, mean1, std1}; 1 <= n_timesteps <= 1024; non-finite statistics and zero std
+ * are refused.  dsx_mix_range_blocks: rows of partials a call needs; partials_dev holds rows * (n_timesteps + 1) * 2
+ * doubles.  out_minmax_host[(n_timesteps + 1)][2] = {min, max} is written after the stream is synchronised. */
+int dsx_mix_range_blocks(int64_t pixels, int n_timesteps);
+int dsx_mix_range(const float* frames0_dev, const float* frames1_dev, int64_t pixels, const double norm[4],
+                  int n_timesteps, double* partials_dev, double* out_minmax_host, void* stream);
+
 /* Pastes the valid region of `count` predicted tiles (count, C, ph, pw) into
  * the zero-initialised canvas (N,H,W,C), channel-last: replaces
  * stitch_predictions (data/tile_stitcher.py:10-81).  regions as from
@@ -347,6 +382,10 @@ int dsx_tileplan_gather(dsx_tileplan* plan, const float* frames_dev, int64_t fir
 int dsx_tileplan_gather_norm(dsx_tileplan* plan, const float* frames0_dev, const float* frames1_dev, int64_t first,
                              int64_t stride, int64_t count, float w0, float w1, const double norm[6],
                              int from_norm_target, float* tiles_in_dev, float* tiles_target_dev, void* stream);
+/* dsx_tiles_gather_mix for the tiles of the sequence */
+int dsx_tileplan_gather_mix(dsx_tileplan* plan, const float* frames0_dev, const float* frames1_dev, int64_t first,
+                            int64_t stride, int64_t count, const double norm[4], double t, const double lohi[4],
+                            float* target_dev, float* mix_dev, float* cls_dev, void* stream);
 /* dsx_stitch (gt_canvas_dev == NULL) or dsx_stitch_psnr for whole predicted tiles (count, C, ph, pw) of the sequence */
 int dsx_tileplan_stitch(dsx_tileplan* plan, const float* tiles_dev, int C, int64_t first, int64_t stride, int64_t count,
                         float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream);
