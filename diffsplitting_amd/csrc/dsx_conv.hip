@@ -31,6 +31,7 @@
 #include "dsx_kernels.h"
 #include <algorithm>
 #include <cstdlib>
+#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -1783,31 +1784,6 @@ bool conv_img_applicable(int dtype, int ks, int stride, const ConvArgs& a, bool 
   }
   return true;
 }
-template <typename DT, int KS, int NPH> static hipError_t launch_img_one(const ConvArgs* ap, size_t lds, hipStream_t st) {
-  auto kern = k_conv_img<DT, KS, NPH>;
-  if (!ap) return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(ap->B * ap->nblocks)), dim3(512), lds, st, *ap);
-  return hipGetLastError();
-}
-template <typename DT, int KS> static hipError_t launch_img_ks(const ConvArgs* a, size_t lds, hipStream_t st) {
-  if (!a) {   // one-time attributes of every instantiation
-    hipError_t e = launch_img_one<DT, KS, 2>(a, lds, st);
-    if (e == hipSuccess) e = launch_img_one<DT, KS, 4>(a, lds, st);
-    if (e == hipSuccess) e = launch_img_one<DT, KS, 8>(a, lds, st);
-    return e;
-  }
-  const int nphase = (a->C0 + a->C1) / (8 * Chunk<DT>::KC);   // 2 / 4: the instantiation unrolled for exactly that count
-  return nphase == 2 ? launch_img_one<DT, KS, 2>(a, lds, st)
-       : nphase == 4 ? launch_img_one<DT, KS, 4>(a, lds, st) : launch_img_one<DT, KS, 8>(a, lds, st);
-}
-template <typename DT> static hipError_t launch_img_dt(int ks, const ConvArgs* a, size_t lds, hipStream_t st) {
-  return ks == 3 ? launch_img_ks<DT, 3>(a, lds, st) : launch_img_ks<DT, 1>(a, lds, st);
-}
-hipError_t launch_conv_img(int dtype, int ks, const ConvArgs& a, hipStream_t st) {
-  const size_t lds = conv_img_lds(dtype, ks);
-  return dtype == 1 ? launch_img_dt<__bf16>(ks, &a, lds, st)
-       : dtype == 2 ? launch_img_dt<_Float16>(ks, &a, lds, st) : launch_img_dt<float>(ks, &a, lds, st);
-}
 
 
 // ===========================================================================================
@@ -1981,182 +1957,53 @@ hipError_t launch_conv_first(int dtype, const ConvArgs& a, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------ dispatch
-struct TileCfg { int MB, WM, WN; };
-static constexpr TileCfg kTiles[TILE_COUNT] = {
-    {8, 1, 4},  // 256 x 128
-    {4, 1, 4},  // 128 x 128
-    {2, 1, 4},  // 64 x 128
-    {4, 2, 2},  // 256 x 64
-    {2, 2, 2},  // 128 x 64
-    {1, 2, 2},  // 64 x 64
-    {1, 4, 1},  // 128 x 32: layers with <= 32 output channels (the final conv, 16-channel Hagen levels): all four
-                // waves along M, no wave multiplies padding columns
-    {2, 4, 1},  // 256 x 32: the same with a 16 x 16 pixel tile (two-chunk variant only, see conv_g2_lds_bytes)
+// kVariants has one row per compiled instantiation of k_conv_mfma, k_conv_ws and k_conv_img.  conv_init sets every
+// row's dynamic-LDS limit, the *_lds_bytes functions take "does this variant exist" and its constants from the row, and
+// the launchers launch the row's kernel: a key without a row is hipErrorInvalidValue, never some other kernel.
+// To add a variant, add ONE row to variants_of (or to ws_nb2_variants, if it has no fp32 build): the maker derives the
+// kernel's template arguments and the row's constants from the same numbers.
+enum ConvFamily { FAM_MFMA, FAM_WS, FAM_IMG };
+struct ConvVariant {
+  int family, dtype, tile, ks, stride, cpg;   // the key.  cpg: chunks per staged group (k_conv_img: NPH, and tile -1)
+  void (*kern)(const ConvArgs);
+  int block, lds_cap;   // threads per workgroup; dynamic-LDS limit: kLdsDefault, or kLdsMax (set by conv_init)
+  int MB, WM, WN, NB;   // wave layout: the tile is 32 MB WM pixels x 32 WN NB channels; WM statistics rows per tile
+  int max_px;           // patch pixels the staging registers are sized for
+  int nit;              // 16-byte staging units per (loader) thread and group
+  int depth, nbuf;      // k_conv_ws: raw groups in flight beyond the current one (P), MFMA images
+  bool fuses_stats;     // the epilogue can emit the GroupNorm partial sums of the result
 };
-
-ConvTileInfo conv_tile_info(int tile) {
-  const TileCfg& t = kTiles[tile];
-  return ConvTileInfo{32 * t.MB * t.WM, 32 * t.WN};
-}
-
-int conv_tile_wm(int tile) { return kTiles[tile].WM; }
-bool conv_tile_fuses_stats(int tile) { return kTiles[tile].MB <= 2; }
-bool conv_ws_fuses_stats(int tile) {
-  return tile == TILE_128x128 || tile == TILE_64x128 || tile == TILE_128x64 || tile == TILE_64x64 || tile == TILE_256x64;
-}
-
-static constexpr int conv_cpg(int ks) { return ks == 1 ? 2 : 1; }
-
-// patch-pixel budget of a tile's staging registers
-static constexpr int max_px(int tile, int ks, int stride) {
-  const int bm = 32 * kTiles[tile].MB * kTiles[tile].WM;
-  if (ks == 1) return bm;  // no halo
-  return stride == 2 ? 400 : (bm == 256 ? 400 : (bm == 128 ? 220 : 144));
-}
-static constexpr int max_it(int dtype, int tile, int ks, int stride) {
-  const int upg = 4 * conv_cpg(ks);   // 16-byte units per pixel per group, either storage type
-  (void)dtype;
-  return (max_px(tile, ks, stride) * upg + 255) / 256;
-}
-
-static int patch_pixels(int ks, int stride, const ConvArgs& a) {
-  const int TW = 1 << a.tw_log2, TH = 1 << a.th_log2;
-  return (((TH - 1) * stride + ks) * ((TW - 1) * stride + ks)) << a.tb_log2;
-}
-
+static constexpr int kLdsDefault = 64 * 1024, kLdsMax = 160 * 1024;
+static constexpr int conv_cpg(int ks) { return ks == 1 ? 2 : 1; }   // the families' default chunks per group
 int conv_chunk_multiple(int ks) { return conv_cpg(ks); }
 
-// LDS bytes per patch row.  The A fragment of a 32-row block is read with ds_read_b128, whose 16-lane
-// groups cover rows {0-3,12-15,20-27} / {4-11,16-19,28-31}: with 16-wide tiles the pitch must be a multiple
-// of 256 B, with 8-wide tiles an odd multiple of 128 B, for the 16 reads to fall on 16 distinct 16-B slots.
-int conv_lds_row(int ks, int stride, int tw_log2) {
-  const int pixb = 64 * conv_cpg(ks) + 16;
-  const int pw = ((1 << tw_log2) - 1) * stride + ks;
-  int rb = (pw * pixb + 15) & ~15;
-  if (ks == 1 || stride != 1) return rb;   // no halo: consecutive pixels already conflict-free
-  if (tw_log2 == 4) rb = (rb + 255) & ~255;
-  else if (tw_log2 == 3) { rb = (rb + 127) & ~127; if (((rb >> 7) & 1) == 0) rb += 128; }
-  return rb;
+// k_conv_mfma.  CPG 2 with a 3 x 3 is the two-chunk form (ConvArgs::cpg == 2): 64 input channels per staged group.  For
+// the 64-channel layers of the 128^2 level the whole K extent is one group: load + GroupNorm/Swish + one barrier + 36
+// MFMA steps + epilogue, three workgroups per CU overlapping each other's phases, instead of the persistent kernel's
+// per-group hand-offs (which dominate when a tile has only two groups).
+static constexpr int mfma_max_px(int bm, int ks, int stride, int cpg) {
+  if (ks == 1) return bm;  // no halo
+  if (stride == 2) return 400;
+  if (cpg == 2) return bm == 256 ? 324 : 220;
+  return bm == 256 ? 400 : (bm == 128 ? 220 : 144);
+}
+template <typename DT, int TILE, int MB, int WM, int WN, int KS, int S = 1, int CPG = conv_cpg(KS)>
+constexpr ConvVariant mfma_row() {
+  constexpr bool G2 = KS == 3 && CPG == 2;
+  constexpr int D = KS == 1 ? 4 : (G2 ? 6 : DSX_RING_DEPTH);
+  constexpr int PX = mfma_max_px(32 * MB * WM, KS, S, CPG);
+  constexpr int MI = (PX * 4 * CPG + 255) / 256;   // 4 CPG 16-byte units per pixel and group, either storage type
+  return {FAM_MFMA, Kind<DT>::value, TILE, KS, S, CPG, k_conv_mfma<DT, MB, WM, WN, KS, S, CPG, D, MI>, 256,
+          G2 ? kLdsMax : kLdsDefault, MB, WM, WN, 1, PX, MI, 0, 2, MB <= 2};
 }
 
-// ---- two-chunk-per-group 3x3 variant (ConvArgs::cpg == 2): 64 input channels per staged group.  For the 64-channel
-// layers of the 128^2 level the whole K extent is one group: load + GroupNorm/Swish + one barrier + 36 MFMA steps +
-// epilogue, three workgroups per CU overlapping each other's phases, instead of the persistent kernel's per-group
-// hand-offs (which dominate when a tile has only two groups).
-int conv_lds_row_g2(int tw_log2) {
-  const int pixb = 64 * 2 + 16;
-  const int pw = ((1 << tw_log2) - 1) + 3;
-  int rb = (pw * pixb + 15) & ~15;
-  if (tw_log2 == 4) rb = (rb + 255) & ~255;
-  else if (tw_log2 == 3) { rb = (rb + 127) & ~127; if (((rb >> 7) & 1) == 0) rb += 128; }
-  return rb;
-}
-// patch pixels the two-chunk variant's staging registers are sized for, per tile
-static constexpr int g2_max_px(int tile) { return tile == TILE_256x32 ? 324 : 220; }
-size_t conv_g2_lds_bytes(int tile, const ConvArgs& a) {
-  if (tile != TILE_128x64 && tile != TILE_256x32 && tile != TILE_128x32) return 0;
-  const ConvTileInfo ti = conv_tile_info(tile);
-  if ((1 << (a.tw_log2 + a.th_log2 + a.tb_log2)) != ti.BM || a.tb_log2 != 0) return 0;
-  if (patch_pixels(3, 1, a) > g2_max_px(tile) || a.lds_row != conv_lds_row_g2(a.tw_log2)) return 0;
-  if (a.kchunks % 2 || a.stage_mode != 0) return 0;
-  const int ph = ((1 << a.th_log2) - 1) + 3;
-  const size_t bufb = (size_t)ph * a.lds_row;
-  const size_t need = (a.kchunks / 2 > 1 ? 2 : 1) * bufb;     // a single group never touches the second buffer
-  return need <= 160 * 1024 ? need : 0;
-}
-template <typename DT, int TILE> static hipError_t launch_g2_tile(const ConvArgs* ap, size_t lds, hipStream_t st) {
-  constexpr TileCfg t = kTiles[TILE];
-  auto kern = k_conv_mfma<DT, t.MB, t.WM, t.WN, 3, 1, 2, 6, (g2_max_px(TILE) * 8 + 255) / 256>;
-  if (!ap) return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  dim3 grid((unsigned)(ap->m_tiles * ap->n_tiles * ap->ksplit));
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, *ap);
-  return hipGetLastError();
-}
-template <typename DT> static hipError_t launch_g2(int tile, const ConvArgs* ap, size_t lds, hipStream_t st) {
-  if (!ap) {   // one-time attributes of every instantiation
-    hipError_t e = launch_g2_tile<DT, TILE_128x64>(ap, lds, st);
-    if (e == hipSuccess) e = launch_g2_tile<DT, TILE_256x32>(ap, lds, st);
-    if (e == hipSuccess) e = launch_g2_tile<DT, TILE_128x32>(ap, lds, st);
-    return e;
-  }
-  return tile == TILE_256x32 ? launch_g2_tile<DT, TILE_256x32>(ap, lds, st)
-       : tile == TILE_128x32 ? launch_g2_tile<DT, TILE_128x32>(ap, lds, st) : launch_g2_tile<DT, TILE_128x64>(ap, lds, st);
-}
-
-size_t conv_lds_bytes(int dtype, int tile, int ks, int stride, const ConvArgs& a) {
-  if (a.cpg == 2 && ks == 3 && stride == 1) return conv_g2_lds_bytes(tile, a);
-  if (tile < 0 || tile >= TILE_COUNT || tile == TILE_256x32) return 0;   // (256 x 32 exists as the two-chunk variant only)
-  if (!(ks == 1 || ks == 3) || !(stride == 1 || (stride == 2 && ks == 3 && tile == TILE_64x64))) return 0;
-  const ConvTileInfo ti = conv_tile_info(tile);
-  if ((1 << (a.tw_log2 + a.th_log2 + a.tb_log2)) != ti.BM) return 0;
-  const int pp = patch_pixels(ks, stride, a);
-  if (pp > max_px(tile, ks, stride)) return 0;
-  if (a.lds_row != conv_lds_row(ks, stride, a.tw_log2)) return 0;
-  const int ph = ((1 << a.th_log2) - 1) * stride + ks;
-  const size_t bufb = (size_t)(ph << a.tb_log2) * a.lds_row;
-  if (2 * bufb > 64 * 1024) return 0;
-  return 2 * bufb;
-}
-
-// ap == nullptr: only set the kernel's dynamic-LDS attribute (conv_init)
-template <typename DT, int TILE, int KS, int S>
-static hipError_t launch_one(const ConvArgs* ap, size_t lds, hipStream_t st) {
-  constexpr TileCfg t = kTiles[TILE];
-  constexpr int CPG = conv_cpg(KS);
-  constexpr int D = KS == 1 ? 4 : DSX_RING_DEPTH;
-  constexpr int MI = max_it(Kind<DT>::value, TILE, KS, S);
-  auto kern = k_conv_mfma<DT, t.MB, t.WM, t.WN, KS, S, CPG, D, MI>;
-  if (!ap)
-    return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-  const ConvArgs& a = *ap;
-  dim3 grid((unsigned)(a.m_tiles * a.n_tiles * a.ksplit));
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  return hipGetLastError();
-}
-
-template <typename DT>
-static hipError_t launch_dt(int tile, int ks, int stride, const ConvArgs* a, size_t lds, hipStream_t st) {
-  if (stride == 2) return launch_one<DT, TILE_64x64, 3, 2>(a, lds, st);
-#define DSX_TILE_CASE(T) \
-  case T: return ks == 3 ? launch_one<DT, T, 3, 1>(a, lds, st) : launch_one<DT, T, 1, 1>(a, lds, st);
-  switch (tile) {
-    DSX_TILE_CASE(TILE_256x128)
-    DSX_TILE_CASE(TILE_128x128)
-    DSX_TILE_CASE(TILE_64x128)
-    DSX_TILE_CASE(TILE_256x64)
-    DSX_TILE_CASE(TILE_128x64)
-    DSX_TILE_CASE(TILE_128x32)
-    default: return ks == 3 ? launch_one<DT, TILE_64x64, 3, 1>(a, lds, st) : launch_one<DT, TILE_64x64, 1, 1>(a, lds, st);
-  }
-#undef DSX_TILE_CASE
-}
-
-hipError_t launch_conv(int dtype, int tile, int ks, int stride, const ConvArgs& a, hipStream_t st) {
-  const size_t lds = conv_lds_bytes(dtype, tile, ks, stride, a);
-  if (lds == 0 || a.ksplit < 1 || a.n_tiles < 1) return hipErrorInvalidValue;
-  if (a.cpg == 2)
-    return dtype == 1 ? launch_g2<__bf16>(tile, &a, lds, st) : dtype == 2 ? launch_g2<_Float16>(tile, &a, lds, st) : launch_g2<float>(tile, &a, lds, st);
-  return dtype == 1 ? launch_dt<__bf16>(tile, ks, stride, &a, lds, st)
-       : dtype == 2 ? launch_dt<_Float16>(tile, ks, stride, &a, lds, st)
-                    : launch_dt<float>(tile, ks, stride, &a, lds, st);
-}
-
-// ---- warp-specialised variant: per (dtype, tile, ks) constants.  Its waves are laid out differently from
-// k_conv_mfma's: MB row blocks x NB N blocks per wave (the 128 x 128 tile is 2 x 2 waves of 64 x 64).
-struct WsTileCfg { int MB, WM, WN, NB; };
-static constexpr WsTileCfg ws_tile(int tile) {
-  return tile == TILE_128x128 ? WsTileCfg{2, 2, 2, 2}
-       : tile == TILE_64x128  ? WsTileCfg{2, 1, 4, 1}
-       : tile == TILE_128x64  ? WsTileCfg{2, 2, 2, 1}
-       : tile == TILE_256x64  ? WsTileCfg{4, 2, 2, 1}    // 16 x 16 pixels: half the tiles (and epilogues) of 128 x 64
-                              : WsTileCfg{1, 2, 2, 1};   // TILE_64x64
-}
-static constexpr bool ws_tile_ok(int tile) {
-  return tile == TILE_128x128 || tile == TILE_64x128 || tile == TILE_128x64 || tile == TILE_64x64 || tile == TILE_256x64;
-}
-int conv_ws_tile_wm(int tile) { return ws_tile(tile).WM; }
-static constexpr int ws_depth(int tile, int ks, int cpg) {   // P: groups of raw activations in flight beyond the current one
-  const int bm = 32 * kTiles[tile].MB * kTiles[tile].WM;
+// k_conv_ws.  Its waves are laid out differently from k_conv_mfma's: MB row blocks x NB N blocks per wave (the
+// 128 x 128 tile is 2 x 2 waves of 64 x 64).
+static constexpr int kWsLoaderWaves = 4;
+// patch pixels the WS loaders are sized for: one image per tile, square-ish tiles (16x8 / 8x16 -> 18x10,
+// 8x8 -> 10x10, 16x4 -> 18x6); other shapes fall back to k_conv_mfma
+static constexpr int ws_max_px(int bm, int ks) { return ks == 1 ? bm : (bm == 256 ? 324 : (bm == 128 ? 180 : 108)); }
+static constexpr int ws_depth(int bm, int ks, int cpg) {
 #ifndef DSX_WS_DEPTH_C2_64
 #define DSX_WS_DEPTH_C2_64 3
 #endif
@@ -2165,168 +2012,241 @@ static constexpr int ws_depth(int tile, int ks, int cpg) {   // P: groups of raw
   if (ks == 1 && cpg == 4) return bm == 64 ? 2 : 1;                     // four-chunk groups of a 1 x 1 conv
   return DSX_WS_DEPTH_EXPR;
 }
-// chunks per group of k_conv_ws: the family default, or two for a 3 x 3 conv that asks for it (ConvArgs::ws_cpg)
-static constexpr int ws_cpg_of(int ks, int ws_cpg) {
-  return (ks == 3 && (ws_cpg == 2 || ws_cpg == 4)) ? ws_cpg : ((ks == 1 && ws_cpg == 4) ? 4 : conv_cpg(ks));
+template <typename DT, int TILE, int MB, int WM, int WN, int NB, int KS, int CPG = conv_cpg(KS)>
+constexpr ConvVariant ws_row() {
+  constexpr int BM = 32 * MB * WM;
+  // weight ring, in steps: a full group for one N block per wave, half of it (same bytes, same time) for two
+  // (1 x 1 with two N blocks per wave or MB 4: a deeper ring spills, and hipcc's spill path fails on this kernel)
+  constexpr int D = KS == 1 ? ((NB == 2 || MB == 4) ? DSX_RING_1X1_NB2 : DSX_RING_1X1_NB1) : ((NB == 2 || MB == 4) ? 6 : 18);   // (MB 4: four MFMAs per step, and the registers are needed)
+  constexpr int PX = ws_max_px(BM, KS);
+  constexpr int NIT = (PX * 4 * CPG + kWsLoaderWaves * 64 - 1) / (kWsLoaderWaves * 64);
+  constexpr int P = ws_depth(BM, KS, CPG);
+  return {FAM_WS, Kind<DT>::value, TILE, KS, 1, CPG, k_conv_ws<DT, MB, WM, WN, NB, KS, CPG, D, NIT, P, kWsLoaderWaves>,
+          256 + 64 * kWsLoaderWaves, kLdsMax, MB, WM, WN, NB, PX, NIT, P, ws_nbuf(BM, KS, NB, CPG), true};
 }
-// LDS row pitch of a 3 x 3 image with `cpg` chunks per pixel (the rule of conv_lds_row for 64 cpg + 16 byte pixels)
-int conv_lds_row_3x3_c(int tw_log2, int cpg) {
-  const int pixb = 64 * cpg + 16;
-  const int pw = ((1 << tw_log2) - 1) + 3;
-  int rb = (pw * pixb + 15) & ~15;
+
+// k_conv_img.  NPH 2 / 4: unrolled for exactly that many channel phases; NPH 8: any count up to 8, read at run time
+template <typename DT, int KS, int NPH> constexpr ConvVariant img_row() {
+  return {FAM_IMG, Kind<DT>::value, -1, KS, 1, NPH, k_conv_img<DT, KS, NPH>, 512, kLdsMax, 0, 0, 0, 0, 0, 0, 0, 0, true};
+}
+
+template <int N> struct ConvVariants {
+  ConvVariant row[N];
+  constexpr const ConvVariant* begin() const { return row; }
+  constexpr const ConvVariant* end() const { return row + N; }
+};
+template <int... N> constexpr ConvVariants<(N + ...)> concat(const ConvVariants<N>&... parts) {
+  ConvVariants<(N + ...)> out{};
+  int n = 0;
+  auto append = [&](const auto& p) { for (const ConvVariant& v : p) out.row[n++] = v; };
+  (append(parts), ...);
+  return out;
+}
+
+// Which variants are compiled, per operand type.
+template <typename DT> constexpr ConvVariants<34> variants_of() {
+  return {{
+      // k_conv_mfma: tile, MB, WM, WN, ks, stride (1), chunks per group (the default of ks)
+      mfma_row<DT, TILE_256x128, 8, 1, 4, 1>(), mfma_row<DT, TILE_256x128, 8, 1, 4, 3>(),
+      mfma_row<DT, TILE_128x128, 4, 1, 4, 1>(), mfma_row<DT, TILE_128x128, 4, 1, 4, 3>(),
+      mfma_row<DT, TILE_64x128, 2, 1, 4, 1>(), mfma_row<DT, TILE_64x128, 2, 1, 4, 3>(),
+      mfma_row<DT, TILE_256x64, 4, 2, 2, 1>(), mfma_row<DT, TILE_256x64, 4, 2, 2, 3>(),
+      mfma_row<DT, TILE_128x64, 2, 2, 2, 1>(), mfma_row<DT, TILE_128x64, 2, 2, 2, 3>(),
+      mfma_row<DT, TILE_128x64, 2, 2, 2, 3, 1, 2>(),   // two-chunk form: an experiment (PlanKnobs::tiles_narrow_g2)
+      mfma_row<DT, TILE_64x64, 1, 2, 2, 1>(), mfma_row<DT, TILE_64x64, 1, 2, 2, 3>(),
+      mfma_row<DT, TILE_64x64, 1, 2, 2, 3, 2>(),       // the stride-2 downsamples
+      // layers with <= 32 output channels (the final conv, 16-channel Hagen levels): all four waves along M, no wave
+      // multiplies padding columns; 256 x 32 (a 16 x 16 pixel tile) exists as the two-chunk form only
+      mfma_row<DT, TILE_128x32, 1, 4, 1, 1>(), mfma_row<DT, TILE_128x32, 1, 4, 1, 3>(),
+      mfma_row<DT, TILE_128x32, 1, 4, 1, 3, 1, 2>(), mfma_row<DT, TILE_256x32, 2, 4, 1, 3, 1, 2>(),
+      // k_conv_ws: tile, MB, WM, WN, NB, ks, chunks per group (the default of ks)
+      ws_row<DT, TILE_64x128, 2, 1, 4, 1, 1>(), ws_row<DT, TILE_64x128, 2, 1, 4, 1, 3>(),
+      ws_row<DT, TILE_64x128, 2, 1, 4, 1, 1, 4>(),     // ConvArgs::ws_cpg: 128 input channels per item of a 1 x 1 conv,
+      ws_row<DT, TILE_64x128, 2, 1, 4, 1, 3, 2>(),     // 64 (the 16 x 16 maps, where the loaders' per-item costs bound the item)
+      ws_row<DT, TILE_64x128, 2, 1, 4, 1, 3, 4>(),     // or 128 of a 3 x 3 conv
+      ws_row<DT, TILE_128x64, 2, 2, 2, 1, 1>(), ws_row<DT, TILE_128x64, 2, 2, 2, 1, 3>(),
+      ws_row<DT, TILE_256x64, 4, 2, 2, 1, 3>(),        // 16 x 16 pixels: half the tiles (and epilogues) of 128 x 64
+      ws_row<DT, TILE_64x64, 1, 2, 2, 1, 1>(), ws_row<DT, TILE_64x64, 1, 2, 2, 1, 3>(),
+      // k_conv_img: ks, NPH
+      img_row<DT, 1, 2>(), img_row<DT, 1, 4>(), img_row<DT, 1, 8>(),
+      img_row<DT, 3, 2>(), img_row<DT, 3, 4>(), img_row<DT, 3, 8>(),
+  }};
+}
+// k_conv_ws with two N blocks per wave: the fp32 build does not fit the registers, so 16-bit operands only
+template <typename DT> constexpr ConvVariants<4> ws_nb2_variants() {
+  return {{ws_row<DT, TILE_128x128, 2, 2, 2, 2, 1>(), ws_row<DT, TILE_128x128, 2, 2, 2, 2, 3>(),
+           ws_row<DT, TILE_128x128, 2, 2, 2, 2, 1, 4>(), ws_row<DT, TILE_128x128, 2, 2, 2, 2, 3, 2>()}};
+}
+static constexpr auto kVariants = concat(variants_of<float>(), variants_of<__bf16>(), variants_of<_Float16>(),
+                                         ws_nb2_variants<__bf16>(), ws_nb2_variants<_Float16>());
+
+// key -> row without a search (the planner asks a few times per conv and candidate tile)
+static constexpr int kKeySlots = 3 * 3 * (TILE_COUNT + 1) * 2 * 2 * 4;
+static constexpr int key_slot(int family, int dtype, int tile, int ks, int stride, int cpg) {
+  const int c = cpg == 1 ? 0 : (cpg == 2 ? 1 : (cpg == 4 ? 2 : (cpg == 8 ? 3 : -1)));
+  if (family < 0 || family > FAM_IMG || dtype < 0 || dtype > 2 || tile < -1 || tile >= TILE_COUNT || (ks != 1 && ks != 3) ||
+      (stride != 1 && stride != 2) || c < 0)
+    return -1;
+  return ((((family * 3 + dtype) * (TILE_COUNT + 1) + tile + 1) * 2 + ks / 2) * 2 + stride - 1) * 4 + c;
+}
+struct VariantIndex { short row[kKeySlots]; bool unique; };
+static constexpr VariantIndex index_variants() {
+  VariantIndex ix{};
+  for (short& r : ix.row) r = -1;
+  ix.unique = true;
+  short n = 0;
+  for (const ConvVariant& v : kVariants) {
+    const int s = key_slot(v.family, v.dtype, v.tile, v.ks, v.stride, v.cpg);
+    if (s < 0 || ix.row[s] >= 0) ix.unique = false;
+    else ix.row[s] = n;
+    ++n;
+  }
+  return ix;
+}
+static constexpr VariantIndex kIndex = index_variants();
+static_assert(kIndex.unique, "kVariants: two rows share a key, or a key is outside key_slot's ranges");
+static const ConvVariant* find_variant(int family, int dtype, int tile, int ks, int stride, int cpg) {
+  const int s = key_slot(family, dtype, tile, ks, stride, cpg);
+  return s >= 0 && kIndex.row[s] >= 0 ? &kVariants.row[kIndex.row[s]] : nullptr;
+}
+
+static constexpr bool variants_consistent() {
+  for (const ConvVariant& a : kVariants) {
+    // the sizing rules assume these limits; block sizes are the kernels' __launch_bounds__
+    const bool big = a.family != FAM_MFMA || (a.ks == 3 && a.cpg == 2);
+    if (a.lds_cap != (big ? kLdsMax : kLdsDefault) || a.block != (a.family == FAM_MFMA ? 256 : 512)) return false;
+    for (const ConvVariant& b : kVariants) {
+      // one wave layout per (family, tile), and both families agree on what a tile's name means (conv_tile_info)
+      if (a.tile == b.tile && (a.MB * a.WM != b.MB * b.WM || a.WN * a.NB != b.WN * b.NB)) return false;
+      if (a.tile == b.tile && a.family == b.family && (a.WM != b.WM || a.fuses_stats != b.fuses_stats)) return false;
+    }
+  }
+  return true;
+}
+static_assert(variants_consistent(), "kVariants: wrong LDS limit / block size, or two layouts for one tile");
+
+ConvTileInfo conv_tile_info(int tile, bool ws) {
+  for (const ConvVariant& v : kVariants)
+    if (v.family == (ws ? FAM_WS : FAM_MFMA) && v.tile == tile) return {32 * v.MB * v.WM, 32 * v.WN * v.NB, v.WM, v.fuses_stats};
+  return {0, 0, 0, false};
+}
+
+// conv_lds_row against the four pitch functions it replaced, for every (ks, stride, cpg) these stood for
+namespace lds_row_was {
+constexpr int banked(int rb, int tw_log2) {
   if (tw_log2 == 4) rb = (rb + 255) & ~255;
   else if (tw_log2 == 3) { rb = (rb + 127) & ~127; if (((rb >> 7) & 1) == 0) rb += 128; }
   return rb;
 }
-// LDS row pitch of a 1 x 1 conv's image with four chunks per pixel (272-byte pixels: no halo, consecutive pixels)
-int conv_lds_row_1x1_c4(int tw_log2) { return (((1 << tw_log2) * (64 * 4 + 16)) + 15) & ~15; }
-static constexpr int kWsLoaderWaves = 4;
-// patch pixels the WS loaders are sized for: one image per tile, square-ish tiles (16x8 / 8x16 -> 18x10,
-// 8x8 -> 10x10, 16x4 -> 18x6); other shapes fall back to k_conv_mfma
-static constexpr int ws_max_px(int tile, int ks) {
-  const int bm = 32 * kTiles[tile].MB * kTiles[tile].WM;
-  return ks == 1 ? bm : (bm == 256 ? 324 : (bm == 128 ? 180 : 108));
+constexpr int plain(int ks, int stride, int tw_log2) {   // conv_lds_row(ks, stride, tw_log2)
+  const int rb = ((((1 << tw_log2) - 1) * stride + ks) * (64 * conv_cpg(ks) + 16) + 15) & ~15;
+  return (ks == 1 || stride != 1) ? rb : banked(rb, tw_log2);
 }
-static constexpr int ws_nit(int tile, int ks, int cpg) {   // staging units per loader thread per group
-  const int upg = 4 * cpg;
-  return (ws_max_px(tile, ks) * upg + kWsLoaderWaves * 64 - 1) / (kWsLoaderWaves * 64);
+constexpr int g2(int tw_log2) { return banked(((((1 << tw_log2) - 1) + 3) * (64 * 2 + 16) + 15) & ~15, tw_log2); }
+constexpr int c3x3(int tw_log2, int cpg) { return banked(((((1 << tw_log2) - 1) + 3) * (64 * cpg + 16) + 15) & ~15, tw_log2); }
+constexpr int c4_1x1(int tw_log2) { return (((1 << tw_log2) * (64 * 4 + 16)) + 15) & ~15; }
+constexpr bool same() {
+  for (int tw = 0; tw <= 4; ++tw) {
+    for (int cpg = 1; cpg <= 4; cpg *= 2)
+      if (conv_lds_row(3, 1, tw, cpg) != c3x3(tw, cpg)) return false;
+    if (conv_lds_row(3, 1, tw, 1) != plain(3, 1, tw) || conv_lds_row(3, 1, tw, 2) != g2(tw)) return false;
+    if (conv_lds_row(3, 2, tw, 1) != plain(3, 2, tw)) return false;
+    if (conv_lds_row(1, 1, tw, 2) != plain(1, 1, tw) || conv_lds_row(1, 1, tw, 4) != c4_1x1(tw)) return false;
+  }
+  return true;
+}
+static_assert(same(), "conv_lds_row changed a row pitch");
+}  // namespace lds_row_was
+
+static int patch_pixels(int ks, int stride, const ConvArgs& a) {
+  const int TW = 1 << a.tw_log2, TH = 1 << a.th_log2;
+  return (((TH - 1) * stride + ks) * ((TW - 1) * stride + ks)) << a.tb_log2;
+}
+static hipError_t launch_variant(const ConvVariant& v, unsigned grid, size_t lds, const ConvArgs& a, hipStream_t st) {
+  void* args[] = {(void*)&a};
+  (void)hipLaunchKernel((const void*)v.kern, dim3(grid), dim3((unsigned)v.block), args, lds, st);
+  return hipGetLastError();
+}
+
+// ---- k_conv_mfma
+static bool is_g2(int ks, int stride, const ConvArgs& a) { return a.cpg == 2 && ks == 3 && stride == 1; }
+static const ConvVariant* mfma_variant(int dtype, int tile, int ks, int stride, const ConvArgs& a) {
+  return find_variant(FAM_MFMA, dtype, tile, ks, stride, is_g2(ks, stride, a) ? 2 : conv_cpg(ks));
+}
+size_t conv_lds_bytes(int dtype, int tile, int ks, int stride, const ConvArgs& a) {
+  const ConvVariant* v = mfma_variant(dtype, tile, ks, stride, a);
+  if (!v) return 0;
+  if ((1 << (a.tw_log2 + a.th_log2 + a.tb_log2)) != 32 * v->MB * v->WM) return 0;
+  if (patch_pixels(ks, stride, a) > v->max_px || a.lds_row != conv_lds_row(ks, stride, a.tw_log2, v->cpg)) return 0;
+  const int ph = ((1 << a.th_log2) - 1) * stride + ks;
+  const size_t bufb = (size_t)(ph << a.tb_log2) * a.lds_row;
+  size_t need = 2 * bufb;
+  if (is_g2(ks, stride, a)) {   // one image per tile, whole groups of aligned sources
+    if (a.tb_log2 != 0 || a.kchunks % 2 || a.stage_mode != 0) return 0;
+    if (a.kchunks / 2 <= 1) need = bufb;   // a single group never touches the second buffer
+  }
+  return need <= (size_t)v->lds_cap ? need : 0;
+}
+hipError_t launch_conv(int dtype, int tile, int ks, int stride, const ConvArgs& a, hipStream_t st) {
+  const size_t lds = conv_lds_bytes(dtype, tile, ks, stride, a);
+  if (lds == 0 || a.ksplit < 1 || a.n_tiles < 1) return hipErrorInvalidValue;
+  return launch_variant(*mfma_variant(dtype, tile, ks, stride, a), (unsigned)(a.m_tiles * a.n_tiles * a.ksplit), lds, a, st);
+}
+
+// ---- k_conv_ws.  Chunks per group: the family default, or ConvArgs::ws_cpg where that names a compiled form
+static const ConvVariant* ws_variant(int dtype, int tile, int ks, const ConvArgs& a) {
+  const int cpg = (ks == 3 && (a.ws_cpg == 2 || a.ws_cpg == 4)) ? a.ws_cpg : ((ks == 1 && a.ws_cpg == 4) ? 4 : conv_cpg(ks));
+  return find_variant(FAM_WS, dtype, tile, ks, 1, cpg);
 }
 size_t conv_ws_lds_bytes(int dtype, int tile, int ks, const ConvArgs& a) {
-  if (!ws_tile_ok(tile) || !(ks == 1 || ks == 3)) return 0;
-  if (tile == TILE_256x64 && ks != 3) return 0;
-  if (ws_tile(tile).NB == 2 && dtype == 0) return 0;
-  const int cpg = ws_cpg_of(ks, a.ws_cpg);
-  if (ks == 3 && cpg == 4) {
-    const int KC = dtype != 0 ? 32 : 16;
-    if (tile != TILE_64x128 || a.cpg == 2 || (a.kchunks & 3) || a.C0 % (4 * KC) || a.C1 % (4 * KC)) return 0;
-    if ((1 << (a.tw_log2 + a.th_log2 + a.tb_log2)) != conv_tile_info(tile).BM) return 0;
-    if (a.lds_row != conv_lds_row_3x3_c(a.tw_log2, 4)) return 0;
-  } else if (ks == 3 && cpg == 2) {
-    // two-chunk 3 x 3 groups: instantiated for the 64-pixel tile (the 16 x 16 maps, where the loaders' per-item costs
-    // bound the item); 144-byte pixels, the row pitch of the other two-chunk kernel
-    const int KC = dtype != 0 ? 32 : 16;
-    if (!(tile == TILE_64x128 || tile == TILE_128x128) || a.cpg == 2 || (a.kchunks & 1) || a.C0 % (2 * KC) || a.C1 % (2 * KC)) return 0;
-    if ((1 << (a.tw_log2 + a.th_log2 + a.tb_log2)) != conv_tile_info(tile).BM) return 0;
-    if (a.lds_row != conv_lds_row_g2(a.tw_log2)) return 0;
-  } else if (ks == 1 && cpg == 4) {
-    // four-chunk 1 x 1 groups (128 input channels per item): the 64- and 128-pixel tiles with 128 output channels
-    const int KC = dtype != 0 ? 32 : 16;
-    if (!(tile == TILE_64x128 || tile == TILE_128x128) || (a.kchunks & 3) || a.C0 % (4 * KC) || a.C1 % (4 * KC)) return 0;
-    if ((1 << (a.tw_log2 + a.th_log2 + a.tb_log2)) != conv_tile_info(tile).BM) return 0;
-    if (a.lds_row != conv_lds_row_1x1_c4(a.tw_log2)) return 0;
-  } else if (conv_lds_bytes(dtype, tile, ks, 1, a) == 0) return 0;
-  if (patch_pixels(ks, 1, a) > ws_max_px(tile, ks)) return 0;
+  const ConvVariant* v = ws_variant(dtype, tile, ks, a);
+  if (!v) return 0;
+  const int cpg = v->cpg;
+  if (cpg != conv_cpg(ks)) {
+    // several chunks per item: whole groups from either source, never on top of the two-chunk k_conv_mfma geometry
+    const int gw = cpg * (dtype != 0 ? 32 : 16);
+    if ((ks == 3 && a.cpg == 2) || a.kchunks % cpg || a.C0 % gw || a.C1 % gw) return 0;
+    if ((1 << (a.tw_log2 + a.th_log2 + a.tb_log2)) != 32 * v->MB * v->WM) return 0;
+    if (a.lds_row != conv_lds_row(ks, 1, a.tw_log2, cpg)) return 0;
+  } else if (conv_lds_bytes(dtype, tile, ks, 1, a) == 0) return 0;   // the tile geometry and row pitch of k_conv_mfma
+  if (patch_pixels(ks, 1, a) > v->max_px) return 0;
   if (a.up && (a.tw_log2 == 0 || a.th_log2 == 0)) return 0;   // the loaders assume an even tile origin when upsampling
   const int ph = ((1 << a.th_log2) - 1) + ks;
   const size_t bufb = (size_t)(ph << a.tb_log2) * a.lds_row;
-  const size_t rawb = (size_t)ws_nit(tile, ks, cpg) * (kWsLoaderWaves * 64 * 16);
+  const size_t rawb = (size_t)v->nit * (kWsLoaderWaves * 64 * 16);
   const size_t affb = a.has_gn ? (((size_t)2 * (a.C0 + a.C1) * 4 + 15) & ~(size_t)15) : 0;  // never keyed on a pointer
-  const WsTileCfg wt = ws_tile(tile);
-  const size_t nbuf = (size_t)ws_nbuf(32 * wt.MB * wt.WM, ks, wt.NB, cpg);
-  const size_t total = nbuf * bufb + 3 * affb + (size_t)(ws_depth(tile, ks, cpg) + 1) * rawb + (nbuf >= 3 ? 32 : 0);
+  const size_t total = v->nbuf * bufb + 3 * affb + (size_t)(v->depth + 1) * rawb + (v->nbuf >= 3 ? 32 : 0);
   if (a.tb_log2 != 0 || a.kchunks / cpg < 2) return 0;   // one image per tile, >= 2 channel groups
   // whole 32-channel blocks, float4 epilogue, scale/shift staged by 256 threads x float4
   if ((long long)a.B * a.Ho * a.Wo * std::max(a.out_ld, a.resid_ld) >= (1LL << 31)) return 0;   // 32-bit element offsets
   const int al = dtype != 0 ? 7 : 3;   // 16-byte rows in elements of the storage type
-  if (a.Cout % (32 * ws_tile(tile).WN * ws_tile(tile).NB) != 0 || (a.out_ld & al) != 0 || (a.resid_ld & al) != 0 ||
-      a.C0 + a.C1 > 1024)
+  if (a.Cout % (32 * v->WN * v->NB) != 0 || (a.out_ld & al) != 0 || (a.resid_ld & al) != 0 || a.C0 + a.C1 > 1024)
     return 0;
   if (dtype != 0 && !(a.act_bf16 && a.out_bf16)) return 0;   // this kernel reads and writes the storage type only
-  return total <= 160 * 1024 ? total : 0;
-}
-
-template <typename DT, int TILE, int KS, int CPG = conv_cpg(KS)>
-static hipError_t launch_ws_one(const ConvArgs* ap, size_t lds, hipStream_t st) {
-  if constexpr (!ws_tile_ok(TILE) || (ws_tile(TILE).NB == 2 && sizeof(DT) == 4)) {
-    return ap ? hipErrorInvalidValue : hipSuccess;   // (the fp32 build has no two-N-block variant: registers)
-  } else {
-    constexpr WsTileCfg t = ws_tile(TILE);
-    // weight ring, in steps: a full group for one N block per wave, half of it (same bytes, same time) for two
-    // (1 x 1 with two N blocks per wave or MB 4: a deeper ring spills, and hipcc's spill path fails on this kernel)
-    constexpr int D = KS == 1 ? ((t.NB == 2 || t.MB == 4) ? DSX_RING_1X1_NB2 : DSX_RING_1X1_NB1) : ((t.NB == 2 || t.MB == 4) ? 6 : 18);   // (MB 4: four MFMAs per step, and the registers are needed)
-    constexpr int NIT = ws_nit(TILE, KS, CPG);
-    constexpr int P = ws_depth(TILE, KS, CPG);
-    auto kern = k_conv_ws<DT, t.MB, t.WM, t.WN, t.NB, KS, CPG, D, NIT, P, kWsLoaderWaves>;
-    if (!ap)
-      return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const ConvArgs& a = *ap;
-    dim3 grid((unsigned)(a.n_tiles * a.ws_wg_per_n));
-    hipLaunchKernelGGL(kern, grid, dim3(256 + 64 * kWsLoaderWaves), lds, st, a);
-    return hipGetLastError();
-  }
-}
-template <typename DT>
-static hipError_t launch_ws_dt(int tile, int ks, const ConvArgs* a, size_t lds, hipStream_t st) {
-#define DSX_WS_CASE(T) \
-  case T: return ks == 3 ? launch_ws_one<DT, T, 3>(a, lds, st) : launch_ws_one<DT, T, 1>(a, lds, st);
-  if ((tile == TILE_64x128 || tile == TILE_128x128) && ks == 1) {   // + the four-chunk 1 x 1 form of these tiles (ConvArgs::ws_cpg == 4)
-    if (!a) {
-      hipError_t e = launch_ws_one<DT, TILE_64x128, 1, 4>(a, lds, st);
-      if (e == hipSuccess) e = launch_ws_one<DT, TILE_128x128, 1, 4>(a, lds, st);
-      if (e != hipSuccess) return e;
-    } else if (a->ws_cpg == 4) {
-      return tile == TILE_64x128 ? launch_ws_one<DT, TILE_64x128, 1, 4>(a, lds, st) : launch_ws_one<DT, TILE_128x128, 1, 4>(a, lds, st);
-    }
-  }
-  if ((tile == TILE_64x128 || tile == TILE_128x128) && ks == 3) {   // + the two-chunk form of these tiles (ConvArgs::ws_cpg == 2)
-    if (!a) {
-      hipError_t e = launch_ws_one<DT, TILE_64x128, 3, 2>(a, lds, st);
-      if (e == hipSuccess) e = launch_ws_one<DT, TILE_128x128, 3, 2>(a, lds, st);
-      if (e == hipSuccess) e = launch_ws_one<DT, TILE_64x128, 3, 4>(a, lds, st);
-      if (e != hipSuccess) return e;
-    } else if (a->ws_cpg == 2) {
-      return tile == TILE_64x128 ? launch_ws_one<DT, TILE_64x128, 3, 2>(a, lds, st) : launch_ws_one<DT, TILE_128x128, 3, 2>(a, lds, st);
-    } else if (a->ws_cpg == 4 && tile == TILE_64x128) {
-      return launch_ws_one<DT, TILE_64x128, 3, 4>(a, lds, st);
-    }
-  }
-  switch (tile) {
-    DSX_WS_CASE(TILE_128x128)
-    DSX_WS_CASE(TILE_64x128)
-    DSX_WS_CASE(TILE_128x64)
-    DSX_WS_CASE(TILE_256x64)
-    DSX_WS_CASE(TILE_64x64)
-    default: return hipErrorInvalidValue;
-  }
-#undef DSX_WS_CASE
+  return total <= (size_t)v->lds_cap ? total : 0;
 }
 hipError_t launch_conv_ws(int dtype, int tile, int ks, const ConvArgs& a, hipStream_t st) {
   const size_t lds = conv_ws_lds_bytes(dtype, tile, ks, a);
   if (lds == 0 || a.ksplit != 1 || a.ws_wg_per_n < 1 || a.stage_mode != 0) return hipErrorInvalidValue;
   if (a.bias && a.film) return hipErrorInvalidValue;   // the planner folds the conv bias into the FiLM bias
-  return dtype == 1 ? launch_ws_dt<__bf16>(tile, ks, &a, lds, st)
-       : dtype == 2 ? launch_ws_dt<_Float16>(tile, ks, &a, lds, st) : launch_ws_dt<float>(tile, ks, &a, lds, st);
+  return launch_variant(*ws_variant(dtype, tile, ks, a), (unsigned)(a.n_tiles * a.ws_wg_per_n), lds, a, st);
+}
+
+// ---- k_conv_img
+hipError_t launch_conv_img(int dtype, int ks, const ConvArgs& a, hipStream_t st) {
+  const int nphase = (a.C0 + a.C1) / (8 * (dtype != 0 ? 32 : 16));   // 1 .. 8 (conv_img_applicable)
+  const ConvVariant* v = find_variant(FAM_IMG, dtype, -1, ks, 1, (nphase == 2 || nphase == 4) ? nphase : 8);
+  if (!v) return hipErrorInvalidValue;
+  return launch_variant(*v, (unsigned)(a.B * a.nblocks), conv_img_lds(dtype, ks), a, st);
 }
 
 hipError_t conv_init() {
+  static std::mutex mu;
   static bool done = false;
+  std::lock_guard<std::mutex> lock(mu);   // executors may be created from several threads
   if (done) return hipSuccess;
-  for (int dtype = 0; dtype < 3; ++dtype)
-    for (int ks = 1; ks <= 3; ks += 2)
-      for (int tile = 0; tile < TILE_COUNT; ++tile)
-        for (int stride = 1; stride <= 2; ++stride) {
-          if (stride == 2 && !(ks == 3 && tile == TILE_64x64)) continue;
-          hipError_t e = dtype == 1 ? launch_dt<__bf16>(tile, ks, stride, nullptr, 0, nullptr)
-                       : dtype == 2 ? launch_dt<_Float16>(tile, ks, stride, nullptr, 0, nullptr)
-                                    : launch_dt<float>(tile, ks, stride, nullptr, 0, nullptr);
-          if (e != hipSuccess) return e;
-          if (stride == 1 && ws_tile_ok(tile)) {
-            e = dtype == 1 ? launch_ws_dt<__bf16>(tile, ks, nullptr, 0, nullptr)
-              : dtype == 2 ? launch_ws_dt<_Float16>(tile, ks, nullptr, 0, nullptr)
-                           : launch_ws_dt<float>(tile, ks, nullptr, 0, nullptr);
-            if (e != hipSuccess) return e;
-          }
-        }
-  {
-    hipError_t e = launch_g2<float>(0, nullptr, 0, nullptr);
-    if (e == hipSuccess) e = launch_g2<__bf16>(0, nullptr, 0, nullptr);
-    if (e == hipSuccess) e = launch_g2<_Float16>(0, nullptr, 0, nullptr);
-    if (e != hipSuccess) return e;
-  }
-  for (int ks = 1; ks <= 3; ks += 2) {
-    hipError_t e = launch_img_dt<float>(ks, nullptr, 0, nullptr);
-    if (e == hipSuccess) e = launch_img_dt<__bf16>(ks, nullptr, 0, nullptr);
-    if (e == hipSuccess) e = launch_img_dt<_Float16>(ks, nullptr, 0, nullptr);
+  for (const ConvVariant& v : kVariants) {
+    const hipError_t e = hipFuncSetAttribute((const void*)v.kern, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_cap);
     if (e != hipSuccess) return e;
   }
   done = true;

@@ -1,6 +1,6 @@
 // dsx_kernels.h — launch interface between the host runtime (dsx_runtime.cpp)
-// and the gfx950 kernels (dsx_kernels.hip).  Internal; the public ABI is
-// include/dsx.h.
+// and the gfx950 kernels (dsx_conv.hip, dsx_ops.hip, dsx_attn.hip).  Internal;
+// the public ABI is include/dsx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -223,8 +223,8 @@ struct ConvArgs {
                           // 2 with a 3x3: the two-chunk variant of k_conv_mfma (64 input channels per barrier: a
                           // 64-channel layer is ONE group, no K loop)
   int ws_wg_per_n;        // warp-specialised kernel: persistent workgroups per N tile (0: k_conv_mfma)
-  int ws_cpg;             // k_conv_ws: chunks per (tile, group) item other than the family default -- 2 for a 3 x 3 conv (lds_row =
-                          // conv_lds_row_g2), 4 for a 1 x 1 conv (conv_lds_row_1x1_c4); 64- and 128-pixel tiles: the loaders'
+  int ws_cpg;             // k_conv_ws: chunks per (tile, group) item other than the family default -- 2 or 4 for a 3 x 3 conv, 4 for
+                          // a 1 x 1 conv (lds_row = conv_lds_row of that many chunks); 64- and 128-pixel tiles: the loaders'
                           // per-item costs are paid once per 64 / 128 input channels
   int xcd_bands;          // k_conv_ws: an XCD's workgroups take a contiguous band of M tiles (else round-robin)
   // k_conv_ws start-up without integer divisions (a dozen of them cost ~2000 cycles before the first DMA could be issued):
@@ -258,23 +258,30 @@ struct ConvArgs {
   long long slab_stride;  // elements between slabs
 };
 
-// tile configurations compiled for the MFMA conv kernel
+// tile configurations compiled for the MFMA conv kernels
 enum ConvTile { TILE_256x128 = 0, TILE_128x128, TILE_64x128, TILE_256x64, TILE_128x64, TILE_64x64, TILE_128x32, TILE_256x32, TILE_COUNT };
-struct ConvTileInfo { int BM, BN; };
-ConvTileInfo conv_tile_info(int tile);
-int conv_tile_wm(int tile);   // waves along M (one statistics row per (tile, wm))
-bool conv_tile_fuses_stats(int tile);   // k_conv_mfma
-bool conv_ws_fuses_stats(int tile);     // k_conv_ws
-int conv_ws_tile_wm(int tile);          // k_conv_ws lays its waves out differently
+// pixels x output channels of a tile, waves along M (one statistics row per (tile, wm)), and whether the epilogue can
+// emit the GroupNorm statistics of the result; `ws`: as k_conv_ws lays the tile out (k_conv_mfma otherwise).  All zero
+// when the kernel is not compiled for the tile.
+struct ConvTileInfo { int BM, BN, WM; bool fuses_stats; };
+ConvTileInfo conv_tile_info(int tile, bool ws = false);
 // input-channel chunks are staged in groups of this many (weights are packed/padded to it)
 int conv_chunk_multiple(int ks);
-int conv_lds_row(int ks, int stride, int tw_log2);
-// two-chunk-per-group 3x3 variant of k_conv_mfma (ConvArgs::cpg == 2): TILE_128x64 (experiment) and the narrow-output
-// tiles TILE_256x32 / TILE_128x32 (convs with <= 32 output channels, e.g. the UNet's final conv)
-int conv_lds_row_g2(int tw_log2);
-int conv_lds_row_3x3_c(int tw_log2, int cpg);   // 3 x 3 conv of k_conv_ws with cpg chunks per item (ConvArgs::ws_cpg == 4)
-int conv_lds_row_1x1_c4(int tw_log2);   // 1 x 1 conv of k_conv_ws with four chunks per item (ConvArgs::ws_cpg == 4)
-size_t conv_g2_lds_bytes(int tile, const ConvArgs& a);
+// LDS bytes per patch row of a tile 2^tw_log2 pixels wide with `cpg` 64-byte chunks per pixel (the family default
+// conv_chunk_multiple(ks), ConvArgs::cpg or ConvArgs::ws_cpg).  The A fragment of a 32-row block is read with
+// ds_read_b128, whose 16-lane groups cover rows {0-3,12-15,20-27} / {4-11,16-19,28-31}: with 16-wide tiles the pitch must
+// be a multiple of 256 B, with 8-wide tiles an odd multiple of 128 B, for the 16 reads to fall on 16 distinct 16-B slots.
+constexpr int conv_lds_row(int ks, int stride, int tw_log2, int cpg) {
+  const int pixb = 64 * cpg + 16;
+  const int pw = ((1 << tw_log2) - 1) * stride + ks;
+  int rb = (pw * pixb + 15) & ~15;
+  if (ks == 1 || stride != 1) return rb;   // no halo: consecutive pixels already conflict-free
+  if (tw_log2 == 4) rb = (rb + 255) & ~255;
+  else if (tw_log2 == 3) { rb = (rb + 127) & ~127; if (((rb >> 7) & 1) == 0) rb += 128; }
+  return rb;
+}
+// k_conv_mfma.  With ConvArgs::cpg == 2 and a 3 x 3 conv: its two-chunk-per-group form, TILE_128x64 (experiment) and the
+// narrow-output tiles TILE_256x32 / TILE_128x32 (convs with <= 32 output channels, e.g. the UNet's final conv).
 // LDS bytes needed by a launch; 0 if the geometry is not supported by `tile`
 size_t conv_lds_bytes(int dtype, int tile, int ks, int stride, const ConvArgs& a);
 hipError_t launch_conv(int dtype, int tile, int ks, int stride, const ConvArgs& a, hipStream_t st);

@@ -873,14 +873,14 @@ static bool tile_geometry(int dtype, int tile, int ks, int stride, int ablate, c
   c.m_tiles = c.tiles_x * c.tiles_y * ((a.B + TB - 1) / TB);
   c.n_tiles = (c.nblocks * 32 + ti.BN - 1) / ti.BN;
   c.ksplit = 1; c.groups_per_split = a.kchunks / conv_chunk_multiple(ks); c.slab_stride = 0;
-  c.lds_row = conv_lds_row(ks, stride, c.tw_log2);
+  c.lds_row = conv_lds_row(ks, stride, c.tw_log2, conv_chunk_multiple(ks));
   c.ablate = ablate;
   return conv_lds_bytes(dtype, tile, ks, stride, c) != 0;
 }
 
 // geometry of `tile` on the two-chunk (cpg = 2) variant of k_conv_mfma: one image per M tile, one N tile, every two
 // 64-byte chunks one staged group; false if the tile cannot be used
-static bool g2_geometry(int tile, const ConvArgs& a, ConvArgs& g) {
+static bool g2_geometry(int dtype, int tile, const ConvArgs& a, ConvArgs& g) {
   const ConvTileInfo ti = conv_tile_info(tile);
   const int TW = pow2_divisor(a.Wo, 16), TH = pow2_divisor(a.Ho, std::max(1, ti.BM / TW));
   if (TW * TH != ti.BM) return false;
@@ -891,9 +891,9 @@ static bool g2_geometry(int tile, const ConvArgs& a, ConvArgs& g) {
   g.m_tiles = g.tiles_x * g.tiles_y * a.B;
   g.n_tiles = 1;
   g.ksplit = 1; g.groups_per_split = a.kchunks / 2; g.slab_stride = 0;
-  g.lds_row = conv_lds_row_g2(g.tw_log2);
+  g.lds_row = conv_lds_row(3, 1, g.tw_log2, 2);
   g.ablate = 0;
-  return conv_g2_lds_bytes(tile, g) != 0;
+  return conv_lds_bytes(dtype, tile, 3, 1, g) != 0;
 }
 
 namespace {
@@ -942,7 +942,7 @@ static bool decide_tile(const PlanKnobs& k, int dtype, int ks, int stride, bool 
   if (k.narrow_g2 && ks == 3 && stride == 1 && a.Cout <= 32 && a.stage_mode == 0 && a.kchunks % 2 == 0 &&
       a.C0 % gw2 == 0 && a.C1 % gw2 == 0 && !a.up) {
     for (int tile : k.tiles_narrow_g2)
-      if (g2_geometry(tile, a, c)) { a = c; tile_out = tile; return true; }
+      if (g2_geometry(dtype, tile, a, c)) { a = c; tile_out = tile; return true; }
   }
   if (ws_allowed) {
     const std::vector<int>& ws_wide =
@@ -997,17 +997,17 @@ static int ws_wg_per_n(const ConvArgs& a) {
 
 // k_conv_ws, chunks per (tile, group) item: several 64-byte chunks where the geometry allows it (PlanKnobs::ws_g2, ws_c4)
 static void decide_ws_chunks(const PlanKnobs& k, int dtype, int ks, int tile, ConvArgs& a) {
-  auto take = [&](bool wanted, int cpg, int lds_row) {
+  auto take = [&](bool wanted, int cpg) {
     ConvArgs t = a;
-    t.ws_cpg = cpg; t.lds_row = lds_row;
-    if (wanted && conv_ws_lds_bytes(dtype, tile, ks, t) != 0) { a.ws_cpg = cpg; a.lds_row = lds_row; }
+    t.ws_cpg = cpg; t.lds_row = conv_lds_row(ks, 1, a.tw_log2, cpg);
+    if (wanted && conv_ws_lds_bytes(dtype, tile, ks, t) != 0) { a.ws_cpg = cpg; a.lds_row = t.lds_row; }
   };
   if (ks == 3) {
     const int min_chunks = conv_tile_info(tile).BM == 64 ? k.ws_g2_min64 : k.ws_g2_min128;
-    take(k.ws_g2 && a.kchunks >= min_chunks, 2, conv_lds_row_g2(a.tw_log2));
-    take(k.ws_g2 && a.kchunks >= k.ws_g4_min64, 4, conv_lds_row_3x3_c(a.tw_log2, 4));
+    take(k.ws_g2 && a.kchunks >= min_chunks, 2);
+    take(k.ws_g2 && a.kchunks >= k.ws_g4_min64, 4);
   }
-  if (ks == 1) take(k.ws_c4 && a.kchunks >= k.ws_c4_min, 4, conv_lds_row_1x1_c4(a.tw_log2));   // 128 input channels per item
+  if (ks == 1) take(k.ws_c4 && a.kchunks >= k.ws_c4_min, 4);   // 128 input channels per item
 }
 
 // k_conv_ws, blockIdx -> work mapping and its division-free start-up: quotients and fastdiv magics (ConvArgs::ws_map)
@@ -1109,10 +1109,11 @@ static int decide_conv(const PlanKnobs& k, int dtype, int norm_groups, const Con
   // (Tried and rejected in round 3, measured: the GroupNorm finalised by the consuming conv's own compute waves during
   // their start-up wait -- 14 to 22 k_gn_finalize launches fewer, but every such conv started 3-7 us later, the same
   // or more than the launch it replaced cost inside the captured graph: step +0.4 .. +1.1 %.  DESIGN.md section 4.)
-  if (k.fuse_stats && s.want_stats && (use_ws ? conv_ws_fuses_stats(tile) : conv_tile_fuses_stats(tile)) &&
+  const ConvTileInfo ti = conv_tile_info(tile, use_ws);
+  if (k.fuse_stats && s.want_stats && ti.fuses_stats &&
       a.ksplit == 1 && a.tb_log2 == 0 && (a.Cout & 15) == 0 && a.out_ld == a.Cout && (a.resid_ld & 7) == 0) {
     ch.stats = STATS_EPILOGUE;
-    ch.stat_nchunk = a.tiles_x * a.tiles_y * (use_ws ? conv_ws_tile_wm(tile) : conv_tile_wm(tile));
+    ch.stat_nchunk = a.tiles_x * a.tiles_y * ti.WM;
   }
   if (a.ksplit > 1 && k.fuse_stats && s.want_stats && a.Cout % 64 == 0 && a.out_ld == a.Cout && (a.Ho * a.Wo) % 16 == 0) {
     ch.stats = STATS_REDUCE;   // statistics in the reduce launch, shifted by bias + film
