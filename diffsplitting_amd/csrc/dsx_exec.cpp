@@ -1,0 +1,386 @@
+// dsx_exec.cpp — the executor: life cycle and introspection, the profiling entry points, the UNet forward, the
+// graph-captured sampling loop, single steps and the time-predictor head.  C ABI in include/dsx.h.
+#include "dsx_rt.h"
+
+// ------------------------------------------------------------------ executor
+// An executor of `m` for (B, H, W) that has yet to be planned: knobs read, conv_naive taken from the model.
+std::unique_ptr<dsx_exec> dsx::new_exec(dsx_model* m, int B, int H, int W, int cond_channels) {
+  auto ex = std::make_unique<dsx_exec>();
+  ex->m = m; ex->B = B; ex->H = H; ex->W = W;
+  ex->knobs = read_plan_knobs();
+  ex->knobs.conv_naive = m->want_naive;   // the model's device image decides (naive weights exist only then)
+  ex->cond_c = cond_channels; ex->x_c = m->cfg.in_channel - cond_channels;
+  return ex;
+}
+
+extern "C" int dsx_exec_create(dsx_model* m, int B, int H, int W, int cond_channels, dsx_exec** out) {
+  if (!m || !out || B < 1 || H < 1 || W < 1) return fail(DSX_ERR_INVALID, "bad argument");
+  if (!m->finalized) return fail(DSX_ERR_STATE, "dsx_model_finalize must precede dsx_exec_create");
+  if (cond_channels < 0 || cond_channels >= m->cfg.in_channel) return fail(DSX_ERR_INVALID, "bad cond_channels");
+  HIP_TRY(conv_init());
+  HIP_TRY(ops_init());
+  auto ex = new_exec(m, B, H, W, cond_channels);
+  const int rc = run_planner(ex.get(), nullptr, nullptr);
+  if (rc) return rc;
+  if (hipMemset(ex->step_ctr, 0, 256) != hipSuccess) return fail(DSX_ERR_HIP, "hipMemset failed");
+  *out = ex.release();
+  return DSX_OK;
+}
+
+// Drops the captured graph.  An executable graph may still have launches queued: wait for them before destroying it.
+static int drop_graph(dsx_exec* ex) {
+  if (ex->graph.exec && ex->last_stream) HIP_TRY(hipStreamSynchronize(ex->last_stream));
+  ex->graph.reset();
+  return DSX_OK;
+}
+
+extern "C" void dsx_exec_destroy(dsx_exec* ex) {
+  if (!ex) return;
+  for (auto& sl : ex->staging)   // a pinned slot an asynchronous copy has yet to read
+    if (sl.busy) (void)hipEventSynchronize(sl.ev.e);
+  (void)drop_graph(ex);
+  delete ex;
+}
+extern "C" size_t dsx_exec_workspace_bytes(const dsx_exec* ex) { return ex ? ex->ws_bytes : 0; }
+// Bounded spins of the conv kernel's loader -> compute hand-off (three-image tiles) that gave up since the executor was
+// created: 0 in every correct run; anything else means wrong pixels were produced.  Synchronises the device.
+extern "C" int dsx_exec_handoff_timeouts(dsx_exec* ex, unsigned* count) {
+  if (!ex || !count) return fail(DSX_ERR_INVALID, "null argument");
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(count, ex->handoff_timeouts, sizeof(unsigned), hipMemcpyDeviceToHost));
+  return DSX_OK;
+}
+extern "C" int dsx_exec_num_launches(const dsx_exec* ex) { return ex ? ex->launches : 0; }
+
+extern "C" int dsx_exec_num_ops(const dsx_exec* ex) { return ex ? (int)ex->ops.size() : 0; }
+extern "C" int dsx_exec_num_layers(const dsx_exec* ex) { return ex ? (int)ex->layers.size() : 0; }
+extern "C" int dsx_exec_layer_info(const dsx_exec* ex, int i, dsx_layer_info* info) {
+  if (!ex || !info || i < 0 || i >= (int)ex->layers.size()) return fail(DSX_ERR_INVALID, "bad layer index");
+  *info = ex->layers[i];
+  return DSX_OK;
+}
+extern "C" int dsx_exec_copy_workspace(const dsx_exec* ex, uint64_t src, size_t bytes, void* dst, void* stream) {
+  if (!ex || !dst) return fail(DSX_ERR_INVALID, "null argument");
+  const uint64_t lo = (uint64_t)(uintptr_t)ex->ws, hi = lo + ex->ws_bytes;
+  if (!ex->ws || src < lo || src > hi || bytes > hi - src) return fail(DSX_ERR_INVALID, "range is not inside the workspace");
+  HIP_TRY(hipMemcpyAsync(dst, (const void*)(uintptr_t)src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return DSX_OK;
+}
+extern "C" int dsx_exec_op_info(const dsx_exec* ex, int i, char* desc, int cap, int* kind, double* flops,
+                                double* bytes) {
+  if (!ex || i < 0 || i >= (int)ex->ops.size()) return fail(DSX_ERR_INVALID, "bad op index");
+  const PlanOp& o = ex->ops[i];
+  if (desc && cap > 0) snprintf(desc, cap, "%s", o.desc.c_str());
+  if (kind) *kind = o.kind;
+  if (flops) *flops = o.flops;
+  if (bytes) *bytes = o.bytes;
+  return DSX_OK;
+}
+// diagnostics: the launches of one kind (DSX_OP_*) captured into a graph of their own and replayed `iters` times;
+// *ms_per_replay = mean time of a replay, *launches = how many launches it holds
+extern "C" int dsx_exec_time_kind(dsx_exec* ex, int kind, int iters, float* ms_per_replay, int* launches,
+                                  void* stream) {
+  if (!ex || !ms_per_replay || iters < 1) return fail(DSX_ERR_INVALID, "bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (!st) return fail(DSX_ERR_INVALID, "dsx_exec_time_kind needs a non-default stream (stream capture)");
+  // kind >= 0: the launches of that kind; -1: every launch of the forward; <= -2: every launch except kind (-kind - 2)
+  auto selected = [&](int k) { return kind >= 0 ? k == kind : (kind == -1 ? true : k != -kind - 2); };
+  int n = 0;
+  for (auto& op : ex->ops) n += selected(op.kind) ? 1 : 0;
+  if (launches) *launches = n;
+  if (n == 0) { *ms_per_replay = 0.f; return DSX_OK; }
+  Graph g;
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  hipError_t err = hipSuccess;
+  for (size_t i = 0; i < ex->ops.size() && err == hipSuccess; ++i)
+    if (selected(ex->ops[i].kind)) err = launch_op(ex->ops[i], st);
+  hipError_t e2 = hipStreamEndCapture(st, &g.graph);
+  if (err != hipSuccess || e2 != hipSuccess || !g.graph)
+    return fail(DSX_ERR_HIP, "capture of the kernel family failed: %s", hipGetErrorString(err != hipSuccess ? err : e2));
+  HIP_TRY(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+  Event e0, e1;
+  HIP_TRY(e0.create());
+  HIP_TRY(e1.create());
+  HIP_TRY(hipGraphLaunch(g.exec, st));   // warm-up replay
+  HIP_TRY(hipEventRecord(e0.e, st));
+  for (int it = 0; it < iters; ++it) HIP_TRY(hipGraphLaunch(g.exec, st));
+  HIP_TRY(hipEventRecord(e1.e, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+  *ms_per_replay = ms / iters;
+  return DSX_OK;
+}
+
+// diagnostics: copy the 128 in-kernel stamps of the launch chosen with DSX_STAMP_OP (zeros if none)
+extern "C" int dsx_exec_read_stamps(dsx_exec* ex, unsigned long long* out128) {
+  if (!ex || !out128) return fail(DSX_ERR_INVALID, "null argument");
+  memset(out128, 0, 128 * 8);
+  if (!ex->stamp_buf) return DSX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out128, ex->stamp_buf, 128 * 8, hipMemcpyDeviceToHost));
+  return DSX_OK;
+}
+
+// Eager, event-timed replay of the UNet plan on `stream` (inputs: whatever the
+// buffers hold).  ms_per_op[i] = mean over `iters` of the hipEvent time around launch i.
+extern "C" int dsx_exec_profile(dsx_exec* ex, int iters, float* ms_per_op, void* stream) {
+  if (!ex || !ms_per_op || iters < 1) return fail(DSX_ERR_INVALID, "bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = ex->ops.size();
+  std::vector<Event> ev(2 * n);
+  for (auto& e : ev) HIP_TRY(e.create());
+  std::vector<double> acc(n, 0.0);
+  for (int it = 0; it < iters; ++it) {
+    static const bool trace = getenv("DSX_TRACE") != nullptr;   // debugging: name each launch, sync after it
+    for (size_t i = 0; i < n; ++i) {
+      if (trace) { fprintf(stderr, "[dsx] op %zu: %s\n", i, ex->ops[i].desc.c_str()); fflush(stderr); }
+      HIP_TRY(hipEventRecord(ev[2 * i].e, st));
+      HIP_TRY(launch_op(ex->ops[i], st));
+      HIP_TRY(hipEventRecord(ev[2 * i + 1].e, st));
+      if (trace) HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = 0; i < n; ++i) {
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, ev[2 * i].e, ev[2 * i + 1].e));
+      acc[i] += ms;
+    }
+  }
+  for (size_t i = 0; i < n; ++i) ms_per_op[i] = (float)(acc[i] / iters);
+  return DSX_OK;
+}
+
+// time embedding + UNet body on `st`; inputs already in ex->in_cond / ex->in_x
+static int run_unet(dsx_exec* ex, bool from_table, int n_time, hipStream_t st, int per_sample = 0) {
+  dsx_model* m = ex->m;
+  if (m->cfg.with_time_emb) {
+    TembArgs t{};
+    t.flavour = m->cfg.flavour; t.B = ex->B; t.n_time = n_time;
+    t.time = from_table ? nullptr : ex->time_buf;
+    t.table = ex->table.as<float>(); t.step_ctr = ex->step_ctr; t.per_sample = per_sample;
+    t.inner = m->cfg.inner_channel; t.freq = m->d_freq;
+    t.w1 = m->d_w1; t.b1 = m->d_b1; t.w2 = m->d_w2; t.b2 = m->d_b2;
+    t.wf = m->d_wf; t.bf = m->d_bf; t.F = m->F; t.film = ex->film;
+    HIP_TRY(launch_temb(t, st));
+  }
+  for (auto& op : ex->ops) HIP_TRY(launch_op(op, st));
+  return DSX_OK;
+}
+
+static int load_inputs(dsx_exec* ex, const float* cond_nchw, const float* x_nchw, int x_total_c,
+                       int x_c_off, hipStream_t st);
+
+extern "C" int dsx_unet_forward(dsx_exec* ex, const float* x, const float* time, int n_time, float* y,
+                                void* stream) {
+  if (!ex || !x || !y) return fail(DSX_ERR_INVALID, "null argument");
+  hipStream_t st = (hipStream_t)stream;
+  dsx_model* m = ex->m;
+  if (m->cfg.with_time_emb) {
+    if (!time || !(n_time == 1 || n_time == ex->B)) return fail(DSX_ERR_INVALID, "n_time must be 1 or B");
+    HIP_TRY(hipMemcpyAsync(ex->time_buf, time, (size_t)n_time * 4, hipMemcpyDeviceToDevice, st));
+  }
+  // x is (B, in_channel, H, W): channels [0,cond_c) feed the cond tensor, the rest the state tensor
+  int rc = load_inputs(ex, ex->cond_c ? x : nullptr, x, m->cfg.in_channel, ex->cond_c, st);
+  if (rc) return rc;
+  if ((rc = run_unet(ex, false, n_time, st))) return rc;
+  HIP_TRY(launch_nhwc_to_nchw((const float*)ex->out.p, y, ex->B, ex->out.C, ex->H, ex->W, st));
+  return DSX_OK;
+}
+
+static int load_inputs(dsx_exec* ex, const float* cond_nchw, const float* x_nchw, int x_total_c,
+                       int x_c_off, hipStream_t st) {
+  const int HW = ex->H * ex->W;
+  if (ex->cond_c) {
+    if (!cond_nchw) return fail(DSX_ERR_INVALID, "this executor was created with cond_channels > 0");
+    const int ctot = (cond_nchw == x_nchw) ? x_total_c : ex->cond_c;
+    HIP_TRY(dsx::launch_nchw_slice_to_nhwc(cond_nchw, ex->in_cond.p, ex->in_cond.st, ex->B, ex->cond_c, ctot,
+                                           0, HW, st));
+  }
+  HIP_TRY(dsx::launch_nchw_slice_to_nhwc(x_nchw, ex->in_x.p, ex->in_x.st, ex->B, ex->x_c, x_total_c, x_c_off,
+                                         HW, st));
+  if (ex->in_x.st)   // the sampler state itself stays fp32
+    HIP_TRY(dsx::launch_nchw_slice_to_nhwc(x_nchw, ex->x_state, 0, ex->B, ex->x_c, x_total_c, x_c_off, HW, st));
+  return DSX_OK;
+}
+
+// ------------------------------------------------------------------ sampler
+static int ensure_table(dsx_exec* ex, const dsx_step_table* tab) {
+  const int T = tab->n_steps * (tab->per_sample > 0 ? tab->per_sample : 1);   // values per column
+  if (T > ex->table_cap) {
+    // the table's column stride (= capacity) is baked into captured graphs: drop them
+    const int rc = drop_graph(ex);
+    if (rc) return rc;
+    const int cap = std::max(T, 2048);
+    HIP_TRY(ex->table.alloc((size_t)6 * cap * sizeof(float)));
+    ex->table_cap = cap;
+  }
+  return DSX_OK;
+}
+
+// a pinned staging slot holding this call's table [6][cap] followed by {seed, noise address}; *out = its host pointer
+static int stage_call(dsx_exec* ex, const dsx_step_table* tab, uint64_t seed, const float* noise, dsx_exec::Staging** out) {
+  const int cap = ex->table_cap;
+  const int T = tab->n_steps * (tab->per_sample > 0 ? tab->per_sample : 1);
+  const size_t need = (size_t)6 * cap + 4;   // + 16 bytes of loop parameters
+  dsx_exec::Staging& sl = ex->staging[ex->staging_next];
+  ex->staging_next = (ex->staging_next + 1) % 4;
+  if (sl.busy) { HIP_TRY(hipEventSynchronize(sl.ev.e)); sl.busy = false; }
+  if (sl.floats < need) {
+    sl.floats = 0;
+    HIP_TRY(sl.host.alloc(need * sizeof(float)));
+    sl.floats = need;
+  }
+  if (!sl.ev.e) HIP_TRY(sl.ev.create(hipEventDisableTiming));
+  float* host = sl.host.as<float>();
+  memset(host, 0, (size_t)6 * cap * sizeof(float));
+  const float* cols[6] = {tab->tcond, tab->a, tab->b, tab->c1, tab->c2, tab->sigma};
+  for (int k = 0; k < 6; ++k)
+    if (cols[k]) memcpy(host + (size_t)k * cap, cols[k], (size_t)T * 4);
+  unsigned long long lp[2] = {seed, (unsigned long long)(uintptr_t)noise};
+  memcpy(host + (size_t)6 * cap, lp, 16);
+  *out = &sl;
+  return DSX_OK;
+}
+
+static int enqueue_step(dsx_exec* ex, const dsx_step_table* tab, bool use_noise, hipStream_t st) {
+  int rc = run_unet(ex, true, tab->per_sample > 0 ? ex->B : 1, st, tab->per_sample > 0 ? 1 : 0);
+  if (rc) return rc;
+  UpdateArgs u{};
+  u.x = ex->x_state; u.x_act = ex->in_x.st ? ex->in_x.p : nullptr; u.x_act_kind = ex->in_x.st;
+  u.net = (const float*)ex->out.p; u.use_noise = use_noise ? 1 : 0; u.loop_params = ex->loop_params;
+  u.tab = ex->table.as<float>(); u.n_steps = ex->table_cap; u.step_ctr = ex->step_ctr;
+  u.predict_eps = tab->predict_eps; u.clip = tab->clip; u.per_sample = tab->per_sample > 0 ? 1 : 0;
+  u.B = ex->B; u.C = ex->x_c; u.H = ex->H; u.W = ex->W;
+  HIP_TRY(launch_update(u, st));
+  HIP_TRY(launch_advance(ex->step_ctr, st));
+  return DSX_OK;
+}
+
+extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x,
+                               const float* noise, uint64_t seed, const int32_t* snap_steps, int n_snap,
+                               float* snaps, int use_graph, void* stream) {
+  if (!ex || !tab || !x || tab->n_steps < 1) return fail(DSX_ERR_INVALID, "bad argument");
+  if (!tab->tcond || !tab->c1 || !tab->c2 || !tab->sigma || (tab->predict_eps && (!tab->a || !tab->b)))
+    return fail(DSX_ERR_INVALID, "step table columns missing");
+  if (ex->out.C != ex->x_c)
+    return fail(DSX_ERR_INVALID, "UNet out_channel (%d) must equal the state channels (%d)", ex->out.C, ex->x_c);
+  if (n_snap > 0 && (!snap_steps || !snaps)) return fail(DSX_ERR_INVALID, "snapshot arrays missing");
+  if (tab->per_sample != 0 && tab->per_sample != ex->B)
+    return fail(DSX_ERR_INVALID, "per_sample step table for %d samples, executor batch %d", tab->per_sample, ex->B);
+  hipStream_t st = (hipStream_t)stream;
+  const int T = tab->n_steps;
+  int rc = ensure_table(ex, tab);
+  if (rc) return rc;
+  // per-call values (step table; seed, noise address: the captured step does not bake them in) go to device memory
+  // from a pinned staging slot of this call's own
+  dsx_exec::Staging* sl = nullptr;
+  if ((rc = stage_call(ex, tab, seed, noise, &sl))) return rc;
+  HIP_TRY(hipMemcpyAsync(ex->table.p, sl->host.p, (size_t)6 * ex->table_cap * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ex->loop_params, sl->host.as<float>() + (size_t)6 * ex->table_cap, 16, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(sl->ev.e, st));
+  sl->busy = true;
+  HIP_TRY(hipMemsetAsync(ex->step_ctr, 0, 4, st));
+  if ((rc = load_inputs(ex, cond, x, ex->x_c, 0, st))) return rc;
+
+  const size_t snap_elems = (size_t)ex->B * ex->x_c * ex->H * ex->W;
+  bool graph_ok = false;
+  if (use_graph) {
+    // the captured step bakes in the mode flags only (not the step count, the seed or the noise address)
+    std::vector<float> sig = {(float)tab->predict_eps, (float)tab->clip, noise ? 1.f : 0.f, tab->per_sample > 0 ? 1.f : 0.f};
+    if (!ex->graph.exec || sig != ex->graph_sig) {
+      if ((rc = drop_graph(ex))) return rc;
+      Stream cs;
+      HIP_TRY(cs.create(hipStreamNonBlocking));
+      hipError_t e = hipStreamBeginCapture(cs.s, hipStreamCaptureModeThreadLocal);
+      if (e == hipSuccess) {
+        rc = enqueue_step(ex, tab, noise != nullptr, cs.s);
+        hipError_t e2 = hipStreamEndCapture(cs.s, &ex->graph.graph);
+        if (rc == DSX_OK && e2 == hipSuccess) e2 = hipGraphInstantiate(&ex->graph.exec, ex->graph.graph, nullptr, nullptr, 0);
+        if (rc != DSX_OK || e2 != hipSuccess) {
+          (void)hipGetLastError();
+          ex->graph.reset();
+        }
+      } else {
+        (void)hipGetLastError();
+      }
+      if (ex->graph.exec) ex->graph_sig = sig;
+      else if (rc != DSX_OK) return rc;
+    }
+    graph_ok = ex->graph.exec != nullptr;
+    if (!graph_ok) return fail(DSX_ERR_HIP, "hipGraph capture of the sampling step failed");
+    ex->last_stream = st;
+  }
+  int snap_i = 0;
+  for (int s = 0; s < T; ++s) {
+    if (graph_ok) HIP_TRY(hipGraphLaunch(ex->graph.exec, st));
+    else if ((rc = enqueue_step(ex, tab, noise != nullptr, st))) return rc;
+    while (snap_i < n_snap && snap_steps[snap_i] == s) {
+      HIP_TRY(launch_nhwc_to_nchw(ex->x_state, snaps + (size_t)snap_i * snap_elems, ex->B, ex->x_c, ex->H,
+                                  ex->W, st));
+      ++snap_i;
+    }
+  }
+  HIP_TRY(launch_nhwc_to_nchw(ex->x_state, x, ex->B, ex->x_c, ex->H, ex->W, st));
+  return DSX_OK;
+}
+
+// ---- single reverse steps: one-row step tables through dsx_sample_loop, no graph (nothing to replay)
+extern "C" int dsx_sr3_step(dsx_exec* ex, float noise_level, float sqrt_recip_ac, float sqrt_recipm1_ac, float coef1,
+                            float coef2, float sigma, int clip_denoised, const float* cond, float* x, const float* noise,
+                            uint64_t seed, void* stream) {
+  dsx_step_table t{};
+  t.n_steps = 1; t.tcond = &noise_level; t.a = &sqrt_recip_ac; t.b = &sqrt_recipm1_ac; t.c1 = &coef1; t.c2 = &coef2;
+  t.sigma = &sigma; t.predict_eps = 1; t.clip = clip_denoised ? 1 : 0; t.per_sample = 0;
+  return dsx_sample_loop(ex, &t, cond, x, noise, seed, nullptr, 0, nullptr, 0, stream);
+}
+extern "C" int dsx_indi_step(dsx_exec* ex, float t_cur, float c_x0, float c_xt, float noise_scale, float* x,
+                             const float* noise, uint64_t seed, void* stream) {
+  dsx_step_table t{};
+  t.n_steps = 1; t.tcond = &t_cur; t.c1 = &c_x0; t.c2 = &c_xt; t.sigma = &noise_scale;
+  t.predict_eps = 0; t.clip = 0; t.per_sample = 0;
+  return dsx_sample_loop(ex, &t, nullptr, x, noise, seed, nullptr, 0, nullptr, 0, stream);
+}
+
+extern "C" int dsx_randn(float* out, int64_t n, uint64_t seed, uint64_t subseq, void* stream) {
+  if (!out || n < 0) return fail(DSX_ERR_INVALID, "bad argument");
+  if (n == 0) return DSX_OK;
+  HIP_TRY(launch_randn(out, n, seed, subseq, (hipStream_t)stream));
+  return DSX_OK;
+}
+
+// ------------------------------------------------------------------ time predictor head
+extern "C" int dsx_time_predictor_set_mask(dsx_exec* ex, const float* w, const float* b) {
+  if (!ex || !w || !b) return fail(DSX_ERR_INVALID, "null argument");
+  const int cin = ex->m->cfg.in_channel;
+  if (ex->out.C != 1) return fail(DSX_ERR_INVALID, "TimePredictor head expects out_channel == 1");
+  const size_t nw = (size_t)49 * cin;
+  std::vector<float> hw(nw);
+  for (int ci = 0; ci < cin; ++ci)
+    for (int t = 0; t < 49; ++t) hw[(size_t)t * cin + ci] = w[(size_t)ci * 49 + t];  // (1,in,7,7) -> [49][in]
+  if (!ex->tp_w.p) HIP_TRY(ex->tp_w.alloc((nw + 64) * 4 + (size_t)ex->B * ex->H * ex->W * 4));
+  ex->tp_b = ex->tp_w.as<float>() + nw;
+  ex->tp_mask = ex->tp_w.as<float>() + nw + 64;
+  HIP_TRY(hipMemcpy(ex->tp_w.p, hw.data(), nw * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ex->tp_b, b, 4, hipMemcpyHostToDevice));
+  return DSX_OK;
+}
+
+extern "C" int dsx_time_predictor_forward(dsx_exec* ex, const float* x, float* t_out, void* stream) {
+  if (!ex || !x || !t_out) return fail(DSX_ERR_INVALID, "null argument");
+  if (!ex->tp_w.p) return fail(DSX_ERR_STATE, "dsx_time_predictor_set_mask first");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = load_inputs(ex, nullptr, x, ex->m->cfg.in_channel, 0, st);
+  if (rc) return rc;
+  if ((rc = run_unet(ex, false, 1, st))) return rc;
+  NaiveConvArgs na{};
+  na.c.src0 = ex->in_x.p; na.c.C0 = ex->x_c; na.c.C1 = 0;
+  na.c.act_bf16 = ex->in_x.st; na.c.out_bf16 = 0;
+  na.c.B = ex->B; na.c.Hs = ex->H; na.c.Ws = ex->W; na.c.Ho = ex->H; na.c.Wo = ex->W;
+  na.c.bias = ex->tp_b; na.c.out = ex->tp_mask; na.c.out_ld = 1; na.c.Cout = 1;
+  na.w = ex->tp_w.as<float>(); na.ks = 7; na.stride = 1; na.sigmoid_out = 1;
+  HIP_TRY(launch_conv_naive(na, st));
+  HIP_TRY(launch_masked_mean((const float*)ex->out.p, ex->tp_mask, ex->B, (long long)ex->H * ex->W, t_out, st));
+  return DSX_OK;
+}

@@ -1,4 +1,4 @@
-// dsx_kernels.h — launch interface between the host runtime (dsx_runtime.cpp)
+// dsx_kernels.h — launch interface between the host runtime (dsx_*.cpp)
 // and the gfx950 kernels (dsx_conv.hip, dsx_ops.hip, dsx_attn.hip).  Internal;
 // the public ABI is include/dsx.h.
 #pragma once
@@ -294,7 +294,7 @@ hipError_t launch_conv_ws(int dtype, int tile, int ks, const ConvArgs& a, hipStr
 bool conv_img_applicable(int dtype, int ks, int stride, const ConvArgs& a, bool gn, int gn_groups);
 hipError_t launch_conv_img(int dtype, int ks, const ConvArgs& a, hipStream_t st);
 // first conv of the UNet (1..7 input channels): the 9 taps x Cin receptive field as ONE K dimension on the MFMA;
-// a.wpack = the im2col-ordered pack (pack_first in dsx_runtime.cpp).  One GroupNorm partial row per (16x16 tile, wave).
+// a.wpack = the im2col-ordered pack (pack_first in dsx_model.cpp).  One GroupNorm partial row per (16x16 tile, wave).
 bool conv_first_applicable(int ks, int stride, const ConvArgs& a, bool gn);
 hipError_t launch_conv_first(int dtype, const ConvArgs& a, hipStream_t st);
 // one-time function attributes (dynamic LDS limit); call outside any stream capture
