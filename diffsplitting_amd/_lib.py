@@ -99,6 +99,10 @@ SIGNATURES = {
     "dsx_image_metrics_blocks": (_i, [_i, _i]),
     "dsx_image_metrics": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp,
                                C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
+    "dsx_lpips_create": (_i, [C.POINTER(_vp), _pi64, C.POINTER(_vp), _pi64, C.POINTER(_vp)]),
+    "dsx_lpips_destroy": (None, [_vp]),
+    "dsx_lpips_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "dsx_lpips_frames": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "dsx_tileplan_create": (_i, [_pi64, _pi64, _pi64, _i, C.POINTER(_vp)]),
     "dsx_tileplan_destroy": (None, [_vp]),
     "dsx_tileplan_total": (_i64, [_vp]),

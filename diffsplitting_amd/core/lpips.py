@@ -1,0 +1,185 @@
+"""LPIPS (AlexNet, version 0.1, spatial off) on the MI355X: the ``lpips.LPIPS(net='alex')`` the evaluation notebooks
+build (notebooks/EvaluateJointIndi.ipynb cell 31, EvaluateJointIndiIterative.ipynb cell 28), on ``dsx_lpips_*``
+(include/dsx.h).
+
+Weights are always supplied by the caller -- a state dict, a local file, or the file(s) the environment variable
+``DSX_LPIPS_WEIGHTS`` names -- and are never fetched.  Two key layouts are accepted: ``lpips.LPIPS.state_dict()``'s
+(``net.slice{1..5}.{0,3,6,8,10}.{weight,bias}``, ``lin{0..4}.model.1.weight``) and the split form (torchvision's
+AlexNet ``features.{0,3,6,8,10}.*`` plus the ``lin{k}.model.1.weight`` of the package's ``alex.pth``).  There is no CPU
+fallback: ``forward`` raises DsxError without a HIP device.  Parity is checked against a float64 restatement of the
+algorithm (tests/lpips_ref.py); it is unpinned against the ``lpips`` package itself.
+"""
+import ctypes as C
+import os
+
+import torch
+
+from .. import _lib
+from .._lib import DsxError, check, lib
+
+SHIFT = (-.030, -.088, -.188)
+SCALE = (.458, .448, .450)
+# (slice, index inside torchvision's features, weight shape)
+TRUNK = ((1, 0, (64, 3, 11, 11)), (2, 3, (192, 64, 5, 5)), (3, 6, (384, 192, 3, 3)), (4, 8, (256, 384, 3, 3)),
+         (5, 10, (256, 256, 3, 3)))
+LIN_CHANNELS = (64, 192, 384, 256, 256)
+ENV = "DSX_LPIPS_WEIGHTS"
+
+_NO_WEIGHTS = (
+    "LPIPS needs its weights from the caller and never fetches them. Supply two local files (or one state dict "
+    "holding both): torchvision's ImageNet AlexNet checkpoint (keys features.{0,3,6,8,10}.weight/bias) and the lpips "
+    "package's weights/v0.1/alex.pth (keys lin{0..4}.model.1.weight) -- as state_dict=, as weights_path= (one path or "
+    f"a list of paths), or as {ENV}=<path>[{os.pathsep}<path>]. A saved lpips.LPIPS(net='alex').state_dict() "
+    "holds both.")
+
+
+def _load_files(paths):
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [p for p in os.fspath(paths).split(os.pathsep) if p]
+    sd = {}
+    for p in paths:
+        if not os.path.isfile(p):
+            raise DsxError(f"LPIPS weight file {p!r} does not exist. " + _NO_WEIGHTS)
+        part = torch.load(p, map_location="cpu", weights_only=True)
+        if not isinstance(part, dict):
+            raise DsxError(f"LPIPS weight file {p!r} does not hold a state dict")
+        sd.update(part)
+    return sd
+
+
+def split_state_dict(sd):
+    """A state dict in either accepted key layout -> (10 trunk tensors, 5 lin tensors), fp32 CPU contiguous, shapes
+    checked by key name.  Raises DsxError on a missing or unknown key, a wrong shape, or scaling-layer buffers that
+    differ from the constants the kernels apply."""
+    sd = dict(sd)
+    trunk, lin = [], []
+    used = set()
+
+    def take(names, shape):
+        for n in names:
+            if n in sd:
+                t = torch.as_tensor(sd[n]).detach()
+                if tuple(t.shape) != tuple(shape):
+                    raise DsxError(f"LPIPS weights: {n} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+                used.add(n)
+                return t.to(torch.float32).cpu().contiguous()
+        raise DsxError(f"LPIPS weights: missing {' (or '.join(names)}{')' if len(names) > 1 else ''}. " + _NO_WEIGHTS)
+
+    for k, idx, shape in TRUNK:
+        trunk.append(take((f"net.slice{k}.{idx}.weight", f"features.{idx}.weight"), shape))
+        trunk.append(take((f"net.slice{k}.{idx}.bias", f"features.{idx}.bias"), shape[:1]))
+    for k, ch in enumerate(LIN_CHANNELS):
+        lin.append(take((f"lin{k}.model.1.weight", f"lins.{k}.model.1.weight"), (1, ch, 1, 1)))
+    for name, const in (("scaling_layer.shift", SHIFT), ("scaling_layer.scale", SCALE)):
+        if name in sd:
+            got = torch.as_tensor(sd[name]).detach().to(torch.float32).flatten()
+            if got.numel() != 3 or not torch.equal(got, torch.tensor(const, dtype=torch.float32)):
+                raise DsxError(f"LPIPS weights: {name} = {got.tolist()} differs from the v0.1 constants {const}")
+            used.add(name)
+    known = _alias_names()
+    for n in sd:
+        # the other layout's spelling of a tensor already taken, the package's `lins` list, torchvision's classifier
+        if n in used or n in known or n.startswith(("lins.", "classifier.")):
+            continue
+        raise DsxError(f"LPIPS weights: unexpected key {n!r} (an AlexNet v0.1 state dict has net.slice*/features.*, "
+                       "lin*.model.1.weight and scaling_layer.* only)")
+    return trunk, lin
+
+
+def _alias_names():
+    names = set()
+    for k, idx, _ in TRUNK:
+        for leaf in ("weight", "bias"):
+            names.add(f"net.slice{k}.{idx}.{leaf}")
+            names.add(f"features.{idx}.{leaf}")
+    for k in range(5):
+        names.add(f"lin{k}.model.1.weight")
+    return names
+
+
+class LPIPS(torch.nn.Module):
+    """``lpips.LPIPS(net='alex', version='0.1', spatial=False)`` with caller-supplied weights.
+
+    ``forward(in0, in1, retPerLayer=False, normalize=False)``: (B, 3, H, W) (or (3, H, W)) pairs in [-1, 1]
+    ([0, 1] with ``normalize=True``) -> (B, 1, 1, 1) on the device, plus the list of the five tap values with
+    ``retPerLayer=True``."""
+
+    def __init__(self, net='alex', version='0.1', spatial=False, state_dict=None, weights_path=None):
+        super().__init__()
+        if net not in ('alex', 'alexnet'):
+            raise DsxError(f"LPIPS(net={net!r}) is not built: only net='alex' (VGG and SqueezeNet trunks are out of scope)")
+        if str(version) != '0.1':
+            raise DsxError(f"LPIPS(version={version!r}) is not built: only version='0.1'")
+        if spatial:
+            raise DsxError("LPIPS(spatial=True) is not built: only the spatial average (spatial=False)")
+        if state_dict is None:
+            path = weights_path or os.environ.get(ENV)
+            if not path:
+                raise DsxError(_NO_WEIGHTS)
+            state_dict = _load_files(path)
+        trunk, lin = split_state_dict(state_dict)
+        self._keep = trunk + lin                                       # host tensors the library reads during create
+        ptr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        cnt = lambda ts: (C.c_int64 * len(ts))(*[t.numel() for t in ts])
+        h = C.c_void_p()
+        check(lib.dsx_lpips_create(ptr(trunk), cnt(trunk), ptr(lin), cnt(lin), C.byref(h)))
+        self._h = h
+        self._keep = None
+
+    def __del__(self):
+        h = self.__dict__.get("_h")
+        if h:
+            self.__dict__["_h"] = None
+            lib.dsx_lpips_destroy(h)
+
+    @staticmethod
+    def _device(*tensors):
+        _lib.require_gpu()
+        for t in tensors:
+            if t.is_cuda:
+                return t.device
+        return torch.device("cuda", torch.cuda.current_device())
+
+    @torch.no_grad()
+    def forward(self, in0, in1, retPerLayer=False, normalize=False):
+        dev = self._device(in0, in1)
+        if in0.dim() == 3:
+            in0, in1 = in0[None], in1[None]
+        if in0.shape != in1.shape or in0.dim() != 4 or in0.shape[1] != 3:
+            raise ValueError(f"LPIPS takes two (B, 3, H, W) tensors of one shape, got {tuple(in0.shape)} and "
+                             f"{tuple(in1.shape)}")
+        a = in0.to(dev, torch.float32).contiguous()
+        b = in1.to(dev, torch.float32).contiguous()
+        if normalize:
+            a, b = 2 * a - 1, 2 * b - 1
+        B, _, H, W = a.shape
+        out = torch.empty((B,), dtype=torch.float32, device=dev)
+        taps = torch.empty((B, 5), dtype=torch.float32, device=dev) if retPerLayer else None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            check(lib.dsx_lpips_forward(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), B, H, W,
+                                        C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(taps.data_ptr()) if retPerLayer else None, C.c_void_p(stream)))
+        val = out.view(B, 1, 1, 1)
+        if retPerLayer:
+            return val, [taps[:, k].reshape(B, 1, 1, 1) for k in range(5)]
+        return val
+
+    @torch.no_grad()
+    def frames(self, target, pred, channel, chunk=0):
+        """compute_lpips of the notebooks for one channel: ``target`` / ``pred`` (N, H, W, C) fp32 channel-last device
+        tensors -> N values (device tensor).  ``chunk``: frames per pass (0 = the library's choice); the values do
+        not depend on it."""
+        dev = self._device(target, pred)
+        if target.shape != pred.shape or target.dim() != 4:
+            raise ValueError(f"target and pred must be (N, H, W, C) of one shape, got {tuple(target.shape)} and "
+                             f"{tuple(pred.shape)}")
+        t = target.to(dev, torch.float32).contiguous()
+        p = pred.to(dev, torch.float32).contiguous()
+        N, H, W, Cn = t.shape
+        out = torch.empty((N,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            check(lib.dsx_lpips_frames(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(p.data_ptr()), N, H, W, Cn,
+                                       int(channel), int(chunk), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        return out

@@ -1,5 +1,6 @@
 """The reference's image-quality module (core/metrics.py), same names and signatures: tensor2img, save_img,
-calculate_psnr and calculate_ssim, plus ``image_metrics``, the batched device form of PSNR and SSIM.
+calculate_psnr and calculate_ssim, plus ``image_metrics``, the batched device form of PSNR and SSIM, and
+``calculate_lpips``, the evaluation notebooks' ``compute_lpips`` on the device.
 
 SSIM runs on the MI355X (``dsx_image_metrics``, include/dsx.h): there is no CPU fallback, so calculate_ssim raises
 DsxError without a device.  The reference writes its grid with torchvision's make_grid and its files with cv2; neither
@@ -161,3 +162,19 @@ def image_metrics(pred, target, min_max=(-1, 1), quantize=True, data_range=255.0
     n = a.shape[1] * a.shape[2] * a.shape[3]
     psnr = [_psnr_from_ssd(s, n, float(data_range)) for s in ssd.tolist()]
     return torch.tensor(psnr, dtype=torch.float64), torch.from_numpy(ssim)
+
+
+def calculate_lpips(target_stitched, pred_stitched, loss_fn, chunk=0):
+    """``compute_lpips(target, pred)`` of notebooks/EvaluateJointIndi.ipynb cell 31 / EvaluateJointIndiIterative.ipynb
+    cell 28 on (N, H, W, C) channel-last frames: per channel, both stacks mapped to [-1, 1] with the TARGET channel's
+    min / max over all frames, replicated to three channels, LPIPS per frame -> {channel: [N floats]}.  ``loss_fn`` is a
+    ``core.lpips.LPIPS``; everything runs on the device (``dsx_lpips_frames``), numpy input is uploaded once."""
+    _lib.require_gpu()
+    dev = next((t.device for t in (target_stitched, pred_stitched) if torch.is_tensor(t) and t.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+    up = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))).to(
+        dev, torch.float32).contiguous()
+    t, p = up(target_stitched), up(pred_stitched)
+    if t.shape != p.shape or t.dim() != 4:
+        raise ValueError(f"target and pred must be (N, H, W, C) of one shape, got {tuple(t.shape)} and {tuple(p.shape)}")
+    return {ch: loss_fn.frames(t, p, ch, chunk).tolist() for ch in range(t.shape[3])}

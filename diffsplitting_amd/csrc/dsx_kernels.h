@@ -451,6 +451,31 @@ hipError_t launch_image_metrics(const float* a, const float* b, int planes, int 
                                 float hi, float rng, double c1, double c2, const SsimWindow& win, double* part,
                                 hipStream_t st);
 
+// LPIPS (AlexNet trunk, v0.1 heads), dsx_lpips.hip: fp32 NHWC, the two images of pair b are images b and B + b of a
+// batch of nimg = 2 B.  Weights are packed by dsx_lpips.cpp: conv1 [N block 2][group 46][lane 64] float4 over
+// k = (ky * 11 + kx) * 3 + c, conv2 .. conv5 [N block][chunk of 32 channels][tap][group 4][lane 64] float4; in both, row
+// i of an N block is output channel 16 ((i >> 2) & 1) + (i & 3) + 4 (i >> 3) and component s of lane (i, h) is
+// k = 8 group + 4 h + s.
+struct LpipsTaps { long long off[5]; int nblk[5]; int hw[5]; };   // per tap: first partial row, rows per pair, pixels
+hipError_t launch_lpips_input_nchw(const float* in0, const float* in1, int B, int H, int W, float* out, hipStream_t st);
+hipError_t launch_lpips_input_frames(const float* tgt, const float* prd, int n, int H, int W, int C, int ch, const float* mm,
+                                     float* out, hipStream_t st);
+int lpips_minmax_blocks(long long pixels);
+// min and max of channel `ch` of a channel-last stack -> mm[2]; part holds 2 * lpips_minmax_blocks(pixels) floats
+hipError_t launch_lpips_minmax(const float* x, long long pixels, int C, int ch, float* part, float* mm, hipStream_t st);
+hipError_t launch_lpips_conv1(const float* in, const float* wpack, const float* bias, float* out, int nimg, int H, int W, int Ho,
+                              int Wo, hipStream_t st);
+// stride 1, pad ks / 2, ks = 3 or 5, Cin % 32 == 0, Cout % 64 == 0, + bias + ReLU
+hipError_t launch_lpips_conv(int ks, const float* in, const float* wpack, const float* bias, float* out, int nimg, int H, int W,
+                             int Cin, int Cout, hipStream_t st);
+hipError_t launch_lpips_pool(const float* in, float* out, int nimg, int H, int W, int Ho, int Wo, int C, hipStream_t st);
+int lpips_dist_blocks(int HW);
+// part[B][lpips_dist_blocks(HW)] doubles: sum over the block's pixels of sum_c lin[c] (f0 / |f0| - f1 / |f1|)^2
+hipError_t launch_lpips_dist(const float* feat, int B, int HW, int C, const float* lin, double* part, hipStream_t st);
+// out[b_off + b] = sum over taps of (partial rows added in order) / pixels; per_tap (may be NULL) [b_off + b][5]
+hipError_t launch_lpips_finish(const double* part, const LpipsTaps& taps, int B, int b_off, float* out, float* per_tap,
+                               hipStream_t st);
+
 // relu(u) * sigmoid-mask reduction of the TimePredictor head
 hipError_t launch_masked_mean(const float* u, const float* mask, int B, long long n, float* out,
                               hipStream_t st);

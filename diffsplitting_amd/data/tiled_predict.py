@@ -52,9 +52,13 @@ class TileExchange:
 
 @torch.no_grad()
 def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8, sampler_kwargs=None,
-                  group=None):
+                  group=None, lpips=None, target_frames=None):
     """``frames_input``: (N,H,W) fp32 CUDA tensor, already normalised (the network input channel).
     Returns the stitched prediction (N,H,W,C) on every rank and the ``TilePlan``.
+
+    ``lpips``: a ``core.lpips.LPIPS``; with it (and ``target_frames`` (N,H,W,C), the ground truth of the prediction
+    channels) the first element is ``(canvas, lpips_dict)``, ``lpips_dict`` = ``core.metrics.calculate_lpips(
+    target_frames, canvas, lpips)``: per channel the LPIPS of every frame, computed on the device.
 
     ``netG`` is what ``define_G`` returns (InDI / JointIndi sampler); its full-batch
     output (``last_full_batch``) is used, not the single element the reference API returns."""
@@ -71,7 +75,13 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
         tiles = plan.gather(frames_input, chunk).unsqueeze(1)         # (b,1,p,p)
         netG.inference(tiles, continuous=False, **kw)
         ex.add(netG.last_full_batch, chunk)
-    return ex.finish(), plan
+    canvas = ex.finish()
+    if lpips is None:
+        return canvas, plan
+    if target_frames is None:
+        raise ValueError("predict_tiled(lpips=...) needs target_frames (N,H,W,C) to compare the prediction with")
+    from ..core.metrics import calculate_lpips
+    return (canvas, calculate_lpips(target_frames, canvas, lpips)), plan
 
 
 # ---- mixed-input evaluation (BASELINE C5: JointIndi + TimePredictor) -----------------------------------------------
@@ -115,7 +125,7 @@ def evaluate_time_predictor(val_set, time_predictor, num_timesteps=20, batch_til
 
 @torch.no_grad()
 def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1, mmse_count=1, batch_tiles=8,
-                        t_from="classifier", table=None, table_timesteps=100, group=None):
+                        t_from="classifier", table=None, table_timesteps=100, group=None, lpips=None):
     """The out-of-distribution split of notebooks/EvaluateJointIndiIterative.ipynb cells 59-64, batched: the two
     channels of every tile of ``val_set`` (a ``SplitDatasetTiledPred``) mixed at ``mixing_t`` -> the TimePredictor's
     estimate of the mixing time per tile (``pred_t_0 = 1 - TP(cls[:, 0])``, ``pred_t_1 = TP(cls[:, 1])``, cell 40) ->
@@ -131,7 +141,11 @@ def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1
     prediction and target first, a positive affine map per channel, under which RangeInvariantPsnr does not change --
     no extra pass.  A sampler's own ``noise_source`` is used (set ``netG.noise_source`` to give both the same).
     Several ranks: tiles are sharded through ``TileExchange`` as in ``predict_tiled``; ``pred_t`` then holds this
-    rank's tiles only (NaN elsewhere) -- the sharded form is not covered by a test."""
+    rank's tiles only (NaN elsewhere) -- the sharded form is not covered by a test.
+
+    ``lpips``: a ``core.lpips.LPIPS``; with it the first element is ``(canvas, psnr, lpips_dict)``, the per-frame LPIPS of
+    every channel against the same normalised target (``core.metrics.calculate_lpips``; its min-max map makes it
+    invariant under the de-normalisation too)."""
     if t_from not in ("classifier", "given"):
         raise ValueError("t_from must be 'classifier' or 'given'")
     i1, i2 = netG.indi1, netG.indi2
@@ -143,7 +157,8 @@ def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1
         from .time_predictor_dataset import compute_input_normalization_dict
         table = compute_input_normalization_dict(val_set._data_dict, table_timesteps, val_set._mean_target,
                                                  val_set._std_target)
-    ex = TileExchange(plan, 2, dev, group, gt=val_set.normalized_target_frames())
+    gt = val_set.normalized_target_frames()
+    ex = TileExchange(plan, 2, dev, group, gt=gt)
     ids = parallel.shard_ids(plan.total, ex.rank, ex.world)
     pred_t = torch.full((plan.total, 2), float("nan"), dtype=torch.float32, device=dev)
     want = ("mix", "cls") if t_from == "classifier" else ("mix",)
@@ -165,4 +180,8 @@ def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1
             i2.inference(in2, continuous=False, num_timesteps=num_timesteps, t_float_start=t2)
             acc2 = i2.last_full_batch.clone() if acc2 is None else acc2 + i2.last_full_batch
         ex.add(torch.cat([acc1, acc2], dim=1) / mmse_count, chunk)
-    return ex.finish(), pred_t
+    if lpips is None:
+        return ex.finish(), pred_t
+    from ..core.metrics import calculate_lpips
+    canvas, psnr = ex.finish()
+    return (canvas, psnr, calculate_lpips(gt, canvas, lpips)), pred_t

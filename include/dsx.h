@@ -359,6 +359,35 @@ int dsx_image_metrics(const float* a_dev, const float* b_dev, int B, int C, int 
                       double hi, double data_range, double* partials_dev, double* out_ssim_host, double* out_ssd_host,
                       void* stream);
 
+/* ------------------------------------------------------------------ LPIPS
+ * The perceptual metric of the reference's evaluation (notebooks/EvaluateJointIndi.ipynb cell 31 and
+ * notebooks/EvaluateJointIndiIterative.ipynb cell 28: lpips.LPIPS(net='alex'), version 0.1, spatial off): scaling
+ * layer, AlexNet feature trunk with its five ReLU taps, per tap the `lin`-weighted squared difference of the
+ * unit-normalised features (f / (sqrt(sum_c f^2) + 1e-10)) averaged over space, summed over the taps.  fp32 on the
+ * exact-fp32 matrix cores; the partial sums are added in a fixed order in double, so equal inputs give bitwise-equal
+ * outputs.  Weights always come from the caller: nothing is ever fetched. */
+typedef struct dsx_lpips dsx_lpips;
+/* Restates LPIPS.__init__'s weight loading.  Host only (works without a GPU; the packed image is uploaded at first
+ * use).  trunk_host: 10 fp32 host tensors in state_dict order, net.slice{1..5}.{0,3,6,8,10}.{weight,bias} (OIHW:
+ * (64,3,11,11), (192,64,5,5), (384,192,3,3), (256,384,3,3), (256,256,3,3)); lin_host: lin{0..4}.model.1.weight
+ * ((1,C,1,1), C = 64, 192, 384, 256, 256).  Element counts are checked and a mismatch is refused by key name. */
+int dsx_lpips_create(const float* const* trunk_host, const int64_t* trunk_numel, const float* const* lin_host,
+                     const int64_t* lin_numel, dsx_lpips** out);
+void dsx_lpips_destroy(dsx_lpips* h);
+/* Restates LPIPS.forward(in0, in1, normalize=False): in0 / in1 (B, 3, H, W) fp32 NCHW in [-1, 1] on the device ->
+ * out_dev[B]; per_tap_dev (may be NULL) receives [B][5], the values retPerLayer=True returns.  Asynchronous on
+ * `stream`.  H, W >= 31 (below that a stage of the trunk is empty); a batch whose largest tensor passes 2 GiB is
+ * refused.  One workspace per handle and (B, H, W), reallocated when they change. */
+int dsx_lpips_forward(dsx_lpips* h, const float* in0_nchw_dev, const float* in1_nchw_dev, int B, int H, int W,
+                      float* out_dev, float* per_tap_dev, void* stream);
+/* Restates compute_lpips of the notebooks for one channel of the stitched frames: target / pred (N, H, W, C) fp32
+ * channel-last on the device; x -> 2 (x - min) / (max - min) - 1 in fp32 with min / max of the TARGET's channel over all
+ * N frames (reduced on the device), replicated to three channels, one value per frame -> out_dev[N].  Frames go through
+ * the trunk `chunk` at a time (0: as many as ~1.5 GiB of workspace hold); the values do not depend on it (bitwise).
+ * A constant target channel divides by zero, as the reference does. */
+int dsx_lpips_frames(dsx_lpips* h, const float* target_nhwc_dev, const float* pred_nhwc_dev, int N, int H, int W, int C,
+                     int channel, int chunk, float* out_dev, void* stream);
+
 /* ------------------------------------------------- tile plan with device-resident tables (the stall-free forms)
  * The entry points above take host tables and upload them per call (a small allocation and a synchronous copy each).
  * A dsx_tileplan keeps the patch starts and valid regions of every tile on the device (uploaded once, at first
