@@ -43,6 +43,7 @@ FLAVOUR_SR3, FLAVOUR_DDPM = 0, 1
 LAYER_CONV, LAYER_ATTN, LAYER_FILM, LAYER_INPUT = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 TILING_TRIM, TILING_PAD, TILING_SHIFT = 0, 1, 2
+RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3
 
 _vp, _i, _i64, _u64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float
 _pi64, _pi32, _pf = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)
@@ -103,6 +104,12 @@ SIGNATURES = {
     "dsx_lpips_destroy": (None, [_vp]),
     "dsx_lpips_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "dsx_lpips_frames": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "dsx_resize_coeffs": (_i, [_i, _i, _i, _pi32, _pi32, _pi32, _i]),
+    "dsx_resize_plan_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "dsx_resize_plan_destroy": (None, [_vp]),
+    "dsx_resize_workspace_bytes": (C.c_size_t, [_vp, _i]),
+    "dsx_resize_u8": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "dsx_u8_to_tensor": (_i, [_vp, _i, _i, _i, _i, _f, _f, _vp, _vp]),
     "dsx_tileplan_create": (_i, [_pi64, _pi64, _pi64, _i, C.POINTER(_vp)]),
     "dsx_tileplan_destroy": (None, [_vp]),
     "dsx_tileplan_total": (_i64, [_vp]),

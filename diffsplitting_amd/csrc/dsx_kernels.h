@@ -476,6 +476,29 @@ hipError_t launch_lpips_dist(const float* feat, int B, int HW, int C, const floa
 hipError_t launch_lpips_finish(const double* part, const LpipsTaps& taps, int B, int b_off, float* out, float* per_tap,
                                hipStream_t st);
 
+// PIL's 8-bit resampler (libImaging/Resample.c), dsx_resize.hip: one pass over a batch of uint8 images [B][rows][W][C]
+// kept as rows of bytes.  Output sample i of the pass uses row t0 + i of the integer tables (xmin, n, k[ksize]) made by
+// dsx_resize_coeffs; a workgroup takes S outputs and T units of the other axis and stages their coefficients and the
+// source window (lds_pitch bytes per staged row) in LDS.
+//   horizontal: n_out columns of n_other rows; src / dst point at the first row, src at byte 0 of it, dst at the first
+//               byte written
+//   vertical  : n_out rows of n_other bytes; src row 0 is source row `base` of the tables, src / dst point at the
+//               first byte column
+struct ResizePassArgs {
+  const unsigned char* src; unsigned char* dst;
+  const int *xmin, *n, *k;
+  long long src_img, dst_img;      // bytes from one image to the next
+  int src_pitch, dst_pitch;        // bytes per row
+  int ksize, t0, C, n_out, n_other, base, S, T, lds_pitch, lds_bytes, B;
+};
+__host__ __device__ inline int resize_tab_bytes(int S, int ksize) { return (((S * ksize + 2 * S) * 4) + 15) & ~15; }
+hipError_t launch_resize_h_u8(const ResizePassArgs& a, hipStream_t st);
+hipError_t launch_resize_v_u8(const ResizePassArgs& a, hipStream_t st);
+// ToTensor + min_max (data/util.py:74-83): [B][HW][C] uint8 -> [B][C][HW] fp32, (u / 255) * (hi - lo) + lo with every
+// operation rounded on its own
+hipError_t launch_u8_to_tensor(const unsigned char* src, int B, long long HW, int C, float lo, float hi, float* dst,
+                               hipStream_t st);
+
 // relu(u) * sigmoid-mask reduction of the TimePredictor head
 hipError_t launch_masked_mean(const float* u, const float* mask, int B, long long n, float* out,
                               hipStream_t st);

@@ -388,6 +388,43 @@ int dsx_lpips_forward(dsx_lpips* h, const float* in0_nchw_dev, const float* in1_
 int dsx_lpips_frames(dsx_lpips* h, const float* target_nhwc_dev, const float* pred_nhwc_dev, int N, int H, int W, int C,
                      int channel, int chunk, float* out_dev, void* stream);
 
+/* ------------------------------------------------------------------ SR3 image path: resize and ToTensor
+ * The first step of the reference's SR3 configurations (data/prepare_data.py:17-40 resize_and_convert /
+ * resize_multiple, data/util.py:74-83 transform_augment): PIL's Image.resize on 8-bit images, antialiased BILINEAR or
+ * BICUBIC (libImaging/Resample.c), and torchvision's ToTensor.  The resampler is fixed-point integer arithmetic --
+ * int32 coefficients scaled by 2^22, per output sample ss = 2^21 + sum pixel * k over its tap window, output
+ * clip(ss >> 22, 0, 255), horizontal pass first, uint8 between the passes, a pass that keeps the length skipped -- so
+ * the device result equals PIL's byte for byte. */
+enum { DSX_RESIZE_BILINEAR = 2, DSX_RESIZE_BICUBIC = 3 };   /* PIL.Image.BILINEAR / BICUBIC */
+/* Restates precompute_coeffs + normalize_coeffs_8bpc for one axis.  Host only (works without a GPU).  Every
+ * intermediate is a double rounded on its own, sums run in tap order: scale = in / out, filterscale = max(scale, 1),
+ * support = {bilinear 1, bicubic 2} * filterscale; per output xx: center = (xx + 0.5) * scale, xmin = max(0,
+ * (int)(center - support + 0.5)), xmax = min(in, (int)(center + support + 0.5)), weight x = filter((x + xmin -
+ * center + 0.5) * (1 / filterscale)) (the product with the reciprocal, as Resample.c writes it), each row divided by
+ * its sum, then (int)(+-0.5 + w * 2^22) with the sign of w.  Bicubic uses a = -0.5.  Returns the row capacity needed
+ * (2 * ceil(support) + 1); with all three outputs NULL that is all it does, else xmin_out[out], n_out[out] (taps of
+ * the row) and k_out[out][cap] (zero past the taps) are filled and cap must reach the capacity. */
+int dsx_resize_coeffs(int in_size, int out_size, int filter, int32_t* xmin_out, int32_t* n_out, int32_t* k_out, int cap);
+/* Image.resize((out_w, out_h), filter) of in_h x in_w images with C = 1 or 3 interleaved channels, followed by the
+ * crop [crop_top, crop_top + crop_h) x [crop_left, crop_left + crop_w) of the resized image (center_crop of
+ * resize_and_convert): only the window is computed.  The plan holds both coefficient tables (built here on the host,
+ * uploaded once at first device use) and the tiling of the two passes.  Sizes below 1, another C or filter id, a window
+ * that leaves the resized image and a resize whose single output does not fit the LDS staging (a reduction by several
+ * thousand) are refused with DSX_ERR_INVALID. */
+typedef struct dsx_resize_plan dsx_resize_plan;
+int dsx_resize_plan_create(int in_h, int in_w, int out_h, int out_w, int crop_top, int crop_left, int crop_h, int crop_w,
+                           int filter, int C, dsx_resize_plan** out);
+void dsx_resize_plan_destroy(dsx_resize_plan* plan);
+/* bytes of the uint8 intermediate between the passes for B images (0 when a pass is skipped) */
+size_t dsx_resize_workspace_bytes(const dsx_resize_plan* plan, int B);
+/* src_dev [B][in_h][in_w][C] uint8 -> dst_dev [B][crop_h][crop_w][C] uint8, asynchronous on `stream`; B <= 65535 */
+int dsx_resize_u8(dsx_resize_plan* plan, const uint8_t* src_dev, int B, uint8_t* dst_dev, uint8_t* workspace_dev,
+                  void* stream);
+/* ToTensor and the min_max map of transform_augment: [B][H][W][C] uint8 -> [B][C][H][W] fp32, v = float(u) / 255.0f
+ * (IEEE division), then v * (hi - lo) + lo with product and sum rounded separately: bitwise what torch computes on the
+ * CPU for min_max = (lo, hi).  C = 1 or 3. */
+int dsx_u8_to_tensor(const uint8_t* src_dev, int B, int H, int W, int C, float lo, float hi, float* dst_dev, void* stream);
+
 /* ------------------------------------------------- tile plan with device-resident tables (the stall-free forms)
  * The entry points above take host tables and upload them per call (a small allocation and a synchronous copy each).
  * A dsx_tileplan keeps the patch starts and valid regions of every tile on the device (uploaded once, at first
