@@ -350,6 +350,38 @@ extern "C" int dsx_randn(float* out, int64_t n, uint64_t seed, uint64_t subseq, 
   return DSX_OK;
 }
 
+// ---- the forward half of the training objective: the noising step and the loss reduction (dsx_objective.hip)
+extern "C" int dsx_q_sample(const float* x0, const float* xe, int B, int C, int Ce, int H, int W, const float* c0,
+                            const float* c1, const float* c2, const float* z, uint64_t seed, uint64_t subseq,
+                            float* z_out, float* dst, int Cdst, int coff, void* stream) {
+  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(DSX_ERR_INVALID, "q_sample: empty shape (%d, %d, %d, %d)", B, C, H, W);
+  if (xe && (Ce < 1 || C % Ce != 0))
+    return fail(DSX_ERR_INVALID, "q_sample: x_end has %d channels, x_start %d: C %% Ce != 0", Ce, C);
+  if (coff < 0 || (int64_t)coff + C > Cdst)
+    return fail(DSX_ERR_INVALID, "q_sample: channels %d..%d do not fit a destination of %d (coff + C > Cdst)", coff,
+                coff + C, Cdst);
+  if ((int64_t)H * W > INT32_MAX || (int64_t)B * Cdst * H * W > ((int64_t)1 << 40))
+    return fail(DSX_ERR_INVALID, "q_sample: tensor too large");
+  if (!x0 || !c0 || !c2 || !dst || (xe && !c1)) return fail(DSX_ERR_INVALID, "q_sample: null argument");
+  QSampleArgs a{x0, xe, c0, c1, c2, z, seed, subseq, z ? nullptr : z_out, dst, B, C, xe ? Ce : 1, H * W, Cdst, coff};
+  HIP_TRY(launch_q_sample(a, (hipStream_t)stream));
+  return DSX_OK;
+}
+extern "C" int dsx_loss_blocks(int C, int H, int W) {
+  if (C < 1 || H < 1 || W < 1 || (int64_t)C * H * W > INT32_MAX)
+    return fail(DSX_ERR_INVALID, "loss: bad sample shape (%d, %d, %d)", C, H, W);
+  return loss_blocks((int64_t)C * H * W);
+}
+extern "C" int dsx_loss(const float* a, const float* b, int B, int C, int H, int W, int squared, double* partial_dev,
+                        double* per_sample_dev, void* stream) {
+  const int blocks = dsx_loss_blocks(C, H, W);
+  if (blocks < 0) return blocks;
+  if (B < 1 || B > 65535) return fail(DSX_ERR_INVALID, "loss: B = %d, must be in 1..65535", B);
+  if (!a || !b || !partial_dev || !per_sample_dev) return fail(DSX_ERR_INVALID, "loss: null argument");
+  HIP_TRY(launch_loss(a, b, B, (int64_t)C * H * W, squared ? 1 : 0, partial_dev, per_sample_dev, (hipStream_t)stream));
+  return DSX_OK;
+}
+
 // ------------------------------------------------------------------ time predictor head
 extern "C" int dsx_time_predictor_set_mask(dsx_exec* ex, const float* w, const float* b) {
   if (!ex || !w || !b) return fail(DSX_ERR_INVALID, "null argument");

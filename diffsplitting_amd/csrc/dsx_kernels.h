@@ -402,6 +402,78 @@ hipError_t launch_update(const UpdateArgs& a, hipStream_t st);
 hipError_t launch_advance(int* step_ctr, hipStream_t st);
 hipError_t launch_randn(float* out, long long n, unsigned long long seed, unsigned long long subseq,
                         hipStream_t st);
+#if defined(__HIPCC__)
+// One IEEE operation each, never contracted into an fma: the pragma takes the `contract` flag off the instruction, and
+// the backend fuses a product into a sum only when both carry it.
+__device__ __forceinline__ float mul_f(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_f(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double mul_d(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double add_d(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// The engine's normal stream: element i of the stream (seed, subseq) is component i % 4 of normal4(seed, subseq, i / 4).
+// Shared by k_randn, k_update (dsx_ops.hip) and k_q_sample (dsx_objective.hip), which must agree bitwise.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
+                                              unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
+    const unsigned n1 = (unsigned)p1;
+    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    const unsigned n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__device__ __forceinline__ void normal4(unsigned long long seed, unsigned long long subseq,
+                                        unsigned long long idx4, float z[4]) {
+  unsigned r[4];
+  philox4x32_10((unsigned)idx4, (unsigned)(idx4 >> 32), (unsigned)subseq, (unsigned)(subseq >> 32),
+                (unsigned)seed, (unsigned)(seed >> 32), r);
+  const float u0 = ((float)r[0] + 0.5f) * 2.3283064365386963e-10f;  // (0,1)
+  const float u1 = ((float)r[1] + 0.5f) * 2.3283064365386963e-10f;
+  const float u2 = ((float)r[2] + 0.5f) * 2.3283064365386963e-10f;
+  const float u3 = ((float)r[3] + 0.5f) * 2.3283064365386963e-10f;
+  const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
+  float s, c;
+  sincosf(6.283185307179586f * u1, &s, &c);
+  z[0] = ra * c; z[1] = ra * s;
+  sincosf(6.283185307179586f * u3, &s, &c);
+  z[2] = rb * c; z[3] = rb * s;
+}
+#endif
+
+// dsx_objective.hip.  q_sample of the three sampler families in one launch (NCHW fp32):
+//   dst[b][coff + c] = c0[b] * x0[b][c] (+ c1[b] * xe[b][c % Ce]) + c2[b] * z[b][c],  each operation rounded on its own.
+// xe == nullptr: the two-term (Gaussian) form.  z == nullptr: z is element i of the normal stream (seed, subseq) at
+// the flat (B, C, H, W) index i (what launch_randn writes) and is stored to z_out when that is not nullptr.
+struct QSampleArgs {
+  const float* x0; const float* xe;
+  const float* c0; const float* c1; const float* c2;     // device, B values each
+  const float* z; unsigned long long seed, subseq; float* z_out;
+  float* dst;
+  int B, C, Ce, HW, Cdst, coff;
+};
+hipError_t launch_q_sample(const QSampleArgs& a, hipStream_t st);
+// per-sample sum |a - b| (squared == 0) or sum (a - b)^2 over n elements, in double: part[B][loss_blocks(n)] partials
+// in a fixed partition, out[B] their sums in a fixed order (two launches, no atomics)
+int loss_blocks(long long n);
+hipError_t launch_loss(const float* a, const float* b, int B, long long n, int squared, double* part, double* out,
+                       hipStream_t st);
 
 // the tiles of one launch: ids first, first + stride, ... (count of them); the tables a kernel indexes with an id
 // (`starts` [..][3], `regions` [..][8], `off` [..]) live on the device -- the plan's own (dsx_tileplan), or a per-call

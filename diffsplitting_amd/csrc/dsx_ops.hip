@@ -347,38 +347,7 @@ hipError_t launch_nhwc_to_nchw(const float* src, float* dst, int B, int C, int H
 // Philox4x32-10 + Box-Muller (device noise for the perf path; the parity path
 // injects host-drawn noise instead, SURVEY §7 "Parity over 2000 steps")
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                              unsigned k0, unsigned k1, unsigned out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ void normal4(unsigned long long seed, unsigned long long subseq,
-                                        unsigned long long idx4, float z[4]) {
-  unsigned r[4];
-  philox4x32_10((unsigned)idx4, (unsigned)(idx4 >> 32), (unsigned)subseq, (unsigned)(subseq >> 32),
-                (unsigned)seed, (unsigned)(seed >> 32), r);
-  const float u0 = ((float)r[0] + 0.5f) * 2.3283064365386963e-10f;  // (0,1)
-  const float u1 = ((float)r[1] + 0.5f) * 2.3283064365386963e-10f;
-  const float u2 = ((float)r[2] + 0.5f) * 2.3283064365386963e-10f;
-  const float u3 = ((float)r[3] + 0.5f) * 2.3283064365386963e-10f;
-  const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
-  float s, c;
-  sincosf(6.283185307179586f * u1, &s, &c);
-  z[0] = ra * c; z[1] = ra * s;
-  sincosf(6.283185307179586f * u3, &s, &c);
-  z[2] = rb * c; z[3] = rb * s;
-}
-
+// (philox4x32_10 and normal4 live in dsx_kernels.h: dsx_objective.hip draws from the same stream)
 __global__ void k_randn(float* __restrict__ out, long long n, unsigned long long seed,
                         unsigned long long subseq) {
   const long long n4 = (n + 3) / 4;
@@ -528,25 +497,7 @@ hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, int H, int
   return hipGetLastError();
 }
 
-// One IEEE operation each, never contracted into an fma: the pragma takes the `contract` flag off the instruction, and
-// the backend fuses a product into a sum only when both carry it.
-__device__ __forceinline__ float mul_f(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float add_f(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ double mul_d(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ double add_d(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
+// (mul_f / add_f / mul_d / add_d, one IEEE operation each, live in dsx_kernels.h)
 // The mixed inputs of the TimePredictor evaluation (notebooks/EvaluateJointIndiIterative.ipynb cells 40/43,
 // time_prediction_evaluation.ipynb cell 4) cut, normalised, mixed and min-max-normalised in one pass; the op list is
 // in include/dsx.h (dsx_tiles_gather_mix).  Channel 0 is indi1's input, channel 1 indi2's.

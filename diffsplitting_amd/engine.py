@@ -494,3 +494,71 @@ def randn(shape, seed, subsequence=0, device="cuda"):
     check(lib.dsx_randn(_dptr(out), out.numel(), C.c_uint64(int(seed)), C.c_uint64(int(subsequence)),
                         _stream_ptr()))
     return out
+
+
+# ---------------------------------------------------------------------------
+# the forward half of the training objective (dsx_q_sample / dsx_loss, include/dsx.h)
+# ---------------------------------------------------------------------------
+def _f32_cuda(t, what, shape=None):
+    """A contiguous float32 CUDA tensor, or a refusal: the kernels read the caller's memory as it is, nothing is
+    converted or copied behind the caller's back."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise DsxError(f"{what} must be a CUDA tensor: the objective runs on the MI355X only (no CPU fallback)")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise DsxError(f"{what} must be a contiguous float32 tensor, got {t.dtype}"
+                       f"{'' if t.is_contiguous() else ', strided'}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise DsxError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t.detach()
+
+
+def q_sample(x0, c0, c2, xe=None, c1=None, z=None, seed=0, subsequence=0, dst=None, coff=0, want_z=False):
+    """``dsx_q_sample``: ``dst[:, coff:coff + C] = c0*x0 (+ c1*xe) + c2*z`` in one launch, every operation rounded on
+    its own.  ``c0`` / ``c1`` / ``c2``: (B,) per-sample coefficients; ``xe`` (B, Ce, H, W) is read at channel
+    ``c % Ce``; ``z`` None draws the Philox normals of ``randn(x0.shape, seed, subsequence)``.  Returns
+    ``(dst, z)``: ``dst`` is a new (B, C, H, W) tensor unless given, ``z`` the normals used (the injected tensor, the
+    drawn ones when ``want_z``, else None).  Every tensor must be contiguous float32 on the device."""
+    x0 = _f32_cuda(x0, "x_start")
+    if x0.dim() != 4:
+        raise DsxError(f"x_start must be (B, C, H, W), got {tuple(x0.shape)}")
+    B, Cn, H, W = x0.shape
+    coef = lambda c, what: _f32_cuda(c, what).reshape(-1)
+    c0, c2 = coef(c0, "c0"), coef(c2, "c2")
+    Ce = 1
+    if xe is not None:
+        xe, c1 = _f32_cuda(xe, "x_end"), coef(c1, "c1")
+        if xe.dim() != 4 or xe.shape[0] != B or tuple(xe.shape[2:]) != (H, W):
+            raise DsxError(f"x_end must be ({B}, Ce, {H}, {W}), got {tuple(xe.shape)}")
+        Ce = xe.shape[1]
+    for c in (c0, c1, c2):
+        if c is not None and c.numel() != B:
+            raise DsxError(f"per-sample coefficients must hold B = {B} values, got {c.numel()}")
+    z_out = None
+    if z is not None:
+        z = _f32_cuda(z, "noise", x0.shape)
+    elif want_z:
+        z_out = torch.empty_like(x0)
+    if dst is None:
+        dst, coff = torch.empty_like(x0), 0
+    elif not (dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous() and dst.dim() == 4
+              and dst.shape[0] == B and tuple(dst.shape[2:]) == (H, W)):
+        raise DsxError(f"dst must be a contiguous float32 CUDA tensor ({B}, Cdst, {H}, {W})")
+    check(lib.dsx_q_sample(_dptr(x0), _dptr(xe), B, Cn, Ce, H, W, _dptr(c0), _dptr(c1), _dptr(c2), _dptr(z),
+                           C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(subsequence)), _dptr(z_out),
+                           _dptr(dst), dst.shape[1], int(coff), _stream_ptr()))
+    return dst, (z if z is not None else z_out)
+
+
+def loss_per_sample(a, b, squared):
+    """``dsx_loss``: per-sample sum |a - b| (L1) or sum (a - b)^2 (L2) over (C, H, W) of two (B, C, H, W) fp32 CUDA
+    tensors, accumulated in double in a fixed order: a (B,) float64 CUDA tensor, bitwise repeatable."""
+    a = _f32_cuda(a, "a")
+    b = _f32_cuda(b, "b", a.shape)
+    if a.dim() != 4:
+        raise DsxError(f"the loss takes (B, C, H, W) tensors, got {tuple(a.shape)}")
+    B, Cn, H, W = a.shape
+    blocks = check(lib.dsx_loss_blocks(Cn, H, W))
+    part = torch.empty(B * blocks, dtype=torch.float64, device=a.device)
+    out = torch.empty(B, dtype=torch.float64, device=a.device)
+    check(lib.dsx_loss(_dptr(a), _dptr(b), B, Cn, H, W, 1 if squared else 0, _dptr(part), _dptr(out), _stream_ptr()))
+    return out

@@ -2,7 +2,8 @@
 get_current_visuals / load_network), running on the HIP engine.
 
 ``test()`` is a superset of the reference's (rot R2): it routes to
-``inference`` (InDI family), ``super_resolution`` (sr3) or ``predict`` (ddpm)."""
+``inference`` (InDI family), ``super_resolution`` (sr3) or ``predict`` (ddpm).
+``eval_loss()`` evaluates the training objective without gradients; ``optimize_parameters`` raises."""
 import logging
 from collections import OrderedDict
 
@@ -29,6 +30,18 @@ class DDPM(BaseModel):
 
     def optimize_parameters(self):
         raise NotImplementedError("training is out of scope of the MI355X sampling engine")
+
+    def eval_loss(self):
+        """The held-out value of the training objective on the fed data: the non-training half of
+        optimize_parameters (model.py:48-61).  ``netG(data)`` runs under no_grad with eval semantics (dropout is
+        identity), fills ``log_dict['l_pix']`` and the sampler's log entries, and returns the float."""
+        self.netG.eval()
+        with torch.no_grad():
+            l_pix = self.netG(self.data)
+        self.log_dict["l_pix"] = l_pix.item()
+        for k, v in self.netG.get_current_log().items():
+            self.log_dict[k] = v
+        return self.log_dict["l_pix"]
 
     def test(self, continuous=False, clip_denoised=True):
         self.netG.eval()

@@ -2,12 +2,16 @@
 
 Each class keeps the reference's constructor / method signatures and return
 shapes and drives ``UNetEngine.sample_loop`` (a captured
-hipGraph per step).  Training entry points raise: the engine is inference-only.
+hipGraph per step).  ``forward`` / ``p_losses`` evaluate the training objective's forward half on the device
+(one noising launch, one UNet forward, one reduction) under ``torch.no_grad()``: the UNet always runs with eval
+semantics (dropout is identity), so the value is the validation objective and carries no graph.
+Training itself (backward, optimiser) stays out of scope.
 
 Noise: by default the per-step noise is drawn on the device (Philox, seeded
 from torch's generator); set ``noise_source`` to a ``randn(shape)`` callable to
 inject host draws in the reference's draw order (parity mode, Q4).
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -33,10 +37,73 @@ class _SamplerBase(nn.Module):
         return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
 
     def forward(self, x, *args, **kwargs):
-        raise NotImplementedError("training (p_losses) is out of scope of the MI355X sampling engine")
+        """The objective's forward evaluation (``p_losses``); no gradients, eval semantics."""
+        return self.p_losses(x, *args, **kwargs)
 
     def get_current_log(self):
         return {}
+
+    # ---- the objective's forward half (dsx_q_sample / dsx_loss) ---------------------------
+    @staticmethod
+    def _need_cuda(*tensors):
+        for t in tensors:
+            if not t.is_cuda:
+                raise DsxError("the objective runs on the MI355X only; pass CUDA tensors (no CPU fallback)")
+
+    def _set_loss(self, device, reduction):
+        if self.loss_type not in ("l1", "l2"):
+            raise NotImplementedError("loss_type {!r}: only 'l1' and 'l2' exist".format(self.loss_type))
+        if reduction not in ("sum", "mean"):
+            raise NotImplementedError("loss reduction {!r}: only 'sum' and 'mean' are built".format(reduction))
+        self._device, self._reduction = device, reduction
+
+    def _loss(self, a, b):
+        """nn.L1Loss / nn.MSELoss(reduction)(a, b) as a 0-dim fp32 device tensor: per-sample sums in double on the
+        device (dsx_loss), added in double, divided by the element count for 'mean', rounded to fp32 once."""
+        if getattr(self, "_reduction", None) is None:
+            raise DsxError("set_loss() first")
+        if a.shape != b.shape:       # torch's losses broadcast (a 1-channel noise against a wider UNet output)
+            a, b = torch.broadcast_tensors(a, b)
+        a, b = a.float().contiguous(), b.float().contiguous()      # no copy for what the samplers themselves produce
+        total = engine.loss_per_sample(a, b, squared=self.loss_type == "l2").sum()
+        if self._reduction == "mean":
+            total = total / a.numel()
+        return total.to(torch.float32)
+
+    def _noise_or_seed(self, noise, shape, device):
+        """(z, seed): the injected draws (``noise`` or one ``noise_source`` draw), else None and a Philox seed."""
+        if noise is None and self.noise_source is not None:
+            noise = self._draw(shape, device)
+        if noise is not None:
+            return noise.to(device=device, dtype=torch.float32).contiguous(), 0
+        return None, self._seed()
+
+    def _q_sample(self, x_start, coef, noise, x_end=None):
+        """The public q_sample of the three families: tensors are brought to contiguous float32 here (a copy only when
+        the caller's are not), the coefficients moved to the device, then one dsx_q_sample launch."""
+        dev = x_start.device
+        x_start = x_start.float().contiguous()
+        c0, c1, c2 = (None if c is None else c.to(dev).contiguous() for c in coef)
+        z, seed = self._noise_or_seed(noise, x_start.shape, dev)
+        xe = None if x_end is None else x_end.float().contiguous()
+        return engine.q_sample(x_start, c0, c2, xe=xe, c1=c1, z=z, seed=seed)[0]
+
+    def _noised_forward(self, x_start, coef, time, noise, cond=None, xe=None, want_noise=True):
+        """x_noisy = q_sample(x_start) written straight into the UNet's input (behind ``cond``'s channels when the
+        model is conditional), then the UNet forward.  ``coef`` = (c0, c1, c2), (B,) each (c1 None: two terms).
+        Returns (x_recon, the normals used or None)."""
+        dev = x_start.device
+        x_start = x_start.float().contiguous()
+        B, Cn, H, W = x_start.shape
+        z, seed = self._noise_or_seed(noise, x_start.shape, dev)
+        c0, c1, c2 = (None if c is None else c.to(dev).contiguous() for c in coef)
+        inp, coff = None, 0
+        if cond is not None:
+            coff = cond.shape[1]
+            inp = torch.empty((B, coff + Cn, H, W), dtype=torch.float32, device=dev)
+            inp[:, :coff] = cond                                     # cat([input, x_noisy], 1): x_noisy by the kernel
+        inp, z = engine.q_sample(x_start, c0, c2, xe=xe, c1=c1, z=z, seed=seed, dst=inp, coff=coff, want_z=want_noise)
+        return self.denoise_fn(inp, time.to(dev)), z
 
     @property
     def prediction_channels(self):
@@ -63,7 +130,7 @@ class GaussianSampler(_SamplerBase):
         self._table = {}
 
     def set_loss(self, device):
-        self._device = device
+        self._set_loss(device, "sum")                                # sr3 diffusion.py:84-90: always reduction='sum'
 
     def set_new_noise_schedule(self, schedule_opt, device):
         bufs, gamma = engine.gaussian_buffers(schedule_opt)
@@ -123,6 +190,43 @@ class GaussianSampler(_SamplerBase):
 
     predict = super_resolution                                       # ddpm diffusion.py:245-247
 
+    # ---- objective (sr3 diffusion.py:215-249) -----------------------------------------------
+    def q_coefficients(self, continuous_sqrt_alpha_cumprod):
+        """(c0, c2) of q_sample for the (B,) fp32 noise levels: the reference's own torch expressions."""
+        c = continuous_sqrt_alpha_cumprod.reshape(-1).to(torch.float32)
+        return c, (1 - c ** 2).sqrt()
+
+    @torch.no_grad()
+    def q_sample(self, x_start, continuous_sqrt_alpha_cumprod, noise=None):
+        """c*x_start + sqrt(1 - c^2)*noise in one launch; ``noise`` None draws on the device (Philox)."""
+        self._need_cuda(x_start)
+        c0, c2 = self.q_coefficients(continuous_sqrt_alpha_cumprod)
+        return self._q_sample(x_start, (c0, None, c2), noise)
+
+    def _sample_gamma(self, b, t=None):
+        """The host draws of p_losses in the reference's order (sr3 diffusion.py:227-234): (t, (b,) fp32 levels)."""
+        if t is None:
+            t = np.random.randint(1, self.num_timesteps + 1)
+        g = self.sqrt_alphas_cumprod_prev
+        return t, torch.FloatTensor(np.random.uniform(g[t - 1], g[t], size=b))
+
+    @torch.no_grad()
+    def p_losses(self, x_in, noise=None, *, t=None, continuous_sqrt_alpha_cumprod=None):
+        """The objective on ``x_in`` = {'target', 'input'}: loss(noise, UNet(q_sample(target))) with eval semantics
+        (dropout is identity: the validation objective), no graph.  ``t`` / ``continuous_sqrt_alpha_cumprod``
+        override the host draws (a superset of the reference's signature)."""
+        x_start = x_in["target"]
+        self._need_cuda(x_start)
+        b = x_start.shape[0]
+        c = continuous_sqrt_alpha_cumprod
+        if c is None:
+            c = self._sample_gamma(b, t)[1]
+        c = c.reshape(b, -1).to(torch.float32)
+        c0, c2 = self.q_coefficients(c)
+        cond = x_in["input"].to(x_start.device).float() if self.conditional else None
+        x_recon, z = self._noised_forward(x_start, (c0, None, c2), c, noise, cond=cond)
+        return self._loss(z, x_recon)
+
 
 class GaussianSamplerDdpm(GaussianSampler):
     kind = "ddpm"
@@ -131,6 +235,61 @@ class GaussianSamplerDdpm(GaussianSampler):
                  conditional=True, schedule_opt=None, **unused):
         super().__init__(denoise_fn, image_size, channels, loss_type, conditional, schedule_opt)
         self.lr_reduction = lr_reduction or "sum"
+
+    def set_loss(self, device):
+        self._set_loss(device, self.lr_reduction)                    # ddpm diffusion.py:96-107
+
+    # ---- forward process (ddpm diffusion.py:156-177, 266-300): gathers from the registered buffers --------------
+    @staticmethod
+    def _extract(a, t, x_shape):
+        out = a.gather(-1, t.to(a.device))
+        return out.reshape(t.shape[0], *((1,) * (len(x_shape) - 1)))
+
+    def q_mean_variance(self, x_start, t):
+        mean = self._extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+        variance = self._extract(1. - self.alphas_cumprod, t, x_start.shape)
+        log_variance = self._extract(self.log_one_minus_alphas_cumprod, t, x_start.shape)
+        return mean, variance, log_variance
+
+    def predict_start_from_noise(self, x_t, t, noise):
+        return (self._extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t -
+                self._extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * noise)
+
+    def q_posterior(self, x_start, x_t, t):
+        posterior_mean = (self._extract(self.posterior_mean_coef1, t, x_t.shape) * x_start +
+                          self._extract(self.posterior_mean_coef2, t, x_t.shape) * x_t)
+        posterior_variance = self._extract(self.posterior_variance, t, x_t.shape)
+        posterior_log_variance_clipped = self._extract(self.posterior_log_variance_clipped, t, x_t.shape)
+        return posterior_mean, posterior_variance, posterior_log_variance_clipped
+
+    def q_coefficients(self, t):
+        """(c0, c2) of q_sample for integer ``t`` (B,): gathered from the schedule buffers."""
+        t = t.reshape(-1).long().to(self.betas.device)
+        return self.sqrt_alphas_cumprod.gather(-1, t), self.sqrt_one_minus_alphas_cumprod.gather(-1, t)
+
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None):
+        self._need_cuda(x_start)
+        c0, c2 = self.q_coefficients(t)
+        return self._q_sample(x_start, (c0, None, c2), noise)
+
+    def _sample_t(self, b):
+        """ddpm diffusion.py:288: drawn from torch's CPU generator."""
+        return torch.randint(0, self.num_timesteps, (b,)).long()
+
+    @torch.no_grad()
+    def p_losses(self, x_in, noise=None, *, t=None):
+        """loss(noise, UNet(q_sample(target, t), t)) with eval semantics (the validation objective), no graph.
+        ``t`` (B,) integer overrides the host draw."""
+        x_start = x_in["target"]
+        self._need_cuda(x_start)
+        if t is None:
+            t = self._sample_t(x_start.shape[0])
+        t = t.reshape(-1).long()
+        c0, c2 = self.q_coefficients(t)
+        cond = x_in["input"].to(x_start.device).float() if self.conditional else None
+        x_recon, z = self._noised_forward(x_start, (c0, None, c2), t, noise, cond=cond)
+        return self._loss(z, x_recon)
 
 
 class InDISampler(_SamplerBase):
@@ -145,14 +304,95 @@ class InDISampler(_SamplerBase):
         self.conditional = conditional
         self.lr_reduction = lr_reduction or "sum"
         self.e = e
+        self._t_sampling_mode = "linear_indi"                        # indi.py:32-39
+        self._linear_indi_a = 1.0
+        self._noise_mode = "gaussian"
         self.num_timesteps = None
         self.val_num_timesteps = val_schedule_opt["n_timestep"] if val_schedule_opt else None
 
     def set_loss(self, device):
-        self._device = device
+        self._set_loss(device, self.lr_reduction)                    # ddpm diffusion.py:96-107
 
     def set_new_noise_schedule(self, schedule_opt, device):
         self.num_timesteps = schedule_opt["n_timestep"]              # indi.py:46-47
+
+    # ---- objective (indi.py:98-175) -----------------------------------------------------------
+    def _gaussian_noise_mode(self):
+        if self._noise_mode not in ("gaussian", "none"):
+            raise NotImplementedError("noise mode {!r} is not built (only 'gaussian'): 'brownian' is refused"
+                                      .format(self._noise_mode))
+
+    def get_e(self, t):
+        self._gaussian_noise_mode()
+        return self.e if self._noise_mode == "gaussian" else 0.0
+
+    def get_t_times_e(self, t):
+        return self.get_e(t) * t
+
+    def q_coefficients(self, t):
+        """(c0, c1, c2) = (1 - t, t, e*t) of q_sample for the (B,) fp32 times: the reference's own expressions."""
+        t = t.reshape(-1).to(torch.float32)
+        return 1 - t, t, self.get_t_times_e(t)
+
+    @torch.no_grad()
+    def q_sample(self, x_start, x_end, t, noise=None):
+        """(1-t)*x_start + t*x_end + noise*(e*t) in one launch.  ``x_end`` (B, Ce, H, W) with C % Ce == 0 stands
+        for its channel-wise repetition to C channels (indi.py:157)."""
+        assert 0 < t.min(), "t > 0"
+        assert t.max() <= 1, "t <= 1. but t is {}".format(t.max())
+        self._need_cuda(x_start, x_end)
+        if x_start.shape[1] % x_end.shape[1] != 0:
+            raise DsxError("x_end has {} channels, x_start {}: C % Ce != 0".format(x_end.shape[1], x_start.shape[1]))
+        return self._q_sample(x_start, self.q_coefficients(t), noise, x_end=x_end)
+
+    def _draw_t_linear_indi(self, batch_size, hi, maxv):
+        """randint(1, hi), then with probability 1 - 1/(a + 1) the value maxv (indi.py:141-147)."""
+        t = torch.randint(1, hi, (batch_size,)).long()
+        alpha = 1 / (self._linear_indi_a + 1)
+        probab = torch.rand(t.shape)
+        t[probab > alpha] = maxv
+        return t
+
+    def _draw_t(self, batch_size):
+        n = self.num_timesteps
+        mode = self._t_sampling_mode
+        if mode in ("linear_ramp", "quadratic_ramp"):
+            p = torch.arange(n) if mode == "linear_ramp" else torch.arange(n) ** 2   # P(t = 0) = 0
+            return torch.multinomial(p / torch.sum(p), batch_size, replacement=True).long()
+        if mode == "uniform":
+            return torch.randint(1, n + 1, (batch_size,)).long()
+        if mode == "uniform_in_range":
+            return torch.randint((2 * n) // 3, n + 1, (batch_size,)).long()
+        if mode == "linear_indi":
+            return self._draw_t_linear_indi(batch_size, n, n)
+        raise NotImplementedError("t sampling mode {!r}".format(mode))
+
+    def sample_t(self, batch_size, device):
+        """indi.py:126-150: drawn from torch's CPU generator (pure host logic), then moved to ``device``."""
+        return (self._draw_t(batch_size) / self.num_timesteps).to(device)
+
+    @torch.no_grad()
+    def get_prediction_during_training(self, x_in, noise=None, *, t=None):
+        """UNet(q_sample(target, input, t), t) with eval semantics (dropout is identity), no graph.  ``t`` (B,)
+        overrides the host draw."""
+        x_start, x_end = x_in["target"], x_in["input"]
+        self._need_cuda(x_start, x_end)
+        assert self.conditional is False
+        if x_end.shape[1] * self.out_channel != x_start.shape[1]:
+            raise DsxError("input has {} channels x out_channel {} != target's {}".format(
+                x_end.shape[1], self.out_channel, x_start.shape[1]))
+        t_float = self.sample_t(x_start.shape[0], "cpu") if t is None else t.reshape(-1).to(torch.float32)
+        assert 0 < t_float.min(), "t > 0"
+        assert t_float.max() <= 1, "t <= 1. but t is {}".format(t_float.max())
+        x_recon, _ = self._noised_forward(x_start, self.q_coefficients(t_float), t_float, noise,
+                                          xe=x_end.float().contiguous(), want_noise=False)
+        return x_recon
+
+    @torch.no_grad()
+    def p_losses(self, x_in, noise=None, *, t=None):
+        """loss(target, get_prediction_during_training(x_in)): the validation objective, no graph."""
+        x_recon = self.get_prediction_during_training(x_in, noise=noise, t=t)
+        return self._loss(x_in["target"], x_recon)
 
     def _start(self, x_in, t_float_start):
         dev = x_in.device
@@ -239,6 +479,25 @@ class InDISampler(_SamplerBase):
         return x[-1:]                                                # indi.py:92-95: ret_img[-1:]
 
 
+class IndiCustomT(InDISampler):
+    """joint_indi.py:10-22: t in (0, 0.5]."""
+
+    def _draw_t(self, batch_size):
+        assert self._t_sampling_mode == "linear_indi"
+        assert self.num_timesteps % 2 == 0, "num_timesteps should be even since we are dividing it by 2 in the next line."
+        maxv = int(self.num_timesteps * 0.5)
+        return self._draw_t_linear_indi(batch_size, maxv, maxv)
+
+
+class IndiFullTranslation(InDISampler):
+    """joint_indi.py:24-36: t over the whole range, the point mass at 0.5."""
+
+    def _draw_t(self, batch_size):
+        assert self._t_sampling_mode == "linear_indi"
+        assert self.num_timesteps % 2 == 0, "num_timesteps should be even since we are dividing it by 2 in the next line."
+        return self._draw_t_linear_indi(batch_size, self.num_timesteps, int(self.num_timesteps * 0.5))
+
+
 class JointIndiSampler(_SamplerBase):
     """JointIndi (ddpm_modules/joint_indi.py:40-149): indi1 at t0, indi2 at 1-t0; the two
     independent loops run concurrently on two HIP streams instead of back to back."""
@@ -250,19 +509,59 @@ class JointIndiSampler(_SamplerBase):
         assert denoise_fn_ch1 is not None and denoise_fn_ch2 is not None and denoise_fn is None
         kw = dict(channels=channels, loss_type=loss_type, out_channel=out_channel, lr_reduction=lr_reduction,
                   conditional=conditional, schedule_opt=schedule_opt, val_schedule_opt=val_schedule_opt, e=e)
-        self.indi1 = InDISampler(denoise_fn_ch1, image_size, **kw)
-        self.indi2 = InDISampler(denoise_fn_ch2, image_size, **kw)
+        indi_class = IndiFullTranslation if allow_full_translation else IndiCustomT   # joint_indi.py:61
+        self.indi1 = indi_class(denoise_fn_ch1, image_size, **kw)
+        self.indi2 = indi_class(denoise_fn_ch2, image_size, **kw)
         self.val_num_timesteps = self.indi1.val_num_timesteps
         self.alpha_param = nn.Parameter(torch.tensor(0.0))           # kept for *_gen.pth compatibility
         self.offset_param = nn.Parameter(torch.tensor(0.0))
         self.scale_param = nn.Parameter(torch.tensor(1.0))
         self.w_input_loss = w_input_loss
+        self.current_log_dict = {}
         self._streams = None
         self.concurrent = True        # the two loops on two HIP streams; False: back to back on the current stream
 
     @property
     def prediction_channels(self):
         return self.indi1.prediction_channels + self.indi2.prediction_channels   # joint_indi.py:135 (channel cat)
+
+    def get_offset(self):
+        return self.offset_param
+
+    def get_scale(self):
+        return self.scale_param
+
+    def get_alpha(self):
+        return torch.sigmoid(self.alpha_param)
+
+    def get_current_log(self):
+        return self.current_log_dict
+
+    @torch.no_grad()
+    def p_losses(self, x_in, noise=None, *, t=None):
+        """joint_indi.py:103-120: channel 0 is indi1's target with channel 1 as its input, the reverse for indi2;
+        indi1's draws come first; the loss is (l1 + l2) / 2.  Eval semantics (the validation objective), no graph.
+        ``t`` = (t1, t2) overrides the two host draws."""
+        target = x_in["target"]
+        self._need_cuda(target)
+        ch0, ch1 = target[:, 0:1].contiguous(), target[:, 1:2].contiguous()
+        t1, t2 = (None, None) if t is None else t
+        # the joint sampler's noise_source, when set, serves both children for this call only: their own is put back
+        kept = (self.indi1.noise_source, self.indi2.noise_source)
+        try:
+            if self.noise_source is not None:
+                self.indi1.noise_source = self.indi2.noise_source = self.noise_source
+            x_recon_ch1 = self.indi1.get_prediction_during_training({"target": ch0, "input": ch1}, noise=noise, t=t1)
+            x_recon_ch2 = self.indi2.get_prediction_during_training({"target": ch1, "input": ch0}, noise=noise, t=t2)
+        finally:
+            self.indi1.noise_source, self.indi2.noise_source = kept
+        loss_splitting = (self.indi1._loss(ch0, x_recon_ch1) + self.indi2._loss(ch1, x_recon_ch2)) / 2
+        loss_input = 0.0
+        self.current_log_dict["loss_splitting"] = loss_splitting.item()
+        self.current_log_dict["alpha"] = self.get_alpha().item()
+        self.current_log_dict["offset"] = self.get_offset().item()
+        self.current_log_dict["scale"] = self.get_scale().item()
+        return loss_splitting + self.w_input_loss * loss_input
 
     def set_loss(self, device):
         self.indi1.set_loss(device)

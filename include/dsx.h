@@ -253,6 +253,39 @@ int dsx_indi_step(dsx_exec* ex, float t_cur, float c_x0, float c_xt, float noise
 /* Fills n fp32 values with N(0,1) from the engine's Philox4x32-10 stream. */
 int dsx_randn(float* out_dev, int64_t n, uint64_t seed, uint64_t subsequence, void* stream);
 
+/* -------------------------------------------------------------- objective
+ * The forward half of the training objective (p_losses): one noising launch, one UNet forward (dsx_unet_forward, with
+ * per-sample time values), one reduction.  No gradients anywhere.
+ *
+ * dsx_q_sample: q_sample of the three sampler families (sr3 diffusion.py:215-222, ddpm diffusion.py:266-274,
+ * indi.py:116-124) in one launch, NCHW fp32, per element
+ *   xe == NULL :  dst = c0[b]*x0 + c2[b]*z
+ *   else       :  dst = (c0[b]*x0 + c1[b]*xe) + c2[b]*z
+ * with every product and sum rounded separately (no FMA contraction), as the step table above.  The two-term form
+ * adds no zero term.  c0 / c1 / c2: device arrays of B values (c1 may be NULL iff xe is).
+ *   x0  : (B, C, H, W)
+ *   xe  : (B, Ce, H, W), C % Ce == 0, read at channel c % Ce: cat([input] * out_channel, 1) of indi.py:157 without
+ *         materialising it
+ *   dst : (B, Cdst, H, W), written at channels coff .. coff + C - 1 (coff + C <= Cdst), the others left untouched: a
+ *         conditional model's UNet input cat([input, x_noisy], 1) needs no second pass
+ *   z   : (B, C, H, W) injected draws; NULL -> the Philox normals dsx_randn writes for (seed, subsequence) at the
+ *         same flat index, bitwise, also stored to z_out (B, C, H, W) when that is not NULL (the Gaussian loss is
+ *         taken against them).  z_out is ignored when z is given.
+ * 16-byte accesses when H*W is a multiple of 4 and the pointers are 16-byte aligned, a scalar path otherwise.
+ *
+ * dsx_loss: per sample, sum |a - b| (squared == 0: nn.L1Loss) or sum (a - b)^2 (nn.MSELoss) over (C, H, W) of
+ * a, b (B, C, H, W) fp32: difference, square and accumulation in double over a fixed partition
+ * (dsx_loss_blocks(C, H, W) workgroups per sample, a function of the shape only) with a fixed-order finish, no
+ * atomics: equal inputs give bitwise-equal outputs.  partial_dev holds B * dsx_loss_blocks doubles, per_sample_dev
+ * receives B doubles (device; nothing is synchronised).  The caller applies the reduction (sum or mean). */
+int dsx_q_sample(const float* x0_dev, const float* xe_dev, int B, int C, int Ce, int H, int W,
+                 const float* c0_dev, const float* c1_dev, const float* c2_dev,
+                 const float* z_dev, uint64_t seed, uint64_t subsequence, float* z_out_dev,
+                 float* dst_dev, int Cdst, int coff, void* stream);
+int dsx_loss_blocks(int C, int H, int W);
+int dsx_loss(const float* a_dev, const float* b_dev, int B, int C, int H, int W, int squared,
+             double* partial_dev, double* per_sample_dev, void* stream);
+
 /* ----------------------------------------------------------------- tiling */
 
 enum { DSX_TILING_TRIM = 0, DSX_TILING_PAD = 1, DSX_TILING_SHIFT = 2 };  /* tiling_manager.py:6-12 */
