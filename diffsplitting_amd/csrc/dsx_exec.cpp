@@ -382,6 +382,40 @@ extern "C" int dsx_loss(const float* a, const float* b, int B, int C, int H, int
   return DSX_OK;
 }
 
+// ---- caller-driven reverse sampling: one update with its intermediates, the start of interpolate (dsx_steps.hip)
+static int steps_shape(const char* what, int B, int C, int H, int W) {
+  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(DSX_ERR_INVALID, "%s: empty shape (%d, %d, %d, %d)", what, B, C, H, W);
+  if ((int64_t)H * W > INT32_MAX || (int64_t)B * C * H * W > ((int64_t)1 << 40))
+    return fail(DSX_ERR_INVALID, "%s: tensor too large", what);
+  return DSX_OK;
+}
+extern "C" int dsx_posterior_step(const float* x, const float* net, int B, int C, int H, int W, const float* a,
+                                  const float* b, const float* c1, const float* c2, const float* sigma,
+                                  int predict_eps, int clip, const float* z, uint64_t seed, uint64_t subseq,
+                                  int repeat_noise, float* x_recon_out, float* mean_out, float* x_out, void* stream) {
+  int rc = steps_shape("posterior_step", B, C, H, W);
+  if (rc) return rc;
+  if (!x || !net || !c1 || !c2 || !sigma) return fail(DSX_ERR_INVALID, "posterior_step: null argument");
+  if (predict_eps && (!a || !b)) return fail(DSX_ERR_INVALID, "posterior_step: predict_eps needs the columns a and b");
+  if (!x_recon_out && !mean_out && !x_out) return fail(DSX_ERR_INVALID, "posterior_step: every output is null");
+  PosteriorStepArgs p{x, net, a, b, c1, c2, sigma, x_out ? z : nullptr, seed, subseq, x_recon_out, mean_out, x_out,
+                      B, predict_eps ? 1 : 0, clip ? 1 : 0, repeat_noise ? 1 : 0, (int64_t)C * H * W};
+  HIP_TRY(launch_posterior_step(p, (int64_t)H * W, (hipStream_t)stream));
+  return DSX_OK;
+}
+extern "C" int dsx_interp_start(const float* x1, const float* x2, int B, int C, int H, int W, const float* a0,
+                                const float* s0, float c, float d, const float* z1, const float* z2, uint64_t seed,
+                                uint64_t subseq, float* out, void* stream) {
+  int rc = steps_shape("interp_start", B, C, H, W);
+  if (rc) return rc;
+  if (!x1 || !x2 || !a0 || !s0 || !out) return fail(DSX_ERR_INVALID, "interp_start: null argument");
+  if ((z1 == nullptr) != (z2 == nullptr))
+    return fail(DSX_ERR_INVALID, "interp_start: both draws are injected, or neither");
+  InterpStartArgs p{x1, x2, a0, s0, z1, z2, seed, subseq, c, d, out, B, (int64_t)C * H * W};
+  HIP_TRY(launch_interp_start(p, (int64_t)H * W, (hipStream_t)stream));
+  return DSX_OK;
+}
+
 // ------------------------------------------------------------------ time predictor head
 extern "C" int dsx_time_predictor_set_mask(dsx_exec* ex, const float* w, const float* b) {
   if (!ex || !w || !b) return fail(DSX_ERR_INVALID, "null argument");

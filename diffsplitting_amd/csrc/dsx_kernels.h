@@ -475,6 +475,30 @@ int loss_blocks(long long n);
 hipError_t launch_loss(const float* a, const float* b, int B, long long n, int squared, double* part, double* out,
                        hipStream_t st);
 
+// dsx_steps.hip.  One reverse update with its intermediates (NCHW fp32, per-sample coefficients, B values each):
+//   x0 = predict_eps ? clamp(a*x - b*net) : net;  mean = c1*x0 + c2*x;  out = mean + z*sigma (mean where sigma == 0)
+// z == nullptr: element i of the normal stream (seed, subseq); repeat: every sample uses sample 0's draw (z then holds
+// C*H*W values).  Outputs that are nullptr are not written.
+struct PosteriorStepArgs {
+  const float* x; const float* net;
+  const float* a; const float* b; const float* c1; const float* c2; const float* sigma;
+  const float* z; unsigned long long seed, subseq;
+  float* x_recon_out; float* mean_out; float* x_out;
+  int B, predict_eps, clip, repeat;
+  long long CHW;
+};
+hipError_t launch_posterior_step(const PosteriorStepArgs& a, long long HW, hipStream_t st);
+// out = c*(a0[b]*x1 + s0[b]*z1) + d*(a0[b]*x2 + s0[b]*z2); z1 == nullptr: the streams (seed, subseq), (seed, subseq + 1)
+struct InterpStartArgs {
+  const float* x1; const float* x2; const float* a0; const float* s0;
+  const float* z1; const float* z2; unsigned long long seed, subseq;
+  float c, d;
+  float* out;
+  int B;
+  long long CHW;
+};
+hipError_t launch_interp_start(const InterpStartArgs& a, long long HW, hipStream_t st);
+
 // the tiles of one launch: ids first, first + stride, ... (count of them); the tables a kernel indexes with an id
 // (`starts` [..][3], `regions` [..][8], `off` [..]) live on the device -- the plan's own (dsx_tileplan), or a per-call
 // table with first = 0, stride = 1

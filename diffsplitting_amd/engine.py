@@ -423,25 +423,63 @@ def gaussian_buffers(schedule_opt):
     return bufs, np.sqrt(np.append(1.0, ac))
 
 
-def gaussian_step_table(bufs, gamma_table_f64, kind, clip_denoised=True):
-    """Rows in execution order i = T-1 .. 0 (sr3 diffusion.py:196-199).
+STEP_COLUMNS = ("tcond", "a", "b", "c1", "c2", "sigma")
 
-    ``kind`` "sr3": tcond = fp32(sqrt_alphas_cumprod_prev[i+1]) (:153-154);
-    "ddpm": tcond = float(i) (ddpm diffusion.py:216-217).  sigma = exp(0.5*logvar)
-    evaluated with torch fp32 like the reference (:175); sigma = 0 at i == 0
+
+def gaussian_step_columns(bufs, gamma_table_f64, kind):
+    """The six step scalars of every timestep, indexed by t = 0 .. T-1 (fp32 numpy, ``STEP_COLUMNS``).
+
+    ``kind`` "sr3": tcond = fp32(sqrt_alphas_cumprod_prev[t+1]) (sr3 diffusion.py:153-154);
+    "ddpm": tcond = float(t) (ddpm diffusion.py:216-217).  sigma = exp(0.5*logvar)
+    evaluated with torch fp32 like the reference (:175); sigma = 0 at t == 0
     (no noise at t == 0: :174 / ddpm :199-203)."""
     T = bufs["betas"].shape[0]
-    order = np.arange(T - 1, -1, -1)
+    t = np.arange(T)
     if kind == "sr3":
-        tcond = torch.tensor(gamma_table_f64[order + 1], dtype=torch.float64).to(torch.float32).numpy()
+        tcond = torch.tensor(gamma_table_f64[t + 1], dtype=torch.float64).to(torch.float32).numpy()
     else:
-        tcond = order.astype(np.float32)
+        tcond = t.astype(np.float32)
     sigma = (0.5 * bufs["posterior_log_variance_clipped"]).exp().numpy().copy()
     sigma[0] = 0.0
-    g = lambda k: bufs[k].numpy()[order]
-    return StepTableHost(tcond, c1=g("posterior_mean_coef1"), c2=g("posterior_mean_coef2"),
-                         sigma=sigma[order], a=g("sqrt_recip_alphas_cumprod"),
-                         b=g("sqrt_recipm1_alphas_cumprod"), predict_eps=True, clip=clip_denoised)
+    g = lambda k: bufs[k].numpy()
+    return dict(tcond=tcond, a=g("sqrt_recip_alphas_cumprod"), b=g("sqrt_recipm1_alphas_cumprod"),
+                c1=g("posterior_mean_coef1"), c2=g("posterior_mean_coef2"), sigma=sigma)
+
+
+def gaussian_step_table(bufs, gamma_table_f64, kind, clip_denoised=True, start=None):
+    """Rows of ``gaussian_step_columns`` in execution order i = T-1 .. 0 (sr3 diffusion.py:196-199), or, with
+    ``start`` = t, the tail i = t-1 .. 0 of it: the loop of interpolate (ddpm diffusion.py:260-262)."""
+    T = bufs["betas"].shape[0]
+    start = T if start is None else int(start)
+    if not 1 <= start <= T:
+        raise DsxError(f"a step table starts at 1 <= t <= {T}, got {start}")
+    cols = gaussian_step_columns(bufs, gamma_table_f64, kind)
+    order = np.arange(start - 1, -1, -1)
+    g = lambda k: cols[k][order]
+    return StepTableHost(g("tcond"), c1=g("c1"), c2=g("c2"), sigma=g("sigma"), a=g("a"), b=g("b"),
+                         predict_eps=True, clip=clip_denoised)
+
+
+def gaussian_step_rows(bufs, gamma_table_f64, kind, t):
+    """The rows of the Gaussian step table for integer ``t`` (a scalar or (B,) values): a dict of ``STEP_COLUMNS`` ->
+    fp32 numpy arrays of ``t``'s shape, the very numbers ``gaussian_step_table`` holds at row T-1-t."""
+    T = bufs["betas"].shape[0]
+    t = np.asarray(t.detach().cpu() if torch.is_tensor(t) else t)
+    if t.dtype.kind not in "iu":
+        raise DsxError(f"timesteps are integers, got {t.dtype}")
+    if t.size and (t.min() < 0 or t.max() >= T):
+        raise DsxError(f"timesteps must lie in 0..{T - 1}")
+    cols = gaussian_step_columns(bufs, gamma_table_f64, kind)
+    return {k: cols[k][t] for k in STEP_COLUMNS}
+
+
+def indi_step_row(delta, cur_t, e=0.01):
+    """(tcond, c1, c2, sigma) of one InDI step (indi.py:65-68) as python floats holding fp32 values: the very torch
+    expressions on a (1,) fp32 tensor, so scalar promotion and rounding (e.g. python_float / tensor == reciprocal *
+    scalar) match."""
+    t_cur = torch.Tensor([cur_t])
+    r = delta / t_cur
+    return t_cur.item(), r.item(), (1 - r).item(), (e * (t_cur - delta)).item()
 
 
 def indi_step_table(num_timesteps, t_float_start, e=0.01):
@@ -450,17 +488,11 @@ def indi_step_table(num_timesteps, t_float_start, e=0.01):
     python-scalar (op) fp32-tensor.  The drift assert of indi.py:64 is dropped (R3)."""
     delta = t_float_start / num_timesteps
     cur_t = t_float_start
-    ts, c1, c2, sg = [], [], [], []
+    rows = []
     for _ in range(num_timesteps):
-        # the very torch expressions of indi.py:65-68 on a (1,) fp32 tensor, so scalar
-        # promotion and rounding (e.g. python_float / tensor == reciprocal * scalar) match
-        t_cur = torch.Tensor([cur_t])
-        r = delta / t_cur
-        ts.append(t_cur.item())
-        c1.append(r.item())
-        c2.append((1 - r).item())
-        sg.append((e * (t_cur - delta)).item())
+        rows.append(indi_step_row(delta, cur_t, e))
         cur_t -= delta
+    ts, c1, c2, sg = zip(*rows)
     return StepTableHost(ts, c1=c1, c2=c2, sigma=sg, predict_eps=False, clip=False)
 
 
@@ -561,4 +593,66 @@ def loss_per_sample(a, b, squared):
     part = torch.empty(B * blocks, dtype=torch.float64, device=a.device)
     out = torch.empty(B, dtype=torch.float64, device=a.device)
     check(lib.dsx_loss(_dptr(a), _dptr(b), B, Cn, H, W, 1 if squared else 0, _dptr(part), _dptr(out), _stream_ptr()))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# caller-driven reverse sampling (dsx_posterior_step / dsx_interp_start, include/dsx.h)
+# ---------------------------------------------------------------------------
+def _coef(c, what, B):
+    c = _f32_cuda(c, what).reshape(-1)
+    if c.numel() != B:
+        raise DsxError(f"{what} must hold B = {B} values, got {c.numel()}")
+    return c
+
+
+def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, clip=False, z=None, seed=0, subsequence=0,
+                   repeat_noise=False, x_recon_out=None, mean_out=None, x_out=None):
+    """``dsx_posterior_step``: one reverse update with its intermediates in one launch.  ``a`` .. ``sigma``: (B,)
+    per-sample coefficients; ``z`` (B, C, H, W) -- (1, C, H, W) under ``repeat_noise`` -- or None for the Philox normals
+    of ``randn(x.shape, seed, subsequence)``.  Only the outputs given are written (``x_out`` may be ``x``); every
+    tensor must be contiguous float32 on the device.  Returns ``(x_recon_out, mean_out, x_out)``."""
+    x = _f32_cuda(x, "x")
+    if x.dim() != 4:
+        raise DsxError(f"x must be (B, C, H, W), got {tuple(x.shape)}")
+    B, Cn, H, W = x.shape
+    net = _f32_cuda(net, "net", x.shape)
+    c1, c2, sigma = _coef(c1, "c1", B), _coef(c2, "c2", B), _coef(sigma, "sigma", B)
+    if predict_eps:
+        if a is None or b is None:
+            raise DsxError("predict_eps needs the columns a and b")
+        a, b = _coef(a, "a", B), _coef(b, "b", B)
+    else:
+        a = b = None
+    if z is not None:
+        z = _f32_cuda(z, "noise", (1, Cn, H, W) if repeat_noise else x.shape)
+    outs = [None if o is None else _f32_cuda(o, what, x.shape)
+            for o, what in ((x_recon_out, "x_recon_out"), (mean_out, "mean_out"), (x_out, "x_out"))]
+    check(lib.dsx_posterior_step(_dptr(x), _dptr(net), B, Cn, H, W, _dptr(a), _dptr(b), _dptr(c1), _dptr(c2),
+                                 _dptr(sigma), 1 if predict_eps else 0, 1 if clip else 0, _dptr(z),
+                                 C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(subsequence)),
+                                 1 if repeat_noise else 0, _dptr(outs[0]), _dptr(outs[1]), _dptr(outs[2]),
+                                 _stream_ptr()))
+    return tuple(outs)
+
+
+def interp_start(x1, x2, a0, s0, lam, z1=None, z2=None, seed=0, subsequence=0, out=None):
+    """``dsx_interp_start``: ``(1 - lam)*q_sample(x1) + lam*q_sample(x2)`` in one launch, ``a0`` / ``s0`` the (B,)
+    coefficients of q_sample.  ``1 - lam`` is formed in double and each scalar rounded to fp32 once, as torch does for
+    a python scalar against an fp32 tensor.  ``z1`` / ``z2``: both injected, or both None for the Philox normals of
+    ``randn(shape, seed, subsequence)`` and ``randn(shape, seed, subsequence + 1)``."""
+    x1 = _f32_cuda(x1, "x1")
+    if x1.dim() != 4:
+        raise DsxError(f"x1 must be (B, C, H, W), got {tuple(x1.shape)}")
+    B, Cn, H, W = x1.shape
+    x2 = _f32_cuda(x2, "x2", x1.shape)
+    a0, s0 = _coef(a0, "a0", B), _coef(s0, "s0", B)
+    if (z1 is None) != (z2 is None):
+        raise DsxError("both draws are injected, or neither")
+    if z1 is not None:
+        z1, z2 = _f32_cuda(z1, "z1", x1.shape), _f32_cuda(z2, "z2", x1.shape)
+    out = torch.empty_like(x1) if out is None else _f32_cuda(out, "out", x1.shape)
+    check(lib.dsx_interp_start(_dptr(x1), _dptr(x2), B, Cn, H, W, _dptr(a0), _dptr(s0), C.c_float(1 - float(lam)),
+                               C.c_float(float(lam)), _dptr(z1), _dptr(z2), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                               C.c_uint64(int(subsequence)), _dptr(out), _stream_ptr()))
     return out

@@ -5,7 +5,9 @@ shapes and drives ``UNetEngine.sample_loop`` (a captured
 hipGraph per step).  ``forward`` / ``p_losses`` evaluate the training objective's forward half on the device
 (one noising launch, one UNet forward, one reduction) under ``torch.no_grad()``: the UNet always runs with eval
 semantics (dropout is identity), so the value is the validation objective and carries no graph.
-Training itself (backward, optimiser) stays out of scope.
+Training itself (backward, optimiser) stays out of scope.  The single reverse steps (``p_mean_variance``, ``p_sample``,
+``inference_one_step``) and ``interpolate`` let a caller drive the loop: one UNet forward and one
+``dsx_posterior_step`` launch per step.
 
 Noise: by default the per-step noise is drawn on the device (Philox, seeded
 from torch's generator); set ``noise_source`` to a ``randn(shape)`` callable to
@@ -190,6 +192,72 @@ class GaussianSampler(_SamplerBase):
 
     predict = super_resolution                                       # ddpm diffusion.py:245-247
 
+    # ---- caller-driven reverse steps (sr3 diffusion.py:141-175, ddpm diffusion.py:163-203) ------------------
+    def _rows(self, t, B, dev):
+        """The step-table rows of ``t`` (an integer, or (B,) integers) as (B,) fp32 device tensors per column."""
+        if self.num_timesteps is None:
+            raise DsxError("set_new_noise_schedule() first")
+        if torch.is_tensor(t):
+            t = t.detach().reshape(-1).cpu()
+            if t.numel() != B:
+                raise DsxError(f"t must hold B = {B} timesteps, got {t.numel()}")
+        rows = engine.gaussian_step_rows(self._bufs_cpu, self.sqrt_alphas_cumprod_prev, self.kind, t)
+        return {k: torch.from_numpy(np.ascontiguousarray(np.broadcast_to(v, (B,)))).to(dev) for k, v in rows.items()}
+
+    @staticmethod
+    def _unet_input(x, condition_x):
+        """cat([condition_x, x], 1) written into one buffer, as the objective's noising launch fills it."""
+        if condition_x is None:
+            return x
+        cc = condition_x.shape[1]
+        inp = torch.empty((x.shape[0], cc + x.shape[1]) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        inp[:, :cc] = condition_x
+        inp[:, cc:] = x
+        return inp
+
+    def _reverse(self, x, t, clip_denoised, condition_x, want, z=None, seed=0, repeat_noise=False):
+        """One UNet forward and one dsx_posterior_step launch: ``want`` = (x_recon, model_mean, sample) flags, the
+        wanted ones are returned as new tensors, the others as None."""
+        self._need_cuda(x, *(() if condition_x is None else (condition_x,)))
+        x = x.float().contiguous()
+        B = x.shape[0]
+        r = self._rows(t, B, x.device)
+        time = r["tcond"].view(B, 1) if self.kind == "sr3" else r["tcond"]
+        net = self.denoise_fn(self._unet_input(x, condition_x), time)
+        outs = [torch.empty_like(x) if w else None for w in want]
+        return engine.posterior_step(x, net, r["c1"], r["c2"], r["sigma"], a=r["a"], b=r["b"], predict_eps=True,
+                                     clip=bool(clip_denoised), z=z, seed=seed, repeat_noise=repeat_noise,
+                                     x_recon_out=outs[0], mean_out=outs[1], x_out=outs[2])
+
+    @torch.no_grad()
+    def predict_start_from_noise(self, x_t, t, noise):
+        self._need_cuda(x_t, noise)
+        x_t = x_t.float().contiguous()
+        r = self._rows(t, x_t.shape[0], x_t.device)
+        return engine.posterior_step(x_t, noise.float().contiguous(), r["c1"], r["c2"], r["sigma"], a=r["a"], b=r["b"],
+                                     predict_eps=True, x_recon_out=torch.empty_like(x_t))[0]
+
+    @torch.no_grad()
+    def q_posterior(self, x_start, x_t, t):
+        self._need_cuda(x_start, x_t)
+        x_t = x_t.float().contiguous()
+        r = self._rows(t, x_t.shape[0], x_t.device)
+        mean = engine.posterior_step(x_t, x_start.float().contiguous(), r["c1"], r["c2"], r["sigma"],
+                                     mean_out=torch.empty_like(x_t))[1]
+        return mean, self.posterior_log_variance_clipped[t]
+
+    @torch.no_grad()
+    def p_mean_variance(self, x, t, clip_denoised: bool, condition_x=None):
+        mean = self._reverse(x, t, clip_denoised, condition_x, (False, True, False))[1]
+        return mean, self.posterior_log_variance_clipped[t]
+
+    @torch.no_grad()
+    def p_sample(self, x, t, clip_denoised=True, condition_x=None):
+        """One draw per call, none at t == 0 (sr3 diffusion.py:174)."""
+        self._need_cuda(x)
+        z, seed = self._noise_or_seed(None, x.shape, x.device) if t > 0 else (None, 0)
+        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), z=z, seed=seed)[2]
+
     # ---- objective (sr3 diffusion.py:215-249) -----------------------------------------------
     def q_coefficients(self, continuous_sqrt_alpha_cumprod):
         """(c0, c2) of q_sample for the (B,) fp32 noise levels: the reference's own torch expressions."""
@@ -261,6 +329,55 @@ class GaussianSamplerDdpm(GaussianSampler):
         posterior_variance = self._extract(self.posterior_variance, t, x_t.shape)
         posterior_log_variance_clipped = self._extract(self.posterior_log_variance_clipped, t, x_t.shape)
         return posterior_mean, posterior_variance, posterior_log_variance_clipped
+
+    # ---- caller-driven reverse steps (ddpm diffusion.py:179-264): t is a (B,) long tensor, entries may differ ----
+    @torch.no_grad()
+    def p_mean_variance(self, x, t, clip_denoised: bool, condition_x=None):
+        mean = self._reverse(x, t, clip_denoised, condition_x, (False, True, False))[1]
+        return (mean, self._extract(self.posterior_variance, t, x.shape),
+                self._extract(self.posterior_log_variance_clipped, t, x.shape))
+
+    @torch.no_grad()
+    def p_sample(self, x, t, clip_denoised=True, repeat_noise=False, condition_x=None):
+        """The draw is taken on every call -- (1, C, H, W) under ``repeat_noise`` -- and a sample at t == 0 gets none of
+        it (the reference's nonzero_mask, ddpm diffusion.py:199-203)."""
+        self._need_cuda(x)
+        shape = ((1,) + tuple(x.shape[1:])) if repeat_noise else tuple(x.shape)
+        z, seed = self._noise_or_seed(None, shape, x.device)
+        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), z=z, seed=seed,
+                             repeat_noise=bool(repeat_noise))[2]
+
+    @torch.no_grad()
+    def interpolate(self, x1, x2, t=None, lam=0.5):
+        """(1 - lam)*q_sample(x1, t) + lam*q_sample(x2, t) in one launch, then the steps i = t-1 .. 0 through the
+        engine's loop; returns the whole batch.  Draws: x1's, x2's, then one per step."""
+        if self.conditional:
+            raise DsxError("interpolate: the reference steps without a condition (ddpm diffusion.py:260-262); a "
+                           "conditional sampler cannot interpolate")
+        self._need_cuda(x1, x2)
+        if self.num_timesteps is None:
+            raise DsxError("set_new_noise_schedule() first")
+        t = self.num_timesteps - 1 if t is None else int(t)
+        assert x1.shape == x2.shape
+        if not 0 <= t < self.num_timesteps:
+            raise DsxError(f"interpolate: t must lie in 0..{self.num_timesteps - 1}, got {t}")
+        dev = x1.device
+        b = x1.shape[0]
+        c0, c2 = self.q_coefficients(torch.full((b,), t, dtype=torch.long))
+        z1, seed = self._noise_or_seed(None, x1.shape, dev)
+        z2 = None if z1 is None else self._draw(x1.shape, dev).contiguous()
+        img = engine.interp_start(x1.float().contiguous(), x2.float().contiguous(), c0.to(dev).contiguous(),
+                                  c2.to(dev).contiguous(), lam, z1=z1, z2=z2, seed=seed)
+        if t == 0:
+            return img
+        noise = None
+        if self.noise_source is not None:
+            noise = torch.stack([self._draw(x1.shape, dev) for _ in range(t)])
+        table = engine.gaussian_step_table(self._bufs_cpu, self.sqrt_alphas_cumprod_prev, self.kind, True, start=t)
+        x, _ = self.denoise_fn.engine().sample_loop(table, img, noise=noise, seed=self._seed(),
+                                                    use_graph=self.use_graph)
+        self.last_full_batch = x
+        return x
 
     def q_coefficients(self, t):
         """(c0, c2) of q_sample for integer ``t`` (B,): gathered from the schedule buffers."""
@@ -393,6 +510,40 @@ class InDISampler(_SamplerBase):
         """loss(target, get_prediction_during_training(x_in)): the validation objective, no graph."""
         x_recon = self.get_prediction_during_training(x_in, noise=noise, t=t)
         return self._loss(x_in["target"], x_recon)
+
+    # ---- the Gaussian methods InDI overrides away (indi.py:50-60,112-114) -----------------------------------
+    def q_mean_variance(self, x_start, t):
+        raise NotImplementedError("This is not needed.")
+
+    def predict_start_from_noise(self, x_t, t, noise):
+        raise NotImplementedError("This is not needed.")
+
+    def q_posterior(self, x_start, x_t, t):
+        raise NotImplementedError("This is not needed.")
+
+    def p_mean_variance(self, x, t, clip_denoised: bool, condition_x=None):
+        raise NotImplementedError("This is not needed.")
+
+    def interpolate(self, x1, x2, t=None, lam=0.5):
+        raise NotImplementedError("This is not needed.")
+
+    @torch.no_grad()
+    def inference_one_step(self, x_t, delta_t, t_cur):
+        """indi.py:62-69: delta/t * UNet(x_t, t) + (1 - delta/t) * x_t + z * e (t - delta), one UNet forward and one
+        dsx_posterior_step launch; the coefficients are one row of ``engine.indi_step_table``.  One draw per call."""
+        assert delta_t <= t_cur, "delta_t should be less than or equal to t_cur."
+        self._gaussian_noise_mode()
+        if not x_t.is_cuda:
+            raise DsxError("inference_one_step runs on the MI355X only; pass a CUDA tensor (no CPU fallback)")
+        dev = x_t.device
+        x_t = x_t.float().contiguous()
+        B = x_t.shape[0]
+        tc, c1, c2, sg = engine.indi_step_row(delta_t, t_cur, self.get_e(t_cur))
+        col = lambda v: torch.full((B,), v, dtype=torch.float32, device=dev)
+        x_0 = self.denoise_fn(x_t, torch.Tensor([tc]).to(dev))
+        z, seed = self._noise_or_seed(None, x_t.shape, dev)
+        return engine.posterior_step(x_t, x_0, col(c1), col(c2), col(sg), predict_eps=False, z=z, seed=seed,
+                                     x_out=torch.empty_like(x_t))[2]
 
     def _start(self, x_in, t_float_start):
         dev = x_in.device

@@ -286,6 +286,38 @@ int dsx_loss_blocks(int C, int H, int W);
 int dsx_loss(const float* a_dev, const float* b_dev, int B, int C, int H, int W, int squared,
              double* partial_dev, double* per_sample_dev, void* stream);
 
+/* ------------------------------------------------- caller-driven reverse sampling
+ * The single reverse steps of the sampler classes as the caller's own loop uses them (p_mean_variance / p_sample, sr3
+ * diffusion.py:151-175, ddpm diffusion.py:179-203; inference_one_step, indi.py:62-69) and the start of interpolate
+ * (ddpm diffusion.py:249-259).  The UNet forward in front of a step is dsx_unet_forward.  NCHW fp32 device tensors, one
+ * launch each, nothing allocated or synchronised; every product and sum rounded separately (no FMA contraction);
+ * 16-byte accesses when H*W is a multiple of 4 and the pointers are 16-byte aligned, a scalar path otherwise.
+ *
+ * dsx_posterior_step: the update of dsx_step_table with per-sample coefficients (device arrays of B values each) and
+ * its intermediate quantities, per element of sample b
+ *   x0   = a[b]*x - b[b]*net, clamped to +-1 if clip    (predict_eps == 0: x0 = net, never clamped; a, b may be NULL)
+ *   mean = c1[b]*x0 + c2[b]*x
+ *   out  = mean + z*sigma[b]                             (sigma[b] == 0: out = mean, nothing drawn, nothing added)
+ *   x, net : (B, C, H, W)
+ *   z      : (B, C, H, W) injected draws, or NULL -> the Philox normals dsx_randn writes for (seed, subsequence) at the
+ *            same flat index, bitwise.  repeat_noise != 0: every sample takes the draw of sample 0 (noise_like(...,
+ *            repeat=True), ddpm diffusion.py:70-75); an injected z then holds (1, C, H, W).  Read only for x_out.
+ *   x_recon_out, mean_out, x_out : (B, C, H, W) each, any of them NULL (not all three), those are left untouched;
+ *            x_out may be x (in place).
+ *
+ * dsx_interp_start:  out = c*(a0[b]*x1 + s0[b]*z1) + d*(a0[b]*x2 + s0[b]*z2), the two inner expressions being
+ * dsx_q_sample's two-term form bitwise; c = (float)(1 - lam), d = (float)lam.  z1, z2 (B, C, H, W): both injected, or
+ * both NULL -> the Philox streams (seed, subsequence) and (seed, subsequence + 1), in that order. */
+int dsx_posterior_step(const float* x_dev, const float* net_dev, int B, int C, int H, int W,
+                       const float* a_dev, const float* b_dev, const float* c1_dev, const float* c2_dev,
+                       const float* sigma_dev, int predict_eps, int clip,
+                       const float* z_dev, uint64_t seed, uint64_t subsequence, int repeat_noise,
+                       float* x_recon_out_dev, float* mean_out_dev, float* x_out_dev, void* stream);
+int dsx_interp_start(const float* x1_dev, const float* x2_dev, int B, int C, int H, int W,
+                     const float* a0_dev, const float* s0_dev, float c, float d,
+                     const float* z1_dev, const float* z2_dev, uint64_t seed, uint64_t subsequence,
+                     float* out_dev, void* stream);
+
 /* ----------------------------------------------------------------- tiling */
 
 enum { DSX_TILING_TRIM = 0, DSX_TILING_PAD = 1, DSX_TILING_SHIFT = 2 };  /* tiling_manager.py:6-12 */

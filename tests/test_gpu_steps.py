@@ -1,0 +1,391 @@
+"""Caller-driven reverse sampling on the MI355X (`-m gpu`, fp32 build): dsx_posterior_step and dsx_interp_start bit-exact
+against the torch fp32 expression, their Philox paths against dsx_randn, and p_mean_variance / p_sample /
+inference_one_step / interpolate of the samplers against the fixtures the reference wrote
+(tools/gen_steps_golden.py) and, chained, against the reference's own loops (oracle/gen_golden.py)."""
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import cases
+from tests.gpu_util import maxabs
+from tests.util import golden_state_dict, load_golden
+
+pytestmark = pytest.mark.gpu
+torch.set_grad_enabled(False)
+FP32_TOL = 1e-3          # the project's per-pixel fp32 bound on a UNet output (tests/test_gpu_parity.py)
+SCHED = cases.SCHEDULES["lin_8"]
+SENTINEL = -7.25
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+def _bit_equal(a, b):
+    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
+
+
+def _rand(shape, seed):
+    return torch.randn(shape, generator=torch.Generator().manual_seed(seed))
+
+
+def _t(g, key):
+    return torch.from_numpy(g[key])
+
+
+def _off(t):
+    """The same values on the device, 4 bytes past a 16-byte boundary."""
+    o = torch.cat([torch.zeros(1), t.reshape(-1)]).cuda()[1:].view(t.shape)
+    assert o.data_ptr() % 16 == 4 and o.is_contiguous()
+    return o
+
+
+# per-sample coefficients, all different; sample 1 has sigma = 0
+COEF = dict(a=torch.tensor([1.0371, 2.2360679, 1.0000501]), b=torch.tensor([0.2748, 2.0, 0.0100123]),
+            c1=torch.tensor([0.75623951, 0.31, 0.9990234]), c2=torch.tensor([0.1, 0.654321, 0.0123]),
+            sigma=torch.tensor([0.37, 0.0, 0.81]))
+
+
+def _ref_step(x, net, co, z, predict_eps, clip, repeat=False):
+    """dsx_posterior_step in torch fp32 on the CPU: separately rounded products and sums."""
+    v = lambda k: co[k].view(-1, 1, 1, 1)
+    x0 = net
+    if predict_eps:
+        x0 = v("a") * x - v("b") * net
+        if clip:
+            x0 = x0.clamp(-1.0, 1.0)
+    mean = v("c1") * x0 + v("c2") * x
+    if repeat:
+        z = z.repeat(x.shape[0], 1, 1, 1)
+    return x0, mean, torch.where(v("sigma") != 0, mean + z * v("sigma"), mean)
+
+
+def _call(x, net, co, put=lambda t: t.cuda(), **kw):
+    from diffsplitting_amd import engine
+    dev = {k: v.cuda() for k, v in co.items()}
+    return engine.posterior_step(put(x) if not x.is_cuda else x, put(net), dev["c1"], dev["c2"], dev["sigma"],
+                                 a=dev["a"], b=dev["b"], **kw)
+
+
+# ----------------------------------------------------------------------------- dsx_posterior_step, injected z
+@pytest.mark.parametrize("shape", [
+    (2, 3, 8, 8),        # 16-byte path
+    (3, 3, 5, 7),        # H*W = 35: scalar path, groups of four straddle rows and samples
+    (1, 1, 1, 1),        # less than one group
+    (3, 2, 64, 68),      # 16-byte path, more than one workgroup
+    (3, 2, 33, 67),      # scalar path, more than one workgroup
+])
+@pytest.mark.parametrize("clip", [0, 1])
+@pytest.mark.parametrize("predict_eps", [0, 1])
+def test_posterior_step_bit_exact(shape, clip, predict_eps):
+    """Every combination of NULL outputs; outputs not asked for keep their sentinel (they are not even passed)."""
+    B = shape[0]
+    co = {k: v[:B] for k, v in COEF.items()}
+    x, net, z = _rand(shape, 1), 0.7 * _rand(shape, 2), _rand(shape, 3)
+    ref = _ref_step(x, net, co, z, predict_eps, clip)
+    if predict_eps and clip:
+        assert bool((ref[0].abs() == 1).any()) or shape == (1, 1, 1, 1)       # the clamp is exercised
+    for want in itertools.product((0, 1), repeat=3):
+        if not any(want):
+            continue
+        bufs = [torch.full(shape, SENTINEL, device="cuda") for _ in range(3)]
+        _call(x, net, co, predict_eps=predict_eps, clip=clip, z=z.cuda(),
+              x_recon_out=bufs[0] if want[0] else None, mean_out=bufs[1] if want[1] else None,
+              x_out=bufs[2] if want[2] else None)
+        for w, got, r in zip(want, bufs, ref):
+            assert _bit_equal(got, r) if w else bool((got == SENTINEL).all()), (want, w)
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 8, 8), (3, 3, 5, 7)])
+def test_posterior_step_in_place_and_unaligned(shape):
+    B = shape[0]
+    co = {k: v[:B] for k, v in COEF.items()}
+    x, net, z = _rand(shape, 4), _rand(shape, 5), _rand(shape, 6)
+    ref = _ref_step(x, net, co, z, 1, 1)
+    # x_out aliasing x
+    xg = x.cuda()
+    recon = torch.empty_like(xg)
+    out = _call(xg, net, co, predict_eps=1, clip=1, z=z.cuda(), x_recon_out=recon, x_out=xg)
+    assert out[2].data_ptr() == xg.data_ptr() and _bit_equal(xg, ref[2]) and _bit_equal(recon, ref[0])
+    # base pointers 4 bytes past a 16-byte boundary: the scalar path whatever H*W is
+    n = x.numel()
+    outs = [torch.full((n + 1,), SENTINEL, device="cuda")[1:].view(shape) for _ in range(3)]
+    _call(x, net, co, put=_off, predict_eps=1, clip=1, z=_off(z), x_recon_out=outs[0], mean_out=outs[1], x_out=outs[2])
+    assert all(_bit_equal(o, r) for o, r in zip(outs, ref))
+    # only one operand misaligned
+    got = _call(x, net, co, predict_eps=1, clip=1, z=_off(z), x_out=torch.empty(shape, device="cuda"))[2]
+    assert _bit_equal(got, ref[2])
+
+
+@pytest.mark.parametrize("shape", [(3, 3, 8, 8), (3, 3, 5, 7)])
+def test_posterior_step_repeat_noise_injected(shape):
+    """An injected z of shape (1, C, H, W) serves every sample (noise_like(..., repeat=True))."""
+    x, net, z = _rand(shape, 7), _rand(shape, 8), _rand((1,) + shape[1:], 9)
+    ref = _ref_step(x, net, COEF, z, 1, 0, repeat=True)
+    got = _call(x, net, COEF, predict_eps=1, clip=0, z=z.cuda(), repeat_noise=True, x_out=torch.empty(shape, device="cuda"))[2]
+    assert _bit_equal(got, ref[2])
+
+
+def test_posterior_step_refusals():
+    from diffsplitting_amd import engine
+    from diffsplitting_amd._lib import DsxError
+    shape = (2, 3, 8, 8)
+    x = _rand(shape, 1).cuda()
+    c = torch.ones(2, device="cuda")
+    with pytest.raises(DsxError, match="output"):
+        engine.posterior_step(x, x, c, c, c)
+    with pytest.raises(DsxError):
+        engine.posterior_step(x, x, c, c, c, predict_eps=True, x_out=torch.empty_like(x))      # no a / b
+    with pytest.raises(DsxError):
+        engine.posterior_step(x, x, c, c, torch.ones(3, device="cuda"), x_out=torch.empty_like(x))
+    with pytest.raises(DsxError):
+        engine.posterior_step(x, x, c, c, c, z=x, repeat_noise=True, x_out=torch.empty_like(x))  # z must be (1, C, H, W)
+    with pytest.raises(DsxError):
+        engine.posterior_step(x.cpu(), x, c, c, c, x_out=torch.empty_like(x))
+
+
+# ----------------------------------------------------------------------------- dsx_posterior_step, Philox z
+@pytest.mark.parametrize("shape", [(3, 3, 8, 8), (3, 3, 5, 7), (3, 1, 64, 67)])
+def test_posterior_step_philox_path(shape):
+    """sigma = 1 and c1 = c2 = 0 make x_out the draw itself (0 + z * 1), so it is compared with dsx_randn directly and
+    never recovered by a division.  Sample 1 has sigma = 0: it gets its mean, here 0."""
+    from diffsplitting_amd import engine
+    B = shape[0]
+    x, net = _rand(shape, 10), _rand(shape, 11)
+    zero = torch.zeros(B)
+    co = dict(a=zero, b=zero, c1=zero, c2=zero, sigma=torch.tensor([1.0, 0.0, 1.0]))
+    run = lambda **kw: _call(x, net, co, predict_eps=0, x_out=torch.empty(shape, device="cuda"), **kw)[2]
+    out = run(seed=1234, subsequence=5)
+    z = engine.randn(shape, 1234, 5)
+    assert _bit_equal(out[0], z[0]) and _bit_equal(out[2], z[2])
+    assert bool((out[1] == 0).all())
+    assert _bit_equal(run(seed=1234, subsequence=5), out)                       # same seed: bitwise equal
+    assert not _bit_equal(run(seed=1235, subsequence=5), out)
+    assert not _bit_equal(run(seed=1234, subsequence=6), out)
+    rep = run(seed=1234, subsequence=5, repeat_noise=True)
+    first = engine.randn((1,) + shape[1:], 1234, 5)[0]                          # sample 0's draw
+    assert _bit_equal(rep[0], first) and _bit_equal(rep[2], first) and _bit_equal(rep[0], out[0])
+    assert bool((rep[1] == 0).all())
+    # with real coefficients the Philox result equals the injected one
+    got = _call(x, net, COEF, predict_eps=1, clip=1, seed=77, subsequence=3, x_out=torch.empty(shape, device="cuda"))[2]
+    inj = _call(x, net, COEF, predict_eps=1, clip=1, z=engine.randn(shape, 77, 3), x_out=torch.empty(shape, device="cuda"))[2]
+    assert _bit_equal(got, inj)
+
+
+# ----------------------------------------------------------------------------- dsx_interp_start
+@pytest.mark.parametrize("tag", ["a", "b"])
+@pytest.mark.parametrize("unaligned", [False, True])
+def test_interp_start_matches_the_fixture(tag, unaligned):
+    """Bitwise the reference's two q_sample results and their lerp, on the 16-byte path and (base pointers offset by
+    4 bytes) on the scalar path."""
+    from diffsplitting_amd import engine
+    g = load_golden("interpolate_ddpm")
+    bufs, _ = engine.gaussian_buffers(SCHED)
+    t, lam = int(g["t_" + tag]), float(g["lam_" + tag])
+    tb = torch.full((2,), t, dtype=torch.long)
+    a0, s0 = bufs["sqrt_alphas_cumprod"].gather(-1, tb).cuda(), bufs["sqrt_one_minus_alphas_cumprod"].gather(-1, tb).cuda()
+    put = _off if unaligned else (lambda v: v.cuda())
+    x1, x2, z1, z2 = (put(_t(g, k)) for k in ("x1", "x2", "noise1_" + tag, "noise2_" + tag))
+    for x, z, want in ((x1, z1, "xt1_"), (x2, z2, "xt2_")):
+        assert _bit_equal(engine.q_sample(x, a0, s0, z=z)[0], _t(g, want + tag))
+    out = engine.interp_start(x1, x2, a0, s0, lam, z1=z1, z2=z2)
+    assert _bit_equal(out, _t(g, "start_" + tag))
+    # lam = 0 and 1 give the two q_sample results themselves (1 * q + 0 * q')
+    assert torch.equal(engine.interp_start(x1, x2, a0, s0, 0.0, z1=z1, z2=z2).cpu(), _t(g, "xt1_" + tag))
+    assert torch.equal(engine.interp_start(x1, x2, a0, s0, 1.0, z1=z1, z2=z2).cpu(), _t(g, "xt2_" + tag))
+
+
+@pytest.mark.parametrize("shape", [(2, 2, 8, 8), (3, 2, 5, 7)])
+def test_interp_start_philox_subsequences(shape):
+    from diffsplitting_amd import engine
+    from diffsplitting_amd._lib import DsxError
+    B = shape[0]
+    x1, x2 = _rand(shape, 12).cuda(), _rand(shape, 13).cuda()
+    a0, s0 = COEF["c1"][:B].cuda(), COEF["c2"][:B].cuda()
+    out = engine.interp_start(x1, x2, a0, s0, 0.3, seed=99, subsequence=4)
+    inj = engine.interp_start(x1, x2, a0, s0, 0.3, z1=engine.randn(shape, 99, 4), z2=engine.randn(shape, 99, 5))
+    assert _bit_equal(out, inj)
+    assert not _bit_equal(engine.interp_start(x1, x2, a0, s0, 0.3, seed=99, subsequence=5), out)
+    with pytest.raises(DsxError):
+        engine.interp_start(x1, x2, a0, s0, 0.3, z1=x1)
+
+
+# ----------------------------------------------------------------------------- through the UNet, against the fixtures
+def _unet(flavour, cfg):
+    from diffsplitting_amd.model.ddpm_modules.unet import UNet as UNetDdpm
+    from diffsplitting_amd.model.sr3_modules.unet import UNet as UNetSr3
+    cls = UNetSr3 if flavour == "sr3" else UNetDdpm
+    return cls(in_channel=cfg["in_channel"], out_channel=cfg["out_channel"], inner_channel=cfg["inner_channel"],
+               norm_groups=cfg["norm_groups"], channel_mults=cfg["channel_mults"], attn_res=cfg["attn_res"],
+               res_blocks=cfg["res_blocks"], image_size=cfg["image_size"])
+
+
+def _load(smp, sd):
+    missing, unexpected = smp.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()}, strict=False)
+    assert not unexpected and all(not k.startswith("denoise_fn") for k in missing), missing
+
+
+class Source:
+    """A noise_source that hands out the given draws in order and records the shapes asked for."""
+
+    def __init__(self, draws=()):
+        self.draws, self.shapes = list(draws), []
+
+    def __call__(self, shape):
+        self.shapes.append(tuple(shape))
+        return self.draws.pop(0) if self.draws else torch.zeros(shape)
+
+
+def _sr3(fixture):
+    from diffsplitting_amd.model.samplers import GaussianSampler
+    sd, g = golden_state_dict(fixture)
+    net = _unet("sr3", cases.UNET_CASES["sr3_tiny"]["cfg"])
+    smp = GaussianSampler(net, 32, channels=3, conditional=True).cuda()
+    smp.set_new_noise_schedule(SCHED, "cuda")
+    _load(smp, sd)
+    return smp, net, g
+
+
+def _ddpm(fixture, cfg, channels, conditional):
+    from diffsplitting_amd.model.samplers import GaussianSamplerDdpm
+    sd, g = golden_state_dict(fixture)
+    net = _unet("ddpm", cfg)
+    smp = GaussianSamplerDdpm(net, 32, channels=channels, conditional=conditional).cuda()
+    smp.set_new_noise_schedule(SCHED, "cuda")
+    _load(smp, sd)
+    return smp, net, g
+
+
+def _indi(fixture, n):
+    from diffsplitting_amd.model.samplers import InDISampler
+    sd, g = golden_state_dict(fixture)
+    net = _unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"])
+    smp = InDISampler(net, 32, channels=2, out_channel=2, conditional=False, val_schedule_opt={"n_timestep": n}).cuda()
+    smp.set_new_noise_schedule({"n_timestep": n}, "cuda")
+    _load(smp, sd)
+    return smp, net, g
+
+
+def _within(name, got, ref, tol=FP32_TOL):
+    err = maxabs(got.cpu(), ref)
+    print(f"\n{name}: max|hip - reference| = {err:.3e} (allowed {tol:.3e})")
+    assert err <= tol, (name, err)
+
+
+def test_sr3_steps_match_the_reference():
+    smp, net, g = _sr3("steps_sr3")
+    rec = {}
+    net.register_forward_hook(lambda m, inp, out: rec.update(net=out))
+    x, cond = _t(g, "x").cuda(), _t(g, "condition").cuda()
+    for t in (7, 3, 0):
+        for clip in (1, 0):
+            tag = f"_t{t}_clip{clip}"
+            mean, logvar = smp.p_mean_variance(x, t, bool(clip), condition_x=cond)
+            _within("sr3 model_mean" + tag, mean, g["model_mean" + tag])
+            assert logvar.shape == () and _bit_equal(logvar, smp.posterior_log_variance_clipped[t])
+            assert _bit_equal(logvar, _t(g, f"log_variance_t{t}"))
+            src = smp.noise_source = Source([_t(g, f"noise_t{t}")])
+            _within("sr3 p_sample" + tag, smp.p_sample(x, t, clip_denoised=bool(clip), condition_x=cond), g["sample" + tag])
+            assert src.shapes == ([tuple(x.shape)] if t > 0 else [])          # one draw per call, none at t == 0
+            smp.noise_source = None
+        _within(f"sr3 UNet output t{t}", rec["net"], g[f"net_t{t}"])
+        scale = max(1.0, float(smp.sqrt_recipm1_alphas_cumprod[t]))            # x_recon = a x - b net: b times the net's error
+        _within(f"sr3 x_recon t{t}", smp.predict_start_from_noise(x, t, rec["net"]), g[f"x_recon_t{t}_clip0"], FP32_TOL * scale)
+        # on the fixture's own UNet output the two kernels' expressions are the reference's bit for bit
+        assert _bit_equal(smp.predict_start_from_noise(x, t, _t(g, f"net_t{t}").cuda()), _t(g, f"x_recon_t{t}_clip0"))
+        for clip in (1, 0):
+            m, lv = smp.q_posterior(_t(g, f"x_recon_t{t}_clip{clip}").cuda(), x, t)
+            assert _bit_equal(m, _t(g, f"model_mean_t{t}_clip{clip}")) and _bit_equal(lv, logvar)
+    # device noise: repeatable under torch's seed, another seed gives another sample
+    outs = []
+    for seed in (1, 1, 2):
+        torch.manual_seed(seed)
+        outs.append(smp.p_sample(x, 7, condition_x=cond))
+    assert _bit_equal(outs[0], outs[1]) and not _bit_equal(outs[0], outs[2])
+
+
+@pytest.mark.parametrize("tag", ["mixed", "repeat"])
+def test_ddpm_steps_match_the_reference(tag):
+    smp, net, g = _ddpm("steps_ddpm", cases.DDPM_COND_CASE["cfg"], 1, True)
+    x, cond, t = _t(g, "x").cuda(), _t(g, "condition").cuda(), _t(g, "t_" + tag).cuda()
+    repeat = tag == "repeat"
+    mean, var, logvar = smp.p_mean_variance(x, t, True, condition_x=cond)
+    _within(f"ddpm {tag} model_mean", mean, g["model_mean_" + tag])
+    assert var.shape == logvar.shape == (2, 1, 1, 1)
+    assert _bit_equal(var, _t(g, "variance_" + tag)) and _bit_equal(logvar, _t(g, "log_variance_" + tag))
+    assert _bit_equal(var.reshape(-1), smp.posterior_variance[t])
+    assert _bit_equal(logvar.reshape(-1), smp.posterior_log_variance_clipped[t])
+    src = smp.noise_source = Source([_t(g, "noise_" + tag)])
+    out = smp.p_sample(x, t, clip_denoised=True, repeat_noise=repeat, condition_x=cond)
+    _within(f"ddpm {tag} p_sample", out, g["sample_" + tag])
+    assert src.shapes == [(1, 1, 32, 32) if repeat else (2, 1, 32, 32)]
+    if not repeat:                                                             # the sample at t == 0 is its model_mean
+        assert int(t[1]) == 0 and _bit_equal(out[1], mean[1])
+    # drawn on every call, t == 0 included
+    src = smp.noise_source = Source()
+    smp.p_sample(x, torch.zeros(2, dtype=torch.long, device="cuda"), condition_x=cond)
+    assert src.shapes == [(2, 1, 32, 32)]
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_indi_one_step_matches_the_reference(tag):
+    smp, net, g = _indi("steps_indi", 4)
+    x = _t(g, "x").cuda()
+    src = smp.noise_source = Source([_t(g, "noise_" + tag)])
+    out = smp.inference_one_step(x, float(g["delta_" + tag]), float(g["t_cur_" + tag]))
+    _within(f"indi one step {tag}", out, g["sample_" + tag])
+    assert src.shapes == [tuple(x.shape)]
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_interpolate_matches_the_reference(tag):
+    smp, net, g = _ddpm("interpolate_ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"], 2, False)
+    t, lam = int(g["t_" + tag]), float(g["lam_" + tag])
+    draws = [_t(g, "noise1_" + tag), _t(g, "noise2_" + tag)] + list(_t(g, "step_noise_" + tag))
+    src = smp.noise_source = Source(draws)
+    x1, x2 = _t(g, "x1").cuda(), _t(g, "x2").cuda()
+    out = smp.interpolate(x1, x2, t=None if tag == "b" else t, lam=lam)
+    assert out.shape == x1.shape                                               # the whole batch
+    _within(f"interpolate {tag}", out, g["result_" + tag])
+    assert src.shapes == [tuple(x1.shape)] * (2 + t) and not src.draws
+    # device noise: repeatable under torch's seed
+    smp.noise_source = None
+    outs = []
+    for seed in (3, 3, 4):
+        torch.manual_seed(seed)
+        outs.append(smp.interpolate(x1, x2, t=t, lam=lam))
+    assert _bit_equal(outs[0], outs[1]) and not _bit_equal(outs[0], outs[2])
+    assert bool(torch.isfinite(outs[0]).all())
+
+
+# ----------------------------------------------------------------------------- chaining, against the reference's loops
+def test_eight_p_sample_calls_reproduce_the_reference_loop():
+    smp, net, g = _sr3("loop_sr3_lin_8")
+    cond = cases.make_cond("sr3_loop").cuda()
+    torch.manual_seed(cases.LOOP_SEED)
+    draws = [torch.randn(2, 3, 32, 32) for _ in range(8)]                     # init + T - 1 steps, reference draw order
+    src = smp.noise_source = Source(draws[1:])
+    img = draws[0].cuda()
+    for i in reversed(range(8)):
+        img = smp.p_sample(img, i, condition_x=cond)
+    assert len(src.shapes) == 7 and not src.draws
+    _within("sr3 chained p_sample vs loop_sr3_lin_8", img, g["ret"][-2:])
+    assert maxabs(img[-1].cpu(), g["last"]) <= FP32_TOL
+
+
+def test_inference_one_step_calls_reproduce_the_reference_loop():
+    n = 3
+    smp, net, g = _indi(f"loop_indi_n{n}_t1.0", n)
+    x_in = cases.make_cond("indi_loop")
+    torch.manual_seed(cases.LOOP_SEED)
+    draws = [torch.randn(3, 2, 32, 48) for _ in range(n + 1)]
+    src = smp.noise_source = Source(draws[1:])
+    x = (torch.cat([x_in] * 2, dim=1) + draws[0] * (0.01 * torch.Tensor([1.0]))).cuda()    # indi.py:80-82
+    delta, cur = 1.0 / n, 1.0
+    for _ in range(smp.num_timesteps):
+        x = smp.inference_one_step(x, delta, cur)
+        cur -= delta
+    assert len(src.shapes) == n
+    _within(f"indi chained inference_one_step vs loop_indi_n{n}_t1.0", x, g["ret"][-3:])
