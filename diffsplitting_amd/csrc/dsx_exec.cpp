@@ -350,18 +350,24 @@ extern "C" int dsx_randn(float* out, int64_t n, uint64_t seed, uint64_t subseq, 
   return DSX_OK;
 }
 
-// ---- the forward half of the training objective: the noising step and the loss reduction (dsx_objective.hip)
+// ---- the pointwise sampler kernels (dsx_steps.hip) and the loss reduction (dsx_objective.hip)
+static int steps_shape(const char* what, int B, int C, int H, int W) {
+  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(DSX_ERR_INVALID, "%s: empty shape (%d, %d, %d, %d)", what, B, C, H, W);
+  if ((int64_t)H * W > INT32_MAX || (int64_t)B * C * H * W > ((int64_t)1 << 40))
+    return fail(DSX_ERR_INVALID, "%s: tensor too large", what);
+  return DSX_OK;
+}
 extern "C" int dsx_q_sample(const float* x0, const float* xe, int B, int C, int Ce, int H, int W, const float* c0,
                             const float* c1, const float* c2, const float* z, uint64_t seed, uint64_t subseq,
                             float* z_out, float* dst, int Cdst, int coff, void* stream) {
-  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(DSX_ERR_INVALID, "q_sample: empty shape (%d, %d, %d, %d)", B, C, H, W);
+  int rc = steps_shape("q_sample", B, C, H, W);
+  if (rc) return rc;
   if (xe && (Ce < 1 || C % Ce != 0))
     return fail(DSX_ERR_INVALID, "q_sample: x_end has %d channels, x_start %d: C %% Ce != 0", Ce, C);
   if (coff < 0 || (int64_t)coff + C > Cdst)
     return fail(DSX_ERR_INVALID, "q_sample: channels %d..%d do not fit a destination of %d (coff + C > Cdst)", coff,
                 coff + C, Cdst);
-  if ((int64_t)H * W > INT32_MAX || (int64_t)B * Cdst * H * W > ((int64_t)1 << 40))
-    return fail(DSX_ERR_INVALID, "q_sample: tensor too large");
+  if ((rc = steps_shape("q_sample", B, Cdst, H, W))) return rc;    // the destination may be the wider tensor
   if (!x0 || !c0 || !c2 || !dst || (xe && !c1)) return fail(DSX_ERR_INVALID, "q_sample: null argument");
   QSampleArgs a{x0, xe, c0, c1, c2, z, seed, subseq, z ? nullptr : z_out, dst, B, C, xe ? Ce : 1, H * W, Cdst, coff};
   HIP_TRY(launch_q_sample(a, (hipStream_t)stream));
@@ -382,13 +388,7 @@ extern "C" int dsx_loss(const float* a, const float* b, int B, int C, int H, int
   return DSX_OK;
 }
 
-// ---- caller-driven reverse sampling: one update with its intermediates, the start of interpolate (dsx_steps.hip)
-static int steps_shape(const char* what, int B, int C, int H, int W) {
-  if (B < 1 || C < 1 || H < 1 || W < 1) return fail(DSX_ERR_INVALID, "%s: empty shape (%d, %d, %d, %d)", what, B, C, H, W);
-  if ((int64_t)H * W > INT32_MAX || (int64_t)B * C * H * W > ((int64_t)1 << 40))
-    return fail(DSX_ERR_INVALID, "%s: tensor too large", what);
-  return DSX_OK;
-}
+// ---- caller-driven reverse sampling: one update with its intermediates, the start of interpolate
 extern "C" int dsx_posterior_step(const float* x, const float* net, int B, int C, int H, int W, const float* a,
                                   const float* b, const float* c1, const float* c2, const float* sigma,
                                   int predict_eps, int clip, const float* z, uint64_t seed, uint64_t subseq,

@@ -402,6 +402,11 @@ hipError_t launch_update(const UpdateArgs& a, hipStream_t st);
 hipError_t launch_advance(int* step_ctr, hipStream_t st);
 hipError_t launch_randn(float* out, long long n, unsigned long long seed, unsigned long long subseq,
                         hipStream_t st);
+// grid of a 256-thread grid-stride launch over `total` items
+static inline unsigned grid_for(long long total) {
+  long long g = (total + 255) / 256;
+  return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
+}
 #if defined(__HIPCC__)
 // One IEEE operation each, never contracted into an fma: the pragma takes the `contract` flag off the instruction, and
 // the backend fuses a product into a sum only when both carry it.
@@ -413,6 +418,10 @@ __device__ __forceinline__ float add_f(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
 }
+__device__ __forceinline__ float sub_f(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 __device__ __forceinline__ double mul_d(double a, double b) {
 #pragma clang fp contract(off)
   return a * b;
@@ -422,8 +431,28 @@ __device__ __forceinline__ double add_d(double a, double b) {
   return a + b;
 }
 
+// The reverse update of every sampler (sr3 diffusion.py:141-175, ddpm diffusion.py:163-203, indi.py:62-69), stated once
+// for the loop (k_update, dsx_ops.hip) and the single steps (k_posterior_step, dsx_steps.hip); every product and sum
+// is rounded on its own, as the reference's ATen op sequence does:
+//   x0   = predict_eps ? clamp(a*x - b*net) : net          (the clamp to +-1 only with clip)
+//   mean = c1*x0 + c2*x
+//   out  = use_z ? mean + z*sigma : mean
+struct StepVals { float x0, mean, out; };
+__device__ __forceinline__ StepVals step_update(float a, float b, float c1, float c2, float sigma, bool predict_eps,
+                                                bool clip, float x, float net, float z, bool use_z) {
+  StepVals v;
+  v.x0 = net;
+  if (predict_eps) {
+    v.x0 = sub_f(mul_f(a, x), mul_f(b, net));
+    if (clip) v.x0 = fminf(fmaxf(v.x0, -1.0f), 1.0f);
+  }
+  v.mean = add_f(mul_f(c1, v.x0), mul_f(c2, x));
+  v.out = use_z ? add_f(v.mean, mul_f(z, sigma)) : v.mean;
+  return v;
+}
+
 // The engine's normal stream: element i of the stream (seed, subseq) is component i % 4 of normal4(seed, subseq, i / 4).
-// Shared by k_randn, k_update (dsx_ops.hip) and k_q_sample (dsx_objective.hip), which must agree bitwise.
+// Shared by k_randn, k_update (dsx_ops.hip) and the pointwise kernels of dsx_steps.hip, which must agree bitwise.
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
                                               unsigned k0, unsigned k1, unsigned out[4]) {
 #pragma unroll
@@ -457,7 +486,7 @@ __device__ __forceinline__ void normal4(unsigned long long seed, unsigned long l
 }
 #endif
 
-// dsx_objective.hip.  q_sample of the three sampler families in one launch (NCHW fp32):
+// dsx_steps.hip.  q_sample of the three sampler families in one launch (NCHW fp32):
 //   dst[b][coff + c] = c0[b] * x0[b][c] (+ c1[b] * xe[b][c % Ce]) + c2[b] * z[b][c],  each operation rounded on its own.
 // xe == nullptr: the two-term (Gaussian) form.  z == nullptr: z is element i of the normal stream (seed, subseq) at
 // the flat (B, C, H, W) index i (what launch_randn writes) and is stored to z_out when that is not nullptr.
@@ -469,13 +498,13 @@ struct QSampleArgs {
   int B, C, Ce, HW, Cdst, coff;
 };
 hipError_t launch_q_sample(const QSampleArgs& a, hipStream_t st);
-// per-sample sum |a - b| (squared == 0) or sum (a - b)^2 over n elements, in double: part[B][loss_blocks(n)] partials
+// dsx_objective.hip.  per-sample sum |a - b| (squared == 0) or sum (a - b)^2 over n elements, in double: part[B][loss_blocks(n)] partials
 // in a fixed partition, out[B] their sums in a fixed order (two launches, no atomics)
 int loss_blocks(long long n);
 hipError_t launch_loss(const float* a, const float* b, int B, long long n, int squared, double* part, double* out,
                        hipStream_t st);
 
-// dsx_steps.hip.  One reverse update with its intermediates (NCHW fp32, per-sample coefficients, B values each):
+// One reverse update with its intermediates (NCHW fp32, per-sample coefficients, B values each):
 //   x0 = predict_eps ? clamp(a*x - b*net) : net;  mean = c1*x0 + c2*x;  out = mean + z*sigma (mean where sigma == 0)
 // z == nullptr: element i of the normal stream (seed, subseq); repeat: every sample uses sample 0's draw (z then holds
 // C*H*W values).  Outputs that are nullptr are not written.

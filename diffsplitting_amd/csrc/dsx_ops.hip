@@ -327,10 +327,6 @@ __global__ void k_nhwc_to_nchw(const float* __restrict__ src, float* __restrict_
     dst[i] = src[(b * HW + hw) * C + c];
   }
 }
-static unsigned grid_for(long long total) {
-  long long g = (total + 255) / 256;
-  return (unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g));
-}
 hipError_t launch_nchw_slice_to_nhwc(const float* src, void* dst, int dst_bf16, int B, int C, int ctot, int coff,
                                      int HW, hipStream_t st) {
   const long long total = (long long)B * C * HW;
@@ -347,7 +343,7 @@ hipError_t launch_nhwc_to_nchw(const float* src, float* dst, int B, int C, int H
 // Philox4x32-10 + Box-Muller (device noise for the perf path; the parity path
 // injects host-drawn noise instead, SURVEY §7 "Parity over 2000 steps")
 // ---------------------------------------------------------------------------
-// (philox4x32_10 and normal4 live in dsx_kernels.h: dsx_objective.hip draws from the same stream)
+// (philox4x32_10 and normal4 live in dsx_kernels.h: dsx_steps.hip draws from the same stream)
 __global__ void k_randn(float* __restrict__ out, long long n, unsigned long long seed,
                         unsigned long long subseq) {
   const long long n4 = (n + 3) / 4;
@@ -367,8 +363,8 @@ hipError_t launch_randn(float* out, long long n, unsigned long long seed, unsign
 
 // ---------------------------------------------------------------------------
 // Sampler update (sr3 diffusion.py:141-175 / ddpm diffusion.py:194-203 /
-// indi.py:62-69).  Every product and sum is rounded on its own (__fmul_rn /
-// __fadd_rn: no FMA contraction) to follow the reference's ATen op sequence.
+// indi.py:62-69): step_update (dsx_kernels.h), the arithmetic k_posterior_step
+// shares, so the loop and the single steps round alike.
 // The step index lives in device memory so one captured graph replays T times.
 // ---------------------------------------------------------------------------
 __global__ void k_update(const UpdateArgs a) {
@@ -404,14 +400,7 @@ __global__ void k_update(const UpdateArgs a) {
         ca = a.tab[1 * (size_t)T + k]; cb = a.tab[2 * (size_t)T + k];
         c1 = a.tab[3 * (size_t)T + k]; c2 = a.tab[4 * (size_t)T + k]; sg = a.tab[5 * (size_t)T + k];
       }
-      const float x = a.x[i];
-      float o = a.net[i];
-      if (a.predict_eps) {
-        o = __fsub_rn(__fmul_rn(ca, x), __fmul_rn(cb, o));
-        if (a.clip) o = fminf(fmaxf(o, -1.0f), 1.0f);
-      }
-      const float mean = __fadd_rn(__fmul_rn(c1, o), __fmul_rn(c2, x));
-      const float xn = __fadd_rn(mean, __fmul_rn(zz, sg));
+      const float xn = step_update(ca, cb, c1, c2, sg, a.predict_eps, a.clip, a.x[i], a.net[i], zz, true).out;
       a.x[i] = xn;
       if (a.x_act) store1_act(a.x_act, (size_t)i, xn, a.x_act_kind);
     }

@@ -544,27 +544,40 @@ def _f32_cuda(t, what, shape=None):
     return t.detach()
 
 
+def _bchw(t, what):
+    """``t`` as a contiguous float32 CUDA tensor and its dimensions (B, C, H, W)."""
+    t = _f32_cuda(t, what)
+    if t.dim() != 4:
+        raise DsxError(f"{what} must be (B, C, H, W), got {tuple(t.shape)}")
+    return (t,) + tuple(t.shape)
+
+
+def _coef(c, what, B, named=True):
+    c = _f32_cuda(c, what).reshape(-1)
+    if c.numel() != B:
+        raise DsxError(f"{what if named else 'per-sample coefficients'} must hold B = {B} values, got {c.numel()}")
+    return c
+
+
+def _seed64(seed):
+    return C.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
 def q_sample(x0, c0, c2, xe=None, c1=None, z=None, seed=0, subsequence=0, dst=None, coff=0, want_z=False):
     """``dsx_q_sample``: ``dst[:, coff:coff + C] = c0*x0 (+ c1*xe) + c2*z`` in one launch, every operation rounded on
     its own.  ``c0`` / ``c1`` / ``c2``: (B,) per-sample coefficients; ``xe`` (B, Ce, H, W) is read at channel
     ``c % Ce``; ``z`` None draws the Philox normals of ``randn(x0.shape, seed, subsequence)``.  Returns
     ``(dst, z)``: ``dst`` is a new (B, C, H, W) tensor unless given, ``z`` the normals used (the injected tensor, the
     drawn ones when ``want_z``, else None).  Every tensor must be contiguous float32 on the device."""
-    x0 = _f32_cuda(x0, "x_start")
-    if x0.dim() != 4:
-        raise DsxError(f"x_start must be (B, C, H, W), got {tuple(x0.shape)}")
-    B, Cn, H, W = x0.shape
-    coef = lambda c, what: _f32_cuda(c, what).reshape(-1)
-    c0, c2 = coef(c0, "c0"), coef(c2, "c2")
+    x0, B, Cn, H, W = _bchw(x0, "x_start")
     Ce = 1
     if xe is not None:
-        xe, c1 = _f32_cuda(xe, "x_end"), coef(c1, "c1")
+        xe = _f32_cuda(xe, "x_end")
         if xe.dim() != 4 or xe.shape[0] != B or tuple(xe.shape[2:]) != (H, W):
             raise DsxError(f"x_end must be ({B}, Ce, {H}, {W}), got {tuple(xe.shape)}")
         Ce = xe.shape[1]
-    for c in (c0, c1, c2):
-        if c is not None and c.numel() != B:
-            raise DsxError(f"per-sample coefficients must hold B = {B} values, got {c.numel()}")
+    c0, c1, c2 = (None if c is None else _coef(c, what, B, named=False)
+                  for c, what in ((c0, "c0"), (c1 if xe is not None else None, "c1"), (c2, "c2")))
     z_out = None
     if z is not None:
         z = _f32_cuda(z, "noise", x0.shape)
@@ -576,8 +589,8 @@ def q_sample(x0, c0, c2, xe=None, c1=None, z=None, seed=0, subsequence=0, dst=No
               and dst.shape[0] == B and tuple(dst.shape[2:]) == (H, W)):
         raise DsxError(f"dst must be a contiguous float32 CUDA tensor ({B}, Cdst, {H}, {W})")
     check(lib.dsx_q_sample(_dptr(x0), _dptr(xe), B, Cn, Ce, H, W, _dptr(c0), _dptr(c1), _dptr(c2), _dptr(z),
-                           C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(subsequence)), _dptr(z_out),
-                           _dptr(dst), dst.shape[1], int(coff), _stream_ptr()))
+                           _seed64(seed), C.c_uint64(int(subsequence)), _dptr(z_out), _dptr(dst), dst.shape[1],
+                           int(coff), _stream_ptr()))
     return dst, (z if z is not None else z_out)
 
 
@@ -599,23 +612,13 @@ def loss_per_sample(a, b, squared):
 # ---------------------------------------------------------------------------
 # caller-driven reverse sampling (dsx_posterior_step / dsx_interp_start, include/dsx.h)
 # ---------------------------------------------------------------------------
-def _coef(c, what, B):
-    c = _f32_cuda(c, what).reshape(-1)
-    if c.numel() != B:
-        raise DsxError(f"{what} must hold B = {B} values, got {c.numel()}")
-    return c
-
-
 def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, clip=False, z=None, seed=0, subsequence=0,
                    repeat_noise=False, x_recon_out=None, mean_out=None, x_out=None):
     """``dsx_posterior_step``: one reverse update with its intermediates in one launch.  ``a`` .. ``sigma``: (B,)
     per-sample coefficients; ``z`` (B, C, H, W) -- (1, C, H, W) under ``repeat_noise`` -- or None for the Philox normals
     of ``randn(x.shape, seed, subsequence)``.  Only the outputs given are written (``x_out`` may be ``x``); every
     tensor must be contiguous float32 on the device.  Returns ``(x_recon_out, mean_out, x_out)``."""
-    x = _f32_cuda(x, "x")
-    if x.dim() != 4:
-        raise DsxError(f"x must be (B, C, H, W), got {tuple(x.shape)}")
-    B, Cn, H, W = x.shape
+    x, B, Cn, H, W = _bchw(x, "x")
     net = _f32_cuda(net, "net", x.shape)
     c1, c2, sigma = _coef(c1, "c1", B), _coef(c2, "c2", B), _coef(sigma, "sigma", B)
     if predict_eps:
@@ -629,10 +632,9 @@ def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, cli
     outs = [None if o is None else _f32_cuda(o, what, x.shape)
             for o, what in ((x_recon_out, "x_recon_out"), (mean_out, "mean_out"), (x_out, "x_out"))]
     check(lib.dsx_posterior_step(_dptr(x), _dptr(net), B, Cn, H, W, _dptr(a), _dptr(b), _dptr(c1), _dptr(c2),
-                                 _dptr(sigma), 1 if predict_eps else 0, 1 if clip else 0, _dptr(z),
-                                 C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(subsequence)),
-                                 1 if repeat_noise else 0, _dptr(outs[0]), _dptr(outs[1]), _dptr(outs[2]),
-                                 _stream_ptr()))
+                                 _dptr(sigma), 1 if predict_eps else 0, 1 if clip else 0, _dptr(z), _seed64(seed),
+                                 C.c_uint64(int(subsequence)), 1 if repeat_noise else 0, _dptr(outs[0]),
+                                 _dptr(outs[1]), _dptr(outs[2]), _stream_ptr()))
     return tuple(outs)
 
 
@@ -641,10 +643,7 @@ def interp_start(x1, x2, a0, s0, lam, z1=None, z2=None, seed=0, subsequence=0, o
     coefficients of q_sample.  ``1 - lam`` is formed in double and each scalar rounded to fp32 once, as torch does for
     a python scalar against an fp32 tensor.  ``z1`` / ``z2``: both injected, or both None for the Philox normals of
     ``randn(shape, seed, subsequence)`` and ``randn(shape, seed, subsequence + 1)``."""
-    x1 = _f32_cuda(x1, "x1")
-    if x1.dim() != 4:
-        raise DsxError(f"x1 must be (B, C, H, W), got {tuple(x1.shape)}")
-    B, Cn, H, W = x1.shape
+    x1, B, Cn, H, W = _bchw(x1, "x1")
     x2 = _f32_cuda(x2, "x2", x1.shape)
     a0, s0 = _coef(a0, "a0", B), _coef(s0, "s0", B)
     if (z1 is None) != (z2 is None):
@@ -653,6 +652,6 @@ def interp_start(x1, x2, a0, s0, lam, z1=None, z2=None, seed=0, subsequence=0, o
         z1, z2 = _f32_cuda(z1, "z1", x1.shape), _f32_cuda(z2, "z2", x1.shape)
     out = torch.empty_like(x1) if out is None else _f32_cuda(out, "out", x1.shape)
     check(lib.dsx_interp_start(_dptr(x1), _dptr(x2), B, Cn, H, W, _dptr(a0), _dptr(s0), C.c_float(1 - float(lam)),
-                               C.c_float(float(lam)), _dptr(z1), _dptr(z2), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                               C.c_float(float(lam)), _dptr(z1), _dptr(z2), _seed64(seed),
                                C.c_uint64(int(subsequence)), _dptr(out), _stream_ptr()))
     return out

@@ -47,10 +47,11 @@ class _SamplerBase(nn.Module):
 
     # ---- the objective's forward half (dsx_q_sample / dsx_loss) ---------------------------
     @staticmethod
-    def _need_cuda(*tensors):
+    def _need_cuda(*tensors, what=None):
         for t in tensors:
             if not t.is_cuda:
-                raise DsxError("the objective runs on the MI355X only; pass CUDA tensors (no CPU fallback)")
+                raise DsxError("the objective runs on the MI355X only; pass CUDA tensors (no CPU fallback)" if what is None
+                               else f"{what} runs on the MI355X only; pass a CUDA tensor (no CPU fallback)")
 
     def _set_loss(self, device, reduction):
         if self.loss_type not in ("l1", "l2"):
@@ -80,32 +81,40 @@ class _SamplerBase(nn.Module):
             return noise.to(device=device, dtype=torch.float32).contiguous(), 0
         return None, self._seed()
 
-    def _q_sample(self, x_start, coef, noise, x_end=None):
-        """The public q_sample of the three families: tensors are brought to contiguous float32 here (a copy only when
-        the caller's are not), the coefficients moved to the device, then one dsx_q_sample launch."""
+    def _q_args(self, x_start, coef, noise):
+        """What engine.q_sample takes: x_start as contiguous float32 (a copy only when the caller's is not), the
+        coefficients (c0, c1, c2) on the device, and the draws (z, seed)."""
         dev = x_start.device
         x_start = x_start.float().contiguous()
-        c0, c1, c2 = (None if c is None else c.to(dev).contiguous() for c in coef)
         z, seed = self._noise_or_seed(noise, x_start.shape, dev)
+        c0, c1, c2 = (None if c is None else c.to(dev).contiguous() for c in coef)
+        return x_start, c0, c2, dict(c1=c1, z=z, seed=seed)
+
+    def _q_sample(self, x_start, coef, noise, x_end=None):
+        """The public q_sample of the three families: one dsx_q_sample launch."""
+        x_start, c0, c2, kw = self._q_args(x_start, coef, noise)
         xe = None if x_end is None else x_end.float().contiguous()
-        return engine.q_sample(x_start, c0, c2, xe=xe, c1=c1, z=z, seed=seed)[0]
+        return engine.q_sample(x_start, c0, c2, xe=xe, **kw)[0]
+
+    @staticmethod
+    def _unet_input(cond, x):
+        """The buffer of cat([cond, x], 1) with ``cond`` written and x's channels left to the caller, and where those
+        begin; (None, 0) without a condition."""
+        if cond is None:
+            return None, 0
+        cc = cond.shape[1]
+        inp = torch.empty((x.shape[0], cc + x.shape[1]) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        inp[:, :cc] = cond
+        return inp, cc
 
     def _noised_forward(self, x_start, coef, time, noise, cond=None, xe=None, want_noise=True):
         """x_noisy = q_sample(x_start) written straight into the UNet's input (behind ``cond``'s channels when the
         model is conditional), then the UNet forward.  ``coef`` = (c0, c1, c2), (B,) each (c1 None: two terms).
         Returns (x_recon, the normals used or None)."""
-        dev = x_start.device
-        x_start = x_start.float().contiguous()
-        B, Cn, H, W = x_start.shape
-        z, seed = self._noise_or_seed(noise, x_start.shape, dev)
-        c0, c1, c2 = (None if c is None else c.to(dev).contiguous() for c in coef)
-        inp, coff = None, 0
-        if cond is not None:
-            coff = cond.shape[1]
-            inp = torch.empty((B, coff + Cn, H, W), dtype=torch.float32, device=dev)
-            inp[:, :coff] = cond                                     # cat([input, x_noisy], 1): x_noisy by the kernel
-        inp, z = engine.q_sample(x_start, c0, c2, xe=xe, c1=c1, z=z, seed=seed, dst=inp, coff=coff, want_z=want_noise)
-        return self.denoise_fn(inp, time.to(dev)), z
+        x_start, c0, c2, kw = self._q_args(x_start, coef, noise)
+        inp, coff = self._unet_input(cond, x_start)
+        inp, z = engine.q_sample(x_start, c0, c2, xe=xe, dst=inp, coff=coff, want_z=want_noise, **kw)
+        return self.denoise_fn(inp, time.to(x_start.device)), z
 
     @property
     def prediction_channels(self):
@@ -150,10 +159,13 @@ class GaussianSampler(_SamplerBase):
                                                            self.kind, clip)
         return self._table[clip]
 
-    @torch.no_grad()
-    def p_sample_loop(self, x_in, clip_denoised=True, continous=False):
+    def _need_schedule(self):
         if self.num_timesteps is None:
             raise DsxError("set_new_noise_schedule() first")
+
+    @torch.no_grad()
+    def p_sample_loop(self, x_in, clip_denoised=True, continous=False):
+        self._need_schedule()
         dev = self.betas.device
         T = self.num_timesteps
         if not self.conditional:
@@ -195,25 +207,13 @@ class GaussianSampler(_SamplerBase):
     # ---- caller-driven reverse steps (sr3 diffusion.py:141-175, ddpm diffusion.py:163-203) ------------------
     def _rows(self, t, B, dev):
         """The step-table rows of ``t`` (an integer, or (B,) integers) as (B,) fp32 device tensors per column."""
-        if self.num_timesteps is None:
-            raise DsxError("set_new_noise_schedule() first")
+        self._need_schedule()
         if torch.is_tensor(t):
             t = t.detach().reshape(-1).cpu()
             if t.numel() != B:
                 raise DsxError(f"t must hold B = {B} timesteps, got {t.numel()}")
         rows = engine.gaussian_step_rows(self._bufs_cpu, self.sqrt_alphas_cumprod_prev, self.kind, t)
         return {k: torch.from_numpy(np.ascontiguousarray(np.broadcast_to(v, (B,)))).to(dev) for k, v in rows.items()}
-
-    @staticmethod
-    def _unet_input(x, condition_x):
-        """cat([condition_x, x], 1) written into one buffer, as the objective's noising launch fills it."""
-        if condition_x is None:
-            return x
-        cc = condition_x.shape[1]
-        inp = torch.empty((x.shape[0], cc + x.shape[1]) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        inp[:, :cc] = condition_x
-        inp[:, cc:] = x
-        return inp
 
     def _reverse(self, x, t, clip_denoised, condition_x, want, z=None, seed=0, repeat_noise=False):
         """One UNet forward and one dsx_posterior_step launch: ``want`` = (x_recon, model_mean, sample) flags, the
@@ -223,7 +223,12 @@ class GaussianSampler(_SamplerBase):
         B = x.shape[0]
         r = self._rows(t, B, x.device)
         time = r["tcond"].view(B, 1) if self.kind == "sr3" else r["tcond"]
-        net = self.denoise_fn(self._unet_input(x, condition_x), time)
+        inp, cc = self._unet_input(condition_x, x)
+        if inp is None:
+            inp = x
+        else:
+            inp[:, cc:] = x
+        net = self.denoise_fn(inp, time)
         outs = [torch.empty_like(x) if w else None for w in want]
         return engine.posterior_step(x, net, r["c1"], r["c2"], r["sigma"], a=r["a"], b=r["b"], predict_eps=True,
                                      clip=bool(clip_denoised), z=z, seed=seed, repeat_noise=repeat_noise,
@@ -283,16 +288,20 @@ class GaussianSampler(_SamplerBase):
         """The objective on ``x_in`` = {'target', 'input'}: loss(noise, UNet(q_sample(target))) with eval semantics
         (dropout is identity: the validation objective), no graph.  ``t`` / ``continuous_sqrt_alpha_cumprod``
         override the host draws (a superset of the reference's signature)."""
-        x_start = x_in["target"]
-        self._need_cuda(x_start)
-        b = x_start.shape[0]
+        self._need_cuda(x_in["target"])
+        b = x_in["target"].shape[0]
         c = continuous_sqrt_alpha_cumprod
         if c is None:
             c = self._sample_gamma(b, t)[1]
-        c = c.reshape(b, -1).to(torch.float32)
-        c0, c2 = self.q_coefficients(c)
+        return self._objective(x_in, noise, c.reshape(b, -1).to(torch.float32))
+
+    def _objective(self, x_in, noise, time):
+        """loss(noise, UNet(q_sample(target), time)): ``time`` -- noise levels (sr3) or integer steps (ddpm) -- is what
+        q_coefficients reads and what the UNet is conditioned on."""
+        x_start = x_in["target"]
+        c0, c2 = self.q_coefficients(time)
         cond = x_in["input"].to(x_start.device).float() if self.conditional else None
-        x_recon, z = self._noised_forward(x_start, (c0, None, c2), c, noise, cond=cond)
+        x_recon, z = self._noised_forward(x_start, (c0, None, c2), time, noise, cond=cond)
         return self._loss(z, x_recon)
 
 
@@ -355,8 +364,7 @@ class GaussianSamplerDdpm(GaussianSampler):
             raise DsxError("interpolate: the reference steps without a condition (ddpm diffusion.py:260-262); a "
                            "conditional sampler cannot interpolate")
         self._need_cuda(x1, x2)
-        if self.num_timesteps is None:
-            raise DsxError("set_new_noise_schedule() first")
+        self._need_schedule()
         t = self.num_timesteps - 1 if t is None else int(t)
         assert x1.shape == x2.shape
         if not 0 <= t < self.num_timesteps:
@@ -398,15 +406,10 @@ class GaussianSamplerDdpm(GaussianSampler):
     def p_losses(self, x_in, noise=None, *, t=None):
         """loss(noise, UNet(q_sample(target, t), t)) with eval semantics (the validation objective), no graph.
         ``t`` (B,) integer overrides the host draw."""
-        x_start = x_in["target"]
-        self._need_cuda(x_start)
+        self._need_cuda(x_in["target"])
         if t is None:
-            t = self._sample_t(x_start.shape[0])
-        t = t.reshape(-1).long()
-        c0, c2 = self.q_coefficients(t)
-        cond = x_in["input"].to(x_start.device).float() if self.conditional else None
-        x_recon, z = self._noised_forward(x_start, (c0, None, c2), t, noise, cond=cond)
-        return self._loss(z, x_recon)
+            t = self._sample_t(x_in["target"].shape[0])
+        return self._objective(x_in, noise, t.reshape(-1).long())
 
 
 class InDISampler(_SamplerBase):
@@ -533,8 +536,7 @@ class InDISampler(_SamplerBase):
         dsx_posterior_step launch; the coefficients are one row of ``engine.indi_step_table``.  One draw per call."""
         assert delta_t <= t_cur, "delta_t should be less than or equal to t_cur."
         self._gaussian_noise_mode()
-        if not x_t.is_cuda:
-            raise DsxError("inference_one_step runs on the MI355X only; pass a CUDA tensor (no CPU fallback)")
+        self._need_cuda(x_t, what="inference_one_step")
         dev = x_t.device
         x_t = x_t.float().contiguous()
         B = x_t.shape[0]
@@ -587,6 +589,10 @@ class InDISampler(_SamplerBase):
         scale = torch.stack([(self.e * torch.Tensor([t])) for t in t_list]).to(dev).view(B, 1, 1, 1)
         x_t = xr + d0 * scale
         table = engine.indi_step_table_per_sample(num_timesteps, t_list, self.e)
+        return self._loop(table, x_t, noise, continuous, num_timesteps, stream)
+
+    def _loop(self, table, x_t, noise, continuous, num_timesteps, stream):
+        """The engine's loop from ``x_t`` (updated in place: ``first`` keeps the start) and what inference returns."""
         snaps = engine.indi_snapshot_steps(num_timesteps) if continuous else []
         first = x_t.clone() if continuous else None
         x, sn = self.denoise_fn.engine().sample_loop(table, x_t, noise=noise, seed=self._seed(), snapshot_steps=snaps,
@@ -596,7 +602,7 @@ class InDISampler(_SamplerBase):
             if stream is not None:
                 stream.synchronize()
             return torch.cat([first] + [s for s in sn], dim=0)
-        return x[-1:]
+        return x[-1:]                                                # indi.py:92-95: ret_img[-1:]
 
     def _noise(self, shape, n, dev):
         if self.noise_source is None:
@@ -609,25 +615,14 @@ class InDISampler(_SamplerBase):
         if num_timesteps is None:
             num_timesteps = self.num_timesteps
         assert self.conditional is False
-        if not x_in.is_cuda:
-            raise DsxError("inference runs on the MI355X only; pass a CUDA tensor (no CPU fallback)")
+        self._need_cuda(x_in, what="inference")
         t_list = self._per_sample_t(t_float_start, x_in.shape[0])
         if t_list is not None:
             return self._inference_per_sample(x_in, t_list, continuous, num_timesteps, stream)
         x_t = self._start(x_in, t_float_start)
         noise = self._noise(x_t.shape, num_timesteps, x_t.device)
         table = engine.indi_step_table(num_timesteps, t_float_start, self.e)   # no drift assert (R3)
-        snaps = engine.indi_snapshot_steps(num_timesteps) if continuous else []
-        first = x_t.clone() if continuous else None
-        x, sn = self.denoise_fn.engine().sample_loop(table, x_t, noise=noise, seed=self._seed(),
-                                                     snapshot_steps=snaps, use_graph=self.use_graph,
-                                                     stream=stream)
-        self.last_full_batch = x
-        if continuous:
-            if stream is not None:
-                stream.synchronize()
-            return torch.cat([first] + [s for s in sn], dim=0)
-        return x[-1:]                                                # indi.py:92-95: ret_img[-1:]
+        return self._loop(table, x_t, noise, continuous, num_timesteps, stream)
 
 
 class IndiCustomT(InDISampler):

@@ -373,6 +373,10 @@ def test_eight_p_sample_calls_reproduce_the_reference_loop():
     assert len(src.shapes) == 7 and not src.draws
     _within("sr3 chained p_sample vs loop_sr3_lin_8", img, g["ret"][-2:])
     assert maxabs(img[-1].cpu(), g["last"]) <= FP32_TOL
+    smp.noise_source = Source(draws)
+    smp.p_sample_loop(cond)
+    print(f"sr3 loop vs chained p_sample: max|diff| = {maxabs(smp.last_full_batch.cpu(), img.cpu()):.3e}")
+    assert torch.equal(smp.last_full_batch, img)                               # the loop is the single steps
 
 
 def test_inference_one_step_calls_reproduce_the_reference_loop():
@@ -389,3 +393,74 @@ def test_inference_one_step_calls_reproduce_the_reference_loop():
         cur -= delta
     assert len(src.shapes) == n
     _within(f"indi chained inference_one_step vs loop_indi_n{n}_t1.0", x, g["ret"][-3:])
+    smp.noise_source = Source(draws)
+    smp.inference(x_in.cuda())
+    print(f"indi loop vs chained inference_one_step: max|diff| = {maxabs(smp.last_full_batch.cpu(), x.cpu()):.3e}")
+    assert torch.equal(smp.last_full_batch, x)                                 # the loop is the single steps
+
+
+# ----------------------------------------------------------------------------- the loop's update is the single step's
+# k_update and k_posterior_step share one arithmetic (step_update).  With the final conv's weights zero the UNet returns
+# its bias in every executor, so the loop and the chained single steps can differ in the update alone: equal values
+# (torch.equal: the loop adds z * 0 where the single step adds nothing, a difference in the sign of a zero at most).
+T_EQ = 8
+BIAS = (0.3, -0.45)
+
+
+def _constant_unet(net, B):
+    net.final_conv__block__3__weight.zero_()
+    net.final_conv__block__3__bias.copy_(torch.tensor(BIAS))
+    out = net(_rand((B, 2, 16, 16), 50).cuda(), torch.full((B,), 0.5).cuda())
+    assert torch.equal(out.cpu(), torch.tensor(BIAS).view(1, 2, 1, 1).expand(B, 2, 16, 16))
+
+
+@pytest.mark.parametrize("clip", [True, False])
+def test_ddpm_loop_equals_chained_p_sample_on_a_constant_unet(clip):
+    smp, net, _ = _ddpm("interpolate_ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"], 2, False)
+    shape = (2, 2, 16, 16)
+    _constant_unet(net, 2)
+    draws = [_rand(shape, 100 + i) for i in range(T_EQ + 1)]                  # the start, then one per step
+    smp.noise_source = Source(draws)
+    loop = smp.p_sample_loop(shape, clip_denoised=clip)
+    assert loop.shape == shape and not smp.noise_source.draws
+    src = smp.noise_source = Source(draws[1:])
+    x = draws[0].cuda()
+    for i in reversed(range(T_EQ)):
+        x = smp.p_sample(x, torch.full((2,), i, dtype=torch.long, device="cuda"), clip_denoised=clip)
+    assert not src.draws
+    assert torch.equal(loop, x)
+
+
+@pytest.mark.parametrize("t_start", [1.0, (1.0, 0.5, 0.75)])
+def test_indi_inference_equals_chained_one_steps_on_a_constant_unet(t_start):
+    """One start time, and one per sample (binary fractions: the host's cur_t -= delta never undershoots delta).  The
+    per-sample loop is compared sample by sample: inference_one_step takes one time for its whole batch."""
+    n = T_EQ
+    smp, net, _ = _indi("loop_indi_n3_t1.0", n)
+    _constant_unet(net, 3)
+    x_in = _rand((3, 1, 16, 16), 60)
+    one = (1, 2, 16, 16)
+    per_sample = isinstance(t_start, tuple)
+    if per_sample:                                                             # sample by sample: start, then n steps
+        draws = [[_rand(one, 1000 * b + i) for i in range(n + 1)] for b in range(3)]
+        smp.noise_source = Source([d for per in draws for d in per])
+        smp.inference(x_in.cuda(), t_float_start=torch.tensor(t_start))
+    else:
+        flat = [_rand((3, 2, 16, 16), 300 + i) for i in range(n + 1)]
+        draws = [[d[b:b + 1].contiguous() for d in flat] for b in range(3)]
+        smp.noise_source = Source(flat)
+        smp.inference(x_in.cuda(), t_float_start=t_start)
+    assert not smp.noise_source.draws
+    loop = smp.last_full_batch
+    assert loop.shape == (3, 2, 16, 16)
+    for b in range(3):
+        t0 = t_start[b] if per_sample else t_start
+        src = smp.noise_source = Source(draws[b][1:])
+        xr = torch.cat([x_in[b:b + 1]] * 2, dim=1).cuda()
+        x = xr + draws[b][0].cuda() * (smp.e * torch.Tensor([t0])).cuda()      # indi.py:80-82
+        delta, cur = t0 / n, t0
+        for _ in range(n):
+            x = smp.inference_one_step(x, delta, cur)
+            cur -= delta
+        assert not src.draws
+        assert torch.equal(loop[b:b + 1], x), b
