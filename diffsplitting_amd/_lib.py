@@ -92,6 +92,8 @@ SIGNATURES = {
     "dsx_posterior_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _i, _vp, _vp,
                                 _vp, _vp]),
     "dsx_interp_start": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "dsx_val_report": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.POINTER(C.c_double),
+                            C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsx_tile_plan": (_i64, [_pi64, _pi64, _pi64, _i, _pi64, _pi64, _i64]),
     "dsx_tile_regions": (_i, [_pi64, _pi64, _pi64, _i, _pi32, _i64]),
     "dsx_tiles_gather": (_i, [_vp, _pi64, _pi64, _pi64, _pi64, _i64, _vp, _vp]),

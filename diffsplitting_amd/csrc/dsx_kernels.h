@@ -431,6 +431,60 @@ __device__ __forceinline__ double add_d(double a, double b) {
   return a + b;
 }
 
+// ---------------------------------------------------------------------------
+// The skeleton the NCHW pointwise kernels share (dsx_steps.hip, dsx_validate.hip).  A thread owns group i4: the four consecutive elements from 4 * i4 (= one
+// Philox block of the flat normal stream, where one is drawn).  VEC: H * W is a multiple of 4 and every base pointer is 16-byte aligned, so
+// a group lies inside one (b, c) row and is one 16-byte access in every tensor; otherwise its first `cnt` elements are
+// accessed one by one.  Each body below is written once over the arrays of a group, so both instantiations give the
+// same bits.
+// ---------------------------------------------------------------------------
+// the elements of a group that exist, unrolled: the arrays of a group stay in registers
+#define DSX_EACH4(j, cnt) _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < (cnt))
+// the flat indices of group i4 of n elements; returns how many of them exist
+template <bool VEC>
+__device__ __forceinline__ int group4(long long i4, long long n, long long at[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) at[j] = i4 * 4 + j;
+  return VEC ? 4 : (int)min(4LL, n - i4 * 4);
+}
+// row[j] = at[j] / len: the (b, c) row with len = H*W, the sample with len = C*H*W.  VEC: one division per group.
+template <bool VEC>
+__device__ __forceinline__ void rows4(const long long at[4], int cnt, long long len, long long row[4]) {
+  if (VEC) row[0] = row[1] = row[2] = row[3] = at[0] / len;
+  else DSX_EACH4(j, cnt) row[j] = at[j] / len;
+}
+template <bool VEC>
+__device__ __forceinline__ void load4(const float* p, const long long at[4], int cnt, float v[4]) {
+  if (VEC) {
+    const float4 t = *(const float4*)(p + at[0]);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    DSX_EACH4(j, cnt) v[j] = p[at[j]];
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(float* p, const long long at[4], int cnt, const float v[4]) {
+  if (VEC) *(float4*)(p + at[0]) = make_float4(v[0], v[1], v[2], v[3]);
+  else DSX_EACH4(j, cnt) p[at[j]] = v[j];
+}
+// the same group in a uint16 tensor: one 8-byte access under VEC (the base pointers then are 8-byte aligned)
+template <bool VEC>
+__device__ __forceinline__ void load4(const unsigned short* p, const long long at[4], int cnt, unsigned v[4]) {
+  if (VEC) {
+    const ushort4 t = *(const ushort4*)(p + at[0]);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    DSX_EACH4(j, cnt) v[j] = p[at[j]];
+  }
+}
+template <bool VEC>
+__device__ __forceinline__ void store4(unsigned short* p, const long long at[4], int cnt, const unsigned v[4]) {
+  if (VEC) *(ushort4*)(p + at[0]) = make_ushort4((unsigned short)v[0], (unsigned short)v[1], (unsigned short)v[2], (unsigned short)v[3]);
+  else DSX_EACH4(j, cnt) p[at[j]] = (unsigned short)v[j];
+}
+template <class... P>
+static inline bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15u) == 0; }   // nullptr counts as aligned
+
 // The reverse update of every sampler (sr3 diffusion.py:141-175, ddpm diffusion.py:163-203, indi.py:62-69), stated once
 // for the loop (k_update, dsx_ops.hip) and the single steps (k_posterior_step, dsx_steps.hip); every product and sum
 // is rounded on its own, as the reference's ATen op sequence does:
@@ -503,6 +557,25 @@ hipError_t launch_q_sample(const QSampleArgs& a, hipStream_t st);
 int loss_blocks(long long n);
 hipError_t launch_loss(const float* a, const float* b, int B, long long n, int squared, double* part, double* out,
                        hipStream_t st);
+
+// dsx_validate.hip.  The validation report of the training loop (split.py:174-241) on NCHW fp32 visuals: uint16 counts
+// (x * std + mean in double, every operation rounded on its own, truncated; the prediction clamped to [0, 65535] first),
+// exact integer statistics, and -- with the three *_n pointers -- the uint16 numerators of the [0, 1] images.  Two
+// launches; the layouts of `part` (B * (C + Cin) * val_blocks(HW) rows of 4 words) and `stats` are stated in include/dsx.h.
+constexpr int kValChunk = 4096;        // pixels of one plane per workgroup of the first launch (DSX_VAL_CHUNK)
+constexpr int kValMaxC = 16;           // target channels (DSX_VAL_MAX_CHANNELS): their mean / std travel in the kernel arguments
+constexpr int kValFinishBlocks = 64;   // workgroups per plane of the second launch at most: each re-reads the plane's partial rows
+struct ValArgs {
+  const float* input; const float* target; const float* pred;                       // (B, Cin, H, W), (B, C, H, W) x 2
+  unsigned short* input_q; unsigned short* target_q; unsigned short* pred_q;
+  unsigned short* input_n; unsigned short* target_n; unsigned short* pred_n;        // all three, or all nullptr
+  unsigned long long* part; unsigned long long* stats;
+  double mean_in, std_in, mean_t[kValMaxC], std_t[kValMaxC];
+  int B, Cin, C, nblk;
+  long long HW;
+};
+int val_blocks(long long HW);
+hipError_t launch_val_report(const ValArgs& a, hipStream_t st);
 
 // One reverse update with its intermediates (NCHW fp32, per-sample coefficients, B values each):
 //   x0 = predict_eps ? clamp(a*x - b*net) : net;  mean = c1*x0 + c2*x;  out = mean + z*sigma (mean where sigma == 0)

@@ -6,42 +6,7 @@
 
 namespace dsx {
 
-// ---------------------------------------------------------------------------
-// The skeleton the three kernels share.  A thread owns group i4: the four consecutive elements from 4 * i4 (= one
-// Philox block of the flat normal stream).  VEC: H * W is a multiple of 4 and every base pointer is 16-byte aligned, so
-// a group lies inside one (b, c) row and is one 16-byte access in every tensor; otherwise its first `cnt` elements are
-// accessed one by one.  Each body below is written once over the arrays of a group, so both instantiations give the
-// same bits.
-// ---------------------------------------------------------------------------
-// the elements of a group that exist, unrolled: the arrays of a group stay in registers
-#define DSX_EACH4(j, cnt) _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < (cnt))
-// the flat indices of group i4 of n elements; returns how many of them exist
-template <bool VEC>
-__device__ __forceinline__ int group4(long long i4, long long n, long long at[4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) at[j] = i4 * 4 + j;
-  return VEC ? 4 : (int)min(4LL, n - i4 * 4);
-}
-// row[j] = at[j] / len: the (b, c) row with len = H*W, the sample with len = C*H*W.  VEC: one division per group.
-template <bool VEC>
-__device__ __forceinline__ void rows4(const long long at[4], int cnt, long long len, long long row[4]) {
-  if (VEC) row[0] = row[1] = row[2] = row[3] = at[0] / len;
-  else DSX_EACH4(j, cnt) row[j] = at[j] / len;
-}
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* p, const long long at[4], int cnt, float v[4]) {
-  if (VEC) {
-    const float4 t = *(const float4*)(p + at[0]);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    DSX_EACH4(j, cnt) v[j] = p[at[j]];
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void store4(float* p, const long long at[4], int cnt, const float v[4]) {
-  if (VEC) *(float4*)(p + at[0]) = make_float4(v[0], v[1], v[2], v[3]);
-  else DSX_EACH4(j, cnt) p[at[j]] = v[j];
-}
+// The skeleton the three kernels share (DSX_EACH4, group4, rows4, load4, store4, aligned16) is in dsx_kernels.h.
 // The normals of a group: elements zi[j] of `z`, or of the stream (seed, subseq) when z is nullptr (element i of a
 // stream is component i % 4 of Philox block i / 4).  block: zi is one whole Philox block -- always under VEC;
 // otherwise (`repeat` on the scalar path) each element looks up its own.
@@ -61,8 +26,6 @@ __device__ __forceinline__ void normals4(const float* z, unsigned long long seed
   }
 }
 
-template <class... P>
-static bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15u) == 0; }   // nullptr counts as aligned
 // one group per thread: k is the VEC or the scalar instantiation
 template <class Args>
 static hipError_t launch_groups4(void (*k)(Args), const Args& a, long long n, hipStream_t st) {

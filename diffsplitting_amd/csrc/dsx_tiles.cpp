@@ -232,6 +232,35 @@ extern "C" int dsx_image_metrics(const float* a, const float* b, int B, int C, i
   return DSX_OK;
 }
 
+// the validation report of the training loop (split.py:174-241): two launches, nothing allocated or synchronised
+extern "C" int dsx_val_report(const float* input, const float* target, const float* prediction, int B, int Cin, int C,
+                              int H, int W, double mean_input, double std_input, const double* mean_target,
+                              const double* std_target, uint16_t* input_q, uint16_t* target_q, uint16_t* pred_q,
+                              uint16_t* input_n, uint16_t* target_n, uint16_t* pred_n, uint64_t* partial_dev,
+                              uint64_t* stats_dev, void* stream) {
+  if (B < 1 || Cin < 1 || C < 1 || H < 1 || W < 1)
+    return fail(DSX_ERR_INVALID, "val_report: empty shape (%d, %d + %d, %d, %d)", B, Cin, C, H, W);
+  if (C > kValMaxC) return fail(DSX_ERR_INVALID, "val_report: %d target channels, at most %d", C, kValMaxC);
+  if ((int64_t)H * W > INT32_MAX) return fail(DSX_ERR_INVALID, "val_report: plane too large");
+  if ((int64_t)B * ((int64_t)C + Cin) > 65535)
+    return fail(DSX_ERR_INVALID, "val_report: B * (C + Cin) = %lld image planes, at most 65535", (long long)B * ((long long)C + Cin));
+  if (!input || !target || !prediction || !mean_target || !std_target || !input_q || !target_q || !pred_q || !partial_dev ||
+      !stats_dev)
+    return fail(DSX_ERR_INVALID, "val_report: null argument");
+  if ((input_n == nullptr) != (target_n == nullptr) || (input_n == nullptr) != (pred_n == nullptr))
+    return fail(DSX_ERR_INVALID, "val_report: the three numerator arrays are given together, or none");
+  ValArgs a{};
+  a.input = input; a.target = target; a.pred = prediction;
+  a.input_q = input_q; a.target_q = target_q; a.pred_q = pred_q;
+  a.input_n = input_n; a.target_n = target_n; a.pred_n = pred_n;
+  a.part = (unsigned long long*)partial_dev; a.stats = (unsigned long long*)stats_dev;
+  a.mean_in = mean_input; a.std_in = std_input;
+  for (int c = 0; c < C; ++c) { a.mean_t[c] = mean_target[c]; a.std_t[c] = std_target[c]; }
+  a.B = B; a.Cin = Cin; a.C = C; a.HW = (int64_t)H * W; a.nblk = val_blocks(a.HW);
+  HIP_TRY(launch_val_report(a, (hipStream_t)stream));
+  return DSX_OK;
+}
+
 // tiles of both channels cut out of device-resident frames AND normalised in the same pass: the batch source of tiled
 // prediction without the per-tile host crop + host->device copy of the reference's DataLoader(batch_size = 1)
 extern "C" int dsx_tiles_gather_norm(const float* frames0, const float* frames1, const int64_t data_shape[3],

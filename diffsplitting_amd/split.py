@@ -8,7 +8,9 @@ validation / tiled-prediction path on MI355X:
 The config file is consumed unchanged (JSON with // comments).  Frames come
 from ``--frames <file.npy>`` ((N,H,W,2) raw channels) or are synthesised when
 the config's data paths do not exist on this machine.  ``-p train`` is refused:
-the engine is inference-only.
+the engine is inference-only.  ``--validate [--results DIR]`` runs the training
+loop's validation report instead (core/validation.py): ``# Validation # PSNR``
+of the first 19 non-tiled items, and with ``--results`` the three images per item.
 """
 import argparse
 import logging
@@ -21,7 +23,7 @@ import torch
 
 from . import parallel
 from .core import logger as Logger
-from .data.split_dataset import DataLocation, SplitDatasetTiledPred
+from .data.split_dataset import DataLocation, SplitDataset, SplitDatasetTiledPred
 from .data.tiled_predict import TileExchange
 from .model import create_model
 
@@ -42,6 +44,9 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks to run (one process per GPU); default: the number of ids in -gpu.  Without a "
                          "launcher (torchrun) the ranks are started here")
+    ap.add_argument("--validate", action="store_true",
+                    help="the training loop's validation report (split.py:163-257) instead of the tiled prediction")
+    ap.add_argument("--results", type=str, default=None, help="with --validate: directory for the image triples")
     args = ap.parse_args(argv)
     if args.phase == "train":
         raise SystemExit("training is out of scope of the MI355X sampling engine; use -p val")
@@ -91,6 +96,8 @@ def main(argv=None):
                                     channel_weights=dsopt.get("channel_weights"), enable_transforms=False,
                                     random_patching=False, input_from_normalized_target=(which == "joint_indi"),
                                     device=dev)
+    if args.validate:
+        return _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log)
     plan = val_set.plan
     ids = parallel.shard_ids(plan.total, rank, world)
 
@@ -119,6 +126,25 @@ def main(argv=None):
                          "was given in path.resume_state)", c, ps[:, c].mean().item(),
                          ps[:, c].std().item() if ps.shape[0] > 1 else 0.0)
     return pred
+
+
+def _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log):
+    """``--validate``: the non-tiled dataset of the same frames with the same normalisation (split.get_datasets without
+    tiled_pred), the validation schedule, and ``core.validation.validate``.  Returns avg_psnr."""
+    from .core.validation import validate
+    items = SplitDataset("Hagen", DataLocation(arrays=(frames[..., 0], frames[..., 1])), patch,
+                         target_channel_idx=dsopt.get("target_channel_idx"), max_qval=dsopt.get("max_qval") or 0.98,
+                         normalization_dict=val_set.get_normalization_dict(), upper_clip=bool(dsopt.get("upper_clip")),
+                         channel_weights=dsopt.get("channel_weights"), enable_transforms=False, random_patching=False,
+                         input_from_normalized_target=(which == "joint_indi"), device=dev)
+    if args.steps:
+        diffusion.netG.set_new_noise_schedule(dict(opt["model"]["beta_schedule"]["val"], n_timestep=args.steps),
+                                              diffusion.device)
+    avg_psnr, per_channel = validate(diffusion, items, n_items=19, batch=args.batch_tiles, result_path=args.results)
+    log.info("# Validation # PSNR: {:.4e}".format(avg_psnr))
+    for ch, vals in per_channel.items():
+        log.info("channel %d: PSNR %.4e over %d items", ch, float(np.mean(vals)), len(vals))
+    return avg_psnr
 
 
 if __name__ == "__main__":

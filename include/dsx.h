@@ -286,6 +286,47 @@ int dsx_loss_blocks(int C, int H, int W);
 int dsx_loss(const float* a_dev, const float* b_dev, int B, int C, int H, int W, int squared,
              double* partial_dev, double* per_sample_dev, void* stream);
 
+/* ------------------------------------------------------- validation report
+ * dsx_val_report: what the training loop's validation block computes per item (split.py:174-241) on the NCHW fp32
+ * visuals input (B, Cin, H, W), target and prediction (B, C, H, W), C <= DSX_VAL_MAX_CHANNELS, B * (C + Cin) <= 65535.
+ * Two launches on `stream`, nothing allocated or synchronised; the second reads the first's partial statistics.
+ *
+ * Launch 1, in double with every product and sum rounded separately (numpy: a float32 array against float64 scalars),
+ * the casts truncating:
+ *   input_q  = uint16((input * std_input + mean_input) / 2)
+ *   target_q = uint16(target * std_target[c] + mean_target[c])
+ *   pred_q   = uint16(clip(prediction * std_target[c] + mean_target[c], 0, 65535))
+ * A value that is NaN before its cast, and a target or input value outside [0, 65536), has no defined uint16 (the
+ * reference's cast is undefined behaviour there): it is stored as 0 and counted.  Each workgroup owns DSX_VAL_CHUNK
+ * pixels of one plane and writes one row of four words {sum (target_q - pred_q)^2, min, max, undefined pixels} to
+ * partial_dev: 4 * DSX_VAL_PART_ROWS(B, Cin, C, H, W) uint64_t.  All statistics are integers: exact, and independent of
+ * the reduction order.
+ *
+ * Launch 2 writes stats_dev, DSX_VAL_STATS_WORDS(B, Cin, C) uint64_t:
+ *   [0]                            undefined pixels, all planes
+ *   [1 + 3 (b C + c) + {0,1,2}]    sum (target_q - pred_q)^2, min and max of target_q over plane (b, c)
+ *   [1 + 3 B C + 2 (b Cin + i) + {0,1}]   min and max of input_q over plane (b, i)
+ * and, when the three numerator arrays are given (all or none; same shapes as the *_q arrays), the numerators of the
+ * [0, 1] images the block writes in 'L' mode:
+ *   target_n = target_q - tmin,   input_n = input_q - (min over the item's input planes),
+ *   pred_n   = min((pred_q - tmin) mod 2^16, tmax - tmin)
+ * the reference's uint16 subtraction wraps where the prediction lies below the target's minimum and its clip to 1 then
+ * saturates the pixel; the denominators are tmax - tmin and imax - (item minimum).
+ *
+ * mean_target / std_target: host arrays of C doubles.  16-byte loads and 8-byte stores when H*W is a multiple of 4,
+ * the fp32 pointers are 16-byte and the uint16 pointers 8-byte aligned; a scalar path otherwise. */
+#define DSX_VAL_CHUNK 4096
+#define DSX_VAL_MAX_CHANNELS 16
+#define DSX_VAL_PART_ROWS(B, Cin, C, H, W) \
+  ((size_t)(B) * ((size_t)(C) + (size_t)(Cin)) * (((size_t)(H) * (size_t)(W) + DSX_VAL_CHUNK - 1) / DSX_VAL_CHUNK))
+#define DSX_VAL_STATS_WORDS(B, Cin, C) (1 + (size_t)(B) * (3 * (size_t)(C) + 2 * (size_t)(Cin)))
+int dsx_val_report(const float* input_dev, const float* target_dev, const float* prediction_dev,
+                   int B, int Cin, int C, int H, int W, double mean_input, double std_input,
+                   const double* mean_target, const double* std_target,
+                   uint16_t* input_q_dev, uint16_t* target_q_dev, uint16_t* pred_q_dev,
+                   uint16_t* input_n_dev, uint16_t* target_n_dev, uint16_t* pred_n_dev,
+                   uint64_t* partial_dev, uint64_t* stats_dev, void* stream);
+
 /* ------------------------------------------------- caller-driven reverse sampling
  * The single reverse steps of the sampler classes as the caller's own loop uses them (p_mean_variance / p_sample, sr3
  * diffusion.py:151-175, ddpm diffusion.py:179-203; inference_one_step, indi.py:62-69) and the start of interpolate
