@@ -8,7 +8,7 @@ OBJ=${DSX_OBJ:-_obj}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $DSX_EXTRA_FLAGS"
 mkdir -p $OBJ
 # every source of the library: kernels (*.hip) and host translation units (*.cpp, compiled as HIP too)
-SRCS="dsx_conv.hip dsx_ops.hip dsx_attn.hip dsx_lpips.hip dsx_resize.hip dsx_objective.hip dsx_steps.hip dsx_validate.hip dsx_model.cpp dsx_plan.cpp dsx_exec.cpp dsx_tiles.cpp dsx_lpips.cpp dsx_resize.cpp"
+SRCS="dsx_conv.hip dsx_ops.hip dsx_attn.hip dsx_lpips.hip dsx_resize.hip dsx_eval.hip dsx_steps.hip dsx_validate.hip dsx_model.cpp dsx_plan.cpp dsx_exec.cpp dsx_tiles.cpp dsx_lpips.cpp dsx_resize.cpp"
 # a changed flag set rebuilds everything
 if [ "$(cat $OBJ/.flags 2>/dev/null)" != "$FLAGS" ]; then rm -f $OBJ/*.o; echo "$FLAGS" > $OBJ/.flags; fi
 stale() {   # stale OBJECT FILE...: the object is missing or older than one of the files
@@ -21,7 +21,7 @@ pids=()
 OBJS=""
 for f in $SRCS; do
   case $f in
-    *.hip) deps="dsx_kernels.h $(echo *.inc)"; lang="" ;;     # included bodies (dsx_conv_ws_item.inc)
+    *.hip) deps="dsx_kernels.h dsx_reduce.h $(echo *.inc)"; lang="" ;;     # included bodies (dsx_conv_ws_item.inc)
     *) deps="dsx_rt.h dsx_kernels.h ../../include/dsx.h"; lang="-x hip" ;;
   esac
   OBJS="$OBJS $OBJ/$f.o"

@@ -350,7 +350,7 @@ extern "C" int dsx_randn(float* out, int64_t n, uint64_t seed, uint64_t subseq, 
   return DSX_OK;
 }
 
-// ---- the pointwise sampler kernels (dsx_steps.hip) and the loss reduction (dsx_objective.hip)
+// ---- the pointwise sampler kernels (dsx_steps.hip) and the loss reduction (dsx_eval.hip)
 static int steps_shape(const char* what, int B, int C, int H, int W) {
   if (B < 1 || C < 1 || H < 1 || W < 1) return fail(DSX_ERR_INVALID, "%s: empty shape (%d, %d, %d, %d)", what, B, C, H, W);
   if ((int64_t)H * W > INT32_MAX || (int64_t)B * C * H * W > ((int64_t)1 << 40))

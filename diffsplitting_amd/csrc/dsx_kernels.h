@@ -1,5 +1,5 @@
 // dsx_kernels.h — launch interface between the host runtime (dsx_*.cpp)
-// and the gfx950 kernels (dsx_conv.hip, dsx_ops.hip, dsx_attn.hip).  Internal;
+// and the gfx950 kernels (dsx_conv.hip, dsx_ops.hip, dsx_attn.hip, dsx_eval.hip, ...).  Internal;
 // the public ABI is include/dsx.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -552,7 +552,7 @@ struct QSampleArgs {
   int B, C, Ce, HW, Cdst, coff;
 };
 hipError_t launch_q_sample(const QSampleArgs& a, hipStream_t st);
-// dsx_objective.hip.  per-sample sum |a - b| (squared == 0) or sum (a - b)^2 over n elements, in double: part[B][loss_blocks(n)] partials
+// dsx_eval.hip.  per-sample sum |a - b| (squared == 0) or sum (a - b)^2 over n elements, in double: part[B][loss_blocks(n)] partials
 // in a fixed partition, out[B] their sums in a fixed order (two launches, no atomics)
 int loss_blocks(long long n);
 hipError_t launch_loss(const float* a, const float* b, int B, long long n, int squared, double* part, double* out,
@@ -601,6 +601,7 @@ struct InterpStartArgs {
 };
 hipError_t launch_interp_start(const InterpStartArgs& a, long long HW, hipStream_t st);
 
+// dsx_eval.hip: tiles, range table, stitch, image metrics.
 // the tiles of one launch: ids first, first + stride, ... (count of them); the tables a kernel indexes with an id
 // (`starts` [..][3], `regions` [..][8], `off` [..]) live on the device -- the plan's own (dsx_tileplan), or a per-call
 // table with first = 0, stride = 1
@@ -697,7 +698,7 @@ hipError_t launch_resize_v_u8(const ResizePassArgs& a, hipStream_t st);
 hipError_t launch_u8_to_tensor(const unsigned char* src, int B, long long HW, int C, float lo, float hi, float* dst,
                                hipStream_t st);
 
-// relu(u) * sigmoid-mask reduction of the TimePredictor head
+// dsx_ops.hip.  relu(u) * sigmoid-mask reduction of the TimePredictor head
 hipError_t launch_masked_mean(const float* u, const float* mask, int B, long long n, float* out,
                               hipStream_t st);
 

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "dsx_kernels.h"
+#include "dsx_reduce.h"
 
 namespace dsx {
 
@@ -100,23 +101,19 @@ __global__ __launch_bounds__(256) void k_lpips_input_frames(const float* __restr
 // min / max of one channel of a channel-last stack (order-independent, so repeatable); part[blocks][2]
 __global__ __launch_bounds__(256) void k_lpips_minmax(const float* __restrict__ x, long long pixels, int C, int ch,
                                                       float* __restrict__ part) {
-  __shared__ float slo[256], shi[256];
+  __shared__ float red[4 * 2];
   float lo = INFINITY, hi = -INFINITY;
   for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < pixels; p += (long long)gridDim.x * 256) {
     const float v = x[(size_t)p * C + ch];
     lo = fminf(lo, v);
     hi = fmaxf(hi, v);
   }
-  slo[threadIdx.x] = lo; shi[threadIdx.x] = hi;
+  block_park<RedMin>(lo, red, 2, 0);
+  block_park<RedMax>(hi, red, 2, 1);
   __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      slo[threadIdx.x] = fminf(slo[threadIdx.x], slo[threadIdx.x + s]);
-      shi[threadIdx.x] = fmaxf(shi[threadIdx.x], shi[threadIdx.x + s]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { part[2 * blockIdx.x] = slo[0]; part[2 * blockIdx.x + 1] = shi[0]; }
+  if (threadIdx.x < 2)
+    part[2 * blockIdx.x + threadIdx.x] = threadIdx.x ? block_combine<RedMax, Pairwise>(red, 2, 1)
+                                                     : block_combine<RedMin, Pairwise>(red, 2, 0);
 }
 __global__ __launch_bounds__(64) void k_lpips_minmax_fin(const float* __restrict__ part, int blocks, float* __restrict__ mm) {
   if (threadIdx.x != 0) return;
@@ -272,6 +269,8 @@ __global__ __launch_bounds__(256) void k_lpips_pool(const float* __restrict__ in
 // feat (2B, HW, C): pair b = images b and B + b.  A wave takes one pixel at a time: 64 lanes x NC channels each, the
 // two norms by a butterfly (every lane gets the same bits), the lin-weighted squared difference accumulated per lane in
 // double; lanes, waves and (k_lpips_finish) workgroups are then added in a fixed order.  part[B][nblk].
+// The butterflies run upwards (kUp: offsets 1 .. 32) and the waves are added serially, unlike the other metric kernels
+// (dsx_reduce.h): these sums round, so another order would give other bits than the ones recorded for this metric.
 template <int NC>
 __global__ __launch_bounds__(256) void k_lpips_dist(const float* __restrict__ feat, int B, int HW, const float* __restrict__ lin,
                                                     int ppb, double* __restrict__ part) {
@@ -294,8 +293,8 @@ __global__ __launch_bounds__(256) void k_lpips_dist(const float* __restrict__ fe
       s0 = fmaf(a[j], a[j], s0);
       s1 = fmaf(c[j], c[j], s1);
     }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) { s0 += __shfl_xor(s0, m, 64); s1 += __shfl_xor(s1, m, 64); }
+    s0 = wave_reduce<RedSum, kUp>(s0);
+    s1 = wave_reduce<RedSum, kUp>(s1);
     const float n0 = sqrtf(s0) + 1e-10f, n1 = sqrtf(s1) + 1e-10f;
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
@@ -303,11 +302,8 @@ __global__ __launch_bounds__(256) void k_lpips_dist(const float* __restrict__ fe
       acc += (double)(w[j] * (d * d));
     }
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m, 64);
-  if (lane == 0) sw[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = ((sw[0] + sw[1]) + sw[2]) + sw[3];
+  acc = block_reduce<RedSum, Serial, kUp>(acc, sw);
+  if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = acc;
 }
 
 __global__ __launch_bounds__(64) void k_lpips_finish(const double* __restrict__ part, LpipsTaps taps, int B, int b_off,

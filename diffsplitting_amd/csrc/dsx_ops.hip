@@ -1,29 +1,12 @@
 // dsx_ops.hip — the non-conv kernels of the sampling path (gfx950):
 // GroupNorm statistics (wavefront-shuffle reductions), time embedding + FiLM,
-// the sampler update with Philox noise, layout conversion, tile gather / stitch.
-// (Attention: dsx_attn.hip.)
+// the sampler update with Philox noise, layout conversion, the TimePredictor head.
+// (Attention: dsx_attn.hip.  Tiles, stitch and the metrics: dsx_eval.hip.)
 #include "dsx_kernels.h"
+#include "dsx_reduce.h"
 #include <algorithm>
 
 namespace dsx {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // ---------------------------------------------------------------------------
 // Per-channel partial sums for GroupNorm (nn.GroupNorm inside Block /
@@ -417,438 +400,11 @@ hipError_t launch_advance(int* step_ctr, hipStream_t st) {
   return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// tiles: gather (N,H,W) frames -> (count, ph, pw); stitch valid regions of
-// (count, C, ph, pw) predictions into the (N,H,W,C) canvas (tile_stitcher.py:26-80).
-// The tiles of a launch are the arithmetic sequence  id = first + k * stride  (k = blockIdx.y): a rank's
-// shard of a plan (or a batch of it) indexes the plan's device tables directly, nothing is uploaded per call.
-// ---------------------------------------------------------------------------
-__global__ void k_tiles_gather(const float* __restrict__ frames, int H, int W, int ph, int pw,
-                               const int* __restrict__ starts, TileSeq seq, float* __restrict__ tiles) {
-  const long long k = blockIdx.y, t = seq.first + k * seq.stride;
-  const int n = starts[t * 3], y0 = starts[t * 3 + 1], x0 = starts[t * 3 + 2];
-  const int total = ph * pw;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int y = i / pw, x = i % pw;
-    tiles[k * total + i] = frames[((size_t)n * H + (y0 + y)) * W + (x0 + x)];
-  }
-}
-hipError_t launch_tiles_gather(const float* frames, int H, int W, int ph, int pw, const int* starts, TileSeq seq,
-                               float* tiles, hipStream_t st) {
-  int gx = (ph * pw + 255) / 256;
-  if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(k_tiles_gather, dim3((unsigned)gx, (unsigned)seq.count), dim3(256), 0, st, frames, H, W,
-                     ph, pw, starts, seq, tiles);
-  return hipGetLastError();
-}
-
-// tile crop + the dataset's normalisation in one pass (SplitDataset.__getitem__, data/split_dataset.py:237-278):
-//   target_c = (frame_c - mean_target_c) / std_target_c                       (normalize_target, :199-201)
-//   input    = w0 * target_0 + w1 * target_1                                   (input_from_normalized_target)
-//            | ((w0 * frame_0 + w1 * frame_1) - mean_input) / std_input        (normalize_inp, :195-197)
-// in double, rounded to fp32 once, exactly as numpy does with its float64 statistics.
-struct GatherNormArgs {
-  const float* f0; const float* f1;
-  int H, W, ph, pw;
-  const int* starts;       // dev [..][3], indexed by tile id
-  TileSeq seq;
-  float w0, w1;
-  double mean_inp, std_inp, mt0, st0, mt1, st1;
-  int from_norm_target;
-  float* tin;              // (count, 1, ph, pw)
-  float* ttar;             // (count, 2, ph, pw)
-};
-__global__ void k_tiles_gather_norm(const GatherNormArgs a) {
-  const long long k = blockIdx.y, t = a.seq.first + k * a.seq.stride;
-  const int n = a.starts[t * 3], y0 = a.starts[t * 3 + 1], x0 = a.starts[t * 3 + 2];
-  const int total = a.ph * a.pw;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int y = i / a.pw, x = i % a.pw;
-    const size_t src = ((size_t)n * a.H + (y0 + y)) * a.W + (x0 + x);
-    const float p0 = a.f0[src], p1 = a.f1[src];
-    const float t0 = (float)(((double)p0 - a.mt0) / a.st0), t1 = (float)(((double)p1 - a.mt1) / a.st1);
-    float in;
-    if (a.from_norm_target) in = __fadd_rn(__fmul_rn(a.w0, t0), __fmul_rn(a.w1, t1));
-    else in = (float)(((double)__fadd_rn(__fmul_rn(a.w0, p0), __fmul_rn(a.w1, p1)) - a.mean_inp) / a.std_inp);
-    a.tin[k * total + i] = in;
-    a.ttar[(k * 2) * total + i] = t0;
-    a.ttar[(k * 2 + 1) * total + i] = t1;
-  }
-}
-hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
-                                    TileSeq seq, float w0, float w1, const double norm[6], int from_norm_target,
-                                    float* tin, float* ttar, hipStream_t st) {
-  GatherNormArgs a{f0, f1, H, W, ph, pw, starts, seq, w0, w1, norm[0], norm[1], norm[2], norm[3], norm[4], norm[5],
-                   from_norm_target, tin, ttar};
-  int gx = (ph * pw + 255) / 256;
-  if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(k_tiles_gather_norm, dim3((unsigned)gx, (unsigned)seq.count), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// (mul_f / add_f / mul_d / add_d, one IEEE operation each, live in dsx_kernels.h)
-// The mixed inputs of the TimePredictor evaluation (notebooks/EvaluateJointIndiIterative.ipynb cells 40/43,
-// time_prediction_evaluation.ipynb cell 4) cut, normalised, mixed and min-max-normalised in one pass; the op list is
-// in include/dsx.h (dsx_tiles_gather_mix).  Channel 0 is indi1's input, channel 1 indi2's.
-struct GatherMixArgs {
-  const float* f0; const float* f1;
-  int H, W, ph, pw;
-  const int* starts;       // dev [..][3], indexed by tile id
-  TileSeq seq;
-  double mt0, st0, mt1, st1;
-  MixWeights mw;
-  float* ttar; float* tmix; float* tcls;   // (count, 2, ph, pw) each, or nullptr
-};
-__global__ void k_tiles_gather_mix(const GatherMixArgs a) {
-  const long long k = blockIdx.y, t = a.seq.first + k * a.seq.stride;
-  const int n = a.starts[t * 3], y0 = a.starts[t * 3 + 1], x0 = a.starts[t * 3 + 2];
-  const int total = a.ph * a.pw;
-  const MixWeights w = a.mw;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int y = i / a.pw, x = i % a.pw;
-    const size_t src = ((size_t)n * a.H + (y0 + y)) * a.W + (x0 + x);
-    const float t0 = (float)(((double)a.f0[src] - a.mt0) / a.st0), t1 = (float)(((double)a.f1[src] - a.mt1) / a.st1);
-    const size_t d0 = (size_t)(k * 2) * total + i, d1 = d0 + total;
-    if (a.ttar) { a.ttar[d0] = t0; a.ttar[d1] = t1; }
-    if (a.tmix || a.tcls) {
-      const float m0 = add_f(mul_f(t0, w.w0), mul_f(t1, w.w1));
-      const float m1 = add_f(mul_f(t1, w.w0), mul_f(t0, w.w1));
-      if (a.tmix) { a.tmix[d0] = m0; a.tmix[d1] = m1; }
-      if (a.tcls) {
-        a.tcls[d0] = add_f(mul_f(2.0f, add_f(m0, -w.lo0)) / w.rng0, -1.0f);
-        a.tcls[d1] = add_f(mul_f(2.0f, add_f(m1, -w.lo1)) / w.rng1, -1.0f);
-      }
-    }
-  }
-}
-hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
-                                   TileSeq seq, const double norm[4], const MixWeights& mw, float* ttar, float* tmix,
-                                   float* tcls, hipStream_t st) {
-  GatherMixArgs a{f0, f1, H, W, ph, pw, starts, seq, norm[0], norm[1], norm[2], norm[3], mw, ttar, tmix, tcls};
-  int gx = (ph * pw + 255) / 256;
-  if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(k_tiles_gather_mix, dim3((unsigned)gx, (unsigned)seq.count), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// The TimePredictor's input range table (compute_input_normalization_dict, data/time_predictor_dataset.py:6-21): for
-// every t_int in 0..n the min and max over all pixels of  t * a + (1 - t) * b,  t = t_int / n,  a, b = the normalised
-// channels -- n + 1 numpy passes over the frame set in the reference, one launch here.  All of it in fp64 with every
-// operation rounded on its own (numpy has no fma), so the table is bitwise numpy's; min / max are exact, the result
-// does not depend on the reduction tree.  fp64-VALU-bound, not HBM-bound: a thread keeps the running min / max of
-// kMixTB values of t in registers (and their weights) while it strides over its workgroup's pixel chunk; the t blocks
-// are blockIdx.x, so the workgroups that re-read a chunk are dispatched together and find it in L2 / MALL.  Wave
-// reduction by shuffles, the four waves through LDS, one partial row per workgroup: part[chunk][t_int][{min, max}].
-constexpr int kMixTB = 8;
-constexpr int kMixMaxChunks = 512;
-__global__ __launch_bounds__(256) void k_mix_range(const float* __restrict__ f0, const float* __restrict__ f1,
-                                                   long long pixels, long long chunk, double m0, double s0, double m1,
-                                                   double s1, int n, double* __restrict__ part) {
-  __shared__ double red[4][kMixTB][2];
-  const int tb = blockIdx.x * kMixTB;
-  double tw[kMixTB], uw[kMixTB], mn[kMixTB], mx[kMixTB];
-#pragma unroll
-  for (int j = 0; j < kMixTB; ++j) {
-    const int ti = min(tb + j, n);             // the rows past n of the last block repeat row n and are not written
-    tw[j] = (double)ti / (double)n;            // IEEE division, as numpy's t_int / n_timesteps
-    uw[j] = 1.0 - tw[j];
-    mn[j] = INFINITY; mx[j] = -INFINITY;
-  }
-  const long long p0 = blockIdx.y * chunk, p1 = min(pixels, p0 + chunk);
-  for (long long p = p0 + threadIdx.x; p < p1; p += 256) {
-    const double a = ((double)f0[p] - m0) / s0, b = ((double)f1[p] - m1) / s1;
-#pragma unroll
-    for (int j = 0; j < kMixTB; ++j) {
-      const double v = add_d(mul_d(tw[j], a), mul_d(uw[j], b));
-      mn[j] = fmin(mn[j], v); mx[j] = fmax(mx[j], v);
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < kMixTB; ++j) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[j] = fmin(mn[j], __shfl_xor(mn[j], o, 64)); mx[j] = fmax(mx[j], __shfl_xor(mx[j], o, 64)); }
-    if (lane == 0) { red[wave][j][0] = mn[j]; red[wave][j][1] = mx[j]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < kMixTB * 2) {
-    const int j = threadIdx.x >> 1, kk = threadIdx.x & 1;
-    if (tb + j <= n) {
-      const double r0 = red[0][j][kk], r1 = red[1][j][kk], r2 = red[2][j][kk], r3 = red[3][j][kk];
-      part[((size_t)blockIdx.y * (n + 1) + (tb + j)) * 2 + kk] =
-          kk ? fmax(fmax(r0, r1), fmax(r2, r3)) : fmin(fmin(r0, r1), fmin(r2, r3));
-    }
-  }
-}
-// pixel workgroups (= rows of partials) of a call: about a thousand pixels per workgroup at least, 512 chunks at most
-int mix_range_blocks(long long pixels) {
-  const long long g = (pixels + 1023) / 1024;
-  return (int)(g > kMixMaxChunks ? kMixMaxChunks : (g < 1 ? 1 : g));
-}
-hipError_t launch_mix_range(const float* f0, const float* f1, long long pixels, const double norm[4], int n, double* part,
-                            hipStream_t st) {
-  const int gy = mix_range_blocks(pixels);
-  const long long chunk = (pixels + gy - 1) / gy;
-  hipLaunchKernelGGL(k_mix_range, dim3((unsigned)((n + kMixTB) / kMixTB), (unsigned)gy), dim3(256), 0, st, f0, f1, pixels,
-                     chunk, norm[0], norm[1], norm[2], norm[3], n, part);
-  return hipGetLastError();
-}
-
-// Where the pixels of tile `t` (the k-th of the launch) come from: whole predicted tiles (count, C, ph, pw), or the
-// packed exchange buffer of tiled multi-GPU prediction -- per rank one flat run of valid regions [C][h][w], tile after
-// tile in id order (rank q owns the ids q, q + world, ...); `off` = pixel offset of every tile inside its rank's run.
-struct TileSrc {
-  const float* base;       // tiles, or the gathered flat buffer [world][rank_stride]
-  int packed;              // 0: whole tiles, 1: packed valid regions
-  int ph, pw;              // whole tiles
-  const long long* off;    // packed: dev [total] pixel offsets
-  long long rank_stride;   // packed: elements between two ranks' runs
-  int world;
-};
-struct TileView { const float* p; int pitch; long long plane; };
-__device__ __forceinline__ TileView tile_view(const TileSrc& s, long long k, long long t, int C, const int* r) {
-  TileView v;
-  if (s.packed) {
-    v.p = s.base + (t % s.world) * s.rank_stride + s.off[t] * C;
-    v.pitch = r[4]; v.plane = (long long)r[3] * r[4];
-  } else {
-    v.p = s.base + (size_t)k * C * s.ph * s.pw + (size_t)r[5] * s.pw + r[6];
-    v.pitch = s.pw; v.plane = (long long)s.ph * s.pw;
-  }
-  return v;
-}
-
-__global__ void k_stitch(const TileSrc src, int C, const int* __restrict__ regions, TileSeq seq,
-                         float* __restrict__ canvas, int H, int W) {
-  const long long k = blockIdx.y, t = seq.first + k * seq.stride;
-  const int* r = regions + t * 8;
-  const int n = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
-  const int total = h * w * C;
-  const TileView v = tile_view(src, k, t, C, r);
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int c = i % C;
-    const int p = i / C;
-    const int x = p % w, y = p / w;
-    canvas[(((size_t)n * H + (y0 + y)) * W + (x0 + x)) * C + c] = v.p[c * v.plane + (size_t)y * v.pitch + x];
-  }
-}
-
-// The valid region of every tile of the sequence, [C][h][w], to its place in this rank's flat run: the crop of
-// tile_stitcher.py:38-56 applied BEFORE the collective (a 512^2 tile of a 256 grid ships 256^2 .. 384^2 pixels).
-__global__ void k_tiles_pack(const float* __restrict__ tiles, int C, int ph, int pw, const int* __restrict__ regions,
-                             const long long* __restrict__ off, TileSeq seq, float* __restrict__ flat) {
-  const long long k = blockIdx.y, t = seq.first + k * seq.stride;
-  const int* r = regions + t * 8;
-  const int h = r[3], w = r[4], ry = r[5], rx = r[6];
-  const int total = C * h * w;
-  const float* tile = tiles + (size_t)k * C * ph * pw;
-  float* dst = flat + off[t] * C;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const int x = i % w, q = i / w, y = q % h, c = q / h;
-    dst[i] = tile[((size_t)c * ph + (ry + y)) * pw + (rx + x)];
-  }
-}
-hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const int* regions, const long long* off,
-                             TileSeq seq, float* flat, hipStream_t st) {
-  int gx = (ph * pw * C + 255) / 256;
-  if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(k_tiles_pack, dim3((unsigned)gx, (unsigned)seq.count), dim3(256), 0, st, tiles, C, ph, pw, regions,
-                     off, seq, flat);
-  return hipGetLastError();
-}
-
-// Stitch + the sums RangeInvariantPsnr needs (core/psnr.py:70-82), in the same pass: while a tile's valid region
-// is pasted, every (tile, workgroup) also reduces, per channel, sum(p), sum(p^2), sum(g), sum(g^2), sum(g p),
-// min(g), max(g) of prediction p against the ground truth g at the same canvas pixels (every canvas pixel is pasted
-// exactly once).  Fixed reduction order (thread -> wave shuffles -> 4 waves): bitwise reproducible.
-// part[k][blockIdx.x][c][8] doubles; the per-frame combination (a few hundred values) is the caller's.
-constexpr int kPsnrMaxC = 4;
-__global__ __launch_bounds__(256) void k_stitch_psnr(const TileSrc src, int C, const int* __restrict__ regions, TileSeq seq,
-                                                      float* __restrict__ canvas, const float* __restrict__ gt, int H, int W,
-                                                      double* __restrict__ part) {
-  __shared__ double red[4][kPsnrMaxC][7];
-  const long long k = blockIdx.y, t = seq.first + k * seq.stride;
-  const int* r = regions + t * 8;
-  const int n = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
-  const TileView v = tile_view(src, k, t, C, r);
-  double sp[kPsnrMaxC], spp[kPsnrMaxC], sg[kPsnrMaxC], sgg[kPsnrMaxC], sgp[kPsnrMaxC], mn[kPsnrMaxC], mx[kPsnrMaxC];
-#pragma unroll
-  for (int c = 0; c < kPsnrMaxC; ++c) { sp[c] = spp[c] = sg[c] = sgg[c] = sgp[c] = 0; mn[c] = INFINITY; mx[c] = -INFINITY; }
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h * w; i += gridDim.x * blockDim.x) {
-    const int x = i % w, y = i / w;
-    const size_t cpix = (((size_t)n * H + (y0 + y)) * W + (x0 + x)) * C;
-#pragma unroll
-    for (int c = 0; c < kPsnrMaxC; ++c) {
-      if (c < C) {
-        const float p = v.p[c * v.plane + (size_t)y * v.pitch + x];
-        const float g = gt[cpix + c];
-        canvas[cpix + c] = p;
-        sp[c] += p; spp[c] += (double)p * p; sg[c] += g; sgg[c] += (double)g * g; sgp[c] += (double)g * p;
-        mn[c] = fmin(mn[c], (double)g); mx[c] = fmax(mx[c], (double)g);
-      }
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int c = 0; c < kPsnrMaxC; ++c) {
-    sp[c] = wave_sum(sp[c]); spp[c] = wave_sum(spp[c]); sg[c] = wave_sum(sg[c]); sgg[c] = wave_sum(sgg[c]);
-    sgp[c] = wave_sum(sgp[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { mn[c] = fmin(mn[c], __shfl_xor(mn[c], o, 64)); mx[c] = fmax(mx[c], __shfl_xor(mx[c], o, 64)); }
-    if (lane == 0) {
-      red[wave][c][0] = sp[c]; red[wave][c][1] = spp[c]; red[wave][c][2] = sg[c]; red[wave][c][3] = sgg[c];
-      red[wave][c][4] = sgp[c]; red[wave][c][5] = mn[c]; red[wave][c][6] = mx[c];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < C * 8) {
-    const int c = threadIdx.x >> 3, kk = threadIdx.x & 7;
-    double o = 0;
-    if (kk < 5) o = (red[0][c][kk] + red[1][c][kk]) + (red[2][c][kk] + red[3][c][kk]);
-    else if (kk == 5) o = fmin(fmin(red[0][c][5], red[1][c][5]), fmin(red[2][c][5], red[3][c][5]));
-    else if (kk == 6) o = fmax(fmax(red[0][c][6], red[1][c][6]), fmax(red[2][c][6], red[3][c][6]));
-    part[(((size_t)k * gridDim.x + blockIdx.x) * C + c) * 8 + kk] = o;
-  }
-}
-// gt == nullptr: plain paste; else also the RangeInvariantPsnr partial sums (C <= 4, gx workgroups per tile)
-hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions, TileSeq seq, float* canvas, int H, int W,
-                         const float* gt, double* part, int gx, hipStream_t st) {
-  const TileSrc src{s.base, s.packed, s.ph, s.pw, s.off, s.rank_stride, s.world < 1 ? 1 : s.world};
-  if (gt != nullptr) {
-    if (C < 1 || C > kPsnrMaxC || gx < 1 || part == nullptr) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_stitch_psnr, dim3((unsigned)gx, (unsigned)seq.count), dim3(256), 0, st, src, C, regions, seq,
-                       canvas, gt, H, W, part);
-  } else {
-    int g = (s.ph * s.pw * C + 255) / 256;
-    if (g > 64) g = 64;
-    hipLaunchKernelGGL(k_stitch, dim3((unsigned)g, (unsigned)seq.count), dim3(256), 0, st, src, C, regions, seq, canvas,
-                       H, W);
-  }
-  return hipGetLastError();
-}
-
-// SSIM (core/metrics.py:72-92) + sum of squared differences (calculate_psnr, :62-69) of image pairs in one pass.
-// One workgroup per (32 x 32 tile of the valid region [5:-5, 5:-5], image plane): the 42 x 42 input tile (10-pixel
-// halo, re-read by the neighbours through L2) is staged in LDS, quantised on the load when asked (tensor2img,
-// :14-34: clamp, (x - lo) / (hi - lo) with IEEE division, * 255, round half to even); then the 11-tap Gaussian is
-// applied horizontally to the five moments x, y, x^2, y^2, x y of all 42 rows (fp64, to LDS) and vertically to the
-// 32 output rows.  Each plane's pixels are partitioned among its tiles (edge tiles also own the 5-pixel border) for
-// the SSD: exact uint64 of integers when quantised, fp64 otherwise.  Fixed reduction order (thread -> wave shuffles
-// -> 4 waves), no atomics: part[plane][tile] = {sum of the SSIM map over the tile, SSD}, bitwise reproducible.
-constexpr int kSsimT = 32, kSsimIn = kSsimT + 10;
-__device__ __forceinline__ float metrics_load(const float* p, bool quantize, float lo, float hi, float rng) {
-  float x = *p;
-  if (quantize) x = rintf((fminf(fmaxf(x, lo), hi) - lo) / rng * 255.0f);
-  return x;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__global__ __launch_bounds__(256) void k_image_metrics(const float* __restrict__ a, const float* __restrict__ b, int H,
-                                                       int W, int quantize, float lo, float hi, float rng, double c1,
-                                                       double c2, SsimWindow win, int tiles_x, double* __restrict__ part) {
-  __shared__ float sa[kSsimIn][kSsimIn], sb[kSsimIn][kSsimIn];
-  __shared__ double hm[5][kSsimIn][kSsimT];
-  __shared__ double red[4];
-  __shared__ unsigned long long redq[4];
-  const int tile = blockIdx.x, plane = blockIdx.y;
-  const int y0 = (tile / tiles_x) * kSsimT, x0 = (tile % tiles_x) * kSsimT;    // output tile = input rows/cols + 5
-  const int ty_last = (H - 10 + kSsimT - 1) / kSsimT - 1, tx_last = tiles_x - 1;
-  // pixels of this tile's SSD share: its output rows/cols, widened to the image edge on the edge tiles
-  const int oy0 = y0 == 0 ? 0 : y0 + 5, oy1 = y0 / kSsimT == ty_last ? H : y0 + 5 + kSsimT;
-  const int ox0 = x0 == 0 ? 0 : x0 + 5, ox1 = x0 / kSsimT == tx_last ? W : x0 + 5 + kSsimT;
-  const size_t pl = (size_t)plane * H * W;
-  const bool q = quantize != 0;
-  double ssd = 0;
-  unsigned long long ssdq = 0;
-  for (int i = threadIdx.x; i < kSsimIn * kSsimIn; i += 256) {
-    const int r = i / kSsimIn, c = i % kSsimIn, y = y0 + r, x = x0 + c;
-    float va = 0.f, vb = 0.f;
-    if (y < H && x < W) {
-      va = metrics_load(a + pl + (size_t)y * W + x, q, lo, hi, rng);
-      vb = metrics_load(b + pl + (size_t)y * W + x, q, lo, hi, rng);
-      if (y >= oy0 && y < oy1 && x >= ox0 && x < ox1) {
-        if (q) { const int d = (int)va - (int)vb; ssdq += (unsigned long long)(d * d); }
-        else { const double d = (double)va - (double)vb; ssd += d * d; }
-      }
-    }
-    sa[r][c] = va; sb[r][c] = vb;
-  }
-  __syncthreads();
-  const int col = threadIdx.x & (kSsimT - 1), r8 = threadIdx.x / kSsimT;
-  for (int r = r8; r < kSsimIn; r += 256 / kSsimT) {
-    double m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0;
-#pragma unroll
-    for (int k = 0; k < 11; ++k) {
-      const double u = sa[r][col + k], v = sb[r][col + k], w = win.w[k];
-      m0 += w * u; m1 += w * v; m2 += w * (u * u); m3 += w * (v * v); m4 += w * (u * v);
-    }
-    hm[0][r][col] = m0; hm[1][r][col] = m1; hm[2][r][col] = m2; hm[3][r][col] = m3; hm[4][r][col] = m4;
-  }
-  __syncthreads();
-  // vertical: 4 consecutive output rows per thread share their 14 rows of horizontal sums (taps in ascending order)
-  constexpr int kRows = kSsimT / (256 / kSsimT);
-  const int rv = r8 * kRows;
-  double acc = 0;
-  if (x0 + col < W - 10) {
-    double mu1[kRows] = {}, mu2[kRows] = {}, e11[kRows] = {}, e22[kRows] = {}, e12[kRows] = {};
-#pragma unroll
-    for (int k = 0; k < kRows + 10; ++k) {
-      const double h0 = hm[0][rv + k][col], h1 = hm[1][rv + k][col], h2 = hm[2][rv + k][col],
-                   h3 = hm[3][rv + k][col], h4 = hm[4][rv + k][col];
-#pragma unroll
-      for (int j = 0; j < kRows; ++j) {
-        if (k - j >= 0 && k - j < 11) {
-          const double w = win.w[k - j];
-          mu1[j] += w * h0; mu2[j] += w * h1; e11[j] += w * h2; e22[j] += w * h3; e12[j] += w * h4;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-      if (y0 + rv + j < H - 10) {
-        const double mu11 = mu1[j] * mu1[j], mu22 = mu2[j] * mu2[j], mu12 = mu1[j] * mu2[j];
-        const double s11 = e11[j] - mu11, s22 = e22[j] - mu22, s12 = e12[j] - mu12;
-        acc += ((2 * mu12 + c1) * (2 * s12 + c2)) / ((mu11 + mu22 + c1) * (s11 + s22 + c2));
-      }
-    }
-  }
-  acc = wave_sum(acc); ssd = wave_sum(ssd); ssdq = wave_sum_u64(ssdq);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { red[wave] = acc; redq[wave] = q ? ssdq : (unsigned long long)__double_as_longlong(ssd); }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double* o = part + ((size_t)plane * gridDim.x + tile) * 2;
-    o[0] = (red[0] + red[1]) + (red[2] + red[3]);
-    if (q) {
-      o[1] = __longlong_as_double((long long)((redq[0] + redq[1]) + (redq[2] + redq[3])));
-    } else {
-      double s[4];
-      for (int w = 0; w < 4; ++w) s[w] = __longlong_as_double((long long)redq[w]);
-      o[1] = (s[0] + s[1]) + (s[2] + s[3]);
-    }
-  }
-}
-int image_metrics_tiles(int H, int W) {
-  return ((H - 10 + kSsimT - 1) / kSsimT) * ((W - 10 + kSsimT - 1) / kSsimT);
-}
-hipError_t launch_image_metrics(const float* a, const float* b, int planes, int H, int W, int quantize, float lo,
-                                float hi, float rng, double c1, double c2, const SsimWindow& win, double* part,
-                                hipStream_t st) {
-  if (H < 11 || W < 11 || planes < 1 || planes > 65535) return hipErrorInvalidValue;
-  const int tiles_x = (W - 10 + kSsimT - 1) / kSsimT;
-  hipLaunchKernelGGL(k_image_metrics, dim3((unsigned)image_metrics_tiles(H, W), (unsigned)planes), dim3(256), 0, st,
-                     a, b, H, W, quantize, lo, hi, rng, c1, c2, win, tiles_x, part);
-  return hipGetLastError();
-}
-
 // TimePredictor head (time_predictor.py:38-44): sum(relu(u)*mask) / sum(mask) per image
 __global__ __launch_bounds__(256) void k_masked_mean(const float* __restrict__ u,
                                                      const float* __restrict__ mask, long long n,
                                                      float* __restrict__ out) {
-  __shared__ double red[8];
+  __shared__ double red[4 * 2];
   const int b = blockIdx.x;
   double num = 0, den = 0;
   for (long long i = threadIdx.x; i < n; i += 256) {
@@ -856,15 +412,10 @@ __global__ __launch_bounds__(256) void k_masked_mean(const float* __restrict__ u
     num += (double)(fmaxf(u[(size_t)b * n + i], 0.f) * m);
     den += (double)m;
   }
-  num = wave_sum(num); den = wave_sum(den);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { red[wave * 2] = num; red[wave * 2 + 1] = den; }
+  block_park<RedSum>(num, red, 2, 0);
+  block_park<RedSum>(den, red, 2, 1);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    double a = 0, d = 0;
-    for (int w = 0; w < 4; ++w) { a += red[w * 2]; d += red[w * 2 + 1]; }
-    out[b] = (float)(a / d);
-  }
+  if (threadIdx.x == 0) out[b] = (float)(block_combine<RedSum, Serial>(red, 2, 0) / block_combine<RedSum, Serial>(red, 2, 1));
 }
 hipError_t launch_masked_mean(const float* u, const float* mask, int B, long long n, float* out,
                               hipStream_t st) {

@@ -1,0 +1,89 @@
+// dsx_reduce.h — the block reduction of the evaluation kernels, stated once (device only).  A workgroup is 256
+// threads = 4 wave64s: every wave folds its 64 lanes with a shuffle butterfly, lane 0 parks the wave's result in LDS,
+// and after one barrier the four results are combined.  Nothing here uses atomics, so the order of the additions is
+// fixed by the code alone and equal inputs give equal bits.  tests/golden/reduce_bits.npz records the outputs of every
+// kernel below; where an output is a double (the loss, the PSNR sums, SSIM / SSD) a changed order shows there, where it
+// is rounded to fp32 first (k_lpips_dist, k_masked_mean) a one-ulp change of the double sum mostly does not.
+//
+// For doubles and floats the ORDER is part of each kernel's result.  Two choices exist, and every kernel keeps its own:
+//   butterfly  kDown  offsets 32, 16, .. 1   every kernel but k_lpips_dist
+//              kUp    offsets 1, 2, .. 32    k_lpips_dist (its two fp32 norms and its double accumulator)
+//   combine    Pairwise  (r0 + r1) + (r2 + r3)   k_loss_partial, k_stitch_psnr, k_image_metrics, k_mix_range,
+//                                                k_lpips_minmax
+//              Serial    ((r0 + r1) + r2) + r3   k_masked_mean, k_lpips_dist, val_block_reduce
+// (min, max and integer sums do not depend on either; k_mix_range, k_lpips_minmax and val_block_reduce are listed for
+// completeness.)
+//
+// Use.  One value:      r = block_reduce<RedSum, Pairwise>(v, red)          red: 4 elements of LDS, r in every thread
+//       several values: block_park<Op>(v_j, red, n, j) for each slot j < n    red: 4 * n elements, [wave][slot]
+//                       __syncthreads()
+//                       block_combine<Op, Pairwise>(red, n, j)              in whichever thread writes slot j
+// so that n values cost one barrier and the combines spread over n threads.  A kernel that reduces twice through the
+// same array puts a barrier in front of the second parking (val_block_reduce: wave_reduce, barrier, wave_park, so
+// that the shuffles of the early waves overlap the wait for the late ones).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace dsx {
+
+struct RedSum {
+  template <class T> static __device__ __forceinline__ T op(T a, T b) { return a + b; }
+};
+struct RedMin {
+  static __device__ __forceinline__ double op(double a, double b) { return fmin(a, b); }
+  static __device__ __forceinline__ float op(float a, float b) { return fminf(a, b); }
+  static __device__ __forceinline__ unsigned op(unsigned a, unsigned b) { return min(a, b); }
+};
+struct RedMax {
+  static __device__ __forceinline__ double op(double a, double b) { return fmax(a, b); }
+  static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
+  static __device__ __forceinline__ unsigned op(unsigned a, unsigned b) { return max(a, b); }
+};
+
+enum WaveOrder { kDown, kUp };
+// all 64 lanes of the wave -> the same value in every lane
+template <class Op, WaveOrder kOrder = kDown, class T>
+__device__ __forceinline__ T wave_reduce(T v) {
+  if (kOrder == kDown) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = Op::op(v, __shfl_xor(v, o, 64));
+  } else {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) v = Op::op(v, __shfl_xor(v, o, 64));
+  }
+  return v;
+}
+
+// the four wave results r[w] = red[w * n + slot]
+struct Pairwise {
+  template <class Op, class T> static __device__ __forceinline__ T of(T r0, T r1, T r2, T r3) {
+    return Op::op(Op::op(r0, r1), Op::op(r2, r3));
+  }
+};
+struct Serial {
+  template <class Op, class T> static __device__ __forceinline__ T of(T r0, T r1, T r2, T r3) {
+    return Op::op(Op::op(Op::op(r0, r1), r2), r3);
+  }
+};
+
+// lane 0 of every wave parks the wave's (already reduced) value
+template <class T>
+__device__ __forceinline__ void wave_park(T v, T* red, int n = 1, int slot = 0) {
+  if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * n + slot] = v;
+}
+template <class Op, WaveOrder kOrder = kDown, class T>
+__device__ __forceinline__ void block_park(T v, T* red, int n = 1, int slot = 0) {
+  wave_park(wave_reduce<Op, kOrder>(v), red, n, slot);
+}
+template <class Op, class Combine, class T>
+__device__ __forceinline__ T block_combine(const T* red, int n = 1, int slot = 0) {
+  return Combine::template of<Op>(red[slot], red[n + slot], red[2 * n + slot], red[3 * n + slot]);
+}
+template <class Op, class Combine, WaveOrder kOrder = kDown, class T>
+__device__ __forceinline__ T block_reduce(T v, T* red) {
+  block_park<Op, kOrder>(v, red);
+  __syncthreads();
+  return block_combine<Op, Combine>(red);
+}
+
+}  // namespace dsx

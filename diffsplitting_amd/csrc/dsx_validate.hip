@@ -2,6 +2,7 @@
 // visuals to uint16 counts, exact integer statistics for the per-channel PSNR, and the numerators of the [0, 1] images
 // the loop writes.  Two launches: k_val_quantise, then k_val_finish, which reads the first launch's partial statistics.
 #include "dsx_kernels.h"
+#include "dsx_reduce.h"
 
 namespace dsx {
 
@@ -14,27 +15,20 @@ namespace dsx {
 // load and one 8-byte store per tensor under VEC).
 // ---------------------------------------------------------------------------
 struct ValStat { unsigned long long ssd; unsigned lo, hi, undef; };
-__device__ __forceinline__ ValStat val_block_reduce(ValStat s, unsigned long long (*red)[4]) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s.ssd += __shfl_xor(s.ssd, o, 64);
-    s.lo = min(s.lo, __shfl_xor(s.lo, o, 64));
-    s.hi = max(s.hi, __shfl_xor(s.hi, o, 64));
-    s.undef += __shfl_xor(s.undef, o, 64);
-  }
+struct ValRed { unsigned long long ssd[4]; unsigned lo[4], hi[4], undef[4]; };   // LDS: the four waves' results
+__device__ __forceinline__ ValStat val_block_reduce(ValStat s, ValRed& red) {
+  s.ssd = wave_reduce<RedSum>(s.ssd);
+  s.lo = wave_reduce<RedMin>(s.lo);
+  s.hi = wave_reduce<RedMax>(s.hi);
+  s.undef = wave_reduce<RedSum>(s.undef);
   __syncthreads();                         // `red` may still be read from the previous reduction
-  if ((threadIdx.x & 63) == 0) {
-    unsigned long long* r = red[threadIdx.x >> 6];
-    r[0] = s.ssd; r[1] = s.lo; r[2] = s.hi; r[3] = s.undef;
-  }
+  wave_park(s.ssd, red.ssd);
+  wave_park(s.lo, red.lo);
+  wave_park(s.hi, red.hi);
+  wave_park(s.undef, red.undef);
   __syncthreads();
-  ValStat t = {0ull, 65535u, 0u, 0u};
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    t.ssd += red[w][0]; t.lo = min(t.lo, (unsigned)red[w][1]); t.hi = max(t.hi, (unsigned)red[w][2]);
-    t.undef += (unsigned)red[w][3];
-  }
-  return t;                                // the same value in every thread
+  return {block_combine<RedSum, Serial>(red.ssd), block_combine<RedMin, Serial>(red.lo),
+          block_combine<RedMax, Serial>(red.hi), block_combine<RedSum, Serial>(red.undef)};   // in every thread
 }
 
 // x * std + mean in double, the product and the sum rounded separately (numpy: float32 array * float64 -> float64)
@@ -55,7 +49,7 @@ __device__ __forceinline__ unsigned val_cast_clamped(double v, unsigned& undef) 
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_val_quantise(const ValArgs a) {
-  __shared__ unsigned long long red[4][4];
+  __shared__ ValRed red;
   const long long HW = a.HW;
   const int plane = blockIdx.y, nT = a.B * a.C;
   const long long g0 = (long long)blockIdx.x * (kValChunk / 4) + threadIdx.x;
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(256) void k_val_quantise(const ValArgs a) {
 // plane share its chunks x, x + gridDim.x, ...
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ ValStat val_reduce_rows(const unsigned long long* part, long long r0, long long r1,
-                                                   unsigned long long (*red)[4]) {
+                                                   ValRed& red) {
   ValStat s = {0ull, 65535u, 0u, 0u};
   for (long long r = r0 + threadIdx.x; r < r1; r += 256) {
     const unsigned long long* row = part + r * 4;
@@ -137,7 +131,7 @@ __device__ __forceinline__ ValStat val_reduce_rows(const unsigned long long* par
 }
 // the undefined pixels alone, over many rows: the counter is 64 bits wide
 __device__ __forceinline__ unsigned long long val_sum_undefined(const unsigned long long* part, long long rows,
-                                                                unsigned long long (*red)[4]) {
+                                                                ValRed& red) {
   ValStat s = {0ull, 65535u, 0u, 0u};
   for (long long r = threadIdx.x; r < rows; r += 256) s.ssd += part[r * 4 + 3];
   return val_block_reduce(s, red).ssd;
@@ -145,7 +139,7 @@ __device__ __forceinline__ unsigned long long val_sum_undefined(const unsigned l
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_val_finish(const ValArgs a) {
-  __shared__ unsigned long long red[4][4];
+  __shared__ ValRed red;
   const long long HW = a.HW;
   const int plane = blockIdx.y, nT = a.B * a.C, nblk = a.nblk;
   const bool is_t = plane < nT;
