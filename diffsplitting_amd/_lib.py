@@ -89,6 +89,7 @@ SIGNATURES = {
     "dsx_q_sample": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _i, _i, _vp]),
     "dsx_loss_blocks": (_i, [_i, _i, _i]),
     "dsx_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dsx_attention": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "dsx_posterior_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _i, _vp, _vp,
                                 _vp, _vp]),
     "dsx_interp_start": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _u64, _u64, _vp, _vp]),

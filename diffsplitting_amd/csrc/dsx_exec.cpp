@@ -388,6 +388,41 @@ extern "C" int dsx_loss(const float* a, const float* b, int B, int C, int H, int
   return DSX_OK;
 }
 
+// ---- the fused attention kernel (dsx_attn.hip) on caller tensors: the planner's launch with the layout spelled out
+extern "C" int dsx_attention(const void* qkv, int ld, int q_col, int k_col, int v_col, void* out, int ldo, int storage,
+                             int B, int L, int C, int col_split, void* stream) {
+  if (!qkv || !out) return fail(DSX_ERR_INVALID, "attention: null argument");
+  if (storage < 0 || storage > 2) return fail(DSX_ERR_INVALID, "attention: storage kind %d (0 fp32, 1 bf16, 2 fp16)", storage);
+  if (!attn_supported(C, L))
+    return fail(DSX_ERR_INVALID, "attention: head dimension %d (8..1024, multiple of 8) with %d tokens is not supported", C, L);
+  if (B < 1) return fail(DSX_ERR_INVALID, "attention: B = %d", B);
+  const int es = storage == 0 ? 4 : 2, epu = 16 / es;          // element size, elements per 16-byte unit
+  if (q_col < 0 || k_col < 0 || v_col < 0 || q_col % epu || k_col % epu || v_col % epu)
+    return fail(DSX_ERR_INVALID, "attention: column offsets (%d, %d, %d) must be non-negative multiples of %d", q_col,
+                k_col, v_col, epu);
+  if (ld < 1 || ld % epu) return fail(DSX_ERR_INVALID, "attention: ld = %d is not a multiple of %d", ld, epu);
+  if ((int64_t)q_col + C > ld || (int64_t)k_col + C > ld || (int64_t)v_col + C > ld)
+    return fail(DSX_ERR_INVALID, "attention: columns (%d, %d, %d) + C = %d do not fit a row of ld = %d", q_col, k_col,
+                v_col, C, ld);
+  if (k_col < q_col || v_col < q_col)
+    return fail(DSX_ERR_INVALID, "attention: k and v must not start before q (offsets are taken relative to q)");
+  if (ldo % 4) return fail(DSX_ERR_INVALID, "attention: ldo = %d is not a multiple of 4", ldo);
+  if (ldo < C) return fail(DSX_ERR_INVALID, "attention: ldo = %d < C = %d", ldo, C);
+  if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 15))
+    return fail(DSX_ERR_INVALID, "attention: qkv and out must be 16-byte aligned");
+  if ((int64_t)L * ld * es >= ((int64_t)1 << 31))
+    return fail(DSX_ERR_INVALID, "attention: one image of %d rows of %d elements does not fit a 2 GiB buffer descriptor", L,
+                ld);
+  if ((int64_t)B * ((L + 31) / 32) * 2 > INT32_MAX) return fail(DSX_ERR_INVALID, "attention: too many query tiles");
+  AttnArgs a{};
+  const char* base = (const char*)qkv;
+  a.q = base + (size_t)q_col * es; a.k = base + (size_t)k_col * es; a.v = base + (size_t)v_col * es; a.ld = ld;
+  a.out = out; a.ldo = ldo; a.storage = storage;
+  a.B = B; a.L = L; a.C = C; a.div = sqrtf((float)C); a.inv_div = 1.0f / a.div;
+  HIP_TRY(launch_attn(a, col_split != 0, (hipStream_t)stream));
+  return DSX_OK;
+}
+
 // ---- caller-driven reverse sampling: one update with its intermediates, the start of interpolate
 extern "C" int dsx_posterior_step(const float* x, const float* net, int B, int C, int H, int W, const float* a,
                                   const float* b, const float* c1, const float* c2, const float* sigma,

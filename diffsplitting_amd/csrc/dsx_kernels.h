@@ -360,6 +360,11 @@ hipError_t launch_splitk_reduce(const SplitKReduceArgs& a, hipStream_t st);
 
 // fused single-head attention (dsx_attn.hip): out[b][i][:] = softmax_j(q_i . k_j / div) . v_j ; no L x L tensor in HBM.
 // q / k / v: token-major rows of `ld` elements (the three thirds of the qkv conv's output), out: rows of `ldo`.
+// The kernel reads all three through ONE buffer descriptor per image, based at q's first row of that image and
+// L * ld * ES bytes long: q, k and v must be column ranges of the same rows with k >= q and v >= q (their byte
+// offsets from q are taken as unsigned), each range inside the row, and L * ld * ES < 2^31.  Three separate
+// allocations cannot be expressed.  launch_attn checks alignment only; dsx_attention (dsx_exec.cpp) checks the rest
+// for caller tensors, the planner satisfies it by construction (ld = 3C, q first).
 struct AttnArgs {
   const void* q; const void* k; const void* v; int ld;
   void* out; int ldo;

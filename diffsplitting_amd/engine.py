@@ -610,6 +610,33 @@ def loss_per_sample(a, b, squared):
 
 
 # ---------------------------------------------------------------------------
+# the fused attention kernel on caller tensors (dsx_attention, include/dsx.h)
+# ---------------------------------------------------------------------------
+_STORAGE = {torch.float32: _lib.DTYPE_F32, torch.bfloat16: _lib.DTYPE_BF16, torch.float16: _lib.DTYPE_F16}
+
+
+def attention(qkv, q_col, k_col, v_col, B, L, Cn, out, col_split=False):
+    """``dsx_attention``: ``out[b*L + i, :Cn] = softmax_j(q_i . k_j / sqrt(Cn)) v_j`` per image, one launch of the
+    UNet's fused kernel.  ``qkv``: a contiguous 2-D CUDA tensor of at least ``B*L`` token rows (fp32, bf16 or fp16)
+    whose columns ``q_col`` / ``k_col`` / ``v_col`` .. ``+ Cn`` hold q, k and v; ``out``: a contiguous 2-D CUDA tensor
+    of the same type with at least ``B*L`` rows of at least ``Cn`` columns, written in place (columns past ``Cn`` and
+    rows past ``B*L`` are left untouched) and returned.  Nothing is converted or copied."""
+    for t, what in ((qkv, "qkv"), (out, "out")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise DsxError(f"{what} must be a CUDA tensor: attention runs on the MI355X only (no CPU fallback)")
+        if t.dim() != 2 or not t.is_contiguous():
+            raise DsxError(f"{what} must be a contiguous 2-D tensor (token rows), got {tuple(t.shape)}")
+    if qkv.dtype not in _STORAGE or out.dtype != qkv.dtype:
+        raise DsxError(f"qkv and out must share one of float32 / bfloat16 / float16, got {qkv.dtype} and {out.dtype}")
+    B, L, Cn = int(B), int(L), int(Cn)
+    if B < 1 or L < 1 or qkv.shape[0] < B * L or out.shape[0] < B * L:
+        raise DsxError(f"B * L = {B} * {L} token rows do not fit qkv ({qkv.shape[0]} rows) and out ({out.shape[0]})")
+    check(lib.dsx_attention(_dptr(qkv), qkv.shape[1], int(q_col), int(k_col), int(v_col), _dptr(out), out.shape[1],
+                            _STORAGE[qkv.dtype], B, L, Cn, 1 if col_split else 0, _stream_ptr()))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # caller-driven reverse sampling (dsx_posterior_step / dsx_interp_start, include/dsx.h)
 # ---------------------------------------------------------------------------
 def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, clip=False, z=None, seed=0, subsequence=0,

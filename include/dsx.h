@@ -286,6 +286,24 @@ int dsx_loss_blocks(int C, int H, int W);
 int dsx_loss(const float* a_dev, const float* b_dev, int B, int C, int H, int W, int squared,
              double* partial_dev, double* per_sample_dev, void* stream);
 
+/* --------------------------------------------------------------- attention
+ * dsx_attention: the UNet's fused single-head self-attention on caller tensors, exactly the launch the planner makes:
+ *   out[b][i][0..C) = sum_j softmax_j(q_i . k_j / sqrtf(C)) v_j     per image b, over that image's L tokens
+ * qkv_dev holds B * L token rows of ld elements; q, k and v are the column ranges [q_col, q_col + C), [k_col, ..),
+ * [v_col, ..) of the same rows.  One buffer, because the kernel reads all three through one buffer descriptor per
+ * image: based at q's first row of the image, L * ld * ES bytes long (ES: element size), which is what keeps rows past
+ * L and columns past C out of the result without a branch.  Hence k_col >= q_col and v_col >= q_col (offsets are
+ * taken relative to q), every range inside the row, and L * ld * ES < 2^31.
+ *   storage  : element type of qkv and out: 0 fp32, 1 bf16, 2 fp16 (DSX_DTYPE_*)
+ *   out_dev  : B * L rows of ldo elements (ldo >= C, ldo % 4 == 0); columns >= C are left untouched
+ *   col_split: 0 / 1, the planner's attn_cs knob: with 257..512 channels and at most 160 query tiles of 32 rows, two
+ *              workgroups share a tile, half of the output channels each
+ * C in 8..1024 and a multiple of 8; column offsets and ld multiples of the 16-byte unit (4 fp32 / 8 16-bit elements);
+ * both base pointers 16-byte aligned.  Anything else is refused with DSX_ERR_INVALID before any device work.  One
+ * launch on `stream`, nothing allocated or synchronised. */
+int dsx_attention(const void* qkv_dev, int ld, int q_col, int k_col, int v_col, void* out_dev, int ldo, int storage,
+                  int B, int L, int C, int col_split, void* stream);
+
 /* ------------------------------------------------------- validation report
  * dsx_val_report: what the training loop's validation block computes per item (split.py:174-241) on the NCHW fp32
  * visuals input (B, Cin, H, W), target and prediction (B, C, H, W), C <= DSX_VAL_MAX_CHANNELS, B * (C + Cin) <= 65535.

@@ -63,6 +63,8 @@ PLANS = {
     "ddpm_tiny_f16_min_grid1": ("ddpm_tiny", "f16", 3, 32, 48, dict(_NO_SPECIAL, DSX_MIN_GRID="1", DSX_WS="0")),
     "sr3_128_b1_f16_splitk": ("sr3_128", "f16", 1, 128, 128, {"DSX_MIN_GRID": "100000", "DSX_WS": "0"}),
     "sr3_128_b1_f16_many_chunk_ws": ("sr3_128", "f16", 1, 128, 128, _MANY_CHUNKS),
+    # the planner's knob -> col_split = 0 -> k_attn<*, 4, 1> at head dimension 512 (the default runs <*, 4, 2>)
+    "sr3_128_b1_bf16_attn_cs1": ("sr3_128", "bf16", 1, 128, 128, {"DSX_ATTN_CS": "1"}),
 }
 
 # every variant tag a checked launch may carry; a new kernel variant must be added here (and so get checked)
