@@ -44,6 +44,7 @@ LAYER_CONV, LAYER_ATTN, LAYER_FILM, LAYER_INPUT = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 TILING_TRIM, TILING_PAD, TILING_SHIFT = 0, 1, 2
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3
+PIX_U8, PIX_U16, PIX_U32, PIX_F32 = 0, 1, 2, 3
 
 _vp, _i, _i64, _u64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float
 _pi64, _pi32, _pf = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)
@@ -131,6 +132,14 @@ SIGNATURES = {
     "dsx_tileplan_pack_layout": (_i, [_vp, _i, _pi64, _pi64]),
     "dsx_tileplan_pack": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),
     "dsx_tileplan_paste_packed": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp]),
+    "dsx_tiff_open": (_i, [C.c_char_p, C.POINTER(_vp)]),
+    "dsx_tiff_info": (_i, [_vp, _pi64, C.POINTER(_i)]),
+    "dsx_tiff_read": (_i, [_vp, _i64, _i64, _vp, C.c_size_t]),
+    "dsx_tiff_close": (None, [_vp]),
+    "dsx_tiff_write": (_i, [C.c_char_p, _vp, _i64, _i64, _i64, _i, C.c_char_p, _i]),
+    "dsx_frames_to_f32": (_i, [_vp, _i, _i64, C.c_double, _vp, _vp]),
+    "dsx_order_stats_workspace_bytes": (C.c_size_t, [_i64, _i]),
+    "dsx_order_stats": (_i, [_vp, _vp, _i64, C.c_double, C.c_double, _pi64, _i, C.POINTER(C.c_double), _vp, _vp]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -8,7 +8,7 @@ OBJ=${DSX_OBJ:-_obj}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $DSX_EXTRA_FLAGS"
 mkdir -p $OBJ
 # every source of the library: kernels (*.hip) and host translation units (*.cpp, compiled as HIP too)
-SRCS="dsx_conv.hip dsx_ops.hip dsx_attn.hip dsx_lpips.hip dsx_resize.hip dsx_eval.hip dsx_steps.hip dsx_validate.hip dsx_model.cpp dsx_plan.cpp dsx_exec.cpp dsx_tiles.cpp dsx_lpips.cpp dsx_resize.cpp"
+SRCS="dsx_conv.hip dsx_ops.hip dsx_attn.hip dsx_lpips.hip dsx_resize.hip dsx_eval.hip dsx_steps.hip dsx_validate.hip dsx_select.hip dsx_model.cpp dsx_plan.cpp dsx_exec.cpp dsx_tiles.cpp dsx_lpips.cpp dsx_resize.cpp dsx_select.cpp dsx_tiff.cpp"
 # a changed flag set rebuilds everything
 if [ "$(cat $OBJ/.flags 2>/dev/null)" != "$FLAGS" ]; then rm -f $OBJ/*.o; echo "$FLAGS" > $OBJ/.flags; fi
 stale() {   # stale OBJECT FILE...: the object is missing or older than one of the files

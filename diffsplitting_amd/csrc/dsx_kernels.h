@@ -631,6 +631,23 @@ hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, int H, int 
 int mix_range_blocks(long long pixels);
 hipError_t launch_mix_range(const float* f0, const float* f1, long long pixels, const double norm[4], int n, double* part,
                             hipStream_t st);
+// dsx_select.hip.  One pass of the radix select behind dsx_order_stats: hist[1 << bits] (64-bit, zeroed by the caller)
+// += the digit (u >> shift) & (2^bits - 1) of every element whose key image u has u >> match_shift == prefix
+// (match_shift = 64: every element).  b == nullptr: single source.
+constexpr int kSelectDigitBits = 11;   // 5 passes of 11 bits and one of 9 cover the 64-bit image
+constexpr int kSelectBins = 1 << kSelectDigitBits;
+constexpr int kSelectMaxBlocks = 2048;
+struct SelectArgs {
+  const float* a; const float* b;
+  long long count;
+  double w0, w1;
+  unsigned long long prefix;
+  int shift, bits, match_shift;
+  unsigned long long* hist;
+};
+hipError_t launch_select_hist(const SelectArgs& s, hipStream_t st);
+// dst = (float)min(src, clip) for count uint8 (src_bytes 1) or uint16 (2) values; clip < 0: none
+hipError_t launch_widen(const void* src, int src_bytes, long long count, double clip, float* dst, hipStream_t st);
 // source of a paste: whole predicted tiles (count, C, ph, pw) of the sequence, or the gathered packed exchange buffer
 // [world][rank_stride] (valid regions [C][h][w] of rank q's tiles q, q + world, ... back to back; `off` = pixel offset
 // of each tile id inside its rank's run)

@@ -6,9 +6,12 @@ validation / tiled-prediction path on MI355X:
     torchrun --nproc-per-node 8 -m diffsplitting_amd.split -c <config> -p val -gpu 0,1,2,3,4,5,6,7
 
 The config file is consumed unchanged (JSON with // comments).  Frames come
-from ``--frames <file.npy>`` ((N,H,W,2) raw channels) or are synthesised when
-the config's data paths do not exist on this machine.  ``-p train`` is refused:
-the engine is inference-only.  ``--validate [--results DIR]`` runs the training
+from the config's own ``datasets.{train,val}.datapath`` stacks with
+``--datapath`` (``get_datasets``: the validation set normalised with the
+training stack's statistics, ``--norm-from val`` for users who hold no training
+data), from ``--frames <file.npy|.tif>`` ((N,H,W,2) raw channels), or are
+synthesised.  ``--out FILE`` (.npy / .tif) writes the stitched prediction in raw
+counts.  ``-p train`` is refused: the engine is inference-only.  ``--validate [--results DIR]`` runs the training
 loop's validation report instead (core/validation.py): ``# Validation # PSNR``
 of the first 19 non-tiled items, and with ``--results`` the three images per item.
 """
@@ -23,9 +26,84 @@ import torch
 
 from . import parallel
 from .core import logger as Logger
+from ._lib import DsxError
 from .data.split_dataset import DataLocation, SplitDataset, SplitDatasetTiledPred
 from .data.tiled_predict import TileExchange
 from .model import create_model
+
+
+def get_datasets(opt, tiled_pred=False, norm_from="train", device="cuda"):
+    """The reference's ``get_datasets(opt, tiled_pred)`` (split.py:30-71) -> (train_set, val_set): locations from
+    ``datasets.{train,val}.datapath.{ch0,ch1}``; ``patch_size``, ``max_qval``, ``upper_clip``, ``channel_weights``,
+    ``target_channel_idx`` and ``uncorrelated_channels`` read as there; the validation set normalised with the
+    TRAINING stack's statistics.  The training set is built with ``enable_transforms=False`` and without random
+    patching: this engine does not train, the set is there for its statistics only.  ``tiled_pred`` gives
+    ``SplitDatasetTiledPred`` with grid = patch // 2 over the validation stack's actual shape (the reference
+    hard-codes (10, 2048, 2048)).  ``norm_from="val"`` takes the statistics from the validation stack itself;
+    ``train_set`` is then None."""
+    ds = opt["datasets"]
+    patch_size = ds["patch_size"]
+    target_channel_idx = ds.get("target_channel_idx", None)
+    upper_clip = ds.get("upper_clip", None)
+    max_qval = ds["max_qval"]
+    channel_weights = ds.get("channel_weights", None)
+    data_type = (ds["train"] if norm_from == "train" else ds["train"] or ds["val"])["name"]
+    assert data_type in ["cifar10", "Hagen"]
+    if data_type == "cifar10":
+        raise DsxError("data_type 'cifar10' (the pickle loader of data/cifar10.py) is out of scope: Hagen .tif / .npy stacks only")
+    if norm_from not in ("train", "val"):
+        raise DsxError(f"norm_from = {norm_from!r}: 'train' or 'val'")
+    loc = lambda part: DataLocation(channelwise_fpath=(ds[part]["datapath"]["ch0"], ds[part]["datapath"]["ch1"]))
+    common = dict(target_channel_idx=target_channel_idx, max_qval=max_qval, upper_clip=bool(upper_clip),
+                  channel_weights=channel_weights, enable_transforms=False, random_patching=False,
+                  input_from_normalized_target=opt["model"]["which_model_G"] == "joint_indi", device=device)
+    train_set, nd = None, None
+    if norm_from == "train":
+        train_set = SplitDataset(data_type, loc("train"), patch_size, normalization_dict=None,
+                                 uncorrelated_channels=bool(ds["train"].get("uncorrelated_channels")), **common)
+        nd = train_set.get_normalization_dict()
+    if tiled_pred:
+        val_set = SplitDatasetTiledPred(data_type, loc("val"), patch_size, grid_size=patch_size // 2,
+                                        normalization_dict=nd, **common)
+    else:
+        val_set = SplitDataset(data_type, loc("val"), patch_size, normalization_dict=nd, **common)
+    return train_set, val_set
+
+
+def _read_frames(path):
+    """--frames: (N,H,W,2) raw channels from .npy or .tif, as fp32."""
+    if str(path).endswith((".tif", ".tiff")):
+        from .data.tiff import imread
+        frames = imread(path)
+        if frames.ndim != 4 or frames.shape[-1] != 2:
+            raise DsxError(f"--frames {path}: (N,H,W,2) expected, the file holds {frames.shape}")
+        return frames.astype(np.float32)
+    return np.load(path, allow_pickle=False).astype(np.float32)
+
+
+def _write_prediction(path, pred, val_set):
+    """--out: the stitched prediction (N,H,W,C), un-normalised to raw counts with the dataset's mean_target /
+    std_target, as .npy (N,H,W,C) float32 or as a .tif hyperstack of N * C float32 pages (frame-major)."""
+    nd = val_set.get_normalization_dict()
+    idx = val_set._target_channel_idx
+    mean, std = (np.asarray(nd[k], dtype=np.float64).reshape(-1) for k in ("mean_target", "std_target"))
+    if idx is not None:
+        mean, std = mean[idx:idx + 1], std[idx:idx + 1]
+    C_out = pred.shape[-1]
+    if mean.size != C_out:
+        raise DsxError(f"--out: the prediction has {C_out} channels, the dataset normalises {mean.size}")
+    mean_t = torch.as_tensor(mean, dtype=torch.float32, device=pred.device)
+    std_t = torch.as_tensor(std, dtype=torch.float32, device=pred.device)
+    raw = (pred * std_t + mean_t).cpu().numpy()
+    if str(path).endswith(".npy"):
+        np.save(path, raw)
+    elif str(path).endswith((".tif", ".tiff")):
+        from .data.tiff import imwrite
+        N, H, W, _ = raw.shape
+        desc = (f"ImageJ=1.11a\nimages={N * C_out}\nchannels={C_out}\nframes={N}\nhyperstack=true\nmode=grayscale\n")
+        imwrite(path, np.ascontiguousarray(raw.transpose(0, 3, 1, 2)).reshape(N * C_out, H, W), description=desc)
+    else:
+        raise DsxError(f"--out {path}: .npy or .tif")
 
 
 def main(argv=None):
@@ -36,7 +114,12 @@ def main(argv=None):
     ap.add_argument("-debug", "-d", action="store_true")
     ap.add_argument("-enable_wandb", action="store_true")
     ap.add_argument("-rootdir", type=str, default=".")
-    ap.add_argument("--frames", type=str, default=None, help=".npy with (N,H,W,2) raw channel frames")
+    ap.add_argument("--frames", type=str, default=None, help=".npy or .tif with (N,H,W,2) raw channel frames")
+    ap.add_argument("--datapath", action="store_true",
+                    help="read the frames from the config's datasets.{train,val}.datapath stacks (get_datasets)")
+    ap.add_argument("--norm-from", type=str, choices=["train", "val"], default="train",
+                    help="with --datapath: the stack whose statistics normalise the validation set")
+    ap.add_argument("--out", type=str, default=None, help="write the stitched prediction in raw counts (.npy / .tif)")
     ap.add_argument("--synthetic", type=str, default="2,512,512", help="N,H,W of synthetic frames")
     ap.add_argument("--steps", type=int, default=None, help="override beta_schedule.val.n_timestep")
     ap.add_argument("--batch-tiles", type=int, default=8)
@@ -50,6 +133,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.phase == "train":
         raise SystemExit("training is out of scope of the MI355X sampling engine; use -p val")
+    if args.datapath and args.frames:
+        raise SystemExit("--datapath and --frames both name the frames: give one")
+    if args.out and not args.out.endswith((".npy", ".tif", ".tiff")):
+        raise SystemExit("--out: a .npy or .tif file")
+    if args.out and args.validate:
+        raise SystemExit("--out writes the tiled prediction: not with --validate")
     n_ranks = args.gpus if args.gpus is not None else len(str(args.gpu_ids).split(","))
     if argv is None and parallel.needs_self_launch(n_ranks):
         # fresh child processes, started before anything here touches the GPU (never an exec after HIP init)
@@ -75,8 +164,15 @@ def main(argv=None):
     netG = diffusion.netG
     n_steps = args.steps or opt["model"]["beta_schedule"]["val"]["n_timestep"]
 
+    dsopt = opt["datasets"] or {}
+    which = opt["model"]["which_model_G"]
+    if args.datapath:
+        _, val_set = get_datasets(opt, tiled_pred=not args.validate, norm_from=args.norm_from, device=dev)
+        if args.validate:
+            return _run_validate(args, opt, diffusion, val_set, log)
+        return _predict(args, netG, val_set, n_steps, int(dsopt["patch_size"]), rank, world, dev, log)
     if args.frames:
-        frames = np.load(args.frames, allow_pickle=False).astype(np.float32)
+        frames = _read_frames(args.frames)
     else:
         n, h, w = (int(v) for v in args.synthetic.split(","))
         rng = np.random.default_rng(0)
@@ -85,11 +181,9 @@ def main(argv=None):
     # the validation dataset of split.get_datasets(opt, tiled_pred=True) (reference split.py:30-71) with the frames
     # resident on the GPU: quantile normalisation (compute_normalization_dict), ShiftBoundary tiling, normalised
     # tile batches cut by one HIP launch
-    dsopt = opt["datasets"] or {}
     patch = (dsopt["val"] or {}).get("patch_size") if dsopt.get("val") else None
     patch = int(patch or dsopt.get("patch_size") or 512)
     patch = min(patch, frames.shape[1], frames.shape[2])
-    which = opt["model"]["which_model_G"]
     val_set = SplitDatasetTiledPred("Hagen", DataLocation(arrays=(frames[..., 0], frames[..., 1])), patch,
                                     grid_size=patch // 2, target_channel_idx=dsopt.get("target_channel_idx"),
                                     max_qval=dsopt.get("max_qval") or 0.98, upper_clip=bool(dsopt.get("upper_clip")),
@@ -98,6 +192,11 @@ def main(argv=None):
                                     device=dev)
     if args.validate:
         return _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log)
+    return _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log)
+
+
+def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
+    """The tiled prediction of ``val_set`` over the ranks; rank 0 writes ``--out``.  Returns the stitched canvas."""
     plan = val_set.plan
     ids = parallel.shard_ids(plan.total, rank, world)
 
@@ -125,18 +224,25 @@ def main(argv=None):
                 log.info("channel %d: RangeInvariantPsnr %.2f +- %.2f dB (random-init weights unless a checkpoint "
                          "was given in path.resume_state)", c, ps[:, c].mean().item(),
                          ps[:, c].std().item() if ps.shape[0] > 1 else 0.0)
+        if args.out:
+            _write_prediction(args.out, pred, val_set)
+            log.info("prediction written to %s", args.out)
     return pred
 
 
 def _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log):
     """``--validate``: the non-tiled dataset of the same frames with the same normalisation (split.get_datasets without
     tiled_pred), the validation schedule, and ``core.validation.validate``.  Returns avg_psnr."""
-    from .core.validation import validate
     items = SplitDataset("Hagen", DataLocation(arrays=(frames[..., 0], frames[..., 1])), patch,
                          target_channel_idx=dsopt.get("target_channel_idx"), max_qval=dsopt.get("max_qval") or 0.98,
                          normalization_dict=val_set.get_normalization_dict(), upper_clip=bool(dsopt.get("upper_clip")),
                          channel_weights=dsopt.get("channel_weights"), enable_transforms=False, random_patching=False,
                          input_from_normalized_target=(which == "joint_indi"), device=dev)
+    return _run_validate(args, opt, diffusion, items, log)
+
+
+def _run_validate(args, opt, diffusion, items, log):
+    from .core.validation import validate
     if args.steps:
         diffusion.netG.set_new_noise_schedule(dict(opt["model"]["beta_schedule"]["val"], n_timestep=args.steps),
                                               diffusion.device)

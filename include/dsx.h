@@ -595,6 +595,52 @@ int dsx_tileplan_pack(dsx_tileplan* plan, const float* tiles_dev, int C, int wor
 int dsx_tileplan_paste_packed(dsx_tileplan* plan, const float* flat_all_dev, int C, int world, int64_t rank_stride_elems,
                               float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream);
 
+/* ------------------------------------------------- frame files: uncompressed TIFF / BigTIFF stacks (host only)
+ * Replaces imread(fpath, plugin='tifffile') of the Hagen loaders (data/split_dataset.py:76-91) for the files the
+ * reference's configs name, and writes the stitched prediction.  Works without a GPU.
+ * Read: classic TIFF (magic 42) and BigTIFF (43), both byte orders, an IFD chain of equally shaped pages, strips with
+ * any RowsPerStrip, Compression = 1, BitsPerSample 8 / 16 / 32 unsigned and 32-bit float, SamplesPerPixel 1..4 chunky,
+ * and ImageJ's contiguous stack (a single IFD whose ImageDescription starts with "ImageJ=" and carries "images=N",
+ * page 0's strips contiguous and the file long enough for N planes from StripOffsets[0]: how stacks past 4 GiB are
+ * stored).  Tiles, PlanarConfiguration = 2, any compression, pages of differing shape or type and other bit depths are
+ * refused, the message naming the tag's value.  Every offset and count of the file is checked against its size before
+ * use: a truncated or inconsistent file is DSX_ERR_INVALID with a message, never a short read.
+ * dsx_tiff_info: shape = {pages, H, W, samples}, *dtype = DSX_PIX_*.  dsx_tiff_read: pages [first_page, first_page +
+ * n_pages) into dst_host (capacity in bytes) in the host's byte order, page-major, rows top to bottom, samples
+ * interleaved. */
+enum { DSX_PIX_U8 = 0, DSX_PIX_U16 = 1, DSX_PIX_U32 = 2, DSX_PIX_F32 = 3 };
+typedef struct dsx_tiff dsx_tiff;
+int dsx_tiff_open(const char* path, dsx_tiff** out);
+int dsx_tiff_info(const dsx_tiff* h, int64_t shape[4], int* dtype);
+int dsx_tiff_read(dsx_tiff* h, int64_t first_page, int64_t n_pages, void* dst_host, size_t capacity);
+void dsx_tiff_close(dsx_tiff* h);
+/* data_host (pages, H, W) of DSX_PIX_U8 / U16 / F32, one sample per pixel -> little-endian uncompressed pages of one
+ * strip each, the pixel data of all pages back to back (readable as an ImageJ contiguous stack too).  description (may
+ * be NULL) becomes page 0's ImageDescription.  bigtiff: 0 classic (refused past 4 GiB), 1 BigTIFF, -1 BigTIFF only
+ * when the file passes 4 GiB. */
+int dsx_tiff_write(const char* path, const void* data_host, int64_t pages, int64_t H, int64_t W, int dtype,
+                   const char* description, int bigtiff);
+
+/* ------------------------------------------------- frame statistics on the device
+ * dst = (float)min(src, upper_clip) for `count` uint8 / uint16 values (src_dtype = DSX_PIX_U8 / DSX_PIX_U16;
+ * upper_clip < 0: no clip): the hard-coded data[data > 1993.0] = 1993.0 of _load_data_channelwise_fpath
+ * (data/split_dataset.py:80-82) and the widening to the fp32 the tile kernels read, applied to the stack as uploaded in
+ * its file width.  Asynchronous on `stream`. */
+int dsx_frames_to_f32(const void* src_dev, int src_dtype, int64_t count, double upper_clip, float* dst_dev, void* stream);
+/* Order statistics for np.quantile of compute_normalization_dict (data/split_dataset.py:58-64) without a sort: for each
+ * 0-based rank the rank-th smallest key over `count` elements, key = (double)a[i] (b_dev NULL) or
+ * (double)a[i]*w0 + (double)b[i]*w1 with both products and the sum rounded on their own (never an fma): numpy's
+ * t1*w0 + t2*w1 on float64 arrays.  Most-significant-digit radix select over the order-preserving integer image of the
+ * key: every pass reads the sources once and histograms one digit of the elements under the current prefix (LDS
+ * counters per workgroup, one 64-bit global atomic per non-empty bin); no per-element temporary.  The counts are
+ * integers: the result is exact and run-to-run identical.  Inputs must be finite (NaN: undefined).  1 <= count <= 2^40,
+ * 1 <= n_ranks <= 4096, ranks in [0, count) (host array, any order, repeats allowed).  workspace_dev holds
+ * dsx_order_stats_workspace_bytes(count, n_ranks) bytes.  out_host[n_ranks] is complete on return (the call
+ * synchronises the stream once per pass). */
+size_t dsx_order_stats_workspace_bytes(int64_t count, int n_ranks);
+int dsx_order_stats(const float* a_dev, const float* b_dev, int64_t count, double w0, double w1, const int64_t* ranks,
+                    int n_ranks, double* out_host, void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
