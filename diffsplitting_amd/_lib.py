@@ -100,6 +100,8 @@ SIGNATURES = {
     "dsx_tile_regions": (_i, [_pi64, _pi64, _pi64, _i, _pi32, _i64]),
     "dsx_tiles_gather": (_i, [_vp, _pi64, _pi64, _pi64, _pi64, _i64, _vp, _vp]),
     "dsx_tiles_gather_norm": (_i, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, _f, _f, C.POINTER(C.c_double), _i, _vp, _vp, _vp]),
+    "dsx_tiles_gather_norm_planes": (_i, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, _f, _f, C.c_double, C.c_double,
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp]),
     "dsx_tiles_gather_mix": (_i, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, C.POINTER(C.c_double), C.c_double,
                                   C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
     "dsx_mix_range_blocks": (_i, [_i64, _i]),

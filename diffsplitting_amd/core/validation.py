@@ -163,13 +163,15 @@ def _save_triple(res, b, stem):
             save_visual_l16(arr[b], f"{stem}_{name}.png")
 
 
-def validate(diffusion, val_set, n_items=19, batch=4, result_path=None, current_step=0):
+def validate(diffusion, val_set, n_items=19, batch=4, result_path=None, current_step=0, on_batch=None):
     """The validation block of the training loop for a loaded model: the first ``n_items`` items of ``val_set`` (a
     ``SplitDataset``; the reference's loop stops after 19), ``batch`` at a time, through ``tiles`` -> ``feed_data`` ->
     ``test(continuous=False)`` -> ``netG.last_full_batch`` -> ``validation_report``.  Returns
     ``(avg_psnr, {ch_idx: [per item]})`` with avg_psnr = mean over the channel keys of the mean over the items.  With
-    ``result_path`` the three images of item idx (from 1) go to ``<result_path>/<current_step>_<idx>_{target,input,pred}.png``."""
-    n = min(int(n_items), len(val_set))
+    ``result_path`` the three images of item idx (from 1) go to ``<result_path>/<current_step>_<idx>_{target,input,pred}.png``.
+    ``n_items=None``: every item.  ``on_batch(first_item, prediction)`` is called with each batch's normalised
+    prediction (B, C, H, W), still on the device."""
+    n = len(val_set) if n_items is None else min(int(n_items), len(val_set))
     if n < 1:
         raise DsxError("validate: no items")
     if result_path is not None:
@@ -184,6 +186,8 @@ def validate(diffusion, val_set, n_items=19, batch=4, result_path=None, current_
         res = validation_report(diffusion.data["input"], diffusion.data["target"], pred.contiguous(), nd,
                                 visuals=result_path is not None)
         undefined += res.undefined
+        if on_batch is not None:
+            on_batch(i0, pred)
         for ch, vals in group_psnr(res).items():
             psnr_values.setdefault(ch, []).extend(vals)
         if result_path is not None:

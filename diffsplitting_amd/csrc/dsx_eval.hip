@@ -76,6 +76,56 @@ hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, int H, int
   return hipGetLastError();
 }
 
+// The same item for frames with colour planes, (N, Cc, H, W) per stack (SplitDataset on data_type 'cifar10',
+// data/split_dataset.py:248-272 with patch.ndim == 3): plane c of stack s is target channel s * Cc + c with its own
+// statistics, the input keeps the Cc planes.  A streaming kernel: workgroup (x, c, k) owns a strided share of plane c of
+// item k, so the plane and its four statistics are uniform in the workgroup and consecutive threads read and write
+// consecutive x.  The arithmetic per element is k_tiles_gather_norm's without from_norm_target.
+struct GatherPlanesArgs {
+  const float* f0; const float* f1;
+  int Cc, H, W, ph, pw;
+  const int* starts;       // dev [..][3] = (frame, y, x), indexed by tile id
+  TileSeq seq;
+  float w0, w1;
+  double mean_inp, std_inp;
+  double mt[2 * kPlanesMaxC], st[2 * kPlanesMaxC];
+  float* tin;              // (count, Cc, ph, pw)
+  float* ttar;             // (count, 2 Cc, ph, pw)
+};
+__global__ void k_tiles_gather_norm_planes(const GatherPlanesArgs a) {
+  const long long k = blockIdx.z, t = a.seq.first + k * a.seq.stride;
+  const int c = blockIdx.y;
+  const int n = a.starts[t * 3], y0 = a.starts[t * 3 + 1], x0 = a.starts[t * 3 + 2];
+  const int total = a.ph * a.pw;
+  const double mt0 = a.mt[c], st0 = a.st[c], mt1 = a.mt[a.Cc + c], st1 = a.st[a.Cc + c];
+  const size_t plane = ((size_t)n * a.Cc + c) * a.H;
+  float* tin = a.tin + ((size_t)k * a.Cc + c) * total;
+  float* tar0 = a.ttar + ((size_t)k * 2 * a.Cc + c) * total;
+  float* tar1 = tar0 + (size_t)a.Cc * total;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int y = i / a.pw, x = i % a.pw;
+    const size_t src = (plane + (y0 + y)) * a.W + (x0 + x);
+    const float p0 = a.f0[src], p1 = a.f1[src];
+    tar0[i] = (float)(((double)p0 - mt0) / st0);
+    tar1[i] = (float)(((double)p1 - mt1) / st1);
+    tin[i] = (float)(((double)__fadd_rn(__fmul_rn(a.w0, p0), __fmul_rn(a.w1, p1)) - a.mean_inp) / a.std_inp);
+  }
+}
+hipError_t launch_tiles_gather_norm_planes(const float* f0, const float* f1, int Cc, int H, int W, int ph, int pw,
+                                           const int* starts, TileSeq seq, float w0, float w1, double mean_inp,
+                                           double std_inp, const double* mean_target, const double* std_target,
+                                           float* tin, float* ttar, hipStream_t st) {
+  if (Cc < 1 || Cc > kPlanesMaxC || seq.count < 1 || seq.count > 65535) return hipErrorInvalidValue;
+  GatherPlanesArgs a{};
+  a.f0 = f0; a.f1 = f1; a.Cc = Cc; a.H = H; a.W = W; a.ph = ph; a.pw = pw; a.starts = starts; a.seq = seq;
+  a.w0 = w0; a.w1 = w1; a.mean_inp = mean_inp; a.std_inp = std_inp; a.tin = tin; a.ttar = ttar;
+  for (int c = 0; c < 2 * Cc; ++c) { a.mt[c] = mean_target[c]; a.st[c] = std_target[c]; }
+  int gx = (int)(((long long)ph * pw + 255) / 256);
+  if (gx > 64) gx = 64;
+  hipLaunchKernelGGL(k_tiles_gather_norm_planes, dim3((unsigned)gx, (unsigned)Cc, (unsigned)seq.count), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 // (mul_f / add_f / mul_d / add_d, one IEEE operation each, live in dsx_kernels.h)
 // The mixed inputs of the TimePredictor evaluation (notebooks/EvaluateJointIndiIterative.ipynb cells 40/43,
 // time_prediction_evaluation.ipynb cell 4) cut, normalised, mixed and min-max-normalised in one pass; the op list is

@@ -617,6 +617,13 @@ hipError_t launch_tiles_gather(const float* frames, int H, int W, int ph, int pw
 hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
                                     TileSeq seq, float w0, float w1, const double norm[6], int from_norm_target,
                                     float* tin, float* ttar, hipStream_t st);
+// the same for frames with colour planes: stacks (N, Cc, H, W), tin (count, Cc, ph, pw), ttar (count, 2 Cc, ph, pw),
+// one mean / std per target plane (2 Cc of each); 1 <= Cc <= kPlanesMaxC, 1 <= seq.count <= 65535 (grid z)
+constexpr int kPlanesMaxC = 8;
+hipError_t launch_tiles_gather_norm_planes(const float* f0, const float* f1, int Cc, int H, int W, int ph, int pw,
+                                           const int* starts, TileSeq seq, float w0, float w1, double mean_inp,
+                                           double std_inp, const double* mean_target, const double* std_target,
+                                           float* tin, float* ttar, hipStream_t st);
 // crop + target normalisation + the two mixed inputs of the TimePredictor evaluation and their min-max-normalised
 // classifier views, fused (op list: include/dsx.h, dsx_tiles_gather_mix).  norm = {mean_t0, std_t0, mean_t1, std_t1};
 // w0 = (float)(1 - t), w1 = (float)t; lo / rng = (float)lo, (float)(hi - lo) of the table rows of the two channels.

@@ -282,6 +282,52 @@ extern "C" int dsx_tiles_gather_norm(const float* frames0, const float* frames1,
   return DSX_OK;
 }
 
+// the same for frames with colour planes (data_type 'cifar10'): every argument is checked on the host, on the int64
+// values, before anything is uploaded or launched
+extern "C" int dsx_tiles_gather_norm_planes(const float* frames0, const float* frames1, const int64_t data_shape[4],
+                                            const int64_t patch_hw[2], const int64_t* patch_start, const int64_t* tile_ids,
+                                            int64_t count, float w0, float w1, double mean_input, double std_input,
+                                            const double* mean_target, const double* std_target, float* tiles_in,
+                                            float* tiles_target, void* stream) {
+  if (!frames0 || !frames1 || !data_shape || !patch_hw || !patch_start || !mean_target || !std_target || !tiles_in ||
+      !tiles_target)
+    return fail(DSX_ERR_INVALID, "gather_norm_planes: null argument");
+  const int64_t N = data_shape[0], Cc = data_shape[1], H = data_shape[2], W = data_shape[3], ph = patch_hw[0], pw = patch_hw[1];
+  if (Cc < 1 || Cc > kPlanesMaxC)
+    return fail(DSX_ERR_INVALID, "gather_norm_planes: %lld colour planes, must be in 1..%d", (long long)Cc, kPlanesMaxC);
+  if (N < 1 || H < 1 || W < 1 || N > INT32_MAX || H > INT32_MAX || W > INT32_MAX)
+    return fail(DSX_ERR_INVALID, "gather_norm_planes: bad frame shape (%lld, %lld, %lld, %lld)", (long long)N, (long long)Cc,
+                (long long)H, (long long)W);
+  if (ph < 1 || pw < 1 || ph > H || pw > W)
+    return fail(DSX_ERR_INVALID, "gather_norm_planes: patch %lld x %lld does not fit the %lld x %lld frames", (long long)ph,
+                (long long)pw, (long long)H, (long long)W);
+  if (ph * pw > INT32_MAX) return fail(DSX_ERR_INVALID, "gather_norm_planes: patch too large");
+  if (!std::isfinite(mean_input) || !std::isfinite(std_input) || std_input == 0.0)
+    return fail(DSX_ERR_INVALID, "gather_norm_planes: mean_input / std_input must be finite with non-zero std");
+  for (int c = 0; c < 2 * Cc; ++c)
+    if (!std::isfinite(mean_target[c]) || !std::isfinite(std_target[c]) || std_target[c] == 0.0)
+      return fail(DSX_ERR_INVALID, "gather_norm_planes: statistics of target plane %d must be finite with non-zero std", c);
+  if (count < 0 || count > 65535)
+    return fail(DSX_ERR_INVALID, "gather_norm_planes: count = %lld, at most 65535 items per call", (long long)count);
+  if (count == 0) return DSX_OK;
+  std::vector<int> starts((size_t)count * 3);
+  for (int64_t i = 0; i < count; ++i) {
+    const int64_t id = tile_ids ? tile_ids[i] : i;
+    if (id < 0) return fail(DSX_ERR_INVALID, "gather_norm_planes: negative tile id");
+    const int64_t n = patch_start[id * 3], y = patch_start[id * 3 + 1], x = patch_start[id * 3 + 2];
+    if (n < 0 || n >= N || y < 0 || y > H - ph || x < 0 || x > W - pw)
+      return fail(DSX_ERR_INVALID, "gather_norm_planes: item %lld at (%lld, %lld, %lld) lies outside the frames", (long long)i,
+                  (long long)n, (long long)y, (long long)x);
+    starts[i * 3] = (int)n; starts[i * 3 + 1] = (int)y; starts[i * 3 + 2] = (int)x;
+  }
+  DevBuf d;
+  HIP_TRY(d.upload(starts.data(), starts.size() * 4));
+  HIP_TRY(launch_tiles_gather_norm_planes(frames0, frames1, (int)Cc, (int)H, (int)W, (int)ph, (int)pw, (const int*)d.p,
+                                          TileSeq{0, 1, count}, w0, w1, mean_input, std_input, mean_target, std_target,
+                                          tiles_in, tiles_target, (hipStream_t)stream));
+  return DSX_OK;   // ~DevBuf waits for the launch
+}
+
 // ---- mixed-input evaluation (the TimePredictor's inputs): host-side argument checks shared by both gather_mix forms
 namespace {
 static int norm4_ok(const double norm[4]) {

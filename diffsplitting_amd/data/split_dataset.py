@@ -4,14 +4,18 @@ computed on the device, and â€” what the tiled-prediction path actually wants â€
 cut by one HIP launch (``tiles(ids)`` -> dsx_tiles_gather_norm) instead of one host crop + host->device copy per
 tile through a DataLoader(batch_size = 1) (data/__init__.py:16-18).
 
-Not available here (and refused loudly): ``enable_transforms`` (albumentations) and ``data_type='cifar10'`` (its
-pickle loader).  ``.tif`` stacks are read by the library's own reader (data/tiff.py: uncompressed TIFF / BigTIFF);
-uint8 / uint16 stacks go to the device in their file width and are clipped and widened there (dsx_frames_to_f32).
-Parity: the arithmetic of ``__getitem__`` is bit-exact against a numpy restatement of :237-278; the quantile of
+Not available here (and refused loudly): ``enable_transforms`` (albumentations).  ``.tif`` stacks are read by the
+library's own reader (data/tiff.py: uncompressed TIFF / BigTIFF); uint8 / uint16 stacks go to the device in their file
+width and are clipped and widened there (dsx_frames_to_f32).  ``data_type='cifar10'`` reads its pickle batches with
+data/cifar10.py; its frames carry colour planes, (N, Cc, H, W) per class with Cc in 1..8 (also accepted through
+``DataLocation(arrays=...)``), the items are {'input': (Cc, p, p), 'target': (2 Cc, p, p)} and a batch of them is one
+launch of dsx_tiles_gather_norm_planes.  Grey (N, H, W) frames take the calls they always took.
+Parity: the Hagen arithmetic of ``__getitem__`` is bit-exact against a numpy restatement of :237-278; the quantile of
 ``compute_normalization_dict`` is numpy's published linear-interpolation definition (checked against
-``numpy.quantile``).  The reference module itself cannot be imported (albumentations / skimage are absent), so there
-is no fixture generated by its own code: *parity unpinned* beyond the reference's known-answer test
-(tests/test_tiling_setup.py: identity normalisation, stitch(tiles(arange)) == arange), which passes through here.
+``numpy.quantile``).  With empty stand-ins for albumentations / skimage the reference module imports, and its own
+``SplitDataset('cifar10', ...)`` wrote tests/golden/cifar_items.npz (tools/gen_cifar_golden.py): loader, normalisation
+dict and items are pinned bit for bit by the reference's code.  The Hagen items have no such fixture (beyond the
+reference's known-answer test, tests/test_tiling_setup.py: identity normalisation, stitch(tiles(arange)) == arange).
 """
 import ctypes as C
 import os
@@ -47,6 +51,7 @@ def _read(path):
     raise DsxError(f"unsupported frame file {path} (.npy, .tif)")
 
 
+MAX_PLANES = 8                                                      # colour planes per stack: half of VAL_MAX_CHANNELS
 UPPER_CLIP = 1993.0                                                 # the reference's hard-coded upper clip (:80-82)
 _NARROW = (np.dtype(np.uint8), np.dtype(np.uint16))                 # uploaded as they are, widened on the device
 
@@ -54,11 +59,15 @@ _NARROW = (np.dtype(np.uint8), np.dtype(np.uint16))                 # uploaded a
 def _load(data_type, dataloc):
     """-> ({0: frames of channel 0 (N,H,W), 1: frames of channel 1}, clip).  ``clip`` is the upper clip that is still
     to be applied -- by dsx_frames_to_f32, on the device -- to channelwise uint8 / uint16 stacks, which keep their
-    dtype; None when the frames are final."""
-    if data_type == "cifar10":
-        raise DsxError("the cifar10 pickle loader (data/cifar10.py) is out of scope; pass arrays")
+    dtype; None when the frames are final.  'cifar10': (n_i, 3, 32, 32) uint8 per class, labels 1 and 7 (:20-22)."""
     if len(dataloc.arrays):
         return {0: np.asarray(dataloc.arrays[0]), 1: np.asarray(dataloc.arrays[1])}, None
+    if data_type == "cifar10":
+        if not dataloc.directory:
+            raise DsxError("data_type 'cifar10' reads a directory of batch files: DataLocation(directory=...) or arrays")
+        from .cifar10 import load_train_val_data
+        data = load_train_val_data(dataloc.directory, [1, 7])
+        return {0: data[0], 1: data[1]}, None
     if dataloc.fpath:
         data = _read(dataloc.fpath)                                 # (N,H,W,2), :85-91: no clip
         if data.ndim != 4 or data.shape[-1] < 2:
@@ -86,8 +95,8 @@ def load_data(data_type, dataloc):
 
 
 def frames_to_device(frames, dev, clip=None):
-    """(N,H,W) host frames -> contiguous fp32 CUDA tensor.  uint8 / uint16 frames are uploaded in their own width and
-    widened (and clipped at ``clip``) by dsx_frames_to_f32; the values equal the host conversion
+    """(N,H,W) or (N,Cc,H,W) host frames -> contiguous fp32 CUDA tensor.  uint8 / uint16 frames are uploaded in their own
+    width and widened (and clipped at ``clip``) by dsx_frames_to_f32; the values equal the host conversion
     ``np.minimum(frames, clip).astype(np.float32)`` bit for bit (every uint16 is an fp32)."""
     frames = np.asarray(frames)
     if frames.dtype not in _NARROW or frames.size == 0 or torch.device(dev).type != "cuda":
@@ -193,7 +202,9 @@ def table_rows(table, mixing_t):
 
 
 class SplitDataset:
-    """Constructor arguments of the reference (:94-103).  Frames live on the GPU as two (N,H,W) fp32 tensors."""
+    """Constructor arguments of the reference (:94-103).  Frames live on the GPU as two fp32 tensors, (N,H,W) or, with
+    colour planes, (N,Cc,H,W)."""
+    _COLOUR_REFUSAL = None                                          # subclasses that are grey-only say why
 
     def __init__(self, data_type, data_location, patch_size, target_channel_idx=None, random_patching=False,
                  enable_transforms=False, max_qval=0.98, normalization_dict=None, uncorrelated_channels=False,
@@ -206,6 +217,7 @@ class SplitDataset:
         self._channel_weights = channel_weights if channel_weights is not None else [1, 1]
         self._input_from_normalized_target = input_from_normalized_target
         data, clip = _load(data_type, data_location)
+        self._planes = self._check_frames(data)                     # None: grey (N,H,W) frames
         self._frameN = min(len(data[0]), len(data[1]))
         self._target_channel_idx = target_channel_idx
         self._random_patching = random_patching
@@ -230,6 +242,28 @@ class SplitDataset:
         self._target1_max = normalization_dict.get("target1_max")
         self._input_max = normalization_dict.get("input_max")
         self._data_shape = tuple(self._dev[0].shape)
+        if self._planes and not self._mean_target.size == self._std_target.size == 2 * self._planes:
+            raise DsxError(f"frames with {self._planes} colour planes need {2 * self._planes} mean_target / std_target "
+                           f"values (one per target plane), got {self._mean_target.size} / {self._std_target.size}")
+
+    def _check_frames(self, data):
+        """The colour-plane count Cc of (N,Cc,H,W) frames, None for (N,H,W) ones; every refusal that concerns the
+        frames' shape, on the host arrays (nothing is on the device yet)."""
+        a, b = data[0], data[1]
+        if a.ndim != b.ndim or a.shape[1:] != b.shape[1:] or a.ndim not in (3, 4):
+            raise DsxError(f"the two channels must hold (N,H,W) or (N,Cc,H,W) frames of one shape, got {a.shape} and {b.shape}")
+        if a.ndim == 3:
+            return None
+        planes = a.shape[1]
+        if not 1 <= planes <= MAX_PLANES:
+            raise DsxError(f"(N,Cc,H,W) frames with Cc = {planes} colour planes: 1..{MAX_PLANES}")
+        if self._COLOUR_REFUSAL:
+            raise DsxError(f"{type(self).__name__} on frames with colour planes {a.shape}: {self._COLOUR_REFUSAL}")
+        if self._input_from_normalized_target and planes > 1:
+            raise DsxError("input_from_normalized_target with colour planes: the reference mixes target[0:1] and "
+                           "target[1:2], which are planes 0 and 1 of the FIRST image once an image has more than one "
+                           "plane -- a grey-data assumption (joint_indi); no configuration pairs it with colour data")
+        return planes
 
     def get_normalization_dict(self):                               # :185-194
         return {"mean_input": self._mean_inp, "std_input": self._std_inp, "mean_target": self._mean_target,
@@ -279,17 +313,46 @@ class SplitDataset:
         CUDA tensors, normalised exactly as ``__getitem__`` does, in one HIP launch."""
         _lib.require_gpu()
         loc = np.ascontiguousarray(np.asarray(locations, dtype=np.int64).reshape(-1, 3))
+        if self._planes and not self._input_from_normalized_target:
+            return self._plane_tiles_at(loc)
         b, p = loc.shape[0], self._patch_size
         dev = self._dev[0].device
         tin = torch.empty((b, 1, p, p), dtype=torch.float32, device=dev)
         ttar = torch.empty((b, 2, p, p), dtype=torch.float32, device=dev)
         i64 = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+        shape3 = (self._data_shape[0],) + self._data_shape[-2:]      # (N,1,H,W) frames are (N,H,W) frames
         check(lib.dsx_tiles_gather_norm(C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()),
-                                        i64(self._data_shape), i64((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        i64(shape3), i64((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
                                         None, b, float(self._channel_weights[0]), float(self._channel_weights[1]),
                                         self._norm6(), 1 if self._input_from_normalized_target else 0,
                                         C.c_void_p(tin.data_ptr()), C.c_void_p(ttar.data_ptr()),
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if self._target_channel_idx is not None:
+            ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
+        return {"input": tin, "target": ttar}
+
+    PLANE_ITEMS_PER_CALL = 65535                                    # dsx_tiles_gather_norm_planes' limit
+
+    def _plane_tiles_at(self, loc):
+        """``tiles_at`` for (N,Cc,H,W) frames -> {'input': (b,Cc,p,p), 'target': (b,2Cc,p,p)}: one launch of
+        dsx_tiles_gather_norm_planes per 65535 items."""
+        b, p, cc = loc.shape[0], self._patch_size, self._planes
+        dev = self._dev[0].device
+        tin = torch.empty((b, cc, p, p), dtype=torch.float32, device=dev)
+        ttar = torch.empty((b, 2 * cc, p, p), dtype=torch.float32, device=dev)
+        pd = C.POINTER(C.c_double)
+        mt = np.ascontiguousarray(self._mean_target.reshape(-1), dtype=np.float64)
+        st = np.ascontiguousarray(self._std_target.reshape(-1), dtype=np.float64)
+        shape, patch = (C.c_int64 * 4)(*[int(x) for x in self._data_shape]), (C.c_int64 * 2)(p, p)
+        with torch.cuda.device(dev):
+            for i0 in range(0, b, self.PLANE_ITEMS_PER_CALL):
+                part = np.ascontiguousarray(loc[i0:i0 + self.PLANE_ITEMS_PER_CALL])
+                check(lib.dsx_tiles_gather_norm_planes(
+                    C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()), shape, patch,
+                    part.ctypes.data_as(C.POINTER(C.c_int64)), None, part.shape[0], float(self._channel_weights[0]),
+                    float(self._channel_weights[1]), float(self._mean_inp), float(self._std_inp), mt.ctypes.data_as(pd),
+                    st.ctypes.data_as(pd), C.c_void_p(tin[i0:].data_ptr()), C.c_void_p(ttar[i0:].data_ptr()),
+                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         if self._target_channel_idx is not None:
             ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
         return {"input": tin, "target": ttar}
@@ -311,6 +374,11 @@ class SplitDataset:
         mt, st = self._mean_target.reshape(-1), self._std_target.reshape(-1)
         return (C.c_double * 4)(float(mt[0]), float(st[0]), float(mt[-1]), float(st[-1]))
 
+    def _grey_only(self, what):
+        if self._planes:
+            raise DsxError(f"{what} on frames with colour planes {self._data_shape}: the mixed-input kernels "
+                           "(dsx_tiles_gather_mix) take two grey channels")
+
     def _mixed_new(self, count, lohi, want):
         p, dev = self._patch_size, self._dev[0].device
         want = tuple(want) if want is not None else ("target", "mix") + (("cls",) if lohi is not None else ())
@@ -326,6 +394,7 @@ class SplitDataset:
         """``locations``: (b, 3) (frame, y, x) corners -> {'target', 'mix', 'cls'} (b, 2, p, p) CUDA tensors in one HIP
         launch (op list: include/dsx.h, dsx_tiles_gather_mix).  ``lohi`` = (lo0, hi0, lo1, hi1), the (min, max) rows of
         the range table that normalise the two mix channels for the classifier; without it there is no 'cls'."""
+        self._grey_only("mixed_tiles_at")
         _lib.require_gpu()
         loc = np.ascontiguousarray(np.asarray(locations, dtype=np.int64).reshape(-1, 3))
         b, p = loc.shape[0], self._patch_size
@@ -343,6 +412,7 @@ class SplitDataset:
         t0*(1-t) + t1*t for indi1, channel 1 = t1*(1-t) + t0*t for indi2) and, with ``table`` (what
         ``compute_input_normalization_dict`` returns), 'cls': the two mix channels min-max-normalised for the
         classifier with the rows int((1-t)*n) and int(t*n) (normalize_indi1/2; ``int`` truncates, as there)."""
+        self._grey_only("mixed_tiles")
         if self._uncorrelated_channels:
             raise DsxError("uncorrelated_channels draws a second random frame per item: training-time only")
         return self.mixed_tiles_at([self._get_location(int(i)) for i in indices], mixing_t, table_rows(table, mixing_t), want)
@@ -355,6 +425,7 @@ class SplitDataset:
 
 class SplitDatasetTiledPred(SplitDataset):
     """data/split_dataset_tiledpred.py:9-32: the dataset whose index is a tile of the ShiftBoundary tiling."""
+    _COLOUR_REFUSAL = "the tile plan (TilePlan, TileIndexManager) is three-dimensional, (N,H,W); colour items are not tiled"
 
     def __init__(self, *args, **kwargs):
         grid_size = kwargs.pop("grid_size", None)

@@ -63,6 +63,7 @@ class TimePredictorDataset(SplitDataset):
     The item is the float32 chain of include/dsx.h (dsx_tiles_gather_mix, channel 1).  That is the reference's own
     arithmetic under numpy 1.x (its environment); under numpy 2 ``img - np.float64(...)`` promotes and the reference's
     normalisation step runs in float64 -- the engine returns the float32 chain in both cases."""
+    _COLOUR_REFUSAL = "the TimePredictor's mixed inputs (dsx_mix_range, dsx_tiles_gather_mix) take two grey channels"
 
     def __init__(self, *args, **kwargs):
         kwargs.pop("step_size", None)                                # accepted and unused, as in the reference (:26-29)

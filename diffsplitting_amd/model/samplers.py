@@ -498,8 +498,8 @@ class InDISampler(_SamplerBase):
         x_start, x_end = x_in["target"], x_in["input"]
         self._need_cuda(x_start, x_end)
         assert self.conditional is False
-        if x_end.shape[1] * self.out_channel != x_start.shape[1]:
-            raise DsxError("input has {} channels x out_channel {} != target's {}".format(
+        if x_end.shape[1] * self._copies(x_end) != x_start.shape[1]:
+            raise DsxError("input has {} channels, repeated to out_channel {} != target's {}".format(
                 x_end.shape[1], self.out_channel, x_start.shape[1]))
         t_float = self.sample_t(x_start.shape[0], "cpu") if t is None else t.reshape(-1).to(torch.float32)
         assert 0 < t_float.min(), "t > 0"
@@ -547,9 +547,19 @@ class InDISampler(_SamplerBase):
         return engine.posterior_step(x_t, x_0, col(c1), col(c2), col(sg), predict_eps=False, z=z, seed=seed,
                                      x_out=torch.empty_like(x_t))[2]
 
+    def _copies(self, x_in):
+        """How often the input is repeated along the channels: to ``out_channel`` channels in all.  indi.py:80,157
+        repeat ``out_channel`` times, which is the same for the one-channel inputs the reference runs on; on a colour
+        input (3 planes, CIFAR's C1: UNet 6 -> 6, target 6 planes) that literal count gives 18 channels and the
+        reference stops in its first conv with a shape error."""
+        cin = x_in.shape[1]
+        if self.out_channel % cin != 0:
+            raise DsxError("out_channel {} is no multiple of the input's {} channels".format(self.out_channel, cin))
+        return self.out_channel // cin
+
     def _start(self, x_in, t_float_start):
         dev = x_in.device
-        x_in = torch.cat([x_in.float()] * self.out_channel, dim=1)   # indi.py:80
+        x_in = torch.cat([x_in.float()] * self._copies(x_in), dim=1)   # indi.py:80
         scale = (self.e * torch.Tensor([t_float_start])).to(dev)     # get_t_times_e, indi.py:106-110
         return x_in + self._draw(x_in.shape, dev) * scale            # indi.py:82
 
@@ -575,7 +585,7 @@ class InDISampler(_SamplerBase):
         the draws are taken sample by sample in that order (start draw, then one draw per step)."""
         dev = x_in.device
         B = x_in.shape[0]
-        xr = torch.cat([x_in.float()] * self.out_channel, dim=1)
+        xr = torch.cat([x_in.float()] * self._copies(x_in), dim=1)
         noise = None
         if self.noise_source is not None:
             starts, steps = [], []

@@ -13,7 +13,12 @@ data), from ``--frames <file.npy|.tif>`` ((N,H,W,2) raw channels), or are
 synthesised.  ``--out FILE`` (.npy / .tif) writes the stitched prediction in raw
 counts.  ``-p train`` is refused: the engine is inference-only.  ``--validate [--results DIR]`` runs the training
 loop's validation report instead (core/validation.py): ``# Validation # PSNR``
-of the first 19 non-tiled items, and with ``--results`` the three images per item.
+of the first 19 non-tiled items (``--items N`` for another count), and with ``--results`` the three images per item.
+
+A ``cifar10`` config with ``--datapath`` reads the pickle batches of its ``datapath`` directories (data/cifar10.py).
+Colour items are not tiled: the run IS the validation report, over the whole validation set unless ``--items`` says
+otherwise, ``--batch-tiles`` items at a time; ``--results DIR`` writes the RGB triples and ``--out FILE.npy`` the
+predictions (N, 2 Cc, p, p) float32 in raw counts.
 """
 import argparse
 import logging
@@ -47,13 +52,14 @@ def get_datasets(opt, tiled_pred=False, norm_from="train", device="cuda"):
     upper_clip = ds.get("upper_clip", None)
     max_qval = ds["max_qval"]
     channel_weights = ds.get("channel_weights", None)
-    data_type = (ds["train"] if norm_from == "train" else ds["train"] or ds["val"])["name"]
+    data_type = _data_type(ds, norm_from)
     assert data_type in ["cifar10", "Hagen"]
-    if data_type == "cifar10":
-        raise DsxError("data_type 'cifar10' (the pickle loader of data/cifar10.py) is out of scope: Hagen .tif / .npy stacks only")
     if norm_from not in ("train", "val"):
         raise DsxError(f"norm_from = {norm_from!r}: 'train' or 'val'")
-    loc = lambda part: DataLocation(channelwise_fpath=(ds[part]["datapath"]["ch0"], ds[part]["datapath"]["ch1"]))
+    if data_type == "cifar10":
+        loc = lambda part: _cifar_location(ds, part, norm_from)
+    else:
+        loc = lambda part: DataLocation(channelwise_fpath=(ds[part]["datapath"]["ch0"], ds[part]["datapath"]["ch1"]))
     common = dict(target_channel_idx=target_channel_idx, max_qval=max_qval, upper_clip=bool(upper_clip),
                   channel_weights=channel_weights, enable_transforms=False, random_patching=False,
                   input_from_normalized_target=opt["model"]["which_model_G"] == "joint_indi", device=device)
@@ -68,6 +74,25 @@ def get_datasets(opt, tiled_pred=False, norm_from="train", device="cuda"):
     else:
         val_set = SplitDataset(data_type, loc("val"), patch_size, normalization_dict=nd, **common)
     return train_set, val_set
+
+
+def _data_type(ds, norm_from="train"):
+    return (ds["train"] if norm_from == "train" else ds["train"] or ds["val"])["name"]
+
+
+def _cifar_location(ds, part, norm_from):
+    """``datasets.<part>.datapath`` of a cifar10 config: a directory of pickle batches (split.py:37-38, 53-54)."""
+    path = (ds[part] or {}).get("datapath")
+    if not isinstance(path, str) or not path:
+        raise DsxError(f"data_type 'cifar10': datasets.{part}.datapath must name a directory of CIFAR-10 batch files, "
+                       f"got {path!r}")
+    if not os.path.isdir(path):
+        hint = ""
+        if part == "train" and norm_from == "train":
+            hint = ("; the statistics of uint8 data depend on the plane count and the channel weights only, so "
+                    "--norm-from val (norm_from='val') gives the same numbers without the training directory")
+        raise DsxError(f"data_type 'cifar10': datasets.{part}.datapath = {path} is not a directory{hint}")
+    return DataLocation(directory=path)
 
 
 def _read_frames(path):
@@ -130,6 +155,9 @@ def main(argv=None):
     ap.add_argument("--validate", action="store_true",
                     help="the training loop's validation report (split.py:163-257) instead of the tiled prediction")
     ap.add_argument("--results", type=str, default=None, help="with --validate: directory for the image triples")
+    ap.add_argument("--items", type=int, default=None,
+                    help="items the validation report scores: default 19 with --validate, the whole validation set "
+                         "for a cifar10 config with --datapath")
     args = ap.parse_args(argv)
     if args.phase == "train":
         raise SystemExit("training is out of scope of the MI355X sampling engine; use -p val")
@@ -150,6 +178,12 @@ def main(argv=None):
     opt = Logger.parse(args)
     if args.dtype:
         opt["model"]["compute_dtype"] = args.dtype
+    # colour items (cifar10) are not tiled: with --datapath the run is the validation report over the whole set
+    colour = bool(args.datapath) and _data_type(opt["datasets"], args.norm_from) == "cifar10"
+    if colour and args.out and not args.out.endswith(".npy"):
+        raise SystemExit("--out: colour items are written as (N, 2 Cc, p, p) .npy; a .tif hyperstack holds grey frames")
+    if args.items is not None and args.items < 1:
+        raise SystemExit("--items: a positive count")
     # -gpu selects the device(s): rank r of a torchrun launch drives gpu_ids[r] (the reference exports
     # CUDA_VISIBLE_DEVICES=gpu_ids instead, core/logger.py:59-65; mapping the index keeps one process per GPU
     # working without touching the environment after HIP may have been initialised)
@@ -167,9 +201,9 @@ def main(argv=None):
     dsopt = opt["datasets"] or {}
     which = opt["model"]["which_model_G"]
     if args.datapath:
-        _, val_set = get_datasets(opt, tiled_pred=not args.validate, norm_from=args.norm_from, device=dev)
-        if args.validate:
-            return _run_validate(args, opt, diffusion, val_set, log)
+        _, val_set = get_datasets(opt, tiled_pred=not (args.validate or colour), norm_from=args.norm_from, device=dev)
+        if args.validate or colour:
+            return _run_validate(args, opt, diffusion, val_set, log, whole_set=colour)
         return _predict(args, netG, val_set, n_steps, int(dsopt["patch_size"]), rank, world, dev, log)
     if args.frames:
         frames = _read_frames(args.frames)
@@ -241,16 +275,45 @@ def _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, l
     return _run_validate(args, opt, diffusion, items, log)
 
 
-def _run_validate(args, opt, diffusion, items, log):
+def _run_validate(args, opt, diffusion, items, log, whole_set=False):
+    """``core.validation.validate`` over the first ``--items`` items (default 19; every item with ``whole_set``), the
+    log lines of the training loop, and with ``--out`` the predictions in raw counts.  Returns avg_psnr."""
     from .core.validation import validate
     if args.steps:
         diffusion.netG.set_new_noise_schedule(dict(opt["model"]["beta_schedule"]["val"], n_timestep=args.steps),
                                               diffusion.device)
-    avg_psnr, per_channel = validate(diffusion, items, n_items=19, batch=args.batch_tiles, result_path=args.results)
+    n_items = args.items if args.items is not None else (None if whole_set else 19)
+    preds = []
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    avg_psnr, per_channel = validate(diffusion, items, n_items=n_items, batch=args.batch_tiles, result_path=args.results,
+                                     on_batch=(lambda i0, pred: preds.append(_raw_counts(pred, items))) if args.out else None)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
     log.info("# Validation # PSNR: {:.4e}".format(avg_psnr))
     for ch, vals in per_channel.items():
         log.info("channel %d: PSNR %.4e over %d items", ch, float(np.mean(vals)), len(vals))
+    if whole_set:
+        n = len(next(iter(per_channel.values())))
+        log.info("validation: %d items in batches of %d: %.3f s (%.1f items/s)", n, args.batch_tiles, dt, n / dt)
+    if args.out:
+        np.save(args.out, torch.cat(preds).cpu().numpy())
+        log.info("predictions written to %s", args.out)
     return avg_psnr
+
+
+def _raw_counts(pred, val_set):
+    """A normalised prediction (B, C, H, W) in raw counts: x * std_target + mean_target per channel in float64, as the
+    validation report un-normalises it, rounded to float32 once."""
+    nd = val_set.get_normalization_dict()
+    idx = val_set._target_channel_idx
+    mean, std = (np.asarray(nd[k], dtype=np.float64).reshape(-1) for k in ("mean_target", "std_target"))
+    if idx is not None:
+        mean, std = mean[idx:idx + 1], std[idx:idx + 1]
+    if mean.size != pred.shape[1]:
+        raise DsxError(f"--out: the prediction has {pred.shape[1]} channels, the dataset normalises {mean.size}")
+    as_t = lambda v: torch.as_tensor(v, dtype=torch.float64, device=pred.device).reshape(1, -1, 1, 1)
+    return (pred.to(torch.float64) * as_t(std) + as_t(mean)).to(torch.float32)
 
 
 if __name__ == "__main__":

@@ -415,6 +415,25 @@ int dsx_tiles_gather_norm(const float* frames0_dev, const float* frames1_dev, co
                           int64_t count, float w0, float w1, const double norm[6], int from_norm_target,
                           float* tiles_in_dev, float* tiles_target_dev, void* stream);
 
+/* dsx_tiles_gather_norm for frames with colour planes: SplitDataset.__getitem__ on data_type 'cifar10'
+ * (data/split_dataset.py:248-249 crop img[..., y:y+p, x:x+p] of (Cc, H, W) images, :265-266 concatenate + normalize_target
+ * against the (2 Cc, 1, 1) statistics, :271-272 weighted input + normalize_inp), for a whole batch of items in one launch.
+ * frames0/1 (N, Cc, H, W) fp32 with data_shape = {N, Cc, H, W}, 1 <= Cc <= 8; patch_hw = {ph, pw}; patch_start_host
+ * holds (frame, y, x) triples and tile_ids_host selects from it (NULL: the first `count` triples), as for
+ * dsx_tiles_gather_norm.  mean_target / std_target: 2 Cc doubles each, plane c of frames0 is target channel c, plane c
+ * of frames1 is channel Cc + c.  Per element, every operation rounded on its own (no fma):
+ *   target_c = (float)(((double)p_c - mean_target[c]) / std_target[c])
+ *   input_c  = (float)(((double)fadd(fmul(w0, p0_c), fmul(w1, p1_c)) - mean_input) / std_input)
+ * tiles_in (count, Cc, ph, pw), tiles_target (count, 2 Cc, ph, pw); nothing outside them is written.  count <= 65535
+ * per call (larger batches are the caller's to slice).  DSX_ERR_INVALID with a message, before any device work: a NULL
+ * pointer, Cc outside 1..8, a patch larger than the frame, a location outside the frame, a non-finite statistic or a
+ * zero std, count outside 0..65535. */
+int dsx_tiles_gather_norm_planes(const float* frames0_dev, const float* frames1_dev, const int64_t data_shape[4],
+                                 const int64_t patch_hw[2], const int64_t* patch_start_host, const int64_t* tile_ids_host,
+                                 int64_t count, float w0, float w1, double mean_input, double std_input,
+                                 const double* mean_target, const double* std_target, float* tiles_in_dev,
+                                 float* tiles_target_dev, void* stream);
+
 /* The mixed inputs of the TimePredictor evaluation for a whole batch of tiles, from the two raw frame stacks, in one
  * pass: replaces get_inputs + normalize_indi1/2 (notebooks/EvaluateJointIndiIterative.ipynb cells 40, 43), the
  * classifier sweep's mixing (notebooks/time_prediction_evaluation.ipynb cell 4) and the arithmetic of
