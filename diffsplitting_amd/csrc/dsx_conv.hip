@@ -1472,6 +1472,12 @@ __global__ __launch_bounds__(256 + 64 * LW, 1) void k_conv_ws(const ConvArgs a) 
 //   * the 8 partial accumulators meet in LDS (fixed order -> bitwise reproducible), the epilogue adds bias / FiLM /
 //     residual, stores, and emits the complete per-(image, channel) GroupNorm sums of the result (one partial row).
 // ===========================================================================================
+// Diagnostic stamps of k_conv_img: the first wave of the workgroup records slot i, the last wave slot 32 + i.
+//   0 entry   1 first loads requested   2 scale / shift ready   3 phase 0 converted, every up-front load requested
+//   4 + p phase p's MFMAs issued   12 .. 15 reduction, store, statistics   20 arrival at the reduction barrier
+//   16 the wave's last weight fragment has landed (an explicit wait of the diagnostic build, in front of the last phase)
+//   17 phase 1 converted   18 first MFMA pair issued   19 GroupNorm arithmetic under way (phase 0's partial sums are in registers)
+#define IMG_STAMP(i) do { DSX_STAMP_T((i), tid == 0); DSX_STAMP_T(32 + (i), tid == 448); } while (0)
 template <typename DT, int KS, int NPH>
 __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
   constexpr int KC = Chunk<DT>::KC;
@@ -1482,10 +1488,17 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
   constexpr int RB = KS == 3 ? 896 : 640;       // conv_lds_row(KS, 1, 3): conflict-free ds_read_b128 of 8-wide rows
   constexpr int IMGB = PW * RB;
   constexpr int NSTEP = TAPS * 2;
-  constexpr int D = NSTEP;                      // weight fragments in flight: a whole phase (latency, not bandwidth, bounds the stream)
+  constexpr int D = NSTEP;                      // ring depth: a whole phase of weight fragments
   constexpr int MAXP = NPH;                     // phases this instantiation is unrolled for (host: C <= NPH * 8 * KC)
-  constexpr bool ALLW = NPH == 2;               // two phases: every weight fragment of the wave is requested up front
   static_assert(NSTEP % D == 0, "ring depth divides the steps of a phase");
+  // Phase 0's fragments go out in static groups: WTOP0 ahead of the GroupNorm arithmetic, the rest in equal groups behind
+  // each phase of the two GroupNorm loops and each unit of phase 0's conversion.  The CU's vector-memory path accepts the
+  // eight waves' loads at about the rate at which it delivers them, so a wave that requests everything first stands at
+  // its last load until most of its data is back; requested in between, the loads are
+  // accepted while the arithmetic runs.
+  constexpr int WTOP0 = D < 4 ? D : 4;
+  constexpr int WREST = D - WTOP0;
+  constexpr int WSLOTS = 2 * MAXP + 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1501,7 +1514,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
   unsigned char* img = lds + wave * (2 * IMGB);
   float* aff = (float*)(lds + 8 * 2 * IMGB) + wave * (8 * 2 * KC);      // [phase][scale KC | shift KC]
 
-  DSX_STAMP(0);
+  IMG_STAMP(0);
   // zero both buffers once: the halo border stays zero (the reference pads AFTER the activation)
   if (KS == 3) {
     // 36 border pixels x 5 sixteen-byte units x 2 buffers = 360 units: top / bottom rows, left / right columns
@@ -1527,23 +1540,23 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
       raw[i] = *(const uint4*)(src + (((size_t)b * 64 + px) * Cs + cl + u * CPU) * ES);
     }
   };
-  auto convert_store = [&](int p, const uint4 (&raw)[4]) __attribute__((always_inline)) {
-    unsigned char* buf = img + (p & 1) * IMGB;
+  // conversion of a slice = its scale / shift (convert_prep) and four units of 64 lanes x 16 bytes (convert_unit), which
+  // the callers interleave with loads and MFMAs
+  auto convert_prep = [&](int p, float (&sc)[CPU], float (&sh)[CPU]) __attribute__((always_inline)) {
     const int u = lane & 3;
-    float sc[CPU], sh[CPU];
     if (a.has_gn) {
 #pragma unroll
       for (int j = 0; j < CPU; ++j) { sc[j] = aff[p * 2 * KC + u * CPU + j]; sh[j] = aff[p * 2 * KC + KC + u * CPU + j]; }
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int px = (lane + 64 * i) >> 2;
-      float v[CPU];
-      Unit<DT>::unpack(raw[i], v);
-      if (a.has_gn) affine_vec(v, sc, sh);
-      if (a.swish) swish_vec(v);
-      *(uint4*)(buf + ((px >> 3) + PAD) * RB + ((px & 7) + PAD) * PIXB + u * 16) = Unit<DT>::pack(v);
-    }
+  };
+  auto convert_unit = [&](int p, const uint4& raw, int i, const float (&sc)[CPU], const float (&sh)[CPU]) __attribute__((always_inline)) {
+    unsigned char* buf = img + (p & 1) * IMGB;
+    const int u = lane & 3, px = (lane + 64 * i) >> 2;
+    float v[CPU];
+    Unit<DT>::unpack(raw, v);
+    if (a.has_gn) affine_vec(v, sc, sh);
+    if (a.swish) swish_vec(v);
+    *(uint4*)(buf + ((px >> 3) + PAD) * RB + ((px & 7) + PAD) * PIXB + u * 16) = Unit<DT>::pack(v);
   };
 
   // ---- GroupNorm operands first: vmcnt retires in order, so the producer's partial sums (and gamma / beta) issued
@@ -1570,7 +1583,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
   }
   uint4 raw0[4], raw1[4];
   load_raw(0, raw0);
-  if (nphase > 1) load_raw(1, raw1);
 
   // ---- weight stream: fragments of (N block nb, chunk 8p + wave), NSTEP x 1 KiB per phase, flat over the phases
   const unsigned char* wbase = (const unsigned char*)a.wpack + (size_t)nb * a.kchunks * (NSTEP * 1024) + lane * 16;
@@ -1580,24 +1592,28 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
     if (++sn == NSTEP) { sn = 0; ++pn; }
     return v;
   };
-  uint4 wq[D], wq1[ALLW ? D : 1];
-#pragma unroll
-  for (int j = 0; j < D; ++j) wq[j] = load_w();
-  if constexpr (ALLW) {
-    if (nphase > 1) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) wq1[j] = load_w();
-    }
-  }
-  DSX_STAMP(1);
+  uint4 wq[D];
+  // fragments [WTOP0 + WREST * G / WSLOTS, WTOP0 + WREST * (G + 1) / WSLOTS) of phase 0 (group -1: the first WTOP0).  Every
+  // load is unconditional and every count a compile-time constant; the scheduling
+  // barriers keep hipcc from gathering the groups at the top again.
+  auto issue_w = [&](auto g_) __attribute__((always_inline)) {
+    constexpr int G = decltype(g_)::value;
+    constexpr int lo = G < 0 ? 0 : WTOP0 + WREST * G / WSLOTS, hi = G < 0 ? WTOP0 : WTOP0 + WREST * (G + 1) / WSLOTS;
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<hi - lo>([&](auto j_) __attribute__((always_inline)) {
+      wq[lo + decltype(j_)::value] = load_w();
+    });
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  issue_w(std::integral_constant<int, -1>{});
+  IMG_STAMP(1);
 
   // ---- GroupNorm: scale / shift of this wave's channels of every phase (lanes = 64 consecutive channels).
-  // All loads of all phases were issued at the top (one memory round trip, not one per phase).
-  if (a.has_gn) {
-    const int cpg = C / a.gn_groups;            // host: power of two <= 64, divides C0
-    double gs[MAXP], gq[MAXP];
-#pragma unroll
-    for (int p = 0; p < MAXP; ++p) {
+  // The GroupNorm operands of all phases were requested at the top (one memory round trip, not one per phase).
+  double gs[MAXP], gq[MAXP];
+  static_for<MAXP>([&](auto p_) __attribute__((always_inline)) {
+    constexpr int p = decltype(p_)::value;
+    if (a.has_gn) {
       const int pp = p < nphase ? p : nphase - 1;
       const int cb = ((pp * 8 + wave) * KC) & ~63, c = cb + lane;
       const bool first = cb < a.C0;
@@ -1606,6 +1622,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
       const double d1 = __builtin_bit_cast(double, ((unsigned long long)ghi[p].y << 32) | ghi[p].x);
       gs[p] = pf32 ? (double)__builtin_bit_cast(float, glo[p].x) : d0;
       gq[p] = pf32 ? (double)__builtin_bit_cast(float, glo[p].y) : d1;
+#ifdef DSX_STAMPS
+      if constexpr (p == 0) { asm volatile("" :: "v"(gs[0]), "v"(gq[0])); IMG_STAMP(19); }
+#endif
       if (nch > 1 && p < nphase) {              // producers with several partial rows (split-K reduce, k_chan_stats): rare
         const char* part = (const char*)(first ? a.gn_part0 : a.gn_part1);
         const int Cs = first ? a.C0 : a.C1, cl = first ? c : c - a.C0;
@@ -1619,14 +1638,19 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
       if (piv.bias || piv.film)                 // shifted partials (k_conv_first / split-K reduce producers): rare here
         stat_unshift(gs[p], gq[p], (double)stat_pivot(piv, b, first ? c : c - a.C0), (double)(a.Hs * a.Ws));
     }
+    issue_w(std::integral_constant<int, p>{});
+    if constexpr (p == 0) { if (nphase > 1) load_raw(1, raw1); }   // needed under phase 0's MFMAs: behind the first group
+  });
+  {
+    const int cpg = a.has_gn ? C / a.gn_groups : 1;   // host: power of two <= 64, divides C0
     // Group sums over <= 64 lanes in fp32 (a channel's sums over the 64 pixels already are fp32 values of the producer's
     // epilogue; the xor butterfly gives every lane of a group the same bits), the cancellation-prone E[x^2] - mean^2 in
     // double, the reciprocal square root by v_rsq_f32 (1 ulp): a dozen instructions per phase instead of a double-
     // precision butterfly, division and square root (~3 k cycles of this latency-bound kernel's prologue with 8 waves/CU).
     const float inv_n = 1.0f / (64.0f * (float)cpg);     // H * W * channels per group: a power of two, exact
-#pragma unroll
-    for (int p = 0; p < MAXP; ++p) {
-      if (p < nphase) {
+    static_for<MAXP>([&](auto p_) __attribute__((always_inline)) {
+      constexpr int p = decltype(p_)::value;
+      if (a.has_gn && p < nphase) {
         const int c0 = (p * 8 + wave) * KC, c = (c0 & ~63) + lane;
         float s = (float)gs[p], q = (float)gq[p];
         for (int o = 1; o < cpg; o <<= 1) { s += __shfl_xor(s, o, 64); q += __shfl_xor(q, o, 64); }
@@ -1641,16 +1665,25 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
           aff[p * 2 * KC + KC + (c - c0)] = gb[p] - meanf * sc;
         }
       }
-    }
+      issue_w(std::integral_constant<int, MAXP + p>{});
+    });
   }
-  // the next image-resident conv's weight slices -> this XCD's L2 (its workgroups with the same label need them): issued
-  // behind this kernel's own first loads, a whole kernel duration ahead of their use
-  const PfAcc pf_acc = l2_prefetch(a.pf, blockIdx.x, gridDim.x, tid, 512);
-  DSX_STAMP(2);
+  IMG_STAMP(2);
   __builtin_amdgcn_s_waitcnt(0xC07F);           // lgkmcnt(0): the zero fill and the aff table are in LDS
-  convert_store(0, raw0);
-  if (nphase > 1) convert_store(1, raw1);
-  DSX_STAMP(3);
+  {
+    float sc[CPU], sh[CPU];
+    convert_prep(0, sc, sh);
+    static_for<4>([&](auto i_) __attribute__((always_inline)) {
+      constexpr int i = decltype(i_)::value;
+      convert_unit(0, raw0[i], i, sc, sh);
+      issue_w(std::integral_constant<int, 2 * MAXP + i>{});
+    });
+  }
+  // the next image-resident conv's weight slices -> this XCD's L2 (its workgroups with the same label need them): behind
+  // every load this kernel requests in front of its first MFMA (and its integer division off the path to that MFMA), a
+  // whole kernel duration ahead of their use
+  const PfAcc pf_acc = l2_prefetch(a.pf, blockIdx.x, gridDim.x, tid, 512);
+  IMG_STAMP(3);
 
   int abase[2][KS];
 #pragma unroll
@@ -1665,27 +1698,49 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
 
-  for (int p = 0; p < nphase; ++p) {
+  // Phase p multiplies buffer p & 1.  Under its MFMAs the wave converts the slice of phase p + 1 (requested a phase
+  // earlier, or at the top) into the other buffer, whose last reader, phase p - 1, has issued all its LDS reads (the
+  // buffers are wave-private and LDS operations of a wave stay in order: no barrier), and requests the slice of phase
+  // p + 2 into the registers that held its own.
+  auto phase = [&](int p, uint4 (&rnext)[4], const uint4 (&rcvt)[4]) __attribute__((always_inline)) {
     const unsigned char* buf = img + (p & 1) * IMGB;
-    if (p + 2 < nphase) load_raw(p + 2, raw0);   // in flight during this phase's MFMAs
+#ifdef DSX_STAMPS
+    if (p == nphase - 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); IMG_STAMP(16); }
+#endif
+    if (p + 2 < nphase) load_raw(p + 2, rnext);  // in flight during this phase's MFMAs
     const bool more = p + 1 < nphase;
+    float csc[CPU], csh[CPU];
+    if (more) convert_prep(p + 1, csc, csh);
     static_for<NSTEP>([&](auto sc_) __attribute__((always_inline)) {
       constexpr int s = decltype(sc_)::value;
       constexpr int tap = s >> 1, fs = s & 1, dy = tap / KS, dx = tap % KS;
-      uint4 wcur = wq[s % D];
-      if constexpr (ALLW) {
-        if (p == 1) wcur = wq1[s % D];           // uniform
-      } else {
-        if (more) wq[s % D] = load_w();          // uniform: the next phase's fragment into the slot just consumed
-      }
+      const uint4 wcur = wq[s % D];
+      if (more) wq[s % D] = load_w();            // uniform: the next phase's fragment into the slot just consumed
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) {
         const f32x4_t px = *(const f32x4_t*)(buf + abase[mb][dy] + dx * PIXB + fs * 32);
         acc[mb] = mfma_step<DT>(wcur, px, acc[mb]);
       }
+      if constexpr (s == 0) { if (p == 0) IMG_STAMP(18); }
+      static_for<4 * (s + 1) / NSTEP - 4 * s / NSTEP>([&](auto i_) __attribute__((always_inline)) {
+        constexpr int i = 4 * s / NSTEP + decltype(i_)::value;
+        if (more) convert_unit(p + 1, rcvt[i], i, csc, csh);
+      });
     });
-    if (p + 2 < nphase) convert_store(p + 2, raw0);   // refill this buffer with the slice of phase p + 2
-    DSX_STAMP(4 + p);
+    if (p == 0) IMG_STAMP(17);
+    IMG_STAMP(4 + p);
+  };
+  if constexpr (NPH != 8) {                     // unrolled: `more` and every load count are constants in each phase (item 17)
+    static_for<NPH / 2>([&](auto h_) __attribute__((always_inline)) {
+      constexpr int p = 2 * decltype(h_)::value;
+      phase(p, raw0, raw1);
+      phase(p + 1, raw1, raw0);
+    });
+  } else {
+    for (int p = 0; p < nphase; p += 2) {
+      phase(p, raw0, raw1);
+      if (p + 1 < nphase) phase(p + 1, raw1, raw0);
+    }
   }
 
   // thread -> pixel tid >> 3, channels 4 * (tid & 7) .. + 3 of the block.  Its epilogue operands are requested here, in
@@ -1703,8 +1758,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
     for (int j = 0; j < 4; ++j) er[j] = act_load<DT>(a.resid, opix * a.resid_ld + n0 + j);
   }
   // ---- the 8 partial sums meet in LDS: part[w][mb][r][lane]
+  IMG_STAMP(20);
   __syncthreads();
-  DSX_STAMP(12);
+  IMG_STAMP(12);
   float* part = (float*)lds;
 #pragma unroll
   for (int mb = 0; mb < 2; ++mb)   // [w][mb][lane][16 registers], 80-byte lane stride: conflict-free 16-byte accesses
@@ -1713,7 +1769,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
       *(float4*)(part + ((wave * 2 + mb) * 64 + lane) * 20 + 4 * j) =
           make_float4(acc[mb][4 * j], acc[mb][4 * j + 1], acc[mb][4 * j + 2], acc[mb][4 * j + 3]);
   __syncthreads();
-  DSX_STAMP(13);
+  IMG_STAMP(13);
   // thread -> pixel tid >> 3, channels 4 * (tid & 7) .. + 3 of the block.  Accumulator register r of lane
   // (li, lh) of block mb is pixel 32 mb + li, channel 16 lh + r.
   const int mbo = px >> 5, lo = (px & 31) + 32 * (cg >> 4), r0 = cg & 15;
@@ -1737,7 +1793,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
     else { w2.x = pack_f16x2(x[0], x[1]); w2.y = pack_f16x2(x[2], x[3]); }
     *(uint2*)((unsigned short*)a.out + opix * a.out_ld + n0) = w2;
   }
-  DSX_STAMP(14);
+  IMG_STAMP(14);
   // ---- GroupNorm sums of the result over the image's 64 pixels (complete: one partial row per image)
   if (a.stat_part != nullptr) {
     float s1[4], s2[4];
@@ -1763,7 +1819,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a) {
     }
   }
   l2_prefetch_retire(a.pf, pf_acc);
-  DSX_STAMP(15);
+  IMG_STAMP(15);
 }
 
 static size_t conv_img_lds(int dtype, int ks) {

@@ -1,0 +1,99 @@
+"""Which image-resident launches (k_conv_img) the smallest model with a full 8 x 8 level plans, and what they cover
+(planner dry run: no GPU, no compute).  tests/test_gpu_conv_img.py checks exactly these launches on the device; this
+file pins its coverage claim: every instantiation of the kernel (both kernel sizes, NPH 2 / 4 / 8 in every operand
+type), one- and two-source inputs, GroupNorm with and without Swish, residual and output statistics on and off."""
+import collections
+import ctypes as C
+import re
+
+import pytest
+
+# SR3 UNet: 32 x 32 input, levels 64 / 256 / 512 channels, attention at 8 x 8, 3 conditioning channels
+IMG_MODEL = dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=32, channel_mults=(1, 4, 8),
+                 attn_res=(8,), res_blocks=1, image_size=32)
+COND_CHANNELS = 3
+
+IMG_LAUNCHES = {
+    "conv3x3 256->512 @8x8 img": 1,
+    "conv1x1 256->512 @8x8 img": 1,
+    "conv3x3 512->512 @8x8 img": 7,
+    "conv1x1 512->1536 @8x8 img": 4,
+    "conv1x1 512->512 @8x8 img": 4,
+    "conv3x3 1024->512 @8x8 img": 1,
+    "conv1x1 1024->512 @8x8 img": 1,
+    "conv1x1 768->512 @8x8 img": 1,
+}
+# channel phases (8 waves x one 64-byte chunk each) -> the NPH the launcher instantiates: 2 and 4 exactly, 8 for the rest
+PHASES = {"bf16": {1, 2, 3, 4}, "f16": {1, 2, 3, 4}, "f32": {2, 4, 6, 8}}
+NPH = {"bf16": {1: 8, 2: 2, 3: 8, 4: 4}, "f16": {1: 8, 2: 2, 3: 8, 4: 4}, "f32": {2: 2, 4: 4, 6: 8, 8: 8}}
+
+
+class ConvArgsHead(C.Structure):
+    """the leading members of ConvArgs (dsx_kernels.h), up to the ones read here: DSX_PLAN_DUMP writes the struct's bytes"""
+    _fields_ = [("src0", C.c_void_p), ("src1", C.c_void_p), ("act_bf16", C.c_int), ("out_bf16", C.c_int),
+                ("C0", C.c_int), ("C1", C.c_int), ("B", C.c_int), ("Hs", C.c_int), ("Ws", C.c_int), ("up", C.c_int),
+                ("Ho", C.c_int), ("Wo", C.c_int), ("gn_scale", C.c_void_p), ("gn_shift", C.c_void_p),
+                ("has_gn", C.c_int), ("swish", C.c_int), ("stage_mode", C.c_int), ("wpack", C.c_void_p),
+                ("bias", C.c_void_p), ("film", C.c_void_p), ("film_bs", C.c_int), ("resid", C.c_void_p),
+                ("resid_ld", C.c_int), ("out", C.c_void_p), ("out_ld", C.c_int), ("Cout", C.c_int),
+                ("nblocks", C.c_int), ("kchunks", C.c_int), ("tw_log2", C.c_int), ("th_log2", C.c_int),
+                ("tb_log2", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("m_tiles", C.c_int),
+                ("n_tiles", C.c_int), ("lds_row", C.c_int), ("cpg", C.c_int), ("ws_wg_per_n", C.c_int),
+                ("ws_cpg", C.c_int), ("xcd_bands", C.c_int), ("ws_map", C.c_int), ("ws_nt_log2", C.c_int),
+                ("ws_per", C.c_int), ("ws_adv_x", C.c_int), ("ws_adv_y", C.c_int), ("ws_adv_b", C.c_int),
+                ("ws_dpy", C.c_int), ("ws_dpx", C.c_int), ("mg_tiles_x", C.c_uint), ("mg_per_img", C.c_uint),
+                ("mg_pw", C.c_uint), ("mg_wpn", C.c_uint), ("mg_per", C.c_uint), ("ws_bigdiv", C.c_int),
+                ("stat_part", C.c_void_p)]
+
+
+def img_launches(dt, B, path, monkeypatch):
+    """[(description, ks, ConvArgsHead)] of the plan's image-resident launches, in launch order"""
+    from diffsplitting_amd import engine
+    cfg = engine.make_cfg("sr3", **IMG_MODEL)
+    monkeypatch.setenv("DSX_PLAN_DUMP", str(path))
+    H = IMG_MODEL["image_size"]
+    a, b, n = engine.plan_dry_run(cfg, dt, B, H, H, COND_CHANNELS)
+    assert a == b
+    out = []
+    lines = path.read_text().splitlines()
+    assert len(lines) == n
+    for line in lines:
+        m = re.match(r'\d+ kind=(\d+) desc="([^"]*)" .* launcher=(\w+) dtype=\d+ tile=-?\d+ ks=(\d+) stride=\d+ '
+                     r'col_split=\d+ args=([0-9a-f]+)$', line)
+        assert m, line[:200]
+        if m.group(2).endswith(" img"):
+            assert m.group(3) == "conv_img" and int(m.group(1)) == 0, line[:200]
+            raw = bytes.fromhex(m.group(5))
+            assert len(raw) >= C.sizeof(ConvArgsHead)
+            out.append((m.group(2), int(m.group(4)), ConvArgsHead.from_buffer_copy(raw[:C.sizeof(ConvArgsHead)])))
+    return out
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("dt", ["bf16", "f16", "f32"])
+def test_img_launches_of_the_smallest_8x8_model(dt, B, tmp_path, monkeypatch):
+    L = img_launches(dt, B, tmp_path / "plan.txt", monkeypatch)
+    assert dict(collections.Counter(d for d, _, _ in L)) == IMG_LAUNCHES
+    kc = 16 if dt == "f32" else 32                     # channels of a 64-byte chunk
+    phases, sizes, sources, acts, resid, stats = set(), set(), set(), set(), set(), set()
+    for desc, ks, a in L:
+        m = re.match(r"conv(\d)x\d (\d+)->(\d+) @8x8 img$", desc)
+        assert int(m.group(1)) == ks and int(m.group(2)) == a.C0 + a.C1 and int(m.group(3)) == a.Cout, desc
+        assert (a.B, a.Hs, a.Ws, a.Ho, a.Wo, a.up) == (B, 8, 8, 8, 8, 0), desc
+        assert (a.C0 + a.C1) % (8 * kc) == 0 and a.kchunks * kc == a.C0 + a.C1, desc
+        assert not (a.swish and not a.has_gn), desc
+        phases.add((a.C0 + a.C1) // (8 * kc))
+        sizes.add(ks)
+        sources.add((a.C0, a.C1))
+        acts.add((bool(a.has_gn), bool(a.swish)))
+        resid.add(a.resid is not None)
+        stats.add(a.stat_part is not None)
+    assert phases == PHASES[dt]
+    assert {NPH[dt][p] for p in phases} == {2, 4, 8}   # every instantiation of the operand type ...
+    assert sizes == {1, 3}                             # ... in both kernel sizes
+    for ks in (1, 3):
+        assert {NPH[dt][(a.C0 + a.C1) // (8 * kc)] for _, k, a in L if k == ks} == {2, 4, 8}, ks
+    assert {(512, 0), (512, 512), (512, 256)} <= sources
+    assert acts == {(True, True), (True, False), (False, False)}   # GroupNorm + Swish, GroupNorm alone (qkv), neither
+    assert resid == {False, True}
+    assert stats == {False, True}
