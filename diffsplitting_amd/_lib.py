@@ -104,6 +104,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_double), C.POINTER(C.c_double), _vp, _vp, _vp]),
     "dsx_tiles_gather_mix": (_i, [_vp, _vp, _pi64, _pi64, _pi64, _pi64, _i64, C.POINTER(C.c_double), C.c_double,
                                   C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    "dsx_tiles_gather_mix_items": (_i, [_vp, _vp, _pi64, _pi64, _pi64, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
     "dsx_mix_range_blocks": (_i, [_i64, _i]),
     "dsx_mix_range": (_i, [_vp, _vp, _i64, C.POINTER(C.c_double), _i, _vp, C.POINTER(C.c_double), _vp]),
     "dsx_stitch": (_i, [_vp, _i64, _i, _i, _i, _pi32, _vp, _pi64, _vp]),

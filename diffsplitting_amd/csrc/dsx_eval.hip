@@ -139,11 +139,10 @@ struct GatherMixArgs {
   MixWeights mw;
   float* ttar; float* tmix; float* tcls;   // (count, 2, ph, pw) each, or nullptr
 };
-__global__ void k_tiles_gather_mix(const GatherMixArgs a) {
-  const long long k = blockIdx.y, t = a.seq.first + k * a.seq.stride;
-  const int n = a.starts[t * 3], y0 = a.starts[t * 3 + 1], x0 = a.starts[t * 3 + 2];
+// item k of a launch, cut at (n, y0, x0) with the weights w: the one body of both mixed gathers, so that an item of
+// k_tiles_gather_mix_items is bitwise the item k_tiles_gather_mix writes for the same location, t and table rows
+__device__ __forceinline__ void mix_item(const GatherMixArgs& a, long long k, int n, int y0, int x0, const MixWeights w) {
   const int total = a.ph * a.pw;
-  const MixWeights w = a.mw;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int y = i / a.pw, x = i % a.pw;
     const size_t src = ((size_t)n * a.H + (y0 + y)) * a.W + (x0 + x);
@@ -160,6 +159,30 @@ __global__ void k_tiles_gather_mix(const GatherMixArgs a) {
       }
     }
   }
+}
+__global__ void k_tiles_gather_mix(const GatherMixArgs a) {
+  const long long k = blockIdx.y, t = a.seq.first + k * a.seq.stride;
+  mix_item(a, k, a.starts[t * 3], a.starts[t * 3 + 1], a.starts[t * 3 + 2], a.mw);
+}
+// the same with one (location, weights) record per item: a batch whose items each carry their own t and table rows
+// (TimePredictorDataset.batch).  The record is uniform in the workgroup (indexed by blockIdx.y); pixels are read and
+// written one dword per lane, consecutive lanes consecutive x: patch starts are arbitrary and ph * pw need not be a
+// multiple of 4, so neither the source rows nor the items of the outputs are 16-byte aligned in general.
+__global__ void k_tiles_gather_mix_items(const GatherMixArgs a, const MixItem* __restrict__ items) {
+  const long long k = blockIdx.y;
+  const MixItem it = items[k];
+  mix_item(a, k, it.n, it.y, it.x, it.w);
+}
+hipError_t launch_tiles_gather_mix_items(const float* f0, const float* f1, int H, int W, int ph, int pw,
+                                         const MixItem* items, long long count, const double norm[4], float* ttar,
+                                         float* tmix, float* tcls, hipStream_t st) {
+  if (count < 1 || count > 65535) return hipErrorInvalidValue;
+  GatherMixArgs a{f0, f1, H, W, ph, pw, nullptr, TileSeq{0, 1, count}, norm[0], norm[1], norm[2], norm[3], MixWeights{},
+                  ttar, tmix, tcls};
+  int gx = (ph * pw + 255) / 256;
+  if (gx > 64) gx = 64;
+  hipLaunchKernelGGL(k_tiles_gather_mix_items, dim3((unsigned)gx, (unsigned)count), dim3(256), 0, st, a, items);
+  return hipGetLastError();
 }
 hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
                                    TileSeq seq, const double norm[4], const MixWeights& mw, float* ttar, float* tmix,

@@ -634,6 +634,12 @@ struct MixWeights { float w0, w1, lo0, rng0, lo1, rng1; };
 hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
                                    TileSeq seq, const double norm[4], const MixWeights& mw, float* ttar, float* tmix,
                                    float* tcls, hipStream_t st);
+// the same with one record per item (dev table, item k of the launch = items[k]): its (frame, y, x) start and its own
+// weights.  1 <= count <= 65535 (grid y); the arithmetic per element is launch_tiles_gather_mix's, bit for bit.
+struct MixItem { int n, y, x; MixWeights w; };
+hipError_t launch_tiles_gather_mix_items(const float* f0, const float* f1, int H, int W, int ph, int pw,
+                                         const MixItem* items /*dev*/, long long count, const double norm[4], float* ttar,
+                                         float* tmix, float* tcls, hipStream_t st);
 // min / max over all pixels of t * a + (1 - t) * b, t = t_int / n for t_int = 0..n, on the normalised channels
 // (compute_input_normalization_dict, data/time_predictor_dataset.py:6-21), fp64 with every operation rounded on its
 // own.  part[mix_range_blocks(pixels)][n + 1][2] = {min, max} per pixel workgroup; the caller reduces over the rows.

@@ -378,6 +378,57 @@ extern "C" int dsx_tiles_gather_mix(const float* frames0, const float* frames1, 
   return DSX_OK;
 }
 
+// one t and one pair of table rows per item; every refusal names the item, and nothing touches the device before the
+// last of them has passed.  The records (start + weights) go up in the one table the call uploads.
+extern "C" int dsx_tiles_gather_mix_items(const float* frames0, const float* frames1, const int64_t data_shape[3],
+                                          const int64_t patch_shape[3], const int64_t* patch_start, int64_t count,
+                                          const double norm[4], const double* t_host, const double* lohi_host,
+                                          float* target, float* mix, float* cls, void* stream) {
+  if (!target && !mix && !cls) return fail(DSX_ERR_INVALID, "gather_mix_items: every output pointer is NULL");
+  if (!frames0 || !frames1 || !data_shape || !patch_shape || !patch_start || !norm || !t_host)
+    return fail(DSX_ERR_INVALID, "gather_mix_items: null argument");
+  if (cls && !lohi_host)
+    return fail(DSX_ERR_INVALID, "gather_mix_items: the classifier view needs the (lo, hi) pairs of every item's two table rows");
+  int rc = norm4_ok(norm);
+  if (rc) return rc;
+  const int64_t N = data_shape[0], H = data_shape[1], W = data_shape[2], ph = patch_shape[1], pw = patch_shape[2];
+  if (N < 1 || H < 1 || W < 1 || N > INT32_MAX || H > INT32_MAX || W > INT32_MAX)
+    return fail(DSX_ERR_INVALID, "gather_mix_items: bad frame shape (%lld, %lld, %lld)", (long long)N, (long long)H, (long long)W);
+  if (ph < 1 || pw < 1 || ph > H || pw > W || ph * pw > INT32_MAX)
+    return fail(DSX_ERR_INVALID, "gather_mix_items: patch %lld x %lld does not fit the %lld x %lld frames", (long long)ph,
+                (long long)pw, (long long)H, (long long)W);
+  if (count < 0 || count > 65535)
+    return fail(DSX_ERR_INVALID, "gather_mix_items: count = %lld, at most 65535 items per call", (long long)count);
+  if (count == 0) return DSX_OK;
+  std::vector<MixItem> items((size_t)count);
+  for (int64_t i = 0; i < count; ++i) {
+    const double t = t_host[i];
+    if (!std::isfinite(t)) return fail(DSX_ERR_INVALID, "gather_mix_items: item %lld: mixing weight t must be finite", (long long)i);
+    MixWeights mw{(float)(1.0 - t), (float)t, 0.f, 1.f, 0.f, 1.f};
+    if (cls) {
+      const double* lohi = lohi_host + i * 4;
+      for (int c = 0; c < 2; ++c) {
+        const double lo = lohi[2 * c], hi = lohi[2 * c + 1];
+        if (!std::isfinite(lo) || !std::isfinite(hi) || hi - lo == 0.0)
+          return fail(DSX_ERR_INVALID, "gather_mix_items: item %lld: table row of channel %d: lo and hi must be finite and differ",
+                      (long long)i, c);
+      }
+      mw.lo0 = (float)lohi[0]; mw.rng0 = (float)(lohi[1] - lohi[0]);
+      mw.lo1 = (float)lohi[2]; mw.rng1 = (float)(lohi[3] - lohi[2]);
+    }
+    const int64_t n = patch_start[i * 3], y = patch_start[i * 3 + 1], x = patch_start[i * 3 + 2];
+    if (n < 0 || n >= N || y < 0 || y > H - ph || x < 0 || x > W - pw)
+      return fail(DSX_ERR_INVALID, "gather_mix_items: item %lld at (%lld, %lld, %lld) lies outside the frames", (long long)i,
+                  (long long)n, (long long)y, (long long)x);
+    items[i] = MixItem{(int)n, (int)y, (int)x, mw};
+  }
+  DevBuf d;
+  HIP_TRY(d.upload(items.data(), items.size() * sizeof(MixItem)));
+  HIP_TRY(launch_tiles_gather_mix_items(frames0, frames1, (int)H, (int)W, (int)ph, (int)pw, d.as<MixItem>(), count, norm,
+                                        target, mix, cls, (hipStream_t)stream));
+  return DSX_OK;   // ~DevBuf waits for the launch
+}
+
 // the range table of the mixed inputs in one launch; the min / max over the partial rows on the host (exact)
 extern "C" int dsx_mix_range_blocks(int64_t pixels, int n_timesteps) {
   if (pixels < 1) return fail(DSX_ERR_INVALID, "mix_range: no pixels");

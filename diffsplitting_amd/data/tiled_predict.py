@@ -141,7 +141,7 @@ def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1
     prediction and target first, a positive affine map per channel, under which RangeInvariantPsnr does not change --
     no extra pass.  A sampler's own ``noise_source`` is used (set ``netG.noise_source`` to give both the same).
     Several ranks: tiles are sharded through ``TileExchange`` as in ``predict_tiled``; ``pred_t`` then holds this
-    rank's tiles only (NaN elsewhere) -- the sharded form is not covered by a test.
+    rank's tiles only (NaN elsewhere); ``gather_pred_t`` completes it on every rank.
 
     ``lpips``: a ``core.lpips.LPIPS``; with it the first element is ``(canvas, psnr, lpips_dict)``, the per-frame LPIPS of
     every channel against the same normalised target (``core.metrics.calculate_lpips``; its min-max map makes it
@@ -185,3 +185,15 @@ def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1
     from ..core.metrics import calculate_lpips
     canvas, psnr = ex.finish()
     return (canvas, psnr, calculate_lpips(gt, canvas, lpips)), pred_t
+
+
+def gather_pred_t(pred_t, group=None):
+    """``pred_t`` (n_tiles, 2) of a sharded ``predict_tiled_mixed`` -- rank q holds the rows of its tiles q, q + W, ...
+    and NaN elsewhere -- completed on every rank: one all-gather of the small table, row i taken from its owner
+    i % W.  One rank: returned as it is."""
+    world = parallel.world_size()
+    if world == 1:
+        return pred_t
+    full = parallel.all_gather_flat(pred_t.reshape(-1).contiguous(), group).view(world, -1, pred_t.shape[1])
+    ids = torch.arange(pred_t.shape[0], device=pred_t.device)
+    return full[ids % world, ids].contiguous()

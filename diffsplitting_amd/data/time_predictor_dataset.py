@@ -3,7 +3,8 @@
 ``compute_input_normalization_dict`` (:6-21) is ``n + 1`` numpy passes over the whole frame set in the reference; here
 it is one HIP launch (``dsx_mix_range``, include/dsx.h) over the frames resident in HBM, bitwise equal to numpy's float64
 result.  ``TimePredictorDataset`` (:24-89) returns ``(inp, t)`` items whose mixing and min-max normalisation run in the
-fused tile kernel (``dsx_tiles_gather_mix``, channel 1).
+fused tile kernel (``dsx_tiles_gather_mix``, channel 1); ``batch`` cuts a whole batch of them, every item with its own
+drawn ``t``, in one launch (``dsx_tiles_gather_mix_items``).
 
 Refused loudly (training-time only): ``gaussian_noise_std_factor``, ``enable_transforms``, ``uncorrelated_channels``.
 """
@@ -91,3 +92,44 @@ class TimePredictorDataset(SplitDataset):
         lo, hi = self.input_normalization_dict[t_int]
         out = self.mixed_tiles_at([loc], t, (lo, hi, lo, hi), want=("cls",))
         return out["cls"][0, 1:2].cpu().numpy(), t
+
+    def batch(self, indices, t_ints=None):
+        """The items of ``indices`` as one batch -> ``(inp (B, 1, p, p) float32 on the device, t (B,) float64 numpy)``,
+        cut by ONE launch (dsx_tiles_gather_mix_items: every item its own t and its own table row).  Item k is bitwise
+        ``self[indices[k]]`` for the same draw.
+
+        ``t_ints`` None: location and ``sample_t()`` per index, in index order -- the ``np.random`` call sequence of
+        ``[self[i] for i in indices]``, so a seeded run draws the same values.  ``t_ints`` given: no random number is
+        consumed for t; each value must be an integer in 0..num_timesteps-1."""
+        self._grey_only("batch")
+        _lib.require_gpu()
+        indices = [int(i) for i in indices]
+        n = self._num_timesteps
+        if t_ints is not None:
+            given = list(t_ints)
+            if len(given) != len(indices):
+                raise DsxError(f"t_ints holds {len(given)} values for {len(indices)} indices")
+            for k, v in enumerate(given):
+                if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < n:
+                    raise DsxError(f"t_ints[{k}] = {v!r}: an integer in 0..{n - 1}")
+        locs, ts, rows = [], [], []
+        for k, index in enumerate(indices):
+            locs.append(self._get_location(index))
+            t, t_int = self.sample_t() if t_ints is None else (int(given[k]) / n, int(given[k]))
+            ts.append(t)
+            rows.append(t_int)
+        b, p, dev = len(indices), self._patch_size, self._dev[0].device
+        t = np.array(ts, dtype=np.float64).reshape(b)
+        cls = torch.empty((b, 2, p, p), dtype=torch.float32, device=dev)
+        if b:
+            loc = np.ascontiguousarray(np.asarray(locs, dtype=np.int64).reshape(b, 3))
+            lohi = np.array([self.input_normalization_dict[r] * 2 for r in rows], dtype=np.float64).reshape(b, 4)
+            i64 = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
+            pd = C.POINTER(C.c_double)
+            with torch.cuda.device(dev):
+                check(lib.dsx_tiles_gather_mix_items(
+                    C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()), i64(self._data_shape),
+                    i64((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)), b, self._norm4(), t.ctypes.data_as(pd),
+                    lohi.ctypes.data_as(pd), None, None, C.c_void_p(cls.data_ptr()),
+                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return cls[:, 1:2].contiguous(), t

@@ -19,6 +19,11 @@ A ``cifar10`` config with ``--datapath`` reads the pickle batches of its ``datap
 Colour items are not tiled: the run IS the validation report, over the whole validation set unless ``--items`` says
 otherwise, ``--batch-tiles`` items at a time; ``--results DIR`` writes the RGB triples and ``--out FILE.npy`` the
 predictions (N, 2 Cc, p, p) float32 in raw counts.
+
+A ``joint_indi`` config with ``--mix-t T`` runs the mixed-input prediction instead (``predict_tiled_mixed``, BASELINE
+C5): the two channels of every tile mixed at ``T``, ``indi1`` / ``indi2`` started at the time the TimePredictor of
+``--time-predictor CONFIG [--time-predictor-checkpoint PTH]`` estimates per tile (``--t-from given``: at ``T`` itself,
+no classifier), ``--mmse N`` repeats averaged.  Frames, ranks and ``--out`` as for the plain prediction.
 """
 import argparse
 import logging
@@ -158,6 +163,13 @@ def main(argv=None):
     ap.add_argument("--items", type=int, default=None,
                     help="items the validation report scores: default 19 with --validate, the whole validation set "
                          "for a cifar10 config with --datapath")
+    ap.add_argument("--mix-t", type=float, default=None,
+                    help="joint_indi only: the mixed-input prediction (predict_tiled_mixed) at this mixing weight")
+    ap.add_argument("--time-predictor", type=str, default=None, help="with --mix-t: the TimePredictor's JSON configuration")
+    ap.add_argument("--time-predictor-checkpoint", type=str, default=None, help="its state_dict file")
+    ap.add_argument("--mmse", type=int, default=None, help="with --mix-t: repeats averaged per tile (default 1)")
+    ap.add_argument("--t-from", type=str, choices=["classifier", "given"], default=None,
+                    help="with --mix-t: start times from the TimePredictor (default) or --mix-t itself")
     args = ap.parse_args(argv)
     if args.phase == "train":
         raise SystemExit("training is out of scope of the MI355X sampling engine; use -p val")
@@ -167,6 +179,7 @@ def main(argv=None):
         raise SystemExit("--out: a .npy or .tif file")
     if args.out and args.validate:
         raise SystemExit("--out writes the tiled prediction: not with --validate")
+    _check_mixed_args(args)
     n_ranks = args.gpus if args.gpus is not None else len(str(args.gpu_ids).split(","))
     if argv is None and parallel.needs_self_launch(n_ranks):
         # fresh child processes, started before anything here touches the GPU (never an exec after HIP init)
@@ -184,6 +197,8 @@ def main(argv=None):
         raise SystemExit("--out: colour items are written as (N, 2 Cc, p, p) .npy; a .tif hyperstack holds grey frames")
     if args.items is not None and args.items < 1:
         raise SystemExit("--items: a positive count")
+    if colour and args.mix_t is not None:
+        raise SystemExit("--mix-t: the mixed-input prediction takes two grey channels, not a cifar10 config")
     # -gpu selects the device(s): rank r of a torchrun launch drives gpu_ids[r] (the reference exports
     # CUDA_VISIBLE_DEVICES=gpu_ids instead, core/logger.py:59-65; mapping the index keeps one process per GPU
     # working without touching the environment after HIP may have been initialised)
@@ -204,6 +219,8 @@ def main(argv=None):
         _, val_set = get_datasets(opt, tiled_pred=not (args.validate or colour), norm_from=args.norm_from, device=dev)
         if args.validate or colour:
             return _run_validate(args, opt, diffusion, val_set, log, whole_set=colour)
+        if args.mix_t is not None:
+            return _predict_mixed(args, netG, val_set, n_steps, int(dsopt["patch_size"]), rank, world, log)
         return _predict(args, netG, val_set, n_steps, int(dsopt["patch_size"]), rank, world, dev, log)
     if args.frames:
         frames = _read_frames(args.frames)
@@ -226,6 +243,8 @@ def main(argv=None):
                                     device=dev)
     if args.validate:
         return _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log)
+    if args.mix_t is not None:
+        return _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log)
     return _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log)
 
 
@@ -258,6 +277,71 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
                 log.info("channel %d: RangeInvariantPsnr %.2f +- %.2f dB (random-init weights unless a checkpoint "
                          "was given in path.resume_state)", c, ps[:, c].mean().item(),
                          ps[:, c].std().item() if ps.shape[0] > 1 else 0.0)
+        if args.out:
+            _write_prediction(args.out, pred, val_set)
+            log.info("prediction written to %s", args.out)
+    return pred
+
+
+_MIXED_FLAGS = (("--mix-t", "mix_t"), ("--time-predictor", "time_predictor"),
+                ("--time-predictor-checkpoint", "time_predictor_checkpoint"), ("--mmse", "mmse"), ("--t-from", "t_from"))
+
+
+def _check_mixed_args(args):
+    """The flags of the mixed-input prediction, checked on the command line and the config file alone (nothing touches
+    the GPU, no rank is started): they need a ``joint_indi`` config and ``--mix-t``.  Without any of them: nothing."""
+    given = [flag for flag, name in _MIXED_FLAGS if getattr(args, name) is not None]
+    if not given:
+        return
+    which = (Logger.load_json(args.config).get("model") or {}).get("which_model_G")
+    if which != "joint_indi":
+        raise SystemExit(f"{', '.join(given)}: the mixed-input prediction runs indi1 and indi2 of a joint_indi config; "
+                         f"this config builds {which!r}")
+    if args.mix_t is None:
+        raise SystemExit(f"{', '.join(given)}: only with --mix-t T (the mixing weight of the mixed-input prediction)")
+    if not (np.isfinite(args.mix_t) and 0.0 <= args.mix_t <= 1.0):
+        raise SystemExit(f"--mix-t {args.mix_t}: a mixing weight in [0, 1]")
+    if args.validate:
+        raise SystemExit("--mix-t is a tiled prediction: not with --validate")
+    if args.mmse is not None and args.mmse < 1:
+        raise SystemExit(f"--mmse {args.mmse}: a positive count of repeats")
+    if (args.t_from or "classifier") == "classifier" and not args.time_predictor:
+        raise SystemExit("--t-from classifier (the default) needs --time-predictor CONFIG; --t-from given starts both "
+                         "samplers at --mix-t")
+    if args.time_predictor_checkpoint and not args.time_predictor:
+        raise SystemExit("--time-predictor-checkpoint: only with --time-predictor CONFIG")
+
+
+def _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log):
+    """``--mix-t``: ``predict_tiled_mixed`` of ``val_set`` over the ranks (the TimePredictor of ``--time-predictor``
+    chooses every tile's start time unless ``--t-from given``); ``pred_t`` is gathered so that rank 0 holds every
+    tile's value; rank 0 logs and writes ``--out``.  Returns the stitched canvas."""
+    from .data.tiled_predict import gather_pred_t, predict_tiled_mixed
+    t_from = args.t_from or "classifier"
+    tp = None
+    if t_from == "classifier":
+        from . import time_prediction
+        tp_opt = Logger.dict_to_nonedict(Logger.load_json(args.time_predictor))
+        if args.dtype:
+            tp_opt["model"]["compute_dtype"] = args.dtype
+        tp = time_prediction.build_time_predictor(tp_opt, args.time_predictor_checkpoint)
+        if args.time_predictor_checkpoint is None and rank == 0:
+            log.info("no --time-predictor-checkpoint given: the TimePredictor keeps its random initial weights")
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    (pred, ps), pred_t = predict_tiled_mixed(netG, tp, val_set, args.mix_t, num_timesteps=n_steps,
+                                             mmse_count=args.mmse or 1, batch_tiles=args.batch_tiles, t_from=t_from)
+    pred_t = gather_pred_t(pred_t)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if rank == 0:
+        total = val_set.plan.total
+        log.info("mixed-input prediction at t = %g (%s start times): %d tiles of %d^2, %d steps, mmse %d, %d GPU(s): "
+                 "%.3f s (%.1f tiles/s)", args.mix_t, t_from, total, patch, n_steps, args.mmse or 1, world, dt, total / dt)
+        for c in range(ps.shape[1]):
+            log.info("channel %d: RangeInvariantPsnr %.2f +- %.2f dB; predicted start time min %.4f mean %.4f max %.4f",
+                     c, ps[:, c].mean().item(), ps[:, c].std().item() if ps.shape[0] > 1 else 0.0,
+                     pred_t[:, c].min().item(), pred_t[:, c].mean().item(), pred_t[:, c].max().item())
         if args.out:
             _write_prediction(args.out, pred, val_set)
             log.info("prediction written to %s", args.out)

@@ -456,6 +456,22 @@ int dsx_tiles_gather_mix(const float* frames0_dev, const float* frames1_dev, con
                          int64_t count, const double norm[4], double t, const double lohi[4], float* target_dev,
                          float* mix_dev, float* cls_dev, void* stream);
 
+/* dsx_tiles_gather_mix for a batch whose items each carry their own mixing weight and table rows, in ONE launch: what
+ * the TimePredictor's validation loop feeds the network (time_prediction_training.py:133-140, every item of
+ * TimePredictorDataset draws its own t).  Item k is cut at patch_start_host[k] = (frame, y, x), mixed with t_host[k]
+ * and, for cls, min-max-normalised with lohi_host[k] = {lo0, hi0, lo1, hi1}; lohi_host may be NULL iff cls_dev is.
+ * Outputs as dsx_tiles_gather_mix: target / mix / cls, each (count, 2, ph, pw) fp32, any of them NULL (not all three);
+ * nothing outside them is written.  The arithmetic per item is the chain documented there, unchanged (fp32, every
+ * operation rounded on its own, no fma; 1.0 - t and hi - lo in double): item k is bitwise what dsx_tiles_gather_mix
+ * writes for that location with t_host[k] and lohi_host[k].  The per-item scalars travel with the patch-start table
+ * the call uploads (one allocation, one copy, one launch).  DSX_ERR_INVALID with a message that names the item, before
+ * any device work: a NULL pointer, a non-finite t[k] or statistic, a zero std, a non-finite or empty (hi == lo) row, a
+ * location outside the frame, count outside 0..65535. */
+int dsx_tiles_gather_mix_items(const float* frames0_dev, const float* frames1_dev, const int64_t data_shape[3],
+                               const int64_t patch_shape[3], const int64_t* patch_start_host, int64_t count,
+                               const double norm[4], const double* t_host, const double* lohi_host, float* target_dev,
+                               float* mix_dev, float* cls_dev, void* stream);
+
 /* The range table the classifier's inputs are normalised with (compute_input_normalization_dict,
  * data/time_predictor_dataset.py:6-21), in one launch instead of n + 1 host passes over the frame set: for every
  * t_int in 0..n_timesteps the min and max over all `pixels` of both stacks (all frames, flat) of
