@@ -43,11 +43,13 @@ FLAVOUR_SR3, FLAVOUR_DDPM = 0, 1
 LAYER_CONV, LAYER_ATTN, LAYER_FILM, LAYER_INPUT = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 TILING_TRIM, TILING_PAD, TILING_SHIFT = 0, 1, 2
+STREAM_ID_LIMIT, STREAM_DRAW_LIMIT = 1 << 40, 1 << 24      # per-sample noise streams: id < 2^40, draw < 2^24
 RESIZE_BILINEAR, RESIZE_BICUBIC = 2, 3
 PIX_U8, PIX_U16, PIX_U32, PIX_F32 = 0, 1, 2, 3
 
 _vp, _i, _i64, _u64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float
 _pi64, _pi32, _pf = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float)
+_pu64 = C.POINTER(C.c_uint64)
 
 # name -> (restype, argtypes); exactly the declarations of include/dsx.h
 SIGNATURES = {
@@ -94,6 +96,10 @@ SIGNATURES = {
     "dsx_posterior_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _i, _vp, _vp,
                                 _vp, _vp]),
     "dsx_interp_start": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "dsx_randn_samples": (_i, [_vp, _i, _i64, _u64, _pu64, C.c_uint32, _vp]),
+    "dsx_sample_loop_streams": (_i, [_vp, C.POINTER(StepTable), _vp, _vp, _vp, _u64, _pi32, _i, _vp, _i, _vp, _pu64, _i]),
+    "dsx_posterior_step_streams": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _i, _vp,
+                                        _vp, _vp, _vp, _pu64, _i]),
     "dsx_val_report": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.POINTER(C.c_double),
                             C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dsx_tile_plan": (_i64, [_pi64, _pi64, _pi64, _i, _pi64, _pi64, _i64]),

@@ -219,11 +219,13 @@ static int ensure_table(dsx_exec* ex, const dsx_step_table* tab) {
   return DSX_OK;
 }
 
-// a pinned staging slot holding this call's table [6][cap] followed by {seed, noise address}; *out = its host pointer
-static int stage_call(dsx_exec* ex, const dsx_step_table* tab, uint64_t seed, const float* noise, dsx_exec::Staging** out) {
+// a pinned staging slot holding this call's table [6][cap] followed by {seed, noise address} and, with per-sample
+// noise streams, the B sample ids; *out = its host pointer
+static int stage_call(dsx_exec* ex, const dsx_step_table* tab, uint64_t seed, const float* noise, const uint64_t* ids,
+                      dsx_exec::Staging** out) {
   const int cap = ex->table_cap;
   const int T = tab->n_steps * (tab->per_sample > 0 ? tab->per_sample : 1);
-  const size_t need = (size_t)6 * cap + 4;   // + 16 bytes of loop parameters
+  const size_t need = (size_t)6 * cap + 4 + (ids ? (size_t)2 * ex->B : 0);   // + 16 bytes of loop parameters (+ ids)
   dsx_exec::Staging& sl = ex->staging[ex->staging_next];
   ex->staging_next = (ex->staging_next + 1) % 4;
   if (sl.busy) { HIP_TRY(hipEventSynchronize(sl.ev.e)); sl.busy = false; }
@@ -240,11 +242,12 @@ static int stage_call(dsx_exec* ex, const dsx_step_table* tab, uint64_t seed, co
     if (cols[k]) memcpy(host + (size_t)k * cap, cols[k], (size_t)T * 4);
   unsigned long long lp[2] = {seed, (unsigned long long)(uintptr_t)noise};
   memcpy(host + (size_t)6 * cap, lp, 16);
+  if (ids) memcpy(host + (size_t)6 * cap + 4, ids, (size_t)ex->B * 8);
   *out = &sl;
   return DSX_OK;
 }
 
-static int enqueue_step(dsx_exec* ex, const dsx_step_table* tab, bool use_noise, hipStream_t st) {
+static int enqueue_step(dsx_exec* ex, const dsx_step_table* tab, bool use_noise, bool streams, hipStream_t st) {
   int rc = run_unet(ex, true, tab->per_sample > 0 ? ex->B : 1, st, tab->per_sample > 0 ? 1 : 0);
   if (rc) return rc;
   UpdateArgs u{};
@@ -253,14 +256,17 @@ static int enqueue_step(dsx_exec* ex, const dsx_step_table* tab, bool use_noise,
   u.tab = ex->table.as<float>(); u.n_steps = ex->table_cap; u.step_ctr = ex->step_ctr;
   u.predict_eps = tab->predict_eps; u.clip = tab->clip; u.per_sample = tab->per_sample > 0 ? 1 : 0;
   u.B = ex->B; u.C = ex->x_c; u.H = ex->H; u.W = ex->W;
+  u.sample_ids = streams ? ex->sample_ids.as<unsigned long long>() : nullptr;   // the executor's buffer, not the ids
   HIP_TRY(launch_update(u, st));
   HIP_TRY(launch_advance(ex->step_ctr, st));
   return DSX_OK;
 }
 
-extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x,
-                               const float* noise, uint64_t seed, const int32_t* snap_steps, int n_snap,
-                               float* snaps, int use_graph, void* stream) {
+// ids == nullptr: the default noise (one stream per step at the flat batch index); else B sample ids, checked by
+// the caller
+static int sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x, const float* noise,
+                       uint64_t seed, const int32_t* snap_steps, int n_snap, float* snaps, int use_graph, void* stream,
+                       const uint64_t* ids) {
   if (!ex || !tab || !x || tab->n_steps < 1) return fail(DSX_ERR_INVALID, "bad argument");
   if (!tab->tcond || !tab->c1 || !tab->c2 || !tab->sigma || (tab->predict_eps && (!tab->a || !tab->b)))
     return fail(DSX_ERR_INVALID, "step table columns missing");
@@ -276,9 +282,13 @@ extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const fl
   // per-call values (step table; seed, noise address: the captured step does not bake them in) go to device memory
   // from a pinned staging slot of this call's own
   dsx_exec::Staging* sl = nullptr;
-  if ((rc = stage_call(ex, tab, seed, noise, &sl))) return rc;
+  if (ids && !ex->sample_ids.p) HIP_TRY(ex->sample_ids.alloc((size_t)ex->B * 8));   // once: captured steps keep the address
+  if ((rc = stage_call(ex, tab, seed, noise, ids, &sl))) return rc;
   HIP_TRY(hipMemcpyAsync(ex->table.p, sl->host.p, (size_t)6 * ex->table_cap * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(ex->loop_params, sl->host.as<float>() + (size_t)6 * ex->table_cap, 16, hipMemcpyHostToDevice, st));
+  if (ids)
+    HIP_TRY(hipMemcpyAsync(ex->sample_ids.p, sl->host.as<float>() + (size_t)6 * ex->table_cap + 4, (size_t)ex->B * 8,
+                           hipMemcpyHostToDevice, st));
   HIP_TRY(hipEventRecord(sl->ev.e, st));
   sl->busy = true;
   HIP_TRY(hipMemsetAsync(ex->step_ctr, 0, 4, st));
@@ -287,15 +297,16 @@ extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const fl
   const size_t snap_elems = (size_t)ex->B * ex->x_c * ex->H * ex->W;
   bool graph_ok = false;
   if (use_graph) {
-    // the captured step bakes in the mode flags only (not the step count, the seed or the noise address)
-    std::vector<float> sig = {(float)tab->predict_eps, (float)tab->clip, noise ? 1.f : 0.f, tab->per_sample > 0 ? 1.f : 0.f};
+    // the captured step bakes in the mode flags only (not the step count, the seed, the noise address or the sample ids)
+    std::vector<float> sig = {(float)tab->predict_eps, (float)tab->clip, noise ? 1.f : 0.f, tab->per_sample > 0 ? 1.f : 0.f,
+                              ids ? 1.f : 0.f};
     if (!ex->graph.exec || sig != ex->graph_sig) {
       if ((rc = drop_graph(ex))) return rc;
       Stream cs;
       HIP_TRY(cs.create(hipStreamNonBlocking));
       hipError_t e = hipStreamBeginCapture(cs.s, hipStreamCaptureModeThreadLocal);
       if (e == hipSuccess) {
-        rc = enqueue_step(ex, tab, noise != nullptr, cs.s);
+        rc = enqueue_step(ex, tab, noise != nullptr, ids != nullptr, cs.s);
         hipError_t e2 = hipStreamEndCapture(cs.s, &ex->graph.graph);
         if (rc == DSX_OK && e2 == hipSuccess) e2 = hipGraphInstantiate(&ex->graph.exec, ex->graph.graph, nullptr, nullptr, 0);
         if (rc != DSX_OK || e2 != hipSuccess) {
@@ -315,7 +326,7 @@ extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const fl
   int snap_i = 0;
   for (int s = 0; s < T; ++s) {
     if (graph_ok) HIP_TRY(hipGraphLaunch(ex->graph.exec, st));
-    else if ((rc = enqueue_step(ex, tab, noise != nullptr, st))) return rc;
+    else if ((rc = enqueue_step(ex, tab, noise != nullptr, ids != nullptr, st))) return rc;
     while (snap_i < n_snap && snap_steps[snap_i] == s) {
       HIP_TRY(launch_nhwc_to_nchw(ex->x_state, snaps + (size_t)snap_i * snap_elems, ex->B, ex->x_c, ex->H,
                                   ex->W, st));
@@ -323,6 +334,50 @@ extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const fl
     }
   }
   HIP_TRY(launch_nhwc_to_nchw(ex->x_state, x, ex->B, ex->x_c, ex->H, ex->W, st));
+  return DSX_OK;
+}
+
+extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x,
+                               const float* noise, uint64_t seed, const int32_t* snap_steps, int n_snap,
+                               float* snaps, int use_graph, void* stream) {
+  return sample_loop(ex, tab, cond, x, noise, seed, snap_steps, n_snap, snaps, use_graph, stream, nullptr);
+}
+
+// ---- per-sample noise streams (include/dsx.h): the sample stream (seed, id, draw) is the stream (seed, id << 24 | draw)
+static int stream_ids_ok(const char* what, const uint64_t* ids, int n_ids, int B, uint64_t draw_last) {
+  if (!ids) return fail(DSX_ERR_INVALID, "%s: sample_ids is null", what);
+  if (n_ids != B) return fail(DSX_ERR_INVALID, "%s: %d sample ids for a batch of %d", what, n_ids, B);
+  if (draw_last >= DSX_STREAM_DRAW_LIMIT)
+    return fail(DSX_ERR_INVALID, "%s: draw ordinal %llu out of range (draw < 2^24)", what, (unsigned long long)draw_last);
+  for (int b = 0; b < B; ++b)
+    if (ids[b] >= DSX_STREAM_ID_LIMIT)
+      return fail(DSX_ERR_INVALID, "%s: sample id %llu (entry %d) out of range (id < 2^40)", what, (unsigned long long)ids[b], b);
+  return DSX_OK;
+}
+
+extern "C" int dsx_sample_loop_streams(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x,
+                                       const float* noise, uint64_t seed, const int32_t* snap_steps, int n_snap,
+                                       float* snaps, int use_graph, void* stream, const uint64_t* sample_ids,
+                                       int n_sample_ids) {
+  if (!ex || !tab) return fail(DSX_ERR_INVALID, "sample_loop_streams: null executor or step table");
+  if (noise) return fail(DSX_ERR_INVALID, "sample_loop_streams: injected noise together with sample_ids");
+  const int rc = stream_ids_ok("sample_loop_streams", sample_ids, n_sample_ids, ex->B, (uint64_t)std::max(tab->n_steps, 0));
+  if (rc) return rc;
+  return sample_loop(ex, tab, cond, x, nullptr, seed, snap_steps, n_snap, snaps, use_graph, stream, sample_ids);
+}
+
+extern "C" int dsx_randn_samples(float* out, int B, int64_t chw, uint64_t seed, const uint64_t* ids, uint32_t draw,
+                                 void* stream) {
+  if (!out || B < 1 || chw < 1) return fail(DSX_ERR_INVALID, "randn_samples: null output or empty shape (%d, %lld)", B, (long long)chw);
+  if ((int64_t)B * chw > ((int64_t)1 << 40)) return fail(DSX_ERR_INVALID, "randn_samples: tensor too large");
+  const int rc = stream_ids_ok("randn_samples", ids, B, B, draw);
+  if (rc) return rc;
+  for (int b0 = 0; b0 < B; b0 += kStreamRows) {     // the ids travel in the kernel arguments, kStreamRows per launch
+    StreamIds s{};
+    const int rows = std::min(B - b0, kStreamRows);
+    for (int r = 0; r < rows; ++r) s.subseq[r] = (ids[b0 + r] << 24) | draw;
+    HIP_TRY(launch_randn_samples(out + (size_t)b0 * chw, rows, chw, seed, s, (hipStream_t)stream));
+  }
   return DSX_OK;
 }
 
@@ -436,6 +491,33 @@ extern "C" int dsx_posterior_step(const float* x, const float* net, int B, int C
   PosteriorStepArgs p{x, net, a, b, c1, c2, sigma, x_out ? z : nullptr, seed, subseq, x_recon_out, mean_out, x_out,
                       B, predict_eps ? 1 : 0, clip ? 1 : 0, repeat_noise ? 1 : 0, (int64_t)C * H * W};
   HIP_TRY(launch_posterior_step(p, (int64_t)H * W, (hipStream_t)stream));
+  return DSX_OK;
+}
+extern "C" int dsx_posterior_step_streams(const float* x, const float* net, int B, int C, int H, int W, const float* a,
+                                          const float* b, const float* c1, const float* c2, const float* sigma,
+                                          int predict_eps, int clip, const float* z, uint64_t seed, uint64_t draw,
+                                          int repeat_noise, float* x_recon_out, float* mean_out, float* x_out,
+                                          void* stream, const uint64_t* sample_ids, int n_sample_ids) {
+  int rc = steps_shape("posterior_step_streams", B, C, H, W);
+  if (rc) return rc;
+  if (z) return fail(DSX_ERR_INVALID, "posterior_step_streams: injected noise together with sample_ids");
+  if (repeat_noise) return fail(DSX_ERR_INVALID, "posterior_step_streams: repeat_noise together with sample_ids");
+  if ((rc = stream_ids_ok("posterior_step_streams", sample_ids, n_sample_ids, B, draw))) return rc;
+  if (!x || !net || !c1 || !c2 || !sigma) return fail(DSX_ERR_INVALID, "posterior_step_streams: null argument");
+  if (predict_eps && (!a || !b)) return fail(DSX_ERR_INVALID, "posterior_step_streams: predict_eps needs the columns a and b");
+  if (!x_recon_out && !mean_out && !x_out) return fail(DSX_ERR_INVALID, "posterior_step_streams: every output is null");
+  const int64_t CHW = (int64_t)C * H * W;
+  for (int b0 = 0; b0 < B; b0 += kStreamRows) {     // kStreamRows samples per launch: their ids are kernel arguments
+    StreamIds s{};
+    const int rows = std::min(B - b0, kStreamRows);
+    for (int r = 0; r < rows; ++r) s.subseq[r] = (sample_ids[b0 + r] << 24) | draw;
+    const size_t off = (size_t)b0 * CHW;
+    auto at = [&](float* p) { return p ? p + off : nullptr; };
+    PosteriorStepArgs p{x + off, net + off, a ? a + b0 : nullptr, b ? b + b0 : nullptr, c1 + b0, c2 + b0, sigma + b0,
+                        nullptr, seed, 0, at(x_recon_out), at(mean_out), at(x_out),
+                        rows, predict_eps ? 1 : 0, clip ? 1 : 0, 0, CHW};
+    HIP_TRY(launch_posterior_step_streams(p, s, (int64_t)H * W, (hipStream_t)stream));
+  }
   return DSX_OK;
 }
 extern "C" int dsx_interp_start(const float* x1, const float* x2, int B, int C, int H, int W, const float* a0,

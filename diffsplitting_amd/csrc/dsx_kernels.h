@@ -404,8 +404,19 @@ struct UpdateArgs {
   int predict_eps, clip;
   int per_sample;         // the table columns hold [step][B] values instead of one per step
   int B, C, H, W;
+  // per-sample noise streams (include/dsx.h): device array of B sample ids, read at every step -> the stream form of
+  // the kernel (element (b, c, hw) takes element c*H*W + hw of the stream (seed, ids[b] << 24 | step + 1)); nullptr ->
+  // the default form, one stream per step at the flat NHWC index
+  const unsigned long long* sample_ids;
 };
 hipError_t launch_update(const UpdateArgs& a, hipStream_t st);
+// Per-sample noise streams without an executor: the Philox subsequences (id << 24 | draw) of up to kStreamRows samples
+// travel in the kernel arguments; larger batches take several launches.
+constexpr int kStreamRows = 32;
+struct StreamIds { unsigned long long subseq[kStreamRows]; };
+// out (rows, chw): row r = the first chw elements of the stream (seed, s.subseq[r]); rows <= kStreamRows
+hipError_t launch_randn_samples(float* out, int rows, long long chw, unsigned long long seed, const StreamIds& s,
+                                hipStream_t st);
 hipError_t launch_advance(int* step_ctr, hipStream_t st);
 hipError_t launch_randn(float* out, long long n, unsigned long long seed, unsigned long long subseq,
                         hipStream_t st);
@@ -545,6 +556,21 @@ __device__ __forceinline__ void normal4(unsigned long long seed, unsigned long l
   sincosf(6.283185307179586f * u3, &s, &c);
   z[2] = rb * c; z[3] = rb * s;
 }
+// Component k (0..3) of normal4(seed, subseq, idx4), bit for bit: the same operations on the half of the Philox block
+// it comes from.  For kernels whose neighbouring elements lie in different blocks (per-sample noise streams).
+__device__ __forceinline__ float normal1(unsigned long long seed, unsigned long long subseq,
+                                         unsigned long long idx4, int k) {
+  unsigned r[4];
+  philox4x32_10((unsigned)idx4, (unsigned)(idx4 >> 32), (unsigned)subseq, (unsigned)(subseq >> 32),
+                (unsigned)seed, (unsigned)(seed >> 32), r);
+  const unsigned ru = (k & 2) ? r[2] : r[0], rv = (k & 2) ? r[3] : r[1];
+  const float u = ((float)ru + 0.5f) * 2.3283064365386963e-10f;  // (0,1)
+  const float v = ((float)rv + 0.5f) * 2.3283064365386963e-10f;
+  const float rad = sqrtf(-2.0f * logf(u));
+  float s, c;
+  sincosf(6.283185307179586f * v, &s, &c);
+  return rad * ((k & 1) ? s : c);
+}
 #endif
 
 // dsx_steps.hip.  q_sample of the three sampler families in one launch (NCHW fp32):
@@ -597,6 +623,9 @@ struct PosteriorStepArgs {
   long long CHW;
 };
 hipError_t launch_posterior_step(const PosteriorStepArgs& a, long long HW, hipStream_t st);
+// the same with z = element (i % CHW) of the stream (a.seed, s.subseq[i / CHW]); a.z, a.subseq and a.repeat are not
+// read; a.B <= kStreamRows
+hipError_t launch_posterior_step_streams(const PosteriorStepArgs& a, const StreamIds& s, long long HW, hipStream_t st);
 // out = c*(a0[b]*x1 + s0[b]*z1) + d*(a0[b]*x2 + s0[b]*z2); z1 == nullptr: the streams (seed, subseq), (seed, subseq + 1)
 struct InterpStartArgs {
   const float* x1; const float* x2; const float* a0; const float* s0;

@@ -343,13 +343,47 @@ hipError_t launch_randn(float* out, long long n, unsigned long long seed, unsign
   hipLaunchKernelGGL(k_randn, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, out, n, seed, subseq);
   return hipGetLastError();
 }
+// Per-sample noise streams (include/dsx.h): row blockIdx.y of out (rows, chw) = the first chw elements of the stream
+// (seed, s.subseq[row]), i.e. what k_randn writes for that subsequence.  VEC: chw is a multiple of 4 and out is 16-byte
+// aligned, so every Philox block of every row is one 16-byte store; otherwise scalar stores, the last block cut at chw.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_randn_samples(float* __restrict__ out, long long chw, unsigned long long seed,
+                                                       const StreamIds s) {
+  const unsigned long long subseq = s.subseq[blockIdx.y];
+  float* __restrict__ row = out + (size_t)blockIdx.y * chw;
+  const long long n4 = (chw + 3) / 4;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4;
+       i += (long long)gridDim.x * blockDim.x) {
+    float z[4];
+    normal4(seed, subseq, (unsigned long long)i, z);
+    if (VEC) {
+      *(float4*)(row + i * 4) = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) if (i * 4 + j < chw) row[i * 4 + j] = z[j];
+    }
+  }
+}
+hipError_t launch_randn_samples(float* out, int rows, long long chw, unsigned long long seed, const StreamIds& s,
+                                hipStream_t st) {
+  if (rows < 1 || rows > kStreamRows) return hipErrorInvalidValue;
+  const bool vec = chw % 4 == 0 && aligned16(out);
+  hipLaunchKernelGGL(vec ? k_randn_samples<true> : k_randn_samples<false>, dim3(grid_for((chw + 3) / 4), (unsigned)rows),
+                     dim3(256), 0, st, out, chw, seed, s);
+  return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------
 // Sampler update (sr3 diffusion.py:141-175 / ddpm diffusion.py:194-203 /
 // indi.py:62-69): step_update (dsx_kernels.h), the arithmetic k_posterior_step
 // shares, so the loop and the single steps round alike.
 // The step index lives in device memory so one captured graph replays T times.
+// STREAMS: per-sample noise streams (include/dsx.h).  The state is NHWC, so the four elements of a group may lie in
+// different pixels, channels (C = 3) and samples: each looks up its own (b, c, hw), the stream of its sample
+// (a.sample_ids[b] << 24 | step + 1) and component (c*HW + hw) % 4 of Philox block (c*HW + hw) / 4 -- the element the
+// NCHW tensor of dsx_randn_samples holds there.  No draw and no sum where sigma == 0.
 // ---------------------------------------------------------------------------
+template <bool STREAMS>
 __global__ void k_update(const UpdateArgs a) {
   const int step = *a.step_ctr;
   const int T = a.n_steps;
@@ -366,7 +400,7 @@ __global__ void k_update(const UpdateArgs a) {
   for (long long i4 = blockIdx.x * (long long)blockDim.x + threadIdx.x; i4 < n4;
        i4 += (long long)gridDim.x * blockDim.x) {
     float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!a.use_noise && (a.per_sample || sg != 0.f)) normal4(seed, (unsigned long long)step + 1, (unsigned long long)i4, z);
+    if (!STREAMS && !a.use_noise && (a.per_sample || sg != 0.f)) normal4(seed, (unsigned long long)step + 1, (unsigned long long)i4, z);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const long long i = i4 * 4 + j;  // NHWC linear index
@@ -383,7 +417,14 @@ __global__ void k_update(const UpdateArgs a) {
         ca = a.tab[1 * (size_t)T + k]; cb = a.tab[2 * (size_t)T + k];
         c1 = a.tab[3 * (size_t)T + k]; c2 = a.tab[4 * (size_t)T + k]; sg = a.tab[5 * (size_t)T + k];
       }
-      const float xn = step_update(ca, cb, c1, c2, sg, a.predict_eps, a.clip, a.x[i], a.net[i], zz, true).out;
+      if (STREAMS && sg != 0.f) {
+        const int c = (int)(i % a.C);
+        const long long p = i / a.C;
+        const long long b = p / HW, e = c * HW + p % HW;              // e: the element's NCHW index inside its sample
+        zz = normal1(seed, (a.sample_ids[b] << 24) | (unsigned long long)(step + 1), (unsigned long long)(e >> 2), (int)(e & 3));
+      }
+      // the stream form adds nothing where sigma == 0, as the single step does (k_posterior_step): the two agree bitwise
+      const float xn = step_update(ca, cb, c1, c2, sg, a.predict_eps, a.clip, a.x[i], a.net[i], zz, !STREAMS || sg != 0.f).out;
       a.x[i] = xn;
       if (a.x_act) store1_act(a.x_act, (size_t)i, xn, a.x_act_kind);
     }
@@ -391,7 +432,7 @@ __global__ void k_update(const UpdateArgs a) {
 }
 hipError_t launch_update(const UpdateArgs& a, hipStream_t st) {
   const long long n4 = ((long long)a.B * a.H * a.W * a.C + 3) / 4;
-  hipLaunchKernelGGL(k_update, dim3(grid_for(n4)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(a.sample_ids ? k_update<true> : k_update<false>, dim3(grid_for(n4)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 __global__ void k_advance(int* ctr) { if (threadIdx.x == 0) *ctr += 1; }

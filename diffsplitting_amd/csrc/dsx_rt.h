@@ -299,6 +299,8 @@ struct dsx_exec {
   bool temb_from_table = false;
   unsigned* handoff_timeouts = nullptr;        // device counter: bounded FULL / FREE spins of k_conv_ws that gave up (0 in a correct run)
   unsigned long long* loop_params = nullptr;   // device {seed, noise address}: per-call values the captured step reads
+  DevBuf sample_ids;                           // device uint64 [B], allocated by the first loop with per-sample noise streams and
+                                               // kept: a captured step holds its address, every call writes its ids there
   // per-call host data (step table, seed, noise address) is staged in pinned memory, one slot per call in flight: a
   // slot is reused only after the event recorded behind its copies has completed, so a second dsx_sample_loop on the
   // same executor never overwrites bytes an earlier call's asynchronous copy has yet to read

@@ -84,8 +84,10 @@ hipError_t launch_q_sample(const QSampleArgs& a, hipStream_t st) {
 // stream (seed, subseq); C*H*W being a multiple of 4 under VEC, a group is one whole Philox block under `repeat` too.
 // x_out may be x: a thread reads its four elements before it writes them.
 // ---------------------------------------------------------------------------
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_posterior_step(const PosteriorStepArgs a) {
+// STREAMS (ids != nullptr): per-sample noise streams (include/dsx.h): element j of sample b takes element j of the stream
+// (seed, ids[b]); under VEC a group is one whole Philox block of its sample's stream.
+template <bool VEC, bool STREAMS>
+__device__ __forceinline__ void posterior_step_body(const PosteriorStepArgs& a, const unsigned long long* ids) {
   const long long CHW = a.CHW, n = (long long)a.B * CHW;
   for (long long i4 = blockIdx.x * (long long)blockDim.x + threadIdx.x; i4 < (n + 3) / 4;
        i4 += (long long)gridDim.x * blockDim.x) {
@@ -94,12 +96,20 @@ __global__ __launch_bounds__(256) void k_posterior_step(const PosteriorStepArgs 
     rows4<VEC>(at, cnt, CHW, b);
     bool use_z[4] = {false, false, false, false}, any = false;
     DSX_EACH4(j, cnt) {
-      zi[j] = a.repeat ? at[j] - b[j] * CHW : at[j];
+      zi[j] = (STREAMS || a.repeat) ? at[j] - b[j] * CHW : at[j];
       use_z[j] = a.x_out != nullptr && a.sigma[b[j]] != 0.f;
       any = any || use_z[j];
     }
     float z[4] = {0.f, 0.f, 0.f, 0.f}, x[4], net[4], x0[4], mean[4], out[4];
-    if (any) normals4<VEC>(a.z, a.seed, a.subseq, zi, !a.repeat, cnt, z);
+    if (STREAMS) {
+      if (VEC) {
+        if (any) normal4(a.seed, ids[b[0]], (unsigned long long)(zi[0] >> 2), z);
+      } else {
+        DSX_EACH4(j, cnt) if (use_z[j]) z[j] = normal1(a.seed, ids[b[j]], (unsigned long long)(zi[j] >> 2), (int)(zi[j] & 3));
+      }
+    } else if (any) {
+      normals4<VEC>(a.z, a.seed, a.subseq, zi, !a.repeat, cnt, z);
+    }
     load4<VEC>(a.x, at, cnt, x);
     load4<VEC>(a.net, at, cnt, net);
     DSX_EACH4(j, cnt) {
@@ -113,9 +123,24 @@ __global__ __launch_bounds__(256) void k_posterior_step(const PosteriorStepArgs 
     if (a.x_out) store4<VEC>(a.x_out, at, cnt, out);
   }
 }
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_posterior_step(const PosteriorStepArgs a) {
+  posterior_step_body<VEC, false>(a, nullptr);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_posterior_step_streams(const PosteriorStepArgs a, const StreamIds s) {
+  posterior_step_body<VEC, true>(a, s.subseq);
+}
 hipError_t launch_posterior_step(const PosteriorStepArgs& a, long long HW, hipStream_t st) {
   const bool vec = HW % 4 == 0 && aligned16(a.x, a.net, a.z, a.x_recon_out, a.mean_out, a.x_out);
   return launch_groups4(vec ? k_posterior_step<true> : k_posterior_step<false>, a, (long long)a.B * a.CHW, st);
+}
+hipError_t launch_posterior_step_streams(const PosteriorStepArgs& a, const StreamIds& s, long long HW, hipStream_t st) {
+  if (a.B < 1 || a.B > kStreamRows) return hipErrorInvalidValue;
+  const bool vec = HW % 4 == 0 && aligned16(a.x, a.net, a.x_recon_out, a.mean_out, a.x_out);
+  hipLaunchKernelGGL(vec ? k_posterior_step_streams<true> : k_posterior_step_streams<false>,
+                     dim3(grid_for(((long long)a.B * a.CHW + 3) / 4)), dim3(256), 0, st, a, s);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------

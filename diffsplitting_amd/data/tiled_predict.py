@@ -52,7 +52,7 @@ class TileExchange:
 
 @torch.no_grad()
 def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8, sampler_kwargs=None,
-                  group=None, lpips=None, target_frames=None):
+                  group=None, lpips=None, target_frames=None, seed=None):
     """``frames_input``: (N,H,W) fp32 CUDA tensor, already normalised (the network input channel).
     Returns the stitched prediction (N,H,W,C) on every rank and the ``TilePlan``.
 
@@ -61,7 +61,11 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
     target_frames, canvas, lpips)``: per channel the LPIPS of every frame, computed on the device.
 
     ``netG`` is what ``define_G`` returns (InDI / JointIndi sampler); its full-batch
-    output (``last_full_batch``) is used, not the single element the reference API returns."""
+    output (``last_full_batch``) is used, not the single element the reference API returns.
+
+    ``seed``: per-sample noise streams (include/dsx.h) with a tile's id as its sample id: a tile's noise then does not
+    depend on ``batch_tiles``, on the order of the batches or on the number of ranks, and neither does its prediction
+    as long as the batch size is the same (the planner may pick other kernels for another)."""
     if grid_size is None:
         grid_size = patch_size // 2                                   # split_dataset_tiledpred.py:13-14
     N, H, W = frames_input.shape
@@ -73,6 +77,8 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
     for i in range(0, len(ids), batch_tiles):
         chunk = ids[i:i + batch_tiles]
         tiles = plan.gather(frames_input, chunk).unsqueeze(1)         # (b,1,p,p)
+        if seed is not None:
+            kw.update(seed=seed, sample_ids=chunk)
         netG.inference(tiles, continuous=False, **kw)
         ex.add(netG.last_full_batch, chunk)
     canvas = ex.finish()
@@ -125,7 +131,7 @@ def evaluate_time_predictor(val_set, time_predictor, num_timesteps=20, batch_til
 
 @torch.no_grad()
 def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1, mmse_count=1, batch_tiles=8,
-                        t_from="classifier", table=None, table_timesteps=100, group=None, lpips=None):
+                        t_from="classifier", table=None, table_timesteps=100, group=None, lpips=None, seed=None):
     """The out-of-distribution split of notebooks/EvaluateJointIndiIterative.ipynb cells 59-64, batched: the two
     channels of every tile of ``val_set`` (a ``SplitDatasetTiledPred``) mixed at ``mixing_t`` -> the TimePredictor's
     estimate of the mixing time per tile (``pred_t_0 = 1 - TP(cls[:, 0])``, ``pred_t_1 = TP(cls[:, 1])``, cell 40) ->
@@ -145,7 +151,10 @@ def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1
 
     ``lpips``: a ``core.lpips.LPIPS``; with it the first element is ``(canvas, psnr, lpips_dict)``, the per-frame LPIPS of
     every channel against the same normalised target (``core.metrics.calculate_lpips``; its min-max map makes it
-    invariant under the de-normalisation too)."""
+    invariant under the de-normalisation too).
+
+    ``seed``: per-sample noise streams; MMSE repeat ``r`` of tile ``k`` draws from sample id ``k + r * plan.total``
+    (``indi2`` from the same id with bit 39 set), whatever batch or rank it runs in."""
     if t_from not in ("classifier", "given"):
         raise ValueError("t_from must be 'classifier' or 'given'")
     i1, i2 = netG.indi1, netG.indi2
@@ -174,10 +183,14 @@ def predict_tiled_mixed(netG, time_predictor, val_set, mixing_t, num_timesteps=1
             t1 = t2 = mixing_t
             pred_t[chunk[0]:chunk[-1] + 1:ex.world] = float(mixing_t)
         acc1 = acc2 = None
-        for _ in range(int(mmse_count)):                              # as core/psnr_based_t_refinement.py:26-39
-            i1.inference(in1, continuous=False, num_timesteps=num_timesteps, t_float_start=t1)
+        for r in range(int(mmse_count)):                              # as core/psnr_based_t_refinement.py:26-39
+            k1 = k2 = {}
+            if seed is not None:
+                rep_ids = [k + r * plan.total for k in chunk]
+                k1, k2 = dict(seed=seed, sample_ids=rep_ids), dict(seed=seed, sample_ids=netG.second_ids(rep_ids))
+            i1.inference(in1, continuous=False, num_timesteps=num_timesteps, t_float_start=t1, **k1)
             acc1 = i1.last_full_batch.clone() if acc1 is None else acc1 + i1.last_full_batch
-            i2.inference(in2, continuous=False, num_timesteps=num_timesteps, t_float_start=t2)
+            i2.inference(in2, continuous=False, num_timesteps=num_timesteps, t_float_start=t2, **k2)
             acc2 = i2.last_full_batch.clone() if acc2 is None else acc2 + i2.last_full_batch
         ex.add(torch.cat([acc1, acc2], dim=1) / mmse_count, chunk)
     if lpips is None:

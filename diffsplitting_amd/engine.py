@@ -316,12 +316,21 @@ class UNetEngine:
         return y
 
     def sample_loop(self, table, x_init, cond=None, noise=None, seed=0, snapshot_steps=(),
-                    use_graph=True, stream=None, slot=0):
+                    use_graph=True, stream=None, slot=0, sample_ids=None):
         """Runs ``table`` (a ``StepTableHost``) from ``x_init`` (B,C,H,W) in place.
         Returns (final_state, snapshots) with snapshots (n_snap,B,C,H,W) or None.
-        Asynchronous on the current (or given) stream."""
+        Asynchronous on the current (or given) stream.
+
+        ``sample_ids`` (B integers): per-sample noise streams (``dsx_sample_loop_streams``): step ``s`` of sample ``b``
+        draws ``randn_samples(.., seed, sample_ids, draw=s + 1)[b]`` whatever the batch it sits in; not together with
+        ``noise``."""
         x = x_init.contiguous()
         B, Cx, H, W = x.shape
+        ids = None
+        if sample_ids is not None:
+            if noise is not None:
+                raise DsxError("sample_ids together with injected noise: the draws come from one or the other")
+            ids = _sample_ids(sample_ids, B)
         cc = 0 if cond is None else cond.shape[1]
         ex = self.executor(B, H, W, cc, slot)
         if cond is not None:
@@ -342,10 +351,13 @@ class UNetEngine:
                 if t is not None:
                     t.record_stream(stream)
         sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
-        check(lib.dsx_sample_loop(ex, C.byref(table.c_struct()), _dptr(cond), _dptr(x), _dptr(noise),
-                                  C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                  steps.ctypes.data_as(C.POINTER(C.c_int32)) if len(steps) else None,
-                                  len(steps), _dptr(snaps), 1 if use_graph else 0, sp))
+        args = (ex, C.byref(table.c_struct()), _dptr(cond), _dptr(x), _dptr(noise), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                steps.ctypes.data_as(C.POINTER(C.c_int32)) if len(steps) else None, len(steps), _dptr(snaps),
+                1 if use_graph else 0, sp)
+        if ids is None:
+            check(lib.dsx_sample_loop(*args))
+        else:
+            check(lib.dsx_sample_loop_streams(*args, ids.ctypes.data_as(_lib._pu64), len(ids)))
         return x, snaps
 
 
@@ -528,6 +540,41 @@ def randn(shape, seed, subsequence=0, device="cuda"):
     return out
 
 
+def _sample_ids(sample_ids, B, limit=_lib.STREAM_ID_LIMIT):
+    """``sample_ids`` as B uint64 values (numpy), refused by name when the count or a value does not fit."""
+    if torch.is_tensor(sample_ids):
+        sample_ids = sample_ids.detach().cpu().tolist()
+    ids = [int(v) for v in sample_ids]
+    if len(ids) != B:
+        raise DsxError(f"sample_ids must hold B = {B} ids, got {len(ids)}")
+    for v in ids:
+        if not 0 <= v < limit:
+            raise DsxError(f"sample id {v} out of range (0 <= id < 2^{limit.bit_length() - 1})")
+    return np.asarray(ids, dtype=np.uint64)
+
+
+def _draw_ordinal(draw):
+    draw = int(draw)
+    if not 0 <= draw < _lib.STREAM_DRAW_LIMIT:
+        raise DsxError(f"draw ordinal {draw} out of range (0 <= draw < 2^24)")
+    return draw
+
+
+def randn_samples(shape, seed, sample_ids, draw=0, device="cuda"):
+    """Per-sample noise streams (``dsx_randn_samples``): a (B, ...) tensor whose row ``b`` is
+    ``randn(shape[1:], seed, subsequence=(sample_ids[b] << 24) | draw)`` -- a function of (seed, id, draw, element) only,
+    not of B or of the row's position.  Draw 0 is a loop's initial state, draw ``s + 1`` belongs to its step ``s``."""
+    _lib.require_gpu()
+    shape = tuple(int(v) for v in shape)
+    if len(shape) < 2 or min(shape) < 1:
+        raise DsxError(f"randn_samples takes a (B, ...) shape of at least two non-empty dimensions, got {shape}")
+    ids = _sample_ids(sample_ids, shape[0])
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    check(lib.dsx_randn_samples(_dptr(out), shape[0], out.numel() // shape[0], _seed64(seed),
+                                ids.ctypes.data_as(_lib._pu64), C.c_uint32(_draw_ordinal(draw)), _stream_ptr()))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # the forward half of the training objective (dsx_q_sample / dsx_loss, include/dsx.h)
 # ---------------------------------------------------------------------------
@@ -640,11 +687,14 @@ def attention(qkv, q_col, k_col, v_col, B, L, Cn, out, col_split=False):
 # caller-driven reverse sampling (dsx_posterior_step / dsx_interp_start, include/dsx.h)
 # ---------------------------------------------------------------------------
 def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, clip=False, z=None, seed=0, subsequence=0,
-                   repeat_noise=False, x_recon_out=None, mean_out=None, x_out=None):
+                   repeat_noise=False, x_recon_out=None, mean_out=None, x_out=None, sample_ids=None, draw=None):
     """``dsx_posterior_step``: one reverse update with its intermediates in one launch.  ``a`` .. ``sigma``: (B,)
     per-sample coefficients; ``z`` (B, C, H, W) -- (1, C, H, W) under ``repeat_noise`` -- or None for the Philox normals
     of ``randn(x.shape, seed, subsequence)``.  Only the outputs given are written (``x_out`` may be ``x``); every
-    tensor must be contiguous float32 on the device.  Returns ``(x_recon_out, mean_out, x_out)``."""
+    tensor must be contiguous float32 on the device.  Returns ``(x_recon_out, mean_out, x_out)``.
+
+    ``sample_ids`` (B integers) with ``draw``: the normals of ``randn_samples(x.shape, seed, sample_ids, draw)``
+    (``dsx_posterior_step_streams``); not together with ``z`` or ``repeat_noise``."""
     x, B, Cn, H, W = _bchw(x, "x")
     net = _f32_cuda(net, "net", x.shape)
     c1, c2, sigma = _coef(c1, "c1", B), _coef(c2, "c2", B), _coef(sigma, "sigma", B)
@@ -658,6 +708,19 @@ def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, cli
         z = _f32_cuda(z, "noise", (1, Cn, H, W) if repeat_noise else x.shape)
     outs = [None if o is None else _f32_cuda(o, what, x.shape)
             for o, what in ((x_recon_out, "x_recon_out"), (mean_out, "mean_out"), (x_out, "x_out"))]
+    if sample_ids is not None:
+        if z is not None or repeat_noise:
+            raise DsxError("sample_ids together with injected noise or repeat_noise: a stream belongs to one sample")
+        if draw is None:
+            raise DsxError("sample_ids need the draw ordinal (draw = step + 1 inside a loop)")
+        ids = _sample_ids(sample_ids, B)
+        check(lib.dsx_posterior_step_streams(_dptr(x), _dptr(net), B, Cn, H, W, _dptr(a), _dptr(b), _dptr(c1), _dptr(c2),
+                                             _dptr(sigma), 1 if predict_eps else 0, 1 if clip else 0, None, _seed64(seed),
+                                             C.c_uint64(_draw_ordinal(draw)), 0, _dptr(outs[0]), _dptr(outs[1]),
+                                             _dptr(outs[2]), _stream_ptr(), ids.ctypes.data_as(_lib._pu64), len(ids)))
+        return tuple(outs)
+    if draw is not None:
+        raise DsxError("draw names a draw of a sample stream: only with sample_ids")
     check(lib.dsx_posterior_step(_dptr(x), _dptr(net), B, Cn, H, W, _dptr(a), _dptr(b), _dptr(c1), _dptr(c2),
                                  _dptr(sigma), 1 if predict_eps else 0, 1 if clip else 0, _dptr(z), _seed64(seed),
                                  C.c_uint64(int(subsequence)), 1 if repeat_noise else 0, _dptr(outs[0]),

@@ -8,7 +8,9 @@ The config is consumed unchanged.  ``datasets.val`` names the image folders (``d
 PNG folders of data/prepare_data.py; ``"hr_only"``: a folder of source images, resized on the device).  Beyond the
 reference's flags: ``--dataroot`` overrides ``datasets.val.dataroot``, ``--batch`` images go through the sampler at once
 (the reference's loader yields one), ``--steps`` overrides ``beta_schedule.val.n_timestep``, ``--dtype`` the MFMA
-operand type and ``--seed`` torch's generator, from which the device noise is seeded.
+operand type and ``--seed`` torch's generator, from which the device noise is seeded.  ``--sample-seed S`` draws every
+image's noise from its own stream instead (seed S, sample id = the image's ordinal in the validation set): image 37 is
+the same whatever ``--batch`` it ran in and whichever images ran before it.
 
 Per image the run writes ``{step}_{idx}_hr.png`` (ground truth), ``{step}_{idx}_inf.png`` (the upsampled input the
 model is conditioned on, the reference's 'INF' visual) and ``{step}_{idx}_sr.png`` (the sample) into ``path.results``
@@ -47,6 +49,8 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=None, help='override beta_schedule.val.n_timestep')
     ap.add_argument('--dtype', type=str, default=None, choices=['f32', 'bf16', 'f16'])
     ap.add_argument('--seed', type=int, default=None)
+    ap.add_argument('--sample-seed', type=int, default=None,
+                    help='per-sample noise streams: image k of the validation set draws from the stream (seed, k)')
     args = ap.parse_args(argv)
     if args.batch < 1:
         raise SystemExit('--batch must be >= 1')
@@ -92,7 +96,11 @@ def main(argv=None):
     psnrs, ssims, files = [], [], []
     for val_data in batches:
         diffusion.feed_data(val_data)
-        diffusion.test(continuous=False)
+        if args.sample_seed is None:
+            diffusion.test(continuous=False)
+        else:                                                 # idx: images done so far = this batch's first ordinal
+            n_batch = int(diffusion.data['HR'].shape[0])
+            diffusion.test(continuous=False, seed=args.sample_seed, sample_ids=range(idx, idx + n_batch))
         sample = diffusion.netG.last_full_batch               # test() returns the last image only (ret_img[-1])
         hr, inf = diffusion.data['HR'], diffusion.data['SR']
         psnr, ssim = Metrics.image_metrics(sample, hr, min_max=(-1, 1))

@@ -43,16 +43,18 @@ class DDPM(BaseModel):
             self.log_dict[k] = v
         return self.log_dict["l_pix"]
 
-    def test(self, continuous=False, clip_denoised=True):
+    def test(self, continuous=False, clip_denoised=True, seed=None, sample_ids=None):
+        """``seed`` / ``sample_ids``: the samplers' per-sample noise streams (off unless given)."""
         self.netG.eval()
         x = self.data["input"]
+        skw = {} if sample_ids is None and seed is None else dict(seed=seed, sample_ids=sample_ids)
         with torch.no_grad():
             if hasattr(self.netG, "inference"):
-                self.prediction = self.netG.inference(x, continuous=continuous)   # model.py:63-76
+                self.prediction = self.netG.inference(x, continuous=continuous, **skw)   # model.py:63-76
             elif hasattr(self.netG, "super_resolution"):
-                self.prediction = self.netG.super_resolution(x, clip_denoised=clip_denoised, continous=continuous)
+                self.prediction = self.netG.super_resolution(x, clip_denoised=clip_denoised, continous=continuous, **skw)
             else:
-                self.prediction = self.netG.predict(x, clip_denoised=clip_denoised, continous=continuous)
+                self.prediction = self.netG.predict(x, clip_denoised=clip_denoised, continous=continuous, **skw)
 
     def sample(self, batch_size=1, continous=False):
         self.netG.eval()

@@ -12,6 +12,13 @@ Training itself (backward, optimiser) stays out of scope.  The single reverse st
 Noise: by default the per-step noise is drawn on the device (Philox, seeded
 from torch's generator); set ``noise_source`` to a ``randn(shape)`` callable to
 inject host draws in the reference's draw order (parity mode, Q4).
+
+Per-sample noise streams (opt-in, include/dsx.h): the sampling loops take ``seed=`` and ``sample_ids=`` (B integers);
+the single steps keep the reference's signatures and have the siblings ``p_sample_seeded`` /
+``inference_one_step_seeded``.
+Every draw of sample ``b`` -- the initial state, draw 0, and step ``s``, draw ``s + 1`` -- then is a function of
+``(seed, sample_ids[b], draw, element)`` alone: the same whatever batch, batch position or rank the sample runs in.
+torch's generator is not touched, and a ``noise_source`` together with ids is refused.
 """
 import numpy as np
 import torch
@@ -37,6 +44,23 @@ class _SamplerBase(nn.Module):
         if self.noise_source is not None:
             return 0   # injected noise: leave torch's generator untouched (the draws must stay in order)
         return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+
+    STREAM2_BIT = 1 << 39            # JointIndi: the second sampler's ids carry this bit, callers' ids stay below it
+
+    def _stream_args(self, seed, sample_ids, B, limit=None):
+        """None without ``sample_ids`` (today's noise); else ``(seed, ids)`` of the per-sample noise streams, checked:
+        B ids below ``limit`` (2^40), a seed, and no ``noise_source`` -- the draws come from one or the other."""
+        if sample_ids is None:
+            if seed is not None:
+                raise DsxError("seed= names the per-sample noise streams: only together with sample_ids=")
+            return None
+        if self.noise_source is not None:
+            raise DsxError("noise_source together with sample_ids: the draws are injected or come from the sample "
+                           "streams, not both")
+        if seed is None:
+            raise DsxError("sample_ids need seed=: a sample stream is named by (seed, sample id)")
+        kw = {} if limit is None else dict(limit=limit)
+        return int(seed), [int(v) for v in engine._sample_ids(sample_ids, B, **kw)]
 
     def forward(self, x, *args, **kwargs):
         """The objective's forward evaluation (``p_losses``); no gradients, eval semantics."""
@@ -164,7 +188,9 @@ class GaussianSampler(_SamplerBase):
             raise DsxError("set_new_noise_schedule() first")
 
     @torch.no_grad()
-    def p_sample_loop(self, x_in, clip_denoised=True, continous=False):
+    def p_sample_loop(self, x_in, clip_denoised=True, continous=False, seed=None, sample_ids=None):
+        """``seed`` / ``sample_ids``: per-sample noise streams -- the initial state is ``randn_samples(draw=0)``, step
+        ``s`` takes draw ``s + 1``; torch's generator is not touched."""
         self._need_schedule()
         dev = self.betas.device
         T = self.num_timesteps
@@ -173,7 +199,11 @@ class GaussianSampler(_SamplerBase):
         else:
             cond = x_in.to(dev).float()
             shape = (cond.shape[0], self.channels) + tuple(cond.shape[2:])
-        img = self._draw(shape, dev)
+        streams = self._stream_args(seed, sample_ids, shape[0])
+        if streams is None:
+            img = self._draw(shape, dev)
+        else:
+            img = engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
         # the loop updates `img` in place: keep a copy of the initial noise for ret_img[0] (sr3 diffusion.py:183-185)
         first = (img.clone() if continous else None) if cond is None else cond.repeat((1, self.channels // cond.shape[1], 1, 1))
         noise = None
@@ -183,9 +213,9 @@ class GaussianSampler(_SamplerBase):
             for s in range(n_draw):
                 noise[s] = self._draw(shape, dev)
         snaps = engine.gaussian_snapshot_steps(T) if continous else []
+        skw = dict(seed=self._seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
         x, sn = self.denoise_fn.engine().sample_loop(self._step_table(bool(clip_denoised)), img, cond=cond,
-                                                     noise=noise, seed=self._seed(), snapshot_steps=snaps,
-                                                     use_graph=self.use_graph)
+                                                     noise=noise, snapshot_steps=snaps, use_graph=self.use_graph, **skw)
         self.last_full_batch = x
         if self.kind == "ddpm" and not self.conditional:
             return x                                                 # ddpm diffusion.py:222
@@ -194,13 +224,14 @@ class GaussianSampler(_SamplerBase):
         return x[-1]                                                 # diffusion.py:200-203: ret_img[-1]
 
     @torch.no_grad()
-    def sample(self, batch_size=1, continous=False):
+    def sample(self, batch_size=1, continous=False, seed=None, sample_ids=None):
         return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size),
-                                  continous=continous)
+                                  continous=continous, seed=seed, sample_ids=sample_ids)
 
     @torch.no_grad()
-    def super_resolution(self, x_in, clip_denoised=True, continous=False):
-        return self.p_sample_loop(x_in, clip_denoised=clip_denoised, continous=continous)
+    def super_resolution(self, x_in, clip_denoised=True, continous=False, seed=None, sample_ids=None):
+        return self.p_sample_loop(x_in, clip_denoised=clip_denoised, continous=continous, seed=seed,
+                                  sample_ids=sample_ids)
 
     predict = super_resolution                                       # ddpm diffusion.py:245-247
 
@@ -215,7 +246,8 @@ class GaussianSampler(_SamplerBase):
         rows = engine.gaussian_step_rows(self._bufs_cpu, self.sqrt_alphas_cumprod_prev, self.kind, t)
         return {k: torch.from_numpy(np.ascontiguousarray(np.broadcast_to(v, (B,)))).to(dev) for k, v in rows.items()}
 
-    def _reverse(self, x, t, clip_denoised, condition_x, want, z=None, seed=0, repeat_noise=False):
+    def _reverse(self, x, t, clip_denoised, condition_x, want, z=None, seed=0, repeat_noise=False, sample_ids=None,
+                 draw=None):
         """One UNet forward and one dsx_posterior_step launch: ``want`` = (x_recon, model_mean, sample) flags, the
         wanted ones are returned as new tensors, the others as None."""
         self._need_cuda(x, *(() if condition_x is None else (condition_x,)))
@@ -232,7 +264,21 @@ class GaussianSampler(_SamplerBase):
         outs = [torch.empty_like(x) if w else None for w in want]
         return engine.posterior_step(x, net, r["c1"], r["c2"], r["sigma"], a=r["a"], b=r["b"], predict_eps=True,
                                      clip=bool(clip_denoised), z=z, seed=seed, repeat_noise=repeat_noise,
-                                     x_recon_out=outs[0], mean_out=outs[1], x_out=outs[2])
+                                     x_recon_out=outs[0], mean_out=outs[1], x_out=outs[2], sample_ids=sample_ids,
+                                     draw=draw)
+
+    def _step_draw(self, t, draw):
+        """The draw ordinal of the reverse step at timestep ``t``: ``T - t``, what the loop uses there (its step
+        ``s = T - 1 - t`` takes draw ``s + 1``), unless the caller names one."""
+        if draw is not None:
+            return int(draw)
+        self._need_schedule()
+        if torch.is_tensor(t):
+            ts = set(int(v) for v in t.detach().reshape(-1).cpu().tolist())
+            if len(ts) != 1:
+                raise DsxError("sample_ids with differing timesteps: pass draw=, one ordinal serves the whole call")
+            t = ts.pop()
+        return self.num_timesteps - int(t)
 
     @torch.no_grad()
     def predict_start_from_noise(self, x_t, t, noise):
@@ -262,6 +308,19 @@ class GaussianSampler(_SamplerBase):
         self._need_cuda(x)
         z, seed = self._noise_or_seed(None, x.shape, x.device) if t > 0 else (None, 0)
         return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), z=z, seed=seed)[2]
+
+    @torch.no_grad()
+    def p_sample_seeded(self, x, t, seed, sample_ids, clip_denoised=True, condition_x=None, draw=None):
+        """``p_sample`` with per-sample noise streams (``p_sample`` itself keeps the reference's signature): the draw
+        the loop takes at this timestep from the streams (seed, sample_ids[b]) -- ``draw`` = T - t unless given -- so
+        the caller's loop from ``randn_samples(draw=0)`` reproduces ``p_sample_loop`` with the same ids bit for bit.
+        ``t``: an integer, or (B,) equal integers (ddpm)."""
+        self._need_cuda(x)
+        streams = self._stream_args(seed, sample_ids, x.shape[0])
+        if streams is None:
+            raise DsxError("p_sample_seeded needs sample_ids (p_sample draws without them)")
+        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), seed=streams[0],
+                             sample_ids=streams[1], draw=self._step_draw(t, draw))[2]
 
     # ---- objective (sr3 diffusion.py:215-249) -----------------------------------------------
     def q_coefficients(self, continuous_sqrt_alpha_cumprod):
@@ -534,6 +593,19 @@ class InDISampler(_SamplerBase):
     def inference_one_step(self, x_t, delta_t, t_cur):
         """indi.py:62-69: delta/t * UNet(x_t, t) + (1 - delta/t) * x_t + z * e (t - delta), one UNet forward and one
         dsx_posterior_step launch; the coefficients are one row of ``engine.indi_step_table``.  One draw per call."""
+        return self._one_step(x_t, delta_t, t_cur, None, None)
+
+    @torch.no_grad()
+    def inference_one_step_seeded(self, x_t, delta_t, t_cur, seed, sample_ids, draw):
+        """``inference_one_step`` with per-sample noise streams (``inference_one_step`` itself keeps the reference's
+        signature): ``draw`` = s + 1 at the caller's step ``s`` is the draw ``inference`` takes there with the same
+        ``seed`` and ``sample_ids``, so the caller's loop reproduces it bit for bit."""
+        streams = self._stream_args(seed, sample_ids, x_t.shape[0])
+        if streams is None:
+            raise DsxError("inference_one_step_seeded needs sample_ids (inference_one_step draws without them)")
+        return self._one_step(x_t, delta_t, t_cur, streams, draw)
+
+    def _one_step(self, x_t, delta_t, t_cur, streams, draw):
         assert delta_t <= t_cur, "delta_t should be less than or equal to t_cur."
         self._gaussian_noise_mode()
         self._need_cuda(x_t, what="inference_one_step")
@@ -543,6 +615,9 @@ class InDISampler(_SamplerBase):
         tc, c1, c2, sg = engine.indi_step_row(delta_t, t_cur, self.get_e(t_cur))
         col = lambda v: torch.full((B,), v, dtype=torch.float32, device=dev)
         x_0 = self.denoise_fn(x_t, torch.Tensor([tc]).to(dev))
+        if streams is not None:
+            return engine.posterior_step(x_t, x_0, col(c1), col(c2), col(sg), predict_eps=False, seed=streams[0],
+                                         sample_ids=streams[1], draw=draw, x_out=torch.empty_like(x_t))[2]
         z, seed = self._noise_or_seed(None, x_t.shape, dev)
         return engine.posterior_step(x_t, x_0, col(c1), col(c2), col(sg), predict_eps=False, z=z, seed=seed,
                                      x_out=torch.empty_like(x_t))[2]
@@ -557,11 +632,17 @@ class InDISampler(_SamplerBase):
             raise DsxError("out_channel {} is no multiple of the input's {} channels".format(self.out_channel, cin))
         return self.out_channel // cin
 
-    def _start(self, x_in, t_float_start):
+    def _draw0(self, shape, dev, streams):
+        """The draw of the initial state: torch's (or the injected one), or draw 0 of the sample streams."""
+        if streams is None:
+            return self._draw(shape, dev)
+        return engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
+
+    def _start(self, x_in, t_float_start, streams=None):
         dev = x_in.device
         x_in = torch.cat([x_in.float()] * self._copies(x_in), dim=1)   # indi.py:80
         scale = (self.e * torch.Tensor([t_float_start])).to(dev)     # get_t_times_e, indi.py:106-110
-        return x_in + self._draw(x_in.shape, dev) * scale            # indi.py:82
+        return x_in + self._draw0(x_in.shape, dev, streams) * scale  # indi.py:82
 
     @staticmethod
     def _per_sample_t(t_float_start, batch):
@@ -579,7 +660,7 @@ class InDISampler(_SamplerBase):
         return t
 
     @torch.no_grad()
-    def _inference_per_sample(self, x_in, t_list, continuous, num_timesteps, stream):
+    def _inference_per_sample(self, x_in, t_list, continuous, num_timesteps, stream, streams=None):
         """One start time per batch element, one batched loop (per-sample step tables).  Equivalent to calling
         ``inference`` on every sample alone, as core/psnr_based_t_refinement.py:26-34 does; with a ``noise_source``
         the draws are taken sample by sample in that order (start draw, then one draw per step)."""
@@ -595,18 +676,19 @@ class InDISampler(_SamplerBase):
             d0 = torch.cat(starts)
             noise = torch.stack(steps, dim=1).contiguous()            # (n, B, C, H, W)
         else:
-            d0 = self._draw(xr.shape, dev)
+            d0 = self._draw0(xr.shape, dev, streams)
         scale = torch.stack([(self.e * torch.Tensor([t])) for t in t_list]).to(dev).view(B, 1, 1, 1)
         x_t = xr + d0 * scale
         table = engine.indi_step_table_per_sample(num_timesteps, t_list, self.e)
-        return self._loop(table, x_t, noise, continuous, num_timesteps, stream)
+        return self._loop(table, x_t, noise, continuous, num_timesteps, stream, streams)
 
-    def _loop(self, table, x_t, noise, continuous, num_timesteps, stream):
+    def _loop(self, table, x_t, noise, continuous, num_timesteps, stream, streams=None):
         """The engine's loop from ``x_t`` (updated in place: ``first`` keeps the start) and what inference returns."""
         snaps = engine.indi_snapshot_steps(num_timesteps) if continuous else []
         first = x_t.clone() if continuous else None
-        x, sn = self.denoise_fn.engine().sample_loop(table, x_t, noise=noise, seed=self._seed(), snapshot_steps=snaps,
-                                                     use_graph=self.use_graph, stream=stream)
+        skw = dict(seed=self._seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
+        x, sn = self.denoise_fn.engine().sample_loop(table, x_t, noise=noise, snapshot_steps=snaps,
+                                                     use_graph=self.use_graph, stream=stream, **skw)
         self.last_full_batch = x
         if continuous:
             if stream is not None:
@@ -621,18 +703,21 @@ class InDISampler(_SamplerBase):
 
     @torch.no_grad()
     def inference(self, x_in, continuous=False, num_timesteps=None, t_float_start=1.0, eps=1e-8,
-                  stream=None):
+                  stream=None, seed=None, sample_ids=None):
+        """``seed`` / ``sample_ids``: per-sample noise streams -- the start perturbation is draw 0 of every sample's
+        stream, step ``s`` takes draw ``s + 1``; torch's generator is not touched."""
         if num_timesteps is None:
             num_timesteps = self.num_timesteps
         assert self.conditional is False
         self._need_cuda(x_in, what="inference")
+        streams = self._stream_args(seed, sample_ids, x_in.shape[0])
         t_list = self._per_sample_t(t_float_start, x_in.shape[0])
         if t_list is not None:
-            return self._inference_per_sample(x_in, t_list, continuous, num_timesteps, stream)
-        x_t = self._start(x_in, t_float_start)
+            return self._inference_per_sample(x_in, t_list, continuous, num_timesteps, stream, streams)
+        x_t = self._start(x_in, t_float_start, streams)
         noise = self._noise(x_t.shape, num_timesteps, x_t.device)
         table = engine.indi_step_table(num_timesteps, t_float_start, self.e)   # no drift assert (R3)
-        return self._loop(table, x_t, noise, continuous, num_timesteps, stream)
+        return self._loop(table, x_t, noise, continuous, num_timesteps, stream, streams)
 
 
 class IndiCustomT(InDISampler):
@@ -728,19 +813,32 @@ class JointIndiSampler(_SamplerBase):
         self.indi2.set_new_noise_schedule(schedule_opt, device)
 
     @torch.no_grad()
-    def inference(self, x_in, continuous=False, num_timesteps=None, t_float_start=0.5, eps=1e-8):
+    def second_ids(self, sample_ids):
+        """The ids indi2 draws from: the caller's (below 2^39) with bit 39 set, so the two channels never share a draw."""
+        return None if sample_ids is None else [v | self.STREAM2_BIT for v in
+                                                engine._sample_ids(sample_ids, len(sample_ids), self.STREAM2_BIT).tolist()]
+
+    @torch.no_grad()
+    def inference(self, x_in, continuous=False, num_timesteps=None, t_float_start=0.5, eps=1e-8, seed=None,
+                  sample_ids=None):
+        """``seed`` / ``sample_ids`` (ids < 2^39): per-sample noise streams; indi1 draws from the ids, indi2 from the
+        ids with bit 39 set."""
         for s in (self.indi1, self.indi2):
             s.noise_source, s.use_graph = self.noise_source, self.use_graph   # indi1's draws first (Q4)
+        if sample_ids is not None and torch.is_tensor(sample_ids):
+            sample_ids = sample_ids.detach().cpu().tolist()
+        k1 = dict(seed=seed, sample_ids=sample_ids)
+        k2 = dict(seed=seed, sample_ids=self.second_ids(sample_ids))
         if self.noise_source is not None or not self.concurrent:
             # host draws are order-dependent: finish indi1's before indi2's start
-            ch1 = self.indi1.inference(x_in, continuous, num_timesteps, t_float_start, eps)
-            ch2 = self.indi2.inference(x_in, continuous, num_timesteps, 1 - t_float_start, eps)
+            ch1 = self.indi1.inference(x_in, continuous, num_timesteps, t_float_start, eps, **k1)
+            ch2 = self.indi2.inference(x_in, continuous, num_timesteps, 1 - t_float_start, eps, **k2)
         else:
             if self._streams is None:
                 self._streams = (torch.cuda.Stream(), torch.cuda.Stream())
             s1, s2 = self._streams
-            ch1 = self.indi1.inference(x_in, continuous, num_timesteps, t_float_start, eps, stream=s1)
-            ch2 = self.indi2.inference(x_in, continuous, num_timesteps, 1 - t_float_start, eps, stream=s2)
+            ch1 = self.indi1.inference(x_in, continuous, num_timesteps, t_float_start, eps, stream=s1, **k1)
+            ch2 = self.indi2.inference(x_in, continuous, num_timesteps, 1 - t_float_start, eps, stream=s2, **k2)
             torch.cuda.current_stream().wait_stream(s1)
             torch.cuda.current_stream().wait_stream(s2)
         self.last_full_batch = torch.cat([self.indi1.last_full_batch, self.indi2.last_full_batch], dim=1)

@@ -24,6 +24,10 @@ A ``joint_indi`` config with ``--mix-t T`` runs the mixed-input prediction inste
 C5): the two channels of every tile mixed at ``T``, ``indi1`` / ``indi2`` started at the time the TimePredictor of
 ``--time-predictor CONFIG [--time-predictor-checkpoint PTH]`` estimates per tile (``--t-from given``: at ``T`` itself,
 no classifier), ``--mmse N`` repeats averaged.  Frames, ranks and ``--out`` as for the plain prediction.
+
+``--sample-seed S`` draws every tile's noise from its own stream (seed S, sample id = tile id; MMSE repeat ``r`` of the
+mixed-input prediction: tile id + r * tiles): the noise does not depend on ``--batch-tiles`` or ``--gpus``, and neither
+does the prediction for an equal batch size.  Off by default.
 """
 import argparse
 import logging
@@ -170,7 +174,12 @@ def main(argv=None):
     ap.add_argument("--mmse", type=int, default=None, help="with --mix-t: repeats averaged per tile (default 1)")
     ap.add_argument("--t-from", type=str, choices=["classifier", "given"], default=None,
                     help="with --mix-t: start times from the TimePredictor (default) or --mix-t itself")
+    ap.add_argument("--sample-seed", type=int, default=None,
+                    help="per-sample noise streams: every tile draws from the stream (seed, tile id), whatever batch "
+                         "or rank predicts it (default: off, one stream per step over the batch)")
     args = ap.parse_args(argv)
+    if args.sample_seed is not None and args.validate:
+        raise SystemExit("--sample-seed names the tiles of a tiled prediction: not with --validate")
     if args.phase == "train":
         raise SystemExit("training is out of scope of the MI355X sampling engine; use -p val")
     if args.datapath and args.frames:
@@ -197,6 +206,8 @@ def main(argv=None):
         raise SystemExit("--out: colour items are written as (N, 2 Cc, p, p) .npy; a .tif hyperstack holds grey frames")
     if args.items is not None and args.items < 1:
         raise SystemExit("--items: a positive count")
+    if colour and args.sample_seed is not None:
+        raise SystemExit("--sample-seed names the tiles of a tiled prediction: colour items are not tiled")
     if colour and args.mix_t is not None:
         raise SystemExit("--mix-t: the mixed-input prediction takes two grey channels, not a cifar10 config")
     # -gpu selects the device(s): rank r of a torchrun launch drives gpu_ids[r] (the reference exports
@@ -263,7 +274,8 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     for i in range(0, len(ids), args.batch_tiles):
         chunk = ids[i:i + args.batch_tiles]
         batch = val_set.tiles(chunk)
-        netG.inference(batch["input"], continuous=False, num_timesteps=n_steps)
+        skw = {} if args.sample_seed is None else dict(seed=args.sample_seed, sample_ids=chunk)
+        netG.inference(batch["input"], continuous=False, num_timesteps=n_steps, **skw)
         ex.add(netG.last_full_batch, chunk)
     res = ex.finish()                                                 # the path's only collective: cropped tiles
     pred, ps = res if score else (res, None)                          # metric accumulated while pasting
@@ -330,7 +342,8 @@ def _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     (pred, ps), pred_t = predict_tiled_mixed(netG, tp, val_set, args.mix_t, num_timesteps=n_steps,
-                                             mmse_count=args.mmse or 1, batch_tiles=args.batch_tiles, t_from=t_from)
+                                             mmse_count=args.mmse or 1, batch_tiles=args.batch_tiles, t_from=t_from,
+                                             seed=args.sample_seed)
     pred_t = gather_pred_t(pred_t)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0

@@ -377,6 +377,53 @@ int dsx_interp_start(const float* x1_dev, const float* x2_dev, int B, int C, int
                      const float* z1_dev, const float* z2_dev, uint64_t seed, uint64_t subsequence,
                      float* out_dev, void* stream);
 
+/* ------------------------------------------------------- per-sample noise streams
+ * An opt-in second way of drawing, for sampling that does not depend on how the work is batched or sharded: every
+ * sample owns the streams named by (seed, sample id), and a draw is a pure function of
+ *   (seed, sample id, draw ordinal, element index j inside the sample's (C, H, W) tensor in NCHW order)
+ * -- not of B, of the sample's position in the batch, of the storage layout or of the rank.
+ *
+ * Definition, through the generator above: the sample stream (seed, id, draw) IS the stream
+ *   (seed, subsequence = (id << 24) | draw)
+ * of dsx_randn, and element j of the sample is element j of that stream (component j % 4 of Philox block j / 4).
+ * id < 2^40 (DSX_STREAM_ID_LIMIT) and draw < 2^24 (DSX_STREAM_DRAW_LIMIT); anything else is refused.
+ * Draw ordinal 0 is the initial state of a loop; ordinal s + 1 belongs to step s (0-based, execution order) of it.  A
+ * step that adds no noise (sigma == 0: SR3's and InDI's last step) draws nothing and still owns its ordinal.
+ *
+ * dsx_randn_samples: out (B, chw) fp32, row b = the first chw elements of the stream (seed, ids[b], draw): what
+ * dsx_randn(out + b * chw, chw, seed, (ids[b] << 24) | draw) writes, bitwise.  16-byte stores when chw is a multiple
+ * of 4 and out is 16-byte aligned, scalar stores (with the tail of the last block) otherwise.  ids_host: B host values,
+ * read before the call returns.
+ *
+ * dsx_sample_loop_streams: dsx_sample_loop with device noise drawn from the sample streams: step s of sample b adds
+ * sigma * element (c * H * W + hw) of the stream (seed, sample_ids[b], s + 1) at state element (b, c, hw), whatever
+ * the layout of the state inside the loop.  The caller draws the initial state (draw 0, dsx_randn_samples).  The ids
+ * are copied to device memory the executor owns before the loop starts; a captured step graph reads them from there,
+ * so one kept graph serves every call whatever its ids.  n_sample_ids must equal the executor's B; n_steps <
+ * DSX_STREAM_DRAW_LIMIT; injected noise together with ids is refused (noise_nchw_dev must be NULL).  With the same
+ * draws injected -- noise[s][b] = dsx_randn_samples(.., ids, s + 1) -- dsx_sample_loop computes the same bits.
+ *
+ * dsx_posterior_step_streams: dsx_posterior_step with z = the sample streams (seed, sample_ids[b], draw), `draw` taking
+ * the place of `subsequence`; an injected z_dev and repeat_noise are refused (a shared draw is what streams are not),
+ * n_sample_ids must equal B.  A caller-driven loop of dsx_unet_forward and this call with draw = s + 1 at step s
+ * reproduces dsx_sample_loop_streams bit for bit. */
+#define DSX_STREAM_ID_LIMIT ((uint64_t)1 << 40)
+#define DSX_STREAM_DRAW_LIMIT ((uint32_t)1 << 24)
+int dsx_randn_samples(float* out_dev, int B, int64_t chw, uint64_t seed, const uint64_t* ids_host, uint32_t draw,
+                      void* stream);
+int dsx_sample_loop_streams(dsx_exec* ex, const dsx_step_table* tab,
+                            const float* cond_nchw_dev, float* x_nchw_dev,
+                            const float* noise_nchw_dev, uint64_t seed,
+                            const int32_t* snap_steps, int n_snap, float* snap_nchw_dev,
+                            int use_graph, void* stream,
+                            const uint64_t* sample_ids_host, int n_sample_ids);
+int dsx_posterior_step_streams(const float* x_dev, const float* net_dev, int B, int C, int H, int W,
+                               const float* a_dev, const float* b_dev, const float* c1_dev, const float* c2_dev,
+                               const float* sigma_dev, int predict_eps, int clip,
+                               const float* z_dev, uint64_t seed, uint64_t draw, int repeat_noise,
+                               float* x_recon_out_dev, float* mean_out_dev, float* x_out_dev, void* stream,
+                               const uint64_t* sample_ids_host, int n_sample_ids);
+
 /* ----------------------------------------------------------------- tiling */
 
 enum { DSX_TILING_TRIM = 0, DSX_TILING_PAD = 1, DSX_TILING_SHIFT = 2 };  /* tiling_manager.py:6-12 */
