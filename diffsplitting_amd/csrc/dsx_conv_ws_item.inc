@@ -1,5 +1,5 @@
 // Body of one (tile, group) item of k_conv_ws's compute waves: the MFMA steps of the group and, at the end of a tile,
-// the epilogue.  Included twice by dsx_conv.hip: in the plain item loop (ring no deeper than a group) and in the loop
+// the epilogue.  Included twice by dsx_conv_ws.hip: in the plain item loop (ring no deeper than a group) and in the loop
 // unrolled over the ring phases of a ring that spans several groups (1 x 1 convs).  Expects `v` (item), `R0` (first
 // ring slot of the item, constexpr) and DSX_WS_ITEM_NEXT (continue / return) from the including scope.  The plain
 // form must stay a literal loop body: wrapped in a lambda, the two-N-block variants run into hipcc's failing spill

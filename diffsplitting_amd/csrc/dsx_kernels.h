@@ -1,5 +1,5 @@
 // dsx_kernels.h — launch interface between the host runtime (dsx_*.cpp)
-// and the gfx950 kernels (dsx_conv.hip, dsx_ops.hip, dsx_attn.hip, dsx_eval.hip, ...).  Internal;
+// and the gfx950 kernels (dsx_conv*.hip, dsx_ops.hip, dsx_attn.hip, dsx_eval.hip, ...).  Internal;
 // the public ABI is include/dsx.h.
 #pragma once
 #include <hip/hip_runtime.h>

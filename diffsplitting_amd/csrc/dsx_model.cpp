@@ -235,7 +235,7 @@ static inline uint16_t f2h(float f) {
   return u;
 }
 
-// OIHW fp32 -> [nblk][kchunk][tap][half][lane][16 B] (see dsx_conv.hip header)
+// OIHW fp32 -> [nblk][kchunk][tap][half][lane][16 B] (see dsx_conv_mfma.hip header)
 static void pack_conv(const float* w, int cout, int cin, int ks, int dtype, std::vector<char>& dst,
                       int& kchunks, int& nblocks) {
   const int KC = dtype != DSX_DTYPE_F32 ? 32 : 16, EPL = dtype != DSX_DTYPE_F32 ? 8 : 4, taps = ks * ks;
@@ -247,7 +247,7 @@ static void pack_conv(const float* w, int cout, int cin, int ks, int dtype, std:
         for (int fs = 0; fs < 2; ++fs)
           for (int lane = 0; lane < 64; ++lane) {
             // MFMA A row i = q + 8*j + 4*hh carries output channel 16*hh + 4*j + q of the block, so that a
-            // lane's 16 accumulator registers are 16 consecutive channels (dsx_conv.hip, store16)
+            // lane's 16 accumulator registers are 16 consecutive channels (dsx_conv_common.h, store16)
             const int i = lane & 31, h = lane >> 5;
             const int n = nb * 32 + 16 * ((i >> 2) & 1) + 4 * (i >> 3) + (i & 3);
             char* p = dst.data() + ((((size_t)(nb * kchunks + kc) * taps + tap) * 2 + fs) * 64 + lane) * 16;

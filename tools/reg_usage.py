@@ -1,5 +1,5 @@
 """Registers / spills / scratch per kernel: hipcc -Rpass-analysis=kernel-resource-usage of one source file.
-    python tools/reg_usage.py diffsplitting_amd/csrc/dsx_conv.hip [filter]"""
+    python tools/reg_usage.py diffsplitting_amd/csrc/dsx_conv_ws.hip [filter]"""
 import re, subprocess, sys
 src = sys.argv[1]; flt = sys.argv[2] if len(sys.argv) > 2 else ""
 r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",

@@ -1,4 +1,4 @@
-"""In-kernel stamps of one k_conv_img launch, first and last wave of a workgroup side by side (IMG_STAMP in dsx_conv.hip):
+"""In-kernel stamps of one k_conv_img launch, first and last wave of a workgroup side by side (IMG_STAMP in dsx_conv_img.hip):
     DSX_STAMP_OP=<conv ordinal>[,<block>] DSX_LIB_PATH=<-DDSX_STAMPS build> python tools/stamps_img.py
 Conv ordinals of the benchmark's plan: 30 conv3x3 512->512, 38 conv3x3 1024->512, 34 conv1x1 512->1536.  Read the shares,
 not the length: the stamps' fences and the explicit wait of stamp 16 forbid overlaps the real kernel has."""
