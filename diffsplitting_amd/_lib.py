@@ -138,6 +138,9 @@ SIGNATURES = {
     "dsx_tileplan_gather_norm": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _f, _f, C.POINTER(C.c_double), _i, _vp, _vp, _vp]),
     "dsx_tileplan_gather_mix": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    "dsx_tileplan_gather_input": (_i, [_vp, _vp, _i, _i64, _i64, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "dsx_moments_update": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
+    "dsx_moments_finish": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "dsx_tileplan_stitch": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "dsx_tileplan_pack_layout": (_i, [_vp, _i, _pi64, _pi64]),
     "dsx_tileplan_pack": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp]),

@@ -126,6 +126,135 @@ hipError_t launch_tiles_gather_norm_planes(const float* f0, const float* f1, int
   return hipGetLastError();
 }
 
+// The network input of an INPUT-ONLY stack (data/input_stack.py): one (N, H, W) stack in which the two structures are
+// already superimposed, resident in its file width (uint8 / uint16 / fp32), cut and normalised in one pass:
+//   x = (float)pixel (exact);  x = min(x, clip) with a clip;  out = (float)(((double)x - mean_input) / std_input)
+// -- the expression k_tiles_gather_norm applies to w0 * p0 + w1 * p1, so a stack that holds that sum gives its 'input'
+// bit for bit.  A streaming kernel: a thread owns four consecutive pixels of one tile row (consecutive lanes,
+// consecutive pixels; the grid grows with ph * pw, no workgroup cap), reads them with the widest loads their address
+// allows and writes one 16-byte store.  The address of a group is aligned to 4, 2 or 1 pixels (x0, W and the row decide;
+// it is the same for every group of a row, so a wave diverges between rows at most):
+//   4: one load of four pixels      2: two loads of two      1: a scalar head, the aligned middle pair, a scalar tail
+// VEC: pw % 4 == 0 and the output is 16-byte aligned.  Otherwise the last group of a row is ragged and the stores are
+// scalar (the loads of the full groups stay wide).  Only pixels of the tile are ever read.
+struct GatherInputArgs {
+  const void* frames;      // (N, H, W) pixels of the kernel's type
+  int H, W, ph, pw;
+  const int* starts;       // dev [..][3], indexed by tile id
+  TileSeq seq;
+  double mean, std;
+  float clip; int has_clip;
+  float* out;              // (count, 1, ph, pw)
+};
+template <class T>
+__device__ __forceinline__ void load_pixels4(const T* p, float v[4]) {
+  typedef T V2 __attribute__((ext_vector_type(2)));
+  typedef T V4 __attribute__((ext_vector_type(4)));
+  const uintptr_t a = (uintptr_t)p;
+  if ((a & (4 * sizeof(T) - 1)) == 0) {
+    const V4 t = *(const V4*)p;
+    v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
+  } else if ((a & (2 * sizeof(T) - 1)) == 0) {
+    const V2 t = *(const V2*)p, u = *(const V2*)(p + 2);
+    v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)u.x; v[3] = (float)u.y;
+  } else {                                     // p is an odd pixel address: p + 1 is a pair boundary
+    const T head = p[0], tail = p[3];
+    const V2 t = *(const V2*)(p + 1);
+    v[0] = (float)head; v[1] = (float)t.x; v[2] = (float)t.y; v[3] = (float)tail;
+  }
+}
+// uint8: the same three cases on integer words (a vector of four bytes is split into two 16-bit loads by the compiler)
+template <>
+__device__ __forceinline__ void load_pixels4<unsigned char>(const unsigned char* p, float v[4]) {
+  const uintptr_t a = (uintptr_t)p;
+  unsigned w;
+  if ((a & 3) == 0) w = *(const unsigned*)p;
+  else if ((a & 1) == 0) w = (unsigned)*(const unsigned short*)p | ((unsigned)*(const unsigned short*)(p + 2) << 16);
+  else w = (unsigned)p[0] | ((unsigned)*(const unsigned short*)(p + 1) << 8) | ((unsigned)p[3] << 24);
+  v[0] = (float)(w & 255u); v[1] = (float)((w >> 8) & 255u); v[2] = (float)((w >> 16) & 255u); v[3] = (float)(w >> 24);
+}
+template <class T, bool VEC>
+__global__ __launch_bounds__(256) void k_tiles_gather_input(const GatherInputArgs a) {
+  const long long k = blockIdx.y, t = a.seq.first + k * a.seq.stride;
+  const int n = a.starts[t * 3], y0 = a.starts[t * 3 + 1], x0 = a.starts[t * 3 + 2];
+  const int gpr = (a.pw + 3) >> 2;             // groups per tile row
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long long)a.ph * gpr) return;
+  const int y = (int)(g / gpr), x = (int)(g - (long long)y * gpr) * 4;
+  const int cnt = VEC ? 4 : min(4, a.pw - x);
+  const T* src = (const T*)a.frames + ((size_t)n * a.H + (y0 + y)) * a.W + (x0 + x);
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (cnt == 4) load_pixels4(src, v);
+  else DSX_EACH4(j, cnt) v[j] = (float)src[j];
+  DSX_EACH4(j, cnt) {
+    const float px = a.has_clip ? fminf(v[j], a.clip) : v[j];
+    v[j] = (float)(((double)px - a.mean) / a.std);
+  }
+  float* dst = a.out + (size_t)k * a.ph * a.pw + (size_t)y * a.pw + x;
+  if (VEC) *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
+  else DSX_EACH4(j, cnt) dst[j] = v[j];
+}
+template <class T>
+static hipError_t launch_gather_input_as(const GatherInputArgs& a, hipStream_t st) {
+  const bool vec = (a.pw & 3) == 0 && aligned16(a.out);
+  const long long groups = (long long)a.ph * ((a.pw + 3) >> 2);
+  const dim3 grid((unsigned)((groups + 255) / 256), (unsigned)a.seq.count);
+  if (vec) hipLaunchKernelGGL((k_tiles_gather_input<T, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_tiles_gather_input<T, false>), grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t launch_tiles_gather_input(const void* frames, int pix_bytes, bool is_float, int H, int W, int ph, int pw,
+                                     const int* starts, TileSeq seq, double mean, double std, double clip, float* out,
+                                     hipStream_t st) {
+  if (seq.count < 1 || seq.count > 65535 || ph < 1 || pw < 1) return hipErrorInvalidValue;
+  const GatherInputArgs a{frames, H, W, ph, pw, starts, seq, mean, std, (float)clip, clip >= 0 ? 1 : 0, out};
+  if (is_float && pix_bytes == 4) return launch_gather_input_as<float>(a, st);
+  if (!is_float && pix_bytes == 2) return launch_gather_input_as<unsigned short>(a, st);
+  if (!is_float && pix_bytes == 1) return launch_gather_input_as<unsigned char>(a, st);
+  return hipErrorInvalidValue;
+}
+
+// Mean and spread over N posterior samples, Welford's recurrence in double, one launch per sample and one to finish:
+//   r == 0: mean = x, M2 = 0;   else d = x - mean;  mean' = mean + d / (r + 1);  M2' = M2 + d * (x - mean')
+//   finish: mean_out = (float)mean;  std_out = n > 1 ? (float)sqrt(M2 / (n - 1)) : 0
+// Every operation is rounded on its own, so a numpy float64 restatement of these lines gives the same bits.  The
+// __d*_rn forms are plain operators in the toolchain's headers and may be contracted once inlined: the product and the
+// sums go through mul_d / add_d / sub_d, which take the `contract` flag off their own instruction.
+__device__ __forceinline__ double sub_d(double a, double b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+__global__ __launch_bounds__(256) void k_moments_update(const float* __restrict__ x, double* __restrict__ mean,
+                                                        double* __restrict__ m2, long long count, int r) {
+  const double rn = (double)(r + 1);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+    const double xv = (double)x[i];
+    if (r == 0) { mean[i] = xv; m2[i] = 0.0; continue; }
+    const double m = mean[i], d = sub_d(xv, m);
+    const double m1 = add_d(m, d / rn);
+    mean[i] = m1;
+    m2[i] = add_d(m2[i], mul_d(d, sub_d(xv, m1)));
+  }
+}
+__global__ __launch_bounds__(256) void k_moments_finish(const double* __restrict__ mean, const double* __restrict__ m2,
+                                                        long long count, int n, float* __restrict__ mean_out,
+                                                        float* __restrict__ std_out) {
+  const double nm1 = (double)(n - 1);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+    mean_out[i] = (float)mean[i];
+    if (std_out) std_out[i] = n > 1 ? (float)sqrt(m2[i] / nm1) : 0.0f;
+  }
+}
+hipError_t launch_moments_update(const float* x, double* mean, double* m2, long long count, int r, hipStream_t st) {
+  hipLaunchKernelGGL(k_moments_update, dim3(grid_for(count)), dim3(256), 0, st, x, mean, m2, count, r);
+  return hipGetLastError();
+}
+hipError_t launch_moments_finish(const double* mean, const double* m2, long long count, int n, float* mean_out,
+                                 float* std_out, hipStream_t st) {
+  hipLaunchKernelGGL(k_moments_finish, dim3(grid_for(count)), dim3(256), 0, st, mean, m2, count, n, mean_out, std_out);
+  return hipGetLastError();
+}
+
 // (mul_f / add_f / mul_d / add_d, one IEEE operation each, live in dsx_kernels.h)
 // The mixed inputs of the TimePredictor evaluation (notebooks/EvaluateJointIndiIterative.ipynb cells 40/43,
 // time_prediction_evaluation.ipynb cell 4) cut, normalised, mixed and min-max-normalised in one pass; the op list is

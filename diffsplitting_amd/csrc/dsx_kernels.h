@@ -655,6 +655,16 @@ hipError_t launch_tiles_gather_norm_planes(const float* f0, const float* f1, int
                                            const int* starts, TileSeq seq, float w0, float w1, double mean_inp,
                                            double std_inp, const double* mean_target, const double* std_target,
                                            float* tin, float* ttar, hipStream_t st);
+// the network input of an input-only stack: frames (N, H, W) of uint8 / uint16 (pix_bytes 1 / 2) or fp32 (is_float, 4)
+// pixels -> out (count, 1, ph, pw) = (float)(((double)min((float)pixel, (float)clip) - mean) / std); clip < 0: none.
+// 1 <= seq.count <= 65535 (grid y); the grid's x grows with ph * pw.
+hipError_t launch_tiles_gather_input(const void* frames, int pix_bytes, bool is_float, int H, int W, int ph, int pw,
+                                     const int* starts, TileSeq seq, double mean, double std, double clip, float* out,
+                                     hipStream_t st);
+// Welford's recurrence over repeated samples, in double with every operation rounded on its own (include/dsx.h)
+hipError_t launch_moments_update(const float* x, double* mean, double* m2, long long count, int r, hipStream_t st);
+hipError_t launch_moments_finish(const double* mean, const double* m2, long long count, int n, float* mean_out,
+                                 float* std_out /* may be nullptr */, hipStream_t st);
 // crop + target normalisation + the two mixed inputs of the TimePredictor evaluation and their min-max-normalised
 // classifier views, fused (op list: include/dsx.h, dsx_tiles_gather_mix).  norm = {mean_t0, std_t0, mean_t1, std_t1};
 // w0 = (float)(1 - t), w1 = (float)t; lo / rng = (float)lo, (float)(hi - lo) of the table rows of the two channels.

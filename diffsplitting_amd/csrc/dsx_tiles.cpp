@@ -619,6 +619,51 @@ extern "C" int dsx_tileplan_gather_mix(dsx_tileplan* p, const float* frames0, co
                                   (hipStream_t)stream));
   return DSX_OK;
 }
+// the network input of an input-only stack, kept in its file width: every argument is checked on the host before
+// anything touches the device (the refusals need no GPU)
+extern "C" int dsx_tileplan_gather_input(dsx_tileplan* p, const void* frames, int pix_type, int64_t first, int64_t stride,
+                                         int64_t count, double mean_input, double std_input, double upper_clip,
+                                         float* tiles_in, void* stream) {
+  if (!p || !frames || !tiles_in) return fail(DSX_ERR_INVALID, "gather_input: null argument");
+  if (pix_type != DSX_PIX_U8 && pix_type != DSX_PIX_U16 && pix_type != DSX_PIX_F32)
+    return fail(DSX_ERR_INVALID, "gather_input: pixel type %d, must be uint8 (%d), uint16 (%d) or float32 (%d)", pix_type,
+                DSX_PIX_U8, DSX_PIX_U16, DSX_PIX_F32);
+  if (count < 1 || count > 65535)
+    return fail(DSX_ERR_INVALID, "gather_input: count = %lld, must be in 1..65535", (long long)count);
+  if (first < 0 || stride < 1 || first >= p->total || (count - 1) > (p->total - 1 - first) / stride)
+    return fail(DSX_ERR_INVALID, "gather_input: tiles %lld + k * %lld (%lld of them) leave the plan (%lld tiles)",
+                (long long)first, (long long)stride, (long long)count, (long long)p->total);
+  if (!std::isfinite(mean_input)) return fail(DSX_ERR_INVALID, "gather_input: mean_input must be finite");
+  if (!std::isfinite(std_input) || !(std_input > 0.0))
+    return fail(DSX_ERR_INVALID, "gather_input: std_input must be finite and positive");
+  if (upper_clip != upper_clip) return fail(DSX_ERR_INVALID, "gather_input: upper_clip is NaN");
+  if (p->t.p[1] * p->t.p[2] > INT32_MAX) return fail(DSX_ERR_INVALID, "gather_input: patch too large");
+  int rc = plan_device(p);
+  if (rc) return rc;
+  HIP_TRY(launch_tiles_gather_input(frames, pix_type == DSX_PIX_U8 ? 1 : pix_type == DSX_PIX_U16 ? 2 : 4,
+                                    pix_type == DSX_PIX_F32, (int)p->t.D[1], (int)p->t.D[2], (int)p->t.p[1], (int)p->t.p[2],
+                                    p->d_starts.as<int>(), TileSeq{first, stride, count}, mean_input, std_input,
+                                    upper_clip, tiles_in, (hipStream_t)stream));
+  return DSX_OK;
+}
+
+// mean and spread over repeated samples (Welford in double; launch_moments_* in dsx_eval.hip)
+extern "C" int dsx_moments_update(const float* x, double* mean, double* m2, int64_t count, int r, void* stream) {
+  if (!x || !mean || !m2) return fail(DSX_ERR_INVALID, "moments_update: null argument");
+  if (count < 1) return fail(DSX_ERR_INVALID, "moments_update: count = %lld, must be positive", (long long)count);
+  if (r < 0 || r >= (1 << 24)) return fail(DSX_ERR_INVALID, "moments_update: r = %d, must be in 0..2^24 - 1", r);
+  HIP_TRY(launch_moments_update(x, mean, m2, (long long)count, r, (hipStream_t)stream));
+  return DSX_OK;
+}
+extern "C" int dsx_moments_finish(const double* mean, const double* m2, int64_t count, int n, float* mean_out,
+                                  float* std_out, void* stream) {
+  if (!mean || !m2 || !mean_out) return fail(DSX_ERR_INVALID, "moments_finish: null argument (only std_out may be NULL)");
+  if (count < 1) return fail(DSX_ERR_INVALID, "moments_finish: count = %lld, must be positive", (long long)count);
+  if (n < 1 || n > (1 << 24)) return fail(DSX_ERR_INVALID, "moments_finish: n = %d, must be in 1..2^24", n);
+  HIP_TRY(launch_moments_finish(mean, m2, (long long)count, n, mean_out, std_out, (hipStream_t)stream));
+  return DSX_OK;
+}
+
 // paste whole predicted tiles (count, C, ph, pw) of the sequence; gt_canvas != NULL: also the PSNR partial sums
 // (count * dsx_stitch_psnr_blocks * C * 8 doubles, as dsx_stitch_psnr)
 extern "C" int dsx_tileplan_stitch(dsx_tileplan* p, const float* tiles, int C, int64_t first, int64_t stride, int64_t count,

@@ -90,6 +90,66 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
     return (canvas, calculate_lpips(target_frames, canvas, lpips)), plan
 
 
+@torch.no_grad()
+def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None):
+    """The tiled prediction of a dataset that cuts its own normalised tiles -- an ``InputStackTiledPred`` (one
+    superimposed acquisition, no ground truth) or a ``SplitDatasetTiledPred`` -- with ``samples`` posterior samples per
+    tile: their mean and, with ``return_std``, the unbiased per-pixel spread, accumulated by one fused launch per sample
+    (``engine.moments_update``, Welford in double) and one to finish.  ``samples == 1``: the prediction itself, spread 0.
+
+    Returns ``(out, plan)``, ``out = {'mean': (N,H,W,C)}`` plus ``'std'`` (N,H,W,C) with ``return_std`` and, for a
+    ``SplitDatasetTiledPred`` whose target has the prediction's channels, ``'psnr'`` (N,C): the RangeInvariantPsnr of the
+    mean against the normalised ground truth, accumulated while pasting.  Everything in normalised units, on every rank.
+
+    ``seed``: per-sample noise streams; sample ``r`` of tile ``k`` draws from sample id ``k + r * plan.total`` (the rule
+    of ``predict_tiled_mixed``), whatever batch or rank it runs in.  Tiles are sharded over the ranks and exchanged
+    through ``TileExchange``: one collective per output canvas."""
+    from .. import engine
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError(f"predict_stack: samples = {samples}: a positive count")
+    plan = dataset.plan
+    C_out = netG.prediction_channels
+    gt = None
+    if hasattr(dataset, "normalized_target_frames"):
+        gt = dataset.normalized_target_frames()                       # every rank holds the frames: no collective
+        if gt.shape[-1] != C_out or C_out > 4:
+            gt = None
+    ex = ex_std = None
+    ids = parallel.shard_ids(plan.total, parallel.rank(), parallel.world_size())
+    skw = {} if num_timesteps is None else dict(num_timesteps=num_timesteps)
+    for i in range(0, len(ids), batch_tiles):
+        chunk = ids[i:i + batch_tiles]
+        x = dataset.tiles(chunk)["input"]
+        if ex is None:
+            ex = TileExchange(plan, C_out, x.device, group, gt=gt)
+            ex_std = TileExchange(plan, C_out, x.device, group) if return_std else None
+        mean = m2 = None
+        for r in range(samples):
+            kw = {} if seed is None else dict(seed=seed, sample_ids=[k + r * plan.total for k in chunk])
+            netG.inference(x, continuous=False, **skw, **kw)
+            if samples > 1:
+                mean, m2 = engine.moments_update(netG.last_full_batch.contiguous(), mean, m2, r)
+        if samples == 1:
+            tiles, spread = netG.last_full_batch, None
+            if return_std:
+                spread = torch.zeros_like(tiles)
+        else:
+            tiles, spread = engine.moments_finish(mean, m2, samples, want_std=return_std)
+        ex.add(tiles, chunk)
+        if return_std:
+            ex_std.add(spread, chunk)
+    if ex is None:                                                    # a rank without tiles still joins the collectives
+        dev = torch.device("cuda", torch.cuda.current_device())
+        ex = TileExchange(plan, C_out, dev, group, gt=gt)
+        ex_std = TileExchange(plan, C_out, dev, group) if return_std else None
+    res = ex.finish()
+    out = {"mean": res[0], "psnr": res[1]} if gt is not None else {"mean": res}
+    if return_std:
+        out["std"] = ex_std.finish()
+    return out, plan
+
+
 # ---- mixed-input evaluation (BASELINE C5: JointIndi + TimePredictor) -----------------------------------------------
 def _batches(ids, batch):
     """Batches of ``batch`` consecutive entries of the arithmetic id list ``ids``; the last short batch is moved back

@@ -745,3 +745,50 @@ def interp_start(x1, x2, a0, s0, lam, z1=None, z2=None, seed=0, subsequence=0, o
                                C.c_float(float(lam)), _dptr(z1), _dptr(z2), _seed64(seed),
                                C.c_uint64(int(subsequence)), _dptr(out), _stream_ptr()))
     return out
+
+
+# ---------------------------------------------------------------------------
+# mean and spread over repeated samples (dsx_moments_update / dsx_moments_finish, include/dsx.h)
+# ---------------------------------------------------------------------------
+def _f64_cuda(t, what, numel):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != numel:
+        raise DsxError(f"{what} must be a contiguous float64 CUDA tensor of {numel} elements")
+    return t
+
+
+def moments_update(x, mean=None, m2=None, r=0):
+    """``dsx_moments_update``: sample ``r`` (0-based) of a series enters the running ``mean`` / ``m2`` (float64 CUDA
+    tensors of ``x``'s shape; allocated when None, which ``r == 0`` alone allows: that sample overwrites them) by
+    Welford's recurrence in double, one fused launch.  Returns ``(mean, m2)``."""
+    x = _f32_cuda(x, "x")
+    if x.numel() < 1:
+        raise DsxError("moments_update: x is empty")
+    if (mean is None) != (m2 is None):
+        raise DsxError("moments_update: mean and m2 are given together, or neither")
+    if mean is None:
+        if int(r) != 0:
+            raise DsxError(f"moments_update: sample r = {r} needs the running mean and m2 of the samples before it")
+        mean = torch.empty(x.shape, dtype=torch.float64, device=x.device)
+        m2 = torch.empty(x.shape, dtype=torch.float64, device=x.device)
+    _f64_cuda(mean, "mean", x.numel())
+    _f64_cuda(m2, "m2", x.numel())
+    with torch.cuda.device(x.device):
+        check(lib.dsx_moments_update(_dptr(x), _dptr(mean), _dptr(m2), x.numel(), int(r), _stream_ptr()))
+    return mean, m2
+
+
+def moments_finish(mean, m2, n, want_std=True):
+    """``dsx_moments_finish`` after ``n`` samples: ``(mean as float32, std as float32 or None)``, the unbiased spread
+    ``sqrt(m2 / (n - 1))`` (0 for ``n == 1``), one launch."""
+    if not torch.is_tensor(mean):
+        raise DsxError("moments_finish: mean must be a float64 CUDA tensor")
+    _f64_cuda(mean, "mean", mean.numel())
+    _f64_cuda(m2, "m2", mean.numel())
+    if mean.numel() < 1:
+        raise DsxError("moments_finish: mean is empty")
+    mean_out = torch.empty(mean.shape, dtype=torch.float32, device=mean.device)
+    std_out = torch.empty(mean.shape, dtype=torch.float32, device=mean.device) if want_std else None
+    with torch.cuda.device(mean.device):
+        check(lib.dsx_moments_finish(_dptr(mean), _dptr(m2), mean.numel(), int(n), _dptr(mean_out), _dptr(std_out),
+                                     _stream_ptr()))
+    return mean_out, std_out

@@ -28,6 +28,15 @@ no classifier), ``--mmse N`` repeats averaged.  Frames, ranks and ``--out`` as f
 ``--sample-seed S`` draws every tile's noise from its own stream (seed S, sample id = tile id; MMSE repeat ``r`` of the
 mixed-input prediction: tile id + r * tiles): the noise does not depend on ``--batch-tiles`` or ``--gpus``, and neither
 does the prediction for an equal batch size.  Off by default.
+
+``--input FILE`` splits a stack that has no ground truth: a ``.tif`` / ``.npy`` (N,H,W) acquisition in which the two
+structures are already superimposed (``data/input_stack.py``; uint8 / uint16 stacks stay on the device in their file
+width).  Its normalisation comes from ``--norm FILE``, written by ``--save-norm FILE`` of a run that had the channels
+(``--datapath``: the training stack's statistics; ``--frames``): ``data/normalization.py``.  ``--input-clip V`` clips the
+counts of the sum first.  ``--samples N`` draws N posterior samples per tile and writes their mean to ``--out``;
+``--std-out FILE`` the per-pixel spread in raw counts (``std * std_target``).  Both also apply to the plain two-channel
+prediction, where the PSNR of the mean shows what averaging buys.  Repeat ``r`` of tile ``k`` draws from sample id
+``k + r * tiles`` under ``--sample-seed``.
 """
 import argparse
 import logging
@@ -115,9 +124,10 @@ def _read_frames(path):
     return np.load(path, allow_pickle=False).astype(np.float32)
 
 
-def _write_prediction(path, pred, val_set):
+def _write_prediction(path, pred, val_set, spread=False):
     """--out: the stitched prediction (N,H,W,C), un-normalised to raw counts with the dataset's mean_target /
-    std_target, as .npy (N,H,W,C) float32 or as a .tif hyperstack of N * C float32 pages (frame-major)."""
+    std_target, as .npy (N,H,W,C) float32 or as a .tif hyperstack of N * C float32 pages (frame-major).  ``spread``
+    (--std-out): a per-pixel standard deviation, scaled by std_target with no mean added."""
     nd = val_set.get_normalization_dict()
     idx = val_set._target_channel_idx
     mean, std = (np.asarray(nd[k], dtype=np.float64).reshape(-1) for k in ("mean_target", "std_target"))
@@ -128,7 +138,7 @@ def _write_prediction(path, pred, val_set):
         raise DsxError(f"--out: the prediction has {C_out} channels, the dataset normalises {mean.size}")
     mean_t = torch.as_tensor(mean, dtype=torch.float32, device=pred.device)
     std_t = torch.as_tensor(std, dtype=torch.float32, device=pred.device)
-    raw = (pred * std_t + mean_t).cpu().numpy()
+    raw = ((pred * std_t) if spread else (pred * std_t + mean_t)).cpu().numpy()
     if str(path).endswith(".npy"):
         np.save(path, raw)
     elif str(path).endswith((".tif", ".tiff")):
@@ -177,6 +187,17 @@ def main(argv=None):
     ap.add_argument("--sample-seed", type=int, default=None,
                     help="per-sample noise streams: every tile draws from the stream (seed, tile id), whatever batch "
                          "or rank predicts it (default: off, one stream per step over the batch)")
+    ap.add_argument("--input", type=str, default=None,
+                    help=".tif or .npy with one (N,H,W) stack in which the two structures are already superimposed "
+                         "(no ground truth); needs --norm")
+    ap.add_argument("--norm", type=str, default=None, help="with --input: the normalisation file (--save-norm)")
+    ap.add_argument("--input-clip", type=float, default=None, help="with --input: clip the counts at this value first")
+    ap.add_argument("--save-norm", type=str, default=None,
+                    help="with --datapath or --frames: write the normalisation the validation set uses to this file")
+    ap.add_argument("--samples", type=int, default=None,
+                    help="posterior samples per tile of the tiled prediction; --out holds their mean (default 1)")
+    ap.add_argument("--std-out", type=str, default=None,
+                    help="write the per-pixel spread over --samples >= 2 samples in raw counts (.npy / .tif)")
     args = ap.parse_args(argv)
     if args.sample_seed is not None and args.validate:
         raise SystemExit("--sample-seed names the tiles of a tiled prediction: not with --validate")
@@ -188,6 +209,7 @@ def main(argv=None):
         raise SystemExit("--out: a .npy or .tif file")
     if args.out and args.validate:
         raise SystemExit("--out writes the tiled prediction: not with --validate")
+    _check_input_args(args)
     _check_mixed_args(args)
     n_ranks = args.gpus if args.gpus is not None else len(str(args.gpu_ids).split(","))
     if argv is None and parallel.needs_self_launch(n_ranks):
@@ -226,8 +248,19 @@ def main(argv=None):
 
     dsopt = opt["datasets"] or {}
     which = opt["model"]["which_model_G"]
+    if args.input:
+        from .data.input_stack import InputStackTiledPred, read_stack
+        from .data.normalization import load_normalization
+        nd, _ = load_normalization(args.norm)
+        stack = read_stack(args.input)
+        patch = min(_config_patch(dsopt), stack.shape[1], stack.shape[2])
+        val_set = InputStackTiledPred(stack, patch, nd, grid_size=patch // 2,
+                                      target_channel_idx=dsopt.get("target_channel_idx"), input_clip=args.input_clip,
+                                      device=dev)
+        return _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log)
     if args.datapath:
         _, val_set = get_datasets(opt, tiled_pred=not (args.validate or colour), norm_from=args.norm_from, device=dev)
+        _save_norm(args, val_set, dsopt, _data_type(dsopt, args.norm_from), rank, log)
         if args.validate or colour:
             return _run_validate(args, opt, diffusion, val_set, log, whole_set=colour)
         if args.mix_t is not None:
@@ -243,15 +276,15 @@ def main(argv=None):
     # the validation dataset of split.get_datasets(opt, tiled_pred=True) (reference split.py:30-71) with the frames
     # resident on the GPU: quantile normalisation (compute_normalization_dict), ShiftBoundary tiling, normalised
     # tile batches cut by one HIP launch
-    patch = (dsopt["val"] or {}).get("patch_size") if dsopt.get("val") else None
-    patch = int(patch or dsopt.get("patch_size") or 512)
-    patch = min(patch, frames.shape[1], frames.shape[2])
+    patch = min(_config_patch(dsopt), frames.shape[1], frames.shape[2])
     val_set = SplitDatasetTiledPred("Hagen", DataLocation(arrays=(frames[..., 0], frames[..., 1])), patch,
                                     grid_size=patch // 2, target_channel_idx=dsopt.get("target_channel_idx"),
                                     max_qval=dsopt.get("max_qval") or 0.98, upper_clip=bool(dsopt.get("upper_clip")),
                                     channel_weights=dsopt.get("channel_weights"), enable_transforms=False,
                                     random_patching=False, input_from_normalized_target=(which == "joint_indi"),
                                     device=dev)
+    if args.frames:
+        _save_norm(args, val_set, dsopt, "Hagen", rank, log)
     if args.validate:
         return _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log)
     if args.mix_t is not None:
@@ -259,31 +292,42 @@ def main(argv=None):
     return _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log)
 
 
-def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
-    """The tiled prediction of ``val_set`` over the ranks; rank 0 writes ``--out``.  Returns the stitched canvas."""
-    plan = val_set.plan
-    ids = parallel.shard_ids(plan.total, rank, world)
+def _config_patch(dsopt):
+    """The patch size of the config: ``datasets.val.patch_size``, else ``datasets.patch_size``, else 512."""
+    patch = (dsopt["val"] or {}).get("patch_size") if dsopt.get("val") else None
+    return int(patch or dsopt.get("patch_size") or 512)
 
+
+def _save_norm(args, val_set, dsopt, data_type, rank, log):
+    """``--save-norm``: rank 0 writes the dict ``val_set`` is normalised with (data/normalization.py)."""
+    if not args.save_norm or rank != 0:
+        return
+    from .data.normalization import save_normalization
+    save_normalization(args.save_norm, val_set.get_normalization_dict(), data_type=data_type,
+                       channel_weights=dsopt.get("channel_weights"), max_qval=dsopt.get("max_qval") or 0.98,
+                       upper_clip=bool(dsopt.get("upper_clip")), target_channel_idx=dsopt.get("target_channel_idx"))
+    log.info("normalisation written to %s", args.save_norm)
+
+
+def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
+    """The tiled prediction of ``val_set`` (two channels, or an input-only stack) over the ranks, ``--samples`` posterior
+    samples per tile; rank 0 writes the mean to ``--out`` and the spread to ``--std-out``.  Returns the stitched mean."""
+    from .data.tiled_predict import predict_stack
+    samples = args.samples or 1
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    # every rank holds the frames: the ground truth needs no tiles and no collective
-    C_out = netG.prediction_channels
-    gt = val_set.normalized_target_frames()                           # (N,H,W,C_target), normalised
-    score = gt.shape[-1] == C_out and C_out <= 4
-    ex = TileExchange(plan, C_out, dev, gt=gt if score else None)
-    for i in range(0, len(ids), args.batch_tiles):
-        chunk = ids[i:i + args.batch_tiles]
-        batch = val_set.tiles(chunk)
-        skw = {} if args.sample_seed is None else dict(seed=args.sample_seed, sample_ids=chunk)
-        netG.inference(batch["input"], continuous=False, num_timesteps=n_steps, **skw)
-        ex.add(netG.last_full_batch, chunk)
-    res = ex.finish()                                                 # the path's only collective: cropped tiles
-    pred, ps = res if score else (res, None)                          # metric accumulated while pasting
+    # every rank holds the frames: the ground truth needs no tiles and no collective; the metric is accumulated while
+    # pasting, and the path's only collectives are the cropped tiles of each output canvas
+    out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
+                              return_std=bool(args.std_out), seed=args.sample_seed)
+    pred, ps = out["mean"], out.get("psnr")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if rank == 0:
         log.info("tiled prediction: %d tiles of %d^2, %d steps, %d GPU(s): %.3f s (%.1f tiles/s)",
                  plan.total, patch, n_steps, world, dt, plan.total / dt)
+        if samples > 1:
+            log.info("mean over %d posterior samples per tile", samples)
         if ps is not None:
             for c in range(ps.shape[1]):
                 log.info("channel %d: RangeInvariantPsnr %.2f +- %.2f dB (random-init weights unless a checkpoint "
@@ -292,7 +336,63 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
         if args.out:
             _write_prediction(args.out, pred, val_set)
             log.info("prediction written to %s", args.out)
+        if args.std_out:
+            _write_prediction(args.std_out, out["std"], val_set, spread=True)
+            log.info("spread over %d samples written to %s", samples, args.std_out)
     return pred
+
+
+def _check_input_args(args):
+    """The flags of the input-only prediction and of the posterior samples, checked on the command line, the config and
+    the normalisation file alone (nothing touches the GPU, no rank is started)."""
+    if args.samples is not None:
+        if args.samples < 1:
+            raise SystemExit(f"--samples {args.samples}: a positive count of posterior samples")
+        if args.mix_t is not None:
+            raise SystemExit("--samples: not with --mix-t; the repeats of the mixed-input prediction are --mmse N")
+        if args.validate:
+            raise SystemExit("--samples repeats the tiles of a tiled prediction: not with --validate")
+    if args.std_out:
+        if not args.std_out.endswith((".npy", ".tif", ".tiff")):
+            raise SystemExit("--std-out: a .npy or .tif file")
+        if args.validate or args.mix_t is not None:
+            raise SystemExit("--std-out writes the spread of a tiled prediction: not with --validate or --mix-t")
+        if (args.samples or 1) < 2:
+            raise SystemExit("--std-out: the spread needs --samples 2 or more (--samples 1 has none)")
+    if args.save_norm and not (args.datapath or args.frames):
+        raise SystemExit("--save-norm writes the normalisation of real channels: only with --datapath or --frames")
+    if not args.input:
+        for flag, value in (("--norm", args.norm), ("--input-clip", args.input_clip)):
+            if value is not None:
+                raise SystemExit(f"{flag}: only with --input FILE")
+        return
+    for flag, value in (("--datapath", args.datapath), ("--frames", args.frames), ("--validate", args.validate),
+                        ("--mix-t", args.mix_t is not None)):
+        if value:
+            raise SystemExit(f"--input with {flag}: an input-only stack has no ground-truth channels; it is a tiled "
+                             "prediction of its own")
+    if not args.norm:
+        raise SystemExit("--input needs --norm FILE: the normalisation of the training set, written by --save-norm (an "
+                         "input-only stack has no channels to compute it from)")
+    if args.input_clip is not None and not (np.isfinite(args.input_clip) and args.input_clip >= 0):
+        raise SystemExit(f"--input-clip {args.input_clip}: a finite, non-negative count")
+    cfg = Logger.load_json(args.config)
+    which = (cfg.get("model") or {}).get("which_model_G")
+    if which == "joint_indi":
+        raise SystemExit("--input with a joint_indi config: its network input is the weighted sum of the NORMALISED "
+                         "channels, which is no function of the superimposed counts unless both stds are equal")
+    from .data.normalization import load_normalization
+    try:
+        _, meta = load_normalization(args.norm)
+    except (DsxError, OSError) as e:
+        raise SystemExit(f"--norm {args.norm}: {e}")
+    if meta["data_type"] == "cifar10":
+        raise SystemExit(f"--norm {args.norm}: a cifar10 normalisation; --input takes a grey (N,H,W) stack, colour items "
+                         "are not tiled")
+    idx = ((cfg.get("datasets") or {}).get("target_channel_idx"))
+    if meta["target_channel_idx"] != idx:
+        raise SystemExit(f"--norm {args.norm}: written for target_channel_idx = {meta['target_channel_idx']}, the config "
+                         f"says {idx}")
 
 
 _MIXED_FLAGS = (("--mix-t", "mix_t"), ("--time-predictor", "time_predictor"),

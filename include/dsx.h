@@ -658,6 +658,27 @@ int dsx_tileplan_gather_norm(dsx_tileplan* plan, const float* frames0_dev, const
 int dsx_tileplan_gather_mix(dsx_tileplan* plan, const float* frames0_dev, const float* frames1_dev, int64_t first,
                             int64_t stride, int64_t count, const double norm[4], double t, const double lohi[4],
                             float* target_dev, float* mix_dev, float* cls_dev, void* stream);
+/* The network input of an INPUT-ONLY stack: frames_dev holds the plan's (N,H,W) frames in their file width, pix_type =
+ * DSX_PIX_U8 / DSX_PIX_U16 / DSX_PIX_F32 (below; DSX_PIX_U32 is refused), in which the two structures are already
+ * superimposed.  Per element of the tiles first + k*stride, k < count (1..65535 per call):
+ *   x = (float)pixel (exact for the integer types);  upper_clip >= 0: x = min(x, (float)upper_clip);
+ *   tiles_in = (float)(((double)x - mean_input) / std_input)
+ * -- what dsx_tileplan_gather_norm (from_norm_target = 0) applies to w0 * p0 + w1 * p1: on a stack that holds
+ * fl(fl(w0 * c0) + fl(w1 * c1)) the tiles equal that call's tiles_in bit for bit.  tiles_in_dev (count, 1, ph, pw).
+ * Null pointers, another pixel type, a count outside 1..65535, tiles outside the plan, a non-finite mean and a
+ * non-finite or non-positive std are DSX_ERR_INVALID before any HIP call. */
+int dsx_tileplan_gather_input(dsx_tileplan* plan, const void* frames_dev, int pix_type, int64_t first, int64_t stride,
+                              int64_t count, double mean_input, double std_input, double upper_clip,
+                              float* tiles_in_dev, void* stream);
+/* Mean and spread over n repeated samples of `count` values (the posterior of a diffusion splitter), Welford's
+ * recurrence in double, one launch per sample r = 0, 1, ... and one to finish:
+ *   update, r == 0: mean = x, M2 = 0;  r > 0: d = x - mean;  mean' = mean + d / (r + 1);  M2' = M2 + d * (x - mean')
+ *   finish: mean_out = (float)mean;  std_out = n > 1 ? (float)sqrt(M2 / (n - 1)) : 0      (std_out_dev may be NULL)
+ * Every operation is rounded on its own (no fma): a float64 restatement of these lines in the same order is bit-equal.
+ * r in 0..2^24 - 1, n in 1..2^24, count >= 1 and non-null pointers, or DSX_ERR_INVALID before any device work. */
+int dsx_moments_update(const float* x_dev, double* mean_dev, double* m2_dev, int64_t count, int r, void* stream);
+int dsx_moments_finish(const double* mean_dev, const double* m2_dev, int64_t count, int n, float* mean_out_dev,
+                       float* std_out_dev, void* stream);
 /* dsx_stitch (gt_canvas_dev == NULL) or dsx_stitch_psnr for whole predicted tiles (count, C, ph, pw) of the sequence */
 int dsx_tileplan_stitch(dsx_tileplan* plan, const float* tiles_dev, int C, int64_t first, int64_t stride, int64_t count,
                         float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream);
