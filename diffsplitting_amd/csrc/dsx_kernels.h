@@ -1,5 +1,5 @@
 // dsx_kernels.h — launch interface between the host runtime (dsx_*.cpp)
-// and the gfx950 kernels (dsx_conv*.hip, dsx_ops.hip, dsx_attn.hip, dsx_eval.hip, ...).  Internal;
+// and the gfx950 kernels (dsx_conv*.hip, dsx_ops.hip, dsx_attn.hip, dsx_tiles.hip, dsx_eval.hip, ...).  Internal;
 // the public ABI is include/dsx.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -637,54 +637,79 @@ struct InterpStartArgs {
 };
 hipError_t launch_interp_start(const InterpStartArgs& a, long long HW, hipStream_t st);
 
-// dsx_eval.hip: tiles, range table, stitch, image metrics.
+// dsx_tiles.hip: tile gather, stitch and pack of tiled prediction (never inside a sampling step).
 // the tiles of one launch: ids first, first + stride, ... (count of them); the tables a kernel indexes with an id
 // (`starts` [..][3], `regions` [..][8], `off` [..]) live on the device -- the plan's own (dsx_tileplan), or a per-call
 // table with first = 0, stride = 1
 struct TileSeq { long long first, stride, count; };
-hipError_t launch_tiles_gather(const float* frames, int H, int W, int ph, int pw, const int* starts /*dev*/, TileSeq seq,
-                               float* tiles, hipStream_t st);
+constexpr long long kMaxItemsPerLaunch = 65535;   // tiles / items of one launch: they are the grid's y (or z)
+// the geometry of a gather: (N, H, W) frames cut into ph x pw patches at starts[id] = (frame, y, x), for the ids of
+// seq.  `starts` is a device table; the per-item kernel (launch_tiles_gather_mix_items) carries its starts in its
+// records and does not read it.
+struct TileGeom { int H, W, ph, pw; const int* starts; TileSeq seq; };
+hipError_t launch_tiles_gather(const float* frames, const TileGeom& g, float* tiles, hipStream_t st);
 // crop + dataset normalisation fused (SplitDataset.__getitem__): norm = {mean_inp, std_inp, mean_t0, std_t0, mean_t1, std_t1}
-hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
-                                    TileSeq seq, float w0, float w1, const double norm[6], int from_norm_target,
-                                    float* tin, float* ttar, hipStream_t st);
+hipError_t launch_tiles_gather_norm(const float* f0, const float* f1, const TileGeom& g, float w0, float w1,
+                                    const double norm[6], int from_norm_target, float* tin, float* ttar, hipStream_t st);
 // the same for frames with colour planes: stacks (N, Cc, H, W), tin (count, Cc, ph, pw), ttar (count, 2 Cc, ph, pw),
-// one mean / std per target plane (2 Cc of each); 1 <= Cc <= kPlanesMaxC, 1 <= seq.count <= 65535 (grid z)
+// one mean / std per target plane (2 Cc of each); 1 <= Cc <= kPlanesMaxC, the items are the grid's z
 constexpr int kPlanesMaxC = 8;
-hipError_t launch_tiles_gather_norm_planes(const float* f0, const float* f1, int Cc, int H, int W, int ph, int pw,
-                                           const int* starts, TileSeq seq, float w0, float w1, double mean_inp,
-                                           double std_inp, const double* mean_target, const double* std_target,
-                                           float* tin, float* ttar, hipStream_t st);
+hipError_t launch_tiles_gather_norm_planes(const float* f0, const float* f1, int Cc, const TileGeom& g, float w0, float w1,
+                                           double mean_inp, double std_inp, const double* mean_target,
+                                           const double* std_target, float* tin, float* ttar, hipStream_t st);
 // the network input of an input-only stack: frames (N, H, W) of uint8 / uint16 (pix_bytes 1 / 2) or fp32 (is_float, 4)
 // pixels -> out (count, 1, ph, pw) = (float)(((double)min((float)pixel, (float)clip) - mean) / std); clip < 0: none.
-// 1 <= seq.count <= 65535 (grid y); the grid's x grows with ph * pw.
-hipError_t launch_tiles_gather_input(const void* frames, int pix_bytes, bool is_float, int H, int W, int ph, int pw,
-                                     const int* starts, TileSeq seq, double mean, double std, double clip, float* out,
-                                     hipStream_t st);
-// Welford's recurrence over repeated samples, in double with every operation rounded on its own (include/dsx.h)
-hipError_t launch_moments_update(const float* x, double* mean, double* m2, long long count, int r, hipStream_t st);
-hipError_t launch_moments_finish(const double* mean, const double* m2, long long count, int n, float* mean_out,
-                                 float* std_out /* may be nullptr */, hipStream_t st);
+// The grid's x grows with ph * pw.
+hipError_t launch_tiles_gather_input(const void* frames, int pix_bytes, bool is_float, const TileGeom& g, double mean,
+                                     double std, double clip, float* out, hipStream_t st);
 // crop + target normalisation + the two mixed inputs of the TimePredictor evaluation and their min-max-normalised
 // classifier views, fused (op list: include/dsx.h, dsx_tiles_gather_mix).  norm = {mean_t0, std_t0, mean_t1, std_t1};
 // w0 = (float)(1 - t), w1 = (float)t; lo / rng = (float)lo, (float)(hi - lo) of the table rows of the two channels.
 // Any of ttar / tmix / tcls may be nullptr (not all three); each is (count, 2, ph, pw).
 struct MixWeights { float w0, w1, lo0, rng0, lo1, rng1; };
-hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, int H, int W, int ph, int pw, const int* starts,
-                                   TileSeq seq, const double norm[4], const MixWeights& mw, float* ttar, float* tmix,
-                                   float* tcls, hipStream_t st);
+hipError_t launch_tiles_gather_mix(const float* f0, const float* f1, const TileGeom& g, const double norm[4],
+                                   const MixWeights& mw, float* ttar, float* tmix, float* tcls, hipStream_t st);
 // the same with one record per item (dev table, item k of the launch = items[k]): its (frame, y, x) start and its own
-// weights.  1 <= count <= 65535 (grid y); the arithmetic per element is launch_tiles_gather_mix's, bit for bit.
+// weights (g.starts is not read, g.seq = {0, 1, count}); the arithmetic per element is launch_tiles_gather_mix's, bit
+// for bit.
 struct MixItem { int n, y, x; MixWeights w; };
-hipError_t launch_tiles_gather_mix_items(const float* f0, const float* f1, int H, int W, int ph, int pw,
-                                         const MixItem* items /*dev*/, long long count, const double norm[4], float* ttar,
-                                         float* tmix, float* tcls, hipStream_t st);
+hipError_t launch_tiles_gather_mix_items(const float* f0, const float* f1, const TileGeom& g, const MixItem* items /*dev*/,
+                                         const double norm[4], float* ttar, float* tmix, float* tcls, hipStream_t st);
+// source of a paste: whole predicted tiles (count, C, ph, pw) of the sequence, or the gathered packed exchange buffer
+// [world][rank_stride] (valid regions [C][h][w] of rank q's tiles q, q + world, ... back to back; `off` = pixel offset
+// of each tile id inside its rank's run)
+struct StitchSrc {
+  const float* base; int packed; int ph, pw;
+  const long long* off; long long rank_stride; int world;
+};
+// paste (gt == nullptr) or paste + per-(tile, workgroup, channel) partial sums for RangeInvariantPsnr:
+// part[count][gx][C][8] doubles {sum p, sum p^2, sum g, sum g^2, sum g p, min g, max g, 0}
+hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions /*dev*/, TileSeq seq, float* canvas, int H, int W,
+                         const float* gt, double* part, int gx, hipStream_t st);
+// valid regions of the sequence's tiles -> this rank's flat run (the crop of tile_stitcher.py:38-56 before the collective)
+hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const int* regions, const long long* off,
+                             TileSeq seq, float* flat, hipStream_t st);
+
+// dsx_eval.hip: Welford moments, range table, image metrics (the loss reduction is declared with the steps above).
+// Welford's recurrence over repeated samples, in double with every operation rounded on its own (include/dsx.h)
+hipError_t launch_moments_update(const float* x, double* mean, double* m2, long long count, int r, hipStream_t st);
+hipError_t launch_moments_finish(const double* mean, const double* m2, long long count, int n, float* mean_out,
+                                 float* std_out /* may be nullptr */, hipStream_t st);
 // min / max over all pixels of t * a + (1 - t) * b, t = t_int / n for t_int = 0..n, on the normalised channels
 // (compute_input_normalization_dict, data/time_predictor_dataset.py:6-21), fp64 with every operation rounded on its
 // own.  part[mix_range_blocks(pixels)][n + 1][2] = {min, max} per pixel workgroup; the caller reduces over the rows.
 int mix_range_blocks(long long pixels);
 hipError_t launch_mix_range(const float* f0, const float* f1, long long pixels, const double norm[4], int n, double* part,
                             hipStream_t st);
+// SSIM (core/metrics.py:72-92) + sum of squared differences of `planes` image pairs (H, W >= 11), optionally quantised
+// on the load as tensor2img does (:14-34); part[planes][image_metrics_tiles(H, W)][2] = {sum of the SSIM map over
+// the tile, SSD (uint64 bits when quantised, else fp64)}.  win = the 11 taps of cv2.getGaussianKernel(11, 1.5).
+struct SsimWindow { double w[11]; };
+int image_metrics_tiles(int H, int W);
+hipError_t launch_image_metrics(const float* a, const float* b, int planes, int H, int W, int quantize, float lo,
+                                float hi, float rng, double c1, double c2, const SsimWindow& win, double* part,
+                                hipStream_t st);
+
 // dsx_select.hip.  One pass of the radix select behind dsx_order_stats: hist[1 << bits] (64-bit, zeroed by the caller)
 // += the digit (u >> shift) & (2^bits - 1) of every element whose key image u has u >> match_shift == prefix
 // (match_shift = 64: every element).  b == nullptr: single source.
@@ -702,29 +727,6 @@ struct SelectArgs {
 hipError_t launch_select_hist(const SelectArgs& s, hipStream_t st);
 // dst = (float)min(src, clip) for count uint8 (src_bytes 1) or uint16 (2) values; clip < 0: none
 hipError_t launch_widen(const void* src, int src_bytes, long long count, double clip, float* dst, hipStream_t st);
-// source of a paste: whole predicted tiles (count, C, ph, pw) of the sequence, or the gathered packed exchange buffer
-// [world][rank_stride] (valid regions [C][h][w] of rank q's tiles q, q + world, ... back to back; `off` = pixel offset
-// of each tile id inside its rank's run)
-struct StitchSrc {
-  const float* base; int packed; int ph, pw;
-  const long long* off; long long rank_stride; int world;
-};
-// paste (gt == nullptr) or paste + per-(tile, workgroup, channel) partial sums for RangeInvariantPsnr:
-// part[count][gx][C][8] doubles {sum p, sum p^2, sum g, sum g^2, sum g p, min g, max g, 0}
-hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions /*dev*/, TileSeq seq, float* canvas, int H, int W,
-                         const float* gt, double* part, int gx, hipStream_t st);
-// valid regions of the sequence's tiles -> this rank's flat run (the crop of tile_stitcher.py:38-56 before the collective)
-hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const int* regions, const long long* off,
-                             TileSeq seq, float* flat, hipStream_t st);
-
-// SSIM (core/metrics.py:72-92) + sum of squared differences of `planes` image pairs (H, W >= 11), optionally quantised
-// on the load as tensor2img does (:14-34); part[planes][image_metrics_tiles(H, W)][2] = {sum of the SSIM map over
-// the tile, SSD (uint64 bits when quantised, else fp64)}.  win = the 11 taps of cv2.getGaussianKernel(11, 1.5).
-struct SsimWindow { double w[11]; };
-int image_metrics_tiles(int H, int W);
-hipError_t launch_image_metrics(const float* a, const float* b, int planes, int H, int W, int quantize, float lo,
-                                float hi, float rng, double c1, double c2, const SsimWindow& win, double* part,
-                                hipStream_t st);
 
 // LPIPS (AlexNet trunk, v0.1 heads), dsx_lpips.hip: fp32 NHWC, the two images of pair b are images b and B + b of a
 // batch of nimg = 2 B.  Weights are packed by dsx_lpips.cpp: conv1 [N block 2][group 46][lane 64] float4 over

@@ -1,6 +1,6 @@
 // dsx_rt.h — what the host translation units of libdsx.so share (dsx_model.cpp, dsx_plan.cpp, dsx_exec.cpp,
-// dsx_tiles.cpp): the error state, the owners of HIP resources, the model and the executor with the plain-data types
-// they contain, and the few functions called across files.  Internal; the public ABI is include/dsx.h.
+// dsx_tiles.cpp, dsx_eval.cpp): the error state, the owners of HIP resources, the model and the executor with the
+// plain-data types they contain, and the few functions called across files.  Internal; the public ABI is include/dsx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -329,4 +329,6 @@ int run_planner(dsx_exec* ex, char* fake_base, size_t* sizing_bytes);
 hipError_t launch_op(const PlanOp& o, hipStream_t st);
 // dsx_exec.cpp
 std::unique_ptr<dsx_exec> new_exec(dsx_model* m, int B, int H, int W, int cond_channels);
+// dsx_eval.cpp
+int norm4_ok(const double norm[4]);
 }  // namespace dsx

@@ -27,7 +27,7 @@ import torch
 
 from .. import _lib
 from .._lib import DsxError, check, lib
-from .tiling import TilePlan
+from .tiling import TilePlan, _i64x3
 from .tiling_manager import TileIndexManager, TilingMode
 
 
@@ -109,7 +109,7 @@ def frames_to_device(frames, dev, clip=None):
     with torch.cuda.device(dst.device):
         check(lib.dsx_frames_to_f32(C.c_void_p(src.data_ptr()), _lib.PIX_U16 if frames.dtype == np.uint16 else _lib.PIX_U8,
                                     frames.size, -1.0 if clip is None else float(clip), C.c_void_p(dst.data_ptr()),
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                    TilePlan._stream()))
         torch.cuda.current_stream().synchronize()                   # `src` is released on return
     return dst
 
@@ -141,7 +141,7 @@ def order_stats_device(a, b, w0, w1, ranks):
         check(lib.dsx_order_stats(C.c_void_p(a.data_ptr()), None if b is None else C.c_void_p(b.data_ptr()), a.numel(),
                                   float(w0), float(w1), ranks.ctypes.data_as(C.POINTER(C.c_int64)), ranks.size,
                                   out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(ws.data_ptr()),
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                  TilePlan._stream()))
     return out
 
 
@@ -319,14 +319,13 @@ class SplitDataset:
         dev = self._dev[0].device
         tin = torch.empty((b, 1, p, p), dtype=torch.float32, device=dev)
         ttar = torch.empty((b, 2, p, p), dtype=torch.float32, device=dev)
-        i64 = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
         shape3 = (self._data_shape[0],) + self._data_shape[-2:]      # (N,1,H,W) frames are (N,H,W) frames
         check(lib.dsx_tiles_gather_norm(C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()),
-                                        i64(shape3), i64((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        _i64x3(shape3), _i64x3((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
                                         None, b, float(self._channel_weights[0]), float(self._channel_weights[1]),
                                         self._norm6(), 1 if self._input_from_normalized_target else 0,
                                         C.c_void_p(tin.data_ptr()), C.c_void_p(ttar.data_ptr()),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                        TilePlan._stream()))
         if self._target_channel_idx is not None:
             ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
         return {"input": tin, "target": ttar}
@@ -352,7 +351,7 @@ class SplitDataset:
                     part.ctypes.data_as(C.POINTER(C.c_int64)), None, part.shape[0], float(self._channel_weights[0]),
                     float(self._channel_weights[1]), float(self._mean_inp), float(self._std_inp), mt.ctypes.data_as(pd),
                     st.ctypes.data_as(pd), C.c_void_p(tin[i0:].data_ptr()), C.c_void_p(ttar[i0:].data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                    TilePlan._stream()))
         if self._target_channel_idx is not None:
             ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
         return {"input": tin, "target": ttar}
@@ -399,11 +398,10 @@ class SplitDataset:
         loc = np.ascontiguousarray(np.asarray(locations, dtype=np.int64).reshape(-1, 3))
         b, p = loc.shape[0], self._patch_size
         out, ptr, lh = self._mixed_new(b, lohi, want)
-        i64 = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
         check(lib.dsx_tiles_gather_mix(C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()),
-                                       i64(self._data_shape), i64((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
+                                       _i64x3(self._data_shape), _i64x3((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
                                        None, b, self._norm4(), float(mixing_t), lh, ptr("target"), ptr("mix"), ptr("cls"),
-                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                       TilePlan._stream()))
         return out
 
     def mixed_tiles(self, indices, mixing_t, table=None, want=None):
@@ -458,7 +456,7 @@ class SplitDatasetTiledPred(SplitDataset):
                                                float(self._channel_weights[0]), float(self._channel_weights[1]),
                                                self._norm6(), 1 if self._input_from_normalized_target else 0,
                                                C.c_void_p(tin.data_ptr()), C.c_void_p(ttar.data_ptr()),
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                               TilePlan._stream()))
         if self._target_channel_idx is not None:
             ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
         return {"input": tin, "target": ttar}
@@ -486,7 +484,7 @@ class SplitDatasetTiledPred(SplitDataset):
             check(lib.dsx_tileplan_gather_mix(self.plan.handle, C.c_void_p(self._dev[0].data_ptr()),
                                               C.c_void_p(self._dev[1].data_ptr()), first, stride, count, self._norm4(),
                                               float(mixing_t), lh, ptr("target"), ptr("mix"), ptr("cls"),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                                              TilePlan._stream()))
         return out
 
     def normalized_target_frames(self):

@@ -447,7 +447,10 @@ int dsx_tile_regions(const int64_t data_shape[3], const int64_t grid_shape[3],
 /* Cuts tiles out of frames on the device: frames (N,H,W) fp32 ->
  * tiles (count, ph, pw) for the tiles listed in tile_ids (host array).
  * Replaces the per-item crop of SplitDataset.__getitem__
- * (data/split_dataset.py:237-246) for batch dispatch. */
+ * (data/split_dataset.py:237-246) for batch dispatch.
+ * This and every other per-call form below (dsx_tiles_gather_*, dsx_stitch*) checks on the host, before anything
+ * touches the device: count in 0..65535 (the tiles of a call are one launch), no negative id, every (frame, y, x) on
+ * its int64 value inside the frames.  DSX_ERR_INVALID otherwise; count == 0 does nothing. */
 int dsx_tiles_gather(const float* frames_dev, const int64_t data_shape[3],
                      const int64_t patch_shape[3], const int64_t* patch_start_host,
                      const int64_t* tile_ids_host, int64_t count, float* tiles_dev, void* stream);
