@@ -119,10 +119,9 @@ class LPIPS(torch.nn.Module):
             state_dict = _load_files(path)
         trunk, lin = split_state_dict(state_dict)
         self._keep = trunk + lin                                       # host tensors the library reads during create
-        ptr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         cnt = lambda ts: (C.c_int64 * len(ts))(*[t.numel() for t in ts])
         h = C.c_void_p()
-        check(lib.dsx_lpips_create(ptr(trunk), cnt(trunk), ptr(lin), cnt(lin), C.byref(h)))
+        check(lib.dsx_lpips_create(_lib.host_pointers(trunk), cnt(trunk), _lib.host_pointers(lin), cnt(lin), C.byref(h)))
         self._h = h
         self._keep = None
 
@@ -155,11 +154,7 @@ class LPIPS(torch.nn.Module):
         B, _, H, W = a.shape
         out = torch.empty((B,), dtype=torch.float32, device=dev)
         taps = torch.empty((B, 5), dtype=torch.float32, device=dev) if retPerLayer else None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            check(lib.dsx_lpips_forward(self._h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), B, H, W,
-                                        C.c_void_p(out.data_ptr()),
-                                        C.c_void_p(taps.data_ptr()) if retPerLayer else None, C.c_void_p(stream)))
+        check(lib.dsx_lpips_forward(self._h, a, b, B, H, W, out, taps, None))
         val = out.view(B, 1, 1, 1)
         if retPerLayer:
             return val, [taps[:, k].reshape(B, 1, 1, 1) for k in range(5)]
@@ -178,8 +173,5 @@ class LPIPS(torch.nn.Module):
         p = pred.to(dev, torch.float32).contiguous()
         N, H, W, Cn = t.shape
         out = torch.empty((N,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            check(lib.dsx_lpips_frames(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(p.data_ptr()), N, H, W, Cn,
-                                       int(channel), int(chunk), C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+        check(lib.dsx_lpips_frames(self._h, t, p, N, H, W, Cn, int(channel), int(chunk), out, None))
         return out

@@ -115,12 +115,9 @@ def _run(a, b, quantize, lo, hi, data_range, stream=None):
     part = torch.empty((B * Cn * blocks * 2,), dtype=torch.float64, device=a.device)
     ssim = np.empty(B, np.float64)
     ssd = np.empty(B, np.float64)
-    if stream is None:
-        stream = torch.cuda.current_stream(a.device).cuda_stream
     pd = C.POINTER(C.c_double)
-    check(lib.dsx_image_metrics(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), B, Cn, H, W, int(quantize),
-                                float(lo), float(hi), float(data_range), C.c_void_p(part.data_ptr()),
-                                ssim.ctypes.data_as(pd), ssd.ctypes.data_as(pd), C.c_void_p(stream)))
+    check(lib.dsx_image_metrics(a, b, B, Cn, H, W, int(quantize), float(lo), float(hi), float(data_range), part,
+                                ssim.ctypes.data_as(pd), ssd.ctypes.data_as(pd), stream))
     return ssim, ssd
 
 
@@ -154,8 +151,6 @@ def image_metrics(pred, target, min_max=(-1, 1), quantize=True, data_range=255.0
     if pred.shape != target.shape or pred.dim() != 4:
         raise ValueError(f"pred and target must be (B, C, H, W) of one shape, got {tuple(pred.shape)} and "
                          f"{tuple(target.shape)}")
-    if not (pred.is_cuda and target.is_cuda):
-        raise DsxError("image_metrics runs on the device: pass CUDA tensors")
     a = pred.to(torch.float32).contiguous()
     b = target.to(torch.float32).contiguous()
     ssim, ssd = _run(a, b, quantize, min_max[0], min_max[1], data_range, stream)

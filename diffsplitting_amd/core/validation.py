@@ -116,13 +116,9 @@ def validation_report(input, target, prediction, normalization_dict, visuals=Tru
     nblk = (H * W + VAL_CHUNK - 1) // VAL_CHUNK
     part = torch.empty(B * (Cn + Cin) * nblk * 4, dtype=torch.int64, device=dev)
     stats = torch.empty(1 + B * (3 * Cn + 2 * Cin), dtype=torch.int64, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
     pd = C.POINTER(C.c_double)
-    with torch.cuda.device(dev):
-        check(lib.dsx_val_report(ptr(input), ptr(target), ptr(prediction), B, Cin, Cn, H, W, mean_in, std_in,
-                                 mean_t.ctypes.data_as(pd), std_t.ctypes.data_as(pd), ptr(iq), ptr(tq), ptr(pq), ptr(inum),
-                                 ptr(tnum), ptr(pnum), ptr(part), ptr(stats),
-                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    check(lib.dsx_val_report(input, target, prediction, B, Cin, Cn, H, W, mean_in, std_in, mean_t.ctypes.data_as(pd),
+                             std_t.ctypes.data_as(pd), iq, tq, pq, inum, tnum, pnum, part, stats, None))
     st = stats.cpu().numpy()
     tst = st[1:1 + 3 * B * Cn].reshape(B, Cn, 3)
     ist = st[1 + 3 * B * Cn:].reshape(B, Cin, 2)

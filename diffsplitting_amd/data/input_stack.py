@@ -7,8 +7,6 @@ The normalisation comes from elsewhere (``data/normalization.py``: the training 
 stacks are uploaded and STAY resident in their file width -- no fp32 copy of the stack exists -- and a batch of normalised
 tiles is one launch of dsx_tileplan_gather_input, which widens, clips and normalises while it cuts.  On a stack that
 holds w0 * ch0 + w1 * ch1 of a two-channel set the tiles are that set's 'input' bit for bit."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -91,11 +89,9 @@ class InputStackTiledPred:
         first, stride, count = seq
         for k0 in range(0, count, ITEMS_PER_CALL):
             n = min(ITEMS_PER_CALL, count - k0)
-            check(lib.dsx_tileplan_gather_input(self.plan.handle, C.c_void_p(self._dev.data_ptr()), self._pix,
-                                                first + k0 * stride, stride, n, self._mean_inp, self._std_inp,
-                                                -1.0 if self._input_clip is None else self._input_clip,
-                                                C.c_void_p(out[k0:].data_ptr()),
-                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            check(lib.dsx_tileplan_gather_input(self.plan.handle, self._dev, self._pix, first + k0 * stride, stride, n,
+                                                self._mean_inp, self._std_inp,
+                                                -1.0 if self._input_clip is None else self._input_clip, out[k0:], None))
 
     def tiles(self, indices):
         """Tile ids -> ``{'input': (b,1,p,p)}`` on the device.  A rank's shard or a batch of it is an arithmetic id
@@ -107,13 +103,11 @@ class InputStackTiledPred:
         p = self._patch_size
         out = torch.empty((ids.size, 1, p, p), dtype=torch.float32, device=self._dev.device)
         seq = as_sequence(ids)
-        with torch.cuda.device(self._dev.device):
-            if seq is not None:
-                if seq[2]:
-                    self._gather_seq(seq, out)
-            else:
-                for k, i in enumerate(ids):
-                    self._gather_seq((int(i), 1, 1), out[k:])
+        if seq is not None:
+            self._gather_seq(seq, out)
+        else:
+            for k, i in enumerate(ids):
+                self._gather_seq((int(i), 1, 1), out[k:])
         return {"input": out}
 
     def __getitem__(self, index):

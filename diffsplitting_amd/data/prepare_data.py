@@ -84,13 +84,11 @@ def _resize_batch(t, size, resample):
     _lib.require_gpu()
     plan = _plan(H, W, size, resample, Cn)
     out = torch.empty((B, size, size, Cn), dtype=torch.uint8, device=t.device)
-    stream = torch.cuda.current_stream(t.device).cuda_stream
     for b0 in range(0, B, _MAX_BATCH):
         n = min(_MAX_BATCH, B - b0)
         ws_bytes = lib.dsx_resize_workspace_bytes(plan.handle, n)
         ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=t.device)
-        check(lib.dsx_resize_u8(plan.handle, C.c_void_p(t[b0:b0 + n].data_ptr()), n, C.c_void_p(out[b0:b0 + n].data_ptr()),
-                                C.c_void_p(ws.data_ptr()), C.c_void_p(stream)))
+        check(lib.dsx_resize_u8(plan.handle, t[b0:b0 + n], n, out[b0:b0 + n], ws, None))
     return out
 
 

@@ -106,11 +106,9 @@ def frames_to_device(frames, dev, clip=None):
     _lib.require_gpu()
     src = torch.as_tensor(np.ascontiguousarray(frames).view(np.uint8)).to(dev)      # raw bytes: torch has no uint16 math
     dst = torch.empty(frames.shape, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dst.device):
-        check(lib.dsx_frames_to_f32(C.c_void_p(src.data_ptr()), _lib.PIX_U16 if frames.dtype == np.uint16 else _lib.PIX_U8,
-                                    frames.size, -1.0 if clip is None else float(clip), C.c_void_p(dst.data_ptr()),
-                                    TilePlan._stream()))
-        torch.cuda.current_stream().synchronize()                   # `src` is released on return
+    check(lib.dsx_frames_to_f32(src, _lib.PIX_U16 if frames.dtype == np.uint16 else _lib.PIX_U8, frames.size,
+                                -1.0 if clip is None else float(clip), dst, None))
+    torch.cuda.current_stream(dst.device).synchronize()             # `src` is released on return
     return dst
 
 
@@ -136,12 +134,9 @@ def order_stats_device(a, b, w0, w1, ranks):
     b = None if b is None else b.reshape(-1).contiguous()
     ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
     out = np.empty(ranks.size, dtype=np.float64)
-    with torch.cuda.device(a.device):
-        ws = torch.empty(int(lib.dsx_order_stats_workspace_bytes(a.numel(), ranks.size)), dtype=torch.uint8, device=a.device)
-        check(lib.dsx_order_stats(C.c_void_p(a.data_ptr()), None if b is None else C.c_void_p(b.data_ptr()), a.numel(),
-                                  float(w0), float(w1), ranks.ctypes.data_as(C.POINTER(C.c_int64)), ranks.size,
-                                  out.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(ws.data_ptr()),
-                                  TilePlan._stream()))
+    ws = torch.empty(int(lib.dsx_order_stats_workspace_bytes(a.numel(), ranks.size)), dtype=torch.uint8, device=a.device)
+    check(lib.dsx_order_stats(a, b, a.numel(), float(w0), float(w1), ranks.ctypes.data_as(C.POINTER(C.c_int64)),
+                              ranks.size, out.ctypes.data_as(C.POINTER(C.c_double)), ws, None))
     return out
 
 
@@ -320,12 +315,10 @@ class SplitDataset:
         tin = torch.empty((b, 1, p, p), dtype=torch.float32, device=dev)
         ttar = torch.empty((b, 2, p, p), dtype=torch.float32, device=dev)
         shape3 = (self._data_shape[0],) + self._data_shape[-2:]      # (N,1,H,W) frames are (N,H,W) frames
-        check(lib.dsx_tiles_gather_norm(C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()),
-                                        _i64x3(shape3), _i64x3((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
-                                        None, b, float(self._channel_weights[0]), float(self._channel_weights[1]),
-                                        self._norm6(), 1 if self._input_from_normalized_target else 0,
-                                        C.c_void_p(tin.data_ptr()), C.c_void_p(ttar.data_ptr()),
-                                        TilePlan._stream()))
+        check(lib.dsx_tiles_gather_norm(self._dev[0], self._dev[1], _i64x3(shape3), _i64x3((1, p, p)),
+                                        loc.ctypes.data_as(C.POINTER(C.c_int64)), None, b,
+                                        float(self._channel_weights[0]), float(self._channel_weights[1]), self._norm6(),
+                                        1 if self._input_from_normalized_target else 0, tin, ttar, None))
         if self._target_channel_idx is not None:
             ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
         return {"input": tin, "target": ttar}
@@ -343,15 +336,12 @@ class SplitDataset:
         mt = np.ascontiguousarray(self._mean_target.reshape(-1), dtype=np.float64)
         st = np.ascontiguousarray(self._std_target.reshape(-1), dtype=np.float64)
         shape, patch = (C.c_int64 * 4)(*[int(x) for x in self._data_shape]), (C.c_int64 * 2)(p, p)
-        with torch.cuda.device(dev):
-            for i0 in range(0, b, self.PLANE_ITEMS_PER_CALL):
-                part = np.ascontiguousarray(loc[i0:i0 + self.PLANE_ITEMS_PER_CALL])
-                check(lib.dsx_tiles_gather_norm_planes(
-                    C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()), shape, patch,
-                    part.ctypes.data_as(C.POINTER(C.c_int64)), None, part.shape[0], float(self._channel_weights[0]),
-                    float(self._channel_weights[1]), float(self._mean_inp), float(self._std_inp), mt.ctypes.data_as(pd),
-                    st.ctypes.data_as(pd), C.c_void_p(tin[i0:].data_ptr()), C.c_void_p(ttar[i0:].data_ptr()),
-                    TilePlan._stream()))
+        for i0 in range(0, b, self.PLANE_ITEMS_PER_CALL):
+            part = np.ascontiguousarray(loc[i0:i0 + self.PLANE_ITEMS_PER_CALL])
+            check(lib.dsx_tiles_gather_norm_planes(
+                self._dev[0], self._dev[1], shape, patch, part.ctypes.data_as(C.POINTER(C.c_int64)), None, part.shape[0],
+                float(self._channel_weights[0]), float(self._channel_weights[1]), float(self._mean_inp),
+                float(self._std_inp), mt.ctypes.data_as(pd), st.ctypes.data_as(pd), tin[i0:], ttar[i0:], None))
         if self._target_channel_idx is not None:
             ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
         return {"input": tin, "target": ttar}
@@ -386,8 +376,7 @@ class SplitDataset:
         out = {k: torch.empty((count, 2, p, p), dtype=torch.float32, device=dev) for k in ("target", "mix", "cls") if k in want}
         if not out:
             raise DsxError("mixed_tiles: nothing asked for (want = target, mix, cls)")
-        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out else None
-        return out, ptr, (C.c_double * 4)(*[float(v) for v in lohi]) if "cls" in out else None
+        return out, (C.c_double * 4)(*[float(v) for v in lohi]) if "cls" in out else None
 
     def mixed_tiles_at(self, locations, mixing_t, lohi=None, want=None):
         """``locations``: (b, 3) (frame, y, x) corners -> {'target', 'mix', 'cls'} (b, 2, p, p) CUDA tensors in one HIP
@@ -397,11 +386,10 @@ class SplitDataset:
         _lib.require_gpu()
         loc = np.ascontiguousarray(np.asarray(locations, dtype=np.int64).reshape(-1, 3))
         b, p = loc.shape[0], self._patch_size
-        out, ptr, lh = self._mixed_new(b, lohi, want)
-        check(lib.dsx_tiles_gather_mix(C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()),
-                                       _i64x3(self._data_shape), _i64x3((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)),
-                                       None, b, self._norm4(), float(mixing_t), lh, ptr("target"), ptr("mix"), ptr("cls"),
-                                       TilePlan._stream()))
+        out, lh = self._mixed_new(b, lohi, want)
+        check(lib.dsx_tiles_gather_mix(self._dev[0], self._dev[1], _i64x3(self._data_shape), _i64x3((1, p, p)),
+                                       loc.ctypes.data_as(C.POINTER(C.c_int64)), None, b, self._norm4(), float(mixing_t), lh,
+                                       out.get("target"), out.get("mix"), out.get("cls"), None))
         return out
 
     def mixed_tiles(self, indices, mixing_t, table=None, want=None):
@@ -451,12 +439,10 @@ class SplitDatasetTiledPred(SplitDataset):
         tin = torch.empty((count, 1, ph, pw), dtype=torch.float32, device=dev)
         ttar = torch.empty((count, 2, ph, pw), dtype=torch.float32, device=dev)
         if count:
-            check(lib.dsx_tileplan_gather_norm(plan.handle, C.c_void_p(self._dev[0].data_ptr()),
-                                               C.c_void_p(self._dev[1].data_ptr()), first, stride, count,
+            check(lib.dsx_tileplan_gather_norm(plan.handle, self._dev[0], self._dev[1], first, stride, count,
                                                float(self._channel_weights[0]), float(self._channel_weights[1]),
                                                self._norm6(), 1 if self._input_from_normalized_target else 0,
-                                               C.c_void_p(tin.data_ptr()), C.c_void_p(ttar.data_ptr()),
-                                               TilePlan._stream()))
+                                               tin, ttar, None))
         if self._target_channel_idx is not None:
             ttar = ttar[:, self._target_channel_idx:self._target_channel_idx + 1].contiguous()
         return {"input": tin, "target": ttar}
@@ -479,12 +465,11 @@ class SplitDatasetTiledPred(SplitDataset):
             return super().mixed_tiles(indices, mixing_t, table, want)
         _lib.require_gpu()
         first, stride, count = seq
-        out, ptr, lh = self._mixed_new(count, table_rows(table, mixing_t), want)
+        out, lh = self._mixed_new(count, table_rows(table, mixing_t), want)
         if count:
-            check(lib.dsx_tileplan_gather_mix(self.plan.handle, C.c_void_p(self._dev[0].data_ptr()),
-                                              C.c_void_p(self._dev[1].data_ptr()), first, stride, count, self._norm4(),
-                                              float(mixing_t), lh, ptr("target"), ptr("mix"), ptr("cls"),
-                                              TilePlan._stream()))
+            check(lib.dsx_tileplan_gather_mix(self.plan.handle, self._dev[0], self._dev[1], first, stride, count,
+                                              self._norm4(), float(mixing_t), lh, out.get("target"), out.get("mix"),
+                                              out.get("cls"), None))
         return out
 
     def normalized_target_frames(self):

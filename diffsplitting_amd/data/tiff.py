@@ -24,7 +24,7 @@ def imread(path):
         check(lib.dsx_tiff_info(h, shape, C.byref(code)))
         n, H, W, S = (int(v) for v in shape)
         out = np.empty((n, H, W) if S == 1 else (n, H, W, S), dtype=_DTYPES[code.value])
-        check(lib.dsx_tiff_read(h, 0, n, out.ctypes.data_as(C.c_void_p), out.nbytes))
+        check(lib.dsx_tiff_read(h, 0, n, out, out.nbytes))
         return out
     finally:
         lib.dsx_tiff_close(h)
@@ -40,5 +40,5 @@ def imwrite(path, array, description=None, bigtiff=None):
         raise DsxError(f"imwrite: (N, H, W) uint8 / uint16 / float32 expected, got {a.shape} {a.dtype}")
     a = np.ascontiguousarray(a)
     desc = None if description is None else str(description).encode()
-    check(lib.dsx_tiff_write(str(path).encode(), a.ctypes.data_as(C.c_void_p), a.shape[0], a.shape[1], a.shape[2],
+    check(lib.dsx_tiff_write(str(path).encode(), a, a.shape[0], a.shape[1], a.shape[2],
                              _CODES[a.dtype], desc, -1 if bigtiff is None else int(bool(bigtiff))))

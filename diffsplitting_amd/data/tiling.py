@@ -87,10 +87,6 @@ class TilePlan:
             except Exception:
                 pass
 
-    @staticmethod
-    def _stream():
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def _ids(self, tile_ids):
         ids = np.arange(self.total, dtype=np.int64) if tile_ids is None else \
             np.ascontiguousarray(np.asarray(tile_ids, dtype=np.int64).reshape(-1))
@@ -109,14 +105,11 @@ class TilePlan:
                           device=frames.device)
         seq = as_sequence(ids)
         if len(ids) and seq is not None:
-            check(lib.dsx_tileplan_gather(self.handle, C.c_void_p(frames.data_ptr()), seq[0], seq[1], seq[2],
-                                          C.c_void_p(out.data_ptr()), self._stream()))
+            check(lib.dsx_tileplan_gather(self.handle, frames, seq[0], seq[1], seq[2], out, None))
         elif len(ids):
-            check(lib.dsx_tiles_gather(C.c_void_p(frames.data_ptr()), _i64x3(self.data_shape),
-                                       _i64x3(self.patch_shape),
+            check(lib.dsx_tiles_gather(frames, _i64x3(self.data_shape), _i64x3(self.patch_shape),
                                        self.patch_start.ctypes.data_as(C.POINTER(C.c_int64)),
-                                       ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids),
-                                       C.c_void_p(out.data_ptr()), self._stream()))
+                                       ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids), out, None))
         return out
 
     def _check_tiles(self, tiles):
@@ -139,13 +132,11 @@ class TilePlan:
             canvas = torch.zeros(self.data_shape + (Cn,), dtype=torch.float32, device=tiles.device)
         seq = as_sequence(ids)
         if len(ids) and seq is not None:
-            check(lib.dsx_tileplan_stitch(self.handle, C.c_void_p(tiles.data_ptr()), Cn, seq[0], seq[1], seq[2],
-                                          C.c_void_p(canvas.data_ptr()), None, None, self._stream()))
+            check(lib.dsx_tileplan_stitch(self.handle, tiles, Cn, seq[0], seq[1], seq[2], canvas, None, None, None))
         elif len(ids):
             reg = np.ascontiguousarray(self.regions[ids])
-            check(lib.dsx_stitch(C.c_void_p(tiles.data_ptr()), len(ids), Cn, self.patch_shape[1],
-                                 self.patch_shape[2], reg.ctypes.data_as(C.POINTER(C.c_int32)),
-                                 C.c_void_p(canvas.data_ptr()), _i64x3(self.data_shape), self._stream()))
+            check(lib.dsx_stitch(tiles, len(ids), Cn, self.patch_shape[1], self.patch_shape[2],
+                                 reg.ctypes.data_as(C.POINTER(C.c_int32)), canvas, _i64x3(self.data_shape), None))
         return canvas
 
     # ---- RangeInvariantPsnr sums accumulated while pasting ---------------------------------------------------
@@ -177,9 +168,7 @@ class TilePlan:
         Cn = tiles.shape[1]
         gt = self._check_gt(gt, Cn)
         rows = torch.empty((seq[2],) + tuple(partials.shape[1:]), dtype=torch.float64, device=tiles.device)
-        check(lib.dsx_tileplan_stitch(self.handle, C.c_void_p(tiles.data_ptr()), Cn, seq[0], seq[1], seq[2],
-                                      C.c_void_p(canvas.data_ptr()), C.c_void_p(gt.data_ptr()),
-                                      C.c_void_p(rows.data_ptr()), self._stream()))
+        check(lib.dsx_tileplan_stitch(self.handle, tiles, Cn, seq[0], seq[1], seq[2], canvas, gt, rows, None))
         partials[seq[0]:seq[0] + (seq[2] - 1) * seq[1] + 1:seq[1]] = rows
 
     def psnr_from_partials(self, partials):
@@ -232,8 +221,7 @@ class TilePlan:
         if flat_rank.dtype != torch.float32 or not flat_rank.is_cuda or not flat_rank.is_contiguous() or \
                 flat_rank.numel() < int(self.pack_layout(world)[1][int(first) % int(world)]) * Cn:
             raise DsxError("flat_rank must be a contiguous float32 CUDA tensor that holds this rank's run")
-        check(lib.dsx_tileplan_pack(self.handle, C.c_void_p(tiles.data_ptr()), Cn, int(world), int(first),
-                                    int(tiles.shape[0]), C.c_void_p(flat_rank.data_ptr()), self._stream()))
+        check(lib.dsx_tileplan_pack(self.handle, tiles, Cn, int(world), int(first), int(tiles.shape[0]), flat_rank, None))
 
     def paste_packed(self, flat_all, Cn, world, gt=None):
         """Every tile of the plan from the gathered exchange buffer (world, rank_stride) -> canvas (N,H,W,C); with
@@ -248,10 +236,7 @@ class TilePlan:
         if gt is not None:
             gt = self._check_gt(gt, Cn)
             part = self.new_psnr_partials(Cn, flat_all.device)
-        check(lib.dsx_tileplan_paste_packed(self.handle, C.c_void_p(flat_all.data_ptr()), int(Cn), int(world), stride,
-                                            C.c_void_p(canvas.data_ptr()),
-                                            C.c_void_p(gt.data_ptr()) if gt is not None else None,
-                                            C.c_void_p(part.data_ptr()) if part is not None else None, self._stream()))
+        check(lib.dsx_tileplan_paste_packed(self.handle, flat_all, int(Cn), int(world), stride, canvas, gt, part, None))
         return canvas if gt is None else (canvas, self.psnr_from_partials(part))
 
 

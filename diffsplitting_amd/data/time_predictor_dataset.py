@@ -50,10 +50,7 @@ def compute_input_normalization_dict(data_dict, n_timesteps, mean_target, std_ta
     part = torch.empty((rows, n + 1, 2), dtype=torch.float64, device=dev)
     out = np.empty((n + 1, 2), dtype=np.float64)
     norm = (C.c_double * 4)(mean[0], std[0], mean[1], std[1])
-    with torch.cuda.device(dev):
-        check(lib.dsx_mix_range(C.c_void_p(f0.data_ptr()), C.c_void_p(f1.data_ptr()), pixels, norm, n,
-                                C.c_void_p(part.data_ptr()), out.ctypes.data_as(C.POINTER(C.c_double)),
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    check(lib.dsx_mix_range(f0, f1, pixels, norm, n, part, out.ctypes.data_as(C.POINTER(C.c_double)), None))
     return {t_int: [out[t_int, 0], out[t_int, 1]] for t_int in range(n + 1)}
 
 
@@ -126,10 +123,8 @@ class TimePredictorDataset(SplitDataset):
             lohi = np.array([self.input_normalization_dict[r] * 2 for r in rows], dtype=np.float64).reshape(b, 4)
             i64 = lambda v: (C.c_int64 * 3)(*[int(x) for x in v])
             pd = C.POINTER(C.c_double)
-            with torch.cuda.device(dev):
-                check(lib.dsx_tiles_gather_mix_items(
-                    C.c_void_p(self._dev[0].data_ptr()), C.c_void_p(self._dev[1].data_ptr()), i64(self._data_shape),
-                    i64((1, p, p)), loc.ctypes.data_as(C.POINTER(C.c_int64)), b, self._norm4(), t.ctypes.data_as(pd),
-                    lohi.ctypes.data_as(pd), None, None, C.c_void_p(cls.data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            check(lib.dsx_tiles_gather_mix_items(
+                self._dev[0], self._dev[1], i64(self._data_shape), i64((1, p, p)),
+                loc.ctypes.data_as(C.POINTER(C.c_int64)), b, self._norm4(), t.ctypes.data_as(pd), lohi.ctypes.data_as(pd),
+                None, None, cls, None))
         return cls[:, 1:2].contiguous(), t

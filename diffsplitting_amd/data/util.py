@@ -6,7 +6,6 @@ device.
 computes on the CPU.  The ``split='train'`` branch (a random horizontal flip) is training-time augmentation and raises
 ``DsxError``: the engine is inference-only.
 """
-import ctypes as C
 import os
 
 import numpy as np
@@ -64,9 +63,7 @@ def u8_to_tensor(u8, min_max=(0, 1)):
         raise DsxError(f"u8_to_tensor takes (B, H, W, 1 or 3) uint8, got {tuple(u8.shape)}")
     B, H, W, Cn = t.shape
     out = torch.empty((B, Cn, H, W), dtype=torch.float32, device=t.device)
-    stream = torch.cuda.current_stream(t.device).cuda_stream
-    check(lib.dsx_u8_to_tensor(C.c_void_p(t.data_ptr()), B, H, W, Cn, float(min_max[0]), float(min_max[1]),
-                               C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
+    check(lib.dsx_u8_to_tensor(t, B, H, W, Cn, float(min_max[0]), float(min_max[1]), out, None))
     return out[0] if single else out
 
 

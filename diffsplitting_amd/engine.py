@@ -68,14 +68,6 @@ def plan_dry_run(cfg, dtype, B, H, W, cond_channels=0):
     return int(a.value), int(b.value), int(n.value)
 
 
-def _dptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class UNetEngine:
     """One UNet on the current GPU: parameter table + executors per (B,H,W,cond)."""
 
@@ -122,14 +114,14 @@ class UNetEngine:
                                    f"((1 + gamma) x + beta, sr3 unet.py:34-50); the engine implements the additive form "
                                    f"every reference config uses (use_affine_level=False), expected {shp}")
                 raise DsxError(f"{key}: shape {tuple(t.shape)} != {shp}")
-            check(lib.dsx_model_set_param(self._h, i, C.c_void_p(t.data_ptr()), t.numel()))
+            check(lib.dsx_model_set_param(self._h, i, t, t.numel()))
         if self.flavour == "sr3" and self.cfg.with_time_emb:
             # PositionalEncoding's table, computed with the same torch ops as the
             # reference (sr3 unet.py:24-28) so the host constant is bit-identical
             count = self.cfg.inner_channel // 2
             step = torch.arange(count, dtype=torch.float32) / count
             freq = torch.exp(-math.log(1e4) * step).contiguous()
-            check(lib.dsx_model_set_posenc_freq(self._h, C.c_void_p(freq.data_ptr()), count))
+            check(lib.dsx_model_set_posenc_freq(self._h, freq, count))
         self._drop_execs()
         self._finalized_dtype = None
 
@@ -162,7 +154,7 @@ class UNetEngine:
         n = C.c_size_t()
         check(lib.dsx_model_packed_bytes(self._h, self._finalized_dtype, C.byref(n)))
         buf = np.empty(n.value, dtype=np.uint8)
-        check(lib.dsx_model_export_packed(self._h, buf.ctypes.data_as(C.c_void_p), n.value))
+        check(lib.dsx_model_export_packed(self._h, buf, n.value))
         import hashlib
         tmp = f"{path}.tmp{os.getpid()}"
         with open(tmp, "wb") as f:
@@ -192,7 +184,7 @@ class UNetEngine:
         if buf.size != n.value or hashlib.sha256(buf.data).digest() != digest:
             return False
         self._drop_execs()
-        check(lib.dsx_model_finalize_packed(self._h, code, buf.ctypes.data_as(C.c_void_p), n.value))
+        check(lib.dsx_model_finalize_packed(self._h, code, buf, n.value))
         self._finalized_dtype = code
         return True
 
@@ -248,7 +240,6 @@ class UNetEngine:
         (B, Ho, Wo, Cout); attention: `q`, `k`, `v`, `out` (B, L, C).  Absent entries are None."""
         ex = self.executor(B, H, W, cond_channels)
         descs = self.op_descriptions(B, H, W, cond_channels)
-        st = _stream_ptr()
         dts = {_lib.DTYPE_F32: torch.float32, _lib.DTYPE_BF16: torch.bfloat16, _lib.DTYPE_F16: torch.float16}
         info = _lib.LayerInfo()
 
@@ -261,8 +252,7 @@ class UNetEngine:
             for s in shape[:-1]:
                 n *= s
             t = torch.empty(n * ld, dtype=dtype, device="cuda")
-            check(lib.dsx_exec_copy_workspace(ex, addr, (n * ld - ld + shape[-1]) * t.element_size(),
-                                              C.c_void_p(t.data_ptr()), st))
+            check(lib.dsx_exec_copy_workspace(ex, addr, (n * ld - ld + shape[-1]) * t.element_size(), t, None))
             return t.view(n, ld)[:, :shape[-1]].reshape(shape)
 
         out = []
@@ -300,19 +290,16 @@ class UNetEngine:
 
     def forward(self, x, time=None, cond_channels=0):
         """denoise_fn(x, t): x (B,Cin,H,W) fp32 cuda NCHW -> (B,Cout,H,W)."""
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise DsxError("x must be a float32 CUDA tensor")
         x = x.contiguous()
         B, _, H, W = x.shape
         ex = self.executor(B, H, W, cond_channels)
         y = torch.empty((B, self.cfg.out_channel, H, W), dtype=torch.float32, device=x.device)
+        t = None                                                     # with_time_emb == 0: no time input
         if self.cfg.with_time_emb:
             t = time.to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
             if t.numel() not in (1, B):
                 raise DsxError(f"time must have 1 or B={B} elements, got {t.numel()}")
-            check(lib.dsx_unet_forward(ex, _dptr(x), _dptr(t), t.numel(), _dptr(y), _stream_ptr()))
-        else:
-            check(lib.dsx_unet_forward(ex, _dptr(x), C.c_void_p(0), 0, _dptr(y), _stream_ptr()))
+        check(lib.dsx_unet_forward(ex, x, t, 0 if t is None else t.numel(), y, None))
         return y
 
     def sample_loop(self, table, x_init, cond=None, noise=None, seed=0, snapshot_steps=(),
@@ -350,10 +337,9 @@ class UNetEngine:
             for t in (x, cond, noise, snaps):
                 if t is not None:
                     t.record_stream(stream)
-        sp = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_ptr()
-        args = (ex, C.byref(table.c_struct()), _dptr(cond), _dptr(x), _dptr(noise), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                steps.ctypes.data_as(C.POINTER(C.c_int32)) if len(steps) else None, len(steps), _dptr(snaps),
-                1 if use_graph else 0, sp)
+        args = (ex, C.byref(table.c_struct()), cond, x, noise, _seed64(seed),
+                steps.ctypes.data_as(C.POINTER(C.c_int32)) if len(steps) else None, len(steps), snaps,
+                1 if use_graph else 0, stream)
         if ids is None:
             check(lib.dsx_sample_loop(*args))
         else:
@@ -535,8 +521,7 @@ def randn(shape, seed, subsequence=0, device="cuda"):
     """N(0,1) from the engine's Philox stream (perf-mode initial states)."""
     _lib.require_gpu()
     out = torch.empty(shape, dtype=torch.float32, device=device)
-    check(lib.dsx_randn(_dptr(out), out.numel(), C.c_uint64(int(seed)), C.c_uint64(int(subsequence)),
-                        _stream_ptr()))
+    check(lib.dsx_randn(out, out.numel(), C.c_uint64(int(seed)), C.c_uint64(int(subsequence)), None))
     return out
 
 
@@ -570,8 +555,8 @@ def randn_samples(shape, seed, sample_ids, draw=0, device="cuda"):
         raise DsxError(f"randn_samples takes a (B, ...) shape of at least two non-empty dimensions, got {shape}")
     ids = _sample_ids(sample_ids, shape[0])
     out = torch.empty(shape, dtype=torch.float32, device=device)
-    check(lib.dsx_randn_samples(_dptr(out), shape[0], out.numel() // shape[0], _seed64(seed),
-                                ids.ctypes.data_as(_lib._pu64), C.c_uint32(_draw_ordinal(draw)), _stream_ptr()))
+    check(lib.dsx_randn_samples(out, shape[0], out.numel() // shape[0], _seed64(seed),
+                                ids.ctypes.data_as(_lib._pu64), C.c_uint32(_draw_ordinal(draw)), None))
     return out
 
 
@@ -635,9 +620,8 @@ def q_sample(x0, c0, c2, xe=None, c1=None, z=None, seed=0, subsequence=0, dst=No
     elif not (dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous() and dst.dim() == 4
               and dst.shape[0] == B and tuple(dst.shape[2:]) == (H, W)):
         raise DsxError(f"dst must be a contiguous float32 CUDA tensor ({B}, Cdst, {H}, {W})")
-    check(lib.dsx_q_sample(_dptr(x0), _dptr(xe), B, Cn, Ce, H, W, _dptr(c0), _dptr(c1), _dptr(c2), _dptr(z),
-                           _seed64(seed), C.c_uint64(int(subsequence)), _dptr(z_out), _dptr(dst), dst.shape[1],
-                           int(coff), _stream_ptr()))
+    check(lib.dsx_q_sample(x0, xe, B, Cn, Ce, H, W, c0, c1, c2, z, _seed64(seed), C.c_uint64(int(subsequence)), z_out,
+                           dst, dst.shape[1], int(coff), None))
     return dst, (z if z is not None else z_out)
 
 
@@ -652,7 +636,7 @@ def loss_per_sample(a, b, squared):
     blocks = check(lib.dsx_loss_blocks(Cn, H, W))
     part = torch.empty(B * blocks, dtype=torch.float64, device=a.device)
     out = torch.empty(B, dtype=torch.float64, device=a.device)
-    check(lib.dsx_loss(_dptr(a), _dptr(b), B, Cn, H, W, 1 if squared else 0, _dptr(part), _dptr(out), _stream_ptr()))
+    check(lib.dsx_loss(a, b, B, Cn, H, W, 1 if squared else 0, part, out, None))
     return out
 
 
@@ -678,8 +662,8 @@ def attention(qkv, q_col, k_col, v_col, B, L, Cn, out, col_split=False):
     B, L, Cn = int(B), int(L), int(Cn)
     if B < 1 or L < 1 or qkv.shape[0] < B * L or out.shape[0] < B * L:
         raise DsxError(f"B * L = {B} * {L} token rows do not fit qkv ({qkv.shape[0]} rows) and out ({out.shape[0]})")
-    check(lib.dsx_attention(_dptr(qkv), qkv.shape[1], int(q_col), int(k_col), int(v_col), _dptr(out), out.shape[1],
-                            _STORAGE[qkv.dtype], B, L, Cn, 1 if col_split else 0, _stream_ptr()))
+    check(lib.dsx_attention(qkv, qkv.shape[1], int(q_col), int(k_col), int(v_col), out, out.shape[1],
+                            _STORAGE[qkv.dtype], B, L, Cn, 1 if col_split else 0, None))
     return out
 
 
@@ -714,17 +698,14 @@ def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, cli
         if draw is None:
             raise DsxError("sample_ids need the draw ordinal (draw = step + 1 inside a loop)")
         ids = _sample_ids(sample_ids, B)
-        check(lib.dsx_posterior_step_streams(_dptr(x), _dptr(net), B, Cn, H, W, _dptr(a), _dptr(b), _dptr(c1), _dptr(c2),
-                                             _dptr(sigma), 1 if predict_eps else 0, 1 if clip else 0, None, _seed64(seed),
-                                             C.c_uint64(_draw_ordinal(draw)), 0, _dptr(outs[0]), _dptr(outs[1]),
-                                             _dptr(outs[2]), _stream_ptr(), ids.ctypes.data_as(_lib._pu64), len(ids)))
+        check(lib.dsx_posterior_step_streams(x, net, B, Cn, H, W, a, b, c1, c2, sigma, 1 if predict_eps else 0,
+                                             1 if clip else 0, None, _seed64(seed), C.c_uint64(_draw_ordinal(draw)), 0,
+                                             *outs, None, ids.ctypes.data_as(_lib._pu64), len(ids)))
         return tuple(outs)
     if draw is not None:
         raise DsxError("draw names a draw of a sample stream: only with sample_ids")
-    check(lib.dsx_posterior_step(_dptr(x), _dptr(net), B, Cn, H, W, _dptr(a), _dptr(b), _dptr(c1), _dptr(c2),
-                                 _dptr(sigma), 1 if predict_eps else 0, 1 if clip else 0, _dptr(z), _seed64(seed),
-                                 C.c_uint64(int(subsequence)), 1 if repeat_noise else 0, _dptr(outs[0]),
-                                 _dptr(outs[1]), _dptr(outs[2]), _stream_ptr()))
+    check(lib.dsx_posterior_step(x, net, B, Cn, H, W, a, b, c1, c2, sigma, 1 if predict_eps else 0, 1 if clip else 0, z,
+                                 _seed64(seed), C.c_uint64(int(subsequence)), 1 if repeat_noise else 0, *outs, None))
     return tuple(outs)
 
 
@@ -741,9 +722,8 @@ def interp_start(x1, x2, a0, s0, lam, z1=None, z2=None, seed=0, subsequence=0, o
     if z1 is not None:
         z1, z2 = _f32_cuda(z1, "z1", x1.shape), _f32_cuda(z2, "z2", x1.shape)
     out = torch.empty_like(x1) if out is None else _f32_cuda(out, "out", x1.shape)
-    check(lib.dsx_interp_start(_dptr(x1), _dptr(x2), B, Cn, H, W, _dptr(a0), _dptr(s0), C.c_float(1 - float(lam)),
-                               C.c_float(float(lam)), _dptr(z1), _dptr(z2), _seed64(seed),
-                               C.c_uint64(int(subsequence)), _dptr(out), _stream_ptr()))
+    check(lib.dsx_interp_start(x1, x2, B, Cn, H, W, a0, s0, C.c_float(1 - float(lam)), C.c_float(float(lam)), z1, z2,
+                               _seed64(seed), C.c_uint64(int(subsequence)), out, None))
     return out
 
 
@@ -772,8 +752,7 @@ def moments_update(x, mean=None, m2=None, r=0):
         m2 = torch.empty(x.shape, dtype=torch.float64, device=x.device)
     _f64_cuda(mean, "mean", x.numel())
     _f64_cuda(m2, "m2", x.numel())
-    with torch.cuda.device(x.device):
-        check(lib.dsx_moments_update(_dptr(x), _dptr(mean), _dptr(m2), x.numel(), int(r), _stream_ptr()))
+    check(lib.dsx_moments_update(x, mean, m2, x.numel(), int(r), None))
     return mean, m2
 
 
@@ -788,7 +767,5 @@ def moments_finish(mean, m2, n, want_std=True):
         raise DsxError("moments_finish: mean is empty")
     mean_out = torch.empty(mean.shape, dtype=torch.float32, device=mean.device)
     std_out = torch.empty(mean.shape, dtype=torch.float32, device=mean.device) if want_std else None
-    with torch.cuda.device(mean.device):
-        check(lib.dsx_moments_finish(_dptr(mean), _dptr(m2), mean.numel(), int(n), _dptr(mean_out), _dptr(std_out),
-                                     _stream_ptr()))
+    check(lib.dsx_moments_finish(mean, m2, mean.numel(), int(n), mean_out, std_out, None))
     return mean_out, std_out

@@ -1,7 +1,5 @@
 """model/ddpm_modules/time_predictor.py of the reference on the HIP engine:
 t_hat = sum(relu(unet(x)) * sigmoid(conv7x7(x))) / sum(sigmoid(conv7x7(x))) per image."""
-import ctypes as C
-
 import torch
 from torch import nn
 
@@ -36,8 +34,7 @@ class TimePredictor(nn.Module):
         ex = eng.executor(B, H, W)
         w = self.foreground_mask.layer.weight.detach().to("cpu", torch.float32).contiguous()
         b = self.foreground_mask.layer.bias.detach().to("cpu", torch.float32).contiguous()
-        check(lib.dsx_time_predictor_set_mask(ex, C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr())))
+        check(lib.dsx_time_predictor_set_mask(ex, w, b))
         out = torch.empty(B, dtype=torch.float32, device=x.device)
-        check(lib.dsx_time_predictor_forward(ex, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        check(lib.dsx_time_predictor_forward(ex, x, out, None))
         return out
