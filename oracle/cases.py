@@ -28,6 +28,36 @@ UNET_CASES = {
                               channel_mults=(1, 2, 4, 8), attn_res=(), res_blocks=1, image_size=32)),
 }
 
+# Channel widths other than 16 2^k (tests/test_gpu_widths.py): inner_channel any multiple of 4, channel_mults 3 and 5.
+# No golden files: the weights are synthesised for the engine's own parameter names, the reference is the fp64 oracle.
+WIDTH_CASES = {
+    # 16-bit rows of 20 channels are 40 bytes: no source is a whole number of 16-byte units; 4 / 8 / 16 channels per group
+    "w20": dict(flavour="ddpm", B=3, H=32, W=48,
+                cfg=dict(in_channel=2, out_channel=2, inner_channel=20, norm_groups=5,
+                         channel_mults=(1, 2, 4), attn_res=(), res_blocks=1, image_size=32)),
+    # w20 with a middle level of 60 channels: the stride-2 and the upsampling conv of that level read 120-byte rows (at
+    # widths 20, 40 and 80 only the 20-channel tensors are no whole 16-byte units, and no upsampling conv reads one)
+    "w20x3": dict(flavour="ddpm", B=3, H=32, W=48,
+                  cfg=dict(in_channel=2, out_channel=2, inner_channel=20, norm_groups=5,
+                           channel_mults=(1, 3, 4), attn_res=(), res_blocks=1, image_size=32)),
+    # 3 / 6 / 9 channels per group; attention at head dimensions 48 (L = 256) and 72
+    "w24": dict(flavour="sr3", B=2, H=32, W=32,
+                cfg=dict(in_channel=6, out_channel=3, inner_channel=24, norm_groups=8,
+                         channel_mults=(1, 2, 3), attn_res=(16,), res_blocks=1, image_size=32)),
+    # widths 40, 120, 200: none a multiple of 16; concatenated inputs of up to 320 channels
+    "w40": dict(flavour="ddpm", B=2, H=32, W=32,
+                cfg=dict(in_channel=1, out_channel=1, inner_channel=40, norm_groups=10,
+                         channel_mults=(1, 3, 5), attn_res=(), res_blocks=2, image_size=32)),
+    # multiples of 16 that are no powers of two: the persistent kernel and split-K with odd counts; attention at 192
+    "w48": dict(flavour="sr3", B=2, H=64, W=64,
+                cfg=dict(in_channel=6, out_channel=3, inner_channel=48, norm_groups=16,
+                         channel_mults=(1, 2, 4), attn_res=(16,), res_blocks=1, image_size=64)),
+    # inner_channel > 64 in the time MLP; 96 output channels on the wide tile lists
+    "w96": dict(flavour="sr3", B=2, H=32, W=32,
+                cfg=dict(in_channel=6, out_channel=3, inner_channel=96, norm_groups=32,
+                         channel_mults=(1, 2), attn_res=(), res_blocks=1, image_size=32)),
+}
+
 # BASELINE C1: config/splitting_cifar10_indi.json:43-44,45-62,71 -- UNet 6 -> 6, inner 16, mults [1,2,4,8], GN16, rb 1,
 # no attn_res; InDI replicates the 1-channel x_in out_channel = 6 times (indi.py:80); batch 4 at 32^2, n = 20 (the file)
 # and n = 100 (BASELINE.json); both step counts trip the reference's drift assert: generated under -O

@@ -197,3 +197,43 @@ def test_gn_stats_checker_accepts_exact_and_rejects_a_missing_tile():
     layer.update(gn_scale=sc2, gn_shift=sh2)
     v1, v2, _ = layer_ref.check_gn_stats(layer, gamma, beta, groups, torch.float32)
     assert not (v1.ok and v2.ok)
+
+
+def test_reach_tags_of_the_widths_module():
+    """tests/test_gpu_widths.py derives its reach conditions from plain layer-table fields (layer_check.reach_tags):
+    hand-made entries, one per condition, and their nearest neighbours that must not count"""
+    from tests.layer_check import reach_tags
+
+    def conv(desc, ks=3, C0=32, C1=0, Cout=32, stride=1, up=0, resid=False, film=False, gn=False):
+        return dict(kind=0, desc=desc, ks=ks, stride=stride, up=up, C0=C0, C1=C1, Cout=Cout, resid=resid, film=film,
+                    gn_scale=gn, gn_in_kernel=0)
+    t64 = "conv3x3 1->1 @8x8 tile64x64"
+    # the scalar epilogue: Cout off 16, on an MFMA-family launch only
+    assert reach_tags(conv(t64, C0=24, Cout=24, resid=True, film=True), "f32", 8) == {"scalar+resid", "scalar+film",
+                                                                                       "scalar nbase>0"}
+    assert reach_tags(conv(t64, Cout=12, film=True), "f32", 8) == {"scalar+film"}
+    assert reach_tags(conv(t64, Cout=48, resid=True, film=True), "f32", 8) == set()
+    assert reach_tags(conv("conv3x3 6->24 @8x8 first", C0=6, Cout=24, film=True), "f32", 8) == set()
+    # stage mode 2: a source off the 16-byte unit (8 channels in 16 bits, 4 in fp32)
+    L = conv("conv1x1s2 1->1 @8x8 tile64x64", ks=1, C0=20, C1=40, Cout=32, stride=2, gn=True)
+    assert reach_tags(L, "bf16", 5) == {"stage2+gn", "stage2+cat", "stage2 1x1", "stage2 s2", "cpg5+"}
+    assert reach_tags(L, "f32", 5) == {"cpg5+"}
+    assert reach_tags(conv("conv3x3up 60->60 @8x8 tile64x64", C0=60, up=1), "f16", 5) == {"stage2 up"}
+    assert reach_tags(conv("conv3x3up 80->80 @8x8 tile64x64", C0=80, up=1), "f16", 5) == set()
+    # split counts, K tails of the persistent kernel, N tails of the wide tiles
+    assert reach_tags(conv(t64 + " splitK6"), "bf16", 8) == {"splitK odd"}
+    assert reach_tags(conv(t64 + " splitK4"), "bf16", 8) == set()
+    assert reach_tags(conv(t64 + " ws", C0=96), "bf16", 8) == set()          # 3 x 3: 32-channel groups
+    assert reach_tags(conv(t64 + " ws c2", C0=96), "bf16", 8) == {"ws ktail"}
+    assert reach_tags(conv("conv1x1 1->1 @8x8 tile64x64 ws +gn", ks=1, C0=96), "bf16", 8) == {"ws ktail"}
+    assert reach_tags(conv("conv1x1 1->1 @8x8 tile64x64 ws +gn", ks=1, C0=96), "f32", 8) == set()
+    assert reach_tags(conv("conv3x3 1->1 @8x8 tile64x128", Cout=96), "bf16", 8) == {"wide ntail"}
+    assert reach_tags(conv("conv3x3 1->1 @8x8 tile128x128", Cout=256), "bf16", 8) == set()
+    assert reach_tags(conv("conv3x3 1->1 @8x8 tile256x64", Cout=96), "bf16", 8) == set()
+    # channels per GroupNorm group, attention head dimensions
+    assert reach_tags(conv(t64, C0=48, gn=True), "f32", 16) == {"cpg3"}
+    assert reach_tags(conv(t64, C0=64, gn=True), "f32", 8) == set()                # 8 per group: a power of two
+    assert reach_tags(conv(t64, C0=48), "f32", 16) == set()                        # no GroupNorm in front
+    assert reach_tags(dict(kind=1, C0=72, desc="attn fused L=64 d=72"), "bf16", 8) == {"attn"}
+    assert reach_tags(dict(kind=1, C0=64, desc="attn fused L=64 d=64"), "bf16", 8) == set()
+    assert reach_tags(dict(kind=3, C0=0, desc=""), "bf16", 8) == set()

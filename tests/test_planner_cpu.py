@@ -173,6 +173,84 @@ def test_random_shapes_size_and_plan_alike(seed):
         assert res["ok"] >= 90, res
 
 
+_WIDTHS_CHILD = r"""
+import ctypes as C, json, random, sys
+sys.path.insert(0, %r)
+from diffsplitting_amd import _lib
+rng = random.Random(int(sys.argv[1]))
+bad, refusals = [], []
+n_ok = 0
+for case in range(int(sys.argv[2])):
+    levels = rng.choice([2, 3, 4])
+    mults = [1] + sorted(rng.choice([1, 2, 3, 4, 5, 6, 8]) for _ in range(levels - 1))
+    inner = 4 * rng.randint(2, 32)
+    groups = rng.choice([g for g in range(1, inner + 1) if inner %% g == 0])
+    flavour = rng.choice([0, 1])
+    cond = rng.choice([0, 1, 3]) if flavour == 0 else 0
+    cin = rng.choice([1, 2, 3]) + cond
+    unit = 1 << (levels - 1)
+    H, W = unit * 8 * rng.randint(1, 3), unit * 8 * rng.randint(1, 3)   # bottom maps of 8 / 16 / 24 per side
+    B = rng.choice([1, 2, 3, 5, 8])
+    attn = [rng.choice([H, H // 2 or 1, 16])] if rng.random() < 0.4 else []
+    cfg = _lib.UnetCfg()
+    cfg.flavour = flavour; cfg.in_channel = cin; cfg.out_channel = rng.choice([1, 2, 3]); cfg.inner_channel = inner
+    cfg.norm_groups = groups; cfg.res_blocks = rng.choice([1, 2]); cfg.image_size = H; cfg.with_time_emb = 1
+    cfg.n_mults = len(mults); cfg.n_attn_res = len(attn)
+    for i, m in enumerate(mults): cfg.channel_mults[i] = m
+    for i, m in enumerate(attn): cfg.attn_res[i] = m
+    for code in (0, 1, 2):
+        a, b, n = C.c_size_t(), C.c_size_t(), C.c_int()
+        rc = _lib.lib.dsx_plan_dry_run(C.byref(cfg), code, B, H, W, cond, C.byref(a), C.byref(b), C.byref(n))
+        if rc != 0:
+            refusals.append((case, code, inner, mults, B, H, W, _lib.lib.dsx_last_error().decode()))
+            continue
+        n_ok += 1
+        if a.value != b.value or a.value == 0: bad.append((case, code, inner, mults, B, H, W, a.value, b.value))
+print(json.dumps({"ok": n_ok, "bad": bad, "refusals": refusals}))
+"""
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_random_widths_size_and_plan_alike(seed):
+    """test_random_shapes_size_and_plan_alike over channel widths: inner_channel any multiple of 4 from 8 to 128,
+    norm_groups any divisor of it, channel_mults that are no powers of two (3, 5, 6).  Every channel count is then
+    some 4 m: K tails, N tails, sources that are no whole 16-byte units.  Sizing and planning walk the same bytes
+    wherever the planner accepts the shape; a refusal is one of the two the planner is meant to give (a head dimension
+    k_attn has no instantiation for, a map no MFMA tile covers), by its message."""
+    for env in ({}, {"DSX_WS_MIN_GRID": "1"}):
+        e = dict(os.environ)
+        e.update(env)
+        r = subprocess.run([sys.executable, "-c", _WIDTHS_CHILD % ROOT, str(seed), "60"], env=e, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        assert not res["bad"], res["bad"][:5]
+        for ref in res["refusals"]:
+            msg = ref[-1]
+            assert "fastdiv" not in msg and "planner" not in msg, ref
+            assert ("attention with head dimension" in msg and "is not supported" in msg) or "no MFMA tile fits" in msg, ref
+        assert res["ok"] + len(res["refusals"]) == 180
+        assert res["ok"] >= 120, (res["ok"], [r[-1] for r in res["refusals"]][:10])
+
+
+def test_refusals_by_message():
+    """The two refusals of the planner that a config at an unusual width or size can meet, by their text."""
+    from diffsplitting_amd import engine
+    from diffsplitting_amd._lib import DsxError
+    # 12 x 3 = 36 channels at the bottom: k_attn stages the head dimension in 16-byte units of bf16 (multiples of 8)
+    cfg = engine.make_cfg("ddpm", 2, 2, 12, 4, (1, 3), (), 1, 32)
+    for dt in ("f32", "bf16", "f16"):
+        with pytest.raises(DsxError, match=r"attention with head dimension 36 is not supported"):
+            engine.plan_dry_run(cfg, dt, 2, 32, 32, 0)
+    # ddpm_tiny (mults 1, 2, 4) at 20 x 36: the second level's maps are 10 x 18, which no 8 x 8 (or larger) tile divides
+    _, kw, *_ = CONFIGS["ragged_48x80_b3"]
+    cfg = engine.make_cfg("ddpm", kw["in_channel"], kw["out_channel"], kw["inner_channel"], kw["norm_groups"],
+                          kw["channel_mults"], kw["attn_res"], kw["res_blocks"], kw["image_size"])
+    for dt in ("f32", "bf16", "f16"):
+        with pytest.raises(DsxError, match=r"no MFMA tile fits conv 3x3 \(10x18 out"):
+            engine.plan_dry_run(cfg, dt, 5, 20, 36, 0)
+
+
 @pytest.mark.parametrize("name,dt", [("c2_sr3_128_b16", "f32"), ("c2_sr3_128_b16", "bf16"), ("c3_hagen_512_b8", "bf16"),
                                      ("ragged_48x80_b3", "bf16")])
 def test_plan_ops_match_recorded_plan(name, dt, tmp_path, monkeypatch):
