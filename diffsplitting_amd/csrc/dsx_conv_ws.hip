@@ -432,7 +432,9 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
     for (int dy = 0; dy < KS; ++dy)
       abase[mb][dy] = (tb * PH + ty * S + dy) * RB + tx * S * PIXB + ws16_slice(kq) * 16;
   }
-  // pixel m + 16 of a row block: 16 pixels to the right (tiles >= 32 wide), else 16 / TW rows down (host: TW >= 8, TB == 1)
+  // pixel m + 16 of a row block: 16 pixels to the right (tiles >= 32 wide), else 16 / TW rows down.  (host: TB == 1 and
+  // TW a power of two <= 16 -- 2 and 4 included, see tile_geometry -- so TW TH >= 64 and the 32 pixels of a row block
+  // are 32 / TW whole rows of one image.)
   const int a16 = TW >= 32 ? 16 * S * PIXB : (16 >> a.tw_log2) * S * RB;
   const int blk0 = (nt * WN + wn) * NB;         // host: Cout % (32 * WN * NB) == 0, so every block exists
   const int wblock = G * (NSTEP * 1024);        // bytes of one N block's fragment stream

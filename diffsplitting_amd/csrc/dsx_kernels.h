@@ -189,7 +189,7 @@ __device__ __forceinline__ void gn_finalize_item(const GnFinArgs& a, const int b
 //   connections are never materialised), optionally nearest-upsampled x2.
 //   Implicit GEMM on MFMA: M = output pixels, N = Cout, K = taps x Cin.
 // ---------------------------------------------------------------------------
-// (tests/test_conv_img_plan_cpu.py mirrors the members up to `stat_part` to read DSX_PLAN_DUMP lines: keep it in step
+// (tests/plan_dump.py mirrors the members up to `stat_part` to read DSX_PLAN_DUMP lines: keep it in step
 // when a member is added, removed or reordered above that one.)
 struct ConvArgs {
   const void* src0;       // NHWC activations in the storage type: fp32, or bf16 when act_bf16

@@ -58,6 +58,17 @@ WIDTH_CASES = {
                          channel_mults=(1, 2), attn_res=(), res_blocks=1, image_size=32)),
 }
 
+# Map shapes off the 8 x 8 tile grid (tests/test_gpu_shapes.py): three-level models the suite already has weights for
+# (golden state dicts of ddpm_tiny and sr3_tiny; w20 synthesised as in tests/test_gpu_widths.py: stage mode 2), at sizes
+# whose level maps are 2 or 4 pixels wide (64x24, 128x24), 12 or 6 wide (64x48, 48x32), and taller than wide or wider
+# than tall with a short side of 6 (64x24, 24x64).  The MFMA tiles they plan: 4x16x1, 2x32x1, 2x16x2, 8x4x2, 16x2x2
+# (TW x TH x images) on the 64-pixel tile and their counterparts on the 128-pixel one.  The weights do not depend on the
+# size, so neither does `cfg`.
+SHAPE_SIZES = ((64, 48), (64, 24), (128, 24), (48, 32), (24, 64))
+SHAPE_MODELS = {"ddpm_tiny": UNET_CASES["ddpm_tiny"], "sr3_tiny": UNET_CASES["sr3_tiny"], "w20": WIDTH_CASES["w20"]}
+SHAPE_CASES = {f"{_m}_{_h}x{_w}": dict(model=_m, flavour=_c["flavour"], B=3, H=_h, W=_w, cfg=_c["cfg"])
+               for _m, _c in SHAPE_MODELS.items() for _h, _w in SHAPE_SIZES}
+
 # BASELINE C1: config/splitting_cifar10_indi.json:43-44,45-62,71 -- UNet 6 -> 6, inner 16, mults [1,2,4,8], GN16, rb 1,
 # no attn_res; InDI replicates the 1-channel x_in out_channel = 6 times (indi.py:80); batch 4 at 32^2, n = 20 (the file)
 # and n = 100 (BASELINE.json); both step counts trip the reference's drift assert: generated under -O

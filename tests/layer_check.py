@@ -109,6 +109,38 @@ def reach_tags(L, dt, groups):
     return out
 
 
+def pow2_divisor(v, cap):
+    """largest power of two that divides v and is <= cap (dsx_plan.cpp)"""
+    p = 1
+    while p * 2 <= cap and v % (p * 2) == 0:
+        p *= 2
+    return p
+
+
+def geom_tag(L):
+    """The geometry class of a conv launch of the MFMA families, e.g. "ws 3x3 4x16x1@64" or "mfma 3x3 s2 8x4x2@64+tail":
+    family (mfma, g2, splitK, ws), kernel size with s2 / up, the tile TW x TH x TB in output pixels and images, the
+    tile's pixel count BM, and +tail when the last tile of a launch misses images (B % TB != 0).  None for every other
+    launch (attention, first / img / naive convs).  The tile is not in the layer table: it is derived from the output map
+    by the planner's rule (tile_geometry in dsx_plan.cpp): TW = the largest power of two <= 16 dividing Wo, TH = the
+    largest <= BM / TW dividing Ho, TB = BM / (TW TH).  tests/test_planner_cpu.py holds this against the tile the planner
+    wrote into each launch's arguments."""
+    if L["kind"] != 0:
+        return None
+    tags = launch_tags(L["desc"])
+    m = re.search(r"\btile(\d+)x\d+\b", L["desc"])
+    if {"first", "img", "naive"} & tags or not m:
+        return None
+    BM = int(m.group(1))
+    TW = pow2_divisor(L["Wo"], 16)
+    TH = pow2_divisor(L["Ho"], max(1, BM // TW))
+    TB = BM // (TW * TH)
+    assert TB >= 1 and TW * TH * TB == BM, (L["desc"], TW, TH, BM)      # the planner admits nothing else
+    fam = "splitK" if "splitK" in tags else ("ws" if "ws" in tags else ("g2" if "g2" in tags else "mfma"))
+    size = f"{L['ks']}x{L['ks']}" + (" s2" if L["stride"] == 2 else "") + (" up" if L["up"] else "")
+    return f"{fam} {size} {TW}x{TH}x{TB}@{BM}" + ("+tail" if L["B"] % TB else "")
+
+
 def inputs(case, B, H, W, flat=False, ddpm_t=None):
     """seeded (x, t) of one forward; `ddpm_t`: the time tensor of a ddpm-flavour case ((1,) or (B,) values)"""
     g = torch.Generator().manual_seed(1000 + B * 7 + H + W)

@@ -3,10 +3,11 @@
 file pins its coverage claim: every instantiation of the kernel (both kernel sizes, NPH 2 / 4 / 8 in every operand
 type), one- and two-source inputs, GroupNorm with and without Swish, residual and output statistics on and off."""
 import collections
-import ctypes as C
 import re
 
 import pytest
+
+from tests.plan_dump import read_dump
 
 # SR3 UNet: 32 x 32 input, levels 64 / 256 / 512 channels, attention at 8 x 8, 3 conditioning channels
 IMG_MODEL = dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=32, channel_mults=(1, 4, 8),
@@ -28,24 +29,6 @@ PHASES = {"bf16": {1, 2, 3, 4}, "f16": {1, 2, 3, 4}, "f32": {2, 4, 6, 8}}
 NPH = {"bf16": {1: 8, 2: 2, 3: 8, 4: 4}, "f16": {1: 8, 2: 2, 3: 8, 4: 4}, "f32": {2: 2, 4: 4, 6: 8, 8: 8}}
 
 
-class ConvArgsHead(C.Structure):
-    """the leading members of ConvArgs (dsx_kernels.h), up to the ones read here: DSX_PLAN_DUMP writes the struct's bytes"""
-    _fields_ = [("src0", C.c_void_p), ("src1", C.c_void_p), ("act_bf16", C.c_int), ("out_bf16", C.c_int),
-                ("C0", C.c_int), ("C1", C.c_int), ("B", C.c_int), ("Hs", C.c_int), ("Ws", C.c_int), ("up", C.c_int),
-                ("Ho", C.c_int), ("Wo", C.c_int), ("gn_scale", C.c_void_p), ("gn_shift", C.c_void_p),
-                ("has_gn", C.c_int), ("swish", C.c_int), ("stage_mode", C.c_int), ("wpack", C.c_void_p),
-                ("bias", C.c_void_p), ("film", C.c_void_p), ("film_bs", C.c_int), ("resid", C.c_void_p),
-                ("resid_ld", C.c_int), ("out", C.c_void_p), ("out_ld", C.c_int), ("Cout", C.c_int),
-                ("nblocks", C.c_int), ("kchunks", C.c_int), ("tw_log2", C.c_int), ("th_log2", C.c_int),
-                ("tb_log2", C.c_int), ("tiles_x", C.c_int), ("tiles_y", C.c_int), ("m_tiles", C.c_int),
-                ("n_tiles", C.c_int), ("lds_row", C.c_int), ("cpg", C.c_int), ("ws_wg_per_n", C.c_int),
-                ("ws_cpg", C.c_int), ("xcd_bands", C.c_int), ("ws_map", C.c_int), ("ws_nt_log2", C.c_int),
-                ("ws_per", C.c_int), ("ws_adv_x", C.c_int), ("ws_adv_y", C.c_int), ("ws_adv_b", C.c_int),
-                ("ws_dpy", C.c_int), ("ws_dpx", C.c_int), ("mg_tiles_x", C.c_uint), ("mg_per_img", C.c_uint),
-                ("mg_pw", C.c_uint), ("mg_wpn", C.c_uint), ("mg_per", C.c_uint), ("ws_bigdiv", C.c_int),
-                ("stat_part", C.c_void_p)]
-
-
 def img_launches(dt, B, path, monkeypatch):
     """[(description, ks, ConvArgsHead)] of the plan's image-resident launches, in launch order"""
     from diffsplitting_amd import engine
@@ -54,18 +37,13 @@ def img_launches(dt, B, path, monkeypatch):
     H = IMG_MODEL["image_size"]
     a, b, n = engine.plan_dry_run(cfg, dt, B, H, H, COND_CHANNELS)
     assert a == b
+    ops = read_dump(path)
+    assert len(ops) == n
     out = []
-    lines = path.read_text().splitlines()
-    assert len(lines) == n
-    for line in lines:
-        m = re.match(r'\d+ kind=(\d+) desc="([^"]*)" .* launcher=(\w+) dtype=\d+ tile=-?\d+ ks=(\d+) stride=\d+ '
-                     r'col_split=\d+ args=([0-9a-f]+)$', line)
-        assert m, line[:200]
-        if m.group(2).endswith(" img"):
-            assert m.group(3) == "conv_img" and int(m.group(1)) == 0, line[:200]
-            raw = bytes.fromhex(m.group(5))
-            assert len(raw) >= C.sizeof(ConvArgsHead)
-            out.append((m.group(2), int(m.group(4)), ConvArgsHead.from_buffer_copy(raw[:C.sizeof(ConvArgsHead)])))
+    for o in ops:
+        if o["desc"].endswith(" img"):
+            assert o["launcher"] == "conv_img" and o["kind"] == 0, o["desc"]
+            out.append((o["desc"], o["ks"], o["conv"]))
     return out
 
 

@@ -237,3 +237,42 @@ def test_reach_tags_of_the_widths_module():
     assert reach_tags(dict(kind=1, C0=72, desc="attn fused L=64 d=72"), "bf16", 8) == {"attn"}
     assert reach_tags(dict(kind=1, C0=64, desc="attn fused L=64 d=64"), "bf16", 8) == set()
     assert reach_tags(dict(kind=3, C0=0, desc=""), "bf16", 8) == set()
+
+
+def test_geom_tags_of_the_shapes_module():
+    """tests/test_gpu_shapes.py names the tile geometry of every MFMA-family launch from plain layer-table fields
+    (layer_check.geom_tag): hand-made entries against tiles worked out by hand from the planner's rule (TW: largest power
+    of two <= 16 dividing Wo; TH: largest <= BM / TW dividing Ho; TB = BM / (TW TH))"""
+    from tests.layer_check import geom_tag
+
+    def conv(desc, Ho, Wo, B=3, ks=3, stride=1, up=0):
+        return dict(kind=0, desc=desc, ks=ks, stride=stride, up=up, Ho=Ho, Wo=Wo, B=B)
+    # the maps every other GPU module runs: 8 x 8 pixels and wider
+    assert geom_tag(conv("conv3x3 64->64 @32x32 tile64x64", 32, 32)) == "mfma 3x3 16x4x1@64"
+    assert geom_tag(conv("conv3x3 64->64 @8x8 tile64x64", 8, 8)) == "mfma 3x3 8x8x1@64"
+    assert geom_tag(conv("conv3x3 64->64 @8x12 tile64x64", 8, 12)) == "mfma 3x3 4x8x2@64+tail"
+    assert geom_tag(conv("conv3x3 64->64 @4x4 tile64x64", 4, 4, B=4)) == "mfma 3x3 4x4x4@64"
+    # narrow maps: 12, 6, 4 and 2 pixels wide, and 6 high
+    assert geom_tag(conv("conv3x3 16->16 @64x12 tile64x64 ws", 64, 12)) == "ws 3x3 4x16x1@64"
+    assert geom_tag(conv("conv1x1 32->32 @64x12 tile64x64 ws +gn", 64, 12, ks=1)) == "ws 1x1 4x16x1@64"
+    assert geom_tag(conv("conv3x3up 32->32 @64x12 tile64x64 ws c2", 64, 12, up=1)) == "ws 3x3 up 4x16x1@64"
+    assert geom_tag(conv("conv1x1 64->64 @32x6 tile64x64 ws", 32, 6, ks=1)) == "ws 1x1 2x32x1@64"
+    assert geom_tag(conv("conv3x3 64->64 @16x6 tile64x64", 16, 6)) == "mfma 3x3 2x16x2@64+tail"
+    assert geom_tag(conv("conv3x3 64->64 @16x6 tile64x64", 16, 6, B=2)) == "mfma 3x3 2x16x2@64"
+    assert geom_tag(conv("conv3x3 64->64 @16x6 tile64x64", 16, 6, B=1)) == "mfma 3x3 2x16x2@64+tail"
+    assert geom_tag(conv("conv3x3 64->64 @6x16 tile64x64 splitK3", 6, 16)) == "splitK 3x3 16x2x2@64+tail"
+    assert geom_tag(conv("conv3x3s2 32->32 @12x8 tile64x64", 12, 8, stride=2)) == "mfma 3x3 s2 8x4x2@64+tail"
+    assert geom_tag(conv("conv3x3s2 32->32 @12x8 tile64x64 splitK2", 12, 8, stride=2)) == "splitK 3x3 s2 8x4x2@64+tail"
+    # the same map on a 128-pixel tile takes twice the rows, or twice the images once the rows are used up
+    assert geom_tag(conv("conv3x3 16->16 @64x12 tile128x32", 64, 12)) == "mfma 3x3 4x32x1@128"
+    assert geom_tag(conv("conv3x3 16->16 @64x12 tile128x32 g2", 64, 12)) == "g2 3x3 4x32x1@128"
+    assert geom_tag(conv("conv1x1 64->64 @16x6 tile128x128", 16, 6, ks=1)) == "mfma 1x1 2x16x4@128+tail"
+    assert geom_tag(conv("conv1x1 64->64 @16x6 tile128x128", 16, 6, ks=1, B=4)) == "mfma 1x1 2x16x4@128"
+    assert geom_tag(conv("conv3x3 64->64 @64x24 tile128x64 ws c2", 64, 24)) == "ws 3x3 8x16x1@128"
+    assert geom_tag(conv("conv3x3 16->3 @64x48 tile256x32 g2", 64, 48)) == "g2 3x3 16x16x1@256"
+    # launches outside the MFMA families, and layers that are no convs
+    assert geom_tag(conv("conv3x3 6->32 @64x48 first", 64, 48)) is None
+    assert geom_tag(conv("conv3x3 512->512 @8x8 img", 8, 8)) is None
+    assert geom_tag(conv("conv3x3-naive 16->16 @64x12", 64, 12)) is None
+    assert geom_tag(dict(kind=1, desc="attn fused L=64 d=64")) is None
+    assert geom_tag(dict(kind=3, desc="")) is None
