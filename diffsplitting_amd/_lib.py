@@ -36,6 +36,11 @@ class StepTable(C.Structure):
                 ("per_sample", C.c_int32)]
 
 
+class SolverTable(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("clip", C.c_int32)] + \
+        [(n, C.POINTER(C.c_float)) for n in ("tcond", "a", "b", "cx", "c0", "cp", "sigma")]
+
+
 class LayerInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "kind", "op_begin", "op_end", "op_main", "ks", "stride", "up", "swish", "B", "Hs", "Ws", "Ho", "Wo",
@@ -125,6 +130,9 @@ SIGNATURES = {
     "dsx_sample_loop_streams": (_i, [_hn, C.POINTER(StepTable), _Df, _Df, _Df, _u64, _pi32, _i, _Df, _i, _st, _pu64, _i]),
     "dsx_posterior_step_streams": (_i, [_Df, _Df, _i, _i, _i, _i, _Df, _Df, _Df, _Df, _Df, _i, _i, _Df, _u64, _u64, _i, _Df,
                                         _Df, _Df, _st, _pu64, _i]),
+    "dsx_solver_loop": (_i, [_hn, C.POINTER(SolverTable), _Df, _Df, _Df, _u64, _pi32, _i, _Df, _i, _st, _pu64, _i]),
+    "dsx_solver_step": (_i, [_Df, _Df, _Df, _i, _i, _i, _i, _Df, _Df, _Df, _Df, _Df, _Df, _i, _Df, _u64, _u64, _Df, _Df, _st,
+                             _pu64, _i, C.c_uint32]),
     "dsx_val_report": (_i, [_Df, _Df, _Df, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.POINTER(C.c_double),
                             C.POINTER(C.c_double), _D16, _D16, _D16, _D16, _D16, _D16, _D64, _D64, _st]),
     "dsx_tile_plan": (_i64, [_pi64, _pi64, _pi64, _i, _pi64, _pi64, _i64]),

@@ -152,14 +152,16 @@ extern "C" int dsx_exec_profile(dsx_exec* ex, int iters, float* ms_per_op, void*
   return DSX_OK;
 }
 
-// time embedding + UNet body on `st`; inputs already in ex->in_cond / ex->in_x
-static int run_unet(dsx_exec* ex, bool from_table, int n_time, hipStream_t st, int per_sample = 0) {
+// time embedding + UNet body on `st`; inputs already in ex->in_cond / ex->in_x.  tcond_table: the device column of
+// per-step time values read at the step counter (nullptr: the step table's own)
+static int run_unet(dsx_exec* ex, bool from_table, int n_time, hipStream_t st, int per_sample = 0,
+                    const float* tcond_table = nullptr) {
   dsx_model* m = ex->m;
   if (m->cfg.with_time_emb) {
     TembArgs t{};
     t.flavour = m->cfg.flavour; t.B = ex->B; t.n_time = n_time;
     t.time = from_table ? nullptr : ex->time_buf;
-    t.table = ex->table.as<float>(); t.step_ctr = ex->step_ctr; t.per_sample = per_sample;
+    t.table = tcond_table ? tcond_table : ex->table.as<float>(); t.step_ctr = ex->step_ctr; t.per_sample = per_sample;
     t.inner = m->cfg.inner_channel; t.freq = m->d_freq;
     t.w1 = m->d_w1; t.b1 = m->d_b1; t.w2 = m->d_w2; t.b2 = m->d_b2;
     t.wf = m->d_wf; t.bf = m->d_bf; t.F = m->F; t.film = ex->film;
@@ -219,13 +221,11 @@ static int ensure_table(dsx_exec* ex, const dsx_step_table* tab) {
   return DSX_OK;
 }
 
-// a pinned staging slot holding this call's table [6][cap] followed by {seed, noise address} and, with per-sample
-// noise streams, the B sample ids; *out = its host pointer
-static int stage_call(dsx_exec* ex, const dsx_step_table* tab, uint64_t seed, const float* noise, const uint64_t* ids,
-                      dsx_exec::Staging** out) {
-  const int cap = ex->table_cap;
-  const int T = tab->n_steps * (tab->per_sample > 0 ? tab->per_sample : 1);
-  const size_t need = (size_t)6 * cap + 4 + (ids ? (size_t)2 * ex->B : 0);   // + 16 bytes of loop parameters (+ ids)
+// a pinned staging slot holding this call's table [ncols][cap] (T values per column; a null column stays zero)
+// followed by {seed, noise address} and, with per-sample noise streams, the B sample ids; *out = its host pointer
+static int stage_call(dsx_exec* ex, const float* const* cols, int ncols, int T, int cap, uint64_t seed, const float* noise,
+                      const uint64_t* ids, dsx_exec::Staging** out) {
+  const size_t need = (size_t)ncols * cap + 4 + (ids ? (size_t)2 * ex->B : 0);   // + 16 bytes of loop parameters (+ ids)
   dsx_exec::Staging& sl = ex->staging[ex->staging_next];
   ex->staging_next = (ex->staging_next + 1) % 4;
   if (sl.busy) { HIP_TRY(hipEventSynchronize(sl.ev.e)); sl.busy = false; }
@@ -236,14 +236,25 @@ static int stage_call(dsx_exec* ex, const dsx_step_table* tab, uint64_t seed, co
   }
   if (!sl.ev.e) HIP_TRY(sl.ev.create(hipEventDisableTiming));
   float* host = sl.host.as<float>();
-  memset(host, 0, (size_t)6 * cap * sizeof(float));
-  const float* cols[6] = {tab->tcond, tab->a, tab->b, tab->c1, tab->c2, tab->sigma};
-  for (int k = 0; k < 6; ++k)
+  memset(host, 0, (size_t)ncols * cap * sizeof(float));
+  for (int k = 0; k < ncols; ++k)
     if (cols[k]) memcpy(host + (size_t)k * cap, cols[k], (size_t)T * 4);
   unsigned long long lp[2] = {seed, (unsigned long long)(uintptr_t)noise};
-  memcpy(host + (size_t)6 * cap, lp, 16);
-  if (ids) memcpy(host + (size_t)6 * cap + 4, ids, (size_t)ex->B * 8);
+  memcpy(host + (size_t)ncols * cap, lp, 16);
+  if (ids) memcpy(host + (size_t)ncols * cap + 4, ids, (size_t)ex->B * 8);
   *out = &sl;
+  return DSX_OK;
+}
+// the staged call -> device memory on `st`: the table, the loop parameters, the ids, the step counter
+static int upload_call(dsx_exec* ex, dsx_exec::Staging* sl, void* table_dev, int ncols, int cap, bool ids, hipStream_t st) {
+  const float* host = sl->host.as<float>();
+  HIP_TRY(hipMemcpyAsync(table_dev, host, (size_t)ncols * cap * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ex->loop_params, host + (size_t)ncols * cap, 16, hipMemcpyHostToDevice, st));
+  if (ids)
+    HIP_TRY(hipMemcpyAsync(ex->sample_ids.p, host + (size_t)ncols * cap + 4, (size_t)ex->B * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(sl->ev.e, st));
+  sl->busy = true;
+  HIP_TRY(hipMemsetAsync(ex->step_ctr, 0, 4, st));
   return DSX_OK;
 }
 
@@ -259,6 +270,53 @@ static int enqueue_step(dsx_exec* ex, const dsx_step_table* tab, bool use_noise,
   u.sample_ids = streams ? ex->sample_ids.as<unsigned long long>() : nullptr;   // the executor's buffer, not the ids
   HIP_TRY(launch_update(u, st));
   HIP_TRY(launch_advance(ex->step_ctr, st));
+  return DSX_OK;
+}
+
+// T steps on `st` from the loaded inputs, snapshots after the named ones, the final state to `x`.  use_graph: `step` is
+// captured once into ex->graph and replayed; a kept graph is replayed only when its signature equals `sig`, so loops
+// whose steps differ (other mode flags, another kernel) recapture instead of replaying each other's step.
+template <class Step>
+static int replay_steps(dsx_exec* ex, const std::vector<float>& sig, Step&& step, int T, const int32_t* snap_steps, int n_snap,
+                        float* snaps, float* x, int use_graph, hipStream_t st) {
+  int rc = DSX_OK;
+  const size_t snap_elems = (size_t)ex->B * ex->x_c * ex->H * ex->W;
+  bool graph_ok = false;
+  if (use_graph) {
+    if (!ex->graph.exec || sig != ex->graph_sig) {
+      if ((rc = drop_graph(ex))) return rc;
+      Stream cs;
+      HIP_TRY(cs.create(hipStreamNonBlocking));
+      hipError_t e = hipStreamBeginCapture(cs.s, hipStreamCaptureModeThreadLocal);
+      if (e == hipSuccess) {
+        rc = step(cs.s);
+        hipError_t e2 = hipStreamEndCapture(cs.s, &ex->graph.graph);
+        if (rc == DSX_OK && e2 == hipSuccess) e2 = hipGraphInstantiate(&ex->graph.exec, ex->graph.graph, nullptr, nullptr, 0);
+        if (rc != DSX_OK || e2 != hipSuccess) {
+          (void)hipGetLastError();
+          ex->graph.reset();
+        }
+      } else {
+        (void)hipGetLastError();
+      }
+      if (ex->graph.exec) ex->graph_sig = sig;
+      else if (rc != DSX_OK) return rc;
+    }
+    graph_ok = ex->graph.exec != nullptr;
+    if (!graph_ok) return fail(DSX_ERR_HIP, "hipGraph capture of the sampling step failed");
+    ex->last_stream = st;
+  }
+  int snap_i = 0;
+  for (int s = 0; s < T; ++s) {
+    if (graph_ok) HIP_TRY(hipGraphLaunch(ex->graph.exec, st));
+    else if ((rc = step(st))) return rc;
+    while (snap_i < n_snap && snap_steps[snap_i] == s) {
+      HIP_TRY(launch_nhwc_to_nchw(ex->x_state, snaps + (size_t)snap_i * snap_elems, ex->B, ex->x_c, ex->H,
+                                  ex->W, st));
+      ++snap_i;
+    }
+  }
+  HIP_TRY(launch_nhwc_to_nchw(ex->x_state, x, ex->B, ex->x_c, ex->H, ex->W, st));
   return DSX_OK;
 }
 
@@ -283,58 +341,16 @@ static int sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* con
   // from a pinned staging slot of this call's own
   dsx_exec::Staging* sl = nullptr;
   if (ids && !ex->sample_ids.p) HIP_TRY(ex->sample_ids.alloc((size_t)ex->B * 8));   // once: captured steps keep the address
-  if ((rc = stage_call(ex, tab, seed, noise, ids, &sl))) return rc;
-  HIP_TRY(hipMemcpyAsync(ex->table.p, sl->host.p, (size_t)6 * ex->table_cap * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ex->loop_params, sl->host.as<float>() + (size_t)6 * ex->table_cap, 16, hipMemcpyHostToDevice, st));
-  if (ids)
-    HIP_TRY(hipMemcpyAsync(ex->sample_ids.p, sl->host.as<float>() + (size_t)6 * ex->table_cap + 4, (size_t)ex->B * 8,
-                           hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(sl->ev.e, st));
-  sl->busy = true;
-  HIP_TRY(hipMemsetAsync(ex->step_ctr, 0, 4, st));
+  const float* cols[6] = {tab->tcond, tab->a, tab->b, tab->c1, tab->c2, tab->sigma};
+  const int per = tab->per_sample > 0 ? tab->per_sample : 1;
+  if ((rc = stage_call(ex, cols, 6, T * per, ex->table_cap, seed, noise, ids, &sl))) return rc;
+  if ((rc = upload_call(ex, sl, ex->table.p, 6, ex->table_cap, ids != nullptr, st))) return rc;
   if ((rc = load_inputs(ex, cond, x, ex->x_c, 0, st))) return rc;
-
-  const size_t snap_elems = (size_t)ex->B * ex->x_c * ex->H * ex->W;
-  bool graph_ok = false;
-  if (use_graph) {
-    // the captured step bakes in the mode flags only (not the step count, the seed, the noise address or the sample ids)
-    std::vector<float> sig = {(float)tab->predict_eps, (float)tab->clip, noise ? 1.f : 0.f, tab->per_sample > 0 ? 1.f : 0.f,
-                              ids ? 1.f : 0.f};
-    if (!ex->graph.exec || sig != ex->graph_sig) {
-      if ((rc = drop_graph(ex))) return rc;
-      Stream cs;
-      HIP_TRY(cs.create(hipStreamNonBlocking));
-      hipError_t e = hipStreamBeginCapture(cs.s, hipStreamCaptureModeThreadLocal);
-      if (e == hipSuccess) {
-        rc = enqueue_step(ex, tab, noise != nullptr, ids != nullptr, cs.s);
-        hipError_t e2 = hipStreamEndCapture(cs.s, &ex->graph.graph);
-        if (rc == DSX_OK && e2 == hipSuccess) e2 = hipGraphInstantiate(&ex->graph.exec, ex->graph.graph, nullptr, nullptr, 0);
-        if (rc != DSX_OK || e2 != hipSuccess) {
-          (void)hipGetLastError();
-          ex->graph.reset();
-        }
-      } else {
-        (void)hipGetLastError();
-      }
-      if (ex->graph.exec) ex->graph_sig = sig;
-      else if (rc != DSX_OK) return rc;
-    }
-    graph_ok = ex->graph.exec != nullptr;
-    if (!graph_ok) return fail(DSX_ERR_HIP, "hipGraph capture of the sampling step failed");
-    ex->last_stream = st;
-  }
-  int snap_i = 0;
-  for (int s = 0; s < T; ++s) {
-    if (graph_ok) HIP_TRY(hipGraphLaunch(ex->graph.exec, st));
-    else if ((rc = enqueue_step(ex, tab, noise != nullptr, ids != nullptr, st))) return rc;
-    while (snap_i < n_snap && snap_steps[snap_i] == s) {
-      HIP_TRY(launch_nhwc_to_nchw(ex->x_state, snaps + (size_t)snap_i * snap_elems, ex->B, ex->x_c, ex->H,
-                                  ex->W, st));
-      ++snap_i;
-    }
-  }
-  HIP_TRY(launch_nhwc_to_nchw(ex->x_state, x, ex->B, ex->x_c, ex->H, ex->W, st));
-  return DSX_OK;
+  // the captured step bakes in the mode flags only (not the step count, the seed, the noise address or the sample ids)
+  const std::vector<float> sig = {(float)tab->predict_eps, (float)tab->clip, noise ? 1.f : 0.f, tab->per_sample > 0 ? 1.f : 0.f,
+                                  ids ? 1.f : 0.f};
+  return replay_steps(ex, sig, [&](hipStream_t s) { return enqueue_step(ex, tab, noise != nullptr, ids != nullptr, s); }, T,
+                      snap_steps, n_snap, snaps, x, use_graph, st);
 }
 
 extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x,
@@ -364,6 +380,65 @@ extern "C" int dsx_sample_loop_streams(dsx_exec* ex, const dsx_step_table* tab, 
   const int rc = stream_ids_ok("sample_loop_streams", sample_ids, n_sample_ids, ex->B, (uint64_t)std::max(tab->n_steps, 0));
   if (rc) return rc;
   return sample_loop(ex, tab, cond, x, nullptr, seed, snap_steps, n_snap, snaps, use_graph, stream, sample_ids);
+}
+
+// ---- few-step solvers (include/dsx.h): sample_loop with a 7-column table of its own and k_solver_update as the update
+static int enqueue_solver_step(dsx_exec* ex, int clip, bool use_noise, bool streams, hipStream_t st) {
+  int rc = run_unet(ex, true, 1, st, 0, ex->solver_table.as<float>());   // column 0 of the solver table: tcond
+  if (rc) return rc;
+  SolverUpdateArgs u{};
+  u.x = ex->x_state; u.x_act = ex->in_x.st ? ex->in_x.p : nullptr; u.x_act_kind = ex->in_x.st;
+  u.net = (const float*)ex->out.p; u.x0_hist = ex->solver_hist.as<float>();
+  u.use_noise = use_noise ? 1 : 0; u.loop_params = ex->loop_params;
+  u.tab = ex->solver_table.as<float>(); u.n_steps = ex->solver_cap; u.step_ctr = ex->step_ctr;
+  u.clip = clip;
+  u.B = ex->B; u.C = ex->x_c; u.H = ex->H; u.W = ex->W;
+  u.sample_ids = streams ? ex->sample_ids.as<unsigned long long>() : nullptr;
+  HIP_TRY(launch_solver_update(u, st));
+  HIP_TRY(launch_advance(ex->step_ctr, st));
+  return DSX_OK;
+}
+
+extern "C" int dsx_solver_loop(dsx_exec* ex, const dsx_solver_table* tab, const float* cond, float* x, const float* noise,
+                               uint64_t seed, const int32_t* snap_steps, int n_snap, float* snaps, int use_graph,
+                               void* stream, const uint64_t* sample_ids, int n_sample_ids) {
+  if (!ex) return fail(DSX_ERR_INVALID, "solver_loop: null executor");
+  if (!tab) return fail(DSX_ERR_INVALID, "solver_loop: null solver table");
+  if (!x || tab->n_steps < 1) return fail(DSX_ERR_INVALID, "solver_loop: null state or empty table");
+  if (!tab->tcond || !tab->a || !tab->b || !tab->cx || !tab->c0 || !tab->cp || !tab->sigma)
+    return fail(DSX_ERR_INVALID, "solver_loop: solver table columns missing");
+  if (tab->cp[0] != 0.f) return fail(DSX_ERR_INVALID, "solver_loop: cp[0] != 0: no previous x0 at the first step");
+  if (ex->out.C != ex->x_c)
+    return fail(DSX_ERR_INVALID, "solver_loop: UNet out_channel (%d) must equal the state channels (%d)", ex->out.C, ex->x_c);
+  if (n_snap > 0 && (!snap_steps || !snaps)) return fail(DSX_ERR_INVALID, "solver_loop: snapshot arrays missing");
+  if (sample_ids) {
+    if (noise) return fail(DSX_ERR_INVALID, "solver_loop: injected noise together with sample_ids");
+    const int rc = stream_ids_ok("solver_loop", sample_ids, n_sample_ids, ex->B, (uint64_t)tab->n_steps);
+    if (rc) return rc;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int T = tab->n_steps;
+  int rc = DSX_OK;
+  if (T > ex->solver_cap) {   // the table's column stride (= capacity) is baked into captured graphs: drop them
+    if ((rc = drop_graph(ex))) return rc;
+    const int cap = std::max(T, 256);
+    HIP_TRY(ex->solver_table.alloc((size_t)kSolverCols * cap * sizeof(float)));
+    ex->solver_cap = cap;
+  }
+  // once each, outside the workspace: captured steps keep the addresses
+  if (!ex->solver_hist.p) HIP_TRY(ex->solver_hist.alloc((size_t)ex->B * ex->x_c * ex->H * ex->W * sizeof(float)));
+  if (sample_ids && !ex->sample_ids.p) HIP_TRY(ex->sample_ids.alloc((size_t)ex->B * 8));
+  dsx_exec::Staging* sl = nullptr;
+  const float* cols[kSolverCols] = {tab->tcond, tab->a, tab->b, tab->cx, tab->c0, tab->cp, tab->sigma};
+  if ((rc = stage_call(ex, cols, kSolverCols, T, ex->solver_cap, seed, noise, sample_ids, &sl))) return rc;
+  if ((rc = upload_call(ex, sl, ex->solver_table.p, kSolverCols, ex->solver_cap, sample_ids != nullptr, st))) return rc;
+  if ((rc = load_inputs(ex, cond, x, ex->x_c, 0, st))) return rc;
+  // first entry 2: no ancestral signature (its first entry is predict_eps, 0 or 1) equals a solver signature
+  const bool use_noise = noise != nullptr, streams = sample_ids != nullptr;
+  const int clip = tab->clip ? 1 : 0;
+  const std::vector<float> sig = {2.f, (float)clip, use_noise ? 1.f : 0.f, 0.f, streams ? 1.f : 0.f};
+  return replay_steps(ex, sig, [&](hipStream_t s) { return enqueue_solver_step(ex, clip, use_noise, streams, s); }, T,
+                      snap_steps, n_snap, snaps, x, use_graph, st);
 }
 
 extern "C" int dsx_randn_samples(float* out, int B, int64_t chw, uint64_t seed, const uint64_t* ids, uint32_t draw,
@@ -517,6 +592,40 @@ extern "C" int dsx_posterior_step_streams(const float* x, const float* net, int 
                         nullptr, seed, 0, at(x_recon_out), at(mean_out), at(x_out),
                         rows, predict_eps ? 1 : 0, clip ? 1 : 0, 0, CHW};
     HIP_TRY(launch_posterior_step_streams(p, s, (int64_t)H * W, (hipStream_t)stream));
+  }
+  return DSX_OK;
+}
+// one solver update (k_solver_step): sample_ids == nullptr -> z_dev or the stream (seed, subsequence); else the sample
+// streams (seed, sample_ids[b], draw)
+extern "C" int dsx_solver_step(const float* x, const float* net, const float* x0_prev, int B, int C, int H, int W,
+                               const float* a, const float* b, const float* cx, const float* c0, const float* cp,
+                               const float* sigma, int clip, const float* z, uint64_t seed, uint64_t subsequence,
+                               float* x_recon_out, float* x_out, void* stream, const uint64_t* sample_ids,
+                               int n_sample_ids, uint32_t draw) {
+  int rc = steps_shape("solver_step", B, C, H, W);
+  if (rc) return rc;
+  if (sample_ids) {
+    if (z) return fail(DSX_ERR_INVALID, "solver_step: injected noise together with sample_ids");
+    if ((rc = stream_ids_ok("solver_step", sample_ids, n_sample_ids, B, draw))) return rc;
+  }
+  if (!x || !net || !a || !b || !cx || !c0 || !sigma) return fail(DSX_ERR_INVALID, "solver_step: null argument");
+  if (x0_prev && !cp) return fail(DSX_ERR_INVALID, "solver_step: x0_prev without the column cp");
+  if (!x_recon_out || !x_out) return fail(DSX_ERR_INVALID, "solver_step: null output");
+  const int64_t CHW = (int64_t)C * H * W;
+  if (!sample_ids) {
+    SolverStepArgs p{x, net, x0_prev, a, b, cx, c0, cp, sigma, z, seed, subsequence, x_recon_out, x_out, B, clip ? 1 : 0, CHW};
+    HIP_TRY(launch_solver_step(p, (int64_t)H * W, (hipStream_t)stream));
+    return DSX_OK;
+  }
+  for (int b0 = 0; b0 < B; b0 += kStreamRows) {     // kStreamRows samples per launch: their ids are kernel arguments
+    StreamIds s{};
+    const int rows = std::min(B - b0, kStreamRows);
+    for (int r = 0; r < rows; ++r) s.subseq[r] = (sample_ids[b0 + r] << 24) | draw;
+    const size_t off = (size_t)b0 * CHW;
+    SolverStepArgs p{x + off, net + off, x0_prev ? x0_prev + off : nullptr, a + b0, b + b0, cx + b0, c0 + b0,
+                     cp ? cp + b0 : nullptr, sigma + b0, nullptr, seed, 0, x_recon_out + off, x_out + off,
+                     rows, clip ? 1 : 0, CHW};
+    HIP_TRY(launch_solver_step_streams(p, s, (int64_t)H * W, (hipStream_t)stream));
   }
   return DSX_OK;
 }

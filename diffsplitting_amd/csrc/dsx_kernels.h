@@ -410,6 +410,23 @@ struct UpdateArgs {
   const unsigned long long* sample_ids;
 };
 hipError_t launch_update(const UpdateArgs& a, hipStream_t st);
+// dsx_solver.hip.  The loop update of the few-step solvers: k_update with solver_update in place of step_update and the
+// previous step's predicted x0 kept on the device.  The members shared with UpdateArgs mean what they mean there.
+constexpr int kSolverCols = 7;
+struct SolverUpdateArgs {
+  float* x; void* x_act; int x_act_kind;
+  const float* net;
+  float* x0_hist;         // NHWC fp32 like x: read where the row's cp != 0, written at every step
+  int use_noise;
+  const unsigned long long* loop_params;
+  const float* tab;       // device table [kSolverCols][n_steps]: tcond,a,b,cx,c0,cp,sigma
+  int n_steps;
+  const int* step_ctr;
+  int clip;
+  int B, C, H, W;
+  const unsigned long long* sample_ids;
+};
+hipError_t launch_solver_update(const SolverUpdateArgs& a, hipStream_t st);
 // Per-sample noise streams without an executor: the Philox subsequences (id << 24 | draw) of up to kStreamRows samples
 // travel in the kernel arguments; larger batches take several launches.
 constexpr int kStreamRows = 32;
@@ -522,6 +539,23 @@ __device__ __forceinline__ StepVals step_update(float a, float b, float c1, floa
   v.out = use_z ? add_f(v.mean, mul_f(z, sigma)) : v.mean;
   return v;
 }
+// The update of the few-step solvers (DDIM, DPM-Solver++(2M) in data prediction; model/solvers.py builds the rows),
+// stated once for the loop (k_solver_update) and the single step (k_solver_step), both in dsx_solver.hip:
+//   x0  = clamp(a*x - b*net)                               (step_update's expression)
+//   m   = c0*x0 + cx*x
+//   m   = cp != 0 ? m + cp*x0_prev : m                     (the caller does not load x0_prev where cp == 0)
+//   out = use_z ? m + z*sigma : m
+// With cp == 0 this is step_update with c1 = c0 and c2 = cx, bit for bit.
+struct SolverVals { float x0, out; };
+__device__ __forceinline__ SolverVals solver_update(float a, float b, float cx, float c0, float cp, float sigma, bool clip,
+                                                    float x, float net, float x0_prev, float z, bool use_z) {
+  const StepVals s = step_update(a, b, c0, cx, sigma, true, clip, x, net, 0.f, false);
+  SolverVals v;
+  v.x0 = s.x0;
+  const float m = cp != 0.f ? add_f(s.mean, mul_f(cp, x0_prev)) : s.mean;
+  v.out = use_z ? add_f(m, mul_f(z, sigma)) : m;
+  return v;
+}
 
 // The engine's normal stream: element i of the stream (seed, subseq) is component i % 4 of normal4(seed, subseq, i / 4).
 // Shared by k_randn, k_update (dsx_ops.hip) and the pointwise kernels of dsx_steps.hip, which must agree bitwise.
@@ -626,6 +660,21 @@ hipError_t launch_posterior_step(const PosteriorStepArgs& a, long long HW, hipSt
 // the same with z = element (i % CHW) of the stream (a.seed, s.subseq[i / CHW]); a.z, a.subseq and a.repeat are not
 // read; a.B <= kStreamRows
 hipError_t launch_posterior_step_streams(const PosteriorStepArgs& a, const StreamIds& s, long long HW, hipStream_t st);
+// dsx_solver.hip.  One solver update (solver_update above; NCHW fp32, per-sample coefficients, B values each).
+// x0_prev == nullptr: every cp is 0 (checked by the caller); it is read only for the samples whose cp != 0.
+// z == nullptr: element i of the normal stream (seed, subseq).  x_recon_out (the next call's x0_prev) and x_out are
+// both written; x_out may be x.
+struct SolverStepArgs {
+  const float* x; const float* net; const float* x0_prev;
+  const float* a; const float* b; const float* cx; const float* c0; const float* cp; const float* sigma;
+  const float* z; unsigned long long seed, subseq;
+  float* x_recon_out; float* x_out;
+  int B, clip;
+  long long CHW;
+};
+hipError_t launch_solver_step(const SolverStepArgs& a, long long HW, hipStream_t st);
+// the same with z = element (i % CHW) of the stream (a.seed, s.subseq[i / CHW]); a.z and a.subseq are not read; a.B <= kStreamRows
+hipError_t launch_solver_step_streams(const SolverStepArgs& a, const StreamIds& s, long long HW, hipStream_t st);
 // out = c*(a0[b]*x1 + s0[b]*z1) + d*(a0[b]*x2 + s0[b]*z2); z1 == nullptr: the streams (seed, subseq), (seed, subseq + 1)
 struct InterpStartArgs {
   const float* x1; const float* x2; const float* a0; const float* s0;

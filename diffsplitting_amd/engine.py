@@ -311,6 +311,16 @@ class UNetEngine:
         ``sample_ids`` (B integers): per-sample noise streams (``dsx_sample_loop_streams``): step ``s`` of sample ``b``
         draws ``randn_samples(.., seed, sample_ids, draw=s + 1)[b]`` whatever the batch it sits in; not together with
         ``noise``."""
+        return self._loop(False, table, x_init, cond, noise, seed, snapshot_steps, use_graph, stream, slot, sample_ids)
+
+    def solver_loop(self, table, x_init, cond=None, noise=None, seed=0, snapshot_steps=(), use_graph=True, stream=None,
+                    sample_ids=None):
+        """``sample_loop`` for the rows of a few-step solver (``table``: a ``model.solvers.SolverTableHost``;
+        ``dsx_solver_loop``): the previous step's predicted x0 stays on the device between the replays of the captured
+        step.  Arguments and return value as ``sample_loop``; ``noise`` is (K, B, C, H, W) for K rows."""
+        return self._loop(True, table, x_init, cond, noise, seed, snapshot_steps, use_graph, stream, 0, sample_ids)
+
+    def _loop(self, solver, table, x_init, cond, noise, seed, snapshot_steps, use_graph, stream, slot, sample_ids):
         x = x_init.contiguous()
         B, Cx, H, W = x.shape
         ids = None
@@ -340,7 +350,10 @@ class UNetEngine:
         args = (ex, C.byref(table.c_struct()), cond, x, noise, _seed64(seed),
                 steps.ctypes.data_as(C.POINTER(C.c_int32)) if len(steps) else None, len(steps), snaps,
                 1 if use_graph else 0, stream)
-        if ids is None:
+        if solver:
+            check(lib.dsx_solver_loop(*args, None if ids is None else ids.ctypes.data_as(_lib._pu64),
+                                      0 if ids is None else len(ids)))
+        elif ids is None:
             check(lib.dsx_sample_loop(*args))
         else:
             check(lib.dsx_sample_loop_streams(*args, ids.ctypes.data_as(_lib._pu64), len(ids)))
@@ -707,6 +720,42 @@ def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, cli
     check(lib.dsx_posterior_step(x, net, B, Cn, H, W, a, b, c1, c2, sigma, 1 if predict_eps else 0, 1 if clip else 0, z,
                                  _seed64(seed), C.c_uint64(int(subsequence)), 1 if repeat_noise else 0, *outs, None))
     return tuple(outs)
+
+
+def solver_step(x, net, a, b, cx, c0, sigma, cp=None, x0_prev=None, clip=False, z=None, seed=0, subsequence=0,
+                x_recon_out=None, x_out=None, sample_ids=None, draw=None):
+    """``dsx_solver_step``: one update of a few-step solver (``model/solvers.py``) in one launch,
+    ``x0 = clamp?(a*x - b*net)``, ``x_out = c0*x0 + cx*x (+ cp*x0_prev) (+ sigma*z)``.  ``a`` .. ``sigma``: (B,)
+    per-sample coefficients; ``x0_prev`` (the previous call's ``x_recon_out``) is read only for the samples whose ``cp``
+    is not 0 and may be None when there is none (``cp`` then counts as 0).  Noise as in ``posterior_step``.  Both
+    outputs are written (new tensors unless given; ``x_out`` may be ``x``, ``x_recon_out`` may be ``x0_prev``).
+    Returns ``(x_recon_out, x_out)``."""
+    x, B, Cn, H, W = _bchw(x, "x")
+    net = _f32_cuda(net, "net", x.shape)
+    a, b, cx, c0, sigma = (_coef(c, what, B) for c, what in ((a, "a"), (b, "b"), (cx, "cx"), (c0, "c0"), (sigma, "sigma")))
+    if x0_prev is not None:
+        if cp is None:
+            raise DsxError("x0_prev needs the column cp")
+        x0_prev, cp = _f32_cuda(x0_prev, "x0_prev", x.shape), _coef(cp, "cp", B)
+    else:
+        cp = None
+    if z is not None:
+        z = _f32_cuda(z, "noise", x.shape)
+    x_recon_out = torch.empty_like(x) if x_recon_out is None else _f32_cuda(x_recon_out, "x_recon_out", x.shape)
+    x_out = torch.empty_like(x) if x_out is None else _f32_cuda(x_out, "x_out", x.shape)
+    ids, n_ids, d = None, 0, 0
+    if sample_ids is not None:
+        if z is not None:
+            raise DsxError("sample_ids together with injected noise: the draws come from one or the other")
+        if draw is None:
+            raise DsxError("sample_ids need the draw ordinal (draw = step + 1 inside a loop)")
+        ids_np = _sample_ids(sample_ids, B)
+        ids, n_ids, d = ids_np.ctypes.data_as(_lib._pu64), len(ids_np), _draw_ordinal(draw)
+    elif draw is not None:
+        raise DsxError("draw names a draw of a sample stream: only with sample_ids")
+    check(lib.dsx_solver_step(x, net, x0_prev, B, Cn, H, W, a, b, cx, c0, cp, sigma, 1 if clip else 0, z, _seed64(seed),
+                              C.c_uint64(int(subsequence)), x_recon_out, x_out, None, ids, n_ids, C.c_uint32(d)))
+    return x_recon_out, x_out
 
 
 def interp_start(x1, x2, a0, s0, lam, z1=None, z2=None, seed=0, subsequence=0, out=None):

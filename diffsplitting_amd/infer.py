@@ -10,7 +10,10 @@ reference's flags: ``--dataroot`` overrides ``datasets.val.dataroot``, ``--batch
 (the reference's loader yields one), ``--steps`` overrides ``beta_schedule.val.n_timestep``, ``--dtype`` the MFMA
 operand type and ``--seed`` torch's generator, from which the device noise is seeded.  ``--sample-seed S`` draws every
 image's noise from its own stream instead (seed S, sample id = the image's ordinal in the validation set): image 37 is
-the same whatever ``--batch`` it ran in and whichever images ran before it.
+the same whatever ``--batch`` it ran in and whichever images ran before it.  ``--solver {ddim,dpmpp2m} --solver-steps K
+[--eta E] [--spacing uniform|logsnr]`` samples with a few-step solver over K timesteps of the schedule the checkpoint
+was trained on (``model/solvers.py``; refused by name for a sampler that is not Gaussian); without ``--solver`` the run is
+the ancestral loop as before.
 
 Per image the run writes ``{step}_{idx}_hr.png`` (ground truth), ``{step}_{idx}_inf.png`` (the upsampled input the
 model is conditioned on, the reference's 'INF' visual) and ``{step}_{idx}_sr.png`` (the sample) into ``path.results``
@@ -51,9 +54,18 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=None)
     ap.add_argument('--sample-seed', type=int, default=None,
                     help='per-sample noise streams: image k of the validation set draws from the stream (seed, k)')
+    ap.add_argument('--solver', type=str, default=None, choices=['ddim', 'dpmpp2m'],
+                    help='few-step sampling over --solver-steps timesteps of the trained schedule')
+    ap.add_argument('--solver-steps', type=int, default=None)
+    ap.add_argument('--eta', type=float, default=0.0, help='ddim only: 0 deterministic .. 1 ancestral variance')
+    ap.add_argument('--spacing', type=str, default=None, choices=['uniform', 'logsnr'])
     args = ap.parse_args(argv)
     if args.batch < 1:
         raise SystemExit('--batch must be >= 1')
+    if args.solver is None and (args.solver_steps is not None or args.eta != 0.0 or args.spacing is not None):
+        raise SystemExit('--solver-steps, --eta and --spacing belong to --solver')
+    if args.solver is not None and args.solver_steps is None:
+        raise SystemExit('--solver needs --solver-steps')
     opt = Logger.parse(args)
     logging.basicConfig(level=logging.INFO, format='%(asctime)s %(message)s')
     log = logging.getLogger('base')
@@ -83,6 +95,8 @@ def main(argv=None):
     diffusion = create_model(opt)
     log.info('Initial Model Finished')
     diffusion.set_new_noise_schedule(opt['model']['beta_schedule']['val'], schedule_phase='val')
+    if args.solver is not None:                               # refused by name for a sampler that is not Gaussian
+        diffusion.set_solver(args.solver, steps=args.solver_steps, eta=args.eta, spacing=args.spacing)
 
     log.info('Begin Model Inference.')
     current_step = 0

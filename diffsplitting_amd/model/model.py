@@ -9,7 +9,8 @@ from collections import OrderedDict
 
 import torch
 
-from . import networks
+from .._lib import DsxError
+from . import networks, solvers
 from .base_model import BaseModel
 
 logger = logging.getLogger("base")
@@ -49,12 +50,33 @@ class DDPM(BaseModel):
         x = self.data["input"]
         skw = {} if sample_ids is None and seed is None else dict(seed=seed, sample_ids=sample_ids)
         with torch.no_grad():
-            if hasattr(self.netG, "inference"):
+            if self.solver is not None:
+                self.prediction = self.netG.solver_sample_loop(x, clip_denoised=clip_denoised, continous=continuous,
+                                                               **self.solver, **skw)
+            elif hasattr(self.netG, "inference"):
                 self.prediction = self.netG.inference(x, continuous=continuous, **skw)   # model.py:63-76
             elif hasattr(self.netG, "super_resolution"):
                 self.prediction = self.netG.super_resolution(x, clip_denoised=clip_denoised, continous=continuous, **skw)
             else:
                 self.prediction = self.netG.predict(x, clip_denoised=clip_denoised, continous=continuous, **skw)
+
+    solver = None                     # set_solver: the keywords of solver_sample_loop that test() passes on
+
+    def set_solver(self, solver=None, steps=None, eta=0.0, spacing=None):
+        """``test()`` samples with a few-step solver ("ddim" / "dpmpp2m", ``model/solvers.py``) over ``steps`` timesteps
+        of the trained schedule; ``solver=None`` (the default state) restores the sampler's own loop."""
+        if solver is None:
+            self.solver = None
+            return
+        if not hasattr(self.netG, "solver_sample_loop"):
+            raise DsxError(f"set_solver: {type(self.netG).__name__} is not a Gaussian sampler (sr3 / ddpm); InDI's "
+                           "loop already takes num_timesteps")
+        if steps is None:
+            raise DsxError("set_solver: a solver needs steps=")
+        solvers.check_solver(solver, eta)
+        if spacing is not None and spacing not in solvers.SPACINGS:
+            raise DsxError(f"set_solver: spacing must be one of {solvers.SPACINGS}, got {spacing!r}")
+        self.solver = dict(solver=solver, steps=int(steps), eta=float(eta), spacing=spacing)
 
     def sample(self, batch_size=1, continous=False):
         self.netG.eval()

@@ -19,6 +19,10 @@ the single steps keep the reference's signatures and have the siblings ``p_sampl
 Every draw of sample ``b`` -- the initial state, draw 0, and step ``s``, draw ``s + 1`` -- then is a function of
 ``(seed, sample_ids[b], draw, element)`` alone: the same whatever batch, batch position or rank the sample runs in.
 torch's generator is not touched, and a ``noise_source`` together with ids is refused.
+
+Few-step sampling (Gaussian samplers only): ``solver_sample_loop`` runs a sub-sequence of the trained schedule with
+DDIM(eta) or DPM-Solver++(2M) rows (``model/solvers.py``) through ``UNetEngine.solver_loop``; ``p_sample_loop`` and
+the other methods keep their parameter lists.
 """
 import numpy as np
 import torch
@@ -26,6 +30,7 @@ from torch import nn
 
 from .. import engine
 from .._lib import DsxError
+from . import solvers
 
 
 class _SamplerBase(nn.Module):
@@ -176,6 +181,7 @@ class GaussianSampler(_SamplerBase):
                 delattr(self, k)
             self.register_buffer(k, v.to(device))
         self._bufs_cpu, self._table = bufs, {}
+        self._ac64 = solvers.alphas_cumprod_f64(schedule_opt)    # float64: the few-step solvers' rows start from it
 
     def _step_table(self, clip):
         if clip not in self._table:
@@ -194,18 +200,7 @@ class GaussianSampler(_SamplerBase):
         self._need_schedule()
         dev = self.betas.device
         T = self.num_timesteps
-        if not self.conditional:
-            shape, cond = tuple(x_in), None
-        else:
-            cond = x_in.to(dev).float()
-            shape = (cond.shape[0], self.channels) + tuple(cond.shape[2:])
-        streams = self._stream_args(seed, sample_ids, shape[0])
-        if streams is None:
-            img = self._draw(shape, dev)
-        else:
-            img = engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
-        # the loop updates `img` in place: keep a copy of the initial noise for ret_img[0] (sr3 diffusion.py:183-185)
-        first = (img.clone() if continous else None) if cond is None else cond.repeat((1, self.channels // cond.shape[1], 1, 1))
+        cond, shape, streams, img, first = self._loop_start(x_in, continous, seed, sample_ids)
         noise = None
         if self.noise_source is not None:  # reference draw order: one per step, none at t == 0 (sr3)
             n_draw = T - 1 if self.kind == "sr3" else T
@@ -222,6 +217,64 @@ class GaussianSampler(_SamplerBase):
         if continous:
             return torch.cat([first] + [s for s in sn], dim=0)
         return x[-1]                                                 # diffusion.py:200-203: ret_img[-1]
+
+    def _loop_start(self, x_in, continous, seed, sample_ids):
+        """What a reverse loop starts from: (cond, state shape, stream arguments or None, initial state, ret_img[0])."""
+        dev = self.betas.device
+        if not self.conditional:
+            shape, cond = tuple(x_in), None
+        else:
+            cond = x_in.to(dev).float()
+            shape = (cond.shape[0], self.channels) + tuple(cond.shape[2:])
+        streams = self._stream_args(seed, sample_ids, shape[0])
+        if streams is None:
+            img = self._draw(shape, dev)
+        else:
+            img = engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
+        # the loop updates `img` in place: keep a copy of the initial noise for ret_img[0] (sr3 diffusion.py:183-185)
+        first = (img.clone() if continous else None) if cond is None else cond.repeat((1, self.channels // cond.shape[1], 1, 1))
+        return cond, shape, streams, img, first
+
+    def solver_table(self, steps=50, solver="dpmpp2m", eta=0.0, spacing=None, timesteps=None, clip_denoised=True):
+        """The rows ``solver_sample_loop`` runs (``model/solvers.py``): a ``SolverTableHost`` with its ``timesteps``."""
+        self._need_schedule()
+        return solvers.solver_table(self._bufs_cpu, self.sqrt_alphas_cumprod_prev, self.kind, self._ac64, solver=solver,
+                                    steps=None if timesteps is not None else steps, eta=eta, spacing=spacing,
+                                    timesteps=timesteps, clip_denoised=bool(clip_denoised))
+
+    @torch.no_grad()
+    def solver_sample_loop(self, x_in, steps=50, solver="dpmpp2m", eta=0.0, spacing=None, timesteps=None,
+                           clip_denoised=True, continous=False, seed=None, sample_ids=None):
+        """Few-step sampling over a sub-sequence of the trained schedule: ``solver`` "ddim" (deterministic, or stochastic
+        with ``eta`` in (0, 1]) or "dpmpp2m" (DPM-Solver++(2M), second order).  The run is ``timesteps`` (strictly
+        descending) or ``steps`` timesteps spaced by ``spacing`` ("uniform" / "logsnr"; default: logsnr for dpmpp2m,
+        uniform for ddim).  Initial state, ``noise_source``, ``seed`` / ``sample_ids`` and the return value as
+        ``p_sample_loop``; ``continous=True`` returns the start followed by the state after every row."""
+        table = self.solver_table(steps, solver, eta, spacing, timesteps, clip_denoised)
+        if self.conditional:
+            self._need_cuda(x_in, what="solver_sample_loop")
+        dev = self.betas.device
+        cond, shape, streams, img, first = self._loop_start(x_in, continous, seed, sample_ids)
+        K = table.n_steps
+        draws = [s for s in range(K) if table.sigma[s] != 0]         # ddim with eta > 0: one per row but the last
+        noise = None
+        if self.noise_source is not None and draws:
+            noise = torch.zeros((K,) + shape, device=dev)
+            for s in draws:
+                noise[s] = self._draw(shape, dev)
+        if streams is not None:
+            skw = dict(seed=streams[0], sample_ids=streams[1])
+        else:
+            skw = dict(seed=self._seed() if draws else 0)
+        x, sn = self.denoise_fn.engine().solver_loop(table, img, cond=cond, noise=noise,
+                                                     snapshot_steps=range(K) if continous else (),
+                                                     use_graph=self.use_graph, **skw)
+        self.last_full_batch = x
+        if self.kind == "ddpm" and not self.conditional:
+            return x
+        if continous:
+            return torch.cat([first] + [s for s in sn], dim=0)
+        return x[-1]
 
     @torch.no_grad()
     def sample(self, batch_size=1, continous=False, seed=None, sample_ids=None):

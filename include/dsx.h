@@ -424,6 +424,53 @@ int dsx_posterior_step_streams(const float* x_dev, const float* net_dev, int B, 
                                float* x_recon_out_dev, float* mean_out_dev, float* x_out_dev, void* stream,
                                const uint64_t* sample_ids_host, int n_sample_ids);
 
+/* ------------------------------------------------------- few-step solvers (additive under DSX_ABI_VERSION 2)
+ * DDIM and DPM-Solver++(2M, data prediction) over a sub-sequence of the trained schedule.  The host builds one row per
+ * step (diffsplitting_amd/model/solvers.py, float64 rounded to fp32 once); the device evaluates, every product and sum
+ * rounded separately,
+ *   x0  = a*x - b*eps, clamped to +-1 if clip            (dsx_step_table's expression with predict_eps = 1)
+ *   m   = c0*x0 + cx*x
+ *   m   = cp != 0 ? m + cp*x0_prev : m                   (x0_prev: the x0 of the previous step; not read when cp == 0)
+ *   x  <- m + sigma*z                                    (noise rules as in dsx_sample_loop / dsx_posterior_step)
+ * With cp == 0 a row is the row (c1 = c0, c2 = cx) of dsx_step_table, bit for bit: DDIM rows through dsx_solver_loop
+ * and through dsx_sample_loop give the same bits.
+ *
+ * dsx_solver_loop: dsx_sample_loop over such rows.  The previous x0 lives in a device buffer the executor allocates at
+ * the first call and keeps (outside the workspace: dsx_exec_workspace_bytes does not change); the captured step differs
+ * from the ancestral one, and an executor that alternates between the two loops recaptures.  cp[0] must be 0 (no
+ * previous x0 at the first step).  sample_ids_host == NULL: the default noise (noise_nchw_dev or Philox (seed, step + 1));
+ * else B ids of the per-sample noise streams, as in dsx_sample_loop_streams.
+ *
+ * dsx_solver_step: one update on NCHW tensors with per-sample coefficients (device arrays of B values each), the
+ * solver sibling of dsx_posterior_step.  x0_prev_dev: (B, C, H, W), read only for the samples whose cp != 0, or NULL
+ * (every cp then counts as 0; cp_dev may be NULL too).  x_recon_out_dev receives x0 -- the next call's x0_prev_dev, it
+ * may be the very buffer -- and x_out_dev the new state (it may be x_dev); both are required.  z_dev: injected draws or
+ * NULL -> the stream (seed, subsequence); with sample_ids_host the sample streams (seed, sample_ids[b], draw) and z_dev
+ * must be NULL.  A caller-driven chain of dsx_unet_forward and this call reproduces dsx_solver_loop bit for bit. */
+typedef struct dsx_solver_table {
+  int32_t n_steps;
+  int32_t clip;
+  const float* tcond;   /* host, n_steps each */
+  const float* a;
+  const float* b;
+  const float* cx;
+  const float* c0;
+  const float* cp;
+  const float* sigma;
+} dsx_solver_table;
+int dsx_solver_loop(dsx_exec* ex, const dsx_solver_table* tab,
+                    const float* cond_nchw_dev, float* x_nchw_dev,
+                    const float* noise_nchw_dev, uint64_t seed,
+                    const int32_t* snap_steps, int n_snap, float* snap_nchw_dev,
+                    int use_graph, void* stream,
+                    const uint64_t* sample_ids_host, int n_sample_ids);
+int dsx_solver_step(const float* x_dev, const float* net_dev, const float* x0_prev_dev, int B, int C, int H, int W,
+                    const float* a_dev, const float* b_dev, const float* cx_dev, const float* c0_dev,
+                    const float* cp_dev, const float* sigma_dev, int clip,
+                    const float* z_dev, uint64_t seed, uint64_t subsequence,
+                    float* x_recon_out_dev, float* x_out_dev, void* stream,
+                    const uint64_t* sample_ids_host, int n_sample_ids, uint32_t draw);
+
 /* ----------------------------------------------------------------- tiling */
 
 enum { DSX_TILING_TRIM = 0, DSX_TILING_PAD = 1, DSX_TILING_SHIFT = 2 };  /* tiling_manager.py:6-12 */
