@@ -152,16 +152,14 @@ extern "C" int dsx_exec_profile(dsx_exec* ex, int iters, float* ms_per_op, void*
   return DSX_OK;
 }
 
-// time embedding + UNet body on `st`; inputs already in ex->in_cond / ex->in_x.  tcond_table: the device column of
-// per-step time values read at the step counter (nullptr: the step table's own)
-static int run_unet(dsx_exec* ex, bool from_table, int n_time, hipStream_t st, int per_sample = 0,
-                    const float* tcond_table = nullptr) {
+// time embedding + UNet body on `st`; inputs already in ex->in_cond / ex->in_x
+static int run_unet(dsx_exec* ex, bool from_table, int n_time, hipStream_t st, int per_sample = 0) {
   dsx_model* m = ex->m;
   if (m->cfg.with_time_emb) {
     TembArgs t{};
     t.flavour = m->cfg.flavour; t.B = ex->B; t.n_time = n_time;
     t.time = from_table ? nullptr : ex->time_buf;
-    t.table = tcond_table ? tcond_table : ex->table.as<float>(); t.step_ctr = ex->step_ctr; t.per_sample = per_sample;
+    t.table = ex->table.as<float>(); t.step_ctr = ex->step_ctr; t.per_sample = per_sample;
     t.inner = m->cfg.inner_channel; t.freq = m->d_freq;
     t.w1 = m->d_w1; t.b1 = m->d_b1; t.w2 = m->d_w2; t.b2 = m->d_b2;
     t.wf = m->d_wf; t.bf = m->d_bf; t.F = m->F; t.film = ex->film;
@@ -208,23 +206,24 @@ static int load_inputs(dsx_exec* ex, const float* cond_nchw, const float* x_nchw
 }
 
 // ------------------------------------------------------------------ sampler
-static int ensure_table(dsx_exec* ex, const dsx_step_table* tab) {
-  const int T = tab->n_steps * (tab->per_sample > 0 ? tab->per_sample : 1);   // values per column
+// the device table [kUpdateCols][cap] holds T values per column
+static int ensure_table(dsx_exec* ex, int T) {
   if (T > ex->table_cap) {
     // the table's column stride (= capacity) is baked into captured graphs: drop them
     const int rc = drop_graph(ex);
     if (rc) return rc;
     const int cap = std::max(T, 2048);
-    HIP_TRY(ex->table.alloc((size_t)6 * cap * sizeof(float)));
+    HIP_TRY(ex->table.alloc((size_t)kUpdateCols * cap * sizeof(float)));
     ex->table_cap = cap;
   }
   return DSX_OK;
 }
 
-// a pinned staging slot holding this call's table [ncols][cap] (T values per column; a null column stays zero)
+// a pinned staging slot holding this call's table [kUpdateCols][cap] (T values per column; a null column stays zero)
 // followed by {seed, noise address} and, with per-sample noise streams, the B sample ids; *out = its host pointer
-static int stage_call(dsx_exec* ex, const float* const* cols, int ncols, int T, int cap, uint64_t seed, const float* noise,
+static int stage_call(dsx_exec* ex, const float* const* cols, int T, uint64_t seed, const float* noise,
                       const uint64_t* ids, dsx_exec::Staging** out) {
+  const int ncols = kUpdateCols, cap = ex->table_cap;
   const size_t need = (size_t)ncols * cap + 4 + (ids ? (size_t)2 * ex->B : 0);   // + 16 bytes of loop parameters (+ ids)
   dsx_exec::Staging& sl = ex->staging[ex->staging_next];
   ex->staging_next = (ex->staging_next + 1) % 4;
@@ -246,9 +245,10 @@ static int stage_call(dsx_exec* ex, const float* const* cols, int ncols, int T, 
   return DSX_OK;
 }
 // the staged call -> device memory on `st`: the table, the loop parameters, the ids, the step counter
-static int upload_call(dsx_exec* ex, dsx_exec::Staging* sl, void* table_dev, int ncols, int cap, bool ids, hipStream_t st) {
+static int upload_call(dsx_exec* ex, dsx_exec::Staging* sl, bool ids, hipStream_t st) {
+  const int ncols = kUpdateCols, cap = ex->table_cap;
   const float* host = sl->host.as<float>();
-  HIP_TRY(hipMemcpyAsync(table_dev, host, (size_t)ncols * cap * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ex->table.p, host, (size_t)ncols * cap * 4, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(ex->loop_params, host + (size_t)ncols * cap, 16, hipMemcpyHostToDevice, st));
   if (ids)
     HIP_TRY(hipMemcpyAsync(ex->sample_ids.p, host + (size_t)ncols * cap + 4, (size_t)ex->B * 8, hipMemcpyHostToDevice, st));
@@ -258,16 +258,27 @@ static int upload_call(dsx_exec* ex, dsx_exec::Staging* sl, void* table_dev, int
   return DSX_OK;
 }
 
-static int enqueue_step(dsx_exec* ex, const dsx_step_table* tab, bool use_noise, bool streams, hipStream_t st) {
-  int rc = run_unet(ex, true, tab->per_sample > 0 ? ex->B : 1, st, tab->per_sample > 0 ? 1 : 0);
+// what a captured step bakes in (not the step count, the seed, the noise address or the sample ids): also the graph's
+// signature, so a DDIM table through dsx_sample_loop and through dsx_solver_loop capture separate graphs
+struct LoopMode {
+  int predict_eps, clip, per_sample;
+  int history;        // the few-step solvers' x0 history (ex->solver_hist) is read and written
+  int use_noise, streams;
+  std::vector<float> sig() const {
+    return {(float)predict_eps, (float)clip, (float)use_noise, (float)per_sample, (float)streams, (float)history};
+  }
+};
+static int enqueue_step(dsx_exec* ex, const LoopMode& m, hipStream_t st) {
+  int rc = run_unet(ex, true, m.per_sample ? ex->B : 1, st, m.per_sample);
   if (rc) return rc;
   UpdateArgs u{};
   u.x = ex->x_state; u.x_act = ex->in_x.st ? ex->in_x.p : nullptr; u.x_act_kind = ex->in_x.st;
-  u.net = (const float*)ex->out.p; u.use_noise = use_noise ? 1 : 0; u.loop_params = ex->loop_params;
+  u.net = (const float*)ex->out.p; u.x0_hist = m.history ? ex->solver_hist.as<float>() : nullptr;
+  u.use_noise = m.use_noise; u.loop_params = ex->loop_params;
   u.tab = ex->table.as<float>(); u.n_steps = ex->table_cap; u.step_ctr = ex->step_ctr;
-  u.predict_eps = tab->predict_eps; u.clip = tab->clip; u.per_sample = tab->per_sample > 0 ? 1 : 0;
+  u.predict_eps = m.predict_eps; u.clip = m.clip; u.per_sample = m.per_sample;
   u.B = ex->B; u.C = ex->x_c; u.H = ex->H; u.W = ex->W;
-  u.sample_ids = streams ? ex->sample_ids.as<unsigned long long>() : nullptr;   // the executor's buffer, not the ids
+  u.sample_ids = m.streams ? ex->sample_ids.as<unsigned long long>() : nullptr;   // the executor's buffer, not the ids
   HIP_TRY(launch_update(u, st));
   HIP_TRY(launch_advance(ex->step_ctr, st));
   return DSX_OK;
@@ -320,8 +331,29 @@ static int replay_steps(dsx_exec* ex, const std::vector<float>& sig, Step&& step
   return DSX_OK;
 }
 
-// ids == nullptr: the default noise (one stream per step at the flat batch index); else B sample ids, checked by
-// the caller
+// The loop behind dsx_sample_loop, dsx_sample_loop_streams and dsx_solver_loop, which check their own arguments.
+// cols: the kUpdateCols host columns in the table's order, `rows` values each (a null column counts as zeros); T steps.
+// ids == nullptr: the default noise (one stream per step at the flat batch index); else B sample ids.
+static int run_loop(dsx_exec* ex, const float* const* cols, int T, int rows, LoopMode m, const float* cond, float* x,
+                    const float* noise, uint64_t seed, const uint64_t* ids, const int32_t* snap_steps, int n_snap,
+                    float* snaps, int use_graph, hipStream_t st) {
+  if (m.history && m.per_sample) return fail(DSX_ERR_INVALID, "x0 history with a per_sample table");
+  m.use_noise = noise ? 1 : 0; m.streams = ids ? 1 : 0;
+  int rc = ensure_table(ex, rows);
+  if (rc) return rc;
+  // once each, outside the workspace: captured steps keep the addresses
+  if (m.history && !ex->solver_hist.p) HIP_TRY(ex->solver_hist.alloc((size_t)ex->B * ex->x_c * ex->H * ex->W * sizeof(float)));
+  if (ids && !ex->sample_ids.p) HIP_TRY(ex->sample_ids.alloc((size_t)ex->B * 8));
+  // per-call values (step table; seed, noise address: the captured step does not bake them in) go to device memory
+  // from a pinned staging slot of this call's own
+  dsx_exec::Staging* sl = nullptr;
+  if ((rc = stage_call(ex, cols, rows, seed, noise, ids, &sl))) return rc;
+  if ((rc = upload_call(ex, sl, ids != nullptr, st))) return rc;
+  if ((rc = load_inputs(ex, cond, x, ex->x_c, 0, st))) return rc;
+  return replay_steps(ex, m.sig(), [&](hipStream_t s) { return enqueue_step(ex, m, s); }, T, snap_steps, n_snap, snaps, x,
+                      use_graph, st);
+}
+
 static int sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x, const float* noise,
                        uint64_t seed, const int32_t* snap_steps, int n_snap, float* snaps, int use_graph, void* stream,
                        const uint64_t* ids) {
@@ -333,24 +365,11 @@ static int sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* con
   if (n_snap > 0 && (!snap_steps || !snaps)) return fail(DSX_ERR_INVALID, "snapshot arrays missing");
   if (tab->per_sample != 0 && tab->per_sample != ex->B)
     return fail(DSX_ERR_INVALID, "per_sample step table for %d samples, executor batch %d", tab->per_sample, ex->B);
-  hipStream_t st = (hipStream_t)stream;
-  const int T = tab->n_steps;
-  int rc = ensure_table(ex, tab);
-  if (rc) return rc;
-  // per-call values (step table; seed, noise address: the captured step does not bake them in) go to device memory
-  // from a pinned staging slot of this call's own
-  dsx_exec::Staging* sl = nullptr;
-  if (ids && !ex->sample_ids.p) HIP_TRY(ex->sample_ids.alloc((size_t)ex->B * 8));   // once: captured steps keep the address
-  const float* cols[6] = {tab->tcond, tab->a, tab->b, tab->c1, tab->c2, tab->sigma};
+  const float* cols[kUpdateCols] = {tab->tcond, tab->a, tab->b, tab->c1, tab->c2, nullptr, tab->sigma};   // cp: zeros
   const int per = tab->per_sample > 0 ? tab->per_sample : 1;
-  if ((rc = stage_call(ex, cols, 6, T * per, ex->table_cap, seed, noise, ids, &sl))) return rc;
-  if ((rc = upload_call(ex, sl, ex->table.p, 6, ex->table_cap, ids != nullptr, st))) return rc;
-  if ((rc = load_inputs(ex, cond, x, ex->x_c, 0, st))) return rc;
-  // the captured step bakes in the mode flags only (not the step count, the seed, the noise address or the sample ids)
-  const std::vector<float> sig = {(float)tab->predict_eps, (float)tab->clip, noise ? 1.f : 0.f, tab->per_sample > 0 ? 1.f : 0.f,
-                                  ids ? 1.f : 0.f};
-  return replay_steps(ex, sig, [&](hipStream_t s) { return enqueue_step(ex, tab, noise != nullptr, ids != nullptr, s); }, T,
-                      snap_steps, n_snap, snaps, x, use_graph, st);
+  const LoopMode m{tab->predict_eps, tab->clip, tab->per_sample > 0 ? 1 : 0, 0, 0, 0};
+  return run_loop(ex, cols, tab->n_steps, tab->n_steps * per, m, cond, x, noise, seed, ids, snap_steps, n_snap, snaps,
+                  use_graph, (hipStream_t)stream);
 }
 
 extern "C" int dsx_sample_loop(dsx_exec* ex, const dsx_step_table* tab, const float* cond, float* x,
@@ -382,23 +401,7 @@ extern "C" int dsx_sample_loop_streams(dsx_exec* ex, const dsx_step_table* tab, 
   return sample_loop(ex, tab, cond, x, nullptr, seed, snap_steps, n_snap, snaps, use_graph, stream, sample_ids);
 }
 
-// ---- few-step solvers (include/dsx.h): sample_loop with a 7-column table of its own and k_solver_update as the update
-static int enqueue_solver_step(dsx_exec* ex, int clip, bool use_noise, bool streams, hipStream_t st) {
-  int rc = run_unet(ex, true, 1, st, 0, ex->solver_table.as<float>());   // column 0 of the solver table: tcond
-  if (rc) return rc;
-  SolverUpdateArgs u{};
-  u.x = ex->x_state; u.x_act = ex->in_x.st ? ex->in_x.p : nullptr; u.x_act_kind = ex->in_x.st;
-  u.net = (const float*)ex->out.p; u.x0_hist = ex->solver_hist.as<float>();
-  u.use_noise = use_noise ? 1 : 0; u.loop_params = ex->loop_params;
-  u.tab = ex->solver_table.as<float>(); u.n_steps = ex->solver_cap; u.step_ctr = ex->step_ctr;
-  u.clip = clip;
-  u.B = ex->B; u.C = ex->x_c; u.H = ex->H; u.W = ex->W;
-  u.sample_ids = streams ? ex->sample_ids.as<unsigned long long>() : nullptr;
-  HIP_TRY(launch_solver_update(u, st));
-  HIP_TRY(launch_advance(ex->step_ctr, st));
-  return DSX_OK;
-}
-
+// ---- few-step solvers (include/dsx.h): the same loop with the x0 history; step_update's c1 = c0, c2 = cx
 extern "C" int dsx_solver_loop(dsx_exec* ex, const dsx_solver_table* tab, const float* cond, float* x, const float* noise,
                                uint64_t seed, const int32_t* snap_steps, int n_snap, float* snaps, int use_graph,
                                void* stream, const uint64_t* sample_ids, int n_sample_ids) {
@@ -416,29 +419,10 @@ extern "C" int dsx_solver_loop(dsx_exec* ex, const dsx_solver_table* tab, const 
     const int rc = stream_ids_ok("solver_loop", sample_ids, n_sample_ids, ex->B, (uint64_t)tab->n_steps);
     if (rc) return rc;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const int T = tab->n_steps;
-  int rc = DSX_OK;
-  if (T > ex->solver_cap) {   // the table's column stride (= capacity) is baked into captured graphs: drop them
-    if ((rc = drop_graph(ex))) return rc;
-    const int cap = std::max(T, 256);
-    HIP_TRY(ex->solver_table.alloc((size_t)kSolverCols * cap * sizeof(float)));
-    ex->solver_cap = cap;
-  }
-  // once each, outside the workspace: captured steps keep the addresses
-  if (!ex->solver_hist.p) HIP_TRY(ex->solver_hist.alloc((size_t)ex->B * ex->x_c * ex->H * ex->W * sizeof(float)));
-  if (sample_ids && !ex->sample_ids.p) HIP_TRY(ex->sample_ids.alloc((size_t)ex->B * 8));
-  dsx_exec::Staging* sl = nullptr;
-  const float* cols[kSolverCols] = {tab->tcond, tab->a, tab->b, tab->cx, tab->c0, tab->cp, tab->sigma};
-  if ((rc = stage_call(ex, cols, kSolverCols, T, ex->solver_cap, seed, noise, sample_ids, &sl))) return rc;
-  if ((rc = upload_call(ex, sl, ex->solver_table.p, kSolverCols, ex->solver_cap, sample_ids != nullptr, st))) return rc;
-  if ((rc = load_inputs(ex, cond, x, ex->x_c, 0, st))) return rc;
-  // first entry 2: no ancestral signature (its first entry is predict_eps, 0 or 1) equals a solver signature
-  const bool use_noise = noise != nullptr, streams = sample_ids != nullptr;
-  const int clip = tab->clip ? 1 : 0;
-  const std::vector<float> sig = {2.f, (float)clip, use_noise ? 1.f : 0.f, 0.f, streams ? 1.f : 0.f};
-  return replay_steps(ex, sig, [&](hipStream_t s) { return enqueue_solver_step(ex, clip, use_noise, streams, s); }, T,
-                      snap_steps, n_snap, snaps, x, use_graph, st);
+  const float* cols[kUpdateCols] = {tab->tcond, tab->a, tab->b, tab->c0, tab->cx, tab->cp, tab->sigma};
+  const LoopMode m{1, tab->clip ? 1 : 0, 0, 1, 0, 0};
+  return run_loop(ex, cols, tab->n_steps, tab->n_steps, m, cond, x, noise, seed, sample_ids, snap_steps, n_snap, snaps,
+                  use_graph, (hipStream_t)stream);
 }
 
 extern "C" int dsx_randn_samples(float* out, int B, int64_t chw, uint64_t seed, const uint64_t* ids, uint32_t draw,
@@ -447,12 +431,9 @@ extern "C" int dsx_randn_samples(float* out, int B, int64_t chw, uint64_t seed, 
   if ((int64_t)B * chw > ((int64_t)1 << 40)) return fail(DSX_ERR_INVALID, "randn_samples: tensor too large");
   const int rc = stream_ids_ok("randn_samples", ids, B, B, draw);
   if (rc) return rc;
-  for (int b0 = 0; b0 < B; b0 += kStreamRows) {     // the ids travel in the kernel arguments, kStreamRows per launch
-    StreamIds s{};
-    const int rows = std::min(B - b0, kStreamRows);
-    for (int r = 0; r < rows; ++r) s.subseq[r] = (ids[b0 + r] << 24) | draw;
-    HIP_TRY(launch_randn_samples(out + (size_t)b0 * chw, rows, chw, seed, s, (hipStream_t)stream));
-  }
+  HIP_TRY(each_stream_chunk(B, ids, draw, [&](int b0, int rows, const StreamIds& s) {   // the ids travel in the kernel arguments
+    return launch_randn_samples(out + (size_t)b0 * chw, rows, chw, seed, s, (hipStream_t)stream);
+  }));
   return DSX_OK;
 }
 
@@ -563,9 +544,9 @@ extern "C" int dsx_posterior_step(const float* x, const float* net, int B, int C
   if (!x || !net || !c1 || !c2 || !sigma) return fail(DSX_ERR_INVALID, "posterior_step: null argument");
   if (predict_eps && (!a || !b)) return fail(DSX_ERR_INVALID, "posterior_step: predict_eps needs the columns a and b");
   if (!x_recon_out && !mean_out && !x_out) return fail(DSX_ERR_INVALID, "posterior_step: every output is null");
-  PosteriorStepArgs p{x, net, a, b, c1, c2, sigma, x_out ? z : nullptr, seed, subseq, x_recon_out, mean_out, x_out,
-                      B, predict_eps ? 1 : 0, clip ? 1 : 0, repeat_noise ? 1 : 0, (int64_t)C * H * W};
-  HIP_TRY(launch_posterior_step(p, (int64_t)H * W, (hipStream_t)stream));
+  const StepArgs p{x, net, nullptr, a, b, c1, c2, nullptr, sigma, x_out ? z : nullptr, seed, subseq, x_recon_out, mean_out, x_out,
+                   B, predict_eps ? 1 : 0, clip ? 1 : 0, repeat_noise ? 1 : 0, (int64_t)C * H * W};
+  HIP_TRY(launch_step(p, (int64_t)H * W, nullptr, 0, (hipStream_t)stream));
   return DSX_OK;
 }
 extern "C" int dsx_posterior_step_streams(const float* x, const float* net, int B, int C, int H, int W, const float* a,
@@ -581,22 +562,13 @@ extern "C" int dsx_posterior_step_streams(const float* x, const float* net, int 
   if (!x || !net || !c1 || !c2 || !sigma) return fail(DSX_ERR_INVALID, "posterior_step_streams: null argument");
   if (predict_eps && (!a || !b)) return fail(DSX_ERR_INVALID, "posterior_step_streams: predict_eps needs the columns a and b");
   if (!x_recon_out && !mean_out && !x_out) return fail(DSX_ERR_INVALID, "posterior_step_streams: every output is null");
-  const int64_t CHW = (int64_t)C * H * W;
-  for (int b0 = 0; b0 < B; b0 += kStreamRows) {     // kStreamRows samples per launch: their ids are kernel arguments
-    StreamIds s{};
-    const int rows = std::min(B - b0, kStreamRows);
-    for (int r = 0; r < rows; ++r) s.subseq[r] = (sample_ids[b0 + r] << 24) | draw;
-    const size_t off = (size_t)b0 * CHW;
-    auto at = [&](float* p) { return p ? p + off : nullptr; };
-    PosteriorStepArgs p{x + off, net + off, a ? a + b0 : nullptr, b ? b + b0 : nullptr, c1 + b0, c2 + b0, sigma + b0,
-                        nullptr, seed, 0, at(x_recon_out), at(mean_out), at(x_out),
-                        rows, predict_eps ? 1 : 0, clip ? 1 : 0, 0, CHW};
-    HIP_TRY(launch_posterior_step_streams(p, s, (int64_t)H * W, (hipStream_t)stream));
-  }
+  const StepArgs p{x, net, nullptr, a, b, c1, c2, nullptr, sigma, nullptr, seed, 0, x_recon_out, mean_out, x_out,
+                   B, predict_eps ? 1 : 0, clip ? 1 : 0, 0, (int64_t)C * H * W};
+  HIP_TRY(launch_step(p, (int64_t)H * W, sample_ids, draw, (hipStream_t)stream));
   return DSX_OK;
 }
-// one solver update (k_solver_step): sample_ids == nullptr -> z_dev or the stream (seed, subsequence); else the sample
-// streams (seed, sample_ids[b], draw)
+// one solver update: step_update's c1 = c0, c2 = cx.  sample_ids == nullptr -> z_dev or the stream (seed, subsequence);
+// else the sample streams (seed, sample_ids[b], draw)
 extern "C" int dsx_solver_step(const float* x, const float* net, const float* x0_prev, int B, int C, int H, int W,
                                const float* a, const float* b, const float* cx, const float* c0, const float* cp,
                                const float* sigma, int clip, const float* z, uint64_t seed, uint64_t subsequence,
@@ -611,22 +583,9 @@ extern "C" int dsx_solver_step(const float* x, const float* net, const float* x0
   if (!x || !net || !a || !b || !cx || !c0 || !sigma) return fail(DSX_ERR_INVALID, "solver_step: null argument");
   if (x0_prev && !cp) return fail(DSX_ERR_INVALID, "solver_step: x0_prev without the column cp");
   if (!x_recon_out || !x_out) return fail(DSX_ERR_INVALID, "solver_step: null output");
-  const int64_t CHW = (int64_t)C * H * W;
-  if (!sample_ids) {
-    SolverStepArgs p{x, net, x0_prev, a, b, cx, c0, cp, sigma, z, seed, subsequence, x_recon_out, x_out, B, clip ? 1 : 0, CHW};
-    HIP_TRY(launch_solver_step(p, (int64_t)H * W, (hipStream_t)stream));
-    return DSX_OK;
-  }
-  for (int b0 = 0; b0 < B; b0 += kStreamRows) {     // kStreamRows samples per launch: their ids are kernel arguments
-    StreamIds s{};
-    const int rows = std::min(B - b0, kStreamRows);
-    for (int r = 0; r < rows; ++r) s.subseq[r] = (sample_ids[b0 + r] << 24) | draw;
-    const size_t off = (size_t)b0 * CHW;
-    SolverStepArgs p{x + off, net + off, x0_prev ? x0_prev + off : nullptr, a + b0, b + b0, cx + b0, c0 + b0,
-                     cp ? cp + b0 : nullptr, sigma + b0, nullptr, seed, 0, x_recon_out + off, x_out + off,
-                     rows, clip ? 1 : 0, CHW};
-    HIP_TRY(launch_solver_step_streams(p, s, (int64_t)H * W, (hipStream_t)stream));
-  }
+  const StepArgs p{x, net, x0_prev, a, b, c0, cx, cp, sigma, z, seed, subsequence, x_recon_out, nullptr, x_out,
+                   B, 1, clip ? 1 : 0, 0, (int64_t)C * H * W};
+  HIP_TRY(launch_step(p, (int64_t)H * W, sample_ids, draw, (hipStream_t)stream));
   return DSX_OK;
 }
 extern "C" int dsx_interp_start(const float* x1, const float* x2, int B, int C, int H, int W, const float* a0,

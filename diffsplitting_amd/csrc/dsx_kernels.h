@@ -387,22 +387,27 @@ hipError_t launch_nchw_slice_to_nhwc(const float* src, void* dst, int dst_bf16, 
                                      int HW, hipStream_t st);
 hipError_t launch_nhwc_to_nchw(const float* src, float* dst, int B, int C, int H, int W, hipStream_t st);
 
+// The loop update (k_update, dsx_steps.hip): one launch per step of dsx_sample_loop, dsx_sample_loop_streams and
+// dsx_solver_loop.
+constexpr int kUpdateCols = 7;
 struct UpdateArgs {
   float* x;               // state, NHWC [B][H][W][C], always fp32
   void* x_act;            // the first conv's copy of the state in the activation storage type (16-bit builds),
                           // or nullptr when the conv reads `x` itself
   int x_act_kind;         // its storage kind (1 bf16, 2 fp16)
   const float* net;       // UNet output, NHWC
+  float* x0_hist;         // the few-step solvers' previous predicted x0, NHWC fp32 like x: read where the row's cp != 0,
+                          // written at every step; nullptr (ancestral loops): never read and never written
   int use_noise;          // 0 -> Philox normals keyed by (seed, step); 1 -> injected draws
   // per-call values live in device memory so that one captured graph serves every call:
   // loop_params[0] = Philox seed, loop_params[1] = address of the injected noise [steps][B][C][H][W] (NCHW,
   // reference draw order)
   const unsigned long long* loop_params;
-  const float* tab;       // device table [6][n_steps]: tcond,a,b,c1,c2,sigma
+  const float* tab;       // device table [kUpdateCols][n_steps]: tcond,a,b,c1,c2,cp,sigma (step_update's names)
   int n_steps;            // column stride of `tab` (its capacity)
   const int* step_ctr;
   int predict_eps, clip;
-  int per_sample;         // the table columns hold [step][B] values instead of one per step
+  int per_sample;         // the table columns hold [step][B] values instead of one per step (never with x0_hist)
   int B, C, H, W;
   // per-sample noise streams (include/dsx.h): device array of B sample ids, read at every step -> the stream form of
   // the kernel (element (b, c, hw) takes element c*H*W + hw of the stream (seed, ids[b] << 24 | step + 1)); nullptr ->
@@ -410,27 +415,22 @@ struct UpdateArgs {
   const unsigned long long* sample_ids;
 };
 hipError_t launch_update(const UpdateArgs& a, hipStream_t st);
-// dsx_solver.hip.  The loop update of the few-step solvers: k_update with solver_update in place of step_update and the
-// previous step's predicted x0 kept on the device.  The members shared with UpdateArgs mean what they mean there.
-constexpr int kSolverCols = 7;
-struct SolverUpdateArgs {
-  float* x; void* x_act; int x_act_kind;
-  const float* net;
-  float* x0_hist;         // NHWC fp32 like x: read where the row's cp != 0, written at every step
-  int use_noise;
-  const unsigned long long* loop_params;
-  const float* tab;       // device table [kSolverCols][n_steps]: tcond,a,b,cx,c0,cp,sigma
-  int n_steps;
-  const int* step_ctr;
-  int clip;
-  int B, C, H, W;
-  const unsigned long long* sample_ids;
-};
-hipError_t launch_solver_update(const SolverUpdateArgs& a, hipStream_t st);
 // Per-sample noise streams without an executor: the Philox subsequences (id << 24 | draw) of up to kStreamRows samples
 // travel in the kernel arguments; larger batches take several launches.
 constexpr int kStreamRows = 32;
 struct StreamIds { unsigned long long subseq[kStreamRows]; };
+// f(b0, rows, s) for every run of up to kStreamRows samples of a batch: s.subseq[r] = ids[b0 + r] << 24 | draw
+template <class F>
+static inline hipError_t each_stream_chunk(int B, const uint64_t* ids, uint64_t draw, F&& f) {
+  for (int b0 = 0; b0 < B; b0 += kStreamRows) {
+    StreamIds s{};
+    const int rows = B - b0 < kStreamRows ? B - b0 : kStreamRows;
+    for (int r = 0; r < rows; ++r) s.subseq[r] = ((unsigned long long)ids[b0 + r] << 24) | draw;
+    const hipError_t e = f(b0, rows, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 // out (rows, chw): row r = the first chw elements of the stream (seed, s.subseq[r]); rows <= kStreamRows
 hipError_t launch_randn_samples(float* out, int rows, long long chw, unsigned long long seed, const StreamIds& s,
                                 hipStream_t st);
@@ -520,15 +520,20 @@ __device__ __forceinline__ void store4(unsigned short* p, const long long at[4],
 template <class... P>
 static inline bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15u) == 0; }   // nullptr counts as aligned
 
-// The reverse update of every sampler (sr3 diffusion.py:141-175, ddpm diffusion.py:163-203, indi.py:62-69), stated once
-// for the loop (k_update, dsx_ops.hip) and the single steps (k_posterior_step, dsx_steps.hip); every product and sum
-// is rounded on its own, as the reference's ATen op sequence does:
+// The reverse update of every sampler -- ancestral (sr3 diffusion.py:141-175, ddpm diffusion.py:163-203, indi.py:62-69)
+// and few-step (DDIM, DPM-Solver++(2M) in data prediction; model/solvers.py builds the rows) -- stated once for the
+// loop (k_update) and the single step (k_step), both in dsx_steps.hip; every product and sum is rounded on its own, as
+// the reference's ATen op sequence does:
 //   x0   = predict_eps ? clamp(a*x - b*net) : net          (the clamp to +-1 only with clip)
 //   mean = c1*x0 + c2*x
+//   mean = cp != 0 ? mean + cp*x0_prev : mean              (the caller does not load x0_prev where cp == 0)
 //   out  = use_z ? mean + z*sigma : mean
+// An ancestral row is a solver row with cp == 0.  The solver tables (dsx_solver_table, dsx_solver_step) name and order
+// their columns cx, c0: x0's coefficient c0 is c1 here and x's coefficient cx is c2 -- c1 = c0, c2 = cx, the only
+// place where the two orders meet (dsx_solver_loop and dsx_solver_step in dsx_exec.cpp fill c1 / c2 by that rule).
 struct StepVals { float x0, mean, out; };
-__device__ __forceinline__ StepVals step_update(float a, float b, float c1, float c2, float sigma, bool predict_eps,
-                                                bool clip, float x, float net, float z, bool use_z) {
+__device__ __forceinline__ StepVals step_update(float a, float b, float c1, float c2, float cp, float sigma, bool predict_eps,
+                                                bool clip, float x, float net, float x0_prev, float z, bool use_z) {
   StepVals v;
   v.x0 = net;
   if (predict_eps) {
@@ -536,29 +541,13 @@ __device__ __forceinline__ StepVals step_update(float a, float b, float c1, floa
     if (clip) v.x0 = fminf(fmaxf(v.x0, -1.0f), 1.0f);
   }
   v.mean = add_f(mul_f(c1, v.x0), mul_f(c2, x));
+  if (cp != 0.f) v.mean = add_f(v.mean, mul_f(cp, x0_prev));
   v.out = use_z ? add_f(v.mean, mul_f(z, sigma)) : v.mean;
-  return v;
-}
-// The update of the few-step solvers (DDIM, DPM-Solver++(2M) in data prediction; model/solvers.py builds the rows),
-// stated once for the loop (k_solver_update) and the single step (k_solver_step), both in dsx_solver.hip:
-//   x0  = clamp(a*x - b*net)                               (step_update's expression)
-//   m   = c0*x0 + cx*x
-//   m   = cp != 0 ? m + cp*x0_prev : m                     (the caller does not load x0_prev where cp == 0)
-//   out = use_z ? m + z*sigma : m
-// With cp == 0 this is step_update with c1 = c0 and c2 = cx, bit for bit.
-struct SolverVals { float x0, out; };
-__device__ __forceinline__ SolverVals solver_update(float a, float b, float cx, float c0, float cp, float sigma, bool clip,
-                                                    float x, float net, float x0_prev, float z, bool use_z) {
-  const StepVals s = step_update(a, b, c0, cx, sigma, true, clip, x, net, 0.f, false);
-  SolverVals v;
-  v.x0 = s.x0;
-  const float m = cp != 0.f ? add_f(s.mean, mul_f(cp, x0_prev)) : s.mean;
-  v.out = use_z ? add_f(m, mul_f(z, sigma)) : m;
   return v;
 }
 
 // The engine's normal stream: element i of the stream (seed, subseq) is component i % 4 of normal4(seed, subseq, i / 4).
-// Shared by k_randn, k_update (dsx_ops.hip) and the pointwise kernels of dsx_steps.hip, which must agree bitwise.
+// Shared by k_randn (dsx_ops.hip) and the pointwise kernels of dsx_steps.hip, k_update among them, which must agree bitwise.
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
                                               unsigned k0, unsigned k1, unsigned out[4]) {
 #pragma unroll
@@ -644,37 +633,24 @@ struct ValArgs {
 int val_blocks(long long HW);
 hipError_t launch_val_report(const ValArgs& a, hipStream_t st);
 
-// One reverse update with its intermediates (NCHW fp32, per-sample coefficients, B values each):
-//   x0 = predict_eps ? clamp(a*x - b*net) : net;  mean = c1*x0 + c2*x;  out = mean + z*sigma (mean where sigma == 0)
-// z == nullptr: element i of the normal stream (seed, subseq); repeat: every sample uses sample 0's draw (z then holds
-// C*H*W values).  Outputs that are nullptr are not written.
-struct PosteriorStepArgs {
-  const float* x; const float* net;
-  const float* a; const float* b; const float* c1; const float* c2; const float* sigma;
+// One reverse update with its intermediates (step_update above; NCHW fp32, per-sample coefficients, B values each):
+//   out = mean + z*sigma (mean where sigma == 0 or x_out == nullptr: no draw and no sum)
+// a / b are read only with predict_eps.  x0_prev == nullptr: every cp counts as 0; else it is read only for the
+// samples whose cp != 0.  z == nullptr: element i of the normal stream (seed, subseq); repeat: every sample uses sample
+// 0's draw (z then holds C*H*W values).  Outputs that are nullptr are not written; x_out may be x and x_recon_out may
+// be x0_prev.
+struct StepArgs {
+  const float* x; const float* net; const float* x0_prev;
+  const float* a; const float* b; const float* c1; const float* c2; const float* cp; const float* sigma;
   const float* z; unsigned long long seed, subseq;
   float* x_recon_out; float* mean_out; float* x_out;
   int B, predict_eps, clip, repeat;
   long long CHW;
 };
-hipError_t launch_posterior_step(const PosteriorStepArgs& a, long long HW, hipStream_t st);
-// the same with z = element (i % CHW) of the stream (a.seed, s.subseq[i / CHW]); a.z, a.subseq and a.repeat are not
-// read; a.B <= kStreamRows
-hipError_t launch_posterior_step_streams(const PosteriorStepArgs& a, const StreamIds& s, long long HW, hipStream_t st);
-// dsx_solver.hip.  One solver update (solver_update above; NCHW fp32, per-sample coefficients, B values each).
-// x0_prev == nullptr: every cp is 0 (checked by the caller); it is read only for the samples whose cp != 0.
-// z == nullptr: element i of the normal stream (seed, subseq).  x_recon_out (the next call's x0_prev) and x_out are
-// both written; x_out may be x.
-struct SolverStepArgs {
-  const float* x; const float* net; const float* x0_prev;
-  const float* a; const float* b; const float* cx; const float* c0; const float* cp; const float* sigma;
-  const float* z; unsigned long long seed, subseq;
-  float* x_recon_out; float* x_out;
-  int B, clip;
-  long long CHW;
-};
-hipError_t launch_solver_step(const SolverStepArgs& a, long long HW, hipStream_t st);
-// the same with z = element (i % CHW) of the stream (a.seed, s.subseq[i / CHW]); a.z and a.subseq are not read; a.B <= kStreamRows
-hipError_t launch_solver_step_streams(const SolverStepArgs& a, const StreamIds& s, long long HW, hipStream_t st);
+// ids == nullptr: one launch.  Else (host array of a.B sample ids) z = element (i % CHW) of the stream
+// (a.seed, ids[i / CHW] << 24 | draw), kStreamRows samples per launch with every tensor and coefficient pointer moved
+// on to the launch's first sample; a.z, a.subseq and a.repeat are not read.
+hipError_t launch_step(const StepArgs& a, long long HW, const uint64_t* ids, uint64_t draw, hipStream_t st);
 // out = c*(a0[b]*x1 + s0[b]*z1) + d*(a0[b]*x2 + s0[b]*z2); z1 == nullptr: the streams (seed, subseq), (seed, subseq + 1)
 struct InterpStartArgs {
   const float* x1; const float* x2; const float* a0; const float* s0;

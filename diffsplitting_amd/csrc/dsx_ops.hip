@@ -1,6 +1,6 @@
 // dsx_ops.hip — the non-conv kernels of the sampling path (gfx950):
 // GroupNorm statistics (wavefront-shuffle reductions), time embedding + FiLM,
-// the sampler update with Philox noise, layout conversion, the TimePredictor head.
+// Philox noise, layout conversion, the TimePredictor head.  (The sampler update: dsx_steps.hip.)
 // (Attention: dsx_attn.hip.  Tiles, stitch and the metrics: dsx_eval.hip.)
 #include "dsx_kernels.h"
 #include "dsx_reduce.h"
@@ -370,74 +370,6 @@ hipError_t launch_randn_samples(float* out, int rows, long long chw, unsigned lo
   const bool vec = chw % 4 == 0 && aligned16(out);
   hipLaunchKernelGGL(vec ? k_randn_samples<true> : k_randn_samples<false>, dim3(grid_for((chw + 3) / 4), (unsigned)rows),
                      dim3(256), 0, st, out, chw, seed, s);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Sampler update (sr3 diffusion.py:141-175 / ddpm diffusion.py:194-203 /
-// indi.py:62-69): step_update (dsx_kernels.h), the arithmetic k_posterior_step
-// shares, so the loop and the single steps round alike.
-// The step index lives in device memory so one captured graph replays T times.
-// STREAMS: per-sample noise streams (include/dsx.h).  The state is NHWC, so the four elements of a group may lie in
-// different pixels, channels (C = 3) and samples: each looks up its own (b, c, hw), the stream of its sample
-// (a.sample_ids[b] << 24 | step + 1) and component (c*HW + hw) % 4 of Philox block (c*HW + hw) / 4 -- the element the
-// NCHW tensor of dsx_randn_samples holds there.  No draw and no sum where sigma == 0.
-// ---------------------------------------------------------------------------
-template <bool STREAMS>
-__global__ void k_update(const UpdateArgs a) {
-  const int step = *a.step_ctr;
-  const int T = a.n_steps;
-  float ca = 0.f, cb = 0.f, c1 = 0.f, c2 = 0.f, sg = 0.f;
-  if (!a.per_sample) {
-    ca = a.tab[1 * T + step]; cb = a.tab[2 * T + step];
-    c1 = a.tab[3 * T + step]; c2 = a.tab[4 * T + step]; sg = a.tab[5 * T + step];
-  }
-  const long long HW = (long long)a.H * a.W;
-  const long long n = (long long)a.B * HW * a.C;
-  const long long n4 = (n + 3) / 4;
-  const unsigned long long seed = a.loop_params[0];
-  const float* __restrict__ noise = (const float*)(uintptr_t)a.loop_params[1];
-  for (long long i4 = blockIdx.x * (long long)blockDim.x + threadIdx.x; i4 < n4;
-       i4 += (long long)gridDim.x * blockDim.x) {
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!STREAMS && !a.use_noise && (a.per_sample || sg != 0.f)) normal4(seed, (unsigned long long)step + 1, (unsigned long long)i4, z);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long i = i4 * 4 + j;  // NHWC linear index
-      if (i >= n) break;
-      float zz = z[j];
-      if (a.use_noise) {
-        const int c = (int)(i % a.C);
-        const long long p = i / a.C;
-        const long long b = p / HW, hw = p % HW;
-        zz = noise[(size_t)step * n + (b * a.C + c) * HW + hw];
-      }
-      if (a.per_sample) {   // per-sample schedule: the row of this element's image
-        const size_t k = (size_t)step * a.B + (size_t)(i / (HW * a.C));
-        ca = a.tab[1 * (size_t)T + k]; cb = a.tab[2 * (size_t)T + k];
-        c1 = a.tab[3 * (size_t)T + k]; c2 = a.tab[4 * (size_t)T + k]; sg = a.tab[5 * (size_t)T + k];
-      }
-      if (STREAMS && sg != 0.f) {
-        const int c = (int)(i % a.C);
-        const long long p = i / a.C;
-        const long long b = p / HW, e = c * HW + p % HW;              // e: the element's NCHW index inside its sample
-        zz = normal1(seed, (a.sample_ids[b] << 24) | (unsigned long long)(step + 1), (unsigned long long)(e >> 2), (int)(e & 3));
-      }
-      // the stream form adds nothing where sigma == 0, as the single step does (k_posterior_step): the two agree bitwise
-      const float xn = step_update(ca, cb, c1, c2, sg, a.predict_eps, a.clip, a.x[i], a.net[i], zz, !STREAMS || sg != 0.f).out;
-      a.x[i] = xn;
-      if (a.x_act) store1_act(a.x_act, (size_t)i, xn, a.x_act_kind);
-    }
-  }
-}
-hipError_t launch_update(const UpdateArgs& a, hipStream_t st) {
-  const long long n4 = ((long long)a.B * a.H * a.W * a.C + 3) / 4;
-  hipLaunchKernelGGL(a.sample_ids ? k_update<true> : k_update<false>, dim3(grid_for(n4)), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-__global__ void k_advance(int* ctr) { if (threadIdx.x == 0) *ctr += 1; }
-hipError_t launch_advance(int* step_ctr, hipStream_t st) {
-  hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, step_ctr);
   return hipGetLastError();
 }
 

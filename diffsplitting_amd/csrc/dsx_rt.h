@@ -294,17 +294,14 @@ struct dsx_exec {
   float* film = nullptr;       // [B][F]
   float* time_buf = nullptr;   // [B] direct time values
   int* step_ctr = nullptr;
-  DevBuf table;                // float [6][cap]
+  DevBuf table;                // float [kUpdateCols][table_cap]: the step table of the loop in flight (UpdateArgs::tab)
   int table_cap = 0;
-  bool temb_from_table = false;
   unsigned* handoff_timeouts = nullptr;        // device counter: bounded FULL / FREE spins of k_conv_ws that gave up (0 in a correct run)
   unsigned long long* loop_params = nullptr;   // device {seed, noise address}: per-call values the captured step reads
   DevBuf sample_ids;                           // device uint64 [B], allocated by the first loop with per-sample noise streams and
                                                // kept: a captured step holds its address, every call writes its ids there
   // few-step solvers (dsx_solver_loop): allocated by the first such call, outside the workspace, and kept like sample_ids
   DevBuf solver_hist;                          // the previous step's predicted x0, NHWC fp32 [B][H][W][x_c]
-  DevBuf solver_table;                         // float [kSolverCols][solver_cap]
-  int solver_cap = 0;
   // per-call host data (step table, seed, noise address) is staged in pinned memory, one slot per call in flight: a
   // slot is reused only after the event recorded behind its copies has completed, so a second dsx_sample_loop on the
   // same executor never overwrites bytes an earlier call's asynchronous copy has yet to read
@@ -312,7 +309,6 @@ struct dsx_exec {
   Staging staging[4];
   int staging_next = 0;
   hipStream_t last_stream = nullptr;           // stream of the most recent graph launches
-  dsx_step_table cur_tab{};
   // graph
   Graph graph;
   std::vector<float> graph_sig;

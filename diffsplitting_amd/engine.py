@@ -558,6 +558,20 @@ def _draw_ordinal(draw):
     return draw
 
 
+def _stream_draw(sample_ids, draw, B, other_noise):
+    """The noise choice of a single step: ``(ids, draw ordinal)`` for per-sample streams, None without ``sample_ids``.
+    ``other_noise``: the refusal when the call names another source of draws too, else None."""
+    if sample_ids is None:
+        if draw is not None:
+            raise DsxError("draw names a draw of a sample stream: only with sample_ids")
+        return None
+    if other_noise:
+        raise DsxError(other_noise)
+    if draw is None:
+        raise DsxError("sample_ids need the draw ordinal (draw = step + 1 inside a loop)")
+    return _sample_ids(sample_ids, B), _draw_ordinal(draw)
+
+
 def randn_samples(shape, seed, sample_ids, draw=0, device="cuda"):
     """Per-sample noise streams (``dsx_randn_samples``): a (B, ...) tensor whose row ``b`` is
     ``randn(shape[1:], seed, subsequence=(sample_ids[b] << 24) | draw)`` -- a function of (seed, id, draw, element) only,
@@ -705,18 +719,14 @@ def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, cli
         z = _f32_cuda(z, "noise", (1, Cn, H, W) if repeat_noise else x.shape)
     outs = [None if o is None else _f32_cuda(o, what, x.shape)
             for o, what in ((x_recon_out, "x_recon_out"), (mean_out, "mean_out"), (x_out, "x_out"))]
-    if sample_ids is not None:
-        if z is not None or repeat_noise:
-            raise DsxError("sample_ids together with injected noise or repeat_noise: a stream belongs to one sample")
-        if draw is None:
-            raise DsxError("sample_ids need the draw ordinal (draw = step + 1 inside a loop)")
-        ids = _sample_ids(sample_ids, B)
+    streams = _stream_draw(sample_ids, draw, B, (z is not None or repeat_noise) and
+                           "sample_ids together with injected noise or repeat_noise: a stream belongs to one sample")
+    if streams:
+        ids, d = streams
         check(lib.dsx_posterior_step_streams(x, net, B, Cn, H, W, a, b, c1, c2, sigma, 1 if predict_eps else 0,
-                                             1 if clip else 0, None, _seed64(seed), C.c_uint64(_draw_ordinal(draw)), 0,
+                                             1 if clip else 0, None, _seed64(seed), C.c_uint64(d), 0,
                                              *outs, None, ids.ctypes.data_as(_lib._pu64), len(ids)))
         return tuple(outs)
-    if draw is not None:
-        raise DsxError("draw names a draw of a sample stream: only with sample_ids")
     check(lib.dsx_posterior_step(x, net, B, Cn, H, W, a, b, c1, c2, sigma, 1 if predict_eps else 0, 1 if clip else 0, z,
                                  _seed64(seed), C.c_uint64(int(subsequence)), 1 if repeat_noise else 0, *outs, None))
     return tuple(outs)
@@ -744,15 +754,10 @@ def solver_step(x, net, a, b, cx, c0, sigma, cp=None, x0_prev=None, clip=False, 
     x_recon_out = torch.empty_like(x) if x_recon_out is None else _f32_cuda(x_recon_out, "x_recon_out", x.shape)
     x_out = torch.empty_like(x) if x_out is None else _f32_cuda(x_out, "x_out", x.shape)
     ids, n_ids, d = None, 0, 0
-    if sample_ids is not None:
-        if z is not None:
-            raise DsxError("sample_ids together with injected noise: the draws come from one or the other")
-        if draw is None:
-            raise DsxError("sample_ids need the draw ordinal (draw = step + 1 inside a loop)")
-        ids_np = _sample_ids(sample_ids, B)
-        ids, n_ids, d = ids_np.ctypes.data_as(_lib._pu64), len(ids_np), _draw_ordinal(draw)
-    elif draw is not None:
-        raise DsxError("draw names a draw of a sample stream: only with sample_ids")
+    streams = _stream_draw(sample_ids, draw, B, z is not None and
+                           "sample_ids together with injected noise: the draws come from one or the other")
+    if streams:
+        ids, n_ids, d = streams[0].ctypes.data_as(_lib._pu64), len(streams[0]), streams[1]
     check(lib.dsx_solver_step(x, net, x0_prev, B, Cn, H, W, a, b, cx, c0, cp, sigma, 1 if clip else 0, z, _seed64(seed),
                               C.c_uint64(int(subsequence)), x_recon_out, x_out, None, ids, n_ids, C.c_uint32(d)))
     return x_recon_out, x_out

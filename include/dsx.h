@@ -432,17 +432,18 @@ int dsx_posterior_step_streams(const float* x_dev, const float* net_dev, int B, 
  *   m   = c0*x0 + cx*x
  *   m   = cp != 0 ? m + cp*x0_prev : m                   (x0_prev: the x0 of the previous step; not read when cp == 0)
  *   x  <- m + sigma*z                                    (noise rules as in dsx_sample_loop / dsx_posterior_step)
- * With cp == 0 a row is the row (c1 = c0, c2 = cx) of dsx_step_table, bit for bit: DDIM rows through dsx_solver_loop
- * and through dsx_sample_loop give the same bits.
+ * This is the update of dsx_step_table with one more term, and the device states it once: a row of dsx_step_table is
+ * the solver row (c0 = c1, cx = c2 -- mind the column order here: cx, then c0) with cp == 0, bit for bit, so DDIM rows
+ * through dsx_solver_loop and through dsx_sample_loop give the same bits.
  *
- * dsx_solver_loop: dsx_sample_loop over such rows.  The previous x0 lives in a device buffer the executor allocates at
+ * dsx_solver_loop: dsx_sample_loop over such rows, through the same update kernel.  The previous x0 lives in a device buffer the executor allocates at
  * the first call and keeps (outside the workspace: dsx_exec_workspace_bytes does not change); the captured step differs
  * from the ancestral one, and an executor that alternates between the two loops recaptures.  cp[0] must be 0 (no
  * previous x0 at the first step).  sample_ids_host == NULL: the default noise (noise_nchw_dev or Philox (seed, step + 1));
  * else B ids of the per-sample noise streams, as in dsx_sample_loop_streams.
  *
- * dsx_solver_step: one update on NCHW tensors with per-sample coefficients (device arrays of B values each), the
- * solver sibling of dsx_posterior_step.  x0_prev_dev: (B, C, H, W), read only for the samples whose cp != 0, or NULL
+ * dsx_solver_step: one update on NCHW tensors with per-sample coefficients (device arrays of B values each):
+ * dsx_posterior_step's kernel with predict_eps = 1 and the history term.  x0_prev_dev: (B, C, H, W), read only for the samples whose cp != 0, or NULL
  * (every cp then counts as 0; cp_dev may be NULL too).  x_recon_out_dev receives x0 -- the next call's x0_prev_dev, it
  * may be the very buffer -- and x_out_dev the new state (it may be x_dev); both are required.  z_dev: injected draws or
  * NULL -> the stream (seed, subsequence); with sample_ids_host the sample streams (seed, sample_ids[b], draw) and z_dev

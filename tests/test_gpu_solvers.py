@@ -123,6 +123,24 @@ def test_solver_step_draws_what_randn_writes(shape):
     assert torch.equal(got[1], want[1])
 
 
+@pytest.mark.parametrize("clip", [False, True])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_solver_columns_map_onto_the_posterior_step(shape, clip):
+    """Without a history a solver step is the ancestral step with c1 = c0 (x0's coefficient) and c2 = cx (x's): the
+    solver's argument order is cx, c0, and COEF's two columns differ, so a swap cannot pass."""
+    from diffsplitting_amd import engine
+    co, x, net, _, z = _inputs(shape, 25)
+    d = {k: v.cuda() for k, v in co.items()}
+    assert not torch.equal(co["cx"], co["c0"])
+    ids = [5, 9, 2][:shape[0]]
+    for kw in (dict(z=z.cuda()), dict(seed=1234, subsequence=77), dict(seed=99, sample_ids=ids, draw=3)):
+        x0, out = engine.solver_step(x.cuda(), net.cuda(), d["a"], d["b"], d["cx"], d["c0"], d["sigma"], clip=clip, **kw)
+        px0, _, pout = engine.posterior_step(x.cuda(), net.cuda(), c1=d["c0"], c2=d["cx"], sigma=d["sigma"], a=d["a"], b=d["b"],
+                                             predict_eps=True, clip=clip, x_recon_out=torch.empty(shape, device="cuda"),
+                                             x_out=torch.empty(shape, device="cuda"), **kw)
+        assert bool(torch.isfinite(out).all()) and torch.equal(x0, px0) and torch.equal(out, pout), kw
+
+
 # ----------------------------------------------------------------------------- ddim rows: the ancestral kernel's bits
 @pytest.mark.parametrize("eta", [0.0, 0.7])
 def test_ddim_rows_through_both_loops_give_the_same_bits(eta):

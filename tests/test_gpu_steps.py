@@ -400,7 +400,7 @@ def test_inference_one_step_calls_reproduce_the_reference_loop():
 
 
 # ----------------------------------------------------------------------------- the loop's update is the single step's
-# k_update and k_posterior_step share one arithmetic (step_update).  With the final conv's weights zero the UNet returns
+# k_update and k_step share one arithmetic (step_update).  With the final conv's weights zero the UNet returns
 # its bias in every executor, so the loop and the chained single steps can differ in the update alone: equal values
 # (torch.equal: the loop adds z * 0 where the single step adds nothing, a difference in the sign of a zero at most).
 T_EQ = 8

@@ -227,7 +227,7 @@ def test_solver_symbols_declared_bound_exported():
     assert _lib.lib.dsx_abi_version() == 2 and re.search(r"#define\s+DSX_ABI_VERSION\s+2\b", header)
     assert len(_lib.StepTable._fields_) == 10 and len(_lib.SIGNATURES["dsx_sample_loop"][1]) == 11
     assert len(_lib.SIGNATURES["dsx_solver_loop"][1]) == 13 and len(_lib.SIGNATURES["dsx_solver_step"][1]) == 23
-    assert "dsx_solver.hip" in open(os.path.join(ROOT, "diffsplitting_amd", "csrc", "build.sh")).read()
+    assert "dsx_steps.hip" in open(os.path.join(ROOT, "diffsplitting_amd", "csrc", "build.sh")).read()
 
 
 ONE = 16                                                             # a non-null address that is never dereferenced
