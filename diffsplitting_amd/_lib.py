@@ -173,6 +173,7 @@ SIGNATURES = {
     "dsx_tileplan_gather_mix": (_i, [_hn, _Df, _Df, _i64, _i64, _i64, C.POINTER(C.c_double), C.c_double,
                                      C.POINTER(C.c_double), _Df, _Df, _Df, _st]),
     "dsx_tileplan_gather_input": (_i, [_hn, _Dv, _i, _i64, _i64, _i64, C.c_double, C.c_double, C.c_double, _Df, _st]),
+    "dsx_tileplan_randn": (_i, [_hn, _i, _i64, _i64, _i64, _u64, _u64, C.c_uint32, _Df, _st]),
     "dsx_moments_update": (_i, [_Df, _Dd, _Dd, _i64, _i, _st]),
     "dsx_moments_finish": (_i, [_Dd, _Dd, _i64, _i, _Df, _Df, _st]),
     "dsx_tileplan_stitch": (_i, [_hn, _Df, _i, _i64, _i64, _i64, _Df, _Df, _Dd, _st]),

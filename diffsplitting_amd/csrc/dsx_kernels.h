@@ -687,6 +687,10 @@ hipError_t launch_tiles_gather_norm_planes(const float* f0, const float* f1, int
 // The grid's x grows with ph * pw.
 hipError_t launch_tiles_gather_input(const void* frames, int pix_bytes, bool is_float, const TileGeom& g, double mean,
                                      double std, double clip, float* out, hipStream_t st);
+// frame-keyed noise: out (count, C, ph, pw), tile k cut at (n, y0, x0) = the crop [c, y0.., x0..] of the (C, H, W) tensor
+// of the sample stream (seed, ((id_base + n) << 24) | draw); C * ph * pw fits 32 bits
+hipError_t launch_tiles_randn(const TileGeom& g, int C, unsigned long long seed, unsigned long long id_base, unsigned draw,
+                              float* out, hipStream_t st);
 // crop + target normalisation + the two mixed inputs of the TimePredictor evaluation and their min-max-normalised
 // classifier views, fused (op list: include/dsx.h, dsx_tiles_gather_mix).  norm = {mean_t0, std_t0, mean_t1, std_t1};
 // w0 = (float)(1 - t), w1 = (float)t; lo / rng = (float)lo, (float)(hi - lo) of the table rows of the two channels.

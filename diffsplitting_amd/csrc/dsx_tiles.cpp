@@ -510,6 +510,29 @@ extern "C" int dsx_tileplan_gather_input(dsx_tileplan* p, const void* frames, in
   return DSX_OK;
 }
 
+// frame-keyed noise of the sequence's tiles: the crops of the noise field (seed, id_base + frame, draw)
+extern "C" int dsx_tileplan_randn(dsx_tileplan* p, int C, int64_t first, int64_t stride, int64_t count, uint64_t seed,
+                                  uint64_t id_base, uint32_t draw, float* out_dev, void* stream) {
+  const char* what = "tileplan_randn";
+  if (!p) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
+  const uint64_t frames = (uint64_t)p->t.D[0];
+  if (id_base >= DSX_STREAM_ID_LIMIT || id_base + (frames - 1) >= DSX_STREAM_ID_LIMIT)
+    return fail(DSX_ERR_INVALID, "%s: id_base = %llu with %llu frames: every field id must be below 2^40", what,
+                (unsigned long long)id_base, (unsigned long long)frames);
+  if (draw >= DSX_STREAM_DRAW_LIMIT)
+    return fail(DSX_ERR_INVALID, "%s: draw ordinal %u, must be below 2^24", what, (unsigned)draw);
+  if ((int64_t)C > INT32_MAX / (p->t.p[1] * p->t.p[2]))
+    return fail(DSX_ERR_INVALID, "%s: C * patch = %d * %lld x %lld exceeds 32 bits", what, C, (long long)p->t.p[1],
+                (long long)p->t.p[2]);
+  if (!out_dev && count != 0) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  TileGeom g;
+  const int rc = geom_of_plan(what, p, first, stride, count, g);
+  if (rc || count == 0) return rc;
+  HIP_TRY(launch_tiles_randn(g, C, seed, id_base, draw, out_dev, (hipStream_t)stream));
+  return DSX_OK;
+}
+
 // paste whole predicted tiles (count, C, ph, pw) of the sequence; gt_canvas != NULL: also the PSNR partial sums
 // (count * dsx_stitch_psnr_blocks * C * 8 doubles, as dsx_stitch_psnr)
 extern "C" int dsx_tileplan_stitch(dsx_tileplan* p, const float* tiles, int C, int64_t first, int64_t stride, int64_t count,

@@ -212,6 +212,56 @@ hipError_t launch_tiles_gather_input(const void* frames, int pix_bytes, bool is_
   return hipErrorInvalidValue;
 }
 
+// Frame-keyed noise for tiled prediction (include/dsx.h, dsx_tileplan_randn): the noise field (seed, id, draw) of a
+// (C, H, W) frame is the sample stream (seed, (id << 24) | draw) read as that tensor -- element (c, y, x) is stream
+// element j = (c*H + y)*W + x, component j % 4 of normal4(seed, subseq, j / 4), what k_randn_samples writes -- and tile k
+// of the launch, cut at (n, y0, x0), receives field(seed, id_base + n, draw)[c, y0 + yy, x0 + xx].  Two tiles of a frame
+// therefore hold the same bits wherever they overlap.  Tile k is blockIdx.y, as in every tile kernel; grid-stride over the
+// groups of the tile: a thread owns four consecutive x of one row of one channel plane (consecutive lanes, consecutive
+// groups; 32-bit index arithmetic, the origin and the subsequence are uniform in the workgroup).  r = j0 & 3 of the
+// group's first element is the same for every group of a tile row (x advances by 4), so a wave diverges between rows
+// at most:
+//   r == 0: the group is one Philox block, one normal4
+//   r != 0: it straddles two blocks: components r..3 of the first and 0..r-1 of the second, two normal4 (a ragged last
+//           group that ends inside the first block takes only that one)
+// VEC: pw % 4 == 0 and `out` is 16-byte aligned: one 16-byte store per group; otherwise scalar stores over the group's
+// first cnt elements.  No LDS, no atomics.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_tiles_randn(float* __restrict__ out, int C, int H, int W, int ph, int pw,
+                                                      const int* __restrict__ starts, TileSeq seq, unsigned long long seed,
+                                                      unsigned long long id_base, unsigned draw) {
+  const TileGeom g{H, W, ph, pw, starts, seq};
+  const long long k = blockIdx.y;
+  const TileOrigin o = tile_origin(g, k);
+  const unsigned long long subseq = ((id_base + (unsigned long long)o.n) << 24) | draw;
+  const int gpr = (pw + 3) >> 2;                                   // groups per tile row
+  const int groups = C * ph * gpr;                                 // <= C * ph * pw, which fits 32 bits (checked on the host)
+  float* __restrict__ tile = out + (size_t)k * C * ph * pw;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += gridDim.x * blockDim.x) {
+    const int row = q / gpr, x = (q - row * gpr) * 4;              // row = c * ph + yy
+    const int c = row / ph, yy = row - c * ph;
+    const unsigned long long j0 = ((unsigned long long)c * H + (o.y0 + yy)) * W + (o.x0 + x);
+    const int r = (int)(j0 & 3), cnt = VEC ? 4 : min(4, pw - x);
+    float a[4], b[4] = {0.f, 0.f, 0.f, 0.f}, v[4] = {0.f, 0.f, 0.f, 0.f};
+    normal4(seed, subseq, j0 >> 2, a);
+    if (r + cnt > 4) normal4(seed, subseq, (j0 >> 2) + 1, b);
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)                                 // constant indices: the blocks stay in registers
+      if (r == rr) DSX_EACH4(j, 4) v[j] = rr + j < 4 ? a[rr + j] : b[rr + j - 4];
+    float* dst = tile + (size_t)row * pw + x;
+    if (VEC) *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
+    else DSX_EACH4(j, cnt) dst[j] = v[j];
+  }
+}
+hipError_t launch_tiles_randn(const TileGeom& g, int C, unsigned long long seed, unsigned long long id_base, unsigned draw,
+                              float* out, hipStream_t st) {
+  const bool vec = (g.pw & 3) == 0 && aligned16(out);
+  const long long groups = (long long)C * g.ph * ((g.pw + 3) >> 2);
+  hipLaunchKernelGGL(vec ? k_tiles_randn<true> : k_tiles_randn<false>, dim3(grid_for(groups), (unsigned)g.seq.count), dim3(256),
+                     0, st, out, C, g.H, g.W, g.ph, g.pw, g.starts, g.seq, seed, id_base, draw);
+  return hipGetLastError();
+}
+
 // (mul_f / add_f / mul_d / add_d, one IEEE operation each, live in dsx_kernels.h)
 // The mixed inputs of the TimePredictor evaluation (notebooks/EvaluateJointIndiIterative.ipynb cells 40/43,
 // time_prediction_evaluation.ipynb cell 4) cut, normalised, mixed and min-max-normalised in one pass; the op list is

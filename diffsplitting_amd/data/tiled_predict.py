@@ -6,6 +6,7 @@ pipeline: gather tiles on the GPU -> batches of tiles through the sampler ->
 import torch
 
 from .. import parallel
+from .._lib import DsxError
 from .tiling import TilePlan
 
 
@@ -90,8 +91,48 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
     return (canvas, calculate_lpips(target_frames, canvas, lpips)), plan
 
 
+def _is_gaussian(netG):
+    from ..model.samplers import GaussianSampler
+    return isinstance(netG, GaussianSampler)
+
+
 @torch.no_grad()
-def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None):
+def sample_tiles(netG, x, num_timesteps=None, solver=None, **noise):
+    """One batch of input tiles ``x`` (b, 1, p, p) through whatever sampler ``define_G`` returned -> its full-batch
+    prediction (b, C, p, p).  InDI family: ``inference`` (``num_timesteps`` steps).  A ``GaussianSampler`` (sr3 / ddpm):
+    ``solver_sample_loop(x, **solver)`` with a solver -- the dict ``DDPM.set_solver`` keeps -- else ``super_resolution``,
+    the full ancestral loop.  ``noise``: ``seed`` / ``sample_ids`` of the per-sample streams, or nothing."""
+    if _is_gaussian(netG):
+        if solver:
+            netG.solver_sample_loop(x, **solver, **noise)
+        else:
+            netG.super_resolution(x, **noise)
+    else:
+        if solver:
+            raise DsxError(f"solver: {type(netG).__name__} is not a Gaussian sampler (sr3 / ddpm); InDI's loop already "
+                           "takes num_timesteps")
+        netG.inference(x, continuous=False, **({} if num_timesteps is None else dict(num_timesteps=num_timesteps)),
+                       **noise)
+    return netG.last_full_batch
+
+
+def _stochastic_rows(netG, num_timesteps, solver):
+    """(rows, C): how many rows of one batch's loop add noise -- each is one materialised (B, C, p, p) draw under
+    noise='field' -- and the channels C of the sampler's state."""
+    if _is_gaussian(netG):
+        if solver:
+            sigma = netG.solver_table(**solver).sigma
+            return sum(1 for s in range(len(sigma)) if sigma[s] != 0), int(netG.channels)
+        netG._need_schedule()
+        return (netG.num_timesteps - 1 if netG.kind == "sr3" else netG.num_timesteps), int(netG.channels)
+    children = [netG.indi1, netG.indi2] if hasattr(netG, "indi1") else [netG]
+    rows = sum(int(num_timesteps if num_timesteps is not None else c.num_timesteps) for c in children)
+    return rows, int(children[0].out_channel)
+
+
+@torch.no_grad()
+def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None,
+                  solver=None, noise="samples", field_noise_bytes=2 << 30):
     """The tiled prediction of a dataset that cuts its own normalised tiles -- an ``InputStackTiledPred`` (one
     superimposed acquisition, no ground truth) or a ``SplitDatasetTiledPred`` -- with ``samples`` posterior samples per
     tile: their mean and, with ``return_std``, the unbiased per-pixel spread, accumulated by one fused launch per sample
@@ -103,12 +144,40 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
 
     ``seed``: per-sample noise streams; sample ``r`` of tile ``k`` draws from sample id ``k + r * plan.total`` (the rule
     of ``predict_tiled_mixed``), whatever batch or rank it runs in.  Tiles are sharded over the ranks and exchanged
-    through ``TileExchange``: one collective per output canvas."""
+    through ``TileExchange``: one collective per output canvas.
+
+    ``solver``: the dict ``DDPM.set_solver`` keeps (``solver``, ``steps``, ``eta``, ``spacing``): a Gaussian sampler
+    (sr3 / ddpm) then runs that few-step solver per batch instead of its full ancestral loop; refused for any other.
+
+    ``noise="field"`` (needs ``seed``): every draw is cut from a noise field keyed by the FRAME position
+    (``TilePlan.randn_field``): a function of (seed, frame, draw ordinal, channel, y, x), so overlapping tiles start from
+    -- and, in a stochastic row, receive -- the same noise where they overlap; posterior sample ``r`` takes
+    ``id_base = r * frames``.  The draws travel in the loop's injected form, one (B, C, p, p) tensor per stochastic
+    row; more than ``field_noise_bytes`` of them per batch is refused.  ``noise="samples"``: the streams above."""
     from .. import engine
     samples = int(samples)
     if samples < 1:
         raise ValueError(f"predict_stack: samples = {samples}: a positive count")
     plan = dataset.plan
+    if solver and not _is_gaussian(netG):
+        raise DsxError(f"predict_stack: solver: {type(netG).__name__} is not a Gaussian sampler (sr3 / ddpm); InDI's "
+                       "loop already takes num_timesteps")
+    if noise not in ("samples", "field"):
+        raise DsxError(f"predict_stack: noise = {noise!r}: 'samples' or 'field'")
+    field = noise == "field"
+    if field:
+        if seed is None:
+            raise DsxError("predict_stack: noise='field' needs seed=: a noise field is named by (seed, frame, draw)")
+        rows, C_state = _stochastic_rows(netG, num_timesteps, solver)
+        B = max(1, min(int(batch_tiles), plan.total))
+        need = rows * B * C_state * plan.patch_shape[1] * plan.patch_shape[2] * 4
+        if need > field_noise_bytes:
+            raise DsxError(f"predict_stack: noise='field' materialises one (B, C, p, p) draw per stochastic row: {rows} "
+                           f"rows x {B} tiles need {need} bytes, field_noise_bytes = {field_noise_bytes}; use a solver "
+                           "(ddim with eta = 0 and dpmpp2m draw once per batch), fewer rows, or a smaller batch")
+        joint_bit = getattr(netG, "STREAM2_BIT", 1 << 39)
+        if samples * plan.data_shape[0] > joint_bit:
+            raise DsxError("predict_stack: samples * frames exceeds the 2^39 field ids of one sampler")
     C_out = netG.prediction_channels
     gt = None
     if hasattr(dataset, "normalized_target_frames"):
@@ -117,28 +186,42 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
             gt = None
     ex = ex_std = None
     ids = parallel.shard_ids(plan.total, parallel.rank(), parallel.world_size())
-    skw = {} if num_timesteps is None else dict(num_timesteps=num_timesteps)
-    for i in range(0, len(ids), batch_tiles):
-        chunk = ids[i:i + batch_tiles]
-        x = dataset.tiles(chunk)["input"]
-        if ex is None:
-            ex = TileExchange(plan, C_out, x.device, group, gt=gt)
-            ex_std = TileExchange(plan, C_out, x.device, group) if return_std else None
-        mean = m2 = None
-        for r in range(samples):
-            kw = {} if seed is None else dict(seed=seed, sample_ids=[k + r * plan.total for k in chunk])
-            netG.inference(x, continuous=False, **skw, **kw)
-            if samples > 1:
-                mean, m2 = engine.moments_update(netG.last_full_batch.contiguous(), mean, m2, r)
-        if samples == 1:
-            tiles, spread = netG.last_full_batch, None
+    kept_field = getattr(netG, "noise_field", None)
+    try:
+        for i in range(0, len(ids), batch_tiles):
+            chunk = ids[i:i + batch_tiles]
+            x = dataset.tiles(chunk)["input"]
+            if ex is None:
+                ex = TileExchange(plan, C_out, x.device, group, gt=gt)
+                ex_std = TileExchange(plan, C_out, x.device, group) if return_std else None
+            mean = m2 = None
+            for r in range(samples):
+                kw = {}
+                if field:
+                    # (shape, draw[, id_bit]): the crops of this batch's tiles out of the fields of sample r; a joint
+                    # sampler's second child adds its bit to the field ids
+                    netG.noise_field = lambda shape, draw, id_bit=0, chunk=chunk, r=r: plan.randn_field(
+                        chunk, shape[1], seed, draw, id_base=r * plan.data_shape[0] + id_bit, device=x.device)
+                elif seed is not None:
+                    kw = dict(seed=seed, sample_ids=[k + r * plan.total for k in chunk])
+                last = sample_tiles(netG, x, num_timesteps, solver, **kw)
+                if samples > 1:
+                    mean, m2 = engine.moments_update(last.contiguous(), mean, m2, r)
+            if samples == 1:
+                tiles, spread = netG.last_full_batch, None
+                if return_std:
+                    spread = torch.zeros_like(tiles)
+            else:
+                tiles, spread = engine.moments_finish(mean, m2, samples, want_std=return_std)
+            ex.add(tiles, chunk)
             if return_std:
-                spread = torch.zeros_like(tiles)
-        else:
-            tiles, spread = engine.moments_finish(mean, m2, samples, want_std=return_std)
-        ex.add(tiles, chunk)
-        if return_std:
-            ex_std.add(spread, chunk)
+                ex_std.add(spread, chunk)
+    finally:
+        if field:
+            netG.noise_field = kept_field
+            for child in (getattr(netG, "indi1", None), getattr(netG, "indi2", None)):
+                if child is not None:                                 # a joint sampler hands its field down per call
+                    child.noise_field = None
     if ex is None:                                                    # a rank without tiles still joins the collectives
         dev = torch.device("cuda", torch.cuda.current_device())
         ex = TileExchange(plan, C_out, dev, group, gt=gt)

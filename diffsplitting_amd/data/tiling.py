@@ -112,6 +112,34 @@ class TilePlan:
                                        ids.ctypes.data_as(C.POINTER(C.c_int64)), len(ids), out, None))
         return out
 
+    def randn_field(self, tile_ids, C_state, seed, draw=0, id_base=0, device="cuda"):
+        """Frame-keyed noise (``dsx_tileplan_randn``): (count, C, ph, pw) normals, tile ``k`` cut at (n, y0, x0) holding
+        the crop ``[:, y0:y0 + ph, x0:x0 + pw]`` of ``engine.randn_samples((1, C, H, W), seed, [id_base + n], draw)`` --
+        a function of (seed, frame, draw, channel, y, x) in frame coordinates, so tiles of one frame share the bits of
+        their overlap.  An arithmetic id sequence takes one launch, any other list one launch per tile."""
+        _lib.require_gpu()
+        ids = self._ids(tile_ids)
+        Cn, draw, id_base = int(C_state), int(draw), int(id_base)
+        if Cn < 1:
+            raise DsxError(f"randn_field: C = {Cn}, must be at least 1")
+        if not 0 <= draw < _lib.STREAM_DRAW_LIMIT:
+            raise DsxError(f"randn_field: draw ordinal {draw} out of range (0 <= draw < 2^24)")
+        if not 0 <= id_base <= _lib.STREAM_ID_LIMIT - self.data_shape[0]:
+            raise DsxError(f"randn_field: id_base = {id_base} with {self.data_shape[0]} frames: every field id must be "
+                           "below 2^40")
+        out = torch.empty((len(ids), Cn, self.patch_shape[1], self.patch_shape[2]), dtype=torch.float32, device=device)
+        seed64 = C.c_uint64(int(seed) & (2 ** 64 - 1))
+        call = lambda first, stride, count, dst: check(lib.dsx_tileplan_randn(
+            self.handle, Cn, first, stride, count, seed64, C.c_uint64(id_base), C.c_uint32(draw), dst, None))
+        seq = as_sequence(ids)
+        if seq is not None:
+            for k0 in range(0, seq[2], 65535):
+                call(seq[0] + k0 * seq[1], seq[1], min(65535, seq[2] - k0), out[k0:])
+        else:
+            for k, i in enumerate(ids):
+                call(int(i), 1, 1, out[k:])
+        return out
+
     def _check_tiles(self, tiles):
         if not tiles.is_cuda or tiles.dtype != torch.float32 or tiles.dim() != 4:
             raise DsxError("tiles must be a (count,C,ph,pw) float32 CUDA tensor")

@@ -20,6 +20,12 @@ Every draw of sample ``b`` -- the initial state, draw 0, and step ``s``, draw ``
 ``(seed, sample_ids[b], draw, element)`` alone: the same whatever batch, batch position or rank the sample runs in.
 torch's generator is not touched, and a ``noise_source`` together with ids is refused.
 
+Draws by ordinal: ``noise_field``, a callable ``(shape, draw) -> CUDA fp32 tensor``, is asked for the initial state
+(draw 0) and for the noise of step ``s`` (draw ``s + 1``) of every sampling loop, which then runs on these draws in the
+injected form; a step that adds no noise keeps its ordinal.  Tiled prediction sets it to noise cut from a frame-keyed
+field (``TilePlan.randn_field``).  Together with ``noise_source`` or ``sample_ids`` it is refused; torch's generator is
+not touched.
+
 Few-step sampling (Gaussian samplers only): ``solver_sample_loop`` runs a sub-sequence of the trained schedule with
 DDIM(eta) or DPM-Solver++(2M) rows (``model/solvers.py``) through ``UNetEngine.solver_loop``; ``p_sample_loop`` and
 the other methods keep their parameter lists.
@@ -37,6 +43,7 @@ class _SamplerBase(nn.Module):
     def __init__(self):
         super().__init__()
         self.noise_source = None      # callable(shape) -> CPU/GPU tensor; None = device RNG
+        self.noise_field = None       # callable(shape, draw ordinal) -> CUDA fp32 tensor; None = the sources above
         self.use_graph = True
         self.last_full_batch = None   # final state of the whole batch (Q1 keeps only one element)
 
@@ -44,6 +51,40 @@ class _SamplerBase(nn.Module):
         if self.noise_source is not None:
             return self.noise_source(tuple(shape)).to(device=device, dtype=torch.float32)
         return torch.randn(tuple(shape), device=device)
+
+    def _uses_field(self, sample_ids=None):
+        """Whether ``noise_field`` provides the draws of this call; refused together with the two other sources."""
+        if self.noise_field is None:
+            return False
+        if self.noise_source is not None:
+            raise DsxError("noise_field together with noise_source: the draws come from one or the other")
+        if sample_ids is not None:
+            raise DsxError("noise_field together with sample_ids: the draws come from the field or from the sample "
+                           "streams, not both")
+        return True
+
+    def _field(self, shape, draw, device):
+        """Draw ``draw`` of ``noise_field`` for a state of ``shape`` (0: the initial state, s + 1: step s)."""
+        shape = tuple(int(v) for v in shape)
+        z = self.noise_field(shape, int(draw))
+        if not torch.is_tensor(z) or not z.is_cuda or z.dtype != torch.float32 or tuple(z.shape) != shape:
+            raise DsxError(f"noise_field(shape, draw) must return a float32 CUDA tensor of shape {shape}")
+        return z.to(device)
+
+    def _field_noise(self, shape, n_steps, draws, device):
+        """The injected form (n_steps, B, C, H, W) of a loop whose steps ``draws`` add noise: step s holds draw s + 1."""
+        draws = list(draws)
+        if not draws:
+            return None
+        noise = torch.zeros((n_steps,) + tuple(shape), device=device)
+        for s in draws:
+            noise[s] = self._field(shape, s + 1, device)
+        return noise
+
+    def _loop_seed(self):
+        """The Philox seed of a sampling loop; with ``noise_field`` every draw is injected and torch's generator stays
+        untouched."""
+        return 0 if self.noise_field is not None else self._seed()
 
     def _seed(self):
         if self.noise_source is not None:
@@ -202,13 +243,15 @@ class GaussianSampler(_SamplerBase):
         T = self.num_timesteps
         cond, shape, streams, img, first = self._loop_start(x_in, continous, seed, sample_ids)
         noise = None
-        if self.noise_source is not None:  # reference draw order: one per step, none at t == 0 (sr3)
+        if self.noise_field is not None:   # checked by _loop_start; the same steps as below, by ordinal
+            noise = self._field_noise(shape, T, range(T - 1 if self.kind == "sr3" else T), dev)
+        elif self.noise_source is not None:  # reference draw order: one per step, none at t == 0 (sr3)
             n_draw = T - 1 if self.kind == "sr3" else T
             noise = torch.zeros((T,) + shape, device=dev)
             for s in range(n_draw):
                 noise[s] = self._draw(shape, dev)
         snaps = engine.gaussian_snapshot_steps(T) if continous else []
-        skw = dict(seed=self._seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
+        skw = dict(seed=self._loop_seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
         x, sn = self.denoise_fn.engine().sample_loop(self._step_table(bool(clip_denoised)), img, cond=cond,
                                                      noise=noise, snapshot_steps=snaps, use_graph=self.use_graph, **skw)
         self.last_full_batch = x
@@ -226,8 +269,11 @@ class GaussianSampler(_SamplerBase):
         else:
             cond = x_in.to(dev).float()
             shape = (cond.shape[0], self.channels) + tuple(cond.shape[2:])
+        field = self._uses_field(sample_ids)
         streams = self._stream_args(seed, sample_ids, shape[0])
-        if streams is None:
+        if field:
+            img = self._field(shape, 0, dev)
+        elif streams is None:
             img = self._draw(shape, dev)
         else:
             img = engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
@@ -258,14 +304,16 @@ class GaussianSampler(_SamplerBase):
         K = table.n_steps
         draws = [s for s in range(K) if table.sigma[s] != 0]         # ddim with eta > 0: one per row but the last
         noise = None
-        if self.noise_source is not None and draws:
+        if self.noise_field is not None:
+            noise = self._field_noise(shape, K, draws, dev)
+        elif self.noise_source is not None and draws:
             noise = torch.zeros((K,) + shape, device=dev)
             for s in draws:
                 noise[s] = self._draw(shape, dev)
         if streams is not None:
             skw = dict(seed=streams[0], sample_ids=streams[1])
         else:
-            skw = dict(seed=self._seed() if draws else 0)
+            skw = dict(seed=self._loop_seed() if draws else 0)
         x, sn = self.denoise_fn.engine().solver_loop(table, img, cond=cond, noise=noise,
                                                      snapshot_steps=range(K) if continous else (),
                                                      use_graph=self.use_graph, **skw)
@@ -687,6 +735,8 @@ class InDISampler(_SamplerBase):
 
     def _draw0(self, shape, dev, streams):
         """The draw of the initial state: torch's (or the injected one), or draw 0 of the sample streams."""
+        if self.noise_field is not None:
+            return self._field(shape, 0, dev)
         if streams is None:
             return self._draw(shape, dev)
         return engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
@@ -721,7 +771,10 @@ class InDISampler(_SamplerBase):
         B = x_in.shape[0]
         xr = torch.cat([x_in.float()] * self._copies(x_in), dim=1)
         noise = None
-        if self.noise_source is not None:
+        if self.noise_field is not None:                              # whole-batch draws by ordinal
+            d0 = self._draw0(xr.shape, dev, streams)
+            noise = self._field_noise(xr.shape, num_timesteps, range(num_timesteps), dev)
+        elif self.noise_source is not None:
             starts, steps = [], []
             for b in range(B):
                 starts.append(self._draw((1,) + tuple(xr.shape[1:]), dev))
@@ -739,7 +792,7 @@ class InDISampler(_SamplerBase):
         """The engine's loop from ``x_t`` (updated in place: ``first`` keeps the start) and what inference returns."""
         snaps = engine.indi_snapshot_steps(num_timesteps) if continuous else []
         first = x_t.clone() if continuous else None
-        skw = dict(seed=self._seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
+        skw = dict(seed=self._loop_seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
         x, sn = self.denoise_fn.engine().sample_loop(table, x_t, noise=noise, snapshot_steps=snaps,
                                                      use_graph=self.use_graph, stream=stream, **skw)
         self.last_full_batch = x
@@ -750,6 +803,8 @@ class InDISampler(_SamplerBase):
         return x[-1:]                                                # indi.py:92-95: ret_img[-1:]
 
     def _noise(self, shape, n, dev):
+        if self.noise_field is not None:
+            return self._field_noise(shape, n, range(n), dev)
         if self.noise_source is None:
             return None
         return torch.stack([self._draw(shape, dev) for _ in range(n)])  # drawn on every step (Q4)
@@ -763,6 +818,7 @@ class InDISampler(_SamplerBase):
             num_timesteps = self.num_timesteps
         assert self.conditional is False
         self._need_cuda(x_in, what="inference")
+        self._uses_field(sample_ids)
         streams = self._stream_args(seed, sample_ids, x_in.shape[0])
         t_list = self._per_sample_t(t_float_start, x_in.shape[0])
         if t_list is not None:
@@ -875,9 +931,13 @@ class JointIndiSampler(_SamplerBase):
     def inference(self, x_in, continuous=False, num_timesteps=None, t_float_start=0.5, eps=1e-8, seed=None,
                   sample_ids=None):
         """``seed`` / ``sample_ids`` (ids < 2^39): per-sample noise streams; indi1 draws from the ids, indi2 from the
-        ids with bit 39 set."""
-        for s in (self.indi1, self.indi2):
+        ids with bit 39 set.  ``noise_field`` here is a callable ``(shape, draw, id_bit)``: indi1 asks with
+        ``id_bit = 0``, indi2 with ``STREAM2_BIT``, which the provider adds to its field ids -- the two channels never
+        share a draw."""
+        field = self.noise_field if self._uses_field(sample_ids) else None
+        for s, bit in ((self.indi1, 0), (self.indi2, self.STREAM2_BIT)):
             s.noise_source, s.use_graph = self.noise_source, self.use_graph   # indi1's draws first (Q4)
+            s.noise_field = None if field is None else (lambda shape, draw, bit=bit: field(shape, draw, bit))
         if sample_ids is not None and torch.is_tensor(sample_ids):
             sample_ids = sample_ids.detach().cpu().tolist()
         k1 = dict(seed=seed, sample_ids=sample_ids)

@@ -37,6 +37,12 @@ counts of the sum first.  ``--samples N`` draws N posterior samples per tile and
 ``--std-out FILE`` the per-pixel spread in raw counts (``std * std_target``).  Both also apply to the plain two-channel
 prediction, where the PSNR of the mean shows what averaging buys.  Repeat ``r`` of tile ``k`` draws from sample id
 ``k + r * tiles`` under ``--sample-seed``.
+
+An ``sr3`` / ``ddpm`` config (the reference's ``config/splitting.json``) runs its full ancestral loop per batch of tiles;
+``--solver {ddim,dpmpp2m} --solver-steps K [--eta E] [--spacing uniform|logsnr]`` samples with a few-step solver over
+the trained schedule instead (``model/solvers.py``).  ``--noise-field`` (needs ``--sample-seed S``) cuts every tile's noise
+from one field per frame -- a draw is a function of (seed, frame, draw ordinal, channel, y, x) -- so that overlapping
+tiles share the noise of their overlap; posterior sample ``r`` draws from the fields ``r * frames + frame``.
 """
 import argparse
 import logging
@@ -198,7 +204,18 @@ def main(argv=None):
                     help="posterior samples per tile of the tiled prediction; --out holds their mean (default 1)")
     ap.add_argument("--std-out", type=str, default=None,
                     help="write the per-pixel spread over --samples >= 2 samples in raw counts (.npy / .tif)")
+    ap.add_argument("--solver", type=str, default=None, choices=["ddim", "dpmpp2m"],
+                    help="sr3 / ddpm configs: sample every batch of tiles with this few-step solver over "
+                         "--solver-steps timesteps of the trained schedule (default: the full ancestral loop)")
+    ap.add_argument("--solver-steps", type=int, default=None, help="with --solver: how many timesteps")
+    ap.add_argument("--eta", type=float, default=None, help="with --solver ddim: stochasticity in [0, 1] (default 0)")
+    ap.add_argument("--spacing", type=str, default=None, choices=["uniform", "logsnr"],
+                    help="with --solver: how the timesteps are spaced (default: logsnr for dpmpp2m, uniform for ddim)")
+    ap.add_argument("--noise-field", action="store_true",
+                    help="with --sample-seed: cut every tile's noise from one field per frame (seed, frame, draw, "
+                         "channel, y, x), so that overlapping tiles share the noise of their overlap")
     args = ap.parse_args(argv)
+    _check_solver_args(args)
     if args.sample_seed is not None and args.validate:
         raise SystemExit("--sample-seed names the tiles of a tiled prediction: not with --validate")
     if args.phase == "train":
@@ -314,12 +331,22 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     samples per tile; rank 0 writes the mean to ``--out`` and the spread to ``--std-out``.  Returns the stitched mean."""
     from .data.tiled_predict import predict_stack
     samples = args.samples or 1
+    solver = _solver_of(args)
+    if hasattr(netG, "solver_sample_loop"):
+        # a Gaussian sampler runs its trained schedule: --steps does not shorten it, --solver does
+        n_steps = solver["steps"] if solver else netG.num_timesteps
+        if rank == 0 and solver:
+            log.info("sr3 / ddpm: %s over %d of the %d trained timesteps per batch of tiles", solver["solver"], n_steps,
+                     netG.num_timesteps)
+        elif rank == 0:
+            log.info("sr3 / ddpm without --solver: the full ancestral loop, %d steps per batch of tiles", n_steps)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     # every rank holds the frames: the ground truth needs no tiles and no collective; the metric is accumulated while
     # pasting, and the path's only collectives are the cropped tiles of each output canvas
     out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
-                              return_std=bool(args.std_out), seed=args.sample_seed)
+                              return_std=bool(args.std_out), seed=args.sample_seed, solver=solver,
+                              noise="field" if args.noise_field else "samples")
     pred, ps = out["mean"], out.get("psnr")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -393,6 +420,44 @@ def _check_input_args(args):
     if meta["target_channel_idx"] != idx:
         raise SystemExit(f"--norm {args.norm}: written for target_channel_idx = {meta['target_channel_idx']}, the config "
                          f"says {idx}")
+
+
+def _check_solver_args(args):
+    """The flags of few-step sampling and of frame-keyed noise, checked on the command line and the config file alone
+    (nothing touches the GPU, no rank is started).  Without any of them: nothing."""
+    if args.noise_field:
+        if args.sample_seed is None:
+            raise SystemExit("--noise-field needs --sample-seed S: a noise field is named by (seed, frame, draw)")
+        if args.validate or args.mix_t is not None:
+            raise SystemExit("--noise-field cuts the noise of a tiled prediction's tiles: not with --validate or --mix-t")
+    given = [flag for flag, value in (("--solver-steps", args.solver_steps), ("--eta", args.eta),
+                                      ("--spacing", args.spacing)) if value is not None]
+    if args.solver is None:
+        if given:
+            raise SystemExit(f"{', '.join(given)}: only with --solver {{ddim,dpmpp2m}}")
+        return
+    which = (Logger.load_json(args.config).get("model") or {}).get("which_model_G")
+    if which not in ("sr3", "ddpm"):
+        raise SystemExit(f"--solver: few-step solvers run a Gaussian sampler (which_model_G sr3 / ddpm); this config "
+                         f"builds {which!r}, whose loop already takes --steps")
+    if args.solver_steps is None:
+        raise SystemExit("--solver needs --solver-steps K: how many timesteps of the trained schedule to run")
+    if args.solver_steps < 1:
+        raise SystemExit(f"--solver-steps {args.solver_steps}: a positive count")
+    if args.validate or args.mix_t is not None:
+        raise SystemExit("--solver samples the tiles of a tiled prediction: not with --validate or --mix-t")
+    from .model import solvers
+    try:
+        solvers.check_solver(args.solver, args.eta or 0.0)
+    except DsxError as e:
+        raise SystemExit(f"--solver {args.solver} --eta {args.eta}: {e}")
+
+
+def _solver_of(args):
+    """The dict ``predict_stack(solver=...)`` takes (what ``DDPM.set_solver`` keeps), or None without --solver."""
+    if args.solver is None:
+        return None
+    return dict(solver=args.solver, steps=int(args.solver_steps), eta=float(args.eta or 0.0), spacing=args.spacing)
 
 
 _MIXED_FLAGS = (("--mix-t", "mix_t"), ("--time-predictor", "time_predictor"),

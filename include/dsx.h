@@ -721,6 +721,19 @@ int dsx_tileplan_gather_mix(dsx_tileplan* plan, const float* frames0_dev, const 
 int dsx_tileplan_gather_input(dsx_tileplan* plan, const void* frames_dev, int pix_type, int64_t first, int64_t stride,
                               int64_t count, double mean_input, double std_input, double upper_clip,
                               float* tiles_in_dev, void* stream);
+/* Frame-keyed noise for tiled prediction.  The NOISE FIELD (seed, id, draw) of a (C, H, W) frame is the sample stream of
+ * dsx_randn_samples with that (seed, id, draw), read as a (C, H, W) tensor: element (c, y, x) is element
+ * j = (c*H + y)*W + x of the stream (seed, (id << 24) | draw), i.e. component j % 4 of Philox block j / 4.  H and W
+ * are the plan's frame extents.  out_dev (count, C, ph, pw) fp32: the tile first + k*stride, cut at patch start
+ * (n, y0, x0), receives field(seed, id_base + n, draw)[c, y0 + yy, x0 + xx] -- the crop of what
+ * dsx_randn_samples(.., C*H*W, seed, {id_base + n}, draw) writes, bit for bit.  Two tiles of one frame hold the same
+ * bits wherever they overlap; a draw does not depend on the tile, the batch or the rank.  One 16-byte store per four
+ * pixels when pw is a multiple of 4 and out_dev is 16-byte aligned, scalar stores otherwise.
+ * A null plan, a sequence that leaves the plan and a count outside 0..65535 are refused as by the other plan forms
+ * (count == 0: DSX_OK without a device); C < 1, id_base + (N - 1) >= DSX_STREAM_ID_LIMIT and
+ * draw >= DSX_STREAM_DRAW_LIMIT are DSX_ERR_INVALID before any HIP call. */
+int dsx_tileplan_randn(dsx_tileplan* plan, int C, int64_t first, int64_t stride, int64_t count, uint64_t seed,
+                       uint64_t id_base, uint32_t draw, float* out_dev, void* stream);
 /* Mean and spread over n repeated samples of `count` values (the posterior of a diffusion splitter), Welford's
  * recurrence in double, one launch per sample r = 0, 1, ... and one to finish:
  *   update, r == 0: mean = x, M2 = 0;  r > 0: d = x - mean;  mean' = mean + d / (r + 1);  M2' = M2 + d * (x - mean')
