@@ -180,6 +180,11 @@ SIGNATURES = {
     "dsx_tileplan_pack_layout": (_i, [_hn, _i, _pi64, _pi64]),
     "dsx_tileplan_pack": (_i, [_hn, _Df, _i, _i, _i64, _i64, _Df, _st]),
     "dsx_tileplan_paste_packed": (_i, [_hn, _Df, _i, _i, _i64, _Df, _Df, _Dd, _st]),
+    "dsx_tileplan_contributors": (_i, [_hn, _pi32, _pi32]),
+    "dsx_tileplan_set_window": (_i, [_hn, _H, _H]),
+    "dsx_tileplan_blend_blocks": (_i, [_hn]),
+    "dsx_tileplan_blend": (_i, [_hn, _Df, _i, _i, _i64, _Df, _Df, _Dd, _st]),
+    "dsx_tileplan_gather_canvas": (_i, [_hn, _Df, _i, _i64, _i64, _i64, _Df, _st]),
     "dsx_tiff_open": (_i, [C.c_char_p, C.POINTER(_vp)]),
     "dsx_tiff_info": (_i, [_hn, _pi64, C.POINTER(_i)]),
     "dsx_tiff_read": (_i, [_hn, _i64, _i64, _H, C.c_size_t]),

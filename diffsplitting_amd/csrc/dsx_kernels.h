@@ -718,6 +718,27 @@ hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions /*dev*/, 
 // valid regions of the sequence's tiles -> this rank's flat run (the crop of tile_stitcher.py:38-56 before the collective)
 hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const int* regions, const long long* off,
                              TileSeq seq, float* flat, hipStream_t st);
+// Blended stitching: the overlap-add of ALL tiles of a plan into the (N,H,W,C) canvas, as a gather (include/dsx.h,
+// dsx_tileplan_blend).  tiles: whole (C, ph, pw) tiles, tile t at  (t % world) * rank_stride + (t / world) * C*ph*pw
+// (world == 1: (total, C, ph, pw)).  The plan's tiles are frame-major, ny x nx per frame, tile (iy, ix) of frame n is
+// id (n*ny + iy)*nx + ix; rows[y] = (first tile row, count) and cols[x] = (first tile column, count) name the
+// contributors of a canvas pixel, wy / wx the separable window.  gt != nullptr: also part[N][blocks][C][8] (C <= 4).
+struct BlendArgs {
+  const float* tiles; int C, world; long long rank_stride;
+  int N, H, W, ph, pw, ny, nx;
+  const int* starts;                 // dev [total][3]
+  const int* rows; const int* cols;  // dev [H][2], [W][2]
+  const float* wy; const float* wx;  // dev [ph], [pw]
+  float* canvas; const float* gt; double* part;
+};
+// workgroups per frame of a blend of (H, W) frames: segments of 256 pixels along x times at most 128 row slots
+struct BlendGrid { int segs, rows; };
+static inline BlendGrid blend_grid(long long H, long long W) {
+  return BlendGrid{(int)((W + 255) / 256), (int)(H > 128 ? 128 : H)};
+}
+hipError_t launch_blend(const BlendArgs& a, hipStream_t st);
+// the tiles of the sequence out of a multi-channel frame state: canvas (N,H,W,C) -> tiles (count, C, ph, pw)
+hipError_t launch_tiles_gather_canvas(const float* canvas, int C, const TileGeom& g, float* tiles, hipStream_t st);
 
 // dsx_eval.hip: Welford moments, range table, image metrics (the loss reduction is declared with the steps above).
 // Welford's recurrence over repeated samples, in double with every operation rounded on its own (include/dsx.h)

@@ -328,6 +328,14 @@ struct dsx_tileplan {
   std::vector<int32_t> starts, regions;          // [total][3], [total][8]
   DevBuf d_starts;                               // int, one device allocation: starts, then regions
   int* d_regions = nullptr;                      // (points into d_starts)
+  // blended stitching: per canvas row (first tile row, count), per canvas column (first tile column, count) -- the
+  // tiles that cover it are one contiguous index range along each axis -- and the separable window wy[ph], wx[pw]
+  std::vector<int32_t> rows, cols;               // [H][2], [W][2]
+  bool covers = false;                           // every canvas pixel has a contributor
+  int *d_rows = nullptr, *d_cols = nullptr;      // (point into d_starts)
+  std::vector<float> window;                     // wy then wx; empty until dsx_tileplan_set_window
+  bool window_stale = false;                     // the host window is newer than d_window
+  DevBuf d_window;                               // float [ph + pw]
   struct Offsets {                               // pack layout for `world` ranks (dsx_tileplan_pack_layout)
     int world = 0;
     std::vector<int64_t> off, rank_pixels;
@@ -345,6 +353,30 @@ static void plan_layout(const dsx_tileplan* p, int world, dsx_tileplan::Offsets&
     o.off[id] = o.rank_pixels[q];
     o.rank_pixels[q] += (int64_t)p->regions[id * 8 + 3] * p->regions[id * 8 + 4];
   }
+}
+
+// Along axis d the patch starts of the tile rows (columns) are s[0] < s[1] < ... (SHIFT: 0, g, 2g, .., D - p), all with
+// the same extent, so the tiles that cover coordinate v are one contiguous index range: tab[v] = (first, count).
+// False where the starts do not increase strictly or some coordinate has no tile (TRIM leaves a border uncovered).
+static bool axis_contributors(const dsx_tileplan* p, int d, std::vector<int32_t>& tab) {
+  const int64_t n = p->t.dim_count(d), D = p->t.D[d], ext = p->t.p[d], step = d == 1 ? p->t.dim_count(2) : 1;
+  tab.assign((size_t)D * 2, 0);
+  bool ok = p->total > 0;
+  for (int64_t k = 0; k < n && ok; ++k) {
+    const int64_t s = p->starts[(size_t)(k * step) * 3 + d];
+    if (k > 0 && s <= p->starts[(size_t)((k - 1) * step) * 3 + d]) ok = false;
+    for (int64_t v = s; v < s + ext && ok; ++v) {
+      if (tab[v * 2 + 1] == 0) tab[v * 2] = (int32_t)k;
+      ++tab[v * 2 + 1];
+    }
+  }
+  for (int64_t v = 0; v < D && ok; ++v) ok = tab[v * 2 + 1] > 0;
+  return ok;
+}
+static void plan_contributors(dsx_tileplan* p) {
+  const bool flat = p->t.g[0] == 1 && p->t.p[0] == 1;      // one frame per tile: ids are (frame, tile row, tile column)
+  const bool oky = axis_contributors(p, 1, p->rows), okx = axis_contributors(p, 2, p->cols);
+  p->covers = flat && oky && okx;
 }
 
 extern "C" int dsx_tileplan_create(const int64_t data_shape[3], const int64_t grid_shape[3], const int64_t patch_shape[3],
@@ -386,6 +418,7 @@ extern "C" int dsx_tileplan_create(const int64_t data_shape[3], const int64_t gr
       }
     }
   }
+  plan_contributors(p.get());
   *out = p.release();
   return DSX_OK;
 }
@@ -411,15 +444,21 @@ extern "C" int dsx_tileplan_pack_layout(const dsx_tileplan* p, int world, int64_
 
 static int plan_device(dsx_tileplan* p) {       // first device use: upload the tables (once)
   if (p->d_starts.p || p->total == 0) return DSX_OK;
-  const size_t nb = (size_t)p->total * (3 + 8) * 4;
+  const size_t nb = ((size_t)p->total * (3 + 8) + p->rows.size() + p->cols.size()) * 4;
   DevBuf d;
   HIP_TRY(d.alloc(nb));
   int* d_regions = d.as<int>() + p->total * 3;
+  int* d_rows = d_regions + p->total * 8;
+  int* d_cols = d_rows + p->rows.size();
   hipError_t e = hipMemcpy(d.p, p->starts.data(), (size_t)p->total * 12, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_regions, p->regions.data(), (size_t)p->total * 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_rows, p->rows.data(), p->rows.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_cols, p->cols.data(), p->cols.size() * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(DSX_ERR_HIP, "upload of the tile tables failed: %s", hipGetErrorString(e));
   p->d_starts = std::move(d);
   p->d_regions = d_regions;
+  p->d_rows = d_rows;
+  p->d_cols = d_cols;
   return DSX_OK;
 }
 static int plan_offsets(dsx_tileplan* p, int world, const dsx_tileplan::Offsets** out) {
@@ -577,5 +616,88 @@ extern "C" int dsx_tileplan_paste_packed(dsx_tileplan* p, const float* flat_all,
   const StitchSrc src{flat_all, 1, g.ph, g.pw, o->d_off.as<long long>(), rank_stride_elems, world};
   HIP_TRY(launch_stitch(src, C, p->d_regions, g.seq, canvas, g.H, g.W, gt_canvas, partials_dev,
                         dsx_stitch_psnr_blocks(g.ph, g.pw), (hipStream_t)stream));
+  return DSX_OK;
+}
+
+// ------------------------------------------------------------------ blended stitching (contract: include/dsx.h)
+extern "C" int dsx_tileplan_contributors(const dsx_tileplan* p, int32_t* rows, int32_t* cols) {
+  if (!p || !rows || !cols) return fail(DSX_ERR_INVALID, "tileplan_contributors: null argument");
+  if (!p->covers)
+    return fail(DSX_ERR_INVALID, "tileplan_contributors: the plan's tiles do not cover the frames (SHIFT tiling of (1, g, g) "
+                                 "grids does)");
+  memcpy(rows, p->rows.data(), p->rows.size() * 4);
+  memcpy(cols, p->cols.data(), p->cols.size() * 4);
+  return DSX_OK;
+}
+extern "C" int dsx_tileplan_set_window(dsx_tileplan* p, const float* wy_host, const float* wx_host) {
+  const char* what = "tileplan_set_window";
+  if (!p || !wy_host || !wx_host) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  const int64_t ph = p->t.p[1], pw = p->t.p[2];
+  for (int64_t i = 0; i < ph + pw; ++i) {
+    const float w = i < ph ? wy_host[i] : wx_host[i - ph];
+    if (!std::isfinite(w) || !(w > 0.f))
+      return fail(DSX_ERR_INVALID, "%s: %s[%lld] = %g: every window value must be finite and > 0", what, i < ph ? "wy" : "wx",
+                  (long long)(i < ph ? i : i - ph), (double)w);
+  }
+  p->window.assign(wy_host, wy_host + ph);
+  p->window.insert(p->window.end(), wx_host, wx_host + pw);
+  p->window_stale = true;                          // goes up once, at the next blend
+  return DSX_OK;
+}
+extern "C" int dsx_tileplan_blend_blocks(const dsx_tileplan* p) {
+  if (!p) return 0;
+  const BlendGrid bg = blend_grid(p->t.D[1], p->t.D[2]);
+  return bg.segs * bg.rows;
+}
+extern "C" int dsx_tileplan_blend(dsx_tileplan* p, const float* tiles_dev, int C, int world, int64_t rank_stride_elems,
+                                  float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream) {
+  const char* what = "tileplan_blend";
+  if (!p || !tiles_dev || !canvas_dev) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
+  if (world < 1) return fail(DSX_ERR_INVALID, "%s: world = %d, must be at least 1", what, world);
+  if (gt_canvas_dev && (!partials_dev || C > 4))
+    return fail(DSX_ERR_INVALID, "%s: PSNR sums need a partials buffer and C <= 4", what);
+  if (!p->covers)
+    return fail(DSX_ERR_INVALID, "%s: the plan's tiles do not cover the frames (SHIFT tiling of (1, g, g) grids does)", what);
+  if (p->window.empty()) return fail(DSX_ERR_INVALID, "%s: the plan has no window: call dsx_tileplan_set_window first", what);
+  if (p->t.D[0] > 65535) return fail(DSX_ERR_INVALID, "%s: %lld frames, at most 65535 per plan", what, (long long)p->t.D[0]);
+  if (p->total > INT32_MAX) return fail(DSX_ERR_INVALID, "%s: %lld tiles, the tile id must fit 31 bits", what, (long long)p->total);
+  const int64_t tile_elems = p->t.p[1] * p->t.p[2];
+  if ((int64_t)C > INT32_MAX / tile_elems)
+    return fail(DSX_ERR_INVALID, "%s: C * patch = %d * %lld x %lld exceeds 32 bits", what, C, (long long)p->t.p[1],
+                (long long)p->t.p[2]);
+  const int64_t most = (p->total + world - 1) / world;       // tiles of rank 0, the longest slot
+  if (world > 1 && (rank_stride_elems < 0 || most > rank_stride_elems / (tile_elems * C)))
+    return fail(DSX_ERR_INVALID, "%s: rank_stride_elems = %lld is smaller than rank 0's %lld whole tiles", what,
+                (long long)rank_stride_elems, (long long)most);
+  int rc = plan_device(p);
+  if (rc) return rc;
+  if (p->window_stale) {
+    if (!p->d_window.p) HIP_TRY(p->d_window.alloc(p->window.size() * 4));
+    if (hipMemcpy(p->d_window.p, p->window.data(), p->window.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+      return fail(DSX_ERR_HIP, "%s: upload of the window failed", what);
+    p->window_stale = false;
+  }
+  const BlendArgs a{tiles_dev, C, world, rank_stride_elems, (int)p->t.D[0], (int)p->t.D[1], (int)p->t.D[2], (int)p->t.p[1],
+                    (int)p->t.p[2], (int)p->t.dim_count(1), (int)p->t.dim_count(2), p->d_starts.as<int>(), p->d_rows,
+                    p->d_cols, p->d_window.as<float>(), p->d_window.as<float>() + p->t.p[1], canvas_dev, gt_canvas_dev,
+                    partials_dev};
+  HIP_TRY(launch_blend(a, (hipStream_t)stream));
+  return DSX_OK;
+}
+// tiles first + k * stride of the plan out of a (N,H,W,C) frame state -> (count, C, ph, pw)
+extern "C" int dsx_tileplan_gather_canvas(dsx_tileplan* p, const float* canvas_dev, int C, int64_t first, int64_t stride,
+                                          int64_t count, float* tiles_dev, void* stream) {
+  const char* what = "tileplan_gather_canvas";
+  if (!p) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
+  if ((int64_t)C > INT32_MAX / (p->t.p[1] * p->t.p[2]))
+    return fail(DSX_ERR_INVALID, "%s: C * patch = %d * %lld x %lld exceeds 32 bits", what, C, (long long)p->t.p[1],
+                (long long)p->t.p[2]);
+  if ((!canvas_dev || !tiles_dev) && count != 0) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  TileGeom g;
+  const int rc = geom_of_plan(what, p, first, stride, count, g);
+  if (rc || count == 0) return rc;
+  HIP_TRY(launch_tiles_gather_canvas(canvas_dev, C, g, tiles_dev, (hipStream_t)stream));
   return DSX_OK;
 }

@@ -449,4 +449,180 @@ hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions, TileSeq 
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Blended stitching (include/dsx.h, dsx_tileplan_blend): the overlap-add of all tiles of a plan as a GATHER.  A thread
+// owns canvas pixels and loops over the tiles that cover them, in ascending tile id; nothing is accumulated across
+// threads or launches, so the canvas is a function of the tiles alone.  Per pixel and channel, every operation rounded
+// on its own:
+//   one contributor: out = v (a copy)      else: num = num + w * v, den = den + w with w = wy[yy] * wx[xx]; out = num / den
+// Workgroup (sx, sy, n) owns the 256 pixels from x = 256 * sx of the rows y = sy, sy + gridDim.y, ... of frame n.  A
+// thread keeps its x: the tile columns that cover it, its offset xx into each and wx[xx] are read once, before the
+// rows (the first four columns stay in registers; a plan with more than four per pixel reads the rest per row).  The
+// contributing tile rows, yy and wy[yy] are uniform in the workgroup.  The contributors are the outer loops and the
+// channels the inner one, so a tile's address and weight are formed once for its C values; den is the same sum for
+// every channel.  Consecutive lanes read consecutive x of a tile row, one dword each (a shifted tile's rows are not
+// 16-byte aligned).  The C values of a pixel are contiguous in the canvas: WIDE writes them as one 8- / 16-byte store
+// (C = 2 / 4 and the canvas aligned to it), otherwise one dword per channel.  CT = C for C <= 4; CT = 0 is any C, one
+// channel after the other.  PSNR: the seven RangeInvariantPsnr sums of k_stitch_psnr per (frame, workgroup, channel),
+// through the same fixed-order block reduction (C <= 4).  No LDS beyond those slots, no atomics.
+// ---------------------------------------------------------------------------
+constexpr int kBlendCols = 4;                  // tile columns of a pixel kept in registers
+__device__ __forceinline__ const float* blend_tile(const BlendArgs& a, unsigned t, unsigned tile_elems) {
+  return a.world == 1 ? a.tiles + (size_t)t * tile_elems
+                      : a.tiles + (size_t)(t % (unsigned)a.world) * a.rank_stride + (size_t)(t / (unsigned)a.world) * tile_elems;
+}
+// any C: channel c of the pixel, the contributors in the same order
+__device__ __forceinline__ float blend_pixel(const BlendArgs& a, unsigned tile0, int ty0, int tyn, int tx0, int txn, int c,
+                                             int y, int x) {
+  const int plane = a.ph * a.pw;
+  float num = 0.f, den = 0.f, v = 0.f;
+  for (int iy = ty0; iy < ty0 + tyn; ++iy)
+    for (int ix = tx0; ix < tx0 + txn; ++ix) {
+      const unsigned t = tile0 + (unsigned)iy * a.nx + ix;
+      const int yy = y - a.starts[(size_t)t * 3 + 1], xx = x - a.starts[(size_t)t * 3 + 2];
+      v = blend_tile(a, t, (unsigned)plane * a.C)[c * plane + yy * a.pw + xx];
+      const float w = mul_f(a.wy[yy], a.wx[xx]);
+      num = add_f(num, mul_f(w, v));
+      den = add_f(den, w);
+    }
+  return tyn * txn == 1 ? v : __fdiv_rn(num, den);
+}
+template <int CT>
+__device__ __forceinline__ void blend_add(const BlendArgs& a, unsigned t, int plane, int off, float w, float v[CT], float num[CT],
+                                          float& den) {
+  const float* p = blend_tile(a, t, (unsigned)plane * CT) + off;
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    v[c] = p[c * plane];
+    num[c] = add_f(num[c], mul_f(w, v[c]));
+  }
+  den = add_f(den, w);
+}
+template <int CT, bool WIDE, bool PSNR>
+__global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
+  constexpr int NC = CT > 0 ? CT : 1;
+  __shared__ double red[PSNR ? 4 * kPsnrMaxC * 7 : 1];
+  const int n = blockIdx.z, x = blockIdx.x * 256 + threadIdx.x;
+  const bool live = x < a.W;
+  const unsigned tile0 = (unsigned)n * a.ny * a.nx;
+  const int plane = a.ph * a.pw;
+  int tx0 = 0, txn = 0, xo[kBlendCols];
+  float wxc[kBlendCols];
+  if (live) { tx0 = a.cols[2 * x]; txn = a.cols[2 * x + 1]; }
+#pragma unroll
+  for (int j = 0; j < kBlendCols; ++j) {       // tile (0, ix) of frame 0 starts at the x every tile of column ix starts at
+    xo[j] = 0; wxc[j] = 0.f;
+    if (CT > 0 && j < txn) { xo[j] = x - a.starts[(size_t)(tx0 + j) * 3 + 2]; wxc[j] = a.wx[xo[j]]; }
+  }
+  double sp[kPsnrMaxC], spp[kPsnrMaxC], sg[kPsnrMaxC], sgg[kPsnrMaxC], sgp[kPsnrMaxC], mn[kPsnrMaxC], mx[kPsnrMaxC];
+#pragma unroll
+  for (int c = 0; c < kPsnrMaxC; ++c) { sp[c] = spp[c] = sg[c] = sgg[c] = sgp[c] = 0; mn[c] = INFINITY; mx[c] = -INFINITY; }
+  for (int y = blockIdx.y; y < a.H; y += gridDim.y) {
+    if (!live) continue;
+    const int ty0 = a.rows[2 * y], tyn = a.rows[2 * y + 1];
+    const size_t cpix = (((size_t)n * a.H + y) * a.W + x) * a.C;
+    if (CT == 0) {
+      for (int c = 0; c < a.C; ++c) a.canvas[cpix + c] = blend_pixel(a, tile0, ty0, tyn, tx0, txn, c, y, x);
+      continue;
+    }
+    float num[NC], v[NC], den = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) num[c] = v[c] = 0.f;
+    for (int iy = ty0; iy < ty0 + tyn; ++iy) {
+      const unsigned trow = tile0 + (unsigned)iy * a.nx;       // tile (iy, 0): every tile of row iy starts at its y
+      const int yy = y - a.starts[(size_t)trow * 3 + 1];
+      const float wyv = a.wy[yy];
+#pragma unroll
+      for (int j = 0; j < kBlendCols; ++j)
+        if (j < txn) blend_add<NC>(a, trow + tx0 + j, plane, yy * a.pw + xo[j], mul_f(wyv, wxc[j]), v, num, den);
+      for (int j = kBlendCols; j < txn; ++j) {
+        const int xx = x - a.starts[(size_t)(tx0 + j) * 3 + 2];
+        blend_add<NC>(a, trow + tx0 + j, plane, yy * a.pw + xx, mul_f(wyv, a.wx[xx]), v, num, den);
+      }
+    }
+    float o[NC];
+    const bool one = tyn * txn == 1;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) o[c] = one ? v[c] : __fdiv_rn(num[c], den);
+    if (WIDE && NC == 2) *(float2*)(a.canvas + cpix) = make_float2(o[0], o[NC > 1 ? 1 : 0]);
+    else if (WIDE && NC == 4) *(float4*)(a.canvas + cpix) = make_float4(o[0], o[NC > 1 ? 1 : 0], o[NC > 2 ? 2 : 0], o[NC > 3 ? 3 : 0]);
+    else {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) a.canvas[cpix + c] = o[c];
+    }
+    if (PSNR) {
+#pragma unroll
+      for (int c = 0; c < NC && c < kPsnrMaxC; ++c) {
+        const float p = o[c], g = a.gt[cpix + c];
+        sp[c] += p; spp[c] += (double)p * p; sg[c] += g; sgg[c] += (double)g * g; sgp[c] += (double)g * p;
+        mn[c] = fmin(mn[c], (double)g); mx[c] = fmax(mx[c], (double)g);
+      }
+    }
+  }
+  if (PSNR) {
+    constexpr int kSlots = kPsnrMaxC * 7;
+#pragma unroll
+    for (int c = 0; c < kPsnrMaxC; ++c) {
+      block_park<RedSum>(sp[c], red, kSlots, c * 7);
+      block_park<RedSum>(spp[c], red, kSlots, c * 7 + 1);
+      block_park<RedSum>(sg[c], red, kSlots, c * 7 + 2);
+      block_park<RedSum>(sgg[c], red, kSlots, c * 7 + 3);
+      block_park<RedSum>(sgp[c], red, kSlots, c * 7 + 4);
+      block_park<RedMin>(mn[c], red, kSlots, c * 7 + 5);
+      block_park<RedMax>(mx[c], red, kSlots, c * 7 + 6);
+    }
+    __syncthreads();
+    if (threadIdx.x < a.C * 8) {
+      const int c = threadIdx.x >> 3, kk = threadIdx.x & 7;
+      double o = 0;
+      if (kk < 5) o = block_combine<RedSum, Pairwise>(red, kSlots, c * 7 + kk);
+      else if (kk == 5) o = block_combine<RedMin, Pairwise>(red, kSlots, c * 7 + 5);
+      else if (kk == 6) o = block_combine<RedMax, Pairwise>(red, kSlots, c * 7 + 6);
+      const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x, blocks = (size_t)gridDim.x * gridDim.y;
+      a.part[(((size_t)n * blocks + b) * a.C + c) * 8 + kk] = o;
+    }
+  }
+}
+template <int CT, bool WIDE>
+static void launch_blend_as(const BlendArgs& a, const dim3 grid, hipStream_t st) {
+  if (a.gt != nullptr) hipLaunchKernelGGL((k_blend<CT, WIDE, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_blend<CT, WIDE, false>), grid, dim3(256), 0, st, a);
+}
+hipError_t launch_blend(const BlendArgs& a, hipStream_t st) {
+  if (a.gt != nullptr && (a.C < 1 || a.C > kPsnrMaxC || a.part == nullptr)) return hipErrorInvalidValue;
+  if (a.N < 1 || a.N > 65535 || a.C < 1) return hipErrorInvalidValue;
+  const BlendGrid bg = blend_grid(a.H, a.W);
+  const dim3 grid((unsigned)bg.segs, (unsigned)bg.rows, (unsigned)a.N);
+  const uintptr_t at = (uintptr_t)a.canvas;
+  if (a.C == 1) launch_blend_as<1, false>(a, grid, st);
+  else if (a.C == 2 && (at & 7u) == 0) launch_blend_as<2, true>(a, grid, st);
+  else if (a.C == 2) launch_blend_as<2, false>(a, grid, st);
+  else if (a.C == 3) launch_blend_as<3, false>(a, grid, st);
+  else if (a.C == 4 && (at & 15u) == 0) launch_blend_as<4, true>(a, grid, st);
+  else if (a.C == 4) launch_blend_as<4, false>(a, grid, st);
+  else hipLaunchKernelGGL((k_blend<0, false, false>), grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// Tiles out of a multi-channel frame state: canvas (N,H,W,C) -> tiles (count, C, ph, pw), tile k of the launch cut at
+// its plan start.  A thread owns a pixel of the tile (consecutive lanes, consecutive x): it reads the C values of the
+// pixel, which are contiguous in the canvas, and writes one dword into each of the C planes.
+__global__ void k_tiles_gather_canvas(const float* __restrict__ canvas, int C, int H, int W, int ph, int pw,
+                                      const int* __restrict__ starts, TileSeq seq, float* __restrict__ tiles) {
+  const TileGeom g{H, W, ph, pw, starts, seq};
+  const long long k = blockIdx.y;
+  const TileOrigin o = tile_origin(g, k);
+  const int total = ph * pw;
+  float* __restrict__ tile = tiles + (size_t)k * C * total;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const float* src = canvas + tile_src(g, (size_t)o.n * H, o.y0, o.x0, i) * C;
+    for (int c = 0; c < C; ++c) tile[(size_t)c * total + i] = src[c];
+  }
+}
+hipError_t launch_tiles_gather_canvas(const float* canvas, int C, const TileGeom& g, float* tiles, hipStream_t st) {
+  hipLaunchKernelGGL(k_tiles_gather_canvas, dim3(tile_grid_x((long long)g.ph * g.pw), (unsigned)g.seq.count), dim3(256), 0,
+                     st, canvas, C, g.H, g.W, g.ph, g.pw, g.starts, g.seq, tiles);
+  return hipGetLastError();
+}
+
 }  // namespace dsx

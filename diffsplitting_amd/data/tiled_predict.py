@@ -14,13 +14,22 @@ class TileExchange:
     """The stitched output of a sharded run.  One rank: every batch is pasted straight into the canvas.  Several ranks:
     every batch's VALID REGIONS are packed into this rank's run of the exchange buffer (the crop of
     tile_stitcher.py:38-56 before the collective), one all-gather of the equal-sized runs (RCCL over xGMI) moves
-    canvas bytes + padding instead of whole (C, p, p) tiles, and every rank pastes from the packed layout."""
+    canvas bytes + padding instead of whole (C, p, p) tiles, and every rank pastes from the packed layout.
 
-    def __init__(self, plan, channels, device, group=None, gt=None):
+    ``blend=True``: blended stitching (``TilePlan.blend``) under ``window``.  This rank's WHOLE predicted tiles stay in a
+    resident buffer -- its slot of the exchange buffer, tile ``id`` at index ``id // world`` --, ``add`` copies a batch
+    in, and ``finish`` is one all-gather of the equal-sized slots (several ranks) and one blend of all tiles."""
+
+    def __init__(self, plan, channels, device, group=None, gt=None, blend=False, window="triangle"):
         self.plan, self.C, self.group, self.gt = plan, int(channels), group, gt
         self.rank, self.world = parallel.rank(), parallel.world_size()
         self.canvas = self.part = self.flat = None
-        if self.world == 1:
+        self.blend = bool(blend)
+        if self.blend:
+            plan.set_window(window)
+            self.flat = torch.zeros(plan.blend_rank_stride(self.world, self.C), dtype=torch.float32, device=device)
+            self.tiles = self.flat.view((-1, self.C) + plan.patch_shape[1:])
+        elif self.world == 1:
             self.canvas = torch.zeros(plan.data_shape + (self.C,), dtype=torch.float32, device=device)
             if gt is not None:
                 self.part = plan.new_psnr_partials(self.C, device)
@@ -31,7 +40,10 @@ class TileExchange:
         """``tiles`` (b, C, p, p): predictions of this rank's tile ids ``ids`` (a batch of its shard, in order)."""
         if len(ids) == 0:
             return
-        if self.world == 1:
+        if self.blend:
+            j = int(ids[0]) // self.world
+            self.tiles[j:j + len(ids)].copy_(tiles)
+        elif self.world == 1:
             if self.gt is not None:
                 self.plan.stitch_psnr_into(tiles, ids, self.canvas, self.gt, self.part)
             else:
@@ -45,6 +57,11 @@ class TileExchange:
 
     def finish(self):
         """-> canvas (N,H,W,C), or (canvas, psnr (N,C)) when a ground truth was given."""
+        if self.blend:
+            if self.world == 1:
+                return self.plan.blend(self.tiles, gt=self.gt)
+            full = parallel.all_gather_flat(self.flat, self.group)   # one collective per canvas, of whole tiles
+            return self.plan.blend(full, world=self.world, gt=self.gt, Cn=self.C)
         if self.world == 1:
             return self.canvas if self.gt is None else (self.canvas, self.plan.psnr_from_partials(self.part))
         full = parallel.all_gather_flat(self.flat, self.group)       # the path's only collective
@@ -53,7 +70,7 @@ class TileExchange:
 
 @torch.no_grad()
 def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8, sampler_kwargs=None,
-                  group=None, lpips=None, target_frames=None, seed=None):
+                  group=None, lpips=None, target_frames=None, seed=None, stitch="crop", window="triangle"):
     """``frames_input``: (N,H,W) fp32 CUDA tensor, already normalised (the network input channel).
     Returns the stitched prediction (N,H,W,C) on every rank and the ``TilePlan``.
 
@@ -66,7 +83,11 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
 
     ``seed``: per-sample noise streams (include/dsx.h) with a tile's id as its sample id: a tile's noise then does not
     depend on ``batch_tiles``, on the order of the batches or on the number of ranks, and neither does its prediction
-    as long as the batch size is the same (the planner may pick other kernels for another)."""
+    as long as the batch size is the same (the planner may pick other kernels for another).
+
+    ``stitch``: ``"crop"`` pastes every tile's inner region (the reference's stitch); ``"blend"`` overlap-adds the whole
+    tiles under the separable ``window`` (``TilePlan.blend``)."""
+    _check_stitch("predict_tiled", stitch, window)
     if grid_size is None:
         grid_size = patch_size // 2                                   # split_dataset_tiledpred.py:13-14
     N, H, W = frames_input.shape
@@ -74,7 +95,7 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
     rank, world = parallel.rank(), parallel.world_size()
     ids = parallel.shard_ids(plan.total, rank, world)
     kw = dict(sampler_kwargs or {})
-    ex = TileExchange(plan, netG.prediction_channels, frames_input.device, group)
+    ex = TileExchange(plan, netG.prediction_channels, frames_input.device, group, blend=stitch == "blend", window=window)
     for i in range(0, len(ids), batch_tiles):
         chunk = ids[i:i + batch_tiles]
         tiles = plan.gather(frames_input, chunk).unsqueeze(1)         # (b,1,p,p)
@@ -89,6 +110,14 @@ def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8,
         raise ValueError("predict_tiled(lpips=...) needs target_frames (N,H,W,C) to compare the prediction with")
     from ..core.metrics import calculate_lpips
     return (canvas, calculate_lpips(target_frames, canvas, lpips)), plan
+
+
+def _check_stitch(what, stitch, window):
+    from .tiling import WINDOWS
+    if stitch not in ("crop", "blend"):
+        raise DsxError(f"{what}: stitch = {stitch!r}: 'crop' or 'blend'")
+    if stitch == "blend" and isinstance(window, str) and window not in WINDOWS:
+        raise DsxError(f"{what}: window = {window!r}: one of {', '.join(WINDOWS)}, or a pair of arrays (wy, wx)")
 
 
 def _is_gaussian(netG):
@@ -132,7 +161,7 @@ def _stochastic_rows(netG, num_timesteps, solver):
 
 @torch.no_grad()
 def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None,
-                  solver=None, noise="samples", field_noise_bytes=2 << 30):
+                  solver=None, noise="samples", field_noise_bytes=2 << 30, stitch=None, window="triangle", fuse=False):
     """The tiled prediction of a dataset that cuts its own normalised tiles -- an ``InputStackTiledPred`` (one
     superimposed acquisition, no ground truth) or a ``SplitDatasetTiledPred`` -- with ``samples`` posterior samples per
     tile: their mean and, with ``return_std``, the unbiased per-pixel spread, accumulated by one fused launch per sample
@@ -153,7 +182,19 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     (``TilePlan.randn_field``): a function of (seed, frame, draw ordinal, channel, y, x), so overlapping tiles start from
     -- and, in a stochastic row, receive -- the same noise where they overlap; posterior sample ``r`` takes
     ``id_base = r * frames``.  The draws travel in the loop's injected form, one (B, C, p, p) tensor per stochastic
-    row; more than ``field_noise_bytes`` of them per batch is refused.  ``noise="samples"``: the streams above."""
+    row; more than ``field_noise_bytes`` of them per batch is refused.  ``noise="samples"``: the streams above.
+
+    ``stitch``: ``"crop"`` (the default) pastes every tile's inner region; ``"blend"`` overlap-adds the whole tiles under
+    the separable ``window`` (``TilePlan.blend``: "triangle", "hann" or a pair of arrays) -- 'mean', 'std' and 'psnr'
+    then each come from a blend.
+
+    ``fuse=True`` (a Gaussian sampler with ``solver``, ``noise="field"`` and ``seed``, one rank; ``stitch`` is then
+    "blend"): per-step frame fusion.  Every posterior sample diffuses each frame as ONE state (N,H,W,C), started from the
+    noise field's draw 0: for every solver row the tiles are cut out of the state (``TilePlan.gather_canvas``), go
+    through one UNet forward and one ``engine.solver_step`` per batch -- with the crops of the field's draw ``s + 1``
+    where the row adds noise and the tiles of the blended x0 of the row before where it has a history term --, and are
+    blended back into the state.  The state after the last row is the sample; with one tile per frame this is the
+    unfused chain bit for bit."""
     from .. import engine
     samples = int(samples)
     if samples < 1:
@@ -164,7 +205,30 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
                        "loop already takes num_timesteps")
     if noise not in ("samples", "field"):
         raise DsxError(f"predict_stack: noise = {noise!r}: 'samples' or 'field'")
+    if fuse:
+        if stitch == "crop":
+            raise DsxError("predict_stack: fuse with stitch='crop': a fused frame is a blend of its tiles; leave stitch "
+                           "out or give 'blend'")
+        if not _is_gaussian(netG):
+            raise DsxError(f"predict_stack: fuse: {type(netG).__name__} is not a Gaussian sampler (sr3 / ddpm); fusion "
+                           "for the InDI family is not provided")
+        if not solver:
+            raise DsxError("predict_stack: fuse needs solver=: the rows of a few-step solver are fused; the ancestral "
+                           "loop is not")
+        if noise != "field" or seed is None:
+            raise DsxError("predict_stack: fuse needs noise='field' and seed=: overlapping tiles must receive the same "
+                           "noise, or the blend would shrink its variance")
+        if parallel.world_size() > 1:
+            raise DsxError("predict_stack: fuse runs on one rank: a collective after every solver row is not provided")
+        stitch = "blend"
+    stitch = "crop" if stitch is None else stitch
+    _check_stitch("predict_stack", stitch, window)
+    blend = stitch == "blend"
     field = noise == "field"
+    if fuse:
+        if samples * plan.data_shape[0] > (1 << 39):
+            raise DsxError("predict_stack: samples * frames exceeds the 2^39 field ids of one sampler")
+        return _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window), plan
     if field:
         if seed is None:
             raise DsxError("predict_stack: noise='field' needs seed=: a noise field is named by (seed, frame, draw)")
@@ -192,8 +256,8 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
             chunk = ids[i:i + batch_tiles]
             x = dataset.tiles(chunk)["input"]
             if ex is None:
-                ex = TileExchange(plan, C_out, x.device, group, gt=gt)
-                ex_std = TileExchange(plan, C_out, x.device, group) if return_std else None
+                ex = TileExchange(plan, C_out, x.device, group, gt=gt, blend=blend, window=window)
+                ex_std = TileExchange(plan, C_out, x.device, group, blend=blend, window=window) if return_std else None
             mean = m2 = None
             for r in range(samples):
                 kw = {}
@@ -224,13 +288,87 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
                     child.noise_field = None
     if ex is None:                                                    # a rank without tiles still joins the collectives
         dev = torch.device("cuda", torch.cuda.current_device())
-        ex = TileExchange(plan, C_out, dev, group, gt=gt)
-        ex_std = TileExchange(plan, C_out, dev, group) if return_std else None
+        ex = TileExchange(plan, C_out, dev, group, gt=gt, blend=blend, window=window)
+        ex_std = TileExchange(plan, C_out, dev, group, blend=blend, window=window) if return_std else None
     res = ex.finish()
     out = {"mean": res[0], "psnr": res[1]} if gt is not None else {"mean": res}
     if return_std:
         out["std"] = ex_std.finish()
     return out, plan
+
+
+def fused_sample(netG, dataset, table, batch_tiles, seed, id_base, order=None, keep_tiles=None):
+    """One posterior sample of per-step frame fusion -> the frame state (N,H,W,C) after the last row of ``table`` (a
+    ``SolverTableHost``).  The state starts as draw 0 of the noise fields ``id_base + n``; per row and batch of tiles:
+    ``gather_canvas`` -> ``denoise_fn`` -> ``engine.solver_step`` -> two resident (total, C, p, p) buffers; after the
+    row's last batch the x tiles are blended into the state, the x0 tiles into the history when the next row reads it.
+    The last short batch is moved back to end at the last tile (one executor, one batch size).  ``order``: a permutation
+    of the batches (the result does not depend on it).  ``keep_tiles``: a list that receives the x tiles of every row
+    before their blend (a copy per row)."""
+    from .. import engine
+    plan = dataset.plan
+    N, H, W = plan.data_shape
+    Cn, dev = int(netG.channels), netG.betas.device
+    X = engine.randn_samples((N, Cn, H, W), seed, [id_base + n for n in range(N)], draw=0, device=dev)
+    X = X.permute(0, 2, 3, 1).contiguous()
+    X0 = None
+    shape = (plan.total, Cn) + plan.patch_shape[1:]
+    xt, x0t = torch.empty(shape, device=dev), torch.empty(shape, device=dev)
+    batches = [(list(chunk), keep) for chunk, keep in _batches(range(plan.total), batch_tiles)]
+    if order is not None:
+        batches = [batches[i] for i in order]
+    K = table.n_steps
+    for s in range(K):
+        for chunk, keep in batches:
+            B = len(chunk)
+            col = lambda name: torch.full((B,), float(getattr(table, name)[s]), device=dev)
+            x = plan.gather_canvas(X, chunk)
+            inp = torch.cat([dataset.tiles(chunk)["input"], x], dim=1) if netG.conditional else x
+            time = col("tcond").view(B, 1) if netG.kind == "sr3" else col("tcond")
+            net = netG.denoise_fn(inp, time)
+            z = plan.randn_field(chunk, Cn, seed, draw=s + 1, id_base=id_base, device=dev) if table.sigma[s] != 0 else None
+            hist = table.cp[s] != 0
+            x0, xo = engine.solver_step(x, net, col("a"), col("b"), col("cx"), col("c0"), col("sigma"),
+                                        cp=col("cp") if hist else None,
+                                        x0_prev=plan.gather_canvas(X0, chunk) if hist else None, clip=table.clip, z=z)
+            last = chunk[-1] + 1
+            xt[last - keep:last] = xo[B - keep:]
+            x0t[last - keep:last] = x0[B - keep:]
+        if keep_tiles is not None:
+            keep_tiles.append(xt.clone())
+        X = plan.blend(xt)
+        if s + 1 < K and table.cp[s + 1] != 0:
+            X0 = plan.blend(x0t)
+    return X
+
+
+def _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window):
+    """``predict_stack(fuse=True)`` after its checks: the frame states of the posterior samples (``fused_sample``) are the
+    stitched frames -- their mean and spread come from ``engine.moments_update`` over whole frames, and 'psnr' from a
+    paste of the mean's own tiles (a copy) against the ground truth."""
+    from .. import engine
+    plan = dataset.plan
+    plan.set_window(window)
+    table = netG.solver_table(**solver)
+    mean = m2 = X = None
+    for r in range(samples):
+        X = fused_sample(netG, dataset, table, batch_tiles, seed, r * plan.data_shape[0])
+        if samples > 1:
+            mean, m2 = engine.moments_update(X, mean, m2, r)
+    spread = None
+    if samples > 1:
+        X, spread = engine.moments_finish(mean, m2, samples, want_std=return_std)
+    elif return_std:
+        spread = torch.zeros_like(X)
+    out = {"mean": X}
+    C_out = netG.prediction_channels
+    if hasattr(dataset, "normalized_target_frames"):
+        gt = dataset.normalized_target_frames()
+        if gt.shape[-1] == C_out and C_out <= 4 and X.shape[-1] == C_out:
+            out["psnr"] = plan.stitch_with_psnr(plan.gather_canvas(X), gt)[1]
+    if return_std:
+        out["std"] = spread
+    return out
 
 
 # ---- mixed-input evaluation (BASELINE C5: JointIndi + TimePredictor) -----------------------------------------------

@@ -29,6 +29,24 @@ def as_sequence(ids):
     return int(ids[0]), d, int(ids.size)
 
 
+WINDOWS = ("triangle", "hann")
+
+
+def window(name, n):
+    """The 1-D blend window ``name`` over ``n`` pixels, float32, every value > 0.  ``"triangle"``: min(i + 1, n - i),
+    integers, so the products of two of them are exact in fp32 up to n = 512.  ``"hann"``: sin^2(pi (i + 1/2) / n),
+    computed in float64 and rounded to fp32 once."""
+    n = int(n)
+    if n < 1:
+        raise DsxError(f"window: n = {n}, must be at least 1")
+    i = np.arange(n, dtype=np.float64)
+    if name == "triangle":
+        return np.minimum(i + 1, n - i).astype(np.float32)
+    if name == "hann":
+        return (np.sin(np.pi * (i + 0.5) / n) ** 2).astype(np.float32)
+    raise DsxError(f"window: {name!r} is not a window; one of {', '.join(WINDOWS)}")
+
+
 class TilePlan:
     """All tiles of data (N,H,W) for a (1,g,g) grid and (1,p,p) patches —
     what ``SplitDatasetTiledPred.__init__`` sets up (split_dataset_tiledpred.py:9-24).
@@ -201,10 +219,10 @@ class TilePlan:
 
     def psnr_from_partials(self, partials):
         """(N, C) RangeInvariantPsnr (core/psnr.py:70-82) from the partial-sum rows of all tiles."""
-        N = self.data_shape[0]
-        per = self.total // N                                       # tile ids are frame-major (tiling_manager.py:145-154)
-        gx, Cn = partials.shape[1], partials.shape[2]
-        p = partials.view(N, per * gx, Cn, 8)
+        N = self.data_shape[0]                                      # tile ids are frame-major (tiling_manager.py:145-154)
+        Cn = partials.shape[2]
+        # rows of a paste, [total][blocks][C][8] (frame-major tiles), or of a blend, [N][blocks][C][8]
+        p = partials.view(N, -1, Cn, 8)
         s = p[..., :5].sum(dim=1)                                    # fixed order: reproducible
         gmin, gmax = p[..., 5].amin(dim=1), p[..., 6].amax(dim=1)
         return range_invariant_psnr_from_sums(s[..., 0], s[..., 1], s[..., 2], s[..., 3], s[..., 4], gmin, gmax,
@@ -266,6 +284,89 @@ class TilePlan:
             part = self.new_psnr_partials(Cn, flat_all.device)
         check(lib.dsx_tileplan_paste_packed(self.handle, flat_all, int(Cn), int(world), stride, canvas, gt, part, None))
         return canvas if gt is None else (canvas, self.psnr_from_partials(part))
+
+    # ---- blended stitching: the overlap-add of all tiles (dsx_tileplan_blend) ---------------------------------------
+    def contributors(self):
+        """Host only: (rows (H, 2), cols (W, 2)) int32 -- per canvas row (first tile row, count), per canvas column
+        (first tile column, count).  Tile (iy, ix) of frame n has id (n * ny + iy) * nx + ix."""
+        rows = np.zeros((self.data_shape[1], 2), dtype=np.int32)
+        cols = np.zeros((self.data_shape[2], 2), dtype=np.int32)
+        check(lib.dsx_tileplan_contributors(self.handle, rows.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            cols.ctypes.data_as(C.POINTER(C.c_int32))))
+        return rows, cols
+
+    def set_window(self, win):
+        """The separable blend window of the plan: a name of ``WINDOWS`` or a pair ``(wy (ph,), wx (pw,))`` of arrays,
+        every value finite and > 0.  Host only; goes to the device once, at the next ``blend``."""
+        if isinstance(win, str):
+            wy, wx = window(win, self.patch_shape[1]), window(win, self.patch_shape[2])
+        else:
+            wy, wx = (np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1)) for w in win)
+        if wy.size != self.patch_shape[1] or wx.size != self.patch_shape[2]:
+            raise DsxError(f"set_window: the window must have {self.patch_shape[1]} and {self.patch_shape[2]} values, "
+                           f"got {wy.size} and {wx.size}")
+        check(lib.dsx_tileplan_set_window(self.handle, wy, wx))
+        self._window = (wy, wx)
+
+    def blend_blocks(self):
+        return int(lib.dsx_tileplan_blend_blocks(self.handle))
+
+    def blend_rank_stride(self, world, Cn):
+        """Elements of one rank's slot of WHOLE tiles in the exchange buffer of a blend: rank 0's, the longest."""
+        return -(-self.total // int(world)) * int(Cn) * self.patch_shape[1] * self.patch_shape[2]
+
+    def blend(self, tiles, world=1, gt=None, canvas=None, Cn=None):
+        """Every tile of the plan, overlap-added under the plan's window (``set_window`` first) -> canvas (N,H,W,C);
+        with ``gt`` also the (N, C) RangeInvariantPsnr: (canvas, psnr).  ``world == 1``: ``tiles`` (total, C, ph, pw).
+        ``world > 1``: the gathered exchange buffer of ``world`` equal slots, rank q's holding its whole tiles q,
+        q + world, ... back to back, with ``Cn`` channels.  The result depends on the tiles alone, not on the layout.
+        The partial-sum rows of the last call, (N, blend_blocks, C, 8) float64 or None, stay in ``last_blend_partials``."""
+        _lib.require_gpu()
+        world = int(world)
+        if world == 1:
+            tiles = self._check_tiles(tiles)
+            if tiles.shape[0] != self.total:
+                raise DsxError("blend needs every tile of the plan")
+            Cn, stride = int(tiles.shape[1]), 0
+        else:
+            tiles = tiles.contiguous()
+            if Cn is None or tiles.dtype != torch.float32 or not tiles.is_cuda:
+                raise DsxError("blend: a gathered buffer is a float32 CUDA tensor and needs its channel count Cn")
+            Cn, stride = int(Cn), tiles.numel() // world
+            if stride < self.blend_rank_stride(world, Cn):
+                raise DsxError("blend: the gathered buffer must hold world slots of blend_rank_stride elements")
+        if canvas is None:
+            canvas = torch.empty(self.data_shape + (Cn,), dtype=torch.float32, device=tiles.device)
+        part = None
+        if gt is not None:
+            gt = self._check_gt(gt, Cn)
+            part = torch.zeros((self.data_shape[0], self.blend_blocks(), Cn, 8), dtype=torch.float64, device=tiles.device)
+        check(lib.dsx_tileplan_blend(self.handle, tiles, Cn, world, stride, canvas, gt, part, None))
+        self.last_blend_partials = part
+        return canvas if gt is None else (canvas, self.psnr_from_partials(part))
+
+    def gather_canvas(self, canvas, tile_ids=None):
+        """The tiles ``tile_ids`` cut out of a multi-channel frame state ``canvas`` (N,H,W,C) fp32 CUDA -> (count, C, ph,
+        pw), bit for bit the slices.  An arithmetic id sequence takes one launch, any other list one launch per tile."""
+        _lib.require_gpu()
+        if not canvas.is_cuda or canvas.dtype != torch.float32 or canvas.dim() != 4 or \
+                tuple(canvas.shape[:3]) != self.data_shape:
+            raise DsxError(f"gather_canvas: canvas must be a float32 CUDA tensor of shape {self.data_shape + ('C',)}")
+        canvas = canvas.contiguous()
+        ids = self._ids(tile_ids)
+        Cn = int(canvas.shape[3])
+        out = torch.empty((len(ids), Cn, self.patch_shape[1], self.patch_shape[2]), dtype=torch.float32,
+                          device=canvas.device)
+        call = lambda first, stride, count, dst: check(lib.dsx_tileplan_gather_canvas(
+            self.handle, canvas, Cn, first, stride, count, dst, None))
+        seq = as_sequence(ids)
+        if seq is not None:
+            for k0 in range(0, seq[2], 65535):
+                call(seq[0] + k0 * seq[1], seq[1], min(65535, seq[2] - k0), out[k0:])
+        else:
+            for k, i in enumerate(ids):
+                call(int(i), 1, 1, out[k:])
+        return out
 
 
 def range_invariant_psnr_from_sums(sp, spp, sg, sgg, sgp, gmin, gmax, n):

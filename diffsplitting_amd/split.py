@@ -43,6 +43,11 @@ An ``sr3`` / ``ddpm`` config (the reference's ``config/splitting.json``) runs it
 the trained schedule instead (``model/solvers.py``).  ``--noise-field`` (needs ``--sample-seed S``) cuts every tile's noise
 from one field per frame -- a draw is a function of (seed, frame, draw ordinal, channel, y, x) -- so that overlapping
 tiles share the noise of their overlap; posterior sample ``r`` draws from the fields ``r * frames + frame``.
+
+``--stitch blend [--window triangle|hann]`` overlap-adds the whole predicted tiles under a separable window instead of
+pasting every tile's inner region (``--stitch crop``, the default); it works for every sampler.  ``--fuse-steps`` (with
+``--solver``, ``--sample-seed S`` and ``--noise-field``, one rank) diffuses every frame as one state: after every solver
+row the tiles are blended on a frame canvas and cut out again.
 """
 import argparse
 import logging
@@ -214,8 +219,17 @@ def main(argv=None):
     ap.add_argument("--noise-field", action="store_true",
                     help="with --sample-seed: cut every tile's noise from one field per frame (seed, frame, draw, "
                          "channel, y, x), so that overlapping tiles share the noise of their overlap")
+    ap.add_argument("--stitch", type=str, default=None, choices=["crop", "blend"],
+                    help="how the predicted tiles become a frame: paste every tile's inner region (crop, the default) "
+                         "or overlap-add whole tiles under --window (blend)")
+    ap.add_argument("--window", type=str, default=None, choices=["triangle", "hann"],
+                    help="with --stitch blend: the separable blend window (default triangle)")
+    ap.add_argument("--fuse-steps", action="store_true",
+                    help="with --solver, --sample-seed and --noise-field: diffuse every frame as one state -- after every "
+                         "solver row the tiles are blended on a frame canvas and cut out again (implies --stitch blend)")
     args = ap.parse_args(argv)
     _check_solver_args(args)
+    _check_stitch_args(args, len(str(args.gpu_ids).split(",")) if args.gpus is None else args.gpus)
     if args.sample_seed is not None and args.validate:
         raise SystemExit("--sample-seed names the tiles of a tiled prediction: not with --validate")
     if args.phase == "train":
@@ -346,7 +360,8 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     # pasting, and the path's only collectives are the cropped tiles of each output canvas
     out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
                               return_std=bool(args.std_out), seed=args.sample_seed, solver=solver,
-                              noise="field" if args.noise_field else "samples")
+                              noise="field" if args.noise_field else "samples", stitch=args.stitch,
+                              window=args.window or "triangle", fuse=args.fuse_steps)
     pred, ps = out["mean"], out.get("psnr")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -451,6 +466,31 @@ def _check_solver_args(args):
         solvers.check_solver(args.solver, args.eta or 0.0)
     except DsxError as e:
         raise SystemExit(f"--solver {args.solver} --eta {args.eta}: {e}")
+
+
+def _check_stitch_args(args, n_ranks):
+    """The flags of blended stitching and of per-step frame fusion, checked on the command line alone (nothing touches
+    the GPU, no rank is started).  Without any of them: nothing."""
+    blend = args.stitch == "blend" or args.fuse_steps
+    if args.window is not None and not blend:
+        raise SystemExit("--window: only with --stitch blend (the window weighs the overlap-add of whole tiles)")
+    if args.stitch == "blend" and (args.validate or args.mix_t is not None):
+        raise SystemExit("--stitch blend stitches the tiles of a tiled prediction: not with --validate or --mix-t")
+    if not args.fuse_steps:
+        return
+    if args.validate or args.mix_t is not None:
+        raise SystemExit("--fuse-steps fuses the tiles of a tiled prediction: not with --validate or --mix-t")
+    if args.stitch == "crop":
+        raise SystemExit("--fuse-steps with --stitch crop: a fused frame is a blend of its tiles; leave --stitch out or give "
+                         "--stitch blend")
+    if args.solver is None:
+        raise SystemExit("--fuse-steps needs --solver {ddim,dpmpp2m}: the rows of a few-step solver are fused; the "
+                         "ancestral loop is not")
+    if args.sample_seed is None or not args.noise_field:
+        raise SystemExit("--fuse-steps needs --sample-seed S and --noise-field: overlapping tiles must receive the same "
+                         "noise, or the blend would shrink its variance")
+    if n_ranks > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--fuse-steps runs on one rank: a collective after every solver row is not provided")
 
 
 def _solver_of(args):

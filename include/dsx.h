@@ -761,6 +761,41 @@ int dsx_tileplan_pack(dsx_tileplan* plan, const float* tiles_dev, int C, int wor
                       float* flat_rank_dev, void* stream);
 int dsx_tileplan_paste_packed(dsx_tileplan* plan, const float* flat_all_dev, int C, int world, int64_t rank_stride_elems,
                               float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream);
+/* Blended stitching: the overlap-add of ALL predicted tiles of a plan into the canvas, instead of the paste of their
+ * inner regions.  The plan's tiles must cover the frames with one frame per tile (SHIFT tiling of a (1, g, g) grid):
+ * along an axis the patch starts are then 0, g, 2g, .., D - p, strictly increasing, so the tiles that cover a canvas
+ * row (column) are one contiguous range of tile rows (columns).
+ *   dsx_tileplan_contributors: host only; rows [H][2] = per canvas row (first tile row, count), cols [W][2] = per canvas
+ *     column (first tile column, count).  Tile (iy, ix) of frame n has id (n*ny + iy)*nx + ix.
+ *   dsx_tileplan_set_window: the separable window w(yy, xx) = wy[yy] * wx[xx] over a tile, wy_host [ph], wx_host [pw];
+ *     host only.  Every value must be finite and > 0, or DSX_ERR_INVALID names the first that is not.  The window goes
+ *     up once, at the next blend; a later call replaces it.
+ *   dsx_tileplan_blend: tiles_dev holds every tile of the plan as whole (C, ph, pw) tiles -- world == 1: (total, C, ph,
+ *     pw); world > 1: the gathered exchange buffer [world][rank_stride_elems], rank q's slot holding its tiles q,
+ *     q + world, ... back to back (the sharding of dsx_tileplan_pack_layout, with whole tiles).  Per canvas pixel and
+ *     channel, fp32, every operation rounded on its own (no fma), the division correctly rounded, the contributors in
+ *     ASCENDING TILE ID:
+ *         one contributor:  out = v                                   (a copy: the bits do not change)
+ *         else  num = 0; den = 0;  per contributor:  w = wy[yy] * wx[xx];  num = num + w * v;  den = den + w
+ *               out = num / den
+ *     The kernel is a gather (a thread owns canvas pixels and loops over their tiles; no atomics, nothing accumulated
+ *     across launches), so canvas_dev (N,H,W,C) is a function of the tiles alone, and every pixel is written exactly
+ *     once.  gt_canvas_dev != NULL: the same pass writes the seven RangeInvariantPsnr sums of dsx_stitch_psnr per
+ *     (frame, workgroup, channel) into partials_dev [N][dsx_tileplan_blend_blocks][C][8] (C <= 4), through the
+ *     fixed-order block reduction: equal inputs give equal bits.
+ *     Null pointers, C < 1, world < 1, a plan that does not cover its frames, a plan without a window, more than 65535
+ *     frames, C * ph * pw beyond 32 bits and a rank_stride_elems below rank 0's whole tiles are DSX_ERR_INVALID before
+ *     any HIP call.  No allocation, copy or synchronisation per call (the tables and the window go up at first use).
+ *   dsx_tileplan_gather_canvas: the inverse cut -- the tiles first + k*stride, k < count, of the plan out of a
+ *     multi-channel frame state canvas_dev (N,H,W,C) -> tiles_dev (count, C, ph, pw), bit for bit the slices.  Refusals
+ *     as dsx_tileplan_randn's, under the name tileplan_gather_canvas. */
+int dsx_tileplan_contributors(const dsx_tileplan* plan, int32_t* rows /*[H][2]*/, int32_t* cols /*[W][2]*/);
+int dsx_tileplan_set_window(dsx_tileplan* plan, const float* wy_host /*ph*/, const float* wx_host /*pw*/);
+int dsx_tileplan_blend_blocks(const dsx_tileplan* plan);
+int dsx_tileplan_blend(dsx_tileplan* plan, const float* tiles_dev, int C, int world, int64_t rank_stride_elems,
+                       float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream);
+int dsx_tileplan_gather_canvas(dsx_tileplan* plan, const float* canvas_dev, int C, int64_t first, int64_t stride,
+                               int64_t count, float* tiles_dev, void* stream);
 
 /* ------------------------------------------------- frame files: uncompressed TIFF / BigTIFF stacks (host only)
  * Replaces imread(fpath, plugin='tifffile') of the Hagen loaders (data/split_dataset.py:76-91) for the files the
