@@ -39,13 +39,13 @@ namespace dsx {
 template <typename DT, int MB, int WM, int WN, int KS, int S, int CPG, int D, int MAX_IT>
 __global__ __launch_bounds__(256, ((KS == 3 && CPG == 2) ? 2   // two-chunk 3 x 3 variant: up to 11 staging units per thread in flight (spills at 168 VGPRs)
                                   : (MB == 1 ? (S == 2 ? 3 : 4) : (MB == 2 ? 3 : (MB == 4 ? 2 : 1))))) void k_conv_mfma(const ConvArgs a);   // dsx_conv_mfma.hip
-template <typename DT, int MB, int WM, int WN, int NB, int KS, int CPG, int D, int NIT, int P, int LW>
+template <typename DT, int MB, int WM, int WN, int NB, int KS, int CPG, int D, int NIT, int P, int LW, bool DIRECT>
 __global__ __launch_bounds__(256 + 64 * LW, 1) void k_conv_ws(const ConvArgs a);   // dsx_conv_ws.hip
 template <typename DT, int KS, int NPH> __global__ __launch_bounds__(512, 1) void k_conv_img(const ConvArgs a);   // dsx_conv_img.hip
 
 enum ConvFamily { FAM_MFMA, FAM_WS, FAM_IMG };
 struct ConvVariant {
-  int family, dtype, tile, ks, stride, cpg;   // the key.  cpg: chunks per staged group (k_conv_img: NPH, and tile -1)
+  int family, dtype, tile, ks, stride, cpg;   // the key (with `direct`).  cpg: chunks per staged group (k_conv_img: NPH, and tile -1)
   void (*kern)(const ConvArgs);
   int block, lds_cap;   // threads per workgroup; dynamic-LDS limit: kLdsDefault, or kLdsMax (set by conv_init)
   int MB, WM, WN, NB;   // wave layout: the tile is 32 MB WM pixels x 32 WN NB channels; WM statistics rows per tile
@@ -53,6 +53,7 @@ struct ConvVariant {
   int nit;              // 16-byte staging units per (loader) thread and group
   int depth, nbuf;      // k_conv_ws: raw groups in flight beyond the current one (P), MFMA images
   bool fuses_stats;     // the epilogue can emit the GroupNorm partial sums of the result
+  bool direct;          // k_conv_ws, part of the key: the loaders DMA straight into the MFMA images (ConvArgs::ws_direct)
 };
 static constexpr int kLdsDefault = 64 * 1024, kLdsMax = 160 * 1024;
 static constexpr int conv_cpg(int ks) { return ks == 1 ? 2 : 1; }   // the families' default chunks per group
@@ -74,7 +75,7 @@ constexpr ConvVariant mfma_row() {
   constexpr int PX = mfma_max_px(32 * MB * WM, KS, S, CPG);
   constexpr int MI = (PX * 4 * CPG + 255) / 256;   // 4 CPG 16-byte units per pixel and group, either storage type
   return {FAM_MFMA, Kind<DT>::value, TILE, KS, S, CPG, k_conv_mfma<DT, MB, WM, WN, KS, S, CPG, D, MI>, 256,
-          G2 ? kLdsMax : kLdsDefault, MB, WM, WN, 1, PX, MI, 0, 2, MB <= 2};
+          G2 ? kLdsMax : kLdsDefault, MB, WM, WN, 1, PX, MI, 0, 2, MB <= 2, false};
 }
 
 // k_conv_ws.  Its waves are laid out differently from k_conv_mfma's: MB row blocks x NB N blocks per wave (the
@@ -104,7 +105,12 @@ static constexpr int ws_depth(int bm, int ks, int cpg) {
 #endif
 static constexpr int ws_nbuf(int bm, int ks, int nb, int cpg) { return DSX_WS_NBUF_EXPR(bm, ks, nb, cpg); }
 
-template <typename DT, int TILE, int MB, int WM, int WN, int NB, int KS, int CPG = conv_cpg(KS)>
+// DIRECT rows (1 x 1 convs with neither GroupNorm nor Swish in front): no raw ring and no conversion -- the LDS-DMAs fill
+// the swizzled MFMA image of the item `depth` items ahead, and the LDS of the ring goes to more images: as many as the old
+// path had items between the DMA request and the MFMAs (ring slots + the fetched item + the converted image).
+static constexpr int ws_direct_images(int bm, int cpg) { return ws_depth(bm, 1, cpg) + 3; }
+
+template <typename DT, int TILE, int MB, int WM, int WN, int NB, int KS, int CPG = conv_cpg(KS), bool DIRECT = false>
 constexpr ConvVariant ws_row() {
   constexpr int BM = 32 * MB * WM;
   // weight ring, in steps: a full group for one N block per wave, half of it (same bytes, same time) for two
@@ -112,14 +118,16 @@ constexpr ConvVariant ws_row() {
   constexpr int D = KS == 1 ? ((NB == 2 || MB == 4) ? DSX_RING_1X1_NB2 : DSX_RING_1X1_NB1) : ((NB == 2 || MB == 4) ? 6 : 18);   // (MB 4: four MFMAs per step, and the registers are needed)
   constexpr int PX = ws_max_px(BM, KS);
   constexpr int NIT = (PX * 4 * CPG + kWsLoaderWaves * 64 - 1) / (kWsLoaderWaves * 64);
-  constexpr int P = ws_depth(BM, KS, CPG);
-  return {FAM_WS, Kind<DT>::value, TILE, KS, 1, CPG, k_conv_ws<DT, MB, WM, WN, NB, KS, CPG, D, NIT, P, kWsLoaderWaves>,
-          256 + 64 * kWsLoaderWaves, kLdsMax, MB, WM, WN, NB, PX, NIT, P, ws_nbuf(BM, KS, NB, CPG), true};
+  static_assert(!DIRECT || (KS == 1 && NB == 1), "direct rows: 1 x 1 convs, one N block per wave");
+  constexpr int NIMG = DIRECT ? ws_direct_images(BM, CPG) : ws_nbuf(BM, KS, NB, CPG);
+  constexpr int P = DIRECT ? NIMG - 1 : ws_depth(BM, KS, CPG);
+  return {FAM_WS, Kind<DT>::value, TILE, KS, 1, CPG, k_conv_ws<DT, MB, WM, WN, NB, KS, CPG, D, NIT, P, kWsLoaderWaves, DIRECT>,
+          256 + 64 * kWsLoaderWaves, kLdsMax, MB, WM, WN, NB, PX, NIT, P, NIMG, true, DIRECT};
 }
 
 // k_conv_img.  NPH 2 / 4: unrolled for exactly that many channel phases; NPH 8: any count up to 8, read at run time
 template <typename DT, int KS, int NPH> constexpr ConvVariant img_row() {
-  return {FAM_IMG, Kind<DT>::value, -1, KS, 1, NPH, k_conv_img<DT, KS, NPH>, 512, kLdsMax, 0, 0, 0, 0, 0, 0, 0, 0, true};
+  return {FAM_IMG, Kind<DT>::value, -1, KS, 1, NPH, k_conv_img<DT, KS, NPH>, 512, kLdsMax, 0, 0, 0, 0, 0, 0, 0, 0, true, false};
 }
 
 template <int N> struct ConvVariants {
@@ -136,7 +144,7 @@ template <int... N> constexpr ConvVariants<(N + ...)> concat(const ConvVariants<
 }
 
 // Which variants are compiled, per operand type.
-template <typename DT> constexpr ConvVariants<34> variants_of() {
+template <typename DT> constexpr ConvVariants<37> variants_of() {
   return {{
       // k_conv_mfma: tile, MB, WM, WN, ks, stride (1), chunks per group (the default of ks)
       mfma_row<DT, TILE_256x128, 8, 1, 4, 1>(), mfma_row<DT, TILE_256x128, 8, 1, 4, 3>(),
@@ -159,6 +167,10 @@ template <typename DT> constexpr ConvVariants<34> variants_of() {
       ws_row<DT, TILE_128x64, 2, 2, 2, 1, 1>(), ws_row<DT, TILE_128x64, 2, 2, 2, 1, 3>(),
       ws_row<DT, TILE_256x64, 4, 2, 2, 1, 3>(),        // 16 x 16 pixels: half the tiles (and epilogues) of 128 x 64
       ws_row<DT, TILE_64x64, 1, 2, 2, 1, 1>(), ws_row<DT, TILE_64x64, 1, 2, 2, 1, 3>(),
+      // k_conv_ws, direct rows: the plain 1 x 1 convs (residual and attention-output convs), per (tile, chunks per item).
+      // (No TILE_64x64 row: no launch of the benchmark takes that tile for a 1 x 1 conv, so it was never measured.)
+      ws_row<DT, TILE_64x128, 2, 1, 4, 1, 1, 2, true>(), ws_row<DT, TILE_64x128, 2, 1, 4, 1, 1, 4, true>(),
+      ws_row<DT, TILE_128x64, 2, 2, 2, 1, 1, 2, true>(),
       // k_conv_img: ks, NPH
       img_row<DT, 1, 2>(), img_row<DT, 1, 4>(), img_row<DT, 1, 8>(),
       img_row<DT, 3, 2>(), img_row<DT, 3, 4>(), img_row<DT, 3, 8>(),
@@ -173,13 +185,13 @@ static constexpr auto kVariants = concat(variants_of<float>(), variants_of<__bf1
                                          ws_nb2_variants<__bf16>(), ws_nb2_variants<_Float16>());
 
 // key -> row without a search (the planner asks a few times per conv and candidate tile)
-static constexpr int kKeySlots = 3 * 3 * (TILE_COUNT + 1) * 2 * 2 * 4;
-static constexpr int key_slot(int family, int dtype, int tile, int ks, int stride, int cpg) {
+static constexpr int kKeySlots = 3 * 3 * (TILE_COUNT + 1) * 2 * 2 * 4 * 2;
+static constexpr int key_slot(int family, int dtype, int tile, int ks, int stride, int cpg, bool direct) {
   const int c = cpg == 1 ? 0 : (cpg == 2 ? 1 : (cpg == 4 ? 2 : (cpg == 8 ? 3 : -1)));
   if (family < 0 || family > FAM_IMG || dtype < 0 || dtype > 2 || tile < -1 || tile >= TILE_COUNT || (ks != 1 && ks != 3) ||
       (stride != 1 && stride != 2) || c < 0)
     return -1;
-  return ((((family * 3 + dtype) * (TILE_COUNT + 1) + tile + 1) * 2 + ks / 2) * 2 + stride - 1) * 4 + c;
+  return (((((family * 3 + dtype) * (TILE_COUNT + 1) + tile + 1) * 2 + ks / 2) * 2 + stride - 1) * 4 + c) * 2 + (direct ? 1 : 0);
 }
 struct VariantIndex { short row[kKeySlots]; bool unique; };
 static constexpr VariantIndex index_variants() {
@@ -188,7 +200,7 @@ static constexpr VariantIndex index_variants() {
   ix.unique = true;
   short n = 0;
   for (const ConvVariant& v : kVariants) {
-    const int s = key_slot(v.family, v.dtype, v.tile, v.ks, v.stride, v.cpg);
+    const int s = key_slot(v.family, v.dtype, v.tile, v.ks, v.stride, v.cpg, v.direct);
     if (s < 0 || ix.row[s] >= 0) ix.unique = false;
     else ix.row[s] = n;
     ++n;
@@ -196,8 +208,8 @@ static constexpr VariantIndex index_variants() {
   return ix;
 }
 static constexpr VariantIndex kIndex = index_variants();
-static const ConvVariant* find_variant(int family, int dtype, int tile, int ks, int stride, int cpg) {
-  const int s = key_slot(family, dtype, tile, ks, stride, cpg);
+static const ConvVariant* find_variant(int family, int dtype, int tile, int ks, int stride, int cpg, bool direct = false) {
+  const int s = key_slot(family, dtype, tile, ks, stride, cpg, direct);
   return s >= 0 && kIndex.row[s] >= 0 ? &kVariants.row[kIndex.row[s]] : nullptr;
 }
 

@@ -69,7 +69,20 @@ static __device__ __forceinline__ void lds_signal(unsigned addr, int wave, int c
 // on across tile boundaries, per-workgroup setup is paid once), and there is one raw s_barrier per
 // group (never __syncthreads: its vmcnt(0) would drain the DMA ring).
 // ===========================================================================================
-template <typename DT, int MB, int WM, int WN, int NB, int KS, int CPG, int D, int NIT, int P, int LW>
+//
+// DIRECT instantiations (ConvArgs::ws_direct: 1 x 1 convs with neither GroupNorm nor Swish in front).  The image the
+// MFMAs read is the activation tile itself, so the loaders only issue LDS-DMAs -- straight into the image of the item P
+// items ahead -- wait with a counted vmcnt for the next item's image and take the per-item barrier: no raw ring, no
+// fetch, no convert.  An LDS-DMA instruction fills 1 KiB contiguously (lane l at +16 l), so the pixel pitch is the
+// unpadded 64 CPG bytes and conflict-free operand reads come from a swizzle on the SOURCE side: LDS slot (pixel m,
+// unit j) holds channel unit j ^ sigma(m), sigma(m) = (m >> 1) & 7 (CPG 2) or m & 15 (CPG 4), and the compute waves
+// read unit u at slot u ^ sigma(m).  A b128 read group holds the 8 even pixels of a 16-pixel block at K slice s and the
+// 8 odd ones at slice s ^ 2 (see mfma16_step).  CPG 2 (128-byte pitch): 16-byte bank slot = 8 (m & 1) + (u ^ sigma):
+// the parities take different halves of the bank row, and inside one (m >> 1) & 7 runs over all 8 values.  CPG 4
+// (256-byte pitch): slot = u ^ (m & 15): the low bit separates the parities (u and u ^ 2 agree in it), the other three
+// run over all values inside a parity.  16 distinct slots either way.  All else (weight stream, MFMA order, epilogue,
+// statistics) is the code of the other instantiations, so a direct launch writes the same bytes.
+template <typename DT, int MB, int WM, int WN, int NB, int KS, int CPG, int D, int NIT, int P, int LW, bool DIRECT>
 __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declaration in dsx_conv_variants.h)
   constexpr int LT = 64 * LW;                   // loader threads
   constexpr int S = 1;
@@ -80,7 +93,7 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
   constexpr int UPG = UPP * CPG;
   constexpr int UPG_LOG2 = UPG == 16 ? 4 : (UPG == 8 ? 3 : 2);
   constexpr int UB = 16;
-  constexpr int PIXB = 64 * CPG + 16;
+  constexpr int PIXB = DIRECT ? 64 * CPG : 64 * CPG + 16;
   constexpr int TAPS = KS * KS;
   constexpr int PAD = KS / 2;
   constexpr int NSTEP = CPG * TAPS * 2;
@@ -107,10 +120,12 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
   const int PPI = PH * PW;
   const int PP = PPI << a.tb_log2;
   const int RB = a.lds_row;
-  const int BUFB = (PH << a.tb_log2) * RB;
+  const int BUFB = DIRECT ? 32 * MB * WM * PIXB : (PH << a.tb_log2) * RB;   // (direct: pixel m of the tile at m PIXB)
   // [image 0 .. NBUF-1][GroupNorm scale/shift of three tiles' images][raw ring][FULL, FREE counters]
   constexpr int NBUF = ws_nbuf(32 * MB * WM, KS, NB, CPG);
   static_assert(NBUF >= 2 && NBUF <= 4, "two images and a barrier, or three / four and counters");
+  constexpr int NIMG = DIRECT ? P + 1 : NBUF;   // images the items rotate through (direct: the barrier hand-off of NBUF == 2)
+  static_assert(!DIRECT || (KS == 1 && NBUF == 2 && NIT * LT == 32 * MB * WM * UPG), "direct: 1 x 1, one barrier per item, whole DMA instructions");
   const int C = a.C0 + a.C1;
   const int AFFB = a.has_gn ? ((2 * C * 4 + 15) & ~15) : 0;     // bytes of one tile's {scale[C], shift[C]}
   float* const aff_base = (float*)(lds + NBUF * BUFB);
@@ -159,6 +174,88 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
     // priority, then age: as the younger wave their GroupNorm/Swish VALU stream only gets the slots the MFMA
     // wave leaves over, and they become the critical path.  Static priority for the whole kernel.
     __builtin_amdgcn_s_setprio(DSX_LOADER_PRIO_EXPR);
+    if constexpr (DIRECT) {
+      // unit it LT + ltid of an item is (pixel it (LT / UPG) + ltid / UPG, slot ltid % UPG): LT / UPG is a multiple of
+      // 16, so sigma -- and with it the channel unit this thread fetches -- is the same for all of its units
+      const int pix0 = ltid >> UPG_LOG2;
+      const int srcu = (ltid & (UPG - 1)) ^ (CPG == 4 ? (pix0 & 15) : ((pix0 >> 1) & 7));
+      int rel[NIT];             // source pixel offset relative to the tile's first pixel
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) {
+        const int m = pix0 + it * (LT >> UPG_LOG2);
+        rel[it] = (m >> a.tw_log2) * a.Ws + (m & (TW - 1));
+      }
+      const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)a.src0, 0, (int)min((long long)a.B * a.Hs * a.Ws * a.C0 * ES, 0x7fffffffLL), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)(a.src1 ? a.src1 : a.src0), 0,
+          a.src1 ? (int)min((long long)a.B * a.Hs * a.Ws * a.C1 * ES, 0x7fffffffLL) : 0, 0x00020000);
+      const int adv_x = a.ws_adv_x, adv_y = a.ws_adv_y, adv_b = a.ws_adv_b;
+      int tx, ty, tb;                                                            // tile being issued
+      {
+        const int q1 = (int)fastdiv((unsigned)p0, a.mg_tiles_x);                  // p0 / tiles_x
+        tb = (int)fastdiv((unsigned)p0, a.mg_per_img);
+        tx = p0 - q1 * a.tiles_x;
+        ty = q1 - tb * a.tiles_y;
+      }
+      auto tile_base = [&]() __attribute__((always_inline)) -> int {
+        return (tb * a.Hs + (ty << a.th_log2)) * a.Ws + (tx << a.tw_log2);
+      };
+      int baseI = tile_base(), gI = 0, issued = 0, bufI = 0;
+      // DMA item (tile, gI) into image bufI; every wave issues exactly NIT instructions.  Channel units past C are out
+      // of the descriptor's range: the bounds check fills them with zeros
+      auto issue_next = [&]() __attribute__((always_inline)) {
+        const int c = gI * (CPG * KC) + srcu * CPU;
+        const bool first = gI * (CPG * KC) < a.C0;            // uniform: a group never straddles the sources
+        const int cs = first ? a.C0 : a.C1;
+        const unsigned coff = c < C ? (unsigned)((first ? c : c - a.C0) * ES) : 0x80000000u;
+        unsigned char* dst = lds + bufI * BUFB + wave * 1024;
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+          const unsigned vo = c < C ? (unsigned)(baseI + rel[it]) * (unsigned)(cs * ES) + coff : 0x80000000u;
+          auto ldst = (__attribute__((address_space(3))) void*)(dst + it * (LT * 16));
+          if (first) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, ldst, 16, vo, 0, 0, 0);
+          else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, ldst, 16, vo, 0, 0, 0);
+        }
+        ++issued;
+        if (++bufI == NIMG) bufI = 0;
+        if (++gI == G) {
+          gI = 0;
+          tx += adv_x;
+          if (tx >= a.tiles_x) { tx -= a.tiles_x; ty += 1; }
+          ty += adv_y;
+          if (ty >= a.tiles_y) { ty -= a.tiles_y; tb += 1; }
+          tb += adv_b;
+          baseI = tile_base();
+        }
+      };
+      // wait until the DMAs of an item have landed; `young` = items requested after it, which may stay in flight
+      auto wait_young = [&](int young) __attribute__((always_inline)) {
+        if (young >= P) wait_vmcnt<P * NIT>();
+        else static_for<P>([&](auto jc) __attribute__((always_inline)) {
+          if (young == decltype(jc)::value) wait_vmcnt<decltype(jc)::value * NIT>();
+        });
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      DSX_STAMP_T(110, tid == 256);       // tables built
+      while (issued < NIMG && issued < total) issue_next();   // every image is free
+      DSX_STAMP_T(111, tid == 256);       // first DMAs issued
+      ws_barrier();                       // (the compute waves' start-up barrier)
+      if (total > 0) wait_young(issued - 1);
+      DSX_STAMP_T(112, tid == 256);       // item 0 has landed
+      ws_barrier();                       // image of item 0 is ready
+      DSX_STAMP_T(64, tid == 256);
+      for (int v = 0; v < total; ++v) {
+        DSX_STAMP_T(65 + 4 * v, tid == 256 && v < 9);
+        DSX_STAMP_T(66 + 4 * v, tid == 256 && v < 9);
+        if (v + 1 < total) wait_young(issued - (v + 2));   // item v + 1 has landed (all of this wave's units of it)
+        DSX_STAMP_T(67 + 4 * v, tid == 256 && v < 9);
+        ws_barrier();                     // the compute waves are done with item v: its image is free, item v + 1 is complete
+        DSX_STAMP_T(68 + 4 * v, tid == 256 && v < 9);
+        if (issued < total) issue_next();   // item v + NIMG into the image of item v
+      }
+      return;
+    }
     // Per-thread, tile-invariant description of its NIT units: LDS image offset, source pixel offset
     // relative to the tile's origin pixel, and which patch borders the unit lies on.  Per tile only the
     // origin offset and four "tile touches the image border" flags change (no divisions, no per-unit
@@ -421,21 +518,29 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
   // A pixel fragment read from LDS feeds 2 NB MFMAs (both 16-channel halves of every N block).
   const int wm = wave / WN, wn = wave % WN;
   const int pq = ws16_pixel(c16);               // this lane's pixel inside a 16-pixel block
-  int abase[MB][KS];                            // ph = 0; the ph = 1 block is `a16` bytes further (uniform)
+  constexpr int AD = DIRECT ? CPG : KS;         // fragment base addresses per row block: one per tap row, or (direct: the
+                                                // swizzle reaches the chunk bits, so no `cg * 64` immediate) one per chunk
+  int abase[MB][AD];                            // ph = 0; the ph = 1 block is `a16` bytes further (uniform)
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
     const int m = (wm * MB + mb) * 32 + pq;
+    if constexpr (DIRECT) {
+      const int sg = CPG == 4 ? (m & 15) : ((m >> 1) & 7);   // sigma(m) == sigma(m + 16)
+#pragma unroll
+      for (int cg = 0; cg < AD; ++cg) abase[mb][cg] = m * PIXB + (((cg * 4 + ws16_slice(kq)) ^ sg) << 4);
+      continue;
+    }
     const int tx = m & (TW - 1);
     const int ty = (m >> a.tw_log2) & (TH - 1);
     const int tb = m >> (a.tw_log2 + a.th_log2);
 #pragma unroll
     for (int dy = 0; dy < KS; ++dy)
-      abase[mb][dy] = (tb * PH + ty * S + dy) * RB + tx * S * PIXB + ws16_slice(kq) * 16;
+      abase[mb][DIRECT ? 0 : dy] = (tb * PH + ty * S + dy) * RB + tx * S * PIXB + ws16_slice(kq) * 16;
   }
   // pixel m + 16 of a row block: 16 pixels to the right (tiles >= 32 wide), else 16 / TW rows down.  (host: TB == 1 and
   // TW a power of two <= 16 -- 2 and 4 included, see tile_geometry -- so TW TH >= 64 and the 32 pixels of a row block
   // are 32 / TW whole rows of one image.)
-  const int a16 = TW >= 32 ? 16 * S * PIXB : (16 >> a.tw_log2) * S * RB;
+  const int a16 = DIRECT ? 16 * PIXB : (TW >= 32 ? 16 * S * PIXB : (16 >> a.tw_log2) * S * RB);
   const int blk0 = (nt * WN + wn) * NB;         // host: Cout % (32 * WN * NB) == 0, so every block exists
   const int wblock = G * (NSTEP * 1024);        // bytes of one N block's fragment stream
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(
@@ -512,7 +617,7 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
 
   // GroupNorm scale/shift of image b -> LDS parity slot, for the loader waves (host: C <= 1024)
   auto load_aff = [&](int b, int slot) __attribute__((always_inline)) {
-    if (a.gn_scale == nullptr || tid * 4 >= C) return;
+    if (DIRECT || a.gn_scale == nullptr || tid * 4 >= C) return;   // (direct: no GroupNorm in front, no slots in LDS)
     float* dst = aff_base + (size_t)slot * (AFFB / 4);
     *(float4*)(dst + tid * 4) = *(const float4*)(a.gn_scale + (size_t)b * C + tid * 4);
     *(float4*)(dst + C + tid * 4) = *(const float4*)(a.gn_shift + (size_t)b * C + tid * 4);
@@ -582,7 +687,7 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
             for (int q = 0; q < NR; ++q) residv[mb][nb][ph][q] = *(const uint4*)(rp + 32 * nb + CPU * q);
         }
     }
-    if (want_aff && a.gn_scale != nullptr && tid * 4 < C) {
+    if (!DIRECT && want_aff && a.gn_scale != nullptr && tid * 4 < C) {
       affv[0] = *(const float4*)(a.gn_scale + (size_t)b_aff * C + tid * 4);
       affv[1] = *(const float4*)(a.gn_shift + (size_t)b_aff * C + tid * 4);
     }
@@ -651,7 +756,7 @@ __global__ void k_conv_ws(const ConvArgs a) {   // (launch bounds: on the declar
 // ---- k_conv_ws.  Chunks per group: the family default, or ConvArgs::ws_cpg where that names a compiled form
 static const ConvVariant* ws_variant(int dtype, int tile, int ks, const ConvArgs& a) {
   const int cpg = (ks == 3 && (a.ws_cpg == 2 || a.ws_cpg == 4)) ? a.ws_cpg : ((ks == 1 && a.ws_cpg == 4) ? 4 : conv_cpg(ks));
-  return find_variant(FAM_WS, dtype, tile, ks, 1, cpg);
+  return find_variant(FAM_WS, dtype, tile, ks, 1, cpg, a.ws_direct != 0);
 }
 size_t conv_ws_lds_bytes(int dtype, int tile, int ks, const ConvArgs& a) {
   const ConvVariant* v = ws_variant(dtype, tile, ks, a);
@@ -670,7 +775,10 @@ size_t conv_ws_lds_bytes(int dtype, int tile, int ks, const ConvArgs& a) {
   const size_t bufb = (size_t)(ph << a.tb_log2) * a.lds_row;
   const size_t rawb = (size_t)v->nit * (kWsLoaderWaves * 64 * 16);
   const size_t affb = a.has_gn ? (((size_t)2 * (a.C0 + a.C1) * 4 + 15) & ~(size_t)15) : 0;  // never keyed on a pointer
-  const size_t total = v->nbuf * bufb + 3 * affb + (size_t)(v->depth + 1) * rawb + (v->nbuf >= 3 ? 32 : 0);
+  // direct rows: a plain 1 x 1 conv (nothing to apply between HBM and the MFMAs); LDS = the images alone
+  if (v->direct && (ks != 1 || a.has_gn || a.swish || a.up)) return 0;
+  const size_t total = v->direct ? (size_t)v->nbuf * (32 * v->MB * v->WM) * (64 * cpg)
+                                 : v->nbuf * bufb + 3 * affb + (size_t)(v->depth + 1) * rawb + (v->nbuf >= 3 ? 32 : 0);
   if (a.tb_log2 != 0 || a.kchunks / cpg < 2) return 0;   // one image per tile, >= 2 channel groups
   // whole 32-channel blocks, float4 epilogue, scale/shift staged by 256 threads x float4
   if ((long long)a.B * a.Ho * a.Wo * std::max(a.out_ld, a.resid_ld) >= (1LL << 31)) return 0;   // 32-bit element offsets

@@ -4,23 +4,24 @@
 // ring slot of the item, constexpr) and DSX_WS_ITEM_NEXT (continue / return) from the including scope.  The plain
 // form must stay a literal loop body: wrapped in a lambda, the two-N-block variants run into hipcc's failing spill
 // path ("Illegal instruction detected: Operand has incorrect register class", ROCm 7.2).
-    unsigned aaddr[MB][KS];                   // LDS byte address of the fragment rows in this item's image
+    unsigned aaddr[MB][AD];                   // LDS byte address of the fragment rows (direct: chunks) in this item's image
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-      for (int dy = 0; dy < KS; ++dy) aaddr[mb][dy] = lds0 + ibuf * BUFB + abase[mb][dy];
+      for (int dy = 0; dy < AD; ++dy) aaddr[mb][dy] = lds0 + ibuf * BUFB + abase[mb][dy];
     if constexpr (NBUF >= 3) lds_wait_all_ge(full_addr, v + 1, a.handoff_timeouts);   // every loader wave has finished this item's image
     f32x4_t fb[PFF + 1];                       // ring of pixel fragments: fragment k of the item lives in fb[k % (PFF + 1)]
     auto read_frag = [&](auto kc_) __attribute__((always_inline)) {
       constexpr int k = decltype(kc_)::value;
       constexpr int t = k / NF, mb = (k % NF) >> 1, ph = k & 1;
       constexpr int cg = t / TAPS, tap = t % TAPS, dy = tap / KS, dx = tap % KS;
-      constexpr int imm = dx * PIXB + cg * 64;
+      constexpr int imm = DIRECT ? 0 : dx * PIXB + cg * 64;   // (direct: the chunk is in the base address, ai = cg)
+      constexpr int ai = DIRECT ? cg : dy;
       static_assert(imm < 65536, "ds offset field");
 #ifndef DSX_ABL_L   // -DDSX_ABL_L: timing experiment, LDS operand reads off (results wrong)
-      lds_read_frag<imm>(fb[k % (PFF + 1)], ph ? aaddr[mb][dy] + (unsigned)a16 : aaddr[mb][dy]);
+      lds_read_frag<imm>(fb[k % (PFF + 1)], ph ? aaddr[mb][ai] + (unsigned)a16 : aaddr[mb][ai]);
 #else
-      touch_frag(fb[k % (PFF + 1)], aaddr[mb][dy]);
+      touch_frag(fb[k % (PFF + 1)], aaddr[mb][ai]);
 #endif
     };
     static_for<PFF>(read_frag);
@@ -54,7 +55,7 @@
     DSX_STAMP_T(1 + 3 * v, tid == 0 && v < 20);
     if constexpr (NBUF == 2) ws_barrier();   // the loaders may now overwrite this image; the next one is complete
     else lds_signal(full_addr + 16, wave, v + 1);   // FREE: this wave is done with items 0 .. v (its operand reads have returned)
-    if (++ibuf == NBUF) ibuf = 0;
+    if (++ibuf == NIMG) ibuf = 0;
     DSX_STAMP_T(2 + 3 * v, tid == 0 && v < 20);
     if (++g < G) DSX_WS_ITEM_NEXT;
     g = 0;
@@ -65,7 +66,7 @@
     // ---- tile finished: epilogue (+ fused statistics).  Accumulator registers 8 ph + r of a lane are channels
     //      8 kq + r of the wave's 32-channel block, for the lane's pixel of the 16-pixel block ph (see mfma16_step).
     // scale/shift of tile ti+3 -> LDS slot (ti+3) % 3 == ti % 3, whose use ended with tile ti
-    if (a.gn_scale != nullptr && ti + 3 < ntile && tid * 4 < C) {
+    if (!DIRECT && a.gn_scale != nullptr && ti + 3 < ntile && tid * 4 < C) {
       float* dst = aff_base + (size_t)aslot * (AFFB / 4);
       *(float4*)(dst + tid * 4) = affv[0];
       *(float4*)(dst + C + tid * 4) = affv[1];

@@ -242,6 +242,8 @@ struct ConvArgs {
   float* stat_part;       // fused GroupNorm partials [B][tiles_x*tiles_y*WM][Cout][2] (fp32) or nullptr
   unsigned* handoff_timeouts;  // k_conv_ws with image counters: incremented when a bounded FULL / FREE spin gives up (never in
                                // a correct run; dsx_exec_handoff_timeouts reads it) -- a lost hand-off must not pass silently
+  int ws_direct;          // k_conv_ws, 1 x 1 conv with neither GroupNorm nor Swish in front: the loader waves DMA the activation
+                          // units straight into swizzled MFMA images (the DIRECT rows of the variant table; lds_row is unused)
   unsigned long long* stamp;  // diagnostic s_memtime stamps of workgroup `stamp_block` (or nullptr)
   int stamp_block;
   int ablate;             // -DDSX_DIAG builds only: DSX_ABLATE timing experiments (results are wrong when non-zero)

@@ -23,7 +23,7 @@ PlanKnobs dsx::read_plan_knobs() {
       {"DSX_WS_1X1", &PlanKnobs::ws_1x1}, {"DSX_WS_MIN_GRID", &PlanKnobs::ws_min_grid}, {"DSX_WS_G2", &PlanKnobs::ws_g2},
       {"DSX_WS_G2_MIN64", &PlanKnobs::ws_g2_min64}, {"DSX_WS_G2_MIN128", &PlanKnobs::ws_g2_min128},
       {"DSX_WS_G4_MIN64", &PlanKnobs::ws_g4_min64}, {"DSX_WS_C4", &PlanKnobs::ws_c4},
-      {"DSX_WS_C4_MIN", &PlanKnobs::ws_c4_min}, {"DSX_WS_MAP3", &PlanKnobs::ws_map3},
+      {"DSX_WS_C4_MIN", &PlanKnobs::ws_c4_min}, {"DSX_WS_DIRECT", &PlanKnobs::ws_direct}, {"DSX_WS_MAP3", &PlanKnobs::ws_map3},
       {"DSX_XCD_BANDS", &PlanKnobs::xcd_bands}, {"DSX_HOST_FIN", &PlanKnobs::host_fin},
       {"DSX_PREFETCH", &PlanKnobs::prefetch}, {"DSX_PREFETCH_WS", &PlanKnobs::prefetch_ws},
       {"DSX_FUSE_STATS", &PlanKnobs::fuse_stats}, {"DSX_NARROW_G2", &PlanKnobs::narrow_g2},
@@ -270,7 +270,8 @@ static int ws_wg_per_n(const ConvArgs& a) {
   return wpn;
 }
 
-// k_conv_ws, chunks per (tile, group) item: several 64-byte chunks where the geometry allows it (PlanKnobs::ws_g2, ws_c4)
+// k_conv_ws, chunks per (tile, group) item: several 64-byte chunks where the geometry allows it (PlanKnobs::ws_g2, ws_c4),
+// and whether a plain 1 x 1 conv takes the direct row of those chunks (PlanKnobs::ws_direct)
 static void decide_ws_chunks(const PlanKnobs& k, int dtype, int ks, int tile, ConvArgs& a) {
   auto take = [&](bool wanted, int cpg) {
     ConvArgs t = a;
@@ -283,6 +284,13 @@ static void decide_ws_chunks(const PlanKnobs& k, int dtype, int ks, int tile, Co
     take(k.ws_g2 && a.kchunks >= k.ws_g4_min64, 4);
   }
   if (ks == 1) take(k.ws_c4 && a.kchunks >= k.ws_c4_min, 4);   // 128 input channels per item
+  // a plain 1 x 1 conv (no GroupNorm, no Swish in front; whole groups from either source: the staging mode 0 that
+  // k_conv_ws requires anyway) takes the direct row of its (type, tile, chunks per item) where one is compiled
+  if (ks == 1 && k.ws_direct && !a.has_gn && !a.swish) {
+    ConvArgs t = a;
+    t.ws_direct = 1;
+    if (conv_ws_lds_bytes(dtype, tile, ks, t) != 0) a.ws_direct = 1;
+  }
 }
 
 // k_conv_ws, blockIdx -> work mapping and its division-free start-up: quotients and fastdiv magics (ConvArgs::ws_map)

@@ -125,6 +125,8 @@ struct PlanKnobs {
   int ws_g4_min64 = 16;      // DSX_WS_G4_MIN64: four chunks per item (64-pixel tile) from this many chunks
   int ws_c4 = 1;             // DSX_WS_C4: 1 x 1 convs, four chunks (128 input channels) per item
   int ws_c4_min = 8;         // DSX_WS_C4_MIN: chunks: at least two groups
+  int ws_direct = 1;         // DSX_WS_DIRECT: plain 1 x 1 convs (no GroupNorm / Swish in front) on the direct rows: LDS-DMA
+                             // straight into the MFMA images (ConvArgs::ws_direct); 0: the raw ring and the copying loaders
   // 1 x 1 convs with several N tiles: an XCD takes every N tile of its M tiles (ws_map 3).  With the N tiles dealt over
   // the XCDs (the 3 x 3 choice: there the weights are the larger operand) every L2 fetched most of the input: 65.7 MB
   // per launch of the 512 -> 1536 qkv conv against 18.4 MB algorithmic (PMC, profiles/r03_pmc_summary.txt).

@@ -24,6 +24,9 @@ for i in range(n):
         k += 1
         if k == want: print("op:", desc.value.decode(), " measured %.1f us" % (ms[i] * 1e3))
 t0 = st[0]
+if st[63] > 0:   # kernel entry -> first MFMA item; the loaders' tables built / first DMAs issued / item 0 landed, from entry
+    print("start-up: entry -> first item %d   (loaders: tables %d | issued %d | item 0 landed %d)"
+          % (st[0] - st[63], st[110] - st[63], st[111] - st[63], st[112] - st[63]))
 print("compute waves (cycles): item: mfma-loop | barrier-wait | epilogue")
 prev = st[0]
 for v in range(20):
