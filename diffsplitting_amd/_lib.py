@@ -154,6 +154,8 @@ SIGNATURES = {
     "dsx_image_metrics_blocks": (_i, [_i, _i]),
     "dsx_image_metrics": (_i, [_Df, _Df, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _Dd, C.POINTER(C.c_double),
                                C.POINTER(C.c_double), _st]),
+    "dsx_msssim_workspace": (_i64, [_i, _i, _i]),
+    "dsx_msssim": (_i, [_Df, _Df, _i, _i, _i, _i, _i, C.c_double, _Dv, C.c_size_t, _H, _st]),
     "dsx_lpips_create": (_i, [C.POINTER(_vp), _pi64, C.POINTER(_vp), _pi64, C.POINTER(_vp)]),
     "dsx_lpips_destroy": (None, [_hn]),
     "dsx_lpips_forward": (_i, [_hn, _Df, _Df, _i, _i, _i, _Df, _Df, _st]),

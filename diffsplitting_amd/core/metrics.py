@@ -1,6 +1,7 @@
 """The reference's image-quality module (core/metrics.py), same names and signatures: tensor2img, save_img,
-calculate_psnr and calculate_ssim, plus ``image_metrics``, the batched device form of PSNR and SSIM, and
-``calculate_lpips``, the evaluation notebooks' ``compute_lpips`` on the device.
+calculate_psnr and calculate_ssim, plus ``image_metrics``, the batched device form of PSNR and SSIM,
+``calculate_lpips``, the evaluation notebooks' ``compute_lpips`` on the device, and ``msssim`` / ``calculate_msssim``,
+a multi-scale SSIM (``dsx_msssim``) with a range-invariant form for stitched frames that have no natural peak.
 
 SSIM runs on the MI355X (``dsx_image_metrics``, include/dsx.h): there is no CPU fallback, so calculate_ssim raises
 DsxError without a device.  The reference writes its grid with torchvision's make_grid and its files with cv2; neither
@@ -173,3 +174,103 @@ def calculate_lpips(target_stitched, pred_stitched, loss_fn, chunk=0):
     if t.shape != p.shape or t.dim() != 4:
         raise ValueError(f"target and pred must be (N, H, W, C) of one shape, got {tuple(t.shape)} and {tuple(p.shape)}")
     return {ch: loss_fn.frames(t, p, ch, chunk).tolist() for ch in range(t.shape[3])}
+
+
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang, Simoncelli, Bovik 2003
+
+
+def msssim_min_side(scales):
+    """The smallest admissible side for ``scales`` scales: the coarsest scale still holds the 11 x 11 window."""
+    return 11 << (scales - 1)
+
+
+def check_msssim_size(H, W, scales):
+    """The size rule of ``dsx_msssim`` on the host: min(H, W) >> (scales - 1) >= 11, else ValueError."""
+    if min(H, W) >> (scales - 1) < 11:
+        raise ValueError(f"MS-SSIM with {scales} scales needs min(H, W) >= {msssim_min_side(scales)} (the coarsest scale "
+                         f"still holds the 11 x 11 window), got {H} x {W}")
+
+
+def _check_msssim_args(pred_shape, target_shape, data_range, range_invariant, weights):
+    """Every refusal of ``msssim`` that needs no device -> the weights as a tuple of floats."""
+    if tuple(pred_shape) != tuple(target_shape) or len(pred_shape) != 4:
+        raise ValueError(f"pred and target must be (B, C, H, W) of one shape, got {tuple(pred_shape)} and "
+                         f"{tuple(target_shape)}")
+    weights = tuple(float(w) for w in weights)
+    if not 1 <= len(weights) <= 5:
+        raise ValueError(f"weights: one per scale, 1 to 5 of them, got {len(weights)}")
+    if not all(math.isfinite(w) and w > 0 for w in weights):
+        raise ValueError(f"weights must be positive, got {weights}")
+    if range_invariant and data_range is not None:
+        raise ValueError("data_range and range_invariant both name the dynamic range: give one (the range-invariant "
+                         "form takes L from the target plane)")
+    if not range_invariant and data_range is None:
+        raise ValueError("give data_range (the dynamic range L) or range_invariant=True")
+    if data_range is not None and not (math.isfinite(data_range) and data_range > 0):
+        raise ValueError(f"data_range must be positive, got {data_range}")
+    check_msssim_size(pred_shape[2], pred_shape[3], len(weights))
+    return weights
+
+
+def _msssim_means(pred, target, scales, range_invariant, data_range, stream=None, workspace=None):
+    """dsx_msssim on (B, C, H, W) fp32 CUDA tensors -> the (B, C, scales, 2) means {cs_s, ssim_s}, float64 numpy.
+    ``workspace``: a CUDA tensor of at least B * C * dsx_msssim_workspace(H, W, scales) bytes (default: a fresh one;
+    its contents on entry do not matter)."""
+    B, Cn, H, W = pred.shape
+    need = check(lib.dsx_msssim_workspace(H, W, scales)) * B * Cn
+    if workspace is None:
+        workspace = torch.empty((need // 8,), dtype=torch.float64, device=pred.device)
+    out = np.empty((B, Cn, scales, 2), np.float64)
+    check(lib.dsx_msssim(pred, target, B * Cn, H, W, scales, int(bool(range_invariant)), float(data_range or 0.0),
+                         workspace, workspace.numel() * workspace.element_size(), out, stream))
+    return out
+
+
+def msssim_from_means(means, weights):
+    """prod_{s < S-1} max(cs_s, 0)^w_s * max(ssim_{S-1}, 0)^w_{S-1} in float64 from (..., S, 2) means {cs_s, ssim_s}."""
+    means = np.asarray(means, np.float64)
+    S = len(weights)
+    terms = np.concatenate([means[..., :S - 1, 0], means[..., S - 1:S, 1]], axis=-1)
+    return np.prod(np.maximum(terms, 0.0) ** np.asarray(weights, np.float64), axis=-1)
+
+
+def msssim(pred, target, data_range=None, range_invariant=False, weights=MSSSIM_WEIGHTS, stream=None,
+           return_scales=False):
+    """Multi-scale SSIM of two (B, C, H, W) CUDA tensors, per plane -> a (B, C) float64 CPU tensor; with
+    ``return_scales`` also the (B, C, S, 2) per-scale means {cs_s, ssim_s} it is formed from.  The definition is
+    ``dsx_msssim``'s (include/dsx.h): 11-tap Gaussian window over the valid region, 2 x 2 mean pooling in double between
+    the scales, S = len(weights) <= 5 scales, weights used as given (a shorter tuple means fewer scales, nothing is
+    renormalised), min(H, W) >> (S - 1) >= 11.
+
+    ``data_range``: the dynamic range L of c1 = (0.01 L)^2, c2 = (0.03 L)^2.  ``range_invariant=True`` (the form for
+    microscopy frames, which have no natural peak) instead applies ``RangeInvariantPsnr``'s transform per plane first:
+    the target standardised, the prediction centred and scaled by the least-squares alpha, L = (max - min) / std of the
+    target; exactly one of the two is given.  A plane whose target is constant (std 0) or whose prediction is constant
+    (sum p~ p~ = 0) gives NaN for that plane, not an error.  No CPU fallback: CPU tensors raise DsxError."""
+    weights = _check_msssim_args(pred.shape, target.shape, data_range, range_invariant, weights)
+    if not (pred.is_cuda and target.is_cuda):
+        raise DsxError(f"msssim runs on the device: pred is on {pred.device}, target on {target.device}")
+    _lib.require_gpu()
+    a = pred.to(torch.float32).contiguous()
+    b = target.to(torch.float32).contiguous()
+    means = _msssim_means(a, b, len(weights), range_invariant, data_range, stream)
+    value = torch.from_numpy(msssim_from_means(means, weights))
+    return (value, torch.from_numpy(means)) if return_scales else value
+
+
+def calculate_msssim(target_stitched, pred_stitched, weights=MSSSIM_WEIGHTS):
+    """Range-invariant MS-SSIM of (N, H, W, C) channel-last frames, numpy or CUDA -> {channel: [N floats]}, mirroring
+    ``calculate_lpips``: every (frame, channel) plane scored on its own by ``msssim(range_invariant=True)``, so raw
+    counts and normalised frames score the same up to input rounding.  numpy input is uploaded once."""
+    if tuple(target_stitched.shape) != tuple(pred_stitched.shape) or len(target_stitched.shape) != 4:
+        raise ValueError(f"target and pred must be (N, H, W, C) of one shape, got {tuple(target_stitched.shape)} and "
+                         f"{tuple(pred_stitched.shape)}")
+    N, H, W, Cn = target_stitched.shape
+    _check_msssim_args((N, Cn, H, W), (N, Cn, H, W), None, True, weights)
+    _lib.require_gpu()
+    dev = next((t.device for t in (target_stitched, pred_stitched) if torch.is_tensor(t) and t.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+    up = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))).to(
+        dev, torch.float32).permute(0, 3, 1, 2).contiguous()
+    value = msssim(up(pred_stitched), up(target_stitched), range_invariant=True, weights=weights)
+    return {ch: value[:, ch].tolist() for ch in range(Cn)}

@@ -1,6 +1,6 @@
-// dsx_eval.cpp — the evaluation entry points that are not tiling: image metrics (SSIM + SSD), the validation report of
-// the training loop, the range table of the mixed inputs and the Welford moments over repeated samples.  Kernels:
-// dsx_eval.hip, dsx_validate.hip.  C ABI in include/dsx.h.
+// dsx_eval.cpp — the evaluation entry points that are not tiling: image metrics (SSIM + SSD), multi-scale SSIM, the
+// validation report of the training loop, the range table of the mixed inputs and the Welford moments over repeated
+// samples.  Kernels: dsx_eval.hip, dsx_msssim.hip, dsx_validate.hip.  C ABI in include/dsx.h.
 #include "dsx_rt.h"
 
 // SSIM + SSD of image pairs (core/metrics.py:62-92), optionally on the tensor2img quantisation (:14-34)
@@ -45,6 +45,47 @@ extern "C" int dsx_image_metrics(const float* a, const float* b, int B, int C, i
     out_ssim[i] = s / valid;
     out_ssd[i] = quantize ? (double)dq : d;
   }
+  return DSX_OK;
+}
+
+// multi-scale SSIM (include/dsx.h): every launch on the caller's stream, one synchronisation to read the means
+static int msssim_check_shape(int H, int W, int scales) {
+  if (scales < 1 || scales > 5) return fail(DSX_ERR_INVALID, "MS-SSIM: %d scales, must be in 1..5", scales);
+  if (H < 1 || W < 1 || ((H < W ? H : W) >> (scales - 1)) < 11)
+    return fail(DSX_ERR_INVALID, "MS-SSIM with %d scales needs min(H, W) >= %d (the coarsest scale still holds the 11 x 11 "
+                "window), got %d x %d", scales, 11 << (scales - 1), H, W);
+  if ((int64_t)H * W > INT32_MAX) return fail(DSX_ERR_INVALID, "MS-SSIM: plane too large");
+  return DSX_OK;
+}
+extern "C" int64_t dsx_msssim_workspace(int H, int W, int scales) {
+  const int rc = msssim_check_shape(H, W, scales);
+  if (rc) return rc;
+  return (int64_t)(msssim_layout(H, W, scales, nullptr) * sizeof(double));
+}
+extern "C" int dsx_msssim(const float* pred, const float* target, int planes, int H, int W, int scales, int range_invariant,
+                          double data_range, void* workspace, size_t workspace_bytes, double* out, void* stream) {
+  const int64_t per_plane = dsx_msssim_workspace(H, W, scales);
+  if (per_plane < 0) return (int)per_plane;
+  if (!pred || !target || !workspace || !out) return fail(DSX_ERR_INVALID, "MS-SSIM: null argument");
+  if (planes < 1 || planes > 65535) return fail(DSX_ERR_INVALID, "MS-SSIM: %d image planes, must be in 1..65535", planes);
+  if (!range_invariant && (!(data_range > 0) || !std::isfinite(data_range)))
+    return fail(DSX_ERR_INVALID, "MS-SSIM: data_range must be positive (or range_invariant set)");
+  if (workspace_bytes < (size_t)per_plane * planes)
+    return fail(DSX_ERR_INVALID, "MS-SSIM: workspace of %zu bytes, %d planes need %zu", workspace_bytes, planes,
+                (size_t)per_plane * planes);
+  if ((uintptr_t)workspace % sizeof(double)) return fail(DSX_ERR_INVALID, "MS-SSIM: the workspace must be 8-byte aligned");
+  SsimWindow win;                              // the window of dsx_image_metrics, computed the same way
+  double sum = 0;
+  for (int i = 0; i < 11; ++i) { const double x = i - 5.0; win.w[i] = std::exp((-0.5 / (1.5 * 1.5)) * x * x); sum += win.w[i]; }
+  sum = 1.0 / sum;
+  for (int i = 0; i < 11; ++i) win.w[i] *= sum;
+  const double L = range_invariant ? 0.0 : data_range;
+  hipStream_t st = (hipStream_t)stream;
+  double* out_dev = nullptr;
+  HIP_TRY(launch_msssim(pred, target, planes, H, W, scales, range_invariant ? 1 : 0, (0.01 * L) * (0.01 * L),
+                        (0.03 * L) * (0.03 * L), win, (double*)workspace, &out_dev, st));
+  HIP_TRY(hipMemcpyAsync(out, out_dev, (size_t)planes * scales * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return DSX_OK;
 }
 

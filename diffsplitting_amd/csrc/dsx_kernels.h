@@ -761,6 +761,13 @@ int image_metrics_tiles(int H, int W);
 hipError_t launch_image_metrics(const float* a, const float* b, int planes, int H, int W, int quantize, float lo,
                                 float hi, float rng, double c1, double c2, const SsimWindow& win, double* part,
                                 hipStream_t st);
+// dsx_msssim.hip.  Multi-scale SSIM of `planes` plane pairs (include/dsx.h, dsx_msssim): every launch of a call on `st`,
+// nothing synchronised.  ws holds planes * msssim_layout(H, W, scales, ..) doubles; *out_dev (inside ws) receives
+// [planes][scales][{mean cs, mean ssim}].  c1, c2 are used when range_invariant == 0, else derived per plane on the device.
+struct MsssimLayout { long long off[5]; int tiles[5]; int H[5]; int W[5]; double count[5]; };
+size_t msssim_layout(int H, int W, int scales, MsssimLayout* lay);
+hipError_t launch_msssim(const float* pred, const float* target, int planes, int H, int W, int scales, int range_invariant,
+                         double c1, double c2, const SsimWindow& win, double* ws, double** out_dev, hipStream_t st);
 
 // dsx_select.hip.  One pass of the radix select behind dsx_order_stats: hist[1 << bits] (64-bit, zeroed by the caller)
 // += the digit (u >> shift) & (2^bits - 1) of every element whose key image u has u >> match_shift == prefix

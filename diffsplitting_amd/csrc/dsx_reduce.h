@@ -9,7 +9,7 @@
 //   butterfly  kDown  offsets 32, 16, .. 1   every kernel but k_lpips_dist
 //              kUp    offsets 1, 2, .. 32    k_lpips_dist (its two fp32 norms and its double accumulator)
 //   combine    Pairwise  (r0 + r1) + (r2 + r3)   k_loss_partial, k_stitch_psnr, k_image_metrics, k_mix_range,
-//                                                k_lpips_minmax
+//                                                k_lpips_minmax, k_msssim_*
 //              Serial    ((r0 + r1) + r2) + r3   k_masked_mean, k_lpips_dist, val_block_reduce
 // (min, max and integer sums do not depend on either; k_mix_range, k_lpips_minmax and val_block_reduce are listed for
 // completeness.)

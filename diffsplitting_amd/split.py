@@ -48,6 +48,10 @@ tiles share the noise of their overlap; posterior sample ``r`` draws from the fi
 pasting every tile's inner region (``--stitch crop``, the default); it works for every sampler.  ``--fuse-steps`` (with
 ``--solver``, ``--sample-seed S`` and ``--noise-field``, one rank) diffuses every frame as one state: after every solver
 row the tiles are blended on a frame canvas and cut out again.
+
+``--ms-ssim`` also scores the stitched prediction with the range-invariant multi-scale SSIM
+(``core.metrics.calculate_msssim``, five scales): rank 0 logs mean +- standard error over the frames per channel.  It
+needs a ground truth (not with ``--input``, ``--validate`` or colour items) and frames of 176 x 176 or more.
 """
 import argparse
 import logging
@@ -227,7 +231,11 @@ def main(argv=None):
     ap.add_argument("--fuse-steps", action="store_true",
                     help="with --solver, --sample-seed and --noise-field: diffuse every frame as one state -- after every "
                          "solver row the tiles are blended on a frame canvas and cut out again (implies --stitch blend)")
+    ap.add_argument("--ms-ssim", action="store_true",
+                    help="also score the stitched prediction with the range-invariant multi-scale SSIM "
+                         "(core.metrics.calculate_msssim: five scales, frames of 176 x 176 or more)")
     args = ap.parse_args(argv)
+    _check_msssim_args(args)
     _check_solver_args(args)
     _check_stitch_args(args, len(str(args.gpu_ids).split(",")) if args.gpus is None else args.gpus)
     if args.sample_seed is not None and args.validate:
@@ -346,6 +354,8 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     from .data.tiled_predict import predict_stack
     samples = args.samples or 1
     solver = _solver_of(args)
+    if args.ms_ssim:
+        _msssim_size_or_exit(*val_set._data_shape[-2:])              # before any tile is predicted
     if hasattr(netG, "solver_sample_loop"):
         # a Gaussian sampler runs its trained schedule: --steps does not shorten it, --solver does
         n_steps = solver["steps"] if solver else netG.num_timesteps
@@ -375,6 +385,7 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
                 log.info("channel %d: RangeInvariantPsnr %.2f +- %.2f dB (random-init weights unless a checkpoint "
                          "was given in path.resume_state)", c, ps[:, c].mean().item(),
                          ps[:, c].std().item() if ps.shape[0] > 1 else 0.0)
+        _log_msssim(args, val_set, pred, ps, log)
         if args.out:
             _write_prediction(args.out, pred, val_set)
             log.info("prediction written to %s", args.out)
@@ -382,6 +393,50 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
             _write_prediction(args.std_out, out["std"], val_set, spread=True)
             log.info("spread over %d samples written to %s", samples, args.std_out)
     return pred
+
+
+def _check_msssim_args(args):
+    """``--ms-ssim``, checked on the command line and the config file alone (nothing touches the GPU, no rank is
+    started): it scores a tiled prediction of two grey channels against their ground truth.  Without it: nothing."""
+    if not args.ms_ssim:
+        return
+    if args.input:
+        raise SystemExit("--ms-ssim with --input: an input-only stack has no ground truth to score against")
+    if args.validate:
+        raise SystemExit("--ms-ssim scores the stitched frames of a tiled prediction: not with --validate")
+    ds = Logger.load_json(args.config).get("datasets") or {}
+    if args.datapath and ((ds.get("train") if args.norm_from == "train" else ds.get("train") or ds.get("val")) or
+                          {}).get("name") == "cifar10":
+        raise SystemExit("--ms-ssim scores the stitched frames of a tiled prediction: the colour items of a cifar10 "
+                         "config are not tiled (and 32 x 32 items cannot hold five scales)")
+    if not (args.datapath or args.frames):
+        try:
+            _, h, w = (int(v) for v in args.synthetic.split(","))
+        except ValueError:
+            raise SystemExit(f"--synthetic {args.synthetic}: N,H,W")
+        _msssim_size_or_exit(h, w)
+
+
+def _msssim_size_or_exit(h, w):
+    from .core.metrics import MSSSIM_WEIGHTS, check_msssim_size
+    try:
+        check_msssim_size(h, w, len(MSSSIM_WEIGHTS))
+    except ValueError as e:
+        raise SystemExit(f"--ms-ssim: {e}")
+
+
+def _log_msssim(args, val_set, pred, ps, log):
+    """``--ms-ssim`` on rank 0, after the stitched prediction has been scored with RangeInvariantPsnr: one line per
+    channel, the mean and the standard error of the mean over the frames."""
+    if not args.ms_ssim:
+        return
+    if ps is None:
+        raise DsxError("--ms-ssim: the dataset holds no target with the prediction's channels to score against")
+    from .core.metrics import calculate_msssim
+    for c, vals in calculate_msssim(val_set.normalized_target_frames(), pred).items():
+        v = np.asarray(vals, np.float64)
+        sem = float(v.std(ddof=1) / np.sqrt(v.size)) if v.size > 1 else 0.0
+        log.info("channel %d: MS-SSIM (range-invariant) %.6f +- %.6f over %d frames", c, float(v.mean()), sem, v.size)
 
 
 def _check_input_args(args):
@@ -536,6 +591,8 @@ def _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log):
     from .data.tiled_predict import gather_pred_t, predict_tiled_mixed
     t_from = args.t_from or "classifier"
     tp = None
+    if args.ms_ssim:
+        _msssim_size_or_exit(*val_set._data_shape[-2:])              # before any tile is predicted
     if t_from == "classifier":
         from . import time_prediction
         tp_opt = Logger.dict_to_nonedict(Logger.load_json(args.time_predictor))
@@ -560,6 +617,7 @@ def _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log):
             log.info("channel %d: RangeInvariantPsnr %.2f +- %.2f dB; predicted start time min %.4f mean %.4f max %.4f",
                      c, ps[:, c].mean().item(), ps[:, c].std().item() if ps.shape[0] > 1 else 0.0,
                      pred_t[:, c].min().item(), pred_t[:, c].mean().item(), pred_t[:, c].max().item())
+        _log_msssim(args, val_set, pred, ps, log)
         if args.out:
             _write_prediction(args.out, pred, val_set)
             log.info("prediction written to %s", args.out)

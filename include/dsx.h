@@ -616,6 +616,35 @@ int dsx_image_metrics(const float* a_dev, const float* b_dev, int B, int C, int 
                       double hi, double data_range, double* partials_dev, double* out_ssim_host, double* out_ssd_host,
                       void* stream);
 
+/* Multi-scale SSIM (Wang, Simoncelli, Bovik 2003) of `planes` plane pairs (pred, target), each H x W fp32 on the
+ * device, over `scales` scales (1..5); optionally range-invariant, for frames that have no natural peak.
+ *   Window     the 11 taps of dsx_image_metrics (Gaussian, sigma 1.5), separable, valid region [5:-5, 5:-5] only;
+ *              c1 = (0.01 L)^2, c2 = (0.03 L)^2, the same at every scale.
+ *   Per scale  over the valid region, in double:  cs = (2 s12 + c2) / (s11 + s22 + c2),
+ *              ssim = (2 mu1 mu2 + c1) / (mu1^2 + mu2^2 + c1) * cs;  the means cs_s and ssim_s of both maps are the
+ *              output, both at every scale: out_host[planes][scales][2] = {cs_s, ssim_s}.
+ *   Between    2 x 2 mean pooling of both planes, an odd last row or column dropped (H -> H / 2):
+ *              ((x00 + x01) + (x10 + x11)) * 0.25 in double; pooled planes stay double, never rounded to fp32.
+ *   Result     prod_{s < S-1} max(cs_s, 0)^w_s * max(ssim_{S-1}, 0)^w_{S-1}, formed by the caller in double from the
+ *              2 S means (core.metrics.msssim; Wang's weights 0.0448, 0.2856, 0.3001, 0.2363, 0.1333, not renormalised
+ *              when fewer are used): the device owns the means only.
+ *   Size rule  the coarsest scale still holds the window: min(H, W) >> (scales - 1) >= 11 (176 for five scales).
+ *   range_invariant != 0 (data_range is then ignored): per plane the transform of RangeInvariantPsnr (core/psnr.py)
+ *              in double, applied on the load of scale 0:  g' = (g - mean g) / std g (unbiased std),
+ *              p' = alpha (p - mean p) with alpha = sum g' p~ / sum p~ p~, p~ = p - mean p, and L = (max g - min g) / std g.
+ *              The plane statistics (sum g, g^2, p, p^2, g p; min and max of g and of p) come from one fixed-order double
+ *              reduction on the device and the coefficients stay there.  std g == 0 or sum p~ p~ == 0 (recognised by
+ *              min == max) gives NaN for that plane, not an error.  The value does not change under a positive affine
+ *              map of the prediction or of the target, up to input rounding.
+ * Everything is enqueued on `stream`, which is synchronised once, to read the planes * scales * 2 means.  The tile
+ * partials are added in an order that depends on the shape alone and nothing uses atomics: equal inputs give
+ * bitwise-equal outputs.  dsx_msssim_workspace(H, W, scales): bytes of workspace PER PLANE PAIR (negative: the shape
+ * is refused); workspace_dev holds planes times that, 8-byte aligned, and every byte of it that the call reads the
+ * call has written.  planes <= 65535. */
+int64_t dsx_msssim_workspace(int H, int W, int scales);
+int dsx_msssim(const float* pred_dev, const float* target_dev, int planes, int H, int W, int scales, int range_invariant,
+               double data_range, void* workspace_dev, size_t workspace_bytes, double* out_host, void* stream);
+
 /* ------------------------------------------------------------------ LPIPS
  * The perceptual metric of the reference's evaluation (notebooks/EvaluateJointIndi.ipynb cell 31 and
  * notebooks/EvaluateJointIndiIterative.ipynb cell 28: lpips.LPIPS(net='alex'), version 0.1, spatial off): scaling
