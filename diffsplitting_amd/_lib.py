@@ -195,6 +195,8 @@ SIGNATURES = {
     "dsx_frames_to_f32": (_i, [_Dv, _i, _i64, C.c_double, _Df, _st]),
     "dsx_order_stats_workspace_bytes": (C.c_size_t, [_i64, _i]),
     "dsx_order_stats": (_i, [_Df, _Df, _i64, C.c_double, C.c_double, _pi64, _i, C.POINTER(C.c_double), _Dv, _st]),
+    "dsx_comoments_blocks": (_i, [_i64]),
+    "dsx_comoments": (_i, [_Df, _Df, _Df, _i64, _i64, _pi64, _Dd, _Dd, _st]),
 }
 
 if not os.path.exists(LIB_PATH):
@@ -216,6 +218,26 @@ def _host_address(a, where):
 def host_pointers(tensors):
     """The addresses of contiguous CPU tensors as a ``void*[]`` (the caller keeps the tensors alive)."""
     return (C.c_void_p * len(tensors))(*[_host_address(t, "a host pointer array") for t in tensors])
+
+
+def plane_view(t, where):
+    """(address, planes, n, plane stride, pixel stride) of a CUDA fp32 tensor (planes, ...) read IN PLACE by a call that
+    takes {plane, pixel} element strides (dsx_comoments): the dimensions behind the first must collapse into one
+    stride, as they do for a contiguous tensor, a channel of a (b, C, p, p) tensor or a channel of a channel-last
+    canvas.  The address goes into a Dev slot as it is; the call's contiguous tensors name its device."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() < 2:
+        got = f"{t.dtype} on {t.device}, {t.dim()} dimensions" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise DsxError(f"{where} must be a CUDA float32 tensor (planes, ...), got {got}")
+    dims = [(n, s) for n, s in zip(t.shape[1:], t.stride()[1:]) if n != 1]
+    n = 1
+    for size, _ in dims:
+        n *= size
+    if n < 1 or any(s < 1 for _, s in dims) or any(dims[k][1] != dims[k + 1][0] * dims[k + 1][1] for k in range(len(dims) - 1)):
+        raise DsxError(f"{where}: shape {tuple(t.shape)} with strides {t.stride()} is no stack of planes with one pixel "
+                       "stride; pass a contiguous copy")
+    pixel = dims[-1][1] if dims else 1
+    plane = t.stride(0) if t.shape[0] > 1 else (n - 1) * pixel + 1
+    return t.data_ptr(), int(t.shape[0]), int(n), int(plane), int(pixel)
 
 
 def common_device(name, devices):

@@ -769,6 +769,22 @@ size_t msssim_layout(int H, int W, int scales, MsssimLayout* lay);
 hipError_t launch_msssim(const float* pred, const float* target, int planes, int H, int W, int scales, int range_invariant,
                          double c1, double c2, const SsimWindow& win, double* ws, double** out_dev, hipStream_t st);
 
+// dsx_refine.hip.  The centred second moments of `planes` plane triples (g, p1, p2) of n pixels each (include/dsx.h,
+// dsx_comoments): one pass on data shifted by each plane's first element, two launches on `st`, nothing synchronised.
+// stride = {plane, pixel} element strides of g, p1, p2; part[planes][comoments_blocks(n)][kComSlots] = the workgroups'
+// {S g', S p1', S p2', S g'g', S p1'p1', S p2'p2', S g'p1', S g'p2', S p1'p2', min g, max g, 0}; out[planes][12].
+// vec: 16-byte loads (pixel strides 1, bases and plane strides multiples of four elements, n % 4 == 0: the caller's check).
+constexpr int kComSlots = 12;
+struct ComArgs {
+  const float* g; const float* p1; const float* p2;
+  long long n, span;       // span = comoments_span(n): pixels per workgroup
+  long long stride[6];
+  double* part; double* out;
+};
+int comoments_blocks(long long n);
+long long comoments_span(long long n);
+hipError_t launch_comoments(const ComArgs& a, int planes, bool vec, hipStream_t st);
+
 // dsx_select.hip.  One pass of the radix select behind dsx_order_stats: hist[1 << bits] (64-bit, zeroed by the caller)
 // += the digit (u >> shift) & (2^bits - 1) of every element whose key image u has u >> match_shift == prefix
 // (match_shift = 64: every element).  b == nullptr: single source.

@@ -9,10 +9,12 @@
 //   butterfly  kDown  offsets 32, 16, .. 1   every kernel but k_lpips_dist
 //              kUp    offsets 1, 2, .. 32    k_lpips_dist (its two fp32 norms and its double accumulator)
 //   combine    Pairwise  (r0 + r1) + (r2 + r3)   k_loss_partial, k_stitch_psnr, k_image_metrics, k_mix_range,
-//                                                k_lpips_minmax, k_msssim_*
+//                                                k_lpips_minmax, k_msssim_*, k_comoments_partial
 //              Serial    ((r0 + r1) + r2) + r3   k_masked_mean, k_lpips_dist, val_block_reduce
 // (min, max and integer sums do not depend on either; k_mix_range, k_lpips_minmax and val_block_reduce are listed for
-// completeness.)
+// completeness.)  k_comoments_partial (dsx_refine.hip): kDown, Pairwise for its nine double sums (and min / max of g);
+// k_comoments_finish then folds a plane's workgroup rows with ONE wave: lane l adds the rows l, l + 64, .. in ascending
+// order, wave_reduce (kDown) folds the lanes.
 //
 // Use.  One value:      r = block_reduce<RedSum, Pairwise>(v, red)          red: 4 elements of LDS, r in every thread
 //       several values: block_park<Op>(v_j, red, n, j) for each slot j < n    red: 4 * n elements, [wave][slot]

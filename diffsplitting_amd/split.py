@@ -24,6 +24,10 @@ A ``joint_indi`` config with ``--mix-t T`` runs the mixed-input prediction inste
 C5): the two channels of every tile mixed at ``T``, ``indi1`` / ``indi2`` started at the time the TimePredictor of
 ``--time-predictor CONFIG [--time-predictor-checkpoint PTH]`` estimates per tile (``--t-from given``: at ``T`` itself,
 no classifier), ``--mmse N`` repeats averaged.  Frames, ranks and ``--out`` as for the plain prediction.
+``--t-from refined [--refine-rounds R] [--refine-scope tile|frame|set] [--refine-step S]`` re-estimates the start times
+from the split's own channel estimates (``predict_tiled_refined``: the scan of core/psnr_based_t_refinement.py, which
+needs no ground truth) and splits again, R times (default 1); round 0 starts at the TimePredictor's estimate when
+``--time-predictor`` is given, else at 0.5.  Rank 0 logs what every round chose.
 
 ``--sample-seed S`` draws every tile's noise from its own stream (seed S, sample id = tile id; MMSE repeat ``r`` of the
 mixed-input prediction: tile id + r * tiles): the noise does not depend on ``--batch-tiles`` or ``--gpus``, and neither
@@ -197,8 +201,16 @@ def main(argv=None):
     ap.add_argument("--time-predictor", type=str, default=None, help="with --mix-t: the TimePredictor's JSON configuration")
     ap.add_argument("--time-predictor-checkpoint", type=str, default=None, help="its state_dict file")
     ap.add_argument("--mmse", type=int, default=None, help="with --mix-t: repeats averaged per tile (default 1)")
-    ap.add_argument("--t-from", type=str, choices=["classifier", "given"], default=None,
-                    help="with --mix-t: start times from the TimePredictor (default) or --mix-t itself")
+    ap.add_argument("--t-from", type=str, choices=["classifier", "given", "refined"], default=None,
+                    help="with --mix-t: start times from the TimePredictor (default), --mix-t itself, or re-estimated "
+                         "from the split's own channel estimates (predict_tiled_refined; --time-predictor optional)")
+    ap.add_argument("--refine-rounds", type=int, default=None,
+                    help="with --t-from refined: how often the start times are re-estimated and the tiles split again "
+                         "(default 1; 0 scores the first split only)")
+    ap.add_argument("--refine-scope", type=str, choices=["tile", "frame", "set"], default=None,
+                    help="with --t-from refined: the tiles whose curves are averaged before the argmax (default frame)")
+    ap.add_argument("--refine-step", type=float, default=None,
+                    help="with --t-from refined: spacing of the scanned mixing times np.arange(0, 1, S) (default 0.05)")
     ap.add_argument("--sample-seed", type=int, default=None,
                     help="per-sample noise streams: every tile draws from the stream (seed, tile id), whatever batch "
                          "or rank predicts it (default: off, one stream per step over the batch)")
@@ -556,7 +568,9 @@ def _solver_of(args):
 
 
 _MIXED_FLAGS = (("--mix-t", "mix_t"), ("--time-predictor", "time_predictor"),
-                ("--time-predictor-checkpoint", "time_predictor_checkpoint"), ("--mmse", "mmse"), ("--t-from", "t_from"))
+                ("--time-predictor-checkpoint", "time_predictor_checkpoint"), ("--mmse", "mmse"), ("--t-from", "t_from"),
+                ("--refine-rounds", "refine_rounds"), ("--refine-scope", "refine_scope"), ("--refine-step", "refine_step"))
+_REFINE_FLAGS = _MIXED_FLAGS[-3:]
 
 
 def _check_mixed_args(args):
@@ -582,18 +596,26 @@ def _check_mixed_args(args):
                          "samplers at --mix-t")
     if args.time_predictor_checkpoint and not args.time_predictor:
         raise SystemExit("--time-predictor-checkpoint: only with --time-predictor CONFIG")
+    refine = [flag for flag, name in _REFINE_FLAGS if getattr(args, name) is not None]
+    if refine and args.t_from != "refined":
+        raise SystemExit(f"{', '.join(refine)}: only with --t-from refined (the start times re-estimated from the split)")
+    if args.refine_rounds is not None and args.refine_rounds < 0:
+        raise SystemExit(f"--refine-rounds {args.refine_rounds}: a count of rounds, 0 or more")
+    if args.refine_step is not None and not (np.isfinite(args.refine_step) and 0.0 < args.refine_step < 1.0):
+        raise SystemExit(f"--refine-step {args.refine_step}: a spacing in (0, 1)")
 
 
 def _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log):
     """``--mix-t``: ``predict_tiled_mixed`` of ``val_set`` over the ranks (the TimePredictor of ``--time-predictor``
     chooses every tile's start time unless ``--t-from given``); ``pred_t`` is gathered so that rank 0 holds every
-    tile's value; rank 0 logs and writes ``--out``.  Returns the stitched canvas."""
-    from .data.tiled_predict import gather_pred_t, predict_tiled_mixed
+    tile's value; rank 0 logs and writes ``--out``.  ``--t-from refined``: ``predict_tiled_refined`` instead (its table
+    is complete on every rank), and a log line per refinement round.  Returns the stitched canvas."""
+    from .data.tiled_predict import gather_pred_t, predict_tiled_mixed, predict_tiled_refined
     t_from = args.t_from or "classifier"
     tp = None
     if args.ms_ssim:
         _msssim_size_or_exit(*val_set._data_shape[-2:])              # before any tile is predicted
-    if t_from == "classifier":
+    if t_from == "classifier" or (t_from == "refined" and args.time_predictor):
         from . import time_prediction
         tp_opt = Logger.dict_to_nonedict(Logger.load_json(args.time_predictor))
         if args.dtype:
@@ -603,14 +625,32 @@ def _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log):
             log.info("no --time-predictor-checkpoint given: the TimePredictor keeps its random initial weights")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    (pred, ps), pred_t = predict_tiled_mixed(netG, tp, val_set, args.mix_t, num_timesteps=n_steps,
-                                             mmse_count=args.mmse or 1, batch_tiles=args.batch_tiles, t_from=t_from,
-                                             seed=args.sample_seed)
-    pred_t = gather_pred_t(pred_t)
+    report = None
+    if t_from == "refined":
+        (pred, ps), pred_t, report = predict_tiled_refined(
+            netG, tp, val_set, args.mix_t, num_timesteps=n_steps, mmse_count=args.mmse or 1,
+            batch_tiles=args.batch_tiles, rounds=1 if args.refine_rounds is None else args.refine_rounds,
+            scope=args.refine_scope or "frame", t_list=np.arange(0, 1.0, args.refine_step or 0.05),
+            seed=args.sample_seed)
+    else:
+        (pred, ps), pred_t = predict_tiled_mixed(netG, tp, val_set, args.mix_t, num_timesteps=n_steps,
+                                                 mmse_count=args.mmse or 1, batch_tiles=args.batch_tiles, t_from=t_from,
+                                                 seed=args.sample_seed)
+        pred_t = gather_pred_t(pred_t)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if rank == 0:
         total = val_set.plan.total
+        for q, rnd in enumerate(report["rounds"] if report else []):
+            chosen = rnd["chosen"][~np.isnan(rnd["chosen"])]
+            if chosen.size == 0:
+                log.info("refinement round %d: every curve is NaN, the start times stay", q)
+                continue
+            log.info("refinement round %d (scope %s, %d of %d units): chosen time min %.4f mean %.4f max %.4f; peak of the "
+                     "mean curve %.2f dB; |chosen - mix_t| mean %.4f max %.4f", q, args.refine_scope or "frame",
+                     chosen.size, rnd["chosen"].size, chosen.min(), chosen.mean(), chosen.max(),
+                     float(np.nanmax(np.nanmean(rnd["mean_curves"][~np.isnan(rnd["chosen"])], axis=0))),
+                     np.abs(chosen - args.mix_t).mean(), np.abs(chosen - args.mix_t).max())
         log.info("mixed-input prediction at t = %g (%s start times): %d tiles of %d^2, %d steps, mmse %d, %d GPU(s): "
                  "%.3f s (%.1f tiles/s)", args.mix_t, t_from, total, patch, n_steps, args.mmse or 1, world, dt, total / dt)
         for c in range(ps.shape[1]):

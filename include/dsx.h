@@ -872,6 +872,36 @@ size_t dsx_order_stats_workspace_bytes(int64_t count, int n_ranks);
 int dsx_order_stats(const float* a_dev, const float* b_dev, int64_t count, double w0, double w1, const int64_t* ranks,
                     int n_ranks, double* out_host, void* workspace_dev, void* stream);
 
+/* ------------------------------------------------- refining the mixing time from the split itself
+ * The centred second moments of `planes` plane triples (g, p1, p2), n fp32 pixels each, in one pass: all that
+ * RangeInvariantPsnr(g, a p1 + b p2) (core/psnr.py:70-82) needs of the three planes, for ANY weights (a, b) -- the scan
+ * of core/psnr_based_t_refinement.py:41-57 without re-reading a plane per grid point.  strides = {plane, pixel} element
+ * strides of g, p1 and p2, so that a (b, 1, p, p) tile tensor, one channel of a (b, 2, p, p) tensor and one channel of a
+ * channel-last (N, H, W, 2) canvas are read in place.  out_dev receives 12 doubles per plane:
+ *   {n, min g, max g, mean g, mean p1, mean p2, Cgg, C11, C22, Cg1, Cg2, C12},   Cxy = sum (x - mean x)(y - mean y)
+ * The curve, for the caller to evaluate in double (core.psnr.range_invariant_psnr_curve does):
+ *   var  = Cgg / (n - 1)                                  (the ddof = 1 standardisation of RangeInvariantPsnr)
+ *   gp   = a Cg1 + b Cg2,    pp = a^2 C11 + 2 a b C12 + b^2 C22
+ *   mse  = ((n - 1) - gp^2 / (var pp)) / n
+ *   PSNR = 10 log10((max g - min g)^2 / var / mse)        NaN where min g == max g or pp <= 0; an mse that rounding
+ *                                                         takes below 0 (an exact fit) counts as 0: +inf
+ * and its continuous maximiser over p = t p1 + (1 - t) p2:  u = S^-1 c,  S = [[C11, C12], [C12, C22]],  c = (Cg1, Cg2),
+ * t* = u0 / (u0 + u1)  (NaN when S is singular or u0 + u1 == 0; not clamped to [0, 1]).
+ * Centring: ONE pass on data shifted by the first element of each plane, x' = (double)x[i] - (double)x[0]; sums of x'
+ * and of the six products accumulate in double (fma allowed), then mean x = x[0] + Sx / n, Cxy = Sxy - Sx Sy / n.  The
+ * contract is an error bound (tests/comoments_ref.py derives it) plus repeatability, not numpy's bits.  A plane is cut
+ * into dsx_comoments_blocks(n) workgroups, a function of n alone, each thread takes fixed pixels in a fixed order and
+ * nothing is an atomic: a plane's 12 numbers have the same bits run to run, at any position in a call, in a call of any
+ * number of planes and on either load path (16-byte loads when every pixel stride is 1, every base is 16-byte aligned,
+ * every plane stride is a multiple of 4 and n % 4 == 0; 4-byte loads otherwise).  Planes are assumed finite.
+ * partial_dev holds planes * dsx_comoments_blocks(n) * 12 doubles.  Two launches on `stream`, no synchronisation.
+ * DSX_ERR_INVALID with a message, before any device work: a NULL pointer, n < 1, planes outside 0..65535 (0: DSX_OK,
+ * nothing is done and no device is needed), a stride < 1, planes > 1 with a plane stride < (n - 1) * pixel stride + 1
+ * (the planes of that operand would overlap). */
+int dsx_comoments_blocks(int64_t n);
+int dsx_comoments(const float* g_dev, const float* p1_dev, const float* p2_dev, int64_t planes, int64_t n,
+                  const int64_t strides[6], double* partial_dev, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
