@@ -2,7 +2,8 @@
 the tensors live on: PSNR and the range-invariant PSNR of grayscale image batches (B,H,W).
 
 ``comoments`` / ``range_invariant_psnr_curve``: RangeInvariantPsnr(g, a p1 + b p2) for ANY weights from one pass over
-the three planes (``dsx_comoments``, include/dsx.h) -- the scan of core/psnr_based_t_refinement.py:41-57 in closed form."""
+the three planes (``dsx_comoments``, include/dsx.h) -- the scan of core/psnr_based_t_refinement.py:41-57 in closed form.
+``range_invariant_psnr_from_sums``: the same metric from the raw sums taken while tiles are pasted or blended."""
 import ctypes as C
 
 import torch
@@ -39,6 +40,24 @@ def RangeInvariantPsnr(gt, pred):
     return _psnr(g, alpha * p, ra)
 
 
+def range_invariant_psnr_from_sums(sp, spp, sg, sgg, sgp, gmin, gmax, n):
+    """``RangeInvariantPsnr`` above in closed form from the raw plane sums the paste and blend kernels take (PsnrSums,
+    csrc/dsx_reduce.h).  With g_ = (g - mean g) / std g (unbiased std, as torch.std) and
+    p0 = p - mean p:  alpha = <g_, p0> / <p0, p0>,  mse = (<g_, g_> - <g_, p0>^2 / <p0, p0>) / n,
+    PSNR = 20 log10( ((max g - min g) / std g) / sqrt(mse) ).
+    ``range_invariant_psnr_curve`` below is the same form on centred moments: Cgg = sgg - n mean_g^2,
+    Cgp = sgp - n mean_g mean_p, Cpp = spp - n mean_p^2; k_msssim_coef (csrc/dsx_msssim.hip) states it on the device."""
+    mean_g, mean_p = sg / n, sp / n
+    var_g = (sgg - n * mean_g * mean_g) / (n - 1.0)
+    std_g = torch.sqrt(var_g)
+    gg = (sgg - n * mean_g * mean_g) / var_g                        # = n - 1
+    gp = (sgp - n * mean_g * mean_p) / std_g
+    pp = spp - n * mean_p * mean_p
+    mse = (gg - gp * gp / pp) / n
+    ra = (gmax - gmin) / std_g
+    return 20.0 * torch.log10(ra / torch.sqrt(mse))
+
+
 MOMENT_NAMES = ("n", "min_g", "max_g", "mean_g", "mean_p1", "mean_p2", "Cgg", "C11", "C22", "Cg1", "Cg2", "C12")
 
 
@@ -71,6 +90,7 @@ def range_invariant_psnr_curve(moments, a, b):
         var = Cgg / (n - 1);  gp = a Cg1 + b Cg2;  pp = a^2 C11 + 2 a b C12 + b^2 C22
         mse = ((n - 1) - gp^2 / (var pp)) / n;  PSNR = 10 log10((max g - min g)^2 / var / mse)
 
+    (``range_invariant_psnr_from_sums`` is this form for one prediction on raw sums: Cgg = sum g^2 - n mean_g^2, ...)
     NaN where min g == max g or pp <= 0; an mse below 0 (rounding, at a fit that is exact) counts as 0: +inf dB.
     ``t_star``: the continuous maximiser over p = t p1 + (1 - t) p2, u = S^-1 c
     with S = [[C11, C12], [C12, C22]], c = (Cg1, Cg2), t* = u0 / (u0 + u1); NaN when S is singular or u0 + u1 == 0, not

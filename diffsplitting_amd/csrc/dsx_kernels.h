@@ -714,7 +714,8 @@ struct StitchSrc {
   const long long* off; long long rank_stride; int world;
 };
 // paste (gt == nullptr) or paste + per-(tile, workgroup, channel) partial sums for RangeInvariantPsnr:
-// part[count][gx][C][8] doubles {sum p, sum p^2, sum g, sum g^2, sum g p, min g, max g, 0}
+// part[count][gx][C][8] doubles {sum p, sum p^2, sum g, sum g^2, sum g p, min g, max g, 0}, C <= kPsnrMaxC
+constexpr int kPsnrMaxC = 4;         // channels of a paste or blend that takes the sums
 hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions /*dev*/, TileSeq seq, float* canvas, int H, int W,
                          const float* gt, double* part, int gx, hipStream_t st);
 // valid regions of the sequence's tiles -> this rank's flat run (the crop of tile_stitcher.py:38-56 before the collective)
@@ -724,7 +725,7 @@ hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const in
 // dsx_tileplan_blend).  tiles: whole (C, ph, pw) tiles, tile t at  (t % world) * rank_stride + (t / world) * C*ph*pw
 // (world == 1: (total, C, ph, pw)).  The plan's tiles are frame-major, ny x nx per frame, tile (iy, ix) of frame n is
 // id (n*ny + iy)*nx + ix; rows[y] = (first tile row, count) and cols[x] = (first tile column, count) name the
-// contributors of a canvas pixel, wy / wx the separable window.  gt != nullptr: also part[N][blocks][C][8] (C <= 4).
+// contributors of a canvas pixel, wy / wx the separable window.  gt != nullptr: also part[N][blocks][C][8] (C <= kPsnrMaxC).
 struct BlendArgs {
   const float* tiles; int C, world; long long rank_stride;
   int N, H, W, ph, pw, ny, nx;

@@ -13,7 +13,8 @@ namespace dsx {
 // per plane: coef[plane * kMsCoef + ..] = {mean g, 1 / std g, mean p, alpha, c1, c2, 0, 0};  the loads of scale 0 are
 // g' = (g - coef[0]) * coef[1] and p' = (p - coef[2]) * coef[3] in double ({0, 1, 0, 1} when not range-invariant: exact)
 constexpr int kMsCoef = 8;
-constexpr int kMsStats = 9;            // sum g, sum g^2, sum p, sum p^2, sum g p, min g, max g, min p, max p
+using MsRow = RedRow<5, 2>;            // PsnrSums' row (sum p, sum p^2, sum g, sum g^2, sum g p, min g, max g), min p, max p
+constexpr int kMsStats = MsRow::kSlots;
 constexpr int kMsStatChunk = 16384;    // elements of a plane per workgroup: 64 per thread
 
 __global__ __launch_bounds__(256) void k_msssim_stats(const float* __restrict__ p, const float* __restrict__ g,
@@ -21,30 +22,26 @@ __global__ __launch_bounds__(256) void k_msssim_stats(const float* __restrict__ 
   __shared__ double red[4 * kMsStats];
   const long long base = (long long)blockIdx.y * n;
   const long long i0 = (long long)blockIdx.x * kMsStatChunk, i1 = min(n, i0 + kMsStatChunk);
-  double sg = 0, sgg = 0, sp = 0, spp = 0, sgp = 0, gmin = INFINITY, gmax = -INFINITY, pmin = INFINITY, pmax = -INFINITY;
+  PsnrSums acc;
+  double pmin = INFINITY, pmax = -INFINITY;
   for (long long i = i0 + threadIdx.x; i < i1; i += 256) {
-    const double gv = (double)g[base + i], pv = (double)p[base + i];
-    sg += gv; sgg += gv * gv; sp += pv; spp += pv * pv; sgp += gv * pv;
-    gmin = fmin(gmin, gv); gmax = fmax(gmax, gv); pmin = fmin(pmin, pv); pmax = fmax(pmax, pv);
+    const float pv = p[base + i];
+    acc.add(pv, g[base + i]);
+    pmin = fmin(pmin, (double)pv); pmax = fmax(pmax, (double)pv);
   }
-  block_park<RedSum>(sg, red, kMsStats, 0); block_park<RedSum>(sgg, red, kMsStats, 1);
-  block_park<RedSum>(sp, red, kMsStats, 2); block_park<RedSum>(spp, red, kMsStats, 3);
-  block_park<RedSum>(sgp, red, kMsStats, 4);
-  block_park<RedMin>(gmin, red, kMsStats, 5); block_park<RedMax>(gmax, red, kMsStats, 6);
-  block_park<RedMin>(pmin, red, kMsStats, 7); block_park<RedMax>(pmax, red, kMsStats, 8);
+  const double v[kMsStats] = {acc.sp, acc.spp, acc.sg, acc.sgg, acc.sgp, acc.mn, acc.mx, pmin, pmax};
+  MsRow::park(v, red);
   __syncthreads();
-  if (threadIdx.x < kMsStats) {
-    const int j = threadIdx.x;
-    part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kMsStats + j] =
-        j < 5 ? block_combine<RedSum, Pairwise>(red, kMsStats, j)
-              : ((j & 1) ? block_combine<RedMin, Pairwise>(red, kMsStats, j) : block_combine<RedMax, Pairwise>(red, kMsStats, j));
-  }
+  if (threadIdx.x < kMsStats)
+    part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kMsStats + threadIdx.x] = MsRow::combine(red, threadIdx.x);
 }
 
 // one workgroup per plane.  Thread t adds the chunk rows t, t + 256, .. front to back, then the block reduction: the
 // order is a function of nblk alone.  The transform of core/psnr.py's RangeInvariantPsnr from the sums:
 //   std g = sqrt((sum g^2 - n mean_g^2) / (n - 1));  alpha = (sum g p - n mean_g mean_p) / std g / (sum p^2 - n mean_p^2)
 //   L = (max g - min g) / std g.  A constant plane is recognised by min == max (exact), not by a rounded variance.
+// The raw sums against the centred moments of range_invariant_psnr_curve (core/psnr.py): Cgg = sum g^2 - n mean_g^2,
+// Cgp = sum g p - n mean_g mean_p, Cpp = sum p^2 - n mean_p^2; range_invariant_psnr_from_sums is the same closed form.
 __global__ __launch_bounds__(256) void k_msssim_coef(const double* __restrict__ part, int nblk, double n,
                                                      int range_invariant, double c1, double c2,
                                                      double* __restrict__ coef) {
@@ -54,27 +51,20 @@ __global__ __launch_bounds__(256) void k_msssim_coef(const double* __restrict__ 
     if (threadIdx.x == 0) { o[0] = 0; o[1] = 1; o[2] = 0; o[3] = 1; o[4] = c1; o[5] = c2; o[6] = 0; o[7] = 0; }
     return;
   }
-  double v[kMsStats] = {0, 0, 0, 0, 0, INFINITY, -INFINITY, INFINITY, -INFINITY};
-  for (int k = threadIdx.x; k < nblk; k += 256) {
-    const double* r = part + ((size_t)blockIdx.x * nblk + k) * kMsStats;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) v[j] += r[j];
-    v[5] = fmin(v[5], r[5]); v[6] = fmax(v[6], r[6]); v[7] = fmin(v[7], r[7]); v[8] = fmax(v[8], r[8]);
-  }
-#pragma unroll
-  for (int j = 0; j < 5; ++j) block_park<RedSum>(v[j], red, kMsStats, j);
-  block_park<RedMin>(v[5], red, kMsStats, 5); block_park<RedMax>(v[6], red, kMsStats, 6);
-  block_park<RedMin>(v[7], red, kMsStats, 7); block_park<RedMax>(v[8], red, kMsStats, 8);
+  double v[kMsStats];
+  MsRow::init(v);
+  for (int k = threadIdx.x; k < nblk; k += 256) MsRow::fold(v, part + ((size_t)blockIdx.x * nblk + k) * kMsStats);
+  MsRow::park(v, red);
   __syncthreads();
   if (threadIdx.x == 0) {
-    double s[5];
+    double s[kMsStats];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) s[j] = block_combine<RedSum, Pairwise>(red, kMsStats, j);
-    const double gmin = block_combine<RedMin, Pairwise>(red, kMsStats, 5), gmax = block_combine<RedMax, Pairwise>(red, kMsStats, 6);
-    const double pmin = block_combine<RedMin, Pairwise>(red, kMsStats, 7), pmax = block_combine<RedMax, Pairwise>(red, kMsStats, 8);
-    const double mg = s[0] / n, mp = s[2] / n;
-    double sd = sqrt(fmax(s[1] - s[0] * mg, 0.0) / (n - 1.0));
-    double alpha = ((s[4] - s[0] * mp) / sd) / (s[3] - s[2] * mp);
+    for (int j = 0; j < kMsStats; ++j) s[j] = MsRow::combine(red, j);
+    const double sp = s[0], spp = s[1], sg = s[2], sgg = s[3], sgp = s[4];
+    const double gmin = s[5], gmax = s[6], pmin = s[7], pmax = s[8];
+    const double mg = sg / n, mp = sp / n;
+    double sd = sqrt(fmax(sgg - sg * mg, 0.0) / (n - 1.0));
+    double alpha = ((sgp - sg * mp) / sd) / (spp - sp * mp);
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     if (!(gmax > gmin)) { sd = nan; alpha = nan; }        // std g == 0 (or a NaN input): NaN for this plane
     if (!(pmax > pmin)) alpha = nan;                      // sum p~ p~ == 0

@@ -75,25 +75,14 @@ __global__ __launch_bounds__(256) void k_comoments_partial(ComArgs a) {
         if (j < m) acc.add(vg[j], v1[j], v2[j], g0, a0, b0);
     }
   }
-  block_park<RedSum>(acc.sg, red, kComSlots, 0);
-  block_park<RedSum>(acc.s1, red, kComSlots, 1);
-  block_park<RedSum>(acc.s2, red, kComSlots, 2);
-  block_park<RedSum>(acc.gg, red, kComSlots, 3);
-  block_park<RedSum>(acc.c11, red, kComSlots, 4);
-  block_park<RedSum>(acc.c22, red, kComSlots, 5);
-  block_park<RedSum>(acc.g1, red, kComSlots, 6);
-  block_park<RedSum>(acc.g2, red, kComSlots, 7);
-  block_park<RedSum>(acc.c12, red, kComSlots, 8);
-  block_park<RedMin>((double)acc.mn, red, kComSlots, 9);
-  block_park<RedMax>((double)acc.mx, red, kComSlots, 10);
+  using Row = RedRow<9, 1>;                      // slot 11 of a part row: unused, 0
+  const double v[Row::kSlots] = {acc.sg, acc.s1, acc.s2, acc.gg, acc.c11, acc.c22, acc.g1, acc.g2, acc.c12,
+                                 (double)acc.mn, (double)acc.mx};
+  Row::park(v, red, kComSlots);
   __syncthreads();
   if (threadIdx.x < kComSlots) {
     const int j = threadIdx.x;
-    double v = 0.0;                              // slot 11: unused
-    if (j < 9) v = block_combine<RedSum, Pairwise>(red, kComSlots, j);
-    else if (j == 9) v = block_combine<RedMin, Pairwise>(red, kComSlots, j);
-    else if (j == 10) v = block_combine<RedMax, Pairwise>(red, kComSlots, j);
-    a.part[((size_t)plane * gridDim.x + blockIdx.x) * kComSlots + j] = v;
+    a.part[((size_t)plane * gridDim.x + blockIdx.x) * kComSlots + j] = j < Row::kSlots ? Row::combine(red, j, kComSlots) : 0.0;
   }
 }
 

@@ -216,7 +216,7 @@ extern "C" int dsx_stitch_psnr_blocks(int ph, int pw) {
 extern "C" int dsx_stitch_psnr(const float* tiles, int64_t count, int C, int ph, int pw, const int32_t* regions,
                                float* canvas, const int64_t data_shape[3], const float* gt_canvas, double* partials_dev,
                                void* stream) {
-  if (!gt_canvas || !partials_dev || C > 4) return fail(DSX_ERR_INVALID, "bad argument (1 <= C <= 4)");
+  if (!gt_canvas || !partials_dev || C > kPsnrMaxC) return fail(DSX_ERR_INVALID, "bad argument (1 <= C <= %d)", kPsnrMaxC);
   return stitch_host("stitch_psnr", tiles, count, C, ph, pw, regions, canvas, data_shape, gt_canvas, partials_dev, stream);
 }
 
@@ -577,7 +577,8 @@ extern "C" int dsx_tileplan_randn(dsx_tileplan* p, int C, int64_t first, int64_t
 extern "C" int dsx_tileplan_stitch(dsx_tileplan* p, const float* tiles, int C, int64_t first, int64_t stride, int64_t count,
                                    float* canvas, const float* gt_canvas, double* partials_dev, void* stream) {
   if (!tiles || !canvas || C < 1) return fail(DSX_ERR_INVALID, "bad argument");
-  if (gt_canvas && (!partials_dev || C > 4)) return fail(DSX_ERR_INVALID, "PSNR sums need a partials buffer and C <= 4");
+  if (gt_canvas && (!partials_dev || C > kPsnrMaxC))
+    return fail(DSX_ERR_INVALID, "PSNR sums need a partials buffer and C <= %d", kPsnrMaxC);
   TileGeom g;
   const int rc = geom_of_plan("tileplan_stitch", p, first, stride, count, g);
   if (rc || count == 0) return rc;
@@ -604,7 +605,8 @@ extern "C" int dsx_tileplan_pack(dsx_tileplan* p, const float* tiles, int C, int
 extern "C" int dsx_tileplan_paste_packed(dsx_tileplan* p, const float* flat_all, int C, int world, int64_t rank_stride_elems,
                                          float* canvas, const float* gt_canvas, double* partials_dev, void* stream) {
   if (!p || !flat_all || !canvas || C < 1 || world < 1) return fail(DSX_ERR_INVALID, "bad argument");
-  if (gt_canvas && (!partials_dev || C > 4)) return fail(DSX_ERR_INVALID, "PSNR sums need a partials buffer and C <= 4");
+  if (gt_canvas && (!partials_dev || C > kPsnrMaxC))
+    return fail(DSX_ERR_INVALID, "PSNR sums need a partials buffer and C <= %d", kPsnrMaxC);
   if (p->total == 0) return DSX_OK;
   TileGeom g;
   int rc = geom_of_plan("tileplan_paste_packed", p, 0, 1, p->total, g);
@@ -655,8 +657,8 @@ extern "C" int dsx_tileplan_blend(dsx_tileplan* p, const float* tiles_dev, int C
   if (!p || !tiles_dev || !canvas_dev) return fail(DSX_ERR_INVALID, "%s: null argument", what);
   if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
   if (world < 1) return fail(DSX_ERR_INVALID, "%s: world = %d, must be at least 1", what, world);
-  if (gt_canvas_dev && (!partials_dev || C > 4))
-    return fail(DSX_ERR_INVALID, "%s: PSNR sums need a partials buffer and C <= 4", what);
+  if (gt_canvas_dev && (!partials_dev || C > kPsnrMaxC))
+    return fail(DSX_ERR_INVALID, "%s: PSNR sums need a partials buffer and C <= %d", what, kPsnrMaxC);
   if (!p->covers)
     return fail(DSX_ERR_INVALID, "%s: the plan's tiles do not cover the frames (SHIFT tiling of (1, g, g) grids does)", what);
   if (p->window.empty()) return fail(DSX_ERR_INVALID, "%s: the plan has no window: call dsx_tileplan_set_window first", what);

@@ -386,19 +386,17 @@ hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const in
 // is pasted, every (tile, workgroup) also reduces, per channel, sum(p), sum(p^2), sum(g), sum(g^2), sum(g p),
 // min(g), max(g) of prediction p against the ground truth g at the same canvas pixels (every canvas pixel is pasted
 // exactly once).  Fixed reduction order (thread -> wave shuffles -> 4 waves): bitwise reproducible.
-// part[k][blockIdx.x][c][8] doubles; the per-frame combination (a few hundred values) is the caller's.
-constexpr int kPsnrMaxC = 4;
+// part[k][blockIdx.x][c][8] doubles (PsnrSums, dsx_reduce.h); the per-frame combination (a few hundred values) is the
+// caller's.
 __global__ __launch_bounds__(256) void k_stitch_psnr(const TileSrc src, int C, const int* __restrict__ regions, TileSeq seq,
                                                       float* __restrict__ canvas, const float* __restrict__ gt, int H, int W,
                                                       double* __restrict__ part) {
-  __shared__ double red[4 * kPsnrMaxC * 7];    // [wave][channel][7 values]
+  __shared__ double red[kPsnrRed];
   const long long k = blockIdx.y, t = seq.first + k * seq.stride;
   const int* r = regions + t * 8;
   const int n = r[0], y0 = r[1], x0 = r[2], h = r[3], w = r[4];
   const TileView v = tile_view(src, k, t, C, r);
-  double sp[kPsnrMaxC], spp[kPsnrMaxC], sg[kPsnrMaxC], sgg[kPsnrMaxC], sgp[kPsnrMaxC], mn[kPsnrMaxC], mx[kPsnrMaxC];
-#pragma unroll
-  for (int c = 0; c < kPsnrMaxC; ++c) { sp[c] = spp[c] = sg[c] = sgg[c] = sgp[c] = 0; mn[c] = INFINITY; mx[c] = -INFINITY; }
+  PsnrSums acc[kPsnrMaxC];
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h * w; i += gridDim.x * blockDim.x) {
     const int x = i % w, y = i / w;
     const size_t cpix = (((size_t)n * H + (y0 + y)) * W + (x0 + x)) * C;
@@ -408,33 +406,13 @@ __global__ __launch_bounds__(256) void k_stitch_psnr(const TileSrc src, int C, c
         const float p = v.p[c * v.plane + (size_t)y * v.pitch + x];
         const float g = gt[cpix + c];
         canvas[cpix + c] = p;
-        sp[c] += p; spp[c] += (double)p * p; sg[c] += g; sgg[c] += (double)g * g; sgp[c] += (double)g * p;
-        mn[c] = fmin(mn[c], (double)g); mx[c] = fmax(mx[c], (double)g);
+        acc[c].add(p, g);
       }
     }
   }
-  constexpr int kSlots = kPsnrMaxC * 7;
-#pragma unroll
-  for (int c = 0; c < kPsnrMaxC; ++c) {
-    block_park<RedSum>(sp[c], red, kSlots, c * 7);
-    block_park<RedSum>(spp[c], red, kSlots, c * 7 + 1);
-    block_park<RedSum>(sg[c], red, kSlots, c * 7 + 2);
-    block_park<RedSum>(sgg[c], red, kSlots, c * 7 + 3);
-    block_park<RedSum>(sgp[c], red, kSlots, c * 7 + 4);
-    block_park<RedMin>(mn[c], red, kSlots, c * 7 + 5);
-    block_park<RedMax>(mx[c], red, kSlots, c * 7 + 6);
-  }
-  __syncthreads();
-  if (threadIdx.x < C * 8) {
-    const int c = threadIdx.x >> 3, kk = threadIdx.x & 7;
-    double o = 0;
-    if (kk < 5) o = block_combine<RedSum, Pairwise>(red, kSlots, c * 7 + kk);
-    else if (kk == 5) o = block_combine<RedMin, Pairwise>(red, kSlots, c * 7 + 5);
-    else if (kk == 6) o = block_combine<RedMax, Pairwise>(red, kSlots, c * 7 + 6);
-    part[(((size_t)k * gridDim.x + blockIdx.x) * C + c) * 8 + kk] = o;
-  }
+  psnr_sums_write(acc, C, red, part + ((size_t)k * gridDim.x + blockIdx.x) * C * 8);
 }
-// gt == nullptr: plain paste; else also the RangeInvariantPsnr partial sums (C <= 4, gx workgroups per tile)
+// gt == nullptr: plain paste; else also the RangeInvariantPsnr partial sums (C <= kPsnrMaxC, gx workgroups per tile)
 hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions, TileSeq seq, float* canvas, int H, int W,
                          const float* gt, double* part, int gx, hipStream_t st) {
   const TileSrc src{s.base, s.packed, s.ph, s.pw, s.off, s.rank_stride, s.world < 1 ? 1 : s.world};
@@ -464,7 +442,7 @@ hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions, TileSeq 
 // 16-byte aligned).  The C values of a pixel are contiguous in the canvas: WIDE writes them as one 8- / 16-byte store
 // (C = 2 / 4 and the canvas aligned to it), otherwise one dword per channel.  CT = C for C <= 4; CT = 0 is any C, one
 // channel after the other.  PSNR: the seven RangeInvariantPsnr sums of k_stitch_psnr per (frame, workgroup, channel),
-// through the same fixed-order block reduction (C <= 4).  No LDS beyond those slots, no atomics.
+// through the same fixed-order block reduction (C <= kPsnrMaxC).  No LDS beyond those slots, no atomics.
 // ---------------------------------------------------------------------------
 constexpr int kBlendCols = 4;                  // tile columns of a pixel kept in registers
 __device__ __forceinline__ const float* blend_tile(const BlendArgs& a, unsigned t, unsigned tile_elems) {
@@ -501,7 +479,7 @@ __device__ __forceinline__ void blend_add(const BlendArgs& a, unsigned t, int pl
 template <int CT, bool WIDE, bool PSNR>
 __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
   constexpr int NC = CT > 0 ? CT : 1;
-  __shared__ double red[PSNR ? 4 * kPsnrMaxC * 7 : 1];
+  __shared__ double red[PSNR ? kPsnrRed : 1];
   const int n = blockIdx.z, x = blockIdx.x * 256 + threadIdx.x;
   const bool live = x < a.W;
   const unsigned tile0 = (unsigned)n * a.ny * a.nx;
@@ -514,9 +492,7 @@ __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
     xo[j] = 0; wxc[j] = 0.f;
     if (CT > 0 && j < txn) { xo[j] = x - a.starts[(size_t)(tx0 + j) * 3 + 2]; wxc[j] = a.wx[xo[j]]; }
   }
-  double sp[kPsnrMaxC], spp[kPsnrMaxC], sg[kPsnrMaxC], sgg[kPsnrMaxC], sgp[kPsnrMaxC], mn[kPsnrMaxC], mx[kPsnrMaxC];
-#pragma unroll
-  for (int c = 0; c < kPsnrMaxC; ++c) { sp[c] = spp[c] = sg[c] = sgg[c] = sgp[c] = 0; mn[c] = INFINITY; mx[c] = -INFINITY; }
+  PsnrSums acc[kPsnrMaxC];
   for (int y = blockIdx.y; y < a.H; y += gridDim.y) {
     if (!live) continue;
     const int ty0 = a.rows[2 * y], tyn = a.rows[2 * y + 1];
@@ -552,35 +528,12 @@ __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
     }
     if (PSNR) {
 #pragma unroll
-      for (int c = 0; c < NC && c < kPsnrMaxC; ++c) {
-        const float p = o[c], g = a.gt[cpix + c];
-        sp[c] += p; spp[c] += (double)p * p; sg[c] += g; sgg[c] += (double)g * g; sgp[c] += (double)g * p;
-        mn[c] = fmin(mn[c], (double)g); mx[c] = fmax(mx[c], (double)g);
-      }
+      for (int c = 0; c < NC && c < kPsnrMaxC; ++c) acc[c].add(o[c], a.gt[cpix + c]);
     }
   }
   if (PSNR) {
-    constexpr int kSlots = kPsnrMaxC * 7;
-#pragma unroll
-    for (int c = 0; c < kPsnrMaxC; ++c) {
-      block_park<RedSum>(sp[c], red, kSlots, c * 7);
-      block_park<RedSum>(spp[c], red, kSlots, c * 7 + 1);
-      block_park<RedSum>(sg[c], red, kSlots, c * 7 + 2);
-      block_park<RedSum>(sgg[c], red, kSlots, c * 7 + 3);
-      block_park<RedSum>(sgp[c], red, kSlots, c * 7 + 4);
-      block_park<RedMin>(mn[c], red, kSlots, c * 7 + 5);
-      block_park<RedMax>(mx[c], red, kSlots, c * 7 + 6);
-    }
-    __syncthreads();
-    if (threadIdx.x < a.C * 8) {
-      const int c = threadIdx.x >> 3, kk = threadIdx.x & 7;
-      double o = 0;
-      if (kk < 5) o = block_combine<RedSum, Pairwise>(red, kSlots, c * 7 + kk);
-      else if (kk == 5) o = block_combine<RedMin, Pairwise>(red, kSlots, c * 7 + 5);
-      else if (kk == 6) o = block_combine<RedMax, Pairwise>(red, kSlots, c * 7 + 6);
-      const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x, blocks = (size_t)gridDim.x * gridDim.y;
-      a.part[(((size_t)n * blocks + b) * a.C + c) * 8 + kk] = o;
-    }
+    const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x, blocks = (size_t)gridDim.x * gridDim.y;
+    psnr_sums_write(acc, a.C, red, a.part + ((size_t)n * blocks + b) * a.C * 8);
   }
 }
 template <int CT, bool WIDE>

@@ -7,7 +7,7 @@ import torch
 
 from .. import parallel
 from .._lib import DsxError
-from .tiling import TilePlan
+from .tiling import PSNR_MAX_CHANNELS, TilePlan
 
 
 class TileExchange:
@@ -246,7 +246,7 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     gt = None
     if hasattr(dataset, "normalized_target_frames"):
         gt = dataset.normalized_target_frames()                       # every rank holds the frames: no collective
-        if gt.shape[-1] != C_out or C_out > 4:
+        if gt.shape[-1] != C_out or C_out > PSNR_MAX_CHANNELS:
             gt = None
     ex = ex_std = None
     ids = parallel.shard_ids(plan.total, parallel.rank(), parallel.world_size())
@@ -364,7 +364,7 @@ def _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, 
     C_out = netG.prediction_channels
     if hasattr(dataset, "normalized_target_frames"):
         gt = dataset.normalized_target_frames()
-        if gt.shape[-1] == C_out and C_out <= 4 and X.shape[-1] == C_out:
+        if gt.shape[-1] == C_out and C_out <= PSNR_MAX_CHANNELS and X.shape[-1] == C_out:
             out["psnr"] = plan.stitch_with_psnr(plan.gather_canvas(X), gt)[1]
     if return_std:
         out["std"] = spread

@@ -7,8 +7,10 @@ import torch
 
 from .. import _lib
 from .._lib import DsxError, check, lib
+from ..core.psnr import range_invariant_psnr_from_sums
 
 TRIM, PAD, SHIFT = _lib.TILING_TRIM, _lib.TILING_PAD, _lib.TILING_SHIFT
+PSNR_MAX_CHANNELS = 4      # kPsnrMaxC (csrc/dsx_kernels.h): channels of a paste or blend that takes the PSNR sums
 
 
 def _i64x3(v):
@@ -197,8 +199,8 @@ class TilePlan:
         gt = gt.to(torch.float32).contiguous()
         if tuple(gt.shape) != self.data_shape + (Cn,) or not gt.is_cuda:
             raise DsxError(f"gt must be a CUDA tensor of shape {self.data_shape + (Cn,)}")
-        if Cn > 4:
-            raise DsxError("the fused PSNR sums handle at most 4 channels")
+        if Cn > PSNR_MAX_CHANNELS:
+            raise DsxError(f"the fused PSNR sums handle at most {PSNR_MAX_CHANNELS} channels")
         return gt
 
     def stitch_psnr_into(self, tiles, tile_ids, canvas, gt, partials):
@@ -367,18 +369,3 @@ class TilePlan:
             for k, i in enumerate(ids):
                 call(int(i), 1, 1, out[k:])
         return out
-
-
-def range_invariant_psnr_from_sums(sp, spp, sg, sgg, sgp, gmin, gmax, n):
-    """core/psnr.py:70-82 in closed form.  With g_ = (g - mean g) / std g (unbiased std, as torch.std) and
-    p0 = p - mean p:  alpha = <g_, p0> / <p0, p0>,  mse = (<g_, g_> - <g_, p0>^2 / <p0, p0>) / n,
-    PSNR = 20 log10( ((max g - min g) / std g) / sqrt(mse) )."""
-    mean_g, mean_p = sg / n, sp / n
-    var_g = (sgg - n * mean_g * mean_g) / (n - 1.0)
-    std_g = torch.sqrt(var_g)
-    gg = (sgg - n * mean_g * mean_g) / var_g                        # = n - 1
-    gp = (sgp - n * mean_g * mean_p) / std_g
-    pp = spp - n * mean_p * mean_p
-    mse = (gg - gp * gp / pp) / n
-    ra = (gmax - gmin) / std_g
-    return 20.0 * torch.log10(ra / torch.sqrt(mse))

@@ -73,6 +73,22 @@ def psnr(img1, img2, peak=255.0):
     return float("inf") if mse == 0 else 20 * math.log10(peak / math.sqrt(mse))
 
 
+def range_invariant_psnr(gt, pred, dtype=np.float64):
+    """RangeInvariantPsnr (core/psnr.py:28-39) per (frame, channel) of (N, ..., C) arrays, every step in ``dtype``."""
+    N, C_ = gt.shape[0], gt.shape[-1]
+    out = np.zeros((N, C_), dtype)
+    for n in range(N):
+        for c in range(C_):
+            g, p = gt[n, ..., c].astype(dtype).ravel(), pred[n, ..., c].astype(dtype).ravel()
+            ra = (g.max() - g.min()) / g.std(ddof=1)
+            g_ = (g - g.mean()) / g.std(ddof=1)
+            g_ = g_ - g_.mean()
+            p0 = p - p.mean()
+            alpha = (g_ * p0).sum() / (p0 * p0).sum()
+            out[n, c] = 20 * np.log10(ra / np.sqrt(((g_ - alpha * p0) ** 2).mean()))
+    return out
+
+
 def tie_values(min_max, n_per_level=1):
     """fp32 inputs whose tensor2img value before rounding is exactly k + 0.5 (round half to even decides them)."""
     lo, rng = np.float32(min_max[0]), np.float32(min_max[1] - min_max[0])

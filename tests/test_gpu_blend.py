@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from tests import blend_ref
+from tests.metrics_ref import range_invariant_psnr
 from tests.test_gpu_field import (BATCH, SEED, SOLVERS, Source, _crops, _indi, _run, _sr3, _stack32, _stochastic_steps,
                                   same_bits)
 
@@ -98,21 +99,6 @@ def test_the_rank_slot_layouts_give_the_one_rank_bits(world):
 
 
 # ----------------------------------------------------------------------------- 3. PSNR
-def _psnr64(gt, pred):
-    """core/psnr.py:70-82 (RangeInvariantPsnr) per (frame, channel) in float64"""
-    N, C_ = gt.shape[0], gt.shape[-1]
-    out = np.zeros((N, C_))
-    for n in range(N):
-        for c in range(C_):
-            g, p = gt[n, ..., c].astype(np.float64).ravel(), pred[n, ..., c].astype(np.float64).ravel()
-            ra = (g.max() - g.min()) / g.std(ddof=1)
-            g_ = (g - g.mean()) / g.std(ddof=1)
-            p0 = p - p.mean()
-            alpha = (g_ * p0).sum() / (p0 * p0).sum()
-            out[n, c] = 20 * np.log10(ra / np.sqrt(((g_ - alpha * p0) ** 2).mean()))
-    return out
-
-
 @pytest.mark.parametrize("Cn", [1, 2, 3, 4])
 def test_blend_psnr(Cn):
     plan = _plan((2, 40, 57), 16, 8)
@@ -126,7 +112,7 @@ def test_blend_psnr(Cn):
     assert part.shape == (2, plan.blend_blocks(), Cn, 8)
     want = blend_ref.blend_ref(plan, tiles, *blend_ref.window_pair(plan, "triangle"))
     assert _same(canvas, want) and same_bits(canvas, plan.blend(t))
-    err = np.abs(psnr.cpu().numpy() - _psnr64(gt, want)).max()
+    err = np.abs(psnr.cpu().numpy() - range_invariant_psnr(gt, want)).max()
     print(f"\nC = {Cn}: largest |psnr - float64| = {err:.3e}")
     assert err < 1e-3                                                   # the bound of the stitch-PSNR test (test_gpu_boundary)
     plan.blend(t, gt=torch.from_numpy(gt).cuda())
@@ -212,7 +198,7 @@ def test_predict_stack_blend_psnr():
     out, plan = predict_stack(smp, val, batch_tiles=BATCH, solver=solver, seed=SEED, stitch="blend")
     assert plan.total == 12 and out["psnr"].shape == (2, 2)
     gt = val.normalized_target_frames()
-    want = _psnr64(gt.cpu().numpy(), out["mean"].cpu().numpy())
+    want = range_invariant_psnr(gt.cpu().numpy(), out["mean"].cpu().numpy())
     assert np.abs(out["psnr"].cpu().numpy() - want).max() < 1e-3
     tiles = torch.cat([_run(smp, val.tiles(list(range(i, i + BATCH)))["input"], solver, seed=SEED,
                             sample_ids=list(range(i, i + BATCH))) for i in range(0, plan.total, BATCH)])

@@ -1,10 +1,11 @@
 """The bits of every kernel that reduces through csrc/dsx_reduce.h, on the MI355X (`-m gpu`).
 
 "Fixed order, bitwise reproducible" is otherwise only tested as "two runs agree".  tests/golden/reduce_bits.npz holds
-the outputs of the cases below as the library of the commit named in its ``meta`` entry produced them -- the commit in
-front of the one that introduced the shared reduction; tools/gen_reduce_golden.py wrote it through these same functions
-with that commit's library loaded.  The comparison is on the raw bits, no tolerance: a butterfly or a combine whose
-order changes shows here, and the fix is the order, never the fixture.
+the outputs of the cases below as the libraries of the commits named in its ``meta`` entry produced them -- for every
+group of cases the commit in front of the one that restated its reductions (the shared reduction; the row reduction and
+the PSNR accumulator); tools/gen_reduce_golden.py wrote it through these same functions with that commit's library
+loaded.  The comparison is on the raw bits, no tolerance: a butterfly or a combine whose order changes shows here, and
+the fix is the order, never the fixture.
 
 Shapes: the smallest that give a full chunk, a ragged tail with partly idle waves and more than one workgroup per
 reduction (stated per case).  Inputs come from seeded CPU generators; only outputs are stored."""
@@ -116,10 +117,70 @@ def case_time_predictor():
     return {"t_out": tp(_randn((2, 1, 32, 32), 151).cuda()).reshape(2).cpu().numpy()}
 
 
+def case_blend_psnr():
+    """dsx_tileplan_blend with gt (k_blend's sums): frames (2, 40, 300), grid 16, patch 32 -- 72 tiles, two 256-pixel
+    segments per row, the second ragged (44 live lanes: three idle waves and a partly idle one); the "hann" window, so
+    the weights are inexact; C = 2 (the wide store) and C = 3."""
+    from diffsplitting_amd.data.tiling import TilePlan
+    plan = TilePlan((2, 40, 300), (1, 16, 16), (1, 32, 32))
+    plan.set_window("hann")
+    out = {}
+    for Cn in (2, 3):
+        tiles = _randn((plan.total, Cn, 32, 32), 160 + Cn).cuda()
+        gt = (_randn((2, 40, 300, Cn), 170 + Cn) * 1.5 + 0.25).cuda()
+        canvas, _ = plan.blend(tiles, gt=gt)
+        out[f"partials_c{Cn}"], out[f"canvas_c{Cn}"] = plan.last_blend_partials.cpu().numpy(), canvas.cpu().numpy()
+    return out
+
+
+def case_stitch_psnr_packed():
+    """dsx_tileplan_paste_packed with gt (k_stitch_psnr's packed source): the plan, tiles and gt of case_stitch_psnr,
+    the tiles packed for world = 3 into one exchange buffer."""
+    from diffsplitting_amd.data.tiling import TilePlan
+    plan = TilePlan((2, 40, 56), (1, 16, 16), (1, 32, 32))
+    tiles = _randn((plan.total, 2, 32, 32), 121).cuda()
+    gt = (_randn((2, 40, 56, 2), 122) * 1.5 + 0.25).cuda()
+    world = 3
+    flat = torch.zeros((world, plan.rank_stride(world, 2)), device="cuda")
+    for q in range(world):
+        plan.pack(tiles[q::world], world, q, flat[q])
+    canvas, psnr = plan.paste_packed(flat, 2, world, gt=gt)
+    return {"canvas": canvas.cpu().numpy(), "psnr": psnr.cpu().numpy()}
+
+
+def case_msssim():
+    """dsx_msssim, five scales, on one (1, 2, 177, 179) pair: 31683 pixels per plane = two statistics chunks, the second
+    with a partly idle last pass; range-invariant (k_msssim_stats, k_msssim_coef) and with data_range = 2."""
+    from diffsplitting_amd.core.metrics import msssim
+    target = _randn((1, 2, 177, 179), 181, 0.8).cuda()
+    pred = (0.7 * target.cpu() + _randn((1, 2, 177, 179), 182, 0.3) + 0.4).cuda()
+    out = {}
+    for name, kw in (("range_invariant", {"range_invariant": True}), ("data_range", {"data_range": 2.0})):
+        out[name] = msssim(pred, target, return_scales=True, **kw)[1].numpy()
+    return out
+
+
+def case_comoments():
+    """dsx_comoments on three planes: n = 8200 contiguous (the 16-byte path, two workgroups of 4100 pixels per plane,
+    the last pass of each with one live thread) and n = 8229 read as channel 1 of a (3, 2, 8229) tensor (the strided
+    path, a ragged last group)."""
+    from diffsplitting_amd.core.psnr import comoments
+    out = {}
+    for name, n in (("contiguous", 8200), ("strided", 8229)):
+        planes = [(_randn((3, 2, n), 190 + k, 30.0) + 1000.0 * k).cuda() for k in range(3)]
+        if name == "contiguous":
+            planes = [x[:, 1].contiguous() for x in planes]
+        else:
+            planes = [x[:, 1] for x in planes]
+        out[name] = comoments(*planes).cpu().numpy()
+    return out
+
+
 # shared with tools/gen_reduce_golden.py: fixture key = "<case>/<output>"
 CASES = {"loss": case_loss, "image_metrics": case_image_metrics, "stitch_psnr": case_stitch_psnr,
          "mix_range": case_mix_range, "val_report": case_val_report, "lpips": case_lpips,
-         "time_predictor": case_time_predictor}
+         "time_predictor": case_time_predictor, "blend_psnr": case_blend_psnr,
+         "stitch_psnr_packed": case_stitch_psnr_packed, "msssim": case_msssim, "comoments": case_comoments}
 
 
 @pytest.fixture(scope="module")

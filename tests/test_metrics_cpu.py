@@ -128,3 +128,21 @@ def test_calculate_ssim_has_no_cpu_fallback():
         pytest.skip("GPU present")
     with pytest.raises(_lib.DsxError):
         calculate_ssim(np.zeros((16, 16), np.uint8), np.zeros((16, 16), np.uint8))
+
+
+def test_range_invariant_psnr_from_sums_is_the_metric():
+    """The closed form on float64 sums of 20 fp32 plane pairs against the metric itself restated in longdouble
+    (core/psnr.py:28-39).  On these inputs the two differ by a few 1e-14 dB: float64 rounding of sums of 1517 terms."""
+    from diffsplitting_amd.core.psnr import range_invariant_psnr_from_sums
+    from tests.metrics_ref import range_invariant_psnr
+    gen = torch.Generator().manual_seed(2024)
+    g = torch.randn((20, 37, 41, 1), generator=gen) * 1.5 + 0.25
+    p = 0.7 * g + 0.5 * torch.randn((20, 37, 41, 1), generator=gen) + 3.0
+    g64, p64 = g.double().reshape(20, -1), p.double().reshape(20, -1)
+    got = range_invariant_psnr_from_sums(p64.sum(1), (p64 * p64).sum(1), g64.sum(1), (g64 * g64).sum(1), (g64 * p64).sum(1),
+                                         g64.amin(1), g64.amax(1), float(37 * 41))
+    want = range_invariant_psnr(g.numpy(), p.numpy(), np.longdouble)[:, 0]
+    err = np.abs(got.numpy().astype(np.longdouble) - want).max()
+    print(f"\nlargest |closed form - longdouble metric| = {float(err):.3e} dB over PSNRs {float(want.min()):.2f} .. "
+          f"{float(want.max()):.2f} dB")
+    assert got.dtype == torch.float64 and err < 1e-10
