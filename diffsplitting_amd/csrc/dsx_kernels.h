@@ -726,6 +726,8 @@ hipError_t launch_tiles_pack(const float* tiles, int C, int ph, int pw, const in
 // (world == 1: (total, C, ph, pw)).  The plan's tiles are frame-major, ny x nx per frame, tile (iy, ix) of frame n is
 // id (n*ny + iy)*nx + ix; rows[y] = (first tile row, count) and cols[x] = (first tile column, count) name the
 // contributors of a canvas pixel, wy / wx the separable window.  gt != nullptr: also part[N][blocks][C][8] (C <= kPsnrMaxC).
+// step != 0 (dsx_tileplan_blend_step; gt == nullptr): the canvas is a frame state, updated in place with the blended
+// value as x0:  X = c_x0*v + c_xt*X (+ z*sigma where sigma != 0), z from the noise field (seed, id_base + n, draw).
 struct BlendArgs {
   const float* tiles; int C, world; long long rank_stride;
   int N, H, W, ph, pw, ny, nx;
@@ -733,6 +735,8 @@ struct BlendArgs {
   const int* rows; const int* cols;  // dev [H][2], [W][2]
   const float* wy; const float* wx;  // dev [ph], [pw]
   float* canvas; const float* gt; double* part;
+  int step; float c_x0, c_xt, sigma;
+  unsigned long long seed, id_base; unsigned draw;
 };
 // workgroups per frame of a blend of (H, W) frames: segments of 256 pixels along x times at most 128 row slots
 struct BlendGrid { int segs, rows; };

@@ -651,9 +651,10 @@ extern "C" int dsx_tileplan_blend_blocks(const dsx_tileplan* p) {
   const BlendGrid bg = blend_grid(p->t.D[1], p->t.D[2]);
   return bg.segs * bg.rows;
 }
-extern "C" int dsx_tileplan_blend(dsx_tileplan* p, const float* tiles_dev, int C, int world, int64_t rank_stride_elems,
-                                  float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream) {
-  const char* what = "tileplan_blend";
+// what dsx_tileplan_blend and dsx_tileplan_blend_step refuse alike, on the host alone
+static int blend_checks(const char* what, const dsx_tileplan* p, const float* tiles_dev, int C, int world,
+                        int64_t rank_stride_elems, const float* canvas_dev, const float* gt_canvas_dev,
+                        const double* partials_dev) {
   if (!p || !tiles_dev || !canvas_dev) return fail(DSX_ERR_INVALID, "%s: null argument", what);
   if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
   if (world < 1) return fail(DSX_ERR_INVALID, "%s: world = %d, must be at least 1", what, world);
@@ -672,6 +673,10 @@ extern "C" int dsx_tileplan_blend(dsx_tileplan* p, const float* tiles_dev, int C
   if (world > 1 && (rank_stride_elems < 0 || most > rank_stride_elems / (tile_elems * C)))
     return fail(DSX_ERR_INVALID, "%s: rank_stride_elems = %lld is smaller than rank 0's %lld whole tiles", what,
                 (long long)rank_stride_elems, (long long)most);
+  return DSX_OK;
+}
+// the tables and the window on the device (first use), then the one launch of both calls
+static int blend_launch(const char* what, dsx_tileplan* p, BlendArgs a, void* stream) {
   int rc = plan_device(p);
   if (rc) return rc;
   if (p->window_stale) {
@@ -680,12 +685,44 @@ extern "C" int dsx_tileplan_blend(dsx_tileplan* p, const float* tiles_dev, int C
       return fail(DSX_ERR_HIP, "%s: upload of the window failed", what);
     p->window_stale = false;
   }
-  const BlendArgs a{tiles_dev, C, world, rank_stride_elems, (int)p->t.D[0], (int)p->t.D[1], (int)p->t.D[2], (int)p->t.p[1],
-                    (int)p->t.p[2], (int)p->t.dim_count(1), (int)p->t.dim_count(2), p->d_starts.as<int>(), p->d_rows,
-                    p->d_cols, p->d_window.as<float>(), p->d_window.as<float>() + p->t.p[1], canvas_dev, gt_canvas_dev,
-                    partials_dev};
+  a.N = (int)p->t.D[0]; a.H = (int)p->t.D[1]; a.W = (int)p->t.D[2]; a.ph = (int)p->t.p[1]; a.pw = (int)p->t.p[2];
+  a.ny = (int)p->t.dim_count(1); a.nx = (int)p->t.dim_count(2);
+  a.starts = p->d_starts.as<int>(); a.rows = p->d_rows; a.cols = p->d_cols;
+  a.wy = p->d_window.as<float>(); a.wx = p->d_window.as<float>() + p->t.p[1];
   HIP_TRY(launch_blend(a, (hipStream_t)stream));
   return DSX_OK;
+}
+extern "C" int dsx_tileplan_blend(dsx_tileplan* p, const float* tiles_dev, int C, int world, int64_t rank_stride_elems,
+                                  float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream) {
+  const char* what = "tileplan_blend";
+  const int rc = blend_checks(what, p, tiles_dev, C, world, rank_stride_elems, canvas_dev, gt_canvas_dev, partials_dev);
+  if (rc) return rc;
+  BlendArgs a{};
+  a.tiles = tiles_dev; a.C = C; a.world = world; a.rank_stride = rank_stride_elems;
+  a.canvas = canvas_dev; a.gt = gt_canvas_dev; a.part = partials_dev;
+  return blend_launch(what, p, a, stream);
+}
+// the blend as the x0 of one reverse step on the frame state (contract: include/dsx.h)
+extern "C" int dsx_tileplan_blend_step(dsx_tileplan* p, const float* x0_tiles_dev, int C, int world,
+                                       int64_t rank_stride_elems, float* state_dev, float c_x0, float c_xt, float sigma,
+                                       uint64_t seed, uint64_t id_base, uint32_t draw, void* stream) {
+  const char* what = "tileplan_blend_step";
+  const int rc = blend_checks(what, p, x0_tiles_dev, C, world, rank_stride_elems, state_dev, nullptr, nullptr);
+  if (rc) return rc;
+  const uint64_t frames = (uint64_t)p->t.D[0];
+  if (id_base >= DSX_STREAM_ID_LIMIT || id_base + (frames - 1) >= DSX_STREAM_ID_LIMIT)
+    return fail(DSX_ERR_INVALID, "%s: id_base = %llu with %llu frames: every field id must be below 2^40", what,
+                (unsigned long long)id_base, (unsigned long long)frames);
+  if (draw >= DSX_STREAM_DRAW_LIMIT)
+    return fail(DSX_ERR_INVALID, "%s: draw ordinal %u, must be below 2^24", what, (unsigned)draw);
+  if (!std::isfinite(c_x0) || !std::isfinite(c_xt) || !std::isfinite(sigma))
+    return fail(DSX_ERR_INVALID, "%s: c_x0 = %g, c_xt = %g, sigma = %g: every coefficient must be finite", what,
+                (double)c_x0, (double)c_xt, (double)sigma);
+  BlendArgs a{};
+  a.tiles = x0_tiles_dev; a.C = C; a.world = world; a.rank_stride = rank_stride_elems;
+  a.canvas = state_dev;
+  a.step = 1; a.c_x0 = c_x0; a.c_xt = c_xt; a.sigma = sigma; a.seed = seed; a.id_base = id_base; a.draw = draw;
+  return blend_launch(what, p, a, stream);
 }
 // tiles first + k * stride of the plan out of a (N,H,W,C) frame state -> (count, C, ph, pw)
 extern "C" int dsx_tileplan_gather_canvas(dsx_tileplan* p, const float* canvas_dev, int C, int64_t first, int64_t stride,

@@ -443,6 +443,13 @@ hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions, TileSeq 
 // (C = 2 / 4 and the canvas aligned to it), otherwise one dword per channel.  CT = C for C <= 4; CT = 0 is any C, one
 // channel after the other.  PSNR: the seven RangeInvariantPsnr sums of k_stitch_psnr per (frame, workgroup, channel),
 // through the same fixed-order block reduction (C <= kPsnrMaxC).  No LDS beyond those slots, no atomics.
+// STEP (include/dsx.h, dsx_tileplan_blend_step): the canvas is a frame state X, updated in place by the thread that
+// owns the pixel -- read once, written once -- with the blended value v as the x0 of one reverse step without an eps
+// form (step_update, dsx_kernels.h):  mean = c_x0*v + c_xt*X;  out = sigma != 0 ? mean + z*sigma : mean,  z = element
+// j = (c*H + y)*W + x of the stream (seed, ((id_base + n) << 24) | draw): the frame's noise field, what k_randn_samples
+// writes and k_tiles_randn crops.  The canvas is NHWC and the field CHW, so the C values of a pixel lie in C different
+// Philox blocks and the four elements of a block in four neighbouring lanes: every lane computes the block of its
+// element and keeps its component (normal1: one log and one sincos, not two).  Nothing is drawn where sigma == 0.
 // ---------------------------------------------------------------------------
 constexpr int kBlendCols = 4;                  // tile columns of a pixel kept in registers
 __device__ __forceinline__ const float* blend_tile(const BlendArgs& a, unsigned t, unsigned tile_elems) {
@@ -476,7 +483,18 @@ __device__ __forceinline__ void blend_add(const BlendArgs& a, unsigned t, int pl
   }
   den = add_f(den, w);
 }
-template <int CT, bool WIDE, bool PSNR>
+// STEP: channel c of pixel (y, x) of a frame whose field is the stream `subseq`: blended value v and state xs -> new state
+__device__ __forceinline__ float blend_step(const BlendArgs& a, unsigned long long subseq, int c, int y, int x, float v,
+                                            float xs) {
+  const bool use_z = a.sigma != 0.f;
+  float z = 0.f;
+  if (use_z) {
+    const unsigned long long j = ((unsigned long long)c * a.H + y) * a.W + x;
+    z = normal1(a.seed, subseq, j >> 2, (int)(j & 3));
+  }
+  return step_update(0.f, 0.f, a.c_x0, a.c_xt, 0.f, a.sigma, false, false, xs, v, 0.f, z, use_z).out;
+}
+template <int CT, bool WIDE, bool PSNR, bool STEP>
 __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
   constexpr int NC = CT > 0 ? CT : 1;
   __shared__ double red[PSNR ? kPsnrRed : 1];
@@ -484,6 +502,7 @@ __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
   const bool live = x < a.W;
   const unsigned tile0 = (unsigned)n * a.ny * a.nx;
   const int plane = a.ph * a.pw;
+  const unsigned long long subseq = ((a.id_base + (unsigned long long)n) << 24) | a.draw;   // STEP: the frame's field
   int tx0 = 0, txn = 0, xo[kBlendCols];
   float wxc[kBlendCols];
   if (live) { tx0 = a.cols[2 * x]; txn = a.cols[2 * x + 1]; }
@@ -498,12 +517,27 @@ __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
     const int ty0 = a.rows[2 * y], tyn = a.rows[2 * y + 1];
     const size_t cpix = (((size_t)n * a.H + y) * a.W + x) * a.C;
     if (CT == 0) {
-      for (int c = 0; c < a.C; ++c) a.canvas[cpix + c] = blend_pixel(a, tile0, ty0, tyn, tx0, txn, c, y, x);
+      for (int c = 0; c < a.C; ++c) {
+        const float v = blend_pixel(a, tile0, ty0, tyn, tx0, txn, c, y, x);
+        a.canvas[cpix + c] = STEP ? blend_step(a, subseq, c, y, x, v, a.canvas[cpix + c]) : v;
+      }
       continue;
     }
-    float num[NC], v[NC], den = 0.f;
+    float num[NC], v[NC], xs[NC], den = 0.f;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) num[c] = v[c] = 0.f;
+    for (int c = 0; c < NC; ++c) num[c] = v[c] = xs[c] = 0.f;
+    if (STEP) {                                  // the state's C values, read as they are written below; asked for before
+      if (WIDE && NC == 2) {                     // the tiles, so that the load is in flight under theirs
+        const float2 t = *(const float2*)(a.canvas + cpix);
+        xs[0] = t.x; xs[NC > 1 ? 1 : 0] = t.y;
+      } else if (WIDE && NC == 4) {
+        const float4 t = *(const float4*)(a.canvas + cpix);
+        xs[0] = t.x; xs[NC > 1 ? 1 : 0] = t.y; xs[NC > 2 ? 2 : 0] = t.z; xs[NC > 3 ? 3 : 0] = t.w;
+      } else {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) xs[c] = a.canvas[cpix + c];
+      }
+    }
     for (int iy = ty0; iy < ty0 + tyn; ++iy) {
       const unsigned trow = tile0 + (unsigned)iy * a.nx;       // tile (iy, 0): every tile of row iy starts at its y
       const int yy = y - a.starts[(size_t)trow * 3 + 1];
@@ -520,6 +554,10 @@ __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
     const bool one = tyn * txn == 1;
 #pragma unroll
     for (int c = 0; c < NC; ++c) o[c] = one ? v[c] : __fdiv_rn(num[c], den);
+    if (STEP) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) o[c] = blend_step(a, subseq, c, y, x, o[c], xs[c]);
+    }
     if (WIDE && NC == 2) *(float2*)(a.canvas + cpix) = make_float2(o[0], o[NC > 1 ? 1 : 0]);
     else if (WIDE && NC == 4) *(float4*)(a.canvas + cpix) = make_float4(o[0], o[NC > 1 ? 1 : 0], o[NC > 2 ? 2 : 0], o[NC > 3 ? 3 : 0]);
     else {
@@ -538,11 +576,13 @@ __global__ __launch_bounds__(256) void k_blend(const BlendArgs a) {
 }
 template <int CT, bool WIDE>
 static void launch_blend_as(const BlendArgs& a, const dim3 grid, hipStream_t st) {
-  if (a.gt != nullptr) hipLaunchKernelGGL((k_blend<CT, WIDE, true>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((k_blend<CT, WIDE, false>), grid, dim3(256), 0, st, a);
+  if (a.step) hipLaunchKernelGGL((k_blend<CT, WIDE, false, true>), grid, dim3(256), 0, st, a);
+  else if (a.gt != nullptr) hipLaunchKernelGGL((k_blend<CT, WIDE, true, false>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_blend<CT, WIDE, false, false>), grid, dim3(256), 0, st, a);
 }
 hipError_t launch_blend(const BlendArgs& a, hipStream_t st) {
   if (a.gt != nullptr && (a.C < 1 || a.C > kPsnrMaxC || a.part == nullptr)) return hipErrorInvalidValue;
+  if (a.step && a.gt != nullptr) return hipErrorInvalidValue;          // a step takes no PSNR sums
   if (a.N < 1 || a.N > 65535 || a.C < 1) return hipErrorInvalidValue;
   const BlendGrid bg = blend_grid(a.H, a.W);
   const dim3 grid((unsigned)bg.segs, (unsigned)bg.rows, (unsigned)a.N);
@@ -553,7 +593,8 @@ hipError_t launch_blend(const BlendArgs& a, hipStream_t st) {
   else if (a.C == 3) launch_blend_as<3, false>(a, grid, st);
   else if (a.C == 4 && (at & 15u) == 0) launch_blend_as<4, true>(a, grid, st);
   else if (a.C == 4) launch_blend_as<4, false>(a, grid, st);
-  else hipLaunchKernelGGL((k_blend<0, false, false>), grid, dim3(256), 0, st, a);
+  else if (a.step) hipLaunchKernelGGL((k_blend<0, false, false, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_blend<0, false, false, false>), grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -2,7 +2,13 @@
 (notebooks/EvaluateJointIndi.ipynb cells 23-26: one tile per ``test()`` call,
 490 strictly serial calls, numpy stitch on the host) as a device-resident
 pipeline: gather tiles on the GPU -> batches of tiles through the sampler ->
-(multi-GPU: one all-gather) -> HIP stitch into the (N,H,W,C) canvas."""
+(multi-GPU: one all-gather) -> HIP stitch into the (N,H,W,C) canvas.
+
+Beyond the paste: blended stitching (``TileExchange(blend=True)``), per-step frame fusion for the Gaussian few-step
+solvers (``predict_stack(fuse=True)``, ``fused_sample``) and frame diffusion for the InDI family
+(``predict_stack_frames``, ``frame_sample``): every frame is one state, a row is one UNet forward per batch of tiles cut
+out of it and one ``TilePlan.blend_step`` launch -- blend of the x0 tiles, InDI update and the frame's noise field in one
+kernel --, over any number of ranks with one all-gather of whole x0 tiles per row."""
 import torch
 
 from .. import parallel
@@ -210,8 +216,8 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
             raise DsxError("predict_stack: fuse with stitch='crop': a fused frame is a blend of its tiles; leave stitch "
                            "out or give 'blend'")
         if not _is_gaussian(netG):
-            raise DsxError(f"predict_stack: fuse: {type(netG).__name__} is not a Gaussian sampler (sr3 / ddpm); fusion "
-                           "for the InDI family is not provided")
+            raise DsxError(f"predict_stack: fuse: {type(netG).__name__} is not a Gaussian sampler (sr3 / ddpm); frame "
+                           "diffusion for the InDI family is predict_stack_frames")
         if not solver:
             raise DsxError("predict_stack: fuse needs solver=: the rows of a few-step solver are fused; the ancestral "
                            "loop is not")
@@ -369,6 +375,136 @@ def _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, 
     if return_std:
         out["std"] = spread
     return out
+
+
+# ---- frame diffusion for the InDI family ----------------------------------------------------------------------------
+def _indi_children(netG, t_float_start):
+    """[(InDI sampler, its start time, the bit its field ids carry)]: the sampler itself, or the two children of a joint
+    sampler (indi1 at t, indi2 at 1 - t under ``STREAM2_BIT``; ``JointIndiSampler.inference``'s defaults)."""
+    if hasattr(netG, "indi1"):
+        t = 0.5 if t_float_start is None else t_float_start
+        return [(netG.indi1, t, 0), (netG.indi2, 1 - t, netG.STREAM2_BIT)]
+    return [(netG, 1.0 if t_float_start is None else t_float_start, 0)]
+
+
+def input_frames(dataset, batch_tiles=8):
+    """The normalised input of every frame, (N,H,W,Cin): the crop-paste (a copy) of the dataset's own input tiles.  Every
+    rank holds the frames, so every rank cuts all tiles: no collective."""
+    plan = dataset.plan
+    canvas = None
+    for i in range(0, plan.total, max(1, int(batch_tiles))):
+        chunk = list(range(i, min(i + max(1, int(batch_tiles)), plan.total)))
+        canvas = plan.stitch(dataset.tiles(chunk)["input"], chunk, canvas)
+    return canvas
+
+
+def frame_sample(child, dataset, x_in, num_timesteps, t_float_start, batch_tiles, seed, id_base, group=None,
+                 keep_tiles=None):
+    """One posterior sample of frame diffusion with the InDI sampler ``child`` -> the frame state (N,H,W,C) after the
+    last row of ``engine.indi_step_table``.  ``x_in`` (N,H,W,Cin): the normalised input frames.  The state starts as
+    ``x_in`` (repeated to the sampler's channels) ``+ Z0 * (e * t)``, Z0 draw 0 of the noise fields ``id_base + n``; per
+    row ``s`` and batch of this rank's tiles: ``gather_canvas`` -> ``denoise_fn`` -> a resident (local tiles, C, p, p) x0
+    buffer, the rank's slot of the exchange buffer; after the row's last batch one all-gather of the slots (several
+    ranks) and one ``TilePlan.blend_step`` with draw ``s + 1``: the whole InDI update of the row, on the canvas.  A short
+    last batch is moved back (one executor).  ``keep_tiles``: a list that receives the x0 tiles of every row before
+    their blend (a copy per row; one rank)."""
+    from .. import engine
+    plan = dataset.plan
+    N, H, W = plan.data_shape
+    dev = x_in.device
+    rank, world = parallel.rank(), parallel.world_size()
+    copies = child._copies(x_in.permute(0, 3, 1, 2))
+    X = torch.cat([x_in] * copies, dim=-1)
+    Cn = int(X.shape[-1])
+    fids = [id_base + n for n in range(N)]
+    z0 = engine.randn_samples((N, Cn, H, W), seed, fids, draw=0, device=dev).permute(0, 2, 3, 1)
+    scale = (child.e * torch.Tensor([t_float_start])).to(dev)          # InDISampler._start's two operations
+    X = (X + z0 * scale).contiguous()
+    table = engine.indi_step_table(num_timesteps, t_float_start, child.e)
+    flat = torch.zeros(plan.blend_rank_stride(world, Cn), dtype=torch.float32, device=dev)
+    x0t = flat.view((-1, Cn) + plan.patch_shape[1:])
+    batches = list(_batches(parallel.shard_ids(plan.total, rank, world), batch_tiles))
+    for s in range(table.n_steps):
+        time = torch.Tensor([float(table.tcond[s])]).to(dev)
+        for chunk, keep in batches:
+            x0 = child.denoise_fn(plan.gather_canvas(X, chunk), time)
+            last = chunk[-1] // world + 1
+            x0t[last - keep:last] = x0[len(chunk) - keep:]
+        if keep_tiles is not None:
+            keep_tiles.append(x0t.clone())
+        row = (float(table.c1[s]), float(table.c2[s]), float(table.sigma[s]), seed, s + 1, id_base)
+        if world == 1:
+            plan.blend_step(x0t, X, *row)
+        else:
+            full = parallel.all_gather_flat(flat, group)              # the row's one collective, of whole x0 tiles
+            plan.blend_step(full, X, *row, world=world, Cn=Cn)
+    return X
+
+
+@torch.no_grad()
+def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_float_start=None, samples=1,
+                         return_std=False, seed=None, group=None, window="triangle"):
+    """``predict_stack`` for the InDI family (``InDISampler`` and its subclasses, ``JointIndiSampler``) with every frame
+    diffused as ONE state: frame diffusion.  The InDI update ``x <- (d/t) x0 + (1 - d/t) x + e (t - d) z`` is affine in
+    the UNet output with coefficients shared by the batch, so a row of a frame is ``X <- c_x0 * blend(x0 tiles) +
+    c_xt * X + sigma * Z`` on the canvas, ``Z`` the frame's noise field: one ``TilePlan.blend_step`` launch per row --
+    no per-tile step launch and no per-tile noise tensors (``frame_sample``).  Overlapping tiles are cut from one
+    state, so they agree after every row, not only in the last blend.
+
+    Returns ``(out, plan)`` with ``predict_stack``'s keys, on every rank.  Posterior sample ``r`` takes the field ids
+    ``r * frames + n``; a joint sampler's second child adds ``STREAM2_BIT``, its two children run one after the other
+    and their states are joined along the channels.  ``t_float_start``: one start time for every frame (default: 1.0,
+    0.5 for a joint sampler, whose second child starts at ``1 - t``).  Tiles are sharded over the ranks: one collective
+    per row and child, every rank holds the same state.  ``samples > 1``: mean and spread over the frame states
+    (``engine.moments_update``).  With one tile per frame this is ``predict_stack(seed=, noise="field")`` bit for bit."""
+    from .. import engine
+    from ..model.samplers import InDISampler, JointIndiSampler
+    what = "predict_stack_frames"
+    if _is_gaussian(netG):
+        raise DsxError(f"{what}: {type(netG).__name__} is a Gaussian sampler (sr3 / ddpm): its per-step frame fusion is "
+                       "predict_stack(fuse=True)")
+    if not isinstance(netG, (InDISampler, JointIndiSampler)):
+        raise DsxError(f"{what}: {type(netG).__name__} is no InDI or JointIndi sampler")
+    if seed is None:
+        raise DsxError(f"{what} needs seed=: a frame's noise field is named by (seed, frame, draw)")
+    if torch.is_tensor(t_float_start) or isinstance(t_float_start, (list, tuple)) or \
+            (hasattr(t_float_start, "shape") and getattr(t_float_start, "ndim", 0) > 0):
+        raise DsxError(f"{what}: a per-sample t_float_start: a frame has one time; give one number")
+    samples = int(samples)
+    if samples < 1:
+        raise DsxError(f"{what}: samples = {samples}: a positive count")
+    children = _indi_children(netG, t_float_start)
+    for child, _, _ in children:
+        if child._noise_mode == "brownian":
+            raise DsxError(f"{what}: noise mode 'brownian' is not built (only 'gaussian')")
+    plan = dataset.plan
+    N = plan.data_shape[0]
+    if samples * N > (1 << 39):
+        raise DsxError(f"{what}: samples * frames exceeds the 2^39 field ids of one sampler")
+    _check_stitch(what, "blend", window)
+    plan.set_window(window)
+    x_in = input_frames(dataset, batch_tiles)
+    mean = m2 = X = None
+    for r in range(samples):
+        parts = [frame_sample(child, dataset, x_in, int(child.num_timesteps if num_timesteps is None else num_timesteps),
+                              t0, batch_tiles, seed, r * N + bit, group) for child, t0, bit in children]
+        X = parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
+        if samples > 1:
+            mean, m2 = engine.moments_update(X, mean, m2, r)
+    spread = None
+    if samples > 1:
+        X, spread = engine.moments_finish(mean, m2, samples, want_std=return_std)
+    elif return_std:
+        spread = torch.zeros_like(X)
+    out = {"mean": X}
+    C_out = netG.prediction_channels
+    if hasattr(dataset, "normalized_target_frames"):
+        gt = dataset.normalized_target_frames()
+        if gt.shape[-1] == C_out and C_out <= PSNR_MAX_CHANNELS and X.shape[-1] == C_out:
+            out["psnr"] = plan.stitch_with_psnr(plan.gather_canvas(X), gt)[1]
+    if return_std:
+        out["std"] = spread
+    return out, plan
 
 
 # ---- mixed-input evaluation (BASELINE C5: JointIndi + TimePredictor) -----------------------------------------------

@@ -347,6 +347,42 @@ class TilePlan:
         self.last_blend_partials = part
         return canvas if gt is None else (canvas, self.psnr_from_partials(part))
 
+    def blend_step(self, x0_tiles, state, c_x0, c_xt, sigma, seed, draw, id_base=0, world=1, Cn=None):
+        """One reverse step of the frame state with the blend of the tiles as its x0 (``dsx_tileplan_blend_step``):
+        ``state`` (N,H,W,C) fp32 CUDA, contiguous, is updated IN PLACE and returned --
+        ``X = c_x0 * blend(x0_tiles) + c_xt * X (+ Z * sigma where sigma != 0)``, every operation rounded on its own,
+        ``Z`` the noise field (seed, id_base + n, draw) of frame n: ``engine.randn_samples((N, C, H, W), seed,
+        [id_base + n], draw)`` in (N,H,W,C) order, generated inside the kernel.  ``x0_tiles``, ``world`` and ``Cn`` as
+        in ``blend``; the state must not alias the tiles."""
+        _lib.require_gpu()
+        world = int(world)
+        if world == 1:
+            x0_tiles = self._check_tiles(x0_tiles)
+            if x0_tiles.shape[0] != self.total:
+                raise DsxError("blend_step needs every tile of the plan")
+            Cn, stride = int(x0_tiles.shape[1]), 0
+        else:
+            x0_tiles = x0_tiles.contiguous()
+            if Cn is None or x0_tiles.dtype != torch.float32 or not x0_tiles.is_cuda:
+                raise DsxError("blend_step: a gathered buffer is a float32 CUDA tensor and needs its channel count Cn")
+            Cn, stride = int(Cn), x0_tiles.numel() // world
+            if stride < self.blend_rank_stride(world, Cn):
+                raise DsxError("blend_step: the gathered buffer must hold world slots of blend_rank_stride elements")
+        if not torch.is_tensor(state) or not state.is_cuda or state.dtype != torch.float32 or \
+                not state.is_contiguous() or tuple(state.shape) != self.data_shape + (Cn,):
+            raise DsxError(f"blend_step: the state must be a contiguous float32 CUDA tensor of shape "
+                           f"{self.data_shape + (Cn,)} (it is updated in place)")
+        draw, id_base = int(draw), int(id_base)
+        if not 0 <= draw < _lib.STREAM_DRAW_LIMIT:
+            raise DsxError(f"blend_step: draw ordinal {draw} out of range (0 <= draw < 2^24)")
+        if not 0 <= id_base <= _lib.STREAM_ID_LIMIT - self.data_shape[0]:
+            raise DsxError(f"blend_step: id_base = {id_base} with {self.data_shape[0]} frames: every field id must be "
+                           "below 2^40")
+        check(lib.dsx_tileplan_blend_step(self.handle, x0_tiles, Cn, world, stride, state, float(c_x0), float(c_xt),
+                                          float(sigma), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(id_base),
+                                          C.c_uint32(draw), None))
+        return state
+
     def gather_canvas(self, canvas, tile_ids=None):
         """The tiles ``tile_ids`` cut out of a multi-channel frame state ``canvas`` (N,H,W,C) fp32 CUDA -> (count, C, ph,
         pw), bit for bit the slices.  An arithmetic id sequence takes one launch, any other list one launch per tile."""

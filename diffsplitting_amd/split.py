@@ -53,6 +53,11 @@ pasting every tile's inner region (``--stitch crop``, the default); it works for
 ``--solver``, ``--sample-seed S`` and ``--noise-field``, one rank) diffuses every frame as one state: after every solver
 row the tiles are blended on a frame canvas and cut out again.
 
+``--frame-steps`` (an ``indi`` / ``joint_indi`` config with ``--sample-seed S``; any number of ranks) is frame diffusion
+for the InDI family (``predict_stack_frames``): every frame is one state, and a step of it is one kernel that blends
+the tiles' UNet outputs and applies the InDI update with the frame's noise field.  ``--samples``, ``--std-out``,
+``--window`` and ``--out`` work as with ``--stitch blend``.
+
 ``--ms-ssim`` also scores the stitched prediction with the range-invariant multi-scale SSIM
 (``core.metrics.calculate_msssim``, five scales): rank 0 logs mean +- standard error over the frames per channel.  It
 needs a ground truth (not with ``--input``, ``--validate`` or colour items) and frames of 176 x 176 or more.
@@ -243,6 +248,10 @@ def main(argv=None):
     ap.add_argument("--fuse-steps", action="store_true",
                     help="with --solver, --sample-seed and --noise-field: diffuse every frame as one state -- after every "
                          "solver row the tiles are blended on a frame canvas and cut out again (implies --stitch blend)")
+    ap.add_argument("--frame-steps", action="store_true",
+                    help="indi / joint_indi configs with --sample-seed: diffuse every frame as one state -- per step the "
+                         "tiles' UNet outputs are blended and the InDI update runs on the frame canvas, with the frame's "
+                         "noise field (implies --stitch blend; any number of ranks)")
     ap.add_argument("--ms-ssim", action="store_true",
                     help="also score the stitched prediction with the range-invariant multi-scale SSIM "
                          "(core.metrics.calculate_msssim: five scales, frames of 176 x 176 or more)")
@@ -250,6 +259,7 @@ def main(argv=None):
     _check_msssim_args(args)
     _check_solver_args(args)
     _check_stitch_args(args, len(str(args.gpu_ids).split(",")) if args.gpus is None else args.gpus)
+    _check_frame_args(args)
     if args.sample_seed is not None and args.validate:
         raise SystemExit("--sample-seed names the tiles of a tiled prediction: not with --validate")
     if args.phase == "train":
@@ -380,10 +390,16 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     t0 = time.perf_counter()
     # every rank holds the frames: the ground truth needs no tiles and no collective; the metric is accumulated while
     # pasting, and the path's only collectives are the cropped tiles of each output canvas
-    out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
-                              return_std=bool(args.std_out), seed=args.sample_seed, solver=solver,
-                              noise="field" if args.noise_field else "samples", stitch=args.stitch,
-                              window=args.window or "triangle", fuse=args.fuse_steps)
+    if args.frame_steps:
+        from .data.tiled_predict import predict_stack_frames
+        out, plan = predict_stack_frames(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps,
+                                         samples=samples, return_std=bool(args.std_out), seed=args.sample_seed,
+                                         window=args.window or "triangle")
+    else:
+        out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
+                                  return_std=bool(args.std_out), seed=args.sample_seed, solver=solver,
+                                  noise="field" if args.noise_field else "samples", stitch=args.stitch,
+                                  window=args.window or "triangle", fuse=args.fuse_steps)
     pred, ps = out["mean"], out.get("psnr")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -538,7 +554,7 @@ def _check_solver_args(args):
 def _check_stitch_args(args, n_ranks):
     """The flags of blended stitching and of per-step frame fusion, checked on the command line alone (nothing touches
     the GPU, no rank is started).  Without any of them: nothing."""
-    blend = args.stitch == "blend" or args.fuse_steps
+    blend = args.stitch == "blend" or args.fuse_steps or args.frame_steps
     if args.window is not None and not blend:
         raise SystemExit("--window: only with --stitch blend (the window weighs the overlap-add of whole tiles)")
     if args.stitch == "blend" and (args.validate or args.mix_t is not None):
@@ -558,6 +574,30 @@ def _check_stitch_args(args, n_ranks):
                          "noise, or the blend would shrink its variance")
     if n_ranks > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--fuse-steps runs on one rank: a collective after every solver row is not provided")
+
+
+def _check_frame_args(args):
+    """``--frame-steps``, checked on the command line and the config file alone (nothing touches the GPU, no rank is
+    started).  Without it: nothing."""
+    if not args.frame_steps:
+        return
+    if args.fuse_steps:
+        raise SystemExit("--frame-steps together with --fuse-steps: --fuse-steps fuses the rows of a Gaussian solver, "
+                         "--frame-steps diffuses the frames of an InDI config; give one")
+    if args.solver is not None:
+        raise SystemExit("--frame-steps with --solver: frame diffusion runs the InDI loop of an indi / joint_indi config; "
+                         "few-step solvers belong to sr3 / ddpm (--fuse-steps)")
+    which = (Logger.load_json(args.config).get("model") or {}).get("which_model_G")
+    if which not in ("indi", "joint_indi"):
+        raise SystemExit(f"--frame-steps diffuses the frames of an InDI sampler (which_model_G indi / joint_indi); this "
+                         f"config builds {which!r}: a Gaussian sampler's fusion is --solver with --fuse-steps")
+    if args.validate or args.mix_t is not None or args.mmse is not None:
+        raise SystemExit("--frame-steps diffuses the frames of a tiled prediction: not with --validate, --mix-t or --mmse")
+    if args.stitch == "crop":
+        raise SystemExit("--frame-steps with --stitch crop: a frame state is a blend of its tiles; leave --stitch out or "
+                         "give --stitch blend")
+    if args.sample_seed is None:
+        raise SystemExit("--frame-steps needs --sample-seed S: a frame's noise field is named by (seed, frame, draw)")
 
 
 def _solver_of(args):

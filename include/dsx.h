@@ -817,7 +817,22 @@ int dsx_tileplan_paste_packed(dsx_tileplan* plan, const float* flat_all_dev, int
  *     any HIP call.  No allocation, copy or synchronisation per call (the tables and the window go up at first use).
  *   dsx_tileplan_gather_canvas: the inverse cut -- the tiles first + k*stride, k < count, of the plan out of a
  *     multi-channel frame state canvas_dev (N,H,W,C) -> tiles_dev (count, C, ph, pw), bit for bit the slices.  Refusals
- *     as dsx_tileplan_randn's, under the name tileplan_gather_canvas. */
+ *     as dsx_tileplan_randn's, under the name tileplan_gather_canvas.
+ *   dsx_tileplan_blend_step: one reverse step of a whole frame state with the BLEND of the tiles as its x0 -- frame
+ *     diffusion for samplers whose update is affine in the network output with coefficients shared by the batch (the
+ *     InDI family).  x0_tiles_dev: the tiles in one of dsx_tileplan_blend's two layouts; state_dev (N,H,W,C) is
+ *     updated IN PLACE and must not alias the tiles.  Per canvas pixel (n, y, x) and channel c, fp32, every operation
+ *     rounded on its own (no fma):
+ *         v    = what dsx_tileplan_blend would write there (ascending tile id, num / den correctly rounded, a pixel
+ *                with one contributor is a copy)
+ *         mean = c_x0 * v + c_xt * X
+ *         out  = sigma == 0 ? mean : mean + z * sigma          (dsx_posterior_step's rules with predict_eps == 0)
+ *         z    = field(seed, id_base + n, draw)[c, y, x]: component j % 4 of Philox block j / 4 of the stream
+ *                (seed, ((id_base + n) << 24) | draw), j = (c*H + y)*W + x -- bitwise what dsx_randn_samples writes
+ *                for that frame and dsx_tileplan_randn crops.  With sigma == 0 nothing is generated.
+ *     A gather like the blend: the thread that owns a pixel reads its state once and writes it once; no atomics, no
+ *     LDS.  Everything dsx_tileplan_blend refuses, a null state, id_base + (N - 1) >= DSX_STREAM_ID_LIMIT,
+ *     draw >= DSX_STREAM_DRAW_LIMIT and a non-finite coefficient are DSX_ERR_INVALID before any HIP call. */
 int dsx_tileplan_contributors(const dsx_tileplan* plan, int32_t* rows /*[H][2]*/, int32_t* cols /*[W][2]*/);
 int dsx_tileplan_set_window(dsx_tileplan* plan, const float* wy_host /*ph*/, const float* wx_host /*pw*/);
 int dsx_tileplan_blend_blocks(const dsx_tileplan* plan);
@@ -825,6 +840,9 @@ int dsx_tileplan_blend(dsx_tileplan* plan, const float* tiles_dev, int C, int wo
                        float* canvas_dev, const float* gt_canvas_dev, double* partials_dev, void* stream);
 int dsx_tileplan_gather_canvas(dsx_tileplan* plan, const float* canvas_dev, int C, int64_t first, int64_t stride,
                                int64_t count, float* tiles_dev, void* stream);
+int dsx_tileplan_blend_step(dsx_tileplan* plan, const float* x0_tiles_dev, int C, int world, int64_t rank_stride_elems,
+                            float* state_dev, float c_x0, float c_xt, float sigma, uint64_t seed, uint64_t id_base,
+                            uint32_t draw, void* stream);
 
 /* ------------------------------------------------- frame files: uncompressed TIFF / BigTIFF stacks (host only)
  * Replaces imread(fpath, plugin='tifffile') of the Hagen loaders (data/split_dataset.py:76-91) for the files the
