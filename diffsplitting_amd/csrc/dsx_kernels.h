@@ -107,6 +107,13 @@ struct GnFinArgs {
   float* shift;
   PrefetchArgs pf;       // weight slices of the conv this GroupNorm feeds (see l2_prefetch)
 };
+// The launch rule of a finalize launch of its own: k_gn_finalize_wide (four waves per item) when a group has more than 512
+// (channel, partial row) pairs (an upper bound: the longer source's rows for every channel), else k_gn_finalize.  One
+// statement for launch_gn_finalize and for DSX_PLAN_DUMP, which names the launcher by it.
+inline bool gn_finalize_is_wide(const GnFinArgs& a) {
+  const int cpg = (a.C0 + a.C1) / a.groups;
+  return (long long)cpg * (a.nchunk0 > a.nchunk1 ? a.nchunk0 : a.nchunk1) > 512;
+}
 #if defined(__HIPCC__)
 // One (image, group) item of the GroupNorm finalize, by one wave (or NW waves): threads stride over (channel-in-group,
 // chunk) partials, fixed assignment + fixed butterfly order -> bitwise reproducible.  Used by k_gn_finalize (one wave per
@@ -175,7 +182,9 @@ __device__ __forceinline__ void gn_finalize_item(const GnFinArgs& a, const int b
     a.scale[(size_t)b * C + c_own] = sc;
     a.shift[(size_t)b * C + c_own] = b_own - meanf * sc;
   }
-  for (int c = c_lo + tid + NT; c < c_lo + cpg; c += NT) {   // groups wider than the workgroup (not in the reference configs)
+  // groups wider than the workgroup (norm_groups 1 .. 3 on wide levels and concats: tests/test_gpu_groups.py runs this
+  // loop in k_gn_finalize at 65 .. 512 channels per group, in k_gn_finalize_wide above 256 and in the hosted finalize)
+  for (int c = c_lo + tid + NT; c < c_lo + cpg; c += NT) {
     const float sc = rstd * a.gamma[c];
     a.scale[(size_t)b * C + c] = sc;
     a.shift[(size_t)b * C + c] = a.beta[c] - meanf * sc;

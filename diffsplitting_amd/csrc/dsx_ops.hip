@@ -110,9 +110,7 @@ __global__ __launch_bounds__(256) void k_gn_finalize_wide(const GnFinArgs a) {
 }
 
 hipError_t launch_gn_finalize(const GnFinArgs& a, hipStream_t st) {
-  const int cpg = (a.C0 + a.C1) / a.groups;
-  const long long items = (long long)cpg * std::max(a.nchunk0, a.nchunk1);   // partial rows x channels per group (upper bound)
-  if (items > 512)
+  if (gn_finalize_is_wide(a))
     hipLaunchKernelGGL(k_gn_finalize_wide, dim3((unsigned)a.B, (unsigned)a.groups), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(k_gn_finalize, dim3((unsigned)a.B, (unsigned)a.groups), dim3(64), 0, st, a);

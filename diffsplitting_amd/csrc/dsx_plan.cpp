@@ -83,8 +83,10 @@ static int dump_plan(const dsx_exec* ex) {
   if (!f) return fail(DSX_ERR_INVALID, "DSX_PLAN_DUMP: cannot write %s", ex->knobs.plan_dump.c_str());
   for (size_t i = 0; i < ex->ops.size(); ++i) {
     const PlanOp& o = ex->ops[i];
+    // (a finalize launch is named by the kernel its launch rule picks: gn_finalize or gn_finalize_wide)
+    const char* name = (o.launcher == L_GN_FINALIZE && gn_finalize_is_wide(o.args.fin)) ? "gn_finalize_wide" : L[o.launcher].name;
     fprintf(f, "%zu kind=%d desc=\"%s\" flops=%.17g bytes=%.17g launcher=%s dtype=%d tile=%d ks=%d stride=%d col_split=%d args=",
-            i, o.kind, o.desc.c_str(), o.flops, o.bytes, L[o.launcher].name, o.dtype, o.tile, o.ks, o.stride, o.col_split);
+            i, o.kind, o.desc.c_str(), o.flops, o.bytes, name, o.dtype, o.tile, o.ks, o.stride, o.col_split);
     const unsigned char* p = (const unsigned char*)&o.args;
     for (size_t b = 0; b < L[o.launcher].bytes; ++b) fprintf(f, "%02x", p[b]);
     fputc('\n', f);

@@ -58,6 +58,27 @@ WIDTH_CASES = {
                          channel_mults=(1, 2), attn_res=(), res_blocks=1, image_size=32)),
 }
 
+# GroupNorm groups wider than 64 channels (tests/test_gpu_groups.py): norm_groups 1, 2 and 3.  Every model above has at
+# most 40 channels per group; here a group has up to 512 (g1), straddles the two sources of a concat with more than 64
+# channels on either side (g2: 256 + 128 channels in groups of 192) or is wide and no power of two (g3: 72, 96, 144).
+# Weights as for WIDTH_CASES: synthesised for the engine's own parameter names, the reference is the fp64 oracle.
+GROUP_CASES = {
+    # one group: 32 .. 256 channels per group on single sources, 64 .. 512 on concats; the 8 x 8 level has 256 and more
+    "g1": dict(flavour="ddpm", B=3, H=32, W=32,
+               cfg=dict(in_channel=2, out_channel=2, inner_channel=32, norm_groups=1,
+                        channel_mults=(1, 2, 4, 8), attn_res=(), res_blocks=1, image_size=32)),
+    # two groups: 32 / 64 / 128 per group, concats of 256 + 128 and 128 + 64 channels whose first group ends inside
+    # source 0 and whose second group begins there; maps large enough for k_conv_ws and its hosted finalize
+    "g2": dict(flavour="sr3", B=2, H=64, W=64,
+               cfg=dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=2,
+                        channel_mults=(1, 2, 4), attn_res=(16,), res_blocks=1, image_size=64)),
+    # three groups at widths 24, 72, 144: 8 / 24 / 48 per group on the sources, 72 and 96 on the concats (stage mode 2
+    # in the 16-bit builds: 24- and 72-channel rows are no whole 16-byte units)
+    "g3": dict(flavour="ddpm", B=3, H=32, W=32,
+               cfg=dict(in_channel=1, out_channel=1, inner_channel=24, norm_groups=3,
+                        channel_mults=(1, 3, 6), attn_res=(), res_blocks=1, image_size=32)),
+}
+
 # Map shapes off the 8 x 8 tile grid (tests/test_gpu_shapes.py): three-level models the suite already has weights for
 # (golden state dicts of ddpm_tiny and sr3_tiny; w20 synthesised as in tests/test_gpu_widths.py: stage mode 2), at sizes
 # whose level maps are 2 or 4 pixels wide (64x24, 128x24), 12 or 6 wide (64x48, 48x32), and taller than wide or wider

@@ -1,8 +1,9 @@
 """One UNet forward with every conv, attention, GroupNorm-statistics, FiLM and input-staging launch checked against a
 float64 reference of that one layer (tests/layer_ref.py: the references and their bounds), computed from the tensors
 the launch actually read (the executor's layer table: the workspace is never reused, so after a forward every
-intermediate is still there).  Shared by tests/test_gpu_layers.py (the golden models) and tests/test_gpu_widths.py
-(models at other channel widths): the caller names the case and brings the state dict."""
+intermediate is still there).  Shared by tests/test_gpu_layers.py (the golden models), tests/test_gpu_widths.py
+(models at other channel widths) and tests/test_gpu_groups.py (GroupNorm groups wider than 64 channels): the caller
+names the case and brings the state dict."""
 import math
 import re
 
@@ -109,6 +110,67 @@ def reach_tags(L, dt, groups):
     return out
 
 
+def finalizes(ops, groups):
+    """The GroupNorm finalizes of a plan, from its launches (tests/plan_dump.py read_dump of a DSX_PLAN_DUMP file):
+    [dict(host, cpg, C0, C1, nchunk0, nchunk1, f32, shifted, consumer)], `host` the kernel that runs gn_finalize_item --
+    "gn_finalize" / "gn_finalize_wide" for a launch of its own (the dump names the launcher by the launch rule), "hosted"
+    for the finalize that the residual 1 x 1 k_conv_ws launch in front of the consumer runs (a `+gn` launch; that
+    GroupNorm has one source, the block's first conv, whose epilogue left fp32 partials: plan_res hosts nothing else).
+    `f32` / `shifted`: a source's partials are fp32 / carry a pivot.  `consumer`: the conv launch that reads the scale
+    and shift.  The layer table does not say which kernel finalized a GroupNorm; the dump does."""
+    from tests.plan_dump import FIN_LAUNCHERS
+    out = []
+    for i, op in enumerate(ops):
+        c = op["conv"]
+        if op["launcher"] in FIN_LAUNCHERS:
+            f = op["fin"]
+            assert f.groups == groups and ops[i + 1]["conv"] is not None and ops[i + 1]["conv"].has_gn, op["desc"]
+            out.append(dict(host=op["launcher"], cpg=(f.C0 + f.C1) // groups, C0=f.C0, C1=f.C1, nchunk0=f.nchunk0,
+                            nchunk1=f.nchunk1, f32=bool(f.f32_0 or (f.C1 and f.f32_1)),
+                            shifted=any(p.bias or p.film for p in (f.piv0, f.piv1)), consumer=ops[i + 1]))
+        elif c is not None and c.has_gn and op["launcher"] in ("conv_mfma", "conv_ws"):
+            prev = ops[i - 1]
+            if prev["launcher"] in FIN_LAUNCHERS:
+                continue
+            # no finalize launch in front (split-K: the main launch is in front of its reduce, which is not a conv)
+            assert prev["launcher"] == "conv_ws" and prev["desc"].endswith(" +gn") and prev["ks"] == 1, \
+                (prev["desc"], op["desc"])
+            assert c.C1 == 0, op["desc"]
+            out.append(dict(host="hosted", cpg=c.C0 // groups, C0=c.C0, C1=0, nchunk0=None, nchunk1=0, f32=True,
+                            shifted=None, consumer=op))
+    return out
+
+
+def group_reach_tags(ops, groups):
+    """the reach conditions of tests/test_gpu_groups.py that the launches `ops` of one plan meet: GroupNorm groups wider
+    than 64 channels in each of the three hosts of gn_finalize_item, and the 8 x 8 convs k_conv_img turns away"""
+    out = set()
+    for f in finalizes(ops, groups):
+        cpg = f["cpg"]
+        if cpg <= 64:
+            continue
+        if f["host"] == "gn_finalize":
+            out.add("fin>64")                  # one wave: the tail loop of gn_finalize_item
+        elif f["host"] == "gn_finalize_wide":
+            out.add("wide own>64" if cpg <= 256 else "wide>256")      # waves 1 .. 3 own channels / the tail loop
+        else:
+            out.add("hosted>64")
+        if f["C1"] and f["C0"] % cpg:
+            out.add("straddle>64")
+        if f["f32"]:
+            out.add("f32part>64")
+        if f["shifted"]:                       # (a launch of its own whose fp32 partials carry a pivot)
+            out.add("shifted>64")
+        if cpg & (cpg - 1):
+            out.add("npow2>64")
+    for op in ops:
+        c = op["conv"]
+        if (c is not None and c.has_gn and op["launcher"] != "conv_img"
+                and (c.Hs, c.Ws, c.Ho, c.Wo) == (8, 8, 8, 8)):
+            out.add("8x8 no img")
+    return out
+
+
 def pow2_divisor(v, cap):
     """largest power of two that divides v and is <= cap (dsx_plan.cpp)"""
     p = 1
@@ -194,7 +256,8 @@ def check_plan(plan, case, sd, dt, B, H, W, env, x, t, dev, monkeypatch, flat=Fa
     the planner knobs `env`, runs one forward of (x, t) and checks every layer.  Asserts that no check failed and that
     no launch carries a tag outside KNOWN_TAGS; returns dict(dtype, tags, layers, worst, table, y): `table` the plain
     fields of every layer (LAYER_FIELDS, plus whether it has a residual / FiLM vector / finalized GroupNorm), `y` the
-    forward's output."""
+    forward's output.  A conv entry of `table` with a finalized GroupNorm also has `gn_ratio`, the largest |mean| / std
+    of its groups (None elsewhere)."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     groups = case["cfg"]["norm_groups"]
@@ -206,6 +269,7 @@ def check_plan(plan, case, sd, dt, B, H, W, env, x, t, dev, monkeypatch, flat=Fa
     images = [0, B - 1] if B >= 4 else None
     fails, tags, worst, n = [], set(), (0.0, ""), 0
     max_gn_ratio = 0.0
+    gn_ratio = {}                                      # layer index -> largest |mean| / std of a group
     film_h, film_e, sd64 = film_reference(sd, case, t, B)
     film_h, film_e = film_h.to(dev), film_e.to(dev)
 
@@ -216,7 +280,7 @@ def check_plan(plan, case, sd, dt, B, H, W, env, x, t, dev, monkeypatch, flat=Fa
         if not v.ok:
             fails.append(v.message())
 
-    for L in table:
+    for li, L in enumerate(table):
         kind = L["kind"]
         if kind == 3:                                  # staged input: bit-equal to round_T(x) in NHWC
             ref = x[:, L["C0"]:L["C0"] + L["Cout"]].permute(0, 2, 3, 1).to(dev).to(L["out"].dtype)
@@ -243,6 +307,7 @@ def check_plan(plan, case, sd, dt, B, H, W, env, x, t, dev, monkeypatch, flat=Fa
         if L["gn_scale"] is not None:
             v1, v2, r = layer_ref.check_gn_stats(L, gamma, beta, groups, op, where)
             max_gn_ratio = max(max_gn_ratio, r)
+            gn_ratio[li] = r
             note(v1, where + " gn_scale")
             note(v2, where + " gn_shift")
         if L["film"] is not None:
@@ -267,8 +332,9 @@ def check_plan(plan, case, sd, dt, B, H, W, env, x, t, dev, monkeypatch, flat=Fa
     unknown = tags - KNOWN_TAGS
     assert not unknown, f"launch variants without per-layer coverage: {unknown}"
     light = []
-    for L in table:
+    for li, L in enumerate(table):
         d = {k: L[k] for k in LAYER_FIELDS}
+        d["gn_ratio"] = gn_ratio.get(li)
         for k in ("resid", "film", "gn_scale"):          # (only a conv's entries hold tensors under these names)
             d[k] = L["kind"] == 0 and L[k] is not None
         light.append(d)

@@ -199,6 +199,48 @@ def test_gn_stats_checker_accepts_exact_and_rejects_a_missing_tile():
     assert not (v1.ok and v2.ok)
 
 
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_gn_stats_checker_at_192_channels_per_group_over_a_concat(dt):
+    """tests/test_gpu_groups.py: 256 + 128 channels in two groups of 192 -- group 0 ends inside source 0, group 1 takes
+    its last 64 channels and source 1.  A kernel-like result (fp32 partial rows of 64 pixels per channel, summed in
+    double as gn_finalize_item does, scale and shift in fp32) passes; a scale / shift that is right in the first 64
+    channels of each group and wrong behind them -- what a finalize that loses the channels past its first wave leaves --
+    fails, whether those channels were never written, their scale is off by 1e-4 (f32) / 1e-2 (bf16: the bound carries
+    u_T = 2^-8) of itself, or their shift by 1e-4 / 2e-2."""
+    g = torch.Generator().manual_seed(192)
+    B, H, W, C0, C1, groups = 2, 16, 16, 256, 128, 2
+    C, cpg = C0 + C1, (C0 + C1) // groups
+    x = torch.randn((B, H, W, C), generator=g) * 0.7 + 1.5 * torch.randn((1, 1, 1, C), generator=g)
+    x = op_round(x, dt)
+    gamma, beta = 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    rows = x.reshape(B, H * W // 64, 64, C)                                  # one partial row per 64 pixels
+    s = rows.sum(2, dtype=torch.float32).double().sum(1)                     # [B][C]
+    q = (rows * rows).sum(2, dtype=torch.float32).double().sum(1)
+    n = float(H * W * cpg)
+    mean = s.reshape(B, groups, cpg).sum(-1) / n
+    var = (q.reshape(B, groups, cpg).sum(-1) / n - mean * mean).clamp(min=0)
+    rstd = (1.0 / torch.sqrt(var + 1e-5)).float().repeat_interleave(cpg, 1)
+    sc = rstd * gamma
+    sh = beta - mean.float().repeat_interleave(cpg, 1) * sc
+    layer = dict(x0=x[..., :C0].to(DT[dt]), x1=x[..., C0:].to(DT[dt]), gn_scale=sc, gn_shift=sh)
+    v1, v2, _ = layer_ref.check_gn_stats(layer, gamma, beta, groups, DT[dt])
+    assert v1.ok and v2.ok, (v1.message(), v2.message())
+    behind = (torch.arange(C) % cpg) >= 64                                   # channels 64 .. 191 of each group
+    for bad_sc, bad_sh in ((torch.where(behind, torch.zeros(()), sc), torch.where(behind, torch.zeros(()), sh)),
+                           (torch.where(behind, sc * (1 + (1e-4 if dt == "f32" else 1e-2)), sc), sh),
+                           (sc, torch.where(behind, sh + (1e-4 if dt == "f32" else 2e-2), sh))):
+        layer.update(gn_scale=bad_sc, gn_shift=bad_sh)
+        v1, v2, _ = layer_ref.check_gn_stats(layer, gamma, beta, groups, DT[dt])
+        assert not (v1.ok and v2.ok)
+        for v in (v1, v2):
+            if not v.ok:
+                assert v.index[1] % cpg >= 64, v.message()                  # and it names a channel behind the 64th
+    # the same corruption in the first 64 channels only is seen there: the check is per channel
+    layer.update(gn_scale=torch.where(behind, sc, torch.zeros(())), gn_shift=sh)
+    v1, _, _ = layer_ref.check_gn_stats(layer, gamma, beta, groups, DT[dt])
+    assert not v1.ok and v1.index[1] % cpg < 64
+
+
 def test_reach_tags_of_the_widths_module():
     """tests/test_gpu_widths.py derives its reach conditions from plain layer-table fields (layer_check.reach_tags):
     hand-made entries, one per condition, and their nearest neighbours that must not count"""
