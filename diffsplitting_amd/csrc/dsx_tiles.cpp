@@ -549,21 +549,31 @@ extern "C" int dsx_tileplan_gather_input(dsx_tileplan* p, const void* frames, in
   return DSX_OK;
 }
 
-// frame-keyed noise of the sequence's tiles: the crops of the noise field (seed, id_base + frame, draw)
-extern "C" int dsx_tileplan_randn(dsx_tileplan* p, int C, int64_t first, int64_t stride, int64_t count, uint64_t seed,
-                                  uint64_t id_base, uint32_t draw, float* out_dev, void* stream) {
-  const char* what = "tileplan_randn";
-  if (!p) return fail(DSX_ERR_INVALID, "%s: null argument", what);
-  if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
+// what every call that names noise fields refuses alike: the field ids of the plan's frames and the draw ordinal
+static int field_ids_ok(const char* what, const dsx_tileplan* p, uint64_t id_base, uint32_t draw) {
   const uint64_t frames = (uint64_t)p->t.D[0];
   if (id_base >= DSX_STREAM_ID_LIMIT || id_base + (frames - 1) >= DSX_STREAM_ID_LIMIT)
     return fail(DSX_ERR_INVALID, "%s: id_base = %llu with %llu frames: every field id must be below 2^40", what,
                 (unsigned long long)id_base, (unsigned long long)frames);
   if (draw >= DSX_STREAM_DRAW_LIMIT)
     return fail(DSX_ERR_INVALID, "%s: draw ordinal %u, must be below 2^24", what, (unsigned)draw);
-  if ((int64_t)C > INT32_MAX / (p->t.p[1] * p->t.p[2]))
-    return fail(DSX_ERR_INVALID, "%s: C * patch = %d * %lld x %lld exceeds 32 bits", what, C, (long long)p->t.p[1],
-                (long long)p->t.p[2]);
+  return DSX_OK;
+}
+// a (C, ph, pw) tile is indexed with 32 bits
+static int tile_elems_ok(const char* what, const dsx_tileplan* p, int C) {
+  const long long ph = p->t.p[1], pw = p->t.p[2];
+  if ((int64_t)C <= INT32_MAX / (ph * pw)) return DSX_OK;
+  return fail(DSX_ERR_INVALID, "%s: C * patch = %d * %lld x %lld exceeds 32 bits", what, C, ph, pw);
+}
+
+// frame-keyed noise of the sequence's tiles: the crops of the noise field (seed, id_base + frame, draw)
+extern "C" int dsx_tileplan_randn(dsx_tileplan* p, int C, int64_t first, int64_t stride, int64_t count, uint64_t seed,
+                                  uint64_t id_base, uint32_t draw, float* out_dev, void* stream) {
+  const char* what = "tileplan_randn";
+  if (!p) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
+  if (const int rc = field_ids_ok(what, p, id_base, draw)) return rc;
+  if (const int rc = tile_elems_ok(what, p, C)) return rc;
   if (!out_dev && count != 0) return fail(DSX_ERR_INVALID, "%s: null argument", what);
   TileGeom g;
   const int rc = geom_of_plan(what, p, first, stride, count, g);
@@ -665,12 +675,9 @@ static int blend_checks(const char* what, const dsx_tileplan* p, const float* ti
   if (p->window.empty()) return fail(DSX_ERR_INVALID, "%s: the plan has no window: call dsx_tileplan_set_window first", what);
   if (p->t.D[0] > 65535) return fail(DSX_ERR_INVALID, "%s: %lld frames, at most 65535 per plan", what, (long long)p->t.D[0]);
   if (p->total > INT32_MAX) return fail(DSX_ERR_INVALID, "%s: %lld tiles, the tile id must fit 31 bits", what, (long long)p->total);
-  const int64_t tile_elems = p->t.p[1] * p->t.p[2];
-  if ((int64_t)C > INT32_MAX / tile_elems)
-    return fail(DSX_ERR_INVALID, "%s: C * patch = %d * %lld x %lld exceeds 32 bits", what, C, (long long)p->t.p[1],
-                (long long)p->t.p[2]);
+  if (const int rc = tile_elems_ok(what, p, C)) return rc;
   const int64_t most = (p->total + world - 1) / world;       // tiles of rank 0, the longest slot
-  if (world > 1 && (rank_stride_elems < 0 || most > rank_stride_elems / (tile_elems * C)))
+  if (world > 1 && (rank_stride_elems < 0 || most > rank_stride_elems / (p->t.p[1] * p->t.p[2] * C)))
     return fail(DSX_ERR_INVALID, "%s: rank_stride_elems = %lld is smaller than rank 0's %lld whole tiles", what,
                 (long long)rank_stride_elems, (long long)most);
   return DSX_OK;
@@ -707,14 +714,8 @@ extern "C" int dsx_tileplan_blend_step(dsx_tileplan* p, const float* x0_tiles_de
                                        int64_t rank_stride_elems, float* state_dev, float c_x0, float c_xt, float sigma,
                                        uint64_t seed, uint64_t id_base, uint32_t draw, void* stream) {
   const char* what = "tileplan_blend_step";
-  const int rc = blend_checks(what, p, x0_tiles_dev, C, world, rank_stride_elems, state_dev, nullptr, nullptr);
-  if (rc) return rc;
-  const uint64_t frames = (uint64_t)p->t.D[0];
-  if (id_base >= DSX_STREAM_ID_LIMIT || id_base + (frames - 1) >= DSX_STREAM_ID_LIMIT)
-    return fail(DSX_ERR_INVALID, "%s: id_base = %llu with %llu frames: every field id must be below 2^40", what,
-                (unsigned long long)id_base, (unsigned long long)frames);
-  if (draw >= DSX_STREAM_DRAW_LIMIT)
-    return fail(DSX_ERR_INVALID, "%s: draw ordinal %u, must be below 2^24", what, (unsigned)draw);
+  if (const int rc = blend_checks(what, p, x0_tiles_dev, C, world, rank_stride_elems, state_dev, nullptr, nullptr)) return rc;
+  if (const int rc = field_ids_ok(what, p, id_base, draw)) return rc;
   if (!std::isfinite(c_x0) || !std::isfinite(c_xt) || !std::isfinite(sigma))
     return fail(DSX_ERR_INVALID, "%s: c_x0 = %g, c_xt = %g, sigma = %g: every coefficient must be finite", what,
                 (double)c_x0, (double)c_xt, (double)sigma);
@@ -730,9 +731,7 @@ extern "C" int dsx_tileplan_gather_canvas(dsx_tileplan* p, const float* canvas_d
   const char* what = "tileplan_gather_canvas";
   if (!p) return fail(DSX_ERR_INVALID, "%s: null argument", what);
   if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
-  if ((int64_t)C > INT32_MAX / (p->t.p[1] * p->t.p[2]))
-    return fail(DSX_ERR_INVALID, "%s: C * patch = %d * %lld x %lld exceeds 32 bits", what, C, (long long)p->t.p[1],
-                (long long)p->t.p[2]);
+  if (const int rc = tile_elems_ok(what, p, C)) return rc;
   if ((!canvas_dev || !tiles_dev) && count != 0) return fail(DSX_ERR_INVALID, "%s: null argument", what);
   TileGeom g;
   const int rc = geom_of_plan(what, p, first, stride, count, g);

@@ -81,6 +81,11 @@ class InputStackTiledPred:
     def get_normalization_dict(self):
         return dict(self._nd)
 
+    @property
+    def device(self):
+        """The device the stack is resident on."""
+        return self._dev.device
+
     def resident_bytes(self):
         """Device bytes the stack occupies (its file width: half of an fp32 copy for uint16, a quarter for uint8)."""
         return self._dev.numel() * self._dev.element_size()

@@ -265,6 +265,11 @@ class SplitDataset:
                 "std_target": self._std_target, "target0_max": self._target0_max, "target1_max": self._target1_max,
                 "input_max": self._input_max}
 
+    @property
+    def device(self):
+        """The one device both channels' frames are resident on."""
+        return self._dev[0].device
+
     def normalize_inp(self, inp):                                   # :195-197
         return ((inp - self._mean_inp) / self._std_inp).astype(np.float32)
 

@@ -1,0 +1,325 @@
+"""The per-tile drivers ``predict_tiled`` / ``predict_stack`` -- every tile runs its own chain, the stitch comes last -- and
+what every driver shares: ``TileExchange``, the batching of an id list (``_batches``, ``store_kept``), the refusals."""
+import torch
+
+from .. import parallel
+from .._lib import DsxError
+from .tiling import PSNR_MAX_CHANNELS, TilePlan
+
+
+class TileExchange:
+    """The stitched output of a sharded run.  One rank: every batch is pasted straight into the canvas.  Several ranks:
+    every batch's VALID REGIONS are packed into this rank's run of the exchange buffer (the crop of
+    tile_stitcher.py:38-56 before the collective), one all-gather of the equal-sized runs (RCCL over xGMI) moves
+    canvas bytes + padding instead of whole (C, p, p) tiles, and every rank pastes from the packed layout.
+
+    ``blend=True``: blended stitching (``TilePlan.blend``) under ``window``.  This rank's WHOLE predicted tiles stay in a
+    resident buffer -- its slot of the exchange buffer, tile ``id`` at index ``id // world`` --, ``add`` copies a batch
+    in, and ``finish`` is one all-gather of the equal-sized slots (several ranks) and one blend of all tiles."""
+
+    def __init__(self, plan, channels, device, group=None, gt=None, blend=False, window="triangle"):
+        self.plan, self.C, self.group, self.gt = plan, int(channels), group, gt
+        self.rank, self.world = parallel.rank(), parallel.world_size()
+        self.canvas = self.part = self.flat = None
+        self.blend = bool(blend)
+        if self.blend:
+            plan.set_window(window)
+            self.flat = torch.zeros(plan.blend_rank_stride(self.world, self.C), dtype=torch.float32, device=device)
+            self.tiles = self.flat.view((-1, self.C) + plan.patch_shape[1:])
+        elif self.world == 1:
+            self.canvas = torch.zeros(plan.data_shape + (self.C,), dtype=torch.float32, device=device)
+            if gt is not None:
+                self.part = plan.new_psnr_partials(self.C, device)
+        else:
+            self.flat = torch.zeros(plan.rank_stride(self.world, self.C), dtype=torch.float32, device=device)
+
+    def add(self, tiles, ids):
+        """``tiles`` (b, C, p, p): predictions of this rank's tile ids ``ids`` (a batch of its shard, in order)."""
+        if len(ids) == 0:
+            return
+        if self.blend:
+            j = int(ids[0]) // self.world
+            self.tiles[j:j + len(ids)].copy_(tiles)
+        elif self.world == 1:
+            if self.gt is not None:
+                self.plan.stitch_psnr_into(tiles, ids, self.canvas, self.gt, self.part)
+            else:
+                self.plan.stitch(tiles, ids, self.canvas)
+        else:
+            self.plan.pack(tiles, self.world, ids[0], self.flat)
+
+    def gathered_bytes(self):
+        """Bytes every rank receives from the collective (world * rank_stride * 4)."""
+        return 0 if self.world == 1 else self.world * self.flat.numel() * 4
+
+    def finish(self):
+        """-> canvas (N,H,W,C), or (canvas, psnr (N,C)) when a ground truth was given."""
+        if self.blend:
+            if self.world == 1:
+                return self.plan.blend(self.tiles, gt=self.gt)
+            full = parallel.all_gather_flat(self.flat, self.group)   # one collective per canvas, of whole tiles
+            return self.plan.blend(full, world=self.world, gt=self.gt, Cn=self.C)
+        if self.world == 1:
+            return self.canvas if self.gt is None else (self.canvas, self.plan.psnr_from_partials(self.part))
+        full = parallel.all_gather_flat(self.flat, self.group)       # the path's only collective
+        return self.plan.paste_packed(full, self.C, self.world, self.gt)
+
+
+def _batches(ids, batch):
+    """Batches of ``batch`` consecutive entries of the arithmetic id list ``ids``; the last short batch is moved back
+    to end at the last id (still arithmetic, same batch size: no second executor) -> (chunk, entries to keep)."""
+    batch = max(1, min(int(batch), len(ids)))
+    for i in range(0, len(ids), batch):
+        if i + batch <= len(ids):
+            yield ids[i:i + batch], batch
+        else:
+            yield ids[len(ids) - batch:], len(ids) - i
+
+
+def store_kept(buf, out, chunk, keep, world=1):
+    """The last ``keep`` entries of ``out``, the output of a batch ``(chunk, keep)`` of ``_batches`` -- the ones before them
+    belong to the batch it was moved back over --, into the resident buffer ``buf`` at local index ``id // world``."""
+    last = chunk[-1] // world + 1
+    buf[last - keep:last] = out[len(chunk) - keep:]
+
+
+# ---- refusals that several drivers share, each worded once: ``what`` names the caller, ``error`` is its exception class
+def _check_stitch(what, stitch, window):
+    from .tiling import WINDOWS
+    if stitch not in ("crop", "blend"):
+        raise DsxError(f"{what}: stitch = {stitch!r}: 'crop' or 'blend'")
+    if stitch == "blend" and isinstance(window, str) and window not in WINDOWS:
+        raise DsxError(f"{what}: window = {window!r}: one of {', '.join(WINDOWS)}, or a pair of arrays (wy, wx)")
+
+
+def _check_samples(what, samples, error):
+    if int(samples) < 1:
+        raise error(f"{what}: samples = {int(samples)}: a positive count")
+    return int(samples)
+
+
+def _check_field_ids(what, samples, frames, limit=1 << 39):
+    if samples * frames > limit:
+        raise DsxError(f"{what}: samples * frames exceeds the 2^39 field ids of one sampler")
+
+
+def _check_solver(what, netG, solver):
+    if solver and not _is_gaussian(netG):                             # what = None: sample_tiles never named itself
+        raise DsxError(f"{what + ': ' if what else ''}solver: {type(netG).__name__} is not a Gaussian sampler (sr3 / ddpm); "
+                       "InDI's loop already takes num_timesteps")
+
+
+def _is_gaussian(netG):
+    from ..model.samplers import GaussianSampler
+    return isinstance(netG, GaussianSampler)
+
+
+def _scorable_gt(dataset, C_out):
+    """The normalised ground truth (N,H,W,C) a stitched prediction of ``C_out`` channels is scored against (every rank
+    holds the frames: no collective), or None: the dataset has none, other channels, or more than the PSNR sums take."""
+    gt = dataset.normalized_target_frames() if hasattr(dataset, "normalized_target_frames") else None
+    return gt if gt is not None and gt.shape[-1] == C_out and C_out <= PSNR_MAX_CHANNELS else None
+
+
+def _mean_and_spread(samples, return_std, draw):
+    """``draw(r)`` for r = 0 .. samples - 1 -> (mean, unbiased spread or None without ``return_std``): one fused
+    ``engine.moments_update`` launch per sample and one ``moments_finish``.  One sample: the draw itself, spread 0."""
+    from .. import engine
+    mean = m2 = x = None
+    for r in range(samples):
+        x = draw(r)
+        if samples > 1:
+            mean, m2 = engine.moments_update(x.contiguous(), mean, m2, r)
+    if samples > 1:
+        return engine.moments_finish(mean, m2, samples, want_std=return_std)
+    return x, (torch.zeros_like(x) if return_std else None)
+
+
+@torch.no_grad()
+def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8, sampler_kwargs=None,
+                  group=None, lpips=None, target_frames=None, seed=None, stitch="crop", window="triangle"):
+    """``frames_input``: (N,H,W) fp32 CUDA tensor, already normalised (the network input channel).
+    Returns the stitched prediction (N,H,W,C) on every rank and the ``TilePlan``.
+
+    ``lpips``: a ``core.lpips.LPIPS``; with it (and ``target_frames`` (N,H,W,C), the ground truth of the prediction
+    channels) the first element is ``(canvas, lpips_dict)``, ``lpips_dict`` = ``core.metrics.calculate_lpips(
+    target_frames, canvas, lpips)``: per channel the LPIPS of every frame, computed on the device.
+
+    ``netG`` is what ``define_G`` returns (InDI / JointIndi sampler); its full-batch
+    output (``last_full_batch``) is used, not the single element the reference API returns.
+
+    ``seed``: per-sample noise streams (include/dsx.h) with a tile's id as its sample id: a tile's noise then does not
+    depend on ``batch_tiles``, on the order of the batches or on the number of ranks, and neither does its prediction
+    as long as the batch size is the same (the planner may pick other kernels for another).
+
+    ``stitch``: ``"crop"`` pastes every tile's inner region (the reference's stitch); ``"blend"`` overlap-adds the whole
+    tiles under the separable ``window`` (``TilePlan.blend``)."""
+    _check_stitch("predict_tiled", stitch, window)
+    if grid_size is None:
+        grid_size = patch_size // 2                                   # split_dataset_tiledpred.py:13-14
+    N, H, W = frames_input.shape
+    plan = TilePlan((N, H, W), (1, grid_size, grid_size), (1, patch_size, patch_size))
+    rank, world = parallel.rank(), parallel.world_size()
+    ids = parallel.shard_ids(plan.total, rank, world)
+    kw = dict(sampler_kwargs or {})
+    ex = TileExchange(plan, netG.prediction_channels, frames_input.device, group, blend=stitch == "blend", window=window)
+    for i in range(0, len(ids), batch_tiles):
+        chunk = ids[i:i + batch_tiles]
+        tiles = plan.gather(frames_input, chunk).unsqueeze(1)         # (b,1,p,p)
+        if seed is not None:
+            kw.update(seed=seed, sample_ids=chunk)
+        netG.inference(tiles, continuous=False, **kw)
+        ex.add(netG.last_full_batch, chunk)
+    canvas = ex.finish()
+    if lpips is None:
+        return canvas, plan
+    if target_frames is None:
+        raise ValueError("predict_tiled(lpips=...) needs target_frames (N,H,W,C) to compare the prediction with")
+    from ..core.metrics import calculate_lpips
+    return (canvas, calculate_lpips(target_frames, canvas, lpips)), plan
+
+
+@torch.no_grad()
+def sample_tiles(netG, x, num_timesteps=None, solver=None, **noise):
+    """One batch of input tiles ``x`` (b, 1, p, p) through whatever sampler ``define_G`` returned -> its full-batch
+    prediction (b, C, p, p).  InDI family: ``inference`` (``num_timesteps`` steps).  A ``GaussianSampler`` (sr3 / ddpm):
+    ``solver_sample_loop(x, **solver)`` with a solver -- the dict ``DDPM.set_solver`` keeps -- else ``super_resolution``,
+    the full ancestral loop.  ``noise``: ``seed`` / ``sample_ids`` of the per-sample streams, or nothing."""
+    _check_solver(None, netG, solver)
+    if not _is_gaussian(netG):
+        netG.inference(x, continuous=False, **({} if num_timesteps is None else dict(num_timesteps=num_timesteps)),
+                       **noise)
+    elif solver:
+        netG.solver_sample_loop(x, **solver, **noise)
+    else:
+        netG.super_resolution(x, **noise)
+    return netG.last_full_batch
+
+
+def _stochastic_rows(netG, num_timesteps, solver):
+    """(rows, C): how many rows of one batch's loop add noise -- each is one materialised (B, C, p, p) draw under
+    noise='field' -- and the channels C of the sampler's state."""
+    if _is_gaussian(netG):
+        if solver:
+            sigma = netG.solver_table(**solver).sigma
+            return sum(1 for s in range(len(sigma)) if sigma[s] != 0), int(netG.channels)
+        netG._need_schedule()
+        return (netG.num_timesteps - 1 if netG.kind == "sr3" else netG.num_timesteps), int(netG.channels)
+    children = [netG.indi1, netG.indi2] if hasattr(netG, "indi1") else [netG]
+    rows = sum(int(num_timesteps if num_timesteps is not None else c.num_timesteps) for c in children)
+    return rows, int(children[0].out_channel)
+
+
+@torch.no_grad()
+def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None,
+                  solver=None, noise="samples", field_noise_bytes=2 << 30, stitch=None, window="triangle", fuse=False):
+    """The tiled prediction of a dataset that cuts its own normalised tiles -- an ``InputStackTiledPred`` (one
+    superimposed acquisition, no ground truth) or a ``SplitDatasetTiledPred`` -- with ``samples`` posterior samples per
+    tile: their mean and, with ``return_std``, the unbiased per-pixel spread, accumulated by one fused launch per sample
+    (``engine.moments_update``, Welford in double) and one to finish.  ``samples == 1``: the prediction itself, spread 0.
+
+    Returns ``(out, plan)``, ``out = {'mean': (N,H,W,C)}`` plus ``'std'`` (N,H,W,C) with ``return_std`` and, for a
+    ``SplitDatasetTiledPred`` whose target has the prediction's channels, ``'psnr'`` (N,C): the RangeInvariantPsnr of the
+    mean against the normalised ground truth, accumulated while pasting.  Everything in normalised units, on every rank.
+
+    ``seed``: per-sample noise streams; sample ``r`` of tile ``k`` draws from sample id ``k + r * plan.total`` (the rule
+    of ``predict_tiled_mixed``), whatever batch or rank it runs in.  Tiles are sharded over the ranks and exchanged
+    through ``TileExchange``: one collective per output canvas.
+
+    ``solver``: the dict ``DDPM.set_solver`` keeps (``solver``, ``steps``, ``eta``, ``spacing``): a Gaussian sampler
+    (sr3 / ddpm) then runs that few-step solver per batch instead of its full ancestral loop; refused for any other.
+
+    ``noise="field"`` (needs ``seed``): every draw is cut from a noise field keyed by the FRAME position
+    (``TilePlan.randn_field``): a function of (seed, frame, draw ordinal, channel, y, x), so overlapping tiles start from
+    -- and, in a stochastic row, receive -- the same noise where they overlap; posterior sample ``r`` takes
+    ``id_base = r * frames``.  The draws travel in the loop's injected form, one (B, C, p, p) tensor per stochastic
+    row; more than ``field_noise_bytes`` of them per batch is refused.  ``noise="samples"``: the streams above.
+
+    ``stitch``: ``"crop"`` (the default) pastes every tile's inner region; ``"blend"`` overlap-adds the whole tiles under
+    the separable ``window`` (``TilePlan.blend``: "triangle", "hann" or a pair of arrays) -- 'mean', 'std' and 'psnr'
+    then each come from a blend.
+
+    ``fuse=True`` (a Gaussian sampler with ``solver``, ``noise="field"`` and ``seed``, one rank; ``stitch`` is then
+    "blend"): per-step frame fusion.  Every posterior sample diffuses each frame as ONE state (N,H,W,C), started from the
+    noise field's draw 0: for every solver row the tiles are cut out of the state (``TilePlan.gather_canvas``), go
+    through one UNet forward and one ``engine.solver_step`` per batch -- with the crops of the field's draw ``s + 1``
+    where the row adds noise and the tiles of the blended x0 of the row before where it has a history term --, and are
+    blended back into the state.  The state after the last row is the sample; with one tile per frame this is the
+    unfused chain bit for bit."""
+    samples = _check_samples("predict_stack", samples, ValueError)
+    plan = dataset.plan
+    _check_solver("predict_stack", netG, solver)
+    if noise not in ("samples", "field"):
+        raise DsxError(f"predict_stack: noise = {noise!r}: 'samples' or 'field'")
+    if fuse:
+        if stitch == "crop":
+            raise DsxError("predict_stack: fuse with stitch='crop': a fused frame is a blend of its tiles; leave stitch "
+                           "out or give 'blend'")
+        if not _is_gaussian(netG):
+            raise DsxError(f"predict_stack: fuse: {type(netG).__name__} is not a Gaussian sampler (sr3 / ddpm); frame "
+                           "diffusion for the InDI family is predict_stack_frames")
+        if not solver:
+            raise DsxError("predict_stack: fuse needs solver=: the rows of a few-step solver are fused; the ancestral "
+                           "loop is not")
+        if noise != "field" or seed is None:
+            raise DsxError("predict_stack: fuse needs noise='field' and seed=: overlapping tiles must receive the same "
+                           "noise, or the blend would shrink its variance")
+        if parallel.world_size() > 1:
+            raise DsxError("predict_stack: fuse runs on one rank: a collective after every solver row is not provided")
+        stitch = "blend"
+    stitch = "crop" if stitch is None else stitch
+    _check_stitch("predict_stack", stitch, window)
+    blend, field = stitch == "blend", noise == "field"
+    if fuse:
+        from .frame_predict import _predict_stack_fused
+        _check_field_ids("predict_stack", samples, plan.data_shape[0])
+        return _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window), plan
+    if field:
+        if seed is None:
+            raise DsxError("predict_stack: noise='field' needs seed=: a noise field is named by (seed, frame, draw)")
+        rows, C_state = _stochastic_rows(netG, num_timesteps, solver)
+        B = max(1, min(int(batch_tiles), plan.total))
+        need = rows * B * C_state * plan.patch_shape[1] * plan.patch_shape[2] * 4
+        if need > field_noise_bytes:
+            raise DsxError(f"predict_stack: noise='field' materialises one (B, C, p, p) draw per stochastic row: {rows} "
+                           f"rows x {B} tiles need {need} bytes, field_noise_bytes = {field_noise_bytes}; use a solver "
+                           "(ddim with eta = 0 and dpmpp2m draw once per batch), fewer rows, or a smaller batch")
+        _check_field_ids("predict_stack", samples, plan.data_shape[0], getattr(netG, "STREAM2_BIT", 1 << 39))
+    C_out = netG.prediction_channels
+    gt = _scorable_gt(dataset, C_out)
+    ids = parallel.shard_ids(plan.total, parallel.rank(), parallel.world_size())
+    # a rank without tiles still joins the collectives, on the device it is bound to
+    dev = dataset.device if len(ids) else torch.device("cuda", torch.cuda.current_device())
+    ex = TileExchange(plan, C_out, dev, group, gt=gt, blend=blend, window=window)
+    ex_std = TileExchange(plan, C_out, dev, group, blend=blend, window=window) if return_std else None
+    kept_field = getattr(netG, "noise_field", None)
+    try:
+        for i in range(0, len(ids), batch_tiles):
+            chunk = ids[i:i + batch_tiles]
+            x = dataset.tiles(chunk)["input"]
+
+            def sample(r):
+                kw = {}
+                if field:
+                    # (shape, draw[, id_bit]): the crops of this batch's tiles out of the fields of sample r; a joint
+                    # sampler's second child adds its bit to the field ids
+                    netG.noise_field = lambda shape, draw, id_bit=0: plan.randn_field(
+                        chunk, shape[1], seed, draw, id_base=r * plan.data_shape[0] + id_bit, device=x.device)
+                elif seed is not None:
+                    kw = dict(seed=seed, sample_ids=[k + r * plan.total for k in chunk])
+                return sample_tiles(netG, x, num_timesteps, solver, **kw)
+            tiles, spread = _mean_and_spread(samples, return_std, sample)
+            ex.add(tiles, chunk)
+            if return_std:
+                ex_std.add(spread, chunk)
+    finally:
+        if field:
+            netG.noise_field = kept_field
+            for child in (getattr(netG, "indi1", None), getattr(netG, "indi2", None)):
+                if child is not None:                                 # a joint sampler hands its field down per call
+                    child.noise_field = None
+    res = ex.finish()
+    out = {"mean": res[0], "psnr": res[1]} if gt is not None else {"mean": res}
+    if return_std:
+        out["std"] = ex_std.finish()
+    return out, plan

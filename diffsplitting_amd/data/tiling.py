@@ -31,6 +31,19 @@ def as_sequence(ids):
     return int(ids[0]), d, int(ids.size)
 
 
+def _per_sequence(ids, call, out):
+    """``call(first, stride, count, dst)`` over the id list ``ids``, rows of ``out`` in its order: an arithmetic sequence
+    in launches of at most 65535 tiles (a grid dimension), any other list one tile per launch.  -> ``out``"""
+    seq = as_sequence(ids)
+    if seq is not None:
+        for k0 in range(0, seq[2], 65535):
+            call(seq[0] + k0 * seq[1], seq[1], min(65535, seq[2] - k0), out[k0:])
+    else:
+        for k, i in enumerate(ids):
+            call(int(i), 1, 1, out[k:])
+    return out
+
+
 WINDOWS = ("triangle", "hann")
 
 
@@ -139,26 +152,25 @@ class TilePlan:
         their overlap.  An arithmetic id sequence takes one launch, any other list one launch per tile."""
         _lib.require_gpu()
         ids = self._ids(tile_ids)
-        Cn, draw, id_base = int(C_state), int(draw), int(id_base)
+        Cn = int(C_state)
         if Cn < 1:
             raise DsxError(f"randn_field: C = {Cn}, must be at least 1")
-        if not 0 <= draw < _lib.STREAM_DRAW_LIMIT:
-            raise DsxError(f"randn_field: draw ordinal {draw} out of range (0 <= draw < 2^24)")
-        if not 0 <= id_base <= _lib.STREAM_ID_LIMIT - self.data_shape[0]:
-            raise DsxError(f"randn_field: id_base = {id_base} with {self.data_shape[0]} frames: every field id must be "
-                           "below 2^40")
+        draw, id_base = self._field_draw("randn_field", draw, id_base)
         out = torch.empty((len(ids), Cn, self.patch_shape[1], self.patch_shape[2]), dtype=torch.float32, device=device)
         seed64 = C.c_uint64(int(seed) & (2 ** 64 - 1))
         call = lambda first, stride, count, dst: check(lib.dsx_tileplan_randn(
             self.handle, Cn, first, stride, count, seed64, C.c_uint64(id_base), C.c_uint32(draw), dst, None))
-        seq = as_sequence(ids)
-        if seq is not None:
-            for k0 in range(0, seq[2], 65535):
-                call(seq[0] + k0 * seq[1], seq[1], min(65535, seq[2] - k0), out[k0:])
-        else:
-            for k, i in enumerate(ids):
-                call(int(i), 1, 1, out[k:])
-        return out
+        return _per_sequence(ids, call, out)
+
+    def _field_draw(self, what, draw, id_base):
+        """-> (draw, id_base) as ints, both in the range of the noise fields of this plan's frames."""
+        draw, id_base = int(draw), int(id_base)
+        if not 0 <= draw < _lib.STREAM_DRAW_LIMIT:
+            raise DsxError(f"{what}: draw ordinal {draw} out of range (0 <= draw < 2^24)")
+        if not 0 <= id_base <= _lib.STREAM_ID_LIMIT - self.data_shape[0]:
+            raise DsxError(f"{what}: id_base = {id_base} with {self.data_shape[0]} frames: every field id must be "
+                           "below 2^40")
+        return draw, id_base
 
     def _check_tiles(self, tiles):
         if not tiles.is_cuda or tiles.dtype != torch.float32 or tiles.dim() != 4:
@@ -317,6 +329,23 @@ class TilePlan:
         """Elements of one rank's slot of WHOLE tiles in the exchange buffer of a blend: rank 0's, the longest."""
         return -(-self.total // int(world)) * int(Cn) * self.patch_shape[1] * self.patch_shape[2]
 
+    def _whole_tiles(self, what, tiles, world, Cn):
+        """Every tile of the plan as ``blend`` and ``blend_step`` take them -> (tiles, Cn, slot stride).  One rank:
+        a (total, C, ph, pw) tensor, stride 0.  Several: the gathered exchange buffer of ``world`` equal slots of at
+        least ``blend_rank_stride`` elements, with its channel count ``Cn``."""
+        if world == 1:
+            tiles = self._check_tiles(tiles)
+            if tiles.shape[0] != self.total:
+                raise DsxError(f"{what} needs every tile of the plan")
+            return tiles, int(tiles.shape[1]), 0
+        tiles = tiles.contiguous()
+        if Cn is None or tiles.dtype != torch.float32 or not tiles.is_cuda:
+            raise DsxError(f"{what}: a gathered buffer is a float32 CUDA tensor and needs its channel count Cn")
+        Cn, stride = int(Cn), tiles.numel() // world
+        if stride < self.blend_rank_stride(world, Cn):
+            raise DsxError(f"{what}: the gathered buffer must hold world slots of blend_rank_stride elements")
+        return tiles, Cn, stride
+
     def blend(self, tiles, world=1, gt=None, canvas=None, Cn=None):
         """Every tile of the plan, overlap-added under the plan's window (``set_window`` first) -> canvas (N,H,W,C);
         with ``gt`` also the (N, C) RangeInvariantPsnr: (canvas, psnr).  ``world == 1``: ``tiles`` (total, C, ph, pw).
@@ -325,18 +354,7 @@ class TilePlan:
         The partial-sum rows of the last call, (N, blend_blocks, C, 8) float64 or None, stay in ``last_blend_partials``."""
         _lib.require_gpu()
         world = int(world)
-        if world == 1:
-            tiles = self._check_tiles(tiles)
-            if tiles.shape[0] != self.total:
-                raise DsxError("blend needs every tile of the plan")
-            Cn, stride = int(tiles.shape[1]), 0
-        else:
-            tiles = tiles.contiguous()
-            if Cn is None or tiles.dtype != torch.float32 or not tiles.is_cuda:
-                raise DsxError("blend: a gathered buffer is a float32 CUDA tensor and needs its channel count Cn")
-            Cn, stride = int(Cn), tiles.numel() // world
-            if stride < self.blend_rank_stride(world, Cn):
-                raise DsxError("blend: the gathered buffer must hold world slots of blend_rank_stride elements")
+        tiles, Cn, stride = self._whole_tiles("blend", tiles, world, Cn)
         if canvas is None:
             canvas = torch.empty(self.data_shape + (Cn,), dtype=torch.float32, device=tiles.device)
         part = None
@@ -356,28 +374,12 @@ class TilePlan:
         in ``blend``; the state must not alias the tiles."""
         _lib.require_gpu()
         world = int(world)
-        if world == 1:
-            x0_tiles = self._check_tiles(x0_tiles)
-            if x0_tiles.shape[0] != self.total:
-                raise DsxError("blend_step needs every tile of the plan")
-            Cn, stride = int(x0_tiles.shape[1]), 0
-        else:
-            x0_tiles = x0_tiles.contiguous()
-            if Cn is None or x0_tiles.dtype != torch.float32 or not x0_tiles.is_cuda:
-                raise DsxError("blend_step: a gathered buffer is a float32 CUDA tensor and needs its channel count Cn")
-            Cn, stride = int(Cn), x0_tiles.numel() // world
-            if stride < self.blend_rank_stride(world, Cn):
-                raise DsxError("blend_step: the gathered buffer must hold world slots of blend_rank_stride elements")
+        x0_tiles, Cn, stride = self._whole_tiles("blend_step", x0_tiles, world, Cn)
         if not torch.is_tensor(state) or not state.is_cuda or state.dtype != torch.float32 or \
                 not state.is_contiguous() or tuple(state.shape) != self.data_shape + (Cn,):
             raise DsxError(f"blend_step: the state must be a contiguous float32 CUDA tensor of shape "
                            f"{self.data_shape + (Cn,)} (it is updated in place)")
-        draw, id_base = int(draw), int(id_base)
-        if not 0 <= draw < _lib.STREAM_DRAW_LIMIT:
-            raise DsxError(f"blend_step: draw ordinal {draw} out of range (0 <= draw < 2^24)")
-        if not 0 <= id_base <= _lib.STREAM_ID_LIMIT - self.data_shape[0]:
-            raise DsxError(f"blend_step: id_base = {id_base} with {self.data_shape[0]} frames: every field id must be "
-                           "below 2^40")
+        draw, id_base = self._field_draw("blend_step", draw, id_base)
         check(lib.dsx_tileplan_blend_step(self.handle, x0_tiles, Cn, world, stride, state, float(c_x0), float(c_xt),
                                           float(sigma), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(id_base),
                                           C.c_uint32(draw), None))
@@ -397,11 +399,4 @@ class TilePlan:
                           device=canvas.device)
         call = lambda first, stride, count, dst: check(lib.dsx_tileplan_gather_canvas(
             self.handle, canvas, Cn, first, stride, count, dst, None))
-        seq = as_sequence(ids)
-        if seq is not None:
-            for k0 in range(0, seq[2], 65535):
-                call(seq[0] + k0 * seq[1], seq[1], min(65535, seq[2] - k0), out[k0:])
-        else:
-            for k, i in enumerate(ids):
-                call(int(i), 1, 1, out[k:])
-        return out
+        return _per_sequence(ids, call, out)

@@ -63,6 +63,7 @@ the tiles' UNet outputs and applies the InDI update with the frame's noise field
 needs a ground truth (not with ``--input``, ``--validate`` or colour items) and frames of 176 x 176 or more.
 """
 import argparse
+import functools
 import logging
 import os
 import sys
@@ -119,7 +120,17 @@ def get_datasets(opt, tiled_pred=False, norm_from="train", device="cuda"):
 
 
 def _data_type(ds, norm_from="train"):
-    return (ds["train"] if norm_from == "train" else ds["train"] or ds["val"])["name"]
+    return ((ds.get("train") if norm_from == "train" else ds.get("train") or ds.get("val")) or {}).get("name")
+
+
+def _config_once(path):
+    """-> ``config()``: (``model.which_model_G``, the ``datasets`` dict) of the configuration file, for the flag checks.
+    The file is read at the first call and only then: a run whose flags ask nothing of it does not open it here."""
+    @functools.lru_cache(maxsize=None)
+    def config():
+        cfg = Logger.load_json(path)
+        return (cfg.get("model") or {}).get("which_model_G"), cfg.get("datasets") or {}
+    return config
 
 
 def _cifar_location(ds, part, norm_from):
@@ -148,18 +159,24 @@ def _read_frames(path):
     return np.load(path, allow_pickle=False).astype(np.float32)
 
 
-def _write_prediction(path, pred, val_set, spread=False):
-    """--out: the stitched prediction (N,H,W,C), un-normalised to raw counts with the dataset's mean_target /
-    std_target, as .npy (N,H,W,C) float32 or as a .tif hyperstack of N * C float32 pages (frame-major).  ``spread``
-    (--std-out): a per-pixel standard deviation, scaled by std_target with no mean added."""
+def _target_stats(val_set, channels):
+    """(mean_target, std_target), float64, of the ``channels`` channels a prediction of ``val_set`` holds."""
     nd = val_set.get_normalization_dict()
     idx = val_set._target_channel_idx
     mean, std = (np.asarray(nd[k], dtype=np.float64).reshape(-1) for k in ("mean_target", "std_target"))
     if idx is not None:
         mean, std = mean[idx:idx + 1], std[idx:idx + 1]
+    if mean.size != channels:
+        raise DsxError(f"--out: the prediction has {channels} channels, the dataset normalises {mean.size}")
+    return mean, std
+
+
+def _write_prediction(path, pred, val_set, spread=False):
+    """--out: the stitched prediction (N,H,W,C), un-normalised to raw counts with the dataset's mean_target /
+    std_target, as .npy (N,H,W,C) float32 or as a .tif hyperstack of N * C float32 pages (frame-major).  ``spread``
+    (--std-out): a per-pixel standard deviation, scaled by std_target with no mean added."""
     C_out = pred.shape[-1]
-    if mean.size != C_out:
-        raise DsxError(f"--out: the prediction has {C_out} channels, the dataset normalises {mean.size}")
+    mean, std = _target_stats(val_set, C_out)
     mean_t = torch.as_tensor(mean, dtype=torch.float32, device=pred.device)
     std_t = torch.as_tensor(std, dtype=torch.float32, device=pred.device)
     raw = ((pred * std_t) if spread else (pred * std_t + mean_t)).cpu().numpy()
@@ -256,10 +273,11 @@ def main(argv=None):
                     help="also score the stitched prediction with the range-invariant multi-scale SSIM "
                          "(core.metrics.calculate_msssim: five scales, frames of 176 x 176 or more)")
     args = ap.parse_args(argv)
-    _check_msssim_args(args)
-    _check_solver_args(args)
+    config = _config_once(args.config)
+    _check_msssim_args(args, config)
+    _check_solver_args(args, config)
     _check_stitch_args(args, len(str(args.gpu_ids).split(",")) if args.gpus is None else args.gpus)
-    _check_frame_args(args)
+    _check_frame_args(args, config)
     if args.sample_seed is not None and args.validate:
         raise SystemExit("--sample-seed names the tiles of a tiled prediction: not with --validate")
     if args.phase == "train":
@@ -270,8 +288,8 @@ def main(argv=None):
         raise SystemExit("--out: a .npy or .tif file")
     if args.out and args.validate:
         raise SystemExit("--out writes the tiled prediction: not with --validate")
-    _check_input_args(args)
-    _check_mixed_args(args)
+    _check_input_args(args, config)
+    _check_mixed_args(args, config)
     n_ranks = args.gpus if args.gpus is not None else len(str(args.gpu_ids).split(","))
     if argv is None and parallel.needs_self_launch(n_ranks):
         # fresh child processes, started before anything here touches the GPU (never an exec after HIP init)
@@ -338,16 +356,18 @@ def main(argv=None):
     # resident on the GPU: quantile normalisation (compute_normalization_dict), ShiftBoundary tiling, normalised
     # tile batches cut by one HIP launch
     patch = min(_config_patch(dsopt), frames.shape[1], frames.shape[2])
-    val_set = SplitDatasetTiledPred("Hagen", DataLocation(arrays=(frames[..., 0], frames[..., 1])), patch,
-                                    grid_size=patch // 2, target_channel_idx=dsopt.get("target_channel_idx"),
-                                    max_qval=dsopt.get("max_qval") or 0.98, upper_clip=bool(dsopt.get("upper_clip")),
-                                    channel_weights=dsopt.get("channel_weights"), enable_transforms=False,
-                                    random_patching=False, input_from_normalized_target=(which == "joint_indi"),
-                                    device=dev)
+    common = dict(target_channel_idx=dsopt.get("target_channel_idx"), max_qval=dsopt.get("max_qval") or 0.98,
+                  upper_clip=bool(dsopt.get("upper_clip")), channel_weights=dsopt.get("channel_weights"),
+                  enable_transforms=False, random_patching=False, input_from_normalized_target=(which == "joint_indi"),
+                  device=dev)
+    location = DataLocation(arrays=(frames[..., 0], frames[..., 1]))
+    val_set = SplitDatasetTiledPred("Hagen", location, patch, grid_size=patch // 2, **common)
     if args.frames:
         _save_norm(args, val_set, dsopt, "Hagen", rank, log)
     if args.validate:
-        return _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log)
+        # the non-tiled dataset of the same frames with the same normalisation (split.get_datasets without tiled_pred)
+        items = SplitDataset("Hagen", location, patch, normalization_dict=val_set.get_normalization_dict(), **common)
+        return _run_validate(args, opt, diffusion, items, log)
     if args.mix_t is not None:
         return _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log)
     return _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log)
@@ -423,7 +443,7 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     return pred
 
 
-def _check_msssim_args(args):
+def _check_msssim_args(args, config):
     """``--ms-ssim``, checked on the command line and the config file alone (nothing touches the GPU, no rank is
     started): it scores a tiled prediction of two grey channels against their ground truth.  Without it: nothing."""
     if not args.ms_ssim:
@@ -432,9 +452,7 @@ def _check_msssim_args(args):
         raise SystemExit("--ms-ssim with --input: an input-only stack has no ground truth to score against")
     if args.validate:
         raise SystemExit("--ms-ssim scores the stitched frames of a tiled prediction: not with --validate")
-    ds = Logger.load_json(args.config).get("datasets") or {}
-    if args.datapath and ((ds.get("train") if args.norm_from == "train" else ds.get("train") or ds.get("val")) or
-                          {}).get("name") == "cifar10":
+    if args.datapath and _data_type(config()[1], args.norm_from) == "cifar10":
         raise SystemExit("--ms-ssim scores the stitched frames of a tiled prediction: the colour items of a cifar10 "
                          "config are not tiled (and 32 x 32 items cannot hold five scales)")
     if not (args.datapath or args.frames):
@@ -467,7 +485,7 @@ def _log_msssim(args, val_set, pred, ps, log):
         log.info("channel %d: MS-SSIM (range-invariant) %.6f +- %.6f over %d frames", c, float(v.mean()), sem, v.size)
 
 
-def _check_input_args(args):
+def _check_input_args(args, config):
     """The flags of the input-only prediction and of the posterior samples, checked on the command line, the config and
     the normalisation file alone (nothing touches the GPU, no rank is started)."""
     if args.samples is not None:
@@ -501,8 +519,7 @@ def _check_input_args(args):
                          "input-only stack has no channels to compute it from)")
     if args.input_clip is not None and not (np.isfinite(args.input_clip) and args.input_clip >= 0):
         raise SystemExit(f"--input-clip {args.input_clip}: a finite, non-negative count")
-    cfg = Logger.load_json(args.config)
-    which = (cfg.get("model") or {}).get("which_model_G")
+    which, ds = config()
     if which == "joint_indi":
         raise SystemExit("--input with a joint_indi config: its network input is the weighted sum of the NORMALISED "
                          "channels, which is no function of the superimposed counts unless both stds are equal")
@@ -514,13 +531,13 @@ def _check_input_args(args):
     if meta["data_type"] == "cifar10":
         raise SystemExit(f"--norm {args.norm}: a cifar10 normalisation; --input takes a grey (N,H,W) stack, colour items "
                          "are not tiled")
-    idx = ((cfg.get("datasets") or {}).get("target_channel_idx"))
+    idx = ds.get("target_channel_idx")
     if meta["target_channel_idx"] != idx:
         raise SystemExit(f"--norm {args.norm}: written for target_channel_idx = {meta['target_channel_idx']}, the config "
                          f"says {idx}")
 
 
-def _check_solver_args(args):
+def _check_solver_args(args, config):
     """The flags of few-step sampling and of frame-keyed noise, checked on the command line and the config file alone
     (nothing touches the GPU, no rank is started).  Without any of them: nothing."""
     if args.noise_field:
@@ -534,7 +551,7 @@ def _check_solver_args(args):
         if given:
             raise SystemExit(f"{', '.join(given)}: only with --solver {{ddim,dpmpp2m}}")
         return
-    which = (Logger.load_json(args.config).get("model") or {}).get("which_model_G")
+    which = config()[0]
     if which not in ("sr3", "ddpm"):
         raise SystemExit(f"--solver: few-step solvers run a Gaussian sampler (which_model_G sr3 / ddpm); this config "
                          f"builds {which!r}, whose loop already takes --steps")
@@ -576,7 +593,7 @@ def _check_stitch_args(args, n_ranks):
         raise SystemExit("--fuse-steps runs on one rank: a collective after every solver row is not provided")
 
 
-def _check_frame_args(args):
+def _check_frame_args(args, config):
     """``--frame-steps``, checked on the command line and the config file alone (nothing touches the GPU, no rank is
     started).  Without it: nothing."""
     if not args.frame_steps:
@@ -587,7 +604,7 @@ def _check_frame_args(args):
     if args.solver is not None:
         raise SystemExit("--frame-steps with --solver: frame diffusion runs the InDI loop of an indi / joint_indi config; "
                          "few-step solvers belong to sr3 / ddpm (--fuse-steps)")
-    which = (Logger.load_json(args.config).get("model") or {}).get("which_model_G")
+    which = config()[0]
     if which not in ("indi", "joint_indi"):
         raise SystemExit(f"--frame-steps diffuses the frames of an InDI sampler (which_model_G indi / joint_indi); this "
                          f"config builds {which!r}: a Gaussian sampler's fusion is --solver with --fuse-steps")
@@ -613,13 +630,13 @@ _MIXED_FLAGS = (("--mix-t", "mix_t"), ("--time-predictor", "time_predictor"),
 _REFINE_FLAGS = _MIXED_FLAGS[-3:]
 
 
-def _check_mixed_args(args):
+def _check_mixed_args(args, config):
     """The flags of the mixed-input prediction, checked on the command line and the config file alone (nothing touches
     the GPU, no rank is started): they need a ``joint_indi`` config and ``--mix-t``.  Without any of them: nothing."""
     given = [flag for flag, name in _MIXED_FLAGS if getattr(args, name) is not None]
     if not given:
         return
-    which = (Logger.load_json(args.config).get("model") or {}).get("which_model_G")
+    which = config()[0]
     if which != "joint_indi":
         raise SystemExit(f"{', '.join(given)}: the mixed-input prediction runs indi1 and indi2 of a joint_indi config; "
                          f"this config builds {which!r}")
@@ -704,17 +721,6 @@ def _predict_mixed(args, netG, val_set, n_steps, patch, rank, world, log):
     return pred
 
 
-def _validate(args, opt, diffusion, val_set, frames, patch, dsopt, which, dev, log):
-    """``--validate``: the non-tiled dataset of the same frames with the same normalisation (split.get_datasets without
-    tiled_pred), the validation schedule, and ``core.validation.validate``.  Returns avg_psnr."""
-    items = SplitDataset("Hagen", DataLocation(arrays=(frames[..., 0], frames[..., 1])), patch,
-                         target_channel_idx=dsopt.get("target_channel_idx"), max_qval=dsopt.get("max_qval") or 0.98,
-                         normalization_dict=val_set.get_normalization_dict(), upper_clip=bool(dsopt.get("upper_clip")),
-                         channel_weights=dsopt.get("channel_weights"), enable_transforms=False, random_patching=False,
-                         input_from_normalized_target=(which == "joint_indi"), device=dev)
-    return _run_validate(args, opt, diffusion, items, log)
-
-
 def _run_validate(args, opt, diffusion, items, log, whole_set=False):
     """``core.validation.validate`` over the first ``--items`` items (default 19; every item with ``whole_set``), the
     log lines of the training loop, and with ``--out`` the predictions in raw counts.  Returns avg_psnr."""
@@ -745,13 +751,7 @@ def _run_validate(args, opt, diffusion, items, log, whole_set=False):
 def _raw_counts(pred, val_set):
     """A normalised prediction (B, C, H, W) in raw counts: x * std_target + mean_target per channel in float64, as the
     validation report un-normalises it, rounded to float32 once."""
-    nd = val_set.get_normalization_dict()
-    idx = val_set._target_channel_idx
-    mean, std = (np.asarray(nd[k], dtype=np.float64).reshape(-1) for k in ("mean_target", "std_target"))
-    if idx is not None:
-        mean, std = mean[idx:idx + 1], std[idx:idx + 1]
-    if mean.size != pred.shape[1]:
-        raise DsxError(f"--out: the prediction has {pred.shape[1]} channels, the dataset normalises {mean.size}")
+    mean, std = _target_stats(val_set, pred.shape[1])
     as_t = lambda v: torch.as_tensor(v, dtype=torch.float64, device=pred.device).reshape(1, -1, 1, 1)
     return (pred.to(torch.float64) * as_t(std) + as_t(mean)).to(torch.float32)
 

@@ -20,7 +20,7 @@ import torch
 from .core import logger as Logger
 from ._lib import DsxError
 from .data.split_dataset import DataLocation, SplitDataset, SplitDatasetTiledPred
-from .data.tiled_predict import _batches, evaluate_time_predictor
+from .data.tiled_predict import _batches, evaluate_time_predictor, store_kept
 from .data.time_predictor_dataset import TimePredictorDataset
 from .model.ddpm_modules.time_predictor import TimePredictor
 
@@ -134,12 +134,11 @@ def validation_loss(model, val_set, batch_size, loss_type):
     pred = torch.empty(n, dtype=torch.float32, device=val_set._dev[0].device)
     t_ints, t_all = [0] * n, np.empty(n, dtype=np.float64)
     for chunk, keep in _batches(range(n), batch_size):
-        own = len(chunk) - keep
-        for i in chunk[own:]:
+        for i in chunk[len(chunk) - keep:]:
             t_ints[i] = val_set.sample_t()[1]
         inp, t = val_set.batch(chunk, t_ints=[t_ints[i] for i in chunk])
-        pred[chunk[own]:chunk[-1] + 1] = model(inp)[own:]
-        t_all[chunk[own]:chunk[-1] + 1] = t[own:]
+        store_kept(pred, model(inp), chunk, keep)
+        store_kept(t_all, t, chunk, keep)
     pred = pred.cpu().numpy()
     val_loss, per_batch = batch_losses(pred, t_all, batch_size, loss_type)
     return val_loss, per_batch, pred, t_all

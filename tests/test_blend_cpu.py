@@ -217,14 +217,14 @@ def test_split_refuses_the_stitch_flags_where_they_do_not_apply(tmp_path, monkey
 def test_predict_stack_refuses_by_name_before_any_launch(monkeypatch):
     from diffsplitting_amd import _lib, parallel
     from diffsplitting_amd._lib import DsxError
-    from diffsplitting_amd.data import tiled_predict
+    from diffsplitting_amd.data import tile_predict
     from diffsplitting_amd.data.tiled_predict import predict_stack, predict_tiled
     from tests.test_field_cpu import _samplers
 
     def touched(*a, **k):
         raise AssertionError("the refusal came too late")
     monkeypatch.setattr(_lib, "require_gpu", touched)
-    monkeypatch.setattr(tiled_predict, "TileExchange", touched)
+    monkeypatch.setattr(tile_predict, "TileExchange", touched)
     g, i, _ = _samplers()
 
     class Stack:

@@ -126,14 +126,14 @@ def test_the_python_face_refuses_before_the_library(monkeypatch):
 def test_predict_stack_frames_refuses_by_name_before_any_launch(monkeypatch):
     from diffsplitting_amd import _lib as L, parallel
     from diffsplitting_amd._lib import DsxError
-    from diffsplitting_amd.data import tiled_predict
+    from diffsplitting_amd.data import tile_predict
     from diffsplitting_amd.data.tiled_predict import predict_stack, predict_stack_frames
     from tests.test_field_cpu import _samplers
 
     def touched(*a, **k):
         raise AssertionError("the refusal came too late")
     monkeypatch.setattr(L, "require_gpu", touched)
-    monkeypatch.setattr(tiled_predict, "TileExchange", touched)
+    monkeypatch.setattr(tile_predict, "TileExchange", touched)
     monkeypatch.setattr(parallel, "all_gather_flat", touched)
     g, i, j = _samplers()
 
