@@ -200,13 +200,9 @@ def _stochastic_rows(netG, num_timesteps, solver):
     """(rows, C): how many rows of one batch's loop add noise -- each is one materialised (B, C, p, p) draw under
     noise='field' -- and the channels C of the sampler's state."""
     if _is_gaussian(netG):
-        if solver:
-            sigma = netG.solver_table(**solver).sigma
-            return sum(1 for s in range(len(sigma)) if sigma[s] != 0), int(netG.channels)
-        netG._need_schedule()
-        return (netG.num_timesteps - 1 if netG.kind == "sr3" else netG.num_timesteps), int(netG.channels)
+        return len(netG.noise_rows(netG.solver_table(**solver) if solver else None)), int(netG.channels)
     children = [netG.indi1, netG.indi2] if hasattr(netG, "indi1") else [netG]
-    rows = sum(int(num_timesteps if num_timesteps is not None else c.num_timesteps) for c in children)
+    rows = sum(len(c.noise_rows(int(num_timesteps if num_timesteps is not None else c.num_timesteps))) for c in children)
     return rows, int(children[0].out_channel)
 
 

@@ -351,12 +351,11 @@ class UNetEngine:
                 steps.ctypes.data_as(C.POINTER(C.c_int32)) if len(steps) else None, len(steps), snaps,
                 1 if use_graph else 0, stream)
         if solver:
-            check(lib.dsx_solver_loop(*args, None if ids is None else ids.ctypes.data_as(_lib._pu64),
-                                      0 if ids is None else len(ids)))
+            check(lib.dsx_solver_loop(*args, *_ids_arg(ids)))
         elif ids is None:
             check(lib.dsx_sample_loop(*args))
         else:
-            check(lib.dsx_sample_loop_streams(*args, ids.ctypes.data_as(_lib._pu64), len(ids)))
+            check(lib.dsx_sample_loop_streams(*args, *_ids_arg(ids)))
         return x, snaps
 
 
@@ -551,6 +550,11 @@ def _sample_ids(sample_ids, B, limit=_lib.STREAM_ID_LIMIT):
     return np.asarray(ids, dtype=np.uint64)
 
 
+def _ids_arg(ids):
+    """The ``(pointer, count)`` pair the library takes for checked ids (``_sample_ids``); ``(None, 0)`` without ids."""
+    return (None, 0) if ids is None else (ids.ctypes.data_as(_lib._pu64), len(ids))
+
+
 def _draw_ordinal(draw):
     draw = int(draw)
     if not 0 <= draw < _lib.STREAM_DRAW_LIMIT:
@@ -725,7 +729,7 @@ def posterior_step(x, net, c1, c2, sigma, a=None, b=None, predict_eps=False, cli
         ids, d = streams
         check(lib.dsx_posterior_step_streams(x, net, B, Cn, H, W, a, b, c1, c2, sigma, 1 if predict_eps else 0,
                                              1 if clip else 0, None, _seed64(seed), C.c_uint64(d), 0,
-                                             *outs, None, ids.ctypes.data_as(_lib._pu64), len(ids)))
+                                             *outs, None, *_ids_arg(ids)))
         return tuple(outs)
     check(lib.dsx_posterior_step(x, net, B, Cn, H, W, a, b, c1, c2, sigma, 1 if predict_eps else 0, 1 if clip else 0, z,
                                  _seed64(seed), C.c_uint64(int(subsequence)), 1 if repeat_noise else 0, *outs, None))
@@ -753,13 +757,10 @@ def solver_step(x, net, a, b, cx, c0, sigma, cp=None, x0_prev=None, clip=False, 
         z = _f32_cuda(z, "noise", x.shape)
     x_recon_out = torch.empty_like(x) if x_recon_out is None else _f32_cuda(x_recon_out, "x_recon_out", x.shape)
     x_out = torch.empty_like(x) if x_out is None else _f32_cuda(x_out, "x_out", x.shape)
-    ids, n_ids, d = None, 0, 0
-    streams = _stream_draw(sample_ids, draw, B, z is not None and
-                           "sample_ids together with injected noise: the draws come from one or the other")
-    if streams:
-        ids, n_ids, d = streams[0].ctypes.data_as(_lib._pu64), len(streams[0]), streams[1]
+    ids, d = _stream_draw(sample_ids, draw, B, z is not None and
+                          "sample_ids together with injected noise: the draws come from one or the other") or (None, 0)
     check(lib.dsx_solver_step(x, net, x0_prev, B, Cn, H, W, a, b, cx, c0, cp, sigma, 1 if clip else 0, z, _seed64(seed),
-                              C.c_uint64(int(subsequence)), x_recon_out, x_out, None, ids, n_ids, C.c_uint32(d)))
+                              C.c_uint64(int(subsequence)), x_recon_out, x_out, None, *_ids_arg(ids), C.c_uint32(d)))
     return x_recon_out, x_out
 
 

@@ -9,9 +9,12 @@ Training itself (backward, optimiser) stays out of scope.  The single reverse st
 ``inference_one_step``) and ``interpolate`` let a caller drive the loop: one UNet forward and one
 ``dsx_posterior_step`` launch per step.
 
-Noise: by default the per-step noise is drawn on the device (Philox, seeded
-from torch's generator); set ``noise_source`` to a ``randn(shape)`` callable to
-inject host draws in the reference's draw order (parity mode, Q4).
+Noise: where a call's normals come from is decided once, by the ``Draws`` object (``model/draws.py``) every public
+sampling entry builds first -- it refuses what does not go together before anything is drawn -- and asks for the
+initial state, for the loop's ``noise`` / ``seed`` / ``sample_ids`` keywords or for a single step's.  Which rows of a
+loop add noise is each sampler's ``noise_rows``.  By default the per-step noise is drawn on the device (Philox, seeded
+from torch's generator); set ``noise_source`` to a ``randn(shape)`` callable to inject host draws in the reference's
+draw order (parity mode, Q4).
 
 Per-sample noise streams (opt-in, include/dsx.h): the sampling loops take ``seed=`` and ``sample_ids=`` (B integers);
 the single steps keep the reference's signatures and have the siblings ``p_sample_seeded`` /
@@ -24,7 +27,7 @@ Draws by ordinal: ``noise_field``, a callable ``(shape, draw) -> CUDA fp32 tenso
 (draw 0) and for the noise of step ``s`` (draw ``s + 1``) of every sampling loop, which then runs on these draws in the
 injected form; a step that adds no noise keeps its ordinal.  Tiled prediction sets it to noise cut from a frame-keyed
 field (``TilePlan.randn_field``).  Together with ``noise_source`` or ``sample_ids`` it is refused; torch's generator is
-not touched.
+not touched.  The single steps, the objective and ``interpolate`` do not consult it (a known gap).
 
 Few-step sampling (Gaussian samplers only): ``solver_sample_loop`` runs a sub-sequence of the trained schedule with
 DDIM(eta) or DPM-Solver++(2M) rows (``model/solvers.py``) through ``UNetEngine.solver_loop``; ``p_sample_loop`` and
@@ -37,6 +40,7 @@ from torch import nn
 from .. import engine
 from .._lib import DsxError
 from . import solvers
+from .draws import Draws
 
 
 class _SamplerBase(nn.Module):
@@ -47,66 +51,12 @@ class _SamplerBase(nn.Module):
         self.use_graph = True
         self.last_full_batch = None   # final state of the whole batch (Q1 keeps only one element)
 
-    def _draw(self, shape, device):
-        if self.noise_source is not None:
-            return self.noise_source(tuple(shape)).to(device=device, dtype=torch.float32)
-        return torch.randn(tuple(shape), device=device)
-
-    def _uses_field(self, sample_ids=None):
-        """Whether ``noise_field`` provides the draws of this call; refused together with the two other sources."""
-        if self.noise_field is None:
-            return False
-        if self.noise_source is not None:
-            raise DsxError("noise_field together with noise_source: the draws come from one or the other")
-        if sample_ids is not None:
-            raise DsxError("noise_field together with sample_ids: the draws come from the field or from the sample "
-                           "streams, not both")
-        return True
-
-    def _field(self, shape, draw, device):
-        """Draw ``draw`` of ``noise_field`` for a state of ``shape`` (0: the initial state, s + 1: step s)."""
-        shape = tuple(int(v) for v in shape)
-        z = self.noise_field(shape, int(draw))
-        if not torch.is_tensor(z) or not z.is_cuda or z.dtype != torch.float32 or tuple(z.shape) != shape:
-            raise DsxError(f"noise_field(shape, draw) must return a float32 CUDA tensor of shape {shape}")
-        return z.to(device)
-
-    def _field_noise(self, shape, n_steps, draws, device):
-        """The injected form (n_steps, B, C, H, W) of a loop whose steps ``draws`` add noise: step s holds draw s + 1."""
-        draws = list(draws)
-        if not draws:
-            return None
-        noise = torch.zeros((n_steps,) + tuple(shape), device=device)
-        for s in draws:
-            noise[s] = self._field(shape, s + 1, device)
-        return noise
-
-    def _loop_seed(self):
-        """The Philox seed of a sampling loop; with ``noise_field`` every draw is injected and torch's generator stays
-        untouched."""
-        return 0 if self.noise_field is not None else self._seed()
-
-    def _seed(self):
-        if self.noise_source is not None:
-            return 0   # injected noise: leave torch's generator untouched (the draws must stay in order)
-        return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-
     STREAM2_BIT = 1 << 39            # JointIndi: the second sampler's ids carry this bit, callers' ids stay below it
 
-    def _stream_args(self, seed, sample_ids, B, limit=None):
-        """None without ``sample_ids`` (today's noise); else ``(seed, ids)`` of the per-sample noise streams, checked:
-        B ids below ``limit`` (2^40), a seed, and no ``noise_source`` -- the draws come from one or the other."""
-        if sample_ids is None:
-            if seed is not None:
-                raise DsxError("seed= names the per-sample noise streams: only together with sample_ids=")
-            return None
-        if self.noise_source is not None:
-            raise DsxError("noise_source together with sample_ids: the draws are injected or come from the sample "
-                           "streams, not both")
-        if seed is None:
-            raise DsxError("sample_ids need seed=: a sample stream is named by (seed, sample id)")
-        kw = {} if limit is None else dict(limit=limit)
-        return int(seed), [int(v) for v in engine._sample_ids(sample_ids, B, **kw)]
+    def _draws(self, B, seed=None, sample_ids=None, field=True):
+        """The ``Draws`` of one call on a batch of ``B``, built -- and everything refused -- before anything is drawn.
+        ``field=False``: a call that does not consult ``noise_field`` (single steps, the objective, ``interpolate``)."""
+        return Draws(self.noise_source, self.noise_field if field else None, seed, sample_ids, B)
 
     def forward(self, x, *args, **kwargs):
         """The objective's forward evaluation (``p_losses``); no gradients, eval semantics."""
@@ -143,22 +93,14 @@ class _SamplerBase(nn.Module):
             total = total / a.numel()
         return total.to(torch.float32)
 
-    def _noise_or_seed(self, noise, shape, device):
-        """(z, seed): the injected draws (``noise`` or one ``noise_source`` draw), else None and a Philox seed."""
-        if noise is None and self.noise_source is not None:
-            noise = self._draw(shape, device)
-        if noise is not None:
-            return noise.to(device=device, dtype=torch.float32).contiguous(), 0
-        return None, self._seed()
-
     def _q_args(self, x_start, coef, noise):
         """What engine.q_sample takes: x_start as contiguous float32 (a copy only when the caller's is not), the
-        coefficients (c0, c1, c2) on the device, and the draws (z, seed)."""
+        coefficients (c0, c1, c2) on the device, and the draws (z, seed): ``noise``, or a single step's."""
         dev = x_start.device
         x_start = x_start.float().contiguous()
-        z, seed = self._noise_or_seed(noise, x_start.shape, dev)
+        zkw = self._draws(x_start.shape[0], field=False).step(x_start.shape, dev, noise=noise)
         c0, c1, c2 = (None if c is None else c.to(dev).contiguous() for c in coef)
-        return x_start, c0, c2, dict(c1=c1, z=z, seed=seed)
+        return x_start, c0, c2, dict(c1=c1, **zkw)
 
     def _q_sample(self, x_start, coef, noise, x_end=None):
         """The public q_sample of the three families: one dsx_q_sample launch."""
@@ -239,47 +181,41 @@ class GaussianSampler(_SamplerBase):
         """``seed`` / ``sample_ids``: per-sample noise streams -- the initial state is ``randn_samples(draw=0)``, step
         ``s`` takes draw ``s + 1``; torch's generator is not touched."""
         self._need_schedule()
-        dev = self.betas.device
-        T = self.num_timesteps
-        cond, shape, streams, img, first = self._loop_start(x_in, continous, seed, sample_ids)
-        noise = None
-        if self.noise_field is not None:   # checked by _loop_start; the same steps as below, by ordinal
-            noise = self._field_noise(shape, T, range(T - 1 if self.kind == "sr3" else T), dev)
-        elif self.noise_source is not None:  # reference draw order: one per step, none at t == 0 (sr3)
-            n_draw = T - 1 if self.kind == "sr3" else T
-            noise = torch.zeros((T,) + shape, device=dev)
-            for s in range(n_draw):
-                noise[s] = self._draw(shape, dev)
-        snaps = engine.gaussian_snapshot_steps(T) if continous else []
-        skw = dict(seed=self._loop_seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
-        x, sn = self.denoise_fn.engine().sample_loop(self._step_table(bool(clip_denoised)), img, cond=cond,
-                                                     noise=noise, snapshot_steps=snaps, use_graph=self.use_graph, **skw)
-        self.last_full_batch = x
-        if self.kind == "ddpm" and not self.conditional:
-            return x                                                 # ddpm diffusion.py:222
-        if continous:
-            return torch.cat([first] + [s for s in sn], dim=0)
-        return x[-1]                                                 # diffusion.py:200-203: ret_img[-1]
+        table = self._step_table(bool(clip_denoised))
+        snaps = engine.gaussian_snapshot_steps(self.num_timesteps) if continous else []
+        return self._run("sample_loop", table, self.noise_rows(), snaps, x_in, continous, seed, sample_ids)
 
-    def _loop_start(self, x_in, continous, seed, sample_ids):
-        """What a reverse loop starts from: (cond, state shape, stream arguments or None, initial state, ret_img[0])."""
+    def noise_rows(self, table=None):
+        """The rows of a loop that add noise.  The ancestral loop follows the reference's draw order: one draw per row,
+        none at t == 0 for sr3 (its last row; ddpm draws there and masks it).  The rows of a solver ``table``: those
+        with sigma != 0 -- none for dpmpp2m and ddim with eta = 0, every row but the last for eta > 0."""
+        if table is not None:
+            return [s for s in range(table.n_steps) if table.sigma[s] != 0]
+        self._need_schedule()
+        return range(self.num_timesteps - 1 if self.kind == "sr3" else self.num_timesteps)
+
+    def _run(self, loop, table, rows, snaps, x_in, continous, seed, sample_ids):
+        """The reverse loop ``loop`` of the engine over ``table``, of which ``rows`` add noise, from draw 0, and what
+        the reference returns of it."""
         dev = self.betas.device
         if not self.conditional:
             shape, cond = tuple(x_in), None
         else:
             cond = x_in.to(dev).float()
             shape = (cond.shape[0], self.channels) + tuple(cond.shape[2:])
-        field = self._uses_field(sample_ids)
-        streams = self._stream_args(seed, sample_ids, shape[0])
-        if field:
-            img = self._field(shape, 0, dev)
-        elif streams is None:
-            img = self._draw(shape, dev)
-        else:
-            img = engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
+        draws = self._draws(shape[0], seed, sample_ids)
+        img = draws.initial(shape, dev)
         # the loop updates `img` in place: keep a copy of the initial noise for ret_img[0] (sr3 diffusion.py:183-185)
         first = (img.clone() if continous else None) if cond is None else cond.repeat((1, self.channels // cond.shape[1], 1, 1))
-        return cond, shape, streams, img, first
+        x, sn = getattr(self.denoise_fn.engine(), loop)(table, img, cond=cond, snapshot_steps=snaps,
+                                                        use_graph=self.use_graph,
+                                                        **draws.loop(shape, table.n_steps, rows, dev))
+        self.last_full_batch = x
+        if self.kind == "ddpm" and not self.conditional:
+            return x                                                 # ddpm diffusion.py:222
+        if continous:
+            return torch.cat([first] + [s for s in sn], dim=0)
+        return x[-1]                                                 # diffusion.py:200-203: ret_img[-1]
 
     def solver_table(self, steps=50, solver="dpmpp2m", eta=0.0, spacing=None, timesteps=None, clip_denoised=True):
         """The rows ``solver_sample_loop`` runs (``model/solvers.py``): a ``SolverTableHost`` with its ``timesteps``."""
@@ -299,30 +235,8 @@ class GaussianSampler(_SamplerBase):
         table = self.solver_table(steps, solver, eta, spacing, timesteps, clip_denoised)
         if self.conditional:
             self._need_cuda(x_in, what="solver_sample_loop")
-        dev = self.betas.device
-        cond, shape, streams, img, first = self._loop_start(x_in, continous, seed, sample_ids)
-        K = table.n_steps
-        draws = [s for s in range(K) if table.sigma[s] != 0]         # ddim with eta > 0: one per row but the last
-        noise = None
-        if self.noise_field is not None:
-            noise = self._field_noise(shape, K, draws, dev)
-        elif self.noise_source is not None and draws:
-            noise = torch.zeros((K,) + shape, device=dev)
-            for s in draws:
-                noise[s] = self._draw(shape, dev)
-        if streams is not None:
-            skw = dict(seed=streams[0], sample_ids=streams[1])
-        else:
-            skw = dict(seed=self._loop_seed() if draws else 0)
-        x, sn = self.denoise_fn.engine().solver_loop(table, img, cond=cond, noise=noise,
-                                                     snapshot_steps=range(K) if continous else (),
-                                                     use_graph=self.use_graph, **skw)
-        self.last_full_batch = x
-        if self.kind == "ddpm" and not self.conditional:
-            return x
-        if continous:
-            return torch.cat([first] + [s for s in sn], dim=0)
-        return x[-1]
+        snaps = range(table.n_steps) if continous else ()
+        return self._run("solver_loop", table, self.noise_rows(table), snaps, x_in, continous, seed, sample_ids)
 
     @torch.no_grad()
     def sample(self, batch_size=1, continous=False, seed=None, sample_ids=None):
@@ -347,10 +261,9 @@ class GaussianSampler(_SamplerBase):
         rows = engine.gaussian_step_rows(self._bufs_cpu, self.sqrt_alphas_cumprod_prev, self.kind, t)
         return {k: torch.from_numpy(np.ascontiguousarray(np.broadcast_to(v, (B,)))).to(dev) for k, v in rows.items()}
 
-    def _reverse(self, x, t, clip_denoised, condition_x, want, z=None, seed=0, repeat_noise=False, sample_ids=None,
-                 draw=None):
+    def _reverse(self, x, t, clip_denoised, condition_x, want, repeat_noise=False, **noise):
         """One UNet forward and one dsx_posterior_step launch: ``want`` = (x_recon, model_mean, sample) flags, the
-        wanted ones are returned as new tensors, the others as None."""
+        wanted ones are returned as new tensors, the others as None.  ``noise``: the keywords of ``Draws.step``."""
         self._need_cuda(x, *(() if condition_x is None else (condition_x,)))
         x = x.float().contiguous()
         B = x.shape[0]
@@ -364,9 +277,8 @@ class GaussianSampler(_SamplerBase):
         net = self.denoise_fn(inp, time)
         outs = [torch.empty_like(x) if w else None for w in want]
         return engine.posterior_step(x, net, r["c1"], r["c2"], r["sigma"], a=r["a"], b=r["b"], predict_eps=True,
-                                     clip=bool(clip_denoised), z=z, seed=seed, repeat_noise=repeat_noise,
-                                     x_recon_out=outs[0], mean_out=outs[1], x_out=outs[2], sample_ids=sample_ids,
-                                     draw=draw)
+                                     clip=bool(clip_denoised), repeat_noise=repeat_noise, x_recon_out=outs[0],
+                                     mean_out=outs[1], x_out=outs[2], **noise)
 
     def _step_draw(self, t, draw):
         """The draw ordinal of the reverse step at timestep ``t``: ``T - t``, what the loop uses there (its step
@@ -407,8 +319,8 @@ class GaussianSampler(_SamplerBase):
     def p_sample(self, x, t, clip_denoised=True, condition_x=None):
         """One draw per call, none at t == 0 (sr3 diffusion.py:174)."""
         self._need_cuda(x)
-        z, seed = self._noise_or_seed(None, x.shape, x.device) if t > 0 else (None, 0)
-        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), z=z, seed=seed)[2]
+        noise = self._draws(x.shape[0], field=False).step(x.shape, x.device) if t > 0 else {}
+        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), **noise)[2]
 
     @torch.no_grad()
     def p_sample_seeded(self, x, t, seed, sample_ids, clip_denoised=True, condition_x=None, draw=None):
@@ -417,11 +329,11 @@ class GaussianSampler(_SamplerBase):
         the caller's loop from ``randn_samples(draw=0)`` reproduces ``p_sample_loop`` with the same ids bit for bit.
         ``t``: an integer, or (B,) equal integers (ddpm)."""
         self._need_cuda(x)
-        streams = self._stream_args(seed, sample_ids, x.shape[0])
-        if streams is None:
+        draws = self._draws(x.shape[0], seed, sample_ids, field=False)
+        if draws.streams is None:
             raise DsxError("p_sample_seeded needs sample_ids (p_sample draws without them)")
-        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), seed=streams[0],
-                             sample_ids=streams[1], draw=self._step_draw(t, draw))[2]
+        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True),
+                             **draws.step(x.shape, x.device, draw=self._step_draw(t, draw)))[2]
 
     # ---- objective (sr3 diffusion.py:215-249) -----------------------------------------------
     def q_coefficients(self, continuous_sqrt_alpha_cumprod):
@@ -512,9 +424,8 @@ class GaussianSamplerDdpm(GaussianSampler):
         it (the reference's nonzero_mask, ddpm diffusion.py:199-203)."""
         self._need_cuda(x)
         shape = ((1,) + tuple(x.shape[1:])) if repeat_noise else tuple(x.shape)
-        z, seed = self._noise_or_seed(None, shape, x.device)
-        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), z=z, seed=seed,
-                             repeat_noise=bool(repeat_noise))[2]
+        return self._reverse(x, t, clip_denoised, condition_x, (False, False, True), repeat_noise=bool(repeat_noise),
+                             **self._draws(x.shape[0], field=False).step(shape, x.device))[2]
 
     @torch.no_grad()
     def interpolate(self, x1, x2, t=None, lam=0.5):
@@ -532,18 +443,17 @@ class GaussianSamplerDdpm(GaussianSampler):
         dev = x1.device
         b = x1.shape[0]
         c0, c2 = self.q_coefficients(torch.full((b,), t, dtype=torch.long))
-        z1, seed = self._noise_or_seed(None, x1.shape, dev)
-        z2 = None if z1 is None else self._draw(x1.shape, dev).contiguous()
+        draws = self._draws(b, field=False)                          # noise_field is not consulted
+        start = draws.step(x1.shape, dev)                            # x1's draw, or the seed of both
+        z1 = start["z"]
+        z2 = None if z1 is None else draws.normal(x1.shape, dev).contiguous()
         img = engine.interp_start(x1.float().contiguous(), x2.float().contiguous(), c0.to(dev).contiguous(),
-                                  c2.to(dev).contiguous(), lam, z1=z1, z2=z2, seed=seed)
+                                  c2.to(dev).contiguous(), lam, z1=z1, z2=z2, seed=start["seed"])
         if t == 0:
             return img
-        noise = None
-        if self.noise_source is not None:
-            noise = torch.stack([self._draw(x1.shape, dev) for _ in range(t)])
         table = engine.gaussian_step_table(self._bufs_cpu, self.sqrt_alphas_cumprod_prev, self.kind, True, start=t)
-        x, _ = self.denoise_fn.engine().sample_loop(table, img, noise=noise, seed=self._seed(),
-                                                    use_graph=self.use_graph)
+        x, _ = self.denoise_fn.engine().sample_loop(table, img, use_graph=self.use_graph,
+                                                    **draws.loop(x1.shape, t, range(t), dev))
         self.last_full_batch = x
         return x
 
@@ -694,19 +604,19 @@ class InDISampler(_SamplerBase):
     def inference_one_step(self, x_t, delta_t, t_cur):
         """indi.py:62-69: delta/t * UNet(x_t, t) + (1 - delta/t) * x_t + z * e (t - delta), one UNet forward and one
         dsx_posterior_step launch; the coefficients are one row of ``engine.indi_step_table``.  One draw per call."""
-        return self._one_step(x_t, delta_t, t_cur, None, None)
+        return self._one_step(x_t, delta_t, t_cur, self._draws(x_t.shape[0], field=False), None)
 
     @torch.no_grad()
     def inference_one_step_seeded(self, x_t, delta_t, t_cur, seed, sample_ids, draw):
         """``inference_one_step`` with per-sample noise streams (``inference_one_step`` itself keeps the reference's
         signature): ``draw`` = s + 1 at the caller's step ``s`` is the draw ``inference`` takes there with the same
         ``seed`` and ``sample_ids``, so the caller's loop reproduces it bit for bit."""
-        streams = self._stream_args(seed, sample_ids, x_t.shape[0])
-        if streams is None:
+        draws = self._draws(x_t.shape[0], seed, sample_ids, field=False)
+        if draws.streams is None:
             raise DsxError("inference_one_step_seeded needs sample_ids (inference_one_step draws without them)")
-        return self._one_step(x_t, delta_t, t_cur, streams, draw)
+        return self._one_step(x_t, delta_t, t_cur, draws, draw)
 
-    def _one_step(self, x_t, delta_t, t_cur, streams, draw):
+    def _one_step(self, x_t, delta_t, t_cur, draws, draw):
         assert delta_t <= t_cur, "delta_t should be less than or equal to t_cur."
         self._gaussian_noise_mode()
         self._need_cuda(x_t, what="inference_one_step")
@@ -716,12 +626,8 @@ class InDISampler(_SamplerBase):
         tc, c1, c2, sg = engine.indi_step_row(delta_t, t_cur, self.get_e(t_cur))
         col = lambda v: torch.full((B,), v, dtype=torch.float32, device=dev)
         x_0 = self.denoise_fn(x_t, torch.Tensor([tc]).to(dev))
-        if streams is not None:
-            return engine.posterior_step(x_t, x_0, col(c1), col(c2), col(sg), predict_eps=False, seed=streams[0],
-                                         sample_ids=streams[1], draw=draw, x_out=torch.empty_like(x_t))[2]
-        z, seed = self._noise_or_seed(None, x_t.shape, dev)
-        return engine.posterior_step(x_t, x_0, col(c1), col(c2), col(sg), predict_eps=False, z=z, seed=seed,
-                                     x_out=torch.empty_like(x_t))[2]
+        return engine.posterior_step(x_t, x_0, col(c1), col(c2), col(sg), predict_eps=False,
+                                     x_out=torch.empty_like(x_t), **draws.step(x_t.shape, dev, draw=draw))[2]
 
     def _copies(self, x_in):
         """How often the input is repeated along the channels: to ``out_channel`` channels in all.  indi.py:80,157
@@ -733,19 +639,20 @@ class InDISampler(_SamplerBase):
             raise DsxError("out_channel {} is no multiple of the input's {} channels".format(self.out_channel, cin))
         return self.out_channel // cin
 
-    def _draw0(self, shape, dev, streams):
-        """The draw of the initial state: torch's (or the injected one), or draw 0 of the sample streams."""
-        if self.noise_field is not None:
-            return self._field(shape, 0, dev)
-        if streams is None:
-            return self._draw(shape, dev)
-        return engine.randn_samples(shape, streams[0], streams[1], draw=0, device=dev)
+    def _repeated(self, x_in):
+        return torch.cat([x_in.float()] * self._copies(x_in), dim=1)   # indi.py:80
+
+    def _perturbed(self, x, d0, t_starts):
+        """``x + d0 * e * t``, t the one start time or one per sample: get_t_times_e (indi.py:106-110), indi.py:82."""
+        scale = torch.stack([self.e * torch.Tensor([t]) for t in t_starts]).to(x.device).view(-1, 1, 1, 1)
+        return x + d0 * scale
 
     def _start(self, x_in, t_float_start, streams=None):
-        dev = x_in.device
-        x_in = torch.cat([x_in.float()] * self._copies(x_in), dim=1)   # indi.py:80
-        scale = (self.e * torch.Tensor([t_float_start])).to(dev)     # get_t_times_e, indi.py:106-110
-        return x_in + self._draw0(x_in.shape, dev, streams) * scale  # indi.py:82
+        """What ``inference`` starts from, for a caller that drives the steps itself: the input repeated to
+        ``out_channel`` channels and perturbed by draw 0.  ``streams``: ``(seed, sample_ids)`` or None."""
+        x = self._repeated(x_in)
+        draws = self._draws(x.shape[0], *(streams or (None, None)))
+        return self._perturbed(x, draws.initial(x.shape, x.device), [t_float_start])
 
     @staticmethod
     def _per_sample_t(t_float_start, batch):
@@ -762,71 +669,43 @@ class InDISampler(_SamplerBase):
             raise DsxError(f"t_float_start has {len(t)} entries for a batch of {batch}")
         return t
 
-    @torch.no_grad()
-    def _inference_per_sample(self, x_in, t_list, continuous, num_timesteps, stream, streams=None):
-        """One start time per batch element, one batched loop (per-sample step tables).  Equivalent to calling
-        ``inference`` on every sample alone, as core/psnr_based_t_refinement.py:26-34 does; with a ``noise_source``
-        the draws are taken sample by sample in that order (start draw, then one draw per step)."""
-        dev = x_in.device
-        B = x_in.shape[0]
-        xr = torch.cat([x_in.float()] * self._copies(x_in), dim=1)
-        noise = None
-        if self.noise_field is not None:                              # whole-batch draws by ordinal
-            d0 = self._draw0(xr.shape, dev, streams)
-            noise = self._field_noise(xr.shape, num_timesteps, range(num_timesteps), dev)
-        elif self.noise_source is not None:
-            starts, steps = [], []
-            for b in range(B):
-                starts.append(self._draw((1,) + tuple(xr.shape[1:]), dev))
-                steps.append(torch.cat([self._draw((1,) + tuple(xr.shape[1:]), dev) for _ in range(num_timesteps)]))
-            d0 = torch.cat(starts)
-            noise = torch.stack(steps, dim=1).contiguous()            # (n, B, C, H, W)
-        else:
-            d0 = self._draw0(xr.shape, dev, streams)
-        scale = torch.stack([(self.e * torch.Tensor([t])) for t in t_list]).to(dev).view(B, 1, 1, 1)
-        x_t = xr + d0 * scale
-        table = engine.indi_step_table_per_sample(num_timesteps, t_list, self.e)
-        return self._loop(table, x_t, noise, continuous, num_timesteps, stream, streams)
+    def noise_rows(self, n_steps):
+        """The rows of a loop that add noise: every one (indi.py:62-69 draws on each step)."""
+        return range(n_steps)
 
-    def _loop(self, table, x_t, noise, continuous, num_timesteps, stream, streams=None):
-        """The engine's loop from ``x_t`` (updated in place: ``first`` keeps the start) and what inference returns."""
-        snaps = engine.indi_snapshot_steps(num_timesteps) if continuous else []
+    @torch.no_grad()
+    def inference(self, x_in, continuous=False, num_timesteps=None, t_float_start=1.0, eps=1e-8,
+                  stream=None, seed=None, sample_ids=None):
+        """``seed`` / ``sample_ids``: per-sample noise streams -- the start perturbation is draw 0 of every sample's
+        stream, step ``s`` takes draw ``s + 1``; torch's generator is not touched.
+
+        ``t_float_start`` with one start time per batch element runs one batched loop on per-sample step tables:
+        equivalent to calling ``inference`` on every sample alone, as core/psnr_based_t_refinement.py:26-34 does; with a
+        ``noise_source`` the draws are taken sample by sample in that order (start draw, then one draw per step)."""
+        n = self.num_timesteps if num_timesteps is None else num_timesteps
+        assert self.conditional is False
+        self._need_cuda(x_in, what="inference")
+        draws = self._draws(x_in.shape[0], seed, sample_ids)
+        t_list = self._per_sample_t(t_float_start, x_in.shape[0])
+        x = self._repeated(x_in)
+        if t_list is None:
+            d0, loop_kw = draws.initial(x.shape, x.device), draws.loop(x.shape, n, self.noise_rows(n), x.device)
+            table = engine.indi_step_table(n, t_float_start, self.e)   # no drift assert (R3)
+        else:                                                        # two tables: they select different captured steps
+            d0, loop_kw = draws.per_sample(x.shape, n, x.device)
+            table = engine.indi_step_table_per_sample(n, t_list, self.e)
+        x_t = self._perturbed(x, d0, t_list or [t_float_start])
+        # the engine's loop updates x_t in place: `first` keeps the start
+        snaps = engine.indi_snapshot_steps(n) if continuous else []
         first = x_t.clone() if continuous else None
-        skw = dict(seed=self._loop_seed()) if streams is None else dict(seed=streams[0], sample_ids=streams[1])
-        x, sn = self.denoise_fn.engine().sample_loop(table, x_t, noise=noise, snapshot_steps=snaps,
-                                                     use_graph=self.use_graph, stream=stream, **skw)
+        x, sn = self.denoise_fn.engine().sample_loop(table, x_t, snapshot_steps=snaps, use_graph=self.use_graph,
+                                                     stream=stream, **loop_kw)
         self.last_full_batch = x
         if continuous:
             if stream is not None:
                 stream.synchronize()
             return torch.cat([first] + [s for s in sn], dim=0)
         return x[-1:]                                                # indi.py:92-95: ret_img[-1:]
-
-    def _noise(self, shape, n, dev):
-        if self.noise_field is not None:
-            return self._field_noise(shape, n, range(n), dev)
-        if self.noise_source is None:
-            return None
-        return torch.stack([self._draw(shape, dev) for _ in range(n)])  # drawn on every step (Q4)
-
-    @torch.no_grad()
-    def inference(self, x_in, continuous=False, num_timesteps=None, t_float_start=1.0, eps=1e-8,
-                  stream=None, seed=None, sample_ids=None):
-        """``seed`` / ``sample_ids``: per-sample noise streams -- the start perturbation is draw 0 of every sample's
-        stream, step ``s`` takes draw ``s + 1``; torch's generator is not touched."""
-        if num_timesteps is None:
-            num_timesteps = self.num_timesteps
-        assert self.conditional is False
-        self._need_cuda(x_in, what="inference")
-        self._uses_field(sample_ids)
-        streams = self._stream_args(seed, sample_ids, x_in.shape[0])
-        t_list = self._per_sample_t(t_float_start, x_in.shape[0])
-        if t_list is not None:
-            return self._inference_per_sample(x_in, t_list, continuous, num_timesteps, stream, streams)
-        x_t = self._start(x_in, t_float_start, streams)
-        noise = self._noise(x_t.shape, num_timesteps, x_t.device)
-        table = engine.indi_step_table(num_timesteps, t_float_start, self.e)   # no drift assert (R3)
-        return self._loop(table, x_t, noise, continuous, num_timesteps, stream, streams)
 
 
 class IndiCustomT(InDISampler):
@@ -934,7 +813,9 @@ class JointIndiSampler(_SamplerBase):
         ids with bit 39 set.  ``noise_field`` here is a callable ``(shape, draw, id_bit)``: indi1 asks with
         ``id_bit = 0``, indi2 with ``STREAM2_BIT``, which the provider adds to its field ids -- the two channels never
         share a draw."""
-        field = self.noise_field if self._uses_field(sample_ids) else None
+        # the children build the Draws of their own calls; the field's refusals are made here, before they are set up
+        Draws.refuse_field_with(self.noise_source, self.noise_field, sample_ids)
+        field = self.noise_field
         for s, bit in ((self.indi1, 0), (self.indi2, self.STREAM2_BIT)):
             s.noise_source, s.use_graph = self.noise_source, self.use_graph   # indi1's draws first (Q4)
             s.noise_field = None if field is None else (lambda shape, draw, bit=bit: field(shape, draw, bit))

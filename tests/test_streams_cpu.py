@@ -119,16 +119,16 @@ def test_sampler_refusals_without_a_device():
     from diffsplitting_amd._lib import DsxError
     from diffsplitting_amd.model import samplers as S
     s = S.InDISampler(None, 32, channels=2, conditional=False)
-    assert s._stream_args(None, None, 2) is None
+    assert s._draws(2, None, None).streams is None
     with pytest.raises(DsxError, match="only together with sample_ids"):
-        s._stream_args(3, None, 2)
+        s._draws(2, 3, None)
     with pytest.raises(DsxError, match="need seed"):
-        s._stream_args(None, [1, 2], 2)
+        s._draws(2, None, [1, 2])
     s.noise_source = lambda shape: None
     with pytest.raises(DsxError, match="noise_source together with sample_ids"):
-        s._stream_args(3, [1, 2], 2)
+        s._draws(2, 3, [1, 2])
     s.noise_source = None
-    assert s._stream_args(3, [5, 9], 2) == (3, [5, 9])
+    assert s._draws(2, 3, [5, 9]).streams == (3, [5, 9])
     j = S.JointIndiSampler.__new__(S.JointIndiSampler)
     assert j.second_ids([1, 2]) == [1 | 1 << 39, 2 | 1 << 39]
     with pytest.raises(DsxError, match=r"2\^39"):
