@@ -198,6 +198,8 @@ SIGNATURES = {
     "dsx_order_stats": (_i, [_Df, _Df, _i64, C.c_double, C.c_double, _pi64, _i, C.POINTER(C.c_double), _Dv, _st]),
     "dsx_comoments_blocks": (_i, [_i64]),
     "dsx_comoments": (_i, [_Df, _Df, _Df, _i64, _i64, _pi64, _Dd, _Dd, _st]),
+    "dsx_calibration_blocks": (_i, [_i64]),
+    "dsx_calibration": (_i, [_Df, _Df, _Df, _i64, _i, _H, _i, _H, _i, _Dd, _Dd, _st]),
 }
 
 if not os.path.exists(LIB_PATH):

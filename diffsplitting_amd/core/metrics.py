@@ -274,3 +274,22 @@ def calculate_msssim(target_stitched, pred_stitched, weights=MSSSIM_WEIGHTS):
         dev, torch.float32).permute(0, 3, 1, 2).contiguous()
     value = msssim(up(pred_stitched), up(target_stitched), range_invariant=True, weights=weights)
     return {ch: value[:, ch].tolist() for ch in range(Cn)}
+
+
+def calculate_calibration(gt_frames, mean, std, bins=30, z=(1, 2, 3), edges=None):
+    """The calibration curve of a predicted spread (core/calibration.py), the face beside ``calculate_msssim``:
+    ``gt_frames``, ``mean`` and ``std`` are (N, H, W, C) channel-last frames, numpy or CUDA, in ONE normalisation (the
+    stitched canvases of ``predict_stack(..., samples=N, return_std=True)`` against
+    ``val_set.normalized_target_frames()``).  Returns ``calibration_stats``' object: per channel the equal-count bins
+    of ``std`` with their rmv and rmse, and the coverage of the intervals ``mean +- z std``.  numpy input is uploaded
+    once."""
+    from .calibration import calibration_stats
+    shapes = [tuple(x.shape) for x in (gt_frames, mean, std)]
+    if len(set(shapes)) != 1 or len(shapes[0]) != 4:
+        raise ValueError(f"gt_frames, mean and std must be (N, H, W, C) of one shape, got {shapes}")
+    _lib.require_gpu()
+    dev = next((t.device for t in (gt_frames, mean, std) if torch.is_tensor(t) and t.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+    up = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))).to(
+        dev, torch.float32).contiguous()
+    return calibration_stats(up(mean), up(std), up(gt_frames), bins=bins, z=z, edges=edges)

@@ -799,6 +799,25 @@ int comoments_blocks(long long n);
 long long comoments_span(long long n);
 hipError_t launch_comoments(const ComArgs& a, int planes, bool vec, hipStream_t st);
 
+// dsx_calib.hip.  The calibration sums of channel-last canvases (mean, std, target), n pixels of C interleaved fp32
+// channels (include/dsx.h, dsx_calibration): one pass, two launches on `st`, nothing synchronised.  A row, of a
+// workgroup's partials and of out alike, is [C][3 * nbins + nz] doubles: per channel nbins x {count, Sv, Se}, then nz
+// coverage counts; part[calibration_blocks(n)][row].  edges[c * (nbins - 1) + j] and z[] travel in the argument struct.
+// vec: 16-byte loads (the three bases 16-byte aligned and n * C % 4 == 0: the caller's check).
+constexpr int kCalMaxC = 4, kCalMaxBins = 64, kCalMaxZ = 8;
+struct CalArgs {
+  const float* mean; const float* sd; const float* target;
+  long long elems, span;   // elems = n * C values; span = C * calibration_span(n): values per workgroup, a multiple of 4
+  int C, nbins, nz;
+  double* part; double* out;
+  double edges[kCalMaxC * (kCalMaxBins - 1)];
+  double z[kCalMaxZ];
+};
+inline int calibration_row(int C, int nbins, int nz) { return C * (3 * nbins + nz); }
+int calibration_blocks(long long n);
+long long calibration_span(long long n);
+hipError_t launch_calibration(const CalArgs& a, bool vec, hipStream_t st);
+
 // dsx_select.hip.  One pass of the radix select behind dsx_order_stats: hist[1 << bits] (64-bit, zeroed by the caller)
 // += the digit (u >> shift) & (2^bits - 1) of every element whose key image u has u >> match_shift == prefix
 // (match_shift = 64: every element).  b == nullptr: single source.

@@ -9,7 +9,7 @@
 //   butterfly  kDown  offsets 32, 16, .. 1   every kernel but k_lpips_dist
 //              kUp    offsets 1, 2, .. 32    k_lpips_dist (its two fp32 norms and its double accumulator)
 //   combine    Pairwise  (r0 + r1) + (r2 + r3)   k_loss_partial, k_image_metrics, k_mix_range, k_lpips_minmax,
-//                                                k_msssim_scale, k_msssim_finish, every RedRow
+//                                                k_msssim_scale, k_msssim_finish, every RedRow, k_calib_partial
 //              Serial    ((r0 + r1) + r2) + r3   k_masked_mean, k_lpips_dist, val_block_reduce
 // (min, max and integer sums do not depend on either; k_mix_range, k_lpips_minmax and val_block_reduce are listed for
 // completeness.)  The rows, RedRow<sums, (min, max) pairs>, all kDown and Pairwise:
@@ -18,6 +18,9 @@
 //   RedRow<9, 1>  k_comoments_partial (dsx_refine.hip): nine sums of shifted data, min / max of g
 // k_comoments_finish then folds a plane's workgroup rows with ONE wave: lane l adds the rows l, l + 64, .. in ascending
 // order, wave_reduce (kDown) folds the lanes.
+// k_calib_partial (dsx_calib.hip) reduces no lanes with a butterfly: a bin's terms meet in the wave's row of LDS in
+// ascending lane order, batch after batch; its four wave rows then combine Pairwise (block_combine per slot), and
+// k_calib_finish folds the workgroup rows of a slot as k_comoments_finish does (rows l, l + 64, .. per lane, then kDown).
 //
 // Use.  One value:      r = block_reduce<RedSum, Pairwise>(v, red)          red: 4 elements of LDS, r in every thread
 //       several values: block_park<Op>(v_j, red, n, j) for each slot j < n    red: 4 * n elements, [wave][slot]

@@ -61,6 +61,12 @@ the tiles' UNet outputs and applies the InDI update with the frame's noise field
 ``--ms-ssim`` also scores the stitched prediction with the range-invariant multi-scale SSIM
 (``core.metrics.calculate_msssim``, five scales): rank 0 logs mean +- standard error over the frames per channel.  It
 needs a ground truth (not with ``--input``, ``--validate`` or colour items) and frames of 176 x 176 or more.
+
+``--calibration FILE [--calibration-bins K]`` (with ``--samples N``, N >= 2, and a ground truth) asks whether the spread
+tracks the real error (``core/calibration.py``): rank 0 bins the pixels of the stitched canvases by predicted std, logs
+per channel the scale, the line ``rmse ~ a rmv + c`` and the coverage at z = 1, 2, 3, and writes curve and fit to FILE.
+``--apply-calibration FILE`` (with ``--std-out``) writes ``a std + c`` (clamped at 0) instead of the raw spread, for a
+stack without ground truth (``--input``); the file must hold the prediction's channel count and ``--samples``.
 """
 import argparse
 import functools
@@ -272,9 +278,16 @@ def main(argv=None):
     ap.add_argument("--ms-ssim", action="store_true",
                     help="also score the stitched prediction with the range-invariant multi-scale SSIM "
                          "(core.metrics.calculate_msssim: five scales, frames of 176 x 176 or more)")
+    ap.add_argument("--calibration", type=str, default=None,
+                    help="with --samples N >= 2 and ground truth: score the spread against the real error "
+                         "(core.calibration: RMV-RMSE bins, line fit, coverage) and write the calibration to this JSON file")
+    ap.add_argument("--calibration-bins", type=int, default=None, help="with --calibration: equal-count bins (default 30)")
+    ap.add_argument("--apply-calibration", type=str, default=None,
+                    help="with --std-out: write the spread recalibrated by this file (a std + c per channel)")
     args = ap.parse_args(argv)
     config = _config_once(args.config)
     _check_msssim_args(args, config)
+    _check_calibration_args(args, config)
     _check_solver_args(args, config)
     _check_stitch_args(args, len(str(args.gpu_ids).split(",")) if args.gpus is None else args.gpus)
     _check_frame_args(args, config)
@@ -413,11 +426,11 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     if args.frame_steps:
         from .data.tiled_predict import predict_stack_frames
         out, plan = predict_stack_frames(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps,
-                                         samples=samples, return_std=bool(args.std_out), seed=args.sample_seed,
-                                         window=args.window or "triangle")
+                                         samples=samples, return_std=bool(args.std_out or args.calibration),
+                                         seed=args.sample_seed, window=args.window or "triangle")
     else:
         out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
-                                  return_std=bool(args.std_out), seed=args.sample_seed, solver=solver,
+                                  return_std=bool(args.std_out or args.calibration), seed=args.sample_seed, solver=solver,
                                   noise="field" if args.noise_field else "samples", stitch=args.stitch,
                                   window=args.window or "triangle", fuse=args.fuse_steps)
     pred, ps = out["mean"], out.get("psnr")
@@ -434,11 +447,17 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
                          "was given in path.resume_state)", c, ps[:, c].mean().item(),
                          ps[:, c].std().item() if ps.shape[0] > 1 else 0.0)
         _log_msssim(args, val_set, pred, ps, log)
+        _log_calibration(args, val_set, pred, out.get("std"), ps, samples, log)
         if args.out:
             _write_prediction(args.out, pred, val_set)
             log.info("prediction written to %s", args.out)
         if args.std_out:
-            _write_prediction(args.std_out, out["std"], val_set, spread=True)
+            spread = out["std"]
+            if args.apply_calibration:
+                from .core.calibration import Calibration
+                spread = Calibration.load(args.apply_calibration).apply(spread)
+                log.info("spread recalibrated by %s", args.apply_calibration)
+            _write_prediction(args.std_out, spread, val_set, spread=True)
             log.info("spread over %d samples written to %s", samples, args.std_out)
     return pred
 
@@ -483,6 +502,63 @@ def _log_msssim(args, val_set, pred, ps, log):
         v = np.asarray(vals, np.float64)
         sem = float(v.std(ddof=1) / np.sqrt(v.size)) if v.size > 1 else 0.0
         log.info("channel %d: MS-SSIM (range-invariant) %.6f +- %.6f over %d frames", c, float(v.mean()), sem, v.size)
+
+
+def _check_calibration_args(args, config):
+    """``--calibration`` / ``--apply-calibration``, checked on the command line, the config and the calibration file alone
+    (nothing touches the GPU, no rank is started).  Without them: nothing."""
+    if args.calibration_bins is not None and not args.calibration:
+        raise SystemExit("--calibration-bins: only with --calibration FILE")
+    if args.calibration:
+        if args.input:
+            raise SystemExit("--calibration with --input: an input-only stack has no ground truth to score the spread "
+                             "against; fit the calibration on a stack with ground truth and use --apply-calibration here")
+        if args.validate:
+            raise SystemExit("--calibration scores the spread of a tiled prediction: not with --validate")
+        if args.mix_t is not None:
+            raise SystemExit("--calibration: not with --mix-t; the mixed-input prediction has no posterior spread")
+        if (args.samples or 1) < 2:
+            raise SystemExit("--calibration: the spread needs --samples 2 or more (--samples 1 has none)")
+        if args.datapath and _data_type(config()[1], args.norm_from) == "cifar10":
+            raise SystemExit("--calibration scores the stitched frames of a tiled prediction: the colour items of a "
+                             "cifar10 config are not tiled")
+        from .core.calibration import MAX_BINS
+        if args.calibration_bins is not None and not 2 <= args.calibration_bins <= MAX_BINS:
+            raise SystemExit(f"--calibration-bins {args.calibration_bins}: 2..{MAX_BINS} equal-count bins")
+    if args.apply_calibration:
+        if not args.std_out:
+            raise SystemExit("--apply-calibration recalibrates the spread that --std-out writes: give --std-out FILE")
+        from .core.calibration import Calibration
+        try:
+            cal = Calibration.load(args.apply_calibration)
+        except (DsxError, OSError) as e:
+            raise SystemExit(f"--apply-calibration {args.apply_calibration}: {e}")
+        channels = 2 if config()[1].get("target_channel_idx") is None else 1
+        if cal.channels != channels:
+            raise SystemExit(f"--apply-calibration {args.apply_calibration}: a calibration of {cal.channels} channels, the "
+                             f"prediction has {channels}")
+        if cal.samples != (args.samples or 1):
+            raise SystemExit(f"--apply-calibration {args.apply_calibration}: fitted at --samples {cal.samples}, this run "
+                             f"draws {args.samples or 1}; the error of an N-sample mean depends on N")
+
+
+def _log_calibration(args, val_set, pred, std, ps, samples, log):
+    """``--calibration`` on rank 0: the gathered canvases against the normalised ground truth, one line per channel, the
+    curve and its fit to the file."""
+    if not args.calibration:
+        return
+    if ps is None:
+        raise DsxError("--calibration: the dataset holds no target with the prediction's channels to score against")
+    from .core.calibration import Calibration
+    from .core.metrics import calculate_calibration
+    stats = calculate_calibration(val_set.normalized_target_frames(), pred, std, bins=args.calibration_bins or 30)
+    cal = Calibration.from_stats(stats, samples, _target_stats(val_set, pred.shape[-1])[1])
+    for c in range(cal.channels):
+        log.info("channel %d: calibration scale %.4f, rmse ~ %.4f rmv %+.4g; coverage at z = 1, 2, 3: %.4f %.4f %.4f "
+                 "(%d bins, %d pixels)", c, cal.scale[c], cal.a[c], cal.c[c], *stats.coverage[c], stats.count.shape[1],
+                 stats.n)
+    cal.save(args.calibration)
+    log.info("calibration over %d samples written to %s", samples, args.calibration)
 
 
 def _check_input_args(args, config):

@@ -920,6 +920,40 @@ int dsx_comoments_blocks(int64_t n);
 int dsx_comoments(const float* g_dev, const float* p1_dev, const float* p2_dev, int64_t planes, int64_t n,
                   const int64_t strides[6], double* partial_dev, double* out_dev, void* stream);
 
+/* ------------------------------------------------- calibrating the posterior spread: RMV-RMSE bins, coverage
+ * Does a predicted per-pixel standard deviation track the real error?  The pixels of every channel are binned by their
+ * predicted std, and per bin the sum of the predicted variances stands beside the sum of the squared errors; the
+ * curve rmv_b = sqrt(Sv_b / count_b) against rmse_b = sqrt(Se_b / count_b), its fit and the interval coverage are the
+ * caller's (core/calibration.py).  mean, std and target are channel-last canvases as predict_stack returns them:
+ * n pixels of C interleaved fp32 channels ((N, H, W, C), n = N H W), read in place, once.  Per channel c and pixel i,
+ * everything in double:
+ *   s   = (double)std[i][c]
+ *   e   = (double)target[i][c] - (double)mean[i][c]                 one rounding
+ *   bin = #{ j : edges[c][j] <= s }                                 np.searchsorted(edges[c], s, side='right'), 0..nbins-1
+ *   count[c][bin] += 1;   Sv[c][bin] += s * s;   Se[c][bin] += e * e
+ *   cover[c][k]  += (s >= 0 && fabs(e) <= z[k] * s)   for k < nz    the product rounded once
+ * edges_host = [C][nbins - 1], ascending per channel (ties allowed); z_host = [nz].  Both travel in the kernel-argument
+ * struct, hence nbins <= 64 and nz <= 8.  out_dev receives C rows of 3 * nbins + nz doubles:
+ *   {count, Sv, Se} of bin 0, .. of bin nbins - 1, then cover[0 .. nz - 1]
+ * The contract: counts and coverage are exact integers (n <= 2^40), equal to a float64 numpy restatement; Sv and Se
+ * lie within (k + 4) 2^-53 of the exactly rounded sum of the exactly formed terms, relative to it, k = the bin's count
+ * (tests/calibration_ref.py derives it); a call's bits are the same run to run and on either load path (16-byte loads
+ * when the three bases are 16-byte aligned and n C % 4 == 0; 4-byte loads otherwise).  The canvases are cut into
+ * dsx_calibration_blocks(n) workgroups, a function of n alone, each thread takes fixed values in a fixed order, and
+ * there is no floating-point atomic: a bin's terms meet in the wave's row of LDS, in ascending lane order or, where more
+ * than 8 of a wave's 64 values share a bin, folded by one shuffle butterfly (csrc/dsx_calib.hip: the values alone
+ * decide), the four waves pairwise, the workgroups' rows in ascending order.  Inputs are assumed finite.
+ * A negative std is binned by its value and never counts as covered (not even z = 0 with e = 0).
+ * partial_dev holds dsx_calibration_blocks(n) * C * (3 * nbins + nz) doubles.  Two launches on `stream`; the call does
+ * not synchronise, allocate or copy.
+ * DSX_ERR_INVALID with a message, before any device work: a NULL pointer (edges_host may be NULL when nbins == 1,
+ * z_host when nz == 0), n outside 1..2^40, C outside 1..4, nbins outside 1..64, nz outside 0..8, an edge that is not
+ * finite, edges that descend, a z that is not finite or negative. */
+int dsx_calibration_blocks(int64_t n);
+int dsx_calibration(const float* mean_dev, const float* std_dev, const float* target_dev, int64_t n, int C,
+                    const double* edges_host, int nbins, const double* z_host, int nz, double* partial_dev, double* out_dev,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
