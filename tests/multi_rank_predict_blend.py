@@ -14,15 +14,14 @@ BATCH = 5
 
 
 def main():
-    from diffsplitting_amd import parallel
     from diffsplitting_amd.data.tiled_predict import predict_stack
     from tests import blend_ref
-    from tests import test_gpu_field as T
-    import torch.distributed as dist
-    torch.set_grad_enabled(False)
-    rank, world = parallel.init(os.environ.get("DSX_DIST_BACKEND") or "nccl")   # (sets the rank's device)
-    smp = T._sr3()
-    stack = T._stack((2, 64, 96), 32, 16, seed=4)
+    from tests import tiled_util as T
+    from tests.bits import same_bits
+    from tests.rank_worker import finish, start
+    rank, world = start()
+    smp = T.sr3()
+    stack = T.stack((2, 64, 96), 32, 16, seed=4)
     plan = stack.plan
     assert plan.total == 30 and plan.total % (BATCH * world) == 0    # every batch is full on every rank
     solver = T.SOLVERS["dpmpp2m"]
@@ -30,21 +29,14 @@ def main():
     tiles = {}
     for i in reversed(range(0, plan.total, BATCH)):
         chunk = list(range(i, i + BATCH))
-        tiles[i] = T._run(smp, stack.tiles(chunk)["input"], solver, seed=T.SEED, sample_ids=chunk)
+        tiles[i] = T.run(smp, stack.tiles(chunk)["input"], solver, seed=T.SEED, sample_ids=chunk)
     tiles = torch.cat([tiles[i] for i in sorted(tiles)])
     want = torch.from_numpy(blend_ref.blend_ref(plan, tiles.cpu().numpy(), *blend_ref.window_pair(plan, "hann")))
-    same = T.same_bits(got["mean"].cpu(), want)
+    same = same_bits(got["mean"].cpu(), want)
     differs = not torch.equal(plan.stitch(tiles).cpu(), want)
     ok = same and differs
-    flag = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-    if not ok:
-        print(f"rank {rank}: blend equal {same}, crop differs {differs}", file=sys.stderr)
-    if rank == 0:
-        print("PREDICT_BLEND_OK" if int(flag.item()) == 1 else "PREDICT_BLEND_MISMATCH", plan.total, world)
-    dist.barrier()
-    dist.destroy_process_group()
-    sys.exit(0 if int(flag.item()) == 1 else 1)
+    finish(ok, "PREDICT_BLEND", plan.total, world,
+           detail=f"blend equal {same}, crop differs {differs}")
 
 
 if __name__ == "__main__":

@@ -14,32 +14,24 @@ BATCH = 5
 
 
 def main():
-    from diffsplitting_amd import parallel
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    from tests import test_gpu_field as T
-    import torch.distributed as dist
-    torch.set_grad_enabled(False)
-    rank, world = parallel.init(os.environ.get("DSX_DIST_BACKEND") or "nccl")   # (sets the rank's device)
-    smp = T._sr3()
-    stack = T._stack((2, 64, 96), 32, 16, seed=4)
+    from tests import tiled_util as T
+    from tests.bits import same_bits
+    from tests.rank_worker import finish, start
+    rank, world = start()
+    smp = T.sr3()
+    stack = T.stack((2, 64, 96), 32, 16, seed=4)
     plan = stack.plan
     assert plan.total == 30 and plan.total % (BATCH * world) == 0    # every batch is full on every rank
     solver = T.SOLVERS["ddim"]
     got, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=T.SEED, noise="field")
-    want = plan.stitch(T._restated_field(smp, stack, solver, BATCH))
-    same = T.same_bits(got["mean"], want)
+    want = plan.stitch(T.restated_field(smp, stack, solver, BATCH))
+    same = same_bits(got["mean"], want)
     streams, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=T.SEED)
     differs = not torch.equal(streams["mean"], want)
     ok = same and differs
-    flag = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-    if not ok:
-        print(f"rank {rank}: field equal {same}, streams differ {differs}", file=sys.stderr)
-    if rank == 0:
-        print("PREDICT_FIELD_OK" if int(flag.item()) == 1 else "PREDICT_FIELD_MISMATCH", plan.total, world)
-    dist.barrier()
-    dist.destroy_process_group()
-    sys.exit(0 if int(flag.item()) == 1 else 1)
+    finish(ok, "PREDICT_FIELD", plan.total, world,
+           detail=f"field equal {same}, streams differ {differs}")
 
 
 if __name__ == "__main__":

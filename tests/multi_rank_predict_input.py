@@ -14,19 +14,17 @@ SEED = 11
 
 
 def main():
-    from diffsplitting_amd import engine, parallel
+    from diffsplitting_amd import engine
     from diffsplitting_amd.data.input_stack import InputStackTiledPred
     from diffsplitting_amd.data.tiled_predict import predict_stack
     from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
+    from tests import nets
+    from tests.bits import same_bits
+    from tests.rank_worker import finish, start
     from tests.util import golden_state_dict
-    import torch.distributed as dist
-    torch.set_grad_enabled(False)
-    rank, world = parallel.init(os.environ.get("DSX_DIST_BACKEND") or "nccl")   # (sets the rank's device)
+    rank, world = start()
     sd, _ = golden_state_dict("unet_hagen_64")
-    sec = _tiny_indi_section()
-    sec["unet"]["channel_multiplier"] = [1, 2, 4, 8]
-    netG = networks.define_G(_opt(sec)).cuda()
+    netG = networks.define_G(nets.opt(nets.hagen64_section())).cuda()
     netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()})
     assert netG.e == 0.01                                          # the sampler's own noise scale: the draws matter
     s = np.random.default_rng(5).integers(0, 6000, (3, 96, 160)).astype(np.uint16)
@@ -51,20 +49,12 @@ def main():
         stds.append(sd_)
     want_mean, want_std = plan.stitch(torch.cat(means)), plan.stitch(torch.cat(stds))
 
-    bits = lambda t: t.contiguous().view(torch.int32)
-    same_mean = torch.equal(bits(got["mean"]), bits(want_mean))
-    same_std = torch.equal(bits(got["std"]), bits(want_std))
+    same_mean = same_bits(got["mean"], want_mean)
+    same_std = same_bits(got["std"], want_std)
     spread = bool((got["std"] > 0).any())                          # the two samples do differ: the comparison can fail
     ok = same_mean and same_std and spread
-    flag = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-    if not ok:
-        print(f"rank {rank}: mean equal {same_mean}, std equal {same_std}, spread {spread}", file=sys.stderr)
-    if rank == 0:
-        print("PREDICT_INPUT_OK" if int(flag.item()) == 1 else "PREDICT_INPUT_MISMATCH", plan.total, world)
-    dist.barrier()
-    dist.destroy_process_group()
-    sys.exit(0 if int(flag.item()) == 1 else 1)
+    finish(ok, "PREDICT_INPUT", plan.total, world,
+           detail=f"mean equal {same_mean}, std equal {same_std}, spread {spread}")
 
 
 if __name__ == "__main__":

@@ -13,15 +13,14 @@ sys.path.insert(0, ROOT)
 
 
 def main():
-    import torch.distributed as dist
     from diffsplitting_amd import parallel
     from diffsplitting_amd.data.tiled_predict import gather_pred_t, predict_tiled_mixed
     from diffsplitting_amd.data.time_predictor_dataset import compute_input_normalization_dict
-    from tests.test_gpu_mixed import _dataset, _networks
-    torch.set_grad_enabled(False)
-    rank, world = parallel.init(os.environ.get("DSX_DIST_BACKEND") or "nccl")   # (sets the rank's device)
-    i1, i2, tp, _, _ = _networks(1)
-    ds, _, _ = _dataset((2, 64, 64), 5)                              # patch 32, grid 16: 18 tiles
+    from tests.mixed_util import dataset, networks
+    from tests.rank_worker import finish, start
+    rank, world = start()
+    i1, i2, tp, _, _ = networks(1)
+    ds, _, _ = dataset((2, 64, 64), 5)                              # patch 32, grid 16: 18 tiles
     total = len(ds)
     netG = types.SimpleNamespace(indi1=i1, indi2=i2, noise_source=None)
     table = compute_input_normalization_dict(ds._data_dict, 100, ds._mean_target, ds._std_target)
@@ -56,15 +55,7 @@ def main():
               "one rank is complete": bool(torch.isfinite(pred_t1).all()),
               "gathered": bool(torch.isfinite(full_t).all()) and torch.equal(full_t, pred_t1)}
     ok = world == 2 and all(checks.values())
-    if not ok:
-        print(f"[rank {rank}] {checks}", file=sys.stderr)
-    flag = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-    if rank == 0:
-        print("PREDICT_MIXED_OK" if int(flag.item()) == 1 else "PREDICT_MIXED_MISMATCH", total, world)
-    dist.barrier()
-    dist.destroy_process_group()
-    sys.exit(0 if int(flag.item()) == 1 else 1)
+    finish(ok, "PREDICT_MIXED", total, world, detail=checks)
 
 
 if __name__ == "__main__":

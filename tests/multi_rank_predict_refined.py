@@ -16,15 +16,15 @@ sys.path.insert(0, ROOT)
 
 
 def main():
-    import torch.distributed as dist
     from diffsplitting_amd import parallel
     from diffsplitting_amd.data.tiled_predict import predict_tiled_refined
     from diffsplitting_amd.data.time_predictor_dataset import compute_input_normalization_dict
-    from tests.test_gpu_mixed import _dataset, _networks
-    torch.set_grad_enabled(False)
-    rank, world = parallel.init(os.environ.get("DSX_DIST_BACKEND") or "nccl")   # (sets the rank's device)
-    i1, i2, tp, _, _ = _networks(1)
-    ds, _, _ = _dataset((2, 64, 64), 5)                              # patch 32, grid 16: 18 tiles
+    from tests.bits import same_bits
+    from tests.mixed_util import dataset, networks
+    from tests.rank_worker import finish, start
+    rank, world = start()
+    i1, i2, tp, _, _ = networks(1)
+    ds, _, _ = dataset((2, 64, 64), 5)                              # patch 32, grid 16: 18 tiles
     total = len(ds)
     netG = types.SimpleNamespace(indi1=i1, indi2=i2, noise_source=None,
                                  second_ids=lambda ids: [int(v) | (1 << 39) for v in ids])
@@ -41,24 +41,15 @@ def main():
         (canvas1, psnr1), pred_t1, rep1 = run()
     finally:
         parallel.rank, parallel.world_size = saved
-    same = lambda a, b: a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-    checks = {"canvas": torch.equal(canvas.view(torch.int32), canvas1.view(torch.int32)),
+    checks = {"canvas": same_bits(canvas, canvas1),
               "psnr": torch.equal(psnr, psnr1), "pred_t": torch.equal(pred_t, pred_t1),
               "complete": bool(torch.isfinite(pred_t).all()), "rounds": len(rep["rounds"]) == len(rep1["rounds"]) == 2}
     for q, (a, b) in enumerate(zip(rep["rounds"], rep1["rounds"])):
         for key in ("start", "moments", "curves", "t_star", "chosen", "mean_curves"):
-            checks[f"round {q} {key}"] = same(np.ascontiguousarray(a[key]), np.ascontiguousarray(b[key]))
-    checks["round 1 differs from round 0"] = not same(rep["rounds"][0]["moments"], rep["rounds"][1]["moments"])
+            checks[f"round {q} {key}"] = same_bits(np.asarray(a[key]), np.asarray(b[key]))
+    checks["round 1 differs from round 0"] = not same_bits(rep["rounds"][0]["moments"], rep["rounds"][1]["moments"])
     ok = world in (2, 3) and total % (3 * world) == 0 and all(checks.values())
-    if not ok:
-        print(f"[rank {rank}] {checks}", file=sys.stderr)
-    flag = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-    if rank == 0:
-        print("PREDICT_REFINED_OK" if int(flag.item()) == 1 else "PREDICT_REFINED_MISMATCH", total, world)
-    dist.barrier()
-    dist.destroy_process_group()
-    sys.exit(0 if int(flag.item()) == 1 else 1)
+    finish(ok, "PREDICT_REFINED", total, world, detail=checks)
 
 
 if __name__ == "__main__":

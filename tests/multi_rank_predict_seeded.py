@@ -14,18 +14,15 @@ SEED = 11
 
 
 def main():
-    from diffsplitting_amd import parallel
     from diffsplitting_amd.data.tiled_predict import predict_tiled
     from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
+    from tests import nets
+    from tests.bits import same_bits
+    from tests.rank_worker import finish, start
     from tests.util import golden_state_dict
-    import torch.distributed as dist
-    torch.set_grad_enabled(False)
-    rank, world = parallel.init(os.environ.get("DSX_DIST_BACKEND") or "nccl")   # (sets the rank's device)
+    rank, world = start()
     sd, _ = golden_state_dict("unet_hagen_64")
-    sec = _tiny_indi_section()
-    sec["unet"]["channel_multiplier"] = [1, 2, 4, 8]
-    netG = networks.define_G(_opt(sec)).cuda()
+    netG = networks.define_G(nets.opt(nets.hagen64_section())).cuda()
     netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()})
     assert netG.e == 0.01                                          # the sampler's own noise scale: the draws matter
     frames = torch.from_numpy(np.random.default_rng(5).standard_normal((3, 96, 160)).astype(np.float32)).cuda()
@@ -41,25 +38,17 @@ def main():
             outs[i] = netG.last_full_batch.clone()
         return plan.stitch(torch.cat([outs[i] for i in sorted(outs)]))
 
-    bits = lambda t: t.contiguous().view(torch.int32)
     pred, plan = predict_tiled(netG, frames, seed=SEED, **kw)
     assert plan.total == 24 and plan.total % (4 * world) == 0      # every batch is full on every rank
-    same = torch.equal(bits(pred), bits(one_rank_reversed(plan, SEED)))
+    same = same_bits(pred, one_rank_reversed(plan, SEED))
     # without a seed the noise depends on the batching: the same comparison fails
     torch.manual_seed(1)
     plain, _ = predict_tiled(netG, frames, **kw)
     torch.manual_seed(1)
     differs = not torch.equal(plain, one_rank_reversed(plan, None))
     ok = same and differs
-    flag = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
-    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-    if not ok:
-        print(f"rank {rank}: seeded equal {same}, unseeded differs {differs}", file=sys.stderr)
-    if rank == 0:
-        print("PREDICT_SEEDED_OK" if int(flag.item()) == 1 else "PREDICT_SEEDED_MISMATCH", plan.total, world)
-    dist.barrier()
-    dist.destroy_process_group()
-    sys.exit(0 if int(flag.item()) == 1 else 1)
+    finish(ok, "PREDICT_SEEDED", plan.total, world,
+           detail=f"seeded equal {same}, unseeded differs {differs}")
 
 
 if __name__ == "__main__":

@@ -2,7 +2,6 @@
 contract (tests/blend_ref.py) on integer frames (bit for bit the frame) and on random frames (a few ulp), the host
 contributor tables against brute force, every host refusal of dsx_tileplan_set_window / _blend / _gather_canvas with
 fake device pointers, and the refusals of ``predict_stack`` and ``split`` by message, with no rank started."""
-import ctypes as C
 import os
 import re
 
@@ -11,33 +10,17 @@ import pytest
 import torch
 
 from tests import blend_ref
+from tests.host_checks import BLEND_PLANS, ERR_INVALID, FAKE, binding, cpu_samplers, last_error, tile_plan
+from tests.nets import write_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_INVALID = -1
-FAKE = C.c_void_p(4096)
 NEW = {"dsx_tileplan_contributors": 3, "dsx_tileplan_set_window": 3, "dsx_tileplan_blend_blocks": 1,
        "dsx_tileplan_blend": 9, "dsx_tileplan_gather_canvas": 8}
 # (frames, patch, grid): ragged extents with a shifted last row / column, up to 12 contributors, a single tile
-PLANS = [((1, 40, 56), 32, 16), ((1, 37, 50), 24, 8), ((1, 64, 96), 32, 16), ((1, 33, 33), 32, 16), ((1, 45, 70), 30, 10),
-         ((1, 32, 32), 32, 32)]
-
-
-def _lib():
-    from diffsplitting_amd import _lib
-    return _lib
-
-
-def _err():
-    return _lib().lib.dsx_last_error().decode()
-
-
-def _plan(shape, patch, grid):
-    from diffsplitting_amd.data.tiling import TilePlan
-    return TilePlan(shape, (1, grid, grid), (1, patch, patch))
 
 
 def test_the_entry_points_are_declared_bound_and_exported():
-    lib = _lib()
+    lib = binding()
     header = open(os.path.join(ROOT, "include", "dsx.h")).read()
     for name, n in NEW.items():
         assert re.search(rf"\bint {name}\(", header), name
@@ -64,11 +47,11 @@ def test_windows():
         window("hann", 0)
 
 
-@pytest.mark.parametrize("shape,patch,grid", PLANS, ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS, ids=str)
 def test_an_integer_frame_comes_back_bit_for_bit(shape, patch, grid):
     """tiles cut from one frame agree wherever they overlap; with integer values (|v| <= 64) and the integer triangle
     window every product and partial sum is an integer below 2^24, so num = v * den exactly and num / den = v"""
-    plan = _plan(shape, patch, grid)
+    plan = tile_plan(shape, patch, grid)
     rng = np.random.default_rng(5)
     frame = rng.integers(-64, 65, size=plan.data_shape + (2,)).astype(np.float32)
     wy, wx = blend_ref.window_pair(plan, "triangle")
@@ -76,11 +59,11 @@ def test_an_integer_frame_comes_back_bit_for_bit(shape, patch, grid):
     assert got.dtype == np.float32 and np.array_equal(got.view(np.int32), frame.view(np.int32))
 
 
-@pytest.mark.parametrize("shape,patch,grid", PLANS, ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS, ids=str)
 def test_a_random_frame_comes_back_within_a_few_ulp(shape, patch, grid):
     """n contributors: n products and n - 1 sums in num, n - 1 sums in den and one division, each within 2^-24 relative;
     the terms have one sign (w > 0, one v), so nothing cancels: |out - v| <= (2 n + 1) 2^-24 |v|, n <= 12 here"""
-    plan = _plan(shape, patch, grid)
+    plan = tile_plan(shape, patch, grid)
     frame = np.random.default_rng(6).standard_normal(plan.data_shape + (1,)).astype(np.float32)
     tiles = blend_ref.cut_tiles(plan, frame)
     for name in ("triangle", "hann"):
@@ -90,7 +73,7 @@ def test_a_random_frame_comes_back_within_a_few_ulp(shape, patch, grid):
 
 def test_random_tiles_against_float64():
     """independent tiles: the fp32 restatement against the same sums in float64"""
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = tile_plan((2, 40, 57), 16, 8)
     tiles = np.random.default_rng(7).standard_normal((plan.total, 3, 16, 16)).astype(np.float32)
     for name in ("triangle", "hann"):
         wy, wx = blend_ref.window_pair(plan, name)
@@ -98,9 +81,9 @@ def test_random_tiles_against_float64():
         assert np.abs(got - want).max() <= 1e-5
 
 
-@pytest.mark.parametrize("shape,patch,grid", PLANS + [((2, 40, 57), 16, 8)], ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS + [((2, 40, 57), 16, 8)], ids=str)
 def test_contributor_tables(shape, patch, grid):
-    plan = _plan(shape, patch, grid)
+    plan = tile_plan(shape, patch, grid)
     rows, cols = plan.contributors()
     want_rows, want_cols = blend_ref.contributors_brute(plan)
     assert np.array_equal(rows, want_rows) and np.array_equal(cols, want_cols)
@@ -114,75 +97,74 @@ def test_a_plan_that_does_not_cover_its_frames_has_no_tables():
     with pytest.raises(DsxError, match="tileplan_contributors: the plan's tiles do not cover the frames"):
         plan.contributors()
     ones = np.ones(32, dtype=np.float32)
-    assert _lib().lib.dsx_tileplan_set_window(plan.handle, ones, ones) == 0
-    assert _lib().lib.dsx_tileplan_blend(plan.handle, FAKE, 1, 1, 0, FAKE, None, None, None) == ERR_INVALID
-    assert "tileplan_blend: the plan's tiles do not cover the frames" in _err()
+    assert binding().lib.dsx_tileplan_set_window(plan.handle, ones, ones) == 0
+    assert binding().lib.dsx_tileplan_blend(plan.handle, FAKE, 1, 1, 0, FAKE, None, None, None) == ERR_INVALID
+    assert "tileplan_blend: the plan's tiles do not cover the frames" in last_error()
 
 
 # ----------------------------------------------------------------------------- host refusals, no device
 def _blend(h, tiles=FAKE, Cn=1, world=1, stride=0, canvas=FAKE, gt=None, part=None):
-    return _lib().lib.dsx_tileplan_blend(h, tiles, Cn, world, stride, canvas, gt, part, None)
+    return binding().lib.dsx_tileplan_blend(h, tiles, Cn, world, stride, canvas, gt, part, None)
 
 
 def test_blend_refusals():
     from diffsplitting_amd._lib import DsxError
-    lib = _lib().lib
-    plan = _plan((2, 40, 57), 16, 8)
-    assert _blend(plan.handle) == ERR_INVALID and "tileplan_blend: the plan has no window" in _err()
+    lib = binding().lib
+    plan = tile_plan((2, 40, 57), 16, 8)
+    assert _blend(plan.handle) == ERR_INVALID and "tileplan_blend: the plan has no window" in last_error()
     for k, bad in ((3, 0.0), (0, -1.0), (15, float("nan")), (7, float("inf")), (2, float("-inf"))):
         for axis in ("wy", "wx"):
             wy, wx = np.ones(16, dtype=np.float32), np.ones(16, dtype=np.float32)
             (wy if axis == "wy" else wx)[k] = bad
             assert lib.dsx_tileplan_set_window(plan.handle, wy, wx) == ERR_INVALID
-            assert f"tileplan_set_window: {axis}[{k}]" in _err() and "finite and > 0" in _err()
+            assert f"tileplan_set_window: {axis}[{k}]" in last_error() and "finite and > 0" in last_error()
             with pytest.raises(DsxError, match=rf"tileplan_set_window: {axis}\[{k}\]"):
                 plan.set_window((wy, wx))
     assert lib.dsx_tileplan_set_window(plan.handle, None, np.ones(16, dtype=np.float32)) == ERR_INVALID
     assert lib.dsx_tileplan_set_window(None, np.ones(16, dtype=np.float32), np.ones(16, dtype=np.float32)) == ERR_INVALID
-    assert _blend(plan.handle) == ERR_INVALID and "has no window" in _err()          # a refused window sets nothing
+    assert _blend(plan.handle) == ERR_INVALID and "has no window" in last_error()          # a refused window sets nothing
     with pytest.raises(DsxError, match="must have 16 and 16 values, got 16 and 15"):
         plan.set_window((np.ones(16), np.ones(15)))
     plan.set_window("triangle")
     plan.set_window("hann")                                             # a second call replaces the first
-    assert _blend(plan.handle, Cn=0) == ERR_INVALID and "tileplan_blend: C = 0" in _err()
-    assert _blend(plan.handle, world=0) == ERR_INVALID and "tileplan_blend: world = 0" in _err()
+    assert _blend(plan.handle, Cn=0) == ERR_INVALID and "tileplan_blend: C = 0" in last_error()
+    assert _blend(plan.handle, world=0) == ERR_INVALID and "tileplan_blend: world = 0" in last_error()
     for kw in (dict(tiles=None), dict(canvas=None)):
-        assert _blend(plan.handle, **kw) == ERR_INVALID and "tileplan_blend: null argument" in _err()
-    assert _blend(None) == ERR_INVALID and "tileplan_blend: null argument" in _err()
-    assert _blend(plan.handle, gt=FAKE) == ERR_INVALID and "PSNR sums need a partials buffer" in _err()
-    assert _blend(plan.handle, Cn=5, gt=FAKE, part=FAKE) == ERR_INVALID and "C <= 4" in _err()
+        assert _blend(plan.handle, **kw) == ERR_INVALID and "tileplan_blend: null argument" in last_error()
+    assert _blend(None) == ERR_INVALID and "tileplan_blend: null argument" in last_error()
+    assert _blend(plan.handle, gt=FAKE) == ERR_INVALID and "PSNR sums need a partials buffer" in last_error()
+    assert _blend(plan.handle, Cn=5, gt=FAKE, part=FAKE) == ERR_INVALID and "C <= 4" in last_error()
     # 56 tiles over 3 ranks: rank 0 holds 19 whole (2, 16, 16) tiles
     need = 19 * 2 * 16 * 16
     assert plan.blend_rank_stride(3, 2) == need
     for stride in (need - 1, 0, -5):
         assert _blend(plan.handle, Cn=2, world=3, stride=stride) == ERR_INVALID
-        assert f"tileplan_blend: rank_stride_elems = {stride} is smaller than rank 0's 19 whole tiles" in _err()
+        assert f"tileplan_blend: rank_stride_elems = {stride} is smaller than rank 0's 19 whole tiles" in last_error()
     assert lib.dsx_tileplan_blend_blocks(plan.handle) == 40 and plan.blend_blocks() == 40     # one segment, 40 rows
-    assert lib.dsx_tileplan_blend_blocks(_plan((1, 300, 600), 32, 16).handle) == 3 * 128
+    assert lib.dsx_tileplan_blend_blocks(tile_plan((1, 300, 600), 32, 16).handle) == 3 * 128
 
 
 def test_gather_canvas_refusals():
-    lib = _lib().lib
-    plan = _plan((2, 40, 57), 16, 8)
+    lib = binding().lib
+    plan = tile_plan((2, 40, 57), 16, 8)
     call = lambda h, f, s, c, Cn=2: lib.dsx_tileplan_gather_canvas(h, FAKE, Cn, f, s, c, FAKE, None)
     name = "tileplan_gather_canvas"
     for first, stride, count in ((plan.total, 1, 1), (0, 0, 2), (1, 2 ** 62, 3), (-1, 1, 1), (plan.total - 3, 1, 4),
                                  (1, 2, 29), (0, -1, 2)):
         assert call(plan.handle, first, stride, count) == ERR_INVALID, (first, stride, count)
-        assert f"{name}: tiles {first} + k * {stride} ({count} of them) leave the plan (56 tiles)" in _err()
+        assert f"{name}: tiles {first} + k * {stride} ({count} of them) leave the plan (56 tiles)" in last_error()
     for count in (65536, -1):
-        assert call(plan.handle, 0, 1, count) == ERR_INVALID and f"{name}: count = {count}" in _err() and "65535" in _err()
-    assert call(None, 0, 1, 1) == ERR_INVALID and f"{name}: null argument" in _err()
-    assert call(plan.handle, 0, 1, 1, Cn=0) == ERR_INVALID and f"{name}: C = 0" in _err()
-    assert lib.dsx_tileplan_gather_canvas(plan.handle, None, 2, 0, 1, 1, FAKE, None) == ERR_INVALID and "null argument" in _err()
-    assert lib.dsx_tileplan_gather_canvas(plan.handle, FAKE, 2, 0, 1, 1, None, None) == ERR_INVALID and "null argument" in _err()
+        assert call(plan.handle, 0, 1, count) == ERR_INVALID and f"{name}: count = {count}" in last_error() and "65535" in last_error()
+    assert call(None, 0, 1, 1) == ERR_INVALID and f"{name}: null argument" in last_error()
+    assert call(plan.handle, 0, 1, 1, Cn=0) == ERR_INVALID and f"{name}: C = 0" in last_error()
+    assert lib.dsx_tileplan_gather_canvas(plan.handle, None, 2, 0, 1, 1, FAKE, None) == ERR_INVALID and "null argument" in last_error()
+    assert lib.dsx_tileplan_gather_canvas(plan.handle, FAKE, 2, 0, 1, 1, None, None) == ERR_INVALID and "null argument" in last_error()
     assert call(plan.handle, 0, 1, 0) == 0
 
 
 # ----------------------------------------------------------------------------- the drivers' refusals, no rank, no device
 def test_split_refuses_the_stitch_flags_where_they_do_not_apply(tmp_path, monkeypatch):
     from diffsplitting_amd import parallel, split
-    from tests.test_field_cpu import _config
 
     def touched(*a, **k):
         raise AssertionError("the refusal came too late: a rank was started or the device was initialised")
@@ -190,7 +172,7 @@ def test_split_refuses_the_stitch_flags_where_they_do_not_apply(tmp_path, monkey
     monkeypatch.setattr(parallel, "self_launch", touched)
     monkeypatch.setattr(split, "create_model", touched)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
-    cfgs = {w: _config(tmp_path, w) for w in ("sr3", "joint_indi")}
+    cfgs = {w: write_config(tmp_path, w) for w in ("sr3", "joint_indi")}
 
     def refused(argv, match, config="sr3"):
         with pytest.raises(SystemExit, match=match):
@@ -219,16 +201,15 @@ def test_predict_stack_refuses_by_name_before_any_launch(monkeypatch):
     from diffsplitting_amd._lib import DsxError
     from diffsplitting_amd.data import tile_predict
     from diffsplitting_amd.data.tiled_predict import predict_stack, predict_tiled
-    from tests.test_field_cpu import _samplers
 
     def touched(*a, **k):
         raise AssertionError("the refusal came too late")
     monkeypatch.setattr(_lib, "require_gpu", touched)
     monkeypatch.setattr(tile_predict, "TileExchange", touched)
-    g, i, _ = _samplers()
+    g, i, _ = cpu_samplers()
 
     class Stack:
-        plan = _plan((2, 40, 57), 32, 16)
+        plan = tile_plan((2, 40, 57), 32, 16)
 
         def tiles(self, ids):
             touched()

@@ -12,13 +12,14 @@ import torch
 
 from tests import blend_ref
 from tests.blend_step_ref import blend_step_ref
-from tests.test_blend_cpu import ERR_INVALID, FAKE, PLANS, _err, _lib, _plan
+from tests.host_checks import BLEND_PLANS, ERR_INVALID, FAKE, binding, cpu_samplers, last_error, tile_plan
+from tests.nets import write_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_the_entry_point_is_declared_bound_and_exported():
-    lib = _lib()
+    lib = binding()
     header = open(os.path.join(ROOT, "include", "dsx.h")).read()
     assert re.search(r"\bint dsx_tileplan_blend_step\(", header)
     assert len(lib.SIGNATURES["dsx_tileplan_blend_step"][1]) == 13 and hasattr(lib._cdll, "dsx_tileplan_blend_step")
@@ -29,7 +30,7 @@ def test_the_entry_point_is_declared_bound_and_exported():
 
 # ----------------------------------------------------------------------------- the restatement
 def test_one_tile_per_frame_is_the_pointwise_formula():
-    plan = _plan((3, 32, 32), 32, 32)
+    plan = tile_plan((3, 32, 32), 32, 32)
     assert plan.total == 3
     rng = np.random.default_rng(1)
     tiles = rng.standard_normal((3, 2, 32, 32)).astype(np.float32)
@@ -45,11 +46,11 @@ def test_one_tile_per_frame_is_the_pointwise_formula():
     assert got.dtype == np.float32 and np.array_equal(got.view(np.int32), want.view(np.int32))
 
 
-@pytest.mark.parametrize("shape,patch,grid", PLANS, ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS, ids=str)
 def test_tiles_cut_from_one_frame_give_the_frame_back(shape, patch, grid):
     """c_x0 = 1, c_xt = 0, sigma = 0: 1 * v + 0 * X = v exactly, so the bound is the blend's own (test_blend_cpu):
     |out - v| <= (2 n + 1) 2^-24 |v| with n <= 12 contributors"""
-    plan = _plan(shape, patch, grid)
+    plan = tile_plan(shape, patch, grid)
     rng = np.random.default_rng(6)
     frame = rng.standard_normal(plan.data_shape + (1,)).astype(np.float32)
     X = rng.standard_normal(plan.data_shape + (1,)).astype(np.float32)
@@ -60,7 +61,7 @@ def test_tiles_cut_from_one_frame_give_the_frame_back(shape, patch, grid):
 
 
 def test_sigma_zero_ignores_the_noise():
-    plan = _plan((1, 40, 56), 32, 16)
+    plan = tile_plan((1, 40, 56), 32, 16)
     rng = np.random.default_rng(2)
     tiles = rng.standard_normal((plan.total, 2, 32, 32)).astype(np.float32)
     X = rng.standard_normal(plan.data_shape + (2,)).astype(np.float32)
@@ -74,7 +75,7 @@ def test_sigma_zero_ignores_the_noise():
 
 # ----------------------------------------------------------------------------- host refusals, no device
 def _step(h, tiles=FAKE, Cn=1, world=1, stride=0, state=FAKE, c=(0.5, 0.5, 0.1), seed=3, id_base=0, draw=1):
-    return _lib().lib.dsx_tileplan_blend_step(h, tiles, Cn, world, stride, state, c[0], c[1], c[2], C.c_uint64(seed),
+    return binding().lib.dsx_tileplan_blend_step(h, tiles, Cn, world, stride, state, c[0], c[1], c[2], C.c_uint64(seed),
                                               C.c_uint64(id_base), C.c_uint32(draw), None)
 
 
@@ -83,41 +84,41 @@ def test_blend_step_refusals():
     name = "tileplan_blend_step"
     trim = tiling.TilePlan((1, 40, 56), (1, 16, 16), (1, 32, 32), mode=tiling.TRIM)
     ones = np.ones(32, dtype=np.float32)
-    assert _lib().lib.dsx_tileplan_set_window(trim.handle, ones, ones) == 0
-    assert _step(trim.handle) == ERR_INVALID and f"{name}: the plan's tiles do not cover the frames" in _err()
-    plan = _plan((2, 40, 57), 16, 8)
-    assert _step(plan.handle) == ERR_INVALID and f"{name}: the plan has no window" in _err()
+    assert binding().lib.dsx_tileplan_set_window(trim.handle, ones, ones) == 0
+    assert _step(trim.handle) == ERR_INVALID and f"{name}: the plan's tiles do not cover the frames" in last_error()
+    plan = tile_plan((2, 40, 57), 16, 8)
+    assert _step(plan.handle) == ERR_INVALID and f"{name}: the plan has no window" in last_error()
     plan.set_window("hann")
     # what the blend refuses
-    assert _step(plan.handle, Cn=0) == ERR_INVALID and f"{name}: C = 0" in _err()
-    assert _step(plan.handle, world=0) == ERR_INVALID and f"{name}: world = 0" in _err()
-    assert _step(None) == ERR_INVALID and f"{name}: null argument" in _err()
-    assert _step(plan.handle, tiles=None) == ERR_INVALID and f"{name}: null argument" in _err()
+    assert _step(plan.handle, Cn=0) == ERR_INVALID and f"{name}: C = 0" in last_error()
+    assert _step(plan.handle, world=0) == ERR_INVALID and f"{name}: world = 0" in last_error()
+    assert _step(None) == ERR_INVALID and f"{name}: null argument" in last_error()
+    assert _step(plan.handle, tiles=None) == ERR_INVALID and f"{name}: null argument" in last_error()
     need = 19 * 2 * 16 * 16                                             # 56 tiles over 3 ranks: rank 0 holds 19
     for stride in (need - 1, 0, -5):
         assert _step(plan.handle, Cn=2, world=3, stride=stride) == ERR_INVALID
-        assert f"{name}: rank_stride_elems = {stride} is smaller than rank 0's 19 whole tiles" in _err()
+        assert f"{name}: rank_stride_elems = {stride} is smaller than rank 0's 19 whole tiles" in last_error()
     # a null state
-    assert _step(plan.handle, state=None) == ERR_INVALID and f"{name}: null argument" in _err()
+    assert _step(plan.handle, state=None) == ERR_INVALID and f"{name}: null argument" in last_error()
     # the field ids of the plan's two frames and the draw ordinal
     for id_base in (2 ** 40 - 1, 2 ** 40, 2 ** 63, 2 ** 64 - 1):
         assert _step(plan.handle, id_base=id_base) == ERR_INVALID
-        assert f"{name}: id_base = {id_base} with 2 frames" in _err() and "below 2^40" in _err()
+        assert f"{name}: id_base = {id_base} with 2 frames" in last_error() and "below 2^40" in last_error()
     for draw in (2 ** 24, 2 ** 32 - 1):
-        assert _step(plan.handle, draw=draw) == ERR_INVALID and f"{name}: draw ordinal {draw}" in _err()
+        assert _step(plan.handle, draw=draw) == ERR_INVALID and f"{name}: draw ordinal {draw}" in last_error()
     # a coefficient that is not finite
     for k in range(3):
         for bad in (float("nan"), float("inf"), float("-inf")):
             c = [0.5, 0.5, 0.1]
             c[k] = bad
-            assert _step(plan.handle, c=c) == ERR_INVALID and f"{name}: c_x0 = " in _err() and "must be finite" in _err()
+            assert _step(plan.handle, c=c) == ERR_INVALID and f"{name}: c_x0 = " in last_error() and "must be finite" in last_error()
 
 
 def test_the_python_face_refuses_before_the_library(monkeypatch):
     from diffsplitting_amd import _lib as L
     from diffsplitting_amd._lib import DsxError
     monkeypatch.setattr(L, "require_gpu", lambda: None)
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = tile_plan((2, 40, 57), 16, 8)
     with pytest.raises(DsxError, match="tiles must be a .* float32 CUDA tensor"):
         plan.blend_step(torch.zeros(plan.total, 2, 16, 16), torch.zeros(2, 40, 57, 2), 0.5, 0.5, 0.0, 3, 1)
 
@@ -128,17 +129,16 @@ def test_predict_stack_frames_refuses_by_name_before_any_launch(monkeypatch):
     from diffsplitting_amd._lib import DsxError
     from diffsplitting_amd.data import tile_predict
     from diffsplitting_amd.data.tiled_predict import predict_stack, predict_stack_frames
-    from tests.test_field_cpu import _samplers
 
     def touched(*a, **k):
         raise AssertionError("the refusal came too late")
     monkeypatch.setattr(L, "require_gpu", touched)
     monkeypatch.setattr(tile_predict, "TileExchange", touched)
     monkeypatch.setattr(parallel, "all_gather_flat", touched)
-    g, i, j = _samplers()
+    g, i, j = cpu_samplers()
 
     class Stack:
-        plan = _plan((2, 40, 57), 32, 16)
+        plan = tile_plan((2, 40, 57), 32, 16)
 
         def tiles(self, ids):
             touched()
@@ -174,7 +174,6 @@ def test_predict_stack_frames_refuses_by_name_before_any_launch(monkeypatch):
 
 def test_split_refuses_frame_steps_where_it_does_not_apply(tmp_path, monkeypatch):
     from diffsplitting_amd import parallel, split
-    from tests.test_field_cpu import _config
 
     def touched(*a, **k):
         raise AssertionError("the refusal came too late: a rank was started or the device was initialised")
@@ -182,7 +181,7 @@ def test_split_refuses_frame_steps_where_it_does_not_apply(tmp_path, monkeypatch
     monkeypatch.setattr(parallel, "self_launch", touched)
     monkeypatch.setattr(split, "create_model", touched)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
-    cfgs = {w: _config(tmp_path, w) for w in ("sr3", "ddpm", "indi", "joint_indi")}
+    cfgs = {w: write_config(tmp_path, w) for w in ("sr3", "ddpm", "indi", "joint_indi")}
 
     def refused(argv, match, config="indi"):
         with pytest.raises(SystemExit, match=match):

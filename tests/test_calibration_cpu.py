@@ -14,6 +14,8 @@ from diffsplitting_amd import _lib
 from diffsplitting_amd._lib import DsxError, check, lib
 from diffsplitting_amd.core import calibration as CAL
 from tests import calibration_ref as REF
+from tests.bits import same_bits
+from tests.nets import write_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dsx_calibration_blocks", "dsx_calibration")
@@ -110,11 +112,11 @@ def test_json_round_trip_is_exact(tmp_path):
     cal.save(path)
     json.load(open(path))                                          # strict JSON (no NaN literal)
     back = CAL.Calibration.load(path)
-    bits = lambda a: np.asarray(a, dtype=np.float64).view(np.uint64)
+    f64 = lambda a: np.asarray(a, dtype=np.float64)
     for k in ("a", "c", "scale", "std_target"):
-        assert np.array_equal(bits(getattr(back, k)), bits(getattr(cal, k))), k
+        assert same_bits(f64(getattr(back, k)), f64(getattr(cal, k))), k
     for k in ("edges", "z", "sv", "se", "rmv", "rmse", "coverage"):
-        assert np.array_equal(bits(getattr(back.stats, k)), bits(getattr(cal.stats, k))), k
+        assert same_bits(f64(getattr(back.stats, k)), f64(getattr(cal.stats, k))), k
     for k in ("count", "covered"):
         assert np.array_equal(getattr(back.stats, k), getattr(cal.stats, k)) and getattr(back.stats, k).dtype == np.int64
     assert (back.samples, back.channels, back.stats.n) == (3, 2, cal.stats.n)
@@ -220,16 +222,6 @@ def test_the_bound_accepts_the_kernels_order_and_rejects_the_typical_mistakes(n_
 
 
 # ----------------------------------------------------------------------------- command line
-def _config(tmp_path, which, **ds):
-    cfg = {"name": "tiny", "phase": "val", "gpu_ids": [0], "path": {"resume_state": None},
-           "datasets": dict({"patch_size": 32, "max_qval": 0.98, "train": {"name": "Hagen", "batch_size": 3},
-                             "val": {"name": "Hagen"}}, **ds),
-           "model": {"which_model_G": which, "loss_type": "l2"}}
-    p = tmp_path / f"{which}{len(ds)}.json"
-    p.write_text(json.dumps(cfg))
-    return str(p)
-
-
 def test_split_refuses_the_calibration_flags_where_they_do_not_apply(tmp_path, monkeypatch):
     """Every refusal is a SystemExit that names the flag, raised on the command line, the config and the calibration file
     alone: no rank is started and nothing touches the device."""
@@ -241,8 +233,8 @@ def test_split_refuses_the_calibration_flags_where_they_do_not_apply(tmp_path, m
     monkeypatch.setattr(parallel, "init", touched)
     monkeypatch.setattr(parallel, "self_launch", touched)
     monkeypatch.setattr(split, "create_model", touched)
-    indi, joint = _config(tmp_path, "indi"), _config(tmp_path, "joint_indi")
-    one = _config(tmp_path, "indi", target_channel_idx=1)
+    indi, joint = write_config(tmp_path, "indi"), write_config(tmp_path, "joint_indi")
+    one = write_config(tmp_path, "indi", target_channel_idx=1)
     norm = str(tmp_path / "n.json")
     nd = {"mean_input": 1.0, "std_input": 2.0, "target0_max": 3.0, "target1_max": 4.0, "input_max": 5.0,
           "mean_target": [1.0, 2.0], "std_target": [3.0, 4.0]}

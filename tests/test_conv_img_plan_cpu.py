@@ -7,23 +7,9 @@ import re
 
 import pytest
 
+from tests.plan_cases import COND_CHANNELS, IMG_LAUNCHES, IMG_MODEL
 from tests.plan_dump import read_dump
 
-# SR3 UNet: 32 x 32 input, levels 64 / 256 / 512 channels, attention at 8 x 8, 3 conditioning channels
-IMG_MODEL = dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=32, channel_mults=(1, 4, 8),
-                 attn_res=(8,), res_blocks=1, image_size=32)
-COND_CHANNELS = 3
-
-IMG_LAUNCHES = {
-    "conv3x3 256->512 @8x8 img": 1,
-    "conv1x1 256->512 @8x8 img": 1,
-    "conv3x3 512->512 @8x8 img": 7,
-    "conv1x1 512->1536 @8x8 img": 4,
-    "conv1x1 512->512 @8x8 img": 4,
-    "conv3x3 1024->512 @8x8 img": 1,
-    "conv1x1 1024->512 @8x8 img": 1,
-    "conv1x1 768->512 @8x8 img": 1,
-}
 # channel phases (8 waves x one 64-byte chunk each) -> the NPH the launcher instantiates: 2 and 4 exactly, 8 for the rest
 PHASES = {"bf16": {1, 2, 3, 4}, "f16": {1, 2, 3, 4}, "f32": {2, 4, 6, 8}}
 NPH = {"bf16": {1: 8, 2: 2, 3: 8, 4: 4}, "f16": {1: 8, 2: 2, 3: 8, 4: 4}, "f32": {2: 2, 4: 4, 6: 8, 8: 8}}

@@ -4,8 +4,8 @@ tests/test_gpu_direct.py reach what that module is there to run."""
 import pytest
 
 from tests.direct_cases import CASES, DIRECT_ENV, DIRECT_ROWS, PLANS, direct_flag, make_cfg
+from tests.plan_cases import CONFIGS
 from tests.plan_dump import read_dump
-from tests.test_planner_cpu import CONFIGS
 
 # the plain 1 x 1 launches of C2 (sr_sr3_16_128, B = 16, bf16): 14 residual convs and 5 attention output projections
 C2_DIRECT = (

@@ -3,21 +3,16 @@ host checks (the shared plan-form checks and the three refusals of its own) with
 of ``split``; ``noise_field`` against the two other noise sources; and the planner on the 3 -> 2 UNet of the reference's
 ``config/splitting.json``."""
 import ctypes as C
-import json
 import os
 import re
 
 import pytest
 import torch
 
+from tests.host_checks import ERR_INVALID, FAKE, cpu_samplers, last_error
+from tests.nets import write_config
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ERR_INVALID = -1
-FAKE = C.c_void_p(4096)                                               # non-NULL, never dereferenced
-
-
-def _err():
-    from diffsplitting_amd import _lib
-    return _lib.lib.dsx_last_error().decode()
 
 
 def test_the_entry_is_declared_bound_and_exported():
@@ -54,28 +49,28 @@ def test_the_shared_plan_form_checks_hold(plan):
     for first, stride, count in ((plan.total, 1, 1), (0, 0, 2), (1, 2 ** 62, 3), (-1, 1, 1), (plan.total - 3, 1, 4),
                                  (1, 2, 29), (0, -1, 2)):
         assert _randn(plan.handle, first, stride, count) == ERR_INVALID, (first, stride, count)
-        assert f"tileplan_randn: tiles {first} + k * {stride} ({count} of them) leave the plan (56 tiles)" in _err()
+        assert f"tileplan_randn: tiles {first} + k * {stride} ({count} of them) leave the plan (56 tiles)" in last_error()
     for count in (65536, -1):
         assert _randn(plan.handle, 0, 1, count) == ERR_INVALID
-        assert f"tileplan_randn: count = {count}" in _err() and "65535" in _err()
-    assert _randn(None, 0, 1, 1) == ERR_INVALID and "tileplan_randn: null argument" in _err()
+        assert f"tileplan_randn: count = {count}" in last_error() and "65535" in last_error()
+    assert _randn(None, 0, 1, 1) == ERR_INVALID and "tileplan_randn: null argument" in last_error()
     assert _randn(plan.handle, 0, 1, 0) == 0                          # nothing to do: no error, and no device
     assert _randn(plan.handle, 0, 1, 0, out=None) == 0
-    assert _randn(plan.handle, 0, 1, 1, out=None) == ERR_INVALID and "tileplan_randn: null argument" in _err()
+    assert _randn(plan.handle, 0, 1, 1, out=None) == ERR_INVALID and "tileplan_randn: null argument" in last_error()
 
 
 def test_the_refusals_of_its_own_are_by_name(plan):
     from diffsplitting_amd import _lib
     for Cn in (0, -3):
-        assert _randn(plan.handle, 0, 1, 1, Cn=Cn) == ERR_INVALID and f"tileplan_randn: C = {Cn}" in _err()
+        assert _randn(plan.handle, 0, 1, 1, Cn=Cn) == ERR_INVALID and f"tileplan_randn: C = {Cn}" in last_error()
     lim = _lib.STREAM_ID_LIMIT
     for id_base in (lim - 1, lim, 2 ** 64 - 1):                       # two frames: id_base + 1 must stay below 2^40
         assert _randn(plan.handle, 0, 1, 1, id_base=id_base) == ERR_INVALID
-        assert f"tileplan_randn: id_base = {id_base} with 2 frames" in _err() and "2^40" in _err()
+        assert f"tileplan_randn: id_base = {id_base} with 2 frames" in last_error() and "2^40" in last_error()
     assert _randn(plan.handle, 0, 1, 0, id_base=lim - 2) == 0         # the last pair of ids that fits
     for draw in (_lib.STREAM_DRAW_LIMIT, 2 ** 32 - 1):
         assert _randn(plan.handle, 0, 1, 1, draw=draw) == ERR_INVALID
-        assert f"tileplan_randn: draw ordinal {draw}" in _err() and "2^24" in _err()
+        assert f"tileplan_randn: draw ordinal {draw}" in last_error() and "2^24" in last_error()
     assert _randn(plan.handle, 0, 1, 0, draw=_lib.STREAM_DRAW_LIMIT - 1) == 0
 
 
@@ -94,16 +89,6 @@ def test_randn_field_refuses_on_the_python_side_too(plan, monkeypatch):
 
 
 # ----------------------------------------------------------------------------- command line
-def _config(tmp_path, which):
-    cfg = {"name": "tiny", "phase": "val", "gpu_ids": [0], "path": {"resume_state": None},
-           "datasets": {"patch_size": 32, "max_qval": 0.98, "train": {"name": "Hagen", "batch_size": 3},
-                        "val": {"name": "Hagen"}},
-           "model": {"which_model_G": which, "loss_type": "l2"}}
-    p = tmp_path / f"{which}.json"
-    p.write_text(json.dumps(cfg))
-    return str(p)
-
-
 def test_split_refuses_the_new_flags_where_they_do_not_apply(tmp_path, monkeypatch):
     """Every refusal is a SystemExit that names the flag, raised on the command line and the config alone: no rank is
     started and nothing touches the device."""
@@ -114,7 +99,7 @@ def test_split_refuses_the_new_flags_where_they_do_not_apply(tmp_path, monkeypat
     monkeypatch.setattr(parallel, "init", touched)
     monkeypatch.setattr(parallel, "self_launch", touched)
     monkeypatch.setattr(split, "create_model", touched)
-    cfgs = {w: _config(tmp_path, w) for w in ("sr3", "ddpm", "indi", "joint_indi")}
+    cfgs = {w: write_config(tmp_path, w) for w in ("sr3", "ddpm", "indi", "joint_indi")}
 
     def refused(argv, match, config="sr3"):
         with pytest.raises(SystemExit, match=match):
@@ -140,19 +125,6 @@ def test_split_refuses_the_new_flags_where_they_do_not_apply(tmp_path, monkeypat
 
 
 # ----------------------------------------------------------------------------- the draw hook
-def _samplers():
-    from diffsplitting_amd.model.samplers import GaussianSampler, InDISampler, JointIndiSampler
-    sched = {"schedule": "linear", "n_timestep": 12, "linear_start": 1e-4, "linear_end": 2e-2}
-    g = GaussianSampler(None, 32, channels=2, conditional=True)
-    g.set_new_noise_schedule(sched, "cpu")
-    i = InDISampler(None, 32, channels=1, out_channel=2, conditional=False)
-    i.set_new_noise_schedule({"n_timestep": 3}, "cpu")
-    j = JointIndiSampler(None, 32, channels=1, out_channel=1, conditional=False, denoise_fn_ch1=torch.nn.Identity(),
-                         denoise_fn_ch2=torch.nn.Identity())
-    j.set_new_noise_schedule({"n_timestep": 4}, "cpu")
-    return g, i, j
-
-
 def test_noise_field_is_refused_together_with_the_other_sources(monkeypatch):
     """by name, before anything is drawn or any kernel runs (the field and the source would raise if asked)"""
     from diffsplitting_amd._lib import DsxError
@@ -161,7 +133,7 @@ def test_noise_field_is_refused_together_with_the_other_sources(monkeypatch):
     def asked(*a, **k):
         raise AssertionError("a draw was taken before the refusal")
     monkeypatch.setattr(samplers._SamplerBase, "_need_cuda", staticmethod(lambda *a, **k: None))
-    g, i, j = _samplers()
+    g, i, j = cpu_samplers()
     assert g.noise_field is None and i.noise_field is None and j.noise_field is None
     x = torch.zeros(2, 1, 32, 32)
     calls = [lambda kw: g.p_sample_loop(x, **kw), lambda kw: g.solver_sample_loop(x, steps=4, **kw),

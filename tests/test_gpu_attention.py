@@ -10,6 +10,8 @@ import pytest
 import torch
 
 from tests import attn_ref
+from tests.bits import same_bits
+from tests.nets import dev  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -40,16 +42,6 @@ def instantiation(C, B, L, col_split):
     ndb = {1: 1, 2: 2, 3: 4, 4: 4}.get(ndb, 8)
     cs = 2 if (ndb == 4 and col_split and B * ((L + 31) // 32) <= 160) else 1
     return ndb, cs
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def _bits(t):
-    return t.contiguous().view(SENTINEL[t.element_size()][0])
 
 
 def _launch(q, k, v, col_split, padded=True):
@@ -153,12 +145,12 @@ def test_images_independent_and_launches_repeatable(L, C, col_split, dt, dev):
     q, k, v = (t.to(DT[dt]) for t in attn_ref.make_pattern("rand", L, C, 3, device=dev))
     out = _launch(q, k, v, col_split)
     again = _launch(q, k, v, col_split)
-    assert torch.equal(_bits(out), _bits(again)), "two launches of the same input differ"
+    assert same_bits(out, again), "two launches of the same input differ"
     for b in range(3):
         alone = _launch(q[b:b + 1], k[b:b + 1], v[b:b + 1], col_split)
-        assert torch.equal(_bits(out[b:b + 1]), _bits(alone)), f"image {b} of a B = 3 launch differs from the image alone"
+        assert same_bits(out[b:b + 1], alone), f"image {b} of a B = 3 launch differs from the image alone"
     planner = _launch(q, k, v, col_split, padded=False)
-    assert torch.equal(_bits(out), _bits(planner)), "the padded and the q-first layout differ"
+    assert same_bits(out, planner), "the padded and the q-first layout differ"
 
 
 def test_attention_wrapper_refuses_cpu_tensors(dev):

@@ -9,17 +9,10 @@ import torch
 from diffsplitting_amd import _lib, engine
 from diffsplitting_amd._lib import Dev, DsxError, Handle, Host, Stream, check, lib
 from diffsplitting_amd.data.tiling import TilePlan
+from tests.bits import same_bits
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _addr(t):
@@ -37,7 +30,7 @@ def test_randn_tensors_against_raw_pointers():
     assert check(lib.dsx_randn(a, n, 11, 5, None)) == 0
     assert check(lib.dsx_randn(_addr(b), n, 11, 5, _current())) == 0
     torch.cuda.synchronize()
-    assert _same(a, b) and not bool((a == -7.25).any())
+    assert same_bits(a, b) and not bool((a == -7.25).any())
 
 
 @pytest.mark.parametrize("injected", [True, False])
@@ -56,9 +49,9 @@ def test_q_sample_tensors_against_raw_pointers(injected):
                                       _current() if raw else None)) == 0
         outs.append((dst, z_out))
     torch.cuda.synchronize()
-    assert _same(outs[0][0], outs[1][0]) and not bool((outs[0][0] == -7.25).any())
+    assert same_bits(outs[0][0], outs[1][0]) and not bool((outs[0][0] == -7.25).any())
     if not injected:
-        assert _same(outs[0][1], outs[1][1]) and not bool((outs[0][1] == -7.25).any())
+        assert same_bits(outs[0][1], outs[1][1]) and not bool((outs[0][1] == -7.25).any())
 
 
 def test_wrappers_launch_on_a_non_default_current_stream():
@@ -70,7 +63,7 @@ def test_wrappers_launch_on_a_non_default_current_stream():
     with torch.cuda.stream(s):
         got = plan.stitch(plan.gather(frames)[:, None].contiguous())
     s.synchronize()
-    assert got.shape == (2, 16, 16, 1) and _same(got, ref)
+    assert got.shape == (2, 16, 16, 1) and same_bits(got, ref)
 
 
 class Recorder:
@@ -120,7 +113,7 @@ def test_tensors_on_another_device_than_the_current_one():
         assert z.device == q.device == torch.device(dev)
         outs[dev] = (z, q)
     assert torch.cuda.current_device() == 0
-    assert _same(outs["cuda:0"][0], outs["cuda:1"][0]) and _same(outs["cuda:0"][1], outs["cuda:1"][1])
+    assert same_bits(outs["cuda:0"][0], outs["cuda:1"][0]) and same_bits(outs["cuda:0"][1], outs["cuda:1"][1])
     with pytest.raises(DsxError, match="dsx_q_sample: tensors on cuda:1 and on cuda:0"):
         lib.dsx_q_sample(outs["cuda:1"][1], None, 2, 3, 1, 5, 7, outs["cuda:0"][0][:, 0, 0, 0].contiguous(), None,
                          outs["cuda:0"][0][:, 0, 0, 1].contiguous(), None, 0, 0, None, outs["cuda:1"][0], 3, 0, None)

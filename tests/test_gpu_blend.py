@@ -3,36 +3,19 @@ contract (tests/blend_ref.py) -- ragged plans, pw % 4 = 2, up to 12 contributors
 an unaligned canvas --, the rank-slot layouts against the one-rank bits, the PSNR sums, dsx_tileplan_gather_canvas
 against torch slicing, and the drivers: ``predict_stack(stitch="blend")`` against the test's own loop plus ``blend_ref``,
 ``TileExchange(blend=True)`` over ranks, ``split --stitch blend`` end to end."""
-import functools
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 from tests import blend_ref
+from tests import tiled_util as T
+from tests.bits import same_bits
 from tests.metrics_ref import range_invariant_psnr
-from tests.test_gpu_field import (BATCH, SEED, SOLVERS, Source, _crops, _indi, _run, _sr3, _stack32, _stochastic_steps,
-                                  same_bits)
+from tests.rank_worker import run_ranks
+from tests.tiled_util import BATCH, BLEND_PLANS, SEED, SOLVERS
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# (frames, patch, grid): 56 tiles with odd W and a shifted last row and column; pw % 4 = 2 twice; 12 contributors; one tile
-PLANS = [((2, 40, 57), 16, 8), ((2, 40, 57), 6, 4), ((2, 40, 57), 10, 6), ((1, 37, 50), 24, 8), ((1, 32, 32), 32, 32)]
-
-
-@functools.lru_cache(maxsize=None)
-def _plan(shape, patch, grid):
-    from diffsplitting_amd.data.tiling import TilePlan
-    return TilePlan(shape, (1, grid, grid), (1, patch, patch))
-
-
-def _random_tiles(plan, Cn, seed=11):
-    return np.random.default_rng(seed).standard_normal((plan.total, Cn) + plan.patch_shape[1:]).astype(np.float32)
 
 
 def _same(canvas, want):
@@ -41,14 +24,14 @@ def _same(canvas, want):
 
 # ----------------------------------------------------------------------------- 1. the contract
 @pytest.mark.parametrize("name", ["triangle", "hann"])
-@pytest.mark.parametrize("shape,patch,grid", PLANS, ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS, ids=str)
 def test_blend_is_its_restatement(shape, patch, grid, name):
-    plan = _plan(shape, patch, grid)
+    plan = T.plan_of(shape, patch, grid)
     plan.set_window(name)
     wy, wx = blend_ref.window_pair(plan, name)
     rng = np.random.default_rng(3)
     for Cn in (1, 2, 3):
-        tiles = _random_tiles(plan, Cn)
+        tiles = T.random_tiles(plan, Cn)
         got = plan.blend(torch.from_numpy(tiles).cuda())
         assert got.shape == plan.data_shape + (Cn,) and _same(got, blend_ref.blend_ref(plan, tiles, wy, wx)), Cn
         # tiles cut from one frame: they agree on every overlap, the blend stays within a few ulp of the frame
@@ -59,9 +42,9 @@ def test_blend_is_its_restatement(shape, patch, grid, name):
         assert (np.abs(got.cpu().numpy().astype(np.float64) - frame) <= 25 * 2.0 ** -24 * np.abs(frame)).all()
 
 
-@pytest.mark.parametrize("shape,patch,grid", PLANS, ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS, ids=str)
 def test_an_integer_frame_comes_back_exactly(shape, patch, grid):
-    plan = _plan(shape, patch, grid)
+    plan = T.plan_of(shape, patch, grid)
     plan.set_window("triangle")
     for Cn in (1, 2, 3, 4, 5):                                          # 5: the kernel's any-C form
         frame = torch.randint(-64, 65, plan.data_shape + (Cn,), generator=torch.Generator().manual_seed(Cn)).float().cuda()
@@ -72,9 +55,9 @@ def test_an_integer_frame_comes_back_exactly(shape, patch, grid):
 @pytest.mark.parametrize("Cn", [1, 2, 4])
 def test_blend_into_an_unaligned_view(Cn):
     """the canvas one float past a 16-byte boundary: one dword per channel whatever C is; its NaN neighbours stay NaN"""
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = T.plan_of((2, 40, 57), 16, 8)
     plan.set_window("hann")
-    tiles = _random_tiles(plan, Cn)
+    tiles = T.random_tiles(plan, Cn)
     n = int(np.prod(plan.data_shape)) * Cn
     buf = torch.full((n + 9,), float("nan"), device="cuda")
     view = buf[5:5 + n].view(plan.data_shape + (Cn,))
@@ -88,10 +71,10 @@ def test_blend_into_an_unaligned_view(Cn):
 # ----------------------------------------------------------------------------- 2. layouts
 @pytest.mark.parametrize("world", [2, 3])
 def test_the_rank_slot_layouts_give_the_one_rank_bits(world):
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = T.plan_of((2, 40, 57), 16, 8)
     plan.set_window("hann")
     for Cn in (1, 2, 3):
-        tiles = _random_tiles(plan, Cn)
+        tiles = T.random_tiles(plan, Cn)
         one = plan.blend(torch.from_numpy(tiles).cuda())
         buf = blend_ref.slots(plan, tiles, world)
         assert buf.shape == (world, plan.blend_rank_stride(world, Cn))
@@ -101,11 +84,11 @@ def test_the_rank_slot_layouts_give_the_one_rank_bits(world):
 # ----------------------------------------------------------------------------- 3. PSNR
 @pytest.mark.parametrize("Cn", [1, 2, 3, 4])
 def test_blend_psnr(Cn):
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = T.plan_of((2, 40, 57), 16, 8)
     plan.set_window("triangle")
     rng = np.random.default_rng(9)
     gt = rng.standard_normal(plan.data_shape + (Cn,)).astype(np.float32)
-    tiles = blend_ref.cut_tiles(plan, gt) + 0.3 * _random_tiles(plan, Cn)
+    tiles = blend_ref.cut_tiles(plan, gt) + 0.3 * T.random_tiles(plan, Cn)
     t = torch.from_numpy(tiles).cuda()
     canvas, psnr = plan.blend(t, gt=torch.from_numpy(gt).cuda())
     part = plan.last_blend_partials.clone()
@@ -120,9 +103,9 @@ def test_blend_psnr(Cn):
 
 
 # ----------------------------------------------------------------------------- 4. the canvas gather
-@pytest.mark.parametrize("shape,patch,grid", PLANS[:4], ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS[:4], ids=str)
 def test_gather_canvas_is_torch_slicing(shape, patch, grid):
-    plan = _plan(shape, patch, grid)
+    plan = T.plan_of(shape, patch, grid)
     p = patch
     for Cn in (1, 2, 3):
         canvas = torch.randn(plan.data_shape + (Cn,), generator=torch.Generator().manual_seed(Cn)).cuda()
@@ -148,17 +131,17 @@ def _own_loop(smp, stack, run):
 def test_predict_stack_blend(name):
     """frames (2, 40, 57), patch 32, grid 16: 12 tiles in batches of 4; `seed` gives every tile its own stream"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    stack = _stack32()
+    stack = T.stack32()
     plan = stack.plan
     if name == "indi":
-        smp, kw = _indi(), dict(num_timesteps=3)
+        smp, kw = T.indi(), dict(num_timesteps=3)
 
         def run(x, chunk):
             smp.inference(x, continuous=False, num_timesteps=3, seed=SEED, sample_ids=chunk)
             return smp.last_full_batch.clone()
     else:
-        smp, kw = _sr3(), dict(solver=SOLVERS[name])
-        run = lambda x, chunk: _run(smp, x, SOLVERS[name], seed=SEED, sample_ids=chunk)
+        smp, kw = T.sr3(), dict(solver=SOLVERS[name])
+        run = lambda x, chunk: T.run(smp, x, SOLVERS[name], seed=SEED, sample_ids=chunk)
     tiles = _own_loop(smp, stack, run)
     for window in ("triangle", "hann"):
         out, plan2 = predict_stack(smp, stack, batch_tiles=BATCH, seed=SEED, stitch="blend", window=window, **kw)
@@ -173,14 +156,13 @@ def test_predict_stack_blend(name):
 def test_predict_stack_blend_mean_and_spread():
     """two posterior samples per tile: the float64 Welford of the two restated samples, mean and spread each blended"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    from tests.test_gpu_field import _welford
-    smp, stack, solver = _sr3(), _stack32(), SOLVERS["ddim"]
+    smp, stack, solver = T.sr3(), T.stack32(), SOLVERS["ddim"]
     plan = stack.plan
     got, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=SEED, samples=2, return_std=True, stitch="blend")
-    xs = [_own_loop(smp, stack, lambda x, chunk, r=r: _run(smp, x, solver, seed=SEED,
+    xs = [_own_loop(smp, stack, lambda x, chunk, r=r: T.run(smp, x, solver, seed=SEED,
                                                            sample_ids=[k + r * plan.total for k in chunk])).cpu().numpy()
           for r in range(2)]
-    mean, std = _welford(xs)
+    mean, std = T.welford(xs)
     win = blend_ref.window_pair(plan, "triangle")
     assert _same(got["mean"], blend_ref.blend_ref(plan, mean, *win))
     assert _same(got["std"], blend_ref.blend_ref(plan, std, *win)) and bool((got["std"] > 0).any())
@@ -194,22 +176,21 @@ def test_predict_stack_blend_psnr():
     frames = (rng.random((2, 40, 57, 2), dtype=np.float32) * 1000.0).astype(np.float32)
     val = SplitDatasetTiledPred("Hagen", DataLocation(arrays=(frames[..., 0], frames[..., 1])), 32, grid_size=16, max_qval=0.98,
                                 enable_transforms=False, random_patching=False, device=torch.device("cuda"))
-    smp, solver = _sr3(), SOLVERS["dpmpp2m"]
+    smp, solver = T.sr3(), SOLVERS["dpmpp2m"]
     out, plan = predict_stack(smp, val, batch_tiles=BATCH, solver=solver, seed=SEED, stitch="blend")
     assert plan.total == 12 and out["psnr"].shape == (2, 2)
     gt = val.normalized_target_frames()
     want = range_invariant_psnr(gt.cpu().numpy(), out["mean"].cpu().numpy())
     assert np.abs(out["psnr"].cpu().numpy() - want).max() < 1e-3
-    tiles = torch.cat([_run(smp, val.tiles(list(range(i, i + BATCH)))["input"], solver, seed=SEED,
+    tiles = torch.cat([T.run(smp, val.tiles(list(range(i, i + BATCH)))["input"], solver, seed=SEED,
                             sample_ids=list(range(i, i + BATCH))) for i in range(0, plan.total, BATCH)])
     assert _same(out["mean"], blend_ref.blend_ref(plan, tiles.cpu().numpy(), *blend_ref.window_pair(plan, "triangle")))
 
 
 def test_predict_tiled_blend():
     from diffsplitting_amd.data.tiled_predict import predict_tiled
-    from tests.test_gpu_field import _smooth
-    netG = _indi()
-    frames = torch.from_numpy(_smooth((2, 40, 57))).cuda()
+    netG = T.indi()
+    frames = torch.from_numpy(T.smooth((2, 40, 57))).cuda()
     got, plan = predict_tiled(netG, frames, 32, batch_tiles=BATCH, seed=SEED, stitch="blend", window="hann")
     tiles = []
     for i in range(0, plan.total, BATCH):
@@ -226,51 +207,13 @@ def test_predict_tiled_blend():
 def test_blended_prediction_does_not_depend_on_the_sharding(world):
     """`world` fresh ranks (parallel.self_launch, under its timeout) share the hardware that is there, gloo transport:
     on every rank the blended canvas equals the one-rank tiles under blend_ref, bitwise (tests/multi_rank_predict_blend.py)"""
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(%d, [%r], timeout=300))\n"
-            % (ROOT, world, os.path.join(ROOT, "tests", "multi_rank_predict_blend.py")))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env["DSX_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=400)
+    r = run_ranks("multi_rank_predict_blend.py", world, backend="gloo", launch_timeout=300, timeout=400)
     assert r.returncode == 0 and "PREDICT_BLEND_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
 
 
 # ----------------------------------------------------------------------------- 6. split, end to end
-def split_runs(tmp_path, runs, extra=()):
-    """fresh `split` processes at once on the tiny sr3 config of tests/test_gpu_field.py -> the bytes of every --out"""
-    from tests.test_gpu_field import SCHED
-    cfg = {"name": "tiny_sr3", "phase": "val", "gpu_ids": [0],
-           "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
-           "datasets": {"patch_size": 32, "max_qval": 0.98, "upper_clip": False, "train": {"name": "Hagen"},
-                        "val": {"name": "Hagen"}},
-           "model": {"which_model_G": "sr3", "loss_type": "l1", "finetune_norm": False,
-                     "unet": {"in_channel": 3, "out_channel": 2, "inner_channel": 16, "norm_groups": 16,
-                              "channel_multiplier": [1, 2], "attn_res": [], "res_blocks": 1, "dropout": 0},
-                     "beta_schedule": {"train": SCHED, "val": SCHED},
-                     "diffusion": {"image_size": 32, "channels": 2, "conditional": True}}}
-    cfg_path = str(tmp_path / "tiny_sr3.json")
-    with open(cfg_path, "w") as f:
-        json.dump(cfg, f)
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    base = [sys.executable, "-m", "diffsplitting_amd.split", "-c", cfg_path, "-p", "val", "-gpu", "0", "--synthetic", "1,64,64",
-            "--solver", "dpmpp2m", "--solver-steps", "4", "--sample-seed", "3", "--batch-tiles", "3"] + list(extra)
-    procs = {}
-    for name, flags in runs.items():
-        root = tmp_path / name
-        root.mkdir()
-        procs[name] = subprocess.Popen(base + flags + ["-rootdir", str(root), "--out", str(root / "pred.npy")], env=env,
-                                       cwd=str(root), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    for name, p in procs.items():
-        log, _ = p.communicate(timeout=300)
-        assert p.returncode == 0, (name, log[-3000:])
-    pred = np.load(tmp_path / next(iter(runs)) / "pred.npy")
-    assert pred.shape == (1, 64, 64, 2) and pred.dtype == np.float32 and np.isfinite(pred).all()
-    return {name: open(tmp_path / name / "pred.npy", "rb").read() for name in runs}
-
-
 def test_split_stitch_blend_end_to_end(tmp_path):
     """the flagged run twice (byte for byte the same file), once cropped and once under the other window"""
-    data = split_runs(tmp_path, {"a": ["--stitch", "blend"], "b": ["--stitch", "blend"], "crop": [],
+    data = T.split_runs(tmp_path, {"a": ["--stitch", "blend"], "b": ["--stitch", "blend"], "crop": [],
                                  "hann": ["--stitch", "blend", "--window", "hann"]})
     assert data["a"] == data["b"] and data["a"] != data["crop"] and data["a"] != data["hann"]

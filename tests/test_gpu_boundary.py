@@ -10,7 +10,9 @@ import torch
 
 from oracle import cases, samplers, tiling
 from oracle.weights import synth_state_dict
+from tests import nets
 from tests.gpu_util import DrawRecorder, maxabs
+from tests.rank_worker import run_ranks
 from tests.util import GOLDEN, golden_state_dict, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -18,31 +20,12 @@ torch.set_grad_enabled(False)
 FP32_TOL = 1e-3
 
 
-def _opt(model_section, **extra):
-    from diffsplitting_amd.core.logger import dict_to_nonedict
-    d = {"model": json.loads(json.dumps(model_section)), "phase": "val", "gpu_ids": [0], "distributed": False,
-         "path": {"resume_state": None}}
-    d.update(extra)
-    return dict_to_nonedict(d)
-
-
-def _tiny_indi_section(in_ch=2, out_ch=2, which="indi"):
-    return {"which_model_G": which, "loss_type": "l1", "lr_reduction": "mean", "finetune_norm": False,
-            "w_input_loss": 0.0,
-            "unet": {"in_channel": in_ch, "out_channel": out_ch, "inner_channel": 16, "norm_groups": 16,
-                     "channel_multiplier": [1, 2, 4] if which == "indi" else [1, 2, 4, 8], "attn_res": [],
-                     "res_blocks": 1, "dropout": 0},
-            "beta_schedule": {"train": {"schedule": "linear", "n_timestep": 20, "linear_start": 1e-6, "linear_end": 1e-2},
-                              "val": {"schedule": "linear", "n_timestep": 3, "linear_start": 1e-6, "linear_end": 1e-2}},
-            "diffusion": {"image_size": 32, "channels": out_ch, "conditional": False}}
-
-
 def test_create_model_indi_test_matches_oracle():
     """create_model -> load_state_dict(reference keys) -> feed_data -> test(): same output as the oracle's
     InDI.inference, including the 'last batch element only' return (Q1) and the full-batch accessor."""
     from diffsplitting_amd.model import create_model
     sd, g = golden_state_dict("loop_indi_n3_t1.0")
-    model = create_model(_opt(_tiny_indi_section()))
+    model = create_model(nets.opt(nets.tiny_indi_section()))
     model.netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()}, strict=True)
     model.set_new_noise_schedule({"n_timestep": 3}, schedule_phase="val")
     x_in = cases.make_cond("indi_loop")
@@ -69,7 +52,7 @@ def test_define_G_sr3_superset_route():
                     "channel_multiplier": [1, 2, 4], "attn_res": [16], "res_blocks": 2, "dropout": 0.2},
            "beta_schedule": {"train": cases.SCHEDULES["lin_8"], "val": cases.SCHEDULES["lin_8"]},
            "diffusion": {"image_size": 32, "channels": 3, "conditional": True}}
-    model = create_model(_opt(sec))
+    model = create_model(nets.opt(sec))
     missing, unexpected = model.netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()}, strict=False)
     assert not unexpected and all(not k.startswith("denoise_fn.") for k in missing)
     cond = cases.make_cond("sr3_loop")
@@ -90,8 +73,8 @@ def test_define_G_sr3_superset_route():
 def test_joint_indi_module():
     from diffsplitting_amd.model import networks
     sd, g = golden_state_dict("loop_joint_n3")
-    sec = _tiny_indi_section(1, 1, "joint_indi")
-    netG = networks.define_G(_opt(sec)).cuda()
+    sec = nets.tiny_indi_section(1, 1, "joint_indi")
+    netG = networks.define_G(nets.opt(sec)).cuda()
     netG.load_state_dict(sd, strict=True)
     netG.set_new_noise_schedule({"n_timestep": 3}, "cuda")
     x_in = cases.make_cond("joint_loop").cuda()
@@ -123,13 +106,13 @@ def test_checkpoint_round_trip(tmp_path):
     """save_network / load_network (model/model.py:131-173) with the reference's file naming."""
     from diffsplitting_amd.model import create_model
     sd, _ = golden_state_dict("loop_indi_n3_t1.0")
-    opt = _opt(_tiny_indi_section())
+    opt = nets.opt(nets.tiny_indi_section())
     opt["path"]["checkpoint"] = str(tmp_path)
     m1 = create_model(opt)
     m1.netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()})
     m1.save_network(epoch=1, iter_step=10)
     assert os.path.exists(tmp_path / "I10_E1_gen.pth")
-    opt2 = _opt(_tiny_indi_section())
+    opt2 = nets.opt(nets.tiny_indi_section())
     opt2["path"]["resume_state"] = str(tmp_path / "I10_E1")
     m2 = create_model(opt2)
     x = cases.make_cond("indi_loop").cuda()
@@ -146,9 +129,7 @@ def test_tiled_prediction_matches_reference_procedure():
     from diffsplitting_amd.data.tiled_predict import predict_tiled
     from diffsplitting_amd.model import networks
     sd, _ = golden_state_dict("unet_hagen_64")
-    sec = _tiny_indi_section()
-    sec["unet"]["channel_multiplier"] = [1, 2, 4, 8]
-    netG = networks.define_G(_opt(sec)).cuda()
+    netG = networks.define_G(nets.opt(nets.hagen64_section())).cuda()
     netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()})
     netG.e = 0.0
     rng = np.random.default_rng(5)
@@ -183,7 +164,7 @@ def test_stitch_predictions_mirror_numpy():
 def test_split_entry_point(tmp_path):
     """`split.py -c <config> -p val` on a config in the reference's schema (with // comments), synthetic frames."""
     from diffsplitting_amd import split
-    sec = _tiny_indi_section()
+    sec = nets.tiny_indi_section()
     cfg = {"name": "tiny_hagen_indi", "phase": "train", "gpu_ids": [0],
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
            "datasets": {"val": {"name": "Hagen", "patch_size": 64, "datatype": "img"}}, "model": sec}
@@ -206,15 +187,9 @@ def test_psnr_metrics_on_device():
 def test_two_rank_predict_tiled():
     """End to end on 2 GPUs (skipped on a 1-GPU box): two fresh ranks started by parallel.self_launch, tiles sharded
     rank-strided, one RCCL all-gather, stitched result bitwise equal to the one-GPU prediction on every rank."""
-    import subprocess
-    import sys
     if torch.cuda.device_count() < 2:
         pytest.skip("needs 2 GPUs")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(2, [%r]))\n" % (root, os.path.join(root, "tests", "multi_gpu_predict_tiled.py")))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    r = run_ranks("multi_gpu_predict_tiled.py", 2, timeout=600)
     assert r.returncode == 0 and "PREDICT_TILED_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
 
 
@@ -224,14 +199,7 @@ def test_ranks_share_the_one_gpu_gloo_transport(world):
     libdsx / executors / tile shard on the ONE GPU, valid regions packed on the device, the exchange over gloo (staged
     through the host: RCCL refuses two ranks on one device), paste from the packed layout -- stitched result bitwise
     equal to the one-rank prediction on every rank.  What stays unexecuted on hardware is the RCCL transport itself."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(%d, [%r], timeout=500))\n" % (root, world, os.path.join(root, "tests", "multi_gpu_predict_tiled.py")))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env["DSX_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    r = run_ranks("multi_gpu_predict_tiled.py", world, backend="gloo", launch_timeout=500, timeout=600)
     assert r.returncode == 0 and "PREDICT_TILED_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
 
 
@@ -346,15 +314,15 @@ def test_packed_weight_cache(tmp_path):
     from diffsplitting_amd.model import create_model
     from diffsplitting_amd.model.engine_unet import EngineUNet
     sd, _ = golden_state_dict("loop_indi_n3_t1.0")
-    opt = _opt(_tiny_indi_section())
+    opt = nets.opt(nets.tiny_indi_section())
     opt["path"]["checkpoint"] = str(tmp_path)
     m1 = create_model(opt)
     m1.netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()})
     m1.save_network(epoch=1, iter_step=10)
     x = cases.make_cond("indi_loop").cuda()
 
-    def load():
-        o = _opt(_tiny_indi_section())
+    def resumed():
+        o = nets.opt(nets.tiny_indi_section())
         o["path"]["resume_state"] = str(tmp_path / "I10_E1")
         m = create_model(o)
         m.netG.e = 0.0
@@ -362,24 +330,24 @@ def test_packed_weight_cache(tmp_path):
         unet = [u for u in m.netG.modules() if isinstance(u, EngineUNet)][0]
         return out, unet.pack_cache_hit
 
-    a, hit_a = load()
+    a, hit_a = resumed()
     assert hit_a is False and (tmp_path / "I10_E1_gen.unet0.f32.dsxpack").exists()
-    b, hit_b = load()
+    b, hit_b = resumed()
     assert hit_b is True and torch.equal(a, b)
     # a different checkpoint under the same name must not reuse the image
     sd2 = {k: v + 0.01 for k, v in m1.netG.state_dict().items()}
     torch.save({k: v.cpu() for k, v in sd2.items()}, tmp_path / "I10_E1_gen.pth")
-    c, hit_c = load()
+    c, hit_c = resumed()
     assert hit_c is False and not torch.equal(a, c)
     # a damaged payload of the right size is refused (SHA-256 of the payload in the header) and rewritten
     pk = tmp_path / "I10_E1_gen.unet0.f32.dsxpack"
     raw = bytearray(pk.read_bytes())
     raw[-5] ^= 0xFF
     pk.write_bytes(bytes(raw))
-    d, hit_d = load()
+    d, hit_d = resumed()
     assert hit_d is False and torch.equal(c, d)
     # weights edited in place after load_network: the cached image no longer describes the module and is not used
-    o = _opt(_tiny_indi_section())
+    o = nets.opt(nets.tiny_indi_section())
     o["path"]["resume_state"] = str(tmp_path / "I10_E1")
     m = create_model(o)
     m.netG.e = 0.0

@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests import nets
 from tests import calibration_ref as REF
+from tests.bits import same_bits
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -41,7 +43,6 @@ def _poisoned(x, offset):
 def _check(n, C, nbins, nz):
     from diffsplitting_amd.core.calibration import calibration_sums
     z = REF.Z_OF[nz]
-    bits = lambda a: a.view(np.uint64)
     for name, (m, s, t) in REF.cases(n, C, seed=nbins + nz).items():
         what = (name, n, C, nbins, nz)
         edges = REF.edges_of(s, nbins)
@@ -62,7 +63,7 @@ def _check(n, C, nbins, nz):
         assert (err <= bnd)[:, ~ints].all(), (what, worst)
         assert got[0][:, 0:3 * nbins:3].sum(axis=1).tolist() == [n] * C
         for other, how in zip(got[1:], ("offset by one element", "contiguous", "second run")):
-            assert np.array_equal(bits(other), bits(got[0])), (what, how)
+            assert same_bits(other, got[0]), (what, how)
         if name == "equal" and nbins > 1:
             assert (got[0][:, 0:3 * (nbins - 1):3] == 0).all()                     # every pixel in the last bin
 
@@ -125,13 +126,6 @@ def test_bin_edges_are_np_quantile(n, C, bins):
 SHAPE, PATCH, GRID, BATCH, STEPS, SEED = (2, 64, 96), 64, 32, 4, 2, 11
 
 
-def _tiny_section():
-    from tests.test_gpu_boundary import _tiny_indi_section
-    sec = _tiny_indi_section()
-    sec["unet"]["channel_multiplier"] = [1, 2, 4, 8]
-    return sec
-
-
 def test_the_posterior_spread_of_a_tiny_network_end_to_end(tmp_path, monkeypatch):
     from diffsplitting_amd import split
     from diffsplitting_amd.core.calibration import Calibration
@@ -144,7 +138,7 @@ def test_the_posterior_spread_of_a_tiny_network_end_to_end(tmp_path, monkeypatch
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
            "datasets": {"patch_size": PATCH, "max_qval": 0.98, "upper_clip": False, "channel_weights": [1, 1],
                         "train": {"name": "Hagen"}, "val": {"name": "Hagen"}},
-           "model": _tiny_section()}
+           "model": nets.hagen64_section()}
     p = lambda name: str(tmp_path / name)
     with open(p("tiny.json"), "w") as f:
         json.dump(cfg, f)

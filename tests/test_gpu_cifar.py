@@ -10,17 +10,20 @@ import numpy as np
 import pytest
 import torch
 
+from tests import nets
 from tests import cifar_files as CF
+from tests.bits import same_bits
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 ERR_INVALID = -1                                                     # DSX_ERR_INVALID
 
 
-def _bits(a):
+def _f32(a):
+    """a tensor or an array as a host array, which must be float32"""
     a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
     assert a.dtype == np.float32
-    return np.ascontiguousarray(a).view(np.uint32)
+    return a
 
 
 @pytest.fixture(scope="module")
@@ -50,10 +53,10 @@ def test_items_bit_equal_to_the_reference(val_dir, tag, patch, kw):
     for k in ("input", "target"):
         want = g[f"{tag}_{k}"]
         assert tuple(out[k].shape) == want.shape and out[k].is_contiguous()
-        assert np.array_equal(_bits(out[k]), _bits(want)), (tag, k)      # tolerance zero: same operations, same order
+        assert same_bits(_f32(out[k]), _f32(want)), (tag, k)      # tolerance zero: same operations, same order
     item = ds[idx[-1]]
     assert item["input"].shape == g[f"{tag}_input"].shape[1:] and isinstance(item["target"], np.ndarray)
-    assert np.array_equal(_bits(item["target"]), _bits(g[f"{tag}_target"][-1]))
+    assert same_bits(_f32(item["target"]), _f32(g[f"{tag}_target"][-1]))
 
 
 # ----------------------------------------------------------------------------- the entry point, called directly
@@ -97,13 +100,12 @@ def test_one_plane_equals_the_grey_export():
     new_tar = torch.empty((len(loc), 2, ph, pw), device="cuda")
     old_in, old_tar = torch.empty_like(new_in), torch.empty_like(new_tar)
     check(_call(a, b, (N, 1, H, W), (ph, pw), loc, w, norm[0], norm[1], [norm[2], norm[4]], [norm[3], norm[5]], new_in, new_tar))
-    i64 = lambda v: (C.c_int64 * 3)(*v)
-    check(lib.dsx_tiles_gather_norm(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), i64((N, H, W)), i64((1, ph, pw)),
+    check(lib.dsx_tiles_gather_norm(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), nets.i64(N, H, W), nets.i64(1, ph, pw),
                                     loc.ctypes.data_as(C.POINTER(C.c_int64)), None, len(loc), w[0], w[1],
                                     (C.c_double * 6)(*norm), 0, C.c_void_p(old_in.data_ptr()), C.c_void_p(old_tar.data_ptr()),
                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
-    assert np.array_equal(_bits(new_in), _bits(old_in)) and np.array_equal(_bits(new_tar), _bits(old_tar))
+    assert same_bits(_f32(new_in), _f32(old_in)) and same_bits(_f32(new_tar), _f32(old_tar))
     assert torch.isfinite(new_tar).all() and new_tar.std() > 0.1
 
 
@@ -131,7 +133,7 @@ def test_direct_call_writes_its_outputs_and_nothing_else():
     for buf, n, want in ((buf_in, n_in, want_in), (buf_tar, n_tar, want_tar)):
         host = buf.cpu().numpy()
         assert np.isnan(host[:pad]).all() and np.isnan(host[pad + n:]).all()
-        assert np.array_equal(_bits(host[pad:pad + n].reshape(want.shape)), _bits(want))
+        assert same_bits(_f32(host[pad:pad + n].reshape(want.shape)), _f32(want))
 
 
 def test_bad_arguments_are_refused_before_any_launch():
@@ -169,10 +171,9 @@ def test_indi_repeats_a_colour_input_to_out_channel_channels():
     objective and the start of the sampling loop see cat([input] * 2) -- the same as handing them that tensor."""
     from diffsplitting_amd._lib import DsxError
     from diffsplitting_amd.model import create_model
-    from tests.test_gpu_boundary import _opt
     g = CF.fixture()
     torch.manual_seed(3)
-    model = create_model(_opt(CF.model_section()))
+    model = create_model(nets.opt(CF.model_section()))
     model.set_new_noise_schedule({"n_timestep": 20}, schedule_phase="val")
     model.netG.set_loss("cuda")
     inp, tar = (torch.from_numpy(g[f"first8_{k}"][:2].copy()).cuda() for k in ("input", "target"))
@@ -230,7 +231,7 @@ def test_split_main_scores_the_validation_set(tmp_path, caplog, monkeypatch, whi
     avg = split.main(argv)
     assert [s[0].shape[0] for s in seen] == [3, 3, 2]
     fed_in, fed_tar, pred = (torch.cat([s[k] for s in seen]) for k in range(3))
-    assert np.array_equal(_bits(fed_in), _bits(g["first8_input"])) and np.array_equal(_bits(fed_tar), _bits(g["first8_target"]))
+    assert same_bits(_f32(fed_in), _f32(g["first8_input"])) and same_bits(_f32(fed_tar), _f32(g["first8_target"]))
     assert pred.shape == (8, 6, 32, 32) and torch.isfinite(pred).all()
     nd = CF.normalization_dict("nd_w11")
     per_triple = {0: [], 3: []}
@@ -250,4 +251,4 @@ def test_split_main_scores_the_validation_set(tmp_path, caplog, monkeypatch, whi
     assert saved.dtype == np.float32 and saved.shape == (8, 6, 32, 32)
     raw = (pred.cpu().numpy().astype(np.float64) * nd["std_target"].reshape(1, 6, 1, 1)
            + nd["mean_target"].reshape(1, 6, 1, 1)).astype(np.float32)
-    assert np.array_equal(_bits(saved), _bits(raw))
+    assert same_bits(_f32(saved), _f32(raw))

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from tests import comoments_ref as CR
+from tests.bits import same_bits
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -136,15 +137,14 @@ def test_a_planes_bits_do_not_depend_on_the_call():
         dg, d1, d2 = (torch.from_numpy(x).cuda() for x in (g, p1, p2))
         five = comoments(dg, d1, d2)
         again = comoments(dg, d1, d2)
-        bits = lambda t: t.contiguous().view(torch.int64)
-        assert torch.equal(bits(five), bits(again))                   # two runs
-        assert torch.equal(bits(five[0]), bits(five[4]))              # first and last
+        assert same_bits(five, again)                   # two runs
+        assert same_bits(five[0], five[4])              # first and last
         for k in range(5):                                            # alone (a view into the stack, and a copy of its own)
-            assert torch.equal(bits(comoments(dg[k:k + 1], d1[k:k + 1], d2[k:k + 1])[0]), bits(five[k])), (n, k)
+            assert same_bits(comoments(dg[k:k + 1], d1[k:k + 1], d2[k:k + 1])[0], five[k]), (n, k)
         alone = comoments(dg[2:3].clone(), d1[2:3].clone(), d2[2:3].clone())
-        assert torch.equal(bits(alone[0]), bits(five[2]))
+        assert same_bits(alone[0], five[2])
         three = comoments(dg[1:4], d1[1:4], d2[1:4])
-        assert torch.equal(bits(three), bits(five[1:4]))
+        assert same_bits(three, five[1:4])
 
 
 def test_views_are_read_in_place():

@@ -9,7 +9,7 @@ import torch
 import bench
 from tests import layer_ref
 from tests.gpu_util import build_engine
-from tests.test_conv_img_plan_cpu import COND_CHANNELS, IMG_LAUNCHES, IMG_MODEL
+from tests.plan_cases import COND_CHANNELS, IMG_LAUNCHES, IMG_MODEL
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)

@@ -23,18 +23,13 @@ from oracle.weights import synth_state_dict
 from tests.direct_cases import CASES, DIRECT_ENV, PLANS, make_cfg
 from tests.gpu_util import build_engine
 from tests.layer_check import check_plan, inputs
+from tests.nets import dev  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 SEED = 41
 _SD = {}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 def _state_dict(name):

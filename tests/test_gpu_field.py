@@ -3,7 +3,6 @@ existing sample streams (every row residue mod 4, the 16-byte and the scalar sto
 field is for (tiles of one frame share the bits of their overlap), ``predict_stack`` with a Gaussian sampler (solvers
 and the ancestral loop) and with ``noise="field"`` against the test's own restatement through ``noise_source``, InDI and
 JointIndi, ``split`` end to end, and the seam property measured against the float64 oracle."""
-import functools
 import json
 import os
 import subprocess
@@ -13,34 +12,13 @@ import numpy as np
 import pytest
 import torch
 
+from tests import tiled_util as T
+from tests.bits import same_bits
+from tests.tiled_util import BATCH, SCHED, SEED, SOLVERS, TINY, Source
+
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 20240
-TINY = dict(in_channel=3, out_channel=2, inner_channel=16, norm_groups=16, channel_mults=(1, 2), attn_res=(), res_blocks=1,
-            image_size=32)
-SCHED = dict(schedule="linear", n_timestep=12, linear_start=1e-3, linear_end=0.3)
-SOLVERS = {"dpmpp2m": dict(solver="dpmpp2m", steps=4, eta=0.0, spacing=None),
-           "ddim": dict(solver="ddim", steps=4, eta=0.5, spacing=None), "ancestral": None}
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def _crops(plan, ids, Cn, seed, draw, id_base=0):
-    """The definition: tile i, cut at (n, y0, x0), holds that crop of the (C, H, W) tensor of the sample stream
-    (seed, id_base + n, draw) -- drawn with the generator that was there before the field."""
-    from diffsplitting_amd import engine
-    N, H, W = plan.data_shape
-    p = plan.patch_shape[1]
-    frames, out = {}, []
-    for i in ids:
-        n, y, x = (int(v) for v in plan.patch_start[int(i)])
-        if n not in frames:
-            frames[n] = engine.randn_samples((1, Cn, H, W), seed, [id_base + n], draw)[0]
-        out.append(frames[n][:, y:y + p, x:x + p])
-    return torch.stack(out).contiguous()
 
 
 def _plan(patch, grid, shape=(2, 40, 57)):
@@ -64,7 +42,7 @@ def test_randn_field_is_the_crop_of_the_sample_stream(Cn, draw, id_base):
         ids = make(plan.total)
         got = plan.randn_field(ids, Cn, SEED, draw, id_base)
         assert got.shape == (len(ids), Cn, 16, 16) and got.data_ptr() % 16 == 0
-        assert same_bits(got, _crops(plan, ids, Cn, SEED, draw, id_base)), name
+        assert same_bits(got, T.crops(plan, ids, Cn, SEED, draw, id_base)), name
     assert plan.randn_field([], Cn, SEED, draw, id_base).shape == (0, Cn, 16, 16)
 
 
@@ -77,7 +55,7 @@ def test_randn_field_scalar_stores(patch, grid, Cn):
     for draw, id_base in ((0, 0), (5, 7)):
         for name, make in ID_LISTS.items():
             ids = make(plan.total)
-            assert same_bits(plan.randn_field(ids, Cn, SEED, draw, id_base), _crops(plan, ids, Cn, SEED, draw, id_base)), name
+            assert same_bits(plan.randn_field(ids, Cn, SEED, draw, id_base), T.crops(plan, ids, Cn, SEED, draw, id_base)), name
 
 
 @pytest.mark.parametrize("patch,grid", [(16, 8), (6, 4)])
@@ -95,7 +73,7 @@ def test_randn_field_into_an_unaligned_view(patch, grid):
                                  None))
     ids = list(range(first, plan.total, stride))
     assert len(ids) == count
-    assert same_bits(view.view(count, Cn, patch, patch), _crops(plan, ids, Cn, SEED, 5, 7))
+    assert same_bits(view.view(count, Cn, patch, patch), T.crops(plan, ids, Cn, SEED, 5, 7))
     assert bool(torch.isnan(buf[:5]).all()) and bool(torch.isnan(buf[5 + n:]).all())
 
 
@@ -127,87 +105,12 @@ def test_tiles_of_a_frame_share_the_bits_of_their_overlap():
     assert same_bits(plan.randn_field([per], Cn, SEED, 3, 0), plan.randn_field([0], Cn, SEED, 3, 1))   # frame 1 = id 1
 
 
-# ----------------------------------------------------------------------------- samplers and stacks
-def _randomise(module, seed):
-    """Seeded random weights (oracle/weights.py: GroupNorm gammas around 1, biases off zero) in every UNet of ``module``."""
-    from diffsplitting_amd.model.engine_unet import EngineUNet
-    from oracle import weights
-    sds = []
-    for k, m in enumerate(u for u in module.modules() if isinstance(u, EngineUNet)):
-        sd = weights.synth_state_dict([(key, tuple(v.shape)) for key, v in m.state_dict().items()], seed=seed + k)
-        m.load_state_dict(sd)
-        sds.append(sd)
-    return sds
-
-
-@functools.lru_cache(maxsize=None)
-def _sr3():
-    """The tiny conditional sr3 sampler: UNet 3 -> 2 (one condition channel + two noisy target channels)"""
-    from diffsplitting_amd.model.samplers import GaussianSampler
-    from diffsplitting_amd.model.sr3_modules.unet import UNet
-    smp = GaussianSampler(UNet(**TINY), 32, channels=2, conditional=True).cuda()
-    smp.set_new_noise_schedule(SCHED, "cuda")
-    smp.weights = _randomise(smp, 41)[0]
-    return smp
-
-
-def _smooth(shape, seed=0):
-    N, H, W = shape
-    n, y, x = np.mgrid[0:N, 0:H, 0:W].astype(np.float64)
-    f = np.sin((x + 3 * n + seed) / 11.0) * np.cos(y / 7.0) + 0.5 * np.sin((x + y + 5 * n) / 17.0)
-    return ((f - f.mean()) / f.std()).astype(np.float32)
-
-
-def _stack(shape, patch, grid, seed=0):
-    from diffsplitting_amd.data.input_stack import InputStackTiledPred
-    nd = dict(mean_input=0.0, std_input=1.0, mean_target=np.zeros(2), std_target=np.ones(2))
-    return InputStackTiledPred(_smooth(shape, seed), patch, nd, grid_size=grid)
-
-
-@functools.lru_cache(maxsize=None)
-def _stack32():
-    s = _stack((2, 40, 57), 32, 16)
-    assert s.plan.total == 12
-    return s
-
-
-BATCH = 4
-
-
-def _run(smp, x, solver, **kw):
-    if solver:
-        smp.solver_sample_loop(x, **solver, **kw)
-    else:
-        smp.super_resolution(x, **kw)
-    return smp.last_full_batch.clone()
-
-
-class Source:
-    """A noise_source that hands out the given draws in order."""
-
-    def __init__(self, draws):
-        self.draws = list(draws)
-
-    def __call__(self, shape):
-        z = self.draws.pop(0)
-        assert tuple(z.shape) == tuple(shape)
-        return z
-
-
-def _stochastic_steps(smp, solver):
-    """The steps s of one loop that add noise (each takes draw s + 1)."""
-    if solver:
-        sigma = smp.solver_table(**solver).sigma
-        return [s for s in range(len(sigma)) if sigma[s] != 0]
-    return list(range(smp.num_timesteps - 1))                          # sr3: none at the last step
-
-
 # ----------------------------------------------------------------------------- 4. the Gaussian tiled path
 @pytest.mark.parametrize("name", list(SOLVERS))
 def test_predict_stack_with_a_gaussian_sampler(name):
     """per-tile streams, as for InDI: the driver equals the test's own loop over the batches plus plan.stitch"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    smp, stack, solver = _sr3(), _stack32(), SOLVERS[name]
+    smp, stack, solver = T.sr3(), T.stack32(), SOLVERS[name]
     plan = stack.plan
     out, plan2 = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=SEED)
     assert plan2 is plan and set(out) == {"mean"} and out["mean"].shape == plan.data_shape + (2,)
@@ -215,7 +118,7 @@ def test_predict_stack_with_a_gaussian_sampler(name):
     tiles = []
     for i in range(0, plan.total, BATCH):
         chunk = list(range(i, i + BATCH))
-        tiles.append(_run(smp, stack.tiles(chunk)["input"], solver, seed=SEED, sample_ids=chunk))
+        tiles.append(T.run(smp, stack.tiles(chunk)["input"], solver, seed=SEED, sample_ids=chunk))
     assert same_bits(out["mean"], plan.stitch(torch.cat(tiles)))
     again, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=SEED + 1)
     assert not torch.equal(again["mean"], out["mean"])
@@ -224,7 +127,7 @@ def test_predict_stack_with_a_gaussian_sampler(name):
 def test_predict_stack_refusals():
     from diffsplitting_amd._lib import DsxError
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    smp, stack = _sr3(), _stack32()
+    smp, stack = T.sr3(), T.stack32()
     with pytest.raises(DsxError, match="noise='field' needs seed"):
         predict_stack(smp, stack, noise="field")
     with pytest.raises(DsxError, match="noise = 'frames'"):
@@ -232,94 +135,43 @@ def test_predict_stack_refusals():
     with pytest.raises(DsxError, match="field_noise_bytes = 100000.*solver.*fewer rows.*smaller batch"):
         predict_stack(smp, stack, noise="field", seed=1, batch_tiles=BATCH, field_noise_bytes=100000)   # 11 rows x 32 KiB
     with pytest.raises(DsxError, match="solver: InDISampler is not a Gaussian sampler"):
-        predict_stack(_indi(), stack, solver=SOLVERS["ddim"])
+        predict_stack(T.indi(), stack, solver=SOLVERS["ddim"])
     assert smp.noise_field is None and smp.noise_source is None
 
 
 # ----------------------------------------------------------------------------- 5. the field through the driver
-def _restated_field(smp, stack, solver, batch, id_base=0, C_state=2, reverse=True):
-    """The prediction tile by tile with ``noise_source`` set to the crops of the field: draw 0 for the initial state,
-    draw s + 1 for every step s that adds noise; the batches from the last to the first."""
-    plan = stack.plan
-    steps = _stochastic_steps(smp, solver)
-    starts = list(range(0, plan.total, batch))
-    tiles = {}
-    try:
-        for i in (reversed(starts) if reverse else starts):
-            chunk = list(range(i, i + batch))
-            smp.noise_source = Source([_crops(plan, chunk, C_state, SEED, d, id_base) for d in [0] + [s + 1 for s in steps]])
-            tiles[i] = _run(smp, stack.tiles(chunk)["input"], solver)
-            assert not smp.noise_source.draws                          # every draw was asked for, in this order
-    finally:
-        smp.noise_source = None
-    return torch.cat([tiles[i] for i in starts])
-
-
 @pytest.mark.parametrize("name", list(SOLVERS))
 def test_field_noise_through_the_driver(name):
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    smp, stack, solver = _sr3(), _stack32(), SOLVERS[name]
+    smp, stack, solver = T.sr3(), T.stack32(), SOLVERS[name]
     plan = stack.plan
-    assert len(_stochastic_steps(smp, solver)) == {"dpmpp2m": 0, "ddim": 3, "ancestral": 11}[name]
+    assert len(T.stochastic_steps(smp, solver)) == {"dpmpp2m": 0, "ddim": 3, "ancestral": 11}[name]
     state = torch.get_rng_state()
     out, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=SEED, noise="field")
     assert torch.equal(torch.get_rng_state(), state) and smp.noise_field is None
-    want = _restated_field(smp, stack, solver, BATCH)
+    want = T.restated_field(smp, stack, solver, BATCH)
     assert same_bits(out["mean"], plan.stitch(want))
     streams, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=SEED)
     assert not torch.equal(streams["mean"], out["mean"])
 
 
-def _welford(xs):
-    """include/dsx.h, dsx_moments_update / dsx_moments_finish restated in float64, one rounded operation at a time"""
-    mean, m2 = xs[0].astype(np.float64), np.zeros(xs[0].shape)
-    for r in range(1, len(xs)):
-        x = xs[r].astype(np.float64)
-        d = x - mean
-        mean = mean + d / (r + 1)
-        m2 = m2 + d * (x - mean)
-    return mean.astype(np.float32), np.sqrt(m2 / (len(xs) - 1)).astype(np.float32)
-
-
 def test_field_noise_two_samples():
     """sample r takes id_base = r * frames; mean and spread are the float64 Welford of the two restated samples"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    smp, stack, solver = _sr3(), _stack32(), SOLVERS["ddim"]
+    smp, stack, solver = T.sr3(), T.stack32(), SOLVERS["ddim"]
     plan = stack.plan
     got, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=SEED, noise="field", samples=2, return_std=True)
-    xs = [_restated_field(smp, stack, solver, BATCH, id_base=r * plan.data_shape[0]).cpu().numpy() for r in range(2)]
+    xs = [T.restated_field(smp, stack, solver, BATCH, id_base=r * plan.data_shape[0]).cpu().numpy() for r in range(2)]
     assert not np.array_equal(xs[0], xs[1])
-    mean, std = _welford(xs)
+    mean, std = T.welford(xs)
     assert same_bits(got["mean"], plan.stitch(torch.from_numpy(mean).cuda()))
     assert same_bits(got["std"], plan.stitch(torch.from_numpy(std).cuda())) and bool((got["std"] > 0).any())
 
 
 # ----------------------------------------------------------------------------- 6. InDI and JointIndi
-@functools.lru_cache(maxsize=None)
-def _indi():
-    from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
-    netG = networks.define_G(_opt(_tiny_indi_section())).cuda()
-    netG.set_new_noise_schedule({"n_timestep": 3}, "cuda")
-    _randomise(netG, 51)
-    assert netG.e == 0.01
-    return netG
-
-
-@functools.lru_cache(maxsize=None)
-def _joint():
-    from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
-    netG = networks.define_G(_opt(_tiny_indi_section(1, 1, "joint_indi"))).cuda()
-    netG.set_new_noise_schedule({"n_timestep": 3}, "cuda")
-    _randomise(netG, 61)
-    assert netG.indi1.e == 0.01 and netG.indi2.e == 0.01
-    return netG
-
-
 def test_field_noise_indi():
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    netG, stack, n = _indi(), _stack32(), 3
+    netG, stack, n = T.indi(), T.stack32(), 3
     plan = stack.plan
     got, _ = predict_stack(netG, stack, batch_tiles=BATCH, num_timesteps=n, seed=SEED, noise="field")
     assert netG.noise_field is None
@@ -327,7 +179,7 @@ def test_field_noise_indi():
     try:
         for i in range(0, plan.total, BATCH):
             chunk = list(range(i, i + BATCH))
-            netG.noise_source = Source([_crops(plan, chunk, 2, SEED, d) for d in range(n + 1)])
+            netG.noise_source = Source([T.crops(plan, chunk, 2, SEED, d) for d in range(n + 1)])
             netG.inference(stack.tiles(chunk)["input"], continuous=False, num_timesteps=n)
             assert not netG.noise_source.draws
             tiles.append(netG.last_full_batch.clone())
@@ -341,7 +193,7 @@ def test_field_noise_indi():
 def test_field_noise_joint_indi():
     """indi1 draws from the field ids of the frames, indi2 from the same ids with bit 39 set"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    netG, stack, n = _joint(), _stack32(), 3
+    netG, stack, n = T.joint(), T.stack32(), 3
     plan = stack.plan
     got, _ = predict_stack(netG, stack, batch_tiles=BATCH, num_timesteps=n, seed=SEED, noise="field")
     assert netG.noise_field is None and netG.indi1.noise_field is None and netG.indi2.noise_field is None
@@ -349,7 +201,7 @@ def test_field_noise_joint_indi():
     try:
         for i in range(0, plan.total, BATCH):
             chunk = list(range(i, i + BATCH))
-            netG.noise_source = Source([_crops(plan, chunk, 1, SEED, d, id_base=bit)
+            netG.noise_source = Source([T.crops(plan, chunk, 1, SEED, d, id_base=bit)
                                         for bit in (0, netG.STREAM2_BIT) for d in range(n + 1)])
             netG.inference(stack.tiles(chunk)["input"], continuous=False, num_timesteps=n)
             assert not netG.noise_source.draws
@@ -397,23 +249,6 @@ def test_split_end_to_end(tmp_path):
 
 
 # ----------------------------------------------------------------------------- 8. the seam property
-def _seam_rms(plan, tiles):
-    """RMS difference of every horizontally adjacent pair of UNCROPPED tiles over the strip of 8 pixels on either side of
-    their crop line (where the stitched frame changes from one tile to the other)."""
-    N, H, W = plan.data_shape
-    d = []
-    for i in range(plan.total - 1):
-        (n0, y0, x0), (n1, y1, x1) = (tuple(int(v) for v in plan.patch_start[k]) for k in (i, i + 1))
-        if (n0, y0) != (n1, y1):
-            continue                                                  # the last tile of a row of tiles
-        line = int(plan.grid_start[i + 1][2])
-        a, b = line - x0, line - x1
-        d.append(tiles[i][:, :, a - 8:a + 8] - tiles[i + 1][:, :, b - 8:b + 8])
-    d = np.stack(d).astype(np.float64)
-    assert d.shape[1:] == (2, plan.patch_shape[1], 16)
-    return float(np.sqrt((d ** 2).mean())), len(d)
-
-
 def test_field_noise_narrows_the_seams():
     """ddim, eta = 0, 4 rows, one (1, 64, 96) frame of smooth input, all 15 tiles in one batch: a tile's result then is a
     function of its input tile and its initial noise.  With the field two neighbours start from the same noise on
@@ -426,21 +261,21 @@ def test_field_noise_narrows_the_seams():
     from diffsplitting_amd import engine
     from oracle import unet as oracle_unet
     from tests import solver_ref
-    smp = _sr3()
-    stack = _stack((1, 64, 96), 32, 16, seed=2)
+    smp = T.sr3()
+    stack = T.stack((1, 64, 96), 32, 16, seed=2)
     plan = stack.plan
     ids = list(range(plan.total))
     assert plan.total == 15 and all(int(v) % 8 == 0 for v in plan.patch_start[:, 1:].reshape(-1))   # no shifted tile
     solver = dict(solver="ddim", steps=4, eta=0.0, spacing=None)
     x = stack.tiles(ids)["input"]
     start = {"field": plan.randn_field(ids, 2, SEED, 0), "streams": engine.randn_samples((15, 2, 32, 32), SEED, ids, 0)}
-    assert same_bits(start["field"], _crops(plan, ids, 2, SEED, 0))
+    assert same_bits(start["field"], T.crops(plan, ids, 2, SEED, 0))
     try:
         smp.noise_field = lambda shape, draw: plan.randn_field(ids, shape[1], SEED, draw)
-        got = {"field": _run(smp, x, solver).cpu().numpy()}
+        got = {"field": T.run(smp, x, solver).cpu().numpy()}
     finally:
         smp.noise_field = None
-    got["streams"] = _run(smp, x, solver, seed=SEED, sample_ids=ids).cpu().numpy()
+    got["streams"] = T.run(smp, x, solver, seed=SEED, sample_ids=ids).cpu().numpy()
     # the float64 oracle on the same weights, input tiles and initial noise
     table = smp.solver_table(**solver)
     sd64 = {k: v.double() for k, v in smp.weights.items()}
@@ -452,9 +287,9 @@ def test_field_noise_narrows_the_seams():
         return oracle_unet.unet_forward(sd64, TINY, "sr3", inp, time).numpy()
     want = {k: solver_ref.run(table.columns(), v.cpu().numpy().astype(np.float64), net, clip=True, dtype=np.float64)[0][-1]
             for k, v in start.items()}
-    rms = {k: _seam_rms(plan, got[k])[0] for k in got}
-    rms64 = {k: _seam_rms(plan, want[k])[0] for k in want}
-    assert _seam_rms(plan, got["field"])[1] == 12                     # 3 rows of tiles, 4 seams each
+    rms = {k: T.seam_rms(plan, got[k])[0] for k in got}
+    rms64 = {k: T.seam_rms(plan, want[k])[0] for k in want}
+    assert T.seam_rms(plan, got["field"])[1] == 12                     # 3 rows of tiles, 4 seams each
     ratio, ratio64 = rms["field"] / rms["streams"], rms64["field"] / rms64["streams"]
     print(f"\nseam rms over 12 seams: field {rms['field']:.6f}, streams {rms['streams']:.6f}, ratio {ratio:.6f}; "
           f"float64 oracle: field {rms64['field']:.6f}, streams {rms64['streams']:.6f}, ratio {ratio64:.6f}")

@@ -12,23 +12,17 @@ import numpy as np
 import pytest
 import torch
 
-from tests import blend_ref
+from tests import blend_ref, nets
+from tests import tiled_util as T
+from tests.bits import same_bits
 from tests.blend_step_ref import blend_step_ref
-from tests.test_gpu_blend import PLANS, _plan, _random_tiles
-from tests.test_gpu_field import SEED, _indi, _joint, _seam_rms, _stack, _stack32, _welford, same_bits
+from tests.rank_worker import run_ranks
+from tests.tiled_util import BLEND_PLANS, SEED
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = ((1 / 3, 2 / 3, 0.00666), (0.5, 0.5, 0.0), (1.0, 0.0, 0.25))      # (c_x0, c_xt, sigma): a row, no noise, no state
-
-
-def _field(plan, Cn, seed, draw, id_base=0):
-    """the noise fields of the plan's frames in the state's layout (N, H, W, C), from the sample streams"""
-    from diffsplitting_amd import engine
-    N, H, W = plan.data_shape
-    z = engine.randn_samples((N, Cn, H, W), seed, [id_base + n for n in range(N)], draw)
-    return np.ascontiguousarray(z.permute(0, 2, 3, 1).cpu().numpy())
 
 
 def _state(plan, Cn, seed=21):
@@ -41,21 +35,21 @@ def _same(state, want):
 
 # ----------------------------------------------------------------------------- 1. the contract
 @pytest.mark.parametrize("name", ["triangle", "hann"])
-@pytest.mark.parametrize("shape,patch,grid", PLANS, ids=str)
+@pytest.mark.parametrize("shape,patch,grid", BLEND_PLANS, ids=str)
 def test_blend_step_is_its_restatement(shape, patch, grid, name):
     """odd W = 57 and C > 1: the stream index (c*H + y)*W + x of a pixel takes every residue mod 4 along a row and from
     row to row, so every component of a Philox block is picked at every lane position"""
-    plan = _plan(shape, patch, grid)
+    plan = T.plan_of(shape, patch, grid)
     plan.set_window(name)
     win = blend_ref.window_pair(plan, name)
     for Cn in (1, 2, 3):
-        tiles, X = _random_tiles(plan, Cn), _state(plan, Cn)
+        tiles, X = T.random_tiles(plan, Cn), _state(plan, Cn)
         dev = torch.from_numpy(tiles).cuda()
         for (c0, cx, sg), draw, id_base in zip(ROWS, (1, 4, 2), (0, 0, 7)):
             state = torch.from_numpy(X).cuda()
             got = plan.blend_step(dev, state, c0, cx, sg, SEED, draw, id_base=id_base)
             assert got.data_ptr() == state.data_ptr()                  # in place
-            Z = _field(plan, Cn, SEED, draw, id_base) if sg != 0 else None
+            Z = T.frame_field(plan, Cn, SEED, draw, id_base) if sg != 0 else None
             assert _same(state, blend_step_ref(plan, tiles, *win, X, c0, cx, sg, Z)), (Cn, c0, cx, sg)
         # sigma == 0: c_x0 * blend + c_xt * X, whatever the draw
         blend = plan.blend(dev).cpu().numpy()
@@ -68,27 +62,27 @@ def test_blend_step_is_its_restatement(shape, patch, grid, name):
         one = plan.blend_step(dev, torch.from_numpy(X).cuda(), c0, cx, sg, SEED, 1)
         two = plan.blend_step(dev, torch.from_numpy(X).cuda(), c0, cx, sg, SEED, 2)
         assert not torch.equal(one, two)
-        assert _same(two, blend_step_ref(plan, tiles, *win, X, c0, cx, sg, _field(plan, Cn, SEED, 2)))
+        assert _same(two, blend_step_ref(plan, tiles, *win, X, c0, cx, sg, T.frame_field(plan, Cn, SEED, 2)))
 
 
 @pytest.mark.parametrize("Cn", [4, 5])
 def test_blend_step_wide_and_any_channel_count(Cn):
     """C = 4 (one 16-byte access per pixel) and C = 5 (the kernel's any-C form)"""
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = T.plan_of((2, 40, 57), 16, 8)
     plan.set_window("triangle")
-    tiles, X = _random_tiles(plan, Cn), _state(plan, Cn)
+    tiles, X = T.random_tiles(plan, Cn), _state(plan, Cn)
     c0, cx, sg = ROWS[0]
     got = plan.blend_step(torch.from_numpy(tiles).cuda(), torch.from_numpy(X).cuda(), c0, cx, sg, SEED, 3, id_base=5)
-    want = blend_step_ref(plan, tiles, *blend_ref.window_pair(plan, "triangle"), X, c0, cx, sg, _field(plan, Cn, SEED, 3, 5))
+    want = blend_step_ref(plan, tiles, *blend_ref.window_pair(plan, "triangle"), X, c0, cx, sg, T.frame_field(plan, Cn, SEED, 3, 5))
     assert _same(got, want)
 
 
 @pytest.mark.parametrize("Cn", [2, 4])
 def test_blend_step_on_an_unaligned_view(Cn):
     """the state one float past a 16-byte boundary: one dword per channel; its NaN neighbours stay NaN"""
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = T.plan_of((2, 40, 57), 16, 8)
     plan.set_window("hann")
-    tiles, X = _random_tiles(plan, Cn), _state(plan, Cn)
+    tiles, X = T.random_tiles(plan, Cn), _state(plan, Cn)
     n = X.size
     buf = torch.full((n + 9,), float("nan"), device="cuda")
     view = buf[5:5 + n].view(X.shape)
@@ -96,18 +90,18 @@ def test_blend_step_on_an_unaligned_view(Cn):
     assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4
     c0, cx, sg = ROWS[0]
     plan.blend_step(torch.from_numpy(tiles).cuda(), view, c0, cx, sg, SEED, 1)
-    want = blend_step_ref(plan, tiles, *blend_ref.window_pair(plan, "hann"), X, c0, cx, sg, _field(plan, Cn, SEED, 1))
+    want = blend_step_ref(plan, tiles, *blend_ref.window_pair(plan, "hann"), X, c0, cx, sg, T.frame_field(plan, Cn, SEED, 1))
     assert _same(view, want)
     assert bool(torch.isnan(buf[:5]).all()) and bool(torch.isnan(buf[5 + n:]).all())
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_the_rank_slot_layouts_give_the_one_rank_bits(world):
-    plan = _plan((2, 40, 57), 16, 8)
+    plan = T.plan_of((2, 40, 57), 16, 8)
     plan.set_window("hann")
     c0, cx, sg = ROWS[0]
     for Cn in (1, 2, 3):
-        tiles, X = _random_tiles(plan, Cn), _state(plan, Cn)
+        tiles, X = T.random_tiles(plan, Cn), _state(plan, Cn)
         one = plan.blend_step(torch.from_numpy(tiles).cuda(), torch.from_numpy(X).cuda(), c0, cx, sg, SEED, 1)
         buf = torch.from_numpy(blend_ref.slots(plan, tiles, world)).cuda()
         got = plan.blend_step(buf, torch.from_numpy(X).cuda(), c0, cx, sg, SEED, 1, world=world, Cn=Cn)
@@ -115,11 +109,11 @@ def test_the_rank_slot_layouts_give_the_one_rank_bits(world):
 
 
 # ----------------------------------------------------------------------------- 2. one tile per frame: the unfused chain
-@pytest.mark.parametrize("make", [_indi, _joint], ids=["indi", "joint_indi"])
+@pytest.mark.parametrize("make", [T.indi, T.joint], ids=["indi", "joint_indi"])
 def test_one_tile_per_frame_is_the_unfused_chain(make):
     """frames (2, 32, 32), patch 32: gather and blend are copies, so frame diffusion is ``inference`` row by row"""
     from diffsplitting_amd.data.tiled_predict import predict_stack, predict_stack_frames
-    netG, stack = make(), _stack((2, 32, 32), 32, 16)
+    netG, stack = make(), T.stack((2, 32, 32), 32, 16)
     assert stack.plan.total == 2
     want, _ = predict_stack(netG, stack, batch_tiles=2, num_timesteps=3, seed=SEED, noise="field")
     got, plan = predict_stack_frames(netG, stack, batch_tiles=2, num_timesteps=3, seed=SEED)
@@ -131,72 +125,21 @@ def test_one_tile_per_frame_is_the_unfused_chain(make):
 
 
 # ----------------------------------------------------------------------------- 3. in general: the restatement
-def _children(netG):
-    if hasattr(netG, "indi1"):
-        return [(netG.indi1, 0.5, 0), (netG.indi2, 1 - 0.5, netG.STREAM2_BIT)]
-    return [(netG, 1.0, 0)]
-
-
-def _input_frames(stack):
-    """the crop-paste of the stack's own input tiles, with numpy"""
-    plan = stack.plan
-    tiles = stack.tiles(list(range(plan.total)))["input"].cpu().numpy()
-    out = np.full(plan.data_shape + (tiles.shape[1],), np.nan, dtype=np.float32)
-    for t, (n, y, x, h, w, ry, rx, _) in enumerate(plan.regions):
-        out[n, y:y + h, x:x + w] = tiles[t][:, ry:ry + h, rx:rx + w].transpose(1, 2, 0)
-    assert np.isfinite(out).all()
-    return out
-
-
-def _restated_child(child, stack, x_in, n, t0, batches, id_base, window, keep_rows=None):
-    """One child's frame state row by row: the state on the host, tiles cut with numpy, one UNet forward per batch (the
-    batches from the last to the first; ``batches`` = (ids, entries kept from the end)), the row's blend and step on the
-    host by tests/blend_step_ref.py with the noise from the sample streams."""
-    from diffsplitting_amd import engine
-    plan = stack.plan
-    copies = child.out_channel // x_in.shape[-1]
-    X = np.concatenate([x_in] * copies, axis=-1)
-    Cn = X.shape[-1]
-    scale = child.e * torch.Tensor([t0])                                # InDISampler._start
-    X = (torch.from_numpy(X) + torch.from_numpy(_field(plan, Cn, SEED, 0, id_base)) * scale).numpy()
-    table = engine.indi_step_table(n, t0, child.e)
-    win = blend_ref.window_pair(plan, window)
-    for s in range(n):
-        cut = blend_ref.cut_tiles(plan, X)
-        x0t = np.full((plan.total, Cn) + plan.patch_shape[1:], np.nan, dtype=np.float32)
-        for chunk, keep in reversed(batches):
-            x0 = child.denoise_fn(torch.from_numpy(cut[chunk]).cuda(), torch.Tensor([float(table.tcond[s])]).cuda())
-            x0t[chunk[-keep:]] = x0.cpu().numpy()[-keep:]
-        if keep_rows is not None:
-            keep_rows.append(x0t)
-        sg = float(table.sigma[s])
-        Z = _field(plan, Cn, SEED, s + 1, id_base) if sg != 0 else None
-        X = blend_step_ref(plan, x0t, *win, X, float(table.c1[s]), float(table.c2[s]), sg, Z)
-    return X
-
-
-def _restated(netG, stack, n, batches, r=0, window="triangle"):
-    x_in = _input_frames(stack)
-    N = stack.plan.data_shape[0]
-    return np.concatenate([_restated_child(child, stack, x_in, n, t0, batches, r * N + bit, window)
-                           for child, t0, bit in _children(netG)], axis=-1)
-
-
 FOURS = [(list(range(i, i + 4)), 4) for i in (0, 4, 8)]
 FIVES = [([0, 1, 2, 3, 4], 5), ([5, 6, 7, 8, 9], 5), ([7, 8, 9, 10, 11], 2)]     # the short last batch moved back
 
 
 @pytest.mark.parametrize("window", ["triangle", "hann"])
-@pytest.mark.parametrize("make", [_indi, _joint], ids=["indi", "joint_indi"])
+@pytest.mark.parametrize("make", [T.indi, T.joint], ids=["indi", "joint_indi"])
 def test_frame_diffusion_is_its_restatement(make, window):
     """frames (2, 40, 57), patch 32, grid 16: 12 tiles in batches of 4, then of 5 with the last moved back"""
     from diffsplitting_amd.data.tiled_predict import predict_stack, predict_stack_frames
-    netG, stack = make(), _stack32()
+    netG, stack = make(), T.stack32()
     got, _ = predict_stack_frames(netG, stack, batch_tiles=4, num_timesteps=3, seed=SEED, window=window)
     assert got["mean"].shape == (2, 40, 57, 2)
-    assert _same(got["mean"], _restated(netG, stack, 3, FOURS, window=window))
+    assert _same(got["mean"], T.restated_frames(netG, stack, 3, FOURS, window=window))
     five, _ = predict_stack_frames(netG, stack, batch_tiles=5, num_timesteps=3, seed=SEED, window=window)
-    assert _same(five["mean"], _restated(netG, stack, 3, FIVES, window=window))
+    assert _same(five["mean"], T.restated_frames(netG, stack, 3, FIVES, window=window))
     unfused, _ = predict_stack(netG, stack, batch_tiles=4, num_timesteps=3, seed=SEED, noise="field", stitch="blend",
                                window=window)
     assert not torch.equal(unfused["mean"], got["mean"])
@@ -206,11 +149,11 @@ def test_frame_diffusion_is_its_restatement(make, window):
 def test_two_samples():
     """sample r takes id_base = r * frames; mean and spread are the float64 Welford of the two restated frame states"""
     from diffsplitting_amd.data.tiled_predict import predict_stack_frames
-    netG, stack = _indi(), _stack32()
+    netG, stack = T.indi(), T.stack32()
     got, _ = predict_stack_frames(netG, stack, batch_tiles=4, num_timesteps=3, seed=SEED, samples=2, return_std=True)
-    xs = [_restated(netG, stack, 3, FOURS, r=r) for r in range(2)]
+    xs = [T.restated_frames(netG, stack, 3, FOURS, r=r) for r in range(2)]
     assert not np.array_equal(xs[0], xs[1])
-    mean, std = _welford(xs)
+    mean, std = T.welford(xs)
     assert _same(got["mean"], mean)
     assert _same(got["std"], std) and bool((got["std"] > 0).any())
 
@@ -220,12 +163,7 @@ def test_two_samples():
 def test_frame_diffusion_does_not_depend_on_the_sharding(world):
     """`world` fresh ranks (parallel.self_launch, under its timeout), gloo transport: on every rank the frames equal
     the one-rank restatement, bitwise (tests/multi_rank_predict_frames.py)"""
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(%d, [%r], timeout=300))\n"
-            % (ROOT, world, os.path.join(ROOT, "tests", "multi_rank_predict_frames.py")))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env["DSX_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=400)
+    r = run_ranks("multi_rank_predict_frames.py", world, backend="gloo", launch_timeout=300, timeout=400)
     assert r.returncode == 0 and "PREDICT_FRAMES_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])
 
 
@@ -267,8 +205,8 @@ def test_frame_diffusion_narrows_what_the_field_leaves():
     over the tiles 1.7e-5 frames, 2.3e-5 field), so the bound is 1.  Random weights only: no trained checkpoint is at hand, so this says nothing about image quality."""
     from diffsplitting_amd import engine
     from diffsplitting_amd.data.tiled_predict import frame_sample, input_frames
-    netG = _indi()
-    stack = _stack((1, 64, 96), 32, 16, seed=2)
+    netG = T.indi()
+    stack = T.stack((1, 64, 96), 32, 16, seed=2)
     plan = stack.plan
     ids = list(range(plan.total))
     assert plan.total == 15 and all(int(v) % 8 == 0 for v in plan.patch_start[:, 1:].reshape(-1))   # no shifted tile
@@ -288,13 +226,13 @@ def test_frame_diffusion_narrows_what_the_field_leaves():
     table = engine.indi_step_table(n, 1.0, netG.e)
     assert abs(float(table.c1[-1]) - 1) < 1e-6
     sd64 = {k: v.detach().double().cpu() for k, v in netG.denoise_fn.state_dict().items()}
-    fields = [_field(plan, 2, SEED, d).astype(np.float64) for d in range(n + 1)]
+    fields = [T.frame_field(plan, 2, SEED, d).astype(np.float64) for d in range(n + 1)]
     x64 = np.concatenate([x_in.cpu().numpy().astype(np.float64)] * 2, axis=-1)
     scale = float((netG.e * torch.Tensor([1.0])).item())
     want = dict(zip(("field", "frames"), oracle_seams(plan, table, sd64, x64, scale, fields)))
-    rms = {k: _seam_rms(plan, got[k])[0] for k in got}
-    rms64 = {k: _seam_rms(plan, want[k])[0] for k in want}
-    assert _seam_rms(plan, got["frames"])[1] == 12
+    rms = {k: T.seam_rms(plan, got[k])[0] for k in got}
+    rms64 = {k: T.seam_rms(plan, want[k])[0] for k in want}
+    assert T.seam_rms(plan, got["frames"])[1] == 12
     ratio, ratio64 = rms["frames"] / rms["field"], rms64["frames"] / rms64["field"]
     print(f"\nseam rms over 12 seams: frames {rms['frames']:.6f}, field {rms['field']:.6f}, ratio {ratio:.6f}; float64 "
           f"oracle: frames {rms64['frames']:.6f}, field {rms64['field']:.6f}, ratio {ratio64:.6f}")
@@ -306,12 +244,11 @@ def test_frame_diffusion_narrows_what_the_field_leaves():
 # ----------------------------------------------------------------------------- 7. split, end to end
 def split_frame_runs(tmp_path, runs):
     """fresh `split` processes at once on a tiny indi config -> the bytes of every --out"""
-    from tests.test_gpu_boundary import _tiny_indi_section
     cfg = {"name": "tiny_indi", "phase": "val", "gpu_ids": [0],
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
            "datasets": {"patch_size": 32, "max_qval": 0.98, "upper_clip": False, "train": {"name": "Hagen"},
                         "val": {"name": "Hagen"}},
-           "model": _tiny_indi_section()}
+           "model": nets.tiny_indi_section()}
     cfg_path = str(tmp_path / "tiny_indi.json")
     with open(cfg_path, "w") as f:
         json.dump(cfg, f)

@@ -16,19 +16,15 @@ import torch
 
 from oracle import cases, samplers
 from oracle.unet import time_predictor_forward, unet_forward
+from tests import nets
 from tests.gpu_util import DrawRecorder, build_engine, maxabs, psnr
+from tests.nets import dev  # noqa: F401  (the fixture)
 from tests.util import golden_state_dict
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 FP32_TOL = 1e-3
 PSNR_MIN = 35.0
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 def _check_digest(y, g, atol=FP32_TOL):
@@ -100,13 +96,12 @@ def test_c3_indi_512_through_the_sampler_class(dev):
 def test_c5_joint_indi_and_time_predictor_512(dev):
     from diffsplitting_amd.model import networks
     from diffsplitting_amd.model.ddpm_modules.time_predictor import TimePredictor
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
     sd, g = golden_state_dict("full_c5_joint")
     case = cases.FULLSIZE_CASES["c5_joint_512"]
     x_in = cases.make_fullsize_input("c5_x", (1, 1, 512, 512))
     rec = DrawRecorder(cases.LOOP_SEED)
     ref = samplers.joint_indi_inference(sd, case["cfg"], x_in, 3, 1, randn=rec, continuous=True, t_float_start=0.5).numpy()
-    netG = networks.define_G(_opt(_tiny_indi_section(1, 1, "joint_indi"))).cuda()
+    netG = networks.define_G(nets.opt(nets.tiny_indi_section(1, 1, "joint_indi"))).cuda()
     netG.load_state_dict(sd, strict=True)
     netG.set_new_noise_schedule({"n_timestep": 3}, "cuda")
     torch.manual_seed(cases.LOOP_SEED)

@@ -8,7 +8,9 @@ import pytest
 import torch
 
 from tests import blend_ref, solver_ref
-from tests.test_gpu_field import (SEED, TINY, _crops, _run, _seam_rms, _sr3, _stack, _stack32, _welford, same_bits)
+from tests import tiled_util as T
+from tests.bits import same_bits
+from tests.tiled_util import SEED, TINY
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -22,7 +24,7 @@ BATCH = 4
 def test_one_tile_per_frame_is_the_unfused_chain(name):
     """frames (2, 32, 32), patch 32: gather and blend are copies, so fusion is ``solver_sample_loop`` row by row"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    smp, stack, solver = _sr3(), _stack((2, 32, 32), 32, 16), SOLVERS[name]
+    smp, stack, solver = T.sr3(), T.stack((2, 32, 32), 32, 16), SOLVERS[name]
     assert stack.plan.total == 2
     kw = dict(batch_tiles=2, solver=solver, seed=SEED, noise="field")
     want, _ = predict_stack(smp, stack, **kw)
@@ -58,7 +60,7 @@ def _restated(smp, stack, solver, batch, id_base=0, window="triangle", reverse=T
             col = lambda name: torch.full((B,), float(getattr(table, name)[s]), device="cuda")
             x = torch.from_numpy(cut[chunk]).cuda()
             net = smp.denoise_fn(torch.cat([stack.tiles(chunk)["input"], x], dim=1), col("tcond").view(B, 1))
-            z = _crops(plan, chunk, Cn, SEED, s + 1, id_base) if table.sigma[s] != 0 else None
+            z = T.crops(plan, chunk, Cn, SEED, s + 1, id_base) if table.sigma[s] != 0 else None
             prev = torch.from_numpy(cut0[chunk]).cuda() if table.cp[s] != 0 else None
             x0, xo = engine.solver_step(x, net, col("a"), col("b"), col("cx"), col("c0"), col("sigma"),
                                         cp=None if prev is None else col("cp"), x0_prev=prev, clip=table.clip, z=z)
@@ -73,7 +75,7 @@ def _restated(smp, stack, solver, batch, id_base=0, window="triangle", reverse=T
 def test_fusion_is_its_restatement(name):
     """frames (2, 40, 57), patch 32, grid 16: 12 tiles in batches of 4, a shifted last row and column"""
     from diffsplitting_amd.data.tiled_predict import fused_sample, predict_stack
-    smp, stack, solver = _sr3(), _stack32(), SOLVERS[name]
+    smp, stack, solver = T.sr3(), T.stack32(), SOLVERS[name]
     plan = stack.plan
     table = smp.solver_table(**solver)
     assert bool(np.any(table.cp != 0)) == (name == "dpmpp2m") and bool(np.any(table.sigma != 0)) == (name == "ddim")
@@ -94,7 +96,7 @@ def test_fusion_is_its_restatement(name):
 def test_a_short_last_batch_is_moved_back():
     """12 tiles in batches of 5: the last batch is tiles 7..11, of which 10 and 11 are kept; one batch size throughout"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    smp, stack, solver = _sr3(), _stack32(), SOLVERS["dpmpp2m"]
+    smp, stack, solver = T.sr3(), T.stack32(), SOLVERS["dpmpp2m"]
     got, _ = predict_stack(smp, stack, batch_tiles=5, solver=solver, seed=SEED, noise="field", fuse=True)
     assert bool(torch.isfinite(got["mean"]).all())
     # every tile of the restatement in a batch of 5 as well: batches 0..4, 5..9 and 7..11, the last keeping two
@@ -132,13 +134,13 @@ def _restated_batches(smp, stack, solver, batches):
 def test_fusion_two_samples():
     """sample r takes id_base = r * frames; mean and spread are the float64 Welford of the two restated frame states"""
     from diffsplitting_amd.data.tiled_predict import predict_stack
-    smp, stack, solver = _sr3(), _stack32(), SOLVERS["ddim"]
+    smp, stack, solver = T.sr3(), T.stack32(), SOLVERS["ddim"]
     N = stack.plan.data_shape[0]
     got, _ = predict_stack(smp, stack, batch_tiles=BATCH, solver=solver, seed=SEED, noise="field", fuse=True, samples=2,
                            return_std=True)
     xs = [_restated(smp, stack, solver, BATCH, id_base=r * N)[0] for r in range(2)]
     assert not np.array_equal(xs[0], xs[1])
-    mean, std = _welford(xs)
+    mean, std = T.welford(xs)
     assert same_bits(got["mean"].cpu(), torch.from_numpy(mean))
     assert same_bits(got["std"].cpu(), torch.from_numpy(std)) and bool((got["std"] > 0).any())
 
@@ -182,8 +184,8 @@ def test_fusion_narrows_what_the_field_leaves():
     tiles 2.5e-6 fused, 4.2e-6 field), so the bound is 0.0399."""
     from diffsplitting_amd import engine
     from diffsplitting_amd.data.tiled_predict import fused_sample
-    smp = _sr3()
-    stack = _stack((1, 64, 96), 32, 16, seed=2)
+    smp = T.sr3()
+    stack = T.stack((1, 64, 96), 32, 16, seed=2)
     plan = stack.plan
     ids = list(range(plan.total))
     assert plan.total == 15 and all(int(v) % 8 == 0 for v in plan.patch_start[:, 1:].reshape(-1))   # no shifted tile
@@ -192,7 +194,7 @@ def test_fusion_narrows_what_the_field_leaves():
     x = stack.tiles(ids)["input"]
     try:
         smp.noise_field = lambda shape, draw: plan.randn_field(ids, shape[1], SEED, draw)
-        got = {"field": _run(smp, x, solver).cpu().numpy()}
+        got = {"field": T.run(smp, x, solver).cpu().numpy()}
     finally:
         smp.noise_field = None
     plan.set_window("triangle")
@@ -201,12 +203,12 @@ def test_fusion_narrows_what_the_field_leaves():
     assert len(rows) == 4
     got["fused"] = rows[-1].cpu().numpy()
     start = engine.randn_samples((1, 2, 64, 96), SEED, [0], draw=0)
-    assert same_bits(plan.gather_canvas(start.permute(0, 2, 3, 1).contiguous()), _crops(plan, ids, 2, SEED, 0))
+    assert same_bits(plan.gather_canvas(start.permute(0, 2, 3, 1).contiguous()), T.crops(plan, ids, 2, SEED, 0))
     sd64 = {k: v.double() for k, v in smp.weights.items()}
     want = dict(zip(("field", "fused"), oracle_seams(plan, table, sd64, x.cpu().numpy(), start.cpu().numpy())))
-    rms = {k: _seam_rms(plan, got[k])[0] for k in got}
-    rms64 = {k: _seam_rms(plan, want[k])[0] for k in want}
-    assert _seam_rms(plan, got["fused"])[1] == 12
+    rms = {k: T.seam_rms(plan, got[k])[0] for k in got}
+    rms64 = {k: T.seam_rms(plan, want[k])[0] for k in want}
+    assert T.seam_rms(plan, got["fused"])[1] == 12
     ratio, ratio64 = rms["fused"] / rms["field"], rms64["fused"] / rms64["field"]
     print(f"\nseam rms over 12 seams before the last blend: fused {rms['fused']:.6f}, field {rms['field']:.6f}, ratio "
           f"{ratio:.6f}; float64 oracle: fused {rms64['fused']:.6f}, field {rms64['field']:.6f}, ratio {ratio64:.6f}")
@@ -219,7 +221,6 @@ def test_fusion_narrows_what_the_field_leaves():
 # ----------------------------------------------------------------------------- 4. split, end to end
 def test_split_fuse_steps_end_to_end(tmp_path):
     """fresh processes at once: --fuse-steps twice (byte for byte the same file), the unfused field run blended and cropped"""
-    from tests.test_gpu_blend import split_runs
-    data = split_runs(tmp_path, {"a": ["--fuse-steps"], "b": ["--fuse-steps"], "blend": ["--stitch", "blend"], "crop": []},
+    data = T.split_runs(tmp_path, {"a": ["--fuse-steps"], "b": ["--fuse-steps"], "blend": ["--stitch", "blend"], "crop": []},
                       extra=["--noise-field"])
     assert data["a"] == data["b"] and data["a"] != data["blend"] and data["a"] != data["crop"]

@@ -38,9 +38,11 @@ import torch
 
 from oracle import cases
 from oracle.unet import unet_forward
-from oracle.weights import synth_state_dict
+from tests import nets
 from tests.gpu_util import maxabs
 from tests.layer_check import DT, check_plan, group_reach_tags, inputs
+from tests.nets import dev  # noqa: F401  (the fixture)
+from tests.plan_cases import GROUP_PLANS as PLANS, GROUP_REACH as REACH, GROUP_REACH_EXEMPT as REACH_EXEMPT
 from tests.plan_dump import read_dump
 
 pytestmark = pytest.mark.gpu
@@ -50,40 +52,9 @@ FP32_TOL = 1e-3        # tests/test_gpu_parity.py: the project's figure for the 
 SEED = 37
 FLAT_LEVEL = 8.0       # the uniform background of the flat plans: |mean| / std <= 8 / sqrt(eps) = 2530
 
-# k_conv_ws wherever it fits (g2: its 16 x 16 level on the persistent kernel, three hosted finalizes of 128 channels per
-# group, k_gn_finalize launches with four partial rows); no hosted finalize (the same GroupNorms by launches of their own)
-_WS = {"DSX_WS_MIN_GRID": "1"}
-_NO_HOST = {"DSX_HOST_FIN": "0"}
-# any grid fills the chip and the persistent kernel is off: other tiles, so other partial-row counts per source
-_WIDE_TILES = {"DSX_MIN_GRID": "1", "DSX_WS": "0"}
-
-# id -> (case, dtype, env, flat).  Every case in every operand type at default knobs; a flat plan per case in f32 and bf16.
-PLANS = {}
-for _c in cases.GROUP_CASES:
-    for _d in ("bf16", "f16", "f32"):
-        PLANS[f"{_c}_{_d}"] = (_c, _d, {}, False)
-    for _d in ("f32", "bf16"):
-        PLANS[f"{_c}_{_d}_flat"] = (_c, _d, {}, True)
-PLANS["g2_bf16_ws"] = ("g2", "bf16", _WS, False)
-PLANS["g2_f32_ws"] = ("g2", "f32", _WS, False)
-PLANS["g1_f16_no_host"] = ("g1", "f16", _NO_HOST, False)
-PLANS["g1_bf16_wide_tiles"] = ("g1", "bf16", _WIDE_TILES, False)
-
-# What must have been checked, per operand type, after every plan ran (test_reach; layer_check.group_reach_tags derives
-# them from the dumped launches).
-REACH = ("fin>64", "wide own>64", "wide>256", "hosted>64", "straddle>64", "f32part>64", "shifted>64", "8x8 no img",
-         "npow2>64")
-REACH_EXEMPT = {}      # dtype -> {tag: reason}: every operand type reaches every tag (g1 at default knobs alone does)
-
 _CHECKED = {}          # plan -> {dtype, reach, layers, worst, flat_wide}
 _SD = {}               # case -> state dict
 _ORACLE = {}           # case -> float64 oracle output
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 def case_inputs(name, flat=False):
@@ -96,13 +67,7 @@ def case_inputs(name, flat=False):
 def state_dict(name):
     """synthetic weights for the engine's own parameter table (no fixture: the engine names its parameters)"""
     if name not in _SD:
-        from diffsplitting_amd import engine
-        case = cases.GROUP_CASES[name]
-        cfg = case["cfg"]
-        eng = engine.UNetEngine(engine.make_cfg(case["flavour"], cfg["in_channel"], cfg["out_channel"],
-                                                cfg["inner_channel"], cfg["norm_groups"], cfg["channel_mults"],
-                                                cfg["attn_res"], cfg["res_blocks"], cfg["image_size"]), case["flavour"])
-        _SD[name] = synth_state_dict(zip(eng.param_names, eng.param_shapes), seed=SEED)
+        _SD[name] = nets.engine_state_dict(cases.GROUP_CASES[name], SEED)
     return _SD[name]
 
 

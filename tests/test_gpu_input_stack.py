@@ -7,17 +7,11 @@ import json
 import numpy as np
 import pytest
 import torch
+from tests import nets
+from tests.bits import same_bits
 
 pytestmark = pytest.mark.gpu
 SEED = 11
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 # ----------------------------------------------------------------------------- gather
@@ -199,13 +193,6 @@ def test_moments_python_face_refuses_what_the_kernel_cannot_take():
 SHAPE, PATCH, GRID, BATCH, STEPS = (3, 96, 160), 64, 32, 4, 2
 
 
-def _tiny_section():
-    from tests.test_gpu_boundary import _tiny_indi_section
-    sec = _tiny_indi_section()
-    sec["unet"]["channel_multiplier"] = [1, 2, 4, 8]
-    return sec
-
-
 @pytest.fixture(scope="module")
 def world():
     """The tiny InDI network of tests/multi_rank_predict_seeded.py, the two channels, their sum as a uint16 stack and the
@@ -213,11 +200,10 @@ def world():
     from diffsplitting_amd.data.input_stack import InputStackTiledPred
     from diffsplitting_amd.data.tiled_predict import predict_stack
     from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt
     from tests.util import golden_state_dict
     torch.set_grad_enabled(False)
     sd, _ = golden_state_dict("unet_hagen_64")
-    netG = networks.define_G(_opt(_tiny_section())).cuda()
+    netG = networks.define_G(nets.opt(nets.hagen64_section())).cuda()
     netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()})
     assert netG.e == 0.01                                             # the sampler's own noise scale: the draws matter
     c0, c1 = _channels(SHAPE, 3000, 21)
@@ -283,7 +269,7 @@ def test_command_line_round_trip(world, tmp_path, monkeypatch):
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
            "datasets": {"patch_size": PATCH, "max_qval": 0.98, "upper_clip": False, "channel_weights": [1, 1],
                         "train": {"name": "Hagen"}, "val": {"name": "Hagen"}},
-           "model": _tiny_section()}
+           "model": nets.hagen64_section()}
     cfg_path = str(tmp_path / "tiny.json")
     with open(cfg_path, "w") as f:
         json.dump(cfg, f)

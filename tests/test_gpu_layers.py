@@ -15,6 +15,7 @@ import torch
 
 from oracle import cases
 from tests.layer_check import DT, KNOWN_TAGS, check_plan, inputs
+from tests.nets import dev  # noqa: F401  (the fixture)
 from tests.util import golden_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -73,12 +74,6 @@ EXEMPT = {
 REQUIRED_TAGS = {dt: KNOWN_TAGS - set(EXEMPT) for dt in DT}
 
 _CHECKED = {}          # plan -> {dtype, tags, layers, worst}
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 def _check_plan(plan, dev, monkeypatch, flat=False):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import nets
 from tests import lpips_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -137,12 +138,9 @@ def test_predict_tiled_returns_lpips_of_its_stitched_output(model):
     from diffsplitting_amd.core.metrics import calculate_lpips
     from diffsplitting_amd.data.tiled_predict import predict_tiled
     from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
     from tests.util import golden_state_dict
     usd, _ = golden_state_dict("unet_hagen_64")
-    sec = _tiny_indi_section()
-    sec["unet"]["channel_multiplier"] = [1, 2, 4, 8]
-    netG = networks.define_G(_opt(sec)).cuda()
+    netG = networks.define_G(nets.opt(nets.hagen64_section())).cuda()
     netG.load_state_dict({"denoise_fn." + k: v for k, v in usd.items()})
     netG.e = 0.0
     rng = np.random.default_rng(5)

@@ -4,7 +4,6 @@ the fp32 restatement of tests/mixed_ref.py and within its derived bound of the f
 items against the reference's, and the two drivers against the same pipelines built from the oracle.
 
 Measured on the MI355X (figures printed by the tests, `-s`): see the docstrings below."""
-import json
 import types
 
 import numpy as np
@@ -13,8 +12,9 @@ import torch
 
 from oracle import cases, samplers, tiling
 from oracle.unet import time_predictor_forward
-from oracle.weights import synth_state_dict
 from tests import mixed_ref as MR
+from tests import mixed_util as MU
+from tests.bits import same_bits
 from tests.gpu_util import maxabs
 from tests.util import load_golden
 
@@ -22,11 +22,6 @@ pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 FP32_TOL = 1e-3
 T_VALUES = [0.0, 0.1, 0.29, 0.5, 1.0]
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 def _table_array(tab):
@@ -72,11 +67,11 @@ def test_range_table_bitwise_equal_to_the_reference_and_repeatable():
             a = _table_array(compute_input_normalization_dict(dev, n, mean, std))
             b = _table_array(compute_input_normalization_dict(dev, n, mean.reshape(-1, 1, 1), std.reshape(-1, 1, 1)))
             ref = g[f"{name}_table_{n}"]
-            assert np.array_equal(_bits(a), _bits(ref)), (name, n, np.abs(a - ref).max())
-            assert np.array_equal(_bits(a), _bits(b)), (name, n)
+            assert same_bits(a, ref), (name, n, np.abs(a - ref).max())
+            assert same_bits(a, b), (name, n)
         # host frames (a list of uint16 arrays, as the reference holds them) are uploaded
         c = _table_array(compute_input_normalization_dict({0: [x for x in ch0], 1: [x for x in ch1]}, 20, mean, std))
-        assert np.array_equal(_bits(c), _bits(g[f"{name}_table_20"]))
+        assert same_bits(c, g[f"{name}_table_20"])
 
 
 @pytest.mark.parametrize("name", ["c", "a"])
@@ -87,7 +82,7 @@ def test_mixed_tiles_bitwise_equal_to_the_fp32_restatement(name):
     g = load_golden("mix_range")
     ds, ch0, ch1 = _tiled(g, name)
     table = compute_input_normalization_dict(ds._data_dict, 100, ds._mean_target, ds._std_target)
-    assert np.array_equal(_bits(_table_array(table)), _bits(g[f"{name}_table_100"]))
+    assert same_bits(_table_array(table), g[f"{name}_table_100"])
     seq = list(range(1, len(ds), 3))                                    # a shard: through the plan's device tables
     irregular = [len(ds) - 1, 0, 7, 7, 3]                               # through the per-call host table
     worst = 0.0
@@ -101,8 +96,8 @@ def test_mixed_tiles_bitwise_equal_to_the_fp32_restatement(name):
             lohi = MR.rows(g[f"{name}_table_100"], t)
             mix, cls = MR.chain_f32(t0, t1, t, lohi)
             got_mix, got_cls = out["mix"].cpu().numpy(), out["cls"].cpu().numpy()
-            assert np.array_equal(_bits(got_mix), _bits(np.moveaxis(mix, 0, 1))), (name, t)
-            assert np.array_equal(_bits(got_cls), _bits(np.moveaxis(cls, 0, 1))), (name, t)
+            assert same_bits(got_mix, np.moveaxis(mix, 0, 1)), (name, t)
+            assert same_bits(got_cls, np.moveaxis(cls, 0, 1)), (name, t)
             m64, c64 = MR.chain_f64(t0, t1, t, lohi)
             bm, bc = MR.chain_bound(t0, t1, t, lohi)
             em = np.abs(np.moveaxis(got_mix, 1, 0) - m64)
@@ -123,7 +118,7 @@ def test_mixed_tiles_bitwise_equal_to_the_fp32_restatement(name):
         t0, t1 = _ref_tiles(base, ch0, ch1, ids)
         out = base.mixed_tiles(ids, 0.29, table)
         mix, cls = MR.chain_f32(t0, t1, 0.29, MR.rows(g[f"{name}_table_100"], 0.29))
-        assert np.array_equal(_bits(out["cls"].cpu().numpy()), _bits(np.moveaxis(cls, 0, 1)))
+        assert same_bits(out["cls"].cpu().numpy(), np.moveaxis(cls, 0, 1))
 
 
 def test_time_predictor_dataset_items_equal_the_reference():
@@ -134,7 +129,7 @@ def test_time_predictor_dataset_items_equal_the_reference():
     nd.update({k: g[f"ds_{k}"] for k in ("mean_input", "std_input", "target0_max", "target1_max", "input_max")})
     ds = TimePredictorDataset("Hagen", DataLocation(arrays=(g["c_ch0"], g["c_ch1"])), 32, max_qval=0.98,
                               normalization_dict=nd, step_size=0.25)
-    assert np.array_equal(_bits(_table_array(ds.input_normalization_dict)), _bits(g["c_table_100"]))
+    assert same_bits(_table_array(ds.input_normalization_dict), g["c_table_100"])
     assert len(ds) == 8
     np.random.seed(int(g["item_seed"]))
     for k, idx in enumerate(g["item_indices"]):
@@ -142,7 +137,7 @@ def test_time_predictor_dataset_items_equal_the_reference():
         ref = g["item_inp"][k]
         assert t == float(g["item_t"][k]) and inp.shape == (1, 32, 32) and inp.dtype == np.float32
         if ref.dtype == np.float32:
-            assert np.array_equal(_bits(inp), _bits(ref))
+            assert same_bits(inp, ref)
         else:                                                       # fixture made under numpy 2: see mixed_ref
             n, y, x = ds.patch_location(int(idx))
             t0 = MR.normalize(g["c_ch0"][n, y:y + 32, x:x + 32], nd["mean_target"][0], nd["std_target"][0])
@@ -150,7 +145,7 @@ def test_time_predictor_dataset_items_equal_the_reference():
             row = g["c_table_100"][int(round(t * 100))]
             lohi = (row[0], row[1]) * 2
             _, cls = MR.chain_f32(t0, t1, t, lohi)
-            assert np.array_equal(_bits(inp[0]), _bits(cls[1]))     # the float32 chain, bitwise
+            assert same_bits(inp[0], cls[1])     # the float32 chain, bitwise
             _, bound = MR.chain_bound(t0, t1, t, lohi)
             err = np.abs(inp[0].astype(np.float64) - ref[0])
             print(f"item {idx}: max err {err.max():.3e} (bound there {bound[1].reshape(-1)[err.argmax()]:.3e})")
@@ -161,47 +156,11 @@ def test_time_predictor_dataset_items_equal_the_reference():
 
 
 # ---- the drivers against the oracle ---------------------------------------------------------------------------------
-def _frames(shape, seed):
-    rng = np.random.default_rng(seed)
-    return (np.minimum(rng.gamma(2.0, 150.0, size=shape), 4000).astype(np.uint16),
-            np.minimum(rng.gamma(3.0, 70.0, size=shape), 4000).astype(np.uint16))
-
-
-def _networks(nsteps):
-    from diffsplitting_amd.model.ddpm_modules.time_predictor import TimePredictor
-    from diffsplitting_amd.model.ddpm_modules.unet import UNet
-    from diffsplitting_amd.model.samplers import InDISampler
-    g = load_golden("refine_n1")
-    keys = {k: [(a, tuple(s)) for a, s in json.loads(bytes(g[k]).decode())] for k in ("keys1", "keys2", "keys_tp")}
-    c = cases.UNET_CASES["joint_32"]["cfg"]
-    sds = {"keys1": synth_state_dict(keys["keys1"], 1), "keys2": synth_state_dict(keys["keys2"], 2),
-           "keys_tp": synth_state_dict(keys["keys_tp"], 0)}
-
-    def sampler(sd):
-        net = UNet(in_channel=1, out_channel=1, inner_channel=c["inner_channel"], norm_groups=c["norm_groups"],
-                   channel_mults=c["channel_mults"], attn_res=c["attn_res"], res_blocks=c["res_blocks"], image_size=32)
-        s = InDISampler(net, 32, channels=1, out_channel=1, conditional=False, val_schedule_opt={"n_timestep": nsteps}).cuda()
-        s.load_state_dict(sd, strict=True)
-        s.set_new_noise_schedule({"n_timestep": nsteps}, "cuda")
-        return s
-
-    tp = TimePredictor(**cases.TIME_PRED_CFG).cuda()
-    tp.load_state_dict(sds["keys_tp"], strict=True)
-    return sampler(sds["keys1"]), sampler(sds["keys2"]), tp, sds, c
-
-
-def _dataset(shape, seed, patch=32, grid=16):
-    from diffsplitting_amd.data.split_dataset import DataLocation, SplitDatasetTiledPred
-    ch0, ch1 = _frames(shape, seed)
-    ds = SplitDatasetTiledPred("Hagen", DataLocation(arrays=(ch0, ch1)), patch, grid_size=grid, max_qval=0.98)
-    return ds, ch0, ch1
-
-
 def test_evaluate_time_predictor_against_the_oracle():
     """18 tiles of 32 x 32 in batches of 8 (the last one padded by overlap), 21 mixing ratios."""
     from diffsplitting_amd.data.tiled_predict import evaluate_time_predictor
-    _, _, tp, sds, _ = _networks(1)
-    ds, ch0, ch1 = _dataset((2, 64, 64), 5)
+    _, _, tp, sds, _ = MU.networks(1)
+    ds, ch0, ch1 = MU.dataset((2, 64, 64), 5)
     n = 20
     all_pred, rmse = evaluate_time_predictor(ds, tp, num_timesteps=n, batch_tiles=8)
     assert all_pred.shape == (n + 1, len(ds)) and all_pred.dtype == np.float32 and len(ds) == 18
@@ -224,8 +183,8 @@ def test_predict_tiled_mixed_against_the_oracle():
     from diffsplitting_amd.core.psnr import RangeInvariantPsnr
     from diffsplitting_amd.data.tiled_predict import predict_tiled_mixed
     from diffsplitting_amd.data.time_predictor_dataset import compute_input_normalization_dict
-    i1, i2, tp, sds, cfg = _networks(1)
-    ds, ch0, ch1 = _dataset((2, 96, 96), 9)
+    i1, i2, tp, sds, cfg = MU.networks(1)
+    ds, ch0, ch1 = MU.dataset((2, 96, 96), 9)
     netG = types.SimpleNamespace(indi1=i1, indi2=i2, noise_source=None)
     mixing_t, T = 0.29, len(ds)
     assert T == 50
@@ -246,7 +205,7 @@ def test_predict_tiled_mixed_against_the_oracle():
     assert canvas.shape == (2, 96, 96, 2) and psnr.shape == (2, 2) and pred_t.shape == (T, 2)
     # the same pipeline from the oracle, tile by tile in the notebook's order (cells 59-64)
     tab = MR.range_table(ch0, ch1, 100, ds._mean_target.reshape(-1), ds._std_target.reshape(-1))
-    assert np.array_equal(_bits(_table_array(table)), _bits(tab))
+    assert same_bits(_table_array(table), tab)
     t0, t1 = _ref_tiles(ds, ch0, ch1, range(T))
     mix, cls = MR.chain_f32(t0, t1, mixing_t, MR.rows(tab, mixing_t))
     osd1, osd2 = sds["keys1"], sds["keys2"]                            # the samplers' keys: "denoise_fn." + the UNet's

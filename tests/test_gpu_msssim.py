@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import nets
 from tests import msssim_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -159,11 +160,10 @@ def test_split_ms_ssim(tmp_path, caplog):
     measured here with the restatement on both (printed; 5.5e-9 on the MI355X) and held a decade under the
     tolerance."""
     from diffsplitting_amd import split
-    from tests.test_gpu_boundary import _tiny_indi_section
     M = _m()
     cfg = {"name": "tiny_hagen_indi", "phase": "train", "gpu_ids": [0],
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
-           "datasets": {"val": {"name": "Hagen", "patch_size": 64, "datatype": "img"}}, "model": _tiny_indi_section()}
+           "datasets": {"val": {"name": "Hagen", "patch_size": 64, "datatype": "img"}}, "model": nets.tiny_indi_section()}
     cfg_path = tmp_path / "tiny.json"
     cfg_path.write_text(json.dumps(cfg, indent=2))
     t, _ = _pair((2, 2, 192, 192), 9)

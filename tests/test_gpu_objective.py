@@ -6,20 +6,14 @@ import pytest
 import torch
 
 from oracle import cases
+from tests import nets
+from tests.bits import bits, same_bits
 from tests.util import golden_state_dict
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 FP32_TOL = 1e-3          # the project's per-pixel fp32 bound on a UNet output
 N_INDI = 20
-
-
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def _bit_equal(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
 def _ref_q(x0, c0, c2, z, xe=None, c1=None):
@@ -29,10 +23,6 @@ def _ref_q(x0, c0, c2, z, xe=None, c1=None):
     if xe is not None:
         out = out + v(c1) * torch.cat([xe] * (x0.shape[1] // xe.shape[1]), dim=1)
     return out + v(c2) * z
-
-
-def _rand(shape, seed):
-    return torch.randn(shape, generator=torch.Generator().manual_seed(seed))
 
 
 COEF = (torch.tensor([0.75623951, 0.31, 0.9990234]), torch.tensor([0.1, 1.0, 0.45]), torch.tensor([0.654321, 0.0123, 0.7]))
@@ -51,13 +41,13 @@ COEF = (torch.tensor([0.75623951, 0.31, 0.9990234]), torch.tensor([0.1, 1.0, 0.4
 def test_q_sample_bit_exact(shape, Ce):
     from diffsplitting_amd import engine
     B, Cn, H, W = shape
-    x0, z = _rand(shape, 1), _rand(shape, 2)
-    xe = _rand((B, Ce, H, W), 3) if Ce else None
+    x0, z = nets.rand(shape, 1), nets.rand(shape, 2)
+    xe = nets.rand((B, Ce, H, W), 3) if Ce else None
     c0, c1, c2 = COEF
     ref = _ref_q(x0, c0, c2, z, xe, c1 if Ce else None)
     out, z_used = engine.q_sample(x0.cuda(), c0.cuda(), c2.cuda(), xe=None if xe is None else xe.cuda(),
                                   c1=c1.cuda() if Ce else None, z=z.cuda())
-    assert _bit_equal(out, ref) and _bit_equal(z_used, z)
+    assert same_bits(out, ref) and same_bits(z_used, z)
 
 
 @pytest.mark.parametrize("H,W", [(5, 7), (8, 12)])
@@ -66,12 +56,12 @@ def test_q_sample_channel_offset_leaves_the_rest_untouched(H, W):
     sentinel."""
     from diffsplitting_amd import engine
     shape = (3, 2, H, W)
-    x0, z, xe = _rand(shape, 4), _rand(shape, 5), _rand((3, 1, H, W), 6)
+    x0, z, xe = nets.rand(shape, 4), nets.rand(shape, 5), nets.rand((3, 1, H, W), 6)
     c0, c1, c2 = COEF
     dst = torch.full((3, 5, H, W), -7.25, device="cuda")
     out, _ = engine.q_sample(x0.cuda(), c0.cuda(), c2.cuda(), xe=xe.cuda(), c1=c1.cuda(), z=z.cuda(), dst=dst, coff=3)
     assert out is dst
-    assert _bit_equal(dst[:, 3:5], _ref_q(x0, c0, c2, z, xe, c1))
+    assert same_bits(dst[:, 3:5], _ref_q(x0, c0, c2, z, xe, c1))
     assert bool((dst[:, :3] == -7.25).all())
 
 
@@ -80,50 +70,50 @@ def test_q_sample_unaligned_base_pointers_take_the_scalar_path():
     from diffsplitting_amd import engine
     shape = (3, 2, 8, 12)
     n = 3 * 2 * 8 * 12
-    x0, z = _rand(shape, 7), _rand(shape, 8)
+    x0, z = nets.rand(shape, 7), nets.rand(shape, 8)
     c0, _, c2 = COEF
     off = lambda t: torch.cat([torch.zeros(1), t.reshape(-1)]).cuda()[1:].view(t.shape)
     xo, zo = off(x0), off(z)
     assert xo.data_ptr() % 16 == 4 and xo.is_contiguous()
     dst = torch.zeros(n + 1, device="cuda")[1:].view(shape)
     engine.q_sample(xo, c0.cuda(), c2.cuda(), z=zo, dst=dst)
-    assert _bit_equal(dst, _ref_q(x0, c0, c2, z))
+    assert same_bits(dst, _ref_q(x0, c0, c2, z))
 
 
 @pytest.mark.parametrize("shape", [(3, 2, 5, 7), (3, 2, 8, 12)])
 def test_q_sample_two_terms_add_no_zero_term(shape):
     """x0 = -0.0 and z = -0.0 at the same places: c0*x0 + c2*z = -0.0, while a third term +0.0 would give +0.0."""
     from diffsplitting_amd import engine
-    x0, z = _rand(shape, 9), _rand(shape, 10)
+    x0, z = nets.rand(shape, 9), nets.rand(shape, 10)
     x0.view(-1)[::3] = -0.0
     z.view(-1)[::3] = -0.0
     c0, _, c2 = COEF
     ref = _ref_q(x0, c0, c2, z)
-    assert bool((_bits(ref).view(-1)[::3] == -2 ** 31).all())           # the sign bit alone: -0.0
+    assert bool((bits(ref).view(-1)[::3] == -2 ** 31).all())           # the sign bit alone: -0.0
     out, _ = engine.q_sample(x0.cuda(), c0.cuda(), c2.cuda(), z=z.cuda())
-    assert _bit_equal(out, ref)
+    assert same_bits(out, ref)
 
 
 # ----------------------------------------------------------------------------- q_sample, Philox z
 @pytest.mark.parametrize("shape", [(3, 2, 5, 7), (3, 3, 8, 12), (2, 1, 64, 67)])
 def test_q_sample_philox_path(shape):
     from diffsplitting_amd import engine
-    x0 = _rand(shape, 11)
-    xe = _rand((shape[0], 1) + shape[2:], 12)
+    x0 = nets.rand(shape, 11)
+    xe = nets.rand((shape[0], 1) + shape[2:], 12)
     c0, c1, c2 = (c[:shape[0]] for c in COEF)
     args = (x0.cuda(), c0.cuda(), c2.cuda())
     for kw in (dict(), dict(xe=xe.cuda(), c1=c1.cuda())):
         out, z = engine.q_sample(*args, seed=1234, subsequence=5, want_z=True, **kw)
-        assert _bit_equal(z, engine.randn(shape, 1234, 5))               # what dsx_randn writes for (seed, subsequence)
+        assert same_bits(z, engine.randn(shape, 1234, 5))               # what dsx_randn writes for (seed, subsequence)
         inj, _ = engine.q_sample(*args, z=z, **kw)
-        assert _bit_equal(out, inj)
-        assert _bit_equal(out, _ref_q(x0, c0, c2, z.cpu(), xe if kw else None, c1 if kw else None))
+        assert same_bits(out, inj)
+        assert same_bits(out, _ref_q(x0, c0, c2, z.cpu(), xe if kw else None, c1 if kw else None))
         again, z_none = engine.q_sample(*args, seed=1234, subsequence=5, **kw)
-        assert z_none is None and _bit_equal(again, out)                  # same seed, with and without z_out
+        assert z_none is None and same_bits(again, out)                  # same seed, with and without z_out
         other, _ = engine.q_sample(*args, seed=1235, subsequence=5, **kw)
-        assert not _bit_equal(other, out)
+        assert not same_bits(other, out)
         other, _ = engine.q_sample(*args, seed=1234, subsequence=6, **kw)
-        assert not _bit_equal(other, out)
+        assert not same_bits(other, out)
 
 
 # ----------------------------------------------------------------------------- dsx_loss
@@ -141,7 +131,7 @@ def test_loss_against_float64_numpy(shape, loss_type):
     at most N 2^-53, and the result is rounded to fp32 once."""
     from diffsplitting_amd import engine
     from diffsplitting_amd._lib import lib
-    a, b = _rand(shape, 13), _rand(shape, 14)
+    a, b = nets.rand(shape, 13), nets.rand(shape, 14)
     d = a.numpy().astype(np.float64) - b.numpy().astype(np.float64)
     term = np.abs(d) if loss_type == "l1" else d * d
     want = term.reshape(shape[0], -1).sum(axis=1)
@@ -158,30 +148,16 @@ def test_loss_against_float64_numpy(shape, loss_type):
         got = _loss_sampler(loss_type, reduction)._loss(ag, bg)
         assert got.dtype == torch.float32 and got.dim() == 0 and got.is_cuda and not got.requires_grad
         assert abs(float(got) - ref) / ref <= 2.0 ** -23
-        assert _bit_equal(got, _loss_sampler(loss_type, reduction)._loss(ag, bg))
+        assert same_bits(got, _loss_sampler(loss_type, reduction)._loss(ag, bg))
     zero = engine.loss_per_sample(ag, ag.clone(), squared=loss_type == "l2")
     assert bool((zero == 0).all())                                                        # a == b: exactly 0
 
 
 # ----------------------------------------------------------------------------- parity with the reference
-def _unet(flavour, cfg):
-    from diffsplitting_amd.model.ddpm_modules.unet import UNet as UNetDdpm
-    from diffsplitting_amd.model.sr3_modules.unet import UNet as UNetSr3
-    cls = UNetSr3 if flavour == "sr3" else UNetDdpm
-    return cls(in_channel=cfg["in_channel"], out_channel=cfg["out_channel"], inner_channel=cfg["inner_channel"],
-               norm_groups=cfg["norm_groups"], channel_mults=cfg["channel_mults"], attn_res=cfg["attn_res"],
-               res_blocks=cfg["res_blocks"], image_size=cfg["image_size"])
-
-
 def _hook(net):
     rec = {}
     net.register_forward_hook(lambda m, inp, out: rec.update(x_recon=out))
     return rec
-
-
-def _load(smp, sd, prefix):
-    missing, unexpected = smp.load_state_dict({prefix + k: v for k, v in sd.items()}, strict=False)
-    assert not unexpected and all(not k.startswith("denoise_fn") and ".denoise_fn" not in k for k in missing), missing
 
 
 def _loss64(a, b, loss_type, reduction):
@@ -214,14 +190,14 @@ def _check_recon(name, x_recon, ref):
 def test_p_losses_sr3_matches_the_reference():
     from diffsplitting_amd.model.samplers import GaussianSampler
     sd, g = golden_state_dict("objective_sr3")
-    net = _unet("sr3", cases.UNET_CASES["sr3_tiny"]["cfg"])
+    net = nets.unet("sr3", cases.UNET_CASES["sr3_tiny"]["cfg"])
     smp = GaussianSampler(net, 32, channels=3, loss_type="l1", conditional=True).cuda()
     smp.set_new_noise_schedule(cases.SCHEDULES["lin_25"], "cuda")
     smp.set_loss("cuda")
-    _load(smp, sd, "denoise_fn.")
+    nets.load(smp, sd)
     c = torch.from_numpy(g["continuous_sqrt_alpha_cumprod"])
     target, noise = torch.from_numpy(g["target"]).cuda(), torch.from_numpy(g["noise"]).cuda()
-    assert _bit_equal(smp.q_sample(target, c, noise=noise), torch.from_numpy(g["x_noisy"]))
+    assert same_bits(smp.q_sample(target, c, noise=noise), torch.from_numpy(g["x_noisy"]))
     rec = _hook(net)
     x_in = {"target": target, "input": torch.from_numpy(g["input"]).cuda()}
     loss = smp(x_in, noise, continuous_sqrt_alpha_cumprod=c)
@@ -229,7 +205,7 @@ def test_p_losses_sr3_matches_the_reference():
     _check_loss("sr3", loss, g["loss"], g["noise"], g["x_recon"], "l1", "sum")
     # the seeded host draws reproduce the reference's run: same t, same noise levels, same loss
     np.random.seed(int(g["seed_numpy"]))
-    assert _bit_equal(smp.p_losses(x_in, noise), loss)
+    assert same_bits(smp.p_losses(x_in, noise), loss)
     # device noise: repeatable under torch's seed, finite, and another seed gives another value
     vals = []
     for seed in (1, 1, 2):
@@ -241,43 +217,43 @@ def test_p_losses_sr3_matches_the_reference():
 def test_p_losses_ddpm_matches_the_reference():
     from diffsplitting_amd.model.samplers import GaussianSamplerDdpm
     sd, g = golden_state_dict("objective_ddpm")
-    net = _unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"])
+    net = nets.unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"])
     smp = GaussianSamplerDdpm(net, 32, channels=1, loss_type="l2", lr_reduction="mean", conditional=True).cuda()
     smp.set_new_noise_schedule(cases.SCHEDULES["lin_8"], "cuda")
     smp.set_loss("cuda")
-    _load(smp, sd, "denoise_fn.")
+    nets.load(smp, sd)
     t = torch.from_numpy(g["t"])
     target, noise = torch.from_numpy(g["target"]).cuda(), torch.from_numpy(g["noise"]).cuda()
-    assert _bit_equal(smp.q_sample(target, t.cuda(), noise=noise), torch.from_numpy(g["x_noisy"]))
+    assert same_bits(smp.q_sample(target, t.cuda(), noise=noise), torch.from_numpy(g["x_noisy"]))
     rec = _hook(net)
     x_in = {"target": target, "input": torch.from_numpy(g["input"]).cuda()}
     loss = smp(x_in, noise, t=t)
     _check_recon("ddpm", rec["x_recon"], g["x_recon"])
     _check_loss("ddpm", loss, g["loss"], g["noise"], g["x_recon"], "l2", "mean")
     torch.manual_seed(int(g["seed_torch"]))                   # the reference's own draw of t
-    assert _bit_equal(smp.p_losses(x_in, noise), loss)
+    assert same_bits(smp.p_losses(x_in, noise), loss)
 
 
 def test_p_losses_indi_matches_the_reference():
     from diffsplitting_amd.model.samplers import InDISampler
     sd, g = golden_state_dict("objective_indi")
-    net = _unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"])
+    net = nets.unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"])
     smp = InDISampler(net, 32, channels=2, loss_type="l1", out_channel=2, conditional=False,
                       val_schedule_opt={"n_timestep": N_INDI}).cuda()
     smp.set_new_noise_schedule({"n_timestep": N_INDI}, "cuda")
     smp.set_loss("cuda")
-    _load(smp, sd, "denoise_fn.")
+    nets.load(smp, sd)
     t = torch.from_numpy(g["t"])
     target, noise, inp = (torch.from_numpy(g[k]).cuda() for k in ("target", "noise", "input"))
-    assert _bit_equal(smp.q_sample(target, inp, t, noise=noise), torch.from_numpy(g["x_noisy"]))
-    assert _bit_equal(smp.q_sample(target, torch.cat([inp] * 2, dim=1), t.cuda(), noise=noise), torch.from_numpy(g["x_noisy"]))
+    assert same_bits(smp.q_sample(target, inp, t, noise=noise), torch.from_numpy(g["x_noisy"]))
+    assert same_bits(smp.q_sample(target, torch.cat([inp] * 2, dim=1), t.cuda(), noise=noise), torch.from_numpy(g["x_noisy"]))
     x_in = {"target": target, "input": inp}
     x_recon = smp.get_prediction_during_training(x_in, noise, t=t)
     _check_recon("indi", x_recon, g["x_recon"])
     loss = smp(x_in, noise, t=t)
     _check_loss("indi", loss, g["loss"], g["target"], g["x_recon"], "l1", "sum")
     torch.manual_seed(int(g["seed_torch"]))                   # the reference's own draw of t
-    assert _bit_equal(smp.p_losses(x_in, noise), loss)
+    assert same_bits(smp.p_losses(x_in, noise), loss)
 
 
 @pytest.mark.parametrize("tag,full", [("custom", False), ("full", True)])
@@ -285,7 +261,7 @@ def test_p_losses_joint_matches_the_reference(tag, full):
     from diffsplitting_amd.model.samplers import JointIndiSampler
     sd, g = golden_state_dict("objective_joint")
     cfg = cases.UNET_CASES["joint_32"]["cfg"]
-    n1, n2 = _unet("ddpm", cfg), _unet("ddpm", cfg)
+    n1, n2 = nets.unet("ddpm", cfg), nets.unet("ddpm", cfg)
     smp = JointIndiSampler(None, 32, channels=1, loss_type="l1", out_channel=1, denoise_fn_ch1=n1, denoise_fn_ch2=n2,
                            conditional=False, val_schedule_opt={"n_timestep": N_INDI}, allow_full_translation=full).cuda()
     smp.load_state_dict(sd, strict=True)
@@ -297,7 +273,7 @@ def test_p_losses_joint_matches_the_reference(tag, full):
     for i, (indi, t) in enumerate(((smp.indi1, t1), (smp.indi2, t2)), start=1):
         noise = torch.from_numpy(g[f"{tag}_noise{i}"]).cuda()
         x_in = {"target": ch[i - 1], "input": ch[2 - i]}
-        assert _bit_equal(indi.q_sample(x_in["target"], x_in["input"], t, noise=noise), torch.from_numpy(g[f"{tag}_x_noisy{i}"]))
+        assert same_bits(indi.q_sample(x_in["target"], x_in["input"], t, noise=noise), torch.from_numpy(g[f"{tag}_x_noisy{i}"]))
         _check_recon(f"joint {tag} indi{i}", indi.get_prediction_during_training(x_in, noise, t=t), g[f"{tag}_x_recon{i}"])
     # the reference hands ONE `noise` to both samplers (None in the fixture's run, so each drew its own): with one
     # injected tensor, the float64 value is recomputed from the fixture's x_recon only where its noise was used
@@ -309,7 +285,7 @@ def test_p_losses_joint_matches_the_reference(tag, full):
     got1 = smp.indi1._loss(ch[0], rec1["x_recon"])
     assert abs(float(got1) - l1) <= tol1
     got2 = smp.indi2._loss(ch[1], rec2["x_recon"])
-    assert _bit_equal(loss, (got1 + got2) / 2)
+    assert same_bits(loss, (got1 + got2) / 2)
     log = smp.get_current_log()
     assert set(log) == {"loss_splitting", "alpha", "offset", "scale"}
     assert log["loss_splitting"] == float(loss)
@@ -334,9 +310,8 @@ def test_p_losses_joint_matches_the_reference(tag, full):
 # ----------------------------------------------------------------------------- boundary
 def test_eval_loss_at_the_model_boundary():
     from diffsplitting_amd.model import create_model
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
     sd, g = golden_state_dict("objective_indi")
-    model = create_model(_opt(_tiny_indi_section()))
+    model = create_model(nets.opt(nets.tiny_indi_section()))
     model.netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()}, strict=True)
     model.feed_data({"input": torch.from_numpy(g["input"]), "target": torch.from_numpy(g["target"])})
     torch.manual_seed(5)

@@ -12,18 +12,13 @@ import torch
 from oracle import cases, samplers, tiling
 from oracle.unet import time_predictor_forward, unet_forward
 from tests.gpu_util import DrawRecorder, build_engine, maxabs, psnr
+from tests.nets import dev  # noqa: F401  (the fixture)
 from tests.util import golden_state_dict, load_golden
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 FP32_TOL = 1e-3
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 # ----------------------------------------------------------------------------- UNet forward

@@ -3,9 +3,6 @@ restatement of tests/comoments_ref.py and against the torch loop it replaces, an
 samplers (the true channels as estimates: the planted mixing time must come back), with the tiny random-weight networks
 of tests/test_gpu_mixed.py (rounds = 0 is predict_tiled_mixed bit for bit; every later round's start times are the
 argmax rule applied to the reported moments; an all-NaN unit keeps its time), and over 1, 2 and 3 ranks."""
-import os
-import subprocess
-import sys
 import types
 
 import numpy as np
@@ -13,10 +10,12 @@ import pytest
 import torch
 
 from tests import comoments_ref as CR
+from tests import mixed_util as MU
+from tests.bits import same_bits
+from tests.rank_worker import run_ranks
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T_LIST = np.arange(0, 1.0, 0.05)
 
 
@@ -51,9 +50,8 @@ def test_fused_scan_equals_the_torch_loop_on_the_fixture_networks():
     number of samples left out is printed).  fused=False still reproduces the fixture."""
     from oracle import cases
     from diffsplitting_amd.core import psnr_based_t_refinement as R
-    from tests.test_gpu_mixed import _networks
     from tests.util import load_golden
-    i1, i2, tp, _, _ = _networks(1)
+    i1, i2, tp, _, _ = MU.networks(1)
     g = load_golden("refine_n1")
     inp = cases.make_cond("time_pred")
     B = inp.shape[0]
@@ -124,8 +122,7 @@ def test_oracle_samplers_recover_the_planted_time(scope):
     """2 x 96 x 96 frames, patch 32, grid 16 (50 tiles), mixing_t = 0.3, no TimePredictor: round 0 starts at 0.5 and one
     round later every unit has chosen t_list[6]."""
     from diffsplitting_amd.data.tiled_predict import predict_tiled_refined
-    from tests.test_gpu_mixed import _dataset
-    ds, _, _ = _dataset((2, 96, 96), 9)
+    ds, _, _ = MU.dataset((2, 96, 96), 9)
     _remember_ids(ds)
     netG = types.SimpleNamespace(indi1=OracleSampler(ds, 0), indi2=OracleSampler(ds, 1), noise_source=None)
     (canvas, psnr), pred_t, rep = predict_tiled_refined(netG, None, ds, 0.3, rounds=1, scope=scope, batch_tiles=8,
@@ -163,10 +160,9 @@ def test_tiny_networks_rounds_and_the_argmax_rule():
     from diffsplitting_amd.data.split_dataset import DataLocation, SplitDatasetTiledPred
     from diffsplitting_amd.data.tiled_predict import predict_tiled_mixed, predict_tiled_refined
     from diffsplitting_amd.data.time_predictor_dataset import compute_input_normalization_dict
-    from tests.test_gpu_mixed import _frames, _networks
-    i1, i2, tp, _, _ = _networks(1)
+    i1, i2, tp, _, _ = MU.networks(1)
     netG = types.SimpleNamespace(indi1=i1, indi2=i2, noise_source=None, second_ids=_second_ids)
-    ch0, ch1 = _frames((2, 64, 64), 5)
+    ch0, ch1 = MU.frames((2, 64, 64), 5)
     ch0[1], ch1[1] = 300, 120                                          # a constant frame: 9 tiles without a curve
     ds = SplitDatasetTiledPred("Hagen", DataLocation(arrays=(ch0, ch1)), 32, grid_size=16, max_qval=0.98)
     T = len(ds)
@@ -175,9 +171,8 @@ def test_tiny_networks_rounds_and_the_argmax_rule():
     kw = dict(num_timesteps=1, mmse_count=2, batch_tiles=6, table=table, seed=5)
     (c_m, p_m), t_m = predict_tiled_mixed(netG, tp, ds, 0.29, **kw)
     (c_0, p_0), t_0, rep0 = predict_tiled_refined(netG, tp, ds, 0.29, rounds=0, **kw)
-    bits = lambda t: t.contiguous().view(torch.int32)
-    assert torch.equal(bits(c_0), bits(c_m)) and torch.equal(bits(t_0), bits(t_m))
-    assert torch.equal(torch.isnan(p_0), torch.isnan(p_m)) and torch.equal(bits(torch.nan_to_num(p_0)), bits(torch.nan_to_num(p_m)))
+    assert same_bits(c_0, c_m) and same_bits(t_0, t_m)
+    assert torch.equal(torch.isnan(p_0), torch.isnan(p_m)) and same_bits(torch.nan_to_num(p_0), torch.nan_to_num(p_m))
     assert len(rep0["rounds"]) == 1 and rep0["rounds"][0]["curves"].shape == (T, 20)
     frame = ds.plan.patch_start[:, 0]
     assert np.isnan(rep0["rounds"][0]["curves"][frame == 1]).all() and np.isfinite(rep0["rounds"][0]["curves"][frame == 0]).all()
@@ -230,8 +225,7 @@ def test_split_command_line_refined(tmp_path, caplog):
     from diffsplitting_amd.core.logger import dict_to_nonedict
     from diffsplitting_amd.data.tiled_predict import predict_tiled_refined
     from diffsplitting_amd.model import create_model
-    from tests.test_gpu_timepred import _write_configs
-    cfgs, _ = _write_configs(tmp_path)
+    cfgs, _ = MU.write_configs(tmp_path)
     cfg, cfg_path = cfgs["joint"]
     caplog.set_level(logging.INFO, logger="base")
     args = ["-c", cfg_path, "-p", "val", "-gpu", "0", "-rootdir", str(tmp_path), "--datapath", "--norm-from", "val",
@@ -259,10 +253,5 @@ def test_refined_prediction_does_not_depend_on_the_sharding(world):
     """`world` fresh ranks sharing the GPU (gloo transport): on every rank canvas, PSNR, pred_t and the whole report of
     predict_tiled_refined(seed=) equal the one-rank run done in the same process, bitwise
     (tests/multi_rank_predict_refined.py)."""
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(%d, [%r], timeout=300))\n"
-            % (ROOT, world, os.path.join(ROOT, "tests", "multi_rank_predict_refined.py")))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env["DSX_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=400)
+    r = run_ranks("multi_rank_predict_refined.py", world, backend="gloo", launch_timeout=300, timeout=400)
     assert r.returncode == 0 and "PREDICT_REFINED_OK" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])

@@ -12,7 +12,7 @@ import torch
 from oracle import cases, samplers
 from tests import resize_ref as R
 from tests.gpu_util import maxabs
-from tests.test_resize_cpu import check_case, load_fixture, make_input
+from tests.resize_cases import check_case, load_fixture, make_input
 from tests.util import golden_state_dict
 
 pytestmark = pytest.mark.gpu

@@ -21,9 +21,12 @@ import torch
 
 from oracle import cases
 from oracle.unet import unet_forward
-from oracle.weights import synth_state_dict
+from tests import nets
 from tests.gpu_util import maxabs
-from tests.layer_check import DT, check_plan, geom_tag, inputs
+from tests.layer_check import check_plan, geom_tag, inputs
+from tests.nets import dev  # noqa: F401  (the fixture)
+from tests.plan_cases import SHAPE_PLANS as PLANS, SHAPE_REACH as REACH, SHAPE_REACH_TAILS as REACH_TAILS
+from tests.plan_cases import shape_reach_by_dtype as reach_by_dtype
 from tests.util import golden_state_dict
 
 pytestmark = pytest.mark.gpu
@@ -32,71 +35,9 @@ torch.set_grad_enabled(False)
 FP32_TOL = 1e-3        # tests/test_gpu_parity.py, tests/test_gpu_widths.py: the fp32 build against the oracle
 SEED = 37              # w20's synthetic weights, as in tests/test_gpu_widths.py
 
-# any grid fills the chip and the persistent kernel is off: the 128-pixel tiles, two and four images per tile
-_WIDE_TILES = {"DSX_MIN_GRID": "1", "DSX_WS": "0"}
-_MANY_CHUNKS = {"DSX_WS_MIN_GRID": "1", "DSX_WS_G2_MIN64": "2", "DSX_WS_G2_MIN128": "2", "DSX_WS_G4_MIN64": "4",
-                "DSX_WS_C4_MIN": "4"}        # as in tests/test_gpu_layers.py: k_conv_ws on the 128-pixel tile
-_SPLITK = {"DSX_MIN_GRID": "100000", "DSX_WS": "0"}
-
-# id -> (case, dtype, B, env)
-PLANS = {}
-for _c in cases.SHAPE_CASES:
-    for _d in DT:
-        PLANS[f"{_c}_{_d}"] = (_c, _d, 3, {})
-for _c, _v in cases.SHAPE_CASES.items():
-    if _v["model"] in ("sr3_tiny", "w20"):
-        for _d in DT:
-            PLANS[f"{_c}_{_d}_wide_tiles"] = (_c, _d, 3, _WIDE_TILES)
-# (ddpm_tiny's 32-channel level on the slim 128 x 32 tile: the only plain 3 x 3 launches at 4x32x1 and 16x4x2 -- in
-# sr3_tiny and w20 that level is wider than 32 channels and takes the 64-pixel tile first)
-for _s in ("128x24", "24x64"):
-    for _d in DT:
-        PLANS[f"ddpm_tiny_{_s}_{_d}_wide_tiles"] = (f"ddpm_tiny_{_s}", _d, 3, _WIDE_TILES)
-for _m in ("ddpm_tiny", "sr3_tiny"):
-    for _s in ("64x48", "64x24", "128x24"):
-        for _d in DT:
-            PLANS[f"{_m}_{_s}_{_d}_many_chunk_ws"] = (f"{_m}_{_s}", _d, 3, _MANY_CHUNKS)
-for _h, _w in cases.SHAPE_SIZES:
-    PLANS[f"sr3_tiny_{_h}x{_w}_f32_splitk"] = (f"sr3_tiny_{_h}x{_w}", "f32", 3, _SPLITK)   # stride 2 under split-K
-# one image on two-image tiles (2x16x2 on the 16 x 6 maps): half of every such tile is empty
-PLANS["ddpm_tiny_64x24_b1_bf16"] = ("ddpm_tiny_64x24", "bf16", 1, {})
-PLANS["ddpm_tiny_64x24_b1_f32"] = ("ddpm_tiny_64x24", "f32", 1, {})
-
-# The geometry classes (tests/layer_check.py geom_tag, less its +tail suffix) that the union over the operand types must
-# contain.  What each operand type must contain is REACH_BY_DTYPE, which tests/test_planner_cpu.py holds equal to what
-# the planner's dry run of these very plans gives.
-_NARROW5 = ("2x16x2", "2x32x1", "4x16x1", "8x4x2", "16x2x2")
-
-
-def _classes(fam, size, tiles, bm):
-    return {f"{fam} {size} {t}@{bm}" for t in tiles}
-
-
-REACH = (_classes("mfma", "1x1", _NARROW5, 64)
-         | _classes("mfma", "1x1", ("2x16x4", "2x32x2", "4x16x2", "4x32x1", "8x4x4", "16x2x4", "16x4x2"), 128)
-         | _classes("mfma", "3x3", _NARROW5, 64) | _classes("mfma", "3x3", ("4x16x2", "4x32x1", "16x4x2"), 128)
-         | _classes("mfma", "3x3 up", ("4x16x1",), 64) | _classes("mfma", "3x3 up", ("4x32x1", "16x4x2"), 128)
-         | _classes("mfma", "3x3 s2", _NARROW5, 64)
-         | _classes("g2", "3x3", ("4x32x1", "16x8x1"), 128)
-         | _classes("splitK", "1x1", _NARROW5, 64) | _classes("splitK", "3x3", _NARROW5, 64)
-         | _classes("splitK", "3x3 up", ("4x16x1",), 64) | _classes("splitK", "3x3 s2", _NARROW5, 64)
-         | _classes("ws", "1x1", ("2x32x1", "4x16x1"), 64) | _classes("ws", "1x1", ("4x32x1", "8x16x1"), 128)
-         | _classes("ws", "3x3", ("4x16x1",), 64) | _classes("ws", "3x3", ("8x16x1",), 128)
-         | _classes("ws", "3x3 up", ("4x16x1",), 64))
-# multi-image tiles whose last tile misses images (B = 3 on two- and four-image tiles), with their suffix
-REACH_TAILS = ({c + "+tail" for c in _classes("mfma", "3x3", ("8x4x2", "2x16x2", "16x2x2"), 64)}
-               | {c + "+tail" for c in _classes("mfma", "1x1", ("2x16x4", "2x32x2", "4x16x2", "8x4x4", "16x2x4", "16x4x2"),
-                                                128)})
-
 _CHECKED = {}          # plan -> {dtype, geom, layers, worst}
 _SD = {}               # model -> state dict
 _ORACLE = {}           # case -> float64 oracle output
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 def _case_inputs(name, B=3):
@@ -108,13 +49,7 @@ def _case_inputs(name, B=3):
 def _state_dict(model):
     if model not in _SD:
         if model == "w20":
-            from diffsplitting_amd import engine
-            case = cases.SHAPE_MODELS[model]
-            cfg = case["cfg"]
-            eng = engine.UNetEngine(engine.make_cfg(case["flavour"], cfg["in_channel"], cfg["out_channel"],
-                                                    cfg["inner_channel"], cfg["norm_groups"], cfg["channel_mults"],
-                                                    cfg["attn_res"], cfg["res_blocks"], cfg["image_size"]), case["flavour"])
-            _SD[model] = synth_state_dict(zip(eng.param_names, eng.param_shapes), seed=SEED)
+            _SD[model] = nets.engine_state_dict(cases.SHAPE_MODELS[model], SEED)
         else:
             _SD[model] = golden_state_dict("unet_" + model)[0]
     return _SD[model]
@@ -159,15 +94,6 @@ def test_fp32_forward_against_fp64_oracle(name, dev):
     print(f"\n{name}: max|hip - oracle64| = {err:.3e}, max|y| = {float(ref.abs().max()):.2f}")
     assert tuple(y.shape) == tuple(ref.shape)
     assert err <= FP32_TOL, err
-
-
-def reach_by_dtype():
-    """dtype -> the classes its plans must reach (tests/golden/shape_reach.json): tests/test_planner_cpu.py asserts that
-    this equals what the planner's dry run of PLANS gives, so the table cannot drift from the planner unnoticed"""
-    import json
-    import os
-    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "shape_reach.json")) as f:
-        return {d: set(v) for d, v in json.load(f).items()}
 
 
 def test_reach():

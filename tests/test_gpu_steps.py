@@ -9,7 +9,10 @@ import pytest
 import torch
 
 from oracle import cases
+from tests import nets
+from tests.bits import same_bits
 from tests.gpu_util import maxabs
+from tests.steps_util import Source, constant_unet, off
 from tests.util import golden_state_dict, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -19,27 +22,8 @@ SCHED = cases.SCHEDULES["lin_8"]
 SENTINEL = -7.25
 
 
-def _bits(t):
-    return t.detach().cpu().contiguous().view(torch.int32)
-
-
-def _bit_equal(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _rand(shape, seed):
-    return torch.randn(shape, generator=torch.Generator().manual_seed(seed))
-
-
 def _t(g, key):
     return torch.from_numpy(g[key])
-
-
-def _off(t):
-    """The same values on the device, 4 bytes past a 16-byte boundary."""
-    o = torch.cat([torch.zeros(1), t.reshape(-1)]).cuda()[1:].view(t.shape)
-    assert o.data_ptr() % 16 == 4 and o.is_contiguous()
-    return o
 
 
 # per-sample coefficients, all different; sample 1 has sigma = 0
@@ -83,7 +67,7 @@ def test_posterior_step_bit_exact(shape, clip, predict_eps):
     """Every combination of NULL outputs; outputs not asked for keep their sentinel (they are not even passed)."""
     B = shape[0]
     co = {k: v[:B] for k, v in COEF.items()}
-    x, net, z = _rand(shape, 1), 0.7 * _rand(shape, 2), _rand(shape, 3)
+    x, net, z = nets.rand(shape, 1), 0.7 * nets.rand(shape, 2), nets.rand(shape, 3)
     ref = _ref_step(x, net, co, z, predict_eps, clip)
     if predict_eps and clip:
         assert bool((ref[0].abs() == 1).any()) or shape == (1, 1, 1, 1)       # the clamp is exercised
@@ -95,44 +79,44 @@ def test_posterior_step_bit_exact(shape, clip, predict_eps):
               x_recon_out=bufs[0] if want[0] else None, mean_out=bufs[1] if want[1] else None,
               x_out=bufs[2] if want[2] else None)
         for w, got, r in zip(want, bufs, ref):
-            assert _bit_equal(got, r) if w else bool((got == SENTINEL).all()), (want, w)
+            assert same_bits(got, r) if w else bool((got == SENTINEL).all()), (want, w)
 
 
 @pytest.mark.parametrize("shape", [(2, 3, 8, 8), (3, 3, 5, 7)])
 def test_posterior_step_in_place_and_unaligned(shape):
     B = shape[0]
     co = {k: v[:B] for k, v in COEF.items()}
-    x, net, z = _rand(shape, 4), _rand(shape, 5), _rand(shape, 6)
+    x, net, z = nets.rand(shape, 4), nets.rand(shape, 5), nets.rand(shape, 6)
     ref = _ref_step(x, net, co, z, 1, 1)
     # x_out aliasing x
     xg = x.cuda()
     recon = torch.empty_like(xg)
     out = _call(xg, net, co, predict_eps=1, clip=1, z=z.cuda(), x_recon_out=recon, x_out=xg)
-    assert out[2].data_ptr() == xg.data_ptr() and _bit_equal(xg, ref[2]) and _bit_equal(recon, ref[0])
+    assert out[2].data_ptr() == xg.data_ptr() and same_bits(xg, ref[2]) and same_bits(recon, ref[0])
     # base pointers 4 bytes past a 16-byte boundary: the scalar path whatever H*W is
     n = x.numel()
     outs = [torch.full((n + 1,), SENTINEL, device="cuda")[1:].view(shape) for _ in range(3)]
-    _call(x, net, co, put=_off, predict_eps=1, clip=1, z=_off(z), x_recon_out=outs[0], mean_out=outs[1], x_out=outs[2])
-    assert all(_bit_equal(o, r) for o, r in zip(outs, ref))
+    _call(x, net, co, put=off, predict_eps=1, clip=1, z=off(z), x_recon_out=outs[0], mean_out=outs[1], x_out=outs[2])
+    assert all(same_bits(o, r) for o, r in zip(outs, ref))
     # only one operand misaligned
-    got = _call(x, net, co, predict_eps=1, clip=1, z=_off(z), x_out=torch.empty(shape, device="cuda"))[2]
-    assert _bit_equal(got, ref[2])
+    got = _call(x, net, co, predict_eps=1, clip=1, z=off(z), x_out=torch.empty(shape, device="cuda"))[2]
+    assert same_bits(got, ref[2])
 
 
 @pytest.mark.parametrize("shape", [(3, 3, 8, 8), (3, 3, 5, 7)])
 def test_posterior_step_repeat_noise_injected(shape):
     """An injected z of shape (1, C, H, W) serves every sample (noise_like(..., repeat=True))."""
-    x, net, z = _rand(shape, 7), _rand(shape, 8), _rand((1,) + shape[1:], 9)
+    x, net, z = nets.rand(shape, 7), nets.rand(shape, 8), nets.rand((1,) + shape[1:], 9)
     ref = _ref_step(x, net, COEF, z, 1, 0, repeat=True)
     got = _call(x, net, COEF, predict_eps=1, clip=0, z=z.cuda(), repeat_noise=True, x_out=torch.empty(shape, device="cuda"))[2]
-    assert _bit_equal(got, ref[2])
+    assert same_bits(got, ref[2])
 
 
 def test_posterior_step_refusals():
     from diffsplitting_amd import engine
     from diffsplitting_amd._lib import DsxError
     shape = (2, 3, 8, 8)
-    x = _rand(shape, 1).cuda()
+    x = nets.rand(shape, 1).cuda()
     c = torch.ones(2, device="cuda")
     with pytest.raises(DsxError, match="output"):
         engine.posterior_step(x, x, c, c, c)
@@ -153,25 +137,25 @@ def test_posterior_step_philox_path(shape):
     never recovered by a division.  Sample 1 has sigma = 0: it gets its mean, here 0."""
     from diffsplitting_amd import engine
     B = shape[0]
-    x, net = _rand(shape, 10), _rand(shape, 11)
+    x, net = nets.rand(shape, 10), nets.rand(shape, 11)
     zero = torch.zeros(B)
     co = dict(a=zero, b=zero, c1=zero, c2=zero, sigma=torch.tensor([1.0, 0.0, 1.0]))
     run = lambda **kw: _call(x, net, co, predict_eps=0, x_out=torch.empty(shape, device="cuda"), **kw)[2]
     out = run(seed=1234, subsequence=5)
     z = engine.randn(shape, 1234, 5)
-    assert _bit_equal(out[0], z[0]) and _bit_equal(out[2], z[2])
+    assert same_bits(out[0], z[0]) and same_bits(out[2], z[2])
     assert bool((out[1] == 0).all())
-    assert _bit_equal(run(seed=1234, subsequence=5), out)                       # same seed: bitwise equal
-    assert not _bit_equal(run(seed=1235, subsequence=5), out)
-    assert not _bit_equal(run(seed=1234, subsequence=6), out)
+    assert same_bits(run(seed=1234, subsequence=5), out)                       # same seed: bitwise equal
+    assert not same_bits(run(seed=1235, subsequence=5), out)
+    assert not same_bits(run(seed=1234, subsequence=6), out)
     rep = run(seed=1234, subsequence=5, repeat_noise=True)
     first = engine.randn((1,) + shape[1:], 1234, 5)[0]                          # sample 0's draw
-    assert _bit_equal(rep[0], first) and _bit_equal(rep[2], first) and _bit_equal(rep[0], out[0])
+    assert same_bits(rep[0], first) and same_bits(rep[2], first) and same_bits(rep[0], out[0])
     assert bool((rep[1] == 0).all())
     # with real coefficients the Philox result equals the injected one
     got = _call(x, net, COEF, predict_eps=1, clip=1, seed=77, subsequence=3, x_out=torch.empty(shape, device="cuda"))[2]
     inj = _call(x, net, COEF, predict_eps=1, clip=1, z=engine.randn(shape, 77, 3), x_out=torch.empty(shape, device="cuda"))[2]
-    assert _bit_equal(got, inj)
+    assert same_bits(got, inj)
 
 
 # ----------------------------------------------------------------------------- dsx_interp_start
@@ -186,12 +170,12 @@ def test_interp_start_matches_the_fixture(tag, unaligned):
     t, lam = int(g["t_" + tag]), float(g["lam_" + tag])
     tb = torch.full((2,), t, dtype=torch.long)
     a0, s0 = bufs["sqrt_alphas_cumprod"].gather(-1, tb).cuda(), bufs["sqrt_one_minus_alphas_cumprod"].gather(-1, tb).cuda()
-    put = _off if unaligned else (lambda v: v.cuda())
+    put = off if unaligned else (lambda v: v.cuda())
     x1, x2, z1, z2 = (put(_t(g, k)) for k in ("x1", "x2", "noise1_" + tag, "noise2_" + tag))
     for x, z, want in ((x1, z1, "xt1_"), (x2, z2, "xt2_")):
-        assert _bit_equal(engine.q_sample(x, a0, s0, z=z)[0], _t(g, want + tag))
+        assert same_bits(engine.q_sample(x, a0, s0, z=z)[0], _t(g, want + tag))
     out = engine.interp_start(x1, x2, a0, s0, lam, z1=z1, z2=z2)
-    assert _bit_equal(out, _t(g, "start_" + tag))
+    assert same_bits(out, _t(g, "start_" + tag))
     # lam = 0 and 1 give the two q_sample results themselves (1 * q + 0 * q')
     assert torch.equal(engine.interp_start(x1, x2, a0, s0, 0.0, z1=z1, z2=z2).cpu(), _t(g, "xt1_" + tag))
     assert torch.equal(engine.interp_start(x1, x2, a0, s0, 1.0, z1=z1, z2=z2).cpu(), _t(g, "xt2_" + tag))
@@ -202,69 +186,44 @@ def test_interp_start_philox_subsequences(shape):
     from diffsplitting_amd import engine
     from diffsplitting_amd._lib import DsxError
     B = shape[0]
-    x1, x2 = _rand(shape, 12).cuda(), _rand(shape, 13).cuda()
+    x1, x2 = nets.rand(shape, 12).cuda(), nets.rand(shape, 13).cuda()
     a0, s0 = COEF["c1"][:B].cuda(), COEF["c2"][:B].cuda()
     out = engine.interp_start(x1, x2, a0, s0, 0.3, seed=99, subsequence=4)
     inj = engine.interp_start(x1, x2, a0, s0, 0.3, z1=engine.randn(shape, 99, 4), z2=engine.randn(shape, 99, 5))
-    assert _bit_equal(out, inj)
-    assert not _bit_equal(engine.interp_start(x1, x2, a0, s0, 0.3, seed=99, subsequence=5), out)
+    assert same_bits(out, inj)
+    assert not same_bits(engine.interp_start(x1, x2, a0, s0, 0.3, seed=99, subsequence=5), out)
     with pytest.raises(DsxError):
         engine.interp_start(x1, x2, a0, s0, 0.3, z1=x1)
 
 
 # ----------------------------------------------------------------------------- through the UNet, against the fixtures
-def _unet(flavour, cfg):
-    from diffsplitting_amd.model.ddpm_modules.unet import UNet as UNetDdpm
-    from diffsplitting_amd.model.sr3_modules.unet import UNet as UNetSr3
-    cls = UNetSr3 if flavour == "sr3" else UNetDdpm
-    return cls(in_channel=cfg["in_channel"], out_channel=cfg["out_channel"], inner_channel=cfg["inner_channel"],
-               norm_groups=cfg["norm_groups"], channel_mults=cfg["channel_mults"], attn_res=cfg["attn_res"],
-               res_blocks=cfg["res_blocks"], image_size=cfg["image_size"])
-
-
-def _load(smp, sd):
-    missing, unexpected = smp.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()}, strict=False)
-    assert not unexpected and all(not k.startswith("denoise_fn") for k in missing), missing
-
-
-class Source:
-    """A noise_source that hands out the given draws in order and records the shapes asked for."""
-
-    def __init__(self, draws=()):
-        self.draws, self.shapes = list(draws), []
-
-    def __call__(self, shape):
-        self.shapes.append(tuple(shape))
-        return self.draws.pop(0) if self.draws else torch.zeros(shape)
-
-
 def _sr3(fixture):
     from diffsplitting_amd.model.samplers import GaussianSampler
     sd, g = golden_state_dict(fixture)
-    net = _unet("sr3", cases.UNET_CASES["sr3_tiny"]["cfg"])
+    net = nets.unet("sr3", cases.UNET_CASES["sr3_tiny"]["cfg"])
     smp = GaussianSampler(net, 32, channels=3, conditional=True).cuda()
     smp.set_new_noise_schedule(SCHED, "cuda")
-    _load(smp, sd)
+    nets.load(smp, sd)
     return smp, net, g
 
 
 def _ddpm(fixture, cfg, channels, conditional):
     from diffsplitting_amd.model.samplers import GaussianSamplerDdpm
     sd, g = golden_state_dict(fixture)
-    net = _unet("ddpm", cfg)
+    net = nets.unet("ddpm", cfg)
     smp = GaussianSamplerDdpm(net, 32, channels=channels, conditional=conditional).cuda()
     smp.set_new_noise_schedule(SCHED, "cuda")
-    _load(smp, sd)
+    nets.load(smp, sd)
     return smp, net, g
 
 
 def _indi(fixture, n):
     from diffsplitting_amd.model.samplers import InDISampler
     sd, g = golden_state_dict(fixture)
-    net = _unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"])
+    net = nets.unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"])
     smp = InDISampler(net, 32, channels=2, out_channel=2, conditional=False, val_schedule_opt={"n_timestep": n}).cuda()
     smp.set_new_noise_schedule({"n_timestep": n}, "cuda")
-    _load(smp, sd)
+    nets.load(smp, sd)
     return smp, net, g
 
 
@@ -284,8 +243,8 @@ def test_sr3_steps_match_the_reference():
             tag = f"_t{t}_clip{clip}"
             mean, logvar = smp.p_mean_variance(x, t, bool(clip), condition_x=cond)
             _within("sr3 model_mean" + tag, mean, g["model_mean" + tag])
-            assert logvar.shape == () and _bit_equal(logvar, smp.posterior_log_variance_clipped[t])
-            assert _bit_equal(logvar, _t(g, f"log_variance_t{t}"))
+            assert logvar.shape == () and same_bits(logvar, smp.posterior_log_variance_clipped[t])
+            assert same_bits(logvar, _t(g, f"log_variance_t{t}"))
             src = smp.noise_source = Source([_t(g, f"noise_t{t}")])
             _within("sr3 p_sample" + tag, smp.p_sample(x, t, clip_denoised=bool(clip), condition_x=cond), g["sample" + tag])
             assert src.shapes == ([tuple(x.shape)] if t > 0 else [])          # one draw per call, none at t == 0
@@ -294,16 +253,16 @@ def test_sr3_steps_match_the_reference():
         scale = max(1.0, float(smp.sqrt_recipm1_alphas_cumprod[t]))            # x_recon = a x - b net: b times the net's error
         _within(f"sr3 x_recon t{t}", smp.predict_start_from_noise(x, t, rec["net"]), g[f"x_recon_t{t}_clip0"], FP32_TOL * scale)
         # on the fixture's own UNet output the two kernels' expressions are the reference's bit for bit
-        assert _bit_equal(smp.predict_start_from_noise(x, t, _t(g, f"net_t{t}").cuda()), _t(g, f"x_recon_t{t}_clip0"))
+        assert same_bits(smp.predict_start_from_noise(x, t, _t(g, f"net_t{t}").cuda()), _t(g, f"x_recon_t{t}_clip0"))
         for clip in (1, 0):
             m, lv = smp.q_posterior(_t(g, f"x_recon_t{t}_clip{clip}").cuda(), x, t)
-            assert _bit_equal(m, _t(g, f"model_mean_t{t}_clip{clip}")) and _bit_equal(lv, logvar)
+            assert same_bits(m, _t(g, f"model_mean_t{t}_clip{clip}")) and same_bits(lv, logvar)
     # device noise: repeatable under torch's seed, another seed gives another sample
     outs = []
     for seed in (1, 1, 2):
         torch.manual_seed(seed)
         outs.append(smp.p_sample(x, 7, condition_x=cond))
-    assert _bit_equal(outs[0], outs[1]) and not _bit_equal(outs[0], outs[2])
+    assert same_bits(outs[0], outs[1]) and not same_bits(outs[0], outs[2])
 
 
 @pytest.mark.parametrize("tag", ["mixed", "repeat"])
@@ -314,15 +273,15 @@ def test_ddpm_steps_match_the_reference(tag):
     mean, var, logvar = smp.p_mean_variance(x, t, True, condition_x=cond)
     _within(f"ddpm {tag} model_mean", mean, g["model_mean_" + tag])
     assert var.shape == logvar.shape == (2, 1, 1, 1)
-    assert _bit_equal(var, _t(g, "variance_" + tag)) and _bit_equal(logvar, _t(g, "log_variance_" + tag))
-    assert _bit_equal(var.reshape(-1), smp.posterior_variance[t])
-    assert _bit_equal(logvar.reshape(-1), smp.posterior_log_variance_clipped[t])
+    assert same_bits(var, _t(g, "variance_" + tag)) and same_bits(logvar, _t(g, "log_variance_" + tag))
+    assert same_bits(var.reshape(-1), smp.posterior_variance[t])
+    assert same_bits(logvar.reshape(-1), smp.posterior_log_variance_clipped[t])
     src = smp.noise_source = Source([_t(g, "noise_" + tag)])
     out = smp.p_sample(x, t, clip_denoised=True, repeat_noise=repeat, condition_x=cond)
     _within(f"ddpm {tag} p_sample", out, g["sample_" + tag])
     assert src.shapes == [(1, 1, 32, 32) if repeat else (2, 1, 32, 32)]
     if not repeat:                                                             # the sample at t == 0 is its model_mean
-        assert int(t[1]) == 0 and _bit_equal(out[1], mean[1])
+        assert int(t[1]) == 0 and same_bits(out[1], mean[1])
     # drawn on every call, t == 0 included
     src = smp.noise_source = Source()
     smp.p_sample(x, torch.zeros(2, dtype=torch.long, device="cuda"), condition_x=cond)
@@ -356,7 +315,7 @@ def test_interpolate_matches_the_reference(tag):
     for seed in (3, 3, 4):
         torch.manual_seed(seed)
         outs.append(smp.interpolate(x1, x2, t=t, lam=lam))
-    assert _bit_equal(outs[0], outs[1]) and not _bit_equal(outs[0], outs[2])
+    assert same_bits(outs[0], outs[1]) and not same_bits(outs[0], outs[2])
     assert bool(torch.isfinite(outs[0]).all())
 
 
@@ -404,22 +363,14 @@ def test_inference_one_step_calls_reproduce_the_reference_loop():
 # its bias in every executor, so the loop and the chained single steps can differ in the update alone: equal values
 # (torch.equal: the loop adds z * 0 where the single step adds nothing, a difference in the sign of a zero at most).
 T_EQ = 8
-BIAS = (0.3, -0.45)
-
-
-def _constant_unet(net, B):
-    net.final_conv__block__3__weight.zero_()
-    net.final_conv__block__3__bias.copy_(torch.tensor(BIAS))
-    out = net(_rand((B, 2, 16, 16), 50).cuda(), torch.full((B,), 0.5).cuda())
-    assert torch.equal(out.cpu(), torch.tensor(BIAS).view(1, 2, 1, 1).expand(B, 2, 16, 16))
 
 
 @pytest.mark.parametrize("clip", [True, False])
 def test_ddpm_loop_equals_chained_p_sample_on_a_constant_unet(clip):
     smp, net, _ = _ddpm("interpolate_ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"], 2, False)
     shape = (2, 2, 16, 16)
-    _constant_unet(net, 2)
-    draws = [_rand(shape, 100 + i) for i in range(T_EQ + 1)]                  # the start, then one per step
+    constant_unet(net, 2)
+    draws = [nets.rand(shape, 100 + i) for i in range(T_EQ + 1)]                  # the start, then one per step
     smp.noise_source = Source(draws)
     loop = smp.p_sample_loop(shape, clip_denoised=clip)
     assert loop.shape == shape and not smp.noise_source.draws
@@ -437,16 +388,16 @@ def test_indi_inference_equals_chained_one_steps_on_a_constant_unet(t_start):
     per-sample loop is compared sample by sample: inference_one_step takes one time for its whole batch."""
     n = T_EQ
     smp, net, _ = _indi("loop_indi_n3_t1.0", n)
-    _constant_unet(net, 3)
-    x_in = _rand((3, 1, 16, 16), 60)
+    constant_unet(net, 3)
+    x_in = nets.rand((3, 1, 16, 16), 60)
     one = (1, 2, 16, 16)
     per_sample = isinstance(t_start, tuple)
     if per_sample:                                                             # sample by sample: start, then n steps
-        draws = [[_rand(one, 1000 * b + i) for i in range(n + 1)] for b in range(3)]
+        draws = [[nets.rand(one, 1000 * b + i) for i in range(n + 1)] for b in range(3)]
         smp.noise_source = Source([d for per in draws for d in per])
         smp.inference(x_in.cuda(), t_float_start=torch.tensor(t_start))
     else:
-        flat = [_rand((3, 2, 16, 16), 300 + i) for i in range(n + 1)]
+        flat = [nets.rand((3, 2, 16, 16), 300 + i) for i in range(n + 1)]
         draws = [[d[b:b + 1].contiguous() for d in flat] for b in range(3)]
         smp.noise_source = Source(flat)
         smp.inference(x_in.cuda(), t_float_start=t_start)

@@ -8,6 +8,8 @@ import pytest
 import torch
 
 from oracle import cases
+from tests import nets
+from tests.bits import same_bits
 from tests.gpu_util import build_engine
 from tests.util import golden_state_dict
 
@@ -16,18 +18,6 @@ torch.set_grad_enabled(False)
 
 TOP = (1 << 40) - 1
 SR3_T4 = dict(schedule="linear", n_timestep=4, linear_start=1e-4, linear_end=2e-1)
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def _bit_equal(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _rand(shape, seed):
-    return torch.randn(tuple(shape), generator=torch.Generator().manual_seed(seed))
 
 
 # ----------------------------------------------------------------------------- 1. randn_samples
@@ -40,10 +30,10 @@ def test_randn_samples_rows_are_the_existing_streams(chw, draw):
     out = engine.randn_samples((len(ids),) + chw, 2024, ids, draw=draw)
     assert out.shape == (len(ids),) + chw
     for b, i in enumerate(ids):
-        assert _bit_equal(out[b].reshape(-1), engine.randn((n,), 2024, subsequence=(i << 24) | draw)), (b, i)
+        assert same_bits(out[b].reshape(-1), engine.randn((n,), 2024, subsequence=(i << 24) | draw)), (b, i)
     # a row does not depend on the batch it is drawn in or on its position there
     alone = engine.randn_samples((1,) + chw, 2024, [ids[3]], draw=draw)
-    assert _bit_equal(alone[0], out[3])
+    assert same_bits(alone[0], out[3])
 
 
 def test_randn_samples_more_rows_than_one_launch_carries():
@@ -52,15 +42,15 @@ def test_randn_samples_more_rows_than_one_launch_carries():
     ids = [(k * 7919) % 1000 + (k << 30) for k in range(70)]
     out = engine.randn_samples((70, 1, 3, 7), 5, ids, draw=3)
     for b in (0, 31, 32, 63, 64, 69):
-        assert _bit_equal(out[b].reshape(-1), engine.randn((21,), 5, subsequence=(ids[b] << 24) | 3)), b
+        assert same_bits(out[b].reshape(-1), engine.randn((21,), 5, subsequence=(ids[b] << 24) | 3)), b
 
 
 def test_randn_samples_ids_differing_above_bit_32_differ():
     from diffsplitting_amd import engine
     out = engine.randn_samples((3, 3, 8, 8), 1, [5, 5 + (1 << 32), 5 + (1 << 39)])
-    assert not _bit_equal(out[0], out[1]) and not _bit_equal(out[0], out[2]) and not _bit_equal(out[1], out[2])
+    assert not same_bits(out[0], out[1]) and not same_bits(out[0], out[2]) and not same_bits(out[1], out[2])
     other_seed = engine.randn_samples((3, 3, 8, 8), 2, [5, 5 + (1 << 32), 5 + (1 << 39)])
-    assert not _bit_equal(out, other_seed)
+    assert not same_bits(out, other_seed)
 
 
 def test_randn_samples_moments():
@@ -106,7 +96,7 @@ def _case(name, B, per_sample=False):
         bufs, gamma = engine.gaussian_buffers(SR3_T4)
         tab = engine.gaussian_step_table(bufs, gamma, "sr3", True)
         assert tab.n_steps == 4 and tab.sigma[-1] == 0 and tab.clip
-        return tab, (B, 3, 32, 32), _rand((B, 3, 32, 32), 40).cuda()
+        return tab, (B, 3, 32, 32), nets.rand((B, 3, 32, 32), 40).cuda()
     if per_sample:
         tab = engine.indi_step_table_per_sample(3, [1.0, 0.6, 0.8, 0.35][:B])
     else:
@@ -137,8 +127,8 @@ def test_loop_with_streams_equals_loop_with_the_same_draws_injected(name, per_sa
     B = 3
     tab, shape, cond = _case(name, B, per_sample)
     got, ref, x0 = _both(_engine(name, dtype), tab, shape, cond, 11, [6, TOP, 1 << 34], use_graph)
-    assert bool(torch.isfinite(got).all()) and not _bit_equal(got, x0)
-    assert _bit_equal(got, ref)
+    assert bool(torch.isfinite(got).all()) and not same_bits(got, x0)
+    assert same_bits(got, ref)
 
 
 @pytest.mark.parametrize("name", ["sr3", "indi2"])
@@ -149,16 +139,16 @@ def test_kept_graph_serves_calls_with_other_ids(name):
     eng = _engine(name, "f32")
     tab, shape, cond = _case(name, 3)
     ids_a, ids_b = [1, 2, 3], [3, 1 << 36, 1]
-    x0 = _rand(shape, 41).cuda()
+    x0 = nets.rand(shape, 41).cuda()
     got_a, _ = eng.sample_loop(tab, x0.clone(), cond=cond, seed=5, sample_ids=ids_a, use_graph=True)
     got_b, _ = eng.sample_loop(tab, x0.clone(), cond=cond, seed=5, sample_ids=ids_b, use_graph=True)
     for got, ids in ((got_a, ids_a), (got_b, ids_b)):            # eager references: the kept graph is not touched
         ref, _ = eng.sample_loop(tab, x0.clone(), cond=cond, noise=_injection(shape, tab.n_steps, 5, ids), use_graph=False)
-        assert _bit_equal(got, ref)
-    assert not _bit_equal(got_a, got_b)
+        assert same_bits(got, ref)
+    assert not same_bits(got_a, got_b)
     # the default noise still works on the same executor afterwards, and differs
     dflt, _ = eng.sample_loop(tab, x0.clone(), cond=cond, seed=5, use_graph=True)
-    assert bool(torch.isfinite(dflt).all()) and not _bit_equal(dflt, got_a)
+    assert bool(torch.isfinite(dflt).all()) and not same_bits(dflt, got_a)
 
 
 def test_loop_refusals_on_the_device():
@@ -166,7 +156,7 @@ def test_loop_refusals_on_the_device():
     from diffsplitting_amd._lib import DsxError
     eng = _engine("indi2", "f32")
     tab, shape, _ = _case("indi2", 3)
-    x0 = _rand(shape, 42).cuda()
+    x0 = nets.rand(shape, 42).cuda()
     with pytest.raises(DsxError, match="injected noise"):
         eng.sample_loop(tab, x0.clone(), noise=torch.zeros((3,) + shape, device="cuda"), sample_ids=[1, 2, 3])
     with pytest.raises(DsxError, match="B = 3"):
@@ -182,39 +172,25 @@ def test_permuting_inputs_and_ids_permutes_the_outputs(name):
     B, perm = 4, [2, 0, 3, 1]
     tab, shape, cond = _case(name, B)
     ids = [10, 1 << 38, 7, 123456789]
-    x0 = _rand(shape, 43).cuda()
+    x0 = nets.rand(shape, 43).cuda()
     out, _ = eng.sample_loop(tab, x0.clone(), cond=cond, seed=9, sample_ids=ids)
     out_p, _ = eng.sample_loop(tab, x0[perm].clone(), cond=None if cond is None else cond[perm].contiguous(), seed=9,
                                sample_ids=[ids[p] for p in perm])
-    assert _bit_equal(out_p, out[perm])
+    assert same_bits(out_p, out[perm])
     # the default noise is indexed by the position in the batch: the same permutation changes the result
     dflt, _ = eng.sample_loop(tab, x0.clone(), cond=cond, seed=9)
     dflt_p, _ = eng.sample_loop(tab, x0[perm].clone(), cond=None if cond is None else cond[perm].contiguous(), seed=9)
-    assert not _bit_equal(dflt_p, dflt[perm])
+    assert not same_bits(dflt_p, dflt[perm])
 
 
 # ----------------------------------------------------------------------------- 4. caller-driven against the loop
-def _unet(flavour, cfg):
-    from diffsplitting_amd.model.ddpm_modules.unet import UNet as UNetDdpm
-    from diffsplitting_amd.model.sr3_modules.unet import UNet as UNetSr3
-    cls = UNetSr3 if flavour == "sr3" else UNetDdpm
-    return cls(in_channel=cfg["in_channel"], out_channel=cfg["out_channel"], inner_channel=cfg["inner_channel"],
-               norm_groups=cfg["norm_groups"], channel_mults=cfg["channel_mults"], attn_res=cfg["attn_res"],
-               res_blocks=cfg["res_blocks"], image_size=cfg["image_size"])
-
-
-def _load(smp, sd):
-    missing, unexpected = smp.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()}, strict=False)
-    assert not unexpected and all(not k.startswith("denoise_fn") for k in missing), missing
-
-
 @functools.lru_cache(maxsize=None)
 def _sr3_sampler():
     from diffsplitting_amd.model.samplers import GaussianSampler
     sd, _ = golden_state_dict("loop_sr3_lin_8")
-    smp = GaussianSampler(_unet("sr3", cases.UNET_CASES["sr3_tiny"]["cfg"]), 32, channels=3, conditional=True).cuda()
+    smp = GaussianSampler(nets.unet("sr3", cases.UNET_CASES["sr3_tiny"]["cfg"]), 32, channels=3, conditional=True).cuda()
     smp.set_new_noise_schedule(SR3_T4, "cuda")
-    _load(smp, sd)
+    nets.load(smp, sd)
     return smp
 
 
@@ -222,19 +198,18 @@ def _sr3_sampler():
 def _indi_sampler():
     from diffsplitting_amd.model.samplers import InDISampler
     sd, _ = golden_state_dict("loop_indi_n3_t1.0")
-    smp = InDISampler(_unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"]), 32, channels=2, out_channel=2,
+    smp = InDISampler(nets.unet("ddpm", cases.UNET_CASES["ddpm_tiny"]["cfg"]), 32, channels=2, out_channel=2,
                       conditional=False, val_schedule_opt={"n_timestep": 3}).cuda()
     smp.set_new_noise_schedule({"n_timestep": 3}, "cuda")
-    _load(smp, sd)
+    nets.load(smp, sd)
     return smp
 
 
 @functools.lru_cache(maxsize=None)
 def _joint_sampler():
     from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
     sd, _ = golden_state_dict("loop_joint_n3")
-    netG = networks.define_G(_opt(_tiny_indi_section(1, 1, "joint_indi"))).cuda()
+    netG = networks.define_G(nets.opt(nets.tiny_indi_section(1, 1, "joint_indi"))).cuda()
     netG.load_state_dict(sd, strict=True)
     netG.set_new_noise_schedule({"n_timestep": 3}, "cuda")
     return netG
@@ -243,14 +218,14 @@ def _joint_sampler():
 def test_p_sample_calls_with_ids_reproduce_the_loop():
     from diffsplitting_amd import engine
     smp = _sr3_sampler()
-    cond = _rand((2, 3, 32, 32), 44).cuda()
+    cond = nets.rand((2, 3, 32, 32), 44).cuda()
     ids, seed, T = [1 << 37, 12], 21, 4
     smp.p_sample_loop(cond, seed=seed, sample_ids=ids)
     loop = smp.last_full_batch.clone()
     img = engine.randn_samples((2, 3, 32, 32), seed, ids, draw=0)
     for t in reversed(range(T)):
         img = smp.p_sample_seeded(img, t, seed, ids, condition_x=cond)
-    assert _bit_equal(loop, img)
+    assert same_bits(loop, img)
 
 
 def test_inference_one_step_calls_with_ids_reproduce_the_loop():
@@ -266,7 +241,7 @@ def test_inference_one_step_calls_with_ids_reproduce_the_loop():
     for s in range(n):
         x = smp.inference_one_step_seeded(x, delta, cur, seed, ids, draw=s + 1)
         cur -= delta
-    assert smp.e == 0.01 and _bit_equal(loop, x)
+    assert smp.e == 0.01 and same_bits(loop, x)
 
 
 @pytest.mark.parametrize("shape", [(40, 3, 5, 7), (40, 2, 4, 8), (3, 1, 5, 5)])
@@ -277,13 +252,13 @@ def test_posterior_step_with_ids_draws_the_sample_streams(shape):
     from diffsplitting_amd import engine
     B = shape[0]
     ids = [(b * 104729) % 5000 + ((b % 3) << 35) for b in range(B)]
-    x, net = _rand(shape, 46).cuda(), _rand(shape, 47).cuda()
+    x, net = nets.rand(shape, 46).cuda(), nets.rand(shape, 47).cuda()
     zero, sigma = torch.zeros(B, device="cuda"), torch.ones(B, device="cuda")
     sigma[1] = 0.0
     out = engine.posterior_step(x, net, zero, zero, sigma, seed=13, sample_ids=ids, draw=6, x_out=torch.empty_like(x))[2]
     z = engine.randn_samples(shape, 13, ids, draw=6)
     keep = [b for b in range(B) if b != 1]
-    assert _bit_equal(out[keep], z[keep])
+    assert same_bits(out[keep], z[keep])
     assert bool((out[1] == 0).all())                                           # its mean, 0 * net + 0 * x: a zero of either sign
 
 
@@ -294,24 +269,24 @@ def _sampler_runs(run):
     cuda_state = torch.cuda.get_rng_state().clone()
     a, b = run(3, [5, 6]), run(3, [5, 6])
     assert torch.equal(torch.get_rng_state(), state) and torch.equal(torch.cuda.get_rng_state(), cuda_state)
-    assert _bit_equal(a, b)
-    assert not _bit_equal(a, run(4, [5, 6]))
+    assert same_bits(a, b)
+    assert not same_bits(a, run(4, [5, 6]))
     c = run(3, [5, 7])
-    assert _bit_equal(a[0], c[0]) and not _bit_equal(a[1], c[1])                # sample 0 kept its id: it kept its bits
+    assert same_bits(a[0], c[0]) and not same_bits(a[1], c[1])                # sample 0 kept its id: it kept its bits
     return a
 
 
 def test_gaussian_sampler_keywords():
     from diffsplitting_amd._lib import DsxError
     smp = _sr3_sampler()
-    cond = _rand((2, 3, 32, 32), 45).cuda()
+    cond = nets.rand((2, 3, 32, 32), 45).cuda()
 
     def run(seed, ids):
         smp.super_resolution(cond, seed=seed, sample_ids=ids)
         return smp.last_full_batch.clone()
     a = _sampler_runs(run)
     smp.predict(cond, seed=3, sample_ids=[5, 6])
-    assert _bit_equal(a, smp.last_full_batch)
+    assert same_bits(a, smp.last_full_batch)
     with pytest.raises(DsxError, match="noise_source together with sample_ids"):
         smp.noise_source = lambda shape: torch.zeros(shape)
         try:
@@ -332,7 +307,7 @@ def test_indi_sampler_keywords():
     _sampler_runs(run)
     # per-sample start times take the same streams
     smp.inference(x_in, t_float_start=torch.tensor([1.0, 1.0]), seed=3, sample_ids=[5, 6])
-    assert _bit_equal(smp.last_full_batch, run(3, [5, 6]))
+    assert same_bits(smp.last_full_batch, run(3, [5, 6]))
 
 
 def test_joint_sampler_channels_do_not_share_draws():
@@ -351,16 +326,16 @@ def test_joint_sampler_channels_do_not_share_draws():
     p1 = netG.indi1._start(x_in, 0.5, (3, ids)) - x_in
     p2 = netG.indi2._start(x_in, 0.5, (3, netG.second_ids(ids))) - x_in
     assert netG.second_ids(ids) == [5 + (1 << 39), 6 + (1 << 39)]
-    assert not _bit_equal(p1, p2) and float((p1 - p2).abs().max()) > 0
+    assert not same_bits(p1, p2) and float((p1 - p2).abs().max()) > 0
     z2 = engine.randn_samples(x_in.shape, 3, [5 + (1 << 39), 6 + (1 << 39)])
-    assert _bit_equal(netG.indi2._start(x_in, 0.5, (3, netG.second_ids(ids))), x_in + z2 * (netG.indi2.e * torch.Tensor([0.5])).cuda())
+    assert same_bits(netG.indi2._start(x_in, 0.5, (3, netG.second_ids(ids))), x_in + z2 * (netG.indi2.e * torch.Tensor([0.5])).cuda())
     with pytest.raises(DsxError, match=r"2\^39"):
         netG.inference(x_in, seed=3, sample_ids=[5, 1 << 39])
     # the concurrent and the back-to-back form draw the same
     a = run(3, ids)
     netG.concurrent = False
     try:
-        assert _bit_equal(a, run(3, ids))
+        assert same_bits(a, run(3, ids))
     finally:
         netG.concurrent = True
 
@@ -370,11 +345,8 @@ def test_predict_tiled_with_a_seed_does_not_depend_on_the_batch_order():
     own e = 0.01), and another without."""
     from diffsplitting_amd.data.tiled_predict import predict_tiled
     from diffsplitting_amd.model import networks
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
     sd, _ = golden_state_dict("unet_hagen_64")
-    sec = _tiny_indi_section()
-    sec["unet"]["channel_multiplier"] = [1, 2, 4, 8]
-    netG = networks.define_G(_opt(sec)).cuda()
+    netG = networks.define_G(nets.opt(nets.hagen64_section())).cuda()
     netG.load_state_dict({"denoise_fn." + k: v for k, v in sd.items()})
     assert netG.e == 0.01
     frames = torch.from_numpy(np.random.default_rng(5).standard_normal((1, 96, 160)).astype(np.float32)).cuda()
@@ -390,7 +362,7 @@ def test_predict_tiled_with_a_seed_does_not_depend_on_the_batch_order():
             netG.inference(plan.gather(frames, chunk).unsqueeze(1), continuous=False, num_timesteps=2, **extra)
             out[i] = netG.last_full_batch.clone()
         return plan.stitch(torch.cat([out[i] for i in sorted(out)]))
-    assert torch.equal(_bits(pred), _bits(reversed_batches(seed=11)))
+    assert same_bits(pred, reversed_batches(seed=11))
     torch.manual_seed(0)
     plain, _ = predict_tiled(netG, frames, patch_size=64, grid_size=32, batch_tiles=4, sampler_kwargs=dict(num_timesteps=2))
     torch.manual_seed(0)
@@ -402,10 +374,9 @@ def test_split_sample_seed(tmp_path):
     """`split --sample-seed S`: the same seed twice gives the same canvas, another seed or no seed another one."""
     import json
     from diffsplitting_amd import split
-    from tests.test_gpu_boundary import _tiny_indi_section
     cfg = {"name": "tiny_hagen_indi", "phase": "train", "gpu_ids": [0],
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
-           "datasets": {"val": {"name": "Hagen", "patch_size": 64, "datatype": "img"}}, "model": _tiny_indi_section()}
+           "datasets": {"val": {"name": "Hagen", "patch_size": 64, "datatype": "img"}}, "model": nets.tiny_indi_section()}
     p = tmp_path / "tiny.json"
     p.write_text(json.dumps(cfg, indent=2))
 
@@ -415,8 +386,8 @@ def test_split_sample_seed(tmp_path):
                            "--steps", "2", "--batch-tiles", "3", *extra]).clone()
     a, b = run("--sample-seed", "7"), run("--sample-seed", "7")
     assert a.shape == (1, 128, 128, 2) and bool(torch.isfinite(a).all())
-    assert _bit_equal(a, b)
-    assert not _bit_equal(a, run("--sample-seed", "8")) and not _bit_equal(a, run())
+    assert same_bits(a, b)
+    assert not same_bits(a, run("--sample-seed", "8")) and not same_bits(a, run())
     with pytest.raises(SystemExit, match="--sample-seed"):
         run("--sample-seed", "7", "--validate")
 

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import nets
 from tests import tiff_files as TF
 
 pytestmark = pytest.mark.gpu
@@ -53,17 +54,6 @@ def test_dataset_from_files_equals_dataset_from_arrays(tmp_path):
     _same_dataset(from_fpath, unclipped)
 
 
-def _tiny_indi_section(in_ch=2, out_ch=2, which="indi"):                          # as tests/test_gpu_boundary.py
-    return {"which_model_G": which, "loss_type": "l1", "lr_reduction": "mean", "finetune_norm": False,
-            "w_input_loss": 0.0,
-            "unet": {"in_channel": in_ch, "out_channel": out_ch, "inner_channel": 16, "norm_groups": 16,
-                     "channel_multiplier": [1, 2, 4] if which == "indi" else [1, 2, 4, 8], "attn_res": [],
-                     "res_blocks": 1, "dropout": 0},
-            "beta_schedule": {"train": {"schedule": "linear", "n_timestep": 20, "linear_start": 1e-6, "linear_end": 1e-2},
-                              "val": {"schedule": "linear", "n_timestep": 3, "linear_start": 1e-6, "linear_end": 1e-2}},
-            "diffusion": {"image_size": 32, "channels": out_ch, "conditional": False}}
-
-
 def _config(tmp_path, val_shape=(2, 96, 160)):
     """Train stacks up to ~1500 counts, val stacks up to ~600: clearly different statistics."""
     paths = {}
@@ -78,7 +68,7 @@ def _config(tmp_path, val_shape=(2, 96, 160)):
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
            "datasets": {"patch_size": 64, "max_qval": 0.98, "upper_clip": False, "channel_weights": [1, 1],
                         "train": ds("train"), "val": ds("val")},
-           "model": _tiny_indi_section()}
+           "model": nets.tiny_indi_section()}
     p = tmp_path / "tiny.json"
     p.write_text(json.dumps(cfg, indent=2))
     return cfg, str(p)

@@ -3,9 +3,7 @@ against the fp32 restatement of tests/mixed_ref.py and against dsx_tiles_gather_
 ``TimePredictorDataset.batch`` against the items, ``validation_loss`` against the same loop built from the oracle, the
 two command lines, and ``predict_tiled_mixed`` sharded over two ranks against one."""
 import ctypes as C
-import json
 import logging
-import os
 
 import numpy as np
 import pytest
@@ -13,31 +11,20 @@ import torch
 
 from oracle import cases
 from oracle.unet import time_predictor_forward
-from oracle.weights import synth_state_dict
 from tests import mixed_ref as MR
+from tests import mixed_util as MU
+from tests import nets
+from tests.bits import same_bits
+from tests.rank_worker import run_ranks
 from tests.util import load_golden
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 FP32_TOL = 1e-3                                                     # the project's fp32 parity bound (test_gpu_mixed.py)
 T_SET = [0.0, 0.01, 0.29, 0.5, 0.99, 1.0]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
 
 
 # ---- 1. the per-item gather ---------------------------------------------------------------------------------------
-_i64 = lambda v: (C.c_int64 * len(v))(*[int(x) for x in v])
-_dbl = lambda v: (C.c_double * len(v))(*[float(x) for x in v])
-
-
 class _Frames:
     """Case b of mix_range.npz on the device: 2 x 37 x 53, an odd width, so that rows are misaligned."""
 
@@ -47,7 +34,7 @@ class _Frames:
         self.mean, self.std, self.table = g["b_mean_target"], g["b_std_target"], g["b_table_100"]
         self.dev = [torch.from_numpy(c.astype(np.float32)).cuda() for c in (self.ch0, self.ch1)]
         self.shape = self.ch0.shape
-        self.norm = _dbl([self.mean[0], self.std[0], self.mean[1], self.std[1]])
+        self.norm = nets.dbl(self.mean[0], self.std[0], self.mean[1], self.std[1])
 
     def starts(self, ph, pw):
         N, H, W = self.shape
@@ -74,8 +61,8 @@ class _Frames:
         ptr = lambda k: C.c_void_p(out[k][1:].data_ptr()) if k in out else None
         lohi = [v for t in ts for v in MR.rows(self.table, t)]
         check(lib.dsx_tiles_gather_mix_items(
-            C.c_void_p(self.dev[0].data_ptr()), C.c_void_p(self.dev[1].data_ptr()), _i64(self.shape), _i64((1, ph, pw)),
-            _i64([v for s in starts for v in s]), count, self.norm, _dbl(ts), _dbl(lohi) if "cls" in out else None,
+            C.c_void_p(self.dev[0].data_ptr()), C.c_void_p(self.dev[1].data_ptr()), nets.i64(*self.shape), nets.i64(1, ph, pw),
+            nets.i64(*[v for s in starts for v in s]), count, self.norm, nets.dbl(*ts), nets.dbl(*lohi) if "cls" in out else None,
             ptr("target"), ptr("mix"), ptr("cls"), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         torch.cuda.synchronize()
         res = {}
@@ -90,8 +77,8 @@ class _Frames:
         from diffsplitting_amd._lib import check, lib
         out = {k: torch.empty((1, 2, ph, pw), dtype=torch.float32, device="cuda") for k in ("target", "mix", "cls")}
         check(lib.dsx_tiles_gather_mix(
-            C.c_void_p(self.dev[0].data_ptr()), C.c_void_p(self.dev[1].data_ptr()), _i64(self.shape), _i64((1, ph, pw)),
-            _i64(loc), None, 1, self.norm, float(t), _dbl(MR.rows(self.table, t)), C.c_void_p(out["target"].data_ptr()),
+            C.c_void_p(self.dev[0].data_ptr()), C.c_void_p(self.dev[1].data_ptr()), nets.i64(*self.shape), nets.i64(1, ph, pw),
+            nets.i64(*loc), None, 1, self.norm, float(t), nets.dbl(*MR.rows(self.table, t)), C.c_void_p(out["target"].data_ptr()),
             C.c_void_p(out["mix"].data_ptr()), C.c_void_p(out["cls"].data_ptr()),
             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return {k: v[0].cpu().numpy() for k, v in out.items()}
@@ -107,20 +94,20 @@ def test_per_item_gather_bitwise(ph, pw):
     for k, (loc, t) in enumerate(zip(starts, ts)):
         ref, single = f.reference(loc, ph, pw, t), f.one_by_one(loc, t, ph, pw)
         for name in ("target", "mix", "cls"):
-            assert _same(got[name][k], ref[name]), (name, k, loc, t)
-            assert _same(got[name][k], single[name]), (name, k, loc, t)
+            assert same_bits(got[name][k], ref[name]), (name, k, loc, t)
+            assert same_bits(got[name][k], single[name]), (name, k, loc, t)
     # count = 1 (the last valid corner), count = 0 (nothing is written)
     one = f.items(starts[1:2], ts[1:2], ph, pw)
-    assert all(_same(one[name][0], got[name][1]) for name in got)
+    assert all(same_bits(one[name][0], got[name][1]) for name in got)
     none = f.items([], [], ph, pw)
     assert all(v.shape == (0, 2, ph, pw) for v in none.values())
     # each output pointer NULL in turn, and each alone
     for drop in ("target", "mix", "cls"):
         want = tuple(n for n in ("target", "mix", "cls") if n != drop)
         part = f.items(starts, ts, ph, pw, want=want)
-        assert sorted(part) == sorted(want) and all(_same(part[n], got[n]) for n in want), drop
+        assert sorted(part) == sorted(want) and all(same_bits(part[n], got[n]) for n in want), drop
         alone = f.items(starts, ts, ph, pw, want=(drop,))
-        assert _same(alone[drop], got[drop]), drop
+        assert same_bits(alone[drop], got[drop]), drop
 
 
 # ---- 2. / 3. the dataset's batches and the validation loop --------------------------------------------------------
@@ -149,7 +136,7 @@ def test_batch_equals_the_items():
         assert inp.is_cuda and inp.shape == (8, 1, 32, 32) and inp.dtype == torch.float32 and inp.is_contiguous()
         assert isinstance(t, np.ndarray) and t.shape == (8,) and t.dtype == np.float64
         assert np.array_equal(t, np.array([it[1] for it in items]))
-        assert _same(inp.cpu().numpy(), np.stack([it[0] for it in items]))
+        assert same_bits(inp.cpu().numpy(), np.stack([it[0] for it in items]))
         assert after_batch == after_items
         assert len(set(t.tolist())) > 1                                  # the items do carry different t
     # given t_ints: the same items, no random number consumed
@@ -170,22 +157,6 @@ def test_batch_equals_the_items():
         ds.batch([0, 1], t_ints=[3])
 
 
-_TP = {}
-
-
-def _time_predictor():
-    """The synthetic TimePredictor of tests/test_gpu_mixed.py::_networks and its state dict."""
-    if not _TP:
-        from diffsplitting_amd.model.ddpm_modules.time_predictor import TimePredictor
-        g = load_golden("refine_n1")
-        keys = [(a, tuple(s)) for a, s in json.loads(bytes(g["keys_tp"]).decode())]
-        sd = synth_state_dict(keys, 0)
-        tp = TimePredictor(**cases.TIME_PRED_CFG).cuda()
-        tp.load_state_dict(sd, strict=True)
-        _TP.update(tp=tp, sd=sd)
-    return _TP["tp"], _TP["sd"]
-
-
 _REF = {}
 
 
@@ -194,7 +165,7 @@ def _oracle_loop(seed):
     time_predictor_forward.  Computed once per seed, shared, never modified."""
     if seed not in _REF:
         ds, g, nd = _dataset()
-        _, sd = _time_predictor()
+        _, sd = MU.time_predictor()
         np.random.seed(seed)
         t_ints = [np.random.randint(0, 100) for _ in range(len(ds))]
         t = np.array([v / 100 for v in t_ints], dtype=np.float64)
@@ -224,7 +195,7 @@ def test_validation_loss_against_the_oracle(loss_type):
     """8 items in batches of 3, 3 and 2 (the short last batch overlaps the one before it), then 8 and 1."""
     from diffsplitting_amd.time_prediction import validation_loss
     ds, _, _ = _dataset()
-    tp, _ = _time_predictor()
+    tp, _ = MU.time_predictor()
     seed = 21
     ref_pred, ref_t = _oracle_loop(seed)
     y = ref_t.astype(np.float32).astype(np.float64)
@@ -245,49 +216,10 @@ def test_validation_loss_against_the_oracle(loss_type):
             if first is None:
                 first = (val_loss, per_batch, pred, t)
             else:                                                        # the same seed again: bitwise the same
-                assert val_loss == first[0] and _same(per_batch, first[1]) and _same(pred, first[2]) and _same(t, first[3])
+                assert val_loss == first[0] and same_bits(per_batch, first[1]) and same_bits(pred, first[2]) and same_bits(t, first[3])
 
 
 # ---- 4. the command lines -----------------------------------------------------------------------------------------
-def _write_configs(tmp_path):
-    from diffsplitting_amd.data.tiff import imwrite
-    rng = np.random.default_rng(9)
-    paths = []
-    for ch, (shape, scale) in enumerate(((2.0, 150.0), (3.0, 70.0))):
-        p = str(tmp_path / f"val_ch{ch}.tif")
-        imwrite(p, np.minimum(rng.gamma(shape, scale, size=(1, 64, 64)), 1900).astype(np.uint16))
-        paths.append(p)
-    part = lambda extra: dict({"name": "Hagen", "datapath": {"ch0": paths[0], "ch1": paths[1]}}, **extra)
-    datasets = {"patch_size": 32, "max_qval": 0.98, "upper_clip": False, "channel_weights": [1, 1],
-                "train": part({"batch_size": 3, "uncorrelated_channels": False, "gaussian_noise_std_factor": 0.02}),
-                "val": part({})}
-    path = {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None}
-    c = cases.TIME_PRED_CFG
-    tp_cfg = {"name": "tiny_tp", "phase": "train", "gpu_ids": [0], "path": path, "datasets": datasets,
-              "model": {"loss_type": "l2", "which_model_G": "UnetClassifier",
-                        "unet": {"in_channel": c["in_channel"], "out_channel": c["out_channel"],
-                                 "inner_channel": c["inner_channel"], "norm_groups": c["norm_groups"],
-                                 "channel_multiplier": list(c["channel_mults"]), "attn_res": list(c["attn_res"]),
-                                 "res_blocks": c["res_blocks"], "dropout": 0.2}}}
-    joint_cfg = {"name": "tiny_joint", "phase": "val", "gpu_ids": [0], "path": path, "datasets": datasets,
-                 "model": {"which_model_G": "joint_indi", "loss_type": "l1", "lr_reduction": "mean", "finetune_norm": False,
-                           "w_input_loss": 0.0,
-                           "unet": {"in_channel": 1, "out_channel": 1, "inner_channel": 16, "norm_groups": 16,
-                                    "channel_multiplier": [1, 2, 4, 8], "attn_res": [], "res_blocks": 1, "dropout": 0},
-                           "beta_schedule": {"train": {"schedule": "linear", "n_timestep": 20, "linear_start": 1e-6, "linear_end": 1e-2},
-                                             "val": {"schedule": "linear", "n_timestep": 3, "linear_start": 1e-6, "linear_end": 1e-2}},
-                           "diffusion": {"image_size": 32, "channels": 1, "conditional": False}}}
-    out = {}
-    for name, cfg in (("tp", tp_cfg), ("joint", joint_cfg)):
-        p = tmp_path / f"{name}.json"
-        p.write_text(json.dumps(cfg, indent=2))
-        out[name] = (cfg, str(p))
-    _, sd = _time_predictor()
-    pth = str(tmp_path / "best_time_predictor.pth")
-    torch.save({k: v.clone() for k, v in sd.items()}, pth)
-    return out, pth
-
-
 def _logged(caplog, prefix):
     lines = [r.getMessage() for r in caplog.records if r.getMessage().startswith(prefix)]
     assert len(lines) == 1, (prefix, lines)
@@ -298,7 +230,7 @@ def test_time_prediction_command_line(tmp_path, caplog):
     from diffsplitting_amd import time_prediction as TP
     from diffsplitting_amd.core.logger import dict_to_nonedict
     from diffsplitting_amd.data.tiled_predict import evaluate_time_predictor
-    cfgs, pth = _write_configs(tmp_path)
+    cfgs, pth = MU.write_configs(tmp_path)
     cfg, cfg_path = cfgs["tp"]
     caplog.set_level(logging.INFO, logger="base")
     res = TP.main(["-c", cfg_path, "--datapath", "--norm-from", "val", "--checkpoint", pth, "--seed", "3", "--sweep", "4"])
@@ -309,12 +241,12 @@ def test_time_prediction_command_line(tmp_path, caplog):
     assert train_set is None and len(val_set) == 4
     np.random.seed(3)
     val_loss, per_batch, pred, t = TP.validation_loss(model, val_set, 3, "l2")
-    assert len(per_batch) == 2 and res["val_loss"] == val_loss and _same(res["pred"], pred) and _same(res["t"], t)
+    assert len(per_batch) == 2 and res["val_loss"] == val_loss and same_bits(res["pred"], pred) and same_bits(res["t"], t)
     assert _logged(caplog, "val_loss: ") == "val_loss: {:.4e}".format(val_loss)
     tiled = TP.tiled_val_set(opt, val_set)
     assert len(tiled) == 9
     all_pred, rmse = evaluate_time_predictor(tiled, model, num_timesteps=4, batch_tiles=3)
-    assert res["rmse"] == rmse and _same(res["all_pred"], all_pred) and all_pred.shape == (5, 9)
+    assert res["rmse"] == rmse and same_bits(res["all_pred"], all_pred) and all_pred.shape == (5, 9)
     assert _logged(caplog, "sweep RMSE: ") == "sweep RMSE: {:.4e}".format(rmse)
     assert sum(r.getMessage().startswith("ratio ") for r in caplog.records) == 5
     # with the training stack's statistics (here the same files): the same value; without a checkpoint: said so
@@ -332,7 +264,7 @@ def test_split_command_line_mixed_prediction(tmp_path, caplog):
     from diffsplitting_amd.core.logger import dict_to_nonedict
     from diffsplitting_amd.data.tiled_predict import predict_tiled_mixed
     from diffsplitting_amd.model import create_model
-    cfgs, pth = _write_configs(tmp_path)
+    cfgs, pth = MU.write_configs(tmp_path)
     (cfg, cfg_path), (tp_cfg, tp_path) = cfgs["joint"], cfgs["tp"]
     out = str(tmp_path / "pred.npy")
     caplog.set_level(logging.INFO, logger="base")
@@ -372,9 +304,5 @@ def test_two_ranks_mixed_prediction_equals_one_rank():
     one-rank run inside the same helper, bit for bit, on every rank."""
     import subprocess
     import sys
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(2, [%r], timeout=500))\n" % (ROOT, os.path.join(ROOT, "tests", "multi_rank_predict_mixed.py")))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    env["DSX_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    r = run_ranks("multi_rank_predict_mixed.py", 2, backend="gloo", launch_timeout=500, timeout=600)
     assert r.returncode == 0 and "PREDICT_MIXED_OK 18 2" in r.stdout, (r.stdout[-500:], r.stderr[-2000:])

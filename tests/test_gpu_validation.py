@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import nets
 from tests.util import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -184,9 +185,8 @@ def test_validate_equals_the_report_applied_by_hand(tmp_path, caplog):
     from diffsplitting_amd.core.validation import group_psnr, validate, validation_report
     from diffsplitting_amd.data.split_dataset import DataLocation, SplitDataset
     from diffsplitting_amd.model import create_model
-    from tests.test_gpu_boundary import _opt, _tiny_indi_section
     torch.manual_seed(11)
-    model = create_model(_opt(_tiny_indi_section()))
+    model = create_model(nets.opt(nets.tiny_indi_section()))
     model.set_new_noise_schedule({"n_timestep": 2}, schedule_phase="val")
     fr = _frames(2, 64, 64)
     val_set = SplitDataset("Hagen", DataLocation(arrays=(fr[..., 0], fr[..., 1])), 32, device="cuda")
@@ -219,10 +219,9 @@ def test_validate_equals_the_report_applied_by_hand(tmp_path, caplog):
 
 
 def _config(tmp_path):
-    from tests.test_gpu_boundary import _tiny_indi_section
     cfg = {"name": "tiny_hagen_indi", "phase": "train", "gpu_ids": [0],
            "path": {"log": "logs", "results": "results", "checkpoint": "checkpoint", "resume_state": None},
-           "datasets": {"val": {"name": "Hagen", "patch_size": 64, "datatype": "img"}}, "model": _tiny_indi_section()}
+           "datasets": {"val": {"name": "Hagen", "patch_size": 64, "datatype": "img"}}, "model": nets.tiny_indi_section()}
     p = tmp_path / "tiny.json"
     p.write_text(json.dumps(cfg, indent=2))
     return ["-c", str(p), "-p", "val", "-gpu", "0", "-rootdir", str(tmp_path), "--synthetic", "2,64,64", "--steps", "2",

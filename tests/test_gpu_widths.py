@@ -19,9 +19,10 @@ import torch
 
 from oracle import cases
 from oracle.unet import unet_forward
-from oracle.weights import synth_state_dict
+from tests import nets
 from tests.gpu_util import maxabs
 from tests.layer_check import DT, check_plan, inputs, reach_tags
+from tests.nets import dev  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -63,12 +64,6 @@ _SD = {}               # case -> state dict
 _ORACLE = {}           # case -> float64 oracle output
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
 def _case_inputs(name):
     case = cases.WIDTH_CASES[name]
     B = case["B"]
@@ -78,15 +73,8 @@ def _case_inputs(name):
 
 
 def _state_dict(name):
-    """synthetic weights for the engine's own parameter table (no fixture: the engine names its parameters)"""
     if name not in _SD:
-        from diffsplitting_amd import engine
-        case = cases.WIDTH_CASES[name]
-        cfg = case["cfg"]
-        eng = engine.UNetEngine(engine.make_cfg(case["flavour"], cfg["in_channel"], cfg["out_channel"],
-                                                cfg["inner_channel"], cfg["norm_groups"], cfg["channel_mults"],
-                                                cfg["attn_res"], cfg["res_blocks"], cfg["image_size"]), case["flavour"])
-        _SD[name] = synth_state_dict(zip(eng.param_names, eng.param_shapes), seed=SEED)
+        _SD[name] = nets.engine_state_dict(cases.WIDTH_CASES[name], SEED)
     return _SD[name]
 
 

@@ -6,8 +6,8 @@ import pytest
 
 from oracle import cases
 from tests.layer_check import finalizes, group_reach_tags
+from tests.plan_cases import GROUP_PLANS as PLANS, GROUP_REACH as REACH, GROUP_REACH_EXEMPT as REACH_EXEMPT
 from tests.plan_dump import read_dump
-from tests.test_gpu_groups import PLANS, REACH, REACH_EXEMPT
 
 KNOBS = ("DSX_WS_MIN_GRID", "DSX_MIN_GRID", "DSX_WS", "DSX_HOST_FIN")      # every knob a plan of the module sets
 DRY = sorted({(name, dt, tuple(sorted(env.items()))) for name, dt, env, _ in PLANS.values()})   # (flat plans: same plan)

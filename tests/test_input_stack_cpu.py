@@ -10,6 +10,8 @@ import re
 import numpy as np
 import pytest
 
+from tests.nets import write_config
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dsx_tileplan_gather_input", "dsx_moments_update", "dsx_moments_finish")
 
@@ -115,16 +117,6 @@ def test_normalization_refuses_malformed_files_by_name(tmp_path):
 
 
 # ----------------------------------------------------------------------------- command line
-def _config(tmp_path, which, **ds):
-    cfg = {"name": "tiny", "phase": "val", "gpu_ids": [0], "path": {"resume_state": None},
-           "datasets": dict({"patch_size": 32, "max_qval": 0.98, "train": {"name": "Hagen", "batch_size": 3},
-                             "val": {"name": "Hagen"}}, **ds),
-           "model": {"which_model_G": which, "loss_type": "l2"}}
-    p = tmp_path / f"{which}{len(ds)}.json"
-    p.write_text(json.dumps(cfg))
-    return str(p)
-
-
 def test_split_refuses_the_new_flags_where_they_do_not_apply(tmp_path, monkeypatch):
     """Every refusal of the issue's section 4 is a SystemExit that names the flag, raised on the command line, the config
     and the normalisation file alone: no rank is started and the process group (the first thing that touches the
@@ -137,7 +129,7 @@ def test_split_refuses_the_new_flags_where_they_do_not_apply(tmp_path, monkeypat
     monkeypatch.setattr(parallel, "init", touched)
     monkeypatch.setattr(parallel, "self_launch", touched)
     monkeypatch.setattr(split, "create_model", touched)
-    indi, joint = _config(tmp_path, "indi"), _config(tmp_path, "joint_indi")
+    indi, joint = write_config(tmp_path, "indi"), write_config(tmp_path, "joint_indi")
     norm, cifar = str(tmp_path / "n.json"), str(tmp_path / "cifar.json")
     for path, dt in ((norm, "Hagen"), (cifar, "cifar10")):
         save_normalization(path, AWKWARD[1], data_type=dt, channel_weights=None, max_qval=0.98, upper_clip=False,
@@ -173,7 +165,7 @@ def test_split_refuses_the_new_flags_where_they_do_not_apply(tmp_path, monkeypat
     refused(["--input", stack, "--norm", norm, "--save-norm", "x.json"], "--save-norm.*--datapath or --frames")
     refused(["--input", stack, "--norm", str(tmp_path / "missing.json")], "--norm .*missing.json")
     refused(["--input", stack, "--norm", norm], "--norm .*target_channel_idx = None, the config says 1",
-            config=_config(tmp_path, "indi", target_channel_idx=1))
+            config=write_config(tmp_path, "indi", target_channel_idx=1))
     # --mmse keeps its meaning and its refusals
     refused(["--mmse", "2"], "--mmse.*joint_indi")
 

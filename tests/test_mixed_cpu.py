@@ -11,15 +11,11 @@ import pytest
 import torch
 
 from tests import mixed_ref as MR
+from tests.bits import same_bits
 from tests.util import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T_VALUES = [0.0, 0.1, 0.29, 0.35000000000000003, 0.5, 1.0]
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 def _case_c(g):
@@ -37,7 +33,7 @@ def test_restated_table_equals_the_reference_bitwise():
             tab = MR.range_table(g[f"{name}_ch0"], g[f"{name}_ch1"], n, g[f"{name}_mean_target"], g[f"{name}_std_target"])
             ref = g[f"{name}_table_{n}"]
             assert ref.shape == (n + 1, 2) and ref.dtype == np.float64
-            assert np.array_equal(_bits(tab), _bits(ref)), (name, n)
+            assert same_bits(tab, ref), (name, n)
     # the fixture is what the issue asks for: an extreme on the first and the last pixel, an awkward pixel count
     a = g["a_table_100"]
     assert g["a_ch0"].reshape(-1)[0] == g["a_ch0"].max() and g["a_ch1"].reshape(-1)[-1] == g["a_ch1"].max()
@@ -60,13 +56,13 @@ def test_fp32_chain_equals_torch_float32_bitwise():
         c2 = 2 * (inp2 - minv) / (maxv - minv) - 1
         assert c1.dtype == torch.float32
         mix, cls = MR.chain_f32(t0, t1, t, MR.rows(table, t))
-        assert np.array_equal(_bits(mix[0]), _bits(inp1[:, 0].numpy())) and np.array_equal(_bits(mix[1]), _bits(inp2[:, 0].numpy()))
-        assert np.array_equal(_bits(cls[0]), _bits(c1[:, 0].numpy())) and np.array_equal(_bits(cls[1]), _bits(c2[:, 0].numpy())), t
+        assert same_bits(mix[0], inp1[:, 0].numpy()) and same_bits(mix[1], inp2[:, 0].numpy())
+        assert same_bits(cls[0], c1[:, 0].numpy()) and same_bits(cls[1], c2[:, 0].numpy()), t
         mt = np.float64(t)                                                  # the sweep: np.arange values, channel 1
         inp = tar[:, :1] * mt + tar[:, 1:2] * (1 - mt)
         t_min, t_max = tab[int(mt * 100)]
         sw = 2 * (inp - t_min) / (t_max - t_min) - 1
-        assert np.array_equal(_bits(cls[1]), _bits(sw[:, 0].numpy())), t
+        assert same_bits(cls[1], sw[:, 0].numpy()), t
     assert int(0.29 * 100) == 28                                            # the truncating row index is exercised
 
 
@@ -89,7 +85,7 @@ def test_fp32_chain_equals_the_reference_items_within_the_bound():
         item = g["item_inp"][k]
         assert item.shape == (1, 32, 32)
         if item.dtype == np.float32:
-            assert np.array_equal(_bits(cls[1]), _bits(item[0]))
+            assert same_bits(cls[1], item[0])
         else:
             _, bound = MR.chain_bound(t0, t1, t, lohi)
             err = np.abs(cls[1].astype(np.float64) - item[0])

@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from oracle import cases
+from tests.bits import same_bits
 from tests.util import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -157,19 +158,15 @@ def test_sample_t_linear_indi_default_and_attributes():
 
 
 # ----------------------------------------------------------------------------- coefficient vectors
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
 def test_coefficients_sr3_bitwise_and_reproduce_x_noisy():
     g = load_golden("objective_sr3")
     c = torch.from_numpy(g["continuous_sqrt_alpha_cumprod"])
     c0, c2 = _sr3().q_coefficients(c)
     cv = c.view(-1, 1, 1, 1)
-    assert torch.equal(_bits(c0), _bits(cv.reshape(-1)))
-    assert torch.equal(_bits(c2), _bits((1 - cv ** 2).sqrt().reshape(-1)))
+    assert same_bits(c0, cv.reshape(-1))
+    assert same_bits(c2, (1 - cv ** 2).sqrt().reshape(-1))
     x = c0.view(-1, 1, 1, 1) * torch.from_numpy(g["target"]) + c2.view(-1, 1, 1, 1) * torch.from_numpy(g["noise"])
-    assert torch.equal(_bits(x), _bits(torch.from_numpy(g["x_noisy"])))
+    assert same_bits(x, torch.from_numpy(g["x_noisy"]))
 
 
 def test_coefficients_ddpm_bitwise_and_reproduce_x_noisy():
@@ -177,10 +174,10 @@ def test_coefficients_ddpm_bitwise_and_reproduce_x_noisy():
     s = _ddpm()
     t = torch.from_numpy(g["t"])
     c0, c2 = s.q_coefficients(t)
-    assert torch.equal(_bits(c0), _bits(s.sqrt_alphas_cumprod.gather(-1, t)))
-    assert torch.equal(_bits(c2), _bits(s.sqrt_one_minus_alphas_cumprod.gather(-1, t)))
+    assert same_bits(c0, s.sqrt_alphas_cumprod.gather(-1, t))
+    assert same_bits(c2, s.sqrt_one_minus_alphas_cumprod.gather(-1, t))
     x = c0.view(-1, 1, 1, 1) * torch.from_numpy(g["target"]) + c2.view(-1, 1, 1, 1) * torch.from_numpy(g["noise"])
-    assert torch.equal(_bits(x), _bits(torch.from_numpy(g["x_noisy"])))
+    assert same_bits(x, torch.from_numpy(g["x_noisy"]))
     # the plain gathers of the forward process
     mean, var, logvar = s.q_mean_variance(torch.from_numpy(g["target"]), t)
     assert torch.equal(mean, c0.view(-1, 1, 1, 1) * torch.from_numpy(g["target"]))
@@ -198,13 +195,13 @@ def test_coefficients_indi_bitwise_and_reproduce_x_noisy():
     t = torch.from_numpy(g["t"])
     c0, c1, c2 = s.q_coefficients(t)
     tv = t.reshape(-1, 1, 1, 1)
-    assert torch.equal(_bits(c0), _bits((1 - tv).reshape(-1))) and torch.equal(_bits(c1), _bits(t))
-    assert torch.equal(_bits(c2), _bits((s.e * tv).reshape(-1)))
+    assert same_bits(c0, (1 - tv).reshape(-1)) and same_bits(c1, t)
+    assert same_bits(c2, (s.e * tv).reshape(-1))
     assert s.get_e(t) == s.e
     v = lambda c: c.view(-1, 1, 1, 1)
     x_end = torch.cat([torch.from_numpy(g["input"])] * 2, dim=1)
     x = v(c0) * torch.from_numpy(g["target"]) + v(c1) * x_end + torch.from_numpy(g["noise"]) * v(c2)
-    assert torch.equal(_bits(x), _bits(torch.from_numpy(g["x_noisy"])))
+    assert same_bits(x, torch.from_numpy(g["x_noisy"]))
 
 
 # ----------------------------------------------------------------------------- refusals

@@ -7,6 +7,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from tests.rank_worker import run_ranks
+
 
 def _free_port():
     with socket.socket() as s:
@@ -177,36 +179,24 @@ def test_bench_refuses_mismatched_world():
 
 
 def test_self_launch_reports_a_failing_rank(tmp_path):
-    import subprocess
-    import sys
     script = tmp_path / "child.py"
     script.write_text("import os, sys\nprint('rank', os.environ['RANK'])\nsys.exit(3 if os.environ['RANK'] == '1' else 0)\n")
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(2, [%r]))\n" % (ROOT, str(script)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    r = run_ranks(str(script), 2, timeout=120)
     assert r.returncode == 1 and "rank 0" in r.stdout and "ranks failed" in r.stderr
 
 
 def test_self_launch_stops_the_others_when_one_rank_dies(tmp_path):
     """A rank that dies before the rendezvous must not leave rank 0 waiting: all children are watched together, the
     first failure (or the timeout) ends the rest."""
-    import subprocess
-    import sys
     import time
     script = tmp_path / "child.py"
     script.write_text("import os, sys, time\nprint('rank', os.environ['RANK'], flush=True)\n"
                       "sys.exit(5) if os.environ['RANK'] == '1' else time.sleep(600)\n")
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(2, [%r]))\n" % (ROOT, str(script)))
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     t0 = time.monotonic()
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    r = run_ranks(str(script), 2, timeout=120)
     assert r.returncode == 1 and "ranks failed" in r.stderr and time.monotonic() - t0 < 60
     # the timeout form
     script.write_text("import time\ntime.sleep(600)\n")
-    code = ("import sys; sys.path.insert(0, %r)\nfrom diffsplitting_amd import parallel\n"
-            "sys.exit(parallel.self_launch(2, [%r], timeout=2))\n" % (ROOT, str(script)))
     t0 = time.monotonic()
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+    r = run_ranks(str(script), 2, launch_timeout=2, timeout=120)
     assert r.returncode == 1 and "timed out" in r.stderr and time.monotonic() - t0 < 60

@@ -13,40 +13,9 @@ import sys
 
 import pytest
 
+from tests.plan_cases import CONFIGS, ENV_SETS
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# (flavour, cfg kwargs, B, H, W, cond_channels)
-CONFIGS = {
-    "c2_sr3_128_b16": ("sr3", dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=32,
-                                   channel_mults=(1, 2, 4, 8, 8), attn_res=(16,), res_blocks=2, image_size=128), 16, 128, 128, 3),
-    "c2_sr3_128_b1": ("sr3", dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=32,
-                                  channel_mults=(1, 2, 4, 8, 8), attn_res=(16,), res_blocks=2, image_size=128), 1, 128, 128, 3),
-    "c4_sr3_512_b2": ("sr3", dict(in_channel=6, out_channel=3, inner_channel=64, norm_groups=16,
-                                  channel_mults=(1, 2, 4, 8, 16), attn_res=(), res_blocks=1, image_size=512), 2, 512, 512, 3),
-    "c3_hagen_512_b8": ("ddpm", dict(in_channel=2, out_channel=2, inner_channel=16, norm_groups=16,
-                                     channel_mults=(1, 2, 4, 8), attn_res=(), res_blocks=1, image_size=32), 8, 512, 512, 0),
-    "c1_cifar_32_b4": ("ddpm", dict(in_channel=6, out_channel=6, inner_channel=16, norm_groups=16,
-                                    channel_mults=(1, 2, 4, 8), attn_res=(), res_blocks=1, image_size=32), 4, 32, 32, 0),
-    "ragged_48x80_b3": ("ddpm", dict(in_channel=2, out_channel=2, inner_channel=16, norm_groups=16,
-                                     channel_mults=(1, 2, 4), attn_res=(), res_blocks=1, image_size=32), 3, 48, 80, 0),
-}
-
-# the settings of the round-1 tuning sweeps (tools/tune.sh runs), the faulting one first
-ENV_SETS = [
-    {"DSX_MIN_GRID": "448"},
-    {},
-    {"DSX_MIN_GRID": "256"}, {"DSX_MIN_GRID": "384"}, {"DSX_MIN_GRID": "768"}, {"DSX_MIN_GRID": "1024"}, {"DSX_MIN_GRID": "2048"},
-    {"DSX_WS_MIN_GRID": "1"}, {"DSX_WS_MIN_GRID": "448"}, {"DSX_WS_MIN_GRID": "100000"},
-    {"DSX_WS": "0"}, {"DSX_SPLITK": "0"}, {"DSX_FUSE_STATS": "0"}, {"DSX_WS": "0", "DSX_SPLITK": "0", "DSX_FUSE_STATS": "0"},
-    {"DSX_TILES_WIDE": "1,2,5"}, {"DSX_TILES_WIDE": "0,1,2,5"}, {"DSX_TILES_WIDE": "2,5"}, {"DSX_TILES_NARROW": "4,5"},
-    {"DSX_TILES_NARROW": "3,4,5"}, {"DSX_TILES_WIDE_SPLIT": "1,2,5"}, {"DSX_TILES_NARROW_SPLIT": "4,5"},
-    {"DSX_TILES_WS_WIDE": "2"}, {"DSX_TILES_WS_WIDE": "2,1"}, {"DSX_TILES_WS_WIDE_1X1": "2"}, {"DSX_TILES_WS_NARROW": "5"},
-    {"DSX_TILES_WS_NARROW": "5,4"}, {"DSX_MIN_GRID": "448", "DSX_TILES_WIDE": "0,2,3,4"}, {"DSX_MIN_GRID": "448", "DSX_WS": "0"},
-    # round 3: chunks per item of the persistent kernel, the 1 x 1 XCD mapping
-    {"DSX_WS_G2": "0"}, {"DSX_WS_C4": "0"}, {"DSX_WS_MAP3": "0"}, {"DSX_WS_G2": "0", "DSX_WS_C4": "0", "DSX_WS_MAP3": "0"},
-    {"DSX_WS_G4_MIN64": "1000"}, {"DSX_WS_G2_MIN64": "2", "DSX_WS_G2_MIN128": "2", "DSX_WS_G4_MIN64": "4", "DSX_WS_C4_MIN": "4"},
-    {"DSX_WS_MIN_GRID": "1", "DSX_WS_G2_MIN64": "2", "DSX_WS_G4_MIN64": "4", "DSX_WS_C4_MIN": "4"},
-]
 
 _CHILD = r"""
 import ctypes as C, json, sys
@@ -330,7 +299,7 @@ def shape_plan_tags(tmp_path):
     from oracle import cases
     from tests.layer_check import geom_tag
     from tests.plan_dump import read_dump
-    from tests.test_gpu_shapes import PLANS
+    from tests.plan_cases import SHAPE_PLANS as PLANS
     code = {"f32": 0, "bf16": 1, "f16": 2}
     by_env = {}
     for plan, (name, dt, B, env) in PLANS.items():
@@ -364,7 +333,8 @@ def test_shape_plans_reach_their_geometry_classes(tmp_path):
     the layer table gives) names the tile the planner wrote into every launch's arguments; the classes each operand
     type's plans reach are the recorded ones (tests/golden/shape_reach.json, which test_reach of the GPU module asks
     for); their union holds the module's REACH and REACH_TAILS."""
-    from tests.test_gpu_shapes import PLANS, REACH, REACH_TAILS, reach_by_dtype
+    from tests.plan_cases import SHAPE_PLANS as PLANS, SHAPE_REACH as REACH, SHAPE_REACH_TAILS as REACH_TAILS
+    from tests.plan_cases import shape_reach_by_dtype as reach_by_dtype
     tags = shape_plan_tags(tmp_path)
     by_dt = {}
     for plan, pairs in tags.items():

@@ -11,18 +11,11 @@ import pytest
 import torch
 
 from oracle import cases
+from tests.bits import same_bits
 from tests.util import load_golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCHED = cases.SCHEDULES["lin_8"]
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def _bit_equal(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
 def _t(g, key):
@@ -89,15 +82,15 @@ def test_sr3_fixture_is_self_consistent(t, clip):
     mean = bufs["posterior_mean_coef1"][t] * x_recon + bufs["posterior_mean_coef2"][t] * x
     logvar = bufs["posterior_log_variance_clipped"][t]
     sample = mean + z * (0.5 * logvar).exp()
-    assert _bit_equal(x_recon, _t(g, "x_recon" + tag))
-    assert _bit_equal(mean, _t(g, "model_mean" + tag))
-    assert _bit_equal(sample, _t(g, "sample" + tag))
-    assert _bit_equal(logvar, _t(g, f"log_variance_t{t}"))
+    assert same_bits(x_recon, _t(g, "x_recon" + tag))
+    assert same_bits(mean, _t(g, "model_mean" + tag))
+    assert same_bits(sample, _t(g, "sample" + tag))
+    assert same_bits(logvar, _t(g, f"log_variance_t{t}"))
     # the same through the step-table row: what the kernel is handed
     r = engine.gaussian_step_rows(bufs, gamma, "sr3", np.full(2, t))
     k0, k1, k2 = _kernel_order(x, net, r, z, clip=bool(clip))
-    assert _bit_equal(k0, x_recon) and _bit_equal(k1, mean)
-    assert _bit_equal(k2, sample) if t > 0 else torch.equal(k2, sample)     # t == 0: the reference adds 0 * sigma
+    assert same_bits(k0, x_recon) and same_bits(k1, mean)
+    assert same_bits(k2, sample) if t > 0 else torch.equal(k2, sample)     # t == 0: the reference adds 0 * sigma
     assert np.array_equal(g[f"time_t{t}"], r["tcond"].reshape(2, 1))        # the UNet's time value
     if clip:
         assert bool((_t(g, f"x_recon_t{t}_clip0").abs() > 1).any())         # the clamp did something
@@ -118,15 +111,15 @@ def test_ddpm_fixture_is_self_consistent(tag):
     assert z.shape[0] == (1 if tag == "repeat" else 2)
     mask = (1 - (t == 0).float()).reshape(2, 1, 1, 1)
     sample = mean + mask * (0.5 * logvar).exp() * noise                      # ddpm diffusion.py:203
-    assert _bit_equal(x_recon, _t(g, "x_recon_" + tag)) and _bit_equal(mean, _t(g, "model_mean_" + tag))
-    assert _bit_equal(sample, _t(g, "sample_" + tag))
-    assert _bit_equal(ext("posterior_variance"), _t(g, "variance_" + tag))
-    assert _bit_equal(logvar, _t(g, "log_variance_" + tag))
+    assert same_bits(x_recon, _t(g, "x_recon_" + tag)) and same_bits(mean, _t(g, "model_mean_" + tag))
+    assert same_bits(sample, _t(g, "sample_" + tag))
+    assert same_bits(ext("posterior_variance"), _t(g, "variance_" + tag))
+    assert same_bits(logvar, _t(g, "log_variance_" + tag))
     r = engine.gaussian_step_rows(bufs, gamma, "ddpm", t)
     k0, k1, k2 = _kernel_order(x, net, r, noise, clip=True)
-    assert _bit_equal(k0, x_recon) and _bit_equal(k1, mean)
+    assert same_bits(k0, x_recon) and same_bits(k1, mean)
     nz = t != 0
-    assert _bit_equal(k2[nz], sample[nz]) and torch.equal(k2, sample)
+    assert same_bits(k2[nz], sample[nz]) and torch.equal(k2, sample)
     assert np.array_equal(g["time_" + tag].astype(np.float32), r["tcond"])   # per-sample float(t)
 
 
@@ -139,7 +132,7 @@ def test_indi_fixture_is_self_consistent(tag):
     t = torch.Tensor([t_cur])
     noise = z * (e * (t - delta))                                            # indi.py:67
     sample = delta / t * net + (1 - delta / t) * x + noise
-    assert _bit_equal(sample, _t(g, "sample_" + tag))
+    assert same_bits(sample, _t(g, "sample_" + tag))
     tc, c1, c2, sg = engine.indi_step_row(delta, t_cur, e)
     assert np.float32(tc) == g["time_" + tag][0]
     r = {k: np.full(2, v, dtype=np.float32) for k, v in (("c1", c1), ("c2", c2), ("sigma", sg))}
@@ -148,7 +141,7 @@ def test_indi_fixture_is_self_consistent(tag):
         assert c2 == 0.0 and sg == 0.0                                       # delta == t_cur: x_t and the noise drop out
         assert torch.equal(out, sample)
     else:
-        assert _bit_equal(out, sample)
+        assert same_bits(out, sample)
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
@@ -164,12 +157,12 @@ def test_interpolate_fixture_pins_the_scalar_rounding(tag):
     xt = []
     for i in (1, 2):
         q = ext("sqrt_alphas_cumprod") * _t(g, f"x{i}") + ext("sqrt_one_minus_alphas_cumprod") * _t(g, f"noise{i}_{tag}")
-        assert _bit_equal(q, _t(g, f"xt{i}_{tag}"))
+        assert same_bits(q, _t(g, f"xt{i}_{tag}"))
         xt.append(q)
     start = _t(g, "start_" + tag)
-    assert _bit_equal((1 - lam) * xt[0] + lam * xt[1], start)
+    assert same_bits((1 - lam) * xt[0] + lam * xt[1], start)
     c, d = torch.tensor(np.float32(1 - lam)), torch.tensor(np.float32(lam))
-    assert _bit_equal(c * xt[0] + d * xt[1], start)
+    assert same_bits(c * xt[0] + d * xt[1], start)
     assert g["step_noise_" + tag].shape == (t, 2, 2, 32, 32)
 
 

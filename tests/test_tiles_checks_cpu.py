@@ -6,6 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.nets import dbl, i64
+
 ERR_INVALID = -1
 N, H, W, P = 2, 40, 56, 32
 FAKE = C.c_void_p(4096)
@@ -18,14 +20,6 @@ def _lib():
 
 def _err():
     return _lib().dsx_last_error().decode()
-
-
-def _i64(*v):
-    return (C.c_int64 * len(v))(*v)
-
-
-def _dbl(*v):
-    return (C.c_double * len(v))(*v)
 
 
 def _table(rows):
@@ -42,28 +36,28 @@ def _ids(ids):
 
 # ----------------------------------------------------------------------------- the five per-call gathers
 def _gather(starts, ids, count):
-    return _lib().dsx_tiles_gather(FAKE, _i64(N, H, W), _i64(1, P, P), starts, ids, count, FAKE, None)
+    return _lib().dsx_tiles_gather(FAKE, i64(N, H, W), i64(1, P, P), starts, ids, count, FAKE, None)
 
 
 def _gather_norm(starts, ids, count):
-    return _lib().dsx_tiles_gather_norm(FAKE, FAKE, _i64(N, H, W), _i64(1, P, P), starts, ids, count, 1.0, 1.0,
-                                        _dbl(0, 1, 0, 1, 0, 1), 0, FAKE, FAKE, None)
+    return _lib().dsx_tiles_gather_norm(FAKE, FAKE, i64(N, H, W), i64(1, P, P), starts, ids, count, 1.0, 1.0,
+                                        dbl(0, 1, 0, 1, 0, 1), 0, FAKE, FAKE, None)
 
 
 def _gather_norm_planes(starts, ids, count):
-    return _lib().dsx_tiles_gather_norm_planes(FAKE, FAKE, _i64(N, 3, H, W), _i64(P, P), starts, ids, count, 1.0, 1.0, 0.0,
-                                               1.0, _dbl(*[0.0] * 6), _dbl(*[1.0] * 6), FAKE, FAKE, None)
+    return _lib().dsx_tiles_gather_norm_planes(FAKE, FAKE, i64(N, 3, H, W), i64(P, P), starts, ids, count, 1.0, 1.0, 0.0,
+                                               1.0, dbl(*[0.0] * 6), dbl(*[1.0] * 6), FAKE, FAKE, None)
 
 
 def _gather_mix(starts, ids, count):
-    return _lib().dsx_tiles_gather_mix(FAKE, FAKE, _i64(N, H, W), _i64(1, P, P), starts, ids, count, _dbl(0, 1, 0, 1), 0.5,
+    return _lib().dsx_tiles_gather_mix(FAKE, FAKE, i64(N, H, W), i64(1, P, P), starts, ids, count, dbl(0, 1, 0, 1), 0.5,
                                        None, FAKE, None, None, None)
 
 
 def _gather_mix_items(starts, ids, count):
     assert ids is None                                                # the per-item form has no id list
     t = np.full(max(int(count), 1), 0.5)
-    return _lib().dsx_tiles_gather_mix_items(FAKE, FAKE, _i64(N, H, W), _i64(1, P, P), starts, count, _dbl(0, 1, 0, 1),
+    return _lib().dsx_tiles_gather_mix_items(FAKE, FAKE, i64(N, H, W), i64(1, P, P), starts, count, dbl(0, 1, 0, 1),
                                              t.ctypes.data_as(C.POINTER(C.c_double)), None, FAKE, None, None, None)
 
 
@@ -106,11 +100,11 @@ def test_gather_refuses_more_items_than_a_launch_takes(name, label, call):
 
 # ----------------------------------------------------------------------------- the two per-call stitches
 def _stitch(regions, count):
-    return _lib().dsx_stitch(FAKE, count, 1, P, P, regions, FAKE, _i64(N, H, W), None)
+    return _lib().dsx_stitch(FAKE, count, 1, P, P, regions, FAKE, i64(N, H, W), None)
 
 
 def _stitch_psnr(regions, count):
-    return _lib().dsx_stitch_psnr(FAKE, count, 1, P, P, regions, FAKE, _i64(N, H, W), FAKE, FAKE, None)
+    return _lib().dsx_stitch_psnr(FAKE, count, 1, P, P, regions, FAKE, i64(N, H, W), FAKE, FAKE, None)
 
 
 STITCHES = [("stitch", _stitch), ("stitch_psnr", _stitch_psnr)]
@@ -146,7 +140,7 @@ def plan():
 def _plan_forms():
     from diffsplitting_amd import _lib
     lib = _lib.lib
-    d4, d6 = _dbl(0, 1, 0, 1), _dbl(0, 1, 0, 1, 0, 1)
+    d4, d6 = dbl(0, 1, 0, 1), dbl(0, 1, 0, 1, 0, 1)
     return [
         ("tileplan_gather", lambda h, f, s, c: lib.dsx_tileplan_gather(h, FAKE, f, s, c, FAKE, None)),
         ("tileplan_gather_norm", lambda h, f, s, c: lib.dsx_tileplan_gather_norm(h, FAKE, FAKE, f, s, c, 1.0, 1.0, d6, 0, FAKE,

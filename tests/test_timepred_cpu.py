@@ -3,12 +3,13 @@ pointers: a call that got past the checks would not return INVALID with these me
 two command lines, and the batching arithmetic of ``validation_loss`` against a torch restatement of the reference's
 loop (time_prediction_training.py:135-140, 144)."""
 import ctypes as C
-import json
 import os
 
 import numpy as np
 import pytest
 import torch
+
+from tests.nets import dbl, i64, write_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dsx_tiles_gather_mix_items"
@@ -29,8 +30,6 @@ def test_host_side_refusals_name_the_item():
     lib = _lib.lib
     err = lambda: lib.dsx_last_error().decode()
     fake = C.c_void_p(4096)
-    dbl = lambda *v: (C.c_double * len(v))(*v)
-    i64 = lambda *v: (C.c_int64 * len(v))(*v)
     shape, patch = i64(2, 8, 9), i64(1, 4, 3)
     norm = dbl(0, 1, 0, 1)
     starts = i64(0, 0, 0, 1, 4, 6, 0, 1, 1)                              # item 1 is the last valid corner
@@ -66,19 +65,9 @@ def test_host_side_refusals_name_the_item():
     assert call(count=0) == 0
 
 
-def _config(tmp_path, which, loss_type="l2"):
-    cfg = {"name": "tiny", "phase": "val", "gpu_ids": [0], "path": {"resume_state": None},
-           "datasets": {"patch_size": 32, "max_qval": 0.98, "train": {"name": "Hagen", "batch_size": 3},
-                        "val": {"name": "Hagen"}},
-           "model": {"which_model_G": which, "loss_type": loss_type}}
-    p = tmp_path / f"{which}.json"
-    p.write_text(json.dumps(cfg))
-    return str(p)
-
-
 def test_split_refuses_the_mixed_flags_where_they_do_not_apply(tmp_path):
     from diffsplitting_amd import split
-    indi, joint = _config(tmp_path, "indi"), _config(tmp_path, "joint_indi")
+    indi, joint = write_config(tmp_path, "indi"), write_config(tmp_path, "joint_indi")
     with pytest.raises(SystemExit, match="--mix-t.*joint_indi"):
         split.main(["-c", indi, "--mix-t", "0.3", "--t-from", "given"])
     for flag, value in (("--time-predictor", joint), ("--time-predictor-checkpoint", "x.pth"), ("--mmse", "2"),
@@ -101,7 +90,7 @@ def test_split_refuses_the_mixed_flags_where_they_do_not_apply(tmp_path):
 def test_time_prediction_refusals(tmp_path):
     from diffsplitting_amd import time_prediction as TP
     from diffsplitting_amd._lib import DsxError
-    cfg = _config(tmp_path, "UnetClassifier")
+    cfg = write_config(tmp_path, "UnetClassifier")
     with pytest.raises(SystemExit, match="--sweep 0"):
         TP.main(["-c", cfg, "--datapath", "--sweep", "0"])
     with pytest.raises(SystemExit, match="-p train"):
@@ -113,7 +102,7 @@ def test_time_prediction_refusals(tmp_path):
     with pytest.raises(DsxError, match="loss_type = 'huber'"):
         TP.batch_losses(np.zeros(4, np.float32), np.zeros(4), 3, "huber")
     with pytest.raises(DsxError, match="loss_type = 'huber'"):            # from the config, before anything is built
-        TP.main(["-c", _config(tmp_path, "UnetClassifier", loss_type="huber"), "--datapath"])
+        TP.main(["-c", write_config(tmp_path, "UnetClassifier", loss_type="huber"), "--datapath"])
     with pytest.raises(NotImplementedError, match="Tiled prediction"):
         TP.get_datasets({}, tiled_pred=True)
 

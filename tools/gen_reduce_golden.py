@@ -49,7 +49,7 @@ def main(commit, path=DEFAULT, *names):
     assert os.path.realpath(lib_path) != os.path.realpath(os.path.join(ROOT, "diffsplitting_amd", "libdsx.so")), \
         "the fixture is recorded from the parent's library, not from this tree's"
     from diffsplitting_amd import _lib
-    from tests.test_gpu_reduce_bits import CASES
+    from tests.reduce_cases import CASES
     assert _lib.LIB_PATH == lib_path
     unknown = [n for n in names if n not in CASES]
     assert not unknown, f"no such case: {unknown}; one of {list(CASES)}"

@@ -6,7 +6,7 @@ alike exactly when the figures agree (DSX_LIB_PATH selects the library; `cmp` th
 import ctypes as C, hashlib, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from tests.test_planner_cpu import CONFIGS, ENV_SETS
+from tests.plan_cases import CONFIGS, ENV_SETS
 from diffsplitting_amd import _lib
 out = sys.argv[1]
 os.makedirs(out, exist_ok=True)
