@@ -579,7 +579,7 @@ __device__ __forceinline__ void normal4(unsigned long long seed, unsigned long l
   unsigned r[4];
   philox4x32_10((unsigned)idx4, (unsigned)(idx4 >> 32), (unsigned)subseq, (unsigned)(subseq >> 32),
                 (unsigned)seed, (unsigned)(seed >> 32), r);
-  const float u0 = ((float)r[0] + 0.5f) * 2.3283064365386963e-10f;  // (0,1)
+  const float u0 = ((float)r[0] + 0.5f) * 2.3283064365386963e-10f;  // (0,1]
   const float u1 = ((float)r[1] + 0.5f) * 2.3283064365386963e-10f;
   const float u2 = ((float)r[2] + 0.5f) * 2.3283064365386963e-10f;
   const float u3 = ((float)r[3] + 0.5f) * 2.3283064365386963e-10f;
@@ -598,7 +598,7 @@ __device__ __forceinline__ float normal1(unsigned long long seed, unsigned long 
   philox4x32_10((unsigned)idx4, (unsigned)(idx4 >> 32), (unsigned)subseq, (unsigned)(subseq >> 32),
                 (unsigned)seed, (unsigned)(seed >> 32), r);
   const unsigned ru = (k & 2) ? r[2] : r[0], rv = (k & 2) ? r[3] : r[1];
-  const float u = ((float)ru + 0.5f) * 2.3283064365386963e-10f;  // (0,1)
+  const float u = ((float)ru + 0.5f) * 2.3283064365386963e-10f;  // (0,1]
   const float v = ((float)rv + 0.5f) * 2.3283064365386963e-10f;
   const float rad = sqrtf(-2.0f * logf(u));
   float s, c;

@@ -13,6 +13,7 @@ from oracle.weights import synth_state_dict
 from tests import nets
 from tests.gpu_util import DrawRecorder, maxabs
 from tests.rank_worker import run_ranks
+from tests.tiled_util import numpy_item as _numpy_item
 from tests.util import GOLDEN, golden_state_dict, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -358,26 +359,11 @@ def test_packed_weight_cache(tmp_path):
     assert unet.pack_cache_hit is not True and not torch.equal(e, d)
 
 
-def _numpy_item(ch0, ch1, loc, p, nd, w, from_norm_target):
-    """SplitDataset.__getitem__ (data/split_dataset.py:237-278) restated with numpy for one grid patch."""
-    n, y, x = loc
-    patch1 = ch0[n, y:y + p, x:x + p].astype(np.float32)[None]
-    patch2 = ch1[n, y:y + p, x:x + p].astype(np.float32)[None]
-    target = np.concatenate([patch1, patch2], axis=0)
-    target = ((target - nd["mean_target"].reshape(-1, 1, 1)) / nd["std_target"].reshape(-1, 1, 1)).astype(np.float32)
-    if from_norm_target:
-        inp = w[0] * target[0:1] + w[1] * target[1:2]
-    else:
-        inp = w[0] * patch1 + w[1] * patch2
-        inp = ((inp - nd["mean_input"]) / nd["std_input"]).astype(np.float32)
-    return {"input": inp, "target": target}
-
-
 def test_device_split_dataset_matches_numpy_restatement():
     """N2: frames resident on the GPU; normalisation statistics (compute_normalization_dict :29-74: quantiles) on the
     device equal numpy's; batches of normalised tiles from one HIP launch are bit-exact with __getitem__'s arithmetic.
     PARITY UNPINNED: data/split_dataset.py cannot be imported here (albumentations, skimage), so the comparison is
-    with a numpy restatement of its arithmetic written in this file (`_numpy_item`), not with the reference itself;
+    with a numpy restatement of its arithmetic (tests/tiled_util.py, `numpy_item`), not with the reference itself;
     the reference's only fixture for this path (tests/test_tiling_setup.py) is the next test."""
     from diffsplitting_amd.data.split_dataset import (DataLocation, SplitDataset, SplitDatasetTiledPred,
                                                       compute_normalization_dict)

@@ -60,32 +60,7 @@ def test_items_bit_equal_to_the_reference(val_dir, tag, patch, kw):
 
 
 # ----------------------------------------------------------------------------- the entry point, called directly
-def _call(f0, f1, shape4, patch, loc, w, mean_inp, std_inp, mt, st, tin, ttar, count=None):
-    from diffsplitting_amd._lib import lib
-    loc = np.ascontiguousarray(np.asarray(loc, dtype=np.int64).reshape(-1, 3))
-    mt, st = np.ascontiguousarray(mt, dtype=np.float64), np.ascontiguousarray(st, dtype=np.float64)
-    pd = C.POINTER(C.c_double)
-    ptr = lambda t: None if t is None else C.c_void_p(t if isinstance(t, int) else t.data_ptr())
-    return lib.dsx_tiles_gather_norm_planes(ptr(f0), ptr(f1), (C.c_int64 * 4)(*shape4), (C.c_int64 * 2)(*patch),
-                                            loc.ctypes.data_as(C.POINTER(C.c_int64)), None,
-                                            loc.shape[0] if count is None else count, float(w[0]), float(w[1]),
-                                            float(mean_inp), float(std_inp), mt.ctypes.data_as(pd), st.ctypes.data_as(pd),
-                                            ptr(tin), ptr(ttar), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-
-def _numpy_items(a, b, loc, ph, pw, w, mean_inp, std_inp, mt, st):
-    """The reference's item (data/split_dataset.py:248-272) in numpy: fp32 crops, the target against the (2 Cc, 1, 1)
-    float64 statistics, the fp32 weighted sum against the float64 input statistics, each rounded to fp32 once."""
-    tin, ttar = [], []
-    for n, y, x in loc:
-        p1 = a[n][..., y:y + ph, x:x + pw].astype(np.float32)
-        p2 = b[n][..., y:y + ph, x:x + pw].astype(np.float32)
-        target = np.concatenate([p1, p2], axis=0)
-        ttar.append(((target.astype(np.float64) - mt.reshape(-1, 1, 1)) / st.reshape(-1, 1, 1)).astype(np.float32))
-        mix = np.float32(w[0]) * p1 + np.float32(w[1]) * p2
-        assert mix.dtype == np.float32
-        tin.append(((mix.astype(np.float64) - np.float64(mean_inp)) / np.float64(std_inp)).astype(np.float32))
-    return np.stack(tin), np.stack(ttar)
+_call, _numpy_items = CF.gather_planes, CF.numpy_items
 
 
 def test_one_plane_equals_the_grey_export():

@@ -8,21 +8,13 @@ import torch
 from oracle import cases
 from tests import nets
 from tests.bits import bits, same_bits
+from tests.steps_util import ref_q as _ref_q
 from tests.util import golden_state_dict
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 FP32_TOL = 1e-3          # the project's per-pixel fp32 bound on a UNet output
 N_INDI = 20
-
-
-def _ref_q(x0, c0, c2, z, xe=None, c1=None):
-    """The reference's q_sample on the CPU in fp32: separately rounded products and sums, left to right."""
-    v = lambda c: c.view(-1, 1, 1, 1)
-    out = v(c0) * x0
-    if xe is not None:
-        out = out + v(c1) * torch.cat([xe] * (x0.shape[1] // xe.shape[1]), dim=1)
-    return out + v(c2) * z
 
 
 COEF = (torch.tensor([0.75623951, 0.31, 0.9990234]), torch.tensor([0.1, 1.0, 0.45]), torch.tensor([0.654321, 0.0123, 0.7]))

@@ -13,6 +13,7 @@ from tests import nets
 from tests.bits import same_bits
 from tests.gpu_util import maxabs
 from tests.steps_util import Source, constant_unet, off
+from tests.steps_util import ref_step as _ref_step
 from tests.util import golden_state_dict, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -30,20 +31,6 @@ def _t(g, key):
 COEF = dict(a=torch.tensor([1.0371, 2.2360679, 1.0000501]), b=torch.tensor([0.2748, 2.0, 0.0100123]),
             c1=torch.tensor([0.75623951, 0.31, 0.9990234]), c2=torch.tensor([0.1, 0.654321, 0.0123]),
             sigma=torch.tensor([0.37, 0.0, 0.81]))
-
-
-def _ref_step(x, net, co, z, predict_eps, clip, repeat=False):
-    """dsx_posterior_step in torch fp32 on the CPU: separately rounded products and sums."""
-    v = lambda k: co[k].view(-1, 1, 1, 1)
-    x0 = net
-    if predict_eps:
-        x0 = v("a") * x - v("b") * net
-        if clip:
-            x0 = x0.clamp(-1.0, 1.0)
-    mean = v("c1") * x0 + v("c2") * x
-    if repeat:
-        z = z.repeat(x.shape[0], 1, 1, 1)
-    return x0, mean, torch.where(v("sigma") != 0, mean + z * v("sigma"), mean)
 
 
 def _call(x, net, co, put=lambda t: t.cuda(), **kw):

@@ -160,6 +160,24 @@ def restated_field(smp, stack, solver, batch, id_base=0, C_state=2, reverse=True
     return torch.cat([tiles[i] for i in starts])
 
 
+def numpy_item(ch0, ch1, loc, p, nd, w, from_norm_target):
+    """SplitDataset.__getitem__ (data/split_dataset.py:237-278) restated with numpy for one patch at ``loc`` = (frame, y,
+    x); ``p``: the patch side, or (ph, pw)."""
+    n, y, x = loc
+    ph, pw = (p, p) if np.isscalar(p) else p
+    patch1 = ch0[n, y:y + ph, x:x + pw].astype(np.float32)[None]
+    patch2 = ch1[n, y:y + ph, x:x + pw].astype(np.float32)[None]
+    target = np.concatenate([patch1, patch2], axis=0)
+    target = ((target - nd["mean_target"].reshape(-1, 1, 1)) / nd["std_target"].reshape(-1, 1, 1)).astype(np.float32)
+    if from_norm_target:
+        inp = np.float32(w[0]) * target[0:1] + np.float32(w[1]) * target[1:2]
+    else:
+        inp = np.float32(w[0]) * patch1 + np.float32(w[1]) * patch2
+        assert inp.dtype == np.float32
+        inp = ((inp.astype(np.float64) - np.float64(nd["mean_input"])) / np.float64(nd["std_input"])).astype(np.float32)
+    return {"input": inp, "target": target}
+
+
 def welford(xs):
     """include/dsx.h, dsx_moments_update / dsx_moments_finish restated in float64, one rounded operation at a time"""
     mean, m2 = xs[0].astype(np.float64), np.zeros(xs[0].shape)
