@@ -200,6 +200,7 @@ SIGNATURES = {
     "dsx_comoments": (_i, [_Df, _Df, _Df, _i64, _i64, _pi64, _Dd, _Dd, _st]),
     "dsx_calibration_blocks": (_i, [_i64]),
     "dsx_calibration": (_i, [_Df, _Df, _Df, _i64, _i, _H, _i, _H, _i, _Dd, _Dd, _st]),
+    "dsx_sample_quantiles": (_i, [_Df, _i64, _i, _i64, _H, _i, _Df, _Df, _Df, _st]),
 }
 
 if not os.path.exists(LIB_PATH):
@@ -241,6 +242,23 @@ def plane_view(t, where):
     pixel = dims[-1][1] if dims else 1
     plane = t.stride(0) if t.shape[0] > 1 else (n - 1) * pixel + 1
     return t.data_ptr(), int(t.shape[0]), int(n), int(plane), int(pixel)
+
+
+def stack_view(t, where):
+    """(address, n, count, sample stride) of a CUDA fp32 tensor (n, ...) read IN PLACE as n samples of ``count`` contiguous
+    elements, one every ``stride`` elements (dsx_sample_quantiles): the whole of a contiguous tensor, or a view such as
+    ``buf[:, :b]`` whose first stride exceeds a sample's size.  The address goes into a Dev slot as it is; the call's
+    contiguous tensors name its device."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise DsxError(f"{where} must be a CUDA tensor: the quantiles run on the MI355X only (no CPU fallback)")
+    if t.dtype != torch.float32 or t.dim() < 2 or t.numel() < 1:
+        raise DsxError(f"{where} must be a non-empty float32 tensor (n, ...), got {t.dtype} {tuple(t.shape)}")
+    count = t[0].numel()
+    stride = int(t.stride(0)) if t.shape[0] > 1 else count
+    if not t[0].is_contiguous() or stride < count:
+        raise DsxError(f"{where} must hold contiguous samples, one every stride >= their size: shape {tuple(t.shape)} with "
+                       f"strides {t.stride()}; pass a contiguous copy")
+    return t.data_ptr(), int(t.shape[0]), int(count), stride
 
 
 def common_device(name, devices):

@@ -225,3 +225,85 @@ class Calibration:
                        doc["std_target"])
         except (KeyError, TypeError, ValueError) as e:
             raise DsxError(f"{path}: not a complete calibration file ({type(e).__name__}: {e})")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The rank histogram (Talagrand diagram): a check of the N samples against ground truth that assumes no distribution.
+# If the target is exchangeable with a pixel's N samples, its rank among them -- the number of samples strictly below
+# it, ``predict_stack(..., ranks=True)['rank']`` -- is uniform on 0..N, and the band between the m-th smallest and the
+# m-th largest sample holds the target with probability (N + 1 - 2 m) / (N + 1).
+RANK_FORMAT = "diffsplitting_amd.rank_histogram"
+RANK_VERSION = 1
+
+
+def rank_histogram(rank, n):
+    """The counts of a channel-last rank canvas (..., C) of ``n`` samples -> (C, n + 1) int64 numpy: ``hist[c][k]`` pixels
+    of channel c have rank k.  One ``torch.bincount`` per channel on the integer image, exact; a value that is no
+    integer in 0..n is refused."""
+    n = int(n)
+    if n < 1:
+        raise DsxError(f"rank_histogram: n = {n} samples, must be positive")
+    rank = rank if isinstance(rank, torch.Tensor) else torch.as_tensor(np.asarray(rank))
+    if rank.dim() < 1 or rank.numel() == 0:
+        raise DsxError(f"rank_histogram: a rank canvas (..., C) with pixels, got shape {tuple(rank.shape)}")
+    C = rank.shape[-1]
+    flat = rank.reshape(-1, C)
+    ints = flat.to(torch.int64)
+    if not bool((ints.to(flat.dtype) == flat).all()) or int(ints.min()) < 0 or int(ints.max()) > n:
+        raise DsxError(f"rank_histogram: every rank must be an integer in 0..{n}")
+    return np.stack([torch.bincount(ints[:, c], minlength=n + 1).cpu().numpy().astype(np.int64) for c in range(C)])
+
+
+def interval_coverage(hist):
+    """What a rank histogram (C, n + 1) says about the central bands -> an object of numpy arrays: ``m`` = 1 .. n // 2,
+    ``nominal`` (len(m),) = (n + 1 - 2 m) / (n + 1), ``observed`` (C, len(m)) = hist[c][m : n - m + 1].sum() / pixels:
+    the share of pixels whose target lies between the m-th smallest and the m-th largest sample; ``pixels`` per channel."""
+    hist = np.asarray(hist, dtype=np.int64)
+    if hist.ndim != 2 or hist.shape[1] < 2:
+        raise DsxError(f"interval_coverage: a histogram (C, n + 1), got shape {hist.shape}")
+    n = hist.shape[1] - 1
+    pixels = hist.sum(axis=1)
+    if (pixels < 1).any() or (pixels != pixels[0]).any():
+        raise DsxError(f"interval_coverage: every channel must hold the same positive pixel count, got {pixels.tolist()}")
+    m = np.arange(1, n // 2 + 1, dtype=np.int64)
+    nominal = (n + 1 - 2 * m) / float(n + 1)
+    observed = np.array([[hist[c, k:n - k + 1].sum() / float(pixels[c]) for k in m] for c in range(hist.shape[0])],
+                        dtype=np.float64).reshape(hist.shape[0], m.size)
+    return types.SimpleNamespace(m=m, nominal=nominal, observed=observed, pixels=int(pixels[0]), samples=n)
+
+
+def save_rank_histogram(path, hist):
+    """The histogram and its bands as JSON: {"format", "version", "channels", "samples", "pixels", "hist" (channels rows
+    of samples + 1 counts), "intervals" (one {"m", "nominal", "observed" per channel} per band)}."""
+    hist = np.asarray(hist, dtype=np.int64)
+    cov = interval_coverage(hist)
+    doc = {"format": RANK_FORMAT, "version": RANK_VERSION, "channels": int(hist.shape[0]), "samples": cov.samples,
+           "pixels": cov.pixels, "hist": [[int(v) for v in row] for row in hist],
+           "intervals": [{"m": int(m), "nominal": float(cov.nominal[j]), "observed": _floats(cov.observed[:, j])}
+                         for j, m in enumerate(cov.m)]}
+    with open(path, "w") as f:
+        json.dump(doc, f, indent=1, allow_nan=False)
+        f.write("\n")
+    return doc
+
+
+def load_rank_histogram(path):
+    """-> the (C, n + 1) int64 histogram of a file ``save_rank_histogram`` wrote."""
+    with open(path) as f:
+        try:
+            doc = json.load(f)
+        except ValueError as e:
+            raise DsxError(f"{path}: not a rank histogram file ({e})")
+    if not isinstance(doc, dict) or doc.get("format") != RANK_FORMAT:
+        raise DsxError(f"{path}: format {doc.get('format') if isinstance(doc, dict) else type(doc).__name__!r}, "
+                       f"expected {RANK_FORMAT!r} (written by split --rank-histogram)")
+    if doc.get("version") != RANK_VERSION:
+        raise DsxError(f"{path}: version {doc.get('version')!r} of the rank histogram file, this build reads version "
+                       f"{RANK_VERSION}")
+    try:
+        hist = np.array(doc["hist"], dtype=np.int64).reshape(int(doc["channels"]), int(doc["samples"]) + 1)
+        if int(doc["pixels"]) != int(hist[0].sum()):
+            raise ValueError(f"{doc['pixels']} pixels, the counts sum to {int(hist[0].sum())}")
+    except (KeyError, TypeError, ValueError) as e:
+        raise DsxError(f"{path}: not a complete rank histogram file ({type(e).__name__}: {e})")
+    return hist

@@ -12,11 +12,7 @@ namespace dsx {
 //   finish: mean_out = (float)mean;  std_out = n > 1 ? (float)sqrt(M2 / (n - 1)) : 0
 // Every operation is rounded on its own, so a numpy float64 restatement of these lines gives the same bits.  The
 // __d*_rn forms are plain operators in the toolchain's headers and may be contracted once inlined: the product and the
-// sums go through mul_d / add_d / sub_d, which take the `contract` flag off their own instruction.
-__device__ __forceinline__ double sub_d(double a, double b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
+// sums go through mul_d / add_d / sub_d (dsx_kernels.h), which take the `contract` flag off their own instruction.
 __global__ __launch_bounds__(256) void k_moments_update(const float* __restrict__ x, double* __restrict__ mean,
                                                         double* __restrict__ m2, long long count, int r) {
   const double rn = (double)(r + 1);

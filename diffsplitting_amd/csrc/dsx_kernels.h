@@ -476,6 +476,10 @@ __device__ __forceinline__ double add_d(double a, double b) {
 #pragma clang fp contract(off)
   return a + b;
 }
+__device__ __forceinline__ double sub_d(double a, double b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 
 // ---------------------------------------------------------------------------
 // The skeleton the NCHW pointwise kernels share (dsx_steps.hip, dsx_validate.hip).  A thread owns group i4: the four consecutive elements from 4 * i4 (= one
@@ -817,6 +821,24 @@ inline int calibration_row(int C, int nbins, int nz) { return C * (3 * nbins + n
 int calibration_blocks(long long n);
 long long calibration_span(long long n);
 hipError_t launch_calibration(const CalArgs& a, bool vec, hipStream_t st);
+
+// dsx_quantiles.hip.  Per-element quantiles and ranks across n <= 64 samples (include/dsx.h, dsx_sample_quantiles): one
+// launch on `st`, nothing synchronised.  Sample r, element i at x[r * stride + i]; out [nq][count]; target and rank
+// [count], both or neither.  lo[k], hi[k], t[k]: the two order statistics of quantile k and the weight between them,
+// formed on the host in double.  The network sorts quantiles_wires(n) wires; on the wide path a thread takes
+// quantiles_per_thread(wires) neighbouring elements with one load of that width per sample (every base a multiple of
+// that many elements, stride and count too: the caller's check), else one element with 4-byte loads.
+constexpr int kQuantMaxN = 64, kQuantMaxQ = 8;
+struct QuantArgs {
+  const float* x; long long stride, count;
+  int n, nq;
+  float* out; const float* target; float* rank;
+  int lo[kQuantMaxQ], hi[kQuantMaxQ];
+  double t[kQuantMaxQ];
+};
+constexpr int quantiles_wires(int n) { return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+constexpr int quantiles_per_thread(int wires) { return wires <= 32 ? 4 : 2; }
+hipError_t launch_quantiles(const QuantArgs& a, bool wide, hipStream_t st);
 
 // dsx_select.hip.  One pass of the radix select behind dsx_order_stats: hist[1 << bits] (64-bit, zeroed by the caller)
 // += the digit (u >> shift) & (2^bits - 1) of every element whose key image u has u >> match_shift == prefix

@@ -6,21 +6,35 @@ import torch
 
 from .. import parallel
 from .._lib import DsxError
-from .tile_predict import (_batches, _check_field_ids, _check_samples, _check_stitch, _is_gaussian, _mean_and_spread,
+from .tile_predict import (_batches, _check_field_ids, _check_quantile_bytes, _check_quantiles, _check_rank_gt,
+                           _check_samples, _check_stitch, _is_gaussian, _mean_and_spread, _mean_spread_quantiles,
                            _scorable_gt, store_kept)
 
 
-def _frame_outputs(netG, dataset, samples, return_std, draw):
+def _frame_outputs(netG, dataset, samples, return_std, draw, q=None, ranks=False):
     """What both frame-state drivers return: the frame states ``draw(r)`` (N,H,W,C) of the posterior samples are the stitched
-    frames -- 'mean', with ``return_std`` 'std', and 'psnr' from a paste of the mean's own tiles against the ground truth."""
+    frames -- 'mean', with ``return_std`` 'std', and 'psnr' from a paste of the mean's own tiles against the ground truth.
+    ``q`` / ``ranks`` (checked by the caller): the states are kept, 'quantiles' (Q,N,H,W,C) and 'rank' (N,H,W,C) are
+    taken over them per pixel."""
     plan, C_out = dataset.plan, netG.prediction_channels
-    X, spread = _mean_and_spread(samples, return_std, draw)
-    out = {"mean": X}
     gt = _scorable_gt(dataset, C_out)
+    quant = rank = None
+    if q is not None or ranks:
+        _check_rank_gt("predict_stack" if _is_gaussian(netG) else "predict_stack_frames", ranks, gt)
+        states = torch.empty((samples,) + tuple(plan.data_shape) + (C_out,), dtype=torch.float32, device=dataset.device)
+        X, spread, quant, rank = _mean_spread_quantiles(samples, return_std, draw, states, q,
+                                                        gt.contiguous() if ranks else None)
+    else:
+        X, spread = _mean_and_spread(samples, return_std, draw)
+    out = {"mean": X}
     if gt is not None and X.shape[-1] == C_out:
         out["psnr"] = plan.stitch_with_psnr(plan.gather_canvas(X), gt)[1]
     if return_std:
         out["std"] = spread
+    if quant is not None:
+        out["quantiles"] = quant
+    if rank is not None:
+        out["rank"] = rank
     return out
 
 
@@ -68,13 +82,13 @@ def fused_sample(netG, dataset, table, batch_tiles, seed, id_base, order=None, k
     return X
 
 
-def _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window):
+def _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q=None, ranks=False):
     """``predict_stack(fuse=True)`` after its checks: the frame states of the posterior samples (``fused_sample``),
     sample ``r`` with the field ids ``r * frames + n``."""
     dataset.plan.set_window(window)
     frames, table = dataset.plan.data_shape[0], netG.solver_table(**solver)
     return _frame_outputs(netG, dataset, samples, return_std,
-                          lambda r: fused_sample(netG, dataset, table, batch_tiles, seed, r * frames))
+                          lambda r: fused_sample(netG, dataset, table, batch_tiles, seed, r * frames), q, ranks)
 
 
 # ---- frame diffusion for the InDI family ----------------------------------------------------------------------------
@@ -140,7 +154,8 @@ def frame_sample(child, dataset, x_in, num_timesteps, t_float_start, batch_tiles
 
 @torch.no_grad()
 def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_float_start=None, samples=1,
-                         return_std=False, seed=None, group=None, window="triangle"):
+                         return_std=False, seed=None, group=None, window="triangle", quantiles=None, ranks=False,
+                         quantile_bytes=8 << 30):
     """``predict_stack`` for the InDI family (``InDISampler`` and its subclasses, ``JointIndiSampler``) with every frame
     diffused as ONE state: frame diffusion.  The InDI update ``x <- (d/t) x0 + (1 - d/t) x + e (t - d) z`` is affine in
     the UNet output with coefficients shared by the batch, so a row of a frame is ``X <- c_x0 * blend(x0 tiles) +
@@ -153,7 +168,11 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
     and their states are joined along the channels.  ``t_float_start``: one start time for every frame (default: 1.0,
     0.5 for a joint sampler, whose second child starts at ``1 - t``).  Tiles are sharded over the ranks: one collective
     per row and child, every rank holds the same state.  ``samples > 1``: mean and spread over the frame states
-    (``engine.moments_update``).  With one tile per frame this is ``predict_stack(seed=, noise="field")`` bit for bit."""
+    (``engine.moments_update``).  With one tile per frame this is ``predict_stack(seed=, noise="field")`` bit for bit.
+
+    ``quantiles=`` / ``ranks=True`` (``samples`` in 2..64): ``out['quantiles']`` (Q,N,H,W,C) and ``out['rank']`` (N,H,W,C)
+    as ``predict_stack`` describes them; a draw is the whole frame state here, so both are exact per pixel.  The
+    ``samples`` states are kept: more than ``quantile_bytes`` of them is refused before any launch."""
     from ..model.samplers import InDISampler, JointIndiSampler
     what = "predict_stack_frames"
     if _is_gaussian(netG):
@@ -174,6 +193,9 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
     plan, N = dataset.plan, dataset.plan.data_shape[0]
     _check_field_ids(what, samples, N)
     _check_stitch(what, "blend", window)
+    q, ranks = _check_quantiles(what, samples, quantiles, ranks, dataset)
+    if q is not None or ranks:
+        _check_quantile_bytes(what, samples, plan, netG.prediction_channels, quantile_bytes)
     plan.set_window(window)
     x_in = input_frames(dataset, batch_tiles)
 
@@ -181,4 +203,4 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
         parts = [frame_sample(child, dataset, x_in, int(child.num_timesteps if num_timesteps is None else num_timesteps),
                               t0, batch_tiles, seed, r * N + bit, group) for child, t0, bit in children]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
-    return _frame_outputs(netG, dataset, samples, return_std, draw), plan
+    return _frame_outputs(netG, dataset, samples, return_std, draw, q, ranks), plan

@@ -135,6 +135,67 @@ def _mean_and_spread(samples, return_std, draw):
     return x, (torch.zeros_like(x) if return_std else None)
 
 
+MAX_QUANTILE_SAMPLES, MAX_QUANTILES = 64, 8                           # dsx_sample_quantiles: n <= 64, nq <= 8
+
+
+def _check_quantiles(what, samples, quantiles, ranks, dataset, blend=False):
+    """The refusals of ``quantiles=`` / ``ranks=`` that need no launch -> (q as a tuple of floats or None, ranks).
+    ``blend``: the maps would be blended tile maps.  A dataset without target frames is refused here; one whose
+    target has other channels by ``_check_rank_gt``, once the frames are at hand."""
+    q = None
+    if quantiles is not None:
+        try:
+            q = tuple(float(v) for v in (quantiles if hasattr(quantiles, "__iter__") else (quantiles,)))
+        except (TypeError, ValueError):
+            raise DsxError(f"{what}: quantiles = {quantiles!r}: 1 to {MAX_QUANTILES} numbers in [0, 1]")
+        if not 1 <= len(q) <= MAX_QUANTILES or any(not 0.0 <= v <= 1.0 for v in q):   # a NaN fails both comparisons
+            raise DsxError(f"{what}: quantiles = {quantiles!r}: 1 to {MAX_QUANTILES} numbers in [0, 1]")
+    ranks = bool(ranks)
+    if q is None and not ranks:
+        return None, False
+    if samples < 2:
+        raise DsxError(f"{what}: quantiles= and ranks= are taken over the posterior samples: samples = {samples}, give 2 "
+                       "or more")
+    if samples > MAX_QUANTILE_SAMPLES:
+        raise DsxError(f"{what}: quantiles= and ranks= sort the samples in registers: samples = {samples}, at most "
+                       f"{MAX_QUANTILE_SAMPLES}")
+    if ranks and blend:
+        raise DsxError(f"{what}: ranks=True with stitch='blend': a blend of per-tile ranks is not a rank; use stitch='crop' "
+                       "or a frame-state path (fuse=True, predict_stack_frames), where ranks are exact per pixel")
+    if ranks and not hasattr(dataset, "normalized_target_frames"):
+        _check_rank_gt(what, ranks, None)
+    return q, ranks
+
+
+def _check_rank_gt(what, ranks, gt):
+    if ranks and gt is None:
+        raise DsxError(f"{what}: ranks=True: the dataset holds no ground truth with the prediction's channels to rank "
+                       "among the samples")
+
+
+def _check_quantile_bytes(what, samples, plan, channels, quantile_bytes):
+    N, H, W = plan.data_shape
+    need = samples * N * H * W * channels * 4
+    if need > quantile_bytes:
+        raise DsxError(f"{what}: quantiles= / ranks= keep the {samples} frame states of {N} x {H} x {W} x {channels}: {need} "
+                       f"bytes, quantile_bytes = {quantile_bytes}; draw fewer samples, split fewer frames per call or raise "
+                       "quantile_bytes")
+
+
+def _mean_spread_quantiles(samples, return_std, draw, buf, q, target):
+    """``_mean_and_spread`` for ``samples >= 2`` that also keeps the draws: ``draw(r)`` is copied into ``buf[r]`` (the
+    samplers reuse their output buffer), feeds the Welford launch from there, and one ``engine.sample_quantiles`` launch
+    reads the whole of ``buf`` -> (mean, spread or None, quantiles (len(q), ...) or None, rank (...) or None)."""
+    from .. import engine
+    mean = m2 = None
+    for r in range(samples):
+        buf[r].copy_(draw(r))
+        mean, m2 = engine.moments_update(buf[r], mean, m2, r)
+    mean, spread = engine.moments_finish(mean, m2, samples, want_std=return_std)
+    quant, rank = engine.sample_quantiles(buf, q, target)
+    return mean, spread, quant, rank
+
+
 @torch.no_grad()
 def predict_tiled(netG, frames_input, patch_size, grid_size=None, batch_tiles=8, sampler_kwargs=None,
                   group=None, lpips=None, target_frames=None, seed=None, stitch="crop", window="triangle"):
@@ -208,7 +269,8 @@ def _stochastic_rows(netG, num_timesteps, solver):
 
 @torch.no_grad()
 def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None,
-                  solver=None, noise="samples", field_noise_bytes=2 << 30, stitch=None, window="triangle", fuse=False):
+                  solver=None, noise="samples", field_noise_bytes=2 << 30, stitch=None, window="triangle", fuse=False,
+                  quantiles=None, ranks=False, quantile_bytes=8 << 30):
     """The tiled prediction of a dataset that cuts its own normalised tiles -- an ``InputStackTiledPred`` (one
     superimposed acquisition, no ground truth) or a ``SplitDatasetTiledPred`` -- with ``samples`` posterior samples per
     tile: their mean and, with ``return_std``, the unbiased per-pixel spread, accumulated by one fused launch per sample
@@ -241,7 +303,18 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     through one UNet forward and one ``engine.solver_step`` per batch -- with the crops of the field's draw ``s + 1``
     where the row adds noise and the tiles of the blended x0 of the row before where it has a history term --, and are
     blended back into the state.  The state after the last row is the sample; with one tile per frame this is the
-    unfused chain bit for bit."""
+    unfused chain bit for bit.
+
+    ``quantiles=(q1, ..)`` (1 to 8 values in [0, 1]) and ``ranks=True`` (both need ``samples`` in 2..64) add
+    ``out['quantiles']`` (Q,N,H,W,C), the per-pixel quantiles of the samples (``np.quantile`` in float64, linear, bit for
+    bit), and ``out['rank']`` (N,H,W,C), the number of samples strictly below the normalised ground truth (0..samples,
+    as float32; ``core.calibration.rank_histogram`` counts them).  The draws of a batch are then kept in one
+    (samples, B, C, p, p) buffer and one ``engine.sample_quantiles`` launch per batch sorts them per element; every map
+    is stitched like 'std', through an exchange of its own.  With ``stitch="blend"`` a quantile map is a BLEND OF THE
+    PER-TILE QUANTILES -- not the quantile of blended samples --, and ``ranks=True`` is refused: a blend of ranks is not a
+    rank.  With ``fuse=True`` a draw is the whole frame state, quantiles and ranks are exact per pixel, and the
+    ``samples`` states are kept: more than ``quantile_bytes`` of them is refused.  ``ranks=True`` needs a dataset whose
+    ground truth has the prediction's channels.  Without either argument nothing changes."""
     samples = _check_samples("predict_stack", samples, ValueError)
     plan = dataset.plan
     _check_solver("predict_stack", netG, solver)
@@ -266,10 +339,13 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     stitch = "crop" if stitch is None else stitch
     _check_stitch("predict_stack", stitch, window)
     blend, field = stitch == "blend", noise == "field"
+    q, ranks = _check_quantiles("predict_stack", samples, quantiles, ranks, dataset, blend=blend and not fuse)
     if fuse:
         from .frame_predict import _predict_stack_fused
         _check_field_ids("predict_stack", samples, plan.data_shape[0])
-        return _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window), plan
+        if q is not None or ranks:
+            _check_quantile_bytes("predict_stack", samples, plan, netG.prediction_channels, quantile_bytes)
+        return _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q, ranks), plan
     if field:
         if seed is None:
             raise DsxError("predict_stack: noise='field' needs seed=: a noise field is named by (seed, frame, draw)")
@@ -283,11 +359,18 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
         _check_field_ids("predict_stack", samples, plan.data_shape[0], getattr(netG, "STREAM2_BIT", 1 << 39))
     C_out = netG.prediction_channels
     gt = _scorable_gt(dataset, C_out)
+    _check_rank_gt("predict_stack", ranks, gt)
     ids = parallel.shard_ids(plan.total, parallel.rank(), parallel.world_size())
     # a rank without tiles still joins the collectives, on the device it is bound to
     dev = dataset.device if len(ids) else torch.device("cuda", torch.cuda.current_device())
     ex = TileExchange(plan, C_out, dev, group, gt=gt, blend=blend, window=window)
     ex_std = TileExchange(plan, C_out, dev, group, blend=blend, window=window) if return_std else None
+    ex_q = [TileExchange(plan, C_out, dev, group, blend=blend, window=window) for _ in q or ()]
+    ex_rank = TileExchange(plan, C_out, dev, group) if ranks else None
+    draws = None                                                      # (samples, B, C, p, p): the draws of one batch
+    if (q is not None or ranks) and len(ids):
+        draws = torch.empty((samples, min(int(batch_tiles), len(ids)), C_out) + tuple(plan.patch_shape[1:]),
+                            dtype=torch.float32, device=dev)
     kept_field = getattr(netG, "noise_field", None)
     try:
         for i in range(0, len(ids), batch_tiles):
@@ -304,7 +387,16 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
                 elif seed is not None:
                     kw = dict(seed=seed, sample_ids=[k + r * plan.total for k in chunk])
                 return sample_tiles(netG, x, num_timesteps, solver, **kw)
-            tiles, spread = _mean_and_spread(samples, return_std, sample)
+            if draws is None:
+                tiles, spread = _mean_and_spread(samples, return_std, sample)
+            else:
+                tiles, spread, quant, rank = _mean_spread_quantiles(
+                    samples, return_std, sample, draws[:, :len(chunk)], q,
+                    plan.gather_canvas(gt, chunk) if ranks else None)
+                for k, e in enumerate(ex_q):
+                    e.add(quant[k], chunk)
+                if ranks:
+                    ex_rank.add(rank, chunk)
             ex.add(tiles, chunk)
             if return_std:
                 ex_std.add(spread, chunk)
@@ -318,4 +410,8 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     out = {"mean": res[0], "psnr": res[1]} if gt is not None else {"mean": res}
     if return_std:
         out["std"] = ex_std.finish()
+    if q is not None:
+        out["quantiles"] = torch.stack([e.finish() for e in ex_q])
+    if ranks:
+        out["rank"] = ex_rank.finish()
     return out, plan

@@ -824,3 +824,30 @@ def moments_finish(mean, m2, n, want_std=True):
     std_out = torch.empty(mean.shape, dtype=torch.float32, device=mean.device) if want_std else None
     check(lib.dsx_moments_finish(mean, m2, mean.numel(), int(n), mean_out, std_out, None))
     return mean_out, std_out
+
+
+# ---------------------------------------------------------------------------
+# quantiles and ranks across a stack of samples (dsx_sample_quantiles, include/dsx.h)
+# ---------------------------------------------------------------------------
+def sample_quantiles(stack, q, target=None):
+    """``dsx_sample_quantiles``: ``stack`` is (n, ...) float32 on the device, n = 1..64 samples of one shape, each
+    contiguous (the whole tensor, or a view such as ``buf[:, :b]`` whose first stride exceeds a sample's size); ``q``: 0
+    to 8 values in [0, 1]; ``target`` (...): a contiguous float32 CUDA tensor of a sample's shape, or None.  Returns
+    ``(quantiles (len(q), ...) or None without q, rank (...) or None without target)``: per element
+    ``np.quantile(stack.astype(float64), q, axis=0).astype(float32)`` bit for bit, and the number of samples strictly
+    below the target as float32.  One launch; the stack is read in place."""
+    address, n, count, stride = _lib.stack_view(stack, "stack")
+    shape = tuple(stack.shape[1:])
+    qs = np.ascontiguousarray(np.atleast_1d(np.asarray(() if q is None else q, dtype=np.float64)))
+    if qs.ndim != 1:
+        raise DsxError(f"q must be a sequence of quantiles, got shape {qs.shape}")
+    if target is not None:
+        target = _f32_cuda(target, "target", shape)
+        _lib.common_device("sample_quantiles", [stack.device, target.device])
+    if not len(qs) and target is None:
+        raise DsxError("sample_quantiles: nq = 0 and no rank output: give q, a target or both")
+    out = torch.empty((len(qs),) + shape, dtype=torch.float32, device=stack.device) if len(qs) else None
+    rank = torch.empty(shape, dtype=torch.float32, device=stack.device) if target is not None else None
+    # the stack goes in by address (it may be a view); out or rank names the device and the stream of the call
+    check(lib.dsx_sample_quantiles(address, stride, n, count, qs if len(qs) else None, len(qs), out, target, rank, None))
+    return out, rank

@@ -67,6 +67,13 @@ tracks the real error (``core/calibration.py``): rank 0 bins the pixels of the s
 per channel the scale, the line ``rmse ~ a rmv + c`` and the coverage at z = 1, 2, 3, and writes curve and fit to FILE.
 ``--apply-calibration FILE`` (with ``--std-out``) writes ``a std + c`` (clamped at 0) instead of the raw spread, for a
 stack without ground truth (``--input``); the file must hold the prediction's channel count and ``--samples``.
+
+``--quantiles Q1,Q2,.. --quantile-out FILE`` (with ``--samples N``, 2 <= N <= 64) writes the per-pixel quantiles of the N
+posterior samples (``predict_stack(quantiles=)``: the median, a credible band) in raw counts, (Q,N,H,W,C) as .npy or
+Q * N * C pages as .tif; with ``--stitch blend`` outside the frame-state paths a map is a blend of per-tile quantiles.
+``--rank-histogram FILE.json`` (with a ground truth) counts per channel the rank of the ground truth among the samples of
+every pixel (``core.calibration.rank_histogram``): uniform counts mean calibrated bands, whatever the posterior's shape;
+rank 0 logs the observed against the nominal coverage of the widest central band and of the one nearest 50 %.
 """
 import argparse
 import functools
@@ -284,10 +291,20 @@ def main(argv=None):
     ap.add_argument("--calibration-bins", type=int, default=None, help="with --calibration: equal-count bins (default 30)")
     ap.add_argument("--apply-calibration", type=str, default=None,
                     help="with --std-out: write the spread recalibrated by this file (a std + c per channel)")
+    ap.add_argument("--quantiles", type=str, default=None,
+                    help="with --samples N >= 2 and --quantile-out: 1 to 8 quantiles in [0, 1] of the posterior samples per "
+                         "pixel, comma-separated (0.05,0.5,0.95)")
+    ap.add_argument("--quantile-out", type=str, default=None,
+                    help="with --quantiles: write the quantile maps in raw counts, (Q,N,H,W,C) .npy or a .tif of "
+                         "Q * N * C pages (quantile-major)")
+    ap.add_argument("--rank-histogram", type=str, default=None,
+                    help="with --samples N >= 2 and ground truth: count the rank of the ground truth among the samples per "
+                         "pixel (core.calibration.rank_histogram) and write histogram and band coverage to this .json file")
     args = ap.parse_args(argv)
     config = _config_once(args.config)
     _check_msssim_args(args, config)
     _check_calibration_args(args, config)
+    _check_quantile_args(args, config)
     _check_solver_args(args, config)
     _check_stitch_args(args, len(str(args.gpu_ids).split(",")) if args.gpus is None else args.gpus)
     _check_frame_args(args, config)
@@ -427,12 +444,12 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
         from .data.tiled_predict import predict_stack_frames
         out, plan = predict_stack_frames(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps,
                                          samples=samples, return_std=bool(args.std_out or args.calibration),
-                                         seed=args.sample_seed, window=args.window or "triangle")
+                                         seed=args.sample_seed, window=args.window or "triangle", **_quantile_kwargs(args))
     else:
         out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
                                   return_std=bool(args.std_out or args.calibration), seed=args.sample_seed, solver=solver,
                                   noise="field" if args.noise_field else "samples", stitch=args.stitch,
-                                  window=args.window or "triangle", fuse=args.fuse_steps)
+                                  window=args.window or "triangle", fuse=args.fuse_steps, **_quantile_kwargs(args))
     pred, ps = out["mean"], out.get("psnr")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -459,6 +476,10 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
                 log.info("spread recalibrated by %s", args.apply_calibration)
             _write_prediction(args.std_out, spread, val_set, spread=True)
             log.info("spread over %d samples written to %s", samples, args.std_out)
+        if args.quantile_out:
+            _write_quantiles(args.quantile_out, out["quantiles"], _parse_quantiles(args.quantiles), val_set)
+            log.info("quantiles %s over %d samples written to %s", args.quantiles, samples, args.quantile_out)
+        _log_rank_histogram(args, out.get("rank"), samples, log)
     return pred
 
 
@@ -559,6 +580,96 @@ def _log_calibration(args, val_set, pred, std, ps, samples, log):
                  stats.n)
     cal.save(args.calibration)
     log.info("calibration over %d samples written to %s", samples, args.calibration)
+
+
+def _parse_quantiles(text):
+    """``--quantiles``: 1 to 8 comma-separated numbers in [0, 1] -> a tuple of floats (SystemExit otherwise)."""
+    try:
+        q = tuple(float(v) for v in str(text).split(","))
+    except ValueError:
+        q = ()
+    if not 1 <= len(q) <= 8 or any(not 0.0 <= v <= 1.0 for v in q):
+        raise SystemExit(f"--quantiles {text}: 1 to 8 comma-separated numbers in [0, 1], such as 0.05,0.5,0.95")
+    return q
+
+
+def _quantile_kwargs(args):
+    """What ``--quantiles`` / ``--rank-histogram`` add to the driver's call: nothing without them."""
+    kw = {}
+    if args.quantiles:
+        kw["quantiles"] = _parse_quantiles(args.quantiles)
+    if args.rank_histogram:
+        kw["ranks"] = True
+    return kw
+
+
+def _check_quantile_args(args, config):
+    """``--quantiles`` / ``--quantile-out`` / ``--rank-histogram``, checked on the command line and the config alone
+    (nothing touches the GPU, no rank is started).  Without them: nothing."""
+    if bool(args.quantiles) != bool(args.quantile_out):
+        if args.quantiles:
+            raise SystemExit("--quantiles: give --quantile-out FILE (.npy / .tif) for the maps")
+        raise SystemExit("--quantile-out: give --quantiles Q1,Q2,.. to say which maps to write")
+    for flag, value, exts in (("--quantile-out", args.quantile_out, (".npy", ".tif", ".tiff")),
+                              ("--rank-histogram", args.rank_histogram, (".json",))):
+        if not value:
+            continue
+        if not value.endswith(exts):
+            raise SystemExit(f"{flag} {value}: a {' or '.join(exts[:2])} file")
+        if args.validate:
+            raise SystemExit(f"{flag} is taken over the posterior samples of a tiled prediction: not with --validate")
+        if args.mix_t is not None:
+            raise SystemExit(f"{flag}: not with --mix-t; the mixed-input prediction has no posterior samples")
+        if (args.samples or 1) < 2:
+            raise SystemExit(f"{flag}: quantiles and ranks are taken over --samples 2 or more (--samples 1 has none)")
+        if args.samples > 64:
+            raise SystemExit(f"{flag}: the samples of a pixel are sorted in registers: --samples {args.samples}, at most 64")
+        if args.datapath and _data_type(config()[1], args.norm_from) == "cifar10":
+            raise SystemExit(f"{flag} is taken over the stitched frames of a tiled prediction: the colour items of a "
+                             "cifar10 config are not tiled")
+    if args.quantiles:
+        _parse_quantiles(args.quantiles)
+    if args.rank_histogram:
+        if args.input:
+            raise SystemExit("--rank-histogram with --input: an input-only stack has no ground truth to rank among the "
+                             "samples")
+        if args.stitch == "blend" and not (args.fuse_steps or args.frame_steps):
+            raise SystemExit("--rank-histogram with --stitch blend: a blend of per-tile ranks is not a rank; use --stitch "
+                             "crop, or a frame-state path (--fuse-steps, --frame-steps) where ranks are exact per pixel")
+
+
+def _write_quantiles(path, quant, q, val_set):
+    """--quantile-out: the quantile maps (Q,N,H,W,C), un-normalised to raw counts like --out (q * std_target +
+    mean_target), as .npy (Q,N,H,W,C) float32 or as a .tif of Q * N * C float32 pages, quantile-major (page
+    (k * N + n) * C + c), the description naming the quantiles and the order."""
+    Q, N, H, W, C_out = quant.shape
+    mean, std = _target_stats(val_set, C_out)
+    raw = (quant * torch.as_tensor(std, dtype=torch.float32, device=quant.device)
+           + torch.as_tensor(mean, dtype=torch.float32, device=quant.device)).cpu().numpy()
+    if str(path).endswith(".npy"):
+        np.save(path, raw)
+        return
+    from .data.tiff import imwrite
+    desc = (f"ImageJ=1.11a\nimages={Q * N * C_out}\nchannels={C_out}\nslices={N}\nframes={Q}\nhyperstack=true\n"
+            f"mode=grayscale\norder=quantile,frame,channel\nquantiles={','.join(repr(v) for v in q)}\n")
+    imwrite(path, np.ascontiguousarray(raw.transpose(0, 1, 4, 2, 3)).reshape(Q * N * C_out, H, W), description=desc)
+
+
+def _log_rank_histogram(args, rank, samples, log):
+    """``--rank-histogram`` on rank 0: the counts of the rank canvas per channel, the coverage of the widest central band
+    and of the one nearest 50 % against their nominal values, histogram and bands to the file."""
+    if not args.rank_histogram:
+        return
+    from .core.calibration import interval_coverage, rank_histogram, save_rank_histogram
+    hist = rank_histogram(rank, samples)
+    cov = interval_coverage(hist)
+    half = int(np.argmin(np.abs(cov.nominal - 0.5)))
+    for c in range(hist.shape[0]):
+        log.info("channel %d: ground truth between the extreme samples in %.4f of the pixels (nominal %.4f); between the "
+                 "%d-th smallest and largest in %.4f (nominal %.4f); %d samples, %d pixels", c, cov.observed[c, 0],
+                 cov.nominal[0], int(cov.m[half]), cov.observed[c, half], cov.nominal[half], samples, cov.pixels)
+    save_rank_histogram(args.rank_histogram, hist)
+    log.info("rank histogram over %d samples written to %s", samples, args.rank_histogram)
 
 
 def _check_input_args(args, config):

@@ -954,6 +954,34 @@ int dsx_calibration(const float* mean_dev, const float* std_dev, const float* ta
                     const double* edges_host, int nbins, const double* z_host, int nz, double* partial_dev, double* out_dev,
                     void* stream);
 
+/* ------------------------------------------------- quantiles and ranks across a stack of posterior samples
+ * The per-element order statistics of n samples, for maps of the median and of credible bands, and the rank of a
+ * target among the samples, for the rank histogram (core/calibration.py) that checks such a band without assuming a
+ * distribution.  x_dev holds n samples of `count` fp32 values: sample r, element i at x_dev[r * sample_stride + i],
+ * sample_stride >= count.  out_dev is [nq][count]; target_dev and rank_dev are [count], both NULL or both given;
+ * out_dev (and q_host) may be NULL with nq == 0 when only ranks are wanted.  Per element i:
+ *   v[0 .. n-1] = the element's n samples in ascending order of the order-preserving integer image of the fp32 value:
+ *                 -0 comes before +0, equal values are indistinguishable
+ * on the host, in double, for every k < nq (the four travel in the kernel-argument struct, hence nq <= 8):
+ *   pos = (n - 1) q[k];   lo = floor(pos);   hi = min(lo + 1, n - 1);   t = pos - lo
+ * on the device, in double, every operation rounded on its own (no fma):
+ *   a = v[lo];   b = v[hi];   d = b - a
+ *   r = t < 0.5 ? a + d t : b - d (1 - t)
+ *   out[k][i] = (float)r
+ * which is np.quantile(x.astype(np.float64), q, axis=0).astype(np.float32) bit for bit (tests/quantile_ref.py), the
+ * expression dsx_order_stats' callers use on the host.
+ *   rank[i] = (float)#{ r : x_r[i] < target[i] }      strict, on the fp32 values: an exact integer in 0..n
+ * Inputs are assumed finite.  The samples are sorted in registers by a fully unrolled compare-exchange network over
+ * n padded to 2, 4, .. 64 wires (csrc/dsx_quantiles.hip), hence n <= 64.  A call's bits do not depend on the load path
+ * (loads of 16 bytes, 8 at n > 32, when every base, sample_stride and count are multiples of that; 4-byte loads
+ * otherwise), on alignment or on sample_stride.  One launch on `stream`; the call does not synchronise, allocate or copy
+ * beyond the argument struct.
+ * DSX_ERR_INVALID with a message, before any device work: a NULL x_dev, n outside 1..64, nq outside 0..8, nq == 0
+ * without a rank output, nq > 0 without q_host and out_dev, count < 1, sample_stride < count, a q that is not finite
+ * or lies outside [0, 1], only one of target_dev / rank_dev, out_dev or rank_dev overlapping the samples' range. */
+int dsx_sample_quantiles(const float* x_dev, int64_t sample_stride, int n, int64_t count, const double* q_host, int nq,
+                         float* out_dev, const float* target_dev, float* rank_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
