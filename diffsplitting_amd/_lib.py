@@ -49,6 +49,12 @@ class LayerInfo(C.Structure):
         [(n, C.c_uint64) for n in ("src0", "src1", "gn_scale", "gn_shift", "film", "resid", "out")]
 
 
+class LpipsLayerTable(C.Structure):
+    _fields_ = [("pairs", C.c_int32), ("nimg", C.c_int32), ("H", C.c_int32 * 8), ("W", C.c_int32 * 8),
+                ("C", C.c_int32 * 8), ("nblk", C.c_int32 * 5), ("hw", C.c_int32 * 5), ("stage", C.c_uint64 * 8),
+                ("part", C.c_uint64 * 5)]
+
+
 FLAVOUR_SR3, FLAVOUR_DDPM = 0, 1
 LAYER_CONV, LAYER_ATTN, LAYER_FILM, LAYER_INPUT = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
@@ -160,6 +166,8 @@ SIGNATURES = {
     "dsx_lpips_destroy": (None, [_hn]),
     "dsx_lpips_forward": (_i, [_hn, _Df, _Df, _i, _i, _i, _Df, _Df, _st]),
     "dsx_lpips_frames": (_i, [_hn, _Df, _Df, _i, _i, _i, _i, _i, _i, _Df, _st]),
+    "dsx_lpips_layers": (_i, [_hn, C.POINTER(LpipsLayerTable)]),
+    "dsx_lpips_copy_workspace": (_i, [_hn, _u64, C.c_size_t, _Dv, _st]),
     "dsx_resize_coeffs": (_i, [_i, _i, _i, _pi32, _pi32, _pi32, _i]),
     "dsx_resize_plan_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "dsx_resize_plan_destroy": (None, [_hn]),

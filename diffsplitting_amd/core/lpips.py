@@ -97,6 +97,26 @@ def _alias_names():
     return names
 
 
+STAGES = ("x0", "f1", "p1", "f2", "p2", "f3", "f4", "f5")
+# the launch that writes each stage (dsx_lpips.hip)
+STAGE_LAUNCH = {"x0": "k_lpips_input_nchw", "f1": "k_lpips_conv1", "p1": "k_lpips_pool", "f2": "k_lpips_conv<5>",
+                "p2": "k_lpips_pool", "f3": "k_lpips_conv<3>", "f4": "k_lpips_conv<3>", "f5": "k_lpips_conv<3>"}
+TAP_STAGES = ("f1", "f2", "f3", "f4", "f5")
+
+
+def geometry(H, W):
+    """Stage name -> (H, W, C) of every stage of the trunk for an H x W input (dsx_lpips.cpp's geometry())."""
+    if H < 31 or W < 31:
+        raise DsxError(f"LPIPS(alex) needs H, W >= 31: below that the second max-pool has no output (got {H} x {W})")
+    conv1 = lambda n: (n + 4 - 11) // 4 + 1
+    pool = lambda n: (n - 3) // 2 + 1
+    h1, w1 = conv1(H), conv1(W)
+    h2, w2 = pool(h1), pool(w1)
+    h3, w3 = pool(h2), pool(w2)
+    return {"x0": (H, W, 3), "f1": (h1, w1, 64), "p1": (h2, w2, 64), "f2": (h2, w2, 192), "p2": (h3, w3, 192),
+            "f3": (h3, w3, 384), "f4": (h3, w3, 256), "f5": (h3, w3, 256)}
+
+
 class LPIPS(torch.nn.Module):
     """``lpips.LPIPS(net='alex', version='0.1', spatial=False)`` with caller-supplied weights.
 
@@ -155,10 +175,37 @@ class LPIPS(torch.nn.Module):
         out = torch.empty((B,), dtype=torch.float32, device=dev)
         taps = torch.empty((B, 5), dtype=torch.float32, device=dev) if retPerLayer else None
         check(lib.dsx_lpips_forward(self._h, a, b, B, H, W, out, taps, None))
+        self._table_dev = dev
         val = out.view(B, 1, 1, 1)
         if retPerLayer:
             return val, [taps[:, k].reshape(B, 1, 1, 1) for k in range(5)]
         return val
+
+    @torch.no_grad()
+    def layer_table(self, stages=None):
+        """Every stage of the last ``forward`` copied out of the workspace (dsx_lpips_layers), for per-launch checks:
+        ``{"pairs": B, "stages": {name: dict(out=(2B, H, W, C) fp32 NHWC device tensor, launch=<kernel that wrote
+        it>)}, "taps": [dict(stage, launch, part=(B, nblk) float64 partial rows, nblk, hw) x 5]}``.  Images b < B are
+        in0's, B + b in1's.  ``stages``: the names to copy (default all of STAGES); the taps are always copied.
+        Raises DsxError before any forward and after ``frames``, which reuses the workspace per chunk."""
+        info = _lib.LpipsLayerTable()
+        check(lib.dsx_lpips_layers(self._h, C.byref(info)))
+        dev = self._table_dev                                          # the device of that forward
+        B, nimg = int(info.pairs), int(info.nimg)
+        out = {"pairs": B, "stages": {}, "taps": []}
+        for s, name in enumerate(STAGES):
+            if stages is not None and name not in stages:
+                continue
+            t = torch.empty((nimg, info.H[s], info.W[s], info.C[s]), dtype=torch.float32, device=dev)
+            check(lib.dsx_lpips_copy_workspace(self._h, info.stage[s], t.numel() * 4, t, None))
+            out["stages"][name] = dict(out=t, launch=STAGE_LAUNCH[name])
+        for k, name in enumerate(TAP_STAGES):
+            p = torch.empty((B, info.nblk[k]), dtype=torch.float64, device=dev)
+            check(lib.dsx_lpips_copy_workspace(self._h, info.part[k], p.numel() * 8, p, None))
+            out["taps"].append(dict(stage=name, launch=f"k_lpips_dist<{LIN_CHANNELS[k] // 64}>", part=p,
+                                    nblk=int(info.nblk[k]), hw=int(info.hw[k])))
+        torch.cuda.current_stream(dev).synchronize()
+        return out
 
     @torch.no_grad()
     def frames(self, target, pred, channel, chunk=0):

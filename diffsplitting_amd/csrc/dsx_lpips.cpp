@@ -28,6 +28,9 @@ struct dsx_lpips {
   DevBuf dev;                      // the same on the device (uploaded at first use)
   DevBuf ws;                       // one workspace per (pairs, H, W)
   int ws_pairs = 0, ws_H = 0, ws_W = 0;
+  size_t ws_bytes = 0;
+  Geo geo{};                       // of the workspace
+  int table_pairs = 0;             // > 0: the workspace holds every stage of one dsx_lpips_forward of that many pairs
   // bump-allocated views into ws
   float *x0 = nullptr, *f1 = nullptr, *p1 = nullptr, *f2 = nullptr, *p2 = nullptr, *f3 = nullptr, *f4 = nullptr, *f5 = nullptr;
   float *mm = nullptr, *mm_part = nullptr;
@@ -96,6 +99,8 @@ int ensure_workspace(dsx_lpips* h, const Geo& g, int pairs) {
   const size_t o_mmp = bump((size_t)1024 * 2 * 4);   // lpips_minmax_blocks <= 1024
   h->ws_pairs = 0;
   HIP_TRY(h->ws.alloc(used));
+  h->ws_bytes = used;
+  h->geo = g;
   char* b = (char*)h->ws.p;
   h->x0 = (float*)(b + o_x0); h->f1 = (float*)(b + o_f1); h->p1 = (float*)(b + o_p1); h->f2 = (float*)(b + o_f2);
   h->p2 = (float*)(b + o_p2); h->f3 = (float*)(b + o_f3); h->f4 = (float*)(b + o_f4); h->f5 = (float*)(b + o_f5);
@@ -201,10 +206,46 @@ extern "C" int dsx_lpips_forward(dsx_lpips* h, const float* in0_nchw_dev, const 
   if (rc) return rc;
   if ((rc = check_sizes(g, B))) return rc;
   if ((rc = ensure_device(h))) return rc;
+  h->table_pairs = 0;
   if ((rc = ensure_workspace(h, g, B))) return rc;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launch_lpips_input_nchw(in0_nchw_dev, in1_nchw_dev, B, H, W, h->x0, st));
-  return run_trunk(h, g, B, 0, out_dev, per_tap_dev, st);
+  if ((rc = run_trunk(h, g, B, 0, out_dev, per_tap_dev, st))) return rc;
+  h->table_pairs = B;
+  return DSX_OK;
+}
+
+extern "C" int dsx_lpips_layers(const dsx_lpips* h, dsx_lpips_layer_table* table) {
+  if (!h || !table) return fail(DSX_ERR_INVALID, "bad argument");
+  if (h->table_pairs < 1 || !h->ws.p)
+    return fail(DSX_ERR_INVALID, "LPIPS layer table: the workspace holds no whole forward (call it after dsx_lpips_forward; "
+                "dsx_lpips_frames reuses the workspace per chunk)");
+  const Geo& g = h->geo;
+  const float* stage[DSX_LPIPS_STAGES] = {h->x0, h->f1, h->p1, h->f2, h->p2, h->f3, h->f4, h->f5};
+  const int sh[DSX_LPIPS_STAGES] = {g.H, g.H1, g.P1h, g.P1h, g.P2h, g.P2h, g.P2h, g.P2h};
+  const int sw[DSX_LPIPS_STAGES] = {g.W, g.W1, g.P1w, g.P1w, g.P2w, g.P2w, g.P2w, g.P2w};
+  const int sc[DSX_LPIPS_STAGES] = {3, 64, 64, 192, 192, 384, 256, 256};
+  *table = dsx_lpips_layer_table{};
+  table->pairs = h->table_pairs;
+  table->nimg = 2 * h->table_pairs;
+  for (int s = 0; s < DSX_LPIPS_STAGES; ++s) {
+    table->H[s] = sh[s]; table->W[s] = sw[s]; table->C[s] = sc[s];
+    table->stage[s] = (uint64_t)(uintptr_t)stage[s];
+  }
+  for (int t = 0; t < 5; ++t) {   // a forward runs ws_pairs pairs: the rows of run_trunk lie where ensure_workspace put them
+    table->nblk[t] = h->taps.nblk[t];
+    table->hw[t] = h->taps.hw[t];
+    table->part[t] = (uint64_t)(uintptr_t)(h->part + h->taps.off[t]);
+  }
+  return DSX_OK;
+}
+
+extern "C" int dsx_lpips_copy_workspace(const dsx_lpips* h, uint64_t src, size_t bytes, void* dst_dev, void* stream) {
+  if (!h || !dst_dev) return fail(DSX_ERR_INVALID, "bad argument");
+  const uint64_t lo = (uint64_t)(uintptr_t)h->ws.p, hi = lo + h->ws_bytes;
+  if (!h->ws.p || src < lo || src > hi || bytes > hi - src) return fail(DSX_ERR_INVALID, "range is not inside the workspace");
+  HIP_TRY(hipMemcpyAsync(dst_dev, (const void*)(uintptr_t)src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return DSX_OK;
 }
 
 // compute_lpips of the evaluation notebooks for one channel: min-max map with the TARGET channel's range over all N
@@ -225,6 +266,7 @@ extern "C" int dsx_lpips_frames(dsx_lpips* h, const float* target_nhwc_dev, cons
   if ((rc = check_sizes(g, chunk))) return rc;
   if ((rc = ensure_device(h))) return rc;
   const long long pixels = (long long)N * H * W;
+  h->table_pairs = 0;
   if ((rc = ensure_workspace(h, g, chunk))) return rc;
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launch_lpips_minmax(target_nhwc_dev, pixels, C, channel, h->mm_part, h->mm, st));

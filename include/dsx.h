@@ -673,6 +673,25 @@ int dsx_lpips_forward(dsx_lpips* h, const float* in0_nchw_dev, const float* in1_
  * A constant target channel divides by zero, as the reference does. */
 int dsx_lpips_frames(dsx_lpips* h, const float* target_nhwc_dev, const float* pred_nhwc_dev, int N, int H, int W, int C,
                      int channel, int chunk, float* out_dev, void* stream);
+/* Stage table (verification): the workspace keeps every stage of the last dsx_lpips_forward, so a test can recompute
+ * each launch from that launch's own input.  Stages in order: x0 (the scaled input), f1 (conv1 + ReLU, tap 1), p1
+ * (pool), f2 (conv2, tap 2), p2 (pool), f3, f4, f5 (conv3..5, taps 3..5); each is fp32 NHWC (nimg, H[s], W[s], C[s]) at
+ * device address stage[s], image b of in0 first, then image b of in1 at nimg / 2 + b.  Per tap t: part[t] is the
+ * address of [pairs][nblk[t]] doubles, the partial sums k_lpips_finish adds in order and divides by hw[t].  Read-only:
+ * no launch, no result changes.  Refused before any forward and after dsx_lpips_frames, which reuses the workspace
+ * per chunk. */
+enum { DSX_LPIPS_STAGES = 8 };
+typedef struct dsx_lpips_layer_table {
+  int32_t pairs, nimg;
+  int32_t H[DSX_LPIPS_STAGES], W[DSX_LPIPS_STAGES], C[DSX_LPIPS_STAGES];
+  int32_t nblk[5], hw[5];
+  uint64_t stage[DSX_LPIPS_STAGES];
+  uint64_t part[5];
+} dsx_lpips_layer_table;
+int dsx_lpips_layers(const dsx_lpips* h, dsx_lpips_layer_table* table);
+/* Copies `bytes` from device address `src` (which must lie inside the handle's workspace) to the caller's device
+ * buffer `dst_dev` on `stream`. */
+int dsx_lpips_copy_workspace(const dsx_lpips* h, uint64_t src, size_t bytes, void* dst_dev, void* stream);
 
 /* ------------------------------------------------------------------ SR3 image path: resize and ToTensor
  * The first step of the reference's SR3 configurations (data/prepare_data.py:17-40 resize_and_convert /

@@ -82,6 +82,39 @@ def test_float_frame_2048_data_range():
     assert psnr[0].item() == pytest.approx(ref.psnr(a[0, 0].numpy(), b[0, 0].numpy(), L), rel=1e-12)
 
 
+# (H, W) -> valid region (H - 10, W - 10): one-row and one-column tile grids (1 x 65, 65 x 1), an exact 32-pixel tile next
+# to a one-pixel tile in both orientations (32 x 33, 33 x 32), 30 x 23, and 2 x 5 tiles (64 x 129)
+UNEVEN = [(11, 75), (75, 11), (42, 43), (43, 42), (40, 33), (74, 139)]
+
+
+@pytest.mark.parametrize("quantize", [True, False])
+@pytest.mark.parametrize("hw", UNEVEN, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_uneven_tile_grids_against_the_restatement(hw, quantize):
+    """k_image_metrics takes its tile from tiles_x and the SSD's owner from ty_last / tx_last: non-square grids against
+    the float64 restatement, three planes each, at the tolerances of the square sizes above"""
+    M = _m()
+    H, W = hw
+    a, b = _images((2, 3, H, W), 100 * H + W)
+    if quantize:
+        psnr, ssim = M.image_metrics(a.to(DEV), b.to(DEV))
+    else:
+        L = 3.7
+        psnr, ssim = M.image_metrics(a.to(DEV), b.to(DEV), quantize=False, data_range=L)
+    assert psnr.shape == (2,) and ssim.shape == (2,)
+    for i in range(2):
+        if quantize:
+            ia, ib = M.tensor2img(a[i]), M.tensor2img(b[i])
+            assert ia.shape == (H, W, 3)
+            assert psnr[i].item() == ref.psnr(ia, ib) == M.calculate_psnr(ia, ib)
+            want = ref.ssim(ia, ib)
+        else:
+            ia, ib = a[i].numpy(), b[i].numpy()
+            assert psnr[i].item() == pytest.approx(ref.psnr(ia, ib, L), rel=1e-12)
+            want = np.mean([ref.ssim_map(ia[c], ib[c], L) for c in range(3)])
+        assert abs(ssim[i].item() - want) <= 1e-9, (ssim[i].item(), want)
+        assert 0.0 < ssim[i].item() < 0.999                  # neither degenerate nor an identical pair
+
+
 @pytest.mark.parametrize("quantize", [True, False])
 def test_identical_inputs(quantize):
     M = _m()

@@ -12,7 +12,8 @@ import torch
 from tests import lpips_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("dsx_lpips_create", "dsx_lpips_destroy", "dsx_lpips_forward", "dsx_lpips_frames")
+NEW = ("dsx_lpips_create", "dsx_lpips_destroy", "dsx_lpips_forward", "dsx_lpips_frames", "dsx_lpips_layers",
+       "dsx_lpips_copy_workspace")
 torch.set_grad_enabled(False)
 
 
