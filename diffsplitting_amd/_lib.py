@@ -196,6 +196,8 @@ SIGNATURES = {
     "dsx_tileplan_blend": (_i, [_hn, _Df, _i, _i, _i64, _Df, _Df, _Dd, _st]),
     "dsx_tileplan_gather_canvas": (_i, [_hn, _Df, _i, _i64, _i64, _i64, _Df, _st]),
     "dsx_tileplan_blend_step": (_i, [_hn, _Df, _i, _i, _i64, _Df, _f, _f, _f, _u64, _u64, C.c_uint32, _st]),
+    "dsx_tileplan_crop_lines": (_i, [_hn, _i, _H, _H]),
+    "dsx_tileplan_disagreement": (_i, [_hn, _Df, _i, _i, _i64, _i, _Df, _Dd, _st]),
     "dsx_tiff_open": (_i, [C.c_char_p, C.POINTER(_vp)]),
     "dsx_tiff_info": (_i, [_hn, _pi64, C.POINTER(_i)]),
     "dsx_tiff_read": (_i, [_hn, _i64, _i64, _H, C.c_size_t]),

@@ -757,6 +757,19 @@ static inline BlendGrid blend_grid(long long H, long long W) {
   return BlendGrid{(int)((W + 255) / 256), (int)(H > 128 ? 128 : H)};
 }
 hipError_t launch_blend(const BlendArgs& a, hipStream_t st);
+// Tile disagreement (include/dsx.h, dsx_tileplan_disagreement): per canvas pixel and channel the unbiased variance among
+// the tiles that cover it, in the blend's geometry, tile layouts and contributor tables.  near_y[H] / near_x[W]: the
+// near-line masks of the call's band.  map (N,H,W,C) of (float)sqrt(var), or nullptr; part[N][blocks][C][8] =
+// {count k >= 2, sum var, band count, band sum var, min var, max var, 0, 0} per (frame, workgroup, channel), C <= kPsnrMaxC.
+struct DisagreeArgs {
+  const float* tiles; int C, world; long long rank_stride;
+  int N, H, W, ph, pw, ny, nx;
+  const int* starts;                 // dev [total][3]
+  const int* rows; const int* cols;  // dev [H][2], [W][2]
+  const unsigned char* near_y; const unsigned char* near_x;   // dev [H], [W]
+  float* map; double* part;
+};
+hipError_t launch_disagreement(const DisagreeArgs& a, hipStream_t st);
 // the tiles of the sequence out of a multi-channel frame state: canvas (N,H,W,C) -> tiles (count, C, ph, pw)
 hipError_t launch_tiles_gather_canvas(const float* canvas, int C, const TileGeom& g, float* tiles, hipStream_t st);
 

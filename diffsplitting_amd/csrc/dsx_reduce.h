@@ -15,6 +15,7 @@
 // completeness.)  The rows, RedRow<sums, (min, max) pairs>, all kDown and Pairwise:
 //   RedRow<5, 1>  PsnrSums: k_stitch_psnr and k_blend<.., true>, once per channel (psnr_sums_write)
 //   RedRow<5, 2>  PsnrSums + min / max of p: k_msssim_stats per chunk, k_msssim_coef over a plane's chunk rows
+//   RedRow<4, 1>  k_tile_disagreement (dsx_tiles.hip), once per channel: two pixel counts, two sums of var, min / max of var
 //   RedRow<9, 1>  k_comoments_partial (dsx_refine.hip): nine sums of shifted data, min / max of g
 // k_comoments_finish then folds a plane's workgroup rows with ONE wave: lane l adds the rows l, l + 64, .. in ascending
 // order, wave_reduce (kDown) folds the lanes.

@@ -342,6 +342,11 @@ struct dsx_tileplan {
     DevBuf d_off;                                // long long [total]
   };
   std::vector<Offsets> offs;
+  struct Band {                                  // the near-line masks of one band (dsx_tileplan_crop_lines) on the device
+    int band = 0;
+    DevBuf d;                                    // uint8 [H + W]: rows, then columns
+  };
+  std::vector<Band> bands;
 };
 
 static void plan_layout(const dsx_tileplan* p, int world, dsx_tileplan::Offsets& o) {
@@ -662,17 +667,18 @@ extern "C" int dsx_tileplan_blend_blocks(const dsx_tileplan* p) {
   return bg.segs * bg.rows;
 }
 // what dsx_tileplan_blend and dsx_tileplan_blend_step refuse alike, on the host alone
+// (windowed == false: dsx_tileplan_disagreement, which needs neither a canvas nor a window)
 static int blend_checks(const char* what, const dsx_tileplan* p, const float* tiles_dev, int C, int world,
                         int64_t rank_stride_elems, const float* canvas_dev, const float* gt_canvas_dev,
-                        const double* partials_dev) {
-  if (!p || !tiles_dev || !canvas_dev) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+                        const double* partials_dev, bool windowed = true) {
+  if (!p || !tiles_dev || (windowed && !canvas_dev)) return fail(DSX_ERR_INVALID, "%s: null argument", what);
   if (C < 1) return fail(DSX_ERR_INVALID, "%s: C = %d, must be at least 1", what, C);
   if (world < 1) return fail(DSX_ERR_INVALID, "%s: world = %d, must be at least 1", what, world);
   if (gt_canvas_dev && (!partials_dev || C > kPsnrMaxC))
     return fail(DSX_ERR_INVALID, "%s: PSNR sums need a partials buffer and C <= %d", what, kPsnrMaxC);
   if (!p->covers)
     return fail(DSX_ERR_INVALID, "%s: the plan's tiles do not cover the frames (SHIFT tiling of (1, g, g) grids does)", what);
-  if (p->window.empty()) return fail(DSX_ERR_INVALID, "%s: the plan has no window: call dsx_tileplan_set_window first", what);
+  if (windowed && p->window.empty()) return fail(DSX_ERR_INVALID, "%s: the plan has no window: call dsx_tileplan_set_window first", what);
   if (p->t.D[0] > 65535) return fail(DSX_ERR_INVALID, "%s: %lld frames, at most 65535 per plan", what, (long long)p->t.D[0]);
   if (p->total > INT32_MAX) return fail(DSX_ERR_INVALID, "%s: %lld tiles, the tile id must fit 31 bits", what, (long long)p->total);
   if (const int rc = tile_elems_ok(what, p, C)) return rc;
@@ -724,6 +730,77 @@ extern "C" int dsx_tileplan_blend_step(dsx_tileplan* p, const float* x0_tiles_de
   a.canvas = state_dev;
   a.step = 1; a.c_x0 = c_x0; a.c_xt = c_xt; a.sigma = sigma; a.seed = seed; a.id_base = id_base; a.draw = draw;
   return blend_launch(what, p, a, stream);
+}
+// ------------------------------------------------------------------ tile disagreement (contract: include/dsx.h)
+// The clipped paste regions partition every frame into nx column ranges times ny row ranges.  Along axis d the range of
+// tile row (column) k is that of tile k * step of frame 0; a range the clip emptied owns nothing.  A coordinate v >= 1
+// whose owner differs from that of v - 1 is a crop line L, and every v with L - band <= v < L + band is near it.
+static void axis_near(const dsx_tileplan* p, int d, int band, uint8_t* near) {
+  const int64_t n = p->t.dim_count(d), D = p->t.D[d], step = d == 1 ? p->t.dim_count(2) : 1;
+  std::vector<int32_t> owner((size_t)D, -1);
+  for (int64_t k = 0; k < n; ++k) {
+    const int32_t* r = p->regions.data() + (size_t)(k * step) * 8;
+    for (int64_t v = r[d]; v < (int64_t)r[d] + r[2 + d]; ++v) owner[v] = (int32_t)k;
+  }
+  memset(near, 0, (size_t)D);
+  for (int64_t L = 1; L < D; ++L) {
+    if (owner[L] == owner[L - 1]) continue;
+    for (int64_t v = std::max<int64_t>(0, L - band); v < std::min<int64_t>(D, L + band); ++v) near[v] = 1;
+  }
+}
+static int band_ok(const char* what, int band) {
+  if (band >= 1 && band <= 65535) return DSX_OK;
+  return fail(DSX_ERR_INVALID, "%s: band = %d, must be in 1..65535", what, band);
+}
+static int covers_ok(const char* what, const dsx_tileplan* p) {
+  if (p->covers) return DSX_OK;
+  return fail(DSX_ERR_INVALID, "%s: the plan's tiles do not cover the frames (SHIFT tiling of (1, g, g) grids does)", what);
+}
+extern "C" int dsx_tileplan_crop_lines(const dsx_tileplan* p, int band, uint8_t* rows, uint8_t* cols) {
+  const char* what = "tileplan_crop_lines";
+  if (!p || !rows || !cols) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  if (const int rc = band_ok(what, band)) return rc;
+  if (const int rc = covers_ok(what, p)) return rc;
+  axis_near(p, 1, band, rows);
+  axis_near(p, 2, band, cols);
+  return DSX_OK;
+}
+// the masks of `band` on the device: built and uploaded at the first call that names the band, then kept with the plan
+static int plan_band(dsx_tileplan* p, int band, const uint8_t** near_y, const uint8_t** near_x) {
+  const int64_t H = p->t.D[1], W = p->t.D[2];
+  for (auto& b : p->bands)
+    if (b.band == band) { *near_y = b.d.as<uint8_t>(); *near_x = b.d.as<uint8_t>() + H; return DSX_OK; }
+  std::vector<uint8_t> m((size_t)(H + W));
+  axis_near(p, 1, band, m.data());
+  axis_near(p, 2, band, m.data() + H);
+  dsx_tileplan::Band b;
+  b.band = band;
+  HIP_TRY(b.d.alloc(m.size()));
+  if (hipMemcpy(b.d.p, m.data(), m.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(DSX_ERR_HIP, "tileplan_disagreement: upload of the band masks failed");
+  p->bands.push_back(std::move(b));
+  *near_y = p->bands.back().d.as<uint8_t>();
+  *near_x = *near_y + H;
+  return DSX_OK;
+}
+extern "C" int dsx_tileplan_disagreement(dsx_tileplan* p, const float* tiles_dev, int C, int world, int64_t rank_stride_elems,
+                                         int band, float* map_dev, double* partials_dev, void* stream) {
+  const char* what = "tileplan_disagreement";
+  if (!p || !tiles_dev || !partials_dev) return fail(DSX_ERR_INVALID, "%s: null argument", what);
+  if (C < 1 || C > kPsnrMaxC) return fail(DSX_ERR_INVALID, "%s: C = %d, must be in 1..%d", what, C, kPsnrMaxC);
+  if (const int rc = band_ok(what, band)) return rc;
+  if (const int rc = blend_checks(what, p, tiles_dev, C, world, rank_stride_elems, nullptr, nullptr, nullptr, false)) return rc;
+  int rc = plan_device(p);
+  if (rc) return rc;
+  DisagreeArgs a{};
+  if ((rc = plan_band(p, band, &a.near_y, &a.near_x))) return rc;
+  a.tiles = tiles_dev; a.C = C; a.world = world; a.rank_stride = rank_stride_elems;
+  a.N = (int)p->t.D[0]; a.H = (int)p->t.D[1]; a.W = (int)p->t.D[2]; a.ph = (int)p->t.p[1]; a.pw = (int)p->t.p[2];
+  a.ny = (int)p->t.dim_count(1); a.nx = (int)p->t.dim_count(2);
+  a.starts = p->d_starts.as<int>(); a.rows = p->d_rows; a.cols = p->d_cols;
+  a.map = map_dev; a.part = partials_dev;
+  HIP_TRY(launch_disagreement(a, (hipStream_t)stream));
+  return DSX_OK;
 }
 // tiles first + k * stride of the plan out of a (N,H,W,C) frame state -> (count, C, ph, pw)
 extern "C" int dsx_tileplan_gather_canvas(dsx_tileplan* p, const float* canvas_dev, int C, int64_t first, int64_t stride,

@@ -452,7 +452,8 @@ hipError_t launch_stitch(const StitchSrc& s, int C, const int* regions, TileSeq 
 // element and keeps its component (normal1: one log and one sincos, not two).  Nothing is drawn where sigma == 0.
 // ---------------------------------------------------------------------------
 constexpr int kBlendCols = 4;                  // tile columns of a pixel kept in registers
-__device__ __forceinline__ const float* blend_tile(const BlendArgs& a, unsigned t, unsigned tile_elems) {
+template <class Args>                          // BlendArgs or DisagreeArgs: the two layouts of whole tiles
+__device__ __forceinline__ const float* blend_tile(const Args& a, unsigned t, unsigned tile_elems) {
   return a.world == 1 ? a.tiles + (size_t)t * tile_elems
                       : a.tiles + (size_t)(t % (unsigned)a.world) * a.rank_stride + (size_t)(t / (unsigned)a.world) * tile_elems;
 }
@@ -595,6 +596,124 @@ hipError_t launch_blend(const BlendArgs& a, hipStream_t st) {
   else if (a.C == 4) launch_blend_as<4, false>(a, grid, st);
   else if (a.step) hipLaunchKernelGGL((k_blend<0, false, false, true>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((k_blend<0, false, false, false>), grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Tile disagreement (include/dsx.h, dsx_tileplan_disagreement): the sibling of the blend that reports how far the
+// contributors of a canvas pixel differ instead of averaging them.  The geometry is k_blend's: workgroup (sx, sy, n)
+// owns the 256 pixels from x = 256 * sx of the rows y = sy, sy + gridDim.y, ...; a thread keeps its x, the tile columns
+// that cover it (the first kBlendCols offsets in registers) and whether its column is near a crop line; the tile rows
+// and the row's near-line flag are uniform in the workgroup.  One dword per tile row and lane.  Per pixel and channel
+// Welford's recurrence over the contributors in ascending tile id, in double, every operation rounded on its own (the
+// update of k_moments_update); var = M2 / (k - 1), s = (float)sqrt(var).  MAP: s goes to map (N,H,W,C), WIDE as one 8- /
+// 16-byte store for C = 2 / 4.  Every thread keeps, per channel, sum and min / max of var over its pixels with k >= 2
+// and the sum over those in the band, and once the two pixel counts (they are the same for every channel); the rows go
+// through RedRow<4, 1>: row[c][8] = {count, sum var, band count, band sum var, min var, max var, 0, 0}.  No atomics.
+// ---------------------------------------------------------------------------
+using DisRow = RedRow<4, 1>;
+constexpr int kDisRed = 4 * kPsnrMaxC * DisRow::kSlots;           // doubles of LDS, [wave][channel][slot]
+template <int CT>
+__device__ __forceinline__ void disagree_add(const DisagreeArgs& a, unsigned t, int plane, int off, int r, double mean[CT],
+                                             double m2[CT]) {
+  const float* p = blend_tile(a, t, (unsigned)plane * CT) + off;
+  const double rn = (double)(r + 1);
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    const double v = (double)p[c * plane];
+    if (r == 0) { mean[c] = v; m2[c] = 0.0; continue; }
+    const double d = sub_d(v, mean[c]);
+    const double m1 = add_d(mean[c], d / rn);
+    m2[c] = add_d(m2[c], mul_d(d, sub_d(v, m1)));
+    mean[c] = m1;
+  }
+}
+template <int CT, bool WIDE, bool MAP>
+__global__ __launch_bounds__(256) void k_tile_disagreement(const DisagreeArgs a) {
+  constexpr int kS = DisRow::kSlots;
+  __shared__ double red[kDisRed];
+  const int n = blockIdx.z, x = blockIdx.x * 256 + threadIdx.x;
+  const bool live = x < a.W;
+  const unsigned tile0 = (unsigned)n * a.ny * a.nx;
+  const int plane = a.ph * a.pw;
+  int tx0 = 0, txn = 0, xo[kBlendCols];
+  bool near_x = false;
+  if (live) { tx0 = a.cols[2 * x]; txn = a.cols[2 * x + 1]; near_x = a.near_x[x] != 0; }
+#pragma unroll
+  for (int j = 0; j < kBlendCols; ++j) xo[j] = j < txn ? x - a.starts[(size_t)(tx0 + j) * 3 + 2] : 0;
+  double cnt = 0.0, cnt_band = 0.0, sum[CT], sum_band[CT], mn[CT], mx[CT];
+#pragma unroll
+  for (int c = 0; c < CT; ++c) { sum[c] = sum_band[c] = 0.0; mn[c] = INFINITY; mx[c] = -INFINITY; }
+  for (int y = blockIdx.y; y < a.H; y += gridDim.y) {
+    if (!live) continue;
+    const int ty0 = a.rows[2 * y], tyn = a.rows[2 * y + 1];
+    const int k = tyn * txn;
+    const bool band = k >= 2 && (near_x || a.near_y[y] != 0);
+    double mean[CT], m2[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) mean[c] = m2[c] = 0.0;
+    int r = 0;
+    for (int iy = ty0; iy < ty0 + tyn; ++iy) {
+      const unsigned trow = tile0 + (unsigned)iy * a.nx;       // tile (iy, 0): every tile of row iy starts at its y
+      const int yy = y - a.starts[(size_t)trow * 3 + 1];
+#pragma unroll
+      for (int j = 0; j < kBlendCols; ++j)
+        if (j < txn) disagree_add<CT>(a, trow + tx0 + j, plane, yy * a.pw + xo[j], r++, mean, m2);
+      for (int j = kBlendCols; j < txn; ++j) {
+        const int xx = x - a.starts[(size_t)(tx0 + j) * 3 + 2];
+        disagree_add<CT>(a, trow + tx0 + j, plane, yy * a.pw + xx, r++, mean, m2);
+      }
+    }
+    float s[CT];
+    const double km1 = (double)(k - 1);
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const double var = k > 1 ? m2[c] / km1 : 0.0;
+      s[c] = (float)sqrt(var);
+      if (k > 1) {
+        sum[c] += var; mn[c] = fmin(mn[c], var); mx[c] = fmax(mx[c], var);
+        if (band) sum_band[c] += var;
+      }
+    }
+    if (k > 1) { cnt += 1.0; if (band) cnt_band += 1.0; }
+    if (MAP) {
+      float* dst = a.map + (((size_t)n * a.H + y) * a.W + x) * CT;
+      if (WIDE && CT == 2) *(float2*)dst = make_float2(s[0], s[CT > 1 ? 1 : 0]);
+      else if (WIDE && CT == 4) *(float4*)dst = make_float4(s[0], s[CT > 1 ? 1 : 0], s[CT > 2 ? 2 : 0], s[CT > 3 ? 3 : 0]);
+      else {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) dst[c] = s[c];
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CT; ++c) {
+    const double v[kS] = {cnt, sum[c], cnt_band, sum_band[c], mn[c], mx[c]};
+    DisRow::park(v, red, kPsnrMaxC * kS, c * kS);
+  }
+  __syncthreads();
+  if (threadIdx.x < CT * 8) {
+    const int c = threadIdx.x >> 3, j = threadIdx.x & 7;
+    const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x, blocks = (size_t)gridDim.x * gridDim.y;
+    a.part[(((size_t)n * blocks + b) * CT + c) * 8 + j] = j < kS ? DisRow::combine(red, j, kPsnrMaxC * kS, c * kS) : 0.0;
+  }
+}
+template <int CT, bool WIDE>
+static void launch_disagreement_as(const DisagreeArgs& a, const dim3 grid, hipStream_t st) {
+  if (a.map != nullptr) hipLaunchKernelGGL((k_tile_disagreement<CT, WIDE, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_tile_disagreement<CT, false, false>), grid, dim3(256), 0, st, a);
+}
+hipError_t launch_disagreement(const DisagreeArgs& a, hipStream_t st) {
+  if (a.N < 1 || a.N > 65535 || a.C < 1 || a.C > kPsnrMaxC || a.part == nullptr) return hipErrorInvalidValue;
+  const BlendGrid bg = blend_grid(a.H, a.W);
+  const dim3 grid((unsigned)bg.segs, (unsigned)bg.rows, (unsigned)a.N);
+  const uintptr_t at = (uintptr_t)a.map;                       // a null map is aligned: its form has no stores
+  if (a.C == 1) launch_disagreement_as<1, false>(a, grid, st);
+  else if (a.C == 2 && (at & 7u) == 0) launch_disagreement_as<2, true>(a, grid, st);
+  else if (a.C == 2) launch_disagreement_as<2, false>(a, grid, st);
+  else if (a.C == 3) launch_disagreement_as<3, false>(a, grid, st);
+  else if ((at & 15u) == 0) launch_disagreement_as<4, true>(a, grid, st);
+  else launch_disagreement_as<4, false>(a, grid, st);
   return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@ import torch
 
 from .. import parallel
 from .._lib import DsxError
-from .tile_predict import (_batches, _check_field_ids, _check_quantile_bytes, _check_quantiles, _check_rank_gt,
+from .tile_predict import (FrameDisagreement, _batches, _check_disagreement, _check_field_ids, _check_frame_map, _check_quantile_bytes, _check_quantiles, _check_rank_gt,
                            _check_samples, _check_stitch, _is_gaussian, _mean_and_spread, _mean_spread_quantiles,
                            _scorable_gt, store_kept)
 
@@ -38,14 +38,15 @@ def _frame_outputs(netG, dataset, samples, return_std, draw, q=None, ranks=False
     return out
 
 
-def fused_sample(netG, dataset, table, batch_tiles, seed, id_base, order=None, keep_tiles=None):
+def fused_sample(netG, dataset, table, batch_tiles, seed, id_base, order=None, keep_tiles=None, measure=None):
     """One posterior sample of per-step frame fusion -> the frame state (N,H,W,C) after the last row of ``table`` (a
     ``SolverTableHost``).  The state starts as draw 0 of the noise fields ``id_base + n``; per row and batch of tiles:
     ``gather_canvas`` -> ``denoise_fn`` -> ``engine.solver_step`` -> two resident (total, C, p, p) buffers; after the
     row's last batch the x tiles are blended into the state, the x0 tiles into the history when the next row reads it.
     The last short batch is moved back to end at the last tile (one executor, one batch size).  ``order``: a permutation
     of the batches (the result does not depend on it).  ``keep_tiles``: a list that receives the x tiles of every row
-    before their blend (a copy per row)."""
+    before their blend (a copy per row).  ``measure``: a ``FrameDisagreement`` that takes the x tiles of the last row,
+    what ``keep_tiles[-1]`` holds."""
     from .. import engine
     plan = dataset.plan
     N, H, W = plan.data_shape
@@ -76,19 +77,30 @@ def fused_sample(netG, dataset, table, batch_tiles, seed, id_base, order=None, k
             store_kept(x0t, x0, chunk, keep)
         if keep_tiles is not None:
             keep_tiles.append(xt.clone())
+        if measure is not None and s == K - 1:
+            measure.child(xt, 1, Cn)
         X = plan.blend(xt)
         if s + 1 < K and table.cp[s + 1] != 0:
             X0 = plan.blend(x0t)
     return X
 
 
-def _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q=None, ranks=False):
+def _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q=None, ranks=False,
+                         measure=None):
     """``predict_stack(fuse=True)`` after its checks: the frame states of the posterior samples (``fused_sample``),
-    sample ``r`` with the field ids ``r * frames + n``."""
+    sample ``r`` with the field ids ``r * frames + n``.  ``measure``: a ``FrameDisagreement`` or None."""
     dataset.plan.set_window(window)
     frames, table = dataset.plan.data_shape[0], netG.solver_table(**solver)
-    return _frame_outputs(netG, dataset, samples, return_std,
-                          lambda r: fused_sample(netG, dataset, table, batch_tiles, seed, r * frames), q, ranks)
+
+    def draw(r):
+        X = fused_sample(netG, dataset, table, batch_tiles, seed, r * frames, measure=measure)
+        if measure is not None:
+            measure.end_sample()
+        return X
+    out = _frame_outputs(netG, dataset, samples, return_std, draw, q, ranks)
+    if measure is not None:
+        out["disagreement"] = measure.result()
+    return out
 
 
 # ---- frame diffusion for the InDI family ----------------------------------------------------------------------------
@@ -114,7 +126,7 @@ def input_frames(dataset, batch_tiles=8):
 
 
 def frame_sample(child, dataset, x_in, num_timesteps, t_float_start, batch_tiles, seed, id_base, group=None,
-                 keep_tiles=None):
+                 keep_tiles=None, measure=None):
     """One posterior sample of frame diffusion with the InDI sampler ``child`` -> the frame state (N,H,W,C) after the
     last row of ``engine.indi_step_table``.  ``x_in`` (N,H,W,Cin): the normalised input frames.  The state starts as
     ``x_in`` (repeated to the sampler's channels) ``+ Z0 * (e * t)``, Z0 draw 0 of the noise fields ``id_base + n``; per
@@ -122,7 +134,8 @@ def frame_sample(child, dataset, x_in, num_timesteps, t_float_start, batch_tiles
     buffer, the rank's slot of the exchange buffer; after the row's last batch one all-gather of the slots (several
     ranks) and one ``TilePlan.blend_step`` with draw ``s + 1``: the whole InDI update of the row, on the canvas.  A short
     last batch is moved back (one executor).  ``keep_tiles``: a list that receives the x0 tiles of every row before
-    their blend (a copy per row; one rank)."""
+    their blend (a copy per row; one rank).  ``measure``: a ``FrameDisagreement`` that takes the x0 tiles of the last row
+    in the layout the row's ``blend_step`` reads, gathered or not."""
     from .. import engine
     plan = dataset.plan
     N, H, W = plan.data_shape
@@ -144,10 +157,15 @@ def frame_sample(child, dataset, x_in, num_timesteps, t_float_start, batch_tiles
         if keep_tiles is not None:
             keep_tiles.append(x0t.clone())
         row = (float(table.c1[s]), float(table.c2[s]), float(table.sigma[s]), seed, s + 1, id_base)
+        last = measure is not None and s == table.n_steps - 1
         if world == 1:
+            if last:
+                measure.child(x0t, 1, Cn)
             plan.blend_step(x0t, X, *row)
         else:
             full = parallel.all_gather_flat(flat, group)              # the row's one collective, of whole x0 tiles
+            if last:
+                measure.child(full, world, Cn)
             plan.blend_step(full, X, *row, world=world, Cn=Cn)
     return X
 
@@ -155,7 +173,7 @@ def frame_sample(child, dataset, x_in, num_timesteps, t_float_start, batch_tiles
 @torch.no_grad()
 def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_float_start=None, samples=1,
                          return_std=False, seed=None, group=None, window="triangle", quantiles=None, ranks=False,
-                         quantile_bytes=8 << 30):
+                         quantile_bytes=8 << 30, disagreement=False, seam_band=8):
     """``predict_stack`` for the InDI family (``InDISampler`` and its subclasses, ``JointIndiSampler``) with every frame
     diffused as ONE state: frame diffusion.  The InDI update ``x <- (d/t) x0 + (1 - d/t) x + e (t - d) z`` is affine in
     the UNet output with coefficients shared by the batch, so a row of a frame is ``X <- c_x0 * blend(x0 tiles) +
@@ -172,7 +190,11 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
 
     ``quantiles=`` / ``ranks=True`` (``samples`` in 2..64): ``out['quantiles']`` (Q,N,H,W,C) and ``out['rank']`` (N,H,W,C)
     as ``predict_stack`` describes them; a draw is the whole frame state here, so both are exact per pixel.  The
-    ``samples`` states are kept: more than ``quantile_bytes`` of them is refused before any launch."""
+    ``samples`` states are kept: more than ``quantile_bytes`` of them is refused before any launch.
+
+    ``disagreement=True`` / ``"sums"`` with ``seam_band``: ``out['disagreement']`` as ``predict_stack`` describes it, of
+    the x0 tiles of the last row before their blend (a joint sampler's two children joined along the channels), per
+    posterior sample: counts and sums are added in sample order, min / max folded; a map needs ``samples == 1``."""
     from ..model.samplers import InDISampler, JointIndiSampler
     what = "predict_stack_frames"
     if _is_gaussian(netG):
@@ -193,6 +215,10 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
     plan, N = dataset.plan, dataset.plan.data_shape[0]
     _check_field_ids(what, samples, N)
     _check_stitch(what, "blend", window)
+    measure = _check_disagreement(what, disagreement, seam_band, max(c.out_channel for c, _, _ in children) if disagreement
+                                  else None)
+    _check_frame_map(what, "the frame-state path", measure, samples)
+    measure = FrameDisagreement(plan, measure, seam_band) if measure else None
     q, ranks = _check_quantiles(what, samples, quantiles, ranks, dataset)
     if q is not None or ranks:
         _check_quantile_bytes(what, samples, plan, netG.prediction_channels, quantile_bytes)
@@ -201,6 +227,11 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
 
     def draw(r):
         parts = [frame_sample(child, dataset, x_in, int(child.num_timesteps if num_timesteps is None else num_timesteps),
-                              t0, batch_tiles, seed, r * N + bit, group) for child, t0, bit in children]
+                              t0, batch_tiles, seed, r * N + bit, group, measure=measure) for child, t0, bit in children]
+        if measure is not None:
+            measure.end_sample()
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1)
-    return _frame_outputs(netG, dataset, samples, return_std, draw, q, ranks), plan
+    out = _frame_outputs(netG, dataset, samples, return_std, draw, q, ranks)
+    if measure is not None:
+        out["disagreement"] = measure.result()
+    return out, plan

@@ -15,13 +15,23 @@ class TileExchange:
 
     ``blend=True``: blended stitching (``TilePlan.blend``) under ``window``.  This rank's WHOLE predicted tiles stay in a
     resident buffer -- its slot of the exchange buffer, tile ``id`` at index ``id // world`` --, ``add`` copies a batch
-    in, and ``finish`` is one all-gather of the equal-sized slots (several ranks) and one blend of all tiles."""
+    in, and ``finish`` is one all-gather of the equal-sized slots (several ranks) and one blend of all tiles.
 
-    def __init__(self, plan, channels, device, group=None, gt=None, blend=False, window="triangle"):
+    ``disagreement=True`` (or ``"sums"``: no map): ``finish`` also measures how far the whole tiles differ where they
+    overlap (``TilePlan.disagreement`` with ``band = seam_band``) and leaves the result in ``self.disagreement``.  Under
+    ``blend=True`` the kernel reads the buffer the blend reads, gathered or not.  Under crop the exchange additionally
+    keeps this rank's whole tiles in a slot of ``blend_rank_stride`` elements and, with several ranks, does ONE MORE
+    all-gather, of those slots -- only when asked; the canvas still comes from the cropped exchange, bit for bit."""
+
+    def __init__(self, plan, channels, device, group=None, gt=None, blend=False, window="triangle", disagreement=False,
+                 seam_band=8):
         self.plan, self.C, self.group, self.gt = plan, int(channels), group, gt
         self.rank, self.world = parallel.rank(), parallel.world_size()
-        self.canvas = self.part = self.flat = None
+        self.canvas = self.part = self.flat = self.whole = self.disagreement = None
         self.blend = bool(blend)
+        self.measure, self.seam_band = _check_disagreement("TileExchange", disagreement, seam_band, self.C), int(seam_band)
+        if self.measure and not self.blend:
+            self.whole = torch.zeros(plan.blend_rank_stride(self.world, self.C), dtype=torch.float32, device=device)
         if self.blend:
             plan.set_window(window)
             self.flat = torch.zeros(plan.blend_rank_stride(self.world, self.C), dtype=torch.float32, device=device)
@@ -37,6 +47,9 @@ class TileExchange:
         """``tiles`` (b, C, p, p): predictions of this rank's tile ids ``ids`` (a batch of its shard, in order)."""
         if len(ids) == 0:
             return
+        if self.whole is not None:
+            j = int(ids[0]) // self.world
+            self.whole.view((-1, self.C) + self.plan.patch_shape[1:])[j:j + len(ids)].copy_(tiles)
         if self.blend:
             j = int(ids[0]) // self.world
             self.tiles[j:j + len(ids)].copy_(tiles)
@@ -56,13 +69,23 @@ class TileExchange:
         """-> canvas (N,H,W,C), or (canvas, psnr (N,C)) when a ground truth was given."""
         if self.blend:
             if self.world == 1:
+                self._measure(self.tiles)
                 return self.plan.blend(self.tiles, gt=self.gt)
             full = parallel.all_gather_flat(self.flat, self.group)   # one collective per canvas, of whole tiles
+            self._measure(full)
             return self.plan.blend(full, world=self.world, gt=self.gt, Cn=self.C)
+        if self.whole is not None:                                    # crop: the whole tiles travel only for the measure
+            self._measure(self.whole.view((-1, self.C) + self.plan.patch_shape[1:]) if self.world == 1 else
+                          parallel.all_gather_flat(self.whole, self.group))
         if self.world == 1:
             return self.canvas if self.gt is None else (self.canvas, self.plan.psnr_from_partials(self.part))
         full = parallel.all_gather_flat(self.flat, self.group)       # the path's only collective
         return self.plan.paste_packed(full, self.C, self.world, self.gt)
+
+    def _measure(self, tiles):
+        if self.measure:
+            self.disagreement = self.plan.disagreement(tiles, world=self.world, Cn=self.C, band=self.seam_band,
+                                                       want_map=self.measure is True)
 
 
 def _batches(ids, batch):
@@ -90,6 +113,49 @@ def _check_stitch(what, stitch, window):
         raise DsxError(f"{what}: stitch = {stitch!r}: 'crop' or 'blend'")
     if stitch == "blend" and isinstance(window, str) and window not in WINDOWS:
         raise DsxError(f"{what}: window = {window!r}: one of {', '.join(WINDOWS)}, or a pair of arrays (wy, wx)")
+
+
+def _check_disagreement(what, disagreement, seam_band, channels=None):
+    """-> False, "sums" or True: what ``disagreement=`` asks for; the refusals that need no launch"""
+    if disagreement is None or disagreement is False:
+        return False
+    if disagreement is not True and disagreement != "sums":
+        raise DsxError(f"{what}: disagreement = {disagreement!r}: False, 'sums' or True")
+    if isinstance(seam_band, bool) or int(seam_band) != seam_band or not 1 <= int(seam_band) <= 65535:
+        raise DsxError(f"{what}: seam_band = {seam_band!r}: an integer in 1..65535")
+    if channels is not None and not 1 <= int(channels) <= PSNR_MAX_CHANNELS:
+        raise DsxError(f"{what}: disagreement: {int(channels)} prediction channels, the measure takes 1..{PSNR_MAX_CHANNELS}")
+    return disagreement
+
+
+def _check_frame_map(what, path, disagreement, samples):
+    if disagreement is True and samples > 1:
+        raise DsxError(f"{what}: disagreement=True on {path} with samples = {samples}: the x0 tiles of every posterior "
+                       "sample have a map of their own; give disagreement='sums', or samples=1")
+
+
+class FrameDisagreement:
+    """The measure on the frame-state paths: ``child`` takes the x0 tiles of a sampler's last row (one call per child of
+    a joint sampler, joined along the channels), ``end_sample`` closes a posterior sample: counts and sums are added
+    in sample order, min / max folded (``fold_disagreement``).  A map is kept for a single sample only."""
+
+    def __init__(self, plan, mode, band):
+        self.plan, self.mode, self.band, self.parts, self.total, self.samples = plan, mode, int(band), [], None, 0
+
+    def child(self, tiles, world, Cn):
+        self.parts.append(self.plan.disagreement(tiles, world=world, Cn=Cn, band=self.band, want_map=self.mode is True))
+
+    def end_sample(self):
+        from .tiling import fold_disagreement
+        parts, self.parts = self.parts, []
+        one = parts[0] if len(parts) == 1 else {
+            k: None if parts[0][k] is None else torch.cat([p[k] for p in parts], dim={"map": -1, "partials": 2}.get(k, 1))
+            for k in parts[0]}
+        self.total = one if self.samples == 0 else fold_disagreement(self.total, one)   # the fold carries no map
+        self.samples += 1
+
+    def result(self):
+        return None if self.total is None else dict(self.total, map=self.total.get("map"))
 
 
 def _check_samples(what, samples, error):
@@ -270,7 +336,7 @@ def _stochastic_rows(netG, num_timesteps, solver):
 @torch.no_grad()
 def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None,
                   solver=None, noise="samples", field_noise_bytes=2 << 30, stitch=None, window="triangle", fuse=False,
-                  quantiles=None, ranks=False, quantile_bytes=8 << 30):
+                  quantiles=None, ranks=False, quantile_bytes=8 << 30, disagreement=False, seam_band=8):
     """The tiled prediction of a dataset that cuts its own normalised tiles -- an ``InputStackTiledPred`` (one
     superimposed acquisition, no ground truth) or a ``SplitDatasetTiledPred`` -- with ``samples`` posterior samples per
     tile: their mean and, with ``return_std``, the unbiased per-pixel spread, accumulated by one fused launch per sample
@@ -314,9 +380,19 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     PER-TILE QUANTILES -- not the quantile of blended samples --, and ``ranks=True`` is refused: a blend of ranks is not a
     rank.  With ``fuse=True`` a draw is the whole frame state, quantiles and ranks are exact per pixel, and the
     ``samples`` states are kept: more than ``quantile_bytes`` of them is refused.  ``ranks=True`` needs a dataset whose
-    ground truth has the prediction's channels.  Without either argument nothing changes."""
+    ground truth has the prediction's channels.  Without either argument nothing changes.
+
+    ``disagreement=True`` (or ``"sums"``: no map) adds ``out['disagreement']``, the dict of ``TilePlan.disagreement`` with
+    ``band = seam_band``: how far the tiles that predicted a pixel differ, over every overlap and over the band around
+    the crop lines -- a quality signal that needs no ground truth.  It measures the tiles the 'mean' exchange receives:
+    with ``samples = N`` the per-tile means of N samples (independent per-tile streams alone make those differ by about
+    ``std * sqrt(2 / N)`` pairwise).  Under ``stitch="crop"`` with several ranks the whole tiles take one more all-gather;
+    'mean', 'std' and 'psnr' keep their bits either way.  With ``fuse=True`` the x tiles of the last solver row are
+    measured, before their blend, per posterior sample: counts and sums are added in sample order, min / max folded, and
+    a map needs ``samples == 1``.  At most 4 prediction channels."""
     samples = _check_samples("predict_stack", samples, ValueError)
     plan = dataset.plan
+    measure = _check_disagreement("predict_stack", disagreement, seam_band, netG.prediction_channels if disagreement else None)
     _check_solver("predict_stack", netG, solver)
     if noise not in ("samples", "field"):
         raise DsxError(f"predict_stack: noise = {noise!r}: 'samples' or 'field'")
@@ -345,7 +421,9 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
         _check_field_ids("predict_stack", samples, plan.data_shape[0])
         if q is not None or ranks:
             _check_quantile_bytes("predict_stack", samples, plan, netG.prediction_channels, quantile_bytes)
-        return _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q, ranks), plan
+        _check_frame_map("predict_stack", "fuse=True", measure, samples)
+        return _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q, ranks,
+                                    FrameDisagreement(plan, measure, seam_band) if measure else None), plan
     if field:
         if seed is None:
             raise DsxError("predict_stack: noise='field' needs seed=: a noise field is named by (seed, frame, draw)")
@@ -363,7 +441,8 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     ids = parallel.shard_ids(plan.total, parallel.rank(), parallel.world_size())
     # a rank without tiles still joins the collectives, on the device it is bound to
     dev = dataset.device if len(ids) else torch.device("cuda", torch.cuda.current_device())
-    ex = TileExchange(plan, C_out, dev, group, gt=gt, blend=blend, window=window)
+    ex = TileExchange(plan, C_out, dev, group, gt=gt, blend=blend, window=window, disagreement=measure,
+                      seam_band=seam_band)
     ex_std = TileExchange(plan, C_out, dev, group, blend=blend, window=window) if return_std else None
     ex_q = [TileExchange(plan, C_out, dev, group, blend=blend, window=window) for _ in q or ()]
     ex_rank = TileExchange(plan, C_out, dev, group) if ranks else None
@@ -414,4 +493,6 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
         out["quantiles"] = torch.stack([e.finish() for e in ex_q])
     if ranks:
         out["rank"] = ex_rank.finish()
+    if measure:
+        out["disagreement"] = ex.disagreement
     return out, plan

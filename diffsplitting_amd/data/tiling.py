@@ -62,6 +62,33 @@ def window(name, n):
     raise DsxError(f"window: {name!r} is not a window; one of {', '.join(WINDOWS)}")
 
 
+def _rms_pair(sum_var, count):
+    """sqrt(2 * sum_var / count): the RMS difference over all pairs of contributors; NaN where the count is 0"""
+    return torch.where(count > 0, torch.sqrt(2.0 * sum_var / count.to(torch.float64)),
+                       torch.full_like(sum_var, float("nan")))
+
+
+def disagreement_from_partials(part):
+    """The rows of ``dsx_tileplan_disagreement``, (N, blocks, C, 8) float64, folded over the workgroups the way
+    ``TilePlan.psnr_from_partials`` folds its rows -> ``count`` (N,C,2) int64, ``sum_var`` (N,C,2), ``min_var`` and
+    ``max_var`` (N,C), ``rms_pair`` (N,C,2); index 0 of the pairs is the overlap (two or more contributors), 1 the band."""
+    s = part[..., :4].sum(dim=1)                                     # fixed order: reproducible
+    count = s[..., 0::2].round().to(torch.int64)
+    sum_var = s[..., 1::2].contiguous()
+    return dict(count=count, sum_var=sum_var, min_var=part[..., 4].amin(dim=1), max_var=part[..., 5].amax(dim=1),
+                rms_pair=_rms_pair(sum_var, count))
+
+
+def fold_disagreement(a, b):
+    """The scores of two measurements of one plan (two posterior samples) as one: counts and sums added, ``a`` first,
+    min / max folded, ``rms_pair`` from the totals; maps and rows are not carried.  ``a`` None: ``b``'s scores."""
+    if a is None:
+        return {k: b[k] for k in ("count", "sum_var", "min_var", "max_var", "rms_pair")}
+    count, sum_var = a["count"] + b["count"], a["sum_var"] + b["sum_var"]
+    return dict(count=count, sum_var=sum_var, min_var=torch.minimum(a["min_var"], b["min_var"]),
+                max_var=torch.maximum(a["max_var"], b["max_var"]), rms_pair=_rms_pair(sum_var, count))
+
+
 class TilePlan:
     """All tiles of data (N,H,W) for a (1,g,g) grid and (1,p,p) patches —
     what ``SplitDatasetTiledPred.__init__`` sets up (split_dataset_tiledpred.py:9-24).
@@ -384,6 +411,45 @@ class TilePlan:
                                           float(sigma), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(id_base),
                                           C.c_uint32(draw), None))
         return state
+
+    # ---- tile disagreement: how far the tiles that predicted a pixel differ (dsx_tileplan_disagreement) -------------
+    def crop_lines(self, band=8):
+        """Host only: (rows (H,), cols (W,)) uint8 -- 1 where the canvas row / column is NEAR A CROP LINE: some line L,
+        the first row / column owned by another tile row / column of ``regions`` than the one before it, has
+        ``L - band <= v < L + band``."""
+        rows = np.zeros(self.data_shape[1], dtype=np.uint8)
+        cols = np.zeros(self.data_shape[2], dtype=np.uint8)
+        check(lib.dsx_tileplan_crop_lines(self.handle, int(band), rows, cols))
+        return rows, cols
+
+    def disagreement(self, tiles, world=1, Cn=None, band=8, want_map=True, out=None):
+        """How far the tiles that cover a canvas pixel differ (contract: include/dsx.h, dsx_tileplan_disagreement):
+        per pixel and channel the unbiased variance ``var`` among its contributors, in ascending tile id, Welford in
+        double.  ``tiles``, ``world`` and ``Cn`` as in ``blend`` (no window is needed); C <= 4.  ``want_map``: also
+        ``s = float32(sqrt(var))`` per pixel, written into ``out`` (a contiguous float32 CUDA tensor of (N,H,W,C)) if one
+        is given.  -> dict:
+
+        ``map`` (N,H,W,C) float32 or None; ``count`` (N,C,2) int64: pixels with two or more contributors, and those of
+        them IN THE BAND (their row or column near a crop line, ``crop_lines(band)``); ``sum_var`` (N,C,2) float64 over
+        the same two sets; ``min_var``, ``max_var`` (N,C) over the first; ``rms_pair`` (N,C,2) =
+        ``sqrt(2 * sum_var / count)``, the RMS difference over all pairs of contributors, NaN where the count is 0;
+        ``partials`` (N, blend_blocks, C, 8) float64, the kernel's rows.  Everything on the device."""
+        _lib.require_gpu()
+        world, band = int(world), int(band)
+        tiles, Cn, stride = self._whole_tiles("disagreement", tiles, world, Cn)
+        if not 1 <= Cn <= PSNR_MAX_CHANNELS:
+            raise DsxError(f"disagreement: C = {Cn}, must be in 1..{PSNR_MAX_CHANNELS}")
+        shape = self.data_shape + (Cn,)
+        if out is not None and not want_map:
+            raise DsxError("disagreement: out= is the map; it needs want_map=True")
+        if out is not None and (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or
+                                not out.is_contiguous() or tuple(out.shape) != shape):
+            raise DsxError(f"disagreement: out must be a contiguous float32 CUDA tensor of shape {shape}")
+        smap = out if out is not None else \
+            torch.empty(shape, dtype=torch.float32, device=tiles.device) if want_map else None
+        part = torch.empty((self.data_shape[0], self.blend_blocks(), Cn, 8), dtype=torch.float64, device=tiles.device)
+        check(lib.dsx_tileplan_disagreement(self.handle, tiles, Cn, world, stride, band, smap, part, None))
+        return dict(disagreement_from_partials(part), map=smap, partials=part)
 
     def gather_canvas(self, canvas, tile_ids=None):
         """The tiles ``tile_ids`` cut out of a multi-channel frame state ``canvas`` (N,H,W,C) fp32 CUDA -> (count, C, ph,

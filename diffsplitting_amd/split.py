@@ -74,6 +74,13 @@ Q * N * C pages as .tif; with ``--stitch blend`` outside the frame-state paths a
 ``--rank-histogram FILE.json`` (with a ground truth) counts per channel the rank of the ground truth among the samples of
 every pixel (``core.calibration.rank_histogram``): uniform counts mean calibrated bands, whatever the posterior's shape;
 rank 0 logs the observed against the nominal coverage of the widest central band and of the one nearest 50 %.
+
+``--seam-report FILE.json [--seam-map FILE.npy|.tif] [--seam-band B]`` measures how far the predicted tiles disagree where
+they overlap (``predict_stack(disagreement=)``, ``TilePlan.disagreement``; no ground truth needed): per channel the RMS
+pairwise difference over every overlap and over the band of B pixels (default 8) around the crop lines, and the largest
+per-pixel spread, in normalised units and in raw counts; ``--seam-map`` writes the per-pixel spread among the tiles in raw
+counts, laid out as ``--std-out``.  It measures the per-tile means of the ``--samples``, or with ``--fuse-steps`` /
+``--frame-steps`` the x0 tiles of the last row (``--seam-map`` then needs ``--samples 1``).
 """
 import argparse
 import functools
@@ -300,8 +307,17 @@ def main(argv=None):
     ap.add_argument("--rank-histogram", type=str, default=None,
                     help="with --samples N >= 2 and ground truth: count the rank of the ground truth among the samples per "
                          "pixel (core.calibration.rank_histogram) and write histogram and band coverage to this .json file")
+    ap.add_argument("--seam-report", type=str, default=None,
+                    help="measure how far the predicted tiles disagree where they overlap (TilePlan.disagreement; needs no "
+                         "ground truth) and write the scores to this .json file")
+    ap.add_argument("--seam-map", type=str, default=None,
+                    help="with --seam-report: write the per-pixel disagreement s in raw counts (.npy / .tif), laid out as "
+                         "--std-out")
+    ap.add_argument("--seam-band", type=int, default=None,
+                    help="with --seam-report: half-width in pixels of the band around the crop lines (default 8)")
     args = ap.parse_args(argv)
     config = _config_once(args.config)
+    _check_seam_args(args, config)
     _check_msssim_args(args, config)
     _check_calibration_args(args, config)
     _check_quantile_args(args, config)
@@ -444,12 +460,14 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
         from .data.tiled_predict import predict_stack_frames
         out, plan = predict_stack_frames(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps,
                                          samples=samples, return_std=bool(args.std_out or args.calibration),
-                                         seed=args.sample_seed, window=args.window or "triangle", **_quantile_kwargs(args))
+                                         seed=args.sample_seed, window=args.window or "triangle", **_quantile_kwargs(args),
+                                         **_seam_kwargs(args))
     else:
         out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
                                   return_std=bool(args.std_out or args.calibration), seed=args.sample_seed, solver=solver,
                                   noise="field" if args.noise_field else "samples", stitch=args.stitch,
-                                  window=args.window or "triangle", fuse=args.fuse_steps, **_quantile_kwargs(args))
+                                  window=args.window or "triangle", fuse=args.fuse_steps, **_quantile_kwargs(args),
+                                  **_seam_kwargs(args))
     pred, ps = out["mean"], out.get("psnr")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -480,7 +498,82 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
             _write_quantiles(args.quantile_out, out["quantiles"], _parse_quantiles(args.quantiles), val_set)
             log.info("quantiles %s over %d samples written to %s", args.quantiles, samples, args.quantile_out)
         _log_rank_histogram(args, out.get("rank"), samples, log)
+        _write_seam_report(args, out.get("disagreement"), val_set, plan, patch, samples, log)
     return pred
+
+
+# ---- --seam-report: how far the predicted tiles disagree where they overlap ---------------------------------------
+def _check_seam_args(args, config):
+    """``--seam-report`` / ``--seam-map`` / ``--seam-band``, checked on the command line and the config alone (nothing
+    touches the GPU, no rank is started).  Without them: nothing."""
+    if not args.seam_report:
+        for flag, value in (("--seam-map", args.seam_map), ("--seam-band", args.seam_band)):
+            if value is not None:
+                raise SystemExit(f"{flag}: only with --seam-report FILE.json")
+        return
+    if not args.seam_report.endswith(".json"):
+        raise SystemExit(f"--seam-report {args.seam_report}: a .json file")
+    if args.seam_map and not args.seam_map.endswith((".npy", ".tif", ".tiff")):
+        raise SystemExit(f"--seam-map {args.seam_map}: a .npy or .tif file")
+    if args.seam_band is not None and not 1 <= args.seam_band <= 65535:
+        raise SystemExit(f"--seam-band {args.seam_band}: 1..65535 pixels")
+    if args.validate:
+        raise SystemExit("--seam-report measures the tiles of a tiled prediction: not with --validate")
+    if args.mix_t is not None:
+        raise SystemExit("--seam-report: not with --mix-t; the measure is not built for the mixed-input prediction")
+    if args.datapath and _data_type(config()[1], args.norm_from) == "cifar10":
+        raise SystemExit("--seam-report measures the tiles of a tiled prediction: the colour items of a cifar10 config are "
+                         "not tiled")
+    if args.seam_map and (args.fuse_steps or args.frame_steps) and (args.samples or 1) > 1:
+        raise SystemExit(f"--seam-map with {'--fuse-steps' if args.fuse_steps else '--frame-steps'} and --samples "
+                         f"{args.samples}: the x0 tiles of every posterior sample have a map of their own; give --samples 1 "
+                         "or leave --seam-map out")
+
+
+def _seam_kwargs(args):
+    """What ``--seam-report`` adds to the driver's call: nothing without it."""
+    if not args.seam_report:
+        return {}
+    return dict(disagreement=True if args.seam_map else "sums", seam_band=args.seam_band or 8)
+
+
+def _write_seam_report(args, dis, val_set, plan, patch, samples, log):
+    """``--seam-report``: the scores per channel over all frames, each once in normalised units and once in raw counts
+    (scaled by std_target, as --std-out scales its spread; a variance by its square); zero counts give null.
+    ``--seam-map``: s in raw counts."""
+    if not args.seam_report:
+        return
+    import json
+    count = dis["count"].sum(dim=0).cpu().numpy()                       # (C, 2): over all frames
+    sum_var = dis["sum_var"].sum(dim=0).cpu().numpy()
+    max_var = dis["max_var"].amax(dim=0).cpu().numpy()
+    C_out = count.shape[0]
+    _, std = _target_stats(val_set, C_out)
+    frame_state = bool(args.fuse_steps or args.frame_steps)
+    both = lambda v, scale: None if v is None else {"normalised": float(v), "raw": float(v * scale)}
+    rms = lambda c, j: float(np.sqrt(2.0 * sum_var[c, j] / count[c, j])) if count[c, j] > 0 else None
+    channels = []
+    for c in range(C_out):
+        largest = float(np.float32(np.sqrt(max_var[c]))) if count[c, 0] > 0 else None
+        channels.append({"channel": c, "overlap_pixels": int(count[c, 0]), "band_pixels": int(count[c, 1]),
+                         "rms_pair_overlap": both(rms(c, 0), std[c]), "rms_pair_band": both(rms(c, 1), std[c]),
+                         "largest_s": both(largest, std[c])})
+        log.info("channel %d: tiles disagree by %s RMS over the overlap, %s within %d pixels of a crop line (raw counts)",
+                 c, *("%.4g" % (v * std[c]) if v is not None else "n/a" for v in (rms(c, 0), rms(c, 1))),
+                 args.seam_band or 8)
+    report = {"band": int(args.seam_band or 8),
+              "stitch": "blend" if (args.stitch == "blend" or frame_state) else "crop",
+              "tiles": int(plan.total), "patch": int(patch), "grid": int(plan.grid_shape[1]), "samples": int(samples),
+              "frames": [int(v) for v in plan.data_shape],
+              "measured": "x0 tiles of the last row" if frame_state else f"per-tile mean of {samples} samples",
+              "rms_pair": "sqrt(2 * mean(var)): the RMS difference over all pairs of tiles that predicted a pixel",
+              "channels": channels}
+    with open(args.seam_report, "w") as f:
+        json.dump(report, f, indent=1)
+    log.info("seam report written to %s", args.seam_report)
+    if args.seam_map:
+        _write_prediction(args.seam_map, dis["map"], val_set, spread=True)
+        log.info("disagreement map written to %s", args.seam_map)
 
 
 def _check_msssim_args(args, config):

@@ -862,6 +862,35 @@ int dsx_tileplan_gather_canvas(dsx_tileplan* plan, const float* canvas_dev, int 
 int dsx_tileplan_blend_step(dsx_tileplan* plan, const float* x0_tiles_dev, int C, int world, int64_t rank_stride_elems,
                             float* state_dev, float c_x0, float c_xt, float sigma, uint64_t seed, uint64_t id_base,
                             uint32_t draw, void* stream);
+/* Tile disagreement: how far the tiles that predicted a canvas pixel differ -- what a blend hides and a crop-paste
+ * switches between.  It needs no ground truth.  The plan must cover its frames with one frame per tile
+ * (dsx_tileplan_blend's condition; no window is needed).  For canvas pixel (n, y, x) and channel c let v_1 .. v_k be its
+ * contributors in ASCENDING TILE ID.  In double, every operation rounded on its own (no fma) -- the recurrence of
+ * dsx_moments_update / dsx_moments_finish:
+ *     mean = v_1; M2 = 0
+ *     for r = 1 .. k-1:   d = v_{r+1} - mean;  mean = mean + d / (r + 1);  M2 = M2 + d * (v_{r+1} - mean)
+ *     var = k > 1 ? M2 / (k - 1) : 0          s = (float)sqrt(var)
+ * var is the unbiased variance among the tiles that predicted the pixel; 2 var is the mean squared difference over all
+ * pairs of contributors, so sqrt(2 * mean(var)) is an RMS pairwise difference.
+ *   Crop lines.  The plan's clipped paste regions (dsx_tileplan_regions) partition every frame.  A canvas column x >= 1 is
+ *   a crop line if the tile column that owns x differs from the one that owns x - 1; rows alike.  With half-width `band`
+ *   (1..65535) column x is NEAR A LINE if some crop line L has L - band <= x < L + band; rows alike.  A pixel is IN THE
+ *   BAND if k >= 2 and its column or its row is near a line: where a crop-pasted frame switches from one tile to another.
+ *   dsx_tileplan_crop_lines: host only; rows [H] and cols [W] = 1 where the row / column is near a line, else 0.
+ *   dsx_tileplan_disagreement: tiles_dev in one of dsx_tileplan_blend's two layouts.  map_dev (N,H,W,C) receives s, or is
+ *     NULL.  partials_dev [N][dsx_tileplan_blend_blocks][C][8] receives per (frame, workgroup, channel), through the
+ *     fixed-order block reduction, over the workgroup's pixels:
+ *         0  count of pixels with k >= 2 (exact)        1  sum of var over those pixels
+ *         2  count of band pixels (exact)               3  sum of var over band pixels
+ *         4 / 5  min / max of var over pixels with k >= 2; +inf / -inf if none        6, 7  0
+ *     A gather like the blend: no atomics, nothing accumulated across launches, equal inputs give equal bits, and the
+ *     result depends on the tiles alone, not on their layout.  The masks of a band go up at the first call that names
+ *     it and stay with the plan: no allocation, copy or synchronisation per call after that.
+ *     Everything dsx_tileplan_blend refuses except a missing window, null tiles or partials, C outside 1..4 and band
+ *     outside 1..65535 are DSX_ERR_INVALID before any HIP call. */
+int dsx_tileplan_crop_lines(const dsx_tileplan* plan, int band, uint8_t* rows /*[H]*/, uint8_t* cols /*[W]*/);
+int dsx_tileplan_disagreement(dsx_tileplan* plan, const float* tiles_dev, int C, int world, int64_t rank_stride_elems,
+                              int band, float* map_dev, double* partials_dev, void* stream);
 
 /* ------------------------------------------------- frame files: uncompressed TIFF / BigTIFF stacks (host only)
  * Replaces imread(fpath, plugin='tifffile') of the Hagen loaders (data/split_dataset.py:76-91) for the files the
