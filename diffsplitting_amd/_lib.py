@@ -211,6 +211,9 @@ SIGNATURES = {
     "dsx_calibration_blocks": (_i, [_i64]),
     "dsx_calibration": (_i, [_Df, _Df, _Df, _i64, _i, _H, _i, _H, _i, _Dd, _Dd, _st]),
     "dsx_sample_quantiles": (_i, [_Df, _i64, _i, _i64, _H, _i, _Df, _Df, _Df, _st]),
+    "dsx_consistency_blocks": (_i, [_i64]),
+    "dsx_consistency": (_i, [_Dv, _i, _Df, _Df, _i64, _i64, _i, _H, _H, _H, C.c_double, C.c_double, _Df, _Df, _Df, _Dd, _Dd,
+                             _st]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -9,7 +9,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $DS
 mkdir -p $OBJ
 # every source of the library: kernels (*.hip) and host translation units (*.cpp, compiled as HIP too); the longest
 # compile first
-SRCS="dsx_conv_mfma.hip dsx_conv_ws.hip dsx_conv_img.hip dsx_conv_direct.hip dsx_conv.hip dsx_ops.hip dsx_attn.hip dsx_lpips.hip dsx_resize.hip dsx_tiles.hip dsx_eval.hip dsx_msssim.hip dsx_steps.hip dsx_validate.hip dsx_select.hip dsx_refine.hip dsx_calib.hip dsx_quantiles.hip dsx_model.cpp dsx_plan.cpp dsx_exec.cpp dsx_tiles.cpp dsx_eval.cpp dsx_lpips.cpp dsx_resize.cpp dsx_select.cpp dsx_refine.cpp dsx_calib.cpp dsx_quantiles.cpp dsx_tiff.cpp"
+SRCS="dsx_conv_mfma.hip dsx_conv_ws.hip dsx_conv_img.hip dsx_conv_direct.hip dsx_conv.hip dsx_ops.hip dsx_attn.hip dsx_lpips.hip dsx_resize.hip dsx_tiles.hip dsx_eval.hip dsx_msssim.hip dsx_steps.hip dsx_validate.hip dsx_select.hip dsx_refine.hip dsx_calib.hip dsx_quantiles.hip dsx_consistency.hip dsx_model.cpp dsx_plan.cpp dsx_exec.cpp dsx_tiles.cpp dsx_eval.cpp dsx_lpips.cpp dsx_resize.cpp dsx_select.cpp dsx_refine.cpp dsx_calib.cpp dsx_quantiles.cpp dsx_consistency.cpp dsx_tiff.cpp"
 # a changed flag set rebuilds everything
 if [ "$(cat $OBJ/.flags 2>/dev/null)" != "$FLAGS" ]; then rm -f $OBJ/*.o; echo "$FLAGS" > $OBJ/.flags; fi
 stale() {   # stale OBJECT FILE...: the object is missing or older than one of the files

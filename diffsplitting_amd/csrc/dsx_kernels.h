@@ -853,6 +853,27 @@ constexpr int quantiles_wires(int n) { return n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ?
 constexpr int quantiles_per_thread(int wires) { return wires <= 32 ? 4 : 2; }
 hipError_t launch_quantiles(const QuantArgs& a, bool wide, hipStream_t st);
 
+// dsx_consistency.hip.  The residual of a split against its acquisition, x - sum_c w_c p_c, its per-frame report row
+// and the Gaussian conditioning of (mean, std) on it (include/dsx.h, dsx_consistency): one pass over `frames` frames
+// of `plane` pixels, two launches on `st` (one without a report), nothing synchronised.  in: (frames, plane) of pix
+// (DSX_PIX_U8 / U16 / F32); mean, sd, omean, osd: (frames, plane, C) fp32; map: (frames, plane); sd, map, omean, osd,
+// out may be null, part only with out.  part[frames][consistency_blocks(plane)][kConSlots]; out[frames][kConSlots].
+// vec: four pixels per thread with 16-byte loads and stores of the fp32 operands and one 4 / 8 / 16-byte load of the
+// input (every base that aligned and plane % 4 == 0: the caller's check).
+constexpr int kConMaxC = 4, kConSlots = 10;
+struct ConArgs {
+  const void* in; const float* mean; const float* sd;
+  float* map; float* omean; float* osd;
+  double* part; double* out;
+  long long plane, span;   // span = consistency_span(plane): pixels per workgroup, a multiple of 4
+  int pix, C;
+  double a[kConMaxC], b[kConMaxC], w[kConMaxC];
+  double clip, noise_var;
+};
+int consistency_blocks(long long plane);
+long long consistency_span(long long plane);
+hipError_t launch_consistency(const ConArgs& a, int frames, bool vec, hipStream_t st);
+
 // dsx_select.hip.  One pass of the radix select behind dsx_order_stats: hist[1 << bits] (64-bit, zeroed by the caller)
 // += the digit (u >> shift) & (2^bits - 1) of every element whose key image u has u >> match_shift == prefix
 // (match_shift = 64: every element).  b == nullptr: single source.

@@ -17,6 +17,9 @@
 //   RedRow<5, 2>  PsnrSums + min / max of p: k_msssim_stats per chunk, k_msssim_coef over a plane's chunk rows
 //   RedRow<4, 1>  k_tile_disagreement (dsx_tiles.hip), once per channel: two pixel counts, two sums of var, min / max of var
 //   RedRow<9, 1>  k_comoments_partial (dsx_refine.hip): nine sums of shifted data, min / max of g
+//   RedRow<8, 1>  k_consistency_partial (dsx_consistency.hip): two pixel counts, sums of r, r^2, x, x^2 over the
+//                 unsaturated pixels, the count and the sum of r^2 / den where den > 0, min / max of r;
+//                 k_consistency_finish folds a frame's workgroup rows as k_comoments_finish does
 // k_comoments_finish then folds a plane's workgroup rows with ONE wave: lane l adds the rows l, l + 64, .. in ascending
 // order, wave_reduce (kDown) folds the lanes.
 // k_calib_partial (dsx_calib.hip) reduces no lanes with a butterfly: a bin's terms meet in the wave's row of LDS in

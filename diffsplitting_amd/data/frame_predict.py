@@ -6,7 +6,7 @@ import torch
 
 from .. import parallel
 from .._lib import DsxError
-from .tile_predict import (FrameDisagreement, _batches, _check_disagreement, _check_field_ids, _check_frame_map, _check_quantile_bytes, _check_quantiles, _check_rank_gt,
+from .tile_predict import (FrameDisagreement, _apply_consistency, _batches, _check_consistency, _check_disagreement, _check_field_ids, _check_frame_map, _check_quantile_bytes, _check_quantiles, _check_rank_gt,
                            _check_samples, _check_stitch, _is_gaussian, _mean_and_spread, _mean_spread_quantiles,
                            _scorable_gt, store_kept)
 
@@ -173,7 +173,8 @@ def frame_sample(child, dataset, x_in, num_timesteps, t_float_start, batch_tiles
 @torch.no_grad()
 def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_float_start=None, samples=1,
                          return_std=False, seed=None, group=None, window="triangle", quantiles=None, ranks=False,
-                         quantile_bytes=8 << 30, disagreement=False, seam_band=8):
+                         quantile_bytes=8 << 30, disagreement=False, seam_band=8, consistency=False,
+                         consistency_noise=0.0, consistency_weights=None):
     """``predict_stack`` for the InDI family (``InDISampler`` and its subclasses, ``JointIndiSampler``) with every frame
     diffused as ONE state: frame diffusion.  The InDI update ``x <- (d/t) x0 + (1 - d/t) x + e (t - d) z`` is affine in
     the UNet output with coefficients shared by the batch, so a row of a frame is ``X <- c_x0 * blend(x0 tiles) +
@@ -194,7 +195,10 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
 
     ``disagreement=True`` / ``"sums"`` with ``seam_band``: ``out['disagreement']`` as ``predict_stack`` describes it, of
     the x0 tiles of the last row before their blend (a joint sampler's two children joined along the channels), per
-    posterior sample: counts and sums are added in sample order, min / max folded; a map needs ``samples == 1``."""
+    posterior sample: counts and sums are added in sample order, min / max folded; a map needs ``samples == 1``.
+
+    ``consistency=`` / ``consistency_noise=`` / ``consistency_weights=``: as ``predict_stack`` describes them, through the
+    same helper on the finished canvases."""
     from ..model.samplers import InDISampler, JointIndiSampler
     what = "predict_stack_frames"
     if _is_gaussian(netG):
@@ -222,6 +226,8 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
     q, ranks = _check_quantiles(what, samples, quantiles, ranks, dataset)
     if q is not None or ranks:
         _check_quantile_bytes(what, samples, plan, netG.prediction_channels, quantile_bytes)
+    cons = _check_consistency(what, consistency, consistency_noise, consistency_weights, dataset, netG.prediction_channels,
+                              q, ranks)
     plan.set_window(window)
     x_in = input_frames(dataset, batch_tiles)
 
@@ -234,4 +240,4 @@ def predict_stack_frames(netG, dataset, batch_tiles=8, num_timesteps=None, t_flo
     out = _frame_outputs(netG, dataset, samples, return_std, draw, q, ranks)
     if measure is not None:
         out["disagreement"] = measure.result()
-    return out, plan
+    return _apply_consistency(out, dataset, cons), plan

@@ -90,6 +90,11 @@ class InputStackTiledPred:
         """Device bytes the stack occupies (its file width: half of an fp32 copy for uint16, a quarter for uint8)."""
         return self._dev.numel() * self._dev.element_size()
 
+    def acquisition(self):
+        """What the data-consistency check (core/consistency.py) needs of the stack: ``(the resident bytes, their pixel
+        type _lib.PIX_*, the (N,H,W) shape, input_clip or None)``.  Nothing is copied."""
+        return self._dev, self._pix, self._data_shape, self._input_clip
+
     def _gather_seq(self, seq, out):
         first, stride, count = seq
         for k0 in range(0, count, ITEMS_PER_CALL):

@@ -248,6 +248,54 @@ def _check_quantile_bytes(what, samples, plan, channels, quantile_bytes):
                        "quantile_bytes")
 
 
+def _check_consistency(what, consistency, noise, weights, dataset, channels, q=None, ranks=False):
+    """The refusals of ``consistency=`` that need no launch -> None (not asked for) or the checked
+    ``(project, rho, weights)``.  The arguments that go with it are refused without it."""
+    if consistency is False or consistency is None:
+        if noise or weights is not None:
+            raise DsxError(f"{what}: consistency_noise= / consistency_weights= without consistency=True or 'project'")
+        return None
+    if consistency is not True and consistency != "project":
+        raise DsxError(f"{what}: consistency = {consistency!r}: False, True (report) or 'project'")
+    from ..core.consistency import check_noise, check_weights
+    if not hasattr(dataset, "acquisition"):
+        raise DsxError(f"{what}: consistency= compares the prediction with the acquisition it was made from: "
+                       f"{type(dataset).__name__} does not expose one (an InputStackTiledPred does: its resident stack, "
+                       "pixel type and input_clip)")
+    if getattr(dataset, "_target_channel_idx", None) is not None:
+        raise DsxError(f"{what}: consistency= with target_channel_idx = {dataset._target_channel_idx}: the prediction "
+                       "holds one of the summands, the sum cannot be formed")
+    n_w = channels if weights is None else len(list(weights))
+    if n_w != channels:
+        raise DsxError(f"{what}: consistency=: {n_w} channel weights for a prediction of {channels} channels (a "
+                       "target_channel_idx config predicts one of the two summands: the sum cannot be formed)")
+    project = consistency == "project"
+    if project and (q is not None or ranks):
+        raise DsxError(f"{what}: consistency='project' with quantiles= / ranks=: quantile and rank maps are not "
+                       "projected; ask for them in a run of their own, or use consistency=True")
+    return project, check_noise(noise), check_weights(weights, channels)
+
+
+def _apply_consistency(out, dataset, checked):
+    """The shared post-processing of ``consistency=``, on the stitched canvases, on every rank (each holds the canvases
+    and the resident stack: no collective).  Adds ``out['consistency']``, the report of the prediction as it was made;
+    under 'project' the conditioned mean and spread replace ``out['mean']`` / ``out['std']`` and the unprojected mean
+    stays under ``out['mean_raw']``."""
+    if checked is None:
+        return out
+    from ..core.consistency import consistency as run
+    project, rho, w = checked
+    stack, pix, _, clip = dataset.acquisition()
+    rep = run(out["mean"], stack, dataset.get_normalization_dict(), weights=w, std=out.get("std"), clip=clip, noise=rho,
+              project=project, pix=pix)
+    if project:
+        out["mean_raw"], out["mean"] = out["mean"], rep.pop("mean")
+        if "std" in rep:
+            out["std"] = rep.pop("std")
+    out["consistency"] = rep
+    return out
+
+
 def _mean_spread_quantiles(samples, return_std, draw, buf, q, target):
     """``_mean_and_spread`` for ``samples >= 2`` that also keeps the draws: ``draw(r)`` is copied into ``buf[r]`` (the
     samplers reuse their output buffer), feeds the Welford launch from there, and one ``engine.sample_quantiles`` launch
@@ -336,7 +384,8 @@ def _stochastic_rows(netG, num_timesteps, solver):
 @torch.no_grad()
 def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, return_std=False, seed=None, group=None,
                   solver=None, noise="samples", field_noise_bytes=2 << 30, stitch=None, window="triangle", fuse=False,
-                  quantiles=None, ranks=False, quantile_bytes=8 << 30, disagreement=False, seam_band=8):
+                  quantiles=None, ranks=False, quantile_bytes=8 << 30, disagreement=False, seam_band=8,
+                  consistency=False, consistency_noise=0.0, consistency_weights=None):
     """The tiled prediction of a dataset that cuts its own normalised tiles -- an ``InputStackTiledPred`` (one
     superimposed acquisition, no ground truth) or a ``SplitDatasetTiledPred`` -- with ``samples`` posterior samples per
     tile: their mean and, with ``return_std``, the unbiased per-pixel spread, accumulated by one fused launch per sample
@@ -389,7 +438,18 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     ``std * sqrt(2 / N)`` pairwise).  Under ``stitch="crop"`` with several ranks the whole tiles take one more all-gather;
     'mean', 'std' and 'psnr' keep their bits either way.  With ``fuse=True`` the x tiles of the last solver row are
     measured, before their blend, per posterior sample: counts and sums are added in sample order, min / max folded, and
-    a map needs ``samples == 1``.  At most 4 prediction channels."""
+    a map needs ``samples == 1``.  At most 4 prediction channels.
+
+    ``consistency=True`` (an ``InputStackTiledPred``) adds ``out['consistency']``: how far the stitched mean is from adding
+    back up to the acquisition, ``r = x - sum_c w_c p_c`` in raw counts, per frame and in total
+    (``core.consistency.consistency``: rms, bias, relative residual, saturated pixels and, with ``return_std``, the
+    ``chi2`` of the spread), with ``consistency_weights`` (w_c, default ones) and ``consistency_noise`` (rho in counts).
+    ``consistency="project"`` also replaces ``out['mean']`` and, where present, ``out['std']`` by the posterior
+    conditioned on that observation, keeps the unprojected mean under ``out['mean_raw']`` and reports the residual before
+    the projection.  One pass over the stitched canvases on every rank, no collective: any number of ranks gives the
+    same bits.  Quantile and rank maps are NOT projected: asking for them together with "project" is refused.  Refused
+    too: a dataset that exposes no acquisition, a ``target_channel_idx`` prediction, weights of another length.
+    Without the argument nothing changes."""
     samples = _check_samples("predict_stack", samples, ValueError)
     plan = dataset.plan
     measure = _check_disagreement("predict_stack", disagreement, seam_band, netG.prediction_channels if disagreement else None)
@@ -416,14 +476,17 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
     _check_stitch("predict_stack", stitch, window)
     blend, field = stitch == "blend", noise == "field"
     q, ranks = _check_quantiles("predict_stack", samples, quantiles, ranks, dataset, blend=blend and not fuse)
+    cons = _check_consistency("predict_stack", consistency, consistency_noise, consistency_weights, dataset,
+                              netG.prediction_channels, q, ranks)
     if fuse:
         from .frame_predict import _predict_stack_fused
         _check_field_ids("predict_stack", samples, plan.data_shape[0])
         if q is not None or ranks:
             _check_quantile_bytes("predict_stack", samples, plan, netG.prediction_channels, quantile_bytes)
         _check_frame_map("predict_stack", "fuse=True", measure, samples)
-        return _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q, ranks,
-                                    FrameDisagreement(plan, measure, seam_band) if measure else None), plan
+        out = _predict_stack_fused(netG, dataset, batch_tiles, samples, return_std, seed, solver, window, q, ranks,
+                                   FrameDisagreement(plan, measure, seam_band) if measure else None)
+        return _apply_consistency(out, dataset, cons), plan
     if field:
         if seed is None:
             raise DsxError("predict_stack: noise='field' needs seed=: a noise field is named by (seed, frame, draw)")
@@ -495,4 +558,4 @@ def predict_stack(netG, dataset, batch_tiles=8, num_timesteps=None, samples=1, r
         out["rank"] = ex_rank.finish()
     if measure:
         out["disagreement"] = ex.disagreement
-    return out, plan
+    return _apply_consistency(out, dataset, cons), plan

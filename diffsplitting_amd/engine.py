@@ -851,3 +851,73 @@ def sample_quantiles(stack, q, target=None):
     # the stack goes in by address (it may be a view); out or rank names the device and the stream of the call
     check(lib.dsx_sample_quantiles(address, stride, n, count, qs if len(qs) else None, len(qs), out, target, rank, None))
     return out, rank
+
+
+# ---------------------------------------------------------------------------
+# data consistency of a split: residual, report rows, projection (dsx_consistency, include/dsx.h)
+# ---------------------------------------------------------------------------
+PIX_OF_DTYPE = {torch.uint8: _lib.PIX_U8, torch.float32: _lib.PIX_F32}
+PIX_OF_DTYPE.update({d: _lib.PIX_U16 for d in _lib.DEV_DTYPES["uint16_t"]})
+PIX_BYTES = {_lib.PIX_U8: 1, _lib.PIX_U16: 2, _lib.PIX_F32: 4}
+CONSISTENCY_SLOTS = 10
+
+
+def consistency(acquisition, mean, scale, shift, weights, std=None, clip=-1.0, noise_var=0.0, want_row=True,
+                want_map=False, want_mean=False, want_std=False, out_mean=None, out_std=None, pix=None):
+    """``dsx_consistency``: ``acquisition`` holds the (frames, ...) pixels of ``mean``'s leading dimensions on the device
+    as the file holds them: a uint8, uint16 (or int16 storage) or float32 tensor of that shape, or, with ``pix``
+    (``_lib.PIX_*``) given, the same bytes under any dtype (``InputStackTiledPred`` keeps a uint16 stack as bytes);
+    ``mean`` and ``std`` (frames, ..., C) float32, channel-last, normalised; ``scale``, ``shift``, ``weights``: C host
+    numbers each (std_target, mean_target, w); ``clip`` < 0: none; ``noise_var`` = rho^2.  Returns
+    ``(rows, map, mean', std')``: the (frames, 10) float64 report rows, the residual map (frames, ...), and the
+    conditioned canvases; each None unless wanted.  ``out_mean`` / ``out_std`` name the tensors the conditioned
+    canvases go to (``mean`` / ``std`` themselves: in place; no other overlap is allowed).  Everything stays on the
+    device; two launches, nothing synchronised."""
+    if not torch.is_tensor(acquisition) or not acquisition.is_cuda or not acquisition.is_contiguous():
+        raise DsxError("consistency: the acquisition must be a contiguous CUDA tensor")
+    if pix is None:
+        if acquisition.dtype not in PIX_OF_DTYPE:
+            raise DsxError(f"consistency: an acquisition of {acquisition.dtype}; uint8, uint16 or float32 pixels")
+        pix = PIX_OF_DTYPE[acquisition.dtype]
+    if pix not in PIX_BYTES:
+        raise DsxError(f"consistency: pix = {pix!r}, must be PIX_U8, PIX_U16 or PIX_F32")
+    mean = _f32_cuda(mean, "consistency: mean")
+    if mean.dim() < 2 or mean.numel() < 1:
+        raise DsxError(f"consistency: mean of shape {tuple(mean.shape)}, expected (frames, ..., C)")
+    frames = int(mean.shape[0])
+    plane = mean[0].numel() // int(mean.shape[-1])
+    if acquisition.numel() * acquisition.element_size() != frames * plane * PIX_BYTES[pix]:
+        raise DsxError(f"consistency: mean of shape {tuple(mean.shape)} for an acquisition of "
+                       f"{acquisition.numel() * acquisition.element_size()} bytes; expected {frames} x {plane} pixels of "
+                       f"{PIX_BYTES[pix]} bytes")
+    nch = int(mean.shape[-1])
+    if std is not None:
+        std = _f32_cuda(std, "consistency: std", mean.shape)
+    host = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (scale, shift, weights)]
+    for v, name in zip(host, ("scale", "shift", "weights")):
+        if v.size != nch:
+            raise DsxError(f"consistency: {v.size} values of {name} for {nch} prediction channels")
+    if (want_std or out_std is not None) and std is None:
+        raise DsxError("consistency: a conditioned spread needs std")
+    tensors = [acquisition, mean] + ([std] if std is not None else [])
+    _lib.common_device("consistency", [t.device for t in tensors])
+    _lib.require_gpu()
+    dev = mean.device
+    rows = part = fmap = None
+    if want_row:
+        blocks = check(lib.dsx_consistency_blocks(plane))
+        part = torch.empty((frames, blocks, CONSISTENCY_SLOTS), dtype=torch.float64, device=dev)
+        rows = torch.empty((frames, CONSISTENCY_SLOTS), dtype=torch.float64, device=dev)
+    if want_map:
+        fmap = torch.empty(mean.shape[:-1], dtype=torch.float32, device=dev)
+    if out_mean is not None:
+        out_mean = _f32_cuda(out_mean, "consistency: out_mean", mean.shape)
+    elif want_mean:
+        out_mean = torch.empty_like(mean)
+    if out_std is not None:
+        out_std = _f32_cuda(out_std, "consistency: out_std", mean.shape)
+    elif want_std:
+        out_std = torch.empty_like(mean)
+    check(lib.dsx_consistency(acquisition, pix, mean, std, frames, plane, nch, host[0], host[1],
+                              host[2], float(clip), float(noise_var), fmap, out_mean, out_std, rows, part, None))
+    return rows, fmap, out_mean, out_std

@@ -81,6 +81,18 @@ pairwise difference over every overlap and over the band of B pixels (default 8)
 per-pixel spread, in normalised units and in raw counts; ``--seam-map`` writes the per-pixel spread among the tiles in raw
 counts, laid out as ``--std-out``.  It measures the per-tile means of the ``--samples``, or with ``--fuse-steps`` /
 ``--frame-steps`` the x0 tiles of the last row (``--seam-map`` then needs ``--samples 1``).
+
+``--consistency-report FILE.json [--consistency-map FILE.npy|.tif] [--project] [--consistency-noise RHO]
+[--channel-weights W0,W1]`` (all need ``--input``) ask whether the split adds back up to the acquisition
+(``core/consistency.py``): the residual ``r = x - sum_c w_c p_c`` in raw counts, with the weights of the norm file's
+``channel_weights`` (else ones).  Rank 0 logs rms, bias, relative residual and saturated share, with ``--samples N >= 2``
+also the ``chi2`` of the spread, and writes them per frame and in total to FILE; ``--consistency-map`` writes r (N,H,W),
+laid out as ``--seam-map``.  ``--project`` conditions the posterior on the observation (noise ``RHO`` counts): ``--out``
+and ``--std-out`` then hold the conditioned mean and spread; with ``--samples 1`` the projection is orthogonal
+(``--std-out`` stays refused).  Order: the spread is first recalibrated by ``--apply-calibration`` where given, THEN it
+weights the projection and the ``chi2``; ``--std-out`` writes the conditioned, recalibrated spread.  The report always
+describes the prediction before the projection.  Quantile maps are not projected: ``--project`` with ``--quantile-out`` is
+refused.
 """
 import argparse
 import functools
@@ -315,8 +327,21 @@ def main(argv=None):
                          "--std-out")
     ap.add_argument("--seam-band", type=int, default=None,
                     help="with --seam-report: half-width in pixels of the band around the crop lines (default 8)")
+    ap.add_argument("--consistency-report", type=str, default=None,
+                    help="with --input: how far the split is from adding back up to the acquisition "
+                         "(core.consistency: rms, bias, relative residual, chi2 of the spread) to this .json file")
+    ap.add_argument("--consistency-map", type=str, default=None,
+                    help="with --input: write the residual x - sum_c w_c p_c (N,H,W) in raw counts (.npy / .tif)")
+    ap.add_argument("--project", action="store_true",
+                    help="with --input: condition mean and spread on the acquisition; --out / --std-out hold the result")
+    ap.add_argument("--consistency-noise", type=float, default=None,
+                    help="with --consistency-report / --project: the noise rho of the observation in raw counts (default 0)")
+    ap.add_argument("--channel-weights", type=str, default=None,
+                    help="with --consistency-report / --project: W0,W1 of x = W0 ch0 + W1 ch1 (default: the norm file's "
+                         "channel_weights, else ones)")
     args = ap.parse_args(argv)
     config = _config_once(args.config)
+    _check_consistency_args(args, config)
     _check_seam_args(args, config)
     _check_msssim_args(args, config)
     _check_calibration_args(args, config)
@@ -452,6 +477,8 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
                      netG.num_timesteps)
         elif rank == 0:
             log.info("sr3 / ddpm without --solver: the full ancestral loop, %d steps per batch of tiles", n_steps)
+    cons = _consistency_wanted(args)
+    want_std = bool(args.std_out or args.calibration or (cons and samples > 1))
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     # every rank holds the frames: the ground truth needs no tiles and no collective; the metric is accumulated while
@@ -459,12 +486,12 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
     if args.frame_steps:
         from .data.tiled_predict import predict_stack_frames
         out, plan = predict_stack_frames(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps,
-                                         samples=samples, return_std=bool(args.std_out or args.calibration),
+                                         samples=samples, return_std=want_std,
                                          seed=args.sample_seed, window=args.window or "triangle", **_quantile_kwargs(args),
                                          **_seam_kwargs(args))
     else:
         out, plan = predict_stack(netG, val_set, batch_tiles=args.batch_tiles, num_timesteps=n_steps, samples=samples,
-                                  return_std=bool(args.std_out or args.calibration), seed=args.sample_seed, solver=solver,
+                                  return_std=want_std, seed=args.sample_seed, solver=solver,
                                   noise="field" if args.noise_field else "samples", stitch=args.stitch,
                                   window=args.window or "triangle", fuse=args.fuse_steps, **_quantile_kwargs(args),
                                   **_seam_kwargs(args))
@@ -483,15 +510,18 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
                          ps[:, c].std().item() if ps.shape[0] > 1 else 0.0)
         _log_msssim(args, val_set, pred, ps, log)
         _log_calibration(args, val_set, pred, out.get("std"), ps, samples, log)
+        spread = out.get("std")
+        if args.apply_calibration:
+            from .core.calibration import Calibration
+            spread = Calibration.load(args.apply_calibration).apply(spread)
+            log.info("spread recalibrated by %s", args.apply_calibration)
+        if cons:
+            # the recalibrated spread, where there is one, weights the projection and the chi2
+            pred, spread = _run_consistency(args, val_set, pred, spread if samples > 1 else None, log)
         if args.out:
             _write_prediction(args.out, pred, val_set)
             log.info("prediction written to %s", args.out)
         if args.std_out:
-            spread = out["std"]
-            if args.apply_calibration:
-                from .core.calibration import Calibration
-                spread = Calibration.load(args.apply_calibration).apply(spread)
-                log.info("spread recalibrated by %s", args.apply_calibration)
             _write_prediction(args.std_out, spread, val_set, spread=True)
             log.info("spread over %d samples written to %s", samples, args.std_out)
         if args.quantile_out:
@@ -500,6 +530,108 @@ def _predict(args, netG, val_set, n_steps, patch, rank, world, dev, log):
         _log_rank_histogram(args, out.get("rank"), samples, log)
         _write_seam_report(args, out.get("disagreement"), val_set, plan, patch, samples, log)
     return pred
+
+
+# ---- --consistency-report / --project: does the split add back up to the acquisition ------------------------------
+def _consistency_wanted(args):
+    return bool(args.consistency_report or args.consistency_map or args.project)
+
+
+def _parse_weights(text):
+    try:
+        w = [float(v) for v in text.split(",")]
+    except ValueError:
+        raise SystemExit(f"--channel-weights {text}: W0,W1, two numbers")
+    return w
+
+
+def _check_consistency_args(args, config):
+    """``--consistency-report`` / ``--consistency-map`` / ``--project`` / ``--consistency-noise`` / ``--channel-weights``,
+    checked on the command line, the config and the norm file alone (nothing touches the GPU, no rank is started).
+    Without them: nothing."""
+    given = [flag for flag, value in (("--consistency-report", args.consistency_report),
+                                      ("--consistency-map", args.consistency_map), ("--project", args.project),
+                                      ("--consistency-noise", args.consistency_noise is not None),
+                                      ("--channel-weights", args.channel_weights)) if value]
+    if not given:
+        return
+    if not args.input:
+        other = next((f for f, v in (("--datapath", args.datapath), ("--frames", args.frames)) if v), "synthetic frames")
+        raise SystemExit(f"{given[0]}: only with --input FILE; the check compares a split with the acquisition it was "
+                         f"made from, and {other} are two ground-truth channels, not an acquisition")
+    if not _consistency_wanted(args):
+        raise SystemExit(f"{given[0]}: only with --consistency-report, --consistency-map or --project")
+    if args.consistency_report and not args.consistency_report.endswith(".json"):
+        raise SystemExit(f"--consistency-report {args.consistency_report}: a .json file")
+    if args.consistency_map and not args.consistency_map.endswith((".npy", ".tif", ".tiff")):
+        raise SystemExit(f"--consistency-map {args.consistency_map}: a .npy or .tif file")
+    rho = args.consistency_noise
+    if rho is not None and not (np.isfinite(rho) and rho >= 0):
+        raise SystemExit(f"--consistency-noise {rho}: rho in raw counts, finite and not negative")
+    if args.project and args.quantile_out:
+        raise SystemExit("--project with --quantile-out: quantile maps are not projected; write them in a run of their own")
+    idx = config()[1].get("target_channel_idx")
+    if idx is not None:
+        raise SystemExit(f"{given[0]}: the config predicts one channel (target_channel_idx = {idx}); the sum "
+                         "sum_c w_c p_c needs every summand")
+    if args.channel_weights is not None:
+        w = _parse_weights(args.channel_weights)
+        if len(w) != 2:
+            raise SystemExit(f"--channel-weights {args.channel_weights}: {len(w)} weights, the split has two channels: W0,W1")
+        if not np.isfinite(w).all() or not any(w):
+            raise SystemExit(f"--channel-weights {args.channel_weights}: finite, and not both zero")
+
+
+def _consistency_weights(args):
+    """--channel-weights, else the norm file's channel_weights, else None (ones)."""
+    if args.channel_weights is not None:
+        return _parse_weights(args.channel_weights)
+    from .data.normalization import load_normalization
+    return load_normalization(args.norm)[1].get("channel_weights")
+
+
+def _run_consistency(args, val_set, pred, spread, log):
+    """Rank 0, on the stitched canvases: report, map and, with ``--project``, the conditioned (mean, spread)."""
+    import json
+    from .core.consistency import consistency, json_report
+    stack, pix, _, clip = val_set.acquisition()
+    rep = consistency(pred, stack, val_set.get_normalization_dict(), weights=_consistency_weights(args), std=spread,
+                      clip=clip, noise=args.consistency_noise or 0.0, project=args.project,
+                      want_map=bool(args.consistency_map), pix=pix)
+    tot = rep["total"]
+    n_all = tot["pixels"] + tot["saturated"]
+    fmt = lambda v: "n/a" if v is None else "%.6g" % v
+    log.info("weights %s: residual x - sum w p: rms %s, bias %s counts, relative %s, saturated %.4f %% of %d pixels",
+             rep["weights"], fmt(tot["rms"]), fmt(tot["bias"]), fmt(tot["relative"]), 100.0 * tot["saturated"] / n_all, n_all)
+    if spread is not None:
+        log.info("weights %s: chi2 %s over %d pixels (near 1: the spread of the sum is honest; well above: over-confident, "
+                 "or the channels' errors are correlated; well below: the opposite)", rep["weights"], fmt(tot["chi2"]),
+                 tot["chi2_pixels"])
+    if args.consistency_report:
+        doc = json_report(rep)
+        doc["projected"] = bool(args.project)
+        doc["spread"] = None if spread is None else ("recalibrated" if args.apply_calibration else "samples")
+        with open(args.consistency_report, "w") as f:
+            json.dump(doc, f, indent=1)
+        log.info("consistency report written to %s", args.consistency_report)
+    if args.consistency_map:
+        _write_frames(args.consistency_map, rep["map"].cpu().numpy())
+        log.info("residual map written to %s", args.consistency_map)
+    if args.project:
+        log.info("--out%s: conditioned on the acquisition (%s)", " / --std-out" if spread is not None else "",
+                 "orthogonal projection" if spread is None and not args.consistency_noise else "Gaussian posterior")
+        return rep["mean"], rep.get("std", spread)
+    return pred, spread
+
+
+def _write_frames(path, frames):
+    """(N,H,W) float32 frames in raw counts as .npy or as a .tif of N pages."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32)
+    if str(path).endswith(".npy"):
+        np.save(path, frames)
+    else:
+        from .data.tiff import imwrite
+        imwrite(path, frames)
 
 
 # ---- --seam-report: how far the predicted tiles disagree where they overlap ---------------------------------------

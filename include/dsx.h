@@ -1030,6 +1030,63 @@ int dsx_calibration(const float* mean_dev, const float* std_dev, const float* ta
 int dsx_sample_quantiles(const float* x_dev, int64_t sample_stride, int n, int64_t count, const double* q_host, int nq,
                          float* out_dev, const float* target_dev, float* rank_dev, void* stream);
 
+/* ------------------------------------------------- data consistency of a split: residual, report row, projection
+ * The network's input is, by construction, x = sum_c w_c p_c in raw counts, so a split of an acquisition must add back
+ * up to it.  One pass over `frames` frames of `plane` = H W pixels forms the residual r = x - sum_c w_c p_c of a
+ * prediction, a report row per frame, and the prediction conditioned on the observation: an independent Gaussian
+ * posterior N(p_c, v_c) conditioned on sum_c w_c t_c = x with noise variance noise_var.
+ *   input_dev     (frames, plane) of `pix` = DSX_PIX_U8 / DSX_PIX_U16 / DSX_PIX_F32, the acquisition in its file width
+ *   mean_dev      (frames, plane, C) fp32, channel-last, normalised, as predict_stack returns it; C in 1..4
+ *   std_dev       the same shape, or NULL
+ *   scale_host[C] = a_c (std_target), shift_host[C] = b_c (mean_target), weight_host[C] = w_c
+ *   clip < 0: none;  noise_var = rho^2 >= 0
+ * Outputs, each may be NULL (not all): map_dev (frames, plane) fp32; out_mean_dev, out_std_dev (frames, plane, C) fp32,
+ * normalised; out_dev [frames][10] doubles, which needs partial_dev of frames * dsx_consistency_blocks(plane) * 10
+ * doubles.  Per pixel, in double, every operation rounded on its own (no fma), channels in ascending order:
+ *   x   = (double)input
+ *   sat = clip >= 0 && x >= clip
+ *   p_c = (double)mean[c] * a_c + b_c
+ *   m   = sum_c w_c * p_c                              ((0 + w_0 p_0) + w_1 p_1) + ..
+ *   r   = x - m
+ *   map = (float)r                                     written for every pixel, saturated ones too
+ *   v_c = std ? ((double)std[c] * a_c)^2 : 1.0
+ *   den = sum_c (w_c * w_c) * v_c + noise_var          the sum over c first, then + noise_var
+ *   if (!sat && den > 0):
+ *     p'_c        = p_c + ((v_c * w_c) * r) / den
+ *     out_mean[c] = (float)((p'_c - b_c) / a_c)
+ *     v'_c        = v_c - ((v_c * w_c) * (v_c * w_c)) / den
+ *     out_std[c]  = (float)(sqrt(max(v'_c, 0)) / a_c)
+ *   else:
+ *     out_mean[c] = mean[c]                            the input's fp32 bits, copied
+ *     out_std[c]  = std ? std[c] : 0                   copied likewise
+ * A saturated pixel only says sum_c w_c p_c >= clip, so it is left alone and counted.  With std == NULL and
+ * noise_var == 0 the update is the orthogonal projection onto the constraint.  The row of a frame, over its pixels:
+ *   0  count of unsaturated pixels k          1  count of saturated pixels              (exact)
+ *   2  sum r      3  sum r * r      4  sum x      5  sum x * x                          over the unsaturated pixels
+ *   6  count of unsaturated pixels with den > 0      7  sum (r * r) / den over those
+ *   8  min r      9  max r                    over the unsaturated pixels (+inf, -inf if none)
+ * The contract: map, out_mean and out_std equal a float64 numpy restatement bit for bit (tests/consistency_ref.py);
+ * counts, min and max are exact; the sums of non-negative terms lie within (k + 4) 2^-53 of the exactly rounded sum of
+ * the same terms, relative to it, and sum r within that factor times sum |r|.  A frame is cut into
+ * dsx_consistency_blocks(plane) workgroups, a function of plane alone, each thread takes fixed pixels in a fixed order,
+ * the rows meet by dsx_reduce.h (kDown, Pairwise) and the workgroup rows in ascending order; there is no atomic.  So a
+ * call's bits do not depend on the load path (four pixels per thread with 16-byte accesses of the fp32 operands and one
+ * 4-, 8- or 16-byte load of the input when every base is that aligned and plane % 4 == 0; single accesses otherwise), on
+ * alignment, on a frame's position in the call or on the number of frames.  Inputs are assumed finite.
+ * Aliasing: the outputs may alias nothing but themselves, with one exception, in place: out_mean_dev == mean_dev and
+ * out_std_dev == std_dev exactly (a thread reads its pixels before it writes them).  Any other overlap of an output
+ * with an input or with another output is refused.
+ * Two launches on `stream` (one when out_dev is NULL); the call does not synchronise, allocate or copy.
+ * DSX_ERR_INVALID with a message, before any device work: a NULL input_dev, mean_dev or host array, out_dev without
+ * partial_dev, frames outside 1..65535, plane < 1, C outside 1..4, an unknown pix (DSX_PIX_U32 included), an a_c that
+ * is not > 0, a scalar that is not finite, noise_var < 0, every w_c == 0, out_std_dev without std_dev, no output at all,
+ * an overlap as above. */
+int dsx_consistency_blocks(int64_t plane);
+int dsx_consistency(const void* input_dev, int pix, const float* mean_dev, const float* std_dev, int64_t frames,
+                    int64_t plane, int C, const double* scale_host, const double* shift_host, const double* weight_host,
+                    double clip, double noise_var, float* map_dev, float* out_mean_dev, float* out_std_dev,
+                    double* out_dev, double* partial_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
